@@ -22,8 +22,8 @@ closed-form minimiser of the same QP (``oracle/closed_form_mp.py``).
 Nodal values come from ``oracle.lssvr_oracle.fem_p1_solve_golden_v1`` -- a FROZEN copy of the P1
 stand-in as it was when the committed fixtures were written -- so that a regeneration
 reproduces their inputs bit for bit (``--verify`` checks that, and reruns the reference on
-the stored inputs; tests/test_oracle_golden.py does the same on every CPU run in the build
-container).
+the stored inputs; tests/test_oracle_golden.py does the same on every CPU run with the oracle's
+step-for-step restatement of ``lssvr_primal``, so that it needs nothing outside the repository).
 
 Usage:  python oracle/gen_golden.py [--only G1,G2,...] | --verify
 """

@@ -11,7 +11,7 @@ mkdir -p $O
 run() { name=$1; shift; rocprofv3 "$@" > $O/$name.log 2>&1; echo "$name rc=$?"; }
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"
 SQ2="SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE"
-run stats   --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline
+run stats   --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
 run fetch   --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 scripts/prof_step.py 100008,9,16 5 wide 12500000
 run write   --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- python3 scripts/prof_step.py 100008,9,16 5 wide 12500000
 run sq_s    --pmc $SQ --kernel-trace --output-format csv -d $O/sq_s -- python3 scripts/prof_step.py 100008,9,16 5 wide

@@ -119,7 +119,7 @@ def test_bench_self_launches_its_ranks(dev):
     gloo on the one GPU of this box: RCCL refuses two ranks on one device), run BASELINE config
     3's strong-scaling mode (here on a smaller total) and report the stitched rate with both
     all-gather algorithms."""
-    out = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--elements", "200008"],
+    out = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--elements", "200008", "--full"],
                      {"LSSVR_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["ranks_in_process_group"] == 2
     assert out["scaling"] == "strong" and out["config"]["elements_total"] == 200008
@@ -148,7 +148,7 @@ def test_bench_self_launches_its_ranks(dev):
 def test_bench_single_rank_line(dev):
     """The N = 1 line the driver records: metric / config of BASELINE config 2, roofline and
     cpu_baseline objects, event-timed value consistent with the host clock."""
-    out = _run_bench(["--steps", "50", "--warmup", "5"], {})
+    out = _run_bench(["--steps", "50", "--warmup", "5", "--full"], {})
     assert out["n_gpus"] == 1 and out["config"]["elements_total"] == 100008
     assert out["dtype"] == "f64" and out["unit"] == "elements/s" and out["vs_baseline"] is None
     rf = out["roofline"]
@@ -173,3 +173,35 @@ def test_bench_single_rank_line(dev):
         assert c["cpu_baseline"]["kind"] == "port" and c["cpu_baseline"]["value"] > 0
         assert c["accuracy"]["rel_l2_vs_60_digit_minimiser"] < 1e-13 and c["config"]["fallback_elements"] == 0
     assert out["config4"]["config"]["elements_total"] == 100008 and out["config5"]["config"]["elements_total"] == 1000008
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(dev, tmp_path):
+    """A plain run (no --full) times EXACTLY K steps once and prints the headline line without the secondary
+    objects; --dump-outputs writes what the last timed step computed: W, status words and the P1 bands of
+    BASELINE config 2's mesh, in float64, the sampled rows right against the float64 KKT oracle."""
+    import numpy as np
+    from oracle import lssvr_oracle as orc
+    out = _run_bench(["--gpus", "1", "--steps", "30", "--warmup", "3", "--dump-outputs", str(tmp_path)], {})
+    assert out["metric"].startswith("LSSVR-enhanced elements/sec") and out["unit"] == "elements/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["steps"] == 30
+    assert out["timed_brackets"] == 1 and out["ms_per_step"] > 0
+    ne = out["config"]["elements_total"]
+    assert ne == 100008 and abs(out["value"] - ne / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    assert out["roofline"]["bound"] == "fp64-valu" and abs(out["roofline"]["kernel_us_avg"] - out["ms_per_step"] * 1e3) < 1e-6
+    for key in ("cpu_baseline", "accuracy", "config4", "config5", "narrow_domain", "stages", "eager_loop", "graph_replay"):
+        assert key not in out, key
+    W = np.load(tmp_path / "W.npy")
+    st = np.load(tmp_path / "status.npy")
+    assert W.dtype == np.float64 and W.shape == (ne, 9) and st.shape == (ne,) and not st.any()
+    assert np.load(tmp_path / "diag.npy").shape == (ne + 1,) and np.load(tmp_path / "off.npy").shape == (ne,)
+    assert not (tmp_path / "W_rows.npy").exists()                 # 7 MB: under the 64 MB cap, written whole
+    half = ne / 24.0
+    nodes = np.arange(ne + 1, dtype=np.float64) * ((2.0 * half) / ne) - half
+    nodes[-1] = half
+    values = np.sin(np.pi * nodes)
+    values[0] = values[-1] = 0.0
+    for i in (0, ne // 2, ne - 1):
+        s = orc.element_system(nodes[i], nodes[i + 1],
+                               *orc.boundary_values(i, ne, nodes[i], nodes[i + 1], values[i], values[i + 1],
+                                                    (-half, half)), 9, 1e4, 16)
+        assert orc.rel_l2_coef(W[i:i + 1], orc.solve_primal_kkt(s)[None, :]).max() < 1e-12

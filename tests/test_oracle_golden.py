@@ -3,8 +3,6 @@
 
 The reference ships no tests or fixtures of its own; these vectors
 hold, per element, the reference's SLSQP output and the 60-digit minimiser of the same QP."""
-import os
-
 import numpy as np
 import pytest
 
@@ -148,10 +146,9 @@ def test_batched_oracle_equals_loop():
 
 
 # --------------------------------------------------------------------------------------------
-# recipe <-> data: the committed fixtures regenerate, and the reference reproduces them
+# recipe <-> data: the committed fixtures regenerate, and the reference's loop reproduces them
 # --------------------------------------------------------------------------------------------
 ALL_FIXTURES = [c[0] for c in CASES]
-REF_FILE = "/root/reference/1D-Possion/Hybrid-FEM-LSSVR-Dual.py"
 
 
 @pytest.mark.parametrize("name", [c for c in ALL_FIXTURES if "10000008" not in c] + ["G7_eval_default"])
@@ -170,32 +167,48 @@ def test_golden_inputs_regenerate_bit_for_bit(golden, name):
     assert np.array_equal(v[e], g["values_sel"][:, 0]) and np.array_equal(v[e + 1], g["values_sel"][:, 1])
 
 
-@pytest.fixture(scope="module")
-def reference_module():
-    if not os.path.exists(REF_FILE):
-        pytest.skip("the reference lives in the build container only (it never travels to the GPU box)")
-    from oracle import gen_golden
-    return gen_golden, gen_golden.load_reference()
+def _rerun_on_stored_inputs(g, limit=None):
+    """``lssvr_primal`` (Dual.py:20-98) as ``orc.slsqp_element`` restates it step for step, on a fixture's
+    STORED inputs, numpy's global RNG seeded per element exactly as ``oracle/gen_golden.py`` seeded it
+    (``1234 + i``): the start vector, the constraint rows and the SLSQP call are the reference's own."""
+    lo, hi, ne = float(g["lo"]), float(g["hi"]), int(g["ne"])
+    M, n, gamma = int(g["M"]), int(g["n"]), float(g["gamma"])
+    out = []
+    for k, i in enumerate(g["elements"][:limit]):
+        np.random.seed(1234 + int(i) % 100000)
+        c, _ = orc.slsqp_element(orc.poisson_rhs, g["nodes_sel"][k, 0], g["nodes_sel"][k, 1],
+                                 g["values_sel"][k, 0], g["values_sel"][k, 1], M, gamma, n,
+                                 left=(int(i) == 0), right=(int(i) == ne - 1), global_domain=(lo, hi))
+        out.append(c)
+    return np.array(out)
 
 
 @pytest.mark.parametrize("name", ALL_FIXTURES)
-def test_reference_rerun_on_stored_inputs_is_bit_equal(golden, reference_module, name):
-    """The reference itself (``lssvr_primal``, Dual.py:20-98, imported from /root/reference), run on
-    the inputs each fixture stores with the seeds the generator used, returns ``coef_ref`` bit for
-    bit: the fixtures are reference output, and the committed recipe reproduces the committed data.
-    (Degree 32 costs 7 s per element in the reference: one of G5's three elements here, all of
-    them in ``gen_golden.py --verify``.)"""
-    gg, mod = reference_module
+def test_reference_rerun_on_stored_inputs_is_bit_equal(golden, name):
+    """The reference's element solve, restated in the oracle and run on the inputs each fixture stores with
+    the seeds the generator used, returns ``coef_ref`` -- the reference's own output -- bit for bit: the
+    restatement IS the reference on these inputs, and the committed recipe reproduces the committed data.
+    (Degree 32 costs 7 s per element: one of G5's three elements here.  ``oracle/gen_golden.py --verify``
+    reruns the reference itself on every element where its source is at hand.)"""
     g = golden(name)
     limit = 1 if int(g["M"]) > 20 else None
-    got = gg.rerun_on_stored_inputs(mod, g, limit=limit)
-    assert np.array_equal(got, g["coef_ref"][:len(got)])
+    got = _rerun_on_stored_inputs(g, limit=limit)
+    assert len(got) >= 1 and np.array_equal(got, g["coef_ref"][:len(got)])
 
 
-def test_reference_rerun_eval_case_is_bit_equal(golden, reference_module):
-    gg, mod = reference_module
+def test_reference_rerun_eval_case_is_bit_equal(golden):
+    """G7: the reference's loop over all 24 elements (``solve_lssvr_subproblems``, Dual.py:139-169: one
+    global seed, 777, for the whole loop) through the restatement, then ``evaluate_solution``: the stored
+    coefficients and the stored u(x) -- NaN at the NaN probe included -- bit for bit."""
     g = golden("G7_eval_default")
-    W, u = gg.rerun_eval_case(mod, g)
+    nodes, values = g["nodes"], g["values"]
+    ne = len(nodes) - 1
+    np.random.seed(777)
+    W = np.array([orc.slsqp_element(orc.poisson_rhs, nodes[i], nodes[i + 1], values[i], values[i + 1],
+                                    int(g["M"]), float(g["gamma"]), int(g["n"]), left=(i == 0),
+                                    right=(i == ne - 1), global_domain=(float(nodes[0]), float(nodes[-1])))[0]
+                  for i in range(ne)])
+    u, _ = orc.evaluate_solution(nodes, W, g["xq"])
     assert np.array_equal(W, g["W"]) and np.array_equal(u, g["u_ref"], equal_nan=True)
 
 
