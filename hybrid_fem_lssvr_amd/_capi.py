@@ -16,7 +16,7 @@ IN_TREE_LIB = os.path.join(_HERE, "csrc", "liblssvr_hip.so")
 # test suite and the benchmark always exercise the one in-tree library.
 LIB_PATH = os.environ.get("LSSVR_HIP_LIB") or IN_TREE_LIB
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 RHS_ARRAY = 0
 RHS_SIN = 1
@@ -123,6 +123,13 @@ SIGNATURES = {
                                       _c_dbl, _c_dbl, _c_dp, _c_dp]),
     "lssvr_eval": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_i64, _c_dp, _c_dp, _c_dp]),
     "lssvr_eval_error": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_i64, C.POINTER(_c_dbl), _c_dp, _c_dp]),
+    "lssvr_eval_deriv": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_i64, _c_dp, _c_dp, _c_dp]),
+    "lssvr_gauss_rule": (_c_int, [_c_int, C.POINTER(_c_dbl), C.POINTER(_c_dbl)]),
+    "lssvr_estimate_points": (_c_int, [_c_dp, _c_i64, _c_int, _c_dp, _c_dp]),
+    "lssvr_adapt_work_bytes": (_c_i64, [_c_i64]),
+    "lssvr_estimate": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_int, C.POINTER(_c_dbl), _c_dp,
+                                _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "lssvr_refine": (_c_int, [_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "lssvr_fp64_probe": (_c_int, [_c_dp, _c_int, _c_int, _c_int, _c_dp]),
     "lssvr_stream_probe": (_c_int, [_c_dp, _c_dp, _c_i64, _c_dp]),
     "lssvr_row_chunk_probe": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp]),

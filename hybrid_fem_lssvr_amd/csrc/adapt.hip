@@ -1,0 +1,494 @@
+// A posteriori error indicator and h-refinement of the enhanced solution (no reference
+// counterpart: Hybrid-FEM-LSSVR-Dual.py computes its per-element slack and discards it).
+//   - derivatives of the enhanced solution at query points (lssvr_eval_deriv)
+//   - per-element residual indicator  eta_e^2 = h_e^2 ||f + u_e''||_e^2 + h_e/2 (J_e^2 + J_{e+1}^2)
+//     with J_i = u_{i-1}'(x_i) - u_i'(x_i) (lssvr_estimate) and its deterministic reduction
+//   - threshold marking + bisection into a new ascending node array (lssvr_refine)
+// DESIGN.md section 11 has the derivation, the mapping and the measured numbers.
+#include <cmath>
+
+#include "lssvr_device.hpp"
+#include "lssvr_kernels.hpp"
+#include "lssvr_eval.hpp"
+
+namespace lssvr {
+
+// ---------------------------------------------------------------------------
+// Gauss-Legendre on [-1, 1] (host): Newton on P_nq from the Tricomi-type initial guess, in
+// long double, mirrored so that the rule is exactly symmetric.  Ascending nodes.
+// ---------------------------------------------------------------------------
+bool gauss_rule(int nq, double* xi, double* wt) {
+  if (nq < 1 || nq > kAdaptMaxNq) return false;
+  const long double pi = 3.141592653589793238462643383279502884L;
+  for (int i = 0; i < (nq + 1) / 2; ++i) {
+    long double z = std::cos(pi * ((long double)i + 0.75L) / ((long double)nq + 0.5L));  // descending
+    long double dp = 1.0L;
+    for (int it = 0; it < 100; ++it) {
+      long double p0 = 1.0L, p1 = z;
+      for (int k = 1; k < nq; ++k) {
+        const long double p2 = ((2 * k + 1) * z * p1 - k * p0) / (k + 1);
+        p0 = p1;
+        p1 = p2;
+      }
+      dp = nq * (z * p1 - p0) / (z * z - 1.0L);
+      const long double dz = p1 / dp;
+      z -= dz;
+      if (std::fabs(dz) < 1e-19L) break;
+    }
+    {   // derivative at the converged root, for the weight
+      long double p0 = 1.0L, p1 = z;
+      for (int k = 1; k < nq; ++k) {
+        const long double p2 = ((2 * k + 1) * z * p1 - k * p0) / (k + 1);
+        p0 = p1;
+        p1 = p2;
+      }
+      dp = nq * (z * p1 - p0) / (z * z - 1.0L);
+    }
+    if (2 * i + 1 == nq) z = 0.0L;
+    const long double w = 2.0L / ((1.0L - z * z) * dp * dp);
+    xi[nq - 1 - i] = (double)z;
+    xi[i] = -(double)z;
+    wt[i] = wt[nq - 1 - i] = (double)w;
+  }
+  return true;
+}
+
+namespace {
+
+// sum_k c_k P_k^(ORDER)(t), ORDER = 1 or 2, by the forward recurrences
+//   P_{k+1} = ((2k+1) t P_k - k P_{k-1}) / (k+1),  P'_{k+1} = P'_{k-1} + (2k+1) P_k,
+//   P''_{k+1} = P''_{k-1} + (2k+1) P'_k
+template <int ORDER>
+__device__ __forceinline__ double legendre_deriv_sum(const double* __restrict__ c, int M, double t) {
+  if (M <= ORDER) return 0.0;
+  double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
+  double acc = ORDER == 1 ? c[1] : 0.0;
+#pragma unroll 1
+  for (int k = 1; k + 1 < M; ++k) {
+    const double a = (double)(2 * k + 1);
+    const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
+    const double d2 = d0 + a * p1;
+    const double s2 = s0 + a * d1;
+    acc = fma(c[k + 1], ORDER == 1 ? d2 : s2, acc);
+    p0 = p1; p1 = p2;
+    d0 = d1; d1 = d2;
+    s0 = s1; s1 = s2;
+  }
+  return acc;
+}
+
+template <int ORDER>
+__global__ __launch_bounds__(kBlock) void eval_deriv_kernel(const double* __restrict__ x,
+                                                             const double* __restrict__ W, int64_t ne,
+                                                             int M, const double* __restrict__ xq,
+                                                             int64_t P, double* __restrict__ out,
+                                                             int64_t* __restrict__ elem) {
+  const double x0 = x[0];
+  const double inv_h = (double)ne / (x[ne] - x0);
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < P;
+       i += (int64_t)gridDim.x * kBlock) {
+    const double xi = xq[i];
+    int64_t j = -1;
+    double v = 0.0;
+    if (xi == xi) {      // NaN: elem -1, value 0 (lssvr_eval's rule)
+      j = locate(x, ne, xi, x0, inv_h);
+      const DomainMap dm = map_params(x[j], x[j + 1]);
+      const double t = dm.off + dm.scl * xi;
+      const double s = legendre_deriv_sum<ORDER>(W + j * M, M, t);
+      v = ORDER == 1 ? s * dm.scl : s * (dm.scl * dm.scl);
+    }
+    out[i] = v;
+    if (elem) elem[i] = j;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// estimator
+// ---------------------------------------------------------------------------
+constexpr int kEstBlock = 128;          // elements per workgroup chunk (two waves)
+constexpr int kEstMaxBlocks = 4096;     // grid cap: partials of the reduction in `work`
+
+int64_t est_blocks(int64_t ne) {
+  const int64_t b = (ne + kEstBlock - 1) / kEstBlock;
+  return b < 1 ? 1 : (b < kEstMaxBlocks ? b : kEstMaxBlocks);
+}
+int64_t ref_blocks(int64_t ne) {
+  const int64_t b = (ne + kBlock - 1) / kBlock;
+  return b < 1 ? 1 : b;
+}
+
+__device__ __forceinline__ double est_point(double a, double b, double xi) {
+  const double mid = 0.5 * (a + b);
+  const double half = 0.5 * (b - a);
+  return mid + half * xi;
+}
+
+// u_e'(x_e) and u_e'(x_{e+1}) from P_k'(+-1) = (+-1)^(k+1) k(k+1)/2
+template <int MT>
+__device__ __forceinline__ void end_derivs(const double (&c)[MT], double scl, double& dl, double& dr) {
+  double sl = 0.0, sr = 0.0;
+#pragma unroll
+  for (int k = 1; k < MT; ++k) {
+    const double w = (double)(k * (k + 1) / 2);
+    sr = fma(c[k], w, sr);
+    sl = fma(c[k], (k & 1) ? w : -w, sl);
+  }
+  dl = sl * scl;
+  dr = sr * scl;
+}
+
+template <int MT>
+__device__ __forceinline__ void load_row_global(const double* __restrict__ W, int64_t e, int M,
+                                                double (&c)[MT]) {
+#pragma unroll
+  for (int k = 0; k < MT; ++k) c[k] = k < M ? W[e * M + k] : 0.0;
+}
+
+// RHS: 0 = LSSVR_RHS_ARRAY (rhs[e*nq + q]), 1 = LSSVR_RHS_SIN, 2 = LSSVR_RHS_ARRAY_PM (rhs[q*ne + e])
+// Dynamic LDS: T[nq*MT] (P_k''(xi_q)) | xi[nq] | wt[nq] | rows[kEstBlock*ms] | dl[kEstBlock] | dr[kEstBlock] |
+// red[3*kEstBlock].  The rule is copied to LDS: indexed by a loop counter in the kernel arguments it would
+// be held in 2*nq*2 VGPRs.
+template <int MT, int RHS>
+__global__ __launch_bounds__(kEstBlock) void estimate_kernel(EstimateArgs p, GaussRuleN g) {
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x;
+  const int nq = p.nq, M = p.M, ms = p.ms;
+  const int64_t ne = p.ne;
+  double* T = lds;
+  double* sxi = T + nq * MT;
+  double* swt = sxi + nq;
+  double* rows = swt + nq;
+  double* sdl = rows + kEstBlock * ms;
+  double* sdr = sdl + kEstBlock;
+  double* red = sdr + kEstBlock;
+  if (tid < nq) {
+    const double t = g.xi[tid];
+    sxi[tid] = t;
+    swt[tid] = g.wt[tid];
+    double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
+    T[tid * MT + 0] = 0.0;
+    if (MT > 1) T[tid * MT + 1] = 0.0;
+    for (int k = 1; k + 1 < MT; ++k) {
+      const double a = (double)(2 * k + 1);
+      const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
+      const double d2 = d0 + a * p1;
+      const double s2 = s0 + a * d1;
+      T[tid * MT + k + 1] = k + 1 < M ? s2 : 0.0;
+      p0 = p1; p1 = p2;
+      d0 = d1; d1 = d2;
+      s0 = s1; s1 = s2;
+    }
+  }
+  // column stepping of the staging copy: i += kEstBlock  ->  (row, col) += (qM, rM)
+  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
+  double bsum = 0.0, bmax = 0.0, bcnt = 0.0;
+  for (int64_t c0 = (int64_t)blockIdx.x * kEstBlock; c0 < ne; c0 += (int64_t)gridDim.x * kEstBlock) {
+    const int nrow = (int)(ne - c0 < kEstBlock ? ne - c0 : kEstBlock);
+    // stage the chunk's contiguous nrow*M doubles of W (coalesced), rows padded to an odd stride
+    {
+      const double* src = p.W + c0 * M;
+      const int total = nrow * M;
+      int r = tid / M, col = tid - (tid / M) * M;
+      for (int i = tid; i < total; i += kEstBlock) {
+        rows[r * ms + col] = src[i];
+        r += qM;
+        col += rM;
+        if (col >= M) {
+          col -= M;
+          ++r;
+        }
+      }
+    }
+    __syncthreads();
+    const int64_t e = c0 + tid;
+    const bool valid = tid < nrow;
+    double c[MT];
+#pragma unroll
+    for (int k = 0; k < MT; ++k) c[k] = (valid && k < M) ? rows[tid * ms + k] : 0.0;
+    double a = 0.0, b = 1.0;
+    if (valid) {
+      a = p.x[e];
+      b = p.x[e + 1];
+    }
+    const DomainMap dm = map_params(a, b);
+    double dl, dr;
+    end_derivs<MT>(c, dm.scl, dl, dr);
+    sdl[tid] = dl;
+    sdr[tid] = dr;
+    __syncthreads();
+    if (valid) {
+      // neighbours' end derivatives: from the staged chunk, recomputed from HBM at chunk edges
+      double dr_prev = 0.0, dl_next = 0.0;
+      if (e > 0) {
+        if (tid > 0) {
+          dr_prev = sdr[tid - 1];
+        } else {
+          double cn[MT];
+          load_row_global<MT>(p.W, e - 1, M, cn);
+          const DomainMap dn = map_params(p.x[e - 1], a);
+          double l, r;
+          end_derivs<MT>(cn, dn.scl, l, r);
+          dr_prev = r;
+        }
+      }
+      if (e + 1 < ne) {
+        if (tid + 1 < nrow) {
+          dl_next = sdl[tid + 1];
+        } else {
+          double cn[MT];
+          load_row_global<MT>(p.W, e + 1, M, cn);
+          const DomainMap dn = map_params(b, p.x[e + 2]);
+          double l, r;
+          end_derivs<MT>(cn, dn.scl, l, r);
+          dl_next = l;
+        }
+      }
+      const double jl = e > 0 ? dr_prev - dl : 0.0;
+      const double jr = e + 1 < ne ? dr - dl_next : 0.0;
+      // interior residual f + u'' at the nq Gauss points
+      const double scl2 = dm.scl * dm.scl;
+      double acc = 0.0;
+#pragma unroll 1
+      for (int q = 0; q < nq; ++q) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 2; k < MT; ++k) s = fma(c[k], T[q * MT + k], s);
+        double f;
+        if constexpr (RHS == 1) f = p.rhs_amp * sin_reduced(p.rhs_omega * est_point(a, b, sxi[q]));
+        else if constexpr (RHS == 2) f = p.rhs_values[(int64_t)q * ne + e];
+        else f = p.rhs_values[e * nq + q];
+        const double r = f + s * scl2;
+        acc = fma(swt[q], r * r, acc);
+      }
+      const double h = dm.oldlen;
+      const double half = 0.5 * h;
+      const double eta2 = (h * h) * (half * acc) + half * (jl * jl + jr * jr);
+      p.eta2[e] = eta2;
+      if (p.jump) {
+        p.jump[e] = jl;
+        if (e + 1 == ne) p.jump[ne] = 0.0;
+      }
+      if (fabs(eta2) < INFINITY) {
+        bsum += eta2;
+        bmax = fmax(bmax, eta2);
+      } else {
+        bcnt += 1.0;
+      }
+    }
+    __syncthreads();      // rows / sdl / sdr are rewritten by the next chunk
+  }
+  red[tid] = bsum;
+  red[kEstBlock + tid] = bmax;
+  red[2 * kEstBlock + tid] = bcnt;
+  __syncthreads();
+  for (int off = kEstBlock / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+      red[tid] += red[tid + off];
+      red[kEstBlock + tid] = fmax(red[kEstBlock + tid], red[kEstBlock + tid + off]);
+      red[2 * kEstBlock + tid] += red[2 * kEstBlock + tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    p.work[3 * blockIdx.x + 0] = red[0];
+    p.work[3 * blockIdx.x + 1] = red[kEstBlock];
+    p.work[3 * blockIdx.x + 2] = red[2 * kEstBlock];
+  }
+}
+
+// one workgroup: the per-block partials in a fixed order -> out3 (bitwise reproducible)
+__global__ __launch_bounds__(kBlock) void estimate_finish_kernel(const double* __restrict__ part, int nb,
+                                                                  double* __restrict__ out3) {
+  __shared__ double sh[3][kBlock];
+  const int tid = threadIdx.x;
+  double s = 0.0, m = 0.0, c = 0.0;
+  for (int i = tid; i < nb; i += kBlock) {
+    s += part[3 * i];
+    m = fmax(m, part[3 * i + 1]);
+    c += part[3 * i + 2];
+  }
+  sh[0][tid] = s;
+  sh[1][tid] = m;
+  sh[2][tid] = c;
+  __syncthreads();
+  for (int off = kBlock / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+      sh[0][tid] += sh[0][tid + off];
+      sh[1][tid] = fmax(sh[1][tid], sh[1][tid + off]);
+      sh[2][tid] += sh[2][tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    out3[0] = sh[0][0];
+    out3[1] = sh[1][0];
+    out3[2] = sh[2][0];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void estimate_points_kernel(const double* __restrict__ x, int64_t ne,
+                                                                  int nq, GaussRuleN g,
+                                                                  double* __restrict__ xq) {
+  const int64_t total = ne * nq;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * kBlock) {
+    const int64_t e = i / nq;
+    const int q = (int)(i - e * nq);
+    xq[i] = est_point(x[e], x[e + 1], g.xi[q]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// marking + bisection: count per block, one-block scan, scatter
+// ---------------------------------------------------------------------------
+// element e is marked iff (eta2[e] is non-finite, or max > 0 and eta2[e] >= theta^2 * max) and it is
+// at least 2 h_min long; mx = the device max of the finite eta2 (out3[1] of lssvr_estimate)
+__device__ __forceinline__ bool marked(const double* __restrict__ x, const double* __restrict__ eta2,
+                                       int64_t e, double mx, double theta2, double h2min) {
+  const double v = eta2[e];
+  const bool big = !(fabs(v) < INFINITY) || (mx > 0.0 && v >= theta2 * mx);
+  return big && (x[e + 1] - x[e] >= h2min);
+}
+
+__global__ __launch_bounds__(kBlock) void refine_count_kernel(const double* __restrict__ x, int64_t ne,
+                                                               const double* __restrict__ eta2,
+                                                               const double* __restrict__ mx,
+                                                               double theta2, double h2min,
+                                                               int64_t* __restrict__ cnt) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const double m_max = mx[0];
+  const bool m = e < ne && marked(x, eta2, e, m_max, theta2, h2min);
+  const int n = __syncthreads_count(m);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = n;
+}
+
+// exclusive offsets of the nb block counts, in place: every thread sums a contiguous run of counts,
+// one workgroup scan of the 256 run sums, then every thread writes its run's offsets
+__global__ __launch_bounds__(kBlock) void refine_scan_kernel(int64_t* __restrict__ cnt, int64_t nb, int64_t ne,
+                                                              int64_t* __restrict__ ne_new) {
+  __shared__ int64_t sh[kBlock];
+  const int tid = threadIdx.x;
+  const int64_t per = (nb + kBlock - 1) / kBlock;
+  const int64_t lo = tid * per < nb ? tid * per : nb;
+  const int64_t hi = lo + per < nb ? lo + per : nb;
+  int64_t s = 0;
+  for (int64_t i = lo; i < hi; ++i) s += cnt[i];
+  sh[tid] = s;
+  __syncthreads();
+  for (int off = 1; off < kBlock; off <<= 1) {
+    const int64_t add = tid >= off ? sh[tid - off] : 0;
+    __syncthreads();
+    sh[tid] += add;
+    __syncthreads();
+  }
+  int64_t run = sh[tid] - s;
+  for (int64_t i = lo; i < hi; ++i) {
+    const int64_t v = cnt[i];
+    cnt[i] = run;
+    run += v;
+  }
+  if (tid == kBlock - 1) *ne_new = ne + sh[kBlock - 1];
+}
+
+__global__ __launch_bounds__(kBlock) void refine_scatter_kernel(const double* __restrict__ x, int64_t ne,
+                                                                 const double* __restrict__ eta2,
+                                                                 const double* __restrict__ mx,
+                                                                 double theta2, double h2min,
+                                                                 const int64_t* __restrict__ offs,
+                                                                 double* __restrict__ x_new,
+                                                                 int64_t* __restrict__ parent) {
+  __shared__ int wsum[kBlock / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t e = (int64_t)blockIdx.x * kBlock + tid;
+  const double m_max = mx[0];
+  const bool m = e < ne && marked(x, eta2, e, m_max, theta2, h2min);
+  const unsigned long long bal = __ballot(m);
+  const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+  if (lane == 0) wsum[wv] = __popcll(bal);
+  __syncthreads();
+  int before = below;
+  for (int w = 0; w < wv; ++w) before += wsum[w];
+  if (e < ne) {
+    const int64_t pos = e + offs[blockIdx.x] + before;
+    const double a = x[e], b = x[e + 1];
+    x_new[pos] = a;
+    if (parent) parent[pos] = e;
+    if (m) {
+      x_new[pos + 1] = 0.5 * (a + b);
+      if (parent) parent[pos + 1] = e;
+    }
+    if (e + 1 == ne) x_new[pos + 1 + (m ? 1 : 0)] = b;
+  }
+}
+
+}  // namespace
+
+int64_t adapt_work_bytes(int64_t ne) {
+  const int64_t a = 3 * est_blocks(ne), b = ref_blocks(ne);
+  return 8 * (a > b ? a : b);
+}
+
+hipError_t eval_deriv(const double* x, const double* W, int64_t ne, int M, int order, const double* xq,
+                      int64_t P, double* out, int64_t* elem, hipStream_t s) {
+  if (order == 0) return eval_points(x, W, ne, M, xq, P, out, elem, s);   // the same kernel: bit-equal
+  if (P == 0) return hipSuccess;
+  const unsigned blocks = (unsigned)((P + kBlock - 1) / kBlock < 16384 ? (P + kBlock - 1) / kBlock : 16384);
+  if (order == 1)
+    hipLaunchKernelGGL(eval_deriv_kernel<1>, dim3(blocks), dim3(kBlock), 0, s, x, W, ne, M, xq, P, out, elem);
+  else
+    hipLaunchKernelGGL(eval_deriv_kernel<2>, dim3(blocks), dim3(kBlock), 0, s, x, W, ne, M, xq, P, out, elem);
+  return hipGetLastError();
+}
+
+hipError_t estimate_points(const double* x, int64_t ne, int nq, double* xq, hipStream_t s) {
+  GaussRuleN g{};
+  if (!gauss_rule(nq, g.xi, g.wt)) return hipErrorInvalidValue;
+  if (ne == 0) return hipSuccess;
+  const int64_t total = ne * nq;
+  const unsigned blocks = (unsigned)((total + kBlock - 1) / kBlock < 8192 ? (total + kBlock - 1) / kBlock : 8192);
+  hipLaunchKernelGGL(estimate_points_kernel, dim3(blocks), dim3(kBlock), 0, s, x, ne, nq, g, xq);
+  return hipGetLastError();
+}
+
+template <int MT>
+static hipError_t launch_estimate(const EstimateArgs& a, const GaussRuleN& g, int rhs, unsigned nb, size_t lds,
+                                  hipStream_t s) {
+  if (rhs == 1)
+    hipLaunchKernelGGL((estimate_kernel<MT, 1>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
+  else if (rhs == 2)
+    hipLaunchKernelGGL((estimate_kernel<MT, 2>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
+  else
+    hipLaunchKernelGGL((estimate_kernel<MT, 0>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s) {
+  GaussRuleN g{};
+  if (!gauss_rule(a.nq, g.xi, g.wt)) return hipErrorInvalidValue;
+  a.ms = a.M | 1;                                   // odd row stride: conflict-free ds_read_b64
+  const int64_t nb = est_blocks(a.ne);
+  const int MT = a.M <= 12 ? 12 : (a.M <= 22 ? 22 : 33);
+  const size_t lds = sizeof(double) * ((size_t)a.nq * (MT + 2) + (size_t)kEstBlock * a.ms + 5 * kEstBlock);
+  hipError_t err;
+  if (MT == 12) err = launch_estimate<12>(a, g, rhs_mode, (unsigned)nb, lds, s);
+  else if (MT == 22) err = launch_estimate<22>(a, g, rhs_mode, (unsigned)nb, lds, s);
+  else err = launch_estimate<33>(a, g, rhs_mode, (unsigned)nb, lds, s);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
+  return hipGetLastError();
+}
+
+hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
+                  double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s) {
+  const int64_t nb = ref_blocks(ne);
+  int64_t* cnt = static_cast<int64_t*>(work);
+  const double theta2 = theta * theta, h2min = 2.0 * h_min;
+  hipLaunchKernelGGL(refine_count_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, x, ne, eta2, eta2_max, theta2,
+                     h2min, cnt);
+  hipLaunchKernelGGL(refine_scan_kernel, dim3(1), dim3(kBlock), 0, s, cnt, nb, ne, ne_new);
+  hipLaunchKernelGGL(refine_scatter_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, x, ne, eta2, eta2_max, theta2,
+                     h2min, cnt, x_new, parent);
+  return hipGetLastError();
+}
+
+}  // namespace lssvr

@@ -726,6 +726,84 @@ int lssvr_eval_error(const double* x, const double* W, int64_t ne, int M, const 
                       "eval_error");
 }
 
+int lssvr_eval_deriv(const double* x, const double* W, int64_t ne, int M, int order, const double* xq,
+                     int64_t P, double* out, int64_t* elem, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (P < 0) return fail(LSSVR_ERR_SIZE, "P < 0");
+  if (M < 1) return fail(LSSVR_ERR_DEGREE, "M = %d < 1", M);
+  if (order < 0 || order > 2) return fail(LSSVR_ERR_DEGREE, "order = %d outside {0, 1, 2}", order);
+  if (!x || !W || (P > 0 && (!xq || !out))) return fail(LSSVR_ERR_NULL, "x, W, xq, out must be non-NULL");
+  return check_launch(lssvr::eval_deriv(x, W, ne, M, order, xq, P, out, elem,
+                                        reinterpret_cast<hipStream_t>(stream)),
+                      "eval_deriv");
+}
+
+int lssvr_gauss_rule(int nq, double* xi_host, double* wt_host) {
+  if (nq < 1 || nq > lssvr::kAdaptMaxNq)
+    return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
+  if (!xi_host || !wt_host) return fail(LSSVR_ERR_NULL, "xi and wt must be non-NULL");
+  lssvr::gauss_rule(nq, xi_host, wt_host);
+  return LSSVR_OK;
+}
+
+int lssvr_estimate_points(const double* x, int64_t ne, int nq, double* xq, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (nq < 1 || nq > lssvr::kAdaptMaxNq)
+    return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
+  if (!x || !xq) return fail(LSSVR_ERR_NULL, "x and xq must be non-NULL");
+  return check_launch(lssvr::estimate_points(x, ne, nq, xq, reinterpret_cast<hipStream_t>(stream)),
+                      "estimate_points");
+}
+
+int64_t lssvr_adapt_work_bytes(int64_t ne) { return lssvr::adapt_work_bytes(ne); }
+
+int lssvr_estimate(const double* x, const double* W, int64_t ne, int M, int nq, int rhs_id,
+                   const double* rhs_params_host, const double* rhs_values, double* eta2, double* jump,
+                   double* out3, void* work, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
+  if (nq < 1 || nq > lssvr::kAdaptMaxNq)
+    return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
+  if (!x || !W || !eta2 || !out3 || !work) return fail(LSSVR_ERR_NULL, "x, W, eta2, out3, work must be non-NULL");
+  lssvr::EstimateArgs a{};
+  a.x = x;
+  a.W = W;
+  a.ne = ne;
+  a.M = M;
+  a.nq = nq;
+  a.eta2 = eta2;
+  a.jump = jump;
+  a.work = static_cast<double*>(work);
+  int mode;
+  if (rhs_id == LSSVR_RHS_SIN) {
+    if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
+    a.rhs_amp = rhs_params_host[0];
+    a.rhs_omega = rhs_params_host[1];
+    mode = 1;
+  } else if (rhs_id == LSSVR_RHS_ARRAY || rhs_id == LSSVR_RHS_ARRAY_PM) {
+    if (!rhs_values) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_ARRAY needs rhs_values[ne*nq]");
+    a.rhs_values = rhs_values;
+    mode = rhs_id == LSSVR_RHS_ARRAY ? 0 : 2;
+  } else {
+    return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
+  }
+  return check_launch(lssvr::estimate(a, mode, out3, reinterpret_cast<hipStream_t>(stream)), "estimate");
+}
+
+int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev, double theta,
+                 double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new_dev, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (!(theta >= 0.0 && theta <= 1.0)) return fail(LSSVR_ERR_SIZE, "theta = %g outside [0, 1]", theta);
+  if (!(h_min >= 0.0) || !(h_min < INFINITY)) return fail(LSSVR_ERR_SIZE, "h_min = %g must be finite and >= 0", h_min);
+  if (!x || !eta2 || !eta2_max_dev || !work || !x_new || !ne_new_dev)
+    return fail(LSSVR_ERR_NULL, "x, eta2, eta2_max, work, x_new, ne_new must be non-NULL");
+  return check_launch(lssvr::refine(x, ne, eta2, eta2_max_dev, theta, h_min, work, x_new, parent, ne_new_dev,
+                                    reinterpret_cast<hipStream_t>(stream)),
+                      "refine");
+}
+
 int lssvr_stream_probe(const double* src, double* dst, int64_t n, void* stream) {
   if (!src || !dst) return fail(LSSVR_ERR_NULL, "src and dst must be non-NULL");
   if (n < 1) return fail(LSSVR_ERR_SIZE, "n must be >= 1");

@@ -166,6 +166,34 @@ hipError_t flux_finish(const double* kloc, const double* load, int64_t ne, bool 
 hipError_t eval_error(const double* x, const double* W, int64_t ne, int M, const double* xq,
                       int64_t P, double amp, double omega, double* out, hipStream_t s);
 
+// a posteriori estimator and h-refinement (adapt.hip)
+constexpr int kAdaptMaxNq = 32;     // Gauss points per element of lssvr_estimate
+constexpr int kAdaptMaxM = 33;
+struct GaussRuleN {                 // Gauss-Legendre on [-1, 1], by value in the kernel arguments
+  double xi[kAdaptMaxNq];
+  double wt[kAdaptMaxNq];
+};
+struct EstimateArgs {
+  const double* x;
+  const double* W;
+  int64_t ne;
+  int M, nq, ms;                    // ms: LDS row stride of the staged W rows (set by estimate())
+  double rhs_amp, rhs_omega;
+  const double* rhs_values;
+  double* eta2;
+  double* jump;
+  double* work;
+};
+bool gauss_rule(int nq, double* xi, double* wt);       // host; false: nq outside [1, kAdaptMaxNq]
+int64_t adapt_work_bytes(int64_t ne);
+hipError_t eval_deriv(const double* x, const double* W, int64_t ne, int M, int order, const double* xq,
+                      int64_t P, double* out, int64_t* elem, hipStream_t s);
+hipError_t estimate_points(const double* x, int64_t ne, int nq, double* xq, hipStream_t s);
+// rhs_mode: 0 = table element-major, 1 = amp*sin(omega x) in-kernel, 2 = table point-major
+hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s);
+hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
+                  double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s);
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

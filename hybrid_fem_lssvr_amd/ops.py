@@ -7,6 +7,7 @@ raises otherwise -- there is no CPU path.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import threading
 
@@ -732,9 +733,10 @@ def p1_flux_finish(kloc, load, work, *, first_global, last_global, prefix=None, 
     return out
 
 
-def evaluate(x, W, xq, *, want_elem=True, out=None, stream=None):
+def evaluate(x, W, xq, *, want_elem=True, out=None, stream=None, deriv=0):
     """``evaluate_solution`` (Dual.py:176-203) -> (u float64[P], elem int64[P] | None).
-    ``out``: optional preallocated float64[P] for u."""
+    ``out``: optional preallocated float64[P] for u.  ``deriv`` = 1 or 2: the first / second
+    x-derivative of the enhanced solution instead (``lssvr_eval_deriv``; same element rule)."""
     lib = _capi.load()
     _dev(x, "x")
     _dev(W, "W")
@@ -742,6 +744,8 @@ def evaluate(x, W, xq, *, want_elem=True, out=None, stream=None):
     ne = x.numel() - 1
     if W.dim() != 2 or W.shape[0] != ne:
         raise ValueError("W must be [ne, M]")
+    if deriv not in (0, 1, 2):
+        raise ValueError(f"deriv must be 0, 1 or 2, got {deriv!r}")
     M = W.shape[1]
     P = xq.numel()
     if out is None:
@@ -751,9 +755,14 @@ def evaluate(x, W, xq, *, want_elem=True, out=None, stream=None):
         if uq.numel() != P or not uq.is_contiguous():
             raise ValueError("out must be a contiguous float64[P] tensor")
     elem = torch.empty(P, dtype=torch.int64, device=x.device) if want_elem else None
-    rc = lib.lssvr_eval(_ptr(x), _ptr(W), ne, int(M), _ptr(xq), P, _ptr(uq), _ptr(elem),
-                        _stream(stream))
-    _capi.check(rc, "lssvr_eval")
+    if deriv == 0:
+        rc = lib.lssvr_eval(_ptr(x), _ptr(W), ne, int(M), _ptr(xq), P, _ptr(uq), _ptr(elem),
+                            _stream(stream))
+        _capi.check(rc, "lssvr_eval")
+    else:
+        rc = lib.lssvr_eval_deriv(_ptr(x), _ptr(W), ne, int(M), int(deriv), _ptr(xq), P, _ptr(uq),
+                                  _ptr(elem), _stream(stream))
+        _capi.check(rc, "lssvr_eval_deriv")
     return uq, elem
 
 
@@ -776,6 +785,99 @@ def eval_error(x, W, xq, *, exact=(1.0, math.pi), out=None, stream=None):
                               _capi.rhs_params(*exact), _ptr(out), _stream(stream))
     _capi.check(rc, "lssvr_eval_error")
     return out
+
+
+def gauss_rule(nq):
+    """Gauss-Legendre nodes (ascending) and weights on [-1, 1] (host; ``lssvr_gauss_rule``)."""
+    import numpy as np
+    lib = _capi.load()
+    xi = (ctypes.c_double * max(int(nq), 1))()
+    wt = (ctypes.c_double * max(int(nq), 1))()
+    _capi.check(lib.lssvr_gauss_rule(int(nq), xi, wt), "lssvr_gauss_rule")
+    return np.array(xi[:nq], dtype=np.float64), np.array(wt[:nq], dtype=np.float64)
+
+
+def adapt_work(x, ne):
+    """Device scratch of ``lssvr_adapt_work_bytes(ne)`` bytes for :func:`estimate` / :func:`refine`."""
+    nbytes = _capi.load().lssvr_adapt_work_bytes(int(ne))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+
+
+def _check_work(work, x, ne):
+    if work is None:
+        return adapt_work(x, ne)
+    _dev(work, "work")
+    if work.numel() * 8 < _capi.load().lssvr_adapt_work_bytes(int(ne)):
+        raise ValueError("work is smaller than lssvr_adapt_work_bytes(ne)")
+    return work
+
+
+def estimate_points(x, nq, *, stream=None):
+    """The estimator's abscissae float64[ne, nq] (tabulate a callable f on it for :func:`estimate`)."""
+    lib = _capi.load()
+    _dev(x, "x")
+    ne = x.numel() - 1
+    xq = torch.empty((ne, int(nq)), dtype=torch.float64, device=x.device)
+    _capi.check(lib.lssvr_estimate_points(_ptr(x), ne, int(nq), _ptr(xq), _stream(stream)),
+                "lssvr_estimate_points")
+    return xq
+
+
+def estimate(x, W, nq, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_values=None, point_major=False,
+             want_jump=False, work=None, stream=None):
+    """Per-element residual indicator of the enhanced solution (``lssvr_estimate``):
+    eta2[e] = h^2 int_e (f + u_e'')^2 + h/2 (J_e^2 + J_{e+1}^2).  ``rhs`` = (amp, omega) evaluates
+    f in-kernel; ``rhs_values`` float64[ne, nq] (f at :func:`estimate_points`) or, with
+    ``point_major``, float64[nq, ne] overrides it.  Returns (eta2 float64[ne], jump float64[ne+1] |
+    None, out3 device float64[3] = {sum, max of the finite eta2, non-finite count})."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(W, "W")
+    ne = x.numel() - 1
+    if W.dim() != 2 or W.shape[0] != ne:
+        raise ValueError("W must be [ne, M]")
+    if rhs_values is not None:
+        _dev(rhs_values, "rhs_values")
+        if rhs_values.numel() != ne * int(nq):
+            raise ValueError(f"rhs_values must hold ne*nq = {ne * int(nq)} doubles")
+        rhs_id, params = (RHS_ARRAY_PM if point_major else RHS_ARRAY), None
+    else:
+        rhs_id, params = RHS_SIN, _capi.rhs_params(*rhs)
+    eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
+    jump = torch.empty(ne + 1, dtype=torch.float64, device=x.device) if want_jump else None
+    out3 = torch.empty(3, dtype=torch.float64, device=x.device)
+    work = _check_work(work, x, ne)
+    rc = lib.lssvr_estimate(_ptr(x), _ptr(W), ne, int(W.shape[1]), int(nq), rhs_id, params,
+                            _ptr(rhs_values), _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work),
+                            _stream(stream))
+    _capi.check(rc, "lssvr_estimate")
+    return eta2, jump, out3
+
+
+def refine(x, eta2, eta2_max, theta, *, h_min=0.0, want_parent=False, work=None, stream=None):
+    """Mark (eta2 non-finite, or eta2 >= theta^2 * max with max > 0; element >= 2 h_min long) and
+    bisect (``lssvr_refine``).  ``eta2_max``: device float64 holding max (e.g. ``out3[1:2]`` of
+    :func:`estimate`).  Returns (x_new float64[ne_new+1], parent int64[ne_new] | None), trimmed to
+    the new length -- one synchronisation, for the count."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(eta2, "eta2")
+    _dev(eta2_max, "eta2_max")
+    ne = x.numel() - 1
+    if eta2.numel() != ne:
+        raise ValueError("eta2 must hold ne doubles")
+    theta = float(theta)
+    if not 0.0 <= theta <= 1.0:
+        raise ValueError(f"theta must be in [0, 1], got {theta}")
+    x_new = torch.empty(2 * ne + 1, dtype=torch.float64, device=x.device)
+    parent = torch.empty(2 * ne, dtype=torch.int64, device=x.device) if want_parent else None
+    ne_new = torch.empty(1, dtype=torch.int64, device=x.device)
+    work = _check_work(work, x, ne)
+    rc = lib.lssvr_refine(_ptr(x), ne, _ptr(eta2), _ptr(eta2_max), theta, float(h_min), _ptr(work),
+                          _ptr(x_new), _ptr(parent), _ptr(ne_new), _stream(stream))
+    _capi.check(rc, "lssvr_refine")
+    n = int(ne_new.item())
+    return x_new[:n + 1], (parent[:n] if parent is not None else None)
 
 
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):

@@ -144,10 +144,11 @@ class EnhancedSolution:
     def n_fallback(self):
         return int((self.status != 0).sum().item())
 
-    def evaluate(self, x_points, return_elements=False):
-        """``evaluate_solution`` (Dual.py:176-203) on the device."""
+    def evaluate(self, x_points, return_elements=False, deriv=0):
+        """``evaluate_solution`` (Dual.py:176-203) on the device; ``deriv`` = 1 / 2: the first /
+        second x-derivative of the enhanced solution instead (same element rule)."""
         xq = _to_dev(np.asarray(x_points, dtype=np.float64).reshape(-1), self.W.device)
-        u, elem = ops.evaluate(self.nodes, self.W, xq, want_elem=True)
+        u, elem = ops.evaluate(self.nodes, self.W, xq, want_elem=True, deriv=deriv)
         u = u.cpu().numpy()
         if return_elements:
             return u, elem.cpu().numpy()
@@ -307,6 +308,7 @@ class FEMLSSVRPrimalSolver:
             raise ValueError("fem_solver must be 'bands' or 'flux'")
         self.fem_solver = fem_solver
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
+        self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
         self._x_dev = None
         self._u_dev = None
 
@@ -396,3 +398,81 @@ class FEMLSSVRPrimalSolver:
         """Element each query point is evaluated in (Dual.py:182-201 rule)."""
         _, elem = self.enhanced.evaluate(np.asarray(x_points).reshape(-1), return_elements=True)
         return elem
+
+    # ---- a posteriori error indicator and h-refinement (no reference counterpart) ------------
+    def _estimate_dev(self, nq):
+        """(eta2 device[ne], out3 device[3]) of the current enhanced solution."""
+        if self.enhanced is None:
+            raise RuntimeError("call solve() first")
+        x, W = self.enhanced.nodes, self.enhanced.W
+        if isinstance(self.rhs, SinRHS):
+            kw = dict(rhs=(self.rhs.amp, self.rhs.omega))
+        else:
+            xq = ops.estimate_points(x, nq)
+            f = np.asarray(self.rhs(xq.cpu().numpy()), dtype=np.float64)
+            if f.shape != tuple(xq.shape):
+                f = np.array(np.broadcast_to(f, tuple(xq.shape)))
+            kw = dict(rhs_values=_to_dev(f, x.device))
+        eta2, _, out3 = ops.estimate(x, W, nq, **kw)
+        return eta2, out3
+
+    def _nq(self, nq):
+        nq = max(int(self.lssvr_M), 8) if nq is None else int(nq)
+        if not 1 <= nq <= 32:
+            raise ValueError(f"nq must be in [1, 32], got {nq}")
+        return nq
+
+    def estimate(self, nq=None):
+        """Per-element error indicator of the enhanced solution after ``solve()``, as numpy:
+        eta_e^2 = h_e^2 int_e (f + u_e'')^2 dx + h_e/2 (J_e^2 + J_{e+1}^2), J = jump of u' at the
+        nodes (0 at the Dirichlet ends), ``nq``-point Gauss (default max(lssvr_M, 8)).  For -u'' = f."""
+        nq = self._nq(nq)
+        eta2, _ = self._estimate_dev(nq)
+        return eta2.cpu().numpy()
+
+    def solve_adaptive(self, tol=None, theta=0.5, max_elements=100000, max_iter=50, h_min=0.0, nq=None):
+        """Solve, estimate, mark, bisect -- repeated.  Each round runs ``solve()`` on the current mesh
+        and the indicator of :meth:`estimate`; it stops when sqrt(sum eta^2) <= ``tol``, after
+        ``max_iter`` rounds, when nothing is marked, or when the refinement would take the mesh above
+        ``max_elements`` (the final mesh never exceeds it); otherwise every element with
+        eta_e >= ``theta`` * max eta (and at least 2 ``h_min`` long) is bisected and ``self.mesh``
+        becomes the new nodes.  Afterwards ``fem_nodes``, ``fem_values``, ``lssvr_functions`` and
+        ``enhanced`` describe the final mesh as after ``solve()``; ``adapt_history`` holds one
+        dict(ne, estimate, marked) per round (marked = elements bisected after that round).
+        Returns the final sqrt(sum eta^2)."""
+        theta = float(theta)
+        if not 0.0 <= theta <= 1.0:
+            raise ValueError(f"theta must be in [0, 1], got {theta}")
+        if isinstance(max_elements, bool) or int(max_elements) != max_elements or max_elements < 1:
+            raise ValueError(f"max_elements must be a positive integer, got {max_elements!r}")
+        if int(max_iter) != max_iter or max_iter < 1:
+            raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
+        if tol is not None and not float(tol) >= 0.0:
+            raise ValueError(f"tol must be >= 0, got {tol!r}")
+        if not float(h_min) >= 0.0:
+            raise ValueError(f"h_min must be >= 0, got {h_min!r}")
+        nq = self._nq(nq)
+        if self.mesh is None:
+            self.mesh = LineMesh.from_nodes(
+                np.linspace(self.global_domain[0], self.global_domain[1], self.num_fem_nodes))
+        if self.mesh.nelements > max_elements:
+            raise ValueError(f"the initial mesh has {self.mesh.nelements} elements > max_elements = {max_elements}")
+        self.adapt_history = []
+        est = float("nan")
+        for it in range(int(max_iter)):
+            self.solve()
+            eta2, out3 = self._estimate_dev(nq)
+            s = out3.cpu().numpy()
+            ne = int(eta2.numel())
+            est = float(np.sqrt(s[0])) if s[2] == 0 else float("inf")
+            rec = dict(ne=ne, estimate=est, marked=0)
+            self.adapt_history.append(rec)
+            if (tol is not None and est <= float(tol)) or it + 1 == int(max_iter):
+                break
+            x_new, _ = ops.refine(self.enhanced.nodes, eta2, out3[1:2], theta, h_min=float(h_min))
+            ne_new = x_new.numel() - 1
+            if ne_new == ne or ne_new > max_elements:
+                break
+            rec["marked"] = ne_new - ne
+            self.mesh = LineMesh.from_nodes(x_new.cpu().numpy())
+        return est

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LSSVR_ABI_VERSION 5
+#define LSSVR_ABI_VERSION 6
 
 /* error codes */
 #define LSSVR_OK              0
@@ -410,6 +410,66 @@ int lssvr_eval(const double* x, const double* W, int64_t ne, int M,
 int lssvr_eval_error(const double* x, const double* W, int64_t ne, int M,
                      const double* xq, int64_t P, const double* exact_params_host,
                      double* out3, void* stream);
+
+/*
+ * A posteriori error indicator and h-refinement (ABI 6; no reference counterpart: Dual.py has no
+ * error measure that does not need the exact solution).  For -u'' = f only.
+ *
+ * lssvr_eval_deriv -- d^order u_h / dx^order at the query points, order in {0, 1, 2}, with
+ * lssvr_eval's element rule (interior node -> left element, outside -> extrapolation, NaN -> elem -1
+ * and value 0).  order 0 IS lssvr_eval (bit-equal); orders 1, 2 take the chain-rule factor scl^order,
+ * scl = 2/(x[j+1]-x[j]) as lssvr_eval's mapdomain computes it.  Any M >= 1.
+ */
+int lssvr_eval_deriv(const double* x, const double* W, int64_t ne, int M, int order,
+                     const double* xq, int64_t P, double* out, int64_t* elem, void* stream);
+
+/*
+ * lssvr_gauss_rule -- HOST: the nq-point Gauss-Legendre rule on [-1, 1] (1 <= nq <= 32), nodes
+ * ascending, by Newton iteration on P_nq (matches numpy.polynomial.legendre.leggauss to 1e-15).
+ */
+int lssvr_gauss_rule(int nq, double* xi_host, double* wt_host);
+
+/*
+ * lssvr_estimate_points -- the estimator's abscissae, element-major:
+ *   xq[e*nq + q] = 0.5*(x[e]+x[e+1]) + 0.5*(x[e+1]-x[e]) * xi_q      (xi of lssvr_gauss_rule)
+ * so that the host can tabulate a callable f for LSSVR_RHS_ARRAY (or, transposed, _ARRAY_PM).
+ */
+int lssvr_estimate_points(const double* x, int64_t ne, int nq, double* xq, void* stream);
+
+/*
+ * lssvr_estimate -- per-element residual indicator of the enhanced solution u_e (row e of W):
+ *   eta2[e] = h_e^2 * int_e (f + u_e'')^2 dx + h_e/2 * (J_e^2 + J_{e+1}^2),
+ *   J_i = u_{i-1}'(x_i) - u_i'(x_i) at interior nodes, J_0 = J_ne = 0 (Dirichlet ends),
+ * the integral by the nq-point Gauss rule (1 <= nq <= 32).
+ *   W[ne*M]         1 <= M <= 33; zero-padded rows (lssvr_enhance_subset, ldw = max M) work unchanged
+ *   rhs_id          LSSVR_RHS_SIN (in-kernel), LSSVR_RHS_ARRAY (rhs_values[e*nq + q]) or
+ *                   LSSVR_RHS_ARRAY_PM (rhs_values[q*ne + e]), f at lssvr_estimate_points
+ *   eta2[ne]        out
+ *   jump[ne+1]      out, may be NULL: the J_i
+ *   out3[3]         out (device): {sum of the finite eta2, max of the finite eta2 (0 if none),
+ *                   count of non-finite eta2}; per-workgroup partials in `work`, then one finishing
+ *                   workgroup: no atomics, bitwise reproducible from run to run
+ *   work            device scratch of lssvr_adapt_work_bytes(ne) bytes
+ */
+int64_t lssvr_adapt_work_bytes(int64_t ne);
+int lssvr_estimate(const double* x, const double* W, int64_t ne, int M, int nq,
+                   int rhs_id, const double* rhs_params_host, const double* rhs_values,
+                   double* eta2, double* jump, double* out3, void* work, void* stream);
+
+/*
+ * lssvr_refine -- threshold marking and bisection.  Element e is marked iff
+ *   (eta2[e] is non-finite, or max > 0 and eta2[e] >= theta^2 * max)  and  x[e+1]-x[e] >= 2*h_min,
+ * max = *eta2_max_dev (DEVICE pointer, typically out3 + 1 of lssvr_estimate: no host round trip).
+ * theta in [0, 1], h_min >= 0.  A marked element is split at 0.5 * (x[e] + x[e+1]).
+ *   x_new[2*ne+1]   out: the new nodes, ascending (capacity 2*ne+1; *ne_new_dev + 1 are written)
+ *   parent[2*ne]    out, may be NULL: old element of every new element
+ *   ne_new_dev      out (device int64): the new element count
+ *   work            device scratch of lssvr_adapt_work_bytes(ne) bytes
+ * Three launches (block counts, a one-workgroup scan, scatter): the output is deterministic.
+ */
+int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev,
+                 double theta, double h_min, void* work, double* x_new, int64_t* parent,
+                 int64_t* ne_new_dev, void* stream);
 
 #ifdef __cplusplus
 }

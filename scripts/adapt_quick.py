@@ -1,0 +1,105 @@
+"""Timing of the a posteriori indicator and the refinement at 1e6 elements on one MI355X (DESIGN.md
+section 11): lssvr_estimate (M = 9, nq = 16, in-kernel sin rhs) and lssvr_refine (theta = 0.5), device
+events around `reps` back-to-back launches after a warm-up, beside lssvr_enhance on the same mesh.
+Prints the algorithmic bytes and flops per element, the bound that applies and the fraction of it;
+``--json PATH`` also writes the record as JSON.
+
+    python scripts/adapt_quick.py [--ne 1000000] [--reps 50] [--json PATH]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from hybrid_fem_lssvr_amd import ops  # noqa: E402
+
+FP64_PEAK_TFLOPS = 78.6      # MI355X vector FP64 peak
+HBM_PEAK_GBS = 8000.0        # spec; 6290 GB/s measured stream rate
+
+
+def timeit(fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e-3 / reps
+
+
+def roofline(name, t, ne, bytes_pe, flops_pe):
+    tb = bytes_pe * ne / (HBM_PEAK_GBS * 1e9)
+    tf = flops_pe * ne / (FP64_PEAK_TFLOPS * 1e12)
+    bound = "hbm" if tb >= tf else "fp64"
+    frac = max(tb, tf) / t
+    print(f"{name}: {t * 1e6:8.1f} us  {bytes_pe:.0f} B/elem, {flops_pe:.0f} flop/elem "
+          f"(intensity {flops_pe / bytes_pe:.1f} flop/B, ridge 9.8) -> {bound}-bound, "
+          f"{frac * 100:.1f}% of the {bound} bound ({bytes_pe * ne / t / 1e9:.0f} GB/s, "
+          f"{flops_pe * ne / t / 1e12:.2f} TFLOP/s)")
+    return dict(us=t * 1e6, bytes_per_element=bytes_pe, flops_per_element=flops_pe, bound=bound, frac=frac)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ne", type=int, default=1_000_000)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--json", default=None, help="write the record to this file")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("adapt_quick.py needs an MI355X")
+    dev = torch.device("cuda:0")
+    ne, M, nq, ncol = args.ne, 9, 16, 12
+    rng = np.random.default_rng(0)
+    h = rng.uniform(0.5, 1.5, ne)
+    x_h = np.concatenate([[-1.0], -1.0 + 2.0 * np.cumsum(h) / h.sum()])
+    x = torch.as_tensor(x_h, device=dev)
+    u = torch.sin(np.pi * x)
+    rhs = (ops.POISSON_AMP, ops.POISSON_OMEGA)
+    gd = (float(x_h[0]), float(x_h[-1]))          # given: no device-to-host read per call
+    W, _ = ops.enhance(x, u, M, 1e4, ncol, rhs=rhs, global_domain=gd)
+    work = ops.adapt_work(x, ne)
+    eta2, _, out3 = ops.estimate(x, W, nq, rhs=rhs, work=work)
+    t_enh = timeit(lambda: ops.enhance(x, u, M, 1e4, ncol, rhs=rhs, global_domain=gd, out=W), args.reps)
+    t_est = timeit(lambda: ops.estimate(x, W, nq, rhs=rhs, work=work), args.reps)
+    # refine: the launches alone (no trimming synchronisation) through the C entry
+    lib = ops._capi.load()
+    x_new = torch.empty(2 * ne + 1, dtype=torch.float64, device=dev)
+    ne_new = torch.empty(1, dtype=torch.int64, device=dev)
+    st = ops._stream(None)
+
+    def ref():
+        ops._capi.check(lib.lssvr_refine(x.data_ptr(), ne, eta2.data_ptr(), out3[1:2].data_ptr(), 0.5, 0.0,
+                                         work.data_ptr(), x_new.data_ptr(), None, ne_new.data_ptr(), st),
+                        "lssvr_refine")
+    t_ref = timeit(ref, args.reps)
+    n_new = int(ne_new.item())
+    # algorithmic traffic and work per element
+    est_bytes = 8 * (M + 1) + 8                               # W row + x (shared nodes), eta2
+    sin_flops = 2 * 10 + 10                                   # odd polynomial through r^21 + reduction
+    est_flops = nq * (2 * (M - 2) + 1 + 2 + 2 + sin_flops + 2) + 4 * (M - 1) + 12
+    ref_bytes = 2 * (8 + 8) + (n_new - ne) / ne * 8 + 8       # x, eta2 twice (count, scatter), x_new
+    ref_flops = 6
+    rec = {"ne": ne, "M": M, "nq": nq, "n_colloc_enhance": ncol, "reps": args.reps,
+           "enhance_us": t_enh * 1e6, "marked": n_new - ne}
+    print(f"ne = {ne}, M = {M}, nq = {nq}; lssvr_enhance (n_colloc = {ncol}) {t_enh * 1e6:.1f} us")
+    rec["estimate"] = roofline("lssvr_estimate", t_est, ne, est_bytes, est_flops)
+    rec["refine"] = roofline("lssvr_refine  ", t_ref, ne, ref_bytes, ref_flops)
+    rec["estimate_over_enhance"] = t_est / t_enh
+    rec["refine_over_enhance"] = t_ref / t_enh
+    print(f"estimate / enhance = {t_est / t_enh:.3f}, refine / enhance = {t_ref / t_enh:.3f}, "
+          f"marked {n_new - ne} of {ne}")
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(rec, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
