@@ -25,10 +25,10 @@ int check_launch(hipError_t e, const char* what) {
   return fail(LSSVR_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
 }
 
-int fill_enhance_args(lssvr::EnhanceArgs& a, const double* x, const double* u, int64_t ne,
-                      int64_t elem_offset, int64_t ne_global, double gxmin, double gxmax,
-                      double bc_left, double bc_right, int M, int n_colloc, double gamma,
-                      double* W) {
+// the arguments every enhancement entry shares, validated and bound
+int bind_enhance(lssvr::EnhanceArgs& a, const double* x, const double* u, int64_t ne, int64_t elem_offset,
+                 int64_t ne_global, double gxmin, double gxmax, double bc_left, double bc_right, int M,
+                 int n_colloc, double gamma, double* W, int32_t* status, int32_t* fail_count) {
   if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
   if (ne > 0 && (!x || !u || !W)) return fail(LSSVR_ERR_NULL, "x, u and W must be non-NULL");
   if (elem_offset < 0 || ne_global < elem_offset + ne)
@@ -56,17 +56,19 @@ int fill_enhance_args(lssvr::EnhanceArgs& a, const double* x, const double* u, i
   a.M = M;
   a.n = n_colloc;
   a.refine = lssvr::enhance_small_refine_steps(M, n_colloc);     // (read by the Poisson lane kernel only)
-  a.tab_es = n_colloc;      // tabulated arrays: element-major unless set_rhs / the caller says otherwise
+  a.tab_es = n_colloc;      // tabulated arrays: element-major unless bind_rhs says otherwise
   a.tab_ps = 1;
   a.W = W;
+  a.status = status;
+  a.fail_count = fail_count;
   static const lssvr::TrigTables trig = lssvr::make_trig_tables();
   a.trig = trig;
   return LSSVR_OK;
 }
 
-// right-hand side of an enhancement call: named (in-kernel) or tabulated
-int set_rhs(lssvr::EnhanceArgs& a, int rhs_id, const double* rhs_params_host,
-            const double* rhs_values, bool need_values, const char* count_name) {
+// right-hand side of an enhancement call: named (in-kernel) or tabulated, element- or point-major
+int bind_rhs(lssvr::EnhanceArgs& a, int rhs_id, const double* rhs_params_host, const double* rhs_values,
+             bool need_values, const char* count_name) {
   a.rhs_id = rhs_id;
   if (rhs_id == LSSVR_RHS_SIN) {
     if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
@@ -88,10 +90,45 @@ int set_rhs(lssvr::EnhanceArgs& a, int rhs_id, const double* rhs_params_host,
   return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
 }
 
-}  // namespace
+// the variable-coefficient triple (a, a', f): three tables in one layout
+int bind_varcoef(lssvr::EnhanceArgs& a, const double* a_values, const double* da_values, const double* rhs_values,
+                 int table_layout, bool need_values) {
+  if (need_values && (!a_values || !da_values || !rhs_values))
+    return fail(LSSVR_ERR_NULL, "a_values, da_values and rhs_values must be non-NULL");
+  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
+    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  a.a_values = a_values;
+  a.da_values = da_values;
+  return bind_rhs(a, table_layout == LSSVR_TABLE_POINT_MAJOR ? LSSVR_RHS_ARRAY_PM : LSSVR_RHS_ARRAY, nullptr,
+                  rhs_values, false, "ne");
+}
 
-namespace {
-// shared tail of lssvr_enhance / lssvr_enhance_profiled
+// a caller's workspace against the `need` bytes that `sizer` reports for the call
+int check_work(const void* work, int64_t work_bytes, int64_t need, const char* sizer) {
+  if (work_bytes < 0 || (work_bytes > 0 && !work)) return fail(LSSVR_ERR_NULL, "work / work_bytes inconsistent");
+  // a workspace that is given but too small is an error, not a silent change of kernel (and, in
+  // the near-square regime, of accuracy: the refinement needs its 32 extra doubles per element)
+  if (work && work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, %s() = %lld (pass work = NULL for the workspace-free "
+                "kernels)", (long long)work_bytes, sizer, (long long)need);
+  return LSSVR_OK;
+}
+
+// P1 assembly arguments shared by lssvr_step, lssvr_step_varcoef and lssvr_p1_assemble (rhs left to the caller)
+int bind_p1(lssvr::P1Args& p, const double* x, int64_t ne, int nquad, double* diag, double* off, double* load) {
+  if (!x || !diag || !off || !load) return fail(LSSVR_ERR_NULL, "x, diag, off, load must be non-NULL");
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  p = lssvr::P1Args{};
+  p.x = x;
+  p.ne = ne;
+  p.nquad = nquad;
+  p.diag = diag;
+  p.off = off;
+  p.load = load;
+  return LSSVR_OK;
+}
+
+// shared tail of every enhancement entry but the shared-operator one
 int enhance_dispatch(const lssvr::EnhanceArgs& a, int solver_id, hipStream_t s,
                      const lssvr::LaunchOpts* o, void* work = nullptr, int64_t work_bytes = 0) {
   // Fewer collocation points than bubble coefficients: the primal normal equations are rank
@@ -123,51 +160,92 @@ int enhance_dispatch(const lssvr::EnhanceArgs& a, int solver_id, hipStream_t s,
   // otherwise the direct Gram on the f64 matrix cores
   return check_launch(lssvr::enhance_large(a, s, o), "enhance_large");
 }
-}  // namespace
 
-namespace {
-// enhance_dispatch, optionally BLOCKING and stamped with the dispatch's own begin / end times
-int dispatch_timed(const lssvr::EnhanceArgs& a, int solver_id, hipStream_t s, void* work,
-                   int64_t work_bytes, float* kernel_ms_host) {
-  if (!kernel_ms_host) return enhance_dispatch(a, solver_id, s, nullptr, work, work_bytes);
-  lssvr::LaunchOpts o;
+// a begin / end event pair for one stamped launch
+int create_events(lssvr::LaunchOpts& o) {
   if (hipEventCreate(&o.start) != hipSuccess || hipEventCreate(&o.stop) != hipSuccess)
     return fail(LSSVR_ERR_LAUNCH, "hipEventCreate failed");
-  int rc = enhance_dispatch(a, solver_id, s, &o, work, work_bytes);
+  return LSSVR_OK;
+}
+
+void destroy_events(const lssvr::LaunchOpts& o) {
+  if (o.start) (void)hipEventDestroy(o.start);
+  if (o.stop) (void)hipEventDestroy(o.stop);
+}
+
+// go(const LaunchOpts*) -> LSSVR_* code: plain (go(nullptr)) when kernel_ms_host is NULL, otherwise BLOCKING and
+// stamped with the dispatch's own begin / end times
+template <typename Launch>
+int timed_launch(Launch&& go, float* kernel_ms_host) {
+  if (!kernel_ms_host) return go(nullptr);
+  lssvr::LaunchOpts o;
+  int rc = create_events(o);
+  if (rc == LSSVR_OK) rc = go(&o);
   if (rc == LSSVR_OK) {
     hipError_t e = hipEventSynchronize(o.stop);
     if (e == hipSuccess) e = hipEventElapsedTime(kernel_ms_host, o.start, o.stop);
     if (e != hipSuccess) rc = fail(LSSVR_ERR_LAUNCH, "profiled launch: %s", hipGetErrorString(e));
   }
-  (void)hipEventDestroy(o.start);
-  (void)hipEventDestroy(o.stop);
+  destroy_events(o);
   return rc;
 }
-}  // namespace
 
-namespace {
-// `repeats` launches of enhance_dispatch back to back, each with its own begin / end stamps, ONE
-// synchronisation at the end (lssvr_enhance_ws_sequence, lssvr_enhance_varcoef_ws_sequence)
-int dispatch_sequence(const lssvr::EnhanceArgs& a, int solver_id, hipStream_t s, void* work, int64_t work_bytes,
-                      int repeats, float* kernel_ms_host) {
+// `repeats` launches of go back to back, each with its own begin / end stamps, ONE synchronisation at the end
+template <typename Launch>
+int timed_sequence(Launch&& go, hipStream_t s, int repeats, float* kernel_ms_host) {
   std::vector<lssvr::LaunchOpts> ev((size_t)repeats);
-  int made = 0;
-  for (; made < repeats; ++made)
-    if (hipEventCreate(&ev[made].start) != hipSuccess || hipEventCreate(&ev[made].stop) != hipSuccess) break;
-  int rc = made == repeats ? LSSVR_OK : fail(LSSVR_ERR_LAUNCH, "hipEventCreate failed");
-  for (int r = 0; r < repeats && rc == LSSVR_OK; ++r) rc = enhance_dispatch(a, solver_id, s, &ev[r], work, work_bytes);
+  int rc = LSSVR_OK;
+  for (int r = 0; r < repeats && rc == LSSVR_OK; ++r) rc = create_events(ev[r]);
+  for (int r = 0; r < repeats && rc == LSSVR_OK; ++r) rc = go(&ev[r]);
   hipError_t e = hipStreamSynchronize(s);            // (also after a failed launch: earlier ones are in flight)
   if (rc == LSSVR_OK && e != hipSuccess) rc = fail(LSSVR_ERR_LAUNCH, "profiled sequence: %s", hipGetErrorString(e));
   for (int r = 0; r < repeats && rc == LSSVR_OK; ++r) {
     e = hipEventElapsedTime(&kernel_ms_host[r], ev[r].start, ev[r].stop);
     if (e != hipSuccess) rc = fail(LSSVR_ERR_LAUNCH, "profiled sequence: %s", hipGetErrorString(e));
   }
-  for (int r = 0; r < repeats; ++r) {
-    if (ev[r].start) (void)hipEventDestroy(ev[r].start);
-    if (ev[r].stop) (void)hipEventDestroy(ev[r].stop);
-  }
+  for (const lssvr::LaunchOpts& o : ev) destroy_events(o);
   return rc;
 }
+
+// preconditions of the *_sequence entries, before their arguments are bound
+int check_sequence(int64_t ne, int repeats, const float* kernel_ms_host) {
+  if (!kernel_ms_host) return fail(LSSVR_ERR_NULL, "kernel_ms_host must be non-NULL (float[repeats])");
+  if (repeats < 1 || repeats > 100000) return fail(LSSVR_ERR_SIZE, "repeats = %d outside [1, 100000]", repeats);
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "nothing to profile: ne = %lld", (long long)ne);
+  return LSSVR_OK;
+}
+
+// the arguments of lssvr_enhance_ws / lssvr_enhance_ws_sequence, validated and bound
+int bind_enhance_ws(lssvr::EnhanceArgs& a, const double* x, const double* u, int64_t ne, int64_t elem_offset,
+                    int64_t ne_global, double gxmin, double gxmax, double bc_left, double bc_right, int M,
+                    int n_colloc, double gamma, int rhs_id, const double* rhs_params_host, const double* rhs_values,
+                    int solver_id, double* W, int32_t* status, int32_t* fail_count, void* work,
+                    int64_t work_bytes) {
+  int rc = bind_enhance(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                        gamma, W, status, fail_count);
+  if (rc == LSSVR_OK) rc = bind_rhs(a, rhs_id, rhs_params_host, rhs_values, ne > 0, "ne");
+  if (rc != LSSVR_OK) return rc;
+  if (solver_id != LSSVR_SOLVER_PRIMAL && solver_id != LSSVR_SOLVER_DUAL &&
+      solver_id != LSSVR_SOLVER_PRIMAL_WAVE && solver_id != LSSVR_SOLVER_PRIMAL_MOMENT)
+    return fail(LSSVR_ERR_SOLVER, "unknown solver_id %d", solver_id);
+  return check_work(work, work_bytes, lssvr_enhance_work_bytes(ne, M, n_colloc, solver_id),
+                    "lssvr_enhance_work_bytes");
+}
+
+// the arguments of lssvr_enhance_varcoef_ws / lssvr_enhance_varcoef_ws_sequence, validated and bound
+int bind_varcoef_ws(lssvr::EnhanceArgs& a, const double* x, const double* u, int64_t ne, int64_t elem_offset,
+                    int64_t ne_global, double gxmin, double gxmax, double bc_left, double bc_right, int M,
+                    int n_colloc, double gamma, const double* a_values, const double* da_values,
+                    const double* rhs_values, int table_layout, double* W, int32_t* status, int32_t* fail_count,
+                    void* work, int64_t work_bytes) {
+  int rc = bind_enhance(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                        gamma, W, status, fail_count);
+  if (rc == LSSVR_OK) rc = bind_varcoef(a, a_values, da_values, rhs_values, table_layout, ne > 0);
+  if (rc != LSSVR_OK) return rc;
+  return check_work(work, work_bytes, lssvr_enhance_varcoef_work_bytes(ne, M, n_colloc),
+                    "lssvr_enhance_varcoef_work_bytes");
+}
+
 }  // namespace
 
 extern "C" {
@@ -181,19 +259,9 @@ int lssvr_enhance(const double* x, const double* u, int64_t ne, int64_t elem_off
                   int M, int n_colloc, double gamma, int rhs_id, const double* rhs_params_host,
                   const double* rhs_values, int solver_id, double* W, int32_t* status,
                   int32_t* fail_count, void* stream) {
-  lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
-  if (rc != LSSVR_OK) return rc;
-  rc = set_rhs(a, rhs_id, rhs_params_host, rhs_values, ne > 0, "ne");
-  if (rc != LSSVR_OK) return rc;
-  a.status = status;
-  a.fail_count = fail_count;
-  if (solver_id != LSSVR_SOLVER_PRIMAL && solver_id != LSSVR_SOLVER_DUAL &&
-      solver_id != LSSVR_SOLVER_PRIMAL_WAVE && solver_id != LSSVR_SOLVER_PRIMAL_MOMENT)
-    return fail(LSSVR_ERR_SOLVER, "unknown solver_id %d", solver_id);
-  if (ne == 0) return LSSVR_OK;
-  return enhance_dispatch(a, solver_id, reinterpret_cast<hipStream_t>(stream), nullptr);
+  return lssvr_enhance_ws(x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, gamma,
+                          rhs_id, rhs_params_host, rhs_values, solver_id, W, status, fail_count, nullptr, 0, stream,
+                          nullptr);
 }
 
 int64_t lssvr_enhance_work_bytes(int64_t ne, int M, int n_colloc, int solver_id) {
@@ -210,26 +278,13 @@ int lssvr_enhance_ws(const double* x, const double* u, int64_t ne, int64_t elem_
                      int32_t* fail_count, void* work, int64_t work_bytes, void* stream,
                      float* kernel_ms_host) {
   lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
-  if (rc != LSSVR_OK) return rc;
-  rc = set_rhs(a, rhs_id, rhs_params_host, rhs_values, ne > 0, "ne");
-  if (rc != LSSVR_OK) return rc;
-  a.status = status;
-  a.fail_count = fail_count;
-  if (solver_id != LSSVR_SOLVER_PRIMAL && solver_id != LSSVR_SOLVER_DUAL &&
-      solver_id != LSSVR_SOLVER_PRIMAL_WAVE && solver_id != LSSVR_SOLVER_PRIMAL_MOMENT)
-    return fail(LSSVR_ERR_SOLVER, "unknown solver_id %d", solver_id);
-  if (work_bytes < 0 || (work_bytes > 0 && !work)) return fail(LSSVR_ERR_NULL, "work / work_bytes inconsistent");
-  // a workspace that is given but too small is an error, not a silent change of kernel (and, in
-  // the near-square regime, of accuracy: the refinement needs its 32 extra doubles per element)
-  const int64_t need = lssvr_enhance_work_bytes(ne, M, n_colloc, solver_id);
-  if (work && work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_enhance_work_bytes(%lld, %d, %d, %d) = %lld "
-                "(pass work = NULL for the workspace-free kernels)", (long long)work_bytes, (long long)ne, M,
-                n_colloc, solver_id, (long long)need);
-  if (ne == 0) return LSSVR_OK;
-  return dispatch_timed(a, solver_id, reinterpret_cast<hipStream_t>(stream), work, work_bytes, kernel_ms_host);
+  const int rc = bind_enhance_ws(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                                 gamma, rhs_id, rhs_params_host, rhs_values, solver_id, W, status, fail_count, work,
+                                 work_bytes);
+  if (rc != LSSVR_OK || ne == 0) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return timed_launch([&](const lssvr::LaunchOpts* o) { return enhance_dispatch(a, solver_id, s, o, work, work_bytes); },
+                      kernel_ms_host);
 }
 
 int lssvr_enhance_ws_sequence(const double* x, const double* u, int64_t ne, int64_t elem_offset,
@@ -238,27 +293,15 @@ int lssvr_enhance_ws_sequence(const double* x, const double* u, int64_t ne, int6
                               const double* rhs_values, int solver_id, double* W, int32_t* status,
                               int32_t* fail_count, void* work, int64_t work_bytes, void* stream,
                               int repeats, float* kernel_ms_host) {
-  if (!kernel_ms_host) return fail(LSSVR_ERR_NULL, "kernel_ms_host must be non-NULL (float[repeats])");
-  if (repeats < 1 || repeats > 100000) return fail(LSSVR_ERR_SIZE, "repeats = %d outside [1, 100000]", repeats);
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "nothing to profile: ne = %lld", (long long)ne);
   lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
+  int rc = check_sequence(ne, repeats, kernel_ms_host);
+  if (rc == LSSVR_OK)
+    rc = bind_enhance_ws(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, gamma,
+                         rhs_id, rhs_params_host, rhs_values, solver_id, W, status, fail_count, work, work_bytes);
   if (rc != LSSVR_OK) return rc;
-  rc = set_rhs(a, rhs_id, rhs_params_host, rhs_values, true, "ne");
-  if (rc != LSSVR_OK) return rc;
-  a.status = status;
-  a.fail_count = fail_count;
-  if (solver_id != LSSVR_SOLVER_PRIMAL && solver_id != LSSVR_SOLVER_DUAL &&
-      solver_id != LSSVR_SOLVER_PRIMAL_WAVE && solver_id != LSSVR_SOLVER_PRIMAL_MOMENT)
-    return fail(LSSVR_ERR_SOLVER, "unknown solver_id %d", solver_id);
-  if (work_bytes < 0 || (work_bytes > 0 && !work)) return fail(LSSVR_ERR_NULL, "work / work_bytes inconsistent");
-  const int64_t need = lssvr_enhance_work_bytes(ne, M, n_colloc, solver_id);
-  if (work && work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_enhance_work_bytes() = %lld", (long long)work_bytes,
-                (long long)need);
-  return dispatch_sequence(a, solver_id, reinterpret_cast<hipStream_t>(stream), work, work_bytes, repeats,
-                           kernel_ms_host);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return timed_sequence([&](const lssvr::LaunchOpts* o) { return enhance_dispatch(a, solver_id, s, o, work, work_bytes); },
+                        s, repeats, kernel_ms_host);
 }
 
 int lssvr_enhance_profiled(const double* x, const double* u, int64_t ne, int64_t elem_offset,
@@ -267,18 +310,10 @@ int lssvr_enhance_profiled(const double* x, const double* u, int64_t ne, int64_t
                            const double* rhs_params_host, const double* rhs_values, int solver_id,
                            double* W, int32_t* status, void* stream, float* kernel_ms_host) {
   if (!kernel_ms_host) return fail(LSSVR_ERR_NULL, "kernel_ms_host must be non-NULL");
-  lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
-  if (rc != LSSVR_OK) return rc;
-  if (ne == 0) return fail(LSSVR_ERR_SIZE, "nothing to profile: ne = 0");
-  rc = set_rhs(a, rhs_id, rhs_params_host, rhs_values, true, "ne");
-  if (rc != LSSVR_OK) return rc;
-  a.status = status;
-  if (solver_id != LSSVR_SOLVER_PRIMAL && solver_id != LSSVR_SOLVER_DUAL &&
-      solver_id != LSSVR_SOLVER_PRIMAL_WAVE && solver_id != LSSVR_SOLVER_PRIMAL_MOMENT)
-    return fail(LSSVR_ERR_SOLVER, "unknown solver_id %d", solver_id);
-  return dispatch_timed(a, solver_id, reinterpret_cast<hipStream_t>(stream), nullptr, 0, kernel_ms_host);
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "nothing to profile: ne = %lld", (long long)ne);
+  return lssvr_enhance_ws(x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, gamma,
+                          rhs_id, rhs_params_host, rhs_values, solver_id, W, status, nullptr, nullptr, 0, stream,
+                          kernel_ms_host);
 }
 
 // lssvr_step's arguments, validated and turned into the kernels' argument blocks: what a plan keeps
@@ -293,33 +328,20 @@ static int bind_step(lssvr_step_plan& b, const double* x, const double* u, int64
                      double* diag, double* off, double* load, double* W, int32_t* status,
                      int32_t* fail_count) {
   lssvr::EnhanceArgs& a = b.a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
+  int rc = bind_enhance(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, gamma,
+                        W, status, fail_count);
   if (rc != LSSVR_OK) return rc;
   if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (!diag || !off || !load) return fail(LSSVR_ERR_NULL, "diag, off, load must be non-NULL");
-  if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "rhs_params = {amp, omega} required");
-  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  rc = bind_p1(b.p, x, ne, nquad, diag, off, load);
+  if (rc == LSSVR_OK) rc = bind_rhs(a, LSSVR_RHS_SIN, rhs_params_host, nullptr, false, "ne");
+  if (rc != LSSVR_OK) return rc;
   if (n_colloc < M - 2)
     return fail(LSSVR_ERR_SOLVER, "lssvr_step: n_colloc = %d < M-2 = %d: the primal normal equations are "
                                   "rank deficient; use lssvr_p1_assemble + lssvr_enhance (dual solver)",
                 n_colloc, M - 2);
-  a.rhs_id = LSSVR_RHS_SIN;
-  a.rhs_amp = rhs_params_host[0];
-  a.rhs_omega = rhs_params_host[1];
-  a.status = status;
-  a.fail_count = fail_count;
-  lssvr::P1Args& p = b.p;
-  p = lssvr::P1Args{};
-  p.x = x;
-  p.ne = ne;
-  p.nquad = nquad;
-  p.rhs_id = LSSVR_RHS_SIN;
-  p.rhs_amp = a.rhs_amp;
-  p.rhs_omega = a.rhs_omega;
-  p.diag = diag;
-  p.off = off;
-  p.load = load;
+  b.p.rhs_id = LSSVR_RHS_SIN;
+  b.p.rhs_amp = a.rhs_amp;
+  b.p.rhs_omega = a.rhs_omega;
   return LSSVR_OK;
 }
 
@@ -394,40 +416,22 @@ int lssvr_step_varcoef(const double* x, const double* u, int64_t ne, int64_t ele
                        const double* rhs_quad, const double* a_quad, double* diag, double* off,
                        double* load, double* W, int32_t* status, int32_t* fail_count, void* stream) {
   lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
+  int rc = bind_enhance(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, gamma,
+                        W, status, fail_count);
   if (rc != LSSVR_OK) return rc;
   if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (!a_values || !da_values || !rhs_values)
-    return fail(LSSVR_ERR_NULL, "a_values, da_values and rhs_values must be non-NULL");
+  rc = bind_varcoef(a, a_values, da_values, rhs_values, table_layout, true);
+  if (rc != LSSVR_OK) return rc;
   if (!rhs_quad || !a_quad) return fail(LSSVR_ERR_NULL, "rhs_quad and a_quad must be non-NULL");
-  if (!diag || !off || !load) return fail(LSSVR_ERR_NULL, "diag, off, load must be non-NULL");
-  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  lssvr::P1Args p;
+  rc = bind_p1(p, x, ne, nquad, diag, off, load);
+  if (rc != LSSVR_OK) return rc;
   if (n_colloc < M - 2)
     return fail(LSSVR_ERR_SOLVER, "lssvr_step_varcoef: n_colloc = %d < M-2 = %d: use lssvr_p1_assemble + "
                                   "lssvr_enhance_varcoef (dual solver)", n_colloc, M - 2);
-  a.rhs_id = LSSVR_RHS_ARRAY;
-  a.rhs_values = rhs_values;
-  a.a_values = a_values;
-  a.da_values = da_values;
-  if (table_layout == LSSVR_TABLE_POINT_MAJOR) {
-    a.tab_es = 1;
-    a.tab_ps = ne;
-  }
-  a.status = status;
-  a.fail_count = fail_count;
-  lssvr::P1Args p{};
-  p.x = x;
-  p.ne = ne;
-  p.nquad = nquad;
   p.rhs_id = LSSVR_RHS_ARRAY;
   p.rhs_quad = rhs_quad;
   p.a_quad = a_quad;
-  p.diag = diag;
-  p.off = off;
-  p.load = load;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (M <= lssvr::kStepVarcoefFusedMaxM) return check_launch(lssvr::step_small_vc(a, p, s), "step_small_vc");
   rc = check_launch(lssvr::p1_assemble(p, s), "p1_assemble");
@@ -435,6 +439,7 @@ int lssvr_step_varcoef(const double* x, const double* u, int64_t ne, int64_t ele
   return enhance_dispatch(a, LSSVR_SOLVER_PRIMAL, s, nullptr);
 }
 
+// (no variable-coefficient kernel takes a workspace: always 0, kept for ABI 6)
 int64_t lssvr_enhance_varcoef_work_bytes(int64_t ne, int M, int n_colloc) {
   (void)ne; (void)M; (void)n_colloc;
   return 0;
@@ -448,32 +453,15 @@ int lssvr_enhance_varcoef_ws(const double* x, const double* u, int64_t ne, int64
                              int32_t* fail_count, void* work, int64_t work_bytes, void* stream,
                              float* kernel_ms_host) {
   lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
-  if (rc != LSSVR_OK) return rc;
-  if (ne > 0 && (!a_values || !da_values || !rhs_values))
-    return fail(LSSVR_ERR_NULL, "a_values, da_values and rhs_values must be non-NULL");
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
-  a.rhs_id = LSSVR_RHS_ARRAY;
-  a.rhs_values = rhs_values;
-  a.a_values = a_values;
-  a.da_values = da_values;
-  if (table_layout == LSSVR_TABLE_POINT_MAJOR) {
-    a.tab_es = 1;
-    a.tab_ps = ne > 0 ? ne : 1;
-  }
-  a.status = status;
-  a.fail_count = fail_count;
-  if (work_bytes < 0 || (work_bytes > 0 && !work)) return fail(LSSVR_ERR_NULL, "work / work_bytes inconsistent");
-  const int64_t need = lssvr_enhance_varcoef_work_bytes(ne, M, n_colloc);
-  if (work && work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_enhance_varcoef_work_bytes() = %lld",
-                (long long)work_bytes, (long long)need);
-  if (ne == 0) return LSSVR_OK;
+  const int rc = bind_varcoef_ws(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                                 gamma, a_values, da_values, rhs_values, table_layout, W, status, fail_count, work,
+                                 work_bytes);
+  if (rc != LSSVR_OK || ne == 0) return rc;
   // (n_colloc < M-2: rank-deficient primal normal equations -> the dual Gram solver)
-  return dispatch_timed(a, LSSVR_SOLVER_PRIMAL, reinterpret_cast<hipStream_t>(stream), work, work_bytes,
-                        kernel_ms_host);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return timed_launch(
+      [&](const lssvr::LaunchOpts* o) { return enhance_dispatch(a, LSSVR_SOLVER_PRIMAL, s, o, work, work_bytes); },
+      kernel_ms_host);
 }
 
 int lssvr_enhance_varcoef_ws_sequence(const double* x, const double* u, int64_t ne, int64_t elem_offset,
@@ -483,34 +471,16 @@ int lssvr_enhance_varcoef_ws_sequence(const double* x, const double* u, int64_t 
                                       const double* rhs_values, int table_layout, double* W, int32_t* status,
                                       int32_t* fail_count, void* work, int64_t work_bytes, void* stream,
                                       int repeats, float* kernel_ms_host) {
-  if (!kernel_ms_host) return fail(LSSVR_ERR_NULL, "kernel_ms_host must be non-NULL (float[repeats])");
-  if (repeats < 1 || repeats > 100000) return fail(LSSVR_ERR_SIZE, "repeats = %d outside [1, 100000]", repeats);
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "nothing to profile: ne = %lld", (long long)ne);
   lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma, W);
+  int rc = check_sequence(ne, repeats, kernel_ms_host);
+  if (rc == LSSVR_OK)
+    rc = bind_varcoef_ws(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, gamma,
+                         a_values, da_values, rhs_values, table_layout, W, status, fail_count, work, work_bytes);
   if (rc != LSSVR_OK) return rc;
-  if (!a_values || !da_values || !rhs_values)
-    return fail(LSSVR_ERR_NULL, "a_values, da_values and rhs_values must be non-NULL");
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
-  a.rhs_id = LSSVR_RHS_ARRAY;
-  a.rhs_values = rhs_values;
-  a.a_values = a_values;
-  a.da_values = da_values;
-  if (table_layout == LSSVR_TABLE_POINT_MAJOR) {
-    a.tab_es = 1;
-    a.tab_ps = ne;
-  }
-  a.status = status;
-  a.fail_count = fail_count;
-  if (work_bytes < 0 || (work_bytes > 0 && !work)) return fail(LSSVR_ERR_NULL, "work / work_bytes inconsistent");
-  const int64_t need = lssvr_enhance_varcoef_work_bytes(ne, M, n_colloc);
-  if (work && work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_enhance_varcoef_work_bytes() = %lld",
-                (long long)work_bytes, (long long)need);
-  return dispatch_sequence(a, LSSVR_SOLVER_PRIMAL, reinterpret_cast<hipStream_t>(stream), work, work_bytes,
-                           repeats, kernel_ms_host);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return timed_sequence(
+      [&](const lssvr::LaunchOpts* o) { return enhance_dispatch(a, LSSVR_SOLVER_PRIMAL, s, o, work, work_bytes); },
+      s, repeats, kernel_ms_host);
 }
 
 int lssvr_enhance_subset(const double* x, const double* u, int64_t ne_mesh,
@@ -542,9 +512,9 @@ int lssvr_enhance_subset_ws(const double* x, const double* u, int64_t ne_mesh,
     return fail(LSSVR_ERR_SIZE, "shard [%lld, %lld) does not fit ne_global = %lld",
                 (long long)elem_offset, (long long)(elem_offset + ne_mesh), (long long)ne_global);
   lssvr::EnhanceArgs a;
-  // (the shard check of fill_enhance_args is on the subset size here: done above for the mesh)
-  int rc = fill_enhance_args(a, x, u, nsub, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, gamma_values ? 1.0 : gamma, W);
+  // (the shard check of bind_enhance is on the subset size here: done above for the mesh)
+  int rc = bind_enhance(a, x, u, nsub, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                        gamma_values ? 1.0 : gamma, W, status, fail_count);
   if (rc != LSSVR_OK) return rc;
   if (n_colloc < M - 2)
     return fail(LSSVR_ERR_SOLVER, "lssvr_enhance_subset: n_colloc < M-2 needs the dual solver, "
@@ -555,16 +525,11 @@ int lssvr_enhance_subset_ws(const double* x, const double* u, int64_t ne_mesh,
   a.ne_mesh = ne_mesh;
   a.gamma_values = gamma_values;
   a.ldw = ldw;
-  rc = set_rhs(a, rhs_id, rhs_params_host, rhs_values, nsub > 0, "nsub");
-  if (rc != LSSVR_OK) return rc;
-  a.status = status;
-  a.fail_count = fail_count;
-  if (work_bytes < 0 || (work_bytes > 0 && !work)) return fail(LSSVR_ERR_NULL, "work / work_bytes inconsistent");
-  const int64_t need = lssvr_enhance_work_bytes(nsub, M, n_colloc, LSSVR_SOLVER_PRIMAL);
-  if (work && work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_enhance_work_bytes(nsub = %lld, %d, %d, 0) = %lld",
-                (long long)work_bytes, (long long)nsub, M, n_colloc, (long long)need);
-  if (nsub == 0) return LSSVR_OK;
+  rc = bind_rhs(a, rhs_id, rhs_params_host, rhs_values, nsub > 0, "nsub");
+  if (rc == LSSVR_OK)
+    rc = check_work(work, work_bytes, lssvr_enhance_work_bytes(nsub, M, n_colloc, LSSVR_SOLVER_PRIMAL),
+                    "lssvr_enhance_work_bytes");
+  if (rc != LSSVR_OK || nsub == 0) return rc;
   // (M <= 22: the lane kernel; above, with a workspace: moments + solve kernels, without: the MFMA kernel)
   return enhance_dispatch(a, LSSVR_SOLVER_PRIMAL, reinterpret_cast<hipStream_t>(stream), nullptr, work, work_bytes);
 }
@@ -576,31 +541,18 @@ int lssvr_enhance_shared(const double* x, const double* u, int64_t ne, int64_t e
                          double* W, int32_t* status, int32_t* fail_count, void* stream,
                          float* kernel_ms_host) {
   lssvr::EnhanceArgs a;
-  int rc = fill_enhance_args(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right,
-                             M, n_colloc, 1.0, W);
+  int rc = bind_enhance(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, 1.0,
+                        W, status, fail_count);
   if (rc != LSSVR_OK) return rc;
   if (M > lssvr::kSharedMaxM)
     return fail(LSSVR_ERR_DEGREE, "shared-operator path: M = %d > %d", M, lssvr::kSharedMaxM);
   if (ne > 0 && !op) return fail(LSSVR_ERR_NULL, "op[(n_colloc+2)*M] must be non-NULL");
-  rc = set_rhs(a, rhs_id, rhs_params_host, rhs_values, ne > 0, "ne");
-  if (rc != LSSVR_OK) return rc;
-  a.status = status;
-  a.fail_count = fail_count;
-  if (ne == 0) return LSSVR_OK;
+  rc = bind_rhs(a, rhs_id, rhs_params_host, rhs_values, ne > 0, "ne");
+  if (rc != LSSVR_OK || ne == 0) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (!kernel_ms_host) return check_launch(lssvr::enhance_shared(a, op, s), "enhance_shared");
-  lssvr::LaunchOpts o;
-  if (hipEventCreate(&o.start) != hipSuccess || hipEventCreate(&o.stop) != hipSuccess)
-    return fail(LSSVR_ERR_LAUNCH, "hipEventCreate failed");
-  rc = check_launch(lssvr::enhance_shared(a, op, s, &o), "enhance_shared(profiled)");
-  if (rc == LSSVR_OK) {
-    if (hipEventSynchronize(o.stop) != hipSuccess ||
-        hipEventElapsedTime(kernel_ms_host, o.start, o.stop) != hipSuccess)
-      rc = fail(LSSVR_ERR_LAUNCH, "event timing failed");
-  }
-  (void)hipEventDestroy(o.start);
-  (void)hipEventDestroy(o.stop);
-  return rc;
+  return timed_launch(
+      [&](const lssvr::LaunchOpts* o) { return check_launch(lssvr::enhance_shared(a, op, s, o), "enhance_shared"); },
+      kernel_ms_host);
 }
 
 int lssvr_colloc_points(const double* x, int64_t ne, int n_colloc, double* xc, void* stream) {
@@ -624,12 +576,9 @@ int lssvr_p1_assemble(const double* x, int64_t ne, int nquad, int rhs_id,
                       double* diag, double* off, double* load, double* kloc, double* floc,
                       void* stream) {
   if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (!x || !diag || !off || !load) return fail(LSSVR_ERR_NULL, "x, diag, off, load must be non-NULL");
-  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
-  lssvr::P1Args a{};
-  a.x = x;
-  a.ne = ne;
-  a.nquad = nquad;
+  lssvr::P1Args a;
+  const int rc = bind_p1(a, x, ne, nquad, diag, off, load);
+  if (rc != LSSVR_OK) return rc;
   a.rhs_id = rhs_id;
   if (rhs_id == LSSVR_RHS_SIN) {
     if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
@@ -642,9 +591,6 @@ int lssvr_p1_assemble(const double* x, int64_t ne, int nquad, int rhs_id,
     return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
   }
   a.a_quad = a_quad;
-  a.diag = diag;
-  a.off = off;
-  a.load = load;
   a.kloc = kloc;
   a.floc = floc;
   return check_launch(lssvr::p1_assemble(a, reinterpret_cast<hipStream_t>(stream)), "p1_assemble");

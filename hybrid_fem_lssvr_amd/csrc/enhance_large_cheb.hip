@@ -818,30 +818,25 @@ hipError_t enhance_large_split(const EnhanceArgs& a, void* work, hipStream_t s, 
   const bool prof = o && o->start && o->stop;
   const bool sine = a.rhs_id == LSSVR_RHS_SIN;
   // (plain launches unless stamped: the hipExt entry only where an event is attached)
-  auto go = [&](auto kernel, dim3 g, dim3 t, hipEvent_t ev_start, hipEvent_t ev_stop, auto... args) {
-    if (ev_start || ev_stop) hipExtLaunchKernelGGL(kernel, g, t, 0, s, ev_start, ev_stop, 0, args...);
-    else hipLaunchKernelGGL(kernel, g, t, 0, s, args...);
-    return hipGetLastError();
-  };
-  hipEvent_t const ev0 = prof ? o->start : nullptr, ev1 = prof ? o->stop : nullptr;
+  const LaunchOpts first{prof ? o->start : nullptr, nullptr}, last{nullptr, prof ? o->stop : nullptr};
   const double* const cws = ws;
   const double* const czws = zws;
-  hipError_t e = sine ? go(moments_kernel<LSSVR_RHS_SIN>, g1, t1, ev0, nullptr, a, ws)
-                      : go(moments_kernel<LSSVR_RHS_ARRAY>, g1, t1, ev0, nullptr, a, ws);
+  hipError_t e = sine ? launch(moments_kernel<LSSVR_RHS_SIN>, g1, t1, s, &first, a, ws)
+                      : launch(moments_kernel<LSSVR_RHS_ARRAY>, g1, t1, s, &first, a, ws);
   if (e != hipSuccess) return e;
   // ridge-dominated elements, from the finished workspace rows and BEFORE a refinement pass overwrites their
   // right-hand sides; the solve kernels below leave those elements alone
-  if ((e = go(ridge_fixup_kernel, gr, tr, nullptr, nullptr, a, cws)) != hipSuccess) return e;
-  if (steps == 0 && enhance_parity_applies(a.M, a.n)) return launch_solve4_parity(a, cws, s, ev1);
-  if (steps == 0) return go(solve4_kernel<0>, g2, t2, nullptr, ev1, a, cws, (double*)nullptr, nxcd);
+  if ((e = launch(ridge_fixup_kernel, gr, tr, s, nullptr, a, cws)) != hipSuccess) return e;
+  if (steps == 0 && enhance_parity_applies(a.M, a.n)) return launch_solve4_parity(a, cws, s, &last);
+  if (steps == 0) return launch(solve4_kernel<0>, g2, t2, s, &last, a, cws, (double*)nullptr, nxcd);
   EnhanceArgs quiet = a;           // failures are counted once, by the last pass
   quiet.fail_count = nullptr;
-  if ((e = go(solve4_kernel<1>, g2, t2, nullptr, nullptr, quiet, cws, zws, nxcd)) != hipSuccess) return e;
+  if ((e = launch(solve4_kernel<1>, g2, t2, s, nullptr, quiet, cws, zws, nxcd)) != hipSuccess) return e;
   for (int it = 1; it <= steps; ++it) {
-    e = sine ? go(residual_kernel<LSSVR_RHS_SIN>, gr, tr, nullptr, nullptr, a, ws, czws)
-             : go(residual_kernel<LSSVR_RHS_ARRAY>, gr, tr, nullptr, nullptr, a, ws, czws);
+    e = sine ? launch(residual_kernel<LSSVR_RHS_SIN>, gr, tr, s, nullptr, a, ws, czws)
+             : launch(residual_kernel<LSSVR_RHS_ARRAY>, gr, tr, s, nullptr, a, ws, czws);
     if (e != hipSuccess) return e;
-    e = go(solve4_kernel<2>, g2, t2, nullptr, it == steps ? ev1 : nullptr, it == steps ? a : quiet, cws, zws, nxcd);
+    e = launch(solve4_kernel<2>, g2, t2, s, it == steps ? &last : nullptr, it == steps ? a : quiet, cws, zws, nxcd);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

@@ -439,15 +439,13 @@ __global__ __launch_bounds__(64 * kWaves, 2) void solve4_parity_kernel(EnhanceAr
 // hold); in between, the full four-systems-per-wave solve runs (enhance_large_cheb.hip).
 bool enhance_parity_applies(int M, int n) { return M > kSmallMaxM && M <= kLargeMaxM && n >= 2 * (M - 2); }
 
-hipError_t launch_solve4_parity(const EnhanceArgs& a, const double* ws, hipStream_t s, hipEvent_t ev_stop) {
+hipError_t launch_solve4_parity(const EnhanceArgs& a, const double* ws, hipStream_t s, const LaunchOpts* o) {
   if (a.a_values || !ws) return hipErrorInvalidValue;
   int64_t blocks = (a.ne + 4 * kWaves - 1) / (4 * kWaves);
   const int64_t resident = (int64_t)cu_count() * kResidentPerCu;       // persistent: one resident set
   if (blocks > resident) blocks = resident;
   const dim3 grid((unsigned)blocks), block(64 * kWaves);
-  if (ev_stop) hipExtLaunchKernelGGL(solve4_parity_kernel, grid, block, 0, s, nullptr, ev_stop, 0, a, ws);
-  else hipLaunchKernelGGL(solve4_parity_kernel, grid, block, 0, s, a, ws);
-  return hipGetLastError();
+  return launch(solve4_parity_kernel, grid, block, s, o, a, ws);
 }
 
 }  // namespace lssvr

@@ -51,8 +51,8 @@ struct EnhanceArgs {
   TrigTables trig;          // sin / cos polynomial coefficients (SGPR operands), set by capi.hip
 };
 
-// Optional per-launch profiling: when both events are set the kernel goes through
-// hipExtLaunchKernelGGL, which stamps them with the dispatch's own begin/end times.
+// Optional per-launch profiling: a kernel with an event attached (start, stop, or both; either may be
+// NULL) goes through hipExtLaunchKernelGGL, which stamps them with the dispatch's own begin/end times.
 struct LaunchOpts {
   hipEvent_t start = nullptr;
   hipEvent_t stop = nullptr;
@@ -61,7 +61,7 @@ struct LaunchOpts {
 template <typename K, typename... Args>
 inline hipError_t launch(K kernel, dim3 grid, dim3 block, hipStream_t s, const LaunchOpts* o,
                          Args... args) {
-  if (o && o->start && o->stop)
+  if (o && (o->start || o->stop))
     hipExtLaunchKernelGGL(kernel, grid, block, 0, s, o->start, o->stop, 0, args...);
   else
     hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
@@ -110,7 +110,7 @@ hipError_t enhance_large_split(const EnhanceArgs& a, void* work, hipStream_t s, 
 // the well-posed regime (n >= 2 (M-2)) of the two-kernel path: parity-split solve (enhance_large_parity.hip)
 constexpr int kMomentWsStride = 96;   // workspace doubles per element: m_0..m_60, a, b, g_l, r_0..r_30, g_r
 bool enhance_parity_applies(int M, int n);
-hipError_t launch_solve4_parity(const EnhanceArgs& a, const double* ws, hipStream_t s, hipEvent_t ev_stop);
+hipError_t launch_solve4_parity(const EnhanceArgs& a, const double* ws, hipStream_t s, const LaunchOpts* o);
 hipError_t enhance_dual(const EnhanceArgs& a, hipStream_t s, const LaunchOpts* o = nullptr);
 constexpr int kSharedMaxM = 33;  // shared-operator path (uniform meshes): coefficients in VGPRs
 hipError_t enhance_shared(const EnhanceArgs& a, const double* op, hipStream_t s,

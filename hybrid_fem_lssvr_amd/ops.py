@@ -7,10 +7,12 @@ raises otherwise -- there is no CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import threading
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -40,8 +42,63 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _check_buffers(ne, M, n_colloc, x, *, out=None, status=None, fail_count=None, rhs_values=None,
-                   n_rhs_rows=None):
+def _shard(x, u, elem_offset, ne_global):
+    """(ne, ne_global) of the shard (x, u): float64[ne+1] device tensors of one length; ``ne_global``
+    defaults to the shard's end."""
+    _dev(x, "x")
+    _dev(u, "u")
+    if x.numel() != u.numel() or x.dim() != 1:
+        raise ValueError("x and u must be 1-D with equal length ne+1")
+    ne = x.numel() - 1
+    return ne, (elem_offset + ne if ne_global is None else ne_global)
+
+
+def _rhs(rhs, values, count, what, point_major=False, name="rhs_values"):
+    """(rhs_id, params) of a right-hand side: ``rhs`` = (amp, omega) evaluated in-kernel, or the table
+    ``values`` of ``count`` (= ``what``) doubles, element-major or ``point_major``."""
+    if values is None:
+        return RHS_SIN, _capi.rhs_params(*rhs)
+    _dev(values, name)
+    if values.numel() != count:
+        raise ValueError(f"{name} must hold {what} = {count} doubles, got {values.numel()}")
+    return (RHS_ARRAY_PM if point_major else RHS_ARRAY), None
+
+
+def _bands(x, ne, bands=None, local=False):
+    """P1 bands {diag[ne+1], off[ne], load[ne+1]} (+ kloc[ne], floc[ne, 2] with ``local``), allocated
+    when not given; a caller's bands become raw device pointers, so they are checked."""
+    if not bands:
+        shapes = {"diag": ne + 1, "off": ne, "load": ne + 1}
+        if local:
+            shapes.update(kloc=ne, floc=(ne, 2))
+        return {k: torch.empty(s, dtype=torch.float64, device=x.device) for k, s in shapes.items()}
+    for k, cnt in (("diag", ne + 1), ("off", ne), ("load", ne + 1)):
+        _dev(bands[k], k)
+        if bands[k].numel() != cnt:
+            raise ValueError(f"bands[{k!r}] must hold {cnt} doubles")
+    return bands
+
+
+def _timed(lib, name, args, repeats=None):
+    """The ``profiled`` convention: ``name(*args, kernel_ms_host)`` BLOCKING -> the launch duration in
+    seconds; ``repeats=k``: ``name_sequence(*args, k, kernel_ms_host)`` -> the list of k durations."""
+    if repeats is not None:
+        arr = (ctypes.c_float * int(repeats))()
+        _capi.check(getattr(lib, name + "_sequence")(*args, int(repeats), arr), name + "_sequence")
+        return [v * 1e-3 for v in arr]
+    ms = ctypes.c_float(0.0)
+    _capi.check(getattr(lib, name)(*args, ctypes.byref(ms)), name + "(profiled)")
+    return ms.value * 1e-3
+
+
+def _check_fail_count(fail_count):
+    if fail_count is not None:
+        _dev(fail_count, "fail_count", torch.int32)
+        if fail_count.numel() < 1:
+            raise ValueError("fail_count must hold one int32")
+
+
+def _check_buffers(ne, M, n_colloc, x, *, out=None, status=None, fail_count=None):
     """Caller-supplied buffers become raw device pointers: a wrong-sized tensor would be an
     out-of-bounds device access, so sizes are checked here.  Returns (out, status), allocated
     when not given."""
@@ -57,16 +114,7 @@ def _check_buffers(ne, M, n_colloc, x, *, out=None, status=None, fail_count=None
         _dev(status, "status", torch.int32)
         if status.numel() != ne:
             raise ValueError(f"status must hold ne = {ne} int32, got {status.numel()}")
-    if fail_count is not None:
-        _dev(fail_count, "fail_count", torch.int32)
-        if fail_count.numel() < 1:
-            raise ValueError("fail_count must hold one int32")
-    if rhs_values is not None:
-        _dev(rhs_values, "rhs_values")
-        rows = ne if n_rhs_rows is None else n_rhs_rows
-        if rhs_values.numel() != rows * n_colloc:
-            raise ValueError(f"rhs_values must hold {rows}*n_colloc = {rows * n_colloc} doubles, "
-                             f"got {rhs_values.numel()}")
+    _check_fail_count(fail_count)
     return out, status
 
 
@@ -150,7 +198,6 @@ def release_workspaces():
 def _work_arg(work, lib, x, ne, M, n_colloc, solver, stream):
     """(context manager yielding the workspace tensor or None) for the ``work=`` convention of the wrappers:
     None = the shared per-device buffer, False = no workspace, a tensor = the caller's own."""
-    import contextlib
     if work is None:
         return workspace(lib, x.device, ne, M, n_colloc, solver, stream)
     if work is False:
@@ -177,27 +224,17 @@ def enhance(x, u, M, gamma, n_colloc=12, *, rhs=(POISSON_AMP, POISSON_OMEGA), rh
     ``work`` must not be shared by launches that can run concurrently.
     """
     lib = _capi.load()
-    _dev(x, "x")
-    _dev(u, "u")
-    if x.numel() != u.numel() or x.dim() != 1:
-        raise ValueError("x and u must be 1-D with equal length ne+1")
-    ne = x.numel() - 1
+    ne, ne_global = _shard(x, u, elem_offset, ne_global)
     if ne < 0:
         raise ValueError("need at least one node")
-    if ne_global is None:
-        ne_global = elem_offset + ne
     if global_domain is None:
         if ne == 0:
             global_domain = (0.0, 0.0)
         else:
             ends = torch.stack([x[0], x[-1]]).cpu()
             global_domain = (float(ends[0]), float(ends[1]))
-    out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count,
-                                 rhs_values=rhs_values)
-    if rhs_values is not None:
-        rhs_id, params = (RHS_ARRAY_PM if point_major else RHS_ARRAY), None
-    else:
-        rhs_id, params = RHS_SIN, _capi.rhs_params(*rhs)
+    out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
+    rhs_id, params = _rhs(rhs, rhs_values, ne * n_colloc, "ne*n_colloc", point_major)
     with _work_arg(work, lib, x, ne, M, n_colloc, solver, stream) as wk:
         rc = lib.lssvr_enhance_ws(_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
                                   float(global_domain[0]), float(global_domain[1]),
@@ -220,10 +257,8 @@ def enhance_subset(x, u, M, gamma, n_colloc, W, *, elem_ids=None, gamma_values=N
     :func:`enhance` (above M = 22 the group runs as the moment / solve kernel pair; ``False``: the
     single f64-MFMA kernel)."""
     lib = _capi.load()
-    _dev(x, "x")
-    _dev(u, "u")
+    ne, ne_global = _shard(x, u, elem_offset, ne_global)
     _dev(W, "W")
-    ne = x.numel() - 1
     if W.dim() != 2 or W.shape[0] != ne or W.shape[1] < M or not W.is_contiguous():
         raise ValueError("W must be a contiguous float64[ne, ldw >= M] tensor")
     if elem_ids is not None:
@@ -239,17 +274,9 @@ def enhance_subset(x, u, M, gamma, n_colloc, W, *, elem_ids=None, gamma_values=N
         _dev(status, "status", torch.int32)
         if status.numel() != ne:
             raise ValueError("status is indexed by mesh element: int32[ne]")
-    if fail_count is not None:
-        _dev(fail_count, "fail_count", torch.int32)
-    if ne_global is None:
-        ne_global = elem_offset + ne
-    if rhs_values is not None:
-        _dev(rhs_values, "rhs_values")
-        if rhs_values.numel() != nsub * n_colloc:
-            raise ValueError("rhs_values must hold nsub*n_colloc doubles (indexed by position in elem_ids)")
-        rhs_id, params = (RHS_ARRAY_PM if point_major else RHS_ARRAY), None
-    else:
-        rhs_id, params = RHS_SIN, _capi.rhs_params(*rhs)
+    _check_fail_count(fail_count)
+    # (rows indexed by position in elem_ids)
+    rhs_id, params = _rhs(rhs, rhs_values, nsub * n_colloc, "nsub*n_colloc", point_major)
     with _work_arg(work, lib, x, nsub, M, n_colloc, SOLVER_PRIMAL, stream) as wk:
         rc = lib.lssvr_enhance_subset_ws(_ptr(x), _ptr(u), ne, _ptr(elem_ids), int(nsub), int(elem_offset),
                                          int(ne_global), float(global_domain[0]), float(global_domain[1]),
@@ -293,34 +320,19 @@ def enhance_shared(x, u, op, M, n_colloc, *, rhs=(POISSON_AMP, POISSON_OMEGA), r
                    fail_count=None, stream=None, profiled=False, point_major=False):
     """``lssvr_enhance_shared`` (uniform meshes; the caller vouches for uniformity).  Returns
     (W, status), or the kernel duration in seconds when ``profiled``."""
-    import ctypes
     lib = _capi.load()
-    _dev(x, "x")
-    _dev(u, "u")
+    ne, ne_global = _shard(x, u, elem_offset, ne_global)
     _dev(op, "op")
-    ne = x.numel() - 1
-    if x.numel() != u.numel() or x.dim() != 1:
-        raise ValueError("x and u must be 1-D with equal length ne+1")
     if op.dim() != 2 or op.shape[0] != n_colloc + 2 or op.shape[1] != M or not op.is_contiguous():
         raise ValueError("op must be a contiguous float64[(n_colloc+2), M] tensor")
-    if ne_global is None:
-        ne_global = elem_offset + ne
-    out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count,
-                                 rhs_values=rhs_values)
-    if rhs_values is not None:
-        rhs_id, params = (RHS_ARRAY_PM if point_major else RHS_ARRAY), None
-    else:
-        rhs_id, params = RHS_SIN, _capi.rhs_params(*rhs)
-    ms = ctypes.c_float(0.0)
-    rc = lib.lssvr_enhance_shared(_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                                  float(global_domain[0]), float(global_domain[1]),
-                                  float(bc[0]), float(bc[1]), int(M), int(n_colloc),
-                                  rhs_id, params, _ptr(rhs_values), _ptr(op),
-                                  _ptr(out), _ptr(status), _ptr(fail_count), _stream(stream),
-                                  ctypes.byref(ms) if profiled else None)
-    _capi.check(rc, "lssvr_enhance_shared")
+    out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
+    rhs_id, params = _rhs(rhs, rhs_values, ne * n_colloc, "ne*n_colloc", point_major)
+    args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]), float(global_domain[1]),
+            float(bc[0]), float(bc[1]), int(M), int(n_colloc), rhs_id, params, _ptr(rhs_values), _ptr(op),
+            _ptr(out), _ptr(status), _ptr(fail_count), _stream(stream))
     if profiled:
-        return ms.value * 1e-3
+        return _timed(lib, "lssvr_enhance_shared", args)
+    _capi.check(lib.lssvr_enhance_shared(*args, None), "lssvr_enhance_shared")
     return out, status
 
 
@@ -332,51 +344,20 @@ def enhance_profiled(x, u, M, gamma, n_colloc=12, *, rhs=(POISSON_AMP, POISSON_O
     two-kernel path above M = 22 the duration of the pair, gap included).  ``repeats=k``: k launches
     back to back, one synchronisation at the end (``lssvr_enhance_ws_sequence``): the list of the k
     durations inside a running sequence instead of one duration in isolation."""
-    import ctypes
     lib = _capi.load()
-    _dev(x, "x")
-    _dev(u, "u")
-    ne = x.numel() - 1
-    if x.numel() != u.numel() or x.dim() != 1:
-        raise ValueError("x and u must be 1-D with equal length ne+1")
-    if ne_global is None:
-        ne_global = elem_offset + ne
+    ne, ne_global = _shard(x, u, elem_offset, ne_global)
     out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status)
-    ms = ctypes.c_float(0.0)
     with _work_arg(work, lib, x, ne, M, n_colloc, solver, stream) as wk:
-        return _enhance_profiled(lib, x, u, ne, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma, rhs,
-                                 solver, out, status, wk, stream, repeats, ms)
-
-
-def _enhance_profiled(lib, x, u, ne, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma, rhs, solver,
-                      out, status, work, stream, repeats, ms):
-    import ctypes
-    if repeats is not None:
-        arr = (ctypes.c_float * int(repeats))()
-        rc = lib.lssvr_enhance_ws_sequence(_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                                           float(global_domain[0]), float(global_domain[1]),
-                                           float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
-                                           RHS_SIN, _capi.rhs_params(*rhs), None, int(solver),
-                                           _ptr(out), _ptr(status), None,
-                                           _ptr(work), 0 if work is None else work.numel() * 8, _stream(stream),
-                                           int(repeats), arr)
-        _capi.check(rc, "lssvr_enhance_ws_sequence")
-        return [v * 1e-3 for v in arr]
-    rc = lib.lssvr_enhance_ws(_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                              float(global_domain[0]), float(global_domain[1]),
-                              float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
-                              RHS_SIN, _capi.rhs_params(*rhs), None, int(solver),
-                              _ptr(out), _ptr(status), None,
-                              _ptr(work), 0 if work is None else work.numel() * 8, _stream(stream),
-                              ctypes.byref(ms))
-    _capi.check(rc, "lssvr_enhance_ws(profiled)")
-    return ms.value * 1e-3
+        args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]),
+                float(global_domain[1]), float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
+                RHS_SIN, _capi.rhs_params(*rhs), None, int(solver), _ptr(out), _ptr(status), None,
+                _ptr(wk), 0 if wk is None else wk.numel() * 8, _stream(stream))
+        return _timed(lib, "lssvr_enhance_ws", args, repeats)
 
 
 def _bind(lib, name, args):
     """(bound foreign function, arguments pre-converted to the ctypes of its signature): a plan is launched many
     times, and converting ~20 Python values per call is a third of the host's ~7 us per launch of an ~8 us step."""
-    import ctypes
     argtypes = _capi.SIGNATURES[name][1]
     ready = (ctypes.Array, ctypes._SimpleCData, ctypes._Pointer, type(ctypes.byref(ctypes.c_int())))
     conv = tuple(a if (a is None or isinstance(a, ready)) else tp(a) for tp, a in zip(argtypes, args))
@@ -392,23 +373,8 @@ class StepPlan:
                  elem_offset=0, ne_global=None, global_domain, bc=(0.0, 0.0), bands=None,
                  out=None, status=None, fail_count=None):
         self.lib = _capi.load()
-        _dev(x, "x")
-        _dev(u, "u")
-        ne = x.numel() - 1
-        dev = x.device
-        if ne_global is None:
-            ne_global = elem_offset + ne
-        self.bands = bands or {
-            "diag": torch.empty(ne + 1, dtype=torch.float64, device=dev),
-            "off": torch.empty(ne, dtype=torch.float64, device=dev),
-            "load": torch.empty(ne + 1, dtype=torch.float64, device=dev),
-        }
-        if x.numel() != u.numel() or x.dim() != 1:
-            raise ValueError("x and u must be 1-D with equal length ne+1")
-        for k, cnt in (("diag", ne + 1), ("off", ne), ("load", ne + 1)):
-            _dev(self.bands[k], k)
-            if self.bands[k].numel() != cnt:
-                raise ValueError(f"bands[{k!r}] must hold {cnt} doubles")
+        ne, ne_global = _shard(x, u, elem_offset, ne_global)
+        self.bands = _bands(x, ne, bands)
         self.W, self.status = _check_buffers(ne, M, n_colloc, x, out=out, status=status,
                                              fail_count=fail_count)
         self.fail_count = fail_count
@@ -416,7 +382,7 @@ class StepPlan:
         # with a workspace the enhancement runs as the faster moment / solve pair: three launches
         # (a private buffer: plans may run concurrently on different streams)
         nb = int(self.lib.lssvr_enhance_work_bytes(ne, int(M), int(n_colloc), SOLVER_PRIMAL))
-        self._work = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev) if nb > 0 else None
+        self._work = torch.empty((nb + 7) // 8, dtype=torch.float64, device=x.device) if nb > 0 else None
         self._keep = (x, u, _capi.rhs_params(*rhs))
         self._args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
                       float(global_domain[0]), float(global_domain[1]), float(bc[0]), float(bc[1]),
@@ -427,7 +393,6 @@ class StepPlan:
         # the library's own plan (lssvr_step_plan_*): the 20 arguments validated and bound once on the C side, a
         # launch is a two-argument call (host cost 4.4 -> ~2 us per launch; with the stream handle passed in, since
         # torch.cuda.current_stream() alone costs 3 us)
-        import ctypes
         self._handle = ctypes.c_void_p()
         create, cargs = _bind(self.lib, "lssvr_step_plan_create", (ctypes.byref(self._handle),) + self._args)
         rc = create(*cargs)
@@ -477,43 +442,23 @@ def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *
     ``repeats=k`` the list of the durations of k launches back to back, one synchronisation at the end.
     ``point_major``: the three tables are float64[n_colloc, ne] (``t[k, e]``) instead of
     float64[ne, n_colloc] -- see :func:`colloc_points`; the fast layout for M <= 22."""
-    import ctypes
     lib = _capi.load()
-    _dev(x, "x")
-    _dev(u, "u")
-    ne = x.numel() - 1
+    ne, ne_global = _shard(x, u, elem_offset, ne_global)
     for t, nm in ((a_values, "a_values"), (da_values, "da_values"), (rhs_values, "rhs_values")):
         _dev(t, nm)
         if t.numel() != ne * n_colloc:
             raise ValueError(f"{nm} must hold ne*n_colloc doubles")
-    if ne_global is None:
-        ne_global = elem_offset + ne
     if global_domain is None:
         ends = torch.stack([x[0], x[-1]]).cpu()
         global_domain = (float(ends[0]), float(ends[1]))
-    if x.numel() != u.numel() or x.dim() != 1:
-        raise ValueError("x and u must be 1-D with equal length ne+1")
     out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
-    ms = ctypes.c_float(0.0)
-    if profiled and repeats is not None:
-        arr = (ctypes.c_float * int(repeats))()
-        rc = lib.lssvr_enhance_varcoef_ws_sequence(
-            _ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]), float(global_domain[1]),
+    args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]), float(global_domain[1]),
             float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma), _ptr(a_values), _ptr(da_values),
             _ptr(rhs_values), TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, _ptr(out), _ptr(status),
-            _ptr(fail_count), None, 0, _stream(stream), int(repeats), arr)
-        _capi.check(rc, "lssvr_enhance_varcoef_ws_sequence")
-        return [v * 1e-3 for v in arr]
-    rc = lib.lssvr_enhance_varcoef_ws(_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                                      float(global_domain[0]), float(global_domain[1]),
-                                      float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
-                                      _ptr(a_values), _ptr(da_values), _ptr(rhs_values),
-                                      TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR,
-                                      _ptr(out), _ptr(status), _ptr(fail_count), None, 0,
-                                      _stream(stream), ctypes.byref(ms) if profiled else None)
-    _capi.check(rc, "lssvr_enhance_varcoef_ws")
+            _ptr(fail_count), None, 0, _stream(stream))
     if profiled:
-        return ms.value * 1e-3
+        return _timed(lib, "lssvr_enhance_varcoef_ws", args, repeats)
+    _capi.check(lib.lssvr_enhance_varcoef_ws(*args, None), "lssvr_enhance_varcoef_ws")
     return out, status
 
 
@@ -554,29 +499,14 @@ class StepPlanVarcoef:
                  nquad=2, point_major=False, elem_offset=0, ne_global=None, global_domain, bc=(0.0, 0.0),
                  bands=None, out=None, status=None, fail_count=None):
         self.lib = _capi.load()
-        _dev(x, "x")
-        _dev(u, "u")
-        ne = x.numel() - 1
-        dev = x.device
-        if x.numel() != u.numel() or x.dim() != 1:
-            raise ValueError("x and u must be 1-D with equal length ne+1")
+        ne, ne_global = _shard(x, u, elem_offset, ne_global)
         for t, nm, cnt in ((a_values, "a_values", ne * n_colloc), (da_values, "da_values", ne * n_colloc),
                            (rhs_values, "rhs_values", ne * n_colloc), (rhs_quad, "rhs_quad", ne * nquad),
                            (a_quad, "a_quad", ne * nquad)):
             _dev(t, nm)
             if t.numel() != cnt:
                 raise ValueError(f"{nm} must hold {cnt} doubles")
-        if ne_global is None:
-            ne_global = elem_offset + ne
-        self.bands = bands or {
-            "diag": torch.empty(ne + 1, dtype=torch.float64, device=dev),
-            "off": torch.empty(ne, dtype=torch.float64, device=dev),
-            "load": torch.empty(ne + 1, dtype=torch.float64, device=dev),
-        }
-        for k, cnt in (("diag", ne + 1), ("off", ne), ("load", ne + 1)):
-            _dev(self.bands[k], k)
-            if self.bands[k].numel() != cnt:
-                raise ValueError(f"bands[{k!r}] must hold {cnt} doubles")
+        self.bands = _bands(x, ne, bands)
         self.W, self.status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
         self._keep = (x, u, a_values, da_values, rhs_values, rhs_quad, a_quad, fail_count)
         self._args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
@@ -630,23 +560,8 @@ def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, 
     lib = _capi.load()
     _dev(x, "x")
     ne = x.numel() - 1
-    dev = x.device
-    if out is None:
-        out = {
-            "diag": torch.empty(ne + 1, dtype=torch.float64, device=dev),
-            "off": torch.empty(ne, dtype=torch.float64, device=dev),
-            "load": torch.empty(ne + 1, dtype=torch.float64, device=dev),
-        }
-        if want_local:
-            out["kloc"] = torch.empty(ne, dtype=torch.float64, device=dev)
-            out["floc"] = torch.empty((ne, 2), dtype=torch.float64, device=dev)
-    if rhs_quad is not None:
-        _dev(rhs_quad, "rhs_quad")
-        if rhs_quad.numel() != ne * nquad:
-            raise ValueError("rhs_quad must hold ne*nquad doubles")
-        rhs_id, params = RHS_ARRAY, None
-    else:
-        rhs_id, params = RHS_SIN, _capi.rhs_params(*rhs)
+    out = _bands(x, ne, out, want_local)
+    rhs_id, params = _rhs(rhs, rhs_quad, ne * nquad, "ne*nquad", name="rhs_quad")
     if a_quad is not None:
         _dev(a_quad, "a_quad")
     rc = lib.lssvr_p1_assemble(_ptr(x), ne, int(nquad), rhs_id, params, _ptr(rhs_quad),
@@ -789,7 +704,6 @@ def eval_error(x, W, xq, *, exact=(1.0, math.pi), out=None, stream=None):
 
 def gauss_rule(nq):
     """Gauss-Legendre nodes (ascending) and weights on [-1, 1] (host; ``lssvr_gauss_rule``)."""
-    import numpy as np
     lib = _capi.load()
     xi = (ctypes.c_double * max(int(nq), 1))()
     wt = (ctypes.c_double * max(int(nq), 1))()
@@ -836,13 +750,7 @@ def estimate(x, W, nq, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_values=None, poi
     ne = x.numel() - 1
     if W.dim() != 2 or W.shape[0] != ne:
         raise ValueError("W must be [ne, M]")
-    if rhs_values is not None:
-        _dev(rhs_values, "rhs_values")
-        if rhs_values.numel() != ne * int(nq):
-            raise ValueError(f"rhs_values must hold ne*nq = {ne * int(nq)} doubles")
-        rhs_id, params = (RHS_ARRAY_PM if point_major else RHS_ARRAY), None
-    else:
-        rhs_id, params = RHS_SIN, _capi.rhs_params(*rhs)
+    rhs_id, params = _rhs(rhs, rhs_values, ne * int(nq), "ne*nq", point_major)
     eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
     jump = torch.empty(ne + 1, dtype=torch.float64, device=x.device) if want_jump else None
     out3 = torch.empty(3, dtype=torch.float64, device=x.device)

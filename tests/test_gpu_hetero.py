@@ -109,6 +109,18 @@ def test_subset_argument_errors(dev):
         ops.enhance_subset(x, u, 12, 1e4, 5, W, global_domain=(nodes[0], nodes[-1]))    # n < M-2
 
 
+def test_subset_rejects_short_u(dev):
+    """u one node short of x: the kernels would read u[ne] out of bounds, so the wrapper rejects it."""
+    import torch
+    from hybrid_fem_lssvr_amd import ops
+    _, nodes, values = _mesh(20, 14)
+    x = torch.as_tensor(nodes, device=dev)
+    u = torch.as_tensor(values[:-1], device=dev)
+    W = torch.zeros((20, 9), dtype=torch.float64, device=dev)
+    with pytest.raises(ValueError):
+        ops.enhance_subset(x, u, 9, 1e4, 16, W, global_domain=(nodes[0], nodes[-1]))
+
+
 def test_subset_out_of_range_ids_touch_nothing(dev):
     """An id outside [0, ne_mesh) must not become an out-of-bounds access: the element is
     skipped (no load, no store) and counted in fail_count; valid ids of the same launch are
