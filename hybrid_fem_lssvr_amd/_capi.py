@@ -16,7 +16,7 @@ IN_TREE_LIB = os.path.join(_HERE, "csrc", "liblssvr_hip.so")
 # test suite and the benchmark always exercise the one in-tree library.
 LIB_PATH = os.environ.get("LSSVR_HIP_LIB") or IN_TREE_LIB
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 RHS_ARRAY = 0
 RHS_SIN = 1
@@ -129,6 +129,8 @@ SIGNATURES = {
     "lssvr_adapt_work_bytes": (_c_i64, [_c_i64]),
     "lssvr_estimate": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_int, C.POINTER(_c_dbl), _c_dp,
                                 _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "lssvr_estimate_varcoef": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_dp, _c_dp, _c_int, _c_dp,
+                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "lssvr_refine": (_c_int, [_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "lssvr_fp64_probe": (_c_int, [_c_dp, _c_int, _c_int, _c_int, _c_dp]),
     "lssvr_stream_probe": (_c_int, [_c_dp, _c_dp, _c_i64, _c_dp]),

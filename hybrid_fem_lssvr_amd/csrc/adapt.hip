@@ -3,6 +3,7 @@
 //   - derivatives of the enhanced solution at query points (lssvr_eval_deriv)
 //   - per-element residual indicator  eta_e^2 = h_e^2 ||f + u_e''||_e^2 + h_e/2 (J_e^2 + J_{e+1}^2)
 //     with J_i = u_{i-1}'(x_i) - u_i'(x_i) (lssvr_estimate) and its deterministic reduction
+//   - the same for -(a u')' = f: residual f + a u'' + a' u', J_i the jump of the flux a u' (lssvr_estimate_varcoef)
 //   - threshold marking + bisection into a new ascending node array (lssvr_refine)
 // DESIGN.md section 11 has the derivation, the mapping and the measured numbers.
 #include <cmath>
@@ -142,6 +143,47 @@ __device__ __forceinline__ void load_row_global(const double* __restrict__ W, in
                                                 double (&c)[MT]) {
 #pragma unroll
   for (int k = 0; k < MT; ++k) c[k] = k < M ? W[e * M + k] : 0.0;
+}
+
+// stage_rows and reduce_partials restate the W staging and the reduction of estimate_kernel for
+// estimate_vc_kernel; estimate_kernel keeps its inline copy (routed through them, its code is scheduled differently).
+//
+// the chunk's contiguous `total` = nrow*M doubles of W from `src` (coalesced) into LDS rows of odd stride ms;
+// column stepping: i += kEstBlock  ->  (row, col) += (qM, rM)
+__device__ __forceinline__ void stage_rows(double* __restrict__ rows, const double* __restrict__ src, int total,
+                                           int M, int ms, int qM, int rM, int tid) {
+  int r = tid / M, col = tid - (tid / M) * M;
+  for (int i = tid; i < total; i += kEstBlock) {
+    rows[r * ms + col] = src[i];
+    r += qM;
+    col += rM;
+    if (col >= M) {
+      col -= M;
+      ++r;
+    }
+  }
+}
+
+// workgroup tree of the per-lane {sum, max, non-finite count} -> work[3*blockIdx.x ..]
+__device__ __forceinline__ void reduce_partials(double* __restrict__ red, int tid, double bsum, double bmax,
+                                                double bcnt, double* __restrict__ work) {
+  red[tid] = bsum;
+  red[kEstBlock + tid] = bmax;
+  red[2 * kEstBlock + tid] = bcnt;
+  __syncthreads();
+  for (int off = kEstBlock / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+      red[tid] += red[tid + off];
+      red[kEstBlock + tid] = fmax(red[kEstBlock + tid], red[kEstBlock + tid + off]);
+      red[2 * kEstBlock + tid] += red[2 * kEstBlock + tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    work[3 * blockIdx.x + 0] = red[0];
+    work[3 * blockIdx.x + 1] = red[kEstBlock];
+    work[3 * blockIdx.x + 2] = red[2 * kEstBlock];
+  }
 }
 
 // RHS: 0 = LSSVR_RHS_ARRAY (rhs[e*nq + q]), 1 = LSSVR_RHS_SIN, 2 = LSSVR_RHS_ARRAY_PM (rhs[q*ne + e])
@@ -294,6 +336,137 @@ __global__ __launch_bounds__(kEstBlock) void estimate_kernel(EstimateArgs p, Gau
     p.work[3 * blockIdx.x + 1] = red[kEstBlock];
     p.work[3 * blockIdx.x + 2] = red[2 * kEstBlock];
   }
+}
+
+// Variable coefficients, -(a u')' = f: residual f + a u'' + a' u' and the jump of the flux a u',
+//   J_e = aR_{e-1} u_{e-1}'(x_e) - aL_e u_e'(x_e)   (a_ends[2e] = aL_e, a_ends[2e+1] = aR_e).
+// The structure of estimate_kernel: a lane per element, W staged through LDS, the neighbours' end fluxes from
+// LDS and recomputed from HBM only at chunk edges (the same products of the same values: bit-identical).
+// PM: the a, a', f tables are point-major t[q*ne + e], else element-major t[e*nq + q].
+// Dynamic LDS: T[nq*MT] pairs {P_k'(xi_q), P_k''(xi_q)} | wt[nq] | rows[kEstBlock*ms] | fl[kEstBlock] |
+// fr[kEstBlock] | red[3*kEstBlock].
+template <int MT, bool PM>
+__global__ __launch_bounds__(kEstBlock) void estimate_vc_kernel(EstimateVcArgs p, GaussRuleN g) {
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x;
+  const int nq = p.nq, M = p.M, ms = p.ms;
+  const int64_t ne = p.ne;
+  double* T = lds;
+  double* swt = T + 2 * nq * MT;
+  double* rows = swt + nq;
+  double* sfl = rows + kEstBlock * ms;
+  double* sfr = sfl + kEstBlock;
+  double* red = sfr + kEstBlock;
+  if (tid < nq) {
+    const double t = g.xi[tid];
+    double* Tq = T + 2 * tid * MT;
+    swt[tid] = g.wt[tid];
+    double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
+    Tq[0] = 0.0;
+    Tq[1] = 0.0;
+    if (MT > 1) {
+      Tq[2] = M > 1 ? 1.0 : 0.0;
+      Tq[3] = 0.0;
+    }
+    for (int k = 1; k + 1 < MT; ++k) {
+      const double a = (double)(2 * k + 1);
+      const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
+      const double d2 = d0 + a * p1;
+      const double s2 = s0 + a * d1;
+      Tq[2 * (k + 1)] = k + 1 < M ? d2 : 0.0;
+      Tq[2 * (k + 1) + 1] = k + 1 < M ? s2 : 0.0;
+      p0 = p1; p1 = p2;
+      d0 = d1; d1 = d2;
+      s0 = s1; s1 = s2;
+    }
+  }
+  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
+  double bsum = 0.0, bmax = 0.0, bcnt = 0.0;
+  for (int64_t c0 = (int64_t)blockIdx.x * kEstBlock; c0 < ne; c0 += (int64_t)gridDim.x * kEstBlock) {
+    const int nrow = (int)(ne - c0 < kEstBlock ? ne - c0 : kEstBlock);
+    stage_rows(rows, p.W + c0 * M, nrow * M, M, ms, qM, rM, tid);
+    __syncthreads();
+    const int64_t e = c0 + tid;
+    const bool valid = tid < nrow;
+    double c[MT];
+#pragma unroll
+    for (int k = 0; k < MT; ++k) c[k] = (valid && k < M) ? rows[tid * ms + k] : 0.0;
+    double xa = 0.0, xb = 1.0, aL = 0.0, aR = 0.0;
+    if (valid) {
+      xa = p.x[e];
+      xb = p.x[e + 1];
+      aL = p.a_ends[2 * e];
+      aR = p.a_ends[2 * e + 1];
+    }
+    const DomainMap dm = map_params(xa, xb);
+    double dl, dr;
+    end_derivs<MT>(c, dm.scl, dl, dr);
+    const double fl = aL * dl, fr = aR * dr;
+    sfl[tid] = fl;
+    sfr[tid] = fr;
+    __syncthreads();
+    if (valid) {
+      double fr_prev = 0.0, fl_next = 0.0;
+      if (e > 0) {
+        if (tid > 0) {
+          fr_prev = sfr[tid - 1];
+        } else {
+          double cn[MT];
+          load_row_global<MT>(p.W, e - 1, M, cn);
+          const DomainMap dn = map_params(p.x[e - 1], xa);
+          double l, r;
+          end_derivs<MT>(cn, dn.scl, l, r);
+          fr_prev = p.a_ends[2 * e - 1] * r;
+        }
+      }
+      if (e + 1 < ne) {
+        if (tid + 1 < nrow) {
+          fl_next = sfl[tid + 1];
+        } else {
+          double cn[MT];
+          load_row_global<MT>(p.W, e + 1, M, cn);
+          const DomainMap dn = map_params(xb, p.x[e + 2]);
+          double l, r;
+          end_derivs<MT>(cn, dn.scl, l, r);
+          fl_next = p.a_ends[2 * e + 2] * l;
+        }
+      }
+      const double jl = e > 0 ? fr_prev - fl : 0.0;
+      const double jr = e + 1 < ne ? fr - fl_next : 0.0;
+      // interior residual f + a u'' + a' u' at the nq Gauss points
+      const double scl2 = dm.scl * dm.scl;
+      double acc = 0.0;
+#pragma unroll 1
+      for (int q = 0; q < nq; ++q) {
+        const double* Tq = T + 2 * q * MT;
+        double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+        for (int k = 1; k < MT; ++k) {
+          s1 = fma(c[k], Tq[2 * k], s1);
+          s2 = fma(c[k], Tq[2 * k + 1], s2);
+        }
+        const int64_t i = PM ? (int64_t)q * ne + e : e * nq + q;
+        const double r = p.rhs_values[i] + p.a_values[i] * (s2 * scl2) + p.da_values[i] * (s1 * dm.scl);
+        acc = fma(swt[q], r * r, acc);
+      }
+      const double h = dm.oldlen;
+      const double half = 0.5 * h;
+      const double eta2 = (h * h) * (half * acc) + half * (jl * jl + jr * jr);
+      p.eta2[e] = eta2;
+      if (p.jump) {
+        p.jump[e] = jl;
+        if (e + 1 == ne) p.jump[ne] = 0.0;
+      }
+      if (fabs(eta2) < INFINITY) {
+        bsum += eta2;
+        bmax = fmax(bmax, eta2);
+      } else {
+        bcnt += 1.0;
+      }
+    }
+    __syncthreads();      // rows / sfl / sfr are rewritten by the next chunk
+  }
+  reduce_partials(red, tid, bsum, bmax, bcnt, p.work);
 }
 
 // one workgroup: the per-block partials in a fixed order -> out3 (bitwise reproducible)
@@ -473,6 +646,32 @@ hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s) {
   if (MT == 12) err = launch_estimate<12>(a, g, rhs_mode, (unsigned)nb, lds, s);
   else if (MT == 22) err = launch_estimate<22>(a, g, rhs_mode, (unsigned)nb, lds, s);
   else err = launch_estimate<33>(a, g, rhs_mode, (unsigned)nb, lds, s);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
+  return hipGetLastError();
+}
+
+template <int MT>
+static hipError_t launch_estimate_vc(const EstimateVcArgs& a, const GaussRuleN& g, bool point_major, unsigned nb,
+                                     size_t lds, hipStream_t s) {
+  if (point_major)
+    hipLaunchKernelGGL((estimate_vc_kernel<MT, true>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
+  else
+    hipLaunchKernelGGL((estimate_vc_kernel<MT, false>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t estimate_varcoef(EstimateVcArgs a, bool point_major, double* out3, hipStream_t s) {
+  GaussRuleN g{};
+  if (!gauss_rule(a.nq, g.xi, g.wt)) return hipErrorInvalidValue;
+  a.ms = a.M | 1;
+  const int64_t nb = est_blocks(a.ne);
+  const int MT = a.M <= 12 ? 12 : (a.M <= 22 ? 22 : 33);
+  const size_t lds = sizeof(double) * ((size_t)a.nq * (2 * MT + 1) + (size_t)kEstBlock * a.ms + 5 * kEstBlock);
+  hipError_t err;
+  if (MT == 12) err = launch_estimate_vc<12>(a, g, point_major, (unsigned)nb, lds, s);
+  else if (MT == 22) err = launch_estimate_vc<22>(a, g, point_major, (unsigned)nb, lds, s);
+  else err = launch_estimate_vc<33>(a, g, point_major, (unsigned)nb, lds, s);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
   return hipGetLastError();

@@ -91,12 +91,19 @@ int bind_rhs(lssvr::EnhanceArgs& a, int rhs_id, const double* rhs_params_host, c
 }
 
 // the variable-coefficient triple (a, a', f): three tables in one layout
-int bind_varcoef(lssvr::EnhanceArgs& a, const double* a_values, const double* da_values, const double* rhs_values,
-                 int table_layout, bool need_values) {
+int check_varcoef_tables(const double* a_values, const double* da_values, const double* rhs_values,
+                         int table_layout, bool need_values) {
   if (need_values && (!a_values || !da_values || !rhs_values))
     return fail(LSSVR_ERR_NULL, "a_values, da_values and rhs_values must be non-NULL");
   if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
     return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  return LSSVR_OK;
+}
+
+int bind_varcoef(lssvr::EnhanceArgs& a, const double* a_values, const double* da_values, const double* rhs_values,
+                 int table_layout, bool need_values) {
+  const int rc = check_varcoef_tables(a_values, da_values, rhs_values, table_layout, need_values);
+  if (rc != LSSVR_OK) return rc;
   a.a_values = a_values;
   a.da_values = da_values;
   return bind_rhs(a, table_layout == LSSVR_TABLE_POINT_MAJOR ? LSSVR_RHS_ARRAY_PM : LSSVR_RHS_ARRAY, nullptr,
@@ -125,6 +132,26 @@ int bind_p1(lssvr::P1Args& p, const double* x, int64_t ne, int nquad, double* di
   p.diag = diag;
   p.off = off;
   p.load = load;
+  return LSSVR_OK;
+}
+
+// the arguments lssvr_estimate and lssvr_estimate_varcoef share, validated and bound
+int bind_estimate(lssvr::EstimateArgs& a, const double* x, const double* W, int64_t ne, int M, int nq, double* eta2,
+                  double* jump, double* out3, void* work) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
+  if (nq < 1 || nq > lssvr::kAdaptMaxNq)
+    return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
+  if (!x || !W || !eta2 || !out3 || !work) return fail(LSSVR_ERR_NULL, "x, W, eta2, out3, work must be non-NULL");
+  a.x = x;
+  a.W = W;
+  a.ne = ne;
+  a.M = M;
+  a.nq = nq;
+  a.eta2 = eta2;
+  a.jump = jump;
+  a.work = static_cast<double*>(work);
   return LSSVR_OK;
 }
 
@@ -706,21 +733,9 @@ int64_t lssvr_adapt_work_bytes(int64_t ne) { return lssvr::adapt_work_bytes(ne);
 int lssvr_estimate(const double* x, const double* W, int64_t ne, int M, int nq, int rhs_id,
                    const double* rhs_params_host, const double* rhs_values, double* eta2, double* jump,
                    double* out3, void* work, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
-  if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
-  if (nq < 1 || nq > lssvr::kAdaptMaxNq)
-    return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
-  if (!x || !W || !eta2 || !out3 || !work) return fail(LSSVR_ERR_NULL, "x, W, eta2, out3, work must be non-NULL");
   lssvr::EstimateArgs a{};
-  a.x = x;
-  a.W = W;
-  a.ne = ne;
-  a.M = M;
-  a.nq = nq;
-  a.eta2 = eta2;
-  a.jump = jump;
-  a.work = static_cast<double*>(work);
+  const int rc = bind_estimate(a, x, W, ne, M, nq, eta2, jump, out3, work);
+  if (rc != LSSVR_OK) return rc;
   int mode;
   if (rhs_id == LSSVR_RHS_SIN) {
     if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
@@ -735,6 +750,23 @@ int lssvr_estimate(const double* x, const double* W, int64_t ne, int M, int nq, 
     return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
   }
   return check_launch(lssvr::estimate(a, mode, out3, reinterpret_cast<hipStream_t>(stream)), "estimate");
+}
+
+int lssvr_estimate_varcoef(const double* x, const double* W, int64_t ne, int M, int nq, const double* a_values,
+                           const double* da_values, const double* rhs_values, int table_layout, const double* a_ends,
+                           double* eta2, double* jump, double* out3, void* work, void* stream) {
+  lssvr::EstimateVcArgs a{};
+  int rc = bind_estimate(a, x, W, ne, M, nq, eta2, jump, out3, work);
+  if (rc == LSSVR_OK) rc = check_varcoef_tables(a_values, da_values, rhs_values, table_layout, true);
+  if (rc != LSSVR_OK) return rc;
+  if (!a_ends) return fail(LSSVR_ERR_NULL, "a_ends must be non-NULL");
+  a.rhs_values = rhs_values;
+  a.a_values = a_values;
+  a.da_values = da_values;
+  a.a_ends = a_ends;
+  return check_launch(lssvr::estimate_varcoef(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,
+                                              reinterpret_cast<hipStream_t>(stream)),
+                      "estimate_varcoef");
 }
 
 int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev, double theta,

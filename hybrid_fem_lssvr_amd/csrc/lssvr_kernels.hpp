@@ -184,6 +184,13 @@ struct EstimateArgs {
   double* jump;
   double* work;
 };
+// variable coefficients: EstimateArgs with rhs_values = the f table, plus the a and a' tables at the same points
+// (same layout) and a_ends[2*ne] = {a at the left end, a at the right end} of every element, seen from inside it
+struct EstimateVcArgs : EstimateArgs {
+  const double* a_values;
+  const double* da_values;
+  const double* a_ends;
+};
 bool gauss_rule(int nq, double* xi, double* wt);       // host; false: nq outside [1, kAdaptMaxNq]
 int64_t adapt_work_bytes(int64_t ne);
 hipError_t eval_deriv(const double* x, const double* W, int64_t ne, int M, int order, const double* xq,
@@ -191,6 +198,7 @@ hipError_t eval_deriv(const double* x, const double* W, int64_t ne, int M, int o
 hipError_t estimate_points(const double* x, int64_t ne, int nq, double* xq, hipStream_t s);
 // rhs_mode: 0 = table element-major, 1 = amp*sin(omega x) in-kernel, 2 = table point-major
 hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s);
+hipError_t estimate_varcoef(EstimateVcArgs a, bool point_major, double* out3, hipStream_t s);
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                   double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s);
 

@@ -762,6 +762,41 @@ def estimate(x, W, nq, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_values=None, poi
     return eta2, jump, out3
 
 
+def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point_major=False, want_jump=False,
+                     work=None, stream=None):
+    """:func:`estimate` for -(a u')' = f (``lssvr_estimate_varcoef``):
+    eta2[e] = h^2 int_e (f + a u_e'' + a' u_e')^2 + h/2 (J_e^2 + J_{e+1}^2), J the jump of the flux a u'.
+    ``a_values``, ``da_values``, ``rhs_values``: a, a' and f at :func:`estimate_points`, float64[ne, nq] or,
+    with ``point_major``, float64[nq, ne]; ``a_ends`` float64[ne, 2]: a at the left and right end of every
+    element, seen from inside it.  Returns (eta2 float64[ne], jump float64[ne+1] | None, out3 device
+    float64[3] = {sum, max of the finite eta2, non-finite count})."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(W, "W")
+    ne = x.numel() - 1
+    nq = int(nq)
+    if W.dim() != 2 or W.shape[0] != ne:
+        raise ValueError("W must be [ne, M]")
+    shape = (nq, ne) if point_major else (ne, nq)
+    for t, nm in ((a_values, "a_values"), (da_values, "da_values"), (rhs_values, "rhs_values")):
+        _dev(t, nm)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{nm} must be {'[nq, ne]' if point_major else '[ne, nq]'} = {list(shape)}, "
+                             f"got {list(t.shape)}")
+    _dev(a_ends, "a_ends")
+    if tuple(a_ends.shape) != (ne, 2):
+        raise ValueError(f"a_ends must be [ne, 2] = [{ne}, 2], got {list(a_ends.shape)}")
+    eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
+    jump = torch.empty(ne + 1, dtype=torch.float64, device=x.device) if want_jump else None
+    out3 = torch.empty(3, dtype=torch.float64, device=x.device)
+    work = _check_work(work, x, ne)
+    rc = lib.lssvr_estimate_varcoef(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, _ptr(a_values), _ptr(da_values),
+                                    _ptr(rhs_values), TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR,
+                                    _ptr(a_ends), _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work), _stream(stream))
+    _capi.check(rc, "lssvr_estimate_varcoef")
+    return eta2, jump, out3
+
+
 def refine(x, eta2, eta2_max, theta, *, h_min=0.0, want_parent=False, work=None, stream=None):
     """Mark (eta2 non-finite, or eta2 >= theta^2 * max with max > 0; element >= 2 h_min long) and
     bisect (``lssvr_refine``).  ``eta2_max``: device float64 holding max (e.g. ``out3[1:2]`` of

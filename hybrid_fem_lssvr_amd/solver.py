@@ -21,7 +21,9 @@ mesh/basis or node array instead of ``np.linspace(a, b, num_fem_nodes)``), ``fem
 (``"bands"``: the assembled float64 tridiagonal system, as ``enforce`` + ``solve`` see it;
 ``"flux"``: exact-structure prefix-scan solve), ``solver``
 (``ops.SOLVER_PRIMAL`` default; ``ops.SOLVER_SHARED``: uniform meshes only, one shared operator
-applied per element).
+applied per element), ``coef`` (a pair ``(a, da)`` of numpy-vectorised callables:
+solve, estimate and refine ``-(a u')' = f`` instead of ``-u'' = f``, BASELINE config 5 and DESIGN.md
+section 11; ``None`` keeps the Poisson rows).
 """
 from __future__ import annotations
 
@@ -109,6 +111,20 @@ def _rhs_mode(rhs, x_dev, n_colloc, M=None):
     if pm:
         f = np.ascontiguousarray(f.T)
     return dict(rhs_values=_to_dev(f, x_dev.device), point_major=pm)
+
+
+def _tabulate(funcs, pts, point_major=False):
+    """Device tables of the callables ``funcs`` at the device points ``pts`` [ne, k]: every callable sees the
+    element-major host array (as :func:`_rhs_mode`'s does); each table is handed over as [ne, k], or
+    transposed to [k, ne] with ``point_major``."""
+    xh = pts.cpu().numpy()
+    out = []
+    for fn in funcs:
+        t = np.asarray(fn(xh), dtype=np.float64)
+        if t.shape != xh.shape:
+            t = np.broadcast_to(t, xh.shape)
+        out.append(_to_dev(t.T if point_major else t, pts.device))
+    return out
 
 
 def _enhance(x, u, M, gamma, n_colloc, *, global_domain, bc, solver, uniform_rtol=1e-9, **kw):
@@ -288,7 +304,7 @@ def lssvr_primal(rhs_func, domain_range, u_xmin, u_xmax, M, gamma,
 class FEMLSSVRPrimalSolver:
     def __init__(self, num_fem_nodes=5, lssvr_M=12, lssvr_gamma=1e6, global_domain=(-1, 1), *,
                  n_colloc=12, rhs=poisson_rhs, nquad=2, mesh=None, device="cuda:0",
-                 solver=ops.SOLVER_PRIMAL, fem_solver="bands"):
+                 solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None):
         # Dual.py:101-108
         self.num_fem_nodes = num_fem_nodes
         self.lssvr_M = lssvr_M
@@ -307,6 +323,16 @@ class FEMLSSVRPrimalSolver:
         if fem_solver not in ("bands", "flux"):
             raise ValueError("fem_solver must be 'bands' or 'flux'")
         self.fem_solver = fem_solver
+        if coef is not None:
+            if not (isinstance(coef, (tuple, list)) and len(coef) == 2 and all(callable(c) for c in coef)):
+                raise ValueError("coef must be a pair (a, da) of callables")
+            # lssvr_enhance_varcoef has no solver selector: it takes its own path by M and n_colloc
+            if solver != ops.SOLVER_PRIMAL:
+                raise ValueError("coef (variable coefficients) needs solver=ops.SOLVER_PRIMAL"
+                                 + (": the shared operator holds the Poisson rows only"
+                                    if solver == ops.SOLVER_SHARED else ""))
+            coef = tuple(coef)
+        self.coef = coef
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
         self._x_dev = None
@@ -325,12 +351,15 @@ class FEMLSSVRPrimalSolver:
             m = self.mesh
         basis = P1Basis(m)
         x = _to_dev(m.nodes, dev)
+        kw = {}
+        if self.coef is not None:        # kloc = abar / h, abar the quadrature mean of a
+            kw["a_quad"] = _tabulate(self.coef[:1], ops.quad_points(x, self.nquad))[0]
         if isinstance(self.rhs, SinRHS):
-            bands = ops.p1_assemble(x, self.nquad, rhs=(self.rhs.amp, self.rhs.omega), want_local=True)
+            bands = ops.p1_assemble(x, self.nquad, rhs=(self.rhs.amp, self.rhs.omega), want_local=True, **kw)
         else:
             xq = ops.quad_points(x, self.nquad)
             fq = _to_dev(self.rhs(xq.cpu().numpy()), dev)
-            bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True)
+            bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
         u0 = main_boundary_condition_left(self.global_domain[0])
         u1 = main_boundary_condition_right(self.global_domain[1])
         if self.fem_solver == "flux":
@@ -362,12 +391,19 @@ class FEMLSSVRPrimalSolver:
         if x is None or x.numel() != nodes.size or not np.array_equal(x.cpu().numpy(), nodes):
             x = _to_dev(nodes, dev)
         u = _to_dev(self.fem_values, dev)       # the attribute is authoritative (may be user-set)
-        kw = _rhs_mode(self.rhs, x, self.n_colloc, self.lssvr_M)
-        W, st = _enhance(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc),
-                         global_domain=(float(self.global_domain[0]), float(self.global_domain[1])),
-                         bc=(main_boundary_condition_left(self.global_domain[0]),
-                             main_boundary_condition_right(self.global_domain[1])),
-                         solver=self.solver_id, **kw)
+        gd = (float(self.global_domain[0]), float(self.global_domain[1]))
+        bc = (main_boundary_condition_left(self.global_domain[0]),
+              main_boundary_condition_right(self.global_domain[1]))
+        if self.coef is None:
+            kw = _rhs_mode(self.rhs, x, self.n_colloc, self.lssvr_M)
+            W, st = _enhance(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc),
+                             global_domain=gd, bc=bc, solver=self.solver_id, **kw)
+        else:
+            # the varcoef kernels take tables only (a SinRHS too); point-major up to M = 22, as in _rhs_mode
+            pm = int(self.lssvr_M) <= 22
+            tabs = _tabulate((self.coef[0], self.coef[1], self.rhs), ops.colloc_points(x, self.n_colloc), pm)
+            W, st = ops.enhance_varcoef(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc), *tabs,
+                                        global_domain=gd, bc=bc, point_major=pm)
         self.enhanced = EnhancedSolution(x, W, st)
         nbad = self.enhanced.n_fallback
         if nbad:
@@ -405,6 +441,14 @@ class FEMLSSVRPrimalSolver:
         if self.enhanced is None:
             raise RuntimeError("call solve() first")
         x, W = self.enhanced.nodes, self.enhanced.W
+        if self.coef is not None:
+            # a, a', f at the Gauss points (point-major: coalesced); a at the nodes from both sides, aL = aR
+            tabs = _tabulate((self.coef[0], self.coef[1], self.rhs), ops.estimate_points(x, nq), True)
+            an = np.asarray(self.coef[0](x.cpu().numpy()), dtype=np.float64)
+            an = np.broadcast_to(an, (x.numel(),))
+            a_ends = _to_dev(np.stack([an[:-1], an[1:]], axis=1), x.device)
+            eta2, _, out3 = ops.estimate_varcoef(x, W, nq, *tabs, a_ends, point_major=True)
+            return eta2, out3
         if isinstance(self.rhs, SinRHS):
             kw = dict(rhs=(self.rhs.amp, self.rhs.omega))
         else:
@@ -425,15 +469,18 @@ class FEMLSSVRPrimalSolver:
     def estimate(self, nq=None):
         """Per-element error indicator of the enhanced solution after ``solve()``, as numpy:
         eta_e^2 = h_e^2 int_e (f + u_e'')^2 dx + h_e/2 (J_e^2 + J_{e+1}^2), J = jump of u' at the
-        nodes (0 at the Dirichlet ends), ``nq``-point Gauss (default max(lssvr_M, 8)).  For -u'' = f."""
+        nodes (0 at the Dirichlet ends), ``nq``-point Gauss (default max(lssvr_M, 8)).  With ``coef = (a, da)``
+        the residual is f + a u_e'' + a' u_e' and J the jump of the flux a u' (a at the nodes from both sides:
+        a callable coefficient is continuous there; ``ops.estimate_varcoef`` takes one-sided values)."""
         nq = self._nq(nq)
         eta2, _ = self._estimate_dev(nq)
         return eta2.cpu().numpy()
 
     def solve_adaptive(self, tol=None, theta=0.5, max_elements=100000, max_iter=50, h_min=0.0, nq=None):
         """Solve, estimate, mark, bisect -- repeated.  Each round runs ``solve()`` on the current mesh
-        and the indicator of :meth:`estimate`; it stops when sqrt(sum eta^2) <= ``tol``, after
-        ``max_iter`` rounds, when nothing is marked, or when the refinement would take the mesh above
+        and the indicator of :meth:`estimate` (for ``-(a u')' = f`` when ``coef`` is set); it stops when
+        sqrt(sum eta^2) <= ``tol``, after ``max_iter`` rounds, when nothing is marked, or when the refinement
+        would take the mesh above
         ``max_elements`` (the final mesh never exceeds it); otherwise every element with
         eta_e >= ``theta`` * max eta (and at least 2 ``h_min`` long) is bisected and ``self.mesh``
         becomes the new nodes.  Afterwards ``fem_nodes``, ``fem_values``, ``lssvr_functions`` and

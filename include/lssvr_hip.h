@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LSSVR_ABI_VERSION 6
+#define LSSVR_ABI_VERSION 7
 
 /* error codes */
 #define LSSVR_OK              0
@@ -413,7 +413,8 @@ int lssvr_eval_error(const double* x, const double* W, int64_t ne, int M,
 
 /*
  * A posteriori error indicator and h-refinement (ABI 6; no reference counterpart: Dual.py has no
- * error measure that does not need the exact solution).  For -u'' = f only.
+ * error measure that does not need the exact solution).  lssvr_estimate is for -u'' = f,
+ * lssvr_estimate_varcoef (ABI 7) for -(a u')' = f; lssvr_refine serves both.
  *
  * lssvr_eval_deriv -- d^order u_h / dx^order at the query points, order in {0, 1, 2}, with
  * lssvr_eval's element rule (interior node -> left element, outside -> extrapolation, NaN -> elem -1
@@ -455,6 +456,23 @@ int64_t lssvr_adapt_work_bytes(int64_t ne);
 int lssvr_estimate(const double* x, const double* W, int64_t ne, int M, int nq,
                    int rhs_id, const double* rhs_params_host, const double* rhs_values,
                    double* eta2, double* jump, double* out3, void* work, void* stream);
+
+/*
+ * lssvr_estimate_varcoef -- lssvr_estimate for -(a u')' = f (ABI 7):
+ *   eta2[e] = h_e^2 * int_e (f + a u_e'' + a' u_e')^2 dx + h_e/2 * (J_e^2 + J_{e+1}^2),
+ *   J_i = aR_{i-1} u_{i-1}'(x_i) - aL_i u_i'(x_i) at interior nodes, J_0 = J_ne = 0,
+ * J the jump of the flux a u'.  Same Gauss rule, W, eta2, out3 and work as lssvr_estimate.
+ *   a_values, da_values, rhs_values   a, a' and f at lssvr_estimate_points, all three in table_layout:
+ *                   LSSVR_TABLE_ELEMENT_MAJOR (t[e*nq + q]) or LSSVR_TABLE_POINT_MAJOR (t[q*ne + e])
+ *   a_ends[2*ne]    {aL_e, aR_e}: a at the left / right end of element e, seen from inside it (a coefficient
+ *                   that jumps at a node gives a flux-continuous solution J = 0)
+ *   jump[ne+1]      out, may be NULL: the J_i
+ * work must hold lssvr_adapt_work_bytes(ne) bytes (not checkable here: no size argument).
+ */
+int lssvr_estimate_varcoef(const double* x, const double* W, int64_t ne, int M, int nq,
+                           const double* a_values, const double* da_values, const double* rhs_values,
+                           int table_layout, const double* a_ends,
+                           double* eta2, double* jump, double* out3, void* work, void* stream);
 
 /*
  * lssvr_refine -- threshold marking and bisection.  Element e is marked iff

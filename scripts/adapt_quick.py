@@ -1,10 +1,11 @@
 """Timing of the a posteriori indicator and the refinement at 1e6 elements on one MI355X (DESIGN.md
 section 11): lssvr_estimate (M = 9, nq = 16, in-kernel sin rhs) and lssvr_refine (theta = 0.5), device
 events around `reps` back-to-back launches after a warm-up, beside lssvr_enhance on the same mesh.
+``--varcoef`` adds lssvr_estimate_varcoef (same M and nq; a, a', f tables) in both table layouts.
 Prints the algorithmic bytes and flops per element, the bound that applies and the fraction of it;
 ``--json PATH`` also writes the record as JSON.
 
-    python scripts/adapt_quick.py [--ne 1000000] [--reps 50] [--json PATH]
+    python scripts/adapt_quick.py [--ne 1000000] [--reps 50] [--varcoef] [--json PATH]
 """
 import argparse
 import json
@@ -51,6 +52,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ne", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--varcoef", action="store_true", help="also time lssvr_estimate_varcoef, both layouts")
     ap.add_argument("--json", default=None, help="write the record to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -96,6 +98,23 @@ def main():
     rec["refine_over_enhance"] = t_ref / t_enh
     print(f"estimate / enhance = {t_est / t_enh:.3f}, refine / enhance = {t_ref / t_enh:.3f}, "
           f"marked {n_new - ne} of {ne}")
+    if args.varcoef:
+        # a = 1 + 0.5 sin(3x), a', f tabulated at the estimator's points; a_ends from a at the nodes
+        xq = ops.estimate_points(x, nq)
+        a_tab = 1.0 + 0.5 * torch.sin(3.0 * xq)
+        tabs = [a_tab, 1.5 * torch.cos(3.0 * xq), ops.POISSON_AMP * torch.sin(ops.POISSON_OMEGA * xq)]
+        an = 1.0 + 0.5 * torch.sin(3.0 * x)
+        a_ends = torch.stack([an[:-1], an[1:]], dim=1).contiguous()
+        # tables a, a', f + a_ends + W row + x (shared nodes) + eta2
+        vc_bytes = 3 * nq * 8 + 16 + 8 * M + 8 + 8
+        # per point: two M-1 term sums (u', u''), 4 for the residual, 2 for the weighted square; end fluxes
+        vc_flops = nq * (4 * (M - 1) + 4 + 2) + 4 * (M - 1) + 2 + 14
+        for pm in (True, False):
+            tt = [t.t().contiguous() for t in tabs] if pm else tabs
+            t_vc = timeit(lambda: ops.estimate_varcoef(x, W, nq, *tt, a_ends, point_major=pm, work=work), args.reps)
+            key = "estimate_varcoef_" + ("point_major" if pm else "element_major")
+            rec[key] = roofline("lssvr_estimate_varcoef (%s)" % ("point-major" if pm else "element-major"),
+                                t_vc, ne, vc_bytes, vc_flops)
     if args.json:
         with open(args.json, "w") as fh:
             json.dump(rec, fh, indent=1)

@@ -1,0 +1,396 @@
+"""GPU: the a posteriori indicator for -(a u')' = f (ABI 7, lssvr_estimate_varcoef) against a numpy restatement
+of its definition, its Poisson limit, exactness on exact solutions, and the facade's ``coef`` keyword through
+solve / estimate / solve_adaptive."""
+import math
+
+import numpy as np
+import pytest
+from numpy.polynomial.legendre import Legendre, legder, legval
+
+from oracle import lssvr_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+
+def _t(a, dev):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a), device=dev)
+
+
+def _mesh(rng, ne, lo=-1.0, span=2.0):
+    h = rng.uniform(0.3, 1.7, ne)
+    return np.concatenate([[lo], lo + span * np.cumsum(h) / h.sum()])
+
+
+# ---------------------------------------------------------------------------
+# numpy restatement
+# ---------------------------------------------------------------------------
+def _ref_points(x, nq):
+    from hybrid_fem_lssvr_amd import ops
+    xi, _ = ops.gauss_rule(nq)
+    a, b = x[:-1, None], x[1:, None]
+    return 0.5 * (a + b) + (0.5 * (b - a)) * xi[None, :]
+
+
+def _ref_estimate_vc(x, W, nq, a, da, f, a_ends):
+    """eta2 = h^2 int (f + a u'' + a' u')^2 + h/2 (J_e^2 + J_{e+1}^2), J_i = aR_{i-1} u_{i-1}'(x_i) - aL_i u_i'(x_i);
+    a, da, f element-major [ne, nq] at the Gauss points, a_ends [ne, 2].  Returns (eta2, J, scale of J, scale of
+    eta2): the scales take every term by its magnitude, so that they bound what rounding can do where the
+    terms cancel."""
+    from hybrid_fem_lssvr_amd import ops
+    xi, wt = ops.gauss_rule(nq)
+    ne, M = W.shape
+    h = x[1:] - x[:-1]
+    scl = 2.0 / h
+    T1 = np.zeros((nq, M))
+    T2 = np.zeros((nq, M))
+    for k in range(M):
+        ek = np.zeros(M)
+        ek[k] = 1.0
+        T1[:, k] = legval(xi, legder(ek, 1))
+        T2[:, k] = legval(xi, legder(ek, 2))
+    t2 = a * ((W @ T2.T) * (scl ** 2)[:, None])
+    t1 = da * ((W @ T1.T) * scl[:, None])
+    r = f + t2 + t1
+    rs = np.abs(f) + np.abs(t2) + np.abs(t1)
+    integ = 0.5 * h * ((r * r) @ wt)
+    ends = np.array([-1.0, 1.0])
+    D = np.zeros((2, M))
+    for k in range(M):
+        ek = np.zeros(M)
+        ek[k] = 1.0
+        D[:, k] = legval(ends, legder(ek, 1))
+    dL = (W @ D[0]) * scl
+    dR = (W @ D[1]) * scl
+    fl, fr = a_ends[:, 0] * dL, a_ends[:, 1] * dR
+    J = np.zeros(ne + 1)
+    J[1:-1] = fr[:-1] - fl[1:]
+    jscale = np.zeros(ne + 1)               # the end-point sums term by term in magnitude
+    jscale[1:-1] = (np.abs(a_ends[:-1, 1]) * ((np.abs(W[:-1]) @ np.abs(D[1])) * scl[:-1])
+                    + np.abs(a_ends[1:, 0]) * ((np.abs(W[1:]) @ np.abs(D[0])) * scl[1:]))
+    eta2 = h * h * integ + 0.5 * h * (J[:-1] ** 2 + J[1:] ** 2)
+    escale = h * h * (0.5 * h * ((rs * rs) @ wt)) + 0.5 * h * (jscale[:-1] ** 2 + jscale[1:] ** 2)
+    return eta2, J, jscale, escale
+
+
+def _random_case(rng, ne, M, nq, pad=0):
+    x = _mesh(rng, ne, lo=-3.0, span=6.0)
+    W = rng.standard_normal((ne, M)) / (1.0 + np.arange(M)) ** 2
+    if pad:
+        W = np.concatenate([W, np.zeros((ne, pad))], axis=1)
+    xq = _ref_points(x, nq)
+    a = 1.0 + 0.5 * np.sin(1.3 * xq)
+    da = 0.65 * np.cos(1.3 * xq)
+    f = 2.5 * np.sin(1.7 * xq) + 0.3
+    a_ends = rng.uniform(0.5, 1.5, (ne, 2))
+    return x, W, a, da, f, a_ends
+
+
+def _run_vc(dev, x, W, nq, a, da, f, a_ends, pm, **kw):
+    from hybrid_fem_lssvr_amd import ops
+    tabs = [_t(t.T if pm else t, dev) for t in (a, da, f)]
+    return ops.estimate_varcoef(_t(x, dev), _t(W, dev), nq, *tabs, _t(a_ends, dev), point_major=pm, **kw)
+
+
+def _check_vs_ref(eta2, jump, o3, x, W, nq, a, da, f, a_ends):
+    e_ref, j_ref, jscale, _ = _ref_estimate_vc(x, W, nq, a, da, f, a_ends)
+    assert np.all(np.abs(eta2 - e_ref) <= 1e-12 * np.abs(e_ref) + 1e-300), np.max(np.abs(eta2 - e_ref) / e_ref)
+    assert jump[0] == 0.0 and jump[-1] == 0.0
+    assert np.all(np.abs(jump - j_ref) <= 1e-12 * jscale)
+    assert o3[2] == 0.0 and o3[1] == np.max(eta2)
+    s = math.fsum(eta2.tolist())
+    assert abs(o3[0] - s) <= 1e-14 * s
+
+
+# ---------------------------------------------------------------------------
+# 1. against numpy
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("nq", [1, 4, 16, 32])
+@pytest.mark.parametrize("M", [1, 2, 9, 12, 13, 22, 23, 33])
+def test_estimate_varcoef_vs_numpy(dev, M, nq):
+    """Both layouts, chunk edges (127 / 128 / 129 elements: one chunk, one full chunk, a second chunk)."""
+    rng = np.random.default_rng(1000 * M + nq)
+    for ne in (1, 127, 128, 129, 3001):
+        x, W, a, da, f, a_ends = _random_case(rng, ne, M, nq)
+        for pm in (False, True):
+            eta2, jump, out3 = _run_vc(dev, x, W, nq, a, da, f, a_ends, pm, want_jump=True)
+            _check_vs_ref(eta2.cpu().numpy(), jump.cpu().numpy(), out3.cpu().numpy(), x, W, nq, a, da, f, a_ends)
+
+
+@pytest.mark.parametrize("M,nq,pm", [(9, 16, True), (9, 16, False), (33, 4, True)])
+def test_estimate_varcoef_grid_stride(dev, M, nq, pm):
+    """More elements than 4096 workgroups x 128 cover at once: the grid-stride loop."""
+    rng = np.random.default_rng(77 + M)
+    ne = 600_001
+    x, W, a, da, f, a_ends = _random_case(rng, ne, M, nq)
+    eta2, jump, out3 = _run_vc(dev, x, W, nq, a, da, f, a_ends, pm, want_jump=True)
+    _check_vs_ref(eta2.cpu().numpy(), jump.cpu().numpy(), out3.cpu().numpy(), x, W, nq, a, da, f, a_ends)
+
+
+@pytest.mark.parametrize("M,pad", [(1, 8), (9, 3), (9, 24), (20, 13)])
+def test_estimate_varcoef_zero_padded_rows(dev, M, pad):
+    """Rows zero-padded to a wider M (as enhance_elements_hetero writes them) give the unpadded indicator."""
+    rng = np.random.default_rng(5 + M + pad)
+    ne, nq = 700, 12
+    x, Wp, a, da, f, a_ends = _random_case(rng, ne, M, nq, pad=pad)
+    for pm in (False, True):
+        eta2, jump, out3 = _run_vc(dev, x, Wp, nq, a, da, f, a_ends, pm, want_jump=True)
+        _check_vs_ref(eta2.cpu().numpy(), jump.cpu().numpy(), out3.cpu().numpy(), x, Wp[:, :M], nq, a, da, f,
+                      a_ends)
+
+
+# ---------------------------------------------------------------------------
+# 2. Poisson limit
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("M,nq", [(2, 3), (9, 16), (17, 20), (33, 32)])
+def test_poisson_limit_equals_estimate(dev, M, nq):
+    from hybrid_fem_lssvr_amd import ops
+    rng = np.random.default_rng(300 + M)
+    ne = 5000
+    x, W, _, _, f, _ = _random_case(rng, ne, M, nq)
+    ones, zeros = np.ones_like(f), np.zeros_like(f)
+    e_p, j_p, o_p = ops.estimate(_t(x, dev), _t(W, dev), nq, rhs_values=_t(f, dev), want_jump=True)
+    e_p, j_p, o_p = e_p.cpu().numpy(), j_p.cpu().numpy(), o_p.cpu().numpy()
+    for pm in (False, True):
+        eta2, jump, out3 = _run_vc(dev, x, W, nq, ones, zeros, f, np.ones((ne, 2)), pm, want_jump=True)
+        eta2, jump, out3 = eta2.cpu().numpy(), jump.cpu().numpy(), out3.cpu().numpy()
+        assert np.all(np.abs(eta2 - e_p) <= 1e-14 * np.abs(e_p))
+        assert np.all(np.abs(jump - j_p) <= 1e-14 * np.max(np.abs(j_p)))
+        assert out3[2] == o_p[2] == 0.0
+        assert np.all(np.abs(out3[:2] - o_p[:2]) <= 1e-14 * np.abs(o_p[:2]))
+
+
+# ---------------------------------------------------------------------------
+# 3. exactness
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("M", [9, 22])
+def test_exact_polynomial_solution_is_rounding_only(dev, M):
+    """W sampled from ONE global polynomial u, polynomial a, f = -(a u')': residual and flux jumps vanish."""
+    from hybrid_fem_lssvr_amd import ops
+    from numpy.polynomial import Polynomial
+    rng = np.random.default_rng(21 + M)
+    ne, nq = 16, 12
+    x = _mesh(rng, ne)
+    p = Polynomial(rng.uniform(-1, 1, 8))
+    ap = Polynomial([2.0, 0.3, -0.4, 0.2])
+    W = np.zeros((ne, M))
+    for e in range(ne):
+        c = p.convert(domain=[x[e], x[e + 1]], kind=Legendre).coef
+        W[e, :c.size] = c
+    xq = _ref_points(x, nq)
+    f = -(ap * p.deriv(1)).deriv(1)(xq)
+    an = ap(x)
+    a_ends = np.stack([an[:-1], an[1:]], axis=1)
+    for pm in (False, True):
+        eta2, _, _ = _run_vc(dev, x, W, nq, ap(xq), ap.deriv(1)(xq), f, a_ends, pm)
+        eta2 = eta2.cpu().numpy()
+        h = x[1:] - x[:-1]
+        _, wt = ops.gauss_rule(nq)
+        bound = h * h * (0.5 * h * ((f * f) @ wt)) + h * (an[:-1] * p.deriv(1)(x[:-1])) ** 2
+        assert np.all(eta2 <= 1e-24 * bound), np.max(eta2 / bound)
+
+
+def test_flux_continuous_layered_solution(dev):
+    """Piecewise-constant a that jumps at every node, W the flux-continuous piecewise-linear solution
+    (a_e u_e' = q on every element, f = 0): the flux jumps vanish, so eta2 is rounding; the Poisson indicator
+    on the same W sees the jumps of u' itself, O(1)."""
+    from hybrid_fem_lssvr_amd import ops
+    rng = np.random.default_rng(4)
+    ne, M, nq, q = 1000, 9, 8, 1.7
+    x = _mesh(rng, ne)
+    h = x[1:] - x[:-1]
+    ae = np.exp(rng.uniform(-2.0, 2.0, ne))               # a in [0.14, 7.4], one value per element
+    slope = q / ae
+    u = np.concatenate([[0.0], np.cumsum(slope * h)])
+    W = np.zeros((ne, M))
+    W[:, 0] = 0.5 * (u[:-1] + u[1:])
+    W[:, 1] = 0.5 * slope * h                              # u_e' = slope_e to rounding (not through cumsum)
+    a_tab = np.repeat(ae[:, None], nq, axis=1)
+    zeros = np.zeros((ne, nq))
+    a_ends = np.stack([ae, ae], axis=1)
+    for pm in (False, True):
+        eta2, jump, out3 = _run_vc(dev, x, W, nq, a_tab, zeros, zeros, a_ends, pm, want_jump=True)
+        eta2, jump = eta2.cpu().numpy(), jump.cpu().numpy()
+        assert np.all(eta2 <= 1e-28 * h * q * q), np.max(eta2 / (h * q * q))
+        assert np.max(np.abs(jump)) <= 1e-13 * q
+    e_p, j_p, _ = ops.estimate(_t(x, dev), _t(W, dev), nq, rhs_values=_t(zeros, dev), want_jump=True)
+    j_p = j_p.cpu().numpy()
+    assert np.all(np.abs(j_p[1:-1] - (slope[:-1] - slope[1:])) <= 1e-13 * (slope[:-1] + slope[1:]))
+    assert np.median(np.abs(j_p[1:-1])) > 0.3 * q
+    assert np.median(e_p.cpu().numpy() / (h * q * q)) > 0.1
+
+
+# ---------------------------------------------------------------------------
+# 4. determinism, non-finite values, argument checks
+# ---------------------------------------------------------------------------
+def test_estimate_varcoef_bitwise_repeatable(dev):
+    rng = np.random.default_rng(9)
+    x, W, a, da, f, a_ends = _random_case(rng, 600_001, 9, 16)
+    runs = [_run_vc(dev, x, W, 16, a, da, f, a_ends, True) for _ in range(2)]
+    (e0, _, o0), (e1, _, o1) = [(e.cpu().numpy(), j, o.cpu().numpy()) for e, j, o in runs]
+    assert np.array_equal(e0.view(np.int64), e1.view(np.int64))
+    assert np.array_equal(o0.view(np.int64), o1.view(np.int64))
+
+
+def test_estimate_varcoef_non_finite_table_entries(dev):
+    """A NaN / inf in a table makes that element's eta2 non-finite: counted in out3[2], excluded from the sum
+    and the max (lssvr_estimate's rule)."""
+    rng = np.random.default_rng(6)
+    ne, M, nq = 70_000, 9, 12
+    x, W, a, da, f, a_ends = _random_case(rng, ne, M, nq)
+    bad = rng.choice(ne, 30, replace=False)
+    a[bad[:10], 3] = np.nan
+    da[bad[10:20], 0] = np.inf
+    f[bad[20:], nq - 1] = np.nan
+    for pm in (False, True):
+        eta2, _, out3 = _run_vc(dev, x, W, nq, a, da, f, a_ends, pm)
+        eta2, o3 = eta2.cpu().numpy(), out3.cpu().numpy()
+        fin = np.isfinite(eta2)
+        assert np.array_equal(np.nonzero(~fin)[0], np.sort(bad))
+        assert o3[2] == 30.0
+        assert o3[1] == np.max(eta2[fin])
+        s = math.fsum(eta2[fin].tolist())
+        assert abs(o3[0] - s) <= 1e-14 * s
+
+
+def test_ops_estimate_varcoef_checks_shapes_and_work(dev):
+    import torch
+    from hybrid_fem_lssvr_amd import ops
+    rng = np.random.default_rng(8)
+    ne, M, nq = 300, 9, 6
+    x, W, a, da, f, a_ends = _random_case(rng, ne, M, nq)
+    xd, Wd = _t(x, dev), _t(W, dev)
+    tabs = [_t(t, dev) for t in (a, da, f)]
+    ends = _t(a_ends, dev)
+    with pytest.raises(ValueError, match=r"\[nq, ne\]"):
+        ops.estimate_varcoef(xd, Wd, nq, *tabs, ends, point_major=True)
+    with pytest.raises(ValueError, match="a_values"):
+        ops.estimate_varcoef(xd, Wd, nq + 1, *tabs, ends)
+    with pytest.raises(ValueError, match="a_ends"):
+        ops.estimate_varcoef(xd, Wd, nq, *tabs, ends[:-1])
+    with pytest.raises(ValueError, match="a_ends"):
+        ops.estimate_varcoef(xd, Wd, nq, *tabs, ends.reshape(-1))
+    with pytest.raises(ValueError, match="W"):
+        ops.estimate_varcoef(xd, Wd[:-1], nq, *tabs, ends)
+    small = torch.empty(1, dtype=torch.float64, device=dev)
+    with pytest.raises(ValueError, match="work"):
+        ops.estimate_varcoef(xd, Wd, nq, *tabs, ends, work=small)
+    work = ops.adapt_work(xd, ne)
+    e1, j1, o1 = ops.estimate_varcoef(xd, Wd, nq, *tabs, ends, work=work)
+    assert j1 is None
+    e2, _, o2 = ops.estimate_varcoef(xd, Wd, nq, *tabs, ends)
+    assert torch.equal(e1, e2) and torch.equal(o1, o2)
+
+
+# ---------------------------------------------------------------------------
+# 5. facade against the oracle (BASELINE config 5)
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("ne,M,n", [(2000, 9, 16), (300, 20, 32), (100, 26, 40)])
+def test_facade_coef_matches_oracle(dev, ne, M, n):
+    import hybrid_fem_lssvr_amd as pkg
+    a, da, f = orc.varcoef_functions(*orc.varcoef_params())
+    nodes = np.linspace(-1, 1, ne + 1)
+    s = pkg.FEMLSSVRPrimalSolver(ne + 1, lssvr_M=M, lssvr_gamma=1e4, global_domain=(-1, 1), n_colloc=n,
+                                 rhs=f, nquad=2, coef=(a, da))
+    s.solve()
+    values = orc.fem_p1_solve(nodes, rhs=f, coef_a=a, nquad=2)
+    assert np.max(np.abs(s.fem_values - values)) < 1e-9
+    W = s.enhanced.W.cpu().numpy()
+    assert s.enhanced.n_fallback == 0
+    Wo = orc.enhance_all_vec(nodes, s.fem_values, M, 1e4, n, rhs=f, coef_a=a, coef_da=da, global_domain=(-1.0, 1.0))
+    assert orc.rel_l2_coef(W, Wo).max() <= (1e-11 if M <= 22 else 1e-10)
+    # the facade's indicator: a, a', f at the Gauss points, a at the nodes from both sides.  The enhanced
+    # solution nearly solves the equation, so its residual is a cancellation: the bar is relative to the
+    # magnitude of the terms (|d eta2| <= 2 sqrt(eta2 * scale) * the relative rounding of the terms)
+    from hybrid_fem_lssvr_amd import ops
+    nq = 12
+    eta2 = s.estimate(nq=nq)
+    xq = ops.estimate_points(s.enhanced.nodes, nq).cpu().numpy()
+    an = a(nodes)
+    a_ends = np.stack([an[:-1], an[1:]], axis=1)
+    e_dir, _, _ = _run_vc(dev, nodes, W, nq, a(xq), da(xq), f(xq), a_ends, True)
+    assert np.array_equal(eta2.view(np.int64), e_dir.cpu().numpy().view(np.int64))
+    e_ref, _, _, escale = _ref_estimate_vc(nodes, W, nq, a(xq), da(xq), f(xq), a_ends)
+    assert np.all(np.abs(eta2 - e_ref) <= 1e-12 * e_ref + 1e-13 * np.sqrt(e_ref * escale))
+    assert np.all(eta2 > 0)
+
+
+def test_facade_unit_coefficient_reproduces_poisson(dev):
+    """coef = (1, 0): the P1 solve is bit-identical to coef=None (abar = the Gauss weights' sum, exactly 1 for
+    the 2-point rule); the varcoef enhancement (tabulated SinRHS) agrees with the Poisson kernels."""
+    import hybrid_fem_lssvr_amd as pkg
+
+    def one(x):
+        return np.ones_like(x)
+
+    def zero(x):
+        return np.zeros_like(x)
+
+    for fem_solver in ("bands", "flux"):
+        kw = dict(lssvr_M=9, lssvr_gamma=1e4, global_domain=(-1, 1), n_colloc=16, fem_solver=fem_solver)
+        s0 = pkg.FEMLSSVRPrimalSolver(97, **kw)
+        s1 = pkg.FEMLSSVRPrimalSolver(97, coef=(one, zero), **kw)
+        s0.solve()
+        s1.solve()
+        assert np.array_equal(s0.fem_values.view(np.int64), s1.fem_values.view(np.int64))
+        W0, W1 = s0.enhanced.W.cpu().numpy(), s1.enhanced.W.cpu().numpy()
+        assert orc.rel_l2_coef(W1, W0).max() <= 1e-10
+
+
+# ---------------------------------------------------------------------------
+# 6. adaptive solve with an interior layer
+# ---------------------------------------------------------------------------
+LC, LK = 0.99, 100.0
+
+
+def _a_layer(x):
+    return 1.0 + LC * np.tanh(LK * np.asarray(x, dtype=np.float64))
+
+
+def _da_layer(x):
+    return LC * LK / np.cosh(LK * np.asarray(x, dtype=np.float64)) ** 2
+
+
+def _F_layer(x):
+    """a F' = 1: F = [x - (c/k) ln(cosh kx + c sinh kx)] / (1 - c^2), the log in overflow-free form."""
+    x = np.asarray(x, dtype=np.float64)
+    lg = np.logaddexp(np.log1p(LC) + LK * x, np.log1p(-LC) - LK * x) - math.log(2.0)
+    return (x - (LC / LK) * lg) / (1.0 - LC * LC)
+
+
+ALPHA = -0.5 * float(_F_layer(1.0) - _F_layer(-1.0))      # u = F + alpha x + beta, u(-1) = u(1) = 0
+BETA = -float(_F_layer(1.0)) - ALPHA
+
+
+def _u_layer(x):
+    return _F_layer(x) + ALPHA * np.asarray(x) + BETA
+
+
+def _f_layer(x):                                       # -(a u')' = -(1 + alpha a)' = -alpha a'
+    return -ALPHA * _da_layer(x)
+
+
+def _layer_solver(nodes):
+    import hybrid_fem_lssvr_amd as pkg
+    return pkg.FEMLSSVRPrimalSolver(len(nodes), lssvr_M=9, lssvr_gamma=1e10, global_domain=(-1, 1), n_colloc=16,
+                                    nquad=5, rhs=_f_layer, mesh=nodes, coef=(_a_layer, _da_layer))
+
+
+def test_solve_adaptive_resolves_coefficient_layer(dev, note):
+    xt = np.linspace(-1, 1, 20001)
+    ut = _u_layer(xt)
+    umax = np.max(np.abs(ut))
+    assert abs(_u_layer(-1.0)) < 1e-12 * umax and abs(_u_layer(1.0)) < 1e-12 * umax
+    uni = _layer_solver(np.linspace(-1, 1, 129))
+    uni.solve()
+    err_uni = np.max(np.abs(uni.evaluate_solution(xt) - ut)) / umax
+    s = _layer_solver(np.linspace(-1, 1, 9))
+    est = s.solve_adaptive(theta=0.5, max_elements=128)
+    ne = len(s.fem_nodes) - 1
+    assert ne <= 128 and s.adapt_history[-1]["ne"] == ne and est == s.adapt_history[-1]["estimate"]
+    err = np.max(np.abs(s.evaluate_solution(xt) - ut)) / umax
+    note("varcoef_layer_uniform128_over_adaptive_max_error", err_uni / err, bar=100.0)
+    note("varcoef_layer_adaptive_elements", ne)
+    assert err_uni / err >= 100.0, (err_uni, err, ne)
+    mid = 0.5 * (s.fem_nodes[1:] + s.fem_nodes[:-1])
+    assert np.count_nonzero(np.abs(mid) < 0.1) > 0.75 * ne
