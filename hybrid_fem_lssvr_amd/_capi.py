@@ -132,6 +132,21 @@ SIGNATURES = {
     "lssvr_estimate_varcoef": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_dp, _c_dp, _c_int, _c_dp,
                                         _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "lssvr_refine": (_c_int, [_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    # reaction term -(a u')' + c u = f (additive to ABI 7)
+    "lssvr_enhance_react": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
+                                     _c_dbl, _c_dbl, _c_dbl, _c_dbl,
+                                     _c_int, _c_int, _c_dbl,
+                                     _c_dp, _c_dp, _c_dp, _c_dp,
+                                     _c_dp, _c_dp, _c_dp, _c_dp]),
+    "lssvr_enhance_react_ws": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
+                                        _c_dbl, _c_dbl, _c_dbl, _c_dbl,
+                                        _c_int, _c_int, _c_dbl,
+                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_int,
+                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_dp, C.POINTER(C.c_float)]),
+    "lssvr_p1_assemble_react": (_c_int, [_c_dp, _c_i64, _c_int, _c_int, C.POINTER(_c_dbl), _c_dp, _c_dp, _c_dp,
+                                         _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "lssvr_estimate_react": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_int,
+                                      _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "lssvr_fp64_probe": (_c_int, [_c_dp, _c_int, _c_int, _c_int, _c_dp]),
     "lssvr_stream_probe": (_c_int, [_c_dp, _c_dp, _c_i64, _c_dp]),
     "lssvr_row_chunk_probe": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp]),

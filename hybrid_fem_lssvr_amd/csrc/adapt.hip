@@ -469,6 +469,141 @@ __global__ __launch_bounds__(kEstBlock) void estimate_vc_kernel(EstimateVcArgs p
   reduce_partials(red, tid, bsum, bmax, bcnt, p.work);
 }
 
+// Reaction term, -(a u')' + c u = f: estimate_vc_kernel with the residual f + a u'' + a' u' - c u.  The LDS table
+// holds the triples {P_k', P_k'', P_k}; staging, neighbour fluxes, jumps and reduction are those of
+// estimate_vc_kernel.  (A copy, not a shared body: routed through one template the existing kernel is scheduled
+// differently, and its device code is kept as it is.)
+// Dynamic LDS: T[nq*MT] triples | wt[nq] | rows[kEstBlock*ms] | fl[kEstBlock] | fr[kEstBlock] | red[3*kEstBlock].
+template <int MT, bool PM>
+__global__ __launch_bounds__(kEstBlock) void estimate_react_kernel(EstimateReactArgs p, GaussRuleN g) {
+  constexpr int TS = 3;                   // table entries per (point, degree)
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x;
+  const int nq = p.nq, M = p.M, ms = p.ms;
+  const int64_t ne = p.ne;
+  double* T = lds;
+  double* swt = T + TS * nq * MT;
+  double* rows = swt + nq;
+  double* sfl = rows + kEstBlock * ms;
+  double* sfr = sfl + kEstBlock;
+  double* red = sfr + kEstBlock;
+  if (tid < nq) {
+    const double t = g.xi[tid];
+    double* Tq = T + TS * tid * MT;
+    swt[tid] = g.wt[tid];
+    double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
+    Tq[0] = 0.0;
+    Tq[1] = 0.0;
+    Tq[2] = 1.0;
+    if (MT > 1) {
+      Tq[TS] = M > 1 ? 1.0 : 0.0;
+      Tq[TS + 1] = 0.0;
+      Tq[TS + 2] = M > 1 ? t : 0.0;
+    }
+    for (int k = 1; k + 1 < MT; ++k) {
+      const double a = (double)(2 * k + 1);
+      const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
+      const double d2 = d0 + a * p1;
+      const double s2 = s0 + a * d1;
+      Tq[TS * (k + 1)] = k + 1 < M ? d2 : 0.0;
+      Tq[TS * (k + 1) + 1] = k + 1 < M ? s2 : 0.0;
+      Tq[TS * (k + 1) + 2] = k + 1 < M ? p2 : 0.0;
+      p0 = p1; p1 = p2;
+      d0 = d1; d1 = d2;
+      s0 = s1; s1 = s2;
+    }
+  }
+  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
+  double bsum = 0.0, bmax = 0.0, bcnt = 0.0;
+  for (int64_t c0 = (int64_t)blockIdx.x * kEstBlock; c0 < ne; c0 += (int64_t)gridDim.x * kEstBlock) {
+    const int nrow = (int)(ne - c0 < kEstBlock ? ne - c0 : kEstBlock);
+    stage_rows(rows, p.W + c0 * M, nrow * M, M, ms, qM, rM, tid);
+    __syncthreads();
+    const int64_t e = c0 + tid;
+    const bool valid = tid < nrow;
+    double c[MT];
+#pragma unroll
+    for (int k = 0; k < MT; ++k) c[k] = (valid && k < M) ? rows[tid * ms + k] : 0.0;
+    double xa = 0.0, xb = 1.0, aL = 0.0, aR = 0.0;
+    if (valid) {
+      xa = p.x[e];
+      xb = p.x[e + 1];
+      aL = p.a_ends[2 * e];
+      aR = p.a_ends[2 * e + 1];
+    }
+    const DomainMap dm = map_params(xa, xb);
+    double dl, dr;
+    end_derivs<MT>(c, dm.scl, dl, dr);
+    const double fl = aL * dl, fr = aR * dr;
+    sfl[tid] = fl;
+    sfr[tid] = fr;
+    __syncthreads();
+    if (valid) {
+      double fr_prev = 0.0, fl_next = 0.0;
+      if (e > 0) {
+        if (tid > 0) {
+          fr_prev = sfr[tid - 1];
+        } else {
+          double cn[MT];
+          load_row_global<MT>(p.W, e - 1, M, cn);
+          const DomainMap dn = map_params(p.x[e - 1], xa);
+          double l, r;
+          end_derivs<MT>(cn, dn.scl, l, r);
+          fr_prev = p.a_ends[2 * e - 1] * r;
+        }
+      }
+      if (e + 1 < ne) {
+        if (tid + 1 < nrow) {
+          fl_next = sfl[tid + 1];
+        } else {
+          double cn[MT];
+          load_row_global<MT>(p.W, e + 1, M, cn);
+          const DomainMap dn = map_params(xb, p.x[e + 2]);
+          double l, r;
+          end_derivs<MT>(cn, dn.scl, l, r);
+          fl_next = p.a_ends[2 * e + 2] * l;
+        }
+      }
+      const double jl = e > 0 ? fr_prev - fl : 0.0;
+      const double jr = e + 1 < ne ? fr - fl_next : 0.0;
+      // interior residual f + a u'' + a' u' - c u at the nq Gauss points
+      const double scl2 = dm.scl * dm.scl;
+      double acc = 0.0;
+#pragma unroll 1
+      for (int q = 0; q < nq; ++q) {
+        const double* Tq = T + TS * q * MT;
+        double s1 = 0.0, s2 = 0.0, s0 = c[0];     // u = sum_k c_k P_k, P_0 = 1
+#pragma unroll
+        for (int k = 1; k < MT; ++k) {
+          s1 = fma(c[k], Tq[TS * k], s1);
+          s2 = fma(c[k], Tq[TS * k + 1], s2);
+          s0 = fma(c[k], Tq[TS * k + 2], s0);
+        }
+        const int64_t i = PM ? (int64_t)q * ne + e : e * nq + q;
+        const double r =
+            p.rhs_values[i] + p.a_values[i] * (s2 * scl2) + p.da_values[i] * (s1 * dm.scl) - p.c_values[i] * s0;
+        acc = fma(swt[q], r * r, acc);
+      }
+      const double h = dm.oldlen;
+      const double half = 0.5 * h;
+      const double eta2 = (h * h) * (half * acc) + half * (jl * jl + jr * jr);
+      p.eta2[e] = eta2;
+      if (p.jump) {
+        p.jump[e] = jl;
+        if (e + 1 == ne) p.jump[ne] = 0.0;
+      }
+      if (fabs(eta2) < INFINITY) {
+        bsum += eta2;
+        bmax = fmax(bmax, eta2);
+      } else {
+        bcnt += 1.0;
+      }
+    }
+    __syncthreads();      // rows / sfl / sfr are rewritten by the next chunk
+  }
+  reduce_partials(red, tid, bsum, bmax, bcnt, p.work);
+}
+
 // one workgroup: the per-block partials in a fixed order -> out3 (bitwise reproducible)
 __global__ __launch_bounds__(kBlock) void estimate_finish_kernel(const double* __restrict__ part, int nb,
                                                                   double* __restrict__ out3) {
@@ -672,6 +807,32 @@ hipError_t estimate_varcoef(EstimateVcArgs a, bool point_major, double* out3, hi
   if (MT == 12) err = launch_estimate_vc<12>(a, g, point_major, (unsigned)nb, lds, s);
   else if (MT == 22) err = launch_estimate_vc<22>(a, g, point_major, (unsigned)nb, lds, s);
   else err = launch_estimate_vc<33>(a, g, point_major, (unsigned)nb, lds, s);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
+  return hipGetLastError();
+}
+
+template <int MT>
+static hipError_t launch_estimate_react(const EstimateReactArgs& a, const GaussRuleN& g, bool point_major,
+                                        unsigned nb, size_t lds, hipStream_t s) {
+  if (point_major)
+    hipLaunchKernelGGL((estimate_react_kernel<MT, true>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
+  else
+    hipLaunchKernelGGL((estimate_react_kernel<MT, false>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t estimate_react(EstimateReactArgs a, bool point_major, double* out3, hipStream_t s) {
+  GaussRuleN g{};
+  if (!gauss_rule(a.nq, g.xi, g.wt)) return hipErrorInvalidValue;
+  a.ms = a.M | 1;
+  const int64_t nb = est_blocks(a.ne);
+  const int MT = a.M <= 12 ? 12 : (a.M <= 22 ? 22 : 33);
+  const size_t lds = sizeof(double) * ((size_t)a.nq * (3 * MT + 1) + (size_t)kEstBlock * a.ms + 5 * kEstBlock);
+  hipError_t err;
+  if (MT == 12) err = launch_estimate_react<12>(a, g, point_major, (unsigned)nb, lds, s);
+  else if (MT == 22) err = launch_estimate_react<22>(a, g, point_major, (unsigned)nb, lds, s);
+  else err = launch_estimate_react<33>(a, g, point_major, (unsigned)nb, lds, s);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
   return hipGetLastError();

@@ -273,6 +273,29 @@ int bind_varcoef_ws(lssvr::EnhanceArgs& a, const double* x, const double* u, int
                     "lssvr_enhance_varcoef_work_bytes");
 }
 
+// the arguments of lssvr_enhance_react_ws, validated and bound: the variable-coefficient ones plus the c table
+int bind_react_ws(lssvr::EnhanceReactArgs& a, const double* x, const double* u, int64_t ne, int64_t elem_offset,
+                  int64_t ne_global, double gxmin, double gxmax, double bc_left, double bc_right, int M,
+                  int n_colloc, double gamma, const double* a_values, const double* da_values,
+                  const double* c_values, const double* rhs_values, int table_layout, double* W, int32_t* status,
+                  int32_t* fail_count, void* work, int64_t work_bytes) {
+  a = lssvr::EnhanceReactArgs{};
+  int rc = bind_varcoef_ws(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc, gamma,
+                           a_values, da_values, rhs_values, table_layout, W, status, fail_count, work, work_bytes);
+  if (rc != LSSVR_OK) return rc;
+  if (ne > 0 && !c_values) return fail(LSSVR_ERR_NULL, "c_values must be non-NULL");
+  if (n_colloc < M - 2)
+    return fail(LSSVR_ERR_SOLVER, "lssvr_enhance_react: n_colloc = %d < M-2 = %d (the reaction rows have no dual "
+                                  "solver)", n_colloc, M - 2);
+  a.c_values = c_values;
+  return LSSVR_OK;
+}
+
+int react_dispatch(const lssvr::EnhanceReactArgs& a, hipStream_t s, const lssvr::LaunchOpts* o) {
+  if (a.M <= lssvr::kReactSmallMaxM) return check_launch(lssvr::enhance_small_react(a, s, o), "enhance_small_react");
+  return check_launch(lssvr::enhance_large_react(a, s, o), "enhance_large_react");
+}
+
 }  // namespace
 
 extern "C" {
@@ -466,6 +489,33 @@ int lssvr_step_varcoef(const double* x, const double* u, int64_t ne, int64_t ele
   return enhance_dispatch(a, LSSVR_SOLVER_PRIMAL, s, nullptr);
 }
 
+int lssvr_enhance_react(const double* x, const double* u, int64_t ne, int64_t elem_offset,
+                        int64_t ne_global, double gxmin, double gxmax, double bc_left,
+                        double bc_right, int M, int n_colloc, double gamma,
+                        const double* a_values, const double* da_values, const double* c_values,
+                        const double* rhs_values, double* W, int32_t* status,
+                        int32_t* fail_count, void* stream) {
+  return lssvr_enhance_react_ws(x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M,
+                                n_colloc, gamma, a_values, da_values, c_values, rhs_values,
+                                LSSVR_TABLE_ELEMENT_MAJOR, W, status, fail_count, nullptr, 0, stream, nullptr);
+}
+
+int lssvr_enhance_react_ws(const double* x, const double* u, int64_t ne, int64_t elem_offset,
+                           int64_t ne_global, double gxmin, double gxmax, double bc_left,
+                           double bc_right, int M, int n_colloc, double gamma,
+                           const double* a_values, const double* da_values, const double* c_values,
+                           const double* rhs_values, int table_layout, double* W, int32_t* status,
+                           int32_t* fail_count, void* work, int64_t work_bytes, void* stream,
+                           float* kernel_ms_host) {
+  lssvr::EnhanceReactArgs a;
+  const int rc = bind_react_ws(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                               gamma, a_values, da_values, c_values, rhs_values, table_layout, W, status,
+                               fail_count, work, work_bytes);
+  if (rc != LSSVR_OK || ne == 0) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return timed_launch([&](const lssvr::LaunchOpts* o) { return react_dispatch(a, s, o); }, kernel_ms_host);
+}
+
 // (no variable-coefficient kernel takes a workspace: always 0, kept for ABI 6)
 int64_t lssvr_enhance_varcoef_work_bytes(int64_t ne, int M, int n_colloc) {
   (void)ne; (void)M; (void)n_colloc;
@@ -623,6 +673,36 @@ int lssvr_p1_assemble(const double* x, int64_t ne, int nquad, int rhs_id,
   return check_launch(lssvr::p1_assemble(a, reinterpret_cast<hipStream_t>(stream)), "p1_assemble");
 }
 
+int lssvr_p1_assemble_react(const double* x, int64_t ne, int nquad, int rhs_id,
+                            const double* rhs_params_host, const double* rhs_quad, const double* a_quad,
+                            const double* c_quad, double* diag, double* off, double* load, double* kloc,
+                            double* floc, void* stream) {
+  // no reaction term: the very launch of lssvr_p1_assemble
+  if (!c_quad)
+    return lssvr_p1_assemble(x, ne, nquad, rhs_id, rhs_params_host, rhs_quad, a_quad, diag, off, load, kloc, floc,
+                             stream);
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  lssvr::P1ReactArgs a{};
+  const int rc = bind_p1(a, x, ne, nquad, diag, off, load);
+  if (rc != LSSVR_OK) return rc;
+  a.rhs_id = rhs_id;
+  if (rhs_id == LSSVR_RHS_SIN) {
+    if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
+    a.rhs_amp = rhs_params_host[0];
+    a.rhs_omega = rhs_params_host[1];
+  } else if (rhs_id == LSSVR_RHS_ARRAY) {
+    if (!rhs_quad) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_ARRAY needs rhs_quad[ne*nquad]");
+    a.rhs_quad = rhs_quad;
+  } else {
+    return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
+  }
+  a.a_quad = a_quad;
+  a.c_quad = c_quad;
+  a.kloc = kloc;
+  a.floc = floc;
+  return check_launch(lssvr::p1_assemble_react(a, reinterpret_cast<hipStream_t>(stream)), "p1_assemble_react");
+}
+
 int lssvr_quad_points(const double* x, int64_t ne, int nquad, double* xq, void* stream) {
   if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne < 0");
   if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
@@ -767,6 +847,25 @@ int lssvr_estimate_varcoef(const double* x, const double* W, int64_t ne, int M, 
   return check_launch(lssvr::estimate_varcoef(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,
                                               reinterpret_cast<hipStream_t>(stream)),
                       "estimate_varcoef");
+}
+
+int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, int nq, const double* a_values,
+                         const double* da_values, const double* c_values, const double* rhs_values, int table_layout,
+                         const double* a_ends, double* eta2, double* jump, double* out3, void* work, void* stream) {
+  lssvr::EstimateReactArgs a{};
+  int rc = bind_estimate(a, x, W, ne, M, nq, eta2, jump, out3, work);
+  if (rc == LSSVR_OK) rc = check_varcoef_tables(a_values, da_values, rhs_values, table_layout, true);
+  if (rc != LSSVR_OK) return rc;
+  if (!c_values) return fail(LSSVR_ERR_NULL, "c_values must be non-NULL");
+  if (!a_ends) return fail(LSSVR_ERR_NULL, "a_ends must be non-NULL");
+  a.rhs_values = rhs_values;
+  a.a_values = a_values;
+  a.da_values = da_values;
+  a.c_values = c_values;
+  a.a_ends = a_ends;
+  return check_launch(lssvr::estimate_react(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,
+                                            reinterpret_cast<hipStream_t>(stream)),
+                      "estimate_react");
 }
 
 int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev, double theta,

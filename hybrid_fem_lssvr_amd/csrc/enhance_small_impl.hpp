@@ -34,17 +34,26 @@ namespace lssvr {
 // array at pitch kStageK + 1 -- whichever is larger; the two uses never overlap in time.
 constexpr int kStageK = 8;
 constexpr int kStageArr = 64 * (kStageK + 1);
-template <int M, int RHS, bool VC>
+// (RX: the reaction rows stage a fourth array, c)
+template <int M, int RHS, bool VC, bool RX = false>
 constexpr int kSmallTilePerWave =
-    (RHS == LSSVR_RHS_ARRAY && (VC ? 3 : 1) * kStageArr > 64 * M) ? (VC ? 3 : 1) * kStageArr : 64 * M;
+    (RHS == LSSVR_RHS_ARRAY && (VC ? (RX ? 4 : 3) : 1) * kStageArr > 64 * M) ? (VC ? (RX ? 4 : 3) : 1) * kStageArr
+                                                                             : 64 * M;
 // (RHS == LSSVR_RHS_ARRAY_PM: point-major tables, read directly -- no staging area)
 // point-major tables: points fetched ahead of their use (measured at config 5, same box: 2 -> 102-104 us,
 // 4 -> 101-109 us, 6 and 8 -> 149 us (256 registers); plain instead of non-temporal loads: no difference)
 constexpr int kPrefetch = 4;
+// reaction rows: four streams; two points ahead keep the M = 9 kernel at two resident waves (four: 256 VGPRs + 14
+// AGPRs, one wave)
+constexpr int kPrefetchReact = 2;
 
-template <int M, int RHS, bool VC>
-__device__ __forceinline__ void enhance_small_body(const EnhanceArgs& p, const unsigned block,
+// RX (with VC): reaction rows -(a u')' + c u, p is an EnhanceReactArgs (lssvr_enhance_react).  Row k gains
+// c_k / scl^2 times L_{j+2}(t_k) minus its boundary combination C0_j + t_k C1_j (the eliminated columns 0 and
+// 1 are L_0 = 1 and L_1 = t), and phi_k the lifting term (c_k / scl^2) (d0 + t_k d1).
+template <int M, int RHS, bool VC, bool RX = false, typename Args = EnhanceArgs>
+__device__ __forceinline__ void enhance_small_body(const Args& p, const unsigned block,
                                                    double* __restrict__ tile) {
+  static_assert(!RX || VC, "reaction rows extend the variable-coefficient rows");
   constexpr int MR = M - 2;
   constexpr int NT = MR * (MR + 1) / 2;
 
@@ -150,10 +159,11 @@ __device__ __forceinline__ void enhance_small_body(const EnhanceArgs& p, const u
       // wave loads kStageK points of its 64 rows at a time with consecutive lanes on consecutive
       // doubles (full 64-byte runs of every row) into LDS, row pitch kStageK + 1 (conflict-free
       // when every lane then reads its own row).
-      [[maybe_unused]] double* const stg = tile + (tid >> 6) * kSmallTilePerWave<M, RHS, VC>;
+      [[maybe_unused]] double* const stg = tile + (tid >> 6) * kSmallTilePerWave<M, RHS, VC, RX>;
       [[maybe_unused]] const int64_t e0 = (int64_t)block * kBlock + (tid & ~63);
       // one collocation point k with its tabulated values (fk, and for variable coefficients a_k, a'_k)
-      auto point = [&](const int k, const double fk_tab, const double ak, const double dak) {
+      auto point = [&](const int k, const double fk_tab, const double ak, const double dak,
+                       [[maybe_unused]] const double ck) {
         const double xk = linspace_at(a, b, dm.oldlen, step, k, n);
         const double tk = dm.off + dm.scl * xk;
         double fk = 0.0, phi;
@@ -181,6 +191,14 @@ __device__ __forceinline__ void enhance_small_body(const EnhanceArgs& p, const u
           for (int j = 0; j < MR; ++j) rho[j] = fma(ak, rho[j], bk * (r1[j + 1] - C1[j]));
           phi = -fma(bk, d1, fk * inv_scl2);
         }
+        if constexpr (RX) {
+          const double cs = ck * inv_scl2;    // c / scl^2
+          double Lk[M];
+          legendre_p<M>(tk, Lk);
+#pragma unroll
+          for (int j = 0; j < MR; ++j) rho[j] = fma(-cs, Lk[j + 2] - fma(tk, C1[j], C0[j]), rho[j]);
+          phi = fma(cs, fma(tk, d1, d0), phi);
+        }
 #pragma unroll
         for (int i = 0; i < MR; ++i) {
 #pragma unroll
@@ -197,12 +215,16 @@ __device__ __forceinline__ void enhance_small_body(const EnhanceArgs& p, const u
         // are requested before the current kPrefetch are worked on (a point is ~110 instructions:
         // four of them cover the latency of HBM with two resident waves per SIMD).  Past the last
         // point the index is clamped (in bounds, value unused).
+        constexpr int PF = RX ? kPrefetchReact : kPrefetch;
         const int64_t ps = p.tab_ps;
         const double* const tf = p.rhs_values + ec * p.tab_es;
         [[maybe_unused]] const double* const ta = VC ? p.a_values + ec * p.tab_es : nullptr;
         [[maybe_unused]] const double* const td = VC ? p.da_values + ec * p.tab_es : nullptr;
-        double cf[kPrefetch], ca[kPrefetch], cdv[kPrefetch];
-        auto fetch = [&](const int k, double& f_, double& a_, double& d_) {
+        [[maybe_unused]] const double* tc = nullptr;
+        if constexpr (RX) tc = p.c_values + ec * p.tab_es;
+        double cf[PF], ca[PF], cdv[PF];
+        [[maybe_unused]] double cc[PF];
+        auto fetch = [&](const int k, double& f_, double& a_, double& d_, [[maybe_unused]] double& c_) {
           const int64_t g = (int64_t)min(k, n - 1) * ps;
           f_ = __builtin_nontemporal_load(tf + g);
           if constexpr (VC) {
@@ -211,21 +233,24 @@ __device__ __forceinline__ void enhance_small_body(const EnhanceArgs& p, const u
           } else {
             a_ = d_ = 0.0;
           }
+          if constexpr (RX) c_ = __builtin_nontemporal_load(tc + g);
         };
 #pragma unroll
-        for (int i = 0; i < kPrefetch; ++i) fetch(i, cf[i], ca[i], cdv[i]);
-        for (int k = 0; k < n; k += kPrefetch) {
-          double nf[kPrefetch], na[kPrefetch], nd[kPrefetch];
+        for (int i = 0; i < PF; ++i) fetch(i, cf[i], ca[i], cdv[i], cc[i]);
+        for (int k = 0; k < n; k += PF) {
+          double nf[PF], na[PF], nd[PF];
+          [[maybe_unused]] double nc[PF];
 #pragma unroll
-          for (int i = 0; i < kPrefetch; ++i) fetch(k + kPrefetch + i, nf[i], na[i], nd[i]);
+          for (int i = 0; i < PF; ++i) fetch(k + PF + i, nf[i], na[i], nd[i], nc[i]);
 #pragma unroll
-          for (int i = 0; i < kPrefetch; ++i)
-            if (k + i < n) point(k + i, cf[i], ca[i], cdv[i]);
+          for (int i = 0; i < PF; ++i)
+            if (k + i < n) point(k + i, cf[i], ca[i], cdv[i], RX ? cc[i] : 0.0);
 #pragma unroll
-          for (int i = 0; i < kPrefetch; ++i) {
+          for (int i = 0; i < PF; ++i) {
             cf[i] = nf[i];
             ca[i] = na[i];
             cdv[i] = nd[i];
+            if constexpr (RX) cc[i] = nc[i];
           }
         }
       } else {
@@ -246,20 +271,22 @@ __device__ __forceinline__ void enhance_small_body(const EnhanceArgs& p, const u
                   stg[kStageArr + row * (kStageK + 1) + kk] = in ? p.a_values[g] : 0.0;
                   stg[2 * kStageArr + row * (kStageK + 1) + kk] = in ? p.da_values[g] : 0.0;
                 }
+                if constexpr (RX) stg[3 * kStageArr + row * (kStageK + 1) + kk] = in ? p.c_values[g] : 0.0;
               }
               __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
               __builtin_amdgcn_wave_barrier();
             }
           }
-          double fk = 0.0, ak = 0.0, dak = 0.0;
+          double fk = 0.0, ak = 0.0, dak = 0.0, ck = 0.0;
           if constexpr (RHS == LSSVR_RHS_ARRAY) {
             fk = stg[lane * (kStageK + 1) + (k & (kStageK - 1))];
             if constexpr (VC) {
               ak = stg[kStageArr + lane * (kStageK + 1) + (k & (kStageK - 1))];
               dak = stg[2 * kStageArr + lane * (kStageK + 1) + (k & (kStageK - 1))];
             }
+            if constexpr (RX) ck = stg[3 * kStageArr + lane * (kStageK + 1) + (k & (kStageK - 1))];
           }
-          point(k, fk, ak, dak);
+          point(k, fk, ak, dak, ck);
         }
       }
       if constexpr (!VC) G[0] = 9.0 * (double)n;
@@ -354,7 +381,7 @@ __device__ __forceinline__ void enhance_small_body(const EnhanceArgs& p, const u
   // --- coalesced store: each wave transposes its own 64 x M tile through LDS --------
   // (wave-private, so no workgroup barrier: a wave that finishes early stores early;
   // LDS operations of one wave execute in order)
-  double* const wt = tile + (tid >> 6) * kSmallTilePerWave<M, RHS, VC>;
+  double* const wt = tile + (tid >> 6) * kSmallTilePerWave<M, RHS, VC, RX>;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // (the staging reads are done)
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -400,6 +427,13 @@ template <int M, int RHS>
 __global__ __launch_bounds__(kBlock) void enhance_small_refine_kernel(EnhanceArgs p) {
   __shared__ double tile[(kBlock / 64) * kChebTilePerWave<M, RHS>];
   enhance_small_body_cheb<M, RHS, true>(p, blockIdx.x, tile);
+}
+
+// Reaction rows -(a u')' + c u = f (lssvr_enhance_react): the variable-coefficient lane kernel with the c table
+template <int M, int RHS>
+__global__ __launch_bounds__(kBlock) void enhance_small_react_kernel(EnhanceReactArgs p) {
+  __shared__ double tile[(kBlock / 64) * kSmallTilePerWave<M, RHS, true, true>];
+  enhance_small_body<M, RHS, true, true, EnhanceReactArgs>(p, blockIdx.x, tile);
 }
 
 // One launch for a whole step of the hot path on one mesh: blocks [0, eblocks) run the
@@ -505,6 +539,14 @@ static hipError_t launch_step_vc(const EnhanceArgs& e, const P1Args& a, const Qu
     if (a.rhs_id == LSSVR_RHS_SIN) return launch_small<MM, LSSVR_RHS_SIN, false>(a, s, o); \
     if (a.tab_ps != 1) return launch_small<MM, LSSVR_RHS_ARRAY_PM, false>(a, s, o);  \
     return launch_small<MM, LSSVR_RHS_ARRAY, false>(a, s, o);
+// the reaction kernels (enhance_small_e.hip instantiates every M)
+#define LSSVR_SMALL_CASE_REACT(MM)                                                                          \
+  case MM: {                                                                                                \
+    const unsigned blocks = (unsigned)((a.ne + kBlock - 1) / kBlock);                                       \
+    if (a.tab_ps != 1)                                                                                      \
+      return launch(enhance_small_react_kernel<MM, LSSVR_RHS_ARRAY_PM>, dim3(blocks), dim3(kBlock), s, o, a); \
+    return launch(enhance_small_react_kernel<MM, LSSVR_RHS_ARRAY>, dim3(blocks), dim3(kBlock), s, o, a);    \
+  }
 #define LSSVR_SMALL_CASE_STEP(MM) \
   case MM:                        \
     return launch_step<MM>(e, a, q, s, o);

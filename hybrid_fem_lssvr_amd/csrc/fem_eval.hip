@@ -82,6 +82,25 @@ hipError_t p1_assemble(const P1Args& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+template <bool SIN>
+__global__ __launch_bounds__(kBlock) void p1_assemble_react_kernel(P1ReactArgs p, QuadRule q) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= p.ne;
+       i += (int64_t)gridDim.x * kBlock)
+    p1_node_react<SIN>(p, q, i);
+}
+
+hipError_t p1_assemble_react(const P1ReactArgs& a, hipStream_t s) {
+  QuadRule q;
+  if (!quad_rule(a.nquad, q)) return hipErrorInvalidValue;
+  const int64_t nn = a.ne + 1;
+  const unsigned blocks = (unsigned)((nn + kBlock - 1) / kBlock < 16384 ? (nn + kBlock - 1) / kBlock : 16384);
+  if (a.rhs_id == LSSVR_RHS_SIN)
+    hipLaunchKernelGGL(p1_assemble_react_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, a, q);
+  else
+    hipLaunchKernelGGL(p1_assemble_react_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, a, q);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // evaluate_solution (Dual.py:176-203)
 // ---------------------------------------------------------------------------

@@ -51,6 +51,12 @@ struct EnhanceArgs {
   TrigTables trig;          // sin / cos polynomial coefficients (SGPR operands), set by capi.hip
 };
 
+// reaction rows -(a u')' + c u = f: the variable-coefficient arguments plus the c table (same layout as the other
+// three).  A struct of its own: the kernels that take EnhanceArgs keep their argument block.
+struct EnhanceReactArgs : EnhanceArgs {
+  const double* c_values;
+};
+
 // Optional per-launch profiling: a kernel with an event attached (start, stop, or both; either may be
 // NULL) goes through hipExtLaunchKernelGGL, which stamps them with the dispatch's own begin/end times.
 struct LaunchOpts {
@@ -101,6 +107,11 @@ inline unsigned cu_count() {
 
 hipError_t enhance_small(const EnhanceArgs& a, hipStream_t s, const LaunchOpts* o = nullptr);
 hipError_t enhance_large(const EnhanceArgs& a, hipStream_t s, const LaunchOpts* o = nullptr);
+// reaction rows (a.a_values, a.da_values, a.c_values, a.rhs_values non-null), primal solve, n >= M - 2: the lane
+// kernel up to kReactSmallMaxM (the degrees it holds in registers without scratch), the MFMA kernel above
+constexpr int kReactSmallMaxM = 16;
+hipError_t enhance_small_react(const EnhanceReactArgs& a, hipStream_t s, const LaunchOpts* o = nullptr);
+hipError_t enhance_large_react(const EnhanceReactArgs& a, hipStream_t s, const LaunchOpts* o = nullptr);
 // Poisson rows, any M <= 33: Chebyshev-moment Gram (enhance_large_cheb.hip, enhance_large_parity.hip): a
 // sequence of kernels with a workspace of enhance_moment_ws_bytes(ne, M, n) bytes in between
 int enhance_refine_steps(int M, int n);
@@ -138,6 +149,11 @@ struct P1Args {
   double* floc;
 };
 hipError_t p1_assemble(const P1Args& a, hipStream_t s);
+// -(a u')' + c u: P1Args plus c at the quadrature points; the consistent mass matrix joins diag and off
+struct P1ReactArgs : P1Args {
+  const double* c_quad;
+};
+hipError_t p1_assemble_react(const P1ReactArgs& a, hipStream_t s);
 // assembly + enhancement of the same mesh in ONE launch (lane-per-element path, in-kernel rhs)
 hipError_t step_small(const EnhanceArgs& e, const P1Args& a, hipStream_t s,
                       const LaunchOpts* o = nullptr);
@@ -191,6 +207,10 @@ struct EstimateVcArgs : EstimateArgs {
   const double* da_values;
   const double* a_ends;
 };
+// -(a u')' + c u = f: plus the c table at the same points, same layout
+struct EstimateReactArgs : EstimateVcArgs {
+  const double* c_values;
+};
 bool gauss_rule(int nq, double* xi, double* wt);       // host; false: nq outside [1, kAdaptMaxNq]
 int64_t adapt_work_bytes(int64_t ne);
 hipError_t eval_deriv(const double* x, const double* W, int64_t ne, int M, int order, const double* xq,
@@ -199,6 +219,7 @@ hipError_t estimate_points(const double* x, int64_t ne, int nq, double* xq, hipS
 // rhs_mode: 0 = table element-major, 1 = amp*sin(omega x) in-kernel, 2 = table point-major
 hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s);
 hipError_t estimate_varcoef(EstimateVcArgs a, bool point_major, double* out3, hipStream_t s);
+hipError_t estimate_react(EstimateReactArgs a, bool point_major, double* out3, hipStream_t s);
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                   double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s);
 

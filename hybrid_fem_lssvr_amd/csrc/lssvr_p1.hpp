@@ -103,4 +103,56 @@ __device__ __forceinline__ void p1_node(const P1Args& p, const QuadRule& q, int6
   band_store(p, &p.load[i], l);
 }
 
+// ---------------------------------------------------------------------------
+// reaction term: the consistent P1 mass matrix of c,
+//   m_e[i][j] = h_e sum_q w_q c(x_q) phi_i(xi_q) phi_j(xi_q),  phi_0 = 1 - xi, phi_1 = xi
+// ---------------------------------------------------------------------------
+struct ElemMass {
+  double ll, lr, rr;
+};
+
+__device__ __forceinline__ ElemMass p1_element_mass(const P1ReactArgs& p, const QuadRule& q, int64_t e) {
+  const double h = p.x[e + 1] - p.x[e];
+  double ll = 0.0, lr = 0.0, rr = 0.0;
+  for (int k = 0; k < p.nquad; ++k) {
+    const double xi = q.xi[k];
+    const double wc = q.wt[k] * p.c_quad[e * p.nquad + k];
+    ll += wc * ((1.0 - xi) * (1.0 - xi));
+    lr += wc * ((1.0 - xi) * xi);
+    rr += wc * (xi * xi);
+  }
+  ElemMass m;
+  m.ll = h * ll;
+  m.lr = h * lr;
+  m.rr = h * rr;
+  return m;
+}
+
+// p1_node with the mass matrix in the bands: diag gains m_ll of the right and m_rr of the left element, off is
+// -k + m_lr; load, kloc (= abar / h) and floc as in p1_node.  Same race-free gather per node.
+template <bool SIN>
+__device__ __forceinline__ void p1_node_react(const P1ReactArgs& p, const QuadRule& q, int64_t i) {
+  double d = 0.0, l = 0.0;
+  if (i < p.ne) {
+    const ElemLocal r = p1_element<SIN>(p, q, i);
+    const ElemMass m = p1_element_mass(p, q, i);
+    d += r.k + m.ll;
+    l += r.fl;
+    band_store(p, &p.off[i], m.lr - r.k);
+    if (p.kloc) p.kloc[i] = r.k;
+    if (p.floc) {
+      p.floc[2 * i] = r.fl;
+      p.floc[2 * i + 1] = r.fr;
+    }
+  }
+  if (i > 0) {
+    const ElemLocal r = p1_element<SIN>(p, q, i - 1);
+    const ElemMass m = p1_element_mass(p, q, i - 1);
+    d += r.k + m.rr;
+    l += r.fr;
+  }
+  band_store(p, &p.diag[i], d);
+  band_store(p, &p.load[i], l);
+}
+
 }  // namespace lssvr

@@ -435,23 +435,41 @@ class StepPlan:
 
 def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *, elem_offset=0,
                     ne_global=None, global_domain=None, bc=(0.0, 0.0), out=None, status=None,
-                    fail_count=None, stream=None, profiled=False, point_major=False, repeats=None):
+                    fail_count=None, stream=None, profiled=False, point_major=False, repeats=None,
+                    c_values=None):
     """BASELINE config 5: rows -a (2/h)^2 L'' - a' (2/h) L' (no reference counterpart; the
     operator it generalises is Dual.py:43-44).  ``profiled``: BLOCKING, returns the launch
     duration in seconds (the dispatch's own begin / end stamps) instead of (W, status); with
     ``repeats=k`` the list of the durations of k launches back to back, one synchronisation at the end.
     ``point_major``: the three tables are float64[n_colloc, ne] (``t[k, e]``) instead of
-    float64[ne, n_colloc] -- see :func:`colloc_points`; the fast layout for M <= 22."""
+    float64[ne, n_colloc] -- see :func:`colloc_points`; the fast layout for M <= 22.
+    ``c_values`` (same shape as the other tables): the reaction rows of -(a u')' + c u = f
+    (``lssvr_enhance_react_ws``: primal solve only, ``n_colloc >= M - 2``, no ``repeats``); ``None`` is the
+    call without it."""
     lib = _capi.load()
     ne, ne_global = _shard(x, u, elem_offset, ne_global)
     for t, nm in ((a_values, "a_values"), (da_values, "da_values"), (rhs_values, "rhs_values")):
         _dev(t, nm)
         if t.numel() != ne * n_colloc:
             raise ValueError(f"{nm} must hold ne*n_colloc doubles")
+    if c_values is not None:
+        _rhs(None, c_values, ne * n_colloc, "ne*n_colloc", name="c_values")
+        if repeats is not None:
+            raise ValueError("repeats is not available with c_values (lssvr_enhance_react_ws has no sequence form)")
     if global_domain is None:
         ends = torch.stack([x[0], x[-1]]).cpu()
         global_domain = (float(ends[0]), float(ends[1]))
     out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
+    if c_values is not None:
+        args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]),
+                float(global_domain[1]), float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
+                _ptr(a_values), _ptr(da_values), _ptr(c_values), _ptr(rhs_values),
+                TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, _ptr(out), _ptr(status),
+                _ptr(fail_count), None, 0, _stream(stream))
+        if profiled:
+            return _timed(lib, "lssvr_enhance_react_ws", args)
+        _capi.check(lib.lssvr_enhance_react_ws(*args, None), "lssvr_enhance_react_ws")
+        return out, status
     args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]), float(global_domain[1]),
             float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma), _ptr(a_values), _ptr(da_values),
             _ptr(rhs_values), TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, _ptr(out), _ptr(status),
@@ -554,9 +572,11 @@ def quad_points(x, nquad=2, *, stream=None):
 
 
 def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, a_quad=None,
-                want_local=False, out=None, stream=None):
+                want_local=False, out=None, stream=None, c_quad=None):
     """Element-local P1 stiffness/load and the assembled tridiagonal bands
-    (Dual.py:117-128).  Returns dict(diag[ne+1], off[ne], load[ne+1][, kloc, floc])."""
+    (Dual.py:117-128).  Returns dict(diag[ne+1], off[ne], load[ne+1][, kloc, floc]).
+    ``c_quad`` float64[ne, nquad] (c at :func:`quad_points`): the consistent mass matrix of the reaction term
+    joins ``diag`` and ``off`` (``lssvr_p1_assemble_react``); ``None`` is the call without it."""
     lib = _capi.load()
     _dev(x, "x")
     ne = x.numel() - 1
@@ -564,6 +584,13 @@ def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, 
     rhs_id, params = _rhs(rhs, rhs_quad, ne * nquad, "ne*nquad", name="rhs_quad")
     if a_quad is not None:
         _dev(a_quad, "a_quad")
+    if c_quad is not None:
+        _rhs(None, c_quad, ne * nquad, "ne*nquad", name="c_quad")
+        rc = lib.lssvr_p1_assemble_react(_ptr(x), ne, int(nquad), rhs_id, params, _ptr(rhs_quad), _ptr(a_quad),
+                                         _ptr(c_quad), _ptr(out["diag"]), _ptr(out["off"]), _ptr(out["load"]),
+                                         _ptr(out.get("kloc")), _ptr(out.get("floc")), _stream(stream))
+        _capi.check(rc, "lssvr_p1_assemble_react")
+        return out
     rc = lib.lssvr_p1_assemble(_ptr(x), ne, int(nquad), rhs_id, params, _ptr(rhs_quad),
                                _ptr(a_quad), _ptr(out["diag"]), _ptr(out["off"]),
                                _ptr(out["load"]), _ptr(out.get("kloc")), _ptr(out.get("floc")),
@@ -763,13 +790,15 @@ def estimate(x, W, nq, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_values=None, poi
 
 
 def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point_major=False, want_jump=False,
-                     work=None, stream=None):
+                     work=None, stream=None, c_values=None):
     """:func:`estimate` for -(a u')' = f (``lssvr_estimate_varcoef``):
     eta2[e] = h^2 int_e (f + a u_e'' + a' u_e')^2 + h/2 (J_e^2 + J_{e+1}^2), J the jump of the flux a u'.
     ``a_values``, ``da_values``, ``rhs_values``: a, a' and f at :func:`estimate_points`, float64[ne, nq] or,
     with ``point_major``, float64[nq, ne]; ``a_ends`` float64[ne, 2]: a at the left and right end of every
     element, seen from inside it.  Returns (eta2 float64[ne], jump float64[ne+1] | None, out3 device
-    float64[3] = {sum, max of the finite eta2, non-finite count})."""
+    float64[3] = {sum, max of the finite eta2, non-finite count}).
+    ``c_values`` (shape of the other tables): the residual of -(a u')' + c u = f, f + a u_e'' + a' u_e' - c u_e
+    (``lssvr_estimate_react``); ``None`` is the call without it."""
     lib = _capi.load()
     _dev(x, "x")
     _dev(W, "W")
@@ -778,7 +807,10 @@ def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point
     if W.dim() != 2 or W.shape[0] != ne:
         raise ValueError("W must be [ne, M]")
     shape = (nq, ne) if point_major else (ne, nq)
-    for t, nm in ((a_values, "a_values"), (da_values, "da_values"), (rhs_values, "rhs_values")):
+    tables = ((a_values, "a_values"), (da_values, "da_values"), (rhs_values, "rhs_values"))
+    if c_values is not None:
+        tables += ((c_values, "c_values"),)
+    for t, nm in tables:
         _dev(t, nm)
         if tuple(t.shape) != shape:
             raise ValueError(f"{nm} must be {'[nq, ne]' if point_major else '[ne, nq]'} = {list(shape)}, "
@@ -790,6 +822,13 @@ def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point
     jump = torch.empty(ne + 1, dtype=torch.float64, device=x.device) if want_jump else None
     out3 = torch.empty(3, dtype=torch.float64, device=x.device)
     work = _check_work(work, x, ne)
+    if c_values is not None:
+        rc = lib.lssvr_estimate_react(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, _ptr(a_values), _ptr(da_values),
+                                      _ptr(c_values), _ptr(rhs_values),
+                                      TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, _ptr(a_ends),
+                                      _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work), _stream(stream))
+        _capi.check(rc, "lssvr_estimate_react")
+        return eta2, jump, out3
     rc = lib.lssvr_estimate_varcoef(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, _ptr(a_values), _ptr(da_values),
                                     _ptr(rhs_values), TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR,
                                     _ptr(a_ends), _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work), _stream(stream))

@@ -23,7 +23,8 @@ mesh/basis or node array instead of ``np.linspace(a, b, num_fem_nodes)``), ``fem
 (``ops.SOLVER_PRIMAL`` default; ``ops.SOLVER_SHARED``: uniform meshes only, one shared operator
 applied per element), ``coef`` (a pair ``(a, da)`` of numpy-vectorised callables:
 solve, estimate and refine ``-(a u')' = f`` instead of ``-u'' = f``, BASELINE config 5 and DESIGN.md
-section 11; ``None`` keeps the Poisson rows).
+section 11; ``None`` keeps the Poisson rows), ``reaction`` (a numpy-vectorised callable ``c >= 0``: solve,
+estimate and refine ``-(a u')' + c u = f``; without ``coef``, a = 1; ``None``: no such term).
 """
 from __future__ import annotations
 
@@ -125,6 +126,14 @@ def _tabulate(funcs, pts, point_major=False):
             t = np.broadcast_to(t, xh.shape)
         out.append(_to_dev(t.T if point_major else t, pts.device))
     return out
+
+
+def _one(x):
+    return np.ones_like(np.asarray(x, dtype=np.float64))
+
+
+def _zero(x):
+    return np.zeros_like(np.asarray(x, dtype=np.float64))
 
 
 def _enhance(x, u, M, gamma, n_colloc, *, global_domain, bc, solver, uniform_rtol=1e-9, **kw):
@@ -304,7 +313,7 @@ def lssvr_primal(rhs_func, domain_range, u_xmin, u_xmax, M, gamma,
 class FEMLSSVRPrimalSolver:
     def __init__(self, num_fem_nodes=5, lssvr_M=12, lssvr_gamma=1e6, global_domain=(-1, 1), *,
                  n_colloc=12, rhs=poisson_rhs, nquad=2, mesh=None, device="cuda:0",
-                 solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None):
+                 solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None):
         # Dual.py:101-108
         self.num_fem_nodes = num_fem_nodes
         self.lssvr_M = lssvr_M
@@ -333,6 +342,16 @@ class FEMLSSVRPrimalSolver:
                                     if solver == ops.SOLVER_SHARED else ""))
             coef = tuple(coef)
         self.coef = coef
+        if reaction is not None:
+            if not callable(reaction):
+                raise ValueError("reaction must be a callable c(x)")
+            if fem_solver == "flux":
+                raise ValueError("reaction needs fem_solver='bands': the flux solve factors A = D^T K D, "
+                                 "which a mass matrix breaks")
+            if solver != ops.SOLVER_PRIMAL:
+                raise ValueError("reaction needs solver=ops.SOLVER_PRIMAL: the reaction rows have a primal "
+                                 "solve only")
+        self.reaction = reaction
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
         self._x_dev = None
@@ -354,6 +373,12 @@ class FEMLSSVRPrimalSolver:
         kw = {}
         if self.coef is not None:        # kloc = abar / h, abar the quadrature mean of a
             kw["a_quad"] = _tabulate(self.coef[:1], ops.quad_points(x, self.nquad))[0]
+        if self.reaction is not None:    # consistent mass matrix of c in the bands
+            cq = _tabulate((self.reaction,), ops.quad_points(x, self.nquad))[0]
+            if bool((cq < 0).any().item()):
+                raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
+                                 "pivot and assumes an SPD matrix (c >= 0)")
+            kw["c_quad"] = cq
         if isinstance(self.rhs, SinRHS):
             bands = ops.p1_assemble(x, self.nquad, rhs=(self.rhs.amp, self.rhs.omega), want_local=True, **kw)
         else:
@@ -394,7 +419,14 @@ class FEMLSSVRPrimalSolver:
         gd = (float(self.global_domain[0]), float(self.global_domain[1]))
         bc = (main_boundary_condition_left(self.global_domain[0]),
               main_boundary_condition_right(self.global_domain[1]))
-        if self.coef is None:
+        if self.reaction is not None:
+            # tables only, like the varcoef kernels; point-major for the lane kernel
+            pm = int(self.lssvr_M) <= 22
+            a, da = self.coef if self.coef is not None else (_one, _zero)
+            ta, tda, tf, tc = _tabulate((a, da, self.rhs, self.reaction), ops.colloc_points(x, self.n_colloc), pm)
+            W, st = ops.enhance_varcoef(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc),
+                                        ta, tda, tf, global_domain=gd, bc=bc, point_major=pm, c_values=tc)
+        elif self.coef is None:
             kw = _rhs_mode(self.rhs, x, self.n_colloc, self.lssvr_M)
             W, st = _enhance(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc),
                              global_domain=gd, bc=bc, solver=self.solver_id, **kw)
@@ -441,6 +473,13 @@ class FEMLSSVRPrimalSolver:
         if self.enhanced is None:
             raise RuntimeError("call solve() first")
         x, W = self.enhanced.nodes, self.enhanced.W
+        if self.reaction is not None:
+            a, da = self.coef if self.coef is not None else (_one, _zero)
+            ta, tda, tf, tc = _tabulate((a, da, self.rhs, self.reaction), ops.estimate_points(x, nq), True)
+            an = np.broadcast_to(np.asarray(a(x.cpu().numpy()), dtype=np.float64), (x.numel(),))
+            a_ends = _to_dev(np.stack([an[:-1], an[1:]], axis=1), x.device)
+            eta2, _, out3 = ops.estimate_varcoef(x, W, nq, ta, tda, tf, a_ends, point_major=True, c_values=tc)
+            return eta2, out3
         if self.coef is not None:
             # a, a', f at the Gauss points (point-major: coalesced); a at the nodes from both sides, aL = aR
             tabs = _tabulate((self.coef[0], self.coef[1], self.rhs), ops.estimate_points(x, nq), True)
@@ -471,7 +510,8 @@ class FEMLSSVRPrimalSolver:
         eta_e^2 = h_e^2 int_e (f + u_e'')^2 dx + h_e/2 (J_e^2 + J_{e+1}^2), J = jump of u' at the
         nodes (0 at the Dirichlet ends), ``nq``-point Gauss (default max(lssvr_M, 8)).  With ``coef = (a, da)``
         the residual is f + a u_e'' + a' u_e' and J the jump of the flux a u' (a at the nodes from both sides:
-        a callable coefficient is continuous there; ``ops.estimate_varcoef`` takes one-sided values)."""
+        a callable coefficient is continuous there; ``ops.estimate_varcoef`` takes one-sided values); with
+        ``reaction = c`` the residual is f + a u_e'' + a' u_e' - c u_e."""
         nq = self._nq(nq)
         eta2, _ = self._estimate_dev(nq)
         return eta2.cpu().numpy()

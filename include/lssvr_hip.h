@@ -489,6 +489,63 @@ int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* 
                  double theta, double h_min, void* work, double* x_new, int64_t* parent,
                  int64_t* ne_new_dev, void* stream);
 
+/*
+ * Reaction term: -(a u')' + c u = f, a > 0 (no reference counterpart, like the variable coefficient).
+ * ADDITIVE to ABI 7: the four entries below are new symbols, no existing entry, struct or constant changes, and
+ * LSSVR_ABI_VERSION stays 7.  A caller that needs them tests for the symbol (dlsym / hasattr).
+ *
+ * lssvr_enhance_react -- lssvr_enhance_varcoef plus c_values, tabulated at the collocation points like a_values.
+ * With s = 2/h, PDE row k of element e is
+ *   -a_k s^2 L_p''(t_k) - da_k s L_p'(t_k) + c_k L_p(t_k).
+ * The boundary rows, gamma, the BC-eliminated solve and the fallback status are those of lssvr_enhance_varcoef.
+ * Primal solve only: n_colloc < M-2 is LSSVR_ERR_SOLVER (no dual form of these rows).  M <= 16 runs the lane
+ * kernel, 17 <= M <= 33 the wave-cooperative MFMA kernel.  c of either sign is accepted here (the rows stay a
+ * least-squares fit); the P1 solve is what needs c >= 0.
+ * lssvr_enhance_react_ws -- with table_layout (LSSVR_TABLE_*, all FOUR tables alike), a workspace argument pair
+ * kept for symmetry with lssvr_enhance_varcoef_ws (lssvr_enhance_varcoef_work_bytes() = 0 bytes are needed) and
+ * kernel_ms_host (BLOCKING measurement aid).
+ */
+int lssvr_enhance_react(const double* x, const double* u, int64_t ne,
+                        int64_t elem_offset, int64_t ne_global,
+                        double gxmin, double gxmax, double bc_left, double bc_right,
+                        int M, int n_colloc, double gamma,
+                        const double* a_values, const double* da_values, const double* c_values,
+                        const double* rhs_values,
+                        double* W, int32_t* status, int32_t* fail_count, void* stream);
+int lssvr_enhance_react_ws(const double* x, const double* u, int64_t ne,
+                           int64_t elem_offset, int64_t ne_global,
+                           double gxmin, double gxmax, double bc_left, double bc_right,
+                           int M, int n_colloc, double gamma,
+                           const double* a_values, const double* da_values, const double* c_values,
+                           const double* rhs_values, int table_layout,
+                           double* W, int32_t* status, int32_t* fail_count,
+                           void* work, int64_t work_bytes, void* stream, float* kernel_ms_host);
+
+/*
+ * lssvr_p1_assemble_react -- lssvr_p1_assemble plus c_quad[e*nquad + q] (c at lssvr_quad_points): the consistent
+ * mass matrix
+ *   m_e[i][j] = h_e sum_q w_q c(x_q) phi_i(xi_q) phi_j(xi_q)
+ * joins the bands: diag[i] += m_i[0][0] + m_{i-1}[1][1], off[i] = -abar_i/h_i + m_i[0][1].  load, kloc (= abar/h)
+ * and floc are those of lssvr_p1_assemble.  c_quad == NULL IS lssvr_p1_assemble (same launch, same bits).
+ * lssvr_tridiag_dirichlet_solve takes the bands as they are; it does not pivot, so the caller keeps the matrix
+ * SPD (c >= 0).  lssvr_p1_flux_solve does not apply (it factors A = D^T K D, which a mass matrix breaks).
+ */
+int lssvr_p1_assemble_react(const double* x, int64_t ne, int nquad,
+                            int rhs_id, const double* rhs_params_host, const double* rhs_quad,
+                            const double* a_quad, const double* c_quad,
+                            double* diag, double* off, double* load,
+                            double* kloc, double* floc, void* stream);
+
+/*
+ * lssvr_estimate_react -- lssvr_estimate_varcoef plus c_values at lssvr_estimate_points (same table_layout):
+ *   eta2[e] = h_e^2 * int_e (f + a u_e'' + a' u_e' - c u_e)^2 dx + h_e/2 * (J_e^2 + J_{e+1}^2),
+ * J the jump of the flux a u' as in lssvr_estimate_varcoef.  Same reduction: no atomics, bitwise reproducible.
+ */
+int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, int nq,
+                         const double* a_values, const double* da_values, const double* c_values,
+                         const double* rhs_values, int table_layout, const double* a_ends,
+                         double* eta2, double* jump, double* out3, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,10 +2,11 @@
 section 11): lssvr_estimate (M = 9, nq = 16, in-kernel sin rhs) and lssvr_refine (theta = 0.5), device
 events around `reps` back-to-back launches after a warm-up, beside lssvr_enhance on the same mesh.
 ``--varcoef`` adds lssvr_estimate_varcoef (same M and nq; a, a', f tables) in both table layouts.
+``--reaction`` (with ``--varcoef``) adds lssvr_estimate_react (a fourth table, c) and its ratio to the varcoef entry.
 Prints the algorithmic bytes and flops per element, the bound that applies and the fraction of it;
 ``--json PATH`` also writes the record as JSON.
 
-    python scripts/adapt_quick.py [--ne 1000000] [--reps 50] [--varcoef] [--json PATH]
+    python scripts/adapt_quick.py [--ne 1000000] [--reps 50] [--varcoef [--reaction]] [--json PATH]
 """
 import argparse
 import json
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--ne", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--varcoef", action="store_true", help="also time lssvr_estimate_varcoef, both layouts")
+    ap.add_argument("--reaction", action="store_true", help="with --varcoef: also time lssvr_estimate_react")
     ap.add_argument("--json", default=None, help="write the record to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -115,6 +117,18 @@ def main():
             key = "estimate_varcoef_" + ("point_major" if pm else "element_major")
             rec[key] = roofline("lssvr_estimate_varcoef (%s)" % ("point-major" if pm else "element-major"),
                                 t_vc, ne, vc_bytes, vc_flops)
+            if args.reaction:
+                c_tab = 2.0 + torch.cos(2.0 * np.pi * xq)
+                c_tab = c_tab.t().contiguous() if pm else c_tab
+                t_rx = timeit(lambda: ops.estimate_varcoef(x, W, nq, *tt, a_ends, point_major=pm, work=work,
+                                                           c_values=c_tab), args.reps)
+                key = "estimate_react_" + ("point_major" if pm else "element_major")
+                # one more table; per point one more M-term sum (u) and 2 for -c u
+                rec[key] = roofline("lssvr_estimate_react   (%s)" % ("point-major" if pm else "element-major"),
+                                    t_rx, ne, vc_bytes + nq * 8, vc_flops + nq * (2 * (M - 1) + 2))
+                rec[key]["over_varcoef"] = t_rx / t_vc
+                print(f"    estimate_react / estimate_varcoef = {t_rx / t_vc:.3f} (bytes {vc_bytes + nq * 8} / "
+                      f"{vc_bytes} = {(vc_bytes + nq * 8) / vc_bytes:.3f})")
     if args.json:
         with open(args.json, "w") as fh:
             json.dump(rec, fh, indent=1)
