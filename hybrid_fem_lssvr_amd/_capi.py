@@ -35,121 +35,85 @@ _c_i64 = C.c_int64
 _c_int = C.c_int
 _c_dbl = C.c_double
 
-# name -> (restype, argtypes); mirrors include/lssvr_hip.h declaration by declaration
+_c_hd = C.POINTER(_c_dbl)   # host double*: rhs parameters, Gauss rules
+_c_hf = C.POINTER(C.c_float)   # host float*: kernel durations in ms
+
+# the argument groups the header's declarations are made of
+_SHARD = [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,      # x, u, ne, elem_offset, ne_global
+          _c_dbl, _c_dbl, _c_dbl, _c_dbl,            # gxmin, gxmax, bc_left, bc_right
+          _c_int, _c_int, _c_dbl]                    # M, n_colloc, gamma
+_SUBSET = [_c_dp, _c_dp, _c_i64, _c_dp, _c_i64, _c_i64, _c_i64,     # x, u, ne_mesh, elem_ids, nsub, offset, ne_global
+           _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_int, _c_int, _c_dbl, _c_dp]    # ..., M, n_colloc, gamma, gamma_values
+_RHS = [_c_int, _c_hd, _c_dp]                        # rhs_id, rhs_params_host, rhs_values / rhs_quad
+_VC_TABLES = [_c_dp, _c_dp, _c_dp]                   # a_values, da_values, rhs_values
+_REACT_TABLES = [_c_dp, _c_dp, _c_dp, _c_dp]         # a_values, da_values, c_values, rhs_values
+_OUT = [_c_dp, _c_dp, _c_dp]                         # W, status, fail_count
+_WS = [_c_dp, _c_i64]                                # work, work_bytes
+_BANDS = [_c_dp, _c_dp, _c_dp]                       # diag, off, load
+_LOCAL = [_c_dp, _c_dp]                              # kloc, floc
+_STREAM = [_c_dp]
+_TIMED = [_c_hf]                                     # kernel_ms_host
+_SEQ = [_c_int, _c_hf]                               # repeats, kernel_ms_host[repeats]
+_MESH = [_c_dp, _c_i64, _c_int]                      # x, ne, n_colloc / nquad / nq
+_SOLN = [_c_dp, _c_dp, _c_i64, _c_int]               # x, W, ne, M
+_EST_OUT = [_c_dp, _c_dp, _c_dp, _c_dp]              # eta2, jump, out3, work
+_STEP = _SHARD + [_c_hd, _c_int] + _BANDS + _OUT     # ..., rhs_params_host, nquad, bands, outputs
+
+
+def _sig(*groups, res=_c_int):
+    return res, [t for g in groups for t in g]
+
+
+# name -> (restype, argtypes); mirrors include/lssvr_hip.h declaration by declaration, one argument group each
+# (tests/test_capi_cpu.py parses the headers and compares every entry with this table)
 SIGNATURES = {
-    "lssvr_version": (_c_int, []),
-    "lssvr_last_error": (C.c_char_p, []),
-    "lssvr_enhance": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                               _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                               _c_int, _c_int, _c_dbl,
-                               _c_int, C.POINTER(_c_dbl), _c_dp, _c_int,
-                               _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_enhance_work_bytes": (_c_i64, [_c_i64, _c_int, _c_int, _c_int]),
-    "lssvr_enhance_ws": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                  _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                  _c_int, _c_int, _c_dbl,
-                                  _c_int, C.POINTER(_c_dbl), _c_dp, _c_int,
-                                  _c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_dp, C.POINTER(C.c_float)]),
-    "lssvr_enhance_ws_sequence": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                           _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                           _c_int, _c_int, _c_dbl,
-                                           _c_int, C.POINTER(_c_dbl), _c_dp, _c_int,
-                                           _c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_dp,
-                                           _c_int, C.POINTER(C.c_float)]),
-    "lssvr_enhance_profiled": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                        _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                        _c_int, _c_int, _c_dbl,
-                                        _c_int, C.POINTER(_c_dbl), _c_dp, _c_int,
-                                        _c_dp, _c_dp, _c_dp, C.POINTER(C.c_float)]),
-    "lssvr_step": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                            _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                            _c_int, _c_int, _c_dbl, C.POINTER(_c_dbl), _c_int,
-                            _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_step_plan_create": (_c_int, [C.POINTER(C.c_void_p), _c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                        _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                        _c_int, _c_int, _c_dbl, C.POINTER(_c_dbl), _c_int,
-                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_step_plan_launch": (_c_int, [C.c_void_p, _c_dp]),
-    "lssvr_step_plan_destroy": (_c_int, [C.c_void_p]),
-    "lssvr_enhance_varcoef": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                       _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                       _c_int, _c_int, _c_dbl,
-                                       _c_dp, _c_dp, _c_dp,
-                                       _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_enhance_varcoef_work_bytes": (_c_i64, [_c_i64, _c_int, _c_int]),
-    "lssvr_enhance_varcoef_ws": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                          _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                          _c_int, _c_int, _c_dbl,
-                                          _c_dp, _c_dp, _c_dp, _c_int,
-                                          _c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_dp, C.POINTER(C.c_float)]),
-    "lssvr_enhance_varcoef_ws_sequence": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                                   _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                                   _c_int, _c_int, _c_dbl,
-                                                   _c_dp, _c_dp, _c_dp, _c_int,
-                                                   _c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_dp,
-                                                   _c_int, C.POINTER(C.c_float)]),
-    "lssvr_step_varcoef": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                    _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                    _c_int, _c_int, _c_dbl,
-                                    _c_dp, _c_dp, _c_dp, _c_int, _c_int, _c_dp, _c_dp,
-                                    _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_enhance_subset": (_c_int, [_c_dp, _c_dp, _c_i64, _c_dp, _c_i64, _c_i64, _c_i64,
-                                      _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                      _c_int, _c_int, _c_dbl, _c_dp,
-                                      _c_int, C.POINTER(_c_dbl), _c_dp,
-                                      _c_dp, _c_i64, _c_dp, _c_dp, _c_dp]),
-    "lssvr_enhance_subset_ws": (_c_int, [_c_dp, _c_dp, _c_i64, _c_dp, _c_i64, _c_i64, _c_i64,
-                                         _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                         _c_int, _c_int, _c_dbl, _c_dp,
-                                         _c_int, C.POINTER(_c_dbl), _c_dp,
-                                         _c_dp, _c_i64, _c_dp, _c_dp, _c_dp, _c_i64, _c_dp]),
-    "lssvr_enhance_shared": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                      _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                      _c_int, _c_int,
-                                      _c_int, C.POINTER(_c_dbl), _c_dp, _c_dp,
-                                      _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_float)]),
-    "lssvr_colloc_points": (_c_int, [_c_dp, _c_i64, _c_int, _c_dp, _c_dp]),
-    "lssvr_colloc_points_pm": (_c_int, [_c_dp, _c_i64, _c_int, _c_dp, _c_dp]),
-    "lssvr_p1_assemble": (_c_int, [_c_dp, _c_i64, _c_int, _c_int, C.POINTER(_c_dbl), _c_dp, _c_dp,
-                                   _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_quad_points": (_c_int, [_c_dp, _c_i64, _c_int, _c_dp, _c_dp]),
-    "lssvr_tridiag_work_bytes": (_c_i64, [_c_i64]),
-    "lssvr_tridiag_dirichlet_solve": (_c_int, [_c_dp, _c_dp, _c_dp, _c_i64, _c_dbl, _c_dbl,
-                                               _c_dp, _c_dp, _c_dp]),
-    "lssvr_p1_flux_work_bytes": (_c_i64, [_c_i64]),
-    "lssvr_p1_flux_solve": (_c_int, [_c_dp, _c_dp, _c_i64, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dp]),
-    "lssvr_p1_flux_aggregate": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_dp, _c_dp]),
-    "lssvr_p1_flux_finish": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_dp, _c_dp,
-                                      _c_dbl, _c_dbl, _c_dp, _c_dp]),
-    "lssvr_eval": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_i64, _c_dp, _c_dp, _c_dp]),
-    "lssvr_eval_error": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_i64, C.POINTER(_c_dbl), _c_dp, _c_dp]),
-    "lssvr_eval_deriv": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_i64, _c_dp, _c_dp, _c_dp]),
-    "lssvr_gauss_rule": (_c_int, [_c_int, C.POINTER(_c_dbl), C.POINTER(_c_dbl)]),
-    "lssvr_estimate_points": (_c_int, [_c_dp, _c_i64, _c_int, _c_dp, _c_dp]),
-    "lssvr_adapt_work_bytes": (_c_i64, [_c_i64]),
-    "lssvr_estimate": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_int, C.POINTER(_c_dbl), _c_dp,
-                                _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_estimate_varcoef": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_dp, _c_dp, _c_int, _c_dp,
-                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_refine": (_c_int, [_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "lssvr_version": _sig(),
+    "lssvr_last_error": _sig(res=C.c_char_p),
+    "lssvr_enhance": _sig(_SHARD, _RHS, [_c_int], _OUT, _STREAM),
+    "lssvr_enhance_work_bytes": _sig([_c_i64, _c_int, _c_int, _c_int], res=_c_i64),
+    "lssvr_enhance_ws": _sig(_SHARD, _RHS, [_c_int], _OUT, _WS, _STREAM, _TIMED),
+    "lssvr_enhance_ws_sequence": _sig(_SHARD, _RHS, [_c_int], _OUT, _WS, _STREAM, _SEQ),
+    "lssvr_enhance_profiled": _sig(_SHARD, _RHS, [_c_int], _OUT[:2], _STREAM, _TIMED),
+    "lssvr_step": _sig(_STEP, _STREAM),
+    "lssvr_step_plan_create": _sig([C.POINTER(C.c_void_p)], _STEP),
+    "lssvr_step_plan_launch": _sig([C.c_void_p], _STREAM),
+    "lssvr_step_plan_destroy": _sig([C.c_void_p]),
+    "lssvr_enhance_varcoef": _sig(_SHARD, _VC_TABLES, _OUT, _STREAM),
+    "lssvr_enhance_varcoef_work_bytes": _sig([_c_i64, _c_int, _c_int], res=_c_i64),
+    "lssvr_enhance_varcoef_ws": _sig(_SHARD, _VC_TABLES, [_c_int], _OUT, _WS, _STREAM, _TIMED),
+    "lssvr_enhance_varcoef_ws_sequence": _sig(_SHARD, _VC_TABLES, [_c_int], _OUT, _WS, _STREAM, _SEQ),
+    "lssvr_step_varcoef": _sig(_SHARD, _VC_TABLES, [_c_int, _c_int, _c_dp, _c_dp], _BANDS, _OUT, _STREAM),
+    "lssvr_enhance_subset": _sig(_SUBSET, _RHS, [_c_dp, _c_i64, _c_dp, _c_dp], _STREAM),
+    "lssvr_enhance_subset_ws": _sig(_SUBSET, _RHS, [_c_dp, _c_i64, _c_dp, _c_dp], _WS, _STREAM),
+    "lssvr_enhance_shared": _sig(_SHARD[:-1], _RHS, [_c_dp], _OUT, _STREAM, _TIMED),
+    "lssvr_colloc_points": _sig(_MESH, [_c_dp], _STREAM),
+    "lssvr_colloc_points_pm": _sig(_MESH, [_c_dp], _STREAM),
+    "lssvr_p1_assemble": _sig(_MESH, _RHS, [_c_dp], _BANDS, _LOCAL, _STREAM),
+    "lssvr_quad_points": _sig(_MESH, [_c_dp], _STREAM),
+    "lssvr_tridiag_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_tridiag_dirichlet_solve": _sig(_BANDS, [_c_i64, _c_dbl, _c_dbl, _c_dp, _c_dp], _STREAM),
+    "lssvr_p1_flux_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_p1_flux_solve": _sig([_c_dp, _c_dp, _c_i64, _c_dbl, _c_dbl, _c_dp, _c_dp], _STREAM),
+    "lssvr_p1_flux_aggregate": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_dp, _c_dp], _STREAM),
+    "lssvr_p1_flux_finish": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp],
+                                 _STREAM),
+    "lssvr_eval": _sig(_SOLN, [_c_dp, _c_i64, _c_dp, _c_dp], _STREAM),
+    "lssvr_eval_error": _sig(_SOLN, [_c_dp, _c_i64, _c_hd, _c_dp], _STREAM),
+    "lssvr_eval_deriv": _sig(_SOLN, [_c_int, _c_dp, _c_i64, _c_dp, _c_dp], _STREAM),
+    "lssvr_gauss_rule": _sig([_c_int, _c_hd, _c_hd]),
+    "lssvr_estimate_points": _sig(_MESH, [_c_dp], _STREAM),
+    "lssvr_adapt_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_estimate": _sig(_SOLN, [_c_int], _RHS, _EST_OUT, _STREAM),
+    "lssvr_estimate_varcoef": _sig(_SOLN, [_c_int], _VC_TABLES, [_c_int, _c_dp], _EST_OUT, _STREAM),
+    "lssvr_refine": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dp, _c_dp], _STREAM),
     # reaction term -(a u')' + c u = f (additive to ABI 7)
-    "lssvr_enhance_react": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                     _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                     _c_int, _c_int, _c_dbl,
-                                     _c_dp, _c_dp, _c_dp, _c_dp,
-                                     _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_enhance_react_ws": (_c_int, [_c_dp, _c_dp, _c_i64, _c_i64, _c_i64,
-                                        _c_dbl, _c_dbl, _c_dbl, _c_dbl,
-                                        _c_int, _c_int, _c_dbl,
-                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_int,
-                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_i64, _c_dp, C.POINTER(C.c_float)]),
-    "lssvr_p1_assemble_react": (_c_int, [_c_dp, _c_i64, _c_int, _c_int, C.POINTER(_c_dbl), _c_dp, _c_dp, _c_dp,
-                                         _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_estimate_react": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_int,
-                                      _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
-    "lssvr_fp64_probe": (_c_int, [_c_dp, _c_int, _c_int, _c_int, _c_dp]),
-    "lssvr_stream_probe": (_c_int, [_c_dp, _c_dp, _c_i64, _c_dp]),
-    "lssvr_row_chunk_probe": (_c_int, [_c_dp, _c_dp, _c_i64, _c_int, _c_int, _c_dp]),
+    "lssvr_enhance_react": _sig(_SHARD, _REACT_TABLES, _OUT, _STREAM),
+    "lssvr_enhance_react_ws": _sig(_SHARD, _REACT_TABLES, [_c_int], _OUT, _WS, _STREAM, _TIMED),
+    "lssvr_p1_assemble_react": _sig(_MESH, _RHS, [_c_dp, _c_dp], _BANDS, _LOCAL, _STREAM),
+    "lssvr_estimate_react": _sig(_SOLN, [_c_int], _REACT_TABLES, [_c_int, _c_dp], _EST_OUT, _STREAM),
+    "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
+    "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
+    "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),
 }
 
 _lib = None

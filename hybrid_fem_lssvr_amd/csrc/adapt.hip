@@ -7,6 +7,7 @@
 //   - threshold marking + bisection into a new ascending node array (lssvr_refine)
 // DESIGN.md section 11 has the derivation, the mapping and the measured numbers.
 #include <cmath>
+#include <type_traits>
 
 #include "lssvr_device.hpp"
 #include "lssvr_kernels.hpp"
@@ -758,84 +759,47 @@ hipError_t estimate_points(const double* x, int64_t ne, int nq, double* xq, hipS
   return hipGetLastError();
 }
 
-template <int MT>
-static hipError_t launch_estimate(const EstimateArgs& a, const GaussRuleN& g, int rhs, unsigned nb, size_t lds,
-                                  hipStream_t s) {
-  if (rhs == 1)
-    hipLaunchKernelGGL((estimate_kernel<MT, 1>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
-  else if (rhs == 2)
-    hipLaunchKernelGGL((estimate_kernel<MT, 2>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
-  else
-    hipLaunchKernelGGL((estimate_kernel<MT, 0>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
-  return hipGetLastError();
-}
-
-hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s) {
+// the host path the three estimators share: `pick(std::integral_constant<int, MT>)` names the kernel of the row
+// bucket MT; its LDS coefficient table holds tab_rows * MT + tab_extra doubles per quadrature point
+template <typename Args, typename Pick>
+static hipError_t launch_estimate_any(Args a, int tab_rows, int tab_extra, double* out3, hipStream_t s, Pick pick) {
   GaussRuleN g{};
   if (!gauss_rule(a.nq, g.xi, g.wt)) return hipErrorInvalidValue;
   a.ms = a.M | 1;                                   // odd row stride: conflict-free ds_read_b64
   const int64_t nb = est_blocks(a.ne);
   const int MT = a.M <= 12 ? 12 : (a.M <= 22 ? 22 : 33);
-  const size_t lds = sizeof(double) * ((size_t)a.nq * (MT + 2) + (size_t)kEstBlock * a.ms + 5 * kEstBlock);
-  hipError_t err;
-  if (MT == 12) err = launch_estimate<12>(a, g, rhs_mode, (unsigned)nb, lds, s);
-  else if (MT == 22) err = launch_estimate<22>(a, g, rhs_mode, (unsigned)nb, lds, s);
-  else err = launch_estimate<33>(a, g, rhs_mode, (unsigned)nb, lds, s);
+  const size_t lds =
+      sizeof(double) * ((size_t)a.nq * (tab_rows * MT + tab_extra) + (size_t)kEstBlock * a.ms + 5 * kEstBlock);
+  void (*kernel)(Args, GaussRuleN);
+  if (MT == 12) kernel = pick(std::integral_constant<int, 12>{});
+  else if (MT == 22) kernel = pick(std::integral_constant<int, 22>{});
+  else kernel = pick(std::integral_constant<int, 33>{});
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(kEstBlock), lds, s, a, g);
+  const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
   return hipGetLastError();
 }
 
-template <int MT>
-static hipError_t launch_estimate_vc(const EstimateVcArgs& a, const GaussRuleN& g, bool point_major, unsigned nb,
-                                     size_t lds, hipStream_t s) {
-  if (point_major)
-    hipLaunchKernelGGL((estimate_vc_kernel<MT, true>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
-  else
-    hipLaunchKernelGGL((estimate_vc_kernel<MT, false>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
-  return hipGetLastError();
+hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s) {
+  return launch_estimate_any(a, 1, 2, out3, s, [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    return rhs_mode == 1 ? estimate_kernel<MT, 1> : rhs_mode == 2 ? estimate_kernel<MT, 2> : estimate_kernel<MT, 0>;
+  });
 }
 
 hipError_t estimate_varcoef(EstimateVcArgs a, bool point_major, double* out3, hipStream_t s) {
-  GaussRuleN g{};
-  if (!gauss_rule(a.nq, g.xi, g.wt)) return hipErrorInvalidValue;
-  a.ms = a.M | 1;
-  const int64_t nb = est_blocks(a.ne);
-  const int MT = a.M <= 12 ? 12 : (a.M <= 22 ? 22 : 33);
-  const size_t lds = sizeof(double) * ((size_t)a.nq * (2 * MT + 1) + (size_t)kEstBlock * a.ms + 5 * kEstBlock);
-  hipError_t err;
-  if (MT == 12) err = launch_estimate_vc<12>(a, g, point_major, (unsigned)nb, lds, s);
-  else if (MT == 22) err = launch_estimate_vc<22>(a, g, point_major, (unsigned)nb, lds, s);
-  else err = launch_estimate_vc<33>(a, g, point_major, (unsigned)nb, lds, s);
-  if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
-  return hipGetLastError();
-}
-
-template <int MT>
-static hipError_t launch_estimate_react(const EstimateReactArgs& a, const GaussRuleN& g, bool point_major,
-                                        unsigned nb, size_t lds, hipStream_t s) {
-  if (point_major)
-    hipLaunchKernelGGL((estimate_react_kernel<MT, true>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
-  else
-    hipLaunchKernelGGL((estimate_react_kernel<MT, false>), dim3(nb), dim3(kEstBlock), lds, s, a, g);
-  return hipGetLastError();
+  return launch_estimate_any(a, 2, 1, out3, s, [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    return point_major ? estimate_vc_kernel<MT, true> : estimate_vc_kernel<MT, false>;
+  });
 }
 
 hipError_t estimate_react(EstimateReactArgs a, bool point_major, double* out3, hipStream_t s) {
-  GaussRuleN g{};
-  if (!gauss_rule(a.nq, g.xi, g.wt)) return hipErrorInvalidValue;
-  a.ms = a.M | 1;
-  const int64_t nb = est_blocks(a.ne);
-  const int MT = a.M <= 12 ? 12 : (a.M <= 22 ? 22 : 33);
-  const size_t lds = sizeof(double) * ((size_t)a.nq * (3 * MT + 1) + (size_t)kEstBlock * a.ms + 5 * kEstBlock);
-  hipError_t err;
-  if (MT == 12) err = launch_estimate_react<12>(a, g, point_major, (unsigned)nb, lds, s);
-  else if (MT == 22) err = launch_estimate_react<22>(a, g, point_major, (unsigned)nb, lds, s);
-  else err = launch_estimate_react<33>(a, g, point_major, (unsigned)nb, lds, s);
-  if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
-  return hipGetLastError();
+  return launch_estimate_any(a, 3, 1, out3, s, [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    return point_major ? estimate_react_kernel<MT, true> : estimate_react_kernel<MT, false>;
+  });
 }
 
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,

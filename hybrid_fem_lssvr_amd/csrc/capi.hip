@@ -135,6 +135,21 @@ int bind_p1(lssvr::P1Args& p, const double* x, int64_t ne, int nquad, double* di
   return LSSVR_OK;
 }
 
+// right-hand side of an assembly: named (in-kernel) or tabulated at the quadrature points
+int bind_p1_rhs(lssvr::P1Args& p, int rhs_id, const double* rhs_params_host, const double* rhs_quad) {
+  p.rhs_id = rhs_id;
+  if (rhs_id == LSSVR_RHS_SIN) {
+    if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
+    p.rhs_amp = rhs_params_host[0];
+    p.rhs_omega = rhs_params_host[1];
+    return LSSVR_OK;
+  }
+  if (rhs_id != LSSVR_RHS_ARRAY) return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
+  if (!rhs_quad) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_ARRAY needs rhs_quad[ne*nquad]");
+  p.rhs_quad = rhs_quad;
+  return LSSVR_OK;
+}
+
 // the arguments lssvr_estimate and lssvr_estimate_varcoef share, validated and bound
 int bind_estimate(lssvr::EstimateArgs& a, const double* x, const double* W, int64_t ne, int M, int nq, double* eta2,
                   double* jump, double* out3, void* work) {
@@ -152,6 +167,27 @@ int bind_estimate(lssvr::EstimateArgs& a, const double* x, const double* W, int6
   a.eta2 = eta2;
   a.jump = jump;
   a.work = static_cast<double*>(work);
+  return LSSVR_OK;
+}
+
+// bind_estimate plus the (a, a', f) tables of lssvr_estimate_varcoef and lssvr_estimate_react
+int bind_estimate_vc(lssvr::EstimateVcArgs& a, const double* x, const double* W, int64_t ne, int M, int nq,
+                     const double* a_values, const double* da_values, const double* rhs_values, int table_layout,
+                     double* eta2, double* jump, double* out3, void* work) {
+  int rc = bind_estimate(a, x, W, ne, M, nq, eta2, jump, out3, work);
+  if (rc == LSSVR_OK) rc = check_varcoef_tables(a_values, da_values, rhs_values, table_layout, true);
+  if (rc != LSSVR_OK) return rc;
+  a.rhs_values = rhs_values;
+  a.a_values = a_values;
+  a.da_values = da_values;
+  return LSSVR_OK;
+}
+
+// what the three lssvr_eval* entries check first
+int check_eval(int64_t ne, int64_t P, int M) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (P < 0) return fail(LSSVR_ERR_SIZE, "P < 0");
+  if (M < 1) return fail(LSSVR_ERR_DEGREE, "M = %d < 1", M);
   return LSSVR_OK;
 }
 
@@ -296,6 +332,15 @@ int react_dispatch(const lssvr::EnhanceReactArgs& a, hipStream_t s, const lssvr:
   return check_launch(lssvr::enhance_large_react(a, s, o), "enhance_large_react");
 }
 
+// the one body of lssvr_colloc_points and lssvr_colloc_points_pm
+int colloc_points_entry(const double* x, int64_t ne, int n_colloc, double* xc, void* stream, bool point_major) {
+  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne < 0");
+  if (n_colloc < 2) return fail(LSSVR_ERR_SIZE, "n_colloc < 2");
+  if (ne > 0 && (!x || !xc)) return fail(LSSVR_ERR_NULL, "x and xc must be non-NULL");
+  return check_launch(lssvr::colloc_points(x, ne, n_colloc, xc, reinterpret_cast<hipStream_t>(stream), point_major),
+                      point_major ? "colloc_points(point-major)" : "colloc_points");
+}
+
 }  // namespace
 
 extern "C" {
@@ -389,10 +434,7 @@ static int bind_step(lssvr_step_plan& b, const double* x, const double* u, int64
     return fail(LSSVR_ERR_SOLVER, "lssvr_step: n_colloc = %d < M-2 = %d: the primal normal equations are "
                                   "rank deficient; use lssvr_p1_assemble + lssvr_enhance (dual solver)",
                 n_colloc, M - 2);
-  b.p.rhs_id = LSSVR_RHS_SIN;
-  b.p.rhs_amp = a.rhs_amp;
-  b.p.rhs_omega = a.rhs_omega;
-  return LSSVR_OK;
+  return bind_p1_rhs(b.p, LSSVR_RHS_SIN, rhs_params_host, nullptr);
 }
 
 static int run_step(const lssvr_step_plan& b, hipStream_t s) {
@@ -633,19 +675,11 @@ int lssvr_enhance_shared(const double* x, const double* u, int64_t ne, int64_t e
 }
 
 int lssvr_colloc_points(const double* x, int64_t ne, int n_colloc, double* xc, void* stream) {
-  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne < 0");
-  if (n_colloc < 2) return fail(LSSVR_ERR_SIZE, "n_colloc < 2");
-  if (ne > 0 && (!x || !xc)) return fail(LSSVR_ERR_NULL, "x and xc must be non-NULL");
-  return check_launch(lssvr::colloc_points(x, ne, n_colloc, xc, reinterpret_cast<hipStream_t>(stream)),
-                      "colloc_points");
+  return colloc_points_entry(x, ne, n_colloc, xc, stream, false);
 }
 
 int lssvr_colloc_points_pm(const double* x, int64_t ne, int n_colloc, double* xc, void* stream) {
-  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne < 0");
-  if (n_colloc < 2) return fail(LSSVR_ERR_SIZE, "n_colloc < 2");
-  if (ne > 0 && (!x || !xc)) return fail(LSSVR_ERR_NULL, "x and xc must be non-NULL");
-  return check_launch(lssvr::colloc_points(x, ne, n_colloc, xc, reinterpret_cast<hipStream_t>(stream), true),
-                      "colloc_points(point-major)");
+  return colloc_points_entry(x, ne, n_colloc, xc, stream, true);
 }
 
 int lssvr_p1_assemble(const double* x, int64_t ne, int nquad, int rhs_id,
@@ -654,19 +688,9 @@ int lssvr_p1_assemble(const double* x, int64_t ne, int nquad, int rhs_id,
                       void* stream) {
   if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
   lssvr::P1Args a;
-  const int rc = bind_p1(a, x, ne, nquad, diag, off, load);
+  int rc = bind_p1(a, x, ne, nquad, diag, off, load);
+  if (rc == LSSVR_OK) rc = bind_p1_rhs(a, rhs_id, rhs_params_host, rhs_quad);
   if (rc != LSSVR_OK) return rc;
-  a.rhs_id = rhs_id;
-  if (rhs_id == LSSVR_RHS_SIN) {
-    if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
-    a.rhs_amp = rhs_params_host[0];
-    a.rhs_omega = rhs_params_host[1];
-  } else if (rhs_id == LSSVR_RHS_ARRAY) {
-    if (!rhs_quad) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_ARRAY needs rhs_quad[ne*nquad]");
-    a.rhs_quad = rhs_quad;
-  } else {
-    return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
-  }
   a.a_quad = a_quad;
   a.kloc = kloc;
   a.floc = floc;
@@ -683,19 +707,9 @@ int lssvr_p1_assemble_react(const double* x, int64_t ne, int nquad, int rhs_id,
                              stream);
   if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
   lssvr::P1ReactArgs a{};
-  const int rc = bind_p1(a, x, ne, nquad, diag, off, load);
+  int rc = bind_p1(a, x, ne, nquad, diag, off, load);
+  if (rc == LSSVR_OK) rc = bind_p1_rhs(a, rhs_id, rhs_params_host, rhs_quad);
   if (rc != LSSVR_OK) return rc;
-  a.rhs_id = rhs_id;
-  if (rhs_id == LSSVR_RHS_SIN) {
-    if (!rhs_params_host) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_SIN needs rhs_params = {amp, omega}");
-    a.rhs_amp = rhs_params_host[0];
-    a.rhs_omega = rhs_params_host[1];
-  } else if (rhs_id == LSSVR_RHS_ARRAY) {
-    if (!rhs_quad) return fail(LSSVR_ERR_RHS, "LSSVR_RHS_ARRAY needs rhs_quad[ne*nquad]");
-    a.rhs_quad = rhs_quad;
-  } else {
-    return fail(LSSVR_ERR_RHS, "unknown rhs_id %d", rhs_id);
-  }
   a.a_quad = a_quad;
   a.c_quad = c_quad;
   a.kloc = kloc;
@@ -757,9 +771,8 @@ int lssvr_p1_flux_finish(const double* kloc, const double* load, int64_t ne, int
 
 int lssvr_eval(const double* x, const double* W, int64_t ne, int M, const double* xq, int64_t P,
                double* uq, int64_t* elem, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (P < 0) return fail(LSSVR_ERR_SIZE, "P < 0");
-  if (M < 1) return fail(LSSVR_ERR_DEGREE, "M = %d < 1", M);
+  const int rc = check_eval(ne, P, M);
+  if (rc != LSSVR_OK) return rc;
   if (!x || !W || (P > 0 && (!xq || !uq))) return fail(LSSVR_ERR_NULL, "x, W, xq, uq must be non-NULL");
   return check_launch(lssvr::eval_points(x, W, ne, M, xq, P, uq, elem,
                                          reinterpret_cast<hipStream_t>(stream)),
@@ -768,9 +781,8 @@ int lssvr_eval(const double* x, const double* W, int64_t ne, int M, const double
 
 int lssvr_eval_error(const double* x, const double* W, int64_t ne, int M, const double* xq,
                      int64_t P, const double* exact_params_host, double* out3, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (P < 0) return fail(LSSVR_ERR_SIZE, "P < 0");
-  if (M < 1) return fail(LSSVR_ERR_DEGREE, "M = %d < 1", M);
+  const int rc = check_eval(ne, P, M);
+  if (rc != LSSVR_OK) return rc;
   if (!x || !W || !out3 || !exact_params_host || (P > 0 && !xq))
     return fail(LSSVR_ERR_NULL, "x, W, xq, exact_params, out3 must be non-NULL");
   return check_launch(lssvr::eval_error(x, W, ne, M, xq, P, exact_params_host[0],
@@ -781,9 +793,8 @@ int lssvr_eval_error(const double* x, const double* W, int64_t ne, int M, const 
 
 int lssvr_eval_deriv(const double* x, const double* W, int64_t ne, int M, int order, const double* xq,
                      int64_t P, double* out, int64_t* elem, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (P < 0) return fail(LSSVR_ERR_SIZE, "P < 0");
-  if (M < 1) return fail(LSSVR_ERR_DEGREE, "M = %d < 1", M);
+  const int rc = check_eval(ne, P, M);
+  if (rc != LSSVR_OK) return rc;
   if (order < 0 || order > 2) return fail(LSSVR_ERR_DEGREE, "order = %d outside {0, 1, 2}", order);
   if (!x || !W || (P > 0 && (!xq || !out))) return fail(LSSVR_ERR_NULL, "x, W, xq, out must be non-NULL");
   return check_launch(lssvr::eval_deriv(x, W, ne, M, order, xq, P, out, elem,
@@ -836,13 +847,10 @@ int lssvr_estimate_varcoef(const double* x, const double* W, int64_t ne, int M, 
                            const double* da_values, const double* rhs_values, int table_layout, const double* a_ends,
                            double* eta2, double* jump, double* out3, void* work, void* stream) {
   lssvr::EstimateVcArgs a{};
-  int rc = bind_estimate(a, x, W, ne, M, nq, eta2, jump, out3, work);
-  if (rc == LSSVR_OK) rc = check_varcoef_tables(a_values, da_values, rhs_values, table_layout, true);
+  const int rc = bind_estimate_vc(a, x, W, ne, M, nq, a_values, da_values, rhs_values, table_layout, eta2, jump, out3,
+                                  work);
   if (rc != LSSVR_OK) return rc;
   if (!a_ends) return fail(LSSVR_ERR_NULL, "a_ends must be non-NULL");
-  a.rhs_values = rhs_values;
-  a.a_values = a_values;
-  a.da_values = da_values;
   a.a_ends = a_ends;
   return check_launch(lssvr::estimate_varcoef(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,
                                               reinterpret_cast<hipStream_t>(stream)),
@@ -853,14 +861,11 @@ int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, in
                          const double* da_values, const double* c_values, const double* rhs_values, int table_layout,
                          const double* a_ends, double* eta2, double* jump, double* out3, void* work, void* stream) {
   lssvr::EstimateReactArgs a{};
-  int rc = bind_estimate(a, x, W, ne, M, nq, eta2, jump, out3, work);
-  if (rc == LSSVR_OK) rc = check_varcoef_tables(a_values, da_values, rhs_values, table_layout, true);
+  const int rc = bind_estimate_vc(a, x, W, ne, M, nq, a_values, da_values, rhs_values, table_layout, eta2, jump, out3,
+                                  work);
   if (rc != LSSVR_OK) return rc;
-  if (!c_values) return fail(LSSVR_ERR_NULL, "c_values must be non-NULL");
+  if (!c_values) return fail(LSSVR_ERR_NULL, "c_values must be non-NULL");     // (checked before a_ends, as ever)
   if (!a_ends) return fail(LSSVR_ERR_NULL, "a_ends must be non-NULL");
-  a.rhs_values = rhs_values;
-  a.a_values = a_values;
-  a.da_values = da_values;
   a.c_values = c_values;
   a.a_ends = a_ends;
   return check_launch(lssvr::estimate_react(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,

@@ -53,6 +53,52 @@ def _shard(x, u, elem_offset, ne_global):
     return ne, (elem_offset + ne if ne_global is None else ne_global)
 
 
+def _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma):
+    """The twelve arguments every shard entry starts with (x, u, ne, elem_offset, ne_global, gxmin, gxmax, bc_left,
+    bc_right, M, n_colloc, gamma); ``global_domain=None`` reads the shard's own ends back from the device."""
+    ne = x.numel() - 1
+    if global_domain is None:
+        if ne == 0:
+            global_domain = (0.0, 0.0)
+        else:
+            ends = torch.stack([x[0], x[-1]]).cpu()
+            global_domain = (float(ends[0]), float(ends[1]))
+    return (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]), float(global_domain[1]),
+            float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma))
+
+
+def _layout(point_major):
+    return TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR
+
+
+def _tables(ne, k, point_major=False, *, shape=False, **named):
+    """Caller tables of ``k`` values per element become raw device pointers: each is a float64 device tensor of
+    ne*k doubles or, with ``shape`` (the estimators), exactly [ne, k] / ``point_major`` [k, ne]."""
+    want = (k, ne) if point_major else (ne, k)
+    for nm, t in named.items():
+        _dev(t, nm)
+        if shape and tuple(t.shape) != want:
+            raise ValueError(f"{nm} must be {'[nq, ne]' if point_major else '[ne, nq]'} = {list(want)}, "
+                             f"got {list(t.shape)}")
+        if t.numel() != ne * k:
+            raise ValueError(f"{nm} must hold {ne * k} doubles, got {t.numel()}")
+
+
+def _variant(a_values, da_values, rhs_values, c_values):
+    """("varcoef" | "react", the table pointers in that entry's order): the optional c table is all that
+    separates ``lssvr_*_varcoef*`` from ``lssvr_*_react*``."""
+    if c_values is None:
+        return "varcoef", (_ptr(a_values), _ptr(da_values), _ptr(rhs_values))
+    return "react", (_ptr(a_values), _ptr(da_values), _ptr(c_values), _ptr(rhs_values))
+
+
+def _scratch(work, nbytes, device):
+    """``work`` when it holds ``nbytes``, else a fresh buffer that does."""
+    if work is None or work.numel() * work.element_size() < nbytes:
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return work
+
+
 def _rhs(rhs, values, count, what, point_major=False, name="rhs_values"):
     """(rhs_id, params) of a right-hand side: ``rhs`` = (amp, omega) evaluated in-kernel, or the table
     ``values`` of ``count`` (= ``what``) doubles, element-major or ``point_major``."""
@@ -227,19 +273,11 @@ def enhance(x, u, M, gamma, n_colloc=12, *, rhs=(POISSON_AMP, POISSON_OMEGA), rh
     ne, ne_global = _shard(x, u, elem_offset, ne_global)
     if ne < 0:
         raise ValueError("need at least one node")
-    if global_domain is None:
-        if ne == 0:
-            global_domain = (0.0, 0.0)
-        else:
-            ends = torch.stack([x[0], x[-1]]).cpu()
-            global_domain = (float(ends[0]), float(ends[1]))
+    pre = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma)
     out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
     rhs_id, params = _rhs(rhs, rhs_values, ne * n_colloc, "ne*n_colloc", point_major)
     with _work_arg(work, lib, x, ne, M, n_colloc, solver, stream) as wk:
-        rc = lib.lssvr_enhance_ws(_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                                  float(global_domain[0]), float(global_domain[1]),
-                                  float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
-                                  rhs_id, params, _ptr(rhs_values), int(solver),
+        rc = lib.lssvr_enhance_ws(*pre, rhs_id, params, _ptr(rhs_values), int(solver),
                                   _ptr(out), _ptr(status), _ptr(fail_count),
                                   _ptr(wk), 0 if wk is None else wk.numel() * 8, _stream(stream), None)
     _capi.check(rc, "lssvr_enhance_ws")
@@ -277,10 +315,10 @@ def enhance_subset(x, u, M, gamma, n_colloc, W, *, elem_ids=None, gamma_values=N
     _check_fail_count(fail_count)
     # (rows indexed by position in elem_ids)
     rhs_id, params = _rhs(rhs, rhs_values, nsub * n_colloc, "nsub*n_colloc", point_major)
+    pre = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma)
     with _work_arg(work, lib, x, nsub, M, n_colloc, SOLVER_PRIMAL, stream) as wk:
-        rc = lib.lssvr_enhance_subset_ws(_ptr(x), _ptr(u), ne, _ptr(elem_ids), int(nsub), int(elem_offset),
-                                         int(ne_global), float(global_domain[0]), float(global_domain[1]),
-                                         float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
+        # (the subset entry takes elem_ids and nsub after ne, gamma_values after gamma)
+        rc = lib.lssvr_enhance_subset_ws(*pre[:3], _ptr(elem_ids), int(nsub), *pre[3:],
                                          _ptr(gamma_values), rhs_id, params, _ptr(rhs_values),
                                          _ptr(W), int(W.shape[1]), _ptr(status), _ptr(fail_count),
                                          _ptr(wk), 0 if wk is None else wk.numel() * 8, _stream(stream))
@@ -327,9 +365,9 @@ def enhance_shared(x, u, op, M, n_colloc, *, rhs=(POISSON_AMP, POISSON_OMEGA), r
         raise ValueError("op must be a contiguous float64[(n_colloc+2), M] tensor")
     out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
     rhs_id, params = _rhs(rhs, rhs_values, ne * n_colloc, "ne*n_colloc", point_major)
-    args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]), float(global_domain[1]),
-            float(bc[0]), float(bc[1]), int(M), int(n_colloc), rhs_id, params, _ptr(rhs_values), _ptr(op),
-            _ptr(out), _ptr(status), _ptr(fail_count), _stream(stream))
+    # (no gamma: it is part of the operator)
+    args = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, 1.0)[:-1] + (
+        rhs_id, params, _ptr(rhs_values), _ptr(op), _ptr(out), _ptr(status), _ptr(fail_count), _stream(stream))
     if profiled:
         return _timed(lib, "lssvr_enhance_shared", args)
     _capi.check(lib.lssvr_enhance_shared(*args, None), "lssvr_enhance_shared")
@@ -348,10 +386,9 @@ def enhance_profiled(x, u, M, gamma, n_colloc=12, *, rhs=(POISSON_AMP, POISSON_O
     ne, ne_global = _shard(x, u, elem_offset, ne_global)
     out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status)
     with _work_arg(work, lib, x, ne, M, n_colloc, solver, stream) as wk:
-        args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]),
-                float(global_domain[1]), float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
-                RHS_SIN, _capi.rhs_params(*rhs), None, int(solver), _ptr(out), _ptr(status), None,
-                _ptr(wk), 0 if wk is None else wk.numel() * 8, _stream(stream))
+        args = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma) + (
+            RHS_SIN, _capi.rhs_params(*rhs), None, int(solver), _ptr(out), _ptr(status), None,
+            _ptr(wk), 0 if wk is None else wk.numel() * 8, _stream(stream))
         return _timed(lib, "lssvr_enhance_ws", args, repeats)
 
 
@@ -384,11 +421,10 @@ class StepPlan:
         nb = int(self.lib.lssvr_enhance_work_bytes(ne, int(M), int(n_colloc), SOLVER_PRIMAL))
         self._work = torch.empty((nb + 7) // 8, dtype=torch.float64, device=x.device) if nb > 0 else None
         self._keep = (x, u, _capi.rhs_params(*rhs))
-        self._args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                      float(global_domain[0]), float(global_domain[1]), float(bc[0]), float(bc[1]),
-                      int(M), int(n_colloc), float(gamma), self._keep[2], int(nquad),
-                      _ptr(self.bands["diag"]), _ptr(self.bands["off"]), _ptr(self.bands["load"]),
-                      _ptr(self.W), _ptr(self.status), _ptr(fail_count))
+        pre = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma)
+        bands = (_ptr(self.bands["diag"]), _ptr(self.bands["off"]), _ptr(self.bands["load"]))
+        outs = (_ptr(self.W), _ptr(self.status), _ptr(fail_count))
+        self._args = pre + (self._keep[2], int(nquad)) + bands + outs
         self._step, self._cargs = _bind(self.lib, "lssvr_step", self._args)
         # the library's own plan (lssvr_step_plan_*): the 20 arguments validated and bound once on the C side, a
         # launch is a two-argument call (host cost 4.4 -> ~2 us per launch; with the stream handle passed in, since
@@ -402,14 +438,9 @@ class StepPlan:
         self._launch = self.lib.lssvr_step_plan_launch
 
         if self._work is not None:
-            self._asm_args = (_ptr(x), ne, int(nquad), RHS_SIN, self._keep[2], None, None,
-                              _ptr(self.bands["diag"]), _ptr(self.bands["off"]), _ptr(self.bands["load"]),
-                              None, None)
-            self._enh_args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                              float(global_domain[0]), float(global_domain[1]), float(bc[0]), float(bc[1]),
-                              int(M), int(n_colloc), float(gamma), RHS_SIN, self._keep[2], None,
-                              SOLVER_PRIMAL, _ptr(self.W), _ptr(self.status), _ptr(fail_count),
-                              _ptr(self._work), self._work.numel() * 8)
+            self._asm_args = (_ptr(x), ne, int(nquad), RHS_SIN, self._keep[2], None, None) + bands + (None, None)
+            self._enh_args = pre + (RHS_SIN, self._keep[2], None, SOLVER_PRIMAL) + outs + (
+                _ptr(self._work), self._work.numel() * 8)
 
     def launch(self, stream=None):
         st = _stream(stream)
@@ -448,35 +479,18 @@ def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *
     call without it."""
     lib = _capi.load()
     ne, ne_global = _shard(x, u, elem_offset, ne_global)
-    for t, nm in ((a_values, "a_values"), (da_values, "da_values"), (rhs_values, "rhs_values")):
-        _dev(t, nm)
-        if t.numel() != ne * n_colloc:
-            raise ValueError(f"{nm} must hold ne*n_colloc doubles")
-    if c_values is not None:
-        _rhs(None, c_values, ne * n_colloc, "ne*n_colloc", name="c_values")
-        if repeats is not None:
-            raise ValueError("repeats is not available with c_values (lssvr_enhance_react_ws has no sequence form)")
-    if global_domain is None:
-        ends = torch.stack([x[0], x[-1]]).cpu()
-        global_domain = (float(ends[0]), float(ends[1]))
+    _tables(ne, n_colloc, a_values=a_values, da_values=da_values, rhs_values=rhs_values,
+            **({} if c_values is None else {"c_values": c_values}))
+    if c_values is not None and repeats is not None:
+        raise ValueError("repeats is not available with c_values (lssvr_enhance_react_ws has no sequence form)")
+    pre = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma)
     out, status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
-    if c_values is not None:
-        args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]),
-                float(global_domain[1]), float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma),
-                _ptr(a_values), _ptr(da_values), _ptr(c_values), _ptr(rhs_values),
-                TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, _ptr(out), _ptr(status),
-                _ptr(fail_count), None, 0, _stream(stream))
-        if profiled:
-            return _timed(lib, "lssvr_enhance_react_ws", args)
-        _capi.check(lib.lssvr_enhance_react_ws(*args, None), "lssvr_enhance_react_ws")
-        return out, status
-    args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global), float(global_domain[0]), float(global_domain[1]),
-            float(bc[0]), float(bc[1]), int(M), int(n_colloc), float(gamma), _ptr(a_values), _ptr(da_values),
-            _ptr(rhs_values), TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, _ptr(out), _ptr(status),
-            _ptr(fail_count), None, 0, _stream(stream))
+    kind, tabs = _variant(a_values, da_values, rhs_values, c_values)
+    name = f"lssvr_enhance_{kind}_ws"
+    args = pre + tabs + (_layout(point_major), _ptr(out), _ptr(status), _ptr(fail_count), None, 0, _stream(stream))
     if profiled:
-        return _timed(lib, "lssvr_enhance_varcoef_ws", args, repeats)
-    _capi.check(lib.lssvr_enhance_varcoef_ws(*args, None), "lssvr_enhance_varcoef_ws")
+        return _timed(lib, name, args, repeats)
+    _capi.check(getattr(lib, name)(*args, None), name)
     return out, status
 
 
@@ -518,22 +532,16 @@ class StepPlanVarcoef:
                  bands=None, out=None, status=None, fail_count=None):
         self.lib = _capi.load()
         ne, ne_global = _shard(x, u, elem_offset, ne_global)
-        for t, nm, cnt in ((a_values, "a_values", ne * n_colloc), (da_values, "da_values", ne * n_colloc),
-                           (rhs_values, "rhs_values", ne * n_colloc), (rhs_quad, "rhs_quad", ne * nquad),
-                           (a_quad, "a_quad", ne * nquad)):
-            _dev(t, nm)
-            if t.numel() != cnt:
-                raise ValueError(f"{nm} must hold {cnt} doubles")
+        _tables(ne, n_colloc, a_values=a_values, da_values=da_values, rhs_values=rhs_values)
+        _tables(ne, nquad, rhs_quad=rhs_quad, a_quad=a_quad)
         self.bands = _bands(x, ne, bands)
         self.W, self.status = _check_buffers(ne, M, n_colloc, x, out=out, status=status, fail_count=fail_count)
         self._keep = (x, u, a_values, da_values, rhs_values, rhs_quad, a_quad, fail_count)
-        self._args = (_ptr(x), _ptr(u), ne, int(elem_offset), int(ne_global),
-                      float(global_domain[0]), float(global_domain[1]), float(bc[0]), float(bc[1]),
-                      int(M), int(n_colloc), float(gamma), _ptr(a_values), _ptr(da_values), _ptr(rhs_values),
-                      TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, int(nquad),
-                      _ptr(rhs_quad), _ptr(a_quad),
-                      _ptr(self.bands["diag"]), _ptr(self.bands["off"]), _ptr(self.bands["load"]),
-                      _ptr(self.W), _ptr(self.status), _ptr(fail_count))
+        self._args = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma) + (
+            _ptr(a_values), _ptr(da_values), _ptr(rhs_values), _layout(point_major), int(nquad),
+            _ptr(rhs_quad), _ptr(a_quad),
+            _ptr(self.bands["diag"]), _ptr(self.bands["off"]), _ptr(self.bands["load"]),
+            _ptr(self.W), _ptr(self.status), _ptr(fail_count))
         self._step, self._cargs = _bind(self.lib, "lssvr_step_varcoef", self._args)
 
     def launch(self, stream=None):
@@ -550,14 +558,9 @@ def colloc_points(x, n_colloc, *, stream=None, point_major=False):
     lib = _capi.load()
     _dev(x, "x")
     ne = x.numel() - 1
-    if point_major:
-        xc = torch.empty((n_colloc, ne), dtype=torch.float64, device=x.device)
-        _capi.check(lib.lssvr_colloc_points_pm(_ptr(x), ne, int(n_colloc), _ptr(xc), _stream(stream)),
-                    "lssvr_colloc_points_pm")
-        return xc
-    xc = torch.empty((ne, n_colloc), dtype=torch.float64, device=x.device)
-    _capi.check(lib.lssvr_colloc_points(_ptr(x), ne, int(n_colloc), _ptr(xc), _stream(stream)),
-                "lssvr_colloc_points")
+    name = "lssvr_colloc_points_pm" if point_major else "lssvr_colloc_points"
+    xc = torch.empty((n_colloc, ne) if point_major else (ne, n_colloc), dtype=torch.float64, device=x.device)
+    _capi.check(getattr(lib, name)(_ptr(x), ne, int(n_colloc), _ptr(xc), _stream(stream)), name)
     return xc
 
 
@@ -584,18 +587,14 @@ def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, 
     rhs_id, params = _rhs(rhs, rhs_quad, ne * nquad, "ne*nquad", name="rhs_quad")
     if a_quad is not None:
         _dev(a_quad, "a_quad")
+    name, coefs = "lssvr_p1_assemble", (_ptr(a_quad),)
     if c_quad is not None:
-        _rhs(None, c_quad, ne * nquad, "ne*nquad", name="c_quad")
-        rc = lib.lssvr_p1_assemble_react(_ptr(x), ne, int(nquad), rhs_id, params, _ptr(rhs_quad), _ptr(a_quad),
-                                         _ptr(c_quad), _ptr(out["diag"]), _ptr(out["off"]), _ptr(out["load"]),
-                                         _ptr(out.get("kloc")), _ptr(out.get("floc")), _stream(stream))
-        _capi.check(rc, "lssvr_p1_assemble_react")
-        return out
-    rc = lib.lssvr_p1_assemble(_ptr(x), ne, int(nquad), rhs_id, params, _ptr(rhs_quad),
-                               _ptr(a_quad), _ptr(out["diag"]), _ptr(out["off"]),
-                               _ptr(out["load"]), _ptr(out.get("kloc")), _ptr(out.get("floc")),
-                               _stream(stream))
-    _capi.check(rc, "lssvr_p1_assemble")
+        _tables(ne, nquad, c_quad=c_quad)
+        name, coefs = "lssvr_p1_assemble_react", (_ptr(a_quad), _ptr(c_quad))
+    rc = getattr(lib, name)(_ptr(x), ne, int(nquad), rhs_id, params, _ptr(rhs_quad), *coefs,
+                            _ptr(out["diag"]), _ptr(out["off"]), _ptr(out["load"]),
+                            _ptr(out.get("kloc")), _ptr(out.get("floc")), _stream(stream))
+    _capi.check(rc, name)
     return out
 
 
@@ -610,9 +609,7 @@ def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=N
         raise ValueError("band lengths must be ne+1, ne, ne+1")
     if out is None:
         out = torch.empty(ne + 1, dtype=torch.float64, device=diag.device)
-    nbytes = lib.lssvr_tridiag_work_bytes(ne)
-    if work is None or work.numel() * work.element_size() < nbytes:
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=diag.device)
+    work = _scratch(work, lib.lssvr_tridiag_work_bytes(ne), diag.device)
     rc = lib.lssvr_tridiag_dirichlet_solve(_ptr(diag), _ptr(off), _ptr(load), ne, float(u0),
                                            float(u1), _ptr(out), _ptr(work), _stream(stream))
     _capi.check(rc, "lssvr_tridiag_dirichlet_solve")
@@ -630,9 +627,7 @@ def p1_flux_solve(kloc, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=Non
         raise ValueError("load must have ne+1 entries")
     if out is None:
         out = torch.empty(ne + 1, dtype=torch.float64, device=kloc.device)
-    nbytes = lib.lssvr_p1_flux_work_bytes(ne)
-    if work is None or work.numel() * work.element_size() < nbytes:
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=kloc.device)
+    work = _scratch(work, lib.lssvr_p1_flux_work_bytes(ne), kloc.device)
     rc = lib.lssvr_p1_flux_solve(_ptr(kloc), _ptr(load), ne, float(u0), float(u1), _ptr(out),
                                  _ptr(work), _stream(stream))
     _capi.check(rc, "lssvr_p1_flux_solve")
@@ -648,9 +643,7 @@ def p1_flux_aggregate(kloc, load, *, first_global, work=None, stream=None):
     ne = kloc.numel()
     if load.numel() < ne + 1:
         raise ValueError("load must have at least ne+1 entries")
-    nbytes = lib.lssvr_p1_flux_work_bytes(ne)
-    if work is None or work.numel() * work.element_size() < nbytes:
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=kloc.device)
+    work = _scratch(work, lib.lssvr_p1_flux_work_bytes(ne), kloc.device)
     agg = torch.empty(3, dtype=torch.float64, device=kloc.device)
     rc = lib.lssvr_p1_flux_aggregate(_ptr(kloc), _ptr(load), ne, int(bool(first_global)), _ptr(work),
                                      _ptr(agg), _stream(stream))
@@ -753,6 +746,13 @@ def _check_work(work, x, ne):
     return work
 
 
+def _estimate_out(x, ne, want_jump):
+    """(eta2[ne], jump[ne+1] | None, out3[3]) of the estimators, uninitialised."""
+    eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
+    jump = torch.empty(ne + 1, dtype=torch.float64, device=x.device) if want_jump else None
+    return eta2, jump, torch.empty(3, dtype=torch.float64, device=x.device)
+
+
 def estimate_points(x, nq, *, stream=None):
     """The estimator's abscissae float64[ne, nq] (tabulate a callable f on it for :func:`estimate`)."""
     lib = _capi.load()
@@ -778,9 +778,7 @@ def estimate(x, W, nq, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_values=None, poi
     if W.dim() != 2 or W.shape[0] != ne:
         raise ValueError("W must be [ne, M]")
     rhs_id, params = _rhs(rhs, rhs_values, ne * int(nq), "ne*nq", point_major)
-    eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
-    jump = torch.empty(ne + 1, dtype=torch.float64, device=x.device) if want_jump else None
-    out3 = torch.empty(3, dtype=torch.float64, device=x.device)
+    eta2, jump, out3 = _estimate_out(x, ne, want_jump)
     work = _check_work(work, x, ne)
     rc = lib.lssvr_estimate(_ptr(x), _ptr(W), ne, int(W.shape[1]), int(nq), rhs_id, params,
                             _ptr(rhs_values), _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work),
@@ -806,33 +804,18 @@ def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point
     nq = int(nq)
     if W.dim() != 2 or W.shape[0] != ne:
         raise ValueError("W must be [ne, M]")
-    shape = (nq, ne) if point_major else (ne, nq)
-    tables = ((a_values, "a_values"), (da_values, "da_values"), (rhs_values, "rhs_values"))
-    if c_values is not None:
-        tables += ((c_values, "c_values"),)
-    for t, nm in tables:
-        _dev(t, nm)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{nm} must be {'[nq, ne]' if point_major else '[ne, nq]'} = {list(shape)}, "
-                             f"got {list(t.shape)}")
+    _tables(ne, nq, point_major, shape=True, a_values=a_values, da_values=da_values, rhs_values=rhs_values,
+            **({} if c_values is None else {"c_values": c_values}))
     _dev(a_ends, "a_ends")
     if tuple(a_ends.shape) != (ne, 2):
         raise ValueError(f"a_ends must be [ne, 2] = [{ne}, 2], got {list(a_ends.shape)}")
-    eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
-    jump = torch.empty(ne + 1, dtype=torch.float64, device=x.device) if want_jump else None
-    out3 = torch.empty(3, dtype=torch.float64, device=x.device)
+    eta2, jump, out3 = _estimate_out(x, ne, want_jump)
     work = _check_work(work, x, ne)
-    if c_values is not None:
-        rc = lib.lssvr_estimate_react(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, _ptr(a_values), _ptr(da_values),
-                                      _ptr(c_values), _ptr(rhs_values),
-                                      TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR, _ptr(a_ends),
-                                      _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work), _stream(stream))
-        _capi.check(rc, "lssvr_estimate_react")
-        return eta2, jump, out3
-    rc = lib.lssvr_estimate_varcoef(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, _ptr(a_values), _ptr(da_values),
-                                    _ptr(rhs_values), TABLE_POINT_MAJOR if point_major else TABLE_ELEMENT_MAJOR,
-                                    _ptr(a_ends), _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work), _stream(stream))
-    _capi.check(rc, "lssvr_estimate_varcoef")
+    kind, tabs = _variant(a_values, da_values, rhs_values, c_values)
+    name = f"lssvr_estimate_{kind}"
+    rc = getattr(lib, name)(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, *tabs, _layout(point_major), _ptr(a_ends),
+                            _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work), _stream(stream))
+    _capi.check(rc, name)
     return eta2, jump, out3
 
 

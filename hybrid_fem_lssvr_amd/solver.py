@@ -93,39 +93,32 @@ def _to_dev(a, device):
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64)), device=device)
 
 
-def _rhs_mode(rhs, x_dev, n_colloc, M=None):
-    """Keyword arguments of ops.enhance for the right-hand side: ``rhs=(amp, omega)`` for the named
-    f, else the callable (Dual.py:20 ``rhs_func``) tabulated on the host at np.linspace's points
-    (Dual.py:40).  The callable ALWAYS sees the element-major array ``x[e, k]`` -- points along the last
-    axis, as in the reference, where it receives the 1-D array of one element's n points (Dual.py:40-44): a
-    callable that returns a per-point vector of shape (n,), or otherwise relies on the last axis being the
-    points, broadcasts the same at every degree (up to M = 22 it used to see the transposed
-    array).  The TABLE is then handed over point-major (``t[k, e]``) for the lane-per-element kernels
-    (M <= 22), which read that layout at full HBM rate, element-major otherwise; same values either way."""
+def _tabulate(fn, pts, point_major=False):
+    """Device table of the callable ``fn`` at the device points ``pts`` [ne, k].  The callable ALWAYS sees the
+    element-major host array ``x[e, k]`` -- points along the last axis, as in the reference, where it receives the
+    1-D array of one element's n points (Dual.py:40-44): a callable that returns a per-point vector of shape (k,),
+    or otherwise relies on the last axis being the points, broadcasts the same at every degree (up to
+    M = 22 it used to see the transposed array).  The table is handed over as [ne, k], or transposed to [k, ne]
+    with ``point_major``; same values either way."""
+    xh = pts.cpu().numpy()
+    t = np.asarray(fn(xh), dtype=np.float64)
+    if t.shape != xh.shape:
+        t = np.broadcast_to(t, xh.shape)
+    return _to_dev(t.T if point_major else t, pts.device)
+
+
+def _point_major(M):
+    """The lane-per-element kernels (M <= 22) read point-major tables (``t[k, e]``) at full HBM rate; above, the
+    tables stay element-major."""
+    return int(M) <= 22
+
+
+def _rhs_mode(rhs, points, point_major=False):
+    """Keyword arguments of the Poisson-row operators for the right-hand side: ``rhs=(amp, omega)`` for the named
+    f, evaluated in-kernel, else the callable (Dual.py:20 ``rhs_func``) tabulated at ``points()``."""
     if isinstance(rhs, SinRHS):
         return dict(rhs=(rhs.amp, rhs.omega))
-    pm = M is not None and int(M) <= 22
-    xc = ops.colloc_points(x_dev, n_colloc)                    # np.linspace per element: [ne, n]
-    f = np.asarray(rhs(xc.cpu().numpy()), dtype=np.float64)
-    if f.shape != tuple(xc.shape):
-        f = np.broadcast_to(f, tuple(xc.shape))
-    if pm:
-        f = np.ascontiguousarray(f.T)
-    return dict(rhs_values=_to_dev(f, x_dev.device), point_major=pm)
-
-
-def _tabulate(funcs, pts, point_major=False):
-    """Device tables of the callables ``funcs`` at the device points ``pts`` [ne, k]: every callable sees the
-    element-major host array (as :func:`_rhs_mode`'s does); each table is handed over as [ne, k], or
-    transposed to [k, ne] with ``point_major``."""
-    xh = pts.cpu().numpy()
-    out = []
-    for fn in funcs:
-        t = np.asarray(fn(xh), dtype=np.float64)
-        if t.shape != xh.shape:
-            t = np.broadcast_to(t, xh.shape)
-        out.append(_to_dev(t.T if point_major else t, pts.device))
-    return out
+    return dict(rhs_values=_tabulate(rhs, points(), point_major), point_major=point_major)
 
 
 def _one(x):
@@ -134,6 +127,28 @@ def _one(x):
 
 def _zero(x):
     return np.zeros_like(np.asarray(x, dtype=np.float64))
+
+
+class _Equation:
+    """-(a u')' + c u = f as the facade holds it: the callables ``a``, ``da``, ``c``, ``f``; ``a`` / ``da`` and
+    ``c`` are None where the term is absent (a = 1, c = 0)."""
+
+    def __init__(self, rhs, coef, reaction):
+        self.a, self.da = coef if coef is not None else (None, None)
+        self.c, self.f = reaction, rhs
+        self.poisson = coef is None and reaction is None       # the Poisson rows: no table but f's
+
+    def tables(self, points, point_major=False):
+        """(a, a', f, c | None) tabulated at ``points``; without ``coef``, a = 1 and a' = 0."""
+        a, da = (_one, _zero) if self.a is None else (self.a, self.da)
+        ta, tda, tf = (_tabulate(fn, points, point_major) for fn in (a, da, self.f))
+        return ta, tda, tf, None if self.c is None else _tabulate(self.c, points, point_major)
+
+    def a_ends(self, x):
+        """a at the left and right end of every element [ne, 2]: a callable a is continuous at the nodes."""
+        an = np.asarray((_one if self.a is None else self.a)(x.cpu().numpy()), dtype=np.float64)
+        an = np.broadcast_to(an, (x.numel(),))
+        return _to_dev(np.stack([an[:-1], an[1:]], axis=1), x.device)
 
 
 def _enhance(x, u, M, gamma, n_colloc, *, global_domain, bc, solver, uniform_rtol=1e-9, **kw):
@@ -225,7 +240,7 @@ def enhance_elements(mesh, nodal_values, M, gamma, *, n_colloc=12, rhs=poisson_r
         raise ValueError("nodal_values must have one value per mesh node")
     if global_domain is None:
         global_domain = (float(m.nodes[0]), float(m.nodes[-1]))
-    kw = _rhs_mode(rhs, x, n_colloc, M)
+    kw = _rhs_mode(rhs, lambda: ops.colloc_points(x, n_colloc), _point_major(M))
     W, st = _enhance(x, u, int(M), float(gamma), int(n_colloc), global_domain=global_domain,
                      bc=bc, solver=solver, **kw)
     return EnhancedSolution(x, W, st)
@@ -261,13 +276,8 @@ def enhance_elements_hetero(mesh, nodal_values, M, gamma, *, n_colloc=12, rhs=po
     for Mg, ng in sorted({(int(a), int(b)) for a, b in zip(Ms, ns)}):
         ids_h = np.nonzero((Ms == Mg) & (ns == ng))[0].astype(np.int64)
         ids = torch.as_tensor(ids_h, device=dev)
-        if isinstance(rhs, SinRHS):
-            kw = dict(rhs=(rhs.amp, rhs.omega))
-        else:
-            # tabulate f at this group's collocation points (np.linspace per element)
-            xc = ops.colloc_points(x, ng)[ids]
-            f = np.asarray(rhs(xc.cpu().numpy()), dtype=np.float64)
-            kw = dict(rhs_values=_to_dev(np.broadcast_to(f, tuple(xc.shape)), dev))
+        # (a callable f is tabulated at this group's collocation points, np.linspace per element)
+        kw = _rhs_mode(rhs, lambda: ops.colloc_points(x, ng)[ids])
         ops.enhance_subset(x, u, Mg, 1.0, ng, W, elem_ids=ids, gamma_values=gv,
                            global_domain=global_domain, bc=bc, status=st, **kw)
     sol = EnhancedSolution(x, W, st)
@@ -295,7 +305,7 @@ def lssvr_primal(rhs_func, domain_range, u_xmin, u_xmax, M, gamma,
     # the kernel derives the flags from the element's global index (Dual.py:150-151)
     off = 0 if is_left_boundary else 1
     ne_global = off + 1 if is_right_boundary else off + 2
-    kw = _rhs_mode(rhs_func, x, n_colloc, M)
+    kw = _rhs_mode(rhs_func, lambda: ops.colloc_points(x, n_colloc), _point_major(M))
     W, st = ops.enhance(x, u, int(M), float(gamma), int(n_colloc), elem_offset=off,
                         ne_global=ne_global,
                         global_domain=(float(global_domain_range[0]), float(global_domain_range[1])),
@@ -357,24 +367,34 @@ class FEMLSSVRPrimalSolver:
         self._x_dev = None
         self._u_dev = None
 
+    @property
+    def _eq(self):
+        # (from the attributes at the time of use: they are public, and were always read when solving)
+        return _Equation(self.rhs, self.coef, self.reaction)
+
+    def _default_mesh(self):
+        return LineMesh.from_nodes(np.linspace(self.global_domain[0], self.global_domain[1], self.num_fem_nodes))
+
+    def _gd_bc(self):
+        """(global domain, Dirichlet values at its two ends) as float pairs."""
+        gd = (float(self.global_domain[0]), float(self.global_domain[1]))
+        return gd, (main_boundary_condition_left(self.global_domain[0]),
+                    main_boundary_condition_right(self.global_domain[1]))
+
     # ---- Dual.py:110-137 --------------------------------------------------------------
     def solve_fem(self):
         """P1 finite-element solve: mesh, element-local assembly, Dirichlet on all
         boundary dofs, tridiagonal solve, nodal values.  Returns ``(u_fem, basis)``
         like the reference (``basis`` is scikit-fem shaped, see ``mesh.py``)."""
         dev = _device(self.device)
-        if self.mesh is None:
-            m = LineMesh.from_nodes(
-                np.linspace(self.global_domain[0], self.global_domain[1], self.num_fem_nodes))
-        else:
-            m = self.mesh
+        m = self._default_mesh() if self.mesh is None else self.mesh
         basis = P1Basis(m)
         x = _to_dev(m.nodes, dev)
-        kw = {}
-        if self.coef is not None:        # kloc = abar / h, abar the quadrature mean of a
-            kw["a_quad"] = _tabulate(self.coef[:1], ops.quad_points(x, self.nquad))[0]
-        if self.reaction is not None:    # consistent mass matrix of c in the bands
-            cq = _tabulate((self.reaction,), ops.quad_points(x, self.nquad))[0]
+        eq, kw = self._eq, {}
+        if eq.a is not None:             # kloc = abar / h, abar the quadrature mean of a
+            kw["a_quad"] = _tabulate(eq.a, ops.quad_points(x, self.nquad))
+        if eq.c is not None:             # consistent mass matrix of c in the bands
+            cq = _tabulate(eq.c, ops.quad_points(x, self.nquad))
             if bool((cq < 0).any().item()):
                 raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
                                  "pivot and assumes an SPD matrix (c >= 0)")
@@ -385,8 +405,7 @@ class FEMLSSVRPrimalSolver:
             xq = ops.quad_points(x, self.nquad)
             fq = _to_dev(self.rhs(xq.cpu().numpy()), dev)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
-        u0 = main_boundary_condition_left(self.global_domain[0])
-        u1 = main_boundary_condition_right(self.global_domain[1])
+        _, (u0, u1) = self._gd_bc()
         if self.fem_solver == "flux":
             # exact-structure solution of A = D^T K D by the element-flux prefix scan
             u = ops.p1_flux_solve(bands["kloc"], bands["load"], u0, u1)
@@ -416,26 +435,18 @@ class FEMLSSVRPrimalSolver:
         if x is None or x.numel() != nodes.size or not np.array_equal(x.cpu().numpy(), nodes):
             x = _to_dev(nodes, dev)
         u = _to_dev(self.fem_values, dev)       # the attribute is authoritative (may be user-set)
-        gd = (float(self.global_domain[0]), float(self.global_domain[1]))
-        bc = (main_boundary_condition_left(self.global_domain[0]),
-              main_boundary_condition_right(self.global_domain[1]))
-        if self.reaction is not None:
-            # tables only, like the varcoef kernels; point-major for the lane kernel
-            pm = int(self.lssvr_M) <= 22
-            a, da = self.coef if self.coef is not None else (_one, _zero)
-            ta, tda, tf, tc = _tabulate((a, da, self.rhs, self.reaction), ops.colloc_points(x, self.n_colloc), pm)
-            W, st = ops.enhance_varcoef(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc),
-                                        ta, tda, tf, global_domain=gd, bc=bc, point_major=pm, c_values=tc)
-        elif self.coef is None:
-            kw = _rhs_mode(self.rhs, x, self.n_colloc, self.lssvr_M)
-            W, st = _enhance(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc),
-                             global_domain=gd, bc=bc, solver=self.solver_id, **kw)
+        gd, bc = self._gd_bc()
+        M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
+        pm = _point_major(M)
+        eq = self._eq
+        if eq.poisson:
+            kw = _rhs_mode(eq.f, lambda: ops.colloc_points(x, n), pm)
+            W, st = _enhance(x, u, M, gamma, n, global_domain=gd, bc=bc, solver=self.solver_id, **kw)
         else:
-            # the varcoef kernels take tables only (a SinRHS too); point-major up to M = 22, as in _rhs_mode
-            pm = int(self.lssvr_M) <= 22
-            tabs = _tabulate((self.coef[0], self.coef[1], self.rhs), ops.colloc_points(x, self.n_colloc), pm)
-            W, st = ops.enhance_varcoef(x, u, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc), *tabs,
-                                        global_domain=gd, bc=bc, point_major=pm)
+            # the varcoef / reaction kernels take tables only (a SinRHS too)
+            ta, tda, tf, tc = eq.tables(ops.colloc_points(x, n), pm)
+            W, st = ops.enhance_varcoef(x, u, M, gamma, n, ta, tda, tf, global_domain=gd, bc=bc, point_major=pm,
+                                        c_values=tc)
         self.enhanced = EnhancedSolution(x, W, st)
         nbad = self.enhanced.n_fallback
         if nbad:
@@ -473,30 +484,14 @@ class FEMLSSVRPrimalSolver:
         if self.enhanced is None:
             raise RuntimeError("call solve() first")
         x, W = self.enhanced.nodes, self.enhanced.W
-        if self.reaction is not None:
-            a, da = self.coef if self.coef is not None else (_one, _zero)
-            ta, tda, tf, tc = _tabulate((a, da, self.rhs, self.reaction), ops.estimate_points(x, nq), True)
-            an = np.broadcast_to(np.asarray(a(x.cpu().numpy()), dtype=np.float64), (x.numel(),))
-            a_ends = _to_dev(np.stack([an[:-1], an[1:]], axis=1), x.device)
-            eta2, _, out3 = ops.estimate_varcoef(x, W, nq, ta, tda, tf, a_ends, point_major=True, c_values=tc)
-            return eta2, out3
-        if self.coef is not None:
-            # a, a', f at the Gauss points (point-major: coalesced); a at the nodes from both sides, aL = aR
-            tabs = _tabulate((self.coef[0], self.coef[1], self.rhs), ops.estimate_points(x, nq), True)
-            an = np.asarray(self.coef[0](x.cpu().numpy()), dtype=np.float64)
-            an = np.broadcast_to(an, (x.numel(),))
-            a_ends = _to_dev(np.stack([an[:-1], an[1:]], axis=1), x.device)
-            eta2, _, out3 = ops.estimate_varcoef(x, W, nq, *tabs, a_ends, point_major=True)
-            return eta2, out3
-        if isinstance(self.rhs, SinRHS):
-            kw = dict(rhs=(self.rhs.amp, self.rhs.omega))
+        eq = self._eq
+        if eq.poisson:
+            eta2, _, out3 = ops.estimate(x, W, nq, **_rhs_mode(eq.f, lambda: ops.estimate_points(x, nq)))
         else:
-            xq = ops.estimate_points(x, nq)
-            f = np.asarray(self.rhs(xq.cpu().numpy()), dtype=np.float64)
-            if f.shape != tuple(xq.shape):
-                f = np.array(np.broadcast_to(f, tuple(xq.shape)))
-            kw = dict(rhs_values=_to_dev(f, x.device))
-        eta2, _, out3 = ops.estimate(x, W, nq, **kw)
+            # a, a', f (, c) at the Gauss points, point-major (coalesced); a at the nodes from both sides, aL = aR
+            ta, tda, tf, tc = eq.tables(ops.estimate_points(x, nq), True)
+            eta2, _, out3 = ops.estimate_varcoef(x, W, nq, ta, tda, tf, eq.a_ends(x), point_major=True,
+                                                 c_values=tc)
         return eta2, out3
 
     def _nq(self, nq):
@@ -540,8 +535,7 @@ class FEMLSSVRPrimalSolver:
             raise ValueError(f"h_min must be >= 0, got {h_min!r}")
         nq = self._nq(nq)
         if self.mesh is None:
-            self.mesh = LineMesh.from_nodes(
-                np.linspace(self.global_domain[0], self.global_domain[1], self.num_fem_nodes))
+            self.mesh = self._default_mesh()
         if self.mesh.nelements > max_elements:
             raise ValueError(f"the initial mesh has {self.mesh.nelements} elements > max_elements = {max_elements}")
         self.adapt_history = []

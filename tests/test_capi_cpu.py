@@ -16,10 +16,12 @@ MEASUREMENT_ONLY = ("lssvr_enhance_profiled", "lssvr_enhance_ws_sequence", "lssv
                     "lssvr_fp64_probe", "lssvr_stream_probe", "lssvr_row_chunk_probe")
 
 
+def _uncommented(path):
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+
+
 def _declared_in(path):
-    txt = open(path).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(lssvr_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(lssvr_[a-z0-9_]+)\s*\(", _uncommented(path))))
 
 
 def _declared():
@@ -46,6 +48,45 @@ def test_header_symbols_exported_and_bound():
     assert lib.lssvr_version() == _capi.ABI_VERSION
     hdr_ver = int(re.search(r"#define LSSVR_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
     assert hdr_ver == _capi.ABI_VERSION
+
+
+def _ctype_of(decl):
+    """ctypes class of one C parameter declaration ("const double* rhs_params_host", "int M", ...)."""
+    m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)\s*(\w+)", decl.strip())
+    assert m, decl
+    base, stars, name = m.groups()
+    if stars == "**":
+        assert base == "lssvr_step_plan", decl
+        return ctypes.POINTER(ctypes.c_void_p)
+    if stars == "*":
+        if name.endswith("_host"):                      # read or written by the host: a typed pointer
+            return ctypes.POINTER({"double": ctypes.c_double, "float": ctypes.c_float}[base])
+        return ctypes.c_void_p                          # device pointers, plans and streams travel as integers
+    return {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "double": ctypes.c_double}[base]
+
+
+def test_signatures_match_header_prototypes():
+    """Every prototype of the two headers against _capi.SIGNATURES: return type, arity and the ctypes class of
+    each argument.  A wrong argtypes entry is silent stack corruption, and nothing else compares the two."""
+    from hybrid_fem_lssvr_amd import _capi
+    protos = {}
+    for path in (HEADER, BENCH_HEADER):
+        for ret, name, params in re.findall(r"^(int|int64_t|const char\*)\s+(lssvr_\w+)\s*\(([^)]*)\)\s*;",
+                                            _uncommented(path), flags=re.M):
+            assert name not in protos, name
+            params = " ".join(params.split())
+            protos[name] = (ret, [] if params == "void" else params.split(","))
+    assert sorted(protos) == _declared() == sorted(_capi.SIGNATURES)
+    restypes = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
+    bad = []
+    for name, (ret, params) in protos.items():
+        res, argtypes = _capi.SIGNATURES[name]
+        want = [_ctype_of(d) for d in params]
+        if res is not restypes[ret] or len(argtypes) != len(want):
+            bad.append((name, ret, len(params), len(argtypes)))
+            continue
+        bad += [(name, i, d.strip(), got) for i, (d, w, got) in enumerate(zip(params, want, argtypes)) if got is not w]
+    assert not bad, "\n".join(map(repr, bad))
 
 
 def test_header_constants_match_binding():
