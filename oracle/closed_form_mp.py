@@ -40,74 +40,58 @@ def _legendre_tables_mp(t, M):
 
 
 def solve_truth(s, dps=60):
-    """``s`` = ``oracle.lssvr_oracle.ElementSystem``.  Rows are rebuilt in
-    extended precision from the float64 (t, x, scl, f, g) it carries; Ahat for the
-    variable-coefficient case is taken from ``s`` as float64 data scaled exactly."""
+    """``s`` = ``oracle.lssvr_oracle.ElementSystem``.  The rows of -(a u')' + c u = f,
+
+        A = scl^2 (-a D2 - (a'/scl) D1 + (c/scl^2) L),
+
+    are *defined* by the float64 data ``s`` carries -- t_k, scl, f(x_k), g and the samples a(x_k), a'(x_k)/scl,
+    c(x_k)/scl^2 (absent: a = 1, a' = 0, c = 0, whose products are exact) -- and are built and solved in mpmath
+    from there."""
     if not HAVE_MP:
         raise RuntimeError("mpmath not available")
     mp.mp.dps = dps
     M, n = s.M, s.n
     scl = mp.mpf(float(s.scl))
     gam = mp.mpf(float(s.gamma))
-    poisson = bool(np.all(s.Ahat[:, :2] == 0.0))
     A = mp.zeros(n, M)
     for k in range(n):
         tk = mp.mpf(float(s.t[k]))
-        _, D1, D2 = _legendre_tables_mp(tk, M)
+        L, D1, D2 = _legendre_tables_mp(tk, M)
+        ak = mp.mpf(1 if s.ak is None else float(s.ak[k]))
+        dak = mp.mpf(0 if s.dak is None else float(s.dak[k]))
+        ck = mp.mpf(0 if s.ck is None else float(s.ck[k]))
+        if s.ak is not None and s.ck is None:
+            # -(a u')' = f keeps the definition its truth values were first computed with: a_k as the rounded
+            # float64 row holds it, recovered from column 2 (L_2'' = 3, L_2' = 3t; column 1 is -a'/scl exactly).
+            # The carried a(x_k) differs from it by an ulp, which moves float64 truth values (DESIGN.md section 14).
+            ak = (-mp.mpf(float(s.Ahat[k, 2])) - dak * 3 * tk) / 3
         for p in range(M):
-            if poisson:
-                A[k, p] = -scl * scl * D2[p]
-            else:
-                # variable coefficient: rows are *defined* by the float64 a(x_k), a'(x_k)
-                # carried in s (ak, dak recovered from columns 1 and 2 of Ahat)
-                dak_over_scl = -mp.mpf(float(s.Ahat[k, 1]))        # L_1'=1, L_1''=0
-                ak = (-mp.mpf(float(s.Ahat[k, 2])) - dak_over_scl * 3 * tk) / 3  # L_2''=3, L_2'=3t
-                A[k, p] = -scl * scl * (ak * D2[p] + dak_over_scl * D1[p])
-    B = mp.zeros(2, M)
+            A[k, p] = scl * scl * (-ak * D2[p] - dak * D1[p] + ck * L[p])
     # the reference evaluates u(xmin), u(xmax) through the same float64 mapdomain
     ta = mp.mpf(float(np.float64(s.off) + np.float64(s.scl) * np.float64(s.a)))
     tb = mp.mpf(float(np.float64(s.off) + np.float64(s.scl) * np.float64(s.b)))
     La, _, _ = _legendre_tables_mp(ta, M)
     Lb, _, _ = _legendre_tables_mp(tb, M)
-    for p in range(M):
-        B[0, p] = La[p]
-        B[1, p] = Lb[p]
-    f = mp.matrix([mp.mpf(float(v)) for v in s.f])
-    g = mp.matrix([mp.mpf(float(v)) for v in s.g])
     K = mp.zeros(M + 2, M + 2)
     AtA = A.T * A
     for i in range(M):
         for j in range(M):
             K[i, j] = gam * AtA[i, j] + (1 if i == j else 0)
-        K[i, M] = B[0, i]
-        K[i, M + 1] = B[1, i]
-        K[M, i] = B[0, i]
-        K[M + 1, i] = B[1, i]
-    Atf = A.T * f
+        K[i, M] = K[M, i] = La[i]
+        K[i, M + 1] = K[M + 1, i] = Lb[i]
+    Atf = A.T * mp.matrix([mp.mpf(float(v)) for v in s.f])
     rhs = mp.matrix(M + 2, 1)
     for i in range(M):
         rhs[i] = gam * Atf[i]
-    rhs[M] = g[0]
-    rhs[M + 1] = g[1]
+    rhs[M] = mp.mpf(float(s.g[0]))
+    rhs[M + 1] = mp.mpf(float(s.g[1]))
     sol = mp.lu_solve(K, rhs)
     return np.array([float(sol[i]) for i in range(M)])
 
 
 def truth_all(nodes, values, M, gamma, n, rhs, global_domain=None, elements=None, dps=60,
-              coef_a=None, coef_da=None, bc_left=0.0, bc_right=0.0):
+              coef_a=None, coef_da=None, bc_left=0.0, bc_right=0.0, coef_c=None):
     """Truth coefficients for ``elements`` (default all) of a mesh."""
     from . import lssvr_oracle as orc
-    nodes = np.asarray(nodes, dtype=np.float64)
-    ne = len(nodes) - 1
-    if global_domain is None:
-        global_domain = (nodes[0], nodes[-1])
-    if elements is None:
-        elements = range(ne)
-    out = []
-    for i in elements:
-        a, b = nodes[i], nodes[i + 1]
-        g_l, g_r = orc.boundary_values(i, ne, a, b, values[i], values[i + 1], global_domain,
-                                       bc_left, bc_right)
-        s = orc.element_system(a, b, g_l, g_r, M, gamma, n, rhs, coef_a, coef_da)
-        out.append(solve_truth(s, dps))
-    return np.array(out)
+    return np.array([solve_truth(s, dps) for s in orc.mesh_element_systems(
+        nodes, values, M, gamma, n, rhs, global_domain, elements, coef_a, coef_da, coef_c, bc_left, bc_right)])

@@ -22,7 +22,11 @@ and hands it to SLSQP (``Dual.py:84-88``).  This module restates
 * ``evaluate_solution`` (``Dual.py:176-203``) and the P1 FEM step the reference
   delegates to scikit-fem (``Dual.py:110-137``; scikit-fem is absent in this
   image, so that part follows SURVEY.md Appendix C and is pinned by the analytic
-  tridiagonal system, not by reference output).
+  tridiagonal system, not by reference output);
+* the product's extensions, which have no reference counterpart: the operator
+  ``-(a u')' + c u = f`` (optional ``coef_a`` / ``coef_da`` / ``coef_c`` through the
+  element system, the solvers' drivers and the P1 step) and the a posteriori
+  indicator (:func:`estimate_indicator`).
 
 The extended-precision "truth" lives in ``oracle/closed_form_mp.py``.
 """
@@ -192,16 +196,23 @@ class ElementSystem:
     """
 
     __slots__ = ("a", "b", "off", "scl", "x", "t", "Ahat", "B", "f", "ftil",
-                 "g", "gamma", "gamma_t", "M", "n")
+                 "g", "gamma", "gamma_t", "M", "n", "ak", "dak", "ck")
 
 
 def element_system(a, b, g_l, g_r, M, gamma, n, rhs=poisson_rhs, coef_a=None,
-                   coef_da=None, f_values=None):
+                   coef_da=None, f_values=None, coef_c=None):
     """Build (Ahat, B, ftil, g) for element [a,b] the way the reference's
     arithmetic defines them (float64 t_k = off + scl*x_k, x_k = linspace).
 
     ``coef_a``/``coef_da`` (callables) switch on the variable-coefficient rows of
-    BASELINE config 5 (no reference counterpart: Dual.py:44 hard-codes -u'').
+    BASELINE config 5 and ``coef_c`` the reaction term of -(a u')' + c u = f (no
+    reference counterpart: Dual.py:44 hard-codes -u''):
+
+        Ahat = -a D2 - (a'/scl) D1 + (c/scl^2) L        
+
+    with a = 1, a' = 0 when ``coef_a`` is absent.  The float64 samples the rows were
+    built from travel with the system as ``ak`` = a(x_k), ``dak`` = a'(x_k)/scl and
+    ``ck`` = c(x_k)/scl^2 (``None`` where the term is absent).
     """
     s = ElementSystem()
     s.a, s.b, s.M, s.n = np.float64(a), np.float64(b), int(M), int(n)
@@ -209,12 +220,16 @@ def element_system(a, b, g_l, g_r, M, gamma, n, rhs=poisson_rhs, coef_a=None,
     s.x = np_linspace(a, b, n)
     s.t = s.off + s.scl * s.x
     L, D1, D2 = legendre_tables(s.t, M)
+    s.ak = s.dak = s.ck = None
     if coef_a is None:
         s.Ahat = -D2
     else:
-        ak = np.asarray(coef_a(s.x), dtype=np.float64)
-        dak = np.asarray(coef_da(s.x), dtype=np.float64)
-        s.Ahat = -(ak[:, None] * D2) - (dak / s.scl)[:, None] * D1
+        s.ak = np.asarray(coef_a(s.x), dtype=np.float64)
+        s.dak = np.asarray(coef_da(s.x), dtype=np.float64) / s.scl
+        s.Ahat = -(s.ak[:, None] * D2) - s.dak[:, None] * D1
+    if coef_c is not None:
+        s.ck = np.asarray(coef_c(s.x), dtype=np.float64) / (s.scl * s.scl)
+        s.Ahat = s.Ahat + s.ck[:, None] * L
     ta = s.off + s.scl * s.a
     tb = s.off + s.scl * s.b
     La, _, _ = legendre_tables(np.array([ta, tb]), M)
@@ -322,32 +337,41 @@ def boundary_values(i, ne, a, b, u_l, u_r, global_domain, bc_left=0.0, bc_right=
     return g_l, g_r
 
 
-def enhance_all(nodes, values, M, gamma, n=12, rhs=poisson_rhs, global_domain=None,
-                solver="bc_elim", coef_a=None, coef_da=None, bc_left=0.0, bc_right=0.0):
-    """Closed-form restatement of ``solve_lssvr_subproblems`` (Dual.py:139-169):
-    returns W float64[ne, M] (row i = ``lssvr_functions[i].coef``) and status."""
+def mesh_element_systems(nodes, values, M, gamma, n, rhs=poisson_rhs, global_domain=None, elements=None,
+                         coef_a=None, coef_da=None, coef_c=None, bc_left=0.0, bc_right=0.0):
+    """The :class:`ElementSystem` of each of ``elements`` (default all) of a mesh, boundary values
+    by :func:`boundary_values`: the one loop behind :func:`enhance_all` and the 60-digit
+    ``closed_form_mp.truth_all``."""
     nodes = np.asarray(nodes, dtype=np.float64)
-    values = np.asarray(values, dtype=np.float64)
     ne = len(nodes) - 1
     if global_domain is None:
         global_domain = (nodes[0], nodes[-1])
-    W = np.zeros((ne, M))
-    status = np.zeros(ne, dtype=np.int32)
-    fn = {"bc_elim": solve_bc_eliminated, "primal": solve_primal_kkt, "dual": solve_dual_gram}[solver]
-    for i in range(ne):
+    for i in (range(ne) if elements is None else elements):
         a, b = nodes[i], nodes[i + 1]
         g_l, g_r = boundary_values(i, ne, a, b, values[i], values[i + 1], global_domain,
                                    bc_left, bc_right)
-        s = element_system(a, b, g_l, g_r, M, gamma, n, rhs, coef_a, coef_da)
-        if solver == "bc_elim":
-            W[i], status[i] = fn(s, return_status=True)
-        else:
-            W[i] = fn(s)
-    return W, status
+        yield element_system(a, b, g_l, g_r, M, gamma, n, rhs, coef_a, coef_da, coef_c=coef_c)
+
+
+def enhance_all(nodes, values, M, gamma, n=12, rhs=poisson_rhs, global_domain=None,
+                solver="bc_elim", coef_a=None, coef_da=None, bc_left=0.0, bc_right=0.0,
+                coef_c=None, elements=None):
+    """Closed-form restatement of ``solve_lssvr_subproblems`` (Dual.py:139-169):
+    returns W float64[ne, M] (row i = ``lssvr_functions[i].coef``) and status; with
+    ``elements``, one row per listed element."""
+    values = np.asarray(values, dtype=np.float64)
+    fn = {"bc_elim": solve_bc_eliminated, "primal": solve_primal_kkt, "dual": solve_dual_gram}[solver]
+    W, status = [], []
+    for s in mesh_element_systems(nodes, values, M, gamma, n, rhs, global_domain, elements,
+                                  coef_a, coef_da, coef_c, bc_left, bc_right):
+        w, st = fn(s, return_status=True) if solver == "bc_elim" else (fn(s), 0)
+        W.append(w)
+        status.append(st)
+    return np.array(W).reshape(-1, M), np.array(status, dtype=np.int32)
 
 
 def enhance_all_vec(nodes, values, M, gamma, n=12, rhs=poisson_rhs, global_domain=None,
-                    coef_a=None, coef_da=None, bc_left=0.0, bc_right=0.0, chunk=200000):
+                    coef_a=None, coef_da=None, bc_left=0.0, bc_right=0.0, chunk=200000, coef_c=None):
     """Batched float64 primal-KKT solve of every element (same rows as
     :func:`element_system`, same equilibration as :func:`solve_primal_kkt`); used by
     the full-size parity tests where the per-element loop is too slow."""
@@ -390,6 +414,8 @@ def enhance_all_vec(nodes, values, M, gamma, n=12, rhs=poisson_rhs, global_domai
             Ahat = -D2
         else:
             Ahat = -(coef_a(x)[..., None] * D2) - (coef_da(x) / scl[:, None])[..., None] * D1
+        if coef_c is not None:
+            Ahat = Ahat + (coef_c(x) / (scl * scl)[:, None])[..., None] * L
         ta = off + scl * a
         tb = off + scl * b
         Bm = np.zeros((m, 2, M))
@@ -511,13 +537,15 @@ def quad_points(nodes, nquad=2):
     return a[:, None] + h[:, None] * xi[None, :]
 
 
-def p1_assemble_local(nodes, rhs=poisson_rhs, coef_a=None, nquad=2):
+def p1_assemble_local(nodes, rhs=poisson_rhs, coef_a=None, nquad=2, coef_c=None):
     """Element-local P1 stiffness and load (Dual.py:117-128).
 
     k_e = abar_e/h [[1,-1],[-1,1]] (abar_e = quadrature mean of a, 1 for Poisson; the
     reference's two minus signs cancel), f_e[j] = h sum_q w_q f(x_q) phi_j(xi_q) with
     the ``nquad``-point Gauss rule on [0,1].  Returns (kdiag[ne], fl[ne], fr[ne]):
-    kdiag = abar_e/h, fl/fr = load on the element's left/right node.
+    kdiag = abar_e/h, fl/fr = load on the element's left/right node.  With ``coef_c`` a
+    fourth item follows, the consistent mass matrix m_e[i][j] = h sum_q w_q c(x_q) phi_i phi_j
+    as (m_ll[ne], m_lr[ne], m_rr[ne]); :func:`p1_scatter` takes either form.
     """
     nodes = np.asarray(nodes, dtype=np.float64)
     xi, wt = gauss_rule01(nquad)
@@ -533,10 +561,14 @@ def p1_assemble_local(nodes, rhs=poisson_rhs, coef_a=None, nquad=2):
         if coef_a is not None:
             am = am + wt[k] * coef_a(xq[:, k])
     abar = np.ones_like(h) if coef_a is None else am
-    return abar / h, h * sl, h * sr
+    if coef_c is None:
+        return abar / h, h * sl, h * sr
+    cq = np.asarray(coef_c(xq), dtype=np.float64)
+    mass = (h * (cq @ (wt * (1.0 - xi) ** 2)), h * (cq @ (wt * (1.0 - xi) * xi)), h * (cq @ (wt * xi ** 2)))
+    return abar / h, h * sl, h * sr, mass
 
 
-def p1_scatter(kdiag, fl, fr):
+def p1_scatter(kdiag, fl, fr, mass=None):
     """Scatter element-local pieces to the global tridiagonal system:
     diag[ne+1], off[ne] (off[i] couples nodes i,i+1), load[ne+1]."""
     ne = len(kdiag)
@@ -546,7 +578,18 @@ def p1_scatter(kdiag, fl, fr):
     diag[1:] += kdiag
     load[:-1] += fl
     load[1:] += fr
-    return diag, -kdiag, load
+    off = -kdiag
+    if mass is not None:
+        diag[:-1] += mass[0]
+        diag[1:] += mass[2]
+        off = off + mass[1]
+    return diag, off, load
+
+
+def p1_bands(nodes, rhs=poisson_rhs, coef_a=None, nquad=2, coef_c=None):
+    """(diag, off, load, kloc) of -(a u')' + c u = f: assembly, then scatter."""
+    kloc, *rest = p1_assemble_local(nodes, rhs, coef_a, nquad, coef_c)
+    return (*p1_scatter(kloc, *rest), kloc)
 
 
 def thomas_dirichlet(diag, off, load, u0=0.0, u1=0.0):
@@ -595,10 +638,9 @@ def banded_dirichlet(diag, off, load, u0=0.0, u1=0.0):
     return u
 
 
-def fem_p1_solve(nodes, rhs=poisson_rhs, coef_a=None, nquad=2):
+def fem_p1_solve(nodes, rhs=poisson_rhs, coef_a=None, nquad=2, coef_c=None):
     """``solve_fem`` (Dual.py:110-137) -> nodal values float64[ne+1]."""
-    kdiag, fl, fr = p1_assemble_local(nodes, rhs, coef_a, nquad)
-    diag, off, load = p1_scatter(kdiag, fl, fr)
+    diag, off, load, _ = p1_bands(nodes, rhs, coef_a, nquad, coef_c)
     if len(diag) > 4096:
         return banded_dirichlet(diag, off, load)
     return thomas_dirichlet(diag, off, load)
@@ -771,3 +813,88 @@ def varcoef_functions(c, phi):
         return -da(x) * np.pi * np.cos(np.pi * x) + a(x) * np.pi ** 2 * np.sin(np.pi * x)
 
     return a, da, f
+
+
+def react_functions(k):
+    """a, a' of BASELINE config 5, c = k (2 + cos 2 pi x), and f manufactured for u = sin(pi x)
+    in -(a u')' + c u = f."""
+    a, da, f_vc = varcoef_functions(*varcoef_params())
+
+    def c(x):
+        x = np.asarray(x, dtype=np.float64)
+        return k * (2.0 + np.cos(2.0 * np.pi * x))
+
+    def f(x):
+        x = np.asarray(x, dtype=np.float64)
+        return f_vc(x) + c(x) * np.sin(np.pi * x)
+
+    return a, da, c, f
+
+
+# --------------------------------------------------------------------------
+# a posteriori indicator (DESIGN.md sections 11 and 12; no reference counterpart)
+# --------------------------------------------------------------------------
+def estimate_points(x, xi):
+    """The indicator's abscissae, element-major [ne, nq]: Gauss nodes ``xi`` of [-1, 1] mapped to each element."""
+    a, b = x[:-1, None], x[1:, None]
+    return 0.5 * (a + b) + (0.5 * (b - a)) * xi[None, :]
+
+
+def estimate_indicator(x, W, xi, wt, f, a=None, da=None, c=None, a_ends=None, scales=False):
+    """eta2[e] = h^2 int_e (f + a u'' + a' u' - c u)^2 + h/2 (J_e^2 + J_{e+1}^2), J_i = aR_{i-1} u_{i-1}'(x_i)
+    - aL_i u_i'(x_i) the flux jump at interior node i (0 at both ends); returns (eta2[ne], J[ne+1]).
+
+    ``xi``, ``wt``: Gauss rule on [-1, 1]; ``f``, ``a``, ``da``, ``c``: element-major [ne, nq] tables at
+    :func:`estimate_points` (an absent table drops its term; absent ``a`` is a = 1); ``a_ends`` [ne, 2]: a at each
+    element's two nodes (absent: 1).  With ``scales`` two more arrays follow, ``jscale[ne+1]`` and ``escale[ne]``:
+    J and eta2 with every term taken by its magnitude, which bound what rounding can do where the terms cancel
+    (without ``a``, the Poisson form, jscale is |u_{i-1}'(x_i)| + |u_i'(x_i)|).
+    """
+    ne, M = W.shape
+    h = x[1:] - x[:-1]
+    scl = 2.0 / h
+    T = np.zeros((3, len(xi), M))           # P_k, P_k', P_k'' at xi
+    D = np.zeros((2, M))                    # P_k'(-1), P_k'(+1)
+    for k in range(M):
+        ek = np.zeros(M)
+        ek[k] = 1.0
+        T[0, :, k] = _leg.legval(xi, ek)
+        T[1, :, k] = _leg.legval(xi, _leg.legder(ek, 1))
+        T[2, :, k] = _leg.legval(xi, _leg.legder(ek, 2))
+        D[:, k] = _leg.legval(np.array([-1.0, 1.0]), _leg.legder(ek, 1))
+    if a is None:
+        # Poisson form: the exact P_k'(+-1) = (+-1)^(k+1) k(k+1)/2.  Clenshaw rounds some of them in the last
+        # bit, and the Poisson bars were set against these tables (DESIGN.md section 14)
+        kk = np.arange(M, dtype=np.float64)
+        D[1] = kk * (kk + 1) / 2
+        D[0] = D[1] * (-1.0) ** (kk + 1)
+    terms = [f, (W @ T[2].T) * (scl ** 2)[:, None]]
+    if a is not None:
+        terms[1] = a * terms[1]
+    if da is not None:
+        terms.append(da * ((W @ T[1].T) * scl[:, None]))
+    if c is not None:
+        terms.append(-(c * (W @ T[0].T)))
+    r = terms[0]
+    rs = np.abs(terms[0])
+    for t in terms[1:]:
+        r = r + t
+        rs = rs + np.abs(t)
+    fl = (W @ D[0]) * scl
+    fr = (W @ D[1]) * scl
+    if a_ends is not None:
+        fl, fr = a_ends[:, 0] * fl, a_ends[:, 1] * fr
+    J = np.zeros(ne + 1)
+    J[1:-1] = fr[:-1] - fl[1:]
+    eta2 = h * h * (0.5 * h * ((r * r) @ wt)) + 0.5 * h * (J[:-1] ** 2 + J[1:] ** 2)
+    if not scales:
+        return eta2, J
+    jscale = np.zeros(ne + 1)
+    if a is None:                           # Poisson form: the two one-sided derivatives by magnitude
+        jscale[1:-1] = np.abs(fr[:-1]) + np.abs(fl[1:])
+    else:                                   # the end-point sums term by term in magnitude
+        ae = np.ones((ne, 2)) if a_ends is None else np.abs(a_ends)
+        jscale[1:-1] = (ae[:-1, 1] * ((np.abs(W[:-1]) @ np.abs(D[1])) * scl[:-1])
+                        + ae[1:, 0] * ((np.abs(W[1:]) @ np.abs(D[0])) * scl[1:]))
+    escale = h * h * (0.5 * h * ((rs * rs) @ wt)) + 0.5 * h * (jscale[:-1] ** 2 + jscale[1:] ** 2)
+    return eta2, J, jscale, escale

@@ -1,6 +1,6 @@
 """numpy prototype of solve_adaptive on -eps u'' + u = 1, u(+-1) = 0: the loop of the facade
 -- P1 with mass matrix, per-element solve, indicator, threshold marking, bisection -- on the float64 restatement
-of tests/react_restatement.py, no GPU.  Prints the element count, the max errors on 20 001 points of the adapted
+of oracle/lssvr_oracle.py, no GPU.  Prints the element count, the max errors on 20 001 points of the adapted
 and of the uniform 128-element solve, and their ratio (the bar of tests/test_gpu_react.py is this ratio / 5)."""
 import math
 import os
@@ -9,8 +9,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import react_restatement as rr                      # noqa: E402
+sys.path.insert(0, ROOT)
 from oracle import lssvr_oracle as orc              # noqa: E402
 
 EPS, M, N, GAMMA, NQUAD, THETA, MAXE = 1e-4, 9, 16, 1e10, 5, 0.5, 128
@@ -26,8 +25,8 @@ def exact(x):
 
 
 def solve(nodes):
-    u = rr.fem_p1_solve_react(nodes, f, a, c, NQUAD)
-    return rr.enhance_all_react(nodes, u, M, GAMMA, N, a, da, c, f, global_domain=(-1.0, 1.0))
+    u = orc.fem_p1_solve(nodes, f, a, NQUAD, c)
+    return orc.enhance_all(nodes, u, M, GAMMA, N, rhs=f, global_domain=(-1.0, 1.0), coef_a=a, coef_da=da, coef_c=c)[0]
 
 
 def main():
@@ -36,9 +35,10 @@ def main():
     nodes = np.linspace(-1, 1, 9)
     while True:
         W = solve(nodes)
-        pts = rr.estimate_points(nodes, xi)
+        pts = orc.estimate_points(nodes, xi)
         an = a(nodes)
-        eta2 = rr.estimate_react(nodes, W, xi, wt, a(pts), da(pts), c(pts), f(pts), np.stack([an[:-1], an[1:]], 1))
+        eta2, _ = orc.estimate_indicator(nodes, W, xi, wt, f(pts), a(pts), da(pts), c(pts),
+                                         np.stack([an[:-1], an[1:]], 1))
         mark = eta2 >= THETA * THETA * eta2.max()
         if len(nodes) - 1 + mark.sum() > MAXE or not mark.any():
             break

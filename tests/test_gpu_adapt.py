@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 from numpy.polynomial.legendre import Legendre
 
+from oracle import lssvr_oracle as orc
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,36 +24,17 @@ def _mesh(rng, ne, lo=-1.0, span=2.0):
 # ---------------------------------------------------------------------------
 # numpy restatements
 # ---------------------------------------------------------------------------
-def _ref_points(x, nq):
+def _points(x, nq):
     from hybrid_fem_lssvr_amd import ops
-    xi, _ = ops.gauss_rule(nq)
-    a, b = x[:-1, None], x[1:, None]
-    return 0.5 * (a + b) + (0.5 * (b - a)) * xi[None, :]
+    return orc.estimate_points(x, ops.gauss_rule(nq)[0])
 
 
-def _ref_estimate(x, W, nq, f):
-    """eta2 = h^2 int (f + u'')^2 + h/2 (J_e^2 + J_{e+1}^2), J_i = u_{i-1}'(x_i) - u_i'(x_i); f [ne, nq]."""
+def _estimate(x, W, nq, f):
+    """The oracle's Poisson indicator (eta2, J, scale of J); f [ne, nq].  The nodes come from numpy, the
+    weights from the library."""
     from hybrid_fem_lssvr_amd import ops
-    _, wt = ops.gauss_rule(nq)
-    xi = np.polynomial.legendre.leggauss(nq)[0]
-    ne, M = W.shape
-    h = x[1:] - x[:-1]
-    scl = 2.0 / h
-    T = np.zeros((nq, M))
-    for k in range(2, M):
-        T[:, k] = Legendre.basis(k).deriv(2)(xi)
-    r = f + (W @ T.T) * (scl ** 2)[:, None]
-    integ = 0.5 * h * ((r * r) @ wt)
-    k = np.arange(M, dtype=np.float64)
-    w = k * (k + 1) / 2
-    dR = (W @ w) * scl
-    dL = (W @ (w * (-1.0) ** (k + 1))) * scl
-    J = np.zeros(ne + 1)
-    J[1:-1] = dR[:-1] - dL[1:]
-    eta2 = h * h * integ + 0.5 * h * (J[:-1] ** 2 + J[1:] ** 2)
-    jscale = np.zeros(ne + 1)
-    jscale[1:-1] = np.abs(dR[:-1]) + np.abs(dL[1:])
-    return eta2, J, jscale
+    return orc.estimate_indicator(x, W, np.polynomial.legendre.leggauss(nq)[0], ops.gauss_rule(nq)[1], f,
+                                  scales=True)[:3]
 
 
 def _ref_refine(x, eta2, mx, theta, h_min):
@@ -129,7 +112,7 @@ def test_estimate_vs_numpy(dev, M, ne, layout):
     W = rng.standard_normal((ne, M)) / (1.0 + np.arange(M)) ** 2
     xd, Wd = _t(x, dev), _t(W, dev)
     pts = ops.estimate_points(xd, nq).cpu().numpy()
-    xq = _ref_points(x, nq)
+    xq = _points(x, nq)
     assert np.array_equal(pts, xq)
     amp, omega = 2.5, 1.7
     f = amp * np.sin(omega * xq)
@@ -141,7 +124,7 @@ def test_estimate_vs_numpy(dev, M, ne, layout):
         kw = dict(rhs_values=_t(f.T, dev), point_major=True)
     eta2, jump, out3 = ops.estimate(xd, Wd, nq, want_jump=True, **kw)
     eta2, jump, o3 = eta2.cpu().numpy(), jump.cpu().numpy(), out3.cpu().numpy()
-    e_ref, j_ref, jscale = _ref_estimate(x, W, nq, f)
+    e_ref, j_ref, jscale = _estimate(x, W, nq, f)
     assert np.all(np.abs(eta2 - e_ref) <= 1e-12 * np.abs(e_ref) + 1e-300)
     assert jump[0] == 0.0 and jump[-1] == 0.0
     assert np.all(np.abs(jump - j_ref) <= 1e-12 * jscale)
@@ -164,7 +147,7 @@ def test_estimate_non_finite_entries(dev):
     W[bad[20:], 5] = np.inf
     eta2, _, out3 = ops.estimate(_t(x, dev), _t(W, dev), nq, rhs=(1.0, 2.0))
     eta2, o3 = eta2.cpu().numpy(), out3.cpu().numpy()
-    e_ref, _, _ = _ref_estimate(x, W, nq, np.sin(2.0 * _ref_points(x, nq)))
+    e_ref, _, _ = _estimate(x, W, nq, np.sin(2.0 * _points(x, nq)))
     fin = np.isfinite(eta2)
     assert np.array_equal(fin, np.isfinite(e_ref))
     assert o3[2] == float(np.count_nonzero(~fin)) and o3[2] >= 40
@@ -186,7 +169,7 @@ def test_estimate_exact_polynomial_is_rounding_only(dev, M):
     for e in range(ne):
         c = p.convert(domain=[x[e], x[e + 1]], kind=Legendre).coef
         W[e, :c.size] = c
-    xq = _ref_points(x, nq)
+    xq = _points(x, nq)
     f = -p.deriv(2)(xq)
     eta2, _, _ = ops.estimate(_t(x, dev), _t(W, dev), nq, rhs_values=_t(f, dev))
     eta2 = eta2.cpu().numpy()

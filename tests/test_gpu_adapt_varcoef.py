@@ -5,7 +5,7 @@ import math
 
 import numpy as np
 import pytest
-from numpy.polynomial.legendre import Legendre, legder, legval
+from numpy.polynomial.legendre import Legendre
 
 from oracle import lssvr_oracle as orc
 
@@ -23,54 +23,19 @@ def _mesh(rng, ne, lo=-1.0, span=2.0):
 
 
 # ---------------------------------------------------------------------------
-# numpy restatement
+# numpy restatement (oracle/lssvr_oracle.py)
 # ---------------------------------------------------------------------------
-def _ref_points(x, nq):
+def _points(x, nq):
     from hybrid_fem_lssvr_amd import ops
-    xi, _ = ops.gauss_rule(nq)
-    a, b = x[:-1, None], x[1:, None]
-    return 0.5 * (a + b) + (0.5 * (b - a)) * xi[None, :]
+    return orc.estimate_points(x, ops.gauss_rule(nq)[0])
 
 
-def _ref_estimate_vc(x, W, nq, a, da, f, a_ends):
-    """eta2 = h^2 int (f + a u'' + a' u')^2 + h/2 (J_e^2 + J_{e+1}^2), J_i = aR_{i-1} u_{i-1}'(x_i) - aL_i u_i'(x_i);
-    a, da, f element-major [ne, nq] at the Gauss points, a_ends [ne, 2].  Returns (eta2, J, scale of J, scale of
-    eta2): the scales take every term by its magnitude, so that they bound what rounding can do where the
-    terms cancel."""
+def _estimate_vc(x, W, nq, a, da, f, a_ends):
+    """The oracle's indicator for -(a u')' = f on the library's Gauss rule: (eta2, J, scale of J, scale of eta2);
+    a, da, f element-major [ne, nq] at the Gauss points, a_ends [ne, 2]."""
     from hybrid_fem_lssvr_amd import ops
     xi, wt = ops.gauss_rule(nq)
-    ne, M = W.shape
-    h = x[1:] - x[:-1]
-    scl = 2.0 / h
-    T1 = np.zeros((nq, M))
-    T2 = np.zeros((nq, M))
-    for k in range(M):
-        ek = np.zeros(M)
-        ek[k] = 1.0
-        T1[:, k] = legval(xi, legder(ek, 1))
-        T2[:, k] = legval(xi, legder(ek, 2))
-    t2 = a * ((W @ T2.T) * (scl ** 2)[:, None])
-    t1 = da * ((W @ T1.T) * scl[:, None])
-    r = f + t2 + t1
-    rs = np.abs(f) + np.abs(t2) + np.abs(t1)
-    integ = 0.5 * h * ((r * r) @ wt)
-    ends = np.array([-1.0, 1.0])
-    D = np.zeros((2, M))
-    for k in range(M):
-        ek = np.zeros(M)
-        ek[k] = 1.0
-        D[:, k] = legval(ends, legder(ek, 1))
-    dL = (W @ D[0]) * scl
-    dR = (W @ D[1]) * scl
-    fl, fr = a_ends[:, 0] * dL, a_ends[:, 1] * dR
-    J = np.zeros(ne + 1)
-    J[1:-1] = fr[:-1] - fl[1:]
-    jscale = np.zeros(ne + 1)               # the end-point sums term by term in magnitude
-    jscale[1:-1] = (np.abs(a_ends[:-1, 1]) * ((np.abs(W[:-1]) @ np.abs(D[1])) * scl[:-1])
-                    + np.abs(a_ends[1:, 0]) * ((np.abs(W[1:]) @ np.abs(D[0])) * scl[1:]))
-    eta2 = h * h * integ + 0.5 * h * (J[:-1] ** 2 + J[1:] ** 2)
-    escale = h * h * (0.5 * h * ((rs * rs) @ wt)) + 0.5 * h * (jscale[:-1] ** 2 + jscale[1:] ** 2)
-    return eta2, J, jscale, escale
+    return orc.estimate_indicator(x, W, xi, wt, f, a, da, a_ends=a_ends, scales=True)
 
 
 def _random_case(rng, ne, M, nq, pad=0):
@@ -78,7 +43,7 @@ def _random_case(rng, ne, M, nq, pad=0):
     W = rng.standard_normal((ne, M)) / (1.0 + np.arange(M)) ** 2
     if pad:
         W = np.concatenate([W, np.zeros((ne, pad))], axis=1)
-    xq = _ref_points(x, nq)
+    xq = _points(x, nq)
     a = 1.0 + 0.5 * np.sin(1.3 * xq)
     da = 0.65 * np.cos(1.3 * xq)
     f = 2.5 * np.sin(1.7 * xq) + 0.3
@@ -93,7 +58,7 @@ def _run_vc(dev, x, W, nq, a, da, f, a_ends, pm, **kw):
 
 
 def _check_vs_ref(eta2, jump, o3, x, W, nq, a, da, f, a_ends):
-    e_ref, j_ref, jscale, _ = _ref_estimate_vc(x, W, nq, a, da, f, a_ends)
+    e_ref, j_ref, jscale, _ = _estimate_vc(x, W, nq, a, da, f, a_ends)
     assert np.all(np.abs(eta2 - e_ref) <= 1e-12 * np.abs(e_ref) + 1e-300), np.max(np.abs(eta2 - e_ref) / e_ref)
     assert jump[0] == 0.0 and jump[-1] == 0.0
     assert np.all(np.abs(jump - j_ref) <= 1e-12 * jscale)
@@ -177,7 +142,7 @@ def test_exact_polynomial_solution_is_rounding_only(dev, M):
     for e in range(ne):
         c = p.convert(domain=[x[e], x[e + 1]], kind=Legendre).coef
         W[e, :c.size] = c
-    xq = _ref_points(x, nq)
+    xq = _points(x, nq)
     f = -(ap * p.deriv(1)).deriv(1)(xq)
     an = ap(x)
     a_ends = np.stack([an[:-1], an[1:]], axis=1)
@@ -310,7 +275,7 @@ def test_facade_coef_matches_oracle(dev, ne, M, n):
     a_ends = np.stack([an[:-1], an[1:]], axis=1)
     e_dir, _, _ = _run_vc(dev, nodes, W, nq, a(xq), da(xq), f(xq), a_ends, True)
     assert np.array_equal(eta2.view(np.int64), e_dir.cpu().numpy().view(np.int64))
-    e_ref, _, _, escale = _ref_estimate_vc(nodes, W, nq, a(xq), da(xq), f(xq), a_ends)
+    e_ref, _, _, escale = _estimate_vc(nodes, W, nq, a(xq), da(xq), f(xq), a_ends)
     assert np.all(np.abs(eta2 - e_ref) <= 1e-12 * e_ref + 1e-13 * np.sqrt(e_ref * escale))
     assert np.all(eta2 > 0)
 

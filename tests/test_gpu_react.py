@@ -1,21 +1,23 @@
 """GPU: the reaction term -(a u')' + c u = f through every layer -- enhancement kernels (lane and MFMA) against the
-float64 restatement (tests/react_restatement.py) and its 60-digit solve, the P1 bands with the mass matrix, the
+float64 restatement (oracle/lssvr_oracle.py, ``coef_c``) and its 60-digit solve, the P1 bands with the mass matrix, the
 indicator, and the facade's ``reaction`` keyword through solve / estimate / solve_adaptive."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-import react_restatement as rr                      # noqa: E402
-from oracle import lssvr_oracle as orc              # noqa: E402
+from oracle import closed_form_mp as cf
+from oracle import lssvr_oracle as orc
 
 pytestmark = pytest.mark.gpu
+
+GAMMA = 1e4
+SIZES = [(2000, 9, 16), (300, 20, 32), (100, 26, 40), (25, 9, 16)]      # (ne, M, n)
+KS = [1.0, 1e4]
+
+
+def _oracle_W(nodes, values, M, n, a, da, c, f, **kw):
+    return orc.enhance_all(nodes, values, M, GAMMA, n, rhs=f, coef_a=a, coef_da=da, coef_c=c, **kw)[0]
 
 
 def _t(a, dev):
@@ -34,24 +36,25 @@ def _enhance(dev, nodes, values, M, n, a, da, c, f, pm, **kw):
     x = _t(nodes, dev)
     ta, tda, tf, tc = _tables(x, n, (a, da, f, c), pm, dev)
     kw.setdefault("global_domain", (float(nodes[0]), float(nodes[-1])))
-    W, st = ops.enhance_varcoef(x, _t(values, dev), M, rr.GAMMA, n, ta, tda, tf, point_major=pm, c_values=tc, **kw)
+    W, st = ops.enhance_varcoef(x, _t(values, dev), M, GAMMA, n, ta, tda, tf, point_major=pm, c_values=tc, **kw)
     return W.cpu().numpy(), st.cpu().numpy()
 
 
 # ---------------------------------------------------------------------------
 # 1. enhancement
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("k", rr.KS)
-@pytest.mark.parametrize("ne,M,n", rr.SIZES)
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("ne,M,n", SIZES)
 def test_enhance_react_vs_restatement_and_60_digits(dev, note, ne, M, n, k):
     """1e-11 against the float64 restatement (1e-10 above M = 22, as the project has it), 1e-13 against the
     60-digit minimiser on elements 0, ne/3, ne-1, both table layouts, which agree to 1e-12."""
-    a, da, c, f = rr.react_functions(k)
+    a, da, c, f = orc.react_functions(k)
     nodes = np.linspace(-1, 1, ne + 1)
     values = np.sin(np.pi * nodes)
-    Wo = rr.enhance_all_react(nodes, values, M, rr.GAMMA, n, a, da, c, f)
+    Wo = _oracle_W(nodes, values, M, n, a, da, c, f)
     sel = [0, ne // 3, ne - 1]
-    tr = rr.truth_all_react(nodes, values, M, rr.GAMMA, n, a, da, c, f, sel) if rr.cf.HAVE_MP else None
+    tr = (cf.truth_all(nodes, values, M, GAMMA, n, f, elements=sel, coef_a=a, coef_da=da, coef_c=c)
+          if cf.HAVE_MP else None)
     got = {}
     for pm in (False, True):
         W, st = _enhance(dev, nodes, values, M, n, a, da, c, f, pm)
@@ -70,10 +73,10 @@ def test_enhance_react_vs_restatement_and_60_digits(dev, note, ne, M, n, k):
     assert orc.rel_l2_coef(got[True], got[False]).max() <= 1e-12
 
 
-@pytest.mark.parametrize("ne,M,n", rr.SIZES)
+@pytest.mark.parametrize("ne,M,n", SIZES)
 def test_enhance_react_with_zero_c_is_varcoef(dev, note, ne, M, n):
     from hybrid_fem_lssvr_amd import ops
-    a, da, _, _ = rr.react_functions(1.0)
+    a, da, _, _ = orc.react_functions(1.0)
     f = orc.varcoef_functions(*orc.varcoef_params())[2]
     nodes = np.linspace(-1, 1, ne + 1)
     values = np.sin(np.pi * nodes)
@@ -81,7 +84,7 @@ def test_enhance_react_with_zero_c_is_varcoef(dev, note, ne, M, n):
         W, st = _enhance(dev, nodes, values, M, n, a, da, lambda x: 0.0 * x, f, pm)
         x = _t(nodes, dev)
         ta, tda, tf = _tables(x, n, (a, da, f), pm, dev)
-        W0, st0 = ops.enhance_varcoef(x, _t(values, dev), M, rr.GAMMA, n, ta, tda, tf, point_major=pm,
+        W0, st0 = ops.enhance_varcoef(x, _t(values, dev), M, GAMMA, n, ta, tda, tf, point_major=pm,
                                       global_domain=(-1.0, 1.0))
         W0 = W0.cpu().numpy()
         assert np.all(st == 0) and np.all(st0.cpu().numpy() == 0)
@@ -96,22 +99,21 @@ def test_enhance_react_with_zero_c_is_varcoef(dev, note, ne, M, n):
 def test_enhance_react_odd_sizes_and_shard(dev, ne, M, n):
     """Element counts off the wave / workgroup multiples, as a shard of a larger mesh (elem_offset > 0,
     ne_global > ne: no end element is a global-boundary one)."""
-    a, da, c, f = rr.react_functions(1e4)
+    a, da, c, f = orc.react_functions(1e4)
     nodes = np.linspace(-0.7, 0.9, ne + 1)
     values = np.sin(np.pi * nodes)
     bar = 1e-11 if M <= 22 else 1e-10
     for pm in (False, True):
         W, st = _enhance(dev, nodes, values, M, n, a, da, c, f, pm)
         assert np.all(st == 0)
-        Wo = rr.enhance_all_react(nodes, values, M, rr.GAMMA, n, a, da, c, f)
+        Wo = _oracle_W(nodes, values, M, n, a, da, c, f)
         assert orc.rel_l2_coef(W, Wo).max() <= bar
         # shard: the same elements as the interior of a mesh of ne + 5 elements; the Dirichlet values do not apply
         W, st = _enhance(dev, nodes, values, M, n, a, da, c, f, pm, elem_offset=3, ne_global=ne + 5,
                          global_domain=(-1.0, 1.0), bc=(7.0, -3.0))
         assert np.all(st == 0)
-        Wo = np.array([orc.solve_bc_eliminated(rr.element_system_react(
-            i, np.concatenate([[-9.0], nodes, [9.0]]), np.concatenate([[0.0], values, [0.0]]), M, rr.GAMMA, n, a, da,
-            c, f, (-9.0, 9.0))[0]) for i in range(1, ne + 1)])
+        Wo = _oracle_W(np.concatenate([[-9.0], nodes, [9.0]]), np.concatenate([[0.0], values, [0.0]]), M, n, a, da,
+                       c, f, global_domain=(-9.0, 9.0), elements=range(1, ne + 1))
         assert orc.rel_l2_coef(W, Wo).max() <= bar
 
 
@@ -121,7 +123,7 @@ def test_enhance_react_leaves_pad_columns_alone(dev, M, n):
     behind the ne*M doubles is untouched: a sentinel row after the last element survives."""
     import torch
     from hybrid_fem_lssvr_amd import ops
-    a, da, c, f = rr.react_functions(1.0)
+    a, da, c, f = orc.react_functions(1.0)
     ne = 130
     nodes = np.linspace(-1, 1, ne + 1)
     values = np.sin(np.pi * nodes)
@@ -129,7 +131,7 @@ def test_enhance_react_leaves_pad_columns_alone(dev, M, n):
     for pm in (False, True):
         buf = torch.full(((ne + 2) * M,), -777.0, dtype=torch.float64, device=dev)
         ta, tda, tf, tc = _tables(x, n, (a, da, f, c), pm, dev)
-        ops.enhance_varcoef(x, _t(values, dev), M, rr.GAMMA, n, ta, tda, tf, point_major=pm, c_values=tc,
+        ops.enhance_varcoef(x, _t(values, dev), M, GAMMA, n, ta, tda, tf, point_major=pm, c_values=tc,
                             out=buf[: ne * M], global_domain=(-1.0, 1.0))
         h = buf.cpu().numpy()
         assert np.all(h[ne * M:] == -777.0) and not np.any(h[: ne * M] == -777.0)
@@ -137,7 +139,7 @@ def test_enhance_react_leaves_pad_columns_alone(dev, M, n):
 
 def test_enhance_react_rejects_fewer_points_than_bubbles(dev):
     from hybrid_fem_lssvr_amd import _capi
-    a, da, c, f = rr.react_functions(1.0)
+    a, da, c, f = orc.react_functions(1.0)
     nodes = np.linspace(-1, 1, 11)
     with pytest.raises(_capi.LssvrHipError, match="M-2"):
         _enhance(dev, nodes, np.sin(np.pi * nodes), 22, 19, a, da, c, f, True)
@@ -150,7 +152,7 @@ def test_enhance_react_rejects_fewer_points_than_bubbles(dev):
 @pytest.mark.parametrize("ne", [1, 37, 255, 256, 5000])
 def test_p1_assemble_react_vs_restatement(dev, ne, nquad):
     from hybrid_fem_lssvr_amd import ops
-    a, da, c, f = rr.react_functions(1e4)
+    a, da, c, f = orc.react_functions(1e4)
     rng = np.random.default_rng(ne + nquad)
     h = rng.uniform(0.5, 1.5, ne)
     nodes = np.concatenate([[-1.0], -1.0 + 2.0 * np.cumsum(h) / h.sum()])
@@ -158,7 +160,7 @@ def test_p1_assemble_react_vs_restatement(dev, ne, nquad):
     xq = ops.quad_points(x, nquad).cpu().numpy()
     fq, aq, cq = _t(f(xq), dev), _t(a(xq), dev), _t(c(xq), dev)
     b = ops.p1_assemble(x, nquad, rhs_quad=fq, a_quad=aq, c_quad=cq, want_local=True)
-    diag, off, load, kloc = rr.p1_bands_react(nodes, f, a, c, nquad)
+    diag, off, load, kloc = orc.p1_bands(nodes, f, a, nquad, c)
     np.testing.assert_allclose(b["diag"].cpu().numpy(), diag, rtol=1e-13, atol=0)
     np.testing.assert_allclose(b["off"].cpu().numpy(), off, rtol=1e-13, atol=0)
     np.testing.assert_allclose(b["load"].cpu().numpy(), load, rtol=1e-13, atol=1e-18)
@@ -185,7 +187,7 @@ def _est_case(rng, ne, M, nq):
     x = np.concatenate([[-3.0], -3.0 + 6.0 * np.cumsum(h) / h.sum()])
     W = rng.standard_normal((ne, M)) / (1.0 + np.arange(M)) ** 2
     xi, wt = ops.gauss_rule(nq)
-    xq = rr.estimate_points(x, xi)
+    xq = orc.estimate_points(x, xi)
     a = 1.0 + 0.5 * np.sin(1.3 * xq)
     da = 0.65 * np.cos(1.3 * xq)
     c = 3.0 + 2.0 * np.cos(0.7 * xq)
@@ -209,7 +211,7 @@ def test_estimate_react_vs_numpy(dev, M, nq):
     rng = np.random.default_rng(2000 * M + nq)
     for ne in (1, 127, 128, 129, 3001):
         x, W, xi, wt, a, da, c, f, a_ends = _est_case(rng, ne, M, nq)
-        ref = rr.estimate_react(x, W, xi, wt, a, da, c, f, a_ends)
+        ref = orc.estimate_indicator(x, W, xi, wt, f, a, da, c, a_ends)[0]
         for pm in (False, True):
             eta2, o3 = _run_est(dev, x, W, nq, a, da, c, f, a_ends, pm)
             assert np.all(np.abs(eta2 - ref) <= 1e-12 * np.abs(ref) + 1e-300), np.max(np.abs(eta2 - ref) / ref)
@@ -239,14 +241,14 @@ def test_facade_solve_with_coef_and_reaction(dev, note, ne, M, n):
     """Manufactured u = sin(pi x): the L2 error of solve() is that of the numpy restatement of the whole pipeline
     (P1 with mass matrix -> Thomas -> per-element solve) within 1e-10 ||u||."""
     import hybrid_fem_lssvr_amd as pkg
-    a, da, c, f = rr.react_functions(1e4)
-    s = pkg.FEMLSSVRPrimalSolver(ne + 1, lssvr_M=M, lssvr_gamma=rr.GAMMA, n_colloc=n, rhs=f, nquad=3,
+    a, da, c, f = orc.react_functions(1e4)
+    s = pkg.FEMLSSVRPrimalSolver(ne + 1, lssvr_M=M, lssvr_gamma=GAMMA, n_colloc=n, rhs=f, nquad=3,
                                  coef=(a, da), reaction=c)
     s.solve()
     nodes = np.linspace(-1, 1, ne + 1)
-    uo = rr.fem_p1_solve_react(nodes, f, a, c, 3)
+    uo = orc.fem_p1_solve(nodes, f, a, 3, c)
     assert np.max(np.abs(s.fem_values - uo)) <= 1e-12
-    Wo = rr.enhance_all_react(nodes, uo, M, rr.GAMMA, n, a, da, c, f)
+    Wo = _oracle_W(nodes, uo, M, n, a, da, c, f)
     xq = np.linspace(-1, 1, 4001)
     ex = np.sin(np.pi * xq)
     e_gpu = np.linalg.norm(s.evaluate_solution(xq) - ex)
@@ -261,11 +263,11 @@ def test_facade_solve_with_coef_and_reaction(dev, note, ne, M, n):
 
 def test_facade_reaction_without_coef_is_unit_a(dev):
     import hybrid_fem_lssvr_amd as pkg
-    _, _, c, _ = rr.react_functions(1.0)
+    _, _, c, _ = orc.react_functions(1.0)
     f = lambda x: (np.pi ** 2 + c(x)) * np.sin(np.pi * x)          # noqa: E731
     one, zero = (lambda x: 1.0 + 0.0 * x), (lambda x: 0.0 * x)
-    s1 = pkg.FEMLSSVRPrimalSolver(41, lssvr_M=9, lssvr_gamma=rr.GAMMA, n_colloc=16, rhs=f, reaction=c)
-    s2 = pkg.FEMLSSVRPrimalSolver(41, lssvr_M=9, lssvr_gamma=rr.GAMMA, n_colloc=16, rhs=f, reaction=c,
+    s1 = pkg.FEMLSSVRPrimalSolver(41, lssvr_M=9, lssvr_gamma=GAMMA, n_colloc=16, rhs=f, reaction=c)
+    s2 = pkg.FEMLSSVRPrimalSolver(41, lssvr_M=9, lssvr_gamma=GAMMA, n_colloc=16, rhs=f, reaction=c,
                                   coef=(one, zero))
     s1.solve()
     s2.solve()
@@ -279,19 +281,19 @@ def test_facade_without_reaction_is_the_old_path(dev):
     """reaction=None: the same W as the direct ops call on the same inputs, bit for bit."""
     import hybrid_fem_lssvr_amd as pkg
     from hybrid_fem_lssvr_amd import ops
-    a, da, _, _ = rr.react_functions(1.0)
+    a, da, _, _ = orc.react_functions(1.0)
     f = orc.varcoef_functions(*orc.varcoef_params())[2]
-    s = pkg.FEMLSSVRPrimalSolver(301, lssvr_M=9, lssvr_gamma=rr.GAMMA, n_colloc=16, rhs=f, coef=(a, da),
+    s = pkg.FEMLSSVRPrimalSolver(301, lssvr_M=9, lssvr_gamma=GAMMA, n_colloc=16, rhs=f, coef=(a, da),
                                  reaction=None)
     s.solve()
     x = _t(s.fem_nodes, dev)
     ta, tda, tf = _tables(x, 16, (a, da, f), True, dev)
-    W, _ = ops.enhance_varcoef(x, _t(s.fem_values, dev), 9, rr.GAMMA, 16, ta, tda, tf, point_major=True,
+    W, _ = ops.enhance_varcoef(x, _t(s.fem_values, dev), 9, GAMMA, 16, ta, tda, tf, point_major=True,
                                global_domain=(-1.0, 1.0))
     assert np.array_equal(W.cpu().numpy(), s.enhanced.W.cpu().numpy())
-    s = pkg.FEMLSSVRPrimalSolver(301, lssvr_M=9, lssvr_gamma=rr.GAMMA, n_colloc=16)
+    s = pkg.FEMLSSVRPrimalSolver(301, lssvr_M=9, lssvr_gamma=GAMMA, n_colloc=16)
     s.solve()
-    W, _ = ops.enhance(_t(s.fem_nodes, dev), _t(s.fem_values, dev), 9, rr.GAMMA, 16, global_domain=(-1.0, 1.0))
+    W, _ = ops.enhance(_t(s.fem_nodes, dev), _t(s.fem_values, dev), 9, GAMMA, 16, global_domain=(-1.0, 1.0))
     assert np.array_equal(W.cpu().numpy(), s.enhanced.W.cpu().numpy())
 
 

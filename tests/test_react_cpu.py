@@ -12,9 +12,6 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
 HEADER = os.path.join(ROOT, "include", "lssvr_hip.h")
 NEW = ["lssvr_enhance_react", "lssvr_enhance_react_ws", "lssvr_p1_assemble_react", "lssvr_estimate_react"]
 
@@ -160,35 +157,35 @@ def test_restatement_agrees_with_its_60_digit_solve(ne, M, n, k):
     """Both float64 solves of the restated system against the 60-digit minimiser of the same QP on elements 0,
     ne/3, ne-1: measured 2e-14 or better on these inputs, so the GPU tests' bars (1e-11 / 1e-10 against the
     restatement, 1e-13 against the minimiser) are reachable.  The bar here is 1e-13, the one the kernels get."""
-    import react_restatement as rr
+    from oracle import closed_form_mp as cf
     from oracle import lssvr_oracle as orc
-    if not rr.cf.HAVE_MP:
+    if not cf.HAVE_MP:
         pytest.skip("mpmath not importable")
-    a, da, c, f = rr.react_functions(k)
+    a, da, c, f = orc.react_functions(k)
     nodes = np.linspace(-1, 1, ne + 1)
     values = np.sin(np.pi * nodes)
     sel = [0, ne // 3, ne - 1]
-    tr = rr.truth_all_react(nodes, values, M, rr.GAMMA, n, a, da, c, f, sel)
-    for solve in (orc.solve_bc_eliminated, orc.solve_primal_kkt):
-        W = rr.enhance_all_react(nodes, values, M, rr.GAMMA, n, a, da, c, f, elements=sel, solve=solve)
+    kw = dict(elements=sel, coef_a=a, coef_da=da, coef_c=c)
+    tr = cf.truth_all(nodes, values, M, 1e4, n, f, **kw)
+    for solver in ("bc_elim", "primal"):
+        W, _ = orc.enhance_all(nodes, values, M, 1e4, n, rhs=f, solver=solver, **kw)
         err = orc.rel_l2_coef(W, tr).max()
-        print(f"ne={ne} M={M} n={n} k={k:g} {solve.__name__}: {err:.2e}")
+        print(f"ne={ne} M={M} n={n} k={k:g} {solver}: {err:.2e}")
         assert err <= 1e-13
 
 
 def test_p1_restatement_is_the_old_one_without_c():
-    import react_restatement as rr
     from oracle import lssvr_oracle as orc
-    a, da, c, f = rr.react_functions(1.0)
+    a, da, c, f = orc.react_functions(1.0)
     nodes = np.linspace(-1, 1, 38)
-    d, o, ld, k = rr.p1_bands_react(nodes, f, a, lambda x: 0.0 * x, 3)
+    d, o, ld, k = orc.p1_bands(nodes, f, a, 3, lambda x: 0.0 * x)
     d0, o0, l0 = orc.p1_scatter(*orc.p1_assemble_local(nodes, f, a, 3))
     assert np.array_equal(d, d0) and np.array_equal(o, o0) and np.array_equal(ld, l0)
     # manufactured u = sin(pi x): the P1 solve with the mass matrix converges at second order
     errs = []
     for ne in (40, 80):
         x = np.linspace(-1, 1, ne + 1)
-        errs.append(np.max(np.abs(rr.fem_p1_solve_react(x, f, a, c, 3) - np.sin(np.pi * x))))
+        errs.append(np.max(np.abs(orc.fem_p1_solve(x, f, a, 3, c) - np.sin(np.pi * x))))
     assert errs[1] < errs[0] / 3.5
 
 
