@@ -146,13 +146,42 @@ __device__ __forceinline__ void load_row_global(const double* __restrict__ W, in
   for (int k = 0; k < MT; ++k) c[k] = k < M ? W[e * M + k] : 0.0;
 }
 
-// stage_rows and reduce_partials restate the W staging and the reduction of estimate_kernel for
-// estimate_vc_kernel; estimate_kernel keeps its inline copy (routed through them, its code is scheduled differently).
+// The pieces the three estimators are made of (one text each: the kernels differ in their tables and residual only).
 //
+// Row t of the LDS coefficient table, TS entries per degree k: {P_k''} (TS = 1), {P_k', P_k''} (2) or
+// {P_k', P_k'', P_k} (3) at t, by the forward recurrences of legendre_deriv_sum; degrees >= M are zero.
+template <int MT, int TS>
+__device__ __forceinline__ void fill_table(double* __restrict__ Tq, double t, int M) {
+  auto put = [&](int k, double d, double s, double v) {
+    const bool in = k < M;
+    if constexpr (TS == 1) {
+      Tq[k] = in ? s : 0.0;
+    } else {
+      Tq[TS * k] = in ? d : 0.0;
+      Tq[TS * k + 1] = in ? s : 0.0;
+      if constexpr (TS == 3) Tq[TS * k + 2] = in ? v : 0.0;
+    }
+  };
+  double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
+  put(0, 0.0, 0.0, 1.0);
+  if (MT > 1) put(1, 1.0, 0.0, t);
+  for (int k = 1; k + 1 < MT; ++k) {
+    const double a = (double)(2 * k + 1);
+    const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
+    const double d2 = d0 + a * p1;
+    const double s2 = s0 + a * d1;
+    put(k + 1, d2, s2, p2);
+    p0 = p1; p1 = p2;
+    d0 = d1; d1 = d2;
+    s0 = s1; s1 = s2;
+  }
+}
+
 // the chunk's contiguous `total` = nrow*M doubles of W from `src` (coalesced) into LDS rows of odd stride ms;
-// column stepping: i += kEstBlock  ->  (row, col) += (qM, rM)
+// column stepping: i += kEstBlock  ->  (row, col) += (kEstBlock / M, kEstBlock % M)
 __device__ __forceinline__ void stage_rows(double* __restrict__ rows, const double* __restrict__ src, int total,
-                                           int M, int ms, int qM, int rM, int tid) {
+                                           int M, int ms, int tid) {
+  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
   int r = tid / M, col = tid - (tid / M) * M;
   for (int i = tid; i < total; i += kEstBlock) {
     rows[r * ms + col] = src[i];
@@ -162,6 +191,56 @@ __device__ __forceinline__ void stage_rows(double* __restrict__ rows, const doub
       col -= M;
       ++r;
     }
+  }
+}
+
+// End value of the neighbour `en` at the node it shares with the chunk (side 0: its left end, 1: its right end),
+// recomputed from HBM: the same function on the same row as the lane that owns it, so bit-identical.  FLUX: scaled
+// by a_ends to the flux a u'.
+template <int MT, bool FLUX>
+__device__ __forceinline__ double neighbour_end(const double* __restrict__ W, const double* __restrict__ x,
+                                                const double* __restrict__ a_ends, int64_t en, int M, int side) {
+  double cn[MT];
+  load_row_global<MT>(W, en, M, cn);
+  const DomainMap dn = map_params(x[en], x[en + 1]);
+  double l, r;
+  end_derivs<MT>(cn, dn.scl, l, r);
+  const double d = side ? r : l;
+  if constexpr (FLUX) return a_ends[2 * en + side] * d;
+  else return d;
+}
+
+// Jumps at both ends of element e = c0 + tid from its own end values (vl, vr): the neighbours' come from the chunk's
+// LDS arrays sl / sr, from neighbour_end at the two chunk edges; J_0 = J_ne = 0.
+template <int MT, bool FLUX>
+__device__ __forceinline__ void end_jumps(const double* __restrict__ W, const double* __restrict__ x,
+                                          const double* __restrict__ a_ends, int64_t e, int64_t ne, int M, int tid,
+                                          int nrow, const double* sl, const double* sr, double vl, double vr,
+                                          double& jl, double& jr) {
+  double r_prev = 0.0, l_next = 0.0;
+  if (e > 0) r_prev = tid > 0 ? sr[tid - 1] : neighbour_end<MT, FLUX>(W, x, a_ends, e - 1, M, 1);
+  if (e + 1 < ne) l_next = tid + 1 < nrow ? sl[tid + 1] : neighbour_end<MT, FLUX>(W, x, a_ends, e + 1, M, 0);
+  jl = e > 0 ? r_prev - vl : 0.0;
+  jr = e + 1 < ne ? vr - l_next : 0.0;
+}
+
+// eta2 and the left jump of element e from acc = the Gauss sum of the squared residual on [-1, 1]; the lane's
+// running {sum, max, non-finite count}
+__device__ __forceinline__ void store_indicator(double* __restrict__ eta2_out, double* __restrict__ jump, int64_t e,
+                                                int64_t ne, double h, double acc, double jl, double jr, double& bsum,
+                                                double& bmax, double& bcnt) {
+  const double half = 0.5 * h;
+  const double eta2 = (h * h) * (half * acc) + half * (jl * jl + jr * jr);
+  eta2_out[e] = eta2;
+  if (jump) {
+    jump[e] = jl;
+    if (e + 1 == ne) jump[ne] = 0.0;
+  }
+  if (fabs(eta2) < INFINITY) {
+    bsum += eta2;
+    bmax = fmax(bmax, eta2);
+  } else {
+    bcnt += 1.0;
   }
 }
 
@@ -205,43 +284,14 @@ __global__ __launch_bounds__(kEstBlock) void estimate_kernel(EstimateArgs p, Gau
   double* sdr = sdl + kEstBlock;
   double* red = sdr + kEstBlock;
   if (tid < nq) {
-    const double t = g.xi[tid];
-    sxi[tid] = t;
+    sxi[tid] = g.xi[tid];
     swt[tid] = g.wt[tid];
-    double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
-    T[tid * MT + 0] = 0.0;
-    if (MT > 1) T[tid * MT + 1] = 0.0;
-    for (int k = 1; k + 1 < MT; ++k) {
-      const double a = (double)(2 * k + 1);
-      const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
-      const double d2 = d0 + a * p1;
-      const double s2 = s0 + a * d1;
-      T[tid * MT + k + 1] = k + 1 < M ? s2 : 0.0;
-      p0 = p1; p1 = p2;
-      d0 = d1; d1 = d2;
-      s0 = s1; s1 = s2;
-    }
+    fill_table<MT, 1>(T + tid * MT, g.xi[tid], M);
   }
-  // column stepping of the staging copy: i += kEstBlock  ->  (row, col) += (qM, rM)
-  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
   double bsum = 0.0, bmax = 0.0, bcnt = 0.0;
   for (int64_t c0 = (int64_t)blockIdx.x * kEstBlock; c0 < ne; c0 += (int64_t)gridDim.x * kEstBlock) {
     const int nrow = (int)(ne - c0 < kEstBlock ? ne - c0 : kEstBlock);
-    // stage the chunk's contiguous nrow*M doubles of W (coalesced), rows padded to an odd stride
-    {
-      const double* src = p.W + c0 * M;
-      const int total = nrow * M;
-      int r = tid / M, col = tid - (tid / M) * M;
-      for (int i = tid; i < total; i += kEstBlock) {
-        rows[r * ms + col] = src[i];
-        r += qM;
-        col += rM;
-        if (col >= M) {
-          col -= M;
-          ++r;
-        }
-      }
-    }
+    stage_rows(rows, p.W + c0 * M, nrow * M, M, ms, tid);
     __syncthreads();
     const int64_t e = c0 + tid;
     const bool valid = tid < nrow;
@@ -260,34 +310,8 @@ __global__ __launch_bounds__(kEstBlock) void estimate_kernel(EstimateArgs p, Gau
     sdr[tid] = dr;
     __syncthreads();
     if (valid) {
-      // neighbours' end derivatives: from the staged chunk, recomputed from HBM at chunk edges
-      double dr_prev = 0.0, dl_next = 0.0;
-      if (e > 0) {
-        if (tid > 0) {
-          dr_prev = sdr[tid - 1];
-        } else {
-          double cn[MT];
-          load_row_global<MT>(p.W, e - 1, M, cn);
-          const DomainMap dn = map_params(p.x[e - 1], a);
-          double l, r;
-          end_derivs<MT>(cn, dn.scl, l, r);
-          dr_prev = r;
-        }
-      }
-      if (e + 1 < ne) {
-        if (tid + 1 < nrow) {
-          dl_next = sdl[tid + 1];
-        } else {
-          double cn[MT];
-          load_row_global<MT>(p.W, e + 1, M, cn);
-          const DomainMap dn = map_params(b, p.x[e + 2]);
-          double l, r;
-          end_derivs<MT>(cn, dn.scl, l, r);
-          dl_next = l;
-        }
-      }
-      const double jl = e > 0 ? dr_prev - dl : 0.0;
-      const double jr = e + 1 < ne ? dr - dl_next : 0.0;
+      double jl, jr;
+      end_jumps<MT, false>(p.W, p.x, nullptr, e, ne, M, tid, nrow, sdl, sdr, dl, dr, jl, jr);
       // interior residual f + u'' at the nq Gauss points
       const double scl2 = dm.scl * dm.scl;
       double acc = 0.0;
@@ -303,181 +327,23 @@ __global__ __launch_bounds__(kEstBlock) void estimate_kernel(EstimateArgs p, Gau
         const double r = f + s * scl2;
         acc = fma(swt[q], r * r, acc);
       }
-      const double h = dm.oldlen;
-      const double half = 0.5 * h;
-      const double eta2 = (h * h) * (half * acc) + half * (jl * jl + jr * jr);
-      p.eta2[e] = eta2;
-      if (p.jump) {
-        p.jump[e] = jl;
-        if (e + 1 == ne) p.jump[ne] = 0.0;
-      }
-      if (fabs(eta2) < INFINITY) {
-        bsum += eta2;
-        bmax = fmax(bmax, eta2);
-      } else {
-        bcnt += 1.0;
-      }
+      store_indicator(p.eta2, p.jump, e, ne, dm.oldlen, acc, jl, jr, bsum, bmax, bcnt);
     }
     __syncthreads();      // rows / sdl / sdr are rewritten by the next chunk
-  }
-  red[tid] = bsum;
-  red[kEstBlock + tid] = bmax;
-  red[2 * kEstBlock + tid] = bcnt;
-  __syncthreads();
-  for (int off = kEstBlock / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-      red[tid] += red[tid + off];
-      red[kEstBlock + tid] = fmax(red[kEstBlock + tid], red[kEstBlock + tid + off]);
-      red[2 * kEstBlock + tid] += red[2 * kEstBlock + tid + off];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    p.work[3 * blockIdx.x + 0] = red[0];
-    p.work[3 * blockIdx.x + 1] = red[kEstBlock];
-    p.work[3 * blockIdx.x + 2] = red[2 * kEstBlock];
-  }
-}
-
-// Variable coefficients, -(a u')' = f: residual f + a u'' + a' u' and the jump of the flux a u',
-//   J_e = aR_{e-1} u_{e-1}'(x_e) - aL_e u_e'(x_e)   (a_ends[2e] = aL_e, a_ends[2e+1] = aR_e).
-// The structure of estimate_kernel: a lane per element, W staged through LDS, the neighbours' end fluxes from
-// LDS and recomputed from HBM only at chunk edges (the same products of the same values: bit-identical).
-// PM: the a, a', f tables are point-major t[q*ne + e], else element-major t[e*nq + q].
-// Dynamic LDS: T[nq*MT] pairs {P_k'(xi_q), P_k''(xi_q)} | wt[nq] | rows[kEstBlock*ms] | fl[kEstBlock] |
-// fr[kEstBlock] | red[3*kEstBlock].
-template <int MT, bool PM>
-__global__ __launch_bounds__(kEstBlock) void estimate_vc_kernel(EstimateVcArgs p, GaussRuleN g) {
-  extern __shared__ double lds[];
-  const int tid = threadIdx.x;
-  const int nq = p.nq, M = p.M, ms = p.ms;
-  const int64_t ne = p.ne;
-  double* T = lds;
-  double* swt = T + 2 * nq * MT;
-  double* rows = swt + nq;
-  double* sfl = rows + kEstBlock * ms;
-  double* sfr = sfl + kEstBlock;
-  double* red = sfr + kEstBlock;
-  if (tid < nq) {
-    const double t = g.xi[tid];
-    double* Tq = T + 2 * tid * MT;
-    swt[tid] = g.wt[tid];
-    double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
-    Tq[0] = 0.0;
-    Tq[1] = 0.0;
-    if (MT > 1) {
-      Tq[2] = M > 1 ? 1.0 : 0.0;
-      Tq[3] = 0.0;
-    }
-    for (int k = 1; k + 1 < MT; ++k) {
-      const double a = (double)(2 * k + 1);
-      const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
-      const double d2 = d0 + a * p1;
-      const double s2 = s0 + a * d1;
-      Tq[2 * (k + 1)] = k + 1 < M ? d2 : 0.0;
-      Tq[2 * (k + 1) + 1] = k + 1 < M ? s2 : 0.0;
-      p0 = p1; p1 = p2;
-      d0 = d1; d1 = d2;
-      s0 = s1; s1 = s2;
-    }
-  }
-  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
-  double bsum = 0.0, bmax = 0.0, bcnt = 0.0;
-  for (int64_t c0 = (int64_t)blockIdx.x * kEstBlock; c0 < ne; c0 += (int64_t)gridDim.x * kEstBlock) {
-    const int nrow = (int)(ne - c0 < kEstBlock ? ne - c0 : kEstBlock);
-    stage_rows(rows, p.W + c0 * M, nrow * M, M, ms, qM, rM, tid);
-    __syncthreads();
-    const int64_t e = c0 + tid;
-    const bool valid = tid < nrow;
-    double c[MT];
-#pragma unroll
-    for (int k = 0; k < MT; ++k) c[k] = (valid && k < M) ? rows[tid * ms + k] : 0.0;
-    double xa = 0.0, xb = 1.0, aL = 0.0, aR = 0.0;
-    if (valid) {
-      xa = p.x[e];
-      xb = p.x[e + 1];
-      aL = p.a_ends[2 * e];
-      aR = p.a_ends[2 * e + 1];
-    }
-    const DomainMap dm = map_params(xa, xb);
-    double dl, dr;
-    end_derivs<MT>(c, dm.scl, dl, dr);
-    const double fl = aL * dl, fr = aR * dr;
-    sfl[tid] = fl;
-    sfr[tid] = fr;
-    __syncthreads();
-    if (valid) {
-      double fr_prev = 0.0, fl_next = 0.0;
-      if (e > 0) {
-        if (tid > 0) {
-          fr_prev = sfr[tid - 1];
-        } else {
-          double cn[MT];
-          load_row_global<MT>(p.W, e - 1, M, cn);
-          const DomainMap dn = map_params(p.x[e - 1], xa);
-          double l, r;
-          end_derivs<MT>(cn, dn.scl, l, r);
-          fr_prev = p.a_ends[2 * e - 1] * r;
-        }
-      }
-      if (e + 1 < ne) {
-        if (tid + 1 < nrow) {
-          fl_next = sfl[tid + 1];
-        } else {
-          double cn[MT];
-          load_row_global<MT>(p.W, e + 1, M, cn);
-          const DomainMap dn = map_params(xb, p.x[e + 2]);
-          double l, r;
-          end_derivs<MT>(cn, dn.scl, l, r);
-          fl_next = p.a_ends[2 * e + 2] * l;
-        }
-      }
-      const double jl = e > 0 ? fr_prev - fl : 0.0;
-      const double jr = e + 1 < ne ? fr - fl_next : 0.0;
-      // interior residual f + a u'' + a' u' at the nq Gauss points
-      const double scl2 = dm.scl * dm.scl;
-      double acc = 0.0;
-#pragma unroll 1
-      for (int q = 0; q < nq; ++q) {
-        const double* Tq = T + 2 * q * MT;
-        double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int k = 1; k < MT; ++k) {
-          s1 = fma(c[k], Tq[2 * k], s1);
-          s2 = fma(c[k], Tq[2 * k + 1], s2);
-        }
-        const int64_t i = PM ? (int64_t)q * ne + e : e * nq + q;
-        const double r = p.rhs_values[i] + p.a_values[i] * (s2 * scl2) + p.da_values[i] * (s1 * dm.scl);
-        acc = fma(swt[q], r * r, acc);
-      }
-      const double h = dm.oldlen;
-      const double half = 0.5 * h;
-      const double eta2 = (h * h) * (half * acc) + half * (jl * jl + jr * jr);
-      p.eta2[e] = eta2;
-      if (p.jump) {
-        p.jump[e] = jl;
-        if (e + 1 == ne) p.jump[ne] = 0.0;
-      }
-      if (fabs(eta2) < INFINITY) {
-        bsum += eta2;
-        bmax = fmax(bmax, eta2);
-      } else {
-        bcnt += 1.0;
-      }
-    }
-    __syncthreads();      // rows / sfl / sfr are rewritten by the next chunk
   }
   reduce_partials(red, tid, bsum, bmax, bcnt, p.work);
 }
 
-// Reaction term, -(a u')' + c u = f: estimate_vc_kernel with the residual f + a u'' + a' u' - c u.  The LDS table
-// holds the triples {P_k', P_k'', P_k}; staging, neighbour fluxes, jumps and reduction are those of
-// estimate_vc_kernel.  (A copy, not a shared body: routed through one template the existing kernel is scheduled
-// differently, and its device code is kept as it is.)
-// Dynamic LDS: T[nq*MT] triples | wt[nq] | rows[kEstBlock*ms] | fl[kEstBlock] | fr[kEstBlock] | red[3*kEstBlock].
-template <int MT, bool PM>
-__global__ __launch_bounds__(kEstBlock) void estimate_react_kernel(EstimateReactArgs p, GaussRuleN g) {
-  constexpr int TS = 3;                   // table entries per (point, degree)
+// Variable coefficients, -(a u')' = f (TS = 2), and the reaction term, -(a u')' + c u = f (TS = 3, Args =
+// EstimateReactArgs): residual f + a u'' + a' u' [- c u] and the jump of the flux a u',
+//   J_e = aR_{e-1} u_{e-1}'(x_e) - aL_e u_e'(x_e)   (a_ends[2e] = aL_e, a_ends[2e+1] = aR_e).
+// The structure of estimate_kernel: a lane per element, W staged through LDS, the neighbours' end fluxes from
+// LDS and recomputed from HBM only at chunk edges (the same products of the same values: bit-identical).
+// PM: the a, a', [c,] f tables are point-major t[q*ne + e], else element-major t[e*nq + q].
+// Dynamic LDS: T[nq*MT] pairs {P_k'(xi_q), P_k''(xi_q)} or triples {P_k', P_k'', P_k} | wt[nq] | rows[kEstBlock*ms] |
+// fl[kEstBlock] | fr[kEstBlock] | red[3*kEstBlock].
+template <int MT, bool PM, int TS, typename Args>
+__device__ __forceinline__ void estimate_tables_body(const Args& p, const GaussRuleN& g) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x;
   const int nq = p.nq, M = p.M, ms = p.ms;
@@ -489,36 +355,13 @@ __global__ __launch_bounds__(kEstBlock) void estimate_react_kernel(EstimateReact
   double* sfr = sfl + kEstBlock;
   double* red = sfr + kEstBlock;
   if (tid < nq) {
-    const double t = g.xi[tid];
-    double* Tq = T + TS * tid * MT;
     swt[tid] = g.wt[tid];
-    double p0 = 1.0, p1 = t, d0 = 0.0, d1 = 1.0, s0 = 0.0, s1 = 0.0;
-    Tq[0] = 0.0;
-    Tq[1] = 0.0;
-    Tq[2] = 1.0;
-    if (MT > 1) {
-      Tq[TS] = M > 1 ? 1.0 : 0.0;
-      Tq[TS + 1] = 0.0;
-      Tq[TS + 2] = M > 1 ? t : 0.0;
-    }
-    for (int k = 1; k + 1 < MT; ++k) {
-      const double a = (double)(2 * k + 1);
-      const double p2 = (a * t * p1 - (double)k * p0) / (double)(k + 1);
-      const double d2 = d0 + a * p1;
-      const double s2 = s0 + a * d1;
-      Tq[TS * (k + 1)] = k + 1 < M ? d2 : 0.0;
-      Tq[TS * (k + 1) + 1] = k + 1 < M ? s2 : 0.0;
-      Tq[TS * (k + 1) + 2] = k + 1 < M ? p2 : 0.0;
-      p0 = p1; p1 = p2;
-      d0 = d1; d1 = d2;
-      s0 = s1; s1 = s2;
-    }
+    fill_table<MT, TS>(T + TS * tid * MT, g.xi[tid], M);
   }
-  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
   double bsum = 0.0, bmax = 0.0, bcnt = 0.0;
   for (int64_t c0 = (int64_t)blockIdx.x * kEstBlock; c0 < ne; c0 += (int64_t)gridDim.x * kEstBlock) {
     const int nrow = (int)(ne - c0 < kEstBlock ? ne - c0 : kEstBlock);
-    stage_rows(rows, p.W + c0 * M, nrow * M, M, ms, qM, rM, tid);
+    stage_rows(rows, p.W + c0 * M, nrow * M, M, ms, tid);
     __syncthreads();
     const int64_t e = c0 + tid;
     const bool valid = tid < nrow;
@@ -540,34 +383,9 @@ __global__ __launch_bounds__(kEstBlock) void estimate_react_kernel(EstimateReact
     sfr[tid] = fr;
     __syncthreads();
     if (valid) {
-      double fr_prev = 0.0, fl_next = 0.0;
-      if (e > 0) {
-        if (tid > 0) {
-          fr_prev = sfr[tid - 1];
-        } else {
-          double cn[MT];
-          load_row_global<MT>(p.W, e - 1, M, cn);
-          const DomainMap dn = map_params(p.x[e - 1], xa);
-          double l, r;
-          end_derivs<MT>(cn, dn.scl, l, r);
-          fr_prev = p.a_ends[2 * e - 1] * r;
-        }
-      }
-      if (e + 1 < ne) {
-        if (tid + 1 < nrow) {
-          fl_next = sfl[tid + 1];
-        } else {
-          double cn[MT];
-          load_row_global<MT>(p.W, e + 1, M, cn);
-          const DomainMap dn = map_params(xb, p.x[e + 2]);
-          double l, r;
-          end_derivs<MT>(cn, dn.scl, l, r);
-          fl_next = p.a_ends[2 * e + 2] * l;
-        }
-      }
-      const double jl = e > 0 ? fr_prev - fl : 0.0;
-      const double jr = e + 1 < ne ? fr - fl_next : 0.0;
-      // interior residual f + a u'' + a' u' - c u at the nq Gauss points
+      double jl, jr;
+      end_jumps<MT, true>(p.W, p.x, p.a_ends, e, ne, M, tid, nrow, sfl, sfr, fl, fr, jl, jr);
+      // interior residual at the nq Gauss points
       const double scl2 = dm.scl * dm.scl;
       double acc = 0.0;
 #pragma unroll 1
@@ -578,31 +396,28 @@ __global__ __launch_bounds__(kEstBlock) void estimate_react_kernel(EstimateReact
         for (int k = 1; k < MT; ++k) {
           s1 = fma(c[k], Tq[TS * k], s1);
           s2 = fma(c[k], Tq[TS * k + 1], s2);
-          s0 = fma(c[k], Tq[TS * k + 2], s0);
+          if constexpr (TS == 3) s0 = fma(c[k], Tq[TS * k + 2], s0);
         }
         const int64_t i = PM ? (int64_t)q * ne + e : e * nq + q;
-        const double r =
-            p.rhs_values[i] + p.a_values[i] * (s2 * scl2) + p.da_values[i] * (s1 * dm.scl) - p.c_values[i] * s0;
+        double r = p.rhs_values[i] + p.a_values[i] * (s2 * scl2) + p.da_values[i] * (s1 * dm.scl);
+        if constexpr (TS == 3) r = r - p.c_values[i] * s0;
         acc = fma(swt[q], r * r, acc);
       }
-      const double h = dm.oldlen;
-      const double half = 0.5 * h;
-      const double eta2 = (h * h) * (half * acc) + half * (jl * jl + jr * jr);
-      p.eta2[e] = eta2;
-      if (p.jump) {
-        p.jump[e] = jl;
-        if (e + 1 == ne) p.jump[ne] = 0.0;
-      }
-      if (fabs(eta2) < INFINITY) {
-        bsum += eta2;
-        bmax = fmax(bmax, eta2);
-      } else {
-        bcnt += 1.0;
-      }
+      store_indicator(p.eta2, p.jump, e, ne, dm.oldlen, acc, jl, jr, bsum, bmax, bcnt);
     }
     __syncthreads();      // rows / sfl / sfr are rewritten by the next chunk
   }
   reduce_partials(red, tid, bsum, bmax, bcnt, p.work);
+}
+
+template <int MT, bool PM>
+__global__ __launch_bounds__(kEstBlock) void estimate_vc_kernel(EstimateVcArgs p, GaussRuleN g) {
+  estimate_tables_body<MT, PM, 2>(p, g);
+}
+
+template <int MT, bool PM>
+__global__ __launch_bounds__(kEstBlock) void estimate_react_kernel(EstimateReactArgs p, GaussRuleN g) {
+  estimate_tables_body<MT, PM, 3>(p, g);
 }
 
 // one workgroup: the per-block partials in a fixed order -> out3 (bitwise reproducible)
