@@ -111,6 +111,9 @@ SIGNATURES = {
     "lssvr_enhance_react_ws": _sig(_SHARD, _REACT_TABLES, [_c_int], _OUT, _WS, _STREAM, _TIMED),
     "lssvr_p1_assemble_react": _sig(_MESH, _RHS, [_c_dp, _c_dp], _BANDS, _LOCAL, _STREAM),
     "lssvr_estimate_react": _sig(_SOLN, [_c_int], _REACT_TABLES, [_c_int, _c_dp], _EST_OUT, _STREAM),
+    # several load cases on one mesh (additive to ABI 7): ..., gxmin, gxmax, bc_values, ncases, M, n_colloc, gamma
+    "lssvr_enhance_multi": _sig(_SHARD[:7], [_c_dp, _c_int], _SHARD[9:], _REACT_TABLES, [_c_int], _OUT, _STREAM,
+                                _TIMED),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

@@ -558,6 +558,60 @@ int lssvr_enhance_react_ws(const double* x, const double* u, int64_t ne, int64_t
   return timed_launch([&](const lssvr::LaunchOpts* o) { return react_dispatch(a, s, o); }, kernel_ms_host);
 }
 
+int lssvr_enhance_multi(const double* x, const double* u, int64_t ne, int64_t elem_offset,
+                        int64_t ne_global, double gxmin, double gxmax, const double* bc_values, int ncases,
+                        int M, int n_colloc, double gamma, const double* a_values, const double* da_values,
+                        const double* c_values, const double* rhs_values, int table_layout, double* W,
+                        int32_t* status, int32_t* fail_count, void* stream, float* kernel_ms_host) {
+  lssvr::EnhanceMultiArgs a{};
+  // the shard / ne / M / n_colloc / gamma / table rules of lssvr_enhance_react_ws (c_values may be NULL here)
+  int rc = bind_varcoef_ws(a, x, u, ne, elem_offset, ne_global, gxmin, gxmax, 0.0, 0.0, M, n_colloc, gamma,
+                           a_values, da_values, rhs_values, table_layout, W, status, fail_count, nullptr, 0);
+  if (rc != LSSVR_OK) return rc;
+  if (ncases < 1) return fail(LSSVR_ERR_SIZE, "ncases = %d < 1", ncases);
+  if (n_colloc < M - 2)
+    return fail(LSSVR_ERR_SOLVER, "lssvr_enhance_multi: n_colloc = %d < M-2 = %d (primal solve only)", n_colloc,
+                M - 2);
+  const int64_t per_case = ne * (int64_t)(M > n_colloc ? M : n_colloc);
+  if (per_case > 0 && per_case * ncases / ncases != per_case) return fail(LSSVR_ERR_SIZE, "ncases*ne*M overflows");
+  if (ne == 0) return LSSVR_OK;
+  a.c_values = c_values;
+  a.bc_values = bc_values;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (M <= lssvr::kReactSmallMaxM)
+    return timed_launch(
+        [&](const lssvr::LaunchOpts* o) { return check_launch(lssvr::enhance_multi(a, ncases, s, o), "enhance_multi"); },
+        kernel_ms_host);
+  // Above the lane kernels: the wave kernel of the single-case entry, once per case -- correct, no faster.  Those
+  // kernels take the Dirichlet pair by value, so a shard that holds an end of the global domain reads bc_values
+  // back first (the stream is synchronised).
+  std::vector<double> bc((size_t)ncases * 2, 0.0);
+  if (bc_values && (elem_offset == 0 || elem_offset + ne == ne_global)) {
+    hipError_t e = hipMemcpyAsync(bc.data(), bc_values, bc.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(LSSVR_ERR_LAUNCH, "lssvr_enhance_multi: bc_values: %s", hipGetErrorString(e));
+  }
+  if (kernel_ms_host) *kernel_ms_host = 0.0f;
+  for (int j = 0; j < ncases; ++j) {
+    lssvr::EnhanceReactArgs r = a;
+    r.u = u + (int64_t)j * (ne + 1);
+    r.rhs_values = rhs_values + (int64_t)j * ne * n_colloc;
+    r.W = W + (int64_t)j * ne * M;
+    r.status = status ? status + (int64_t)j * ne : nullptr;
+    r.bc_left = bc[2 * (size_t)j];
+    r.bc_right = bc[2 * (size_t)j + 1];
+    float ms = 0.0f;
+    rc = timed_launch(
+        [&](const lssvr::LaunchOpts* o) {
+          return c_values ? react_dispatch(r, s, o) : enhance_dispatch(r, LSSVR_SOLVER_PRIMAL, s, o);
+        },
+        kernel_ms_host ? &ms : nullptr);
+    if (rc != LSSVR_OK) return rc;
+    if (kernel_ms_host) *kernel_ms_host += ms;
+  }
+  return LSSVR_OK;
+}
+
 // (no variable-coefficient kernel takes a workspace: always 0, kept for ABI 6)
 int64_t lssvr_enhance_varcoef_work_bytes(int64_t ne, int M, int n_colloc) {
   (void)ne; (void)M; (void)n_colloc;

@@ -57,6 +57,15 @@ struct EnhanceReactArgs : EnhanceArgs {
   const double* c_values;
 };
 
+// several load cases on one mesh (lssvr_enhance_multi, enhance_multi.hip): u, rhs_values, W and status are
+// case-major ([case][ne+1], [case][ne*n], [case][ne*M], [case][ne]) and point at the first case of the pass;
+// bc_values[case][2] = {left, right} lives on the DEVICE (NULL: zeros) and replaces bc_left / bc_right; c_values
+// may be NULL (variable-coefficient rows)
+struct EnhanceMultiArgs : EnhanceReactArgs {
+  const double* bc_values;
+  int nc;                   // cases of this pass (set by enhance_multi)
+};
+
 // Optional per-launch profiling: a kernel with an event attached (start, stop, or both; either may be
 // NULL) goes through hipExtLaunchKernelGGL, which stamps them with the dispatch's own begin/end times.
 struct LaunchOpts {
@@ -112,6 +121,9 @@ hipError_t enhance_large(const EnhanceArgs& a, hipStream_t s, const LaunchOpts* 
 constexpr int kReactSmallMaxM = 16;
 hipError_t enhance_small_react(const EnhanceReactArgs& a, hipStream_t s, const LaunchOpts* o = nullptr);
 hipError_t enhance_large_react(const EnhanceReactArgs& a, hipStream_t s, const LaunchOpts* o = nullptr);
+// ncases load cases, M <= kReactSmallMaxM: one factorisation per element and pass, enhance_multi_rc(M) cases a pass
+int enhance_multi_rc(int M);
+hipError_t enhance_multi(const EnhanceMultiArgs& a, int ncases, hipStream_t s, const LaunchOpts* o = nullptr);
 // Poisson rows, any M <= 33: Chebyshev-moment Gram (enhance_large_cheb.hip, enhance_large_parity.hip): a
 // sequence of kernels with a workspace of enhance_moment_ws_bytes(ne, M, n) bytes in between
 int enhance_refine_steps(int M, int n);

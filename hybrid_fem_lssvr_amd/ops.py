@@ -494,6 +494,76 @@ def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *
     return out, status
 
 
+def enhance_multi(x, U, M, gamma, n_colloc, a_values, da_values, rhs_values, *, c_values=None, bc=None,
+                  point_major=False, elem_offset=0, ne_global=None, global_domain, out=None, status=None,
+                  fail_count=None, stream=None, timed=False):
+    """``ncases`` load cases on one mesh in one call (``lssvr_enhance_multi``): the element systems of
+    ``-(a u')' + c u = f`` are formed and factored once per element, every case brings its own nodal values
+    ``U[ncases, ne+1]``, right-hand side ``rhs_values[ncases, ne, n_colloc]`` (``point_major``:
+    ``[ncases, n_colloc, ne]``, like the coefficient tables ``[n_colloc, ne]``) and Dirichlet pair
+    ``bc[ncases, 2]`` (a float64 device tensor, or an array-like that is copied to the device; ``None``: zeros).
+    ``c_values=None``: the variable-coefficient rows.  ``global_domain`` is required (no read-back of the shard's
+    ends).  Returns (W float64[ncases, ne, M], status int32[ncases, ne]); ``fail_count`` counts (case, element)
+    fallbacks; ``status=False`` passes NULL (no status written, None returned).  ``timed``: BLOCKING, returns the
+    duration of all passes in seconds instead.  Primal solve only (``n_colloc >= M - 2``); M <= 16 is the
+    one-factorisation lane kernel, above it the single-case kernel runs once per case."""
+    lib = _capi.load()
+    M, n_colloc = int(M), int(n_colloc)
+    named = dict(x=x, U=U, a_values=a_values, da_values=da_values, rhs_values=rhs_values)
+    if c_values is not None:
+        named["c_values"] = c_values
+    for nm, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{nm}: expected a torch.Tensor device buffer, got {type(t).__name__}")
+    # shapes first (metadata only), then dtype / device / contiguity of every buffer
+    if x.dim() != 1 or x.numel() < 1 or U.dim() != 2 or U.shape[1] != x.numel() or U.shape[0] < 1:
+        raise ValueError(f"U must be [ncases, ne+1] = [>= 1, {x.numel()}] for x of {x.numel()} nodes, "
+                         f"got {list(U.shape)}")
+    ncases, ne = int(U.shape[0]), x.numel() - 1
+    tab = (n_colloc, ne) if point_major else (ne, n_colloc)
+    for nm in list(named)[2:]:
+        want = (ncases,) + tab if nm == "rhs_values" else tab
+        if tuple(named[nm].shape) != want:
+            raise ValueError(f"{nm} must be {list(want)} ({'point' if point_major else 'element'}-major), "
+                             f"got {list(named[nm].shape)}")
+    for nm, t in named.items():
+        _dev(t, nm)
+    ne_global = elem_offset + ne if ne_global is None else ne_global
+    if bc is not None:
+        if not isinstance(bc, torch.Tensor):
+            bc = torch.as_tensor(np.ascontiguousarray(np.asarray(bc, dtype=np.float64)), device=x.device)
+        _dev(bc, "bc")
+        if tuple(bc.shape) != (ncases, 2):
+            raise ValueError(f"bc must be [ncases, 2] = [{ncases}, 2], got {list(bc.shape)}")
+    for nm, t in (("U", U), ("a_values", a_values), ("da_values", da_values), ("rhs_values", rhs_values),
+                  ("c_values", c_values), ("bc", bc), ("out", out), ("status", status), ("fail_count", fail_count)):
+        if isinstance(t, torch.Tensor) and t.device != x.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, x on {x.device}")
+    if out is None:
+        out = torch.empty((ncases, ne, M), dtype=torch.float64, device=x.device)
+    else:
+        _dev(out, "out")
+        if out.numel() != ncases * ne * M:
+            raise ValueError(f"out must hold ncases*ne*M = {ncases * ne * M} doubles, got {out.numel()}")
+    if status is None:
+        status = torch.empty((ncases, ne), dtype=torch.int32, device=x.device)
+    elif status is not False:
+        _dev(status, "status", torch.int32)
+        if status.numel() != ncases * ne:
+            raise ValueError(f"status must hold ncases*ne = {ncases * ne} int32, got {status.numel()}")
+    else:
+        status = None                        # status=False: the entry's NULL (no status is written)
+    _check_fail_count(fail_count)
+    args = (_ptr(x), _ptr(U), ne, int(elem_offset), int(ne_global), float(global_domain[0]),
+            float(global_domain[1]), _ptr(bc), ncases, M, n_colloc, float(gamma), _ptr(a_values), _ptr(da_values),
+            _ptr(c_values), _ptr(rhs_values), _layout(point_major), _ptr(out), _ptr(status), _ptr(fail_count),
+            _stream(stream))
+    if timed:
+        return _timed(lib, "lssvr_enhance_multi", args)
+    _capi.check(lib.lssvr_enhance_multi(*args, None), "lssvr_enhance_multi")
+    return out, status
+
+
 class StepGraph:
     """``steps`` launches of a bound plan (:class:`StepPlan`, :class:`StepPlanVarcoef`) captured ONCE in a
     hipGraph and replayed: a loop of steps on fixed buffers without the host in it.  On the MI355X a replayed

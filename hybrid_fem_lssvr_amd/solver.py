@@ -381,14 +381,11 @@ class FEMLSSVRPrimalSolver:
         return gd, (main_boundary_condition_left(self.global_domain[0]),
                     main_boundary_condition_right(self.global_domain[1]))
 
-    # ---- Dual.py:110-137 --------------------------------------------------------------
-    def solve_fem(self):
-        """P1 finite-element solve: mesh, element-local assembly, Dirichlet on all
-        boundary dofs, tridiagonal solve, nodal values.  Returns ``(u_fem, basis)``
-        like the reference (``basis`` is scikit-fem shaped, see ``mesh.py``)."""
+    def _fem(self, rhs, u0, u1):
+        """(mesh, x device, u device, bands) of the P1 solve for the right-hand side ``rhs`` and the Dirichlet
+        values ``u0``, ``u1``; no attribute of the solver is written."""
         dev = _device(self.device)
         m = self._default_mesh() if self.mesh is None else self.mesh
-        basis = P1Basis(m)
         x = _to_dev(m.nodes, dev)
         eq, kw = self._eq, {}
         if eq.a is not None:             # kloc = abar / h, abar the quadrature mean of a
@@ -399,13 +396,12 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
                                  "pivot and assumes an SPD matrix (c >= 0)")
             kw["c_quad"] = cq
-        if isinstance(self.rhs, SinRHS):
-            bands = ops.p1_assemble(x, self.nquad, rhs=(self.rhs.amp, self.rhs.omega), want_local=True, **kw)
+        if isinstance(rhs, SinRHS):
+            bands = ops.p1_assemble(x, self.nquad, rhs=(rhs.amp, rhs.omega), want_local=True, **kw)
         else:
             xq = ops.quad_points(x, self.nquad)
-            fq = _to_dev(self.rhs(xq.cpu().numpy()), dev)
+            fq = _to_dev(rhs(xq.cpu().numpy()), dev)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
-        _, (u0, u1) = self._gd_bc()
         if self.fem_solver == "flux":
             # exact-structure solution of A = D^T K D by the element-flux prefix scan
             u = ops.p1_flux_solve(bands["kloc"], bands["load"], u0, u1)
@@ -416,6 +412,15 @@ class FEMLSSVRPrimalSolver:
             # here (the reference negates both forms, Dual.py:117-124: -K u = -b; this code
             # assembles +K u = +b, the same u)
             u = ops.tridiag_dirichlet_solve(bands["diag"], bands["off"], bands["load"], u0, u1)
+        return m, x, u, bands
+
+    # ---- Dual.py:110-137 --------------------------------------------------------------
+    def solve_fem(self):
+        """P1 finite-element solve: mesh, element-local assembly, Dirichlet on all
+        boundary dofs, tridiagonal solve, nodal values.  Returns ``(u_fem, basis)``
+        like the reference (``basis`` is scikit-fem shaped, see ``mesh.py``)."""
+        m, x, u, bands = self._fem(self.rhs, *self._gd_bc()[1])
+        basis = P1Basis(m)
         self.bands = bands
         self._x_dev, self._u_dev = x, u
         u_fem = u.cpu().numpy()
@@ -462,6 +467,38 @@ class FEMLSSVRPrimalSolver:
         """Complete solution: FEM + LSSVR."""
         self.solve_fem()
         self.solve_lssvr_subproblems()
+
+    def solve_many(self, rhs_list, bc=None):
+        """Several load cases on this solver's mesh and operator: for every right-hand side of ``rhs_list`` the P1
+        assembly and Dirichlet solve (``coef``, ``reaction``, ``nquad`` and ``fem_solver`` as configured), then ONE
+        ``ops.enhance_multi`` over all cases -- the element systems are formed and factored once, not once per case.
+        ``bc``: ``None`` (the module's boundary functions, as ``solve()`` uses) or one ``(left, right)`` pair per
+        case.  Returns a list of :class:`EnhancedSolution`, one per case; ``rhs``, ``fem_values``, ``enhanced`` and
+        the other attributes of the solver are left as they are.  Without ``coef`` the tables hold a = 1, a' = 0."""
+        torch = _torch()
+        rhs_list = list(rhs_list)
+        if not rhs_list or not all(callable(f) for f in rhs_list):
+            raise ValueError("rhs_list must be a non-empty sequence of callables")
+        if self.solver_id != ops.SOLVER_PRIMAL:
+            raise ValueError("solve_many needs solver=ops.SOLVER_PRIMAL")
+        gd, bc0 = self._gd_bc()
+        if bc is None:
+            bc = [bc0] * len(rhs_list)
+        bc = np.asarray(bc, dtype=np.float64)
+        if bc.shape != (len(rhs_list), 2):
+            raise ValueError(f"bc must hold one (left, right) pair per case: {(len(rhs_list), 2)}, got {bc.shape}")
+        M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
+        pm = int(M) <= 16                    # the lane kernel of lssvr_enhance_multi reads point-major tables
+        x, us = None, []
+        for f, (u0, u1) in zip(rhs_list, bc):
+            _, x, u, _ = self._fem(f, float(u0), float(u1))
+            us.append(u)
+        pts = ops.colloc_points(x, n)
+        ta, tda, _, tc = _Equation(_zero, self.coef, self.reaction).tables(pts, pm)
+        tf = torch.stack([_tabulate(f, pts, pm) for f in rhs_list])
+        W, st = ops.enhance_multi(x, torch.stack(us), M, gamma, n, ta, tda, tf, c_values=tc,
+                                  bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd)
+        return [EnhancedSolution(x, W[j], st[j]) for j in range(len(rhs_list))]
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):

@@ -546,6 +546,42 @@ int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, in
                          const double* rhs_values, int table_layout, const double* a_ends,
                          double* eta2, double* jump, double* out3, void* work, void* stream);
 
+/*
+ * Several load cases on one mesh: factor once, many right-hand sides.  ADDITIVE to ABI 7 like the reaction entries
+ * (a new symbol; LSSVR_ABI_VERSION stays 7).
+ *
+ * lssvr_enhance_multi -- lssvr_enhance_react_ws (c_values given) or lssvr_enhance_varcoef_ws (c_values == NULL) for
+ * ncases right-hand sides, nodal vectors and Dirichlet pairs at once.  The element system S = G + eps (I + C^T C)
+ * depends on the mesh, the a / a' / c tables, gamma, M and n_colloc only, so for M <= 16 one lane kernel forms and
+ * factors it ONCE per element and pass and runs the two triangular solves per case; a pass holds up to RC(M) cases
+ * in registers (8 at M = 2, 4 at M = 3..6 and 9..13, 3 at 7, 2 at 8 and 14, 1 at 15 and 16)
+ * and ceil(ncases / RC) passes are launched, each of which reads the coefficient tables once.  17 <= M <= 33 runs
+ * the single-case entry's kernel once per case: correct, no faster than separate calls, and a shard that holds an
+ * end of the global domain reads bc_values back to the host first (one stream synchronisation).
+ * All pointers are DEVICE pointers, case-major and contiguous:
+ *   u[ncases][ne+1]            nodal values of every case
+ *   bc_values[ncases][2]       {left, right} Dirichlet value of every case; NULL: all zero.  The boundary rule is
+ *                              that of lssvr_enhance with the case's own pair
+ *   a_values, da_values        required, shared by the cases; c_values may be NULL (no reaction term)
+ *   rhs_values[ncases][ne*n_colloc]   every slab in table_layout (LSSVR_TABLE_*), like the coefficient tables
+ *   W[ncases][ne][M]           out
+ *   status[ncases][ne]         out, may be NULL
+ *   fail_count                 one counter, may be NULL: +1 per (case, element) fallback
+ * Fallback (Dual.py:164-169) per case: a breakdown of the factorisation gives EVERY case of that element the linear
+ * interpolant of its own (g_l, g_r) and status 1; a case whose own right-hand side or solution is not finite falls
+ * back alone.  Primal solve only: n_colloc < M-2 is LSSVR_ERR_SOLVER; ncases < 1 is LSSVR_ERR_SIZE; ne == 0 is a
+ * successful no-op.  kernel_ms_host != NULL: BLOCKING, the duration from the first pass's begin to the last one's
+ * end (above M = 16: the sum over the cases).
+ */
+int lssvr_enhance_multi(const double* x, const double* u, int64_t ne,
+                        int64_t elem_offset, int64_t ne_global,
+                        double gxmin, double gxmax, const double* bc_values, int ncases,
+                        int M, int n_colloc, double gamma,
+                        const double* a_values, const double* da_values, const double* c_values,
+                        const double* rhs_values, int table_layout,
+                        double* W, int32_t* status, int32_t* fail_count,
+                        void* stream, float* kernel_ms_host);
+
 #ifdef __cplusplus
 }
 #endif
