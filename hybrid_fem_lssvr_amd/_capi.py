@@ -114,6 +114,12 @@ SIGNATURES = {
     # several load cases on one mesh (additive to ABI 7): ..., gxmin, gxmax, bc_values, ncases, M, n_colloc, gamma
     "lssvr_enhance_multi": _sig(_SHARD[:7], [_c_dp, _c_int], _SHARD[9:], _REACT_TABLES, [_c_int], _OUT, _STREAM,
                                 _TIMED),
+    # hp-adaptive refinement (additive to ABI 7)
+    "lssvr_smoothness": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_dp], _STREAM),
+    "lssvr_refine_hp": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dbl, _c_int, _c_int, _c_dp,
+                             _c_dp, _c_dp, _c_dp, _c_dp, _c_dp], _STREAM),
+    "lssvr_group_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_group_by_degree": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dp], _STREAM),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

@@ -12,6 +12,7 @@
 #include "lssvr_device.hpp"
 #include "lssvr_kernels.hpp"
 #include "lssvr_eval.hpp"
+#include "lssvr_adapt.hpp"
 
 namespace lssvr {
 
@@ -107,18 +108,7 @@ __global__ __launch_bounds__(kBlock) void eval_deriv_kernel(const double* __rest
 // ---------------------------------------------------------------------------
 // estimator
 // ---------------------------------------------------------------------------
-constexpr int kEstBlock = 128;          // elements per workgroup chunk (two waves)
-constexpr int kEstMaxBlocks = 4096;     // grid cap: partials of the reduction in `work`
-
-int64_t est_blocks(int64_t ne) {
-  const int64_t b = (ne + kEstBlock - 1) / kEstBlock;
-  return b < 1 ? 1 : (b < kEstMaxBlocks ? b : kEstMaxBlocks);
-}
-int64_t ref_blocks(int64_t ne) {
-  const int64_t b = (ne + kBlock - 1) / kBlock;
-  return b < 1 ? 1 : b;
-}
-
+// (chunk geometry kEstBlock / est_blocks / ref_blocks and stage_rows: lssvr_adapt.hpp)
 __device__ __forceinline__ double est_point(double a, double b, double xi) {
   const double mid = 0.5 * (a + b);
   const double half = 0.5 * (b - a);
@@ -174,23 +164,6 @@ __device__ __forceinline__ void fill_table(double* __restrict__ Tq, double t, in
     p0 = p1; p1 = p2;
     d0 = d1; d1 = d2;
     s0 = s1; s1 = s2;
-  }
-}
-
-// the chunk's contiguous `total` = nrow*M doubles of W from `src` (coalesced) into LDS rows of odd stride ms;
-// column stepping: i += kEstBlock  ->  (row, col) += (kEstBlock / M, kEstBlock % M)
-__device__ __forceinline__ void stage_rows(double* __restrict__ rows, const double* __restrict__ src, int total,
-                                           int M, int ms, int tid) {
-  const int qM = kEstBlock / M, rM = kEstBlock - (kEstBlock / M) * M;
-  int r = tid / M, col = tid - (tid / M) * M;
-  for (int i = tid; i < total; i += kEstBlock) {
-    rows[r * ms + col] = src[i];
-    r += qM;
-    col += rM;
-    if (col >= M) {
-      col -= M;
-      ++r;
-    }
   }
 }
 
@@ -469,9 +442,7 @@ __global__ __launch_bounds__(kBlock) void estimate_points_kernel(const double* _
 // at least 2 h_min long; mx = the device max of the finite eta2 (out3[1] of lssvr_estimate)
 __device__ __forceinline__ bool marked(const double* __restrict__ x, const double* __restrict__ eta2,
                                        int64_t e, double mx, double theta2, double h2min) {
-  const double v = eta2[e];
-  const bool big = !(fabs(v) < INFINITY) || (mx > 0.0 && v >= theta2 * mx);
-  return big && (x[e + 1] - x[e] >= h2min);
+  return indicator_marked(eta2[e], mx, theta2) && (x[e + 1] - x[e] >= h2min);
 }
 
 __global__ __launch_bounds__(kBlock) void refine_count_kernel(const double* __restrict__ x, int64_t ne,

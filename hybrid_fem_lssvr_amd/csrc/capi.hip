@@ -940,6 +940,46 @@ int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* 
                       "refine");
 }
 
+int lssvr_smoothness(const double* W, int64_t ldw, const int32_t* deg, int64_t ne, double* sigma, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (ldw < 2 || ldw > lssvr::kAdaptMaxM)
+    return fail(LSSVR_ERR_DEGREE, "ldw = %lld outside [2, %d]", (long long)ldw, lssvr::kAdaptMaxM);
+  if (!W || !deg || !sigma) return fail(LSSVR_ERR_NULL, "W, deg and sigma must be non-NULL");
+  return check_launch(lssvr::smoothness(W, (int)ldw, deg, ne, sigma, reinterpret_cast<hipStream_t>(stream)),
+                      "smoothness");
+}
+
+int lssvr_refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev, double theta,
+                    double h_min, const double* sigma, const int32_t* deg, double sigma_min, int dM, int M_max,
+                    void* work, double* x_new, int32_t* deg_new, int64_t* parent, int64_t* ne_new_dev,
+                    int64_t* counts2_dev, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (!(theta >= 0.0 && theta <= 1.0)) return fail(LSSVR_ERR_SIZE, "theta = %g outside [0, 1]", theta);
+  if (!(h_min >= 0.0) || !(h_min < INFINITY)) return fail(LSSVR_ERR_SIZE, "h_min = %g must be finite and >= 0", h_min);
+  if (dM < 1) return fail(LSSVR_ERR_DEGREE, "dM = %d < 1", dM);
+  if (M_max < 2 || M_max > lssvr::kAdaptMaxM)
+    return fail(LSSVR_ERR_DEGREE, "M_max = %d outside [2, %d]", M_max, lssvr::kAdaptMaxM);
+  if (!x || !eta2 || !eta2_max_dev || !sigma || !deg || !work || !x_new || !deg_new || !ne_new_dev || !counts2_dev)
+    return fail(LSSVR_ERR_NULL, "x, eta2, eta2_max, sigma, deg, work, x_new, deg_new, ne_new, counts2 must be "
+                "non-NULL");
+  return check_launch(lssvr::refine_hp(x, ne, eta2, eta2_max_dev, theta, h_min, sigma, deg, sigma_min, dM, M_max,
+                                       work, x_new, deg_new, parent, ne_new_dev, counts2_dev,
+                                       reinterpret_cast<hipStream_t>(stream)),
+                      "refine_hp");
+}
+
+int64_t lssvr_group_work_bytes(int64_t ne) { return lssvr::group_work_bytes(ne); }
+
+int lssvr_group_by_degree(const int32_t* deg, int64_t ne, int64_t* ids, int64_t* offsets, void* work, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (!deg || !ids || !offsets || !work) return fail(LSSVR_ERR_NULL, "deg, ids, offsets and work must be non-NULL");
+  return check_launch(lssvr::group_by_degree(deg, ne, ids, offsets, work, reinterpret_cast<hipStream_t>(stream)),
+                      "group_by_degree");
+}
+
 int lssvr_stream_probe(const double* src, double* dst, int64_t n, void* stream) {
   if (!src || !dst) return fail(LSSVR_ERR_NULL, "src and dst must be non-NULL");
   if (n < 1) return fail(LSSVR_ERR_SIZE, "n must be >= 1");

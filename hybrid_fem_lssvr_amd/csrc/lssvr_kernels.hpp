@@ -235,6 +235,16 @@ hipError_t estimate_react(EstimateReactArgs a, bool point_major, double* out3, h
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                   double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s);
 
+// hp-adaptive refinement (adapt_hp.hip)
+hipError_t smoothness(const double* W, int ldw, const int32_t* deg, int64_t ne, double* sigma, hipStream_t s);
+hipError_t refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
+                     double h_min, const double* sigma, const int32_t* deg, double sigma_min, int dM, int M_max,
+                     void* work, double* x_new, int32_t* deg_new, int64_t* parent, int64_t* ne_new, int64_t* counts2,
+                     hipStream_t s);
+int64_t group_work_bytes(int64_t ne);
+hipError_t group_by_degree(const int32_t* deg, int64_t ne, int64_t* ids, int64_t* offsets, void* work,
+                           hipStream_t s);
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

@@ -915,6 +915,105 @@ def refine(x, eta2, eta2_max, theta, *, h_min=0.0, want_parent=False, work=None,
     return x_new[:n + 1], (parent[:n] if parent is not None else None)
 
 
+MIN_DEGREE, MAX_DEGREE = 2, 33       # the degree parameter M of an element (lssvr_enhance: 2 <= M <= 33)
+
+
+def _degrees(deg, ne, name="deg"):
+    """``deg`` as the kernels take it: a contiguous device int32[ne]."""
+    _dev(deg, name, torch.int32)
+    if deg.dim() != 1 or deg.numel() != ne:
+        raise ValueError(f"{name} must be int32[ne] = [{ne}], got {list(deg.shape)}")
+    return deg
+
+
+def smoothness(x, W, deg, *, out=None, stream=None):
+    """Decay rate of every element's Legendre coefficients (``lssvr_smoothness``): minus the least-squares slope
+    of ln(envelope of |W[e, p]|) against p = 1 .. deg[e]-1.  ``W`` float64[ne, ldw] (zero-padded rows, 2 <= ldw
+    <= 33), ``deg`` int32[ne] with 2 <= deg[e] <= ldw (not checked here: a degree outside that range gives NaN).
+    ``x`` float64[ne+1] only fixes ne -- the window of every element is [-1, 1], so the rate does not depend on
+    its length.  Returns sigma float64[ne]: +inf for a zero row or fewer than two usable points, NaN for a
+    non-finite row."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(W, "W")
+    ne = x.numel() - 1
+    if ne < 1:
+        raise ValueError("need at least one element")
+    if W.dim() != 2 or W.shape[0] != ne:
+        raise ValueError("W must be [ne, ldw]")
+    ldw = int(W.shape[1])
+    if not MIN_DEGREE <= ldw <= MAX_DEGREE:
+        raise ValueError(f"W must have 2 <= ldw <= 33 columns, got {ldw}")
+    _degrees(deg, ne)
+    if out is None:
+        out = torch.empty(ne, dtype=torch.float64, device=x.device)
+    else:
+        _dev(out, "out")
+        if out.numel() != ne:
+            raise ValueError(f"out must hold ne = {ne} doubles, got {out.numel()}")
+    _capi.check(lib.lssvr_smoothness(_ptr(W), ldw, _ptr(deg), ne, _ptr(out), _stream(stream)), "lssvr_smoothness")
+    return out
+
+
+def refine_hp(x, eta2, eta2_max, theta, sigma, deg, *, sigma_min=1.0, dM=2, M_max=MAX_DEGREE, h_min=0.0,
+              want_parent=False, work=None, stream=None):
+    """:func:`refine`'s marking, then p or h (``lssvr_refine_hp``): a marked element (eta2 non-finite, or eta2 >=
+    theta^2 * max with max > 0) gets ``deg + dM`` when ``sigma >= sigma_min`` and ``deg + dM <= M_max``, else is
+    bisected when it is at least 2 ``h_min`` long (both halves keep ``deg``), else stays.  ``sigma`` float64[ne]
+    from :func:`smoothness`, ``deg`` int32[ne].  Returns (x_new float64[ne_new+1], deg_new int32[ne_new], parent
+    int64[ne_new] | None, (bisected, raised)), trimmed to the new length -- one synchronisation, for the counts."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(eta2, "eta2")
+    _dev(eta2_max, "eta2_max")
+    _dev(sigma, "sigma")
+    ne = x.numel() - 1
+    if ne < 1:
+        raise ValueError("need at least one element")
+    if eta2.numel() != ne or sigma.numel() != ne:
+        raise ValueError("eta2 and sigma must hold ne doubles")
+    if eta2_max.numel() < 1:
+        raise ValueError("eta2_max must hold one double")
+    _degrees(deg, ne)
+    theta = float(theta)
+    if not 0.0 <= theta <= 1.0:
+        raise ValueError(f"theta must be in [0, 1], got {theta}")
+    if int(dM) != dM or dM < 1:
+        raise ValueError(f"dM must be a positive integer, got {dM!r}")
+    if int(M_max) != M_max or not MIN_DEGREE <= M_max <= MAX_DEGREE:
+        raise ValueError(f"M_max must be in [2, 33], got {M_max!r}")
+    x_new = torch.empty(2 * ne + 1, dtype=torch.float64, device=x.device)
+    deg_new = torch.empty(2 * ne, dtype=torch.int32, device=x.device)
+    parent = torch.empty(2 * ne, dtype=torch.int64, device=x.device) if want_parent else None
+    cnt = torch.empty(3, dtype=torch.int64, device=x.device)         # {ne_new, bisected, raised}
+    work = _check_work(work, x, ne)
+    rc = lib.lssvr_refine_hp(_ptr(x), ne, _ptr(eta2), _ptr(eta2_max), theta, float(h_min), _ptr(sigma), _ptr(deg),
+                             float(sigma_min), int(dM), int(M_max), _ptr(work), _ptr(x_new), _ptr(deg_new),
+                             _ptr(parent), _ptr(cnt[0:1]), _ptr(cnt[1:3]), _stream(stream))
+    _capi.check(rc, "lssvr_refine_hp")
+    n, split, raised = (int(v) for v in cnt.cpu())
+    return x_new[:n + 1], deg_new[:n], (parent[:n] if parent is not None else None), (split, raised)
+
+
+def group_by_degree(deg, *, work=None, stream=None):
+    """Stable counting sort of the element indices by degree (``lssvr_group_by_degree``).  ``deg`` int32[ne].
+    Returns (ids int64[ne], offsets int64[35]), both on the device: the elements of degree M are
+    ``ids[offsets[M]:offsets[M+1]]`` in ascending mesh order -- a slice that :func:`enhance_subset` takes as
+    ``elem_ids``; ``offsets[34]`` counts the elements sorted.  An element whose degree is outside 2 .. 33 is in no
+    group (then ``offsets[34] < ne`` and the tail of ``ids`` is unwritten)."""
+    lib = _capi.load()
+    _dev(deg, "deg", torch.int32)
+    ne = deg.numel()
+    if deg.dim() != 1 or ne < 1:
+        raise ValueError("deg must be int32[ne] with ne >= 1")
+    ids = torch.empty(ne, dtype=torch.int64, device=deg.device)
+    offsets = torch.empty(MAX_DEGREE + 2, dtype=torch.int64, device=deg.device)
+    work = _scratch(None if work is None else _dev(work, "work"), lib.lssvr_group_work_bytes(ne), deg.device)
+    rc = lib.lssvr_group_by_degree(_ptr(deg), ne, _ptr(ids), _ptr(offsets), _ptr(work), _stream(stream))
+    _capi.check(rc, "lssvr_group_by_degree")
+    return ids, offsets
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

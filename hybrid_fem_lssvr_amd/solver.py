@@ -28,6 +28,8 @@ estimate and refine ``-(a u')' + c u = f``; without ``coef
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 from numpy.polynomial.legendre import Legendre
 
@@ -364,6 +366,7 @@ class FEMLSSVRPrimalSolver:
         self.reaction = reaction
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
+        self.element_degrees = None     # one M per element (2 .. 33) instead of lssvr_M; solve_adaptive(mode="hp")
         self._x_dev = None
         self._u_dev = None
 
@@ -428,6 +431,50 @@ class FEMLSSVRPrimalSolver:
         self.fem_values = u_fem.copy()
         return u_fem, basis
 
+    # ---- one degree per element (no reference counterpart: Dual.py:101 has one lssvr_M) ----
+    def _check_hp(self, what):
+        if self.coef is not None or self.reaction is not None:
+            raise ValueError(f"{what} needs the Poisson rows (no coef, no reaction): lssvr_enhance_subset holds "
+                             "those only")
+        if self.solver_id != ops.SOLVER_PRIMAL:
+            raise ValueError(f"{what} needs solver=ops.SOLVER_PRIMAL")
+
+    def _check_degrees(self, ne):
+        """``element_degrees`` as an int64 host array: one degree in 2 .. 33 per element."""
+        self._check_hp("element_degrees")
+        deg = np.asarray(self.element_degrees)
+        if deg.shape != (ne,) or not np.issubdtype(deg.dtype, np.integer):
+            raise ValueError(f"element_degrees must hold one integer per element ({ne}), got shape {deg.shape} "
+                             f"of {deg.dtype}")
+        if deg.min() < ops.MIN_DEGREE or deg.max() > ops.MAX_DEGREE:
+            raise ValueError(f"element_degrees must lie in [2, 33], got [{deg.min()}, {deg.max()}]")
+        return deg.astype(np.int64)
+
+    def group_colloc(self, M):
+        """Collocation points of the elements of degree ``M`` when ``element_degrees`` is set:
+        max(n_colloc, 2 M) -- n >= 2 (M - 2) keeps a raised element in the parity-solve regime and away from
+        the near-square one."""
+        return max(int(self.n_colloc), 2 * int(M))
+
+    def _enhance_by_degree(self, x, u, degrees, gamma, gd, bc):
+        """Group the elements by degree on the device, read the 35 offsets back once, one ``enhance_subset`` per
+        non-empty degree into a zeroed W[ne, max M]."""
+        torch = _torch()
+        ne = degrees.size
+        ids, offsets = ops.group_by_degree(torch.as_tensor(degrees.astype(np.int32), device=x.device))
+        off = offsets.cpu().numpy()
+        W = torch.zeros((ne, int(degrees.max())), dtype=torch.float64, device=x.device)
+        st = torch.zeros((ne,), dtype=torch.int32, device=x.device)
+        for Mg in range(ops.MIN_DEGREE, ops.MAX_DEGREE + 1):
+            sub = ids[off[Mg]:off[Mg + 1]]
+            if sub.numel() == 0:
+                continue
+            ng = self.group_colloc(Mg)
+            # (a callable f is tabulated at this group's collocation points, np.linspace per element)
+            kw = _rhs_mode(self.rhs, lambda: ops.colloc_points(x, ng)[sub])
+            ops.enhance_subset(x, u, Mg, gamma, ng, W, elem_ids=sub, global_domain=gd, bc=bc, status=st, **kw)
+        return W, st
+
     # ---- Dual.py:139-169 --------------------------------------------------------------
     def solve_lssvr_subproblems(self):
         """Solve LSSVR with the primal method in each element (one kernel launch)."""
@@ -444,7 +491,11 @@ class FEMLSSVRPrimalSolver:
         M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
         pm = _point_major(M)
         eq = self._eq
-        if eq.poisson:
+        degrees = None
+        if self.element_degrees is not None:
+            degrees = self._check_degrees(nodes.size - 1)
+            W, st = self._enhance_by_degree(x, u, degrees, gamma, gd, bc)
+        elif eq.poisson:
             kw = _rhs_mode(eq.f, lambda: ops.colloc_points(x, n), pm)
             W, st = _enhance(x, u, M, gamma, n, global_domain=gd, bc=bc, solver=self.solver_id, **kw)
         else:
@@ -453,6 +504,8 @@ class FEMLSSVRPrimalSolver:
             W, st = ops.enhance_varcoef(x, u, M, gamma, n, ta, tda, tf, global_domain=gd, bc=bc, point_major=pm,
                                         c_values=tc)
         self.enhanced = EnhancedSolution(x, W, st)
+        if degrees is not None:
+            self.enhanced.degrees = degrees
         nbad = self.enhanced.n_fallback
         if nbad:
             bad = np.nonzero(st.cpu().numpy())[0]
@@ -548,7 +601,8 @@ class FEMLSSVRPrimalSolver:
         eta2, _ = self._estimate_dev(nq)
         return eta2.cpu().numpy()
 
-    def solve_adaptive(self, tol=None, theta=0.5, max_elements=100000, max_iter=50, h_min=0.0, nq=None):
+    def solve_adaptive(self, tol=None, theta=0.5, max_elements=100000, max_iter=50, h_min=0.0, nq=None, *,
+                       mode="h", M_max=None, dM=2, sigma_min=1.0, max_dof=None):
         """Solve, estimate, mark, bisect -- repeated.  Each round runs ``solve()`` on the current mesh
         and the indicator of :meth:`estimate` (for ``-(a u')' = f`` when ``coef`` is set); it stops when
         sqrt(sum eta^2) <= ``tol``, after ``max_iter`` rounds, when nothing is marked, or when the refinement
@@ -558,7 +612,18 @@ class FEMLSSVRPrimalSolver:
         becomes the new nodes.  Afterwards ``fem_nodes``, ``fem_values``, ``lssvr_functions`` and
         ``enhanced`` describe the final mesh as after ``solve()``; ``adapt_history`` holds one
         dict(ne, estimate, marked) per round (marked = elements bisected after that round).
-        Returns the final sqrt(sum eta^2)."""
+        Returns the final sqrt(sum eta^2).
+
+        ``mode="hp"`` (Poisson rows, ``solver=ops.SOLVER_PRIMAL``): every element starts at ``lssvr_M``; a marked
+        element whose Legendre coefficients decay at a rate ``ops.smoothness`` >= ``sigma_min`` gets ``dM`` more
+        coefficients while that stays <= ``M_max`` (default min(33, lssvr_M + 12)), any other marked element is
+        bisected and both halves keep its degree (``ops.refine_hp``).  ``element_degrees`` carries the degrees
+        from round to round and describes the final mesh; the indicator takes ``nq`` = min(32, max(max M_e, 8))
+        Gauss points unless given; every round records dict(ne, estimate, marked, raised, dof) with marked =
+        elements bisected, raised = elements raised after that round and dof = sum of M_e.  It also stops when a
+        round neither bisects nor raises, or when the refinement would take sum M_e above ``max_dof`` (hp only)."""
+        if mode not in ("h", "hp"):
+            raise ValueError(f"mode must be 'h' or 'hp', got {mode!r}")
         theta = float(theta)
         if not 0.0 <= theta <= 1.0:
             raise ValueError(f"theta must be in [0, 1], got {theta}")
@@ -570,6 +635,11 @@ class FEMLSSVRPrimalSolver:
             raise ValueError(f"tol must be >= 0, got {tol!r}")
         if not float(h_min) >= 0.0:
             raise ValueError(f"h_min must be >= 0, got {h_min!r}")
+        if mode == "hp":
+            return self._solve_adaptive_hp(tol, theta, max_elements, int(max_iter), float(h_min), nq, M_max, dM,
+                                           sigma_min, max_dof)
+        if max_dof is not None:
+            raise ValueError("max_dof bounds sum M_e of mode='hp'; mode='h' is bounded by max_elements")
         nq = self._nq(nq)
         if self.mesh is None:
             self.mesh = self._default_mesh()
@@ -593,4 +663,56 @@ class FEMLSSVRPrimalSolver:
                 break
             rec["marked"] = ne_new - ne
             self.mesh = LineMesh.from_nodes(x_new.cpu().numpy())
+        return est
+
+    def _solve_adaptive_hp(self, tol, theta, max_elements, max_iter, h_min, nq, M_max, dM, sigma_min, max_dof):
+        """The rounds of ``solve_adaptive(mode="hp")``; the arguments it shares with mode "h" are validated."""
+        torch = _torch()
+        self._check_hp("mode='hp'")
+        M0 = int(self.lssvr_M)
+        M_max = min(ops.MAX_DEGREE, M0 + 12) if M_max is None else M_max
+        if isinstance(M_max, bool) or int(M_max) != M_max or not M0 <= M_max <= ops.MAX_DEGREE:
+            raise ValueError(f"M_max must be an integer in [lssvr_M, 33] = [{M0}, 33], got {M_max!r}")
+        if isinstance(dM, bool) or int(dM) != dM or dM < 1:
+            raise ValueError(f"dM must be a positive integer, got {dM!r}")
+        if math.isnan(float(sigma_min)):
+            raise ValueError("sigma_min must not be NaN")
+        if max_dof is not None and (isinstance(max_dof, bool) or int(max_dof) != max_dof or max_dof < 1):
+            raise ValueError(f"max_dof must be a positive integer, got {max_dof!r}")
+        if nq is not None:
+            nq = self._nq(nq)
+        if self.mesh is None:
+            self.mesh = self._default_mesh()
+        if self.mesh.nelements > max_elements:
+            raise ValueError(f"the initial mesh has {self.mesh.nelements} elements > max_elements = {max_elements}")
+        deg = np.full(self.mesh.nelements, M0, dtype=np.int64)
+        if max_dof is not None and deg.sum() > max_dof:
+            raise ValueError(f"the initial mesh has {deg.sum()} coefficients > max_dof = {max_dof}")
+        self.adapt_history = []
+        est = float("nan")
+        for it in range(max_iter):
+            self.element_degrees = deg
+            self.solve()
+            eta2, out3 = self._estimate_dev(min(32, max(int(deg.max()), 8)) if nq is None else nq)
+            s = out3.cpu().numpy()
+            ne = int(eta2.numel())
+            est = float(np.sqrt(s[0])) if s[2] == 0 else float("inf")
+            rec = dict(ne=ne, estimate=est, marked=0, raised=0, dof=int(deg.sum()))
+            self.adapt_history.append(rec)
+            if (tol is not None and est <= float(tol)) or it + 1 == max_iter:
+                break
+            x, W = self.enhanced.nodes, self.enhanced.W
+            deg_dev = torch.as_tensor(deg.astype(np.int32), device=x.device)
+            sigma = ops.smoothness(x, W, deg_dev)
+            x_new, deg_new, _, (split, raised) = ops.refine_hp(x, eta2, out3[1:2], theta, sigma, deg_dev,
+                                                               sigma_min=float(sigma_min), dM=int(dM),
+                                                               M_max=int(M_max), h_min=h_min)
+            deg_new = deg_new.cpu().numpy().astype(np.int64)
+            if split + raised == 0 or ne + split > max_elements:
+                break
+            if max_dof is not None and deg_new.sum() > max_dof:
+                break
+            rec["marked"], rec["raised"] = split, raised
+            self.mesh = LineMesh.from_nodes(x_new.cpu().numpy())
+            deg = deg_new
         return est

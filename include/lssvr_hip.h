@@ -582,6 +582,73 @@ int lssvr_enhance_multi(const double* x, const double* u, int64_t ne,
                         double* W, int32_t* status, int32_t* fail_count,
                         void* stream, float* kernel_ms_host);
 
+/*
+ * hp-adaptive refinement: raise the degree where the solution is smooth, bisect where it is not (no reference
+ * counterpart).  ADDITIVE to ABI 7 like the reaction entries (four new symbols;
+ * LSSVR_ABI_VERSION stays 7).  Together with lssvr_enhance_subset_ws (one degree per group of elements) and
+ * lssvr_estimate / lssvr_eval (zero-padded rows) they close the loop: estimate, lssvr_smoothness, lssvr_refine_hp,
+ * lssvr_group_by_degree, one lssvr_enhance_subset_ws per non-empty degree.
+ *
+ * lssvr_smoothness -- decay rate of every element's Legendre coefficients.
+ *   W[ne*ldw]       zero-padded rows, 2 <= ldw <= 33
+ *   deg[ne]         device int32: the degree parameter M of every element, 2 <= deg[e] <= ldw
+ *   sigma[ne]       out.  With M = deg[e], c_p = |W[e*ldw + p]| (p < M), mx = max_p c_p and the envelope
+ *                   env_p = max_{p <= q < M} c_q for p = 1 .. M-1 (it absorbs the parity zeros of a symmetric
+ *                   solution), sigma[e] is minus the least-squares slope of ln env_p against p over the points with
+ *                   env_p >= 2^-52 * mx (and env_p > 0):
+ *                     sigma = -sum (p - pbar)(y_p - ybar) / sum (p - pbar)^2,  y_p = ln env_p,
+ *                   pbar, ybar the means over the kept points.  NaN when one of the M coefficients is not finite
+ *                   (or deg[e] is outside [2, ldw]: nothing of the row is read); otherwise +inf when mx == 0,
+ *                   M < 3 or fewer than two points are kept.
+ * The window is [-1, 1] for every element, so sigma does not depend on the element's length.  A lane per element,
+ * W staged through LDS, at most 4096 workgroups of 128 elements per pass; no atomics, bitwise reproducible.
+ */
+int lssvr_smoothness(const double* W, int64_t ldw, const int32_t* deg, int64_t ne, double* sigma, void* stream);
+
+/*
+ * lssvr_refine_hp -- lssvr_refine's marking, then p or h.  Element e is marked iff
+ *   eta2[e] is non-finite, or max > 0 and eta2[e] >= theta^2 * max          (max = *eta2_max_dev, a DEVICE pointer)
+ * -- lssvr_refine's predicate without the length condition.  A marked element
+ *   is RAISED (deg_new = deg[e] + dM, not split)  iff  sigma[e] >= sigma_min and deg[e] + dM <= M_max
+ *                                                     (a NaN sigma or sigma_min compares false),
+ *   otherwise is BISECTED at 0.5 * (x[e] + x[e+1])  iff  x[e+1] - x[e] >= 2*h_min; both children inherit deg[e],
+ *   otherwise stays as it is.
+ * theta in [0, 1], h_min >= 0 and finite, dM >= 1, 2 <= M_max <= 33.
+ *   sigma[ne]       lssvr_smoothness of the solution the indicator belongs to
+ *   deg[ne]         device int32
+ *   x_new[2*ne+1]   out: the new nodes, ascending (capacity 2*ne+1; *ne_new_dev + 1 are written)
+ *   deg_new[2*ne]   out (device int32): degree of every new element
+ *   parent[2*ne]    out, may be NULL: old element of every new element
+ *   ne_new_dev      out (device int64): the new element count
+ *   counts2_dev     out (device int64[2]): {elements bisected, elements raised}
+ *   work            device scratch of lssvr_adapt_work_bytes(ne) bytes
+ * The three launches of lssvr_refine (block counts, a one-workgroup scan, scatter): deterministic, and x_new and
+ * parent equal lssvr_refine's bit for bit when nothing is raised.
+ */
+int lssvr_refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev,
+                    double theta, double h_min, const double* sigma, const int32_t* deg,
+                    double sigma_min, int dM, int M_max, void* work,
+                    double* x_new, int32_t* deg_new, int64_t* parent, int64_t* ne_new_dev,
+                    int64_t* counts2_dev, void* stream);
+
+/*
+ * lssvr_group_by_degree -- stable counting sort of the element indices by degree: the elem_ids of
+ * lssvr_enhance_subset(_ws) for every degree of a p-adaptive mesh, grouped on the device.
+ *   deg[ne]         device int32
+ *   ids[ne]         out (device int64): the elements of degree M are ids[offsets[M] .. offsets[M+1]) in ascending
+ *                   mesh order
+ *   offsets[35]     out (device int64): offsets[0] = offsets[1] = offsets[2] = 0 (no degree below 2),
+ *                   offsets[34] = the number of elements sorted
+ *   work            device scratch of lssvr_group_work_bytes(ne) bytes
+ * An element whose degree is outside [2, 33] is in no group: nothing is written for it, offsets[34] counts the
+ * others, the trailing ids stay unwritten and the call still succeeds -- validate the degrees first.
+ * Per-workgroup histograms of the 32 degrees, one scanning workgroup, a scatter by ballot rank: no atomics, the
+ * output is deterministic.
+ */
+int64_t lssvr_group_work_bytes(int64_t ne);
+int lssvr_group_by_degree(const int32_t* deg, int64_t ne, int64_t* ids, int64_t* offsets,
+                          void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,10 +3,12 @@ section 11): lssvr_estimate (M = 9, nq = 16, in-kernel sin rhs) and lssvr_refine
 events around `reps` back-to-back launches after a warm-up, beside lssvr_enhance on the same mesh.
 ``--varcoef`` adds lssvr_estimate_varcoef (same M and nq; a, a', f tables) in both table layouts.
 ``--reaction`` (with ``--varcoef``) adds lssvr_estimate_react (a fourth table, c) and its ratio to the varcoef entry.
+``--hp`` adds the three hp entries on the same W (ldw = M): lssvr_smoothness, lssvr_refine_hp (sigma_min = 1, dM = 2,
+M_max = 21) and lssvr_group_by_degree (degrees 5 .. 21 mixed), each against its HBM bound.
 Prints the algorithmic bytes and flops per element, the bound that applies and the fraction of it;
 ``--json PATH`` also writes the record as JSON.
 
-    python scripts/adapt_quick.py [--ne 1000000] [--reps 50] [--varcoef [--reaction]] [--json PATH]
+    python scripts/adapt_quick.py [--ne 1000000] [--reps 50] [--varcoef [--reaction]] [--hp] [--json PATH]
 """
 import argparse
 import json
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--varcoef", action="store_true", help="also time lssvr_estimate_varcoef, both layouts")
     ap.add_argument("--reaction", action="store_true", help="with --varcoef: also time lssvr_estimate_react")
+    ap.add_argument("--hp", action="store_true", help="also time lssvr_smoothness, lssvr_refine_hp, lssvr_group_by_degree")
     ap.add_argument("--json", default=None, help="write the record to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -129,6 +132,45 @@ def main():
                 rec[key]["over_varcoef"] = t_rx / t_vc
                 print(f"    estimate_react / estimate_varcoef = {t_rx / t_vc:.3f} (bytes {vc_bytes + nq * 8} / "
                       f"{vc_bytes} = {(vc_bytes + nq * 8) / vc_bytes:.3f})")
+    if args.hp:
+        deg = torch.full((ne,), M, dtype=torch.int32, device=dev)
+        sigma = torch.empty(ne, dtype=torch.float64, device=dev)
+        deg_new = torch.empty(2 * ne, dtype=torch.int32, device=dev)
+        cnt = torch.empty(3, dtype=torch.int64, device=dev)
+
+        def smooth():
+            ops._capi.check(lib.lssvr_smoothness(W.data_ptr(), M, deg.data_ptr(), ne, sigma.data_ptr(), st),
+                            "lssvr_smoothness")
+
+        def ref_hp():
+            ops._capi.check(lib.lssvr_refine_hp(x.data_ptr(), ne, eta2.data_ptr(), out3[1:2].data_ptr(), 0.5, 0.0,
+                                                sigma.data_ptr(), deg.data_ptr(), 1.0, 2, 21, work.data_ptr(),
+                                                x_new.data_ptr(), deg_new.data_ptr(), None, cnt[0:1].data_ptr(),
+                                                cnt[1:3].data_ptr(), st), "lssvr_refine_hp")
+        t_sm = timeit(smooth, args.reps)
+        t_hp = timeit(ref_hp, args.reps)
+        n_hp, n_split, n_raised = (int(v) for v in cnt.cpu())
+        mixed = torch.as_tensor(rng.integers(5, 22, ne).astype(np.int32), device=dev)
+        ids = torch.empty(ne, dtype=torch.int64, device=dev)
+        offsets = torch.empty(35, dtype=torch.int64, device=dev)
+        gwork = torch.empty(lib.lssvr_group_work_bytes(ne) // 8, dtype=torch.float64, device=dev)
+
+        def group():
+            ops._capi.check(lib.lssvr_group_by_degree(mixed.data_ptr(), ne, ids.data_ptr(), offsets.data_ptr(),
+                                                      gwork.data_ptr(), st), "lssvr_group_by_degree")
+        t_gr = timeit(group, args.reps)
+        # W row, deg, sigma; one log (~40 flop) + ~10 flop per coefficient
+        rec["smoothness"] = roofline("lssvr_smoothness     ", t_sm, ne, 8 * M + 4 + 8, 50 * (M - 1))
+        # x, eta2, sigma, deg twice (count, scatter); x_new, deg_new of the new elements
+        rec["refine_hp"] = roofline("lssvr_refine_hp      ", t_hp, ne, 2 * (8 + 8 + 8 + 4) + n_hp / ne * 12, 8)
+        # deg twice (histogram, scatter), ids
+        rec["group_by_degree"] = roofline("lssvr_group_by_degree", t_gr, ne, 2 * 4 + 8, 1)
+        rec["refine_hp"].update(bisected=n_split, raised=n_raised)
+        for k, t in (("smoothness", t_sm), ("refine_hp", t_hp), ("group_by_degree", t_gr)):
+            rec[k]["over_estimate"] = t / t_est
+        print(f"smoothness / estimate = {t_sm / t_est:.3f}, refine_hp / estimate = {t_hp / t_est:.3f}, "
+              f"group_by_degree / estimate = {t_gr / t_est:.3f}, refine_hp / refine = {t_hp / t_ref:.3f}; "
+              f"refine_hp bisected {n_split}, raised {n_raised} of {ne}")
     if args.json:
         with open(args.json, "w") as fh:
             json.dump(rec, fh, indent=1)
