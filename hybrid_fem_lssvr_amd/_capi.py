@@ -114,6 +114,10 @@ SIGNATURES = {
     # several load cases on one mesh (additive to ABI 7): ..., gxmin, gxmax, bc_values, ncases, M, n_colloc, gamma
     "lssvr_enhance_multi": _sig(_SHARD[:7], [_c_dp, _c_int], _SHARD[9:], _REACT_TABLES, [_c_int], _OUT, _STREAM,
                                 _TIMED),
+    # convection term -(a u')' + b u' + c u = f (additive to ABI 7): ..., a_quad, c_quad, b_quad, diag, sub, sup, load
+    "lssvr_p1_assemble_conv": _sig(_MESH, _RHS, [_c_dp, _c_dp, _c_dp], [_c_dp], _BANDS, _LOCAL, _STREAM),
+    "lssvr_tridiag_ns_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_tridiag_ns_dirichlet_solve": _sig([_c_dp], _BANDS, [_c_i64, _c_dbl, _c_dbl, _c_dp, _c_dp], _STREAM),
     # hp-adaptive refinement (additive to ABI 7)
     "lssvr_smoothness": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_dp], _STREAM),
     "lssvr_refine_hp": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dbl, _c_int, _c_int, _c_dp,

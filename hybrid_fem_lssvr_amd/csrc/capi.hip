@@ -771,6 +771,27 @@ int lssvr_p1_assemble_react(const double* x, int64_t ne, int nquad, int rhs_id,
   return check_launch(lssvr::p1_assemble_react(a, reinterpret_cast<hipStream_t>(stream)), "p1_assemble_react");
 }
 
+int lssvr_p1_assemble_conv(const double* x, int64_t ne, int nquad, int rhs_id,
+                           const double* rhs_params_host, const double* rhs_quad, const double* a_quad,
+                           const double* c_quad, const double* b_quad, double* diag, double* sub, double* sup,
+                           double* load, double* kloc, double* floc, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (!sub || !sup) return fail(LSSVR_ERR_NULL, "sub and sup must be non-NULL");
+  lssvr::P1ConvArgs a{};
+  int rc = bind_p1(a, x, ne, nquad, diag, sub, load);
+  if (rc == LSSVR_OK) rc = bind_p1_rhs(a, rhs_id, rhs_params_host, rhs_quad);
+  if (rc != LSSVR_OK) return rc;
+  a.off = nullptr;                // one band no longer: sub and sup
+  a.a_quad = a_quad;
+  a.c_quad = c_quad;
+  a.b_quad = b_quad;
+  a.sub = sub;
+  a.sup = sup;
+  a.kloc = kloc;
+  a.floc = floc;
+  return check_launch(lssvr::p1_assemble_conv(a, reinterpret_cast<hipStream_t>(stream)), "p1_assemble_conv");
+}
+
 int lssvr_quad_points(const double* x, int64_t ne, int nquad, double* xq, void* stream) {
   if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne < 0");
   if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
@@ -790,6 +811,18 @@ int lssvr_tridiag_dirichlet_solve(const double* diag, const double* off, const d
   return check_launch(lssvr::tridiag_dirichlet_solve(diag, off, load, ne, u0, u1, u, work,
                                                      reinterpret_cast<hipStream_t>(stream)),
                       "tridiag_dirichlet_solve");
+}
+
+int64_t lssvr_tridiag_ns_work_bytes(int64_t ne) { return lssvr::tridiag_ns_work_bytes(ne); }
+
+int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                     int64_t ne, double u0, double u1, double* u, void* work, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (!diag || !sub || !sup || !load || !u || !work)
+    return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u, work must be non-NULL");
+  return check_launch(lssvr::tridiag_ns_dirichlet_solve(diag, sub, sup, load, ne, u0, u1, u, work,
+                                                        reinterpret_cast<hipStream_t>(stream)),
+                      "tridiag_ns_dirichlet_solve");
 }
 
 int64_t lssvr_p1_flux_work_bytes(int64_t ne) { return lssvr::flux_work_bytes(ne); }

@@ -166,6 +166,15 @@ struct P1ReactArgs : P1Args {
   const double* c_quad;
 };
 hipError_t p1_assemble_react(const P1ReactArgs& a, hipStream_t s);
+// -(a u')' + b u' + c u (p1_conv.hip): plus b at the quadrature points; the matrix is no longer symmetric, so `off`
+// is unused and the two off-diagonal bands are sub[ne] (u_i in row i+1) and sup[ne] (u_{i+1} in row i).  a_quad,
+// c_quad and b_quad may each be NULL.
+struct P1ConvArgs : P1ReactArgs {
+  const double* b_quad;
+  double* sub;
+  double* sup;
+};
+hipError_t p1_assemble_conv(const P1ConvArgs& a, hipStream_t s);
 // assembly + enhancement of the same mesh in ONE launch (lane-per-element path, in-kernel rhs)
 hipError_t step_small(const EnhanceArgs& e, const P1Args& a, hipStream_t s,
                       const LaunchOpts* o = nullptr);
@@ -177,6 +186,11 @@ int64_t tridiag_work_bytes(int64_t ne);
 hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const double* load,
                                    int64_t ne, double u0, double u1, double* u, void* work,
                                    hipStream_t s);
+
+// the same solve for bands that are not symmetric (tridiag_ns.hip); no pivoting: diagonally dominant rows
+int64_t tridiag_ns_work_bytes(int64_t ne);
+hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                      int64_t ne, double u0, double u1, double* u, void* work, hipStream_t s);
 
 int64_t flux_work_bytes(int64_t ne);
 hipError_t flux_dirichlet_solve(const double* kloc, const double* load, int64_t ne, double u0,

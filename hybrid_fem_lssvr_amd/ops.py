@@ -84,6 +84,19 @@ def _tables(ne, k, point_major=False, *, shape=False, **named):
             raise ValueError(f"{nm} must hold {ne * k} doubles, got {t.numel()}")
 
 
+def _fold(da_values, b_values):
+    """The first-derivative table of -(a u')' + b u' = -a u'' - (a' - b) u': ``da_values - b_values`` (one float64
+    subtraction per entry; same shape and layout), or ``da_values`` itself without ``b_values``."""
+    if b_values is None:
+        return da_values
+    _dev(da_values, "da_values")
+    _dev(b_values, "b_values")
+    if b_values.shape != da_values.shape or b_values.device != da_values.device:
+        raise ValueError(f"b_values must have the shape and device of da_values {list(da_values.shape)}, "
+                         f"got {list(b_values.shape)} on {b_values.device}")
+    return da_values - b_values
+
+
 def _variant(a_values, da_values, rhs_values, c_values):
     """("varcoef" | "react", the table pointers in that entry's order): the optional c table is all that
     separates ``lssvr_*_varcoef*`` from ``lssvr_*_react*``."""
@@ -110,15 +123,16 @@ def _rhs(rhs, values, count, what, point_major=False, name="rhs_values"):
     return (RHS_ARRAY_PM if point_major else RHS_ARRAY), None
 
 
-def _bands(x, ne, bands=None, local=False):
+def _bands(x, ne, bands=None, local=False, offdiag=("off",)):
     """P1 bands {diag[ne+1], off[ne], load[ne+1]} (+ kloc[ne], floc[ne, 2] with ``local``), allocated
-    when not given; a caller's bands become raw device pointers, so they are checked."""
+    when not given; a caller's bands become raw device pointers, so they are checked.  ``offdiag``: the names of
+    the off-diagonal bands, ("sub", "sup") for the non-symmetric assembly."""
     if not bands:
-        shapes = {"diag": ne + 1, "off": ne, "load": ne + 1}
+        shapes = {"diag": ne + 1, **{k: ne for k in offdiag}, "load": ne + 1}
         if local:
             shapes.update(kloc=ne, floc=(ne, 2))
         return {k: torch.empty(s, dtype=torch.float64, device=x.device) for k, s in shapes.items()}
-    for k, cnt in (("diag", ne + 1), ("off", ne), ("load", ne + 1)):
+    for k, cnt in (("diag", ne + 1), *((k, ne) for k in offdiag), ("load", ne + 1)):
         _dev(bands[k], k)
         if bands[k].numel() != cnt:
             raise ValueError(f"bands[{k!r}] must hold {cnt} doubles")
@@ -467,7 +481,7 @@ class StepPlan:
 def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *, elem_offset=0,
                     ne_global=None, global_domain=None, bc=(0.0, 0.0), out=None, status=None,
                     fail_count=None, stream=None, profiled=False, point_major=False, repeats=None,
-                    c_values=None):
+                    c_values=None, b_values=None):
     """BASELINE config 5: rows -a (2/h)^2 L'' - a' (2/h) L' (no reference counterpart; the
     operator it generalises is Dual.py:43-44).  ``profiled``: BLOCKING, returns the launch
     duration in seconds (the dispatch's own begin / end stamps) instead of (W, status); with
@@ -476,9 +490,13 @@ def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *
     float64[ne, n_colloc] -- see :func:`colloc_points`; the fast layout for M <= 22.
     ``c_values`` (same shape as the other tables): the reaction rows of -(a u')' + c u = f
     (``lssvr_enhance_react_ws``: primal solve only, ``n_colloc >= M - 2``, no ``repeats``); ``None`` is the
-    call without it."""
+    call without it.
+    ``b_values`` (shape and layout of ``da_values``): the convection coefficient of -(a u')' + b u' (+ c u) = f;
+    the kernels read ``da_values`` only as the coefficient of the first-derivative row, so they are handed
+    ``da_values - b_values``; ``None`` is the call without it."""
     lib = _capi.load()
     ne, ne_global = _shard(x, u, elem_offset, ne_global)
+    da_values = _fold(da_values, b_values)
     _tables(ne, n_colloc, a_values=a_values, da_values=da_values, rhs_values=rhs_values,
             **({} if c_values is None else {"c_values": c_values}))
     if c_values is not None and repeats is not None:
@@ -496,7 +514,7 @@ def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *
 
 def enhance_multi(x, U, M, gamma, n_colloc, a_values, da_values, rhs_values, *, c_values=None, bc=None,
                   point_major=False, elem_offset=0, ne_global=None, global_domain, out=None, status=None,
-                  fail_count=None, stream=None, timed=False):
+                  fail_count=None, stream=None, timed=False, b_values=None):
     """``ncases`` load cases on one mesh in one call (``lssvr_enhance_multi``): the element systems of
     ``-(a u')' + c u = f`` are formed and factored once per element, every case brings its own nodal values
     ``U[ncases, ne+1]``, right-hand side ``rhs_values[ncases, ne, n_colloc]`` (``point_major``:
@@ -506,9 +524,12 @@ def enhance_multi(x, U, M, gamma, n_colloc, a_values, da_values, rhs_values, *, 
     ends).  Returns (W float64[ncases, ne, M], status int32[ncases, ne]); ``fail_count`` counts (case, element)
     fallbacks; ``status=False`` passes NULL (no status written, None returned).  ``timed``: BLOCKING, returns the
     duration of all passes in seconds instead.  Primal solve only (``n_colloc >= M - 2``); M <= 16 is the
-    one-factorisation lane kernel, above it the single-case kernel runs once per case."""
+    one-factorisation lane kernel, above it the single-case kernel runs once per case.
+    ``b_values`` (shape and layout of ``da_values``): the convection coefficient b of -(a u')' + b u' + c u = f, as in
+    :func:`enhance_varcoef` -- the kernels are handed ``da_values - b_values``; ``None``: no such term."""
     lib = _capi.load()
     M, n_colloc = int(M), int(n_colloc)
+    da_values = _fold(da_values, b_values)
     named = dict(x=x, U=U, a_values=a_values, da_values=da_values, rhs_values=rhs_values)
     if c_values is not None:
         named["c_values"] = c_values
@@ -645,15 +666,20 @@ def quad_points(x, nquad=2, *, stream=None):
 
 
 def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, a_quad=None,
-                want_local=False, out=None, stream=None, c_quad=None):
+                want_local=False, out=None, stream=None, c_quad=None, b_quad=None):
     """Element-local P1 stiffness/load and the assembled tridiagonal bands
     (Dual.py:117-128).  Returns dict(diag[ne+1], off[ne], load[ne+1][, kloc, floc]).
     ``c_quad`` float64[ne, nquad] (c at :func:`quad_points`): the consistent mass matrix of the reaction term
-    joins ``diag`` and ``off`` (``lssvr_p1_assemble_react``); ``None`` is the call without it."""
+    joins ``diag`` and ``off`` (``lssvr_p1_assemble_react``); ``None`` is the call without it.
+    ``b_quad`` float64[ne, nquad] (b at :func:`quad_points`): the convection term b u' joins the bands
+    (``lssvr_p1_assemble_conv``) and makes them non-symmetric -- the dict then holds ``sub[ne]`` (the coefficient of
+    u_i in row i+1) and ``sup[ne]`` (that of u_{i+1} in row i) instead of ``off``, for
+    :func:`tridiag_ns_dirichlet_solve`; ``None`` is the call without it."""
     lib = _capi.load()
     _dev(x, "x")
     ne = x.numel() - 1
-    out = _bands(x, ne, out, want_local)
+    offdiag = ("off",) if b_quad is None else ("sub", "sup")
+    out = _bands(x, ne, out, want_local, offdiag)
     rhs_id, params = _rhs(rhs, rhs_quad, ne * nquad, "ne*nquad", name="rhs_quad")
     if a_quad is not None:
         _dev(a_quad, "a_quad")
@@ -661,8 +687,11 @@ def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, 
     if c_quad is not None:
         _tables(ne, nquad, c_quad=c_quad)
         name, coefs = "lssvr_p1_assemble_react", (_ptr(a_quad), _ptr(c_quad))
+    if b_quad is not None:
+        _tables(ne, nquad, b_quad=b_quad)
+        name, coefs = "lssvr_p1_assemble_conv", (_ptr(a_quad), _ptr(c_quad), _ptr(b_quad))
     rc = getattr(lib, name)(_ptr(x), ne, int(nquad), rhs_id, params, _ptr(rhs_quad), *coefs,
-                            _ptr(out["diag"]), _ptr(out["off"]), _ptr(out["load"]),
+                            _ptr(out["diag"]), *(_ptr(out[k]) for k in offdiag), _ptr(out["load"]),
                             _ptr(out.get("kloc")), _ptr(out.get("floc")), _stream(stream))
     _capi.check(rc, name)
     return out
@@ -683,6 +712,31 @@ def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=N
     rc = lib.lssvr_tridiag_dirichlet_solve(_ptr(diag), _ptr(off), _ptr(load), ne, float(u0),
                                            float(u1), _ptr(out), _ptr(work), _stream(stream))
     _capi.check(rc, "lssvr_tridiag_dirichlet_solve")
+    return out
+
+
+def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
+    """:func:`tridiag_dirichlet_solve` for bands that are not symmetric (``lssvr_tridiag_ns_dirichlet_solve``):
+    row i is sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i] -> u[ne+1].  No pivoting: the rows must be
+    diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``)."""
+    lib = _capi.load()
+    for nm, t in (("diag", diag), ("sub", sub), ("sup", sup), ("load", load)):
+        _dev(t, nm)
+    ne = sub.numel()
+    if diag.numel() != ne + 1 or sup.numel() != ne or load.numel() != ne + 1:
+        raise ValueError("band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)")
+    if ne < 1:
+        raise ValueError("need at least one element")
+    if out is None:
+        out = torch.empty(ne + 1, dtype=torch.float64, device=diag.device)
+    else:
+        _dev(out, "out")
+        if out.numel() != ne + 1:
+            raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
+    work = _scratch(work, lib.lssvr_tridiag_ns_work_bytes(ne), diag.device)
+    rc = lib.lssvr_tridiag_ns_dirichlet_solve(_ptr(diag), _ptr(sub), _ptr(sup), _ptr(load), ne, float(u0),
+                                              float(u1), _ptr(out), _ptr(work), _stream(stream))
+    _capi.check(rc, "lssvr_tridiag_ns_dirichlet_solve")
     return out
 
 
@@ -858,7 +912,7 @@ def estimate(x, W, nq, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_values=None, poi
 
 
 def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point_major=False, want_jump=False,
-                     work=None, stream=None, c_values=None):
+                     work=None, stream=None, c_values=None, b_values=None):
     """:func:`estimate` for -(a u')' = f (``lssvr_estimate_varcoef``):
     eta2[e] = h^2 int_e (f + a u_e'' + a' u_e')^2 + h/2 (J_e^2 + J_{e+1}^2), J the jump of the flux a u'.
     ``a_values``, ``da_values``, ``rhs_values``: a, a' and f at :func:`estimate_points`, float64[ne, nq] or,
@@ -866,10 +920,14 @@ def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point
     element, seen from inside it.  Returns (eta2 float64[ne], jump float64[ne+1] | None, out3 device
     float64[3] = {sum, max of the finite eta2, non-finite count}).
     ``c_values`` (shape of the other tables): the residual of -(a u')' + c u = f, f + a u_e'' + a' u_e' - c u_e
-    (``lssvr_estimate_react``); ``None`` is the call without it."""
+    (``lssvr_estimate_react``); ``None`` is the call without it.
+    ``b_values`` (shape and layout of ``da_values``): the convection coefficient of -(a u')' + b u' (+ c u) = f -- the
+    residual becomes f + a u_e'' + (a' - b) u_e' (- c u_e): the kernels are handed ``da_values - b_values``, the flux
+    jump uses a alone; ``None`` is the call without it."""
     lib = _capi.load()
     _dev(x, "x")
     _dev(W, "W")
+    da_values = _fold(da_values, b_values)
     ne = x.numel() - 1
     nq = int(nq)
     if W.dim() != 2 or W.shape[0] != ne:

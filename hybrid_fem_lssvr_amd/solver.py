@@ -24,7 +24,10 @@ mesh/basis or node array instead of ``np.linspace(a, b, num_fem_nodes)``), ``fem
 applied per element), ``coef`` (a pair ``(a, da)`` of numpy-vectorised callables:
 solve, estimate and refine ``-(a u')' = f`` instead of ``-u'' = f``, BASELINE config 5 and DESIGN.md
 section 11; ``None`` keeps the Poisson rows), ``reaction`` (a numpy-vectorised callable ``c >= 0``: solve,
-estimate and refine ``-(a u')' + c u = f``; without ``coef``, a = 1; ``None``: no such term).
+estimate and refine ``-(a u')' + c u = f``; without ``coef``, a = 1; ``None``: no such term),
+``convection`` (a numpy-vectorised callable ``b``: solve, estimate and refine ``-(a u')' + b u' + c u = f``, DESIGN.md
+section 18; the P1 system is then non-symmetric and is solved without stabilisation, so every element must have a cell
+Peclet number ``|b| h / (2 a) <= 1``; ``None``: no such term).
 """
 from __future__ import annotations
 
@@ -132,18 +135,23 @@ def _zero(x):
 
 
 class _Equation:
-    """-(a u')' + c u = f as the facade holds it: the callables ``a``, ``da``, ``c``, ``f``; ``a`` / ``da`` and
-    ``c`` are None where the term is absent (a = 1, c = 0)."""
+    """-(a u')' + b u' + c u = f as the facade holds it: the callables ``a``, ``da``, ``b``, ``c``, ``f``; ``a`` /
+    ``da``, ``b`` and ``c`` are None where the term is absent (a = 1, b = 0, c = 0)."""
 
-    def __init__(self, rhs, coef, reaction):
+    def __init__(self, rhs, coef, reaction, convection=None):
         self.a, self.da = coef if coef is not None else (None, None)
-        self.c, self.f = reaction, rhs
-        self.poisson = coef is None and reaction is None       # the Poisson rows: no table but f's
+        self.b, self.c, self.f = convection, reaction, rhs
+        # the Poisson rows: no table but f's
+        self.poisson = coef is None and reaction is None and convection is None
 
     def tables(self, points, point_major=False):
-        """(a, a', f, c | None) tabulated at ``points``; without ``coef``, a = 1 and a' = 0."""
+        """(a, a', f, c | None) tabulated at ``points``; without ``coef``, a = 1 and a' = 0.  With convection the
+        second table is the folded first-derivative coefficient a' - b of -(a u')' + b u' = -a u'' - (a' - b) u',
+        which is all the enhancement and indicator kernels read it as (without ``coef``: -b)."""
         a, da = (_one, _zero) if self.a is None else (self.a, self.da)
         ta, tda, tf = (_tabulate(fn, points, point_major) for fn in (a, da, self.f))
+        if self.b is not None:
+            tda = tda - _tabulate(self.b, points, point_major)
         return ta, tda, tf, None if self.c is None else _tabulate(self.c, points, point_major)
 
     def a_ends(self, x):
@@ -325,7 +333,7 @@ def lssvr_primal(rhs_func, domain_range, u_xmin, u_xmax, M, gamma,
 class FEMLSSVRPrimalSolver:
     def __init__(self, num_fem_nodes=5, lssvr_M=12, lssvr_gamma=1e6, global_domain=(-1, 1), *,
                  n_colloc=12, rhs=poisson_rhs, nquad=2, mesh=None, device="cuda:0",
-                 solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None):
+                 solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None, convection=None):
         # Dual.py:101-108
         self.num_fem_nodes = num_fem_nodes
         self.lssvr_M = lssvr_M
@@ -364,6 +372,16 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("reaction needs solver=ops.SOLVER_PRIMAL: the reaction rows have a primal "
                                  "solve only")
         self.reaction = reaction
+        if convection is not None:
+            if not callable(convection):
+                raise ValueError("convection must be a callable b(x)")
+            if fem_solver == "flux":
+                raise ValueError("convection needs fem_solver='bands': the flux solve factors A = D^T K D, "
+                                 "which a non-symmetric matrix breaks")
+            if solver != ops.SOLVER_PRIMAL:
+                raise ValueError("convection needs solver=ops.SOLVER_PRIMAL: the rows with a first-derivative "
+                                 "term have a primal solve only")
+        self.convection = convection
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
         self.element_degrees = None     # one M per element (2 .. 33) instead of lssvr_M; solve_adaptive(mode="hp")
@@ -373,7 +391,7 @@ class FEMLSSVRPrimalSolver:
     @property
     def _eq(self):
         # (from the attributes at the time of use: they are public, and were always read when solving)
-        return _Equation(self.rhs, self.coef, self.reaction)
+        return _Equation(self.rhs, self.coef, self.reaction, self.convection)
 
     def _default_mesh(self):
         return LineMesh.from_nodes(np.linspace(self.global_domain[0], self.global_domain[1], self.num_fem_nodes))
@@ -399,13 +417,18 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
                                  "pivot and assumes an SPD matrix (c >= 0)")
             kw["c_quad"] = cq
+        if eq.b is not None:             # b u' in the bands: sub and sup instead of off
+            kw["b_quad"] = self._convection_quad(eq, x)
         if isinstance(rhs, SinRHS):
             bands = ops.p1_assemble(x, self.nquad, rhs=(rhs.amp, rhs.omega), want_local=True, **kw)
         else:
             xq = ops.quad_points(x, self.nquad)
             fq = _to_dev(rhs(xq.cpu().numpy()), dev)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
-        if self.fem_solver == "flux":
+        if eq.b is not None:
+            # no pivoting and no stabilisation: _convection_quad has checked the cell Peclet number
+            u = ops.tridiag_ns_dirichlet_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], u0, u1)
+        elif self.fem_solver == "flux":
             # exact-structure solution of A = D^T K D by the element-flux prefix scan
             u = ops.p1_flux_solve(bands["kloc"], bands["load"], u0, u1)
         else:
@@ -416,6 +439,23 @@ class FEMLSSVRPrimalSolver:
             # assembles +K u = +b, the same u)
             u = ops.tridiag_dirichlet_solve(bands["diag"], bands["off"], bands["load"], u0, u1)
         return m, x, u, bands
+
+    def _convection_quad(self, eq, x):
+        """b at the quadrature points [ne, nquad], after the check that makes the unpivoted, unstabilised solve safe:
+        the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 on every element (bbar, abar: quadrature means).
+        Host arithmetic on the tabulated values, before the assembly is launched."""
+        xq = ops.quad_points(x, self.nquad).cpu().numpy()
+        w = 0.5 * np.polynomial.legendre.leggauss(int(self.nquad))[1]
+        bq = np.array(np.broadcast_to(np.asarray(eq.b(xq), dtype=np.float64), xq.shape))     # (a writable copy)
+        abar = 1.0 if eq.a is None else np.broadcast_to(np.asarray(eq.a(xq), dtype=np.float64), xq.shape) @ w
+        nodes = x.cpu().numpy()
+        pe = np.abs(bq @ w) * np.diff(nodes) / (2.0 * abar)
+        worst = int(np.argmax(pe)) if np.all(np.isfinite(pe)) else int(np.argmax(~np.isfinite(pe)))
+        if not pe[worst] <= 1.0:
+            raise ValueError(f"cell Peclet number |b| h / (2 a) = {pe[worst]:.3g} > 1 on element {worst} "
+                             f"[{nodes[worst]:.6g}, {nodes[worst + 1]:.6g}]: the P1 solve of the convection term has "
+                             "no stabilisation and does not pivot; refine the mesh there")
+        return _to_dev(bq, x.device)
 
     # ---- Dual.py:110-137 --------------------------------------------------------------
     def solve_fem(self):
@@ -433,9 +473,9 @@ class FEMLSSVRPrimalSolver:
 
     # ---- one degree per element (no reference counterpart: Dual.py:101 has one lssvr_M) ----
     def _check_hp(self, what):
-        if self.coef is not None or self.reaction is not None:
-            raise ValueError(f"{what} needs the Poisson rows (no coef, no reaction): lssvr_enhance_subset holds "
-                             "those only")
+        if self.coef is not None or self.reaction is not None or self.convection is not None:
+            raise ValueError(f"{what} needs the Poisson rows (no coef, no reaction, no convection): "
+                             "lssvr_enhance_subset holds those only")
         if self.solver_id != ops.SOLVER_PRIMAL:
             raise ValueError(f"{what} needs solver=ops.SOLVER_PRIMAL")
 
@@ -547,7 +587,7 @@ class FEMLSSVRPrimalSolver:
             _, x, u, _ = self._fem(f, float(u0), float(u1))
             us.append(u)
         pts = ops.colloc_points(x, n)
-        ta, tda, _, tc = _Equation(_zero, self.coef, self.reaction).tables(pts, pm)
+        ta, tda, _, tc = _Equation(_zero, self.coef, self.reaction, self.convection).tables(pts, pm)
         tf = torch.stack([_tabulate(f, pts, pm) for f in rhs_list])
         W, st = ops.enhance_multi(x, torch.stack(us), M, gamma, n, ta, tda, tf, c_values=tc,
                                   bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd)

@@ -203,6 +203,9 @@ int lssvr_step_plan_destroy(lssvr_step_plan* plan);
  * with a_values/da_values/rhs_values tabulated at the collocation points
  * ([ne*n_colloc], row-major per element).  Other arguments as lssvr_enhance.
  * n_colloc < M-2 is routed to the dual solver (n_colloc <= 64), like lssvr_enhance.
+ * Convection: da_values is read only as the coefficient of the first-derivative row, and
+ * -(a u')' + b u' = -a u'' - (a' - b) u', so a table holding a' - b (one subtraction per
+ * point) gives the rows of -(a u')' + b u' = f; see "Convection term" at the end.
  */
 int lssvr_enhance_varcoef(const double* x, const double* u, int64_t ne,
                           int64_t elem_offset, int64_t ne_global,
@@ -468,6 +471,7 @@ int lssvr_estimate(const double* x, const double* W, int64_t ne, int M, int nq,
  *                   that jumps at a node gives a flux-continuous solution J = 0)
  *   jump[ne+1]      out, may be NULL: the J_i
  * work must hold lssvr_adapt_work_bytes(ne) bytes (not checkable here: no size argument).
+ * da_values holding a' - b: the residual f + a u_e'' + (a' - b) u_e' of -(a u')' + b u' = f; J uses a alone.
  */
 int lssvr_estimate_varcoef(const double* x, const double* W, int64_t ne, int M, int nq,
                            const double* a_values, const double* da_values, const double* rhs_values,
@@ -500,7 +504,8 @@ int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* 
  * The boundary rows, gamma, the BC-eliminated solve and the fallback status are those of lssvr_enhance_varcoef.
  * Primal solve only: n_colloc < M-2 is LSSVR_ERR_SOLVER (no dual form of these rows).  M <= 16 runs the lane
  * kernel, 17 <= M <= 33 the wave-cooperative MFMA kernel.  c of either sign is accepted here (the rows stay a
- * least-squares fit); the P1 solve is what needs c >= 0.
+ * least-squares fit); the P1 solve is what needs c >= 0.  da_values holding a' - b: the rows of
+ * -(a u')' + b u' + c u = f ("Convection term" at the end).
  * lssvr_enhance_react_ws -- with table_layout (LSSVR_TABLE_*, all FOUR tables alike), a workspace argument pair
  * kept for symmetry with lssvr_enhance_varcoef_ws (lssvr_enhance_varcoef_work_bytes() = 0 bytes are needed) and
  * kernel_ms_host (BLOCKING measurement aid).
@@ -540,6 +545,8 @@ int lssvr_p1_assemble_react(const double* x, int64_t ne, int nquad,
  * lssvr_estimate_react -- lssvr_estimate_varcoef plus c_values at lssvr_estimate_points (same table_layout):
  *   eta2[e] = h_e^2 * int_e (f + a u_e'' + a' u_e' - c u_e)^2 dx + h_e/2 * (J_e^2 + J_{e+1}^2),
  * J the jump of the flux a u' as in lssvr_estimate_varcoef.  Same reduction: no atomics, bitwise reproducible.
+ * da_values holding a' - b: the residual f + a u_e'' + (a' - b) u_e' - c u_e of -(a u')' + b u' + c u = f; the
+ * flux jump uses a alone and does not change.
  */
 int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, int nq,
                          const double* a_values, const double* da_values, const double* c_values,
@@ -572,6 +579,7 @@ int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, in
  * back alone.  Primal solve only: n_colloc < M-2 is LSSVR_ERR_SOLVER; ncases < 1 is LSSVR_ERR_SIZE; ne == 0 is a
  * successful no-op.  kernel_ms_host != NULL: BLOCKING, the duration from the first pass's begin to the last one's
  * end (above M = 16: the sum over the cases).
+ * da_values holding a' - b: the rows of -(a u')' + b u' + c u = f for every case ("Convection term" at the end).
  */
 int lssvr_enhance_multi(const double* x, const double* u, int64_t ne,
                         int64_t elem_offset, int64_t ne_global,
@@ -648,6 +656,51 @@ int lssvr_refine_hp(const double* x, int64_t ne, const double* eta2, const doubl
 int64_t lssvr_group_work_bytes(int64_t ne);
 int lssvr_group_by_degree(const int32_t* deg, int64_t ne, int64_t* ids, int64_t* offsets,
                           void* work, void* stream);
+
+/*
+ * Convection term: -(a u')' + b u' + c u = f (no reference counterpart).  ADDITIVE to ABI 7 like the reaction entries:
+ * three new symbols, no existing entry, struct or constant changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * Enhancement and indicator need no new entry.  -(a u')' + b u' = -a u'' - (a' - b) u', and lssvr_enhance_varcoef(_ws),
+ * lssvr_enhance_react(_ws), lssvr_enhance_multi, lssvr_estimate_varcoef and lssvr_estimate_react read da_values only
+ * as the coefficient of the first-derivative term (the flux jump of the indicator uses a alone).  THE CONVENTION: a
+ * caller with a convection coefficient b passes da_values[k] = a'(x_k) - b(x_k) at the same points, in the same
+ * layout; everything else is as documented at those entries.
+ *
+ * What changes is the P1 half: the Galerkin matrix of b u' is not symmetric.
+ *
+ * lssvr_p1_assemble_conv -- lssvr_p1_assemble_react plus b_quad[e*nquad + q] (b at lssvr_quad_points).  Per element
+ *   C_e[i][j] = sum_q w_q b(x_q) phi_i(xi_q) * s_j,   s_0 = -1, s_1 = +1   (h_e phi_j' = -+1),
+ * joins the element matrix.  With beta0_e = sum_q w_q b_q (1 - xi_q), beta1_e = sum_q w_q b_q xi_q:
+ *   diag[ne+1]   diag[i] = (abar_i/h_i + m_i[0][0] - beta0_i) + (abar_{i-1}/h_{i-1} + m_{i-1}[1][1] + beta1_{i-1})
+ *   sub[ne]      the coefficient of u_i in row i+1:   -abar_i/h_i + m_i[0][1] - beta1_i
+ *   sup[ne]      the coefficient of u_{i+1} in row i: -abar_i/h_i + m_i[0][1] + beta0_i
+ *   load[ne+1], kloc[ne], floc[2*ne] (the last two may be NULL): those of lssvr_p1_assemble
+ * (constant coefficients on a uniform mesh: sub, sup = -a/h -+ b/2 + c h/6, diag = 2a/h + 2ch/3).  a_quad, c_quad and
+ * b_quad may each be NULL (a = 1, c = 0, b = 0).  b_quad == NULL gives sub == sup == the `off` of
+ * lssvr_p1_assemble_react and its diag and load, bit for bit.  A thread per node gathers its two elements: no atomics,
+ * bitwise reproducible.
+ *
+ * lssvr_tridiag_ns_dirichlet_solve -- lssvr_tridiag_dirichlet_solve for these bands: u[0] = u0, u[ne] = u1 and, for
+ * 0 < i < ne,  sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i].  Same recursive substructuring (every 8th
+ * unknown a separator; condense, reduce, expand; parallel cyclic reduction in LDS at <= 512 unknowns), both
+ * off-diagonal bands carried through every level.  work: device scratch of lssvr_tridiag_ns_work_bytes(ne).
+ * NO PIVOTING.  That is safe when every row is diagonally dominant, |sub[i-1]| + |sup[i]| <= diag[i]: elimination
+ * keeps row dominance, so every Schur complement of every level has it and no divisor vanishes.  The rows of
+ * lssvr_p1_assemble_conv are dominant when c >= 0 and the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 on every
+ * element (bbar, abar: quadrature means; exact for coefficients constant on each element, DESIGN.md section 18 for
+ * the rest).  Above that the P1 solution oscillates and the solve may lose accuracy without notice: refine the mesh
+ * until the bound holds (there is no upwinding here).  The caller checks; this entry does not look at the values.
+ */
+int lssvr_p1_assemble_conv(const double* x, int64_t ne, int nquad,
+                           int rhs_id, const double* rhs_params_host, const double* rhs_quad,
+                           const double* a_quad, const double* c_quad, const double* b_quad,
+                           double* diag, double* sub, double* sup, double* load,
+                           double* kloc, double* floc, void* stream);
+int64_t lssvr_tridiag_ns_work_bytes(int64_t ne);
+int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                     int64_t ne, double u0, double u1,
+                                     double* u, void* work, void* stream);
 
 #ifdef __cplusplus
 }
