@@ -800,29 +800,33 @@ int lssvr_quad_points(const double* x, int64_t ne, int nquad, double* xq, void* 
                       "quad_points");
 }
 
+// one solver and one workspace formula behind both pairs of entries (tridiag.hip)
 int64_t lssvr_tridiag_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }
+int64_t lssvr_tridiag_ns_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }
+
+// sup == NULL: the symmetric entry, whose one band `off` arrives as sub
+static int tridiag_solve(const double* diag, const double* sub, const double* sup, const double* load, int64_t ne,
+                         double u0, double u1, double* u, void* work, void* stream, bool sym) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
+    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (sym)
+    return check_launch(lssvr::tridiag_dirichlet_solve(diag, sub, load, ne, u0, u1, u, work, st),
+                        "tridiag_dirichlet_solve");
+  return check_launch(lssvr::tridiag_ns_dirichlet_solve(diag, sub, sup, load, ne, u0, u1, u, work, st),
+                      "tridiag_ns_dirichlet_solve");
+}
 
 int lssvr_tridiag_dirichlet_solve(const double* diag, const double* off, const double* load,
                                   int64_t ne, double u0, double u1, double* u, void* work,
                                   void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (!diag || !off || !load || !u || !work)
-    return fail(LSSVR_ERR_NULL, "diag, off, load, u, work must be non-NULL");
-  return check_launch(lssvr::tridiag_dirichlet_solve(diag, off, load, ne, u0, u1, u, work,
-                                                     reinterpret_cast<hipStream_t>(stream)),
-                      "tridiag_dirichlet_solve");
+  return tridiag_solve(diag, off, nullptr, load, ne, u0, u1, u, work, stream, true);
 }
-
-int64_t lssvr_tridiag_ns_work_bytes(int64_t ne) { return lssvr::tridiag_ns_work_bytes(ne); }
 
 int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                      int64_t ne, double u0, double u1, double* u, void* work, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (!diag || !sub || !sup || !load || !u || !work)
-    return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u, work must be non-NULL");
-  return check_launch(lssvr::tridiag_ns_dirichlet_solve(diag, sub, sup, load, ne, u0, u1, u, work,
-                                                        reinterpret_cast<hipStream_t>(stream)),
-                      "tridiag_ns_dirichlet_solve");
+  return tridiag_solve(diag, sub, sup, load, ne, u0, u1, u, work, stream, false);
 }
 
 int64_t lssvr_p1_flux_work_bytes(int64_t ne) { return lssvr::flux_work_bytes(ne); }

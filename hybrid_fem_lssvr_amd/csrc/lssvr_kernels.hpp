@@ -182,13 +182,13 @@ constexpr int kStepVarcoefFusedMaxM = 12;   // lssvr_step_varcoef: one launch up
 hipError_t step_small_vc(const EnhanceArgs& e, const P1Args& a, hipStream_t s, const LaunchOpts* o = nullptr);
 hipError_t quad_points(const double* x, int64_t ne, int nquad, double* xq, hipStream_t s);
 
+// tridiag.hip: recursive substructuring, no pivoting (diagonally dominant rows).  One set of kernels and one
+// workspace size for the symmetric bands (off) and the non-symmetric ones (sub, sup); only the second ends its base
+// level with a step of iterative refinement.
 int64_t tridiag_work_bytes(int64_t ne);
 hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const double* load,
                                    int64_t ne, double u0, double u1, double* u, void* work,
                                    hipStream_t s);
-
-// the same solve for bands that are not symmetric (tridiag_ns.hip); no pivoting: diagonally dominant rows
-int64_t tridiag_ns_work_bytes(int64_t ne);
 hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                       int64_t ne, double u0, double u1, double* u, void* work, hipStream_t s);
 

@@ -5,7 +5,7 @@
 // With beta0_e = sum_q w_q b_q (1 - xi_q) and beta1_e = sum_q w_q b_q xi_q (beta0 + beta1 = the quadrature mean of b):
 //   sub[i]  = -k_i + m_i[0][1] - beta1_i,      sup[i] = -k_i + m_i[0][1] + beta0_i,
 //   diag[i] = (k_i + m_i[0][0] - beta0_i) + (k_{i-1} + m_{i-1}[1][1] + beta1_{i-1}).
-// tridiag_ns.hip solves these bands.
+// tridiag.hip solves these bands.
 #include "lssvr_device.hpp"
 #include "lssvr_kernels.hpp"
 #include "lssvr_p1.hpp"

@@ -697,34 +697,16 @@ def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, 
     return out
 
 
-def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
-    """``enforce`` + ``solve`` (Dual.py:129-130) on the assembled bands -> u[ne+1]."""
+def _tridiag_solve(entry, names, bands, lengths, u0, u1, out, work, stream):
+    """The C ``entry`` on ``bands`` (``names`` in its order: diag, one or two off-diagonal bands, load) -> u[ne+1];
+    ``lengths`` is the message for bands that are not ne+1, ne(, ne), ne+1 doubles long."""
     lib = _capi.load()
-    _dev(diag, "diag")
-    _dev(off, "off")
-    _dev(load, "load")
-    ne = off.numel()
-    if diag.numel() != ne + 1 or load.numel() != ne + 1:
-        raise ValueError("band lengths must be ne+1, ne, ne+1")
-    if out is None:
-        out = torch.empty(ne + 1, dtype=torch.float64, device=diag.device)
-    work = _scratch(work, lib.lssvr_tridiag_work_bytes(ne), diag.device)
-    rc = lib.lssvr_tridiag_dirichlet_solve(_ptr(diag), _ptr(off), _ptr(load), ne, float(u0),
-                                           float(u1), _ptr(out), _ptr(work), _stream(stream))
-    _capi.check(rc, "lssvr_tridiag_dirichlet_solve")
-    return out
-
-
-def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
-    """:func:`tridiag_dirichlet_solve` for bands that are not symmetric (``lssvr_tridiag_ns_dirichlet_solve``):
-    row i is sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i] -> u[ne+1].  No pivoting: the rows must be
-    diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``)."""
-    lib = _capi.load()
-    for nm, t in (("diag", diag), ("sub", sub), ("sup", sup), ("load", load)):
+    for nm, t in zip(names, bands):
         _dev(t, nm)
-    ne = sub.numel()
-    if diag.numel() != ne + 1 or sup.numel() != ne or load.numel() != ne + 1:
-        raise ValueError("band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)")
+    diag = bands[0]
+    ne = bands[1].numel()
+    if diag.numel() != ne + 1 or bands[-2].numel() != ne or bands[-1].numel() != ne + 1:
+        raise ValueError(lengths)
     if ne < 1:
         raise ValueError("need at least one element")
     if out is None:
@@ -733,11 +715,25 @@ def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None
         _dev(out, "out")
         if out.numel() != ne + 1:
             raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
-    work = _scratch(work, lib.lssvr_tridiag_ns_work_bytes(ne), diag.device)
-    rc = lib.lssvr_tridiag_ns_dirichlet_solve(_ptr(diag), _ptr(sub), _ptr(sup), _ptr(load), ne, float(u0),
-                                              float(u1), _ptr(out), _ptr(work), _stream(stream))
-    _capi.check(rc, "lssvr_tridiag_ns_dirichlet_solve")
+    # one solver behind both entries: lssvr_tridiag_ns_work_bytes returns the same number
+    work = _scratch(work, lib.lssvr_tridiag_work_bytes(ne), diag.device)
+    rc = getattr(lib, entry)(*map(_ptr, bands), ne, float(u0), float(u1), _ptr(out), _ptr(work), _stream(stream))
+    _capi.check(rc, entry)
     return out
+
+
+def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
+    """``enforce`` + ``solve`` (Dual.py:129-130) on the assembled bands -> u[ne+1]."""
+    return _tridiag_solve("lssvr_tridiag_dirichlet_solve", ("diag", "off", "load"), (diag, off, load),
+                          "band lengths must be ne+1, ne, ne+1", u0, u1, out, work, stream)
+
+
+def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
+    """:func:`tridiag_dirichlet_solve` for bands that are not symmetric (``lssvr_tridiag_ns_dirichlet_solve``):
+    row i is sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i] -> u[ne+1].  No pivoting: the rows must be
+    diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``)."""
+    return _tridiag_solve("lssvr_tridiag_ns_dirichlet_solve", ("diag", "sub", "sup", "load"), (diag, sub, sup, load),
+                          "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)", u0, u1, out, work, stream)
 
 
 def p1_flux_solve(kloc, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):

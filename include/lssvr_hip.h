@@ -353,6 +353,9 @@ int lssvr_quad_points(const double* x, int64_t ne, int nquad, double* xq, void* 
  * lssvr_tridiag_dirichlet_solve -- `enforce(A, b, D=all boundary dofs)` + `solve`
  * (Dual.py:129-130) for the assembled P1 bands: u[0]=u0, u[ne]=u1, interior by a
  * device tridiagonal solve.  work: device scratch of lssvr_tridiag_work_bytes(ne).
+ * lssvr_tridiag_work_bytes(ne) == lssvr_tridiag_ns_work_bytes(ne): one solver runs behind both entries.  The value
+ * is smaller than earlier builds of ABI 7 returned (they also charged one double per unknown and level that no
+ * kernel touched); a buffer sized by the earlier value is large enough.
  */
 int64_t lssvr_tridiag_work_bytes(int64_t ne);
 int lssvr_tridiag_dirichlet_solve(const double* diag, const double* off, const double* load,
@@ -684,7 +687,9 @@ int lssvr_group_by_degree(const int32_t* deg, int64_t ne, int64_t* ids, int64_t*
  * lssvr_tridiag_ns_dirichlet_solve -- lssvr_tridiag_dirichlet_solve for these bands: u[0] = u0, u[ne] = u1 and, for
  * 0 < i < ne,  sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i].  Same recursive substructuring (every 8th
  * unknown a separator; condense, reduce, expand; parallel cyclic reduction in LDS at <= 512 unknowns), both
- * off-diagonal bands carried through every level.  work: device scratch of lssvr_tridiag_ns_work_bytes(ne).
+ * off-diagonal bands carried through every level.  work: device scratch of lssvr_tridiag_ns_work_bytes(ne), which
+ * equals lssvr_tridiag_work_bytes(ne): the two entries share their kernels, and a buffer sized by either function
+ * serves both.  This entry alone ends the <= 512-unknown level with one step of iterative refinement.
  * NO PIVOTING.  That is safe when every row is diagonally dominant, |sub[i-1]| + |sup[i]| <= diag[i]: elimination
  * keeps row dominance, so every Schur complement of every level has it and no divisor vanishes.  The rows of
  * lssvr_p1_assemble_conv are dominant when c >= 0 and the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 on every

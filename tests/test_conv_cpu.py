@@ -65,6 +65,9 @@ def test_conv_argument_errors_without_gpu():
     assert wb(1) == wb(2) == wb(513) and 0 < wb(513) <= 1024
     assert 8 * 100000 < wb(100000) < 2 * 8 * 100000
     assert wb(10_000_000) < 2 * 8 * 10_000_000
+    # one solver, one workspace formula: the symmetric entry asks for the same bytes
+    for ne in (1, 2, 513, 514, 4097, 100000, 10_000_000):
+        assert lib.lssvr_tridiag_work_bytes(ne) == wb(ne), ne
 
 
 def test_ops_reject_host_tensors():

@@ -67,6 +67,29 @@ TRIDIAG_FORWARD_BAR = {1: 0.0, 2: 1e-15, 3: 1e-15, 24: 1e-14, 511: 2.5e-12, 512:
                        514: 2.5e-12, 1025: 4e-12, 16385: 2e-9, 100000: 7e-8, 1234567: 2e-6}
 
 
+def test_tridiag_caller_buffers(dev):
+    """Caller-supplied ``out`` and ``work`` at ne = 514 (one chunked level, a last chunk of one row): ``work`` of
+    exactly lssvr_tridiag_work_bytes(ne) is enough -- 64 guard doubles behind it keep their sentinel -- and the result
+    is bit-equal to the call that allocates both; an ``out`` of ne doubles is refused."""
+    import torch
+    from hybrid_fem_lssvr_amd import _capi, ops
+    ne = 514
+    diag, off, load, _ = orc.p1_bands(np.linspace(-1, 1, ne + 1))
+    d, o, l = _t(diag, dev), _t(off, dev), _t(load, dev)
+    u_ref = ops.tridiag_dirichlet_solve(d, o, l, 0.25, -0.5)
+    nbytes = _capi.load().lssvr_tridiag_work_bytes(ne)
+    assert nbytes % 8 == 0
+    sentinel = -7.25
+    buf = torch.full((nbytes // 8 + 64,), sentinel, dtype=torch.float64, device=dev)
+    out = torch.full((ne + 1,), sentinel, dtype=torch.float64, device=dev)
+    u = ops.tridiag_dirichlet_solve(d, o, l, 0.25, -0.5, out=out, work=buf[:nbytes // 8])
+    assert u is out
+    assert torch.equal(buf[nbytes // 8:], torch.full((64,), sentinel, dtype=torch.float64, device=dev))
+    assert torch.equal(out, u_ref)
+    with pytest.raises(ValueError, match="out must hold"):
+        ops.tridiag_dirichlet_solve(d, o, l, 0.25, -0.5, out=out[:ne])
+
+
 @pytest.mark.parametrize("ne", [1, 2, 3, 24, 2047, 2048, 2049, 100000, 1234567, 10000000])
 def test_p1_flux_solve(dev, ne):
     """Prefix-scan solve of the P1 system: residual at rounding level, and -- unlike any
