@@ -118,6 +118,11 @@ SIGNATURES = {
     "lssvr_p1_assemble_conv": _sig(_MESH, _RHS, [_c_dp, _c_dp, _c_dp], [_c_dp], _BANDS, _LOCAL, _STREAM),
     "lssvr_tridiag_ns_work_bytes": _sig([_c_i64], res=_c_i64),
     "lssvr_tridiag_ns_dirichlet_solve": _sig([_c_dp], _BANDS, [_c_i64, _c_dbl, _c_dbl, _c_dp, _c_dp], _STREAM),
+    # the P1 half of several load cases (additive to ABI 7): ..., ne, nc, bc_values, u, work, work_bytes
+    "lssvr_p1_load_multi": _sig(_MESH, [_c_dp, _c_int, _c_dp], _STREAM),
+    "lssvr_tridiag_multi_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
+    "lssvr_tridiag_dirichlet_solve_multi": _sig(_BANDS, [_c_i64, _c_int, _c_dp, _c_dp], _WS, _STREAM),
+    "lssvr_tridiag_ns_dirichlet_solve_multi": _sig([_c_dp], _BANDS, [_c_i64, _c_int, _c_dp, _c_dp], _WS, _STREAM),
     # hp-adaptive refinement (additive to ABI 7)
     "lssvr_smoothness": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_dp], _STREAM),
     "lssvr_refine_hp": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dbl, _c_int, _c_int, _c_dp,

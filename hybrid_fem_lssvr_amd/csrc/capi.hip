@@ -829,6 +829,51 @@ int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, cons
   return tridiag_solve(diag, sub, sup, load, ne, u0, u1, u, work, stream, false);
 }
 
+// several load cases on one mesh: the loads in one launch, the solves with the bands read once per pass
+int lssvr_p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,
+                        void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
+  if (!x || !rhs_quad || !load) return fail(LSSVR_ERR_NULL, "x, rhs_quad, load must be non-NULL");
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  return check_launch(lssvr::p1_load_multi(x, ne, nquad, rhs_quad, nc, load, reinterpret_cast<hipStream_t>(stream)),
+                      "p1_load_multi");
+}
+
+int64_t lssvr_tridiag_multi_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_multi_work_bytes(ne, nc); }
+
+// sup == NULL: the symmetric entry, whose one band `off` arrives as sub
+static int tridiag_solve_multi(const double* diag, const double* sub, const double* sup, const double* load,
+                               int64_t ne, int nc, const double* bc_values, double* u, void* work,
+                               int64_t work_bytes, void* stream, bool sym) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
+  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
+    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
+  const int64_t need = lssvr::tridiag_multi_work_bytes(ne, nc);
+  if (work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_multi_work_bytes(%lld, %d) = %lld",
+                (long long)work_bytes, (long long)ne, nc, (long long)need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (sym)
+    return check_launch(lssvr::tridiag_dirichlet_solve_multi(diag, sub, load, ne, nc, bc_values, u, work, st),
+                        "tridiag_dirichlet_solve_multi");
+  return check_launch(lssvr::tridiag_ns_dirichlet_solve_multi(diag, sub, sup, load, ne, nc, bc_values, u, work, st),
+                      "tridiag_ns_dirichlet_solve_multi");
+}
+
+int lssvr_tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne, int nc,
+                                        const double* bc_values, double* u, void* work, int64_t work_bytes,
+                                        void* stream) {
+  return tridiag_solve_multi(diag, off, nullptr, load, ne, nc, bc_values, u, work, work_bytes, stream, true);
+}
+
+int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
+                                           const double* load, int64_t ne, int nc, const double* bc_values, double* u,
+                                           void* work, int64_t work_bytes, void* stream) {
+  return tridiag_solve_multi(diag, sub, sup, load, ne, nc, bc_values, u, work, work_bytes, stream, false);
+}
+
 int64_t lssvr_p1_flux_work_bytes(int64_t ne) { return lssvr::flux_work_bytes(ne); }
 
 int lssvr_p1_flux_solve(const double* kloc, const double* load, int64_t ne, double u0, double u1,

@@ -101,6 +101,25 @@ hipError_t p1_assemble_react(const P1ReactArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the loads of nc right-hand sides on one mesh: one thread per node, the gather of p1_node (lssvr_p1.hpp)
+__global__ __launch_bounds__(kBlock) void p1_load_multi_kernel(const double* __restrict__ x, int64_t ne, int nquad,
+                                                                QuadRule q, const double* __restrict__ rhs_quad,
+                                                                int nc, double* __restrict__ load) {
+  const LoadWeights w = p1_load_weights(q, nquad);
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= ne; i += (int64_t)gridDim.x * kBlock)
+    p1_node_load_multi(x, ne, nquad, w, rhs_quad, nc, load, i);
+}
+
+hipError_t p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,
+                         hipStream_t s) {
+  QuadRule q;
+  if (!quad_rule(nquad, q)) return hipErrorInvalidValue;
+  const int64_t nn = ne + 1;
+  const unsigned blocks = (unsigned)((nn + kBlock - 1) / kBlock < 16384 ? (nn + kBlock - 1) / kBlock : 16384);
+  hipLaunchKernelGGL(p1_load_multi_kernel, dim3(blocks), dim3(kBlock), 0, s, x, ne, nquad, q, rhs_quad, nc, load);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // evaluate_solution (Dual.py:176-203)
 // ---------------------------------------------------------------------------

@@ -191,6 +191,20 @@ hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const 
                                    hipStream_t s);
 hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                       int64_t ne, double u0, double u1, double* u, void* work, hipStream_t s);
+// nc right-hand sides load[nc][ne+1] on one set of bands -> u[nc][ne+1], the end values from the device array
+// bc[nc][2] (NULL: zeros): the bands are read and the pivots computed once per pass of kTriMultiCases cases
+// (DESIGN.md section 19).  Row q has the bits of the single entry on case q.
+constexpr int kTriMultiCases = 8;
+int64_t tridiag_multi_work_bytes(int64_t ne, int nc);
+hipError_t tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne,
+                                         int nc, const double* bc, double* u, void* work, hipStream_t s);
+hipError_t tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
+                                            const double* load, int64_t ne, int nc, const double* bc, double* u,
+                                            void* work, hipStream_t s);
+// fem_eval.hip: the load of p1_assemble / _react / _conv for nc tabulated right-hand sides rhs_quad[nc][ne*nquad] ->
+// load[nc][ne+1], no bands
+hipError_t p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,
+                         hipStream_t s);
 
 int64_t flux_work_bytes(int64_t ne);
 hipError_t flux_dirichlet_solve(const double* kloc, const double* load, int64_t ne, double u0,

@@ -104,6 +104,58 @@ __device__ __forceinline__ void p1_node(const P1Args& p, const QuadRule& q, int6
 }
 
 // ---------------------------------------------------------------------------
+// the load vectors of several right-hand sides on one mesh (p1_load_multi_kernel, fem_eval.hip)
+// ---------------------------------------------------------------------------
+// The two load weights of every quadrature point, wl[k] = w_k (1 - xi_k) and wr[k] = w_k xi_k: the products that
+// p1_element forms inside its loop, formed once per thread.
+struct LoadWeights {
+  double wl[5], wr[5];
+};
+
+__device__ __forceinline__ LoadWeights p1_load_weights(const QuadRule& q, int nquad) {
+  LoadWeights w;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const double xi = k < nquad ? q.xi[k] : 0.0;
+    const double wt = k < nquad ? q.wt[k] : 0.0;
+    w.wl[k] = wt * (1.0 - xi);
+    w.wr[k] = wt * xi;
+  }
+  return w;
+}
+
+// fl (RIGHT == false) or fr (RIGHT == true) of p1_element<false> for the table f[nquad] of one element of length h:
+// the same sum in the same order, then h * sum
+template <bool RIGHT>
+__device__ __forceinline__ double p1_element_load(const LoadWeights& w, int nquad, const double* __restrict__ f,
+                                                  double h) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < 5; ++k)             // (unrolled: the weights stay in registers)
+    if (k < nquad) s += (RIGHT ? w.wr[k] : w.wl[k]) * f[k];
+  return h * s;
+}
+
+// p1_node's load entry of node i for nc right-hand sides, rhs_quad[j][ne*nquad] -> load[j][ne+1]: x and the weights
+// are read once, the per-case arithmetic is p1_element's and p1_node's (l = 0; l += fl of the right element; l += fr
+// of the left element).  No matrix bands are written.
+__device__ __forceinline__ void p1_node_load_multi(const double* __restrict__ x, int64_t ne, int nquad,
+                                                   const LoadWeights& w, const double* __restrict__ rhs_quad, int nc,
+                                                   double* __restrict__ load, int64_t i) {
+  const double xi = x[i];
+  const double hr = i < ne ? x[i + 1] - xi : 0.0;
+  const double hl = i > 0 ? xi - x[i - 1] : 0.0;
+  const int64_t per_case = ne * nquad;
+  for (int j = 0; j < nc; ++j) {
+    const double* f = rhs_quad + j * per_case;
+    double l = 0.0;
+    if (i < ne) l += p1_element_load<false>(w, nquad, f + i * nquad, hr);
+    if (i > 0) l += p1_element_load<true>(w, nquad, f + (i - 1) * nquad, hl);
+    load[j * (ne + 1) + i] = l;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // reaction term: the consistent P1 mass matrix of c,
 //   m_e[i][j] = h_e sum_q w_q c(x_q) phi_i(xi_q) phi_j(xi_q),  phi_0 = 1 - xi, phi_1 = xi
 // ---------------------------------------------------------------------------

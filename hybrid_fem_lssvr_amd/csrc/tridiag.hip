@@ -322,11 +322,408 @@ hipError_t dirichlet_solve(const TriSys& s, int64_t ne, double* u, void* work, h
   return solve_level<kRefine>(s, u + 1, reinterpret_cast<double*>(work), st);
 }
 
+// ---------------------------------------------------------------------------
+// Several right-hand sides on one matrix.  In the kernels above everything except the y
+// recurrence and the right-hand side is independent of the load: the multi forms load the three bands of a chunk
+// once, compute the pivots (1/den), cp, v, w, bp and cc[] once and keep them in registers, and then send one case
+// after the other through the y recurrence alone.  Every case goes through the operations of the single-RHS kernels
+// in their order (the build has -ffp-contract=off, so a product and a sum are never fused unless the source says
+// fma()), so row q of the result has the bits of the single entry on case q.
+// ---------------------------------------------------------------------------
+
+// s: the bands, and in s.r the right-hand side of the pass's first case; case q is rs doubles further on (s.u0 and
+// s.u1 are not read: the end values of case q are bc[2q], bc[2q+1], zeros when bc is NULL).  A pass holds
+// 1 <= nlive <= NC cases; slot q >= nlive repeats case nlive-1 (loads in bounds) and stores nothing.
+struct TriSysMulti {
+  TriSys s;
+  int64_t rs;
+  const double* bc;
+  int nlive;
+};
+
+// the load-independent half of ChunkEnds, one per chunk ...
+struct ChunkEndsShared {
+  double vF, wF, vL, wL;
+};
+// ... and the half of one case
+struct ChunkEndsCase {
+  double yF, yL;
+};
+
+__device__ __forceinline__ int case_of(const TriSysMulti& ms, int q) { return q < ms.nlive ? q : ms.nlive - 1; }
+
+// r_at for case c
+__device__ __forceinline__ double r_at_case(const TriSysMulti& ms, int c, int64_t i) {
+  const TriSys& s = ms.s;
+  double v = s.r[c * ms.rs + i];
+  if (i == 0 && s.bl) v -= s.bl[0] * (ms.bc ? ms.bc[2 * c] : 0.0);
+  if (i == s.m - 1 && s.br) v -= s.br[0] * (ms.bc ? ms.bc[2 * c + 1] : 0.0);
+  return v;
+}
+
+// the r of load_rows for case c: the kLc-1 values back to back
+__device__ __forceinline__ void load_case_rows(const TriSysMulti& ms, int c, int64_t b, int64_t e,
+                                               double (&r)[kLc - 1]) {
+#pragma unroll
+  for (int t = 0; t < kLc - 1; ++t) r[t] = r_at_case(ms, c, (b + t < e) ? b + t : b);
+}
+
+// tri_condense_kernel for NC cases: es[nc] once, ec[NC][nc] per case
+template <int NC>
+__global__ __launch_bounds__(kBlock) void tri_condense_multi_kernel(TriSysMulti ms, int64_t nc,
+                                                                    ChunkEndsShared* __restrict__ es,
+                                                                    ChunkEndsCase* __restrict__ ec) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= nc) return;
+  const TriSys& s = ms.s;
+  const int64_t b = j * kLc;
+  const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
+  const int len = (int)(e - b);
+  ChunkRows rb;
+  load_rows(s, b, e, rb);       // (rb.r is not read here: the cases bring their own, and the dead loads are dropped)
+  double dd[kLc - 1], du[kLc - 1];       // 1/den of the downward and of the upward sweep
+  ChunkEndsShared c;
+  {
+    double den = 1.0 / rb.d[0];
+    double v = -rb.lo[0] * den, cp = rb.up[0] * den;
+    dd[0] = den;
+#pragma unroll
+    for (int t = 1; t < kLc - 1; ++t) {
+      if (t < len) {
+        const double l = rb.lo[t];
+        den = 1.0 / (rb.d[t] - l * cp);
+        v = (-l * v) * den;
+        cp = rb.up[t] * den;
+      }
+      dd[t] = den;
+    }
+    c.vL = v;
+    c.wL = -cp;
+  }
+  {
+    double den = 1.0, bp = 0.0, w = 0.0;
+#pragma unroll
+    for (int t = kLc - 2; t >= 0; --t) {
+      if (t < len) {
+        if (t == len - 1) {
+          den = 1.0 / rb.d[t];
+          w = -rb.up[t] * den;
+        } else {
+          const double u = rb.up[t];
+          den = 1.0 / (rb.d[t] - u * bp);
+          w = (-u * w) * den;
+        }
+        bp = rb.lo[t] * den;
+      }
+      du[t] = den;
+    }
+    c.wF = w;
+    c.vF = -bp;
+  }
+  es[j] = c;
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    double r[kLc - 1];
+    load_case_rows(ms, case_of(ms, q), b, e, r);
+    ChunkEndsCase cq;
+    {
+      double y = r[0] * dd[0];
+#pragma unroll
+      for (int t = 1; t < kLc - 1; ++t)
+        if (t < len) y = (r[t] - rb.lo[t] * y) * dd[t];
+      cq.yL = y;
+    }
+    {
+      double y = 0.0;
+#pragma unroll
+      for (int t = kLc - 2; t >= 0; --t)
+        if (t < len) y = (t == len - 1) ? r[t] * du[t] : (r[t] - rb.up[t] * y) * du[t];
+      cq.yF = y;
+    }
+    if (q < ms.nlive) ec[q * nc + j] = cq;
+  }
+}
+
+// tri_reduce_kernel for NC cases: one LO, D, UP [ns], R[NC][ns]
+template <int NC>
+__global__ __launch_bounds__(kBlock) void tri_reduce_multi_kernel(TriSysMulti ms, int64_t ns, int64_t nc,
+                                                                  const ChunkEndsShared* __restrict__ es,
+                                                                  const ChunkEndsCase* __restrict__ ec,
+                                                                  double* __restrict__ LO, double* __restrict__ D,
+                                                                  double* __restrict__ UP, double* __restrict__ R) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= ns) return;
+  const TriSys& s = ms.s;
+  const int64_t p = j * kLc + kLc - 1;
+  const double l = s.lo[p];
+  const double u = up_at(s, p);
+  const bool right = j + 1 < nc;
+  const ChunkEndsShared cl = es[j];
+  double dd = s.d[p] + l * cl.wL;
+  double uu = 0.0;
+  if (right) {
+    const ChunkEndsShared cr = es[j + 1];
+    dd += u * cr.vF;
+    uu = u * cr.wF;
+  }
+  LO[j] = l * cl.vL;
+  D[j] = dd;
+  UP[j] = uu;
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    const int c = case_of(ms, q);
+    double rr = r_at_case(ms, c, p) - l * ec[c * nc + j].yL;
+    if (right) rr -= u * ec[c * nc + j + 1].yF;
+    if (q < ms.nlive) R[q * ns + j] = rr;
+  }
+}
+
+// tri_expand_kernel for NC cases: X[NC][ns] in, case q's level solution at x + q*xs out
+template <int NC>
+__global__ __launch_bounds__(kBlock) void tri_expand_multi_kernel(TriSysMulti ms, int64_t ns, int64_t nc,
+                                                                  const double* __restrict__ X,
+                                                                  double* __restrict__ x, int64_t xs) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= nc) return;
+  const TriSys& s = ms.s;
+  const int64_t b = j * kLc;
+  const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
+  const int len = (int)(e - b);
+  ChunkRows rb;
+  load_rows(s, b, e, rb);       // (rb.r: see tri_condense_multi_kernel)
+  // the factorisation of the chunk, once: 1/den and the modified upper band of every row
+  double cc[kLc - 1], dn[kLc - 1];
+  double c = 0.0, den = 1.0, upl = 0.0;
+#pragma unroll
+  for (int t = 0; t < kLc - 1; ++t) {
+    if (t < len) {
+      const double l = rb.lo[t];
+      den = 1.0 / (t == 0 ? rb.d[t] : rb.d[t] - l * c);
+      c = rb.up[t] * den;
+      if (t == len - 1) upl = rb.up[t];
+    }
+    cc[t] = c;
+    dn[t] = den;
+  }
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    const int cs = case_of(ms, q);
+    const double xl = j > 0 ? X[cs * ns + j - 1] : 0.0;
+    const double xr = j < ns ? X[cs * ns + j] : 0.0;
+    double r[kLc - 1];
+    load_case_rows(ms, cs, b, e, r);
+    double yy[kLc - 1];
+    double y = 0.0;
+#pragma unroll
+    for (int t = 0; t < kLc - 1; ++t) {
+      if (t < len) {
+        double ri = r[t];
+        if (t == 0) ri -= rb.lo[t] * xl;
+        if (t == len - 1) ri -= upl * xr;
+        y = (t == 0 ? ri : ri - rb.lo[t] * y) * dn[t];
+      }
+      yy[t] = y;
+    }
+    if (q < ms.nlive) {
+      double* xq = x + q * xs;
+      double xn = 0.0;
+#pragma unroll
+      for (int t = kLc - 2; t >= 0; --t) {
+        if (t < len) {
+          xn = (t == len - 1) ? yy[t] : yy[t] - cc[t] * xn;
+          xq[b + t] = xn;
+        }
+      }
+      if (j < ns) xq[b + kLc - 1] = xr;
+    }
+  }
+}
+
+// tri_pcr for NC right-hand sides: the matrix is reduced once, every step's two multipliers serve all the cases
+template <int NC>
+__device__ __forceinline__ void tri_pcr_multi(double li, double di, double ui, const double (&rin)[NC], int i, int m,
+                                              double* lo, double* d, double* up, double (*r)[kBase],
+                                              double (&x)[NC]) {
+  const bool in = i < m;
+  double ri[NC];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) ri[q] = rin[q];
+  for (int st = 1; st < m; st <<= 1) {
+    lo[i] = li;
+    d[i] = di;
+    up[i] = ui;
+#pragma unroll
+    for (int q = 0; q < NC; ++q) r[q][i] = ri[q];
+    __syncthreads();
+    if (in) {
+      double nl = 0.0, nu = 0.0;
+      if (i - st >= 0) {
+        const double al = -li / d[i - st];
+        di += al * up[i - st];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) ri[q] += al * r[q][i - st];
+        nl = al * lo[i - st];
+      }
+      if (i + st < m) {
+        const double be = -ui / d[i + st];
+        di += be * lo[i + st];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) ri[q] += be * r[q][i + st];
+        nu = be * up[i + st];
+      }
+      li = nl;
+      ui = nu;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < NC; ++q) x[q] = ri[q] / di;
+}
+
+// tri_base_kernel for NC cases: one matrix and NC right-hand sides in LDS, (3 + NC) * 4 KiB
+template <int NC, bool kRefine>
+__global__ __launch_bounds__(kBase) void tri_base_multi_kernel(TriSysMulti ms, double* __restrict__ x, int64_t xs) {
+  __shared__ double lo[kBase], d[kBase], up[kBase], r[NC][kBase];
+  const TriSys& s = ms.s;
+  const int i = threadIdx.x;
+  const int m = (int)s.m;
+  const bool in = i < m;
+  double li = 0.0, di = 1.0, ui = 0.0, ri[NC], xi[NC];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) ri[q] = 0.0;
+  if (in) {
+    li = lo_at(s, i);
+    di = s.d[i];
+    ui = up_at(s, i);
+#pragma unroll
+    for (int q = 0; q < NC; ++q) ri[q] = r_at_case(ms, case_of(ms, q), i);
+  }
+  tri_pcr_multi<NC>(li, di, ui, ri, i, m, lo, d, up, r, xi);
+  if constexpr (kRefine) {
+    // the refinement step of tri_base_kernel, case by case, with its residual FMAs
+#pragma unroll
+    for (int q = 0; q < NC; ++q) r[q][i] = xi[q];
+    __syncthreads();
+    double res[NC], dx[NC];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      res[q] = 0.0;
+      if (in) {
+        res[q] = fma(-di, xi[q], ri[q]);
+        if (i > 0) res[q] = fma(-li, r[q][i - 1], res[q]);
+        if (i + 1 < m) res[q] = fma(-ui, r[q][i + 1], res[q]);
+      }
+    }
+    __syncthreads();
+    tri_pcr_multi<NC>(li, di, ui, res, i, m, lo, d, up, r, dx);
+#pragma unroll
+    for (int q = 0; q < NC; ++q) xi[q] += dx[q];
+  }
+  if (in) {
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+      if (q < ms.nlive) x[q * xs + i] = xi[q];
+  }
+}
+
+// u[q][0] = bc[q][0], u[q][ne] = bc[q][1] for all the cases of a call (zeros without bc)
+__global__ void tri_ends_multi_kernel(double* u, int64_t ne, int nc, const double* bc) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nc) return;
+  u[q * (ne + 1)] = bc ? bc[2 * q] : 0.0;
+  u[q * (ne + 1) + ne] = bc ? bc[2 * q + 1] : 0.0;
+}
+
+// workspace (in doubles) of the levels above the base with K cases in a pass: es[4*nc] + ec[K][2*nc] + LO, D, UP
+// [3*ns] + R, X [K][2*ns]; K = 1 is level_doubles
+int64_t level_doubles_multi(int64_t m, int64_t K) {
+  int64_t tot = 0;
+  while (m > kBase) {
+    const int64_t nc = (m + kLc - 1) / kLc, ns = m / kLc;
+    tot += (4 + 2 * K) * nc + (3 + 2 * K) * ns + 16;
+    m = ns;
+  }
+  return tot + 16;
+}
+
+// solve_level for the NC slots of one pass: case q's solution of this level at x + q*xs
+template <int NC, bool kRefine>
+hipError_t solve_level_multi(const TriSysMulti& ms, double* x, int64_t xs, double* work, hipStream_t st) {
+  const TriSys& s = ms.s;
+  if (s.m <= 0) return hipSuccess;
+  if (s.m <= kBase) {
+    hipLaunchKernelGGL((tri_base_multi_kernel<NC, kRefine>), dim3(1), dim3((unsigned)kBase), 0, st, ms, x, xs);
+    return hipGetLastError();
+  }
+  const int64_t nc = (s.m + kLc - 1) / kLc, ns = s.m / kLc;
+  // (the per-case arrays hold the live cases only: idle slots store nothing, and the workspace of a call with fewer
+  // cases than a pass is sized for those)
+  const int64_t K = ms.nlive;
+  ChunkEndsShared* es = reinterpret_cast<ChunkEndsShared*>(work);
+  ChunkEndsCase* ec = reinterpret_cast<ChunkEndsCase*>(es + nc);
+  double* LO = reinterpret_cast<double*>(ec + K * nc);
+  double* D = LO + ns;
+  double* UP = D + ns;
+  double* R = UP + ns;
+  double* X = R + K * ns;
+  double* next = X + K * ns + 16;
+  const unsigned gc = (unsigned)((nc + kBlock - 1) / kBlock);
+  const unsigned gs = (unsigned)((ns + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(tri_condense_multi_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, ms, nc, es, ec);
+  hipLaunchKernelGGL(tri_reduce_multi_kernel<NC>, dim3(gs), dim3(kBlock), 0, st, ms, ns, nc, es, ec, LO, D, UP, R);
+  const TriSysMulti red{TriSys{LO, D, UP, R, nullptr, nullptr, 0.0, 0.0, ns}, ns, nullptr, ms.nlive};
+  const hipError_t err = solve_level_multi<NC, kRefine>(red, X, ns, next, st);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(tri_expand_multi_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, ms, ns, nc, X, x, xs);
+  return hipGetLastError();
+}
+
+// dirichlet_solve for nc cases, kTriMultiCases to a pass; the passes reuse the one workspace in stream order.  A pass
+// of one case runs the NC = 1 instantiation, a pass of 2 .. kTriMultiCases cases the NC = kTriMultiCases one.
+template <bool kRefine>
+hipError_t dirichlet_solve_multi(const TriSys& s, int64_t ne, int nc, const double* bc, double* u, void* work,
+                                 hipStream_t st) {
+  hipLaunchKernelGGL(tri_ends_multi_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, u, ne, nc, bc);
+  if (s.m <= 0) return hipGetLastError();
+  const int64_t stride = ne + 1;
+  for (int q0 = 0; q0 < nc; q0 += kTriMultiCases) {
+    const int nlive = nc - q0 < kTriMultiCases ? nc - q0 : kTriMultiCases;
+    TriSysMulti ms{s, stride, bc ? bc + 2 * (int64_t)q0 : nullptr, nlive};
+    ms.s.r += q0 * stride;
+    double* x = u + q0 * stride + 1;
+    const hipError_t err = nlive == 1
+                               ? solve_level_multi<1, kRefine>(ms, x, stride, reinterpret_cast<double*>(work), st)
+                               : solve_level_multi<kTriMultiCases, kRefine>(ms, x, stride,
+                                                                            reinterpret_cast<double*>(work), st);
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 int64_t tridiag_work_bytes(int64_t ne) {
   const int64_t m = ne > 1 ? ne - 1 : 0;
   return 8 * level_doubles(m) + 256;
+}
+
+// nc = 1: tridiag_work_bytes(ne); it grows with nc up to kTriMultiCases, the cases of one pass
+int64_t tridiag_multi_work_bytes(int64_t ne, int nc) {
+  const int64_t m = ne > 1 ? ne - 1 : 0;
+  return 8 * level_doubles_multi(m, nc < kTriMultiCases ? (nc > 1 ? nc : 1) : kTriMultiCases) + 256;
+}
+
+hipError_t tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne,
+                                         int nc, const double* bc, double* u, void* work, hipStream_t st) {
+  const TriSys s{off, diag + 1, off + 1, load + 1, off, off + (ne - 1), 0.0, 0.0, ne - 1};
+  return dirichlet_solve_multi<false>(s, ne, nc, bc, u, work, st);
+}
+
+hipError_t tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
+                                            const double* load, int64_t ne, int nc, const double* bc, double* u,
+                                            void* work, hipStream_t st) {
+  const TriSys s{sub, diag + 1, sup + 1, load + 1, sub, sup + (ne - 1), 0.0, 0.0, ne - 1};
+  return dirichlet_solve_multi<true>(s, ne, nc, bc, u, work, st);
 }
 
 // interior unknown k <-> node k+1: lo = off[k] (u_k in row k+1), d = diag[k+1], up = off[k+1], r = load[k+1]; the end

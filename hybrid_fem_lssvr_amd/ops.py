@@ -697,35 +697,65 @@ def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, 
     return out
 
 
-def _tridiag_solve(entry, names, bands, lengths, u0, u1, out, work, stream):
+def _tridiag_solve(entry, names, bands, lengths, ends, out, work, stream, multi=False):
     """The C ``entry`` on ``bands`` (``names`` in its order: diag, one or two off-diagonal bands, load) -> u[ne+1];
-    ``lengths`` is the message for bands that are not ne+1, ne(, ne), ne+1 doubles long."""
+    ``lengths`` is the message for bands that are not ne+1, ne(, ne), ne+1 doubles long; ``ends`` = (u0, u1).
+    ``multi``: the ``*_multi`` entry -- load is [nc, ne+1], ``ends`` the device array bc[nc, 2] or None, ``out`` may
+    hold more than nc cases (the first nc are written and returned), a ``work`` that is given must be large enough."""
     lib = _capi.load()
     for nm, t in zip(names, bands):
         _dev(t, nm)
-    diag = bands[0]
+    diag, load = bands[0], bands[-1]
     ne = bands[1].numel()
-    if diag.numel() != ne + 1 or bands[-2].numel() != ne or bands[-1].numel() != ne + 1:
+    per_case = load.shape[-1] if multi and load.dim() == 2 else load.numel()
+    if diag.numel() != ne + 1 or bands[-2].numel() != ne or per_case != ne + 1 or (multi and load.dim() != 2):
         raise ValueError(lengths)
     if ne < 1:
         raise ValueError("need at least one element")
+    nc = int(load.shape[0]) if multi else 1
+    if nc < 1:
+        raise ValueError("need at least one case")
     if out is None:
-        out = torch.empty(ne + 1, dtype=torch.float64, device=diag.device)
+        out = torch.empty((nc, ne + 1) if multi else ne + 1, dtype=torch.float64, device=diag.device)
     else:
         _dev(out, "out")
-        if out.numel() != ne + 1:
+        if multi and (out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc):
+            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
+        if not multi and out.numel() != ne + 1:
             raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
-    # one solver behind both entries: lssvr_tridiag_ns_work_bytes returns the same number
-    work = _scratch(work, lib.lssvr_tridiag_work_bytes(ne), diag.device)
-    rc = getattr(lib, entry)(*map(_ptr, bands), ne, float(u0), float(u1), _ptr(out), _ptr(work), _stream(stream))
+    if not multi:
+        # one solver behind both entries: lssvr_tridiag_ns_work_bytes returns the same number
+        work = _scratch(work, lib.lssvr_tridiag_work_bytes(ne), diag.device)
+        tail = (ne, float(ends[0]), float(ends[1]), _ptr(out), _ptr(work))
+    else:
+        need = lib.lssvr_tridiag_multi_work_bytes(ne, nc)
+        if work is None:
+            work = _scratch(None, need, diag.device)
+        else:
+            _dev(work, "work")
+            if work.numel() * work.element_size() < need:
+                raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                                 f"lssvr_tridiag_multi_work_bytes({ne}, {nc}) = {need}")
+        bc = ends
+        if bc is not None:
+            if not isinstance(bc, torch.Tensor):
+                bc = torch.as_tensor(np.ascontiguousarray(np.asarray(bc, dtype=np.float64)), device=diag.device)
+            _dev(bc, "bc")
+            if tuple(bc.shape) != (nc, 2):
+                raise ValueError(f"bc must be [nc, 2] = [{nc}, 2], got {list(bc.shape)}")
+        for nm, t in (*zip(names, bands), ("bc", bc), ("out", out), ("work", work)):
+            if t is not None and t.device != diag.device:
+                raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
+        tail = (ne, nc, _ptr(bc), _ptr(out), _ptr(work), work.numel() * work.element_size())
+    rc = getattr(lib, entry)(*map(_ptr, bands), *tail, _stream(stream))
     _capi.check(rc, entry)
-    return out
+    return out[:nc] if multi else out
 
 
 def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
     """``enforce`` + ``solve`` (Dual.py:129-130) on the assembled bands -> u[ne+1]."""
     return _tridiag_solve("lssvr_tridiag_dirichlet_solve", ("diag", "off", "load"), (diag, off, load),
-                          "band lengths must be ne+1, ne, ne+1", u0, u1, out, work, stream)
+                          "band lengths must be ne+1, ne, ne+1", (u0, u1), out, work, stream)
 
 
 def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
@@ -733,7 +763,61 @@ def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None
     row i is sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i] -> u[ne+1].  No pivoting: the rows must be
     diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``)."""
     return _tridiag_solve("lssvr_tridiag_ns_dirichlet_solve", ("diag", "sub", "sup", "load"), (diag, sub, sup, load),
-                          "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)", u0, u1, out, work, stream)
+                          "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)", (u0, u1), out, work,
+                          stream)
+
+
+# cases per pass of the multi-RHS tridiagonal solve (kTriMultiCases of the library): lssvr_tridiag_multi_work_bytes
+# grows with nc up to here
+TRIDIAG_MULTI_CASES = 8
+
+
+def tridiag_dirichlet_solve_multi(diag, off, load, bc=None, *, out=None, work=None, stream=None):
+    """``load.shape[0]`` calls of :func:`tridiag_dirichlet_solve` on the same bands in one
+    (``lssvr_tridiag_dirichlet_solve_multi``), bit-identical to them: load float64[nc, ne+1] -> u[nc, ne+1] with
+    u[j, 0], u[j, ne] = bc[j] (a float64 device tensor [nc, 2], or an array-like that is copied to the device;
+    ``None``: zeros).  The bands are read and the pivots computed once per pass of ``TRIDIAG_MULTI_CASES`` cases.
+    ``out`` [>= nc, ne+1]: its first nc rows are written and returned; ``work``: at least
+    ``lssvr_tridiag_multi_work_bytes(ne, nc)`` bytes (``ValueError`` otherwise)."""
+    return _tridiag_solve("lssvr_tridiag_dirichlet_solve_multi", ("diag", "off", "load"), (diag, off, load),
+                          "band lengths must be ne+1, ne and load [nc, ne+1]", bc, out, work, stream, multi=True)
+
+
+def tridiag_ns_dirichlet_solve_multi(diag, sub, sup, load, bc=None, *, out=None, work=None, stream=None):
+    """:func:`tridiag_dirichlet_solve_multi` for the non-symmetric bands: ``load.shape[0]`` calls of
+    :func:`tridiag_ns_dirichlet_solve` in one (``lssvr_tridiag_ns_dirichlet_solve_multi``), bit-identical to them."""
+    return _tridiag_solve("lssvr_tridiag_ns_dirichlet_solve_multi", ("diag", "sub", "sup", "load"),
+                          (diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] (diag, sub, "
+                          "sup, load)", bc, out, work, stream, multi=True)
+
+
+def p1_load_multi(x, rhs_quad, nquad=2, *, out=None, stream=None):
+    """The ``load`` of :func:`p1_assemble` for ``nc`` tabulated right-hand sides in one launch
+    (``lssvr_p1_load_multi``): rhs_quad float64[nc, ne, nquad] (f at :func:`quad_points`, case by case) ->
+    load[nc, ne+1], each row bit-identical to ``p1_assemble(x, nquad, rhs_quad=rhs_quad[j], ...)["load"]`` with or
+    without ``a_quad`` / ``c_quad`` / ``b_quad``.  No matrix bands are written.  ``out`` [>= nc, ne+1]: its first nc
+    rows are written and returned."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(rhs_quad, "rhs_quad")
+    ne, nquad = x.numel() - 1, int(nquad)
+    if x.dim() != 1 or ne < 1:
+        raise ValueError("x must be 1-D with at least two nodes")
+    if rhs_quad.dim() != 3 or tuple(rhs_quad.shape[1:]) != (ne, nquad) or rhs_quad.shape[0] < 1:
+        raise ValueError(f"rhs_quad must be [nc >= 1, ne, nquad] = [nc, {ne}, {nquad}], got {list(rhs_quad.shape)}")
+    nc = int(rhs_quad.shape[0])
+    if out is None:
+        out = torch.empty((nc, ne + 1), dtype=torch.float64, device=x.device)
+    else:
+        _dev(out, "out")
+        if out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc:
+            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
+    for nm, t in (("rhs_quad", rhs_quad), ("out", out)):
+        if t.device != x.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, x on {x.device}")
+    rc = lib.lssvr_p1_load_multi(_ptr(x), ne, nquad, _ptr(rhs_quad), nc, _ptr(out), _stream(stream))
+    _capi.check(rc, "lssvr_p1_load_multi")
+    return out[:nc]
 
 
 def p1_flux_solve(kloc, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):

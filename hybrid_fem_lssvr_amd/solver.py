@@ -440,6 +440,63 @@ class FEMLSSVRPrimalSolver:
             u = ops.tridiag_dirichlet_solve(bands["diag"], bands["off"], bands["load"], u0, u1)
         return m, x, u, bands
 
+    def _fem_many(self, rhs_list, bc):
+        """(x device, U device [ncases, ne+1]) of the P1 solves of :meth:`solve_many`: what ``_fem`` per case returns,
+        bit for bit, with the work that does not depend on the load done once -- the coefficient tables and their
+        checks, ONE assembly of the bands, the loads of all callable right-hand sides in one ``ops.p1_load_multi``,
+        one multi-RHS solve.  A ``SinRHS`` keeps its load from the in-kernel-sin assembly; ``fem_solver="flux"``
+        keeps the per-case path.  ``bc``: float64 host array [ncases, 2]."""
+        torch = _torch()
+        if self.fem_solver == "flux" and self.convection is None:
+            x, us = None, []
+            for f, (u0, u1) in zip(rhs_list, bc):
+                _, x, u, _ = self._fem(f, float(u0), float(u1))
+                us.append(u)
+            return x, torch.stack(us)
+        dev = _device(self.device)
+        m = self._default_mesh() if self.mesh is None else self.mesh
+        x = _to_dev(m.nodes, dev)
+        eq, kw = self._eq, {}
+        xq = ops.quad_points(x, self.nquad)
+        if eq.a is not None:
+            kw["a_quad"] = _tabulate(eq.a, xq)
+        if eq.c is not None:
+            cq = _tabulate(eq.c, xq)
+            if bool((cq < 0).any().item()):
+                raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
+                                 "pivot and assumes an SPD matrix (c >= 0)")
+            kw["c_quad"] = cq
+        if eq.b is not None:
+            kw["b_quad"] = self._convection_quad(eq, x)
+        load = torch.empty((len(rhs_list), x.numel()), dtype=torch.float64, device=dev)
+        tabulated = [j for j, f in enumerate(rhs_list) if not isinstance(f, SinRHS)]
+        bands = None
+        for j, f in enumerate(rhs_list):
+            if isinstance(f, SinRHS):           # its load keeps the bits of the in-kernel sin; the bands come along
+                bands = ops.p1_assemble(x, self.nquad, rhs=(f.amp, f.omega), **kw)
+                load[j].copy_(bands["load"])
+        if tabulated:
+            xq_host = xq.cpu().numpy()
+            fq = [_to_dev(rhs_list[j](xq_host), dev) for j in tabulated]
+            for j, t in zip(tabulated, fq):
+                if t.numel() != xq.numel():
+                    raise ValueError(f"rhs_list[{j}] must return one value per quadrature point "
+                                     f"({list(xq.shape)}), got {list(t.shape)}")
+            fq = torch.stack([t.reshape(xq.shape) for t in fq])
+            if bands is None:                   # the bands do not depend on the right-hand side
+                bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq[0], **kw)
+            loads = ops.p1_load_multi(x, fq, self.nquad)
+            if len(tabulated) == len(rhs_list):
+                load = loads
+            else:
+                load[torch.as_tensor(tabulated, device=dev)] = loads
+        bc_dev = _to_dev(bc, dev)
+        if eq.b is not None:
+            U = ops.tridiag_ns_dirichlet_solve_multi(bands["diag"], bands["sub"], bands["sup"], load, bc_dev)
+        else:
+            U = ops.tridiag_dirichlet_solve_multi(bands["diag"], bands["off"], load, bc_dev)
+        return x, U
+
     def _convection_quad(self, eq, x):
         """b at the quadrature points [ne, nquad], after the check that makes the unpivoted, unstabilised solve safe:
         the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 on every element (bbar, abar: quadrature means).
@@ -582,14 +639,11 @@ class FEMLSSVRPrimalSolver:
             raise ValueError(f"bc must hold one (left, right) pair per case: {(len(rhs_list), 2)}, got {bc.shape}")
         M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
         pm = int(M) <= 16                    # the lane kernel of lssvr_enhance_multi reads point-major tables
-        x, us = None, []
-        for f, (u0, u1) in zip(rhs_list, bc):
-            _, x, u, _ = self._fem(f, float(u0), float(u1))
-            us.append(u)
+        x, U = self._fem_many(rhs_list, bc)
         pts = ops.colloc_points(x, n)
         ta, tda, _, tc = _Equation(_zero, self.coef, self.reaction, self.convection).tables(pts, pm)
         tf = torch.stack([_tabulate(f, pts, pm) for f in rhs_list])
-        W, st = ops.enhance_multi(x, torch.stack(us), M, gamma, n, ta, tda, tf, c_values=tc,
+        W, st = ops.enhance_multi(x, U, M, gamma, n, ta, tda, tf, c_values=tc,
                                   bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd)
         return [EnhancedSolution(x, W[j], st[j]) for j in range(len(rhs_list))]
 

@@ -707,6 +707,38 @@ int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, cons
                                      int64_t ne, double u0, double u1,
                                      double* u, void* work, void* stream);
 
+/*
+ * Several load cases on one mesh and one operator, the P1 half (additive to ABI 7; lssvr_enhance_multi is the other
+ * half).  nc >= 1 cases; case j's arrays lie j * (their single-case length) doubles after case 0's.
+ *
+ * lssvr_p1_load_multi -- load[nc][ne+1] from rhs_quad[nc][ne*nquad] (f at lssvr_quad_points, case by case) in one
+ * launch that reads x once and writes no matrix bands.  Replaces nc calls of lssvr_p1_assemble / _react / _conv with
+ * LSSVR_RHS_ARRAY as far as `load` goes: load[j] is bit-identical to theirs for rhs_quad[j] (the load does not depend
+ * on a_quad, c_quad or b_quad).  The bands come from ONE call of those entries with any right-hand side.
+ *
+ * lssvr_tridiag_dirichlet_solve_multi -- replaces nc calls of lssvr_tridiag_dirichlet_solve on the same diag and off,
+ * bit-identical: u[j][0] = bc_values[j][0], u[j][ne] = bc_values[j][1] and the interior of case j from load[j].
+ * bc_values is a DEVICE array [nc][2] (NULL: zeros), the convention of lssvr_enhance_multi: nothing is read back and
+ * no stream is synchronised, so the call can be captured in a graph.  The cases run 8
+ * to a pass; in a pass the bands are read and the pivots of every level computed once.  work: device scratch of
+ * work_bytes >= lssvr_tridiag_multi_work_bytes(ne, nc) bytes; that value equals lssvr_tridiag_work_bytes(ne) at
+ * nc = 1, grows with nc up to the 8 cases of one pass and with ne.  ne == 1 writes only the two end values of every
+ * case.  Same no-pivoting rule as the single entry.
+ *
+ * lssvr_tridiag_ns_dirichlet_solve_multi -- replaces nc calls of lssvr_tridiag_ns_dirichlet_solve on the same diag,
+ * sub and sup, bit-identical (the step of iterative refinement of the <= 512-unknown level included, once per case).
+ * Arguments and workspace as above.
+ */
+int lssvr_p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,
+                        void* stream);
+int64_t lssvr_tridiag_multi_work_bytes(int64_t ne, int nc);
+int lssvr_tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load,
+                                        int64_t ne, int nc, const double* bc_values,
+                                        double* u, void* work, int64_t work_bytes, void* stream);
+int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
+                                           const double* load, int64_t ne, int nc, const double* bc_values,
+                                           double* u, void* work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
