@@ -804,29 +804,37 @@ int lssvr_quad_points(const double* x, int64_t ne, int nquad, double* xq, void* 
 int64_t lssvr_tridiag_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }
 int64_t lssvr_tridiag_ns_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }
 
-// sup == NULL: the symmetric entry, whose one band `off` arrives as sub
+// The four entries.  sup == NULL: a symmetric entry, whose one band `off` arrives as sub.  The single-RHS entries are
+// nc = 1 with the end values u0, u1 by value (bc NULL); they have no work_bytes argument, and only the multi entries
+// check it.
 static int tridiag_solve(const double* diag, const double* sub, const double* sup, const double* load, int64_t ne,
-                         double u0, double u1, double* u, void* work, void* stream, bool sym) {
+                         int nc, const double* bc, double u0, double u1, double* u, void* work, int64_t work_bytes,
+                         void* stream, bool sym, bool multi) {
   if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
   if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
     return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
+  const int64_t need = lssvr::tridiag_multi_work_bytes(ne, nc);
+  if (multi && work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_multi_work_bytes(%lld, %d) = %lld",
+                (long long)work_bytes, (long long)ne, nc, (long long)need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (sym)
-    return check_launch(lssvr::tridiag_dirichlet_solve(diag, sub, load, ne, u0, u1, u, work, st),
-                        "tridiag_dirichlet_solve");
-  return check_launch(lssvr::tridiag_ns_dirichlet_solve(diag, sub, sup, load, ne, u0, u1, u, work, st),
-                      "tridiag_ns_dirichlet_solve");
+    return check_launch(lssvr::tridiag_dirichlet_solve(diag, sub, load, ne, nc, bc, u0, u1, u, work, st),
+                        multi ? "tridiag_dirichlet_solve_multi" : "tridiag_dirichlet_solve");
+  return check_launch(lssvr::tridiag_ns_dirichlet_solve(diag, sub, sup, load, ne, nc, bc, u0, u1, u, work, st),
+                      multi ? "tridiag_ns_dirichlet_solve_multi" : "tridiag_ns_dirichlet_solve");
 }
 
 int lssvr_tridiag_dirichlet_solve(const double* diag, const double* off, const double* load,
                                   int64_t ne, double u0, double u1, double* u, void* work,
                                   void* stream) {
-  return tridiag_solve(diag, off, nullptr, load, ne, u0, u1, u, work, stream, true);
+  return tridiag_solve(diag, off, nullptr, load, ne, 1, nullptr, u0, u1, u, work, 0, stream, true, false);
 }
 
 int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                      int64_t ne, double u0, double u1, double* u, void* work, void* stream) {
-  return tridiag_solve(diag, sub, sup, load, ne, u0, u1, u, work, stream, false);
+  return tridiag_solve(diag, sub, sup, load, ne, 1, nullptr, u0, u1, u, work, 0, stream, false, false);
 }
 
 // several load cases on one mesh: the loads in one launch, the solves with the bands read once per pass
@@ -842,36 +850,16 @@ int lssvr_p1_load_multi(const double* x, int64_t ne, int nquad, const double* rh
 
 int64_t lssvr_tridiag_multi_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_multi_work_bytes(ne, nc); }
 
-// sup == NULL: the symmetric entry, whose one band `off` arrives as sub
-static int tridiag_solve_multi(const double* diag, const double* sub, const double* sup, const double* load,
-                               int64_t ne, int nc, const double* bc_values, double* u, void* work,
-                               int64_t work_bytes, void* stream, bool sym) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
-  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
-    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
-  const int64_t need = lssvr::tridiag_multi_work_bytes(ne, nc);
-  if (work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_multi_work_bytes(%lld, %d) = %lld",
-                (long long)work_bytes, (long long)ne, nc, (long long)need);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (sym)
-    return check_launch(lssvr::tridiag_dirichlet_solve_multi(diag, sub, load, ne, nc, bc_values, u, work, st),
-                        "tridiag_dirichlet_solve_multi");
-  return check_launch(lssvr::tridiag_ns_dirichlet_solve_multi(diag, sub, sup, load, ne, nc, bc_values, u, work, st),
-                      "tridiag_ns_dirichlet_solve_multi");
-}
-
 int lssvr_tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne, int nc,
                                         const double* bc_values, double* u, void* work, int64_t work_bytes,
                                         void* stream) {
-  return tridiag_solve_multi(diag, off, nullptr, load, ne, nc, bc_values, u, work, work_bytes, stream, true);
+  return tridiag_solve(diag, off, nullptr, load, ne, nc, bc_values, 0.0, 0.0, u, work, work_bytes, stream, true, true);
 }
 
 int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
                                            const double* load, int64_t ne, int nc, const double* bc_values, double* u,
                                            void* work, int64_t work_bytes, void* stream) {
-  return tridiag_solve_multi(diag, sub, sup, load, ne, nc, bc_values, u, work, work_bytes, stream, false);
+  return tridiag_solve(diag, sub, sup, load, ne, nc, bc_values, 0.0, 0.0, u, work, work_bytes, stream, false, true);
 }
 
 int64_t lssvr_p1_flux_work_bytes(int64_t ne) { return lssvr::flux_work_bytes(ne); }

@@ -182,25 +182,20 @@ constexpr int kStepVarcoefFusedMaxM = 12;   // lssvr_step_varcoef: one launch up
 hipError_t step_small_vc(const EnhanceArgs& e, const P1Args& a, hipStream_t s, const LaunchOpts* o = nullptr);
 hipError_t quad_points(const double* x, int64_t ne, int nquad, double* xq, hipStream_t s);
 
-// tridiag.hip: recursive substructuring, no pivoting (diagonally dominant rows).  One set of kernels and one
-// workspace size for the symmetric bands (off) and the non-symmetric ones (sub, sup); only the second ends its base
-// level with a step of iterative refinement.
-int64_t tridiag_work_bytes(int64_t ne);
-hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const double* load,
-                                   int64_t ne, double u0, double u1, double* u, void* work,
-                                   hipStream_t s);
-hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
-                                      int64_t ne, double u0, double u1, double* u, void* work, hipStream_t s);
-// nc right-hand sides load[nc][ne+1] on one set of bands -> u[nc][ne+1], the end values from the device array
-// bc[nc][2] (NULL: zeros): the bands are read and the pivots computed once per pass of kTriMultiCases cases
-// (DESIGN.md section 19).  Row q has the bits of the single entry on case q.
+// tridiag.hip: recursive substructuring, no pivoting (diagonally dominant rows).  One set of kernels for the
+// symmetric bands (off) and the non-symmetric ones (sub, sup); only the second ends its base level with a step of
+// iterative refinement.  nc right-hand sides load[nc][ne+1] on one set of bands -> u[nc][ne+1]; the end values of case
+// q are bc[q][0], bc[q][1] of the device array bc[nc][2] or, with bc NULL, u0 and u1 for every case (by value: the
+// single-RHS C entries are nc = 1 with bc NULL).  The bands are read and the pivots computed once per pass of
+// kTriMultiCases cases; row q does not depend on nc, bit for bit.
 constexpr int kTriMultiCases = 8;
 int64_t tridiag_multi_work_bytes(int64_t ne, int nc);
-hipError_t tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne,
-                                         int nc, const double* bc, double* u, void* work, hipStream_t s);
-hipError_t tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
-                                            const double* load, int64_t ne, int nc, const double* bc, double* u,
-                                            void* work, hipStream_t s);
+int64_t tridiag_work_bytes(int64_t ne);       // tridiag_multi_work_bytes(ne, 1)
+hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const double* load, int64_t ne, int nc,
+                                   const double* bc, double u0, double u1, double* u, void* work, hipStream_t s);
+hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                      int64_t ne, int nc, const double* bc, double u0, double u1, double* u,
+                                      void* work, hipStream_t s);
 // fem_eval.hip: the load of p1_assemble / _react / _conv for nc tabulated right-hand sides rhs_quad[nc][ne*nquad] ->
 // load[nc][ne+1], no bands
 hipError_t p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,

@@ -16,6 +16,14 @@
 // vanish.  The symmetric P1 matrix is SPD (Schur complements of SPD are SPD).  The non-symmetric rows are dominant
 // when, on every element, the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 and c >= 0.
 // Outside that the solve may divide by a small number without notice: the caller refines the mesh first.
+//
+// Several right-hand sides on one matrix.  Everything except the y recurrence and the
+// right-hand side is independent of the load, so every kernel takes NC cases: it loads the three bands of a chunk
+// once, computes the pivots (1/den), cp, v, w, bp and cc[] once and keeps them in registers, and then sends one case
+// after the other through the y recurrence alone.  A call is cut into passes of kTriMultiCases cases; a pass of one
+// case -- every call of the single-RHS entries is one -- runs the NC = 1 instantiation.  The operations of a case
+// and their order do not depend on NC (the build has -ffp-contract=off, so a product and a sum are never fused unless
+// the source says fma()), so row q of a multi call has the bits of the single entry on case q.
 #include "lssvr_device.hpp"
 #include "lssvr_kernels.hpp"
 
@@ -43,27 +51,51 @@ struct TriSys {
   int64_t m;
 };
 
+// The cases of one pass on s: s.r is the right-hand side of the first, case q is rs doubles further on, and its end
+// values are bc[2q], bc[2q+1] -- or, with bc NULL, s.u0 and s.u1 (by value: the single entries, and zeros for a multi
+// call without bc).  A pass holds 1 <= nlive <= NC cases; slot q >= nlive repeats case nlive-1 (loads in bounds) and
+// stores nothing.
+struct TriCases {
+  TriSys s;
+  int64_t rs;
+  const double* bc;
+  int nlive;
+};
+
 __device__ __forceinline__ double lo_at(const TriSys& s, int64_t i) { return i == 0 ? 0.0 : s.lo[i]; }
 __device__ __forceinline__ double up_at(const TriSys& s, int64_t i) { return i == s.m - 1 ? 0.0 : s.up[i]; }
-__device__ __forceinline__ double r_at(const TriSys& s, int64_t i) {
-  double v = s.r[i];
-  if (i == 0 && s.bl) v -= s.bl[0] * s.u0;
-  if (i == s.m - 1 && s.br) v -= s.br[0] * s.u1;
+template <int NC>
+__device__ __forceinline__ int case_of(const TriCases& tc, int q) {
+  if constexpr (NC == 1)
+    return 0;       // a pass of one case has no idle slot
+  else
+    return q < tc.nlive ? q : tc.nlive - 1;
+}
+// the right-hand side of row i for case c
+__device__ __forceinline__ double r_at(const TriCases& tc, int c, int64_t i) {
+  const TriSys& s = tc.s;
+  double v = s.r[c * tc.rs + i];
+  if (i == 0 && s.bl) v -= s.bl[0] * (tc.bc ? tc.bc[2 * c] : s.u0);
+  if (i == s.m - 1 && s.br) v -= s.br[0] * (tc.bc ? tc.bc[2 * c + 1] : s.u1);
   return v;
 }
 
 // x_interior = y + v * x_{left separator} + w * x_{right separator}; only the values at the first (F) and last (L)
-// interior unknown are needed for the reduced system.
-struct ChunkEnds {
-  double yF, vF, wF, yL, vL, wL;
+// interior unknown are needed for the reduced system.  v and w do not depend on the load: one per chunk ...
+struct ChunkEndsShared {
+  double vF, wF, vL, wL;
+};
+// ... and y, one per chunk and case
+struct ChunkEndsCase {
+  double yF, yL;
 };
 
 // The kLc-1 interior rows of a chunk, loaded back to back into registers before they are used: a thread walks its
 // own 64-byte stretch of every array, so its uses of a 128-byte line must be adjacent in time or the line is evicted
 // from the 32 KB L1 by the other 63 lanes' lines in between (measured: 1.6x less time at 1e7 unknowns than one load
-// per step).
+// per step).  The right-hand sides follow case by case, in the same way (load_case_rows).
 struct ChunkRows {
-  double lo[kLc - 1], d[kLc - 1], up[kLc - 1], r[kLc - 1];
+  double lo[kLc - 1], d[kLc - 1], up[kLc - 1];
 };
 
 // rows b .. b+kLc-2 clipped to [b, e): entries outside are a copy of row b and are never used
@@ -74,316 +106,33 @@ __device__ __forceinline__ void load_rows(const TriSys& s, int64_t b, int64_t e,
     rb.lo[t] = lo_at(s, i);
     rb.d[t] = s.d[i];
     rb.up[t] = up_at(s, i);
-    rb.r[t] = r_at(s, i);
   }
 }
 
-// chunk j: interior unknowns [j*kLc, min(j*kLc + kLc-1, m)), never empty for j < nc = ceil(m / kLc)
-__global__ __launch_bounds__(kBlock) void tri_condense_kernel(TriSys s, int64_t nc, ChunkEnds* __restrict__ ends) {
-  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (j >= nc) return;
-  const int64_t b = j * kLc;
-  const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
-  const int len = (int)(e - b);
-  ChunkRows rb;
-  load_rows(s, b, e, rb);
-  ChunkEnds c;
-  {  // downward sweep -> values at the last interior unknown; one division per row (1/den), three multiplications
-    double den = 1.0 / rb.d[0];
-    double y = rb.r[0] * den, v = -rb.lo[0] * den, cp = rb.up[0] * den;
-#pragma unroll
-    for (int t = 1; t < kLc - 1; ++t) {
-      if (t < len) {
-        const double l = rb.lo[t];
-        den = 1.0 / (rb.d[t] - l * cp);
-        y = (rb.r[t] - l * y) * den;
-        v = (-l * v) * den;
-        cp = rb.up[t] * den;
-      }
-    }
-    c.yL = y;
-    c.vL = v;
-    c.wL = -cp;               // rhs -up[e-1] e_last  ->  -up[e-1]/den_last  (den holds 1/den)
-  }
-  {  // upward sweep -> values at the first interior unknown
-    double den = 1.0, bp = 0.0, y = 0.0, w = 0.0;
-#pragma unroll
-    for (int t = kLc - 2; t >= 0; --t) {
-      if (t < len) {
-        if (t == len - 1) {
-          den = 1.0 / rb.d[t];
-          y = rb.r[t] * den;
-          w = -rb.up[t] * den;
-        } else {
-          const double u = rb.up[t];
-          den = 1.0 / (rb.d[t] - u * bp);
-          y = (rb.r[t] - u * y) * den;
-          w = (-u * w) * den;
-        }
-        bp = rb.lo[t] * den;
-      }
-    }
-    c.yF = y;
-    c.wF = w;
-    c.vF = -bp;
-  }
-  ends[j] = c;
-}
-
-// separator j sits at p = j*kLc + kLc-1 < m (j < ns = m / kLc), between chunk j (left) and chunk j+1 (right)
-__global__ __launch_bounds__(kBlock) void tri_reduce_kernel(TriSys s, int64_t ns, int64_t nc,
-                                                             const ChunkEnds* __restrict__ ends,
-                                                             double* __restrict__ LO, double* __restrict__ D,
-                                                             double* __restrict__ UP, double* __restrict__ R) {
-  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (j >= ns) return;
-  const int64_t p = j * kLc + kLc - 1;
-  const double l = s.lo[p];
-  const double u = up_at(s, p);
-  const ChunkEnds cl = ends[j];
-  double dd = s.d[p] + l * cl.wL;
-  double rr = r_at(s, p) - l * cl.yL;
-  double uu = 0.0;
-  if (j + 1 < nc) {
-    const ChunkEnds cr = ends[j + 1];
-    dd += u * cr.vF;
-    rr -= u * cr.yF;
-    uu = u * cr.wF;
-  }
-  LO[j] = l * cl.vL;
-  D[j] = dd;
-  UP[j] = uu;
-  R[j] = rr;
-}
-
-// re-solve every chunk with its separator values X[ns] known; x (length m) receives the whole level's solution
-__global__ __launch_bounds__(kBlock) void tri_expand_kernel(TriSys s, int64_t ns, int64_t nc,
-                                                             const double* __restrict__ X, double* __restrict__ x) {
-  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (j >= nc) return;
-  const int64_t b = j * kLc;
-  const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
-  const int len = (int)(e - b);
-  const double xl = j > 0 ? X[j - 1] : 0.0;
-  const double xr = j < ns ? X[j] : 0.0;
-  ChunkRows rb;
-  load_rows(s, b, e, rb);
-  // forward elimination; the modified coefficients stay in registers (kLc-1 = 7 of each), so the back substitution
-  // touches memory only to store the solution
-  double cc[kLc - 1], yy[kLc - 1];
-  double c = 0.0, y = 0.0;
-#pragma unroll
-  for (int t = 0; t < kLc - 1; ++t) {
-    if (t < len) {
-      double ri = rb.r[t];
-      if (t == 0) ri -= rb.lo[t] * xl;
-      if (t == len - 1) ri -= rb.up[t] * xr;
-      const double l = rb.lo[t];
-      const double den = 1.0 / (t == 0 ? rb.d[t] : rb.d[t] - l * c);
-      y = (t == 0 ? ri : ri - l * y) * den;
-      c = rb.up[t] * den;
-    }
-    cc[t] = c;
-    yy[t] = y;
-  }
-  double xn = 0.0;
-#pragma unroll
-  for (int t = kLc - 2; t >= 0; --t) {
-    if (t < len) {
-      xn = (t == len - 1) ? yy[t] : yy[t] - cc[t] * xn;
-      x[b + t] = xn;
-    }
-  }
-  if (j < ns) x[b + kLc - 1] = xr;
-}
-
-// Parallel cyclic reduction of row i (li, di, ui, ri) of an m-row system in LDS, all kBase threads of the one
-// workgroup together, ceil(log2 m) steps.  Each step eliminates x[i-st] and x[i+st] from row i with the rows st
-// away: the new lower band comes from their lower band, the new upper band from their upper band.  Returns x[i].
-__device__ __forceinline__ double tri_pcr(double li, double di, double ui, double ri, int i, int m, double* lo,
-                                          double* d, double* up, double* r) {
-  const bool in = i < m;
-  for (int st = 1; st < m; st <<= 1) {
-    lo[i] = li;
-    d[i] = di;
-    up[i] = ui;
-    r[i] = ri;
-    __syncthreads();
-    if (in) {
-      double nl = 0.0, nu = 0.0;
-      if (i - st >= 0) {
-        const double al = -li / d[i - st];
-        di += al * up[i - st];
-        ri += al * r[i - st];
-        nl = al * lo[i - st];
-      }
-      if (i + st < m) {
-        const double be = -ui / d[i + st];
-        di += be * lo[i + st];
-        ri += be * r[i + st];
-        nu = be * up[i + st];
-      }
-      li = nl;
-      ui = nu;
-    }
-    __syncthreads();
-  }
-  return ri / di;
-}
-
-// Base level (m <= kBase unknowns): parallel cyclic reduction, one workgroup of kBase threads -- a serial Thomas
-// sweep by one thread would pay a global-memory round trip per unknown (~100 us for 100 unknowns; this takes a few
-// us).  PCR needs no pivoting for the SPD / diagonally dominant systems that reach this level.
-// kRefine (the non-symmetric entry): then ONE step of iterative refinement with the residual of the original rows.
-// Cyclic reduction computes every unknown by its own chain of eliminations, so the rounding errors of neighbouring
-// unknowns are unrelated, and the matrix amplifies such a rough error by |A| in the residual: at 510 unknowns of a
-// P1 Laplacian the residual came out at 1.15 times the rounding-level bar the chunked levels meet with room to
-// spare (measured on an MI355X, DESIGN.md section 18).  The correction costs a second reduction of one workgroup, a
-// few microseconds.  The symmetric entry does without it: the step would change its bits and its time.
-template <bool kRefine>
-__global__ __launch_bounds__(kBase) void tri_base_kernel(TriSys s, double* __restrict__ x) {
-  __shared__ double lo[kBase], d[kBase], up[kBase], r[kBase];
-  const int i = threadIdx.x;
-  const int m = (int)s.m;
-  const bool in = i < m;
-  double li = 0.0, di = 1.0, ui = 0.0, ri = 0.0;
-  if (in) {
-    li = lo_at(s, i);
-    di = s.d[i];
-    ui = up_at(s, i);
-    ri = r_at(s, i);
-  }
-  double xi = tri_pcr(li, di, ui, ri, i, m, lo, d, up, r);
-  if constexpr (kRefine) {
-    // residual of row i with fused multiply-adds (one rounding each): r - lo x[i-1] - d x[i] - up x[i+1]
-    r[i] = xi;
-    __syncthreads();
-    double res = 0.0;
-    if (in) {
-      res = fma(-di, xi, ri);
-      if (i > 0) res = fma(-li, r[i - 1], res);
-      if (i + 1 < m) res = fma(-ui, r[i + 1], res);
-    }
-    __syncthreads();
-    xi += tri_pcr(li, di, ui, res, i, m, lo, d, up, r);
-  }
-  if (in) x[i] = xi;
-}
-
-__global__ void tri_ends_kernel(double* u, int64_t ne, double u0, double u1) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    u[0] = u0;
-    u[ne] = u1;
-  }
-}
-
-// workspace (in doubles) of the levels above the base: ends[6*nc] + reduced LO, D, UP, R, X [5*ns]
-int64_t level_doubles(int64_t m) {
-  int64_t tot = 0;
-  while (m > kBase) {
-    const int64_t nc = (m + kLc - 1) / kLc, ns = m / kLc;
-    tot += 6 * nc + 5 * ns + 16;
-    m = ns;
-  }
-  return tot + 16;
-}
-
-template <bool kRefine>
-hipError_t solve_level(const TriSys& s, double* x, double* work, hipStream_t st) {
-  if (s.m <= 0) return hipSuccess;
-  if (s.m <= kBase) {
-    hipLaunchKernelGGL(tri_base_kernel<kRefine>, dim3(1), dim3((unsigned)kBase), 0, st, s, x);
-    return hipGetLastError();
-  }
-  const int64_t nc = (s.m + kLc - 1) / kLc, ns = s.m / kLc;
-  ChunkEnds* ends = reinterpret_cast<ChunkEnds*>(work);
-  double* LO = reinterpret_cast<double*>(ends + nc);
-  double* D = LO + ns;
-  double* UP = D + ns;
-  double* R = UP + ns;
-  double* X = R + ns;
-  double* next = X + ns + 16;
-  const unsigned gc = (unsigned)((nc + kBlock - 1) / kBlock);
-  const unsigned gs = (unsigned)((ns + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(tri_condense_kernel, dim3(gc), dim3(kBlock), 0, st, s, nc, ends);
-  hipLaunchKernelGGL(tri_reduce_kernel, dim3(gs), dim3(kBlock), 0, st, s, ns, nc, ends, LO, D, UP, R);
-  const TriSys red{LO, D, UP, R, nullptr, nullptr, 0.0, 0.0, ns};
-  const hipError_t err = solve_level<kRefine>(red, X, next, st);
-  if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(tri_expand_kernel, dim3(gc), dim3(kBlock), 0, st, s, ns, nc, X, x);
-  return hipGetLastError();
-}
-
-// u[0] = u0, u[ne] = u1, then the ne-1 interior unknowns of s into u[1 ..]
-template <bool kRefine>
-hipError_t dirichlet_solve(const TriSys& s, int64_t ne, double* u, void* work, hipStream_t st) {
-  hipLaunchKernelGGL(tri_ends_kernel, dim3(1), dim3(64), 0, st, u, ne, s.u0, s.u1);
-  if (s.m <= 0) return hipGetLastError();
-  return solve_level<kRefine>(s, u + 1, reinterpret_cast<double*>(work), st);
-}
-
-// ---------------------------------------------------------------------------
-// Several right-hand sides on one matrix.  In the kernels above everything except the y
-// recurrence and the right-hand side is independent of the load: the multi forms load the three bands of a chunk
-// once, compute the pivots (1/den), cp, v, w, bp and cc[] once and keep them in registers, and then send one case
-// after the other through the y recurrence alone.  Every case goes through the operations of the single-RHS kernels
-// in their order (the build has -ffp-contract=off, so a product and a sum are never fused unless the source says
-// fma()), so row q of the result has the bits of the single entry on case q.
-// ---------------------------------------------------------------------------
-
-// s: the bands, and in s.r the right-hand side of the pass's first case; case q is rs doubles further on (s.u0 and
-// s.u1 are not read: the end values of case q are bc[2q], bc[2q+1], zeros when bc is NULL).  A pass holds
-// 1 <= nlive <= NC cases; slot q >= nlive repeats case nlive-1 (loads in bounds) and stores nothing.
-struct TriSysMulti {
-  TriSys s;
-  int64_t rs;
-  const double* bc;
-  int nlive;
-};
-
-// the load-independent half of ChunkEnds, one per chunk ...
-struct ChunkEndsShared {
-  double vF, wF, vL, wL;
-};
-// ... and the half of one case
-struct ChunkEndsCase {
-  double yF, yL;
-};
-
-__device__ __forceinline__ int case_of(const TriSysMulti& ms, int q) { return q < ms.nlive ? q : ms.nlive - 1; }
-
-// r_at for case c
-__device__ __forceinline__ double r_at_case(const TriSysMulti& ms, int c, int64_t i) {
-  const TriSys& s = ms.s;
-  double v = s.r[c * ms.rs + i];
-  if (i == 0 && s.bl) v -= s.bl[0] * (ms.bc ? ms.bc[2 * c] : 0.0);
-  if (i == s.m - 1 && s.br) v -= s.br[0] * (ms.bc ? ms.bc[2 * c + 1] : 0.0);
-  return v;
-}
-
-// the r of load_rows for case c: the kLc-1 values back to back
-__device__ __forceinline__ void load_case_rows(const TriSysMulti& ms, int c, int64_t b, int64_t e,
+// the right-hand sides of those rows for case c: the kLc-1 values back to back
+__device__ __forceinline__ void load_case_rows(const TriCases& tc, int c, int64_t b, int64_t e,
                                                double (&r)[kLc - 1]) {
 #pragma unroll
-  for (int t = 0; t < kLc - 1; ++t) r[t] = r_at_case(ms, c, (b + t < e) ? b + t : b);
+  for (int t = 0; t < kLc - 1; ++t) r[t] = r_at(tc, c, (b + t < e) ? b + t : b);
 }
 
-// tri_condense_kernel for NC cases: es[nc] once, ec[NC][nc] per case
+// chunk j: interior unknowns [j*kLc, min(j*kLc + kLc-1, m)), never empty for j < nc = ceil(m / kLc); es[nc] once,
+// ec[nlive][nc] per case
 template <int NC>
-__global__ __launch_bounds__(kBlock) void tri_condense_multi_kernel(TriSysMulti ms, int64_t nc,
-                                                                    ChunkEndsShared* __restrict__ es,
-                                                                    ChunkEndsCase* __restrict__ ec) {
+__global__ __launch_bounds__(kBlock) void tri_condense_kernel(TriCases tc, int64_t nc,
+                                                              ChunkEndsShared* __restrict__ es,
+                                                              ChunkEndsCase* __restrict__ ec) {
+  const TriSys& s = tc.s;
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (j >= nc) return;
-  const TriSys& s = ms.s;
   const int64_t b = j * kLc;
   const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
   const int len = (int)(e - b);
   ChunkRows rb;
-  load_rows(s, b, e, rb);       // (rb.r is not read here: the cases bring their own, and the dead loads are dropped)
+  load_rows(s, b, e, rb);
   double dd[kLc - 1], du[kLc - 1];       // 1/den of the downward and of the upward sweep
   ChunkEndsShared c;
-  {
+  {  // downward sweep -> values at the last interior unknown; one division per row (1/den), three multiplications
     double den = 1.0 / rb.d[0];
     double v = -rb.lo[0] * den, cp = rb.up[0] * den;
     dd[0] = den;
@@ -398,9 +147,9 @@ __global__ __launch_bounds__(kBlock) void tri_condense_multi_kernel(TriSysMulti 
       dd[t] = den;
     }
     c.vL = v;
-    c.wL = -cp;
+    c.wL = -cp;               // rhs -up[e-1] e_last  ->  -up[e-1]/den_last  (den holds 1/den)
   }
-  {
+  {  // upward sweep -> values at the first interior unknown
     double den = 1.0, bp = 0.0, w = 0.0;
 #pragma unroll
     for (int t = kLc - 2; t >= 0; --t) {
@@ -424,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void tri_condense_multi_kernel(TriSysMulti 
 #pragma unroll
   for (int q = 0; q < NC; ++q) {
     double r[kLc - 1];
-    load_case_rows(ms, case_of(ms, q), b, e, r);
+    load_case_rows(tc, case_of<NC>(tc, q), b, e, r);
     ChunkEndsCase cq;
     {
       double y = r[0] * dd[0];
@@ -440,20 +189,21 @@ __global__ __launch_bounds__(kBlock) void tri_condense_multi_kernel(TriSysMulti 
         if (t < len) y = (t == len - 1) ? r[t] * du[t] : (r[t] - rb.up[t] * y) * du[t];
       cq.yF = y;
     }
-    if (q < ms.nlive) ec[q * nc + j] = cq;
+    if (q < tc.nlive) ec[q * nc + j] = cq;
   }
 }
 
-// tri_reduce_kernel for NC cases: one LO, D, UP [ns], R[NC][ns]
+// separator j sits at p = j*kLc + kLc-1 < m (j < ns = m / kLc), between chunk j (left) and chunk j+1 (right): one LO,
+// D, UP [ns], R[nlive][ns]
 template <int NC>
-__global__ __launch_bounds__(kBlock) void tri_reduce_multi_kernel(TriSysMulti ms, int64_t ns, int64_t nc,
-                                                                  const ChunkEndsShared* __restrict__ es,
-                                                                  const ChunkEndsCase* __restrict__ ec,
-                                                                  double* __restrict__ LO, double* __restrict__ D,
-                                                                  double* __restrict__ UP, double* __restrict__ R) {
+__global__ __launch_bounds__(kBlock) void tri_reduce_kernel(TriCases tc, int64_t ns, int64_t nc,
+                                                            const ChunkEndsShared* __restrict__ es,
+                                                            const ChunkEndsCase* __restrict__ ec,
+                                                            double* __restrict__ LO, double* __restrict__ D,
+                                                            double* __restrict__ UP, double* __restrict__ R) {
+  const TriSys& s = tc.s;
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (j >= ns) return;
-  const TriSys& s = ms.s;
   const int64_t p = j * kLc + kLc - 1;
   const double l = s.lo[p];
   const double u = up_at(s, p);
@@ -471,27 +221,29 @@ __global__ __launch_bounds__(kBlock) void tri_reduce_multi_kernel(TriSysMulti ms
   UP[j] = uu;
 #pragma unroll
   for (int q = 0; q < NC; ++q) {
-    const int c = case_of(ms, q);
-    double rr = r_at_case(ms, c, p) - l * ec[c * nc + j].yL;
+    const int c = case_of<NC>(tc, q);
+    double rr = r_at(tc, c, p) - l * ec[c * nc + j].yL;
     if (right) rr -= u * ec[c * nc + j + 1].yF;
-    if (q < ms.nlive) R[q * ns + j] = rr;
+    if (q < tc.nlive) R[q * ns + j] = rr;
   }
 }
 
-// tri_expand_kernel for NC cases: X[NC][ns] in, case q's level solution at x + q*xs out
+// re-solve every chunk with its separator values X[nlive][ns] known; x + q*xs (length m) receives the whole level's
+// solution of case q
 template <int NC>
-__global__ __launch_bounds__(kBlock) void tri_expand_multi_kernel(TriSysMulti ms, int64_t ns, int64_t nc,
-                                                                  const double* __restrict__ X,
-                                                                  double* __restrict__ x, int64_t xs) {
+__global__ __launch_bounds__(kBlock) void tri_expand_kernel(TriCases tc, int64_t ns, int64_t nc,
+                                                            const double* __restrict__ X, double* __restrict__ x,
+                                                            int64_t xs) {
+  const TriSys& s = tc.s;
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (j >= nc) return;
-  const TriSys& s = ms.s;
   const int64_t b = j * kLc;
   const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
   const int len = (int)(e - b);
   ChunkRows rb;
-  load_rows(s, b, e, rb);       // (rb.r: see tri_condense_multi_kernel)
-  // the factorisation of the chunk, once: 1/den and the modified upper band of every row
+  load_rows(s, b, e, rb);
+  // the factorisation of the chunk, once: 1/den and the modified upper band of every row stay in registers (kLc-1 = 7
+  // of each), so the back substitution of a case touches memory only to store the solution
   double cc[kLc - 1], dn[kLc - 1];
   double c = 0.0, den = 1.0, upl = 0.0;
 #pragma unroll
@@ -507,11 +259,11 @@ __global__ __launch_bounds__(kBlock) void tri_expand_multi_kernel(TriSysMulti ms
   }
 #pragma unroll
   for (int q = 0; q < NC; ++q) {
-    const int cs = case_of(ms, q);
+    const int cs = case_of<NC>(tc, q);
     const double xl = j > 0 ? X[cs * ns + j - 1] : 0.0;
     const double xr = j < ns ? X[cs * ns + j] : 0.0;
     double r[kLc - 1];
-    load_case_rows(ms, cs, b, e, r);
+    load_case_rows(tc, cs, b, e, r);
     double yy[kLc - 1];
     double y = 0.0;
 #pragma unroll
@@ -524,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void tri_expand_multi_kernel(TriSysMulti ms
       }
       yy[t] = y;
     }
-    if (q < ms.nlive) {
+    if (q < tc.nlive) {
       double* xq = x + q * xs;
       double xn = 0.0;
 #pragma unroll
@@ -539,11 +291,13 @@ __global__ __launch_bounds__(kBlock) void tri_expand_multi_kernel(TriSysMulti ms
   }
 }
 
-// tri_pcr for NC right-hand sides: the matrix is reduced once, every step's two multipliers serve all the cases
+// Parallel cyclic reduction of row i (li, di, ui, rin[NC]) of an m-row system in LDS, all kBase threads of the one
+// workgroup together, ceil(log2 m) steps.  Each step eliminates x[i-st] and x[i+st] from row i with the rows st
+// away: the new lower band comes from their lower band, the new upper band from their upper band.  The matrix is
+// reduced once, every step's two multipliers serve all the cases.  x receives x[i] of every case.
 template <int NC>
-__device__ __forceinline__ void tri_pcr_multi(double li, double di, double ui, const double (&rin)[NC], int i, int m,
-                                              double* lo, double* d, double* up, double (*r)[kBase],
-                                              double (&x)[NC]) {
+__device__ __forceinline__ void tri_pcr(double li, double di, double ui, const double (&rin)[NC], int i, int m,
+                                        double* lo, double* d, double* up, double (*r)[kBase], double (&x)[NC]) {
   const bool in = i < m;
   double ri[NC];
 #pragma unroll
@@ -580,11 +334,20 @@ __device__ __forceinline__ void tri_pcr_multi(double li, double di, double ui, c
   for (int q = 0; q < NC; ++q) x[q] = ri[q] / di;
 }
 
-// tri_base_kernel for NC cases: one matrix and NC right-hand sides in LDS, (3 + NC) * 4 KiB
+// Base level (m <= kBase unknowns): parallel cyclic reduction, one workgroup of kBase threads -- a serial Thomas
+// sweep by one thread would pay a global-memory round trip per unknown (~100 us for 100 unknowns; this takes a few
+// us).  PCR needs no pivoting for the SPD / diagonally dominant systems that reach this level.  One matrix and NC
+// right-hand sides in LDS, (3 + NC) * 4 KiB.
+// kRefine (the non-symmetric entry): then ONE step of iterative refinement with the residual of the original rows.
+// Cyclic reduction computes every unknown by its own chain of eliminations, so the rounding errors of neighbouring
+// unknowns are unrelated, and the matrix amplifies such a rough error by |A| in the residual: at 510 unknowns of a
+// P1 Laplacian the residual came out at 1.15 times the rounding-level bar the chunked levels meet with room to
+// spare (measured on an MI355X, DESIGN.md section 18).  The correction costs a second reduction of one workgroup, a
+// few microseconds.  The symmetric entry does without it: the step would change its bits and its time.
 template <int NC, bool kRefine>
-__global__ __launch_bounds__(kBase) void tri_base_multi_kernel(TriSysMulti ms, double* __restrict__ x, int64_t xs) {
+__global__ __launch_bounds__(kBase) void tri_base_kernel(TriCases tc, double* __restrict__ x, int64_t xs) {
+  const TriSys& s = tc.s;
   __shared__ double lo[kBase], d[kBase], up[kBase], r[NC][kBase];
-  const TriSys& s = ms.s;
   const int i = threadIdx.x;
   const int m = (int)s.m;
   const bool in = i < m;
@@ -596,11 +359,12 @@ __global__ __launch_bounds__(kBase) void tri_base_multi_kernel(TriSysMulti ms, d
     di = s.d[i];
     ui = up_at(s, i);
 #pragma unroll
-    for (int q = 0; q < NC; ++q) ri[q] = r_at_case(ms, case_of(ms, q), i);
+    for (int q = 0; q < NC; ++q) ri[q] = r_at(tc, case_of<NC>(tc, q), i);
   }
-  tri_pcr_multi<NC>(li, di, ui, ri, i, m, lo, d, up, r, xi);
+  tri_pcr<NC>(li, di, ui, ri, i, m, lo, d, up, r, xi);
   if constexpr (kRefine) {
-    // the refinement step of tri_base_kernel, case by case, with its residual FMAs
+    // case by case, the residual of row i with fused multiply-adds (one rounding each): r - lo x[i-1] - d x[i] -
+    // up x[i+1]
 #pragma unroll
     for (int q = 0; q < NC; ++q) r[q][i] = xi[q];
     __syncthreads();
@@ -615,28 +379,28 @@ __global__ __launch_bounds__(kBase) void tri_base_multi_kernel(TriSysMulti ms, d
       }
     }
     __syncthreads();
-    tri_pcr_multi<NC>(li, di, ui, res, i, m, lo, d, up, r, dx);
+    tri_pcr<NC>(li, di, ui, res, i, m, lo, d, up, r, dx);
 #pragma unroll
     for (int q = 0; q < NC; ++q) xi[q] += dx[q];
   }
   if (in) {
 #pragma unroll
     for (int q = 0; q < NC; ++q)
-      if (q < ms.nlive) x[q * xs + i] = xi[q];
+      if (q < tc.nlive) x[q * xs + i] = xi[q];
   }
 }
 
-// u[q][0] = bc[q][0], u[q][ne] = bc[q][1] for all the cases of a call (zeros without bc)
-__global__ void tri_ends_multi_kernel(double* u, int64_t ne, int nc, const double* bc) {
+// u[q][0] = bc[q][0], u[q][ne] = bc[q][1] for all the cases of a call (u0, u1 without bc)
+__global__ void tri_ends_kernel(double* u, int64_t ne, int nc, const double* bc, double u0, double u1) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nc) return;
-  u[q * (ne + 1)] = bc ? bc[2 * q] : 0.0;
-  u[q * (ne + 1) + ne] = bc ? bc[2 * q + 1] : 0.0;
+  u[q * (ne + 1)] = bc ? bc[2 * q] : u0;
+  u[q * (ne + 1) + ne] = bc ? bc[2 * q + 1] : u1;
 }
 
 // workspace (in doubles) of the levels above the base with K cases in a pass: es[4*nc] + ec[K][2*nc] + LO, D, UP
-// [3*ns] + R, X [K][2*ns]; K = 1 is level_doubles
-int64_t level_doubles_multi(int64_t m, int64_t K) {
+// [3*ns] + R, X [K][2*ns]
+int64_t level_doubles(int64_t m, int64_t K) {
   int64_t tot = 0;
   while (m > kBase) {
     const int64_t nc = (m + kLc - 1) / kLc, ns = m / kLc;
@@ -646,19 +410,19 @@ int64_t level_doubles_multi(int64_t m, int64_t K) {
   return tot + 16;
 }
 
-// solve_level for the NC slots of one pass: case q's solution of this level at x + q*xs
+// one level for the NC slots of a pass: case q's solution of this level at x + q*xs
 template <int NC, bool kRefine>
-hipError_t solve_level_multi(const TriSysMulti& ms, double* x, int64_t xs, double* work, hipStream_t st) {
-  const TriSys& s = ms.s;
+hipError_t solve_level(const TriCases& tc, double* x, int64_t xs, double* work, hipStream_t st) {
+  const TriSys& s = tc.s;
   if (s.m <= 0) return hipSuccess;
   if (s.m <= kBase) {
-    hipLaunchKernelGGL((tri_base_multi_kernel<NC, kRefine>), dim3(1), dim3((unsigned)kBase), 0, st, ms, x, xs);
+    hipLaunchKernelGGL((tri_base_kernel<NC, kRefine>), dim3(1), dim3((unsigned)kBase), 0, st, tc, x, xs);
     return hipGetLastError();
   }
   const int64_t nc = (s.m + kLc - 1) / kLc, ns = s.m / kLc;
   // (the per-case arrays hold the live cases only: idle slots store nothing, and the workspace of a call with fewer
   // cases than a pass is sized for those)
-  const int64_t K = ms.nlive;
+  const int64_t K = tc.nlive;
   ChunkEndsShared* es = reinterpret_cast<ChunkEndsShared*>(work);
   ChunkEndsCase* ec = reinterpret_cast<ChunkEndsCase*>(es + nc);
   double* LO = reinterpret_cast<double*>(ec + K * nc);
@@ -669,32 +433,34 @@ hipError_t solve_level_multi(const TriSysMulti& ms, double* x, int64_t xs, doubl
   double* next = X + K * ns + 16;
   const unsigned gc = (unsigned)((nc + kBlock - 1) / kBlock);
   const unsigned gs = (unsigned)((ns + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(tri_condense_multi_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, ms, nc, es, ec);
-  hipLaunchKernelGGL(tri_reduce_multi_kernel<NC>, dim3(gs), dim3(kBlock), 0, st, ms, ns, nc, es, ec, LO, D, UP, R);
-  const TriSysMulti red{TriSys{LO, D, UP, R, nullptr, nullptr, 0.0, 0.0, ns}, ns, nullptr, ms.nlive};
-  const hipError_t err = solve_level_multi<NC, kRefine>(red, X, ns, next, st);
+  hipLaunchKernelGGL(tri_condense_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, tc, nc, es, ec);
+  hipLaunchKernelGGL(tri_reduce_kernel<NC>, dim3(gs), dim3(kBlock), 0, st, tc, ns, nc, es, ec, LO, D, UP, R);
+  const TriCases red{TriSys{LO, D, UP, R, nullptr, nullptr, 0.0, 0.0, ns}, ns, nullptr, tc.nlive};
+  const hipError_t err = solve_level<NC, kRefine>(red, X, ns, next, st);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(tri_expand_multi_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, ms, ns, nc, X, x, xs);
+  hipLaunchKernelGGL(tri_expand_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, tc, ns, nc, X, x, xs);
   return hipGetLastError();
 }
 
-// dirichlet_solve for nc cases, kTriMultiCases to a pass; the passes reuse the one workspace in stream order.  A pass
-// of one case runs the NC = 1 instantiation, a pass of 2 .. kTriMultiCases cases the NC = kTriMultiCases one.
+// u[q][0], u[q][ne] = the end values of case q, then the ne-1 interior unknowns of s into u[q][1 ..], for the nc
+// cases that follow s.r at a stride of ne+1, kTriMultiCases to a pass; the passes reuse the one workspace in stream
+// order.  A pass of one case runs the NC = 1 instantiation, a pass of 2 .. kTriMultiCases cases the
+// NC = kTriMultiCases one.  The end values are bc[nc][2] on the device or, with bc NULL, s.u0 and s.u1 for every case.
 template <bool kRefine>
-hipError_t dirichlet_solve_multi(const TriSys& s, int64_t ne, int nc, const double* bc, double* u, void* work,
-                                 hipStream_t st) {
-  hipLaunchKernelGGL(tri_ends_multi_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, u, ne, nc, bc);
+hipError_t dirichlet_solve(const TriSys& s, int64_t ne, int nc, const double* bc, double* u, void* work,
+                           hipStream_t st) {
+  hipLaunchKernelGGL(tri_ends_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, u, ne, nc, bc, s.u0, s.u1);
   if (s.m <= 0) return hipGetLastError();
   const int64_t stride = ne + 1;
   for (int q0 = 0; q0 < nc; q0 += kTriMultiCases) {
     const int nlive = nc - q0 < kTriMultiCases ? nc - q0 : kTriMultiCases;
-    TriSysMulti ms{s, stride, bc ? bc + 2 * (int64_t)q0 : nullptr, nlive};
-    ms.s.r += q0 * stride;
+    TriCases tc{s, stride, bc ? bc + 2 * (int64_t)q0 : nullptr, nlive};
+    tc.s.r += q0 * stride;
     double* x = u + q0 * stride + 1;
     const hipError_t err = nlive == 1
-                               ? solve_level_multi<1, kRefine>(ms, x, stride, reinterpret_cast<double*>(work), st)
-                               : solve_level_multi<kTriMultiCases, kRefine>(ms, x, stride,
-                                                                            reinterpret_cast<double*>(work), st);
+                               ? solve_level<1, kRefine>(tc, x, stride, reinterpret_cast<double*>(work), st)
+                               : solve_level<kTriMultiCases, kRefine>(tc, x, stride,
+                                                                      reinterpret_cast<double*>(work), st);
     if (err != hipSuccess) return err;
   }
   return hipSuccess;
@@ -702,43 +468,28 @@ hipError_t dirichlet_solve_multi(const TriSys& s, int64_t ne, int nc, const doub
 
 }  // namespace
 
-int64_t tridiag_work_bytes(int64_t ne) {
-  const int64_t m = ne > 1 ? ne - 1 : 0;
-  return 8 * level_doubles(m) + 256;
-}
-
-// nc = 1: tridiag_work_bytes(ne); it grows with nc up to kTriMultiCases, the cases of one pass
+// it grows with nc up to kTriMultiCases, the cases of one pass
 int64_t tridiag_multi_work_bytes(int64_t ne, int nc) {
   const int64_t m = ne > 1 ? ne - 1 : 0;
-  return 8 * level_doubles_multi(m, nc < kTriMultiCases ? (nc > 1 ? nc : 1) : kTriMultiCases) + 256;
+  return 8 * level_doubles(m, nc < kTriMultiCases ? (nc > 1 ? nc : 1) : kTriMultiCases) + 256;
 }
 
-hipError_t tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne,
-                                         int nc, const double* bc, double* u, void* work, hipStream_t st) {
-  const TriSys s{off, diag + 1, off + 1, load + 1, off, off + (ne - 1), 0.0, 0.0, ne - 1};
-  return dirichlet_solve_multi<false>(s, ne, nc, bc, u, work, st);
-}
-
-hipError_t tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
-                                            const double* load, int64_t ne, int nc, const double* bc, double* u,
-                                            void* work, hipStream_t st) {
-  const TriSys s{sub, diag + 1, sup + 1, load + 1, sub, sup + (ne - 1), 0.0, 0.0, ne - 1};
-  return dirichlet_solve_multi<true>(s, ne, nc, bc, u, work, st);
-}
+int64_t tridiag_work_bytes(int64_t ne) { return tridiag_multi_work_bytes(ne, 1); }
 
 // interior unknown k <-> node k+1: lo = off[k] (u_k in row k+1), d = diag[k+1], up = off[k+1], r = load[k+1]; the end
-// rows lose off[0] * u0 and off[ne-1] * u1 to the right-hand side
-hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const double* load, int64_t ne, double u0,
-                                   double u1, double* u, void* work, hipStream_t st) {
+// rows lose off[0] * u[0] and off[ne-1] * u[ne] to the right-hand side
+hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const double* load, int64_t ne, int nc,
+                                   const double* bc, double u0, double u1, double* u, void* work, hipStream_t st) {
   const TriSys s{off, diag + 1, off + 1, load + 1, off, off + (ne - 1), u0, u1, ne - 1};
-  return dirichlet_solve<false>(s, ne, u, work, st);
+  return dirichlet_solve<false>(s, ne, nc, bc, u, work, st);
 }
 
-// the same with lo = sub[k], up = sup[k+1]; the end rows lose sub[0] * u0 and sup[ne-1] * u1
+// the same with lo = sub[k], up = sup[k+1]; the end rows lose sub[0] * u[0] and sup[ne-1] * u[ne]
 hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
-                                      int64_t ne, double u0, double u1, double* u, void* work, hipStream_t st) {
+                                      int64_t ne, int nc, const double* bc, double u0, double u1, double* u,
+                                      void* work, hipStream_t st) {
   const TriSys s{sub, diag + 1, sup + 1, load + 1, sub, sup + (ne - 1), u0, u1, ne - 1};
-  return dirichlet_solve<true>(s, ne, u, work, st);
+  return dirichlet_solve<true>(s, ne, nc, bc, u, work, st);
 }
 
 }  // namespace lssvr

@@ -715,38 +715,39 @@ def _tridiag_solve(entry, names, bands, lengths, ends, out, work, stream, multi=
     nc = int(load.shape[0]) if multi else 1
     if nc < 1:
         raise ValueError("need at least one case")
+    shape = (nc, ne + 1) if multi else (ne + 1,)
     if out is None:
-        out = torch.empty((nc, ne + 1) if multi else ne + 1, dtype=torch.float64, device=diag.device)
+        out = torch.empty(shape, dtype=torch.float64, device=diag.device)
     else:
         _dev(out, "out")
         if multi and (out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc):
             raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
         if not multi and out.numel() != ne + 1:
             raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
-    if not multi:
-        # one solver behind both entries: lssvr_tridiag_ns_work_bytes returns the same number
-        work = _scratch(work, lib.lssvr_tridiag_work_bytes(ne), diag.device)
-        tail = (ne, float(ends[0]), float(ends[1]), _ptr(out), _ptr(work))
-    else:
-        need = lib.lssvr_tridiag_multi_work_bytes(ne, nc)
-        if work is None:
-            work = _scratch(None, need, diag.device)
-        else:
-            _dev(work, "work")
-            if work.numel() * work.element_size() < need:
-                raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                                 f"lssvr_tridiag_multi_work_bytes({ne}, {nc}) = {need}")
-        bc = ends
-        if bc is not None:
-            if not isinstance(bc, torch.Tensor):
-                bc = torch.as_tensor(np.ascontiguousarray(np.asarray(bc, dtype=np.float64)), device=diag.device)
-            _dev(bc, "bc")
-            if tuple(bc.shape) != (nc, 2):
-                raise ValueError(f"bc must be [nc, 2] = [{nc}, 2], got {list(bc.shape)}")
+    # one solver and one formula behind the four entries: at nc = 1 this is lssvr_tridiag_work_bytes(ne) and
+    # lssvr_tridiag_ns_work_bytes(ne)
+    need = lib.lssvr_tridiag_multi_work_bytes(ne, nc)
+    if multi and work is not None:     # (the single entries replace a work that is too small)
+        _dev(work, "work")
+        if work.numel() * work.element_size() < need:
+            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                             f"lssvr_tridiag_multi_work_bytes({ne}, {nc}) = {need}")
+    work = _scratch(work, need, diag.device)
+    bc = ends if multi else None
+    if bc is not None:
+        if not isinstance(bc, torch.Tensor):
+            bc = torch.as_tensor(np.ascontiguousarray(np.asarray(bc, dtype=np.float64)), device=diag.device)
+        _dev(bc, "bc")
+        if tuple(bc.shape) != (nc, 2):
+            raise ValueError(f"bc must be [nc, 2] = [{nc}, 2], got {list(bc.shape)}")
+    if multi:
+        # (not on the single entries: at 1e5 elements their call is bound by the host, and this loop is 2.6 us of it)
         for nm, t in (*zip(names, bands), ("bc", bc), ("out", out), ("work", work)):
             if t is not None and t.device != diag.device:
                 raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
         tail = (ne, nc, _ptr(bc), _ptr(out), _ptr(work), work.numel() * work.element_size())
+    else:
+        tail = (ne, float(ends[0]), float(ends[1]), _ptr(out), _ptr(work))
     rc = getattr(lib, entry)(*map(_ptr, bands), *tail, _stream(stream))
     _capi.check(rc, entry)
     return out[:nc] if multi else out

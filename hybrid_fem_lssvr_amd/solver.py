@@ -402,30 +402,35 @@ class FEMLSSVRPrimalSolver:
         return gd, (main_boundary_condition_left(self.global_domain[0]),
                     main_boundary_condition_right(self.global_domain[1]))
 
-    def _fem(self, rhs, u0, u1):
-        """(mesh, x device, u device, bands) of the P1 solve for the right-hand side ``rhs`` and the Dirichlet
-        values ``u0``, ``u1``; no attribute of the solver is written."""
-        dev = _device(self.device)
+    def _fem_setup(self):
+        """(mesh, x device, xq device, kw) of a P1 assembly: the nodes, the quadrature points and the coefficient
+        tables ``ops.p1_assemble`` takes as keywords, after the checks that make the unpivoted solve safe."""
         m = self._default_mesh() if self.mesh is None else self.mesh
-        x = _to_dev(m.nodes, dev)
+        x = _to_dev(m.nodes, _device(self.device))
+        xq = ops.quad_points(x, self.nquad)
         eq, kw = self._eq, {}
         if eq.a is not None:             # kloc = abar / h, abar the quadrature mean of a
-            kw["a_quad"] = _tabulate(eq.a, ops.quad_points(x, self.nquad))
+            kw["a_quad"] = _tabulate(eq.a, xq)
         if eq.c is not None:             # consistent mass matrix of c in the bands
-            cq = _tabulate(eq.c, ops.quad_points(x, self.nquad))
+            cq = _tabulate(eq.c, xq)
             if bool((cq < 0).any().item()):
                 raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
                                  "pivot and assumes an SPD matrix (c >= 0)")
             kw["c_quad"] = cq
         if eq.b is not None:             # b u' in the bands: sub and sup instead of off
-            kw["b_quad"] = self._convection_quad(eq, x)
+            kw["b_quad"] = self._convection_quad(eq, x, xq)
+        return m, x, xq, kw
+
+    def _fem(self, rhs, u0, u1):
+        """(mesh, x device, u device, bands) of the P1 solve for the right-hand side ``rhs`` and the Dirichlet
+        values ``u0``, ``u1``; no attribute of the solver is written."""
+        m, x, xq, kw = self._fem_setup()
         if isinstance(rhs, SinRHS):
             bands = ops.p1_assemble(x, self.nquad, rhs=(rhs.amp, rhs.omega), want_local=True, **kw)
         else:
-            xq = ops.quad_points(x, self.nquad)
-            fq = _to_dev(rhs(xq.cpu().numpy()), dev)
+            fq = _to_dev(rhs(xq.cpu().numpy()), x.device)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
-        if eq.b is not None:
+        if "b_quad" in kw:
             # no pivoting and no stabilisation: _convection_quad has checked the cell Peclet number
             u = ops.tridiag_ns_dirichlet_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], u0, u1)
         elif self.fem_solver == "flux":
@@ -453,21 +458,8 @@ class FEMLSSVRPrimalSolver:
                 _, x, u, _ = self._fem(f, float(u0), float(u1))
                 us.append(u)
             return x, torch.stack(us)
-        dev = _device(self.device)
-        m = self._default_mesh() if self.mesh is None else self.mesh
-        x = _to_dev(m.nodes, dev)
-        eq, kw = self._eq, {}
-        xq = ops.quad_points(x, self.nquad)
-        if eq.a is not None:
-            kw["a_quad"] = _tabulate(eq.a, xq)
-        if eq.c is not None:
-            cq = _tabulate(eq.c, xq)
-            if bool((cq < 0).any().item()):
-                raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
-                                 "pivot and assumes an SPD matrix (c >= 0)")
-            kw["c_quad"] = cq
-        if eq.b is not None:
-            kw["b_quad"] = self._convection_quad(eq, x)
+        _, x, xq, kw = self._fem_setup()
+        dev = x.device
         load = torch.empty((len(rhs_list), x.numel()), dtype=torch.float64, device=dev)
         tabulated = [j for j, f in enumerate(rhs_list) if not isinstance(f, SinRHS)]
         bands = None
@@ -491,17 +483,17 @@ class FEMLSSVRPrimalSolver:
             else:
                 load[torch.as_tensor(tabulated, device=dev)] = loads
         bc_dev = _to_dev(bc, dev)
-        if eq.b is not None:
+        if "b_quad" in kw:
             U = ops.tridiag_ns_dirichlet_solve_multi(bands["diag"], bands["sub"], bands["sup"], load, bc_dev)
         else:
             U = ops.tridiag_dirichlet_solve_multi(bands["diag"], bands["off"], load, bc_dev)
         return x, U
 
-    def _convection_quad(self, eq, x):
-        """b at the quadrature points [ne, nquad], after the check that makes the unpivoted, unstabilised solve safe:
+    def _convection_quad(self, eq, x, xq):
+        """b at the quadrature points ``xq`` [ne, nquad], after the check that makes the unpivoted, unstabilised solve safe:
         the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 on every element (bbar, abar: quadrature means).
         Host arithmetic on the tabulated values, before the assembly is launched."""
-        xq = ops.quad_points(x, self.nquad).cpu().numpy()
+        xq = xq.cpu().numpy()
         w = 0.5 * np.polynomial.legendre.leggauss(int(self.nquad))[1]
         bq = np.array(np.broadcast_to(np.asarray(eq.b(xq), dtype=np.float64), xq.shape))     # (a writable copy)
         abar = 1.0 if eq.a is None else np.broadcast_to(np.asarray(eq.a(xq), dtype=np.float64), xq.shape) @ w

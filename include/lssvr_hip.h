@@ -720,7 +720,8 @@ int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, cons
  * bit-identical: u[j][0] = bc_values[j][0], u[j][ne] = bc_values[j][1] and the interior of case j from load[j].
  * bc_values is a DEVICE array [nc][2] (NULL: zeros), the convention of lssvr_enhance_multi: nothing is read back and
  * no stream is synchronised, so the call can be captured in a graph.  The cases run 8
- * to a pass; in a pass the bands are read and the pivots of every level computed once.  work: device scratch of
+ * to a pass; in a pass the bands are read and the pivots of every level computed once (the single entry is the pass of
+ * one case of the same kernels, with its end values by value).  work: device scratch of
  * work_bytes >= lssvr_tridiag_multi_work_bytes(ne, nc) bytes; that value equals lssvr_tridiag_work_bytes(ne) at
  * nc = 1, grows with nc up to the 8 cases of one pass and with ne.  ne == 1 writes only the two end values of every
  * case.  Same no-pivoting rule as the single entry.

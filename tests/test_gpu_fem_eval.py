@@ -2,9 +2,12 @@
 P1 assembly (Dual.py:117-128), Dirichlet + tridiagonal solve (Dual.py:129-130),
 evaluate_solution (Dual.py:176-203), the variable-coefficient rows (BASELINE config 5)
 and the Python facade that mirrors the reference's call surface."""
+import functools
+
 import numpy as np
 import pytest
 
+import convection_rules as cr
 from oracle import lssvr_oracle as orc
 from oracle import closed_form_mp as cf
 
@@ -67,27 +70,72 @@ TRIDIAG_FORWARD_BAR = {1: 0.0, 2: 1e-15, 3: 1e-15, 24: 1e-14, 511: 2.5e-12, 512:
                        514: 2.5e-12, 1025: 4e-12, 16385: 2e-9, 100000: 7e-8, 1234567: 2e-6}
 
 
-def test_tridiag_caller_buffers(dev):
-    """Caller-supplied ``out`` and ``work`` at ne = 514 (one chunked level, a last chunk of one row): ``work`` of
-    exactly lssvr_tridiag_work_bytes(ne) is enough -- 64 guard doubles behind it keep their sentinel -- and the result
-    is bit-equal to the call that allocates both; an ``out`` of ne doubles is refused."""
+@functools.lru_cache(maxsize=None)
+def _buffer_case(ne, operator):
+    """(single entry, its sizer's name, the bands in the entry's order), computed once and shared: do not write to
+    the arrays.  "sym": the P1 Laplacian; "ns": -u'' + b u' + u with the cell Peclet number at 0.5."""
+    from hybrid_fem_lssvr_amd import ops
+    nodes = np.linspace(-1, 1, ne + 1)
+    if operator == "sym":
+        diag, off, load, _ = orc.p1_bands(nodes)
+        return ops.tridiag_dirichlet_solve, "lssvr_tridiag_work_bytes", (diag, off, load)
+    b = lambda x: 0.5 * ne + 0.0 * np.asarray(x, dtype=np.float64)          # noqa: E731  (|b| h / 2, h = 2 / ne)
+    diag, sub, sup, load, _ = cr.conv_bands(nodes, orc.poisson_rhs, None, b, lambda x: 1.0 + 0.0 * x)
+    return ops.tridiag_ns_dirichlet_solve, "lssvr_tridiag_ns_work_bytes", (diag, sub, sup, load)
+
+
+# 514: one chunked level, a last chunk of one row; 4105: two chunked levels
+@pytest.mark.parametrize("operator", ["sym", "ns"])
+@pytest.mark.parametrize("ne", [514, 4105])
+def test_tridiag_caller_buffers(dev, ne, operator):
+    """Caller-supplied ``out`` and ``work``: ``work`` of exactly lssvr_tridiag_work_bytes(ne) /
+    lssvr_tridiag_ns_work_bytes(ne) is enough -- 64 guard doubles behind it keep their sentinel -- and the result is
+    bit-equal to the call that allocates both; an ``out`` of ne doubles is refused."""
     import torch
-    from hybrid_fem_lssvr_amd import _capi, ops
-    ne = 514
-    diag, off, load, _ = orc.p1_bands(np.linspace(-1, 1, ne + 1))
-    d, o, l = _t(diag, dev), _t(off, dev), _t(load, dev)
-    u_ref = ops.tridiag_dirichlet_solve(d, o, l, 0.25, -0.5)
-    nbytes = _capi.load().lssvr_tridiag_work_bytes(ne)
+    from hybrid_fem_lssvr_amd import _capi
+    solve, sizer, bands = _buffer_case(ne, operator)
+    bands = [_t(b, dev) for b in bands]
+    u_ref = solve(*bands, 0.25, -0.5)
+    nbytes = getattr(_capi.load(), sizer)(ne)
     assert nbytes % 8 == 0
     sentinel = -7.25
     buf = torch.full((nbytes // 8 + 64,), sentinel, dtype=torch.float64, device=dev)
     out = torch.full((ne + 1,), sentinel, dtype=torch.float64, device=dev)
-    u = ops.tridiag_dirichlet_solve(d, o, l, 0.25, -0.5, out=out, work=buf[:nbytes // 8])
+    u = solve(*bands, 0.25, -0.5, out=out, work=buf[:nbytes // 8])
     assert u is out
     assert torch.equal(buf[nbytes // 8:], torch.full((64,), sentinel, dtype=torch.float64, device=dev))
     assert torch.equal(out, u_ref)
     with pytest.raises(ValueError, match="out must hold"):
-        ops.tridiag_dirichlet_solve(d, o, l, 0.25, -0.5, out=out[:ne])
+        solve(*bands, 0.25, -0.5, out=out[:ne])
+
+
+@pytest.mark.parametrize("operator", ["sym", "ns"])
+def test_tridiag_single_entry_in_a_graph(dev, operator):
+    """A single-RHS call with ``out`` and ``work`` given is captured in a hipGraph (as ops.StepGraph captures: after
+    a warm-up call, capture_error_mode="thread_local") and replayed once: the end values travel by value, so the
+    entry does nothing a capture forbids (no allocation, copy or synchronisation), and the replay has the bits of
+    the eager call with u[0], u[ne] exact.  ne = 4105: two chunked levels."""
+    import torch
+    from hybrid_fem_lssvr_amd import _capi
+    ne = 4105
+    solve, sizer, bands = _buffer_case(ne, operator)
+    bands = [_t(b, dev) for b in bands]
+    u_ref = solve(*bands, 0.25, -0.5)
+    work = torch.empty(getattr(_capi.load(), sizer)(ne) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(ne + 1, dtype=torch.float64, device=dev)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        solve(*bands, 0.25, -0.5, out=out, work=work)             # warm-up outside the capture
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        solve(*bands, 0.25, -0.5, out=out, work=work)
+    out.fill_(-7.25)
+    graph.replay()
+    torch.cuda.synchronize(dev)
+    assert torch.equal(out, u_ref)
+    assert out[0].item() == 0.25 and out[-1].item() == -0.5
 
 
 @pytest.mark.parametrize("ne", [1, 2, 3, 24, 2047, 2048, 2049, 100000, 1234567, 10000000])
