@@ -27,6 +27,8 @@ SOLVER_PRIMAL = 0
 SOLVER_DUAL = 1
 SOLVER_PRIMAL_WAVE = 2
 SOLVER_PRIMAL_MOMENT = 3
+END_DIRICHLET = 0
+END_ROBIN = 1
 ST_OK = 0
 ST_FALLBACK = 1
 
@@ -57,6 +59,7 @@ _SEQ = [_c_int, _c_hf]                               # repeats, kernel_ms_host[r
 _MESH = [_c_dp, _c_i64, _c_int]                      # x, ne, n_colloc / nquad / nq
 _SOLN = [_c_dp, _c_dp, _c_i64, _c_int]               # x, W, ne, M
 _EST_OUT = [_c_dp, _c_dp, _c_dp, _c_dp]              # eta2, jump, out3, work
+_ENDS = [_c_int, _c_int, _c_dp, _c_hd]                # kind_left, kind_right, end_values, kappa_host
 _STEP = _SHARD + [_c_hd, _c_int] + _BANDS + _OUT     # ..., rhs_params_host, nquad, bands, outputs
 
 
@@ -123,6 +126,12 @@ SIGNATURES = {
     "lssvr_tridiag_multi_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
     "lssvr_tridiag_dirichlet_solve_multi": _sig(_BANDS, [_c_i64, _c_int, _c_dp, _c_dp], _WS, _STREAM),
     "lssvr_tridiag_ns_dirichlet_solve_multi": _sig([_c_dp], _BANDS, [_c_i64, _c_int, _c_dp, _c_dp], _WS, _STREAM),
+    # Neumann / Robin ends (additive to ABI 7): ..., kind_left, kind_right, end_values, kappa_host, ne, nc, u, work
+    "lssvr_tridiag_bc_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
+    "lssvr_tridiag_bc_solve_multi": _sig(_BANDS, _ENDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
+    "lssvr_tridiag_ns_bc_solve_multi": _sig([_c_dp], _BANDS, _ENDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
+    "lssvr_estimate_ends": _sig([_c_dp, _c_dp, _c_int, _c_i64, _c_int, _c_int, _c_hd, _c_hd, _c_hd, _c_dp, _c_dp],
+                                _STREAM),
     # hp-adaptive refinement (additive to ABI 7)
     "lssvr_smoothness": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_dp], _STREAM),
     "lssvr_refine_hp": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dbl, _c_int, _c_int, _c_dp,

@@ -423,6 +423,49 @@ __global__ __launch_bounds__(kBlock) void estimate_finish_kernel(const double* _
   }
 }
 
+// The boundary term of the indicator at a Robin end a du/dn + kappa u = g, after an estimator
+// has written eta2 and out3: with the end element's row,
+//   J = g - kappa u_e(x_end) - a du_e/dn,   du_e/dn = -u_e'(x_0) at the left end, +u_e'(x_ne) at the right one,
+// eta2[e] += h_e/2 J^2, and out3 follows: sum += the added term, max = max(max, new eta2); a value that stops being
+// finite leaves the sum as it is and raises the non-finite count (one that was not finite is already counted).  One
+// thread does both ends one after the other -- ne == 1 has them in one element -- so there is no atomic and the
+// result is reproducible.  P_k(+-1) = (+-1)^k, P_k'(+-1) = (+-1)^(k+1) k(k+1)/2.
+__global__ void estimate_ends_kernel(EstimateEndsArgs p) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double sum = p.out3[0], mx = p.out3[1], cnt = p.out3[2];
+  for (int side = 0; side < 2; ++side) {
+    if (p.kind[side] != 1) continue;
+    const int64_t e = side ? p.ne - 1 : 0;
+    const double* c = p.W + e * p.M;
+    const DomainMap dm = map_params(p.x[e], p.x[e + 1]);
+    double val = 0.0, der = 0.0;
+    for (int k = 0; k < p.M; ++k) {
+      const double w = (double)(k * (k + 1) / 2);
+      const bool flip = side == 0 && (k & 1);          // (-1)^k at the left end
+      val = fma(c[k], flip ? -1.0 : 1.0, val);
+      der = fma(c[k], (side == 0 && !(k & 1)) ? -w : w, der);
+    }
+    der *= dm.scl;
+    const double dn = side ? der : -der;
+    const double J = p.g[side] - p.kappa[side] * val - p.a[side] * dn;
+    const double add = (0.5 * dm.oldlen) * (J * J);
+    const double old = p.eta2[e];
+    const double now = old + add;
+    p.eta2[e] = now;
+    if (fabs(old) < INFINITY) {
+      if (fabs(now) < INFINITY) {
+        sum += add;
+        mx = fmax(mx, now);
+      } else {
+        cnt += 1.0;
+      }
+    }
+  }
+  p.out3[0] = sum;
+  p.out3[1] = mx;
+  p.out3[2] = cnt;
+}
+
 __global__ __launch_bounds__(kBlock) void estimate_points_kernel(const double* __restrict__ x, int64_t ne,
                                                                   int nq, GaussRuleN g,
                                                                   double* __restrict__ xq) {
@@ -586,6 +629,12 @@ hipError_t estimate_react(EstimateReactArgs a, bool point_major, double* out3, h
     constexpr int MT = decltype(mt)::value;
     return point_major ? estimate_react_kernel<MT, true> : estimate_react_kernel<MT, false>;
   });
+}
+
+hipError_t estimate_ends(const EstimateEndsArgs& a, hipStream_t s) {
+  if (a.kind[0] != 1 && a.kind[1] != 1) return hipSuccess;       // two Dirichlet ends: nothing is added
+  hipLaunchKernelGGL(estimate_ends_kernel, dim3(1), dim3(1), 0, s, a);
+  return hipGetLastError();
 }
 
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,

@@ -862,6 +862,60 @@ int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub
   return tridiag_solve(diag, sub, sup, load, ne, nc, bc_values, 0.0, 0.0, u, work, work_bytes, stream, false, true);
 }
 
+// Free ends: Dirichlet or Robin at each end (tridiag.hip).  sup == NULL: the symmetric entry, `off` arrives as sub.
+int64_t lssvr_tridiag_bc_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_bc_work_bytes(ne, nc); }
+
+static int check_end_kinds(int kind_left, int kind_right, const double* kappa_host) {
+  if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
+      (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
+    return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
+                kind_right);
+  if (!kappa_host) return fail(LSSVR_ERR_NULL, "kappa_host must be non-NULL");
+  for (int i = 0; i < 2; ++i)
+    if ((i ? kind_right : kind_left) == LSSVR_END_ROBIN && !(kappa_host[i] >= 0.0 && kappa_host[i] < INFINITY))
+      return fail(LSSVR_ERR_SIZE, "kappa[%d] = %g must be finite and >= 0", i, kappa_host[i]);
+  return LSSVR_OK;
+}
+
+static int tridiag_bc_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                            int kind_left, int kind_right, const double* end_values, const double* kappa_host,
+                            int64_t ne, int nc, double* u, void* work, int64_t work_bytes, void* stream, bool sym) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
+  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
+    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
+  const int rc = check_end_kinds(kind_left, kind_right, kappa_host);
+  if (rc != LSSVR_OK) return rc;
+  const int64_t need = lssvr::tridiag_bc_work_bytes(ne, nc);
+  if (work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_bc_work_bytes(%lld, %d) = %lld",
+                (long long)work_bytes, (long long)ne, nc, (long long)need);
+  const bool f0 = kind_left == LSSVR_END_ROBIN, f1 = kind_right == LSSVR_END_ROBIN;
+  const double k0 = f0 ? kappa_host[0] : 0.0, k1 = f1 ? kappa_host[1] : 0.0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (sym)
+    return check_launch(lssvr::tridiag_bc_solve(diag, sub, load, ne, nc, f0, f1, k0, k1, end_values, u, work, st),
+                        "tridiag_bc_solve_multi");
+  return check_launch(lssvr::tridiag_ns_bc_solve(diag, sub, sup, load, ne, nc, f0, f1, k0, k1, end_values, u, work,
+                                                 st),
+                      "tridiag_ns_bc_solve_multi");
+}
+
+int lssvr_tridiag_bc_solve_multi(const double* diag, const double* off, const double* load, int kind_left,
+                                 int kind_right, const double* end_values, const double* kappa_host, int64_t ne,
+                                 int nc, double* u, void* work, int64_t work_bytes, void* stream) {
+  return tridiag_bc_solve(diag, off, nullptr, load, kind_left, kind_right, end_values, kappa_host, ne, nc, u, work,
+                          work_bytes, stream, true);
+}
+
+int lssvr_tridiag_ns_bc_solve_multi(const double* diag, const double* sub, const double* sup, const double* load,
+                                    int kind_left, int kind_right, const double* end_values,
+                                    const double* kappa_host, int64_t ne, int nc, double* u, void* work,
+                                    int64_t work_bytes, void* stream) {
+  return tridiag_bc_solve(diag, sub, sup, load, kind_left, kind_right, end_values, kappa_host, ne, nc, u, work,
+                          work_bytes, stream, false);
+}
+
 int64_t lssvr_p1_flux_work_bytes(int64_t ne) { return lssvr::flux_work_bytes(ne); }
 
 int lssvr_p1_flux_solve(const double* kloc, const double* load, int64_t ne, double u0, double u1,
@@ -995,6 +1049,33 @@ int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, in
   return check_launch(lssvr::estimate_react(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,
                                             reinterpret_cast<hipStream_t>(stream)),
                       "estimate_react");
+}
+
+int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int kind_left, int kind_right,
+                        const double* kappa_host, const double* g_host, const double* a_ends_host, double* eta2,
+                        double* out3, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
+  if (!x || !W || !eta2 || !out3) return fail(LSSVR_ERR_NULL, "x, W, eta2, out3 must be non-NULL");
+  const int rc = check_end_kinds(kind_left, kind_right, kappa_host);
+  if (rc != LSSVR_OK) return rc;
+  if (!g_host || !a_ends_host) return fail(LSSVR_ERR_NULL, "g_host and a_ends_host must be non-NULL");
+  lssvr::EstimateEndsArgs a{};
+  a.x = x;
+  a.W = W;
+  a.ne = ne;
+  a.M = M;
+  a.kind[0] = kind_left;
+  a.kind[1] = kind_right;
+  for (int i = 0; i < 2; ++i) {
+    a.kappa[i] = a.kind[i] == LSSVR_END_ROBIN ? kappa_host[i] : 0.0;
+    a.g[i] = g_host[i];
+    a.a[i] = a_ends_host[i];
+  }
+  a.eta2 = eta2;
+  a.out3 = out3;
+  return check_launch(lssvr::estimate_ends(a, reinterpret_cast<hipStream_t>(stream)), "estimate_ends");
 }
 
 int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev, double theta,

@@ -196,6 +196,16 @@ hipError_t tridiag_dirichlet_solve(const double* diag, const double* off, const 
 hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                       int64_t ne, int nc, const double* bc, double u0, double u1, double* u,
                                       void* work, hipStream_t s);
+// The same solves with free ends: f0 / f1 make node 0 / node ne an unknown whose row gets k0 /
+// k1 on the diagonal and bc[q][0] / bc[q][1] on the right-hand side, inside the kernels (a Robin end a du/dn +
+// kappa u = g); an end that is not free is a Dirichlet end with the value bc[q][.].  bc NULL: zeros.  The bands are
+// read only.  tridiag_bc_work_bytes is sized for two free ends.
+int64_t tridiag_bc_work_bytes(int64_t ne, int nc);
+hipError_t tridiag_bc_solve(const double* diag, const double* off, const double* load, int64_t ne, int nc, bool f0,
+                            bool f1, double k0, double k1, const double* bc, double* u, void* work, hipStream_t s);
+hipError_t tridiag_ns_bc_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                               int64_t ne, int nc, bool f0, bool f1, double k0, double k1, const double* bc,
+                               double* u, void* work, hipStream_t s);
 // fem_eval.hip: the load of p1_assemble / _react / _conv for nc tabulated right-hand sides rhs_quad[nc][ne*nquad] ->
 // load[nc][ne+1], no bands
 hipError_t p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,
@@ -255,6 +265,18 @@ hipError_t estimate_points(const double* x, int64_t ne, int nq, double* xq, hipS
 hipError_t estimate(EstimateArgs a, int rhs_mode, double* out3, hipStream_t s);
 hipError_t estimate_varcoef(EstimateVcArgs a, bool point_major, double* out3, hipStream_t s);
 hipError_t estimate_react(EstimateReactArgs a, bool point_major, double* out3, hipStream_t s);
+// the boundary term of a Robin end, added to eta2 and out3 after any of the three estimators (adapt.hip)
+struct EstimateEndsArgs {
+  const double* x;
+  const double* W;
+  int64_t ne;
+  int M;
+  int kind[2];                      // 0 Dirichlet (nothing added), 1 Robin
+  double kappa[2], g[2], a[2];      // per end; a = the coefficient a at x_0 and x_ne
+  double* eta2;
+  double* out3;
+};
+hipError_t estimate_ends(const EstimateEndsArgs& a, hipStream_t s);
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                   double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s);
 

@@ -24,6 +24,13 @@
 // case -- every call of the single-RHS entries is one -- runs the NC = 1 instantiation.  The operations of a case
 // and their order do not depend on NC (the build has -ffp-contract=off, so a product and a sum are never fused unless
 // the source says fma()), so row q of a multi call has the bits of the single entry on case q.
+//
+// Free ends.  A Robin end a du/dn + kappa u = g keeps its end node as an unknown: the system
+// then starts at node 0 (ends at node ne), that row has no known neighbour (bl / br NULL), and the kernels add kappa
+// to its diagonal and g to its right-hand side where they read them -- the caller's bands are never written.  The
+// kernels are templates on the type of their cases: TriCases is the Dirichlet text, unchanged, TriCasesFree adds the
+// two end terms; the reduced levels of either are TriCases.  With both ends Dirichlet the TriCasesFree instantiation
+// performs the operations of the TriCases one, bit for bit.
 #include "lssvr_device.hpp"
 #include "lssvr_kernels.hpp"
 
@@ -62,6 +69,14 @@ struct TriCases {
   int nlive;
 };
 
+// TriCases whose first (f0) / last (f1) row is the row of a free end node: the kernels add k0 / k1 to its diagonal
+// and the end value of the case (g of the Robin condition) to its right-hand side; s.bl / s.br is NULL there.  An end
+// that is not free is a Dirichlet end as in TriCases.
+struct TriCasesFree : TriCases {
+  double k0, k1;
+  int f0, f1;
+};
+
 __device__ __forceinline__ double lo_at(const TriSys& s, int64_t i) { return i == 0 ? 0.0 : s.lo[i]; }
 __device__ __forceinline__ double up_at(const TriSys& s, int64_t i) { return i == s.m - 1 ? 0.0 : s.up[i]; }
 template <int NC>
@@ -77,6 +92,20 @@ __device__ __forceinline__ double r_at(const TriCases& tc, int c, int64_t i) {
   double v = s.r[c * tc.rs + i];
   if (i == 0 && s.bl) v -= s.bl[0] * (tc.bc ? tc.bc[2 * c] : s.u0);
   if (i == s.m - 1 && s.br) v -= s.br[0] * (tc.bc ? tc.bc[2 * c + 1] : s.u1);
+  return v;
+}
+__device__ __forceinline__ double r_at(const TriCasesFree& tc, int c, int64_t i) {
+  double v = r_at(static_cast<const TriCases&>(tc), c, i);
+  if (i == 0 && tc.f0) v += tc.bc ? tc.bc[2 * c] : tc.s.u0;
+  if (i == tc.s.m - 1 && tc.f1) v += tc.bc ? tc.bc[2 * c + 1] : tc.s.u1;
+  return v;
+}
+// the diagonal of row i
+__device__ __forceinline__ double d_at(const TriCases& tc, int64_t i) { return tc.s.d[i]; }
+__device__ __forceinline__ double d_at(const TriCasesFree& tc, int64_t i) {
+  double v = tc.s.d[i];
+  if (i == 0 && tc.f0) v += tc.k0;
+  if (i == tc.s.m - 1 && tc.f1) v += tc.k1;
   return v;
 }
 
@@ -99,18 +128,21 @@ struct ChunkRows {
 };
 
 // rows b .. b+kLc-2 clipped to [b, e): entries outside are a copy of row b and are never used
-__device__ __forceinline__ void load_rows(const TriSys& s, int64_t b, int64_t e, ChunkRows& rb) {
+template <typename TC>
+__device__ __forceinline__ void load_rows(const TC& tc, int64_t b, int64_t e, ChunkRows& rb) {
+  const TriSys& s = tc.s;
 #pragma unroll
   for (int t = 0; t < kLc - 1; ++t) {
     const int64_t i = (b + t < e) ? b + t : b;
     rb.lo[t] = lo_at(s, i);
-    rb.d[t] = s.d[i];
+    rb.d[t] = d_at(tc, i);
     rb.up[t] = up_at(s, i);
   }
 }
 
 // the right-hand sides of those rows for case c: the kLc-1 values back to back
-__device__ __forceinline__ void load_case_rows(const TriCases& tc, int c, int64_t b, int64_t e,
+template <typename TC>
+__device__ __forceinline__ void load_case_rows(const TC& tc, int c, int64_t b, int64_t e,
                                                double (&r)[kLc - 1]) {
 #pragma unroll
   for (int t = 0; t < kLc - 1; ++t) r[t] = r_at(tc, c, (b + t < e) ? b + t : b);
@@ -118,8 +150,8 @@ __device__ __forceinline__ void load_case_rows(const TriCases& tc, int c, int64_
 
 // chunk j: interior unknowns [j*kLc, min(j*kLc + kLc-1, m)), never empty for j < nc = ceil(m / kLc); es[nc] once,
 // ec[nlive][nc] per case
-template <int NC>
-__global__ __launch_bounds__(kBlock) void tri_condense_kernel(TriCases tc, int64_t nc,
+template <int NC, typename TC>
+__global__ __launch_bounds__(kBlock) void tri_condense_kernel(TC tc, int64_t nc,
                                                               ChunkEndsShared* __restrict__ es,
                                                               ChunkEndsCase* __restrict__ ec) {
   const TriSys& s = tc.s;
@@ -129,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void tri_condense_kernel(TriCases tc, int64
   const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
   const int len = (int)(e - b);
   ChunkRows rb;
-  load_rows(s, b, e, rb);
+  load_rows(tc, b, e, rb);
   double dd[kLc - 1], du[kLc - 1];       // 1/den of the downward and of the upward sweep
   ChunkEndsShared c;
   {  // downward sweep -> values at the last interior unknown; one division per row (1/den), three multiplications
@@ -195,8 +227,8 @@ __global__ __launch_bounds__(kBlock) void tri_condense_kernel(TriCases tc, int64
 
 // separator j sits at p = j*kLc + kLc-1 < m (j < ns = m / kLc), between chunk j (left) and chunk j+1 (right): one LO,
 // D, UP [ns], R[nlive][ns]
-template <int NC>
-__global__ __launch_bounds__(kBlock) void tri_reduce_kernel(TriCases tc, int64_t ns, int64_t nc,
+template <int NC, typename TC>
+__global__ __launch_bounds__(kBlock) void tri_reduce_kernel(TC tc, int64_t ns, int64_t nc,
                                                             const ChunkEndsShared* __restrict__ es,
                                                             const ChunkEndsCase* __restrict__ ec,
                                                             double* __restrict__ LO, double* __restrict__ D,
@@ -209,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void tri_reduce_kernel(TriCases tc, int64_t
   const double u = up_at(s, p);
   const bool right = j + 1 < nc;
   const ChunkEndsShared cl = es[j];
-  double dd = s.d[p] + l * cl.wL;
+  double dd = d_at(tc, p) + l * cl.wL;
   double uu = 0.0;
   if (right) {
     const ChunkEndsShared cr = es[j + 1];
@@ -230,8 +262,8 @@ __global__ __launch_bounds__(kBlock) void tri_reduce_kernel(TriCases tc, int64_t
 
 // re-solve every chunk with its separator values X[nlive][ns] known; x + q*xs (length m) receives the whole level's
 // solution of case q
-template <int NC>
-__global__ __launch_bounds__(kBlock) void tri_expand_kernel(TriCases tc, int64_t ns, int64_t nc,
+template <int NC, typename TC>
+__global__ __launch_bounds__(kBlock) void tri_expand_kernel(TC tc, int64_t ns, int64_t nc,
                                                             const double* __restrict__ X, double* __restrict__ x,
                                                             int64_t xs) {
   const TriSys& s = tc.s;
@@ -241,7 +273,7 @@ __global__ __launch_bounds__(kBlock) void tri_expand_kernel(TriCases tc, int64_t
   const int64_t e = (b + kLc - 1 < s.m) ? b + kLc - 1 : s.m;
   const int len = (int)(e - b);
   ChunkRows rb;
-  load_rows(s, b, e, rb);
+  load_rows(tc, b, e, rb);
   // the factorisation of the chunk, once: 1/den and the modified upper band of every row stay in registers (kLc-1 = 7
   // of each), so the back substitution of a case touches memory only to store the solution
   double cc[kLc - 1], dn[kLc - 1];
@@ -344,8 +376,8 @@ __device__ __forceinline__ void tri_pcr(double li, double di, double ui, const d
 // P1 Laplacian the residual came out at 1.15 times the rounding-level bar the chunked levels meet with room to
 // spare (measured on an MI355X).  The correction costs a second reduction of one workgroup, a
 // few microseconds.  The symmetric entry does without it: the step would change its bits and its time.
-template <int NC, bool kRefine>
-__global__ __launch_bounds__(kBase) void tri_base_kernel(TriCases tc, double* __restrict__ x, int64_t xs) {
+template <int NC, bool kRefine, typename TC>
+__global__ __launch_bounds__(kBase) void tri_base_kernel(TC tc, double* __restrict__ x, int64_t xs) {
   const TriSys& s = tc.s;
   __shared__ double lo[kBase], d[kBase], up[kBase], r[NC][kBase];
   const int i = threadIdx.x;
@@ -356,7 +388,7 @@ __global__ __launch_bounds__(kBase) void tri_base_kernel(TriCases tc, double* __
   for (int q = 0; q < NC; ++q) ri[q] = 0.0;
   if (in) {
     li = lo_at(s, i);
-    di = s.d[i];
+    di = d_at(tc, i);
     ui = up_at(s, i);
 #pragma unroll
     for (int q = 0; q < NC; ++q) ri[q] = r_at(tc, case_of<NC>(tc, q), i);
@@ -398,6 +430,15 @@ __global__ void tri_ends_kernel(double* u, int64_t ne, int nc, const double* bc,
   u[q * (ne + 1) + ne] = bc ? bc[2 * q + 1] : u1;
 }
 
+// the same for a solve with free ends: only a Dirichlet end (f0 / f1 zero) has its value written, a free end is an
+// unknown of the solve (bc NULL: zeros)
+__global__ void tri_free_ends_kernel(double* u, int64_t ne, int nc, const double* bc, int f0, int f1) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nc) return;
+  if (!f0) u[q * (ne + 1)] = bc ? bc[2 * q] : 0.0;
+  if (!f1) u[q * (ne + 1) + ne] = bc ? bc[2 * q + 1] : 0.0;
+}
+
 // workspace (in doubles) of the levels above the base with K cases in a pass: es[4*nc] + ec[K][2*nc] + LO, D, UP
 // [3*ns] + R, X [K][2*ns]
 int64_t level_doubles(int64_t m, int64_t K) {
@@ -410,13 +451,14 @@ int64_t level_doubles(int64_t m, int64_t K) {
   return tot + 16;
 }
 
-// one level for the NC slots of a pass: case q's solution of this level at x + q*xs
-template <int NC, bool kRefine>
-hipError_t solve_level(const TriCases& tc, double* x, int64_t xs, double* work, hipStream_t st) {
+// one level for the NC slots of a pass: case q's solution of this level at x + q*xs (TC: TriCases, or TriCasesFree at
+// the top level of a solve with free ends; the reduced system of either is a TriCases)
+template <int NC, bool kRefine, typename TC>
+hipError_t solve_level(const TC& tc, double* x, int64_t xs, double* work, hipStream_t st) {
   const TriSys& s = tc.s;
   if (s.m <= 0) return hipSuccess;
   if (s.m <= kBase) {
-    hipLaunchKernelGGL((tri_base_kernel<NC, kRefine>), dim3(1), dim3((unsigned)kBase), 0, st, tc, x, xs);
+    hipLaunchKernelGGL((tri_base_kernel<NC, kRefine, TC>), dim3(1), dim3((unsigned)kBase), 0, st, tc, x, xs);
     return hipGetLastError();
   }
   const int64_t nc = (s.m + kLc - 1) / kLc, ns = s.m / kLc;
@@ -433,37 +475,70 @@ hipError_t solve_level(const TriCases& tc, double* x, int64_t xs, double* work, 
   double* next = X + K * ns + 16;
   const unsigned gc = (unsigned)((nc + kBlock - 1) / kBlock);
   const unsigned gs = (unsigned)((ns + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(tri_condense_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, tc, nc, es, ec);
-  hipLaunchKernelGGL(tri_reduce_kernel<NC>, dim3(gs), dim3(kBlock), 0, st, tc, ns, nc, es, ec, LO, D, UP, R);
+  hipLaunchKernelGGL((tri_condense_kernel<NC, TC>), dim3(gc), dim3(kBlock), 0, st, tc, nc, es, ec);
+  hipLaunchKernelGGL((tri_reduce_kernel<NC, TC>), dim3(gs), dim3(kBlock), 0, st, tc, ns, nc, es, ec, LO, D, UP, R);
   const TriCases red{TriSys{LO, D, UP, R, nullptr, nullptr, 0.0, 0.0, ns}, ns, nullptr, tc.nlive};
   const hipError_t err = solve_level<NC, kRefine>(red, X, ns, next, st);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(tri_expand_kernel<NC>, dim3(gc), dim3(kBlock), 0, st, tc, ns, nc, X, x, xs);
+  hipLaunchKernelGGL((tri_expand_kernel<NC, TC>), dim3(gc), dim3(kBlock), 0, st, tc, ns, nc, X, x, xs);
   return hipGetLastError();
 }
 
+// The unknowns of `all` (its s, its stride, the end values of case 0; nlive is set here) for the nc cases that follow
+// s.r at that stride, kTriMultiCases to a pass, into x + q*stride; the passes reuse the one workspace in stream order.
+// A pass of one case runs the NC = 1 instantiation, a pass of 2 .. kTriMultiCases cases the NC = kTriMultiCases one.
+template <bool kRefine, typename TC>
+hipError_t solve_passes(const TC& all, int nc, double* x, void* work, hipStream_t st) {
+  const int64_t stride = all.rs;
+  for (int q0 = 0; q0 < nc; q0 += kTriMultiCases) {
+    TC tc = all;
+    tc.nlive = nc - q0 < kTriMultiCases ? nc - q0 : kTriMultiCases;
+    if (tc.bc) tc.bc += 2 * (int64_t)q0;
+    tc.s.r += q0 * stride;
+    double* xq = x + q0 * stride;
+    const hipError_t err =
+        tc.nlive == 1 ? solve_level<1, kRefine>(tc, xq, stride, reinterpret_cast<double*>(work), st)
+                      : solve_level<kTriMultiCases, kRefine>(tc, xq, stride, reinterpret_cast<double*>(work), st);
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
 // u[q][0], u[q][ne] = the end values of case q, then the ne-1 interior unknowns of s into u[q][1 ..], for the nc
-// cases that follow s.r at a stride of ne+1, kTriMultiCases to a pass; the passes reuse the one workspace in stream
-// order.  A pass of one case runs the NC = 1 instantiation, a pass of 2 .. kTriMultiCases cases the
-// NC = kTriMultiCases one.  The end values are bc[nc][2] on the device or, with bc NULL, s.u0 and s.u1 for every case.
+// cases that follow s.r at a stride of ne+1.  The end values are bc[nc][2] on the device or, with bc NULL, s.u0 and
+// s.u1 for every case.
 template <bool kRefine>
 hipError_t dirichlet_solve(const TriSys& s, int64_t ne, int nc, const double* bc, double* u, void* work,
                            hipStream_t st) {
   hipLaunchKernelGGL(tri_ends_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, u, ne, nc, bc, s.u0, s.u1);
   if (s.m <= 0) return hipGetLastError();
-  const int64_t stride = ne + 1;
-  for (int q0 = 0; q0 < nc; q0 += kTriMultiCases) {
-    const int nlive = nc - q0 < kTriMultiCases ? nc - q0 : kTriMultiCases;
-    TriCases tc{s, stride, bc ? bc + 2 * (int64_t)q0 : nullptr, nlive};
-    tc.s.r += q0 * stride;
-    double* x = u + q0 * stride + 1;
-    const hipError_t err = nlive == 1
-                               ? solve_level<1, kRefine>(tc, x, stride, reinterpret_cast<double*>(work), st)
-                               : solve_level<kTriMultiCases, kRefine>(tc, x, stride,
-                                                                      reinterpret_cast<double*>(work), st);
-    if (err != hipSuccess) return err;
-  }
-  return hipSuccess;
+  return solve_passes<kRefine>(TriCases{s, ne + 1, bc, 0}, nc, u + 1, work, st);
+}
+
+// The solve with free ends on the bands diag[ne+1], lo[ne], up[ne] (lo[i]: u_i in row i+1, up[i]: u_{i+1} in row i)
+// and load[nc][ne+1]: unknown k is node k + sh, sh = 0 with a free left end and 1 with a Dirichlet one, so the band
+// pointers are shifted by sh (lo by sh - 1: lo_at never reads entry 0 of a system) and there are ne - 1 + f0 + f1
+// unknowns -- at least one unless ne == 1 with two Dirichlet ends.  A Dirichlet end hands its neighbour's row
+// lo[0] * value (up[ne-1] * value) as in dirichlet_solve and has its value written by tri_free_ends_kernel.
+template <bool kRefine>
+hipError_t free_solve(const double* diag, const double* lo, const double* up, const double* load, int64_t ne, int nc,
+                      bool f0, bool f1, double k0, double k1, const double* bc, double* u, void* work,
+                      hipStream_t st) {
+  if (!f0 || !f1)
+    hipLaunchKernelGGL(tri_free_ends_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, u, ne, nc, bc,
+                       (int)f0, (int)f1);
+  const int sh = f0 ? 0 : 1;
+  const int64_t m = ne - 1 + (f0 ? 1 : 0) + (f1 ? 1 : 0);
+  if (m <= 0) return hipGetLastError();
+  const TriSys s{lo + sh - 1, diag + sh, up + sh, load + sh, f0 ? nullptr : lo, f1 ? nullptr : up + (ne - 1),
+                 0.0,         0.0,       m};
+  TriCasesFree all{};
+  static_cast<TriCases&>(all) = TriCases{s, ne + 1, bc, 0};
+  all.k0 = k0;
+  all.k1 = k1;
+  all.f0 = f0;
+  all.f1 = f1;
+  return solve_passes<kRefine>(all, nc, u + sh, work, st);
 }
 
 }  // namespace
@@ -475,6 +550,11 @@ int64_t tridiag_multi_work_bytes(int64_t ne, int nc) {
 }
 
 int64_t tridiag_work_bytes(int64_t ne) { return tridiag_multi_work_bytes(ne, 1); }
+
+// sized for two free ends, ne + 1 unknowns, whatever the kinds of a call are
+int64_t tridiag_bc_work_bytes(int64_t ne, int nc) {
+  return 8 * level_doubles(ne + 1, nc < kTriMultiCases ? (nc > 1 ? nc : 1) : kTriMultiCases) + 256;
+}
 
 // interior unknown k <-> node k+1: lo = off[k] (u_k in row k+1), d = diag[k+1], up = off[k+1], r = load[k+1]; the end
 // rows lose off[0] * u[0] and off[ne-1] * u[ne] to the right-hand side
@@ -490,6 +570,18 @@ hipError_t tridiag_ns_dirichlet_solve(const double* diag, const double* sub, con
                                       void* work, hipStream_t st) {
   const TriSys s{sub, diag + 1, sup + 1, load + 1, sub, sup + (ne - 1), u0, u1, ne - 1};
   return dirichlet_solve<true>(s, ne, nc, bc, u, work, st);
+}
+
+// free ends: the symmetric bands (lo = up = off) and the non-symmetric ones
+hipError_t tridiag_bc_solve(const double* diag, const double* off, const double* load, int64_t ne, int nc, bool f0,
+                            bool f1, double k0, double k1, const double* bc, double* u, void* work, hipStream_t st) {
+  return free_solve<false>(diag, off, off, load, ne, nc, f0, f1, k0, k1, bc, u, work, st);
+}
+
+hipError_t tridiag_ns_bc_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                               int64_t ne, int nc, bool f0, bool f1, double k0, double k1, const double* bc,
+                               double* u, void* work, hipStream_t st) {
+  return free_solve<true>(diag, sub, sup, load, ne, nc, f0, f1, k0, k1, bc, u, work, st);
 }
 
 }  // namespace lssvr

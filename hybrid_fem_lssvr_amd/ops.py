@@ -792,6 +792,120 @@ def tridiag_ns_dirichlet_solve_multi(diag, sub, sup, load, bc=None, *, out=None,
                           "sup, load)", bc, out, work, stream, multi=True)
 
 
+END_DIRICHLET, END_ROBIN = _capi.END_DIRICHLET, _capi.END_ROBIN      # LSSVR_END_*: the kind of one end of the domain
+
+
+def _end_kinds(end_kinds, kappa):
+    """((kind_left, kind_right), host double[2] kappa) of a call with free ends: kinds in {0, 1}, kappa finite and
+    >= 0 (``ValueError`` otherwise; read at a Robin end only, but checked at both)."""
+    try:
+        kinds = tuple(end_kinds)
+        kap = tuple(float(k) for k in kappa)
+    except TypeError:
+        raise TypeError("end_kinds and kappa must be pairs (left, right)") from None
+    if len(kinds) != 2 or len(kap) != 2:
+        raise ValueError("end_kinds and kappa must be pairs (left, right)")
+    if any(isinstance(k, bool) or k not in (END_DIRICHLET, END_ROBIN) for k in kinds):
+        raise ValueError(f"end_kinds must be END_DIRICHLET (0) or END_ROBIN (1), got {kinds!r}")
+    if not all(math.isfinite(k) and k >= 0.0 for k in kap):
+        raise ValueError(f"kappa must be finite and >= 0, got {kap!r}")
+    return (int(kinds[0]), int(kinds[1])), (ctypes.c_double * 2)(*kap)
+
+
+def _tridiag_bc_solve(entry, names, bands, lengths, end_kinds, kappa, end_values, out, work, stream, multi):
+    """The ``*_bc_solve_multi`` entry on ``bands`` (``names`` in its order) -> u[nc, ne+1], or u[ne+1] for the single
+    form (``multi`` False: load [ne+1], ``end_values`` a host pair)."""
+    lib = _capi.load()
+    for nm, t in zip(names, bands):
+        _dev(t, nm)
+    diag, load = bands[0], bands[-1]
+    ne = bands[1].numel()
+    if not multi:
+        if load.dim() != 1:
+            raise ValueError(lengths)
+        load = load.unsqueeze(0)
+    if (diag.numel() != ne + 1 or bands[-2].numel() != ne or load.dim() != 2 or load.shape[1] != ne + 1):
+        raise ValueError(lengths)
+    if ne < 1:
+        raise ValueError("need at least one element")
+    nc = int(load.shape[0])
+    if nc < 1:
+        raise ValueError("need at least one case")
+    kinds, kap = _end_kinds(end_kinds, kappa)
+    if out is None:
+        out = torch.empty((nc, ne + 1), dtype=torch.float64, device=diag.device)
+    else:
+        _dev(out, "out")
+        if not multi:
+            if out.numel() != ne + 1:
+                raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
+            out = out.view(1, ne + 1)
+        elif out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc:
+            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
+    need = lib.lssvr_tridiag_bc_work_bytes(ne, nc)
+    if work is not None:
+        _dev(work, "work")
+        if multi and work.numel() * work.element_size() < need:
+            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                             f"lssvr_tridiag_bc_work_bytes({ne}, {nc}) = {need}")
+    work = _scratch(work, need, diag.device)
+    ev = end_values
+    if ev is not None:
+        if not isinstance(ev, torch.Tensor):
+            ev = np.asarray(ev, dtype=np.float64)
+            ev = torch.as_tensor(np.ascontiguousarray(ev if multi else ev.reshape(-1, 2)), device=diag.device)
+        _dev(ev, "end_values")
+        if tuple(ev.shape) != (nc, 2):
+            raise ValueError(f"end_values must be [nc, 2] = [{nc}, 2], got {list(ev.shape)}")
+    for nm, t in (*zip(names, bands), ("end_values", ev), ("out", out), ("work", work)):
+        if t is not None and t.device != diag.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
+    rc = getattr(lib, entry)(*map(_ptr, bands), kinds[0], kinds[1], _ptr(ev), kap, ne, nc, _ptr(out), _ptr(work),
+                             work.numel() * work.element_size(), _stream(stream))
+    _capi.check(rc, entry)
+    return out[:nc] if multi else out[0]
+
+
+def tridiag_bc_solve_multi(diag, off, load, end_kinds, kappa, end_values=None, *, out=None, work=None, stream=None):
+    """:func:`tridiag_dirichlet_solve_multi` with a Dirichlet or a Robin condition at each end
+    (``lssvr_tridiag_bc_solve_multi``).  ``end_kinds`` = (left, right), each ``END_DIRICHLET`` or ``END_ROBIN``;
+    ``kappa`` = (left, right), finite and >= 0, read at a Robin end (Neumann: 0); ``end_values`` float64[nc, 2] (a
+    device tensor, or an array-like that is copied to the device; ``None``: zeros): g of case j at a Robin end
+    ``a du/dn + kappa u = g`` (outward normal), the value itself at a Dirichlet end.  kappa and g join the end row
+    inside the kernels; ``diag``, ``off`` and ``load`` are left as they are.  Row j is bit-identical to the call with
+    that case alone, and two Dirichlet ends give the bits of :func:`tridiag_dirichlet_solve_multi`.  ``work``: at
+    least ``lssvr_tridiag_bc_work_bytes(ne, nc)`` bytes (``ValueError`` otherwise)."""
+    return _tridiag_bc_solve("lssvr_tridiag_bc_solve_multi", ("diag", "off", "load"), (diag, off, load),
+                             "band lengths must be ne+1, ne and load [nc, ne+1]", end_kinds, kappa, end_values, out,
+                             work, stream, True)
+
+
+def tridiag_bc_solve(diag, off, load, end_kinds, kappa, end_values=(0.0, 0.0), *, out=None, work=None, stream=None):
+    """One right-hand side of :func:`tridiag_bc_solve_multi` (the nc = 1 call of the same entry): load float64[ne+1],
+    ``end_values`` a pair (left, right) -> u[ne+1]."""
+    return _tridiag_bc_solve("lssvr_tridiag_bc_solve_multi", ("diag", "off", "load"), (diag, off, load),
+                             "band lengths must be ne+1, ne, ne+1", end_kinds, kappa, end_values, out, work, stream,
+                             False)
+
+
+def tridiag_ns_bc_solve_multi(diag, sub, sup, load, end_kinds, kappa, end_values=None, *, out=None, work=None,
+                              stream=None):
+    """:func:`tridiag_bc_solve_multi` for the non-symmetric bands (``lssvr_tridiag_ns_bc_solve_multi``); two Dirichlet
+    ends give the bits of :func:`tridiag_ns_dirichlet_solve_multi`.  No pivoting: at a Robin end the row is dominant
+    when kappa + b(x_end) n / 2 >= 0 (n = -1 left, +1 right)."""
+    return _tridiag_bc_solve("lssvr_tridiag_ns_bc_solve_multi", ("diag", "sub", "sup", "load"),
+                             (diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] (diag, "
+                             "sub, sup, load)", end_kinds, kappa, end_values, out, work, stream, True)
+
+
+def tridiag_ns_bc_solve(diag, sub, sup, load, end_kinds, kappa, end_values=(0.0, 0.0), *, out=None, work=None,
+                        stream=None):
+    """One right-hand side of :func:`tridiag_ns_bc_solve_multi` (the nc = 1 call of the same entry)."""
+    return _tridiag_bc_solve("lssvr_tridiag_ns_bc_solve_multi", ("diag", "sub", "sup", "load"),
+                             (diag, sub, sup, load), "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)",
+                             end_kinds, kappa, end_values, out, work, stream, False)
+
+
 def p1_load_multi(x, rhs_quad, nquad=2, *, out=None, stream=None):
     """The ``load`` of :func:`p1_assemble` for ``nc`` tabulated right-hand sides in one launch
     (``lssvr_p1_load_multi``): rhs_quad float64[nc, ne, nquad] (f at :func:`quad_points`, case by case) ->
@@ -1026,6 +1140,41 @@ def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point
                             _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work), _stream(stream))
     _capi.check(rc, name)
     return eta2, jump, out3
+
+
+def estimate_ends(x, W, end_kinds, kappa, g, a_ends, eta2, out3, *, stream=None):
+    """The boundary term of the indicator at Robin ends (``lssvr_estimate_ends``), IN PLACE on the ``eta2`` [ne] and
+    ``out3`` [3] that :func:`estimate` or :func:`estimate_varcoef` returned: at a Robin end
+    J = g - kappa u_e(x_end) - a du_e/dn from the end element's row of ``W`` [ne, M], eta2[end element] += h/2 J^2,
+    out3 = {sum + the added terms, max with the new values, non-finite count + 1 for a value that stops being
+    finite}.  ``end_kinds``, ``kappa``: as in :func:`tridiag_bc_solve_multi`; ``g`` = (left, right); ``a_ends`` =
+    (a(x_0), a(x_ne)).  A Dirichlet end adds nothing.  Returns (eta2, out3)."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(W, "W")
+    _dev(eta2, "eta2")
+    _dev(out3, "out3")
+    ne = x.numel() - 1
+    if x.dim() != 1 or ne < 1:
+        raise ValueError("x must be 1-D with at least two nodes")
+    if W.dim() != 2 or W.shape[0] != ne:
+        raise ValueError("W must be [ne, M]")
+    if eta2.numel() != ne or out3.numel() != 3:
+        raise ValueError(f"eta2 must hold ne = {ne} doubles and out3 three, got {eta2.numel()} and {out3.numel()}")
+    kinds, kap = _end_kinds(end_kinds, kappa)
+    pairs = []
+    for nm, v in (("g", g), ("a_ends", a_ends)):
+        v = tuple(float(t) for t in v)
+        if len(v) != 2:
+            raise ValueError(f"{nm} must be a pair (left, right)")
+        pairs.append((ctypes.c_double * 2)(*v))
+    for nm, t in (("W", W), ("eta2", eta2), ("out3", out3)):
+        if t.device != x.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, x on {x.device}")
+    rc = lib.lssvr_estimate_ends(_ptr(x), _ptr(W), int(W.shape[1]), ne, kinds[0], kinds[1], kap, *pairs, _ptr(eta2),
+                                 _ptr(out3), _stream(stream))
+    _capi.check(rc, "lssvr_estimate_ends")
+    return eta2, out3
 
 
 def refine(x, eta2, eta2_max, theta, *, h_min=0.0, want_parent=False, work=None, stream=None):

@@ -27,7 +27,10 @@ section 11; ``None`` keeps the Poisson rows), ``reaction`` (a numpy-vectorised c
 estimate and refine ``-(a u')' + c u = f``; without ``coef``, a = 1; ``None``: no such term),
 ``convection`` (a numpy-vectorised callable ``b``: solve, estimate and refine ``-(a u')' + b u' + c u = f``, DESIGN.md
 section 18; the P1 system is then non-symmetric and is solved without stabilisation, so every element must have a cell
-Peclet number ``|b| h / (2 a) <= 1``; ``None``: no such term).
+Peclet number ``|b| h / (2 a) <= 1``; ``None``: no such term), ``boundary`` (a pair ``(left, right)``, each ``None``,
+``("dirichlet", g)``, ``("neumann", g)`` or ``("robin", kappa, g)``: the condition ``a du/dn + kappa u = g`` with the
+outward normal at an end instead of a fixed value; ``None`` keeps the module's Dirichlet
+functions).
 """
 from __future__ import annotations
 
@@ -159,6 +162,48 @@ class _Equation:
         an = np.asarray((_one if self.a is None else self.a)(x.cpu().numpy()), dtype=np.float64)
         an = np.broadcast_to(an, (x.numel(),))
         return _to_dev(np.stack([an[:-1], an[1:]], axis=1), x.device)
+
+
+class _Boundary:
+    """``boundary=(left, right)`` of the facade, parsed: per end ``kinds`` (``ops.END_DIRICHLET`` / ``END_ROBIN``),
+    ``kappa`` (0 at a Dirichlet end) and ``values`` -- g of a Robin end, the value of a ``("dirichlet", g)`` end, None
+    for an end left to the module's Dirichlet function.  ``ValueError`` for anything else."""
+
+    def __init__(self, boundary):
+        if not isinstance(boundary, (tuple, list)) or len(boundary) != 2:
+            raise ValueError("boundary must be a pair (left, right)")
+        self.kinds, self.kappa, self.values = [], [], []
+        for side, spec in zip(("left", "right"), boundary):
+            kind, kappa, g = ops.END_DIRICHLET, 0.0, None
+            if spec is not None:
+                if not isinstance(spec, (tuple, list)) or not spec or spec[0] not in ("dirichlet", "neumann", "robin"):
+                    raise ValueError(f"boundary[{side}] must be None, ('dirichlet', g), ('neumann', g) or "
+                                     f"('robin', kappa, g), got {spec!r}")
+                if len(spec) != (3 if spec[0] == "robin" else 2):
+                    raise ValueError(f"boundary[{side}] = {spec!r}: '{spec[0]}' takes "
+                                     f"{'kappa and g' if spec[0] == 'robin' else 'g'}")
+                g = float(spec[-1])
+                if spec[0] != "dirichlet":
+                    kind = ops.END_ROBIN
+                    kappa = float(spec[1]) if spec[0] == "robin" else 0.0
+                if not math.isfinite(g) or not math.isfinite(kappa):
+                    raise ValueError(f"boundary[{side}] = {spec!r}: kappa and g must be finite")
+                if kappa < 0.0:
+                    raise ValueError(f"boundary[{side}]: kappa = {kappa} < 0 (a du/dn + kappa u = g needs kappa >= 0: "
+                                     "the solve does not pivot)")
+            self.kinds.append(kind)
+            self.kappa.append(kappa)
+            self.values.append(g)
+
+    @property
+    def robin(self):
+        return ops.END_ROBIN in self.kinds
+
+    def shard(self, ne):
+        """The shard arguments with which the enhancement kernels take the FEM nodal value, not a Dirichlet value, as
+        the constraint row at a Robin end: their boundary flags fire for global element 0 and ne_global - 1 only."""
+        off = 1 if self.kinds[0] == ops.END_ROBIN else 0
+        return dict(elem_offset=off, ne_global=off + ne + (1 if self.kinds[1] == ops.END_ROBIN else 0))
 
 
 def _enhance(x, u, M, gamma, n_colloc, *, global_domain, bc, solver, uniform_rtol=1e-9, **kw):
@@ -333,7 +378,8 @@ def lssvr_primal(rhs_func, domain_range, u_xmin, u_xmax, M, gamma,
 class FEMLSSVRPrimalSolver:
     def __init__(self, num_fem_nodes=5, lssvr_M=12, lssvr_gamma=1e6, global_domain=(-1, 1), *,
                  n_colloc=12, rhs=poisson_rhs, nquad=2, mesh=None, device="cuda:0",
-                 solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None, convection=None):
+                 solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None, convection=None,
+                 boundary=None):
         # Dual.py:101-108
         self.num_fem_nodes = num_fem_nodes
         self.lssvr_M = lssvr_M
@@ -382,6 +428,14 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("convection needs solver=ops.SOLVER_PRIMAL: the rows with a first-derivative "
                                  "term have a primal solve only")
         self.convection = convection
+        if boundary is not None and _Boundary(boundary).robin:
+            if fem_solver == "flux":
+                raise ValueError("a Neumann or Robin end needs fem_solver='bands': the flux solve factors "
+                                 "A = D^T K D between two Dirichlet values")
+            if solver == ops.SOLVER_SHARED:
+                raise ValueError("a Neumann or Robin end needs a per-element solver, not ops.SOLVER_SHARED: the "
+                                 "shared operator takes its end rows from the Dirichlet values")
+        self.boundary = boundary
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
         self.element_degrees = None     # one M per element (2 .. 33) instead of lssvr_M; solve_adaptive(mode="hp")
@@ -396,16 +450,57 @@ class FEMLSSVRPrimalSolver:
     def _default_mesh(self):
         return LineMesh.from_nodes(np.linspace(self.global_domain[0], self.global_domain[1], self.num_fem_nodes))
 
+    @property
+    def _bnd(self):
+        """The parsed ``boundary`` when an end is Neumann or Robin, else None: ``boundary=None`` and two Dirichlet
+        ends take the Dirichlet path."""
+        if self.boundary is None:
+            return None
+        b = _Boundary(self.boundary)
+        return b if b.robin else None
+
     def _gd_bc(self):
-        """(global domain, Dirichlet values at its two ends) as float pairs."""
+        """(global domain, end values at its two ends) as float pairs: the Dirichlet value -- the module's function,
+        or g of ``("dirichlet", g)`` -- or, at a Neumann or Robin end, its g."""
         gd = (float(self.global_domain[0]), float(self.global_domain[1]))
-        return gd, (main_boundary_condition_left(self.global_domain[0]),
-                    main_boundary_condition_right(self.global_domain[1]))
+        bc = (main_boundary_condition_left(self.global_domain[0]),
+              main_boundary_condition_right(self.global_domain[1]))
+        if self.boundary is not None:
+            bc = tuple(d if g is None else g for d, g in zip(bc, _Boundary(self.boundary).values))
+        return gd, bc
+
+    def _check_boundary(self, m):
+        """What makes the unpivoted solve with a Neumann or Robin end safe, on the host and before any launch: the
+        matrix is not singular, and with convection the end row keeps its dominance."""
+        bnd = self._bnd
+        if bnd is None:
+            return
+        if self.fem_solver == "flux" or self.solver_id == ops.SOLVER_SHARED:      # (attributes are public)
+            raise ValueError("a Neumann or Robin end needs fem_solver='bands' and a per-element solver")
+        eq = self._eq
+        nodes = np.asarray(m.nodes, dtype=np.float64)
+        if bnd.kinds == [ops.END_ROBIN, ops.END_ROBIN] and bnd.kappa[0] + bnd.kappa[1] == 0.0:
+            positive = False
+            if eq.c is not None:
+                xi = np.polynomial.legendre.leggauss(int(self.nquad))[0]
+                xq = 0.5 * (nodes[:-1] + nodes[1:])[:, None] + 0.5 * np.diff(nodes)[:, None] * xi[None, :]
+                positive = bool(np.any(np.broadcast_to(np.asarray(eq.c(xq), dtype=np.float64), xq.shape) > 0.0))
+            if not positive:
+                raise ValueError("singular problem: two Neumann ends (kappa_left + kappa_right = 0) and no reaction "
+                                 "that is positive at a quadrature point leave u determined up to a constant")
+        if eq.b is not None:
+            b_end = np.broadcast_to(np.asarray(eq.b(nodes[[0, -1]]), dtype=np.float64), (2,))
+            for i, (side, n) in enumerate((("left", -1.0), ("right", 1.0))):
+                if bnd.kinds[i] == ops.END_ROBIN and not bnd.kappa[i] + 0.5 * n * float(b_end[i]) >= 0.0:
+                    raise ValueError(f"{side} end: kappa + b n / 2 = {bnd.kappa[i] + 0.5 * n * float(b_end[i]):.3g} "
+                                     "< 0 (n the outward normal): an inflow Neumann or Robin end this weak loses "
+                                     "coercivity, and the solve does not pivot; raise kappa or fix u there")
 
     def _fem_setup(self):
         """(mesh, x device, xq device, kw) of a P1 assembly: the nodes, the quadrature points and the coefficient
         tables ``ops.p1_assemble`` takes as keywords, after the checks that make the unpivoted solve safe."""
         m = self._default_mesh() if self.mesh is None else self.mesh
+        self._check_boundary(m)
         x = _to_dev(m.nodes, _device(self.device))
         xq = ops.quad_points(x, self.nquad)
         eq, kw = self._eq, {}
@@ -422,15 +517,24 @@ class FEMLSSVRPrimalSolver:
         return m, x, xq, kw
 
     def _fem(self, rhs, u0, u1):
-        """(mesh, x device, u device, bands) of the P1 solve for the right-hand side ``rhs`` and the Dirichlet
-        values ``u0``, ``u1``; no attribute of the solver is written."""
+        """(mesh, x device, u device, bands) of the P1 solve for the right-hand side ``rhs`` and the end values
+        ``u0``, ``u1`` (:meth:`_gd_bc`); no attribute of the solver is written."""
         m, x, xq, kw = self._fem_setup()
         if isinstance(rhs, SinRHS):
             bands = ops.p1_assemble(x, self.nquad, rhs=(rhs.amp, rhs.omega), want_local=True, **kw)
         else:
             fq = _to_dev(rhs(xq.cpu().numpy()), x.device)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
-        if "b_quad" in kw:
+        bnd = self._bnd
+        if bnd is not None:
+            # a Neumann or Robin end stays an unknown; kappa and g join its row inside the solve (_check_boundary has
+            # run, and with convection _convection_quad)
+            if "b_quad" in kw:
+                u = ops.tridiag_ns_bc_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], bnd.kinds,
+                                            bnd.kappa, (u0, u1))
+            else:
+                u = ops.tridiag_bc_solve(bands["diag"], bands["off"], bands["load"], bnd.kinds, bnd.kappa, (u0, u1))
+        elif "b_quad" in kw:
             # no pivoting and no stabilisation: _convection_quad has checked the cell Peclet number
             u = ops.tridiag_ns_dirichlet_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], u0, u1)
         elif self.fem_solver == "flux":
@@ -483,7 +587,14 @@ class FEMLSSVRPrimalSolver:
             else:
                 load[torch.as_tensor(tabulated, device=dev)] = loads
         bc_dev = _to_dev(bc, dev)
-        if "b_quad" in kw:
+        bnd = self._bnd
+        if bnd is not None:
+            if "b_quad" in kw:
+                U = ops.tridiag_ns_bc_solve_multi(bands["diag"], bands["sub"], bands["sup"], load, bnd.kinds,
+                                                  bnd.kappa, bc_dev)
+            else:
+                U = ops.tridiag_bc_solve_multi(bands["diag"], bands["off"], load, bnd.kinds, bnd.kappa, bc_dev)
+        elif "b_quad" in kw:
             U = ops.tridiag_ns_dirichlet_solve_multi(bands["diag"], bands["sub"], bands["sup"], load, bc_dev)
         else:
             U = ops.tridiag_dirichlet_solve_multi(bands["diag"], bands["off"], load, bc_dev)
@@ -545,7 +656,7 @@ class FEMLSSVRPrimalSolver:
         the near-square one."""
         return max(int(self.n_colloc), 2 * int(M))
 
-    def _enhance_by_degree(self, x, u, degrees, gamma, gd, bc):
+    def _enhance_by_degree(self, x, u, degrees, gamma, gd, bc, **shard):
         """Group the elements by degree on the device, read the 35 offsets back once, one ``enhance_subset`` per
         non-empty degree into a zeroed W[ne, max M]."""
         torch = _torch()
@@ -561,7 +672,8 @@ class FEMLSSVRPrimalSolver:
             ng = self.group_colloc(Mg)
             # (a callable f is tabulated at this group's collocation points, np.linspace per element)
             kw = _rhs_mode(self.rhs, lambda: ops.colloc_points(x, ng)[sub])
-            ops.enhance_subset(x, u, Mg, gamma, ng, W, elem_ids=sub, global_domain=gd, bc=bc, status=st, **kw)
+            ops.enhance_subset(x, u, Mg, gamma, ng, W, elem_ids=sub, global_domain=gd, bc=bc, status=st, **kw,
+                               **shard)
         return W, st
 
     # ---- Dual.py:139-169 --------------------------------------------------------------
@@ -580,18 +692,24 @@ class FEMLSSVRPrimalSolver:
         M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
         pm = _point_major(M)
         eq = self._eq
+        # at a Neumann or Robin end the end element takes the FEM nodal value as its constraint row, as at every
+        # interior node: the enhanced solution meets the flux condition to the accuracy of the element fit only
+        bnd = self._bnd
+        if bnd is not None and self.solver_id == ops.SOLVER_SHARED:
+            raise ValueError("a Neumann or Robin end needs a per-element solver, not ops.SOLVER_SHARED")
+        shard = {} if bnd is None else bnd.shard(nodes.size - 1)
         degrees = None
         if self.element_degrees is not None:
             degrees = self._check_degrees(nodes.size - 1)
-            W, st = self._enhance_by_degree(x, u, degrees, gamma, gd, bc)
+            W, st = self._enhance_by_degree(x, u, degrees, gamma, gd, bc, **shard)
         elif eq.poisson:
             kw = _rhs_mode(eq.f, lambda: ops.colloc_points(x, n), pm)
-            W, st = _enhance(x, u, M, gamma, n, global_domain=gd, bc=bc, solver=self.solver_id, **kw)
+            W, st = _enhance(x, u, M, gamma, n, global_domain=gd, bc=bc, solver=self.solver_id, **kw, **shard)
         else:
             # the varcoef / reaction kernels take tables only (a SinRHS too)
             ta, tda, tf, tc = eq.tables(ops.colloc_points(x, n), pm)
             W, st = ops.enhance_varcoef(x, u, M, gamma, n, ta, tda, tf, global_domain=gd, bc=bc, point_major=pm,
-                                        c_values=tc)
+                                        c_values=tc, **shard)
         self.enhanced = EnhancedSolution(x, W, st)
         if degrees is not None:
             self.enhanced.degrees = degrees
@@ -614,8 +732,8 @@ class FEMLSSVRPrimalSolver:
         """Several load cases on this solver's mesh and operator: for every right-hand side of ``rhs_list`` the P1
         assembly and Dirichlet solve (``coef``, ``reaction``, ``nquad`` and ``fem_solver`` as configured), then ONE
         ``ops.enhance_multi`` over all cases -- the element systems are formed and factored once, not once per case.
-        ``bc``: ``None`` (the module's boundary functions, as ``solve()`` uses) or one ``(left, right)`` pair per
-        case.  Returns a list of :class:`EnhancedSolution`, one per case; ``rhs``, ``fem_values``, ``enhanced`` and
+        ``bc``: ``None`` (the end values ``solve()`` uses) or one ``(left, right)`` pair per case -- at a Neumann or
+        Robin end of ``boundary`` the entry is that case's g; the kinds and kappa belong to the matrix and are shared.  Returns a list of :class:`EnhancedSolution`, one per case; ``rhs``, ``fem_values``, ``enhanced`` and
         the other attributes of the solver are left as they are.  Without ``coef`` the tables hold a = 1, a' = 0."""
         torch = _torch()
         rhs_list = list(rhs_list)
@@ -635,8 +753,10 @@ class FEMLSSVRPrimalSolver:
         pts = ops.colloc_points(x, n)
         ta, tda, _, tc = _Equation(_zero, self.coef, self.reaction, self.convection).tables(pts, pm)
         tf = torch.stack([_tabulate(f, pts, pm) for f in rhs_list])
+        bnd = self._bnd
         W, st = ops.enhance_multi(x, U, M, gamma, n, ta, tda, tf, c_values=tc,
-                                  bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd)
+                                  bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd,
+                                  **({} if bnd is None else bnd.shard(x.numel() - 1)))
         return [EnhancedSolution(x, W[j], st[j]) for j in range(len(rhs_list))]
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
@@ -668,6 +788,11 @@ class FEMLSSVRPrimalSolver:
             ta, tda, tf, tc = eq.tables(ops.estimate_points(x, nq), True)
             eta2, _, out3 = ops.estimate_varcoef(x, W, nq, ta, tda, tf, eq.a_ends(x), point_major=True,
                                                  c_values=tc)
+        bnd = self._bnd
+        if bnd is not None:              # the boundary residual of the Neumann / Robin ends joins eta2 and out3
+            ends = np.array([float(self.fem_nodes[0]), float(self.fem_nodes[-1])])      # (host copy of the nodes)
+            a_ends = (1.0, 1.0) if eq.a is None else np.broadcast_to(np.asarray(eq.a(ends), dtype=np.float64), (2,))
+            ops.estimate_ends(x, W, bnd.kinds, bnd.kappa, self._gd_bc()[1], a_ends, eta2, out3)
         return eta2, out3
 
     def _nq(self, nq):

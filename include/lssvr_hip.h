@@ -740,6 +740,51 @@ int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub
                                            const double* load, int64_t ne, int nc, const double* bc_values,
                                            double* u, void* work, int64_t work_bytes, void* stream);
 
+/*
+ * Neumann and Robin boundary conditions (no reference counterpart).  ADDITIVE to ABI 7: four new
+ * symbols and two constants, no existing entry, struct or constant changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * At each end of the domain, independently, LSSVR_END_DIRICHLET (u = g, what every other entry does) or
+ * LSSVR_END_ROBIN:  a du/dn + kappa u = g  with the outward normal (du/dn = -u' at x_0, +u' at x_ne), kappa >= 0;
+ * Neumann is kappa = 0.  A Robin end adds kappa u(x_end) v(x_end) to the bilinear form and g v(x_end) to the load, so
+ * its node stays an unknown and its row is  (diag[end] + kappa) u[end] + (neighbour) = load[end] + g.
+ *
+ * lssvr_tridiag_bc_solve_multi -- lssvr_tridiag_dirichlet_solve_multi with that choice at each end.  kind_left,
+ * kind_right: LSSVR_END_*; kappa_host[2]: host array, read at a Robin end (finite, >= 0); end_values: DEVICE array
+ * [nc][2] (NULL: zeros), g of case j at a Robin end and the value itself at a Dirichlet end.  kappa and g are added
+ * inside the kernels where they read the end row: diag, off and load are read only, as assembled by lssvr_p1_assemble
+ * / _react.  A single right-hand side is nc = 1.  Both ends Dirichlet gives the bits of
+ * lssvr_tridiag_dirichlet_solve_multi.  work: device scratch of work_bytes >= lssvr_tridiag_bc_work_bytes(ne, nc),
+ * which is sized for two free ends (ne + 1 unknowns) whatever the kinds are.  Same no-pivoting rule: kappa >= 0 keeps
+ * an SPD matrix SPD.  Two Neumann ends without a reaction term make the matrix singular; the caller checks.
+ *
+ * lssvr_tridiag_ns_bc_solve_multi -- the same for the bands of lssvr_p1_assemble_conv; both ends Dirichlet gives the
+ * bits of lssvr_tridiag_ns_dirichlet_solve_multi.  Row dominance at a Robin end needs kappa + b(x_end) n / 2 >= 0
+ * (n = -1 left, +1 right); the caller checks.
+ *
+ * lssvr_estimate_ends -- the boundary term of the indicator, after lssvr_estimate, lssvr_estimate_varcoef or
+ * lssvr_estimate_react on the same stream: at a Robin end, with the end element's row of W[ne][M] (M: the row
+ * length; zero-padded rows of mixed degree are fine),
+ *   J = g - kappa u_e(x_end) - a du_e/dn,   eta2[end element] += h/2 J^2,
+ * and out3 follows: sum += the added term, max = max(max, new eta2); a value that becomes non-finite raises the
+ * non-finite count instead.  g_host[2], a_ends_host[2] (a at x_0 and at x_ne), kappa_host[2]: host arrays.  A
+ * Dirichlet end adds nothing; two Dirichlet ends launch nothing.  One thread, no atomics: reproducible.
+ */
+#define LSSVR_END_DIRICHLET 0
+#define LSSVR_END_ROBIN 1
+int64_t lssvr_tridiag_bc_work_bytes(int64_t ne, int nc);
+int lssvr_tridiag_bc_solve_multi(const double* diag, const double* off, const double* load,
+                                 int kind_left, int kind_right, const double* end_values,
+                                 const double* kappa_host, int64_t ne, int nc,
+                                 double* u, void* work, int64_t work_bytes, void* stream);
+int lssvr_tridiag_ns_bc_solve_multi(const double* diag, const double* sub, const double* sup, const double* load,
+                                    int kind_left, int kind_right, const double* end_values,
+                                    const double* kappa_host, int64_t ne, int nc,
+                                    double* u, void* work, int64_t work_bytes, void* stream);
+int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int kind_left, int kind_right,
+                        const double* kappa_host, const double* g_host, const double* a_ends_host,
+                        double* eta2, double* out3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
