@@ -10,6 +10,7 @@ from .mesh import LineMesh, P1Basis, as_line_mesh  # noqa: F401
 from .solver import (  # noqa: F401
     EnhancedSolution,
     FEMLSSVRPrimalSolver,
+    GoalEstimate,
     SinRHS,
     enhance_elements,
     enhance_elements_hetero,

@@ -132,6 +132,11 @@ SIGNATURES = {
     "lssvr_tridiag_ns_bc_solve_multi": _sig([_c_dp], _BANDS, _ENDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
     "lssvr_estimate_ends": _sig([_c_dp, _c_dp, _c_int, _c_i64, _c_int, _c_int, _c_hd, _c_hd, _c_hd, _c_dp, _c_dp],
                                 _STREAM),
+    # goal-oriented estimator (additive to ABI 7): x, Wu, Wz, ne, M, nq, a, a', c, f, j, layout, a_ends, kinds,
+    # kappa_host, g_host, a_bnd_host, jump_free, eta, eta2, q, out4, work
+    "lssvr_goal_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_estimate_goal": _sig([_c_dp, _c_dp, _c_dp, _c_i64, _c_int, _c_int], _REACT_TABLES, [_c_dp, _c_int, _c_dp],
+                                [_c_int, _c_int, _c_hd, _c_hd, _c_hd, _c_int], [_c_dp] * 5, _STREAM),
     # hp-adaptive refinement (additive to ABI 7)
     "lssvr_smoothness": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_dp], _STREAM),
     "lssvr_refine_hp": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dbl, _c_int, _c_int, _c_dp,

@@ -1078,6 +1078,60 @@ int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int
   return check_launch(lssvr::estimate_ends(a, reinterpret_cast<hipStream_t>(stream)), "estimate_ends");
 }
 
+int64_t lssvr_goal_work_bytes(int64_t ne) { return lssvr::goal_work_bytes(ne); }
+
+int lssvr_estimate_goal(const double* x, const double* Wu, const double* Wz, int64_t ne, int M, int nq,
+                        const double* a_values, const double* da_values, const double* c_values,
+                        const double* rhs_values, const double* goal_values, int table_layout, const double* a_ends,
+                        int kind_left, int kind_right, const double* kappa_host, const double* g_host,
+                        const double* a_bnd_host, int jump_free, double* eta, double* eta2, double* q, double* out4,
+                        void* work, void* stream) {
+  // the checks of bind_estimate_vc, on this entry's own argument names
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
+  if (nq < 1 || nq > lssvr::kAdaptMaxNq)
+    return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
+  if (!x || !Wu || !Wz || !eta || !eta2 || !out4 || !work)
+    return fail(LSSVR_ERR_NULL, "x, Wu, Wz, eta, eta2, out4, work must be non-NULL");
+  int rc = check_varcoef_tables(a_values, da_values, rhs_values, table_layout, true);
+  if (rc != LSSVR_OK) return rc;
+  if (!goal_values) return fail(LSSVR_ERR_NULL, "goal_values must be non-NULL");
+  if (!a_ends) return fail(LSSVR_ERR_NULL, "a_ends must be non-NULL");
+  rc = check_end_kinds(kind_left, kind_right, kappa_host);
+  if (rc != LSSVR_OK) return rc;
+  if (!g_host || !a_bnd_host) return fail(LSSVR_ERR_NULL, "g_host and a_bnd_host must be non-NULL");
+  if (jump_free != 0 && jump_free != 1) return fail(LSSVR_ERR_SIZE, "jump_free = %d must be 0 or 1", jump_free);
+  lssvr::GoalArgs a{};
+  a.x = x;
+  a.Wu = Wu;
+  a.Wz = Wz;
+  a.ne = ne;
+  a.M = M;
+  a.nq = nq;
+  a.a_values = a_values;
+  a.da_values = da_values;
+  a.c_values = c_values;
+  a.rhs_values = rhs_values;
+  a.goal_values = goal_values;
+  a.a_ends = a_ends;
+  a.kind[0] = kind_left;
+  a.kind[1] = kind_right;
+  for (int i = 0; i < 2; ++i) {
+    a.kappa[i] = a.kind[i] == LSSVR_END_ROBIN ? kappa_host[i] : 0.0;
+    a.g[i] = g_host[i];
+    a.a_bnd[i] = a_bnd_host[i];
+  }
+  a.jump_free = jump_free;
+  a.eta = eta;
+  a.eta2 = eta2;
+  a.q = q;
+  a.work = static_cast<double*>(work);
+  return check_launch(lssvr::estimate_goal(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out4,
+                                           reinterpret_cast<hipStream_t>(stream)),
+                      "estimate_goal");
+}
+
 int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev, double theta,
                  double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new_dev, void* stream) {
   if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);

@@ -280,6 +280,31 @@ hipError_t estimate_ends(const EstimateEndsArgs& a, hipStream_t s);
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                   double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s);
 
+// goal-oriented estimator (adapt_goal.hip): the residual of Wu weighted with the dual solution Wz, both [ne, M]
+struct GoalArgs {
+  const double* x;
+  const double* Wu;
+  const double* Wz;
+  int64_t ne;
+  int M, nq, ms;                    // ms: LDS row stride of the staged rows (set by estimate_goal())
+  const double* a_values;           // a, a', c (or nullptr), f and j at lssvr_estimate_points, one layout
+  const double* da_values;
+  const double* c_values;
+  const double* rhs_values;
+  const double* goal_values;
+  const double* a_ends;             // [ne, 2], as EstimateVcArgs
+  int kind[2];                      // per end of the domain, as EstimateEndsArgs: 0 Dirichlet, 1 Robin
+  int jump_free;                    // 1: weight with z_e minus its linear interpolant at the element's nodes
+  double kappa[2], g[2], a_bnd[2];
+  double* eta;                      // [ne] signed
+  double* eta2;                     // [ne] eta^2
+  double* q;                        // [ne] int_e j u_e, or nullptr
+  double* work;                     // goal_work_bytes(ne)
+};
+int64_t goal_work_bytes(int64_t ne);
+// out4 = {sum of eta over the elements whose eta^2 is finite, max finite eta^2, non-finite count, sum of finite q_e}
+hipError_t estimate_goal(GoalArgs a, bool point_major, double* out4, hipStream_t s);
+
 // hp-adaptive refinement (adapt_hp.hip)
 hipError_t smoothness(const double* W, int ldw, const int32_t* deg, int64_t ne, double* sigma, hipStream_t s);
 hipError_t refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,

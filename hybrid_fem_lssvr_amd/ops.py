@@ -1177,6 +1177,79 @@ def estimate_ends(x, W, end_kinds, kappa, g, a_ends, eta2, out3, *, stream=None)
     return eta2, out3
 
 
+def goal_work(x, ne):
+    """Device scratch of ``lssvr_goal_work_bytes(ne)`` bytes for :func:`estimate_goal`."""
+    nbytes = _capi.load().lssvr_goal_work_bytes(int(ne))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+
+
+def estimate_goal(x, Wu, Wz, nq, a_values, da_values, rhs_values, goal_values, a_ends, *, c_values=None,
+                  point_major=False, end_kinds=(0, 0), kappa=(0, 0), g=(0, 0), a_bnd=(1, 1), work=None, stream=None,
+                  q=None, jump_free=False):
+    """Dual-weighted residual of the enhanced solution ``Wu`` [ne, M] for the quantity J(u) = int j u dx of
+    -(a u')' + c u = f, weighted with the enhanced dual solution ``Wz`` [ne, M] (``lssvr_estimate_goal``):
+    eta[e] = int_e (f + a u_e'' + a' u_e' - c u_e) z_e - 1/2 (J_e z_e(x_e) + J_{e+1} z_e(x_{e+1})), J the jump of the
+    flux a u', plus (g - kappa u_e - a du_e/dn) z_e at a Robin end of the domain (``end_kinds``, ``kappa``, ``g`` =
+    (left, right) of the primal problem as in :func:`estimate_ends`, ``a_bnd`` = (a(x_0), a(x_ne))).
+    ``a_values``, ``da_values``, ``rhs_values``, ``goal_values``, ``c_values``: a, a', f, j and c (or ``None``) at
+    :func:`estimate_points`, float64[ne, nq] or, with ``point_major``, float64[nq, ne]; ``a_ends`` float64[ne, 2] as
+    in :func:`estimate_varcoef`.  Returns (eta float64[ne] SIGNED, eta2 = eta^2 float64[ne], out4 device float64[4] =
+    {sum of eta where eta2 is finite, max finite eta2, non-finite count, sum of the finite q_e}), q_e = int_e j u_e:
+    out4[0] + out4[3] is the corrected value of J.  ``q``: a float64[ne] device tensor that receives q_e.
+    ``work``: :func:`goal_work`.  ``jump_free``: weight with z_e minus its linear interpolant at the element's nodes
+    instead -- the jump and end terms drop out, eta[e] = int_e R (z_e - I_h z_e): the form to mark from, since bisecting
+    element e reduces it (half a jump at a node shared with a coarse neighbour it does not)."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(Wu, "Wu")
+    _dev(Wz, "Wz")
+    ne = x.numel() - 1
+    nq = int(nq)
+    if x.dim() != 1 or ne < 1:
+        raise ValueError("x must be 1-D with at least two nodes")
+    if Wu.dim() != 2 or Wu.shape[0] != ne:
+        raise ValueError("Wu must be [ne, M]")
+    if Wz.shape != Wu.shape:
+        raise ValueError(f"Wz must have the shape of Wu {list(Wu.shape)}, got {list(Wz.shape)}")
+    _tables(ne, nq, point_major, shape=True, a_values=a_values, da_values=da_values, rhs_values=rhs_values,
+            goal_values=goal_values, **({} if c_values is None else {"c_values": c_values}))
+    _dev(a_ends, "a_ends")
+    if tuple(a_ends.shape) != (ne, 2):
+        raise ValueError(f"a_ends must be [ne, 2] = [{ne}, 2], got {list(a_ends.shape)}")
+    kinds, kap = _end_kinds(end_kinds, kappa)
+    pairs = []
+    for nm, v in (("g", g), ("a_bnd", a_bnd)):
+        v = tuple(float(t) for t in v)
+        if len(v) != 2:
+            raise ValueError(f"{nm} must be a pair (left, right)")
+        pairs.append((ctypes.c_double * 2)(*v))
+    if q is not None:
+        _dev(q, "q")
+        if q.numel() != ne:
+            raise ValueError(f"q must hold ne = {ne} doubles, got {q.numel()}")
+    if work is None:
+        work = goal_work(x, ne)
+    else:
+        _dev(work, "work")
+        if work.numel() * 8 < lib.lssvr_goal_work_bytes(ne):
+            raise ValueError("work is smaller than lssvr_goal_work_bytes(ne)")
+    tensors = dict(Wu=Wu, Wz=Wz, a_values=a_values, da_values=da_values, rhs_values=rhs_values,
+                   goal_values=goal_values, a_ends=a_ends, work=work, c_values=c_values, q=q)
+    for nm, t in tensors.items():
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, x on {x.device}")
+    eta = torch.empty(ne, dtype=torch.float64, device=x.device)
+    eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
+    out4 = torch.empty(4, dtype=torch.float64, device=x.device)
+    rc = lib.lssvr_estimate_goal(_ptr(x), _ptr(Wu), _ptr(Wz), ne, int(Wu.shape[1]), nq, _ptr(a_values),
+                                 _ptr(da_values), _ptr(c_values), _ptr(rhs_values), _ptr(goal_values),
+                                 _layout(point_major), _ptr(a_ends), kinds[0], kinds[1], kap, *pairs,
+                                 1 if jump_free else 0, _ptr(eta), _ptr(eta2), _ptr(q), _ptr(out4), _ptr(work),
+                                 _stream(stream))
+    _capi.check(rc, "lssvr_estimate_goal")
+    return eta, eta2, out4
+
+
 def refine(x, eta2, eta2_max, theta, *, h_min=0.0, want_parent=False, work=None, stream=None):
     """Mark (eta2 non-finite, or eta2 >= theta^2 * max with max > 0; element >= 2 h_min long) and
     bisect (``lssvr_refine``).  ``eta2_max``: device float64 holding max (e.g. ``out3[1:2]`` of

@@ -250,6 +250,22 @@ class EnhancedSolution:
         return u
 
 
+class GoalEstimate:
+    """What :meth:`FEMLSSVRPrimalSolver.solve_goal` returns for J(u) = int j u dx: ``value`` = J(u_enh),
+    ``correction`` = sum eta_e (NaN when an eta_e is not finite), ``corrected`` = value + correction, ``eta`` the
+    signed per-element terms as numpy, and the device tensors ``eta2`` [ne] = eta^2 and ``out4`` =
+    {sum eta, max eta2, non-finite count, sum q} of ``ops.estimate_goal`` for ``ops.refine``."""
+
+    def __init__(self, eta, eta2, out4):
+        self.eta2, self.out4 = eta2, out4
+        self.eta = eta.cpu().numpy()
+        s = out4.cpu().numpy()
+        self.n_nonfinite = int(s[2])
+        self.value = float(s[3])
+        self.correction = float(s[0]) if self.n_nonfinite == 0 else float("nan")
+        self.corrected = self.value + self.correction
+
+
 class _ElementFunctions:
     """``solver.lssvr_functions``: a read-only sequence whose item i is
     ``Legendre(W[i], [x_i, x_{i+1}])`` (Dual.py:95, 163) -- built lazily from the device
@@ -438,6 +454,7 @@ class FEMLSSVRPrimalSolver:
         self.boundary = boundary
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
+        self.dual = None                # EnhancedSolution of the dual problem after solve_goal
         self.element_degrees = None     # one M per element (2 .. 33) instead of lssvr_M; solve_adaptive(mode="hp")
         self._x_dev = None
         self._u_dev = None
@@ -713,14 +730,17 @@ class FEMLSSVRPrimalSolver:
         self.enhanced = EnhancedSolution(x, W, st)
         if degrees is not None:
             self.enhanced.degrees = degrees
+        self._report_fallbacks()
+        self.lssvr_functions = _ElementFunctions(nodes, W)
+
+    def _report_fallbacks(self):
         nbad = self.enhanced.n_fallback
         if nbad:
-            bad = np.nonzero(st.cpu().numpy())[0]
+            bad = np.nonzero(self.enhanced.status.cpu().numpy())[0]
             for i in bad[:10]:
                 print(f"Error in element {i+1}: factorisation breakdown, linear interpolant used")
             if nbad > 10:
                 print(f"... and {nbad - 10} more elements")
-        self.lssvr_functions = _ElementFunctions(nodes, W)
 
     # ---- Dual.py:171-174 --------------------------------------------------------------
     def solve(self):
@@ -735,6 +755,10 @@ class FEMLSSVRPrimalSolver:
         ``bc``: ``None`` (the end values ``solve()`` uses) or one ``(left, right)`` pair per case -- at a Neumann or
         Robin end of ``boundary`` the entry is that case's g; the kinds and kappa belong to the matrix and are shared.  Returns a list of :class:`EnhancedSolution`, one per case; ``rhs``, ``fem_values``, ``enhanced`` and
         the other attributes of the solver are left as they are.  Without ``coef`` the tables hold a = 1, a' = 0."""
+        return self._solve_many(rhs_list, bc)[0]
+
+    def _solve_many(self, rhs_list, bc):
+        """:meth:`solve_many` -> (its list, x device, U device [ncases, ne+1] the P1 nodal values of the cases)."""
         torch = _torch()
         rhs_list = list(rhs_list)
         if not rhs_list or not all(callable(f) for f in rhs_list):
@@ -757,7 +781,7 @@ class FEMLSSVRPrimalSolver:
         W, st = ops.enhance_multi(x, U, M, gamma, n, ta, tda, tf, c_values=tc,
                                   bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd,
                                   **({} if bnd is None else bnd.shard(x.numel() - 1)))
-        return [EnhancedSolution(x, W[j], st[j]) for j in range(len(rhs_list))]
+        return [EnhancedSolution(x, W[j], st[j]) for j in range(len(rhs_list))], x, U
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):
@@ -812,8 +836,106 @@ class FEMLSSVRPrimalSolver:
         eta2, _ = self._estimate_dev(nq)
         return eta2.cpu().numpy()
 
+    # ---- goal-oriented estimation: the dual-weighted residual (no reference counterpart) ------------
+    def _check_goal(self, goal):
+        """What :meth:`solve_goal` needs, checked on the host before any GPU use."""
+        if not callable(goal):
+            raise ValueError("goal must be a callable j(x): the density of J(u) = int j u dx")
+        if self.convection is not None:
+            raise ValueError("goal needs an operator without convection: the adjoint of -(a u')' + b u' + c u has "
+                             "-b and c - b', another matrix than the primal's")
+        if self.solver_id != ops.SOLVER_PRIMAL:
+            raise ValueError("goal needs solver=ops.SOLVER_PRIMAL: the primal and the dual solution share one "
+                             "factorisation through solve_many")
+        if self.fem_solver == "flux" and self._bnd is not None:
+            raise ValueError("goal with a Neumann or Robin end needs fem_solver='bands'")
+        if self.element_degrees is not None:
+            raise ValueError("goal needs one degree for all elements (element_degrees is set, e.g. by "
+                             "solve_adaptive(mode='hp')): solve_many and the dual-weighted residual take one lssvr_M")
+
+    def _goal_nq(self, nq):
+        """Gauss points of the goal path: min(32, max(2 lssvr_M, 16)) unless given.  More than :meth:`estimate`'s
+        max(lssvr_M, 8): eta_e is SIGNED, so the quadrature error of int R z does not hide under a square -- where f
+        has a layer that 8 points do not resolve it is as large as the correction itself."""
+        return self._nq(min(32, max(2 * int(self.lssvr_M), 16)) if nq is None else nq)
+
+    def solve_goal(self, goal, nq=None):
+        """Solve for ``rhs`` and for the dual problem of the quantity of interest J(u) = int ``goal`` u dx in one
+        :meth:`solve_many` (same matrix: no convection), then weight the residual of the enhanced primal solution with
+        the enhanced dual solution (``ops.estimate_goal``, ``nq``-point Gauss, default min(32, max(2 lssvr_M, 16))).
+        The dual case has zero end data: the value 0 at a Dirichlet end, g = 0 at a Neumann or Robin end.  Afterwards
+        ``fem_nodes``,
+        ``fem_values``, ``enhanced`` and ``lssvr_functions`` hold the primal case as after ``solve()`` and ``dual``
+        the dual :class:`EnhancedSolution`.  Returns a :class:`GoalEstimate`: ``value`` = J(u_enh), ``correction`` =
+        sum eta_e, ``corrected`` = their sum -- the enhanced solution is continuous and takes the Dirichlet values, so
+        sum eta_e = J(u) - J(u_enh) up to the error of the dual solution and of the ``nq``-point rule on R z: the
+        correction is only as good as that rule resolves f."""
+        return self._solve_goal(goal, nq)[0]
+
+    def _solve_goal(self, goal, nq):
+        """:meth:`solve_goal` -> (its GoalEstimate, marking): ``marking()`` is a second launch on the same tables in
+        the jump-free form -> (eta2 device [ne], out4 device [4]) of eta_e = int_e R (z_e - I_h z_e)."""
+        self._check_goal(goal)
+        nq = self._goal_nq(nq)
+        bc0 = self._gd_bc()[1]
+        (primal, dual), x, U = self._solve_many([self.rhs, goal], [bc0, (0.0, 0.0)])
+        eq = self._eq
+        pts = ops.estimate_points(x, nq)
+        ta, tda, tf, tc = eq.tables(pts, True)
+        tj = _tabulate(goal, pts, True)
+        nodes = x.cpu().numpy()
+        kw = {}
+        bnd = self._bnd
+        if bnd is not None:
+            ends = nodes[[0, -1]]
+            a_bnd = (1.0, 1.0) if eq.a is None else np.broadcast_to(np.asarray(eq.a(ends), dtype=np.float64), (2,))
+            kw = dict(end_kinds=bnd.kinds, kappa=bnd.kappa, g=bc0, a_bnd=a_bnd)
+        a_ends = eq.a_ends(x)
+        eta, eta2, out4 = ops.estimate_goal(x, primal.W, dual.W, nq, ta, tda, tf, tj, a_ends, c_values=tc,
+                                            point_major=True, **kw)
+
+        def marking():
+            return ops.estimate_goal(x, primal.W, dual.W, nq, ta, tda, tf, tj, a_ends, c_values=tc,
+                                     point_major=True, jump_free=True, **kw)[1:]
+
+        self._x_dev, self._u_dev = x, U[0]
+        self.fem_nodes = nodes
+        self.fem_values = U[0].cpu().numpy()
+        self.enhanced, self.dual = primal, dual
+        self._report_fallbacks()
+        self.lssvr_functions = _ElementFunctions(nodes, primal.W)
+        return GoalEstimate(eta, eta2, out4), marking
+
+    def _solve_adaptive_goal(self, goal, tol, theta, max_elements, max_iter, h_min, nq):
+        """The rounds of ``solve_adaptive(goal=j)``; the arguments it shares with the residual loop are validated."""
+        nq = self._goal_nq(nq)
+        if self.mesh is None:
+            self.mesh = self._default_mesh()
+        if self.mesh.nelements > max_elements:
+            raise ValueError(f"the initial mesh has {self.mesh.nelements} elements > max_elements = {max_elements}")
+        self.adapt_history = []
+        est = float("nan")
+        for it in range(max_iter):
+            ge, marking = self._solve_goal(goal, nq)
+            ne = int(ge.eta.size)
+            est = float(np.abs(ge.eta).sum()) if ge.n_nonfinite == 0 else float("inf")
+            rec = dict(ne=ne, estimate=est, correction=ge.correction, value=ge.value, marked=0)
+            self.adapt_history.append(rec)
+            if (tol is not None and est <= float(tol)) or it + 1 == max_iter:
+                break
+            # marked from the jump-free form: half a jump at a node shared with a coarse neighbour stays as it is
+            # however often the fine element is bisected, and the loop would stall on it
+            mark2, mark4 = marking()
+            x_new, _ = ops.refine(self.enhanced.nodes, mark2, mark4[1:2], theta, h_min=h_min)
+            ne_new = x_new.numel() - 1
+            if ne_new == ne or ne_new > max_elements:
+                break
+            rec["marked"] = ne_new - ne
+            self.mesh = LineMesh.from_nodes(x_new.cpu().numpy())
+        return est
+
     def solve_adaptive(self, tol=None, theta=0.5, max_elements=100000, max_iter=50, h_min=0.0, nq=None, *,
-                       mode="h", M_max=None, dM=2, sigma_min=1.0, max_dof=None):
+                       mode="h", M_max=None, dM=2, sigma_min=1.0, max_dof=None, goal=None):
         """Solve, estimate, mark, bisect -- repeated.  Each round runs ``solve()`` on the current mesh
         and the indicator of :meth:`estimate` (for ``-(a u')' = f`` when ``coef`` is set); it stops when
         sqrt(sum eta^2) <= ``tol``, after ``max_iter`` rounds, when nothing is marked, or when the refinement
@@ -832,9 +954,22 @@ class FEMLSSVRPrimalSolver:
         from round to round and describes the final mesh; the indicator takes ``nq`` = min(32, max(max M_e, 8))
         Gauss points unless given; every round records dict(ne, estimate, marked, raised, dof) with marked =
         elements bisected, raised = elements raised after that round and dof = sum of M_e.  It also stops when a
-        round neither bisects nor raises, or when the refinement would take sum M_e above ``max_dof`` (hp only)."""
+        round neither bisects nor raises, or when the refinement would take sum M_e above ``max_dof`` (hp only).
+
+        ``goal=j`` (a callable; ``mode="h"``, no convection, ``solver=ops.SOLVER_PRIMAL``): refine for the quantity
+        J(u) = int j u dx instead.  Each round is :meth:`solve_goal`; the elements are marked by the same rule from the
+        square of the jump-free form of the dual-weighted residual, int_e R (z - I_h z) with I_h z the linear
+        interpolant of the dual solution at the element's nodes (``ops.estimate_goal(jump_free=True)``: what bisecting
+        the element itself reduces); a round's estimate is sum |eta_e| -- an upper bound of the
+        correction |sum eta_e|, so cancellation between elements cannot stop the loop early -- and is what ``tol``
+        is compared with and what is returned; ``adapt_history`` holds dict(ne, estimate, correction, value, marked)
+        per round, value = J(u_enh) and correction = sum eta_e on that round's mesh."""
         if mode not in ("h", "hp"):
             raise ValueError(f"mode must be 'h' or 'hp', got {mode!r}")
+        if goal is not None:
+            if mode != "h":
+                raise ValueError("goal needs mode='h': the dual-weighted residual marks elements for bisection only")
+            self._check_goal(goal)
         theta = float(theta)
         if not 0.0 <= theta <= 1.0:
             raise ValueError(f"theta must be in [0, 1], got {theta}")
@@ -851,6 +986,8 @@ class FEMLSSVRPrimalSolver:
                                            sigma_min, max_dof)
         if max_dof is not None:
             raise ValueError("max_dof bounds sum M_e of mode='hp'; mode='h' is bounded by max_elements")
+        if goal is not None:
+            return self._solve_adaptive_goal(goal, tol, theta, int(max_elements), int(max_iter), float(h_min), nq)
         nq = self._nq(nq)
         if self.mesh is None:
             self.mesh = self._default_mesh()

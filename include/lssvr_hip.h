@@ -785,6 +785,44 @@ int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int
                         const double* kappa_host, const double* g_host, const double* a_ends_host,
                         double* eta2, double* out3, void* stream);
 
+/*
+ * Goal-oriented error estimation (dual-weighted residual).  ADDITIVE to ABI 7 (new symbols; LSSVR_ABI_VERSION stays 7).
+ *
+ * lssvr_estimate_goal -- for a quantity of interest J(u) = int j u dx of -(a u')' + c u = f (no convection term: the
+ * adjoint then has the primal's matrix), the residual of the enhanced primal solution u_e (row e of Wu[ne][M])
+ * weighted with the enhanced dual solution z_e (row e of Wz[ne][M], the solution for the right-hand side j with zero
+ * end data; same M and row length):
+ *   eta[e]  = int_e R z_e dx - 1/2 (J_e z_e(x_e) + J_{e+1} z_e(x_{e+1}))
+ *             + at a Robin end of the domain, in its end element: (g - kappa u_e(x_end) - a du_e/dn) z_e(x_end)
+ *   R = f + a u_e'' + a' u_e' - c u_e (lssvr_estimate_react's residual; c_values == NULL drops the c term),
+ *   J_i = aR_{i-1} u_{i-1}'(x_i) - aL_i u_i'(x_i) the flux jump of lssvr_estimate_varcoef, J_0 = J_ne = 0,
+ *   eta2[e] = eta[e]^2 (what lssvr_refine marks from),   q[e] = int_e j u_e dx (q may be NULL).
+ * eta is SIGNED: for a continuous u_e that takes the Dirichlet values and the exact z, sum_e eta[e] = J(u) - J(u_e),
+ * so sum eta + sum q is a corrected value of J.  The integrals are the nq-point Gauss rule of lssvr_gauss_rule.
+ *   a_values, da_values, c_values, rhs_values, goal_values   a, a', c, f and j at lssvr_estimate_points, all in
+ *                   table_layout (LSSVR_TABLE_ELEMENT_MAJOR t[e*nq + q] or LSSVR_TABLE_POINT_MAJOR t[q*ne + e])
+ *   a_ends          [ne][2] as in lssvr_estimate_varcoef
+ *   kind_left, kind_right, kappa_host[2], g_host[2], a_bnd_host[2]   the ends of the domain as in lssvr_estimate_ends
+ *                   (g of the PRIMAL problem; a_bnd = a at x_0 and x_ne); a Dirichlet end adds nothing
+ *   jump_free       0: as above.  1: the weight is z_e - I_h z_e, I_h z_e the linear interpolant of z_e at the element's
+ *                   two nodes; it vanishes there, so the jump and end terms drop out: eta[e] = int_e R (z_e - I_h z_e).
+ *                   This is the form to MARK from (a bisection of element e reduces it; half a jump at a node shared
+ *                   with a coarse neighbour it does not); its sum is the correction only where the residual is
+ *                   orthogonal to the piecewise linears.  q and out4[3] do not depend on it.
+ *   out4            device double[4] = {sum of eta over the elements whose eta^2 is finite, max of the finite eta2,
+ *                   number of non-finite eta2, sum of the finite q}
+ *   work            device scratch of lssvr_goal_work_bytes(ne) bytes
+ * 1 <= M <= 33, 1 <= nq <= 32.  A non-finite row of Wu makes its own eta and, through the flux jumps, both
+ * neighbours' non-finite.  No atomics: every output is bitwise reproducible.
+ */
+int64_t lssvr_goal_work_bytes(int64_t ne);
+int lssvr_estimate_goal(const double* x, const double* Wu, const double* Wz, int64_t ne, int M, int nq,
+                        const double* a_values, const double* da_values, const double* c_values,
+                        const double* rhs_values, const double* goal_values, int table_layout,
+                        const double* a_ends, int kind_left, int kind_right, const double* kappa_host,
+                        const double* g_host, const double* a_bnd_host, int jump_free,
+                        double* eta, double* eta2, double* q, double* out4, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
