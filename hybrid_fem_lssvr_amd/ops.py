@@ -972,14 +972,36 @@ def p1_flux_aggregate(kloc, load, *, first_global, work=None, stream=None):
 
 def p1_flux_finish(kloc, load, work, *, first_global, last_global, prefix=None, grand=None,
                    u0=0.0, u1=0.0, out=None, stream=None):
-    """Second half of the sharded flux solve: nodal values u[ne+1] of this shard."""
+    """Second half of the sharded flux solve: nodal values u[ne+1] of this shard.  ``work`` is the buffer
+    :func:`p1_flux_aggregate` returned for the same ``kloc`` and ``load``; it becomes a raw device pointer that the
+    kernel reads ``lssvr_p1_flux_work_bytes(ne)`` bytes of, so it is checked here and never replaced."""
     lib = _capi.load()
+    _dev(kloc, "kloc")
+    _dev(load, "load")
+    _dev(work, "work")
     ne = kloc.numel()
+    if ne < 1:
+        raise ValueError("kloc must hold at least one element")
+    if load.numel() < ne + 1:
+        raise ValueError("load must have at least ne+1 entries")
+    nbytes = lib.lssvr_p1_flux_work_bytes(ne)
+    if work.numel() * work.element_size() < nbytes:
+        raise ValueError(f"work must hold lssvr_p1_flux_work_bytes({ne}) = {nbytes} bytes, got "
+                         f"{work.numel() * work.element_size()}")
     if out is None:
         out = torch.empty(ne + 1, dtype=torch.float64, device=kloc.device)
+    else:
+        _dev(out, "out")
+        if out.numel() < ne + 1:
+            raise ValueError("out must have at least ne+1 entries")
     for t, nm in ((prefix, "prefix"), (grand, "grand")):
         if t is not None:
             _dev(t, nm)
+            if t.numel() < 3:
+                raise ValueError(f"{nm} must hold 3 doubles")
+    for nm, t in (("load", load), ("work", work), ("out", out), ("prefix", prefix), ("grand", grand)):
+        if t is not None and t.device != kloc.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, kloc on {kloc.device}")
     rc = lib.lssvr_p1_flux_finish(_ptr(kloc), _ptr(load), ne, int(bool(first_global)),
                                   int(bool(last_global)), _ptr(work), _ptr(prefix), _ptr(grand),
                                   float(u0), float(u1), _ptr(out), _stream(stream))
