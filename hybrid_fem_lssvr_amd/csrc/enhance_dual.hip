@@ -25,7 +25,7 @@
 //     where w is CARRIED (never recomputed from lam: the rounding of A'^T lam, |lam| ~ gamma scl^4
 //     |residual|, is what limits the plain dual form to 1e-10 on BASELINE config 1), and a final
 //     re-projection of w onto the boundary rows.
-// numpy prototype of exactly this arrangement: scripts/proto/dual_projected.py (float64, relative
+// numpy restatement of exactly this arrangement: oracle/lssvr_oracle.py solve_dual_projected(carried=True) (float64, relative
 // L2 to the 60-digit minimiser: 1e-16 on config 1, <= 1e-12 at degree 32 / 64 points, 5e-12 where
 // n = M - 2 = 31 and the primal normal equations are at 3e-6).
 //
@@ -382,6 +382,7 @@ __global__ __launch_bounds__(64, LSSVR_DUAL_MINW(LPE)) void enhance_dual_kernel(
   // unguarded steps on one element of the 24-element fixture mesh; every other element improves).
   double nrm = 0.0;
   double res = residual(lam, wv, nrm);
+  bool refining = true;                          // (uniform over the element's lanes: nrm is a butterfly sum)
 #pragma unroll 1
   for (int it = 0; it < nrefine; ++it) {
     double dl = dr * backward(forward(res));
@@ -390,15 +391,19 @@ __global__ __launch_bounds__(64, LSSVR_DUAL_MINW(LPE)) void enhance_dual_kernel(
     const double wv_c = wv + at_times(dl);
     double nrm_c = 0.0;
     const double res_c = residual(lam_c, wv_c, nrm_c);
-    const bool better = nrm_c < 4.0 * nrm;       // (NaN: rejected; a step may raise the norm 2x: at the
-                                                 // rounding floor the norm is noise, a diverging step gains 100x)
+    // (NaN: rejected; a step may raise the norm 2x: at the rounding floor the norm is noise, a diverging step
+    // gains 100x)
+    const bool better = refining && nrm_c < 4.0 * nrm;
     // a rejected step would be recomputed identically, a step that gains less than 2x in the norm
-    // is at the rounding floor: the wave stops refining once none of its elements gains any more
+    // is at the rounding floor: the ELEMENT is done there -- the elements of a wave stop one by one, and one that
+    // has stopped keeps its result while the wave runs on for the others (its row must not depend on which
+    // elements share its wave: a shard boundary moves them) -- and the wave leaves once none of them gains any more
     const bool gains = better && (nrm_c < 0.25 * nrm);
     lam = better ? lam_c : lam;
     wv = better ? wv_c : wv;
     res = better ? res_c : res;
     nrm = better ? nrm_c : nrm;
+    refining = gains;
     if (!__any(gains)) break;
   }
   // ---- w = w_bc + w', re-projected onto the boundary rows -------------------------------------

@@ -171,6 +171,20 @@ def make_eval_case(mod, name):
           f"elem equal={np.array_equal(eo, elem)}")
 
 
+def make_dual_grid(name="G9_dual_grid"):
+    """G9: the dual Gram solver's (M, n) sweep (tests/dual_rules.py holds the grid, the mesh and the float64
+    restatement): per case the 60-digit minimiser of three elements and the restatement's own error against it.
+    No reference output in it -- the project's oracle only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dual_rules
+    t0 = time.perf_counter()
+    out = dual_rules.build_fixture()
+    np.savez(os.path.join(OUT_DIR, name + ".npz"), **out)
+    e = out["proto_err"]
+    print(f"{name}: {e.size} pairs, proto_err {e.min():.1e} .. {e.max():.1e}, "
+          f"{int((e > dual_rules.ENVELOPE).sum())} outside the envelope  ({time.perf_counter()-t0:.0f}s)")
+
+
 def rerun_on_stored_inputs(mod, g, limit=None):
     """The reference on a fixture's STORED inputs (``nodes_sel``, ``values_sel``; same per-element
     seeds as :func:`run_reference`): returns coefficients to compare with ``coef_ref`` -- bit for
@@ -215,6 +229,8 @@ def verify():
         if not fn.endswith(".npz"):
             continue
         g = dict(np.load(os.path.join(OUT_DIR, fn), allow_pickle=False))
+        if "proto_err" in g:          # G9: made by the oracle alone (tests/test_dual_cpu.py re-derives a sample)
+            continue
         if "elements" not in g:
             W, u = rerun_eval_case(mod, g)
             ok_in = np.array_equal(orc.fem_p1_solve_golden_v1(g["nodes"]), g["values"])
@@ -241,6 +257,8 @@ def main():
         sys.exit(1 if verify() else 0)
     only = set(filter(None, args.only.split(",")))
     os.makedirs(OUT_DIR, exist_ok=True)
+    if only == {"G9"}:               # needs no reference
+        return make_dual_grid()
     mod = load_reference()
 
     def want(k):
@@ -266,6 +284,8 @@ def main():
         make_eval_case(mod, "G7_eval_default")
     if want("G8"):   # class defaults (Dual.py:101)
         make_case(mod, "G8_classdefaults_ne4_M12_n12", -1.0, 1.0, 4, 12, 1e6, 12)
+    if want("G9"):   # dual solver sweep: truths and the float64 restatement's error
+        make_dual_grid()
 
 
 if __name__ == "__main__":

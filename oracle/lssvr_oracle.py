@@ -274,6 +274,63 @@ def solve_dual_gram(s):
     return s.Ahat.T @ sol[:n] + s.B.T @ sol[n:]
 
 
+def solve_dual_projected(s, refine=0, equil=True, carried=False):
+    """The arrangement of csrc/enhance_dual.hip in float64: the 2 x 2 boundary block B B^T as the first (block)
+    pivot (projected feature map A' = A - (A B^T)(B B^T)^-1 B), the Jacobi-equilibrated n x n system
+    (K + eps I) lam = f', K = A' A'^T, LU with partial pivoting (LAPACK), ``refine`` refinement steps with the
+    residual in operator form, r = f' - A' w - eps lam.
+
+    ``carried=False`` is the first prototype: w is recomputed from lam in every step and every step is kept.
+    ``carried=True`` is what the kernels do: w is carried (w += A'^T dlam, never recomputed from lam), the residual
+    is accumulated in long double (the kernels use double-double products and sums), a step is kept only if it
+    leaves the equilibrated residual norm below 4 x the previous one, the loop ends once a step gains less than
+    4 x, and the result is projected back onto the boundary rows."""
+    import scipy.linalg as sla
+    n = s.n
+    A = s.Ahat                      # n x M
+    B = s.B                         # 2 x M
+    eps = 1.0 / s.gamma_t
+    Q = B @ B.T
+    Qi = np.linalg.inv(Q)
+    Cc = (A @ B.T) @ Qi             # n x 2: c_k
+    Ap = A - Cc @ B                 # projected rows
+    wbc = B.T @ (Qi @ s.g)          # minimum-norm solution of B w = g
+    fp = s.ftil - A @ wbc
+    K = Ap @ Ap.T
+    Kd = K + eps * np.eye(n)
+    d = 1.0 / np.sqrt(np.diag(Kd)) if equil else np.ones(n)
+    Ks = Kd * d[:, None] * d[None, :]
+    lu = sla.lu_factor(Ks)
+    lam = d * sla.lu_solve(lu, d * fp)
+    if not carried:
+        for _ in range(refine):
+            w1 = Ap.T @ lam
+            r = fp - Ap @ w1 - eps * lam           # operator-form residual
+            lam = lam + d * sla.lu_solve(lu, d * r)
+        return wbc + Ap.T @ lam
+    LD = np.longdouble
+    ApL, fpL = Ap.astype(LD), fp.astype(LD)
+
+    def residual(lam_, w_):
+        r_ = d * ((fpL - LD(eps) * lam_.astype(LD)) - ApL @ w_.astype(LD)).astype(np.float64)
+        return r_, float(r_ @ r_)
+
+    w = Ap.T @ lam
+    res, nrm = residual(lam, w)
+    for _ in range(refine):
+        dl = d * sla.lu_solve(lu, res)
+        lam_c, w_c = lam + dl, w + Ap.T @ dl
+        res_c, nrm_c = residual(lam_c, w_c)
+        better = nrm_c < 4.0 * nrm                 # (NaN: rejected)
+        gains = better and nrm_c < 0.25 * nrm
+        if better:
+            lam, w, res, nrm = lam_c, w_c, res_c, nrm_c
+        if not gains:
+            break
+    wp = wbc + w
+    return wp - B.T @ (Qi @ (B @ wp - s.g))
+
+
 def solve_bc_eliminated(s, return_status=False):
     """The algorithm the HIP kernels implement ("per-element solve"):
 
