@@ -1,10 +1,12 @@
-// A posteriori error indicator and h-refinement of the enhanced solution (no reference
+// A posteriori error indicator and h / hp refinement of the enhanced solution (no reference
 // counterpart: Hybrid-FEM-LSSVR-Dual.py computes its per-element slack and discards it).
 //   - derivatives of the enhanced solution at query points (lssvr_eval_deriv)
 //   - per-element residual indicator  eta_e^2 = h_e^2 ||f + u_e''||_e^2 + h_e/2 (J_e^2 + J_{e+1}^2)
 //     with J_i = u_{i-1}'(x_i) - u_i'(x_i) (lssvr_estimate) and its deterministic reduction
 //   - the same for -(a u')' = f: residual f + a u'' + a' u', J_i the jump of the flux a u' (lssvr_estimate_varcoef)
-//   - threshold marking + bisection into a new ascending node array (lssvr_refine)
+//   - threshold marking + bisection into a new ascending node array (lssvr_refine), and the same three kernels with
+//     the raise-or-bisect rule and the degrees of the new mesh (lssvr_refine_hp)
+// The block scan, the per-block reduction tree and its finish kernel are lssvr_adapt.hpp's.
 // DESIGN.md section 11 has the derivation, the mapping and the measured numbers.
 #include <cmath>
 #include <type_traits>
@@ -137,28 +139,6 @@ __device__ __forceinline__ void store_indicator(double* __restrict__ eta2_out, d
   }
 }
 
-// workgroup tree of the per-lane {sum, max, non-finite count} -> work[3*blockIdx.x ..]
-__device__ __forceinline__ void reduce_partials(double* __restrict__ red, int tid, double bsum, double bmax,
-                                                double bcnt, double* __restrict__ work) {
-  red[tid] = bsum;
-  red[kEstBlock + tid] = bmax;
-  red[2 * kEstBlock + tid] = bcnt;
-  __syncthreads();
-  for (int off = kEstBlock / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-      red[tid] += red[tid + off];
-      red[kEstBlock + tid] = fmax(red[kEstBlock + tid], red[kEstBlock + tid + off]);
-      red[2 * kEstBlock + tid] += red[2 * kEstBlock + tid + off];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    work[3 * blockIdx.x + 0] = red[0];
-    work[3 * blockIdx.x + 1] = red[kEstBlock];
-    work[3 * blockIdx.x + 2] = red[2 * kEstBlock];
-  }
-}
-
 // RHS: 0 = LSSVR_RHS_ARRAY (rhs[e*nq + q]), 1 = LSSVR_RHS_SIN, 2 = LSSVR_RHS_ARRAY_PM (rhs[q*ne + e])
 // Dynamic LDS: T[nq*MT] (P_k''(xi_q)) | xi[nq] | wt[nq] | rows[kEstBlock*ms] | dl[kEstBlock] | dr[kEstBlock] |
 // red[3*kEstBlock].  The rule is copied to LDS: indexed by a loop counter in the kernel arguments it would
@@ -224,7 +204,7 @@ __global__ __launch_bounds__(kEstBlock) void estimate_kernel(EstimateArgs p, Gau
     }
     __syncthreads();      // rows / sdl / sdr are rewritten by the next chunk
   }
-  reduce_partials(red, tid, bsum, bmax, bcnt, p.work);
+  reduce_partials<kEstBlock, 3>(red, tid, {bsum, bmax, bcnt}, p.work);
 }
 
 // Variable coefficients, -(a u')' = f (TS = 2), and the reaction term, -(a u')' + c u = f (TS = 3, Args =
@@ -300,7 +280,7 @@ __device__ __forceinline__ void estimate_tables_body(const Args& p, const GaussR
     }
     __syncthreads();      // rows / sfl / sfr are rewritten by the next chunk
   }
-  reduce_partials(red, tid, bsum, bmax, bcnt, p.work);
+  reduce_partials<kEstBlock, 3>(red, tid, {bsum, bmax, bcnt}, p.work);
 }
 
 template <int MT, bool PM>
@@ -311,36 +291,6 @@ __global__ __launch_bounds__(kEstBlock) void estimate_vc_kernel(EstimateVcArgs p
 template <int MT, bool PM>
 __global__ __launch_bounds__(kEstBlock) void estimate_react_kernel(EstimateReactArgs p, GaussRuleN g) {
   estimate_tables_body<MT, PM, 3>(p, g);
-}
-
-// one workgroup: the per-block partials in a fixed order -> out3 (bitwise reproducible)
-__global__ __launch_bounds__(kBlock) void estimate_finish_kernel(const double* __restrict__ part, int nb,
-                                                                  double* __restrict__ out3) {
-  __shared__ double sh[3][kBlock];
-  const int tid = threadIdx.x;
-  double s = 0.0, m = 0.0, c = 0.0;
-  for (int i = tid; i < nb; i += kBlock) {
-    s += part[3 * i];
-    m = fmax(m, part[3 * i + 1]);
-    c += part[3 * i + 2];
-  }
-  sh[0][tid] = s;
-  sh[1][tid] = m;
-  sh[2][tid] = c;
-  __syncthreads();
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-      sh[0][tid] += sh[0][tid + off];
-      sh[1][tid] = fmax(sh[1][tid], sh[1][tid + off]);
-      sh[2][tid] += sh[2][tid + off];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    out3[0] = sh[0][0];
-    out3[1] = sh[1][0];
-    out3[2] = sh[2][0];
-  }
 }
 
 // The boundary term of the indicator at a Robin end a du/dn + kappa u = g, after an estimator
@@ -399,84 +349,123 @@ __global__ __launch_bounds__(kBlock) void estimate_points_kernel(const double* _
 }
 
 // ---------------------------------------------------------------------------
-// marking + bisection: count per block, one-block scan, scatter
+// marking + bisection: count per block, one-block scan, scatter.  One text for lssvr_refine (HP = false) and
+// lssvr_refine_hp (HP = true): the h instance reads no sigma / deg and writes no deg_new / counts2.
 // ---------------------------------------------------------------------------
-// element e is marked iff (eta2[e] is non-finite, or max > 0 and eta2[e] >= theta^2 * max) and it is
-// at least 2 h_min long; mx = the device max of the finite eta2 (out3[1] of lssvr_estimate)
-__device__ __forceinline__ bool marked(const double* __restrict__ x, const double* __restrict__ eta2,
-                                       int64_t e, double mx, double theta2, double h2min) {
-  return indicator_marked(eta2[e], mx, theta2) && (x[e + 1] - x[e] >= h2min);
+struct RefineArgs {
+  const double* x;
+  int64_t ne;
+  const double* eta2;
+  const double* mx;          // the device max of the finite eta2 (out3[1] of lssvr_estimate)
+  double theta2, h2min;
+  const double* sigma;       // HP only, from here on
+  const int32_t* deg;
+  double sigma_min;
+  int dM, M_max;
+};
+
+// 0: unchanged, 1: bisected, 2: degree raised (HP only).  Element e is marked iff eta2[e] is non-finite, or max > 0
+// and eta2[e] >= theta^2 * max; a marked element is raised where its coefficients decay fast enough and the degree
+// has room, else bisected where it is at least 2 h_min long
+template <bool HP>
+__device__ __forceinline__ int action(const RefineArgs& p, int64_t e, double m_max) {
+  if (!indicator_marked(p.eta2[e], m_max, p.theta2)) return 0;
+  if constexpr (HP) {
+    if (p.sigma[e] >= p.sigma_min && (int64_t)p.deg[e] + p.dM <= p.M_max) return 2;      // NaN compares false
+  }
+  return p.x[e + 1] - p.x[e] >= p.h2min ? 1 : 0;
 }
 
-__global__ __launch_bounds__(kBlock) void refine_count_kernel(const double* __restrict__ x, int64_t ne,
-                                                               const double* __restrict__ eta2,
-                                                               const double* __restrict__ mx,
-                                                               double theta2, double h2min,
-                                                               int64_t* __restrict__ cnt) {
+// cnt[block] = bisected | raised << 32 (each at most kBlock; raised = 0 without HP)
+template <bool HP>
+__global__ __launch_bounds__(kBlock) void refine_count_kernel(RefineArgs p, int64_t* __restrict__ cnt) {
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const double m_max = mx[0];
-  const bool m = e < ne && marked(x, eta2, e, m_max, theta2, h2min);
-  const int n = __syncthreads_count(m);
+  const double m_max = p.mx[0];
+  const int act = e < p.ne ? action<HP>(p, e, m_max) : 0;
+  int64_t n = __syncthreads_count(act == 1);
+  if constexpr (HP) n |= (int64_t)__syncthreads_count(act == 2) << 32;
   if (threadIdx.x == 0) cnt[blockIdx.x] = n;
 }
 
-// exclusive offsets of the nb block counts, in place: every thread sums a contiguous run of counts,
-// one workgroup scan of the 256 run sums, then every thread writes its run's offsets
+// exclusive offsets of the nb bisected counts, in place: every thread sums a contiguous run of counts, one workgroup
+// scan of the 256 run sums, then every thread writes its run's offsets; HP: the two totals to counts2 = {bisected,
+// raised}
+template <bool HP>
 __global__ __launch_bounds__(kBlock) void refine_scan_kernel(int64_t* __restrict__ cnt, int64_t nb, int64_t ne,
-                                                              int64_t* __restrict__ ne_new) {
-  __shared__ int64_t sh[kBlock];
+                                                              int64_t* __restrict__ ne_new,
+                                                              int64_t* __restrict__ counts2) {
+  constexpr int NL = HP ? 2 : 1;
   const int tid = threadIdx.x;
   const int64_t per = (nb + kBlock - 1) / kBlock;
   const int64_t lo = tid * per < nb ? tid * per : nb;
   const int64_t hi = lo + per < nb ? lo + per : nb;
-  int64_t s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += cnt[i];
-  sh[tid] = s;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {
-    const int64_t add = tid >= off ? sh[tid - off] : 0;
-    __syncthreads();
-    sh[tid] += add;
-    __syncthreads();
-  }
-  int64_t run = sh[tid] - s;
+  int64_t sum[NL] = {}, total[NL];
   for (int64_t i = lo; i < hi; ++i) {
-    const int64_t v = cnt[i];
+    sum[0] += cnt[i] & 0xffffffffLL;
+    if constexpr (HP) sum[1] += cnt[i] >> 32;
+  }
+  block_scan<NL>(sum, total);
+  int64_t run = sum[0];
+  for (int64_t i = lo; i < hi; ++i) {
+    const int64_t v = cnt[i] & 0xffffffffLL;
     cnt[i] = run;
     run += v;
   }
-  if (tid == kBlock - 1) *ne_new = ne + sh[kBlock - 1];
+  if (tid == kBlock - 1) {
+    *ne_new = ne + total[0];
+    if constexpr (HP) {
+      counts2[0] = total[0];
+      counts2[1] = total[1];
+    }
+  }
 }
 
-__global__ __launch_bounds__(kBlock) void refine_scatter_kernel(const double* __restrict__ x, int64_t ne,
-                                                                 const double* __restrict__ eta2,
-                                                                 const double* __restrict__ mx,
-                                                                 double theta2, double h2min,
-                                                                 const int64_t* __restrict__ offs,
+template <bool HP>
+__global__ __launch_bounds__(kBlock) void refine_scatter_kernel(RefineArgs p, const int64_t* __restrict__ offs,
                                                                  double* __restrict__ x_new,
+                                                                 int32_t* __restrict__ deg_new,
                                                                  int64_t* __restrict__ parent) {
   __shared__ int wsum[kBlock / 64];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t e = (int64_t)blockIdx.x * kBlock + tid;
-  const double m_max = mx[0];
-  const bool m = e < ne && marked(x, eta2, e, m_max, theta2, h2min);
+  const double m_max = p.mx[0];
+  const int act = e < p.ne ? action<HP>(p, e, m_max) : 0;
+  const bool m = act == 1;
   const unsigned long long bal = __ballot(m);
   const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
   if (lane == 0) wsum[wv] = __popcll(bal);
   __syncthreads();
   int before = below;
   for (int w = 0; w < wv; ++w) before += wsum[w];
-  if (e < ne) {
+  if (e < p.ne) {
     const int64_t pos = e + offs[blockIdx.x] + before;
-    const double a = x[e], b = x[e + 1];
+    const double a = p.x[e], b = p.x[e + 1];
     x_new[pos] = a;
     if (parent) parent[pos] = e;
     if (m) {
       x_new[pos + 1] = 0.5 * (a + b);
       if (parent) parent[pos + 1] = e;
     }
-    if (e + 1 == ne) x_new[pos + 1 + (m ? 1 : 0)] = b;
+    if constexpr (HP) {
+      const int32_t d = p.deg[e];
+      deg_new[pos] = act == 2 ? d + p.dM : d;
+      if (m) deg_new[pos + 1] = d;
+    }
+    if (e + 1 == p.ne) x_new[pos + 1 + (m ? 1 : 0)] = b;
   }
+}
+
+// the three launches of both host entries; work: ref_blocks(ne) int64 counters
+template <bool HP>
+hipError_t launch_refine(const RefineArgs& p, void* work, double* x_new, int32_t* deg_new, int64_t* parent,
+                         int64_t* ne_new, int64_t* counts2, hipStream_t s) {
+  const int64_t nb = ref_blocks(p.ne);
+  int64_t* cnt = static_cast<int64_t*>(work);
+  hipLaunchKernelGGL(refine_count_kernel<HP>, dim3((unsigned)nb), dim3(kBlock), 0, s, p, cnt);
+  hipLaunchKernelGGL(refine_scan_kernel<HP>, dim3(1), dim3(kBlock), 0, s, cnt, nb, p.ne, ne_new, counts2);
+  hipLaunchKernelGGL(refine_scatter_kernel<HP>, dim3((unsigned)nb), dim3(kBlock), 0, s, p, cnt, x_new, deg_new,
+                     parent);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -526,7 +515,7 @@ static hipError_t launch_estimate_any(Args a, int tab_rows, int tab_extra, doubl
   hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(kEstBlock), lds, s, a, g);
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(estimate_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
+  hipLaunchKernelGGL(finish_kernel<3>, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out3);
   return hipGetLastError();
 }
 
@@ -559,15 +548,16 @@ hipError_t estimate_ends(const EstimateEndsArgs& a, hipStream_t s) {
 
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                   double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s) {
-  const int64_t nb = ref_blocks(ne);
-  int64_t* cnt = static_cast<int64_t*>(work);
-  const double theta2 = theta * theta, h2min = 2.0 * h_min;
-  hipLaunchKernelGGL(refine_count_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, x, ne, eta2, eta2_max, theta2,
-                     h2min, cnt);
-  hipLaunchKernelGGL(refine_scan_kernel, dim3(1), dim3(kBlock), 0, s, cnt, nb, ne, ne_new);
-  hipLaunchKernelGGL(refine_scatter_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, x, ne, eta2, eta2_max, theta2,
-                     h2min, cnt, x_new, parent);
-  return hipGetLastError();
+  const RefineArgs p{x, ne, eta2, eta2_max, theta * theta, 2.0 * h_min, nullptr, nullptr, 0.0, 0, 0};
+  return launch_refine<false>(p, work, x_new, nullptr, parent, ne_new, nullptr, s);
+}
+
+hipError_t refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
+                     double h_min, const double* sigma, const int32_t* deg, double sigma_min, int dM, int M_max,
+                     void* work, double* x_new, int32_t* deg_new, int64_t* parent, int64_t* ne_new, int64_t* counts2,
+                     hipStream_t s) {
+  const RefineArgs p{x, ne, eta2, eta2_max, theta * theta, 2.0 * h_min, sigma, deg, sigma_min, dM, M_max};
+  return launch_refine<true>(p, work, x_new, deg_new, parent, ne_new, counts2, s);
 }
 
 }  // namespace lssvr

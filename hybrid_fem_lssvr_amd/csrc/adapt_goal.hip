@@ -7,7 +7,8 @@
 // signed, with eta_e^2 for the marking of lssvr_refine and q_e = int_e j u_e dx, so that sum eta_e + sum q_e is the
 // corrected value of J.  The structure of adapt.hip's estimate_tables_body: a lane per element, both row sets staged
 // through LDS at the odd stride, the neighbours' end fluxes from LDS and recomputed from HBM only at chunk edges, the
-// per-block tree and a one-workgroup finish; no atomics, every output bitwise reproducible.
+// per-block tree and the one-workgroup finish of lssvr_adapt.hpp (four slots); no atomics, every output bitwise
+// reproducible.
 #include <cmath>
 #include <type_traits>
 
@@ -21,10 +22,7 @@ namespace lssvr {
 // (97 KiB); with 64 rows the largest launch (M = 33, nq = 32) takes 61 KiB.
 constexpr int kGoalBlock = 64;
 
-static int64_t goal_blocks(int64_t ne) {
-  const int64_t b = (ne + kGoalBlock - 1) / kGoalBlock;
-  return b < 1 ? 1 : (b < kEstMaxBlocks ? b : kEstMaxBlocks);
-}
+static int64_t goal_blocks(int64_t ne) { return chunk_blocks<kGoalBlock>(ne); }
 
 int64_t goal_work_bytes(int64_t ne) { return 8 * 4 * goal_blocks(ne); }
 
@@ -141,51 +139,8 @@ __global__ __launch_bounds__(kGoalBlock) void estimate_goal_kernel(GoalArgs p, G
     }
     __syncthreads();      // rows / sfl / sfr are rewritten by the next chunk
   }
-  // workgroup tree of the per-lane {sum eta, max eta^2, non-finite count, sum q} -> work[4*blockIdx.x ..]
-  red[tid] = bsum;
-  red[kGoalBlock + tid] = bmax;
-  red[2 * kGoalBlock + tid] = bcnt;
-  red[3 * kGoalBlock + tid] = bq;
-  __syncthreads();
-  for (int off = kGoalBlock / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-      red[tid] += red[tid + off];
-      red[kGoalBlock + tid] = fmax(red[kGoalBlock + tid], red[kGoalBlock + tid + off]);
-      red[2 * kGoalBlock + tid] += red[2 * kGoalBlock + tid + off];
-      red[3 * kGoalBlock + tid] += red[3 * kGoalBlock + tid + off];
-    }
-    __syncthreads();
-  }
-  if (tid < 4) p.work[4 * blockIdx.x + tid] = red[tid * kGoalBlock];
-}
-
-// one workgroup: the per-block partials in a fixed order -> out4 (bitwise reproducible)
-__global__ __launch_bounds__(kBlock) void goal_finish_kernel(const double* __restrict__ part, int nb,
-                                                              double* __restrict__ out4) {
-  __shared__ double sh[4][kBlock];
-  const int tid = threadIdx.x;
-  double s = 0.0, m = 0.0, c = 0.0, q = 0.0;
-  for (int i = tid; i < nb; i += kBlock) {
-    s += part[4 * i];
-    m = fmax(m, part[4 * i + 1]);
-    c += part[4 * i + 2];
-    q += part[4 * i + 3];
-  }
-  sh[0][tid] = s;
-  sh[1][tid] = m;
-  sh[2][tid] = c;
-  sh[3][tid] = q;
-  __syncthreads();
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-      sh[0][tid] += sh[0][tid + off];
-      sh[1][tid] = fmax(sh[1][tid], sh[1][tid + off]);
-      sh[2][tid] += sh[2][tid + off];
-      sh[3][tid] += sh[3][tid + off];
-    }
-    __syncthreads();
-  }
-  if (tid < 4) out4[tid] = sh[tid][0];
+  // the per-lane {sum eta, max eta^2, non-finite count, sum q} -> work[4*blockIdx.x ..]
+  reduce_partials<kGoalBlock, 4>(red, tid, {bsum, bmax, bcnt, bq}, p.work);
 }
 
 template <int MT>
@@ -211,7 +166,7 @@ hipError_t estimate_goal(GoalArgs a, bool point_major, double* out4, hipStream_t
   hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(kGoalBlock), lds, s, a, g);
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(goal_finish_kernel, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out4);
+  hipLaunchKernelGGL(finish_kernel<4>, dim3(1), dim3(kBlock), 0, s, a.work, (int)nb, out4);
   return hipGetLastError();
 }
 

@@ -1,8 +1,9 @@
-// hp-adaptive refinement (no reference counterpart): what chooses the degrees of a mesh that
-// lssvr_enhance_subset enhances with one degree per element.
+// hp-adaptive refinement (no reference counterpart): what surrounds the choice of the degrees of
+// a mesh that lssvr_enhance_subset enhances with one degree per element.
 //   - decay rate of each element's Legendre coefficients (lssvr_smoothness)
-//   - threshold marking, then raise the degree where the decay is fast, bisect where it is not (lssvr_refine_hp)
 //   - stable counting sort of the element indices by degree (lssvr_group_by_degree)
+// The marking itself (lssvr_refine_hp: raise the degree where the decay is fast, bisect where it is not) is the HP
+// instance of adapt.hip's marking kernels.
 // The structure of adapt.hip: a lane per element, W staged through LDS at an odd stride, no atomics, every output
 // bitwise reproducible from run to run.
 #include <cmath>
@@ -74,110 +75,6 @@ __global__ __launch_bounds__(kEstBlock) void smoothness_kernel(const double* __r
 }
 
 // ---------------------------------------------------------------------------
-// hp marking: count per block, one-block scan, scatter (the launches of lssvr_refine)
-// ---------------------------------------------------------------------------
-struct RefineHpArgs {
-  const double* x;
-  int64_t ne;
-  const double* eta2;
-  const double* mx;
-  double theta2, h2min;
-  const double* sigma;
-  const int32_t* deg;
-  double sigma_min;
-  int dM, M_max;
-};
-
-// 0: unchanged, 1: bisected, 2: degree raised
-__device__ __forceinline__ int hp_action(const RefineHpArgs& p, int64_t e, double m_max) {
-  if (!indicator_marked(p.eta2[e], m_max, p.theta2)) return 0;
-  if (p.sigma[e] >= p.sigma_min && (int64_t)p.deg[e] + p.dM <= p.M_max) return 2;      // NaN compares false
-  return p.x[e + 1] - p.x[e] >= p.h2min ? 1 : 0;
-}
-
-// cnt[block] = bisected | raised << 32 (each at most kBlock)
-__global__ __launch_bounds__(kBlock) void refine_hp_count_kernel(RefineHpArgs p, int64_t* __restrict__ cnt) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const double m_max = p.mx[0];
-  const int act = e < p.ne ? hp_action(p, e, m_max) : 0;
-  const int ns = __syncthreads_count(act == 1);
-  const int nr = __syncthreads_count(act == 2);
-  if (threadIdx.x == 0) cnt[blockIdx.x] = (int64_t)ns | ((int64_t)nr << 32);
-}
-
-// refine_scan_kernel of adapt.hip on the packed counts: exclusive offsets of the bisected counts in place, the two
-// totals to counts2 = {bisected, raised}
-__global__ __launch_bounds__(kBlock) void refine_hp_scan_kernel(int64_t* __restrict__ cnt, int64_t nb, int64_t ne,
-                                                                int64_t* __restrict__ ne_new,
-                                                                int64_t* __restrict__ counts2) {
-  __shared__ int64_t sh[kBlock];
-  __shared__ int64_t shr[kBlock];
-  const int tid = threadIdx.x;
-  const int64_t per = (nb + kBlock - 1) / kBlock;
-  const int64_t lo = tid * per < nb ? tid * per : nb;
-  const int64_t hi = lo + per < nb ? lo + per : nb;
-  int64_t s = 0, r = 0;
-  for (int64_t i = lo; i < hi; ++i) {
-    s += cnt[i] & 0xffffffffLL;
-    r += cnt[i] >> 32;
-  }
-  sh[tid] = s;
-  shr[tid] = r;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {
-    const int64_t add = tid >= off ? sh[tid - off] : 0;
-    const int64_t addr = tid >= off ? shr[tid - off] : 0;
-    __syncthreads();
-    sh[tid] += add;
-    shr[tid] += addr;
-    __syncthreads();
-  }
-  int64_t run = sh[tid] - s;
-  for (int64_t i = lo; i < hi; ++i) {
-    const int64_t v = cnt[i] & 0xffffffffLL;
-    cnt[i] = run;
-    run += v;
-  }
-  if (tid == kBlock - 1) {
-    *ne_new = ne + sh[kBlock - 1];
-    counts2[0] = sh[kBlock - 1];
-    counts2[1] = shr[kBlock - 1];
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void refine_hp_scatter_kernel(RefineHpArgs p, const int64_t* __restrict__ offs,
-                                                                   double* __restrict__ x_new,
-                                                                   int32_t* __restrict__ deg_new,
-                                                                   int64_t* __restrict__ parent) {
-  __shared__ int wsum[kBlock / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t e = (int64_t)blockIdx.x * kBlock + tid;
-  const double m_max = p.mx[0];
-  const int act = e < p.ne ? hp_action(p, e, m_max) : 0;
-  const bool m = act == 1;
-  const unsigned long long bal = __ballot(m);
-  const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-  if (lane == 0) wsum[wv] = __popcll(bal);
-  __syncthreads();
-  int before = below;
-  for (int w = 0; w < wv; ++w) before += wsum[w];
-  if (e < p.ne) {
-    const int64_t pos = e + offs[blockIdx.x] + before;
-    const double a = p.x[e], b = p.x[e + 1];
-    const int32_t d = p.deg[e];
-    x_new[pos] = a;
-    deg_new[pos] = act == 2 ? d + p.dM : d;
-    if (parent) parent[pos] = e;
-    if (m) {
-      x_new[pos + 1] = 0.5 * (a + b);
-      deg_new[pos + 1] = d;
-      if (parent) parent[pos + 1] = e;
-    }
-    if (e + 1 == p.ne) x_new[pos + 1 + (m ? 1 : 0)] = b;
-  }
-}
-
-// ---------------------------------------------------------------------------
 // grouping by degree: per-workgroup histograms, one scanning workgroup, scatter
 // ---------------------------------------------------------------------------
 constexpr int kGroupBins = 32;          // degrees 2 .. 33
@@ -230,30 +127,22 @@ __global__ __launch_bounds__(kBlock) void group_hist_kernel(const int32_t* __res
 // bin's first entry is the start of its degree in ids
 __global__ __launch_bounds__(kBlock) void group_scan_kernel(int64_t* __restrict__ hist, int nb,
                                                             int64_t* __restrict__ offsets) {
-  __shared__ int64_t sh[kBlock];
   const int tid = threadIdx.x;
   const int n = kGroupBins * nb;
   const int per = (n + kBlock - 1) / kBlock;
   const int lo = tid * per < n ? tid * per : n;
   const int hi = lo + per < n ? lo + per : n;
-  int64_t s = 0;
-  for (int i = lo; i < hi; ++i) s += hist[i];
-  sh[tid] = s;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {
-    const int64_t add = tid >= off ? sh[tid - off] : 0;
-    __syncthreads();
-    sh[tid] += add;
-    __syncthreads();
-  }
-  int64_t run = sh[tid] - s;
+  int64_t sum[1] = {}, total[1];
+  for (int i = lo; i < hi; ++i) sum[0] += hist[i];
+  block_scan<1>(sum, total);
+  int64_t run = sum[0];
   for (int i = lo; i < hi; ++i) {
     const int64_t v = hist[i];
     hist[i] = run;
     if (i % nb == 0) offsets[2 + i / nb] = run;
     run += v;
   }
-  if (tid == kBlock - 1) offsets[2 + kGroupBins] = sh[kBlock - 1];
+  if (tid == kBlock - 1) offsets[2 + kGroupBins] = total[0];
   if (tid < 2) offsets[tid] = 0;
 }
 
@@ -302,20 +191,6 @@ hipError_t smoothness(const double* W, int ldw, const int32_t* deg, int64_t ne, 
   const size_t lds = sizeof(double) * (size_t)kEstBlock * ms;
   hipLaunchKernelGGL(smoothness_kernel, dim3((unsigned)est_blocks(ne)), dim3(kEstBlock), lds, s, W, ldw, ms, deg, ne,
                      sigma);
-  return hipGetLastError();
-}
-
-hipError_t refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
-                     double h_min, const double* sigma, const int32_t* deg, double sigma_min, int dM, int M_max,
-                     void* work, double* x_new, int32_t* deg_new, int64_t* parent, int64_t* ne_new, int64_t* counts2,
-                     hipStream_t s) {
-  const int64_t nb = ref_blocks(ne);
-  int64_t* cnt = static_cast<int64_t*>(work);
-  const RefineHpArgs p{x, ne, eta2, eta2_max, theta * theta, 2.0 * h_min, sigma, deg, sigma_min, dM, M_max};
-  hipLaunchKernelGGL(refine_hp_count_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, p, cnt);
-  hipLaunchKernelGGL(refine_hp_scan_kernel, dim3(1), dim3(kBlock), 0, s, cnt, nb, ne, ne_new, counts2);
-  hipLaunchKernelGGL(refine_hp_scatter_kernel, dim3((unsigned)nb), dim3(kBlock), 0, s, p, cnt, x_new, deg_new,
-                     parent);
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
-// What the estimator / h-refinement kernels (adapt.hip), the hp kernels (adapt_hp.hip) and the goal-oriented
-// estimator (adapt_goal.hip) share: the chunk geometry, the coalesced staging of W rows through LDS, the marking
-// predicate, and the Legendre table, end values and flux jumps of the estimators.
+// What the estimator / refinement kernels (adapt.hip), the smoothness / grouping kernels (adapt_hp.hip) and the
+// goal-oriented estimator (adapt_goal.hip) share: the chunk geometry, the coalesced staging of W rows through LDS, the
+// marking predicate, the one-workgroup exclusive scan, the deterministic reduction (per-block tree + finish kernel),
+// and the Legendre table, end values and flux jumps of the estimators.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -12,10 +13,13 @@ namespace lssvr {
 constexpr int kEstBlock = 128;          // elements per workgroup chunk (two waves)
 constexpr int kEstMaxBlocks = 4096;     // grid cap: partials of the reduction in `work`
 
-inline int64_t est_blocks(int64_t ne) {
-  const int64_t b = (ne + kEstBlock - 1) / kEstBlock;
+// workgroups of a grid-stride launch over chunks of BLOCK elements
+template <int BLOCK>
+inline int64_t chunk_blocks(int64_t ne) {
+  const int64_t b = (ne + BLOCK - 1) / BLOCK;
   return b < 1 ? 1 : (b < kEstMaxBlocks ? b : kEstMaxBlocks);
 }
+inline int64_t est_blocks(int64_t ne) { return chunk_blocks<kEstBlock>(ne); }
 inline int64_t ref_blocks(int64_t ne) {
   const int64_t b = (ne + kBlock - 1) / kBlock;
   return b < 1 ? 1 : b;
@@ -43,6 +47,67 @@ __device__ __forceinline__ void stage_rows(double* __restrict__ rows, const doub
 // mx = the device max of the finite eta2 (out3[1] of lssvr_estimate)
 __device__ __forceinline__ bool indicator_marked(double v, double mx, double theta2) {
   return !(fabs(v) < INFINITY) || (mx > 0.0 && v >= theta2 * mx);
+}
+
+// One workgroup of kBlock threads, NL lanes of int64 (integer: exact): v[l] = this thread's run sum in, the exclusive
+// prefix of the kBlock run sums out (Hillis-Steele over LDS); total[l] = the sum of all of them.  Every thread of the
+// workgroup calls it, once per kernel.
+template <int NL>
+__device__ __forceinline__ void block_scan(int64_t (&v)[NL], int64_t (&total)[NL]) {
+  __shared__ int64_t sh[NL][kBlock];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int l = 0; l < NL; ++l) sh[l][tid] = v[l];
+  __syncthreads();
+  for (int off = 1; off < kBlock; off <<= 1) {
+    int64_t add[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) add[l] = tid >= off ? sh[l][tid - off] : 0;
+    __syncthreads();
+#pragma unroll
+    for (int l = 0; l < NL; ++l) sh[l][tid] += add[l];
+    __syncthreads();
+  }
+#pragma unroll
+  for (int l = 0; l < NL; ++l) {
+    v[l] = sh[l][tid] - v[l];
+    total[l] = sh[l][kBlock - 1];
+  }
+}
+
+// Workgroup tree (halving offsets: a fixed order, bitwise reproducible) of the BLOCK threads' NS values v[] ->
+// out[NS*blockIdx.x ..]: slot 1 is a maximum, the other slots are sums.  red: NS*BLOCK doubles of LDS, slot-major.
+template <int BLOCK, int NS>
+__device__ __forceinline__ void reduce_partials(double* __restrict__ red, int tid, const double (&v)[NS],
+                                                double* __restrict__ out) {
+#pragma unroll
+  for (int s = 0; s < NS; ++s) red[s * BLOCK + tid] = v[s];
+  __syncthreads();
+  for (int off = BLOCK / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const double a = red[s * BLOCK + tid], b = red[s * BLOCK + tid + off];
+        red[s * BLOCK + tid] = s == 1 ? fmax(a, b) : a + b;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < NS) out[NS * blockIdx.x + tid] = red[tid * BLOCK];
+}
+
+// one workgroup: the nb per-block partials part[NS*i ..] in a fixed order -> out[0..NS) (bitwise reproducible)
+template <int NS>
+__global__ __launch_bounds__(kBlock) void finish_kernel(const double* __restrict__ part, int nb,
+                                                         double* __restrict__ out) {
+  __shared__ double sh[NS * kBlock];
+  const int tid = threadIdx.x;
+  double v[NS] = {};
+  for (int i = tid; i < nb; i += kBlock) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) v[s] = s == 1 ? fmax(v[s], part[NS * i + s]) : v[s] + part[NS * i + s];
+  }
+  reduce_partials<kBlock, NS>(sh, tid, v, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -305,7 +305,7 @@ int64_t goal_work_bytes(int64_t ne);
 // out4 = {sum of eta over the elements whose eta^2 is finite, max finite eta^2, non-finite count, sum of finite q_e}
 hipError_t estimate_goal(GoalArgs a, bool point_major, double* out4, hipStream_t s);
 
-// hp-adaptive refinement (adapt_hp.hip)
+// hp-adaptive refinement (adapt_hp.hip; refine_hp: adapt.hip, the kernels of refine)
 hipError_t smoothness(const double* W, int ldw, const int32_t* deg, int64_t ne, double* sigma, hipStream_t s);
 hipError_t refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                      double h_min, const double* sigma, const int32_t* deg, double sigma_min, int dM, int M_max,

@@ -1072,19 +1072,41 @@ def gauss_rule(nq):
     return np.array(xi[:nq], dtype=np.float64), np.array(wt[:nq], dtype=np.float64)
 
 
+def _adapt_scratch(work, x, ne, entry="lssvr_adapt_work_bytes"):
+    """The device scratch of ``entry(ne)`` bytes an adaptive entry takes: a fresh buffer on ``x``'s device, or the
+    caller's ``work`` once it is a device buffer of that size."""
+    nbytes = getattr(_capi.load(), entry)(int(ne))
+    if work is None:
+        return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    _dev(work, "work")
+    if work.numel() * 8 < nbytes:
+        raise ValueError(f"work is smaller than {entry}(ne)")
+    return work
+
+
 def adapt_work(x, ne):
     """Device scratch of ``lssvr_adapt_work_bytes(ne)`` bytes for :func:`estimate` / :func:`refine`."""
-    nbytes = _capi.load().lssvr_adapt_work_bytes(int(ne))
-    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    return _adapt_scratch(None, x, ne)
 
 
-def _check_work(work, x, ne):
-    if work is None:
-        return adapt_work(x, ne)
-    _dev(work, "work")
-    if work.numel() * 8 < _capi.load().lssvr_adapt_work_bytes(int(ne)):
-        raise ValueError("work is smaller than lssvr_adapt_work_bytes(ne)")
-    return work
+def goal_work(x, ne):
+    """Device scratch of ``lssvr_goal_work_bytes(ne)`` bytes for :func:`estimate_goal`."""
+    return _adapt_scratch(None, x, ne, "lssvr_goal_work_bytes")
+
+
+def _pair(name, v):
+    """A (left, right) argument as the C ABI takes it: double[2]."""
+    v = tuple(float(t) for t in v)
+    if len(v) != 2:
+        raise ValueError(f"{name} must be a pair (left, right)")
+    return (ctypes.c_double * 2)(*v)
+
+
+def _same_device(x, **tensors):
+    """Every given tensor lives where ``x`` does (``None`` entries: arguments not given)."""
+    for nm, t in tensors.items():
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, x on {x.device}")
 
 
 def _estimate_out(x, ne, want_jump):
@@ -1120,7 +1142,7 @@ def estimate(x, W, nq, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_values=None, poi
         raise ValueError("W must be [ne, M]")
     rhs_id, params = _rhs(rhs, rhs_values, ne * int(nq), "ne*nq", point_major)
     eta2, jump, out3 = _estimate_out(x, ne, want_jump)
-    work = _check_work(work, x, ne)
+    work = _adapt_scratch(work, x, ne)
     rc = lib.lssvr_estimate(_ptr(x), _ptr(W), ne, int(W.shape[1]), int(nq), rhs_id, params,
                             _ptr(rhs_values), _ptr(eta2), _ptr(jump), _ptr(out3), _ptr(work),
                             _stream(stream))
@@ -1155,7 +1177,7 @@ def estimate_varcoef(x, W, nq, a_values, da_values, rhs_values, a_ends, *, point
     if tuple(a_ends.shape) != (ne, 2):
         raise ValueError(f"a_ends must be [ne, 2] = [{ne}, 2], got {list(a_ends.shape)}")
     eta2, jump, out3 = _estimate_out(x, ne, want_jump)
-    work = _check_work(work, x, ne)
+    work = _adapt_scratch(work, x, ne)
     kind, tabs = _variant(a_values, da_values, rhs_values, c_values)
     name = f"lssvr_estimate_{kind}"
     rc = getattr(lib, name)(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, *tabs, _layout(point_major), _ptr(a_ends),
@@ -1184,25 +1206,12 @@ def estimate_ends(x, W, end_kinds, kappa, g, a_ends, eta2, out3, *, stream=None)
     if eta2.numel() != ne or out3.numel() != 3:
         raise ValueError(f"eta2 must hold ne = {ne} doubles and out3 three, got {eta2.numel()} and {out3.numel()}")
     kinds, kap = _end_kinds(end_kinds, kappa)
-    pairs = []
-    for nm, v in (("g", g), ("a_ends", a_ends)):
-        v = tuple(float(t) for t in v)
-        if len(v) != 2:
-            raise ValueError(f"{nm} must be a pair (left, right)")
-        pairs.append((ctypes.c_double * 2)(*v))
-    for nm, t in (("W", W), ("eta2", eta2), ("out3", out3)):
-        if t.device != x.device:
-            raise RuntimeError(f"{nm} lives on {t.device}, x on {x.device}")
+    pairs = _pair("g", g), _pair("a_ends", a_ends)
+    _same_device(x, W=W, eta2=eta2, out3=out3)
     rc = lib.lssvr_estimate_ends(_ptr(x), _ptr(W), int(W.shape[1]), ne, kinds[0], kinds[1], kap, *pairs, _ptr(eta2),
                                  _ptr(out3), _stream(stream))
     _capi.check(rc, "lssvr_estimate_ends")
     return eta2, out3
-
-
-def goal_work(x, ne):
-    """Device scratch of ``lssvr_goal_work_bytes(ne)`` bytes for :func:`estimate_goal`."""
-    nbytes = _capi.load().lssvr_goal_work_bytes(int(ne))
-    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
 
 
 def estimate_goal(x, Wu, Wz, nq, a_values, da_values, rhs_values, goal_values, a_ends, *, c_values=None,
@@ -1239,27 +1248,14 @@ def estimate_goal(x, Wu, Wz, nq, a_values, da_values, rhs_values, goal_values, a
     if tuple(a_ends.shape) != (ne, 2):
         raise ValueError(f"a_ends must be [ne, 2] = [{ne}, 2], got {list(a_ends.shape)}")
     kinds, kap = _end_kinds(end_kinds, kappa)
-    pairs = []
-    for nm, v in (("g", g), ("a_bnd", a_bnd)):
-        v = tuple(float(t) for t in v)
-        if len(v) != 2:
-            raise ValueError(f"{nm} must be a pair (left, right)")
-        pairs.append((ctypes.c_double * 2)(*v))
+    pairs = _pair("g", g), _pair("a_bnd", a_bnd)
     if q is not None:
         _dev(q, "q")
         if q.numel() != ne:
             raise ValueError(f"q must hold ne = {ne} doubles, got {q.numel()}")
-    if work is None:
-        work = goal_work(x, ne)
-    else:
-        _dev(work, "work")
-        if work.numel() * 8 < lib.lssvr_goal_work_bytes(ne):
-            raise ValueError("work is smaller than lssvr_goal_work_bytes(ne)")
-    tensors = dict(Wu=Wu, Wz=Wz, a_values=a_values, da_values=da_values, rhs_values=rhs_values,
-                   goal_values=goal_values, a_ends=a_ends, work=work, c_values=c_values, q=q)
-    for nm, t in tensors.items():
-        if t is not None and t.device != x.device:
-            raise RuntimeError(f"{nm} lives on {t.device}, x on {x.device}")
+    work = _adapt_scratch(work, x, ne, "lssvr_goal_work_bytes")
+    _same_device(x, Wu=Wu, Wz=Wz, a_values=a_values, da_values=da_values, rhs_values=rhs_values,
+                 goal_values=goal_values, a_ends=a_ends, work=work, c_values=c_values, q=q)
     eta = torch.empty(ne, dtype=torch.float64, device=x.device)
     eta2 = torch.empty(ne, dtype=torch.float64, device=x.device)
     out4 = torch.empty(4, dtype=torch.float64, device=x.device)
@@ -1272,30 +1268,64 @@ def estimate_goal(x, Wu, Wz, nq, a_values, da_values, rhs_values, goal_values, a
     return eta, eta2, out4
 
 
-def refine(x, eta2, eta2_max, theta, *, h_min=0.0, want_parent=False, work=None, stream=None):
-    """Mark (eta2 non-finite, or eta2 >= theta^2 * max with max > 0; element >= 2 h_min long) and
-    bisect (``lssvr_refine``).  ``eta2_max``: device float64 holding max (e.g. ``out3[1:2]`` of
-    :func:`estimate`).  Returns (x_new float64[ne_new+1], parent int64[ne_new] | None), trimmed to
-    the new length -- one synchronisation, for the count."""
+def _refine(x, eta2, eta2_max, theta, h_min, want_parent, work, stream, hp=None):
+    """What :func:`refine` and :func:`refine_hp` share: the checks, the outputs sized for the case that every element
+    is bisected, the launch, ONE synchronisation for the device counters and the trim to the new length.  ``hp`` =
+    (sigma, deg, sigma_min, dM, M_max) selects ``lssvr_refine_hp``.  Returns (x_new, deg_new | None, parent | None,
+    the counters after ne_new)."""
     lib = _capi.load()
     _dev(x, "x")
     _dev(eta2, "eta2")
     _dev(eta2_max, "eta2_max")
     ne = x.numel() - 1
-    if eta2.numel() != ne:
-        raise ValueError("eta2 must hold ne doubles")
+    if hp is None:
+        if eta2.numel() != ne:
+            raise ValueError("eta2 must hold ne doubles")
+    else:
+        sigma, deg, sigma_min, dM, M_max = hp
+        _dev(sigma, "sigma")
+        if ne < 1:
+            raise ValueError("need at least one element")
+        if eta2.numel() != ne or sigma.numel() != ne:
+            raise ValueError("eta2 and sigma must hold ne doubles")
+        if eta2_max.numel() < 1:
+            raise ValueError("eta2_max must hold one double")
+        _degrees(deg, ne)
     theta = float(theta)
     if not 0.0 <= theta <= 1.0:
         raise ValueError(f"theta must be in [0, 1], got {theta}")
+    if hp is not None:
+        if int(dM) != dM or dM < 1:
+            raise ValueError(f"dM must be a positive integer, got {dM!r}")
+        if int(M_max) != M_max or not MIN_DEGREE <= M_max <= MAX_DEGREE:
+            raise ValueError(f"M_max must be in [2, 33], got {M_max!r}")
     x_new = torch.empty(2 * ne + 1, dtype=torch.float64, device=x.device)
+    deg_new = torch.empty(2 * ne, dtype=torch.int32, device=x.device) if hp is not None else None
     parent = torch.empty(2 * ne, dtype=torch.int64, device=x.device) if want_parent else None
-    ne_new = torch.empty(1, dtype=torch.int64, device=x.device)
-    work = _check_work(work, x, ne)
-    rc = lib.lssvr_refine(_ptr(x), ne, _ptr(eta2), _ptr(eta2_max), theta, float(h_min), _ptr(work),
-                          _ptr(x_new), _ptr(parent), _ptr(ne_new), _stream(stream))
-    _capi.check(rc, "lssvr_refine")
-    n = int(ne_new.item())
-    return x_new[:n + 1], (parent[:n] if parent is not None else None)
+    cnt = torch.empty(1 if hp is None else 3, dtype=torch.int64, device=x.device)    # {ne_new [, bisected, raised]}
+    work = _adapt_scratch(work, x, ne)
+    head = (_ptr(x), ne, _ptr(eta2), _ptr(eta2_max), theta, float(h_min))
+    if hp is None:
+        name = "lssvr_refine"
+        rc = lib.lssvr_refine(*head, _ptr(work), _ptr(x_new), _ptr(parent), _ptr(cnt), _stream(stream))
+    else:
+        name = "lssvr_refine_hp"
+        rc = lib.lssvr_refine_hp(*head, _ptr(sigma), _ptr(deg), float(sigma_min), int(dM), int(M_max), _ptr(work),
+                                 _ptr(x_new), _ptr(deg_new), _ptr(parent), _ptr(cnt[0:1]), _ptr(cnt[1:3]),
+                                 _stream(stream))
+    _capi.check(rc, name)
+    n, *counts = (int(v) for v in cnt.cpu())
+    return (x_new[:n + 1], deg_new[:n] if hp is not None else None, parent[:n] if parent is not None else None,
+            tuple(counts))
+
+
+def refine(x, eta2, eta2_max, theta, *, h_min=0.0, want_parent=False, work=None, stream=None):
+    """Mark (eta2 non-finite, or eta2 >= theta^2 * max with max > 0; element >= 2 h_min long) and
+    bisect (``lssvr_refine``).  ``eta2_max``: device float64 holding max (e.g. ``out3[1:2]`` of
+    :func:`estimate`).  Returns (x_new float64[ne_new+1], parent int64[ne_new] | None), trimmed to
+    the new length -- one synchronisation, for the count."""
+    x_new, _, parent, _ = _refine(x, eta2, eta2_max, theta, h_min, want_parent, work, stream)
+    return x_new, parent
 
 
 MIN_DEGREE, MAX_DEGREE = 2, 33       # the degree parameter M of an element (lssvr_enhance: 2 <= M <= 33)
@@ -1345,37 +1375,7 @@ def refine_hp(x, eta2, eta2_max, theta, sigma, deg, *, sigma_min=1.0, dM=2, M_ma
     bisected when it is at least 2 ``h_min`` long (both halves keep ``deg``), else stays.  ``sigma`` float64[ne]
     from :func:`smoothness`, ``deg`` int32[ne].  Returns (x_new float64[ne_new+1], deg_new int32[ne_new], parent
     int64[ne_new] | None, (bisected, raised)), trimmed to the new length -- one synchronisation, for the counts."""
-    lib = _capi.load()
-    _dev(x, "x")
-    _dev(eta2, "eta2")
-    _dev(eta2_max, "eta2_max")
-    _dev(sigma, "sigma")
-    ne = x.numel() - 1
-    if ne < 1:
-        raise ValueError("need at least one element")
-    if eta2.numel() != ne or sigma.numel() != ne:
-        raise ValueError("eta2 and sigma must hold ne doubles")
-    if eta2_max.numel() < 1:
-        raise ValueError("eta2_max must hold one double")
-    _degrees(deg, ne)
-    theta = float(theta)
-    if not 0.0 <= theta <= 1.0:
-        raise ValueError(f"theta must be in [0, 1], got {theta}")
-    if int(dM) != dM or dM < 1:
-        raise ValueError(f"dM must be a positive integer, got {dM!r}")
-    if int(M_max) != M_max or not MIN_DEGREE <= M_max <= MAX_DEGREE:
-        raise ValueError(f"M_max must be in [2, 33], got {M_max!r}")
-    x_new = torch.empty(2 * ne + 1, dtype=torch.float64, device=x.device)
-    deg_new = torch.empty(2 * ne, dtype=torch.int32, device=x.device)
-    parent = torch.empty(2 * ne, dtype=torch.int64, device=x.device) if want_parent else None
-    cnt = torch.empty(3, dtype=torch.int64, device=x.device)         # {ne_new, bisected, raised}
-    work = _check_work(work, x, ne)
-    rc = lib.lssvr_refine_hp(_ptr(x), ne, _ptr(eta2), _ptr(eta2_max), theta, float(h_min), _ptr(sigma), _ptr(deg),
-                             float(sigma_min), int(dM), int(M_max), _ptr(work), _ptr(x_new), _ptr(deg_new),
-                             _ptr(parent), _ptr(cnt[0:1]), _ptr(cnt[1:3]), _stream(stream))
-    _capi.check(rc, "lssvr_refine_hp")
-    n, split, raised = (int(v) for v in cnt.cpu())
-    return x_new[:n + 1], deg_new[:n], (parent[:n] if parent is not None else None), (split, raised)
+    return _refine(x, eta2, eta2_max, theta, h_min, want_parent, work, stream, (sigma, deg, sigma_min, dM, M_max))
 
 
 def group_by_degree(deg, *, work=None, stream=None):

@@ -906,33 +906,59 @@ class FEMLSSVRPrimalSolver:
         self.lssvr_functions = _ElementFunctions(nodes, primal.W)
         return GoalEstimate(eta, eta2, out4), marking
 
-    def _solve_adaptive_goal(self, goal, tol, theta, max_elements, max_iter, h_min, nq):
-        """The rounds of ``solve_adaptive(goal=j)``; the arguments it shares with the residual loop are validated."""
-        nq = self._goal_nq(nq)
+    def _adapt_rounds(self, tol, max_elements, max_iter, round_fn, start=None):
+        """The round loop of every ``solve_adaptive`` mode; host logic only, so a scripted ``round_fn`` can drive it.
+        ``round_fn()`` solves and estimates on ``self.mesh`` -> (ne, estimate, the record's further fields, refine);
+        ``refine()`` -> (the new nodes as a host array, what the refinement changes in the record: counts) or
+        ``None`` for a veto of the mode's own.  It stops at ``tol``, after ``max_iter`` rounds (neither refines), at
+        a veto, when every count is 0, or when the new mesh would exceed ``max_elements``; otherwise the record is
+        updated and ``self.mesh`` becomes the new nodes.  ``start(ne)``: the mode's own check of the initial mesh,
+        before ``adapt_history`` is reset.  Returns the last estimate."""
         if self.mesh is None:
             self.mesh = self._default_mesh()
         if self.mesh.nelements > max_elements:
             raise ValueError(f"the initial mesh has {self.mesh.nelements} elements > max_elements = {max_elements}")
+        if start is not None:
+            start(self.mesh.nelements)
         self.adapt_history = []
         est = float("nan")
         for it in range(max_iter):
-            ge, marking = self._solve_goal(goal, nq)
-            ne = int(ge.eta.size)
-            est = float(np.abs(ge.eta).sum()) if ge.n_nonfinite == 0 else float("inf")
-            rec = dict(ne=ne, estimate=est, correction=ge.correction, value=ge.value, marked=0)
+            ne, est, fields, refine = round_fn()
+            rec = dict(ne=ne, estimate=est, **fields)
             self.adapt_history.append(rec)
             if (tol is not None and est <= float(tol)) or it + 1 == max_iter:
                 break
-            # marked from the jump-free form: half a jump at a node shared with a coarse neighbour stays as it is
-            # however often the fine element is bisected, and the loop would stall on it
-            mark2, mark4 = marking()
-            x_new, _ = ops.refine(self.enhanced.nodes, mark2, mark4[1:2], theta, h_min=h_min)
-            ne_new = x_new.numel() - 1
-            if ne_new == ne or ne_new > max_elements:
+            out = refine()
+            if out is None:
                 break
-            rec["marked"] = ne_new - ne
-            self.mesh = LineMesh.from_nodes(x_new.cpu().numpy())
+            nodes, counts = out
+            if not any(counts.values()) or len(nodes) - 1 > max_elements:
+                break
+            rec.update(counts)
+            self.mesh = LineMesh.from_nodes(nodes)
         return est
+
+    def _refine_h(self, ne, eta2, eta2_max, theta, h_min):
+        """``refine()`` of the modes that only bisect (:meth:`_adapt_rounds`)."""
+        x_new, _ = ops.refine(self.enhanced.nodes, eta2, eta2_max, theta, h_min=h_min)
+        return x_new.cpu().numpy(), dict(marked=x_new.numel() - 1 - ne)
+
+    def _solve_adaptive_goal(self, goal, tol, theta, max_elements, max_iter, h_min, nq):
+        """The rounds of ``solve_adaptive(goal=j)``; the arguments it shares with the residual loop are validated."""
+        nq = self._goal_nq(nq)
+
+        def round_fn():
+            ge, marking = self._solve_goal(goal, nq)
+            ne = int(ge.eta.size)
+            est = float(np.abs(ge.eta).sum()) if ge.n_nonfinite == 0 else float("inf")
+
+            def refine():
+                # marked from the jump-free form: half a jump at a node shared with a coarse neighbour stays as it is
+                # however often the fine element is bisected, and the loop would stall on it
+                mark2, mark4 = marking()
+                return self._refine_h(ne, mark2, mark4[1:2], theta, h_min)
+            return ne, est, dict(correction=ge.correction, value=ge.value, marked=0), refine
+        return self._adapt_rounds(tol, max_elements, max_iter, round_fn)
 
     def solve_adaptive(self, tol=None, theta=0.5, max_elements=100000, max_iter=50, h_min=0.0, nq=None, *,
                        mode="h", M_max=None, dM=2, sigma_min=1.0, max_dof=None, goal=None):
@@ -989,29 +1015,19 @@ class FEMLSSVRPrimalSolver:
         if goal is not None:
             return self._solve_adaptive_goal(goal, tol, theta, int(max_elements), int(max_iter), float(h_min), nq)
         nq = self._nq(nq)
-        if self.mesh is None:
-            self.mesh = self._default_mesh()
-        if self.mesh.nelements > max_elements:
-            raise ValueError(f"the initial mesh has {self.mesh.nelements} elements > max_elements = {max_elements}")
-        self.adapt_history = []
-        est = float("nan")
-        for it in range(int(max_iter)):
+
+        def round_fn():
             self.solve()
-            eta2, out3 = self._estimate_dev(nq)
-            s = out3.cpu().numpy()
-            ne = int(eta2.numel())
-            est = float(np.sqrt(s[0])) if s[2] == 0 else float("inf")
-            rec = dict(ne=ne, estimate=est, marked=0)
-            self.adapt_history.append(rec)
-            if (tol is not None and est <= float(tol)) or it + 1 == int(max_iter):
-                break
-            x_new, _ = ops.refine(self.enhanced.nodes, eta2, out3[1:2], theta, h_min=float(h_min))
-            ne_new = x_new.numel() - 1
-            if ne_new == ne or ne_new > max_elements:
-                break
-            rec["marked"] = ne_new - ne
-            self.mesh = LineMesh.from_nodes(x_new.cpu().numpy())
-        return est
+            ne, est, eta2, out3 = self._estimate_round(nq)
+            return ne, est, dict(marked=0), lambda: self._refine_h(ne, eta2, out3[1:2], theta, float(h_min))
+        return self._adapt_rounds(tol, max_elements, int(max_iter), round_fn)
+
+    def _estimate_round(self, nq):
+        """(ne, sqrt(sum eta^2) or inf where an eta^2 is not finite, eta2 device [ne], out3 device [3]) of the
+        residual indicator on the current enhanced solution."""
+        eta2, out3 = self._estimate_dev(nq)
+        s = out3.cpu().numpy()
+        return int(eta2.numel()), (float(np.sqrt(s[0])) if s[2] == 0 else float("inf")), eta2, out3
 
     def _solve_adaptive_hp(self, tol, theta, max_elements, max_iter, h_min, nq, M_max, dM, sigma_min, max_dof):
         """The rounds of ``solve_adaptive(mode="hp")``; the arguments it shares with mode "h" are validated."""
@@ -1029,38 +1045,31 @@ class FEMLSSVRPrimalSolver:
             raise ValueError(f"max_dof must be a positive integer, got {max_dof!r}")
         if nq is not None:
             nq = self._nq(nq)
-        if self.mesh is None:
-            self.mesh = self._default_mesh()
-        if self.mesh.nelements > max_elements:
-            raise ValueError(f"the initial mesh has {self.mesh.nelements} elements > max_elements = {max_elements}")
-        deg = np.full(self.mesh.nelements, M0, dtype=np.int64)
-        if max_dof is not None and deg.sum() > max_dof:
-            raise ValueError(f"the initial mesh has {deg.sum()} coefficients > max_dof = {max_dof}")
-        self.adapt_history = []
-        est = float("nan")
-        for it in range(max_iter):
+        deg = None                     # int64[ne]: the degrees of the current mesh, carried from round to round
+
+        def start(ne):
+            nonlocal deg
+            deg = np.full(ne, M0, dtype=np.int64)
+            if max_dof is not None and deg.sum() > max_dof:
+                raise ValueError(f"the initial mesh has {deg.sum()} coefficients > max_dof = {max_dof}")
+
+        def round_fn():
             self.element_degrees = deg
             self.solve()
-            eta2, out3 = self._estimate_dev(min(32, max(int(deg.max()), 8)) if nq is None else nq)
-            s = out3.cpu().numpy()
-            ne = int(eta2.numel())
-            est = float(np.sqrt(s[0])) if s[2] == 0 else float("inf")
-            rec = dict(ne=ne, estimate=est, marked=0, raised=0, dof=int(deg.sum()))
-            self.adapt_history.append(rec)
-            if (tol is not None and est <= float(tol)) or it + 1 == max_iter:
-                break
-            x, W = self.enhanced.nodes, self.enhanced.W
-            deg_dev = torch.as_tensor(deg.astype(np.int32), device=x.device)
-            sigma = ops.smoothness(x, W, deg_dev)
-            x_new, deg_new, _, (split, raised) = ops.refine_hp(x, eta2, out3[1:2], theta, sigma, deg_dev,
-                                                               sigma_min=float(sigma_min), dM=int(dM),
-                                                               M_max=int(M_max), h_min=h_min)
-            deg_new = deg_new.cpu().numpy().astype(np.int64)
-            if split + raised == 0 or ne + split > max_elements:
-                break
-            if max_dof is not None and deg_new.sum() > max_dof:
-                break
-            rec["marked"], rec["raised"] = split, raised
-            self.mesh = LineMesh.from_nodes(x_new.cpu().numpy())
-            deg = deg_new
-        return est
+            ne, est, eta2, out3 = self._estimate_round(min(32, max(int(deg.max()), 8)) if nq is None else nq)
+
+            def refine():
+                nonlocal deg
+                x, W = self.enhanced.nodes, self.enhanced.W
+                deg_dev = torch.as_tensor(deg.astype(np.int32), device=x.device)
+                sigma = ops.smoothness(x, W, deg_dev)
+                x_new, deg_new, _, (split, raised) = ops.refine_hp(x, eta2, out3[1:2], theta, sigma, deg_dev,
+                                                                   sigma_min=float(sigma_min), dM=int(dM),
+                                                                   M_max=int(M_max), h_min=h_min)
+                deg_new = deg_new.cpu().numpy().astype(np.int64)
+                if max_dof is not None and deg_new.sum() > max_dof:
+                    return None
+                deg = deg_new          # (read by the next round only: a stop of the loop's leaves element_degrees)
+                return x_new.cpu().numpy(), dict(marked=split, raised=raised)
+            return ne, est, dict(marked=0, raised=0, dof=int(deg.sum())), refine
+        return self._adapt_rounds(tol, max_elements, max_iter, round_fn, start)

@@ -633,8 +633,8 @@ int lssvr_smoothness(const double* W, int64_t ldw, const int32_t* deg, int64_t n
  *   ne_new_dev      out (device int64): the new element count
  *   counts2_dev     out (device int64[2]): {elements bisected, elements raised}
  *   work            device scratch of lssvr_adapt_work_bytes(ne) bytes
- * The three launches of lssvr_refine (block counts, a one-workgroup scan, scatter): deterministic, and x_new and
- * parent equal lssvr_refine's bit for bit when nothing is raised.
+ * The three kernels of lssvr_refine (block counts, a one-workgroup scan, scatter) in their hp instance: deterministic,
+ * and x_new and parent equal lssvr_refine's bit for bit when nothing is raised.
  */
 int lssvr_refine_hp(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev,
                     double theta, double h_min, const double* sigma, const int32_t* deg,

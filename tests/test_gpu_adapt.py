@@ -183,8 +183,9 @@ def test_estimate_exact_polynomial_is_rounding_only(dev, M):
 # lssvr_refine
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("ne,theta,h_min", [(1, 0.5, 0.0), (1, 1.0, 0.0), (1, 0.0, 0.0), (2, 0.5, 0.0),
+                                            (255, 0.5, 0.0), (256, 0.5, 0.0), (257, 0.5, 0.0),
                                             (1000, 0.0, 0.0), (1000, 1.0, 0.0), (1000, 0.5, 0.0),
-                                            (4099, 0.3, 3e-4), (2_000_000, 0.5, 0.0),
+                                            (4099, 0.3, 3e-4), (256 * 256 + 1, 0.5, 0.0), (2_000_000, 0.5, 0.0),
                                             (2_000_000, 0.7, 4e-7)])
 def test_refine_vs_numpy(dev, ne, theta, h_min):
     import torch
