@@ -137,6 +137,11 @@ SIGNATURES = {
     "lssvr_goal_work_bytes": _sig([_c_i64], res=_c_i64),
     "lssvr_estimate_goal": _sig([_c_dp, _c_dp, _c_dp, _c_i64, _c_int, _c_int], _REACT_TABLES, [_c_dp, _c_int, _c_dp],
                                 [_c_int, _c_int, _c_hd, _c_hd, _c_hd, _c_int], [_c_dp] * 5, _STREAM),
+    # periodic ends (additive to ABI 7): ..., ne, nc, u, work, work_bytes; x, W, M, ne, a_seam_host, eta2, out3
+    "lssvr_tridiag_periodic_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
+    "lssvr_tridiag_periodic_solve_multi": _sig(_BANDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
+    "lssvr_tridiag_ns_periodic_solve_multi": _sig([_c_dp], _BANDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
+    "lssvr_estimate_seam": _sig([_c_dp, _c_dp, _c_int, _c_i64, _c_hd, _c_dp, _c_dp], _STREAM),
     # hp-adaptive refinement (additive to ABI 7)
     "lssvr_smoothness": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_dp], _STREAM),
     "lssvr_refine_hp": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dbl, _c_int, _c_int, _c_dp,

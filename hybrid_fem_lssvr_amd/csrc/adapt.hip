@@ -4,6 +4,8 @@
 //   - per-element residual indicator  eta_e^2 = h_e^2 ||f + u_e''||_e^2 + h_e/2 (J_e^2 + J_{e+1}^2)
 //     with J_i = u_{i-1}'(x_i) - u_i'(x_i) (lssvr_estimate) and its deterministic reduction
 //   - the same for -(a u')' = f: residual f + a u'' + a' u', J_i the jump of the flux a u' (lssvr_estimate_varcoef)
+//   - the boundary term of a Robin end (lssvr_estimate_ends) and the flux jump across the seam of a
+//     periodic domain (lssvr_estimate_seam, section 22): one thread each, in place on eta2 and out3
 //   - threshold marking + bisection into a new ascending node array (lssvr_refine), and the same three kernels with
 //     the raise-or-bisect rule and the degrees of the new mesh (lssvr_refine_hp)
 // The block scan, the per-block reduction tree and its finish kernel are lssvr_adapt.hpp's.
@@ -336,6 +338,48 @@ __global__ void estimate_ends_kernel(EstimateEndsArgs p) {
   p.out3[2] = cnt;
 }
 
+// The seam term of the indicator on a periodic domain, after an estimator has written eta2 and
+// out3 with J_0 = J_ne = 0: node ne is node 0, and the flux jumps across it like across any interior node,
+//   J = a[0] u_{ne-1}'(x_ne) - a[1] u_0'(x_0),   eta2[ne-1] += h_{ne-1}/2 J^2,   eta2[0] += h_0/2 J^2,
+// with the end derivatives of estimate_ends_kernel; out3 follows as there.  One thread does element ne-1 and then
+// element 0 (ne >= 2: two elements), so there is no atomic and the result is reproducible.
+__global__ void estimate_seam_kernel(EstimateSeamArgs p) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double sum = p.out3[0], mx = p.out3[1], cnt = p.out3[2];
+  double der[2], len[2];                 // side 0: u_0'(x_0), h_0; side 1: u_{ne-1}'(x_ne), h_{ne-1}
+  for (int side = 0; side < 2; ++side) {
+    const int64_t e = side ? p.ne - 1 : 0;
+    const double* c = p.W + e * p.M;
+    const DomainMap dm = map_params(p.x[e], p.x[e + 1]);
+    double d = 0.0;
+    for (int k = 0; k < p.M; ++k) {
+      const double w = (double)(k * (k + 1) / 2);
+      d = fma(c[k], (side == 0 && !(k & 1)) ? -w : w, d);
+    }
+    der[side] = d * dm.scl;
+    len[side] = dm.oldlen;
+  }
+  const double J = p.a[0] * der[1] - p.a[1] * der[0];
+  for (int side = 1; side >= 0; --side) {
+    const int64_t e = side ? p.ne - 1 : 0;
+    const double add = (0.5 * len[side]) * (J * J);
+    const double old = p.eta2[e];
+    const double now = old + add;
+    p.eta2[e] = now;
+    if (fabs(old) < INFINITY) {
+      if (fabs(now) < INFINITY) {
+        sum += add;
+        mx = fmax(mx, now);
+      } else {
+        cnt += 1.0;
+      }
+    }
+  }
+  p.out3[0] = sum;
+  p.out3[1] = mx;
+  p.out3[2] = cnt;
+}
+
 __global__ __launch_bounds__(kBlock) void estimate_points_kernel(const double* __restrict__ x, int64_t ne,
                                                                   int nq, GaussRuleN g,
                                                                   double* __restrict__ xq) {
@@ -543,6 +587,11 @@ hipError_t estimate_react(EstimateReactArgs a, bool point_major, double* out3, h
 hipError_t estimate_ends(const EstimateEndsArgs& a, hipStream_t s) {
   if (a.kind[0] != 1 && a.kind[1] != 1) return hipSuccess;       // two Dirichlet ends: nothing is added
   hipLaunchKernelGGL(estimate_ends_kernel, dim3(1), dim3(1), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t estimate_seam(const EstimateSeamArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(estimate_seam_kernel, dim3(1), dim3(1), 0, s, a);
   return hipGetLastError();
 }
 

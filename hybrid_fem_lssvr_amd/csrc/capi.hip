@@ -916,6 +916,39 @@ int lssvr_tridiag_ns_bc_solve_multi(const double* diag, const double* sub, const
                           work_bytes, stream, false);
 }
 
+// Periodic ends (tridiag.hip).  sup == NULL: the symmetric entry, `off` arrives as sub.
+int64_t lssvr_tridiag_periodic_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_periodic_work_bytes(ne, nc); }
+
+static int tridiag_periodic_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                  int64_t ne, int nc, double* u, void* work, int64_t work_bytes, void* stream,
+                                  bool sym) {
+  if (ne < 2) return fail(LSSVR_ERR_SIZE, "ne = %lld < 2: a periodic mesh has at least two elements", (long long)ne);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
+  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
+    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
+  const int64_t need = lssvr::tridiag_periodic_work_bytes(ne, nc);
+  if (work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_periodic_work_bytes(%lld, %d) = %lld",
+                (long long)work_bytes, (long long)ne, nc, (long long)need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (sym)
+    return check_launch(lssvr::tridiag_periodic_solve(diag, sub, load, ne, nc, u, work, st),
+                        "tridiag_periodic_solve_multi");
+  return check_launch(lssvr::tridiag_ns_periodic_solve(diag, sub, sup, load, ne, nc, u, work, st),
+                      "tridiag_ns_periodic_solve_multi");
+}
+
+int lssvr_tridiag_periodic_solve_multi(const double* diag, const double* off, const double* load, int64_t ne, int nc,
+                                       double* u, void* work, int64_t work_bytes, void* stream) {
+  return tridiag_periodic_solve(diag, off, nullptr, load, ne, nc, u, work, work_bytes, stream, true);
+}
+
+int lssvr_tridiag_ns_periodic_solve_multi(const double* diag, const double* sub, const double* sup,
+                                          const double* load, int64_t ne, int nc, double* u, void* work,
+                                          int64_t work_bytes, void* stream) {
+  return tridiag_periodic_solve(diag, sub, sup, load, ne, nc, u, work, work_bytes, stream, false);
+}
+
 int64_t lssvr_p1_flux_work_bytes(int64_t ne) { return lssvr::flux_work_bytes(ne); }
 
 int lssvr_p1_flux_solve(const double* kloc, const double* load, int64_t ne, double u0, double u1,
@@ -1076,6 +1109,25 @@ int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int
   a.eta2 = eta2;
   a.out3 = out3;
   return check_launch(lssvr::estimate_ends(a, reinterpret_cast<hipStream_t>(stream)), "estimate_ends");
+}
+
+int lssvr_estimate_seam(const double* x, const double* W, int M, int64_t ne, const double* a_seam_host, double* eta2,
+                        double* out3, void* stream) {
+  if (ne < 2) return fail(LSSVR_ERR_SIZE, "ne = %lld < 2: a periodic mesh has at least two elements", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
+  if (!x || !W || !eta2 || !out3) return fail(LSSVR_ERR_NULL, "x, W, eta2, out3 must be non-NULL");
+  if (!a_seam_host) return fail(LSSVR_ERR_NULL, "a_seam_host must be non-NULL");
+  lssvr::EstimateSeamArgs a{};
+  a.x = x;
+  a.W = W;
+  a.ne = ne;
+  a.M = M;
+  a.a[0] = a_seam_host[0];
+  a.a[1] = a_seam_host[1];
+  a.eta2 = eta2;
+  a.out3 = out3;
+  return check_launch(lssvr::estimate_seam(a, reinterpret_cast<hipStream_t>(stream)), "estimate_seam");
 }
 
 int64_t lssvr_goal_work_bytes(int64_t ne) { return lssvr::goal_work_bytes(ne); }

@@ -206,6 +206,14 @@ hipError_t tridiag_bc_solve(const double* diag, const double* off, const double*
 hipError_t tridiag_ns_bc_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                int64_t ne, int nc, bool f0, bool f1, double k0, double k1, const double* bc,
                                double* u, void* work, hipStream_t s);
+// The same solves with periodic ends: node ne is node 0, the rows of node 0 and node ne add up
+// to the seam row.  ne >= 2.  u[q][0] == u[q][ne], bit for bit; the bands and loads are read only; row q does not
+// depend on nc.  work: tridiag_periodic_work_bytes(ne, nc) bytes.
+int64_t tridiag_periodic_work_bytes(int64_t ne, int nc);
+hipError_t tridiag_periodic_solve(const double* diag, const double* off, const double* load, int64_t ne, int nc,
+                                  double* u, void* work, hipStream_t s);
+hipError_t tridiag_ns_periodic_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                     int64_t ne, int nc, double* u, void* work, hipStream_t s);
 // fem_eval.hip: the load of p1_assemble / _react / _conv for nc tabulated right-hand sides rhs_quad[nc][ne*nquad] ->
 // load[nc][ne+1], no bands
 hipError_t p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,
@@ -277,6 +285,17 @@ struct EstimateEndsArgs {
   double* out3;
 };
 hipError_t estimate_ends(const EstimateEndsArgs& a, hipStream_t s);
+// the flux jump across the seam of a periodic domain, added to eta2 and out3 in the same way (adapt.hip)
+struct EstimateSeamArgs {
+  const double* x;
+  const double* W;
+  int64_t ne;
+  int M;
+  double a[2];                      // a at x_ne seen from element ne-1, a at x_0 seen from element 0
+  double* eta2;
+  double* out3;
+};
+hipError_t estimate_seam(const EstimateSeamArgs& a, hipStream_t s);
 hipError_t refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max, double theta,
                   double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new, hipStream_t s);
 

@@ -31,6 +31,11 @@
 // kernels are templates on the type of their cases: TriCases is the Dirichlet text, unchanged, TriCasesFree adds the
 // two end terms; the reduced levels of either are TriCases.  With both ends Dirichlet the TriCasesFree instantiation
 // performs the operations of the TriCases one, bit for bit.
+//
+// Periodic ends.  Node ne is node 0 and the matrix gains two corner entries.  The seam value s
+// is one more separator: the Dirichlet kernels above, called as they are, give y (end values 0) for every case and z
+// (zero load, end values 1) once per call; tri_seam_kernel solves the seam row for s, tri_seam_combine_kernel writes
+// u = y + s z.  Row dominance of the cyclic matrix is that of its Schur complement, so no pivoting here either.
 #include "lssvr_device.hpp"
 #include "lssvr_kernels.hpp"
 
@@ -541,6 +546,65 @@ hipError_t free_solve(const double* diag, const double* lo, const double* up, co
   return solve_passes<kRefine>(all, nc, u + sh, work, st);
 }
 
+// Periodic ends: node ne is node 0, its value s the one unknown beside the ne - 1 interior
+// ones.  With y[q] the Dirichlet solve of case q for the end values (0, 0) -- already in u -- and z the solve with
+// zero load for the end values (1, 1), u_int = y + s z, and the seam row
+//   (d[0] + d[ne]) s + up[0] u[1] + lo[ne-1] u[ne-1] = load[0] + load[ne]
+// gives s: the Schur complement on this one separator.  One thread per case, a plain division, no atomics.
+__global__ void tri_seam_kernel(const double* __restrict__ d, const double* __restrict__ lo,
+                                const double* __restrict__ up, const double* __restrict__ load,
+                                const double* __restrict__ y, const double* __restrict__ z, int64_t ne, int nc,
+                                double* __restrict__ s) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nc) return;
+  const double* lq = load + q * (ne + 1);
+  const double* yq = y + q * (ne + 1);
+  const double u0 = up[0], l1 = lo[ne - 1];
+  const double num = ((lq[0] + lq[ne]) - u0 * yq[1]) - l1 * yq[ne - 1];
+  const double den = ((d[0] + d[ne]) + u0 * z[1]) + l1 * z[ne - 1];
+  s[q] = num / den;
+}
+
+// u[q] = y[q] + s[q] z in place over the y that the passes wrote, and u[q][0] = u[q][ne] = s[q]; blockIdx.y strides
+// over the cases, blockIdx.x over the nodes
+__global__ __launch_bounds__(kBlock) void tri_seam_combine_kernel(double* __restrict__ u,
+                                                                  const double* __restrict__ z,
+                                                                  const double* __restrict__ s, int64_t ne, int nc) {
+  for (int q = blockIdx.y; q < nc; q += gridDim.y) {
+    const double sq = s[q];
+    double* uq = u + q * (ne + 1);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= ne; i += (int64_t)gridDim.x * kBlock)
+      uq[i] = (i == 0 || i == ne) ? sq : uq[i] + sq * z[i];
+  }
+}
+
+// work: the workspace of the Dirichlet passes, then z[ne+1], the zero load [ne+1] and s[nc].  z is solved once per
+// call, as a pass of one case with its end values by value; the nc cases then run through solve_passes with zero end
+// values, straight into u.
+template <bool kRefine>
+hipError_t periodic_solve(const double* diag, const double* lo, const double* up, const double* load, int64_t ne,
+                          int nc, double* u, void* work, hipStream_t st) {
+  double* z = reinterpret_cast<double*>(static_cast<char*>(work) + tridiag_multi_work_bytes(ne, nc));
+  double* zero = z + (ne + 1);
+  double* s = zero + (ne + 1);
+  hipError_t err = hipMemsetAsync(zero, 0, sizeof(double) * (size_t)(ne + 1), st);
+  if (err != hipSuccess) return err;
+  const TriSys sys{lo, diag + 1, up + 1, zero + 1, lo, up + (ne - 1), 1.0, 1.0, ne - 1};
+  err = solve_passes<kRefine>(TriCases{sys, ne + 1, nullptr, 0}, 1, z + 1, work, st);
+  if (err != hipSuccess) return err;
+  TriSys sy = sys;
+  sy.r = load + 1;
+  sy.u0 = sy.u1 = 0.0;
+  err = solve_passes<kRefine>(TriCases{sy, ne + 1, nullptr, 0}, nc, u + 1, work, st);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(tri_seam_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, diag, lo, up, load, u, z, ne,
+                     nc, s);
+  const int64_t gx = (ne + kBlock) / kBlock;
+  hipLaunchKernelGGL(tri_seam_combine_kernel, dim3((unsigned)(gx < 4096 ? gx : 4096), (unsigned)(nc < 64 ? nc : 64)),
+                     dim3(kBlock), 0, st, u, z, s, ne, nc);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // it grows with nc up to kTriMultiCases, the cases of one pass
@@ -582,6 +646,21 @@ hipError_t tridiag_ns_bc_solve(const double* diag, const double* sub, const doub
                                int64_t ne, int nc, bool f0, bool f1, double k0, double k1, const double* bc,
                                double* u, void* work, hipStream_t st) {
   return free_solve<true>(diag, sub, sup, load, ne, nc, f0, f1, k0, k1, bc, u, work, st);
+}
+
+// periodic ends: the workspace of the Dirichlet passes + z and its zero load (16 (ne+1) bytes) + s[nc]
+int64_t tridiag_periodic_work_bytes(int64_t ne, int nc) {
+  return tridiag_multi_work_bytes(ne, nc) + 16 * (ne + 1) + 8 * (int64_t)(nc > 1 ? nc : 1) + 256;
+}
+
+hipError_t tridiag_periodic_solve(const double* diag, const double* off, const double* load, int64_t ne, int nc,
+                                  double* u, void* work, hipStream_t st) {
+  return periodic_solve<false>(diag, off, off, load, ne, nc, u, work, st);
+}
+
+hipError_t tridiag_ns_periodic_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                     int64_t ne, int nc, double* u, void* work, hipStream_t st) {
+  return periodic_solve<true>(diag, sub, sup, load, ne, nc, u, work, st);
 }
 
 }  // namespace lssvr

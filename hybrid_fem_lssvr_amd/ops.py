@@ -906,6 +906,85 @@ def tridiag_ns_bc_solve(diag, sub, sup, load, end_kinds, kappa, end_values=(0.0,
                              end_kinds, kappa, end_values, out, work, stream, False)
 
 
+def _tridiag_periodic_solve(entry, names, bands, lengths, out, work, stream, multi):
+    """The ``*_periodic_solve_multi`` entry on ``bands`` (``names`` in its order) -> u[nc, ne+1], or u[ne+1] for the
+    single form (``multi`` False: load [ne+1])."""
+    lib = _capi.load()
+    for nm, t in zip(names, bands):
+        _dev(t, nm)
+    diag, load = bands[0], bands[-1]
+    ne = bands[1].numel()
+    if not multi:
+        if load.dim() != 1:
+            raise ValueError(lengths)
+        load = load.unsqueeze(0)
+    if (diag.numel() != ne + 1 or bands[-2].numel() != ne or load.dim() != 2 or load.shape[1] != ne + 1):
+        raise ValueError(lengths)
+    if ne < 2:
+        raise ValueError("a periodic mesh needs at least two elements")
+    nc = int(load.shape[0])
+    if nc < 1:
+        raise ValueError("need at least one case")
+    if out is None:
+        out = torch.empty((nc, ne + 1), dtype=torch.float64, device=diag.device)
+    else:
+        _dev(out, "out")
+        if not multi:
+            if out.numel() != ne + 1:
+                raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
+            out = out.view(1, ne + 1)
+        elif out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc:
+            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
+    need = lib.lssvr_tridiag_periodic_work_bytes(ne, nc)
+    if work is not None:
+        _dev(work, "work")
+        if multi and work.numel() * work.element_size() < need:
+            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                             f"lssvr_tridiag_periodic_work_bytes({ne}, {nc}) = {need}")
+    work = _scratch(work, need, diag.device)
+    for nm, t in (*zip(names, bands), ("out", out), ("work", work)):
+        if t.device != diag.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
+    rc = getattr(lib, entry)(*map(_ptr, bands), ne, nc, _ptr(out), _ptr(work), work.numel() * work.element_size(),
+                             _stream(stream))
+    _capi.check(rc, entry)
+    return out[:nc] if multi else out[0]
+
+
+def tridiag_periodic_solve_multi(diag, off, load, *, out=None, work=None, stream=None):
+    """:func:`tridiag_dirichlet_solve_multi` with periodic ends (``lssvr_tridiag_periodic_solve_multi``): node ne is
+    node 0, the rows 0 and ne of the bands are the two halves of the seam row
+    (diag[0] + diag[ne]) s + off[0] u[1] + off[ne-1] u[ne-1] = load[0] + load[ne].  load float64[nc, ne+1] ->
+    u[nc, ne+1] with u[j, 0] == u[j, ne] bit for bit; ne >= 2.  ``diag``, ``off`` and ``load`` are left as they are;
+    row j is bit-identical to the call with that case alone.  The matrix must not be singular (a reaction term that
+    is positive somewhere); no pivoting.  ``work``: at least ``lssvr_tridiag_periodic_work_bytes(ne, nc)`` bytes
+    (``ValueError`` otherwise)."""
+    return _tridiag_periodic_solve("lssvr_tridiag_periodic_solve_multi", ("diag", "off", "load"), (diag, off, load),
+                                   "band lengths must be ne+1, ne and load [nc, ne+1]", out, work, stream, True)
+
+
+def tridiag_periodic_solve(diag, off, load, *, out=None, work=None, stream=None):
+    """One right-hand side of :func:`tridiag_periodic_solve_multi` (the nc = 1 call of the same entry): load
+    float64[ne+1] -> u[ne+1]."""
+    return _tridiag_periodic_solve("lssvr_tridiag_periodic_solve_multi", ("diag", "off", "load"), (diag, off, load),
+                                   "band lengths must be ne+1, ne, ne+1", out, work, stream, False)
+
+
+def tridiag_ns_periodic_solve_multi(diag, sub, sup, load, *, out=None, work=None, stream=None):
+    """:func:`tridiag_periodic_solve_multi` for the non-symmetric bands (``lssvr_tridiag_ns_periodic_solve_multi``):
+    the seam row is (diag[0] + diag[ne]) s + sup[0] u[1] + sub[ne-1] u[ne-1] = load[0] + load[ne]."""
+    return _tridiag_periodic_solve("lssvr_tridiag_ns_periodic_solve_multi", ("diag", "sub", "sup", "load"),
+                                   (diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] "
+                                   "(diag, sub, sup, load)", out, work, stream, True)
+
+
+def tridiag_ns_periodic_solve(diag, sub, sup, load, *, out=None, work=None, stream=None):
+    """One right-hand side of :func:`tridiag_ns_periodic_solve_multi` (the nc = 1 call of the same entry)."""
+    return _tridiag_periodic_solve("lssvr_tridiag_ns_periodic_solve_multi", ("diag", "sub", "sup", "load"),
+                                   (diag, sub, sup, load), "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, "
+                                   "load)", out, work, stream, False)
+
+
 def p1_load_multi(x, rhs_quad, nquad=2, *, out=None, stream=None):
     """The ``load`` of :func:`p1_assemble` for ``nc`` tabulated right-hand sides in one launch
     (``lssvr_p1_load_multi``): rhs_quad float64[nc, ne, nquad] (f at :func:`quad_points`, case by case) ->
@@ -1211,6 +1290,31 @@ def estimate_ends(x, W, end_kinds, kappa, g, a_ends, eta2, out3, *, stream=None)
     rc = lib.lssvr_estimate_ends(_ptr(x), _ptr(W), int(W.shape[1]), ne, kinds[0], kinds[1], kap, *pairs, _ptr(eta2),
                                  _ptr(out3), _stream(stream))
     _capi.check(rc, "lssvr_estimate_ends")
+    return eta2, out3
+
+
+def estimate_seam(x, W, a_seam, eta2, out3, *, stream=None):
+    """The seam term of the indicator on a periodic domain (``lssvr_estimate_seam``), IN PLACE on the ``eta2`` [ne]
+    and ``out3`` [3] that :func:`estimate` or :func:`estimate_varcoef` returned: J = a_seam[0] u_{ne-1}'(x_ne) -
+    a_seam[1] u_0'(x_0) from the last and the first row of ``W`` [ne, M], eta2[ne-1] += h_{ne-1}/2 J^2 and
+    eta2[0] += h_0/2 J^2; out3 follows as in :func:`estimate_ends`.  ``a_seam`` = (a at x_ne seen from element ne-1,
+    a at x_0 seen from element 0); ne >= 2.  Returns (eta2, out3)."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(W, "W")
+    _dev(eta2, "eta2")
+    _dev(out3, "out3")
+    ne = x.numel() - 1
+    if x.dim() != 1 or ne < 2:
+        raise ValueError("x must be 1-D with at least three nodes: a periodic mesh has at least two elements")
+    if W.dim() != 2 or W.shape[0] != ne:
+        raise ValueError("W must be [ne, M]")
+    if eta2.numel() != ne or out3.numel() != 3:
+        raise ValueError(f"eta2 must hold ne = {ne} doubles and out3 three, got {eta2.numel()} and {out3.numel()}")
+    a = _pair("a_seam", a_seam)
+    _same_device(x, W=W, eta2=eta2, out3=out3)
+    rc = lib.lssvr_estimate_seam(_ptr(x), _ptr(W), int(W.shape[1]), ne, a, _ptr(eta2), _ptr(out3), _stream(stream))
+    _capi.check(rc, "lssvr_estimate_seam")
     return eta2, out3
 
 

@@ -29,8 +29,10 @@ estimate and refine ``-(a u')' + c u = f``; without ``coef
 section 18; the P1 system is then non-symmetric and is solved without stabilisation, so every element must have a cell
 Peclet number ``|b| h / (2 a) <= 1``; ``None``: no such term), ``boundary`` (a pair ``(left, right)``, each ``None``,
 ``("dirichlet", g)``, ``("neumann", g)`` or ``("robin", kappa, g)``: the condition ``a du/dn + kappa u = g`` with the
-outward normal at an end instead of a fixed value; ``None`` keeps the module's Dirichlet
-functions).
+outward normal at an end instead of a fixed value; or the string ``"periodic"``:
+``u(x_0) = u(x_ne)`` and ``a u'(x_0) = a u'(x_ne)``, DESIGN.md section 22 -- it needs a reaction term that is positive
+somewhere, coefficients that are periodic on the interval, ``fem_solver="bands"`` and a per-element solver, and has no
+``solve_goal``; ``None`` keeps the module's Dirichlet functions).
 """
 from __future__ import annotations
 
@@ -444,7 +446,14 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("convection needs solver=ops.SOLVER_PRIMAL: the rows with a first-derivative "
                                  "term have a primal solve only")
         self.convection = convection
-        if boundary is not None and _Boundary(boundary).robin:
+        if isinstance(boundary, str) and boundary == "periodic":
+            if fem_solver == "flux":
+                raise ValueError("boundary='periodic' needs fem_solver='bands': the flux solve factors "
+                                 "A = D^T K D between two Dirichlet values")
+            if solver == ops.SOLVER_SHARED:
+                raise ValueError("boundary='periodic' needs a per-element solver, not ops.SOLVER_SHARED: the "
+                                 "shared operator takes its end rows from the Dirichlet values")
+        elif boundary is not None and _Boundary(boundary).robin:
             if fem_solver == "flux":
                 raise ValueError("a Neumann or Robin end needs fem_solver='bands': the flux solve factors "
                                  "A = D^T K D between two Dirichlet values")
@@ -471,10 +480,24 @@ class FEMLSSVRPrimalSolver:
     def _bnd(self):
         """The parsed ``boundary`` when an end is Neumann or Robin, else None: ``boundary=None`` and two Dirichlet
         ends take the Dirichlet path."""
-        if self.boundary is None:
+        if self.boundary is None or self._periodic:
             return None
         b = _Boundary(self.boundary)
         return b if b.robin else None
+
+    @property
+    def _periodic(self):
+        """``boundary="periodic"``: u(x_0) = u(x_ne) and a u'(x_0) = a u'(x_ne), DESIGN.md section 22."""
+        return isinstance(self.boundary, str) and self.boundary == "periodic"
+
+    def _shard(self, ne):
+        """The shard arguments of the enhancement for the configured ends: none with Dirichlet ends, those of
+        :meth:`_Boundary.shard` with a Neumann or Robin end; on a periodic domain no Dirichlet flag may fire, so
+        elements 0 and ne-1 take the seam value as their nodal constraint like an interior node."""
+        if self._periodic:
+            return dict(elem_offset=1, ne_global=ne + 2)
+        bnd = self._bnd
+        return {} if bnd is None else bnd.shard(ne)
 
     def _gd_bc(self):
         """(global domain, end values at its two ends) as float pairs: the Dirichlet value -- the module's function,
@@ -482,13 +505,45 @@ class FEMLSSVRPrimalSolver:
         gd = (float(self.global_domain[0]), float(self.global_domain[1]))
         bc = (main_boundary_condition_left(self.global_domain[0]),
               main_boundary_condition_right(self.global_domain[1]))
-        if self.boundary is not None:
+        if self.boundary is not None and not self._periodic:      # (periodic: no end value is read anywhere)
             bc = tuple(d if g is None else g for d, g in zip(bc, _Boundary(self.boundary).values))
         return gd, bc
+
+    def _reaction_positive(self, eq, nodes):
+        """Whether the reaction term is positive at a quadrature point of the P1 assembly."""
+        if eq.c is None:
+            return False
+        xi = np.polynomial.legendre.leggauss(int(self.nquad))[0]
+        xq = 0.5 * (nodes[:-1] + nodes[1:])[:, None] + 0.5 * np.diff(nodes)[:, None] * xi[None, :]
+        return bool(np.any(np.broadcast_to(np.asarray(eq.c(xq), dtype=np.float64), xq.shape) > 0.0))
+
+    def _check_periodic(self, m):
+        """What the periodic solve needs, on the host and before any launch: the assembled bands and a per-element
+        solver, at least two elements, a problem that is not singular, and coefficients that are periodic on this
+        interval."""
+        if self.fem_solver == "flux" or self.solver_id == ops.SOLVER_SHARED:      # (attributes are public)
+            raise ValueError("boundary='periodic' needs fem_solver='bands' and a per-element solver")
+        eq = self._eq
+        nodes = np.asarray(m.nodes, dtype=np.float64)
+        if nodes.size < 3:
+            raise ValueError("boundary='periodic' needs at least two elements")
+        if not self._reaction_positive(eq, nodes):
+            raise ValueError("singular problem: periodic ends and no reaction that is positive at a quadrature point "
+                             "leave u determined up to a constant")
+        ends = nodes[[0, -1]]
+        for name, fn in (("coef a", eq.a), ("coef da", eq.da), ("convection", eq.b), ("reaction", eq.c)):
+            if fn is None:
+                continue
+            v = np.broadcast_to(np.asarray(fn(ends), dtype=np.float64), (2,))
+            if not abs(float(v[0]) - float(v[1])) <= 1e-12 * max(1.0, abs(float(v[0])), abs(float(v[1]))):
+                raise ValueError(f"{name} is not periodic on [{ends[0]:.6g}, {ends[1]:.6g}]: {float(v[0])!r} at the "
+                                 f"left end, {float(v[1])!r} at the right end")
 
     def _check_boundary(self, m):
         """What makes the unpivoted solve with a Neumann or Robin end safe, on the host and before any launch: the
         matrix is not singular, and with convection the end row keeps its dominance."""
+        if self._periodic:
+            return self._check_periodic(m)
         bnd = self._bnd
         if bnd is None:
             return
@@ -497,12 +552,7 @@ class FEMLSSVRPrimalSolver:
         eq = self._eq
         nodes = np.asarray(m.nodes, dtype=np.float64)
         if bnd.kinds == [ops.END_ROBIN, ops.END_ROBIN] and bnd.kappa[0] + bnd.kappa[1] == 0.0:
-            positive = False
-            if eq.c is not None:
-                xi = np.polynomial.legendre.leggauss(int(self.nquad))[0]
-                xq = 0.5 * (nodes[:-1] + nodes[1:])[:, None] + 0.5 * np.diff(nodes)[:, None] * xi[None, :]
-                positive = bool(np.any(np.broadcast_to(np.asarray(eq.c(xq), dtype=np.float64), xq.shape) > 0.0))
-            if not positive:
+            if not self._reaction_positive(eq, nodes):
                 raise ValueError("singular problem: two Neumann ends (kappa_left + kappa_right = 0) and no reaction "
                                  "that is positive at a quadrature point leave u determined up to a constant")
         if eq.b is not None:
@@ -543,7 +593,13 @@ class FEMLSSVRPrimalSolver:
             fq = _to_dev(rhs(xq.cpu().numpy()), x.device)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
         bnd = self._bnd
-        if bnd is not None:
+        if self._periodic:
+            # node ne is node 0: the cyclic solve reads no end value (_check_periodic has run)
+            if "b_quad" in kw:
+                u = ops.tridiag_ns_periodic_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"])
+            else:
+                u = ops.tridiag_periodic_solve(bands["diag"], bands["off"], bands["load"])
+        elif bnd is not None:
             # a Neumann or Robin end stays an unknown; kappa and g join its row inside the solve (_check_boundary has
             # run, and with convection _convection_quad)
             if "b_quad" in kw:
@@ -603,6 +659,10 @@ class FEMLSSVRPrimalSolver:
                 load = loads
             else:
                 load[torch.as_tensor(tabulated, device=dev)] = loads
+        if self._periodic:
+            if "b_quad" in kw:
+                return x, ops.tridiag_ns_periodic_solve_multi(bands["diag"], bands["sub"], bands["sup"], load)
+            return x, ops.tridiag_periodic_solve_multi(bands["diag"], bands["off"], load)
         bc_dev = _to_dev(bc, dev)
         bnd = self._bnd
         if bnd is not None:
@@ -650,6 +710,12 @@ class FEMLSSVRPrimalSolver:
 
     # ---- one degree per element (no reference counterpart: Dual.py:101 has one lssvr_M) ----
     def _check_hp(self, what):
+        if self._periodic:
+            # a periodic problem needs a reaction term, which lssvr_enhance_subset does not hold: the degree groups
+            # run through the table kernels instead (_enhance_by_degree_tables), with any coefficients
+            if self.solver_id != ops.SOLVER_PRIMAL:
+                raise ValueError(f"{what} needs solver=ops.SOLVER_PRIMAL")
+            return
         if self.coef is not None or self.reaction is not None or self.convection is not None:
             raise ValueError(f"{what} needs the Poisson rows (no coef, no reaction, no convection): "
                              "lssvr_enhance_subset holds those only")
@@ -693,6 +759,27 @@ class FEMLSSVRPrimalSolver:
                                **shard)
         return W, st
 
+    def _enhance_by_degree_tables(self, x, u, degrees, gamma, gd, bc, **shard):
+        """:meth:`_enhance_by_degree` for rows that ``lssvr_enhance_subset`` does not hold (coefficients, reaction,
+        convection; taken by ``boundary="periodic"``): the table kernels have no element list, so every degree that
+        occurs is one ``ops.enhance_varcoef`` over the whole mesh at that degree's collocation count, and the rows of
+        its own elements are copied into a zeroed W[ne, max M].  The cost is one whole-mesh launch per distinct
+        degree."""
+        torch = _torch()
+        eq = self._eq
+        W = torch.zeros((degrees.size, int(degrees.max())), dtype=torch.float64, device=x.device)
+        st = torch.zeros((degrees.size,), dtype=torch.int32, device=x.device)
+        for Mg in np.unique(degrees):
+            Mg = int(Mg)
+            ng, pm = self.group_colloc(Mg), _point_major(Mg)
+            ta, tda, tf, tc = eq.tables(ops.colloc_points(x, ng), pm)
+            Wg, sg = ops.enhance_varcoef(x, u, Mg, gamma, ng, ta, tda, tf, global_domain=gd, bc=bc, point_major=pm,
+                                         c_values=tc, **shard)
+            ids = torch.as_tensor(np.nonzero(degrees == Mg)[0], device=x.device)
+            W[ids, :Mg] = Wg[ids]
+            st[ids] = sg[ids]
+        return W, st
+
     # ---- Dual.py:139-169 --------------------------------------------------------------
     def solve_lssvr_subproblems(self):
         """Solve LSSVR with the primal method in each element (one kernel launch)."""
@@ -714,11 +801,14 @@ class FEMLSSVRPrimalSolver:
         bnd = self._bnd
         if bnd is not None and self.solver_id == ops.SOLVER_SHARED:
             raise ValueError("a Neumann or Robin end needs a per-element solver, not ops.SOLVER_SHARED")
-        shard = {} if bnd is None else bnd.shard(nodes.size - 1)
+        if self._periodic and self.solver_id == ops.SOLVER_SHARED:
+            raise ValueError("boundary='periodic' needs a per-element solver, not ops.SOLVER_SHARED")
+        shard = self._shard(nodes.size - 1)
         degrees = None
         if self.element_degrees is not None:
             degrees = self._check_degrees(nodes.size - 1)
-            W, st = self._enhance_by_degree(x, u, degrees, gamma, gd, bc, **shard)
+            by_degree = self._enhance_by_degree_tables if self._periodic else self._enhance_by_degree
+            W, st = by_degree(x, u, degrees, gamma, gd, bc, **shard)
         elif eq.poisson:
             kw = _rhs_mode(eq.f, lambda: ops.colloc_points(x, n), pm)
             W, st = _enhance(x, u, M, gamma, n, global_domain=gd, bc=bc, solver=self.solver_id, **kw, **shard)
@@ -753,7 +843,8 @@ class FEMLSSVRPrimalSolver:
         assembly and Dirichlet solve (``coef``, ``reaction``, ``nquad`` and ``fem_solver`` as configured), then ONE
         ``ops.enhance_multi`` over all cases -- the element systems are formed and factored once, not once per case.
         ``bc``: ``None`` (the end values ``solve()`` uses) or one ``(left, right)`` pair per case -- at a Neumann or
-        Robin end of ``boundary`` the entry is that case's g; the kinds and kappa belong to the matrix and are shared.  Returns a list of :class:`EnhancedSolution`, one per case; ``rhs``, ``fem_values``, ``enhanced`` and
+        Robin end of ``boundary`` the entry is that case's g; the kinds and kappa belong to the matrix and are shared
+        (``boundary="periodic"`` has no end values: ``bc`` must be ``None``).  Returns a list of :class:`EnhancedSolution`, one per case; ``rhs``, ``fem_values``, ``enhanced`` and
         the other attributes of the solver are left as they are.  Without ``coef`` the tables hold a = 1, a' = 0."""
         return self._solve_many(rhs_list, bc)[0]
 
@@ -765,6 +856,8 @@ class FEMLSSVRPrimalSolver:
             raise ValueError("rhs_list must be a non-empty sequence of callables")
         if self.solver_id != ops.SOLVER_PRIMAL:
             raise ValueError("solve_many needs solver=ops.SOLVER_PRIMAL")
+        if self._periodic and bc is not None:
+            raise ValueError("boundary='periodic' has no end values: bc must be None")
         gd, bc0 = self._gd_bc()
         if bc is None:
             bc = [bc0] * len(rhs_list)
@@ -777,10 +870,9 @@ class FEMLSSVRPrimalSolver:
         pts = ops.colloc_points(x, n)
         ta, tda, _, tc = _Equation(_zero, self.coef, self.reaction, self.convection).tables(pts, pm)
         tf = torch.stack([_tabulate(f, pts, pm) for f in rhs_list])
-        bnd = self._bnd
         W, st = ops.enhance_multi(x, U, M, gamma, n, ta, tda, tf, c_values=tc,
                                   bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd,
-                                  **({} if bnd is None else bnd.shard(x.numel() - 1)))
+                                  **self._shard(x.numel() - 1))
         return [EnhancedSolution(x, W[j], st[j]) for j in range(len(rhs_list))], x, U
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
@@ -817,6 +909,10 @@ class FEMLSSVRPrimalSolver:
             ends = np.array([float(self.fem_nodes[0]), float(self.fem_nodes[-1])])      # (host copy of the nodes)
             a_ends = (1.0, 1.0) if eq.a is None else np.broadcast_to(np.asarray(eq.a(ends), dtype=np.float64), (2,))
             ops.estimate_ends(x, W, bnd.kinds, bnd.kappa, self._gd_bc()[1], a_ends, eta2, out3)
+        if self._periodic:               # the flux jump across the seam joins eta2 and out3
+            seam = np.array([float(self.fem_nodes[-1]), float(self.fem_nodes[0])])      # (host copy of the nodes)
+            a_seam = (1.0, 1.0) if eq.a is None else np.broadcast_to(np.asarray(eq.a(seam), dtype=np.float64), (2,))
+            ops.estimate_seam(x, W, a_seam, eta2, out3)
         return eta2, out3
 
     def _nq(self, nq):
@@ -841,6 +937,9 @@ class FEMLSSVRPrimalSolver:
         """What :meth:`solve_goal` needs, checked on the host before any GPU use."""
         if not callable(goal):
             raise ValueError("goal must be a callable j(x): the density of J(u) = int j u dx")
+        if self._periodic:
+            raise ValueError("goal needs Dirichlet, Neumann or Robin ends: the dual-weighted residual has no seam "
+                             "term, boundary='periodic' is not supported")
         if self.convection is not None:
             raise ValueError("goal needs an operator without convection: the adjoint of -(a u')' + b u' + c u has "
                              "-b and c - b', another matrix than the primal's")
@@ -973,7 +1072,8 @@ class FEMLSSVRPrimalSolver:
         dict(ne, estimate, marked) per round (marked = elements bisected after that round).
         Returns the final sqrt(sum eta^2).
 
-        ``mode="hp"`` (Poisson rows, ``solver=ops.SOLVER_PRIMAL``): every element starts at ``lssvr_M``; a marked
+        ``mode="hp"`` (``solver=ops.SOLVER_PRIMAL``; Poisson rows, or any rows with ``boundary="periodic"``, where each
+        degree group runs through the table kernels over the whole mesh): every element starts at ``lssvr_M``; a marked
         element whose Legendre coefficients decay at a rate ``ops.smoothness`` >= ``sigma_min`` gets ``dM`` more
         coefficients while that stays <= ``M_max`` (default min(33, lssvr_M + 12)), any other marked element is
         bisected and both halves keep its degree (``ops.refine_hp``).  ``element_degrees`` carries the degrees

@@ -823,6 +823,52 @@ int lssvr_estimate_goal(const double* x, const double* Wu, const double* Wz, int
                         const double* g_host, const double* a_bnd_host, int jump_free,
                         double* eta, double* eta2, double* q, double* out4, void* work, void* stream);
 
+/*
+ * Periodic boundary conditions (no reference counterpart).  ADDITIVE to ABI 7: four new symbols,
+ * no existing entry, struct or constant changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * u(x_0) = u(x_ne) and a u'(x_0) = a u'(x_ne): node ne is node 0.  Its value s is one unknown, and the rows that the
+ * assembly entries write for node 0 and for node ne are the two halves of its row:
+ *   (diag[0] + diag[ne]) s + sup[0] u[1] + sub[ne-1] u[ne-1] = load[0] + load[ne]
+ * (off[0] and off[ne-1] for the symmetric bands); the rows 0 < i < ne are those of the Dirichlet entries with
+ * u[0] = u[ne] = s.  The matrix is cyclic tridiagonal: two corner entries.
+ *
+ * lssvr_tridiag_periodic_solve_multi -- nc >= 1 right-hand sides load[nc][ne+1] on the bands of lssvr_p1_assemble /
+ * _react -> u[nc][ne+1] with u[j][0] == u[j][ne] == s_j, bit for bit.  A single right-hand side is nc = 1.  By
+ * linearity u_int = y_j + s_j z: y_j the Dirichlet solve of case j with end values (0, 0), z the Dirichlet solve with
+ * zero load and end values (1, 1) -- independent of the load, solved once per call -- and
+ *   s_j = (load_j[0] + load_j[ne] - sup[0] y_j[1] - sub[ne-1] y_j[ne-1])
+ *         / (diag[0] + diag[ne] + sup[0] z[1] + sub[ne-1] z[ne-1]),
+ * the Schur complement on the seam.  y and z run through the kernels of lssvr_tridiag_dirichlet_solve_multi (8 cases to
+ * a pass, z a pass of its own); one thread per case computes s_j, one pass writes u = y + s z in place.  Row j does not
+ * depend on nc, bit for bit.  diag, off and load are read only.  ne >= 2.  work: device scratch of
+ * work_bytes >= lssvr_tridiag_periodic_work_bytes(ne, nc), which is lssvr_tridiag_multi_work_bytes(ne, nc) plus z, its
+ * zero load and the s_j (host arithmetic only).  Same no-pivoting rule as the Dirichlet entries: the cyclic matrix of
+ * an SPD / row-dominant problem is SPD / row-dominant, and so is its Schur complement.  The denominator vanishes for a
+ * singular problem (no reaction term: u is determined up to a constant); the caller checks, this entry does not.
+ *
+ * lssvr_tridiag_ns_periodic_solve_multi -- the same for the bands of lssvr_p1_assemble_conv, through the kernels of
+ * lssvr_tridiag_ns_dirichlet_solve_multi (the step of iterative refinement of the <= 512-unknown level included).
+ *
+ * lssvr_estimate_seam -- the seam term of the indicator, after lssvr_estimate, lssvr_estimate_varcoef or
+ * lssvr_estimate_react on the same stream (they set J_0 = J_ne = 0): with row ne-1 and row 0 of W[ne][M],
+ *   J = a_seam[0] u_{ne-1}'(x_ne) - a_seam[1] u_0'(x_0),   eta2[ne-1] += h_{ne-1}/2 J^2,   eta2[0] += h_0/2 J^2,
+ * a_seam_host[2] (host) = a at x_ne seen from element ne-1 and a at x_0 seen from element 0.  out3 follows as in
+ * lssvr_estimate_ends: sum += the added terms, max = max(max, new eta2); a value that becomes non-finite raises the
+ * non-finite count instead.  ne >= 2.  One thread (element ne-1, then element 0), no atomics: reproducible.
+ *
+ * The enhancement needs no new entry: with elem_offset = 1 and ne_global = ne + 2 no Dirichlet flag fires, and the
+ * elements 0 and ne-1 take s as their nodal constraint like any interior value.
+ */
+int64_t lssvr_tridiag_periodic_work_bytes(int64_t ne, int nc);
+int lssvr_tridiag_periodic_solve_multi(const double* diag, const double* off, const double* load,
+                                       int64_t ne, int nc, double* u, void* work, int64_t work_bytes, void* stream);
+int lssvr_tridiag_ns_periodic_solve_multi(const double* diag, const double* sub, const double* sup,
+                                          const double* load, int64_t ne, int nc,
+                                          double* u, void* work, int64_t work_bytes, void* stream);
+int lssvr_estimate_seam(const double* x, const double* W, int M, int64_t ne, const double* a_seam_host,
+                        double* eta2, double* out3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
