@@ -142,6 +142,10 @@ SIGNATURES = {
     "lssvr_tridiag_periodic_solve_multi": _sig(_BANDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
     "lssvr_tridiag_ns_periodic_solve_multi": _sig([_c_dp], _BANDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
     "lssvr_estimate_seam": _sig([_c_dp, _c_dp, _c_int, _c_i64, _c_hd, _c_dp, _c_dp], _STREAM),
+    # element lists for the table kernels (additive to ABI 7): ..., gamma_values, a, a', c, f, layout, W, ldw, status,
+    # fail_count; x, ne_mesh, elem_ids, nsub, n_colloc, layout, xc
+    "lssvr_enhance_react_subset": _sig(_SUBSET, _REACT_TABLES, [_c_int], [_c_dp, _c_i64, _c_dp, _c_dp], _STREAM),
+    "lssvr_colloc_points_subset": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_int, _c_int, _c_dp], _STREAM),
     # hp-adaptive refinement (additive to ABI 7)
     "lssvr_smoothness": _sig([_c_dp, _c_i64, _c_dp, _c_i64, _c_dp], _STREAM),
     "lssvr_refine_hp": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dbl, _c_dbl, _c_dp, _c_dp, _c_dbl, _c_int, _c_int, _c_dp,

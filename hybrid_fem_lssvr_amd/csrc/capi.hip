@@ -707,6 +707,69 @@ int lssvr_enhance_subset_ws(const double* x, const double* u, int64_t ne_mesh,
   return enhance_dispatch(a, LSSVR_SOLVER_PRIMAL, reinterpret_cast<hipStream_t>(stream), nullptr, work, work_bytes);
 }
 
+int lssvr_enhance_react_subset(const double* x, const double* u, int64_t ne_mesh,
+                               const int64_t* elem_ids, int64_t nsub, int64_t elem_offset,
+                               int64_t ne_global, double gxmin, double gxmax, double bc_left,
+                               double bc_right, int M, int n_colloc, double gamma,
+                               const double* gamma_values, const double* a_values, const double* da_values,
+                               const double* c_values, const double* rhs_values, int table_layout,
+                               double* W, int64_t ldw, int32_t* status, int32_t* fail_count, void* stream) {
+  // the element-list rules of lssvr_enhance_subset_ws ...
+  if (ne_mesh < 0 || nsub < 0) return fail(LSSVR_ERR_SIZE, "ne_mesh / nsub < 0");
+  if (!elem_ids && nsub != ne_mesh)
+    return fail(LSSVR_ERR_SIZE, "elem_ids == NULL means every element: nsub must equal ne_mesh");
+  if (elem_ids && nsub > ne_mesh) return fail(LSSVR_ERR_SIZE, "nsub = %lld > ne_mesh = %lld",
+                                              (long long)nsub, (long long)ne_mesh);
+  if (ldw != 0 && ldw < M) return fail(LSSVR_ERR_SIZE, "ldw = %lld < M = %d", (long long)ldw, M);
+  if (ne_global < elem_offset + ne_mesh)
+    return fail(LSSVR_ERR_SIZE, "shard [%lld, %lld) does not fit ne_global = %lld",
+                (long long)elem_offset, (long long)(elem_offset + ne_mesh), (long long)ne_global);
+  // ... then the one validation path of lssvr_enhance_react_ws / lssvr_enhance_varcoef_ws, on the launch count (the
+  // tables are indexed by position: point-major stride nsub)
+  lssvr::EnhanceReactArgs a{};
+  int rc;
+  if (c_values) {
+    rc = bind_react_ws(a, x, u, nsub, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                       gamma_values ? 1.0 : gamma, a_values, da_values, c_values, rhs_values, table_layout, W, status,
+                       fail_count, nullptr, 0);
+  } else {
+    rc = bind_varcoef_ws(a, x, u, nsub, elem_offset, ne_global, gxmin, gxmax, bc_left, bc_right, M, n_colloc,
+                         gamma_values ? 1.0 : gamma, a_values, da_values, rhs_values, table_layout, W, status,
+                         fail_count, nullptr, 0);
+    if (rc == LSSVR_OK && n_colloc < M - 2)
+      return fail(LSSVR_ERR_SOLVER, "lssvr_enhance_react_subset: n_colloc = %d < M-2 = %d needs the dual solver, "
+                                    "which has no subset form", n_colloc, M - 2);
+  }
+  if (rc != LSSVR_OK || nsub == 0) return rc;
+  a.gamma = gamma;
+  a.inv_gamma = 1.0 / gamma;
+  a.elem_ids = elem_ids;
+  a.ne_mesh = ne_mesh;
+  a.gamma_values = gamma_values;
+  a.ldw = ldw;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // (c_values == NULL: the lane kernel up to M = 22, the MFMA kernel above; else react_dispatch's pair)
+  return c_values ? react_dispatch(a, s, nullptr) : enhance_dispatch(a, LSSVR_SOLVER_PRIMAL, s, nullptr);
+}
+
+int lssvr_colloc_points_subset(const double* x, int64_t ne_mesh, const int64_t* elem_ids, int64_t nsub,
+                               int n_colloc, int table_layout, double* xc, void* stream) {
+  if (ne_mesh < 0 || nsub < 0) return fail(LSSVR_ERR_SIZE, "ne_mesh / nsub < 0");
+  if (n_colloc < 2) return fail(LSSVR_ERR_SIZE, "n_colloc < 2");
+  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
+    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  if (!elem_ids && nsub != ne_mesh)
+    return fail(LSSVR_ERR_SIZE, "elem_ids == NULL means every element: nsub must equal ne_mesh");
+  if (elem_ids && nsub > ne_mesh) return fail(LSSVR_ERR_SIZE, "nsub = %lld > ne_mesh = %lld",
+                                              (long long)nsub, (long long)ne_mesh);
+  if (nsub * (int64_t)n_colloc / n_colloc != nsub) return fail(LSSVR_ERR_SIZE, "nsub*n_colloc overflows");
+  if (nsub > 0 && (!x || !xc)) return fail(LSSVR_ERR_NULL, "x and xc must be non-NULL");
+  return check_launch(lssvr::colloc_points_subset(x, ne_mesh, elem_ids, nsub, n_colloc, xc,
+                                                  reinterpret_cast<hipStream_t>(stream),
+                                                  table_layout == LSSVR_TABLE_POINT_MAJOR),
+                      "colloc_points_subset");
+}
+
 int lssvr_enhance_shared(const double* x, const double* u, int64_t ne, int64_t elem_offset,
                          int64_t ne_global, double gxmin, double gxmax, double bc_left,
                          double bc_right, int M, int n_colloc, int rhs_id,

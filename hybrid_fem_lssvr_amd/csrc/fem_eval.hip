@@ -39,6 +39,42 @@ hipError_t colloc_points(const double* x, int64_t ne, int n, double* xc, hipStre
   return hipGetLastError();
 }
 
+// The abscissae of the listed elements only (lssvr_colloc_points_subset): output position (pos, k) holds point k of
+// mesh element ids[pos], by the arithmetic of colloc_points_kernel.  One thread per (position, point), grid-stride;
+// an id outside [0, ne_mesh) reads and writes nothing.
+template <bool PM>
+__global__ __launch_bounds__(kBlock) void colloc_points_subset_kernel(const double* __restrict__ x, int64_t ne_mesh,
+                                                                       const int64_t* __restrict__ ids, int64_t nsub,
+                                                                       int n, double* __restrict__ xc) {
+  const int64_t total = nsub * n;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * kBlock) {
+    // output index i: element-major (pos, k) = (i / n, i % n); point-major (k, pos) = (i / nsub, i % nsub)
+    const int64_t pos = PM ? i % nsub : i / n;
+    const int k = (int)(PM ? i / nsub : i - pos * n);
+    const int64_t e = ids ? ids[pos] : pos;
+    if (e < 0 || e >= ne_mesh) continue;
+    const double a = x[e], b = x[e + 1];
+    const double delta = b - a;
+    const double step = delta / (double)(n - 1);
+    xc[i] = linspace_at(a, b, delta, step, k, n);
+  }
+}
+
+hipError_t colloc_points_subset(const double* x, int64_t ne_mesh, const int64_t* ids, int64_t nsub, int n, double* xc,
+                                hipStream_t s, bool point_major) {
+  if (nsub == 0) return hipSuccess;
+  const int64_t total = nsub * n;
+  const unsigned blocks = (unsigned)((total + kBlock - 1) / kBlock < 8192 ? (total + kBlock - 1) / kBlock : 8192);
+  if (point_major)
+    hipLaunchKernelGGL(colloc_points_subset_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, x, ne_mesh, ids, nsub, n,
+                       xc);
+  else
+    hipLaunchKernelGGL(colloc_points_subset_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, x, ne_mesh, ids, nsub, n,
+                       xc);
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(kBlock) void quad_points_kernel(const double* __restrict__ x,
                                                               int64_t ne, int nq, QuadRule q,
                                                               double* __restrict__ xq) {

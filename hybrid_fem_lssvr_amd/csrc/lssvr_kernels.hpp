@@ -140,6 +140,10 @@ hipError_t enhance_shared(const EnhanceArgs& a, const double* op, hipStream_t s,
                           const LaunchOpts* o = nullptr);
 
 hipError_t colloc_points(const double* x, int64_t ne, int n, double* xc, hipStream_t s, bool point_major = false);
+// the same abscissae for the nsub elements ids[0..nsub) of a mesh of ne_mesh elements (ids NULL: all, in order), by
+// position in the list; an id outside [0, ne_mesh) writes nothing
+hipError_t colloc_points_subset(const double* x, int64_t ne_mesh, const int64_t* ids, int64_t nsub, int n, double* xc,
+                                hipStream_t s, bool point_major);
 
 struct QuadRule {
   double xi[5];

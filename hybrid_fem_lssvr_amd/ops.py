@@ -512,6 +512,61 @@ def enhance_varcoef(x, u, M, gamma, n_colloc, a_values, da_values, rhs_values, *
     return out, status
 
 
+def _elem_list(elem_ids, ne, x):
+    """nsub of an element list: ``elem_ids`` a 1-D int64 device tensor on x's device with at most ne entries, or None
+    for all ne elements in order."""
+    if elem_ids is None:
+        return ne
+    _dev(elem_ids, "elem_ids", torch.int64)
+    if elem_ids.dim() != 1 or elem_ids.numel() > ne:
+        raise ValueError(f"elem_ids must be int64[nsub <= ne = {ne}], got {list(elem_ids.shape)}")
+    if elem_ids.device != x.device:
+        raise RuntimeError(f"elem_ids lives on {elem_ids.device}, x on {x.device}")
+    return elem_ids.numel()
+
+
+def enhance_varcoef_subset(x, u, M, gamma, n_colloc, W, a_values, da_values, rhs_values, *, elem_ids=None,
+                           gamma_values=None, c_values=None, b_values=None, point_major=False, elem_offset=0,
+                           ne_global=None, global_domain, bc=(0.0, 0.0), status=None, fail_count=None, stream=None):
+    """``lssvr_enhance_react_subset``: :func:`enhance_varcoef` for the elements ``elem_ids`` (int64 device tensor of
+    mesh indices; None = all) of the shard (x, u) with one (M, n_colloc) -- what :func:`enhance_subset` is to
+    :func:`enhance`.  The tables hold nsub * n_colloc doubles, indexed by POSITION in ``elem_ids``: float64[nsub,
+    n_colloc], or [n_colloc, nsub] with ``point_major`` (tabulate on :func:`colloc_points_subset`); ``c_values``
+    and ``b_values`` as in :func:`enhance_varcoef`.  ``gamma_values`` (float64[ne]) and ``status`` (int32[ne]) are
+    indexed by mesh element; rows go to ``W[id, :M]`` of the caller's float64[ne, ldw >= M] array (zero it first when
+    ldw > M), rows that are not listed are not written.  Primal solve only (``n_colloc >= M - 2``)."""
+    lib = _capi.load()
+    M, n_colloc = int(M), int(n_colloc)
+    ne, ne_global = _shard(x, u, elem_offset, ne_global)
+    _dev(W, "W")
+    if W.dim() != 2 or W.shape[0] != ne or W.shape[1] < M:
+        raise ValueError("W must be a contiguous float64[ne, ldw >= M] tensor")
+    nsub = _elem_list(elem_ids, ne, x)
+    da_values = _fold(da_values, b_values)
+    named = dict(a_values=a_values, da_values=da_values, rhs_values=rhs_values)
+    if c_values is not None:
+        named["c_values"] = c_values
+    _tables(nsub, n_colloc, **named)
+    if gamma_values is not None:
+        _dev(gamma_values, "gamma_values")
+        if gamma_values.numel() != ne:
+            raise ValueError("gamma_values must hold one value per mesh element")
+    if status is not None:
+        _dev(status, "status", torch.int32)
+        if status.numel() != ne:
+            raise ValueError("status is indexed by mesh element: int32[ne]")
+    _check_fail_count(fail_count)
+    _same_device(x, u=u, W=W, gamma_values=gamma_values, status=status, fail_count=fail_count, **named)
+    pre = _prefix(x, u, elem_offset, ne_global, global_domain, bc, M, n_colloc, gamma)
+    # (the subset entry takes elem_ids and nsub after ne, gamma_values after gamma; it has one table order: c third)
+    rc = lib.lssvr_enhance_react_subset(*pre[:3], _ptr(elem_ids), int(nsub), *pre[3:], _ptr(gamma_values),
+                                        _ptr(a_values), _ptr(da_values), _ptr(c_values), _ptr(rhs_values),
+                                        _layout(point_major), _ptr(W), int(W.shape[1]), _ptr(status),
+                                        _ptr(fail_count), _stream(stream))
+    _capi.check(rc, "lssvr_enhance_react_subset")
+    return W
+
+
 def enhance_multi(x, U, M, gamma, n_colloc, a_values, da_values, rhs_values, *, c_values=None, bc=None,
                   point_major=False, elem_offset=0, ne_global=None, global_domain, out=None, status=None,
                   fail_count=None, stream=None, timed=False, b_values=None):
@@ -652,6 +707,27 @@ def colloc_points(x, n_colloc, *, stream=None, point_major=False):
     name = "lssvr_colloc_points_pm" if point_major else "lssvr_colloc_points"
     xc = torch.empty((n_colloc, ne) if point_major else (ne, n_colloc), dtype=torch.float64, device=x.device)
     _capi.check(getattr(lib, name)(_ptr(x), ne, int(n_colloc), _ptr(xc), _stream(stream)), name)
+    return xc
+
+
+def colloc_points_subset(x, elem_ids, n_colloc, *, stream=None, point_major=False):
+    """:func:`colloc_points` for the elements ``elem_ids`` (int64 device tensor of mesh indices; None = all) only, by
+    position in the list (``lssvr_colloc_points_subset``) -> float64[nsub, n], or float64[n, nsub] with
+    ``point_major``: bit for bit ``colloc_points(x, n)[elem_ids]``, without the whole-mesh table.  The row of an id
+    outside the mesh is left unwritten."""
+    lib = _capi.load()
+    _dev(x, "x")
+    n_colloc = int(n_colloc)
+    if x.dim() != 1 or x.numel() < 1:
+        raise ValueError("x must be float64[ne+1]")
+    if n_colloc < 2:
+        raise ValueError(f"n_colloc must be >= 2, got {n_colloc}")
+    ne = x.numel() - 1
+    nsub = _elem_list(elem_ids, ne, x)
+    xc = torch.empty((n_colloc, nsub) if point_major else (nsub, n_colloc), dtype=torch.float64, device=x.device)
+    rc = lib.lssvr_colloc_points_subset(_ptr(x), ne, _ptr(elem_ids), int(nsub), n_colloc, _layout(point_major),
+                                        _ptr(xc), _stream(stream))
+    _capi.check(rc, "lssvr_colloc_points_subset")
     return xc
 
 

@@ -32,7 +32,10 @@ Peclet number ``|b| h / (2 a) <= 1``; ``None``: no such term), ``boundary`` (a p
 outward normal at an end instead of a fixed value; or the string ``"periodic"``:
 ``u(x_0) = u(x_ne)`` and ``a u'(x_0) = a u'(x_ne)``, DESIGN.md section 22 -- it needs a reaction term that is positive
 somewhere, coefficients that are periodic on the interval, ``fem_solver="bands"`` and a per-element solver, and has no
-``solve_goal``; ``None`` keeps the module's Dirichlet functions).
+``solve_goal``; ``None`` keeps the module's Dirichlet functions), ``element_lists`` (``True``: ``element_degrees`` and
+``solve_adaptive(mode="hp")`` work with ``coef``, ``reaction`` and ``convection`` and every ``boundary``, one element-list
+launch of the table kernels per degree group; ``False``, the default, keeps every path as it was:
+Poisson rows, or ``boundary="periodic"`` through one whole-mesh launch per degree, anything else is refused).
 """
 from __future__ import annotations
 
@@ -397,7 +400,7 @@ class FEMLSSVRPrimalSolver:
     def __init__(self, num_fem_nodes=5, lssvr_M=12, lssvr_gamma=1e6, global_domain=(-1, 1), *,
                  n_colloc=12, rhs=poisson_rhs, nquad=2, mesh=None, device="cuda:0",
                  solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None, convection=None,
-                 boundary=None):
+                 boundary=None, element_lists=False):
         # Dual.py:101-108
         self.num_fem_nodes = num_fem_nodes
         self.lssvr_M = lssvr_M
@@ -461,6 +464,9 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("a Neumann or Robin end needs a per-element solver, not ops.SOLVER_SHARED: the "
                                  "shared operator takes its end rows from the Dirichlet values")
         self.boundary = boundary
+        # one degree per element (element_degrees, solve_adaptive(mode="hp")) for coef / reaction / convection with any
+        # boundary, through the element lists of the table kernels; False: every path as it was
+        self.element_lists = bool(element_lists)
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
         self.dual = None                # EnhancedSolution of the dual problem after solve_goal
@@ -710,6 +716,13 @@ class FEMLSSVRPrimalSolver:
 
     # ---- one degree per element (no reference counterpart: Dual.py:101 has one lssvr_M) ----
     def _check_hp(self, what):
+        if self.element_lists:
+            # every operator and boundary kind: the Poisson rows run through lssvr_enhance_subset
+            # (_enhance_by_degree), coefficients, reaction and convection through the element lists of the table
+            # kernels (_enhance_by_degree_lists); both are primal solves
+            if self.solver_id != ops.SOLVER_PRIMAL:
+                raise ValueError(f"{what} needs solver=ops.SOLVER_PRIMAL")
+            return
         if self._periodic:
             # a periodic problem needs a reaction term, which lssvr_enhance_subset does not hold: the degree groups
             # run through the table kernels instead (_enhance_by_degree_tables), with any coefficients
@@ -718,7 +731,8 @@ class FEMLSSVRPrimalSolver:
             return
         if self.coef is not None or self.reaction is not None or self.convection is not None:
             raise ValueError(f"{what} needs the Poisson rows (no coef, no reaction, no convection): "
-                             "lssvr_enhance_subset holds those only")
+                             "lssvr_enhance_subset holds those only (element_lists=True runs the others through "
+                             "the element lists of the table kernels)")
         if self.solver_id != ops.SOLVER_PRIMAL:
             raise ValueError(f"{what} needs solver=ops.SOLVER_PRIMAL")
 
@@ -760,11 +774,11 @@ class FEMLSSVRPrimalSolver:
         return W, st
 
     def _enhance_by_degree_tables(self, x, u, degrees, gamma, gd, bc, **shard):
-        """:meth:`_enhance_by_degree` for rows that ``lssvr_enhance_subset`` does not hold (coefficients, reaction,
-        convection; taken by ``boundary="periodic"``): the table kernels have no element list, so every degree that
-        occurs is one ``ops.enhance_varcoef`` over the whole mesh at that degree's collocation count, and the rows of
-        its own elements are copied into a zeroed W[ne, max M].  The cost is one whole-mesh launch per distinct
-        degree."""
+        """:meth:`_enhance_by_degree` for rows that ``lssvr_enhance_subset`` does not hold, without element lists
+        (``boundary="periodic"`` with ``element_lists=False``): every degree that occurs is one ``ops.enhance_varcoef``
+        over the whole mesh at that degree's collocation count, and the rows of its own elements are copied into a
+        zeroed W[ne, max M].  The cost is one whole-mesh launch per distinct degree; :meth:`_enhance_by_degree_lists`
+        removes that factor."""
         torch = _torch()
         eq = self._eq
         W = torch.zeros((degrees.size, int(degrees.max())), dtype=torch.float64, device=x.device)
@@ -778,6 +792,28 @@ class FEMLSSVRPrimalSolver:
             ids = torch.as_tensor(np.nonzero(degrees == Mg)[0], device=x.device)
             W[ids, :Mg] = Wg[ids]
             st[ids] = sg[ids]
+        return W, st
+
+    def _enhance_by_degree_lists(self, x, u, degrees, gamma, gd, bc, **shard):
+        """:meth:`_enhance_by_degree` for rows that ``lssvr_enhance_subset`` does not hold (coefficients, reaction,
+        convection; every ``boundary``; ``element_lists=True``): the same grouping, and per non-empty degree the
+        collocation points of its own elements (``ops.colloc_points_subset``), the tables on those points, and one
+        ``ops.enhance_varcoef_subset`` into a zeroed W[ne, max M].  Every element is tabulated and solved once."""
+        torch = _torch()
+        eq = self._eq
+        ne = degrees.size
+        ids, offsets = ops.group_by_degree(torch.as_tensor(degrees.astype(np.int32), device=x.device))
+        off = offsets.cpu().numpy()
+        W = torch.zeros((ne, int(degrees.max())), dtype=torch.float64, device=x.device)
+        st = torch.zeros((ne,), dtype=torch.int32, device=x.device)
+        for Mg in range(ops.MIN_DEGREE, ops.MAX_DEGREE + 1):
+            sub = ids[off[Mg]:off[Mg + 1]]
+            if sub.numel() == 0:
+                continue
+            ng, pm = self.group_colloc(Mg), _point_major(Mg)
+            ta, tda, tf, tc = eq.tables(ops.colloc_points_subset(x, sub, ng), pm)
+            ops.enhance_varcoef_subset(x, u, Mg, gamma, ng, W, ta, tda, tf, elem_ids=sub, c_values=tc,
+                                       point_major=pm, global_domain=gd, bc=bc, status=st, **shard)
         return W, st
 
     # ---- Dual.py:139-169 --------------------------------------------------------------
@@ -808,6 +844,8 @@ class FEMLSSVRPrimalSolver:
         if self.element_degrees is not None:
             degrees = self._check_degrees(nodes.size - 1)
             by_degree = self._enhance_by_degree_tables if self._periodic else self._enhance_by_degree
+            if self.element_lists and not eq.poisson:
+                by_degree = self._enhance_by_degree_lists
             W, st = by_degree(x, u, degrees, gamma, gd, bc, **shard)
         elif eq.poisson:
             kw = _rhs_mode(eq.f, lambda: ops.colloc_points(x, n), pm)
@@ -1073,7 +1111,9 @@ class FEMLSSVRPrimalSolver:
         Returns the final sqrt(sum eta^2).
 
         ``mode="hp"`` (``solver=ops.SOLVER_PRIMAL``; Poisson rows, or any rows with ``boundary="periodic"``, where each
-        degree group runs through the table kernels over the whole mesh): every element starts at ``lssvr_M``; a marked
+        degree group runs through the table kernels over the whole mesh; with ``element_lists=True`` any of ``coef``,
+        ``reaction``, ``convection`` and any ``boundary``, each degree group through the element lists of the table
+        kernels): every element starts at ``lssvr_M``; a marked
         element whose Legendre coefficients decay at a rate ``ops.smoothness`` >= ``sigma_min`` gets ``dM`` more
         coefficients while that stays <= ``M_max`` (default min(33, lssvr_M + 12)), any other marked element is
         bisected and both halves keep its degree (``ops.refine_hp``).  ``element_degrees`` carries the degrees

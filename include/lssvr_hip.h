@@ -869,6 +869,50 @@ int lssvr_tridiag_ns_periodic_solve_multi(const double* diag, const double* sub,
 int lssvr_estimate_seam(const double* x, const double* W, int M, int64_t ne, const double* a_seam_host,
                         double* eta2, double* out3, void* stream);
 
+/*
+ * Element lists for the table kernels: hp refinement of -(a u')' + b u' + c u = f.  ADDITIVE to
+ * ABI 7: two new symbols, no existing entry, struct, constant or kernel instantiation changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * lssvr_enhance_react_subset -- lssvr_enhance_react_ws for the nsub elements elem_ids[0..nsub) of a shard of ne_mesh
+ * elements, with the element-list conventions of lssvr_enhance_subset: ONE (M, n_colloc) per call, a p-adaptive mesh
+ * is one call per degree that occurs (lssvr_group_by_degree supplies the lists).
+ *   x[ne_mesh+1], u[ne_mesh+1], gamma_values[ne_mesh] (NULL = the scalar gamma), status[ne_mesh] (may be NULL)
+ *                        indexed by MESH element
+ *   elem_ids[nsub]       device int64 mesh indices, distinct (NULL = all elements in order; nsub must equal ne_mesh)
+ *   a_values, da_values, c_values, rhs_values   a, a', c, f at the n_colloc abscissae of the LISTED elements
+ *                        (lssvr_colloc_points_subset), indexed by POSITION in elem_ids: LSSVR_TABLE_ELEMENT_MAJOR
+ *                        t[pos*n_colloc + k] or LSSVR_TABLE_POINT_MAJOR t[k*nsub + pos].  da_values = a' - b gives the
+ *                        convection rows (the convention above)
+ *   c_values == NULL     the variable-coefficient rows -(a u')' = f: the kernels lssvr_enhance_varcoef_ws picks for
+ *                        this (M, n_colloc) -- the lane kernel up to M = 22, the f64-MFMA kernel above.  Otherwise the
+ *                        reaction rows: the lane kernel up to M = 16, the f64-MFMA kernel above
+ *   W, ldw               row of mesh element id starts at W + id*ldw (ldw >= M; 0 = M), as in lssvr_enhance_subset;
+ *                        rows that are not listed are not written
+ * An id outside [0, ne_mesh) touches nothing -- no row, no status, no table entry is used for a store -- and is
+ * counted in fail_count.  Primal solve only: n_colloc < M-2 is LSSVR_ERR_SOLVER (a list launch has no dual route).
+ * elem_ids == NULL with nsub != ne_mesh, nsub > ne_mesh and 0 < ldw < M are LSSVR_ERR_SIZE; nsub == 0 succeeds and
+ * launches nothing.  With elem_ids == NULL, gamma_values == NULL and ldw 0 or M the call issues the launch of
+ * lssvr_enhance_react_ws (c_values == NULL: lssvr_enhance_varcoef_ws) and gives its bits.  The rows of the lane
+ * kernels do not depend on what else is in the launch, bit for bit; the f64-MFMA kernel picks the series or the
+ * recurrence for its boundary rows per PAIR of launch neighbours, so there a row may differ in the last bits with its
+ * neighbour.
+ *
+ * lssvr_colloc_points_subset -- the abscissae of lssvr_colloc_points(_pm) for the listed elements only, by position:
+ * xc[pos*n_colloc + k] (LSSVR_TABLE_ELEMENT_MAJOR) or xc[k*nsub + pos] (LSSVR_TABLE_POINT_MAJOR), bit for bit the
+ * entries of element elem_ids[pos] of the whole-mesh call.  elem_ids == NULL: all elements in order (nsub must equal
+ * ne_mesh).  Nothing is written for an id outside [0, ne_mesh).
+ */
+int lssvr_enhance_react_subset(const double* x, const double* u, int64_t ne_mesh,
+                               const int64_t* elem_ids, int64_t nsub,
+                               int64_t elem_offset, int64_t ne_global,
+                               double gxmin, double gxmax, double bc_left, double bc_right,
+                               int M, int n_colloc, double gamma, const double* gamma_values,
+                               const double* a_values, const double* da_values, const double* c_values,
+                               const double* rhs_values, int table_layout,
+                               double* W, int64_t ldw, int32_t* status, int32_t* fail_count, void* stream);
+int lssvr_colloc_points_subset(const double* x, int64_t ne_mesh, const int64_t* elem_ids, int64_t nsub,
+                               int n_colloc, int table_layout, double* xc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
