@@ -130,6 +130,10 @@ SIGNATURES = {
     "lssvr_tridiag_bc_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
     "lssvr_tridiag_bc_solve_multi": _sig(_BANDS, _ENDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
     "lssvr_tridiag_ns_bc_solve_multi": _sig([_c_dp], _BANDS, _ENDS, [_c_i64, _c_int, _c_dp], _WS, _STREAM),
+    # pivoting solve (additive to ABI 7): the _ns_bc_ arguments with info between u and work
+    "lssvr_tridiag_pivot_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
+    "lssvr_tridiag_pivot_solve_multi": _sig([_c_dp], _BANDS, _ENDS, [_c_i64, _c_int, _c_dp, _c_dp], _WS, _STREAM),
+    "lssvr_tridiag_pivot_solve_host": _sig([_c_dp], _BANDS, _ENDS, [_c_i64, _c_int, _c_dp, _c_dp]),
     "lssvr_estimate_ends": _sig([_c_dp, _c_dp, _c_int, _c_i64, _c_int, _c_int, _c_hd, _c_hd, _c_hd, _c_dp, _c_dp],
                                 _STREAM),
     # goal-oriented estimator (additive to ABI 7): x, Wu, Wz, ne, M, nq, a, a', c, f, j, layout, a_ends, kinds,

@@ -928,15 +928,20 @@ int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub
 // Free ends: Dirichlet or Robin at each end (tridiag.hip).  sup == NULL: the symmetric entry, `off` arrives as sub.
 int64_t lssvr_tridiag_bc_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_bc_work_bytes(ne, nc); }
 
-static int check_end_kinds(int kind_left, int kind_right, const double* kappa_host) {
+// (any_sign: the pivoting solve takes a kappa of either sign)
+static int check_end_kinds(int kind_left, int kind_right, const double* kappa_host, bool any_sign = false) {
   if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
       (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
     return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
                 kind_right);
   if (!kappa_host) return fail(LSSVR_ERR_NULL, "kappa_host must be non-NULL");
   for (int i = 0; i < 2; ++i)
-    if ((i ? kind_right : kind_left) == LSSVR_END_ROBIN && !(kappa_host[i] >= 0.0 && kappa_host[i] < INFINITY))
-      return fail(LSSVR_ERR_SIZE, "kappa[%d] = %g must be finite and >= 0", i, kappa_host[i]);
+    if ((i ? kind_right : kind_left) == LSSVR_END_ROBIN) {
+      if (any_sign && !(kappa_host[i] > -INFINITY && kappa_host[i] < INFINITY))
+        return fail(LSSVR_ERR_SIZE, "kappa[%d] = %g must be finite", i, kappa_host[i]);
+      if (!any_sign && !(kappa_host[i] >= 0.0 && kappa_host[i] < INFINITY))
+        return fail(LSSVR_ERR_SIZE, "kappa[%d] = %g must be finite and >= 0", i, kappa_host[i]);
+    }
   return LSSVR_OK;
 }
 
@@ -977,6 +982,45 @@ int lssvr_tridiag_ns_bc_solve_multi(const double* diag, const double* sub, const
                                     int64_t work_bytes, void* stream) {
   return tridiag_bc_solve(diag, sub, sup, load, kind_left, kind_right, end_values, kappa_host, ne, nc, u, work,
                           work_bytes, stream, false);
+}
+
+// The pivoting solve (tridiag_pivot.hip): the ends of lssvr_tridiag_ns_bc_solve_multi, any non-singular matrix.
+int64_t lssvr_tridiag_pivot_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_pivot_work_bytes(ne, nc); }
+
+int lssvr_tridiag_pivot_solve_multi(const double* diag, const double* sub, const double* sup, const double* load,
+                                    int kind_left, int kind_right, const double* end_values,
+                                    const double* kappa_host, int64_t ne, int nc, double* u, int32_t* info,
+                                    void* work, int64_t work_bytes, void* stream) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
+  if (!diag || !sub || !sup || !load || !u || !work)
+    return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u, work must be non-NULL");
+  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
+  if (rc != LSSVR_OK) return rc;
+  const int64_t need = lssvr::tridiag_pivot_work_bytes(ne, nc);
+  if (work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_pivot_work_bytes(%lld, %d) = %lld",
+                (long long)work_bytes, (long long)ne, nc, (long long)need);
+  const bool f0 = kind_left == LSSVR_END_ROBIN, f1 = kind_right == LSSVR_END_ROBIN;
+  const double k0 = f0 ? kappa_host[0] : 0.0, k1 = f1 ? kappa_host[1] : 0.0;
+  return check_launch(lssvr::tridiag_pivot_solve(diag, sub, sup, load, ne, nc, f0, f1, k0, k1, end_values, u, info,
+                                                 work, reinterpret_cast<hipStream_t>(stream)),
+                      "tridiag_pivot_solve_multi");
+}
+
+// the same on host arrays, no device involved
+int lssvr_tridiag_pivot_solve_host(const double* diag, const double* sub, const double* sup, const double* load,
+                                   int kind_left, int kind_right, const double* end_values,
+                                   const double* kappa_host, int64_t ne, int nc, double* u, int32_t* info) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
+  if (!diag || !sub || !sup || !load || !u) return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u must be non-NULL");
+  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
+  if (rc != LSSVR_OK) return rc;
+  const bool f0 = kind_left == LSSVR_END_ROBIN, f1 = kind_right == LSSVR_END_ROBIN;
+  lssvr::tridiag_pivot_host(diag, sub, sup, load, ne, nc, f0, f1, f0 ? kappa_host[0] : 0.0, f1 ? kappa_host[1] : 0.0,
+                            end_values, u, info);
+  return LSSVR_OK;
 }
 
 // Periodic ends (tridiag.hip).  sup == NULL: the symmetric entry, `off` arrives as sub.

@@ -218,6 +218,18 @@ hipError_t tridiag_periodic_solve(const double* diag, const double* off, const d
                                   double* u, void* work, hipStream_t s);
 hipError_t tridiag_ns_periodic_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                      int64_t ne, int nc, double* u, void* work, hipStream_t s);
+// tridiag_pivot.hip: the solve with free ends above for tridiagonal matrices that need not be dominant -- a recursive partitioned
+// solve with scaled partial pivoting at every level.  Same unknowns, end terms and passes as
+// tridiag_ns_bc_solve; k0 / k1 of any sign; the symmetric caller passes off for sub and sup.  info (device, may be
+// NULL): the number of pivots, over all levels, that were zero or not finite after the row choice -- 0 for a matrix
+// that is non-singular to working precision.  Row q does not depend on nc, bit for bit.
+int64_t tridiag_pivot_work_bytes(int64_t ne, int nc);
+hipError_t tridiag_pivot_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                               int64_t ne, int nc, bool f0, bool f1, double k0, double k1, const double* bc,
+                               double* u, int32_t* info, void* work, hipStream_t s);
+// the same solve on host arrays, without a device, through the routines the kernels call (for tests without a GPU)
+void tridiag_pivot_host(const double* diag, const double* sub, const double* sup, const double* load, int64_t ne,
+                        int nc, bool f0, bool f1, double k0, double k1, const double* bc, double* u, int32_t* info);
 // fem_eval.hip: the load of p1_assemble / _react / _conv for nc tabulated right-hand sides rhs_quad[nc][ne*nquad] ->
 // load[nc][ne+1], no bands
 hipError_t p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,

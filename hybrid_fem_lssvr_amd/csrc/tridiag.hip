@@ -16,6 +16,7 @@
 // vanish.  The symmetric P1 matrix is SPD (Schur complements of SPD are SPD).  The non-symmetric rows are dominant
 // when, on every element, the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 and c >= 0.
 // Outside that the solve may divide by a small number without notice: the caller refines the mesh first.
+// (tridiag_pivot.hip is the solver that pivots: lssvr_tridiag_pivot_solve_multi)
 //
 // Several right-hand sides on one matrix.  Everything except the y recurrence and the
 // right-hand side is independent of the load, so every kernel takes NC cases: it loads the three bands of a chunk

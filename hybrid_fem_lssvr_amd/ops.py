@@ -838,7 +838,8 @@ def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=N
 def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
     """:func:`tridiag_dirichlet_solve` for bands that are not symmetric (``lssvr_tridiag_ns_dirichlet_solve``):
     row i is sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i] -> u[ne+1].  No pivoting: the rows must be
-    diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``)."""
+    diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``);
+    :func:`tridiag_pivot_solve` pivots."""
     return _tridiag_solve("lssvr_tridiag_ns_dirichlet_solve", ("diag", "sub", "sup", "load"), (diag, sub, sup, load),
                           "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)", (u0, u1), out, work,
                           stream)
@@ -871,9 +872,10 @@ def tridiag_ns_dirichlet_solve_multi(diag, sub, sup, load, bc=None, *, out=None,
 END_DIRICHLET, END_ROBIN = _capi.END_DIRICHLET, _capi.END_ROBIN      # LSSVR_END_*: the kind of one end of the domain
 
 
-def _end_kinds(end_kinds, kappa):
+def _end_kinds(end_kinds, kappa, any_sign=False):
     """((kind_left, kind_right), host double[2] kappa) of a call with free ends: kinds in {0, 1}, kappa finite and
-    >= 0 (``ValueError`` otherwise; read at a Robin end only, but checked at both)."""
+    >= 0 (``ValueError`` otherwise; read at a Robin end only, but checked at both).  ``any_sign``: the pivoting solve
+    takes a finite kappa of either sign."""
     try:
         kinds = tuple(end_kinds)
         kap = tuple(float(k) for k in kappa)
@@ -883,7 +885,9 @@ def _end_kinds(end_kinds, kappa):
         raise ValueError("end_kinds and kappa must be pairs (left, right)")
     if any(isinstance(k, bool) or k not in (END_DIRICHLET, END_ROBIN) for k in kinds):
         raise ValueError(f"end_kinds must be END_DIRICHLET (0) or END_ROBIN (1), got {kinds!r}")
-    if not all(math.isfinite(k) and k >= 0.0 for k in kap):
+    if any_sign and not all(math.isfinite(k) for k in kap):
+        raise ValueError(f"kappa must be finite, got {kap!r}")
+    if not any_sign and not all(math.isfinite(k) and k >= 0.0 for k in kap):
         raise ValueError(f"kappa must be finite and >= 0, got {kap!r}")
     return (int(kinds[0]), int(kinds[1])), (ctypes.c_double * 2)(*kap)
 
@@ -980,6 +984,87 @@ def tridiag_ns_bc_solve(diag, sub, sup, load, end_kinds, kappa, end_values=(0.0,
     return _tridiag_bc_solve("lssvr_tridiag_ns_bc_solve_multi", ("diag", "sub", "sup", "load"),
                              (diag, sub, sup, load), "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)",
                              end_kinds, kappa, end_values, out, work, stream, False)
+
+
+def _tridiag_pivot_solve(bands, lengths, end_kinds, kappa, end_values, out, work, stream, multi, return_info):
+    """``lssvr_tridiag_pivot_solve_multi`` on ``bands`` = (diag, sub, sup, load) -> u[nc, ne+1], or u[ne+1] for the
+    single form; with ``return_info`` the pair (u, info), info an int32 device tensor of one element."""
+    lib = _capi.load()
+    names = ("diag", "sub", "sup", "load")
+    for nm, t in zip(names, bands):
+        _dev(t, nm)
+    diag, load = bands[0], bands[-1]
+    ne = bands[1].numel()
+    if not multi:
+        if load.dim() != 1:
+            raise ValueError(lengths)
+        load = load.unsqueeze(0)
+    if (diag.numel() != ne + 1 or bands[2].numel() != ne or load.dim() != 2 or load.shape[1] != ne + 1):
+        raise ValueError(lengths)
+    if ne < 1:
+        raise ValueError("need at least one element")
+    nc = int(load.shape[0])
+    if nc < 1:
+        raise ValueError("need at least one case")
+    kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
+    if out is None:
+        out = torch.empty((nc, ne + 1), dtype=torch.float64, device=diag.device)
+    else:
+        _dev(out, "out")
+        if not multi:
+            if out.numel() != ne + 1:
+                raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
+            out = out.view(1, ne + 1)
+        elif out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc:
+            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
+    need = lib.lssvr_tridiag_pivot_work_bytes(ne, nc)
+    if work is not None:
+        _dev(work, "work")
+        if work.numel() * work.element_size() < need:
+            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                             f"lssvr_tridiag_pivot_work_bytes({ne}, {nc}) = {need}")
+    work = _scratch(work, need, diag.device)
+    ev = end_values
+    if ev is not None:
+        if not isinstance(ev, torch.Tensor):
+            ev = np.asarray(ev, dtype=np.float64)
+            ev = torch.as_tensor(np.ascontiguousarray(ev if multi else ev.reshape(-1, 2)), device=diag.device)
+        _dev(ev, "end_values")
+        if tuple(ev.shape) != (nc, 2):
+            raise ValueError(f"end_values must be [nc, 2] = [{nc}, 2], got {list(ev.shape)}")
+    info = torch.zeros(1, dtype=torch.int32, device=diag.device) if return_info else None
+    for nm, t in (*zip(names, bands), ("end_values", ev), ("out", out), ("work", work)):
+        if t is not None and t.device != diag.device:
+            raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
+    rc = lib.lssvr_tridiag_pivot_solve_multi(*map(_ptr, (diag, bands[1], bands[2], load)), kinds[0], kinds[1],
+                                             _ptr(ev), kap, ne, nc, _ptr(out), _ptr(info), _ptr(work),
+                                             work.numel() * work.element_size(), _stream(stream))
+    _capi.check(rc, "lssvr_tridiag_pivot_solve_multi")
+    u = out[:nc] if multi else out[0]
+    return (u, info) if return_info else u
+
+
+def tridiag_pivot_solve_multi(diag, sub, sup, load, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0),
+                              end_values=None, *, out=None, work=None, stream=None, return_info=False):
+    """:func:`tridiag_ns_bc_solve_multi` for tridiagonal matrices that are not diagonally dominant but well conditioned
+    (``lssvr_tridiag_pivot_solve_multi``): a recursive partitioned solve with scaled partial
+    pivoting at every level, so the rows need not be diagonally dominant -- negative or sign-changing reaction, cell
+    Peclet number above 1 (the Galerkin solution, oscillations included), a Robin end with ``kappa`` of either sign.
+    Symmetric bands: pass ``off`` for both ``sub`` and ``sup``.  Arguments as in :func:`tridiag_ns_bc_solve_multi`;
+    row j is bit-identical to the call with that case alone; the bands and loads are left as they are.  ``work``: at
+    least ``lssvr_tridiag_pivot_work_bytes(ne, nc)`` bytes.  ``return_info=True``: ``(u, info)`` with ``info`` an
+    int32 device tensor [1], the number of pivots that were zero or not finite after the row choice -- nonzero means
+    the matrix is singular and ``u`` is not a solution; zero says only that no such pivot was met."""
+    return _tridiag_pivot_solve((diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] (diag, "
+                                "sub, sup, load)", end_kinds, kappa, end_values, out, work, stream, True, return_info)
+
+
+def tridiag_pivot_solve(diag, sub, sup, load, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0),
+                        end_values=(0.0, 0.0), *, out=None, work=None, stream=None, return_info=False):
+    """One right-hand side of :func:`tridiag_pivot_solve_multi` (the nc = 1 call of the same entry): load
+    float64[ne+1], ``end_values`` a pair (left, right) -> u[ne+1]."""
+    return _tridiag_pivot_solve((diag, sub, sup, load), "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, "
+                                "load)", end_kinds, kappa, end_values, out, work, stream, False, return_info)
 
 
 def _tridiag_periodic_solve(entry, names, bands, lengths, out, work, stream, multi):

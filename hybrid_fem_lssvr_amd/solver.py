@@ -19,7 +19,10 @@ Additions over the reference (all keyword-only, defaults reproduce the reference
 ``nquad`` (scikit-fem's default 2-point rule for P1), ``mesh`` (a scikit-fem style
 mesh/basis or node array instead of ``np.linspace(a, b, num_fem_nodes)``), ``fem_solver``
 (``"bands"``: the assembled float64 tridiagonal system, as ``enforce`` + ``solve`` see it;
-``"flux"``: exact-structure prefix-scan solve), ``solver``
+``"flux"``: exact-structure prefix-scan solve; ``"pivot"``: the bands through the
+pivoting partitioned solve of DESIGN.md section 24 -- it lifts the host checks ``c >= 0``, cell Peclet number <= 1 and
+``kappa + b n / 2 >= 0`` of the unpivoted solve, returns the plain Galerkin solution above Peclet 1, raises
+``RuntimeError`` for a system that is singular to working precision, and has no periodic form), ``solver``
 (``ops.SOLVER_PRIMAL`` default; ``ops.SOLVER_SHARED``: uniform meshes only, one shared operator
 applied per element), ``coef`` (a pair ``(a, da)`` of numpy-vectorised callables:
 solve, estimate and refine ``-(a u')' = f`` instead of ``-u'' = f``, BASELINE config 5 and DESIGN.md
@@ -416,8 +419,8 @@ class FEMLSSVRPrimalSolver:
         self.mesh = None if mesh is None else as_line_mesh(mesh)
         self.device = device
         self.solver_id = solver
-        if fem_solver not in ("bands", "flux"):
-            raise ValueError("fem_solver must be 'bands' or 'flux'")
+        if fem_solver not in ("bands", "flux", "pivot"):
+            raise ValueError("fem_solver must be 'bands', 'flux' or 'pivot'")
         self.fem_solver = fem_solver
         if coef is not None:
             if not (isinstance(coef, (tuple, list)) and len(coef) == 2 and all(callable(c) for c in coef)):
@@ -450,6 +453,10 @@ class FEMLSSVRPrimalSolver:
                                  "term have a primal solve only")
         self.convection = convection
         if isinstance(boundary, str) and boundary == "periodic":
+            if fem_solver == "pivot":
+                raise ValueError("boundary='periodic' needs fem_solver='bands': the seam Schur complement is built "
+                                 "from two Dirichlet solves, which can be singular where the periodic problem is "
+                                 "not; the pivoting solve has no cyclic form yet")
             if fem_solver == "flux":
                 raise ValueError("boundary='periodic' needs fem_solver='bands': the flux solve factors "
                                  "A = D^T K D between two Dirichlet values")
@@ -515,19 +522,20 @@ class FEMLSSVRPrimalSolver:
             bc = tuple(d if g is None else g for d, g in zip(bc, _Boundary(self.boundary).values))
         return gd, bc
 
-    def _reaction_positive(self, eq, nodes):
-        """Whether the reaction term is positive at a quadrature point of the P1 assembly."""
+    def _reaction_positive(self, eq, nodes, nonzero=False):
+        """Whether the reaction term is positive (``nonzero``: not zero) at a quadrature point of the P1 assembly."""
         if eq.c is None:
             return False
         xi = np.polynomial.legendre.leggauss(int(self.nquad))[0]
         xq = 0.5 * (nodes[:-1] + nodes[1:])[:, None] + 0.5 * np.diff(nodes)[:, None] * xi[None, :]
-        return bool(np.any(np.broadcast_to(np.asarray(eq.c(xq), dtype=np.float64), xq.shape) > 0.0))
+        cq = np.broadcast_to(np.asarray(eq.c(xq), dtype=np.float64), xq.shape)
+        return bool(np.any(cq != 0.0 if nonzero else cq > 0.0))
 
     def _check_periodic(self, m):
         """What the periodic solve needs, on the host and before any launch: the assembled bands and a per-element
         solver, at least two elements, a problem that is not singular, and coefficients that are periodic on this
         interval."""
-        if self.fem_solver == "flux" or self.solver_id == ops.SOLVER_SHARED:      # (attributes are public)
+        if self.fem_solver != "bands" or self.solver_id == ops.SOLVER_SHARED:     # (attributes are public)
             raise ValueError("boundary='periodic' needs fem_solver='bands' and a per-element solver")
         eq = self._eq
         nodes = np.asarray(m.nodes, dtype=np.float64)
@@ -547,7 +555,8 @@ class FEMLSSVRPrimalSolver:
 
     def _check_boundary(self, m):
         """What makes the unpivoted solve with a Neumann or Robin end safe, on the host and before any launch: the
-        matrix is not singular, and with convection the end row keeps its dominance."""
+        matrix is not singular, and with convection the end row keeps its dominance.  ``fem_solver="pivot"`` needs
+        only the first: two Neumann ends and a reaction that vanishes at every quadrature point."""
         if self._periodic:
             return self._check_periodic(m)
         bnd = self._bnd
@@ -555,13 +564,15 @@ class FEMLSSVRPrimalSolver:
             return
         if self.fem_solver == "flux" or self.solver_id == ops.SOLVER_SHARED:      # (attributes are public)
             raise ValueError("a Neumann or Robin end needs fem_solver='bands' and a per-element solver")
+        pivot = self.fem_solver == "pivot"
         eq = self._eq
         nodes = np.asarray(m.nodes, dtype=np.float64)
         if bnd.kinds == [ops.END_ROBIN, ops.END_ROBIN] and bnd.kappa[0] + bnd.kappa[1] == 0.0:
-            if not self._reaction_positive(eq, nodes):
+            if not self._reaction_positive(eq, nodes, nonzero=pivot):
                 raise ValueError("singular problem: two Neumann ends (kappa_left + kappa_right = 0) and no reaction "
-                                 "that is positive at a quadrature point leave u determined up to a constant")
-        if eq.b is not None:
+                                 f"that is {'nonzero' if pivot else 'positive'} at a quadrature point leave u "
+                                 "determined up to a constant")
+        if eq.b is not None and not pivot:
             b_end = np.broadcast_to(np.asarray(eq.b(nodes[[0, -1]]), dtype=np.float64), (2,))
             for i, (side, n) in enumerate((("left", -1.0), ("right", 1.0))):
                 if bnd.kinds[i] == ops.END_ROBIN and not bnd.kappa[i] + 0.5 * n * float(b_end[i]) >= 0.0:
@@ -581,7 +592,7 @@ class FEMLSSVRPrimalSolver:
             kw["a_quad"] = _tabulate(eq.a, xq)
         if eq.c is not None:             # consistent mass matrix of c in the bands
             cq = _tabulate(eq.c, xq)
-            if bool((cq < 0).any().item()):
+            if self.fem_solver != "pivot" and bool((cq < 0).any().item()):
                 raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
                                  "pivot and assumes an SPD matrix (c >= 0)")
             kw["c_quad"] = cq
@@ -599,7 +610,9 @@ class FEMLSSVRPrimalSolver:
             fq = _to_dev(rhs(xq.cpu().numpy()), x.device)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
         bnd = self._bnd
-        if self._periodic:
+        if self.fem_solver == "pivot":
+            u = self._pivot_solve(bands, bands["load"], (u0, u1), False)
+        elif self._periodic:
             # node ne is node 0: the cyclic solve reads no end value (_check_periodic has run)
             if "b_quad" in kw:
                 u = ops.tridiag_ns_periodic_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"])
@@ -665,6 +678,8 @@ class FEMLSSVRPrimalSolver:
                 load = loads
             else:
                 load[torch.as_tensor(tabulated, device=dev)] = loads
+        if self.fem_solver == "pivot":
+            return x, self._pivot_solve(bands, load, _to_dev(bc, dev), True)
         if self._periodic:
             if "b_quad" in kw:
                 return x, ops.tridiag_ns_periodic_solve_multi(bands["diag"], bands["sub"], bands["sup"], load)
@@ -683,13 +698,32 @@ class FEMLSSVRPrimalSolver:
             U = ops.tridiag_dirichlet_solve_multi(bands["diag"], bands["off"], load, bc_dev)
         return x, U
 
+    def _pivot_solve(self, bands, load, end_values, multi):
+        """The P1 solve of ``fem_solver="pivot"`` on the assembled bands -- symmetric (off) or
+        not (sub, sup) -- with the configured ends; ``RuntimeError`` when the solve met a pivot that was zero or not
+        finite.  Reading that count waits for the solve."""
+        sub, sup = (bands["sub"], bands["sup"]) if "sub" in bands else (bands["off"], bands["off"])
+        bnd = self._bnd
+        kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (bnd.kinds, bnd.kappa)
+        fn = ops.tridiag_pivot_solve_multi if multi else ops.tridiag_pivot_solve
+        u, info = fn(bands["diag"], sub, sup, load, kinds, kappa, end_values, return_info=True)
+        bad = int(info.item())
+        if bad:
+            raise RuntimeError(f"P1 system singular to working precision: the pivoting tridiagonal solve met {bad} "
+                               "pivot(s) that were zero or not finite; the problem has no unique discrete solution "
+                               "on this mesh (change the mesh, the coefficients or the boundary conditions)")
+        return u
+
     def _convection_quad(self, eq, x, xq):
         """b at the quadrature points ``xq`` [ne, nquad], after the check that makes the unpivoted, unstabilised solve safe:
         the cell Peclet number |bbar_e| h_e / (2 abar_e) <= 1 on every element (bbar, abar: quadrature means).
-        Host arithmetic on the tabulated values, before the assembly is launched."""
+        Host arithmetic on the tabulated values, before the assembly is launched.  ``fem_solver="pivot"`` tabulates b
+        and skips the check: above Peclet 1 it returns the Galerkin solution, oscillations included."""
         xq = xq.cpu().numpy()
         w = 0.5 * np.polynomial.legendre.leggauss(int(self.nquad))[1]
         bq = np.array(np.broadcast_to(np.asarray(eq.b(xq), dtype=np.float64), xq.shape))     # (a writable copy)
+        if self.fem_solver == "pivot":
+            return _to_dev(bq, x.device)
         abar = 1.0 if eq.a is None else np.broadcast_to(np.asarray(eq.a(xq), dtype=np.float64), xq.shape) @ w
         nodes = x.cpu().numpy()
         pe = np.abs(bq @ w) * np.diff(nodes) / (2.0 * abar)

@@ -757,6 +757,7 @@ int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub
  * lssvr_tridiag_dirichlet_solve_multi.  work: device scratch of work_bytes >= lssvr_tridiag_bc_work_bytes(ne, nc),
  * which is sized for two free ends (ne + 1 unknowns) whatever the kinds are.  Same no-pivoting rule: kappa >= 0 keeps
  * an SPD matrix SPD.  Two Neumann ends without a reaction term make the matrix singular; the caller checks.
+ * (lssvr_tridiag_pivot_solve_multi, below, is the solve that pivots.)
  *
  * lssvr_tridiag_ns_bc_solve_multi -- the same for the bands of lssvr_p1_assemble_conv; both ends Dirichlet gives the
  * bits of lssvr_tridiag_ns_dirichlet_solve_multi.  Row dominance at a Robin end needs kappa + b(x_end) n / 2 >= 0
@@ -784,6 +785,38 @@ int lssvr_tridiag_ns_bc_solve_multi(const double* diag, const double* sub, const
 int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int kind_left, int kind_right,
                         const double* kappa_host, const double* g_host, const double* a_ends_host,
                         double* eta2, double* out3, void* stream);
+
+/*
+ * Pivoting tridiagonal solve.  ADDITIVE to ABI 7: two new symbols, no existing entry, struct or
+ * constant changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * lssvr_tridiag_pivot_solve_multi -- lssvr_tridiag_ns_bc_solve_multi for well-conditioned tridiagonal matrices whose
+ * rows need not be diagonally dominant (negative or sign-changing reaction, cell Peclet number above 1,
+ * kappa + b n / 2 < 0 at a Robin end); what is not covered is in DESIGN.md section 24.  A recursive partitioned solve
+ * with scaled partial pivoting inside every partition and at the coarsest level.  diag, sub, sup, load, kind_left,
+ * kind_right, end_values, kappa_host,
+ * ne, nc and u as in lssvr_tridiag_ns_bc_solve_multi, except that kappa_host may have either sign (finite); a
+ * symmetric caller passes `off` for both sub and sup.  The bands and loads are read only.  ne == 1 and systems of one
+ * or two unknowns are handled.  Row j of u is bit-identical to the nc = 1 call on case j.
+ *   info   DEVICE int32 (NULL: not wanted): the number of pivots, over all levels, that were zero or not finite after
+ *          the row choice.  0: no such pivot was met -- no more than that: a matrix that is singular only up to
+ *          rounding gives large finite values and 0.  > 0: the matrix is singular; the entry still returns
+ *          LSSVR_OK, u then holds finite garbage -- such a pivot's reciprocal is replaced by 0, nothing is divided by
+ *          it.  Read it after synchronising the stream.
+ *   work   device scratch of work_bytes >= lssvr_tridiag_pivot_work_bytes(ne, nc), sized for two free ends.
+ * Above cell Peclet number 1 this returns the Galerkin solution, oscillations included: pivoting is not stabilisation.
+ * lssvr_tridiag_pivot_solve_host -- the same solve on HOST arrays (diag, sub, sup, load, end_values, u and info all in
+ * host memory), partition by partition through the routines the kernels are made of, with the same levels and passes.
+ * No device is touched: it exists so that the arithmetic can be checked where there is no GPU, and it is not fast.
+ */
+int64_t lssvr_tridiag_pivot_work_bytes(int64_t ne, int nc);
+int lssvr_tridiag_pivot_solve_multi(const double* diag, const double* sub, const double* sup, const double* load,
+                                    int kind_left, int kind_right, const double* end_values,
+                                    const double* kappa_host, int64_t ne, int nc,
+                                    double* u, int32_t* info, void* work, int64_t work_bytes, void* stream);
+int lssvr_tridiag_pivot_solve_host(const double* diag, const double* sub, const double* sup, const double* load,
+                                   int kind_left, int kind_right, const double* end_values,
+                                   const double* kappa_host, int64_t ne, int nc, double* u, int32_t* info);
 
 /*
  * Goal-oriented error estimation (dual-weighted residual).  ADDITIVE to ABI 7 (new symbols; LSSVR_ABI_VERSION stays 7).
