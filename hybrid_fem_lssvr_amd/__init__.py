@@ -8,6 +8,7 @@ gfx950 kernels behind a C ABI (``include/lssvr_hip.h``).
 from . import _capi, ops  # noqa: F401
 from .mesh import LineMesh, P1Basis, as_line_mesh  # noqa: F401
 from .solver import (  # noqa: F401
+    EigenSolution,
     EnhancedSolution,
     FEMLSSVRPrimalSolver,
     GoalEstimate,

@@ -61,6 +61,7 @@ _SOLN = [_c_dp, _c_dp, _c_i64, _c_int]               # x, W, ne, M
 _EST_OUT = [_c_dp, _c_dp, _c_dp, _c_dp]              # eta2, jump, out3, work
 _ENDS = [_c_int, _c_int, _c_dp, _c_hd]                # kind_left, kind_right, end_values, kappa_host
 _STEP = _SHARD + [_c_hd, _c_int] + _BANDS + _OUT     # ..., rhs_params_host, nquad, bands, outputs
+_EIG_BANDS = [_c_dp] * 4 + [_c_int, _c_int, _c_hd]   # kdiag, koff, mdiag, moff, kind_left, kind_right, kappa_host
 
 
 def _sig(*groups, res=_c_int):
@@ -156,6 +157,16 @@ SIGNATURES = {
                              _c_dp, _c_dp, _c_dp, _c_dp, _c_dp], _STREAM),
     "lssvr_group_work_bytes": _sig([_c_i64], res=_c_i64),
     "lssvr_group_by_degree": _sig([_c_dp, _c_i64, _c_dp, _c_dp, _c_dp], _STREAM),
+    # eigenproblems (additive to ABI 7): kdiag, koff, mdiag, moff, kind_left, kind_right, kappa_host, ne, ...
+    "lssvr_eig_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
+    "lssvr_eig_apply": _sig(_EIG_BANDS, [_c_i64, _c_int], [_c_dp] * 4, _WS, _STREAM),
+    "lssvr_eig_ritz": _sig([_c_dp, _c_dp, _c_int, _c_dbl, _c_dp, _c_dp, _c_dp], _STREAM),
+    "lssvr_eig_ritz_host": _sig([_c_hd, _c_hd, _c_int, _c_dbl, _c_hd, _c_hd, _c_dp]),
+    "lssvr_eig_rotate": _sig([_c_dp] * 5, [_c_int, _c_int, _c_i64, _c_int], [_c_dp] * 3, _WS, _STREAM),
+    "lssvr_eig_count": _sig(_EIG_BANDS, [_c_i64, _c_dp, _c_int, _c_dbl, _c_dp], _STREAM),
+    "lssvr_eig_count_host": _sig([_c_hd] * 4, [_c_int, _c_int, _c_hd], [_c_i64, _c_hd, _c_int, _c_dbl, _c_dp]),
+    "lssvr_eig_rayleigh": _sig(_SOLN, [_c_int], [_c_dp] * 3, [_c_int], [_c_int, _c_int, _c_hd], [_c_dp, _c_dp],
+                               _STREAM),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

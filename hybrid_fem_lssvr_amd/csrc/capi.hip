@@ -1367,4 +1367,167 @@ int lssvr_fp64_probe(double* out, int blocks, int iters, int use_mfma, void* str
                       "fp64_probe");
 }
 
+// Eigenproblems (eigen.hip).  What the entries share: the sizes, the four bands and the ends.
+static int bind_eig(lssvr::EigArgs& a, const double* kdiag, const double* koff, const double* mdiag,
+                    const double* moff, int kind_left, int kind_right, const double* kappa_host, int64_t ne, int nb) {
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (nb < 1 || nb > 8) return fail(LSSVR_ERR_SIZE, "nb = %d outside [1, 8]", nb);
+  if (!kdiag || !koff || !mdiag || !moff) return fail(LSSVR_ERR_NULL, "kdiag, koff, mdiag, moff must be non-NULL");
+  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
+  if (rc != LSSVR_OK) return rc;
+  a.kdiag = kdiag;
+  a.koff = koff;
+  a.mdiag = mdiag;
+  a.moff = moff;
+  a.ne = ne;
+  a.nb = nb;
+  a.f0 = kind_left == LSSVR_END_ROBIN;
+  a.f1 = kind_right == LSSVR_END_ROBIN;
+  a.k0 = a.f0 ? kappa_host[0] : 0.0;
+  a.k1 = a.f1 ? kappa_host[1] : 0.0;
+  return LSSVR_OK;
+}
+
+static int check_eig_work(const void* work, int64_t work_bytes, int64_t ne, int nb) {
+  if (!work) return fail(LSSVR_ERR_NULL, "work must be non-NULL");
+  const int64_t need = lssvr::eig_work_bytes(ne, nb);
+  if (work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_eig_work_bytes(%lld, %d) = %lld", (long long)work_bytes,
+                (long long)ne, nb, (long long)need);
+  return LSSVR_OK;
+}
+
+int64_t lssvr_eig_work_bytes(int64_t ne, int nb) { return lssvr::eig_work_bytes(ne, nb); }
+
+int lssvr_eig_apply(const double* kdiag, const double* koff, const double* mdiag, const double* moff, int kind_left,
+                    int kind_right, const double* kappa_host, int64_t ne, int nb, const double* Z, double* MZ,
+                    double* KZ, double* gram, void* work, int64_t work_bytes, void* stream) {
+  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
+  if (ne == 0) return LSSVR_OK;
+  lssvr::EigArgs a{};
+  int rc = bind_eig(a, kdiag, koff, mdiag, moff, kind_left, kind_right, kappa_host, ne, nb);
+  if (rc != LSSVR_OK) return rc;
+  if (!Z || !MZ || !KZ || !gram) return fail(LSSVR_ERR_NULL, "Z, MZ, KZ, gram must be non-NULL");
+  rc = check_eig_work(work, work_bytes, ne, nb);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::eig_apply(a, Z, MZ, KZ, gram, work, reinterpret_cast<hipStream_t>(stream)), "eig_apply");
+}
+
+static int check_ritz(const double* A, const double* B, int nb, double sigma, const double* theta, const double* Q) {
+  if (nb < 1 || nb > 8) return fail(LSSVR_ERR_SIZE, "nb = %d outside [1, 8]", nb);
+  if (!A || !B || !theta || !Q) return fail(LSSVR_ERR_NULL, "A, B, theta, Q must be non-NULL");
+  if (!(sigma > -INFINITY && sigma < INFINITY)) return fail(LSSVR_ERR_SIZE, "sigma = %g must be finite", sigma);
+  return LSSVR_OK;
+}
+
+int lssvr_eig_ritz(const double* A, const double* B, int nb, double sigma, double* theta, double* Q, int32_t* info,
+                   void* stream) {
+  const int rc = check_ritz(A, B, nb, sigma, theta, Q);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::eig_ritz_device(A, B, nb, sigma, theta, Q, info, reinterpret_cast<hipStream_t>(stream)),
+                      "eig_ritz");
+}
+
+int lssvr_eig_ritz_host(const double* A_host, const double* B_host, int nb, double sigma, double* theta_host,
+                        double* Q_host, int32_t* info) {
+  const int rc = check_ritz(A_host, B_host, nb, sigma, theta_host, Q_host);
+  if (rc != LSSVR_OK) return rc;
+  const int bad = lssvr::eig_ritz_host(A_host, B_host, nb, sigma, theta_host, Q_host);
+  if (info) info[0] = bad;
+  return LSSVR_OK;
+}
+
+int lssvr_eig_rotate(const double* Z, const double* MZ, const double* KZ, const double* Q, const double* theta,
+                     int kind_left, int kind_right, int64_t ne, int nb, double* X, double* Y, double* res2, void* work,
+                     int64_t work_bytes, void* stream) {
+  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
+  if (ne == 0) return LSSVR_OK;
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (nb < 1 || nb > 8) return fail(LSSVR_ERR_SIZE, "nb = %d outside [1, 8]", nb);
+  if (!Z || !MZ || !KZ || !Q || !theta || !X || !Y || !res2)
+    return fail(LSSVR_ERR_NULL, "Z, MZ, KZ, Q, theta, X, Y, res2 must be non-NULL");
+  if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
+      (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
+    return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
+                kind_right);
+  const int rc = check_eig_work(work, work_bytes, ne, nb);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::eig_rotate(Z, MZ, KZ, Q, theta, ne, nb, kind_left == LSSVR_END_ROBIN,
+                                        kind_right == LSSVR_END_ROBIN, X, Y, res2, work,
+                                        reinterpret_cast<hipStream_t>(stream)),
+                      "eig_rotate");
+}
+
+static int bind_eig_count(lssvr::EigArgs& a, const double* kdiag, const double* koff, const double* mdiag,
+                          const double* moff, int kind_left, int kind_right, const double* kappa_host, int64_t ne,
+                          const double* shifts, int ns, double pivmin, const int32_t* counts) {
+  if (ns < 0) return fail(LSSVR_ERR_SIZE, "ns = %d < 0", ns);
+  const int rc = bind_eig(a, kdiag, koff, mdiag, moff, kind_left, kind_right, kappa_host, ne, 1);
+  if (rc != LSSVR_OK) return rc;
+  if (ns > 0 && (!shifts || !counts)) return fail(LSSVR_ERR_NULL, "shifts and counts must be non-NULL");
+  if (!(pivmin > 0.0 && pivmin < INFINITY)) return fail(LSSVR_ERR_SIZE, "pivmin = %g must be finite and > 0", pivmin);
+  return LSSVR_OK;
+}
+
+int lssvr_eig_count(const double* kdiag, const double* koff, const double* mdiag, const double* moff, int kind_left,
+                    int kind_right, const double* kappa_host, int64_t ne, const double* shifts, int ns, double pivmin,
+                    int32_t* counts, void* stream) {
+  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
+  if (ne == 0) return LSSVR_OK;
+  lssvr::EigArgs a{};
+  const int rc = bind_eig_count(a, kdiag, koff, mdiag, moff, kind_left, kind_right, kappa_host, ne, shifts, ns, pivmin,
+                                counts);
+  if (rc != LSSVR_OK) return rc;
+  if (ns == 0) return LSSVR_OK;
+  return check_launch(lssvr::eig_count_device(a, shifts, ns, pivmin, counts, reinterpret_cast<hipStream_t>(stream)),
+                      "eig_count");
+}
+
+int lssvr_eig_count_host(const double* kdiag_host, const double* koff_host, const double* mdiag_host,
+                         const double* moff_host, int kind_left, int kind_right, const double* kappa_host, int64_t ne,
+                         const double* shifts_host, int ns, double pivmin, int32_t* counts) {
+  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
+  if (ne == 0) return LSSVR_OK;
+  lssvr::EigArgs a{};
+  const int rc = bind_eig_count(a, kdiag_host, koff_host, mdiag_host, moff_host, kind_left, kind_right, kappa_host, ne,
+                                shifts_host, ns, pivmin, counts);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::eig_count_host(a, shifts_host, ns, pivmin, counts);
+  return LSSVR_OK;
+}
+
+int lssvr_eig_rayleigh(const double* x, const double* W, int64_t ne, int M, int nq, const double* a_values,
+                       const double* c_values, const double* rho_values, int table_layout, int kind_left,
+                       int kind_right, const double* kappa_host, double* out3, void* work, void* stream) {
+  if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
+  if (ne == 0) return LSSVR_OK;
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
+  if (nq < 1 || nq > lssvr::kAdaptMaxNq)
+    return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
+  if (!x || !W || !out3 || !work) return fail(LSSVR_ERR_NULL, "x, W, out3, work must be non-NULL");
+  if (!a_values || !c_values || !rho_values)
+    return fail(LSSVR_ERR_NULL, "a_values, c_values and rho_values must be non-NULL");
+  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
+    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::EigRayleighArgs a{};
+  a.x = x;
+  a.W = W;
+  a.ne = ne;
+  a.M = M;
+  a.nq = nq;
+  a.a_values = a_values;
+  a.c_values = c_values;
+  a.rho_values = rho_values;
+  a.kind[0] = kind_left;
+  a.kind[1] = kind_right;
+  for (int i = 0; i < 2; ++i) a.kappa[i] = a.kind[i] == LSSVR_END_ROBIN ? kappa_host[i] : 0.0;
+  a.work = work;
+  return check_launch(lssvr::eig_rayleigh(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,
+                                          reinterpret_cast<hipStream_t>(stream)),
+                      "eig_rayleigh");
+}
+
 }  // extern "C"

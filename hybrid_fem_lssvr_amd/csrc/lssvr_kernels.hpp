@@ -350,6 +350,50 @@ int64_t group_work_bytes(int64_t ne);
 hipError_t group_by_degree(const int32_t* deg, int64_t ne, int64_t* ids, int64_t* offsets, void* work,
                            hipStream_t s);
 
+// eigen.hip: block inverse iteration for -(a u')' + c u = lambda rho u.  K = (kdiag, koff) and
+// M = (mdiag, moff) are P1 bands, read only; f0 / f1 make node 0 / node ne an unknown whose K diagonal gets k0 / k1.
+// Vectors are [nb][ne+1], nb <= 8; rows outside the unknowns are written as 0 and not read.
+struct EigArgs {
+  const double* kdiag;
+  const double* koff;
+  const double* mdiag;
+  const double* moff;
+  int64_t ne;
+  int nb;
+  bool f0, f1;
+  double k0, k1;
+};
+int64_t eig_work_bytes(int64_t ne, int nb);
+// MZ = M Z, KZ = K Z, gram = {A = Z^T K Z, B = Z^T M Z} (two full nb x nb matrices)
+hipError_t eig_apply(const EigArgs& a, const double* Z, double* MZ, double* KZ, double* gram, void* work,
+                     hipStream_t s);
+// theta[nb] ascending in |theta - sigma|, Q[nb][nb] with Q^T A Q = diag theta, Q^T B Q = I; info: dependent columns
+hipError_t eig_ritz_device(const double* A, const double* B, int nb, double sigma, double* theta, double* Q,
+                           int32_t* info, hipStream_t s);
+int eig_ritz_host(const double* A, const double* B, int nb, double sigma, double* theta, double* Q);
+// X = Z Q, Y = (MZ) Q, each column signed; res2[2*nb] = {|(KZ) Q_j - theta_j (MZ) Q_j|^2, |X_j|^2}
+hipError_t eig_rotate(const double* Z, const double* MZ, const double* KZ, const double* Q, const double* theta,
+                      int64_t ne, int nb, bool f0, bool f1, double* X, double* Y, double* res2, void* work,
+                      hipStream_t s);
+// counts[t] = negative pivots of LDL^T (K - shifts[t] M), pivots below pivmin in size taken as -pivmin
+hipError_t eig_count_device(const EigArgs& a, const double* shifts, int ns, double pivmin, int32_t* counts,
+                            hipStream_t s);
+void eig_count_host(const EigArgs& a, const double* shifts, int ns, double pivmin, int32_t* counts);
+struct EigRayleighArgs {
+  const double* x;
+  const double* W;
+  int64_t ne;
+  int M, nq;
+  const double* a_values;           // a, c and rho at lssvr_estimate_points, one layout
+  const double* c_values;
+  const double* rho_values;
+  int kind[2];                      // per end of the domain: 0 Dirichlet, 1 Robin
+  double kappa[2];
+  void* work;                       // eig_work_bytes(ne, 1)
+};
+// out3 = {sum_e int (a u_e'^2 + c u_e^2) + sum_ends kappa u(x_end)^2, sum_e int rho u_e^2, sum |terms| of the first}
+hipError_t eig_rayleigh(const EigRayleighArgs& a, bool point_major, double* out3, hipStream_t s);
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

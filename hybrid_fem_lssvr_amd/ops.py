@@ -1662,6 +1662,187 @@ def group_by_degree(deg, *, work=None, stream=None):
     return ids, offsets
 
 
+# --------------------------------------------------------------------------
+# eigenproblems -(a u')' + c u = lambda rho u
+# --------------------------------------------------------------------------
+EIG_MAX_BLOCK = 8      # widest block of iteration vectors: one pass of the multi solvers
+
+
+def _eig_bands(kdiag, koff, mdiag, moff):
+    """ne of the four bands K = (kdiag[ne+1], koff[ne]), M = (mdiag[ne+1], moff[ne]), checked."""
+    for nm, t in (("kdiag", kdiag), ("koff", koff), ("mdiag", mdiag), ("moff", moff)):
+        _dev(t, nm)
+    ne = koff.numel()
+    if ne < 1:
+        raise ValueError("need at least one element")
+    if kdiag.numel() != ne + 1 or mdiag.numel() != ne + 1 or moff.numel() != ne:
+        raise ValueError("band lengths must be ne+1, ne, ne+1, ne (kdiag, koff, mdiag, moff)")
+    _same_device(kdiag, koff=koff, mdiag=mdiag, moff=moff)
+    return ne
+
+
+def _eig_block(ne, like, **vectors):
+    """nb of the block vectors [nb, ne+1] (all of one shape, on ``like``'s device), checked."""
+    nb = None
+    for nm, t in vectors.items():
+        _dev(t, nm)
+        if t.dim() != 2 or t.shape[1] != ne + 1 or not 1 <= t.shape[0] <= EIG_MAX_BLOCK:
+            raise ValueError(f"{nm} must be [nb, ne+1] = [1 .. {EIG_MAX_BLOCK}, {ne + 1}], got {list(t.shape)}")
+        if nb is not None and t.shape[0] != nb:
+            raise ValueError(f"{nm} must hold nb = {nb} vectors, got {t.shape[0]}")
+        nb = int(t.shape[0])
+    _same_device(like, **vectors)
+    return nb
+
+
+def _eig_out(t, name, shape, like, dtype=torch.float64):
+    """The output buffer ``t`` (allocated when None) of ``shape`` on ``like``'s device."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    _dev(t, name, dtype)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    _same_device(like, **{name: t})
+    return t
+
+
+def _eig_work(work, ne, nb, like):
+    need = _capi.load().lssvr_eig_work_bytes(ne, nb)
+    if work is not None:
+        _dev(work, "work")
+        if work.numel() * work.element_size() < need:
+            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                             f"lssvr_eig_work_bytes({ne}, {nb}) = {need}")
+        _same_device(like, work=work)
+    return _scratch(work, need, like.device)
+
+
+def eig_apply(kdiag, koff, mdiag, moff, Z, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0), *, MZ=None,
+              KZ=None, gram=None, work=None, stream=None):
+    """``lssvr_eig_apply``: MZ = M Z, KZ = K Z and gram float64[2, nb, nb] = (Z^T K Z, Z^T M Z) for the block
+    ``Z`` float64[nb, ne+1] and the P1 bands K = (kdiag, koff), M = (mdiag, moff).  ``end_kinds``, ``kappa`` as in
+    :func:`tridiag_pivot_solve_multi`: a Robin end's node is an unknown and kappa joins K's end diagonal; rows outside
+    the unknowns are written as 0 and not read.  The Gram sums run in a fixed order: bitwise reproducible.  Returns
+    (MZ, KZ, gram)."""
+    lib = _capi.load()
+    ne = _eig_bands(kdiag, koff, mdiag, moff)
+    nb = _eig_block(ne, kdiag, Z=Z)
+    kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
+    MZ = _eig_out(MZ, "MZ", (nb, ne + 1), kdiag)
+    KZ = _eig_out(KZ, "KZ", (nb, ne + 1), kdiag)
+    gram = _eig_out(gram, "gram", (2, nb, nb), kdiag)
+    work = _eig_work(work, ne, nb, kdiag)
+    rc = lib.lssvr_eig_apply(_ptr(kdiag), _ptr(koff), _ptr(mdiag), _ptr(moff), kinds[0], kinds[1], kap, ne, nb, _ptr(Z),
+                             _ptr(MZ), _ptr(KZ), _ptr(gram), _ptr(work), work.numel() * work.element_size(),
+                             _stream(stream))
+    _capi.check(rc, "lssvr_eig_apply")
+    return MZ, KZ, gram
+
+
+def eig_ritz(gram, sigma=0.0, *, theta=None, Q=None, info=None, stream=None):
+    """``lssvr_eig_ritz`` on ``gram`` float64[2, nb, nb] = (A, B) as :func:`eig_apply` leaves it: theta float64[nb]
+    ascending in |theta - sigma| and Q float64[nb, nb] (column j the vector of theta[j]) with Q^T A Q = diag theta,
+    Q^T B Q = I, on the device; info int32[1]: the number of dependent columns of B (zero vectors, ordered last).
+    Returns (theta, Q, info)."""
+    lib = _capi.load()
+    _dev(gram, "gram")
+    if gram.dim() != 3 or gram.shape[0] != 2 or gram.shape[1] != gram.shape[2] or \
+            not 1 <= gram.shape[1] <= EIG_MAX_BLOCK:
+        raise ValueError(f"gram must be [2, nb, nb] with nb in 1 .. {EIG_MAX_BLOCK}, got {list(gram.shape)}")
+    sigma = float(sigma)
+    if not math.isfinite(sigma):
+        raise ValueError(f"sigma must be finite, got {sigma!r}")
+    nb = int(gram.shape[1])
+    theta = _eig_out(theta, "theta", (nb,), gram)
+    Q = _eig_out(Q, "Q", (nb, nb), gram)
+    info = _eig_out(info, "info", (1,), gram, torch.int32)
+    rc = lib.lssvr_eig_ritz(_ptr(gram[0]), _ptr(gram[1]), nb, sigma, _ptr(theta), _ptr(Q), _ptr(info),
+                            _stream(stream))
+    _capi.check(rc, "lssvr_eig_ritz")
+    return theta, Q, info
+
+
+def eig_rotate(Z, MZ, KZ, Q, theta, end_kinds=(END_DIRICHLET, END_DIRICHLET), *, X=None, Y=None, res2=None,
+               work=None, stream=None):
+    """``lssvr_eig_rotate``: X = Z Q, Y = (MZ) Q and res2 float64[2, nb] = (|(KZ) Q_j - theta_j (MZ) Q_j|^2, |X_j|^2)
+    for the blocks float64[nb, ne+1] and the device arrays ``Q`` [nb, nb], ``theta`` [nb] of :func:`eig_ritz`.  Each
+    column is signed so that X's value at the first unknown is >= 0; X and Y must not be Z, MZ or KZ.  Returns
+    (X, Y, res2)."""
+    lib = _capi.load()
+    _dev(Z, "Z")
+    if Z.dim() != 2 or Z.shape[1] < 2:
+        raise ValueError(f"Z must be [nb, ne+1] with ne >= 1, got {list(Z.shape)}")
+    ne = int(Z.shape[1]) - 1
+    nb = _eig_block(ne, Z, Z=Z, MZ=MZ, KZ=KZ)
+    _dev(Q, "Q")
+    _dev(theta, "theta")
+    if tuple(Q.shape) != (nb, nb) or tuple(theta.shape) != (nb,):
+        raise ValueError(f"Q must be [{nb}, {nb}] and theta [{nb}], got {list(Q.shape)} and {list(theta.shape)}")
+    _same_device(Z, Q=Q, theta=theta)
+    kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
+    X = _eig_out(X, "X", (nb, ne + 1), Z)
+    Y = _eig_out(Y, "Y", (nb, ne + 1), Z)
+    for nm, t in (("X", X), ("Y", Y)):
+        if any(t.data_ptr() == s.data_ptr() for s in (Z, MZ, KZ)):
+            raise ValueError(f"{nm} must not be Z, MZ or KZ")
+    res2 = _eig_out(res2, "res2", (2, nb), Z)
+    work = _eig_work(work, ne, nb, Z)
+    rc = lib.lssvr_eig_rotate(_ptr(Z), _ptr(MZ), _ptr(KZ), _ptr(Q), _ptr(theta), kinds[0], kinds[1], ne, nb, _ptr(X),
+                              _ptr(Y), _ptr(res2), _ptr(work), work.numel() * work.element_size(), _stream(stream))
+    _capi.check(rc, "lssvr_eig_rotate")
+    return X, Y, res2
+
+
+def eig_count(kdiag, koff, mdiag, moff, shifts, pivmin, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0),
+              *, out=None, stream=None):
+    """``lssvr_eig_count``: for every entry of ``shifts`` float64[ns] (device) the number of negative pivots of
+    LDL^T (K - s M) over the unknowns -- the number of eigenvalues of the pencil below s -- as int32[ns] on the device.
+    ``pivmin`` > 0: a pivot smaller in size becomes -pivmin (dstebz).  One lane per shift, serial over the rows."""
+    lib = _capi.load()
+    ne = _eig_bands(kdiag, koff, mdiag, moff)
+    _dev(shifts, "shifts")
+    if shifts.dim() != 1:
+        raise ValueError("shifts must be 1-D")
+    _same_device(kdiag, shifts=shifts)
+    ns = int(shifts.numel())
+    pivmin = float(pivmin)
+    if not (pivmin > 0.0 and math.isfinite(pivmin)):
+        raise ValueError(f"pivmin must be finite and > 0, got {pivmin!r}")
+    kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
+    out = _eig_out(out, "out", (ns,), kdiag, torch.int32)
+    rc = lib.lssvr_eig_count(_ptr(kdiag), _ptr(koff), _ptr(mdiag), _ptr(moff), kinds[0], kinds[1], kap, ne,
+                             _ptr(shifts), ns, pivmin, _ptr(out), _stream(stream))
+    _capi.check(rc, "lssvr_eig_count")
+    return out
+
+
+def eig_rayleigh(x, W, nq, a_values, c_values, rho_values, *, point_major=False,
+                 end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0), out=None, work=None, stream=None):
+    """``lssvr_eig_rayleigh``: for the enhanced mode ``W`` [ne, M] on the nodes ``x`` and the tables of a, c and rho at
+    :func:`estimate_points` (float64[ne, nq] or, with ``point_major``, [nq, ne]) the device array out3 =
+    {sum_e int (a u_e'^2 + c u_e^2) + kappa u(x_end)^2 at the Robin ends, sum_e int rho u_e^2, sum |terms| of the
+    first}: out3[0] / out3[1] is the Rayleigh quotient.  Fixed-order sums: bitwise reproducible."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(W, "W")
+    ne = x.numel() - 1
+    nq = int(nq)
+    if x.dim() != 1 or ne < 1:
+        raise ValueError("x must be 1-D with at least two nodes")
+    if W.dim() != 2 or W.shape[0] != ne:
+        raise ValueError("W must be [ne, M]")
+    _tables(ne, nq, point_major, shape=True, a_values=a_values, c_values=c_values, rho_values=rho_values)
+    kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
+    out = _eig_out(out, "out", (3,), x)
+    work = _eig_work(work, ne, 1, x)
+    _same_device(x, W=W, a_values=a_values, c_values=c_values, rho_values=rho_values)
+    rc = lib.lssvr_eig_rayleigh(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, _ptr(a_values), _ptr(c_values),
+                                _ptr(rho_values), _layout(point_major), kinds[0], kinds[1], kap, _ptr(out), _ptr(work),
+                                _stream(stream))
+    _capi.check(rc, "lssvr_eig_rayleigh")
+    return out
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

@@ -274,6 +274,29 @@ class GoalEstimate:
         self.corrected = self.value + self.correction
 
 
+class EigenSolution:
+    """What :meth:`FEMLSSVRPrimalSolver.solve_eigen` returns for the k eigenvalues of -(a u')' + c u = lambda rho u
+    nearest the shift, in the order of their distance from it:
+
+    * ``values_fem`` float64[k]: the P1 eigenvalues; ``values`` float64[k]: the Rayleigh quotients of the enhanced
+      modes (``None`` with ``enhance=False``);
+    * ``residuals`` float64[k]: |K x_j - theta_j M x_j|_2; ``index`` int[k]: the position of each mode in the ascending
+      discrete spectrum, counted from 0 (the number of eigenvalues below it), by the Sturm count (``None`` when the iteration did not converge);
+    * ``iterations``, ``converged``; ``nodal`` float64[k, ne+1]: the modes' nodal values, M-orthonormal, each with a
+      positive value at the first unknown; ``modes``: k :class:`EnhancedSolution` (empty with ``enhance=False``)."""
+
+    def __init__(self, values_fem, values, residuals, index, iterations, converged, nodal, modes, sigma):
+        self.values_fem, self.values, self.residuals, self.index = values_fem, values, residuals, index
+        self.iterations, self.converged, self.nodal, self.modes, self.sigma = iterations, converged, nodal, modes, sigma
+
+    def evaluate(self, j, x, deriv=0):
+        """The enhanced mode ``j`` (its ``deriv``-th derivative) at the points ``x``."""
+        if not self.modes:
+            raise RuntimeError("solve_eigen ran with enhance=False: there are no enhanced modes to evaluate")
+        x = np.asarray(x, dtype=np.float64)
+        return self.modes[j].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
+
+
 class _ElementFunctions:
     """``solver.lssvr_functions``: a read-only sequence whose item i is
     ``Legendre(W[i], [x_i, x_{i+1}])`` (Dual.py:95, 163) -- built lazily from the device
@@ -807,14 +830,14 @@ class FEMLSSVRPrimalSolver:
                                **shard)
         return W, st
 
-    def _enhance_by_degree_tables(self, x, u, degrees, gamma, gd, bc, **shard):
+    def _enhance_by_degree_tables(self, x, u, degrees, gamma, gd, bc, eq=None, **shard):
         """:meth:`_enhance_by_degree` for rows that ``lssvr_enhance_subset`` does not hold, without element lists
         (``boundary="periodic"`` with ``element_lists=False``): every degree that occurs is one ``ops.enhance_varcoef``
         over the whole mesh at that degree's collocation count, and the rows of its own elements are copied into a
         zeroed W[ne, max M].  The cost is one whole-mesh launch per distinct degree; :meth:`_enhance_by_degree_lists`
-        removes that factor."""
+        removes that factor.  ``eq``: the equation whose rows are fitted (default: the solver's own)."""
         torch = _torch()
-        eq = self._eq
+        eq = self._eq if eq is None else eq
         W = torch.zeros((degrees.size, int(degrees.max())), dtype=torch.float64, device=x.device)
         st = torch.zeros((degrees.size,), dtype=torch.int32, device=x.device)
         for Mg in np.unique(degrees):
@@ -828,13 +851,14 @@ class FEMLSSVRPrimalSolver:
             st[ids] = sg[ids]
         return W, st
 
-    def _enhance_by_degree_lists(self, x, u, degrees, gamma, gd, bc, **shard):
+    def _enhance_by_degree_lists(self, x, u, degrees, gamma, gd, bc, eq=None, **shard):
         """:meth:`_enhance_by_degree` for rows that ``lssvr_enhance_subset`` does not hold (coefficients, reaction,
         convection; every ``boundary``; ``element_lists=True``): the same grouping, and per non-empty degree the
         collocation points of its own elements (``ops.colloc_points_subset``), the tables on those points, and one
-        ``ops.enhance_varcoef_subset`` into a zeroed W[ne, max M].  Every element is tabulated and solved once."""
+        ``ops.enhance_varcoef_subset`` into a zeroed W[ne, max M].  Every element is tabulated and solved once.
+        ``eq``: the equation whose rows are fitted (default: the solver's own)."""
         torch = _torch()
-        eq = self._eq
+        eq = self._eq if eq is None else eq
         ne = degrees.size
         ids, offsets = ops.group_by_degree(torch.as_tensor(degrees.astype(np.int32), device=x.device))
         off = offsets.cpu().numpy()
@@ -946,6 +970,189 @@ class FEMLSSVRPrimalSolver:
                                   bc=_to_dev(bc, x.device), point_major=pm, global_domain=gd,
                                   **self._shard(x.numel() - 1))
         return [EnhancedSolution(x, W[j], st[j]) for j in range(len(rhs_list))], x, U
+
+    # ---- eigenproblems (no reference counterpart) ------------------------
+    def _check_eigen(self, k, sigma, weight, tol, max_iter, check_every):
+        """What :meth:`solve_eigen` does not cover, on the host and before any device call -> (mesh, nodes, kinds,
+        kappa, number of unknowns)."""
+        if self.convection is not None:
+            raise ValueError("solve_eigen has no convection term: the pencil of -(a u')' + b u' + c u = lambda rho u "
+                             "is not symmetric, and the Rayleigh-Ritz step and the Sturm count need a symmetric one")
+        if self._periodic:
+            raise ValueError("solve_eigen has no boundary='periodic': a shift inside the spectrum needs the pivoting "
+                             "solve, which has no cyclic form")
+        if self.fem_solver == "flux":
+            raise ValueError("solve_eigen needs fem_solver='bands' or 'pivot': the flux solve factors A = D^T K D, "
+                             "which the mass matrix of the shift breaks")
+        if self.solver_id != ops.SOLVER_PRIMAL:
+            raise ValueError("solve_eigen needs solver=ops.SOLVER_PRIMAL: the modes are enhanced through the "
+                             "reaction rows, which have a primal solve only")
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 6:
+            raise ValueError(f"k must be an integer in 1 .. 6 (the block of k + 2 vectors is one pass of the "
+                             f"multi-RHS solvers), got {k!r}")
+        if not math.isfinite(float(sigma)):
+            raise ValueError(f"sigma must be finite, got {sigma!r}")
+        if weight is not None and not callable(weight):
+            raise ValueError("weight must be a callable rho(x) or None")
+        if not (float(tol) > 0.0) or int(max_iter) < 1 or int(check_every) < 1:
+            raise ValueError("tol must be > 0, max_iter and check_every >= 1")
+        if any(float(v) != 0.0 for v in self._gd_bc()[1]):
+            raise ValueError(f"solve_eigen needs homogeneous end data (u = 0 or a du/dn + kappa u = 0), got the end "
+                             f"values {self._gd_bc()[1]!r}")
+        bnd = self._bnd
+        kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (tuple(bnd.kinds), tuple(bnd.kappa))
+        m = self._default_mesh() if self.mesh is None else self.mesh
+        nodes = np.asarray(m.nodes, dtype=np.float64)
+        unknowns = nodes.size - 2 + sum(1 for kd in kinds if kd == ops.END_ROBIN)
+        if int(k) > unknowns:
+            raise ValueError(f"k = {k} > {unknowns}, the number of unknowns of the P1 system")
+        xi = np.polynomial.legendre.leggauss(int(self.nquad))[0]
+        xq = 0.5 * (nodes[:-1] + nodes[1:])[:, None] + 0.5 * np.diff(nodes)[:, None] * xi[None, :]
+        rq = np.broadcast_to(np.asarray((_one if weight is None else weight)(xq), dtype=np.float64), xq.shape)
+        if not np.all(rq > 0.0):
+            raise ValueError("weight must be positive at every quadrature point (rho > 0): M would not be positive "
+                             "definite")
+        if self.element_degrees is not None:
+            deg = np.asarray(self.element_degrees)
+            if deg.shape != (nodes.size - 1,) or not np.issubdtype(deg.dtype, np.integer) or \
+                    deg.min() < ops.MIN_DEGREE or deg.max() > ops.MAX_DEGREE:
+                raise ValueError(f"element_degrees must hold one integer in [2, 33] per element ({nodes.size - 1})")
+        return m, nodes, kinds, kappa, unknowns
+
+    def solve_eigen(self, k=1, sigma=0.0, weight=None, tol=1e-12, max_iter=200, check_every=4, enhance=True, nq=None):
+        """The ``k`` <= 6 eigenvalues nearest ``sigma`` of -(a u')' + c u = lambda rho u with the solver's ``mesh``,
+        ``coef``, ``reaction`` and ``boundary`` (Dirichlet, Neumann or Robin ends with zero data), ``weight`` = rho (a
+        callable, ``None``: 1); ``rhs`` is not read.  Block inverse iteration with the fixed shift and a Rayleigh-Ritz
+        step on the device: per iteration one multi-RHS solve of (K - sigma M) Z = Y -- the
+        unpivoted solve when c - sigma rho >= 0 at every quadrature point, else the pivoting one --, ``ops.eig_apply``,
+        ``ops.eig_ritz`` and ``ops.eig_rotate``; theta, the residuals and the info words are read back every
+        ``check_every`` iterations.  It stops when |K x_j - theta_j M x_j|_2 <= tol |K|_max |x_j|_2 for the first k
+        columns, or at ``max_iter``.  A Sturm count then certifies that the k values are consecutive and gives their
+        positions in the spectrum (``RuntimeError`` with the counts otherwise).  With ``enhance`` every mode is fitted
+        per element by the reaction rows with the table c - theta_j rho (``lssvr_M``, ``n_colloc``, ``lssvr_gamma``,
+        ``element_degrees``), and its Rayleigh quotient, by ``nq``-point Gauss, is the enhanced eigenvalue.  Returns
+        an :class:`EigenSolution`."""
+        torch = _torch()
+        m, nodes, kinds, kappa, unknowns = self._check_eigen(k, sigma, weight, tol, max_iter, check_every)
+        k, sigma, ne = int(k), float(sigma), nodes.size - 1
+        rho = _one if weight is None else weight
+        eq = self._eq
+        dev = _device(self.device)
+        x = _to_dev(nodes, dev)
+        xq = ops.quad_points(x, self.nquad)
+        zq = torch.zeros_like(xq)
+        aq = None if eq.a is None else _tabulate(eq.a, xq)
+        cq = zq if eq.c is None else _tabulate(eq.c, xq)
+        rq = _tabulate(rho, xq)
+        sq = cq - sigma * rq
+        K = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=cq)
+        Mb = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=rq)
+        S = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=sq)
+        # one read for the sizes the host needs: the sign of c - sigma rho, |K|_max, |M off|_max and M's Gershgorin floor
+        md, mo = Mb["diag"], Mb["off"]
+        lo, hi = (0 if kinds[0] == ops.END_ROBIN else 1), (ne + 1 if kinds[1] == ops.END_ROBIN else ne)
+        row = md[lo:hi].clone()
+        row[1:] -= mo[lo:hi - 1].abs()
+        row[:-1] -= mo[lo:hi - 1].abs()
+        smin, smax, kmax, komax, momax, mmin = (float(v) for v in torch.stack(
+            [sq.min(), sq.max(), torch.maximum(K["diag"].abs().max() + max(kappa), K["off"].abs().max()),
+             K["off"].abs().max(), mo.abs().max(), row.min()]).cpu())
+        pure_neumann = kinds == (ops.END_ROBIN,) * 2 and kappa[0] + kappa[1] == 0.0
+        pivot = self.fem_solver == "pivot" or smin < 0.0 or (pure_neumann and smax == 0.0)
+        nb = min(ops.EIG_MAX_BLOCK, k + 2, unknowns)
+        y0 = np.zeros((nb, ne + 1))
+        y0[:, lo:hi] = np.random.default_rng(0).standard_normal((nb, hi - lo))
+        Y = _to_dev(y0, dev)
+        Z, X, MZ, KZ = (torch.empty_like(Y) for _ in range(4))
+        gram = torch.empty((2, nb, nb), dtype=torch.float64, device=dev)
+        theta = torch.empty(nb, dtype=torch.float64, device=dev)
+        Q = torch.empty((nb, nb), dtype=torch.float64, device=dev)
+        res2 = torch.empty((2, nb), dtype=torch.float64, device=dev)
+        rinfo = torch.zeros(1, dtype=torch.int32, device=dev)
+        pinfo = rinfo
+        lib = ops._capi.load()
+        swork = ops._scratch(None, max(lib.lssvr_tridiag_pivot_work_bytes(ne, nb),
+                                       lib.lssvr_tridiag_bc_work_bytes(ne, nb)), dev)
+        ework = ops._scratch(None, lib.lssvr_eig_work_bytes(ne, nb), dev)
+        it, converged, th, res, xn = 0, False, None, None, None
+        while it < int(max_iter) and not converged:
+            it += 1
+            if pivot:
+                _, pinfo = ops.tridiag_pivot_solve_multi(S["diag"], S["off"], S["off"], Y, kinds, kappa, out=Z,
+                                                         work=swork, return_info=True)
+            else:
+                ops.tridiag_bc_solve_multi(S["diag"], S["off"], Y, kinds, kappa, out=Z, work=swork)
+            ops.eig_apply(K["diag"], K["off"], md, mo, Z, kinds, kappa, MZ=MZ, KZ=KZ, gram=gram, work=ework)
+            ops.eig_ritz(gram, sigma, theta=theta, Q=Q, info=rinfo)
+            ops.eig_rotate(Z, MZ, KZ, Q, theta, kinds, X=X, Y=Y, res2=res2, work=ework)
+            if it % int(check_every) and it != int(max_iter):
+                continue
+            host = torch.cat([theta, res2.reshape(-1), pinfo.double(), rinfo.double()]).cpu().numpy()     # one small copy
+            th, res, xn = host[:nb], np.sqrt(host[nb:2 * nb]), np.sqrt(host[2 * nb:3 * nb])
+            if pivot and host[3 * nb]:
+                raise RuntimeError(f"K - sigma M is singular to working precision at sigma = {sigma!r}: the pivoting "
+                                   f"solve met {int(host[3 * nb])} pivot(s) that were zero or not finite; sigma is an "
+                                   "eigenvalue of the discrete problem, move it")
+            if host[3 * nb + 1]:
+                raise RuntimeError(f"the block of iteration vectors lost {int(host[3 * nb + 1])} column(s): their "
+                                   "images under the shifted inverse are linearly dependent to working precision "
+                                   "(sigma is too close to an eigenvalue for a block of this width)")
+            if not np.all(np.isfinite(host)):
+                raise RuntimeError("block inverse iteration produced non-finite values")
+            converged = bool(np.all(res[:k] <= float(tol) * kmax * xn[:k]))
+        index = None
+        if converged:
+            # the k values are consecutive eigenvalues: the Sturm counts just outside them differ by k
+            eps = 2.0 ** -53
+            floor = 64.0 * eps * kmax / mmin
+            order = np.argsort(th[:k], kind="stable")
+            t_lo, t_hi = th[order[0]], th[order[-1]]
+            below = [t for t in th[k:] if t < t_lo]
+            above = [t for t in th[k:] if t > t_hi]
+            d_lo = max(0.5 * (t_lo - max(below)) if below else 0.0, res[order[0]] / math.sqrt(mmin), floor)
+            d_hi = max(0.5 * (min(above) - t_hi) if above else 0.0, res[order[-1]] / math.sqrt(mmin), floor)
+            shifts = _to_dev([t_lo - d_lo, t_hi + d_hi], dev)
+            pivmin = np.finfo(np.float64).tiny * max(1.0, (komax + max(abs(t_lo - d_lo), abs(t_hi + d_hi)) * momax) ** 2)
+            cnt = ops.eig_count(K["diag"], K["off"], md, mo, shifts, pivmin, kinds, kappa).cpu().numpy()
+            if int(cnt[1]) - int(cnt[0]) != k:
+                raise RuntimeError(f"solve_eigen found {k} value(s) in [{t_lo!r}, {t_hi!r}], but the Sturm counts "
+                                   f"{int(cnt[0])} below {t_lo - d_lo!r} and {int(cnt[1])} below {t_hi + d_hi!r} "
+                                   f"say the discrete problem has {int(cnt[1]) - int(cnt[0])} there")
+            index = np.empty(k, dtype=np.int64)
+            index[order] = int(cnt[0]) + np.arange(k)
+        nodal = X[:k].cpu().numpy()
+        values, modes = None, []
+        if enhance:
+            M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
+            gd = (float(self.global_domain[0]), float(self.global_domain[1]))
+            shard = self._shard(ne)
+            degrees = None if self.element_degrees is None else np.asarray(self.element_degrees).astype(np.int64)
+            nqe = max(M if degrees is None else int(degrees.max()), 8) if nq is None else int(nq)
+            if not 1 <= nqe <= 32:
+                raise ValueError(f"nq must be in [1, 32], got {nqe}")
+            pts = ops.estimate_points(x, nqe)
+            ta, tc, tr = (_tabulate(fn, pts, True) for fn in (_one if eq.a is None else eq.a,
+                                                            _zero if eq.c is None else eq.c, rho))
+            values = np.empty(k)
+            for j in range(k):
+                tj = float(th[j])
+                c0 = _zero if eq.c is None else eq.c
+                eqj = _Equation(_zero, self.coef, lambda t, tj=tj, c0=c0: np.asarray(c0(t), dtype=np.float64)
+                                - tj * np.asarray(rho(t), dtype=np.float64), None)
+                u = X[j].contiguous()
+                if degrees is not None:
+                    by_degree = self._enhance_by_degree_lists if self.element_lists else self._enhance_by_degree_tables
+                    W, st = by_degree(x, u, degrees, gamma, gd, (0.0, 0.0), eq=eqj, **shard)
+                else:
+                    pm = _point_major(M)
+                    ea, eda, ef, ec = eqj.tables(ops.colloc_points(x, n), pm)
+                    W, st = ops.enhance_varcoef(x, u, M, gamma, n, ea, eda, ef, global_domain=gd, bc=(0.0, 0.0),
+                                                point_major=pm, c_values=ec, **shard)
+                modes.append(EnhancedSolution(x, W, st))
+                out3 = ops.eig_rayleigh(x, W, nqe, ta, tc, tr, point_major=True, end_kinds=kinds, kappa=kappa,
+                                        work=ework).cpu().numpy()
+                values[j] = out3[0] / out3[1]
+        return EigenSolution(th[:k].copy(), values, res[:k].copy(), index, it, converged, nodal, modes, sigma)
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):

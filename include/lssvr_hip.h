@@ -946,6 +946,73 @@ int lssvr_enhance_react_subset(const double* x, const double* u, int64_t ne_mesh
 int lssvr_colloc_points_subset(const double* x, int64_t ne_mesh, const int64_t* elem_ids, int64_t nsub,
                                int n_colloc, int table_layout, double* xc, void* stream);
 
+/*
+ * Eigenproblems: -(a u')' + c u = lambda rho u, a > 0, rho > 0, with u = 0 or a du/dn + kappa u = 0 at each end (no
+ * reference counterpart).  ADDITIVE to ABI 7: nine new symbols, no existing entry, struct, constant
+ * or kernel changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * The kernels of block inverse iteration with a fixed shift sigma and a Rayleigh-Ritz step.  K = (kdiag[ne+1], koff[ne])
+ * are the bands of lssvr_p1_assemble_react with c_quad = c, M = (mdiag, moff) those of the same entry with an a_quad of
+ * zeros and c_quad = rho (the consistent mass matrix weighted by rho); one more call with c_quad = c - sigma rho gives
+ * the bands of the shifted solve Z = (K - sigma M)^-1 Y, which is lssvr_tridiag_bc_solve_multi (c - sigma rho >= 0) or
+ * lssvr_tridiag_pivot_solve_multi (any sigma) with nc = nb.  The bands are read only.  kind_left, kind_right and
+ * kappa_host[2] as in lssvr_tridiag_pivot_solve_multi: a Robin end keeps its node as an unknown and adds kappa (finite,
+ * either sign) to K's end diagonal by value; a Dirichlet end's node is no unknown.  Block vectors are DEVICE arrays
+ * [nb][ne+1], 1 <= nb <= 8, the layout of the multi solvers; rows outside the unknowns are written as exactly 0 and are
+ * not read.  ne == 0 succeeds and launches nothing.  Every reduction runs in a fixed order -- lanes of a wave, waves of
+ * a workgroup, workgroups in index order by one finishing workgroup --, no atomics: bitwise reproducible.
+ *
+ * lssvr_eig_apply -- MZ = M Z, KZ = K Z and gram[2*nb*nb] = {A = Z^T K Z, B = Z^T M Z}, two full symmetric row-major
+ * matrices.  The vector outputs of case j do not depend on nb, bit for bit.  work: device scratch of
+ * work_bytes >= lssvr_eig_work_bytes(ne, nb).
+ *
+ * lssvr_eig_ritz -- the nb x nb pencil (A, B), device arrays (gram and gram + nb*nb): theta[nb] ascending in
+ * |theta - sigma| (ties by index) and Q[nb*nb] row-major, column j the vector of theta[j], with Q^T A Q = diag theta and
+ * Q^T B Q = I.  Cholesky of B, C = L^-1 A L^-T, cyclic Jacobi (at most 20 sweeps), Q = L^-T V; one thread.  info (device
+ * int32, may be NULL): the number of dependent columns of B -- a Cholesky pivot at or below 2^-46 of B's diagonal entry.
+ * Such a column is replaced by zeros (nothing is divided by the pivot), its theta is 0 and it is ordered last.
+ * lssvr_eig_ritz_host -- the same routine on HOST arrays (info too), bit for bit: no device is touched.
+ *
+ * lssvr_eig_rotate -- X = Z Q, Y = (MZ) Q and res2[2*nb] = {|(KZ) Q_j - theta_j (MZ) Q_j|_2^2, j < nb; |X_j|_2^2, j < nb}.
+ * Column j of X and Y is signed so that X's value at the first unknown is >= 0.  Q and theta are device arrays, as
+ * lssvr_eig_ritz leaves them.  X and Y must not overlap Z, MZ or KZ.  work as in lssvr_eig_apply.
+ *
+ * lssvr_eig_count -- counts[t] (device int32[ns]) = the number of negative pivots of LDL^T (K - shifts[t] M) over the
+ * unknowns, d_i = alpha_i - beta_{i-1}^2 / d_{i-1}, a pivot with |d| < pivmin taken as -pivmin (LAPACK dstebz): the
+ * number of eigenvalues of the pencil below shifts[t] (Sylvester).  shifts: device double[ns]; pivmin > 0, typically
+ * DBL_MIN * max(1, max beta^2).  One lane per shift, serial over the rows: not for the inner loop.
+ * lssvr_eig_count_host -- the same on HOST arrays (counts too), bit for bit.
+ *
+ * lssvr_eig_rayleigh -- for an enhanced mode W[ne][M] (1 <= M <= 33; zero-padded rows of mixed degree are fine) and
+ * a_values, c_values, rho_values at lssvr_estimate_points (1 <= nq <= 32; table_layout as in lssvr_estimate_react):
+ *   out3[0] = sum_e int_e (a u_e'^2 + c u_e^2) dx + sum over the Robin ends of kappa u_e(x_end)^2,
+ *   out3[1] = sum_e int_e rho u_e^2 dx,     out3[2] = the sum of the absolute values of the terms of out3[0],
+ * so that out3[0] / out3[1] is the Rayleigh quotient and out3[2] the scale of its rounding.  work: device scratch of
+ * lssvr_eig_work_bytes(ne, 1) bytes (not checkable here: no size argument).
+ */
+int64_t lssvr_eig_work_bytes(int64_t ne, int nb);
+int lssvr_eig_apply(const double* kdiag, const double* koff, const double* mdiag, const double* moff,
+                    int kind_left, int kind_right, const double* kappa_host, int64_t ne, int nb,
+                    const double* Z, double* MZ, double* KZ, double* gram,
+                    void* work, int64_t work_bytes, void* stream);
+int lssvr_eig_ritz(const double* A, const double* B, int nb, double sigma, double* theta, double* Q, int32_t* info,
+                   void* stream);
+int lssvr_eig_ritz_host(const double* A_host, const double* B_host, int nb, double sigma, double* theta_host,
+                        double* Q_host, int32_t* info);
+int lssvr_eig_rotate(const double* Z, const double* MZ, const double* KZ, const double* Q, const double* theta,
+                     int kind_left, int kind_right, int64_t ne, int nb, double* X, double* Y, double* res2,
+                     void* work, int64_t work_bytes, void* stream);
+int lssvr_eig_count(const double* kdiag, const double* koff, const double* mdiag, const double* moff,
+                    int kind_left, int kind_right, const double* kappa_host, int64_t ne,
+                    const double* shifts, int ns, double pivmin, int32_t* counts, void* stream);
+int lssvr_eig_count_host(const double* kdiag_host, const double* koff_host, const double* mdiag_host,
+                         const double* moff_host, int kind_left, int kind_right, const double* kappa_host, int64_t ne,
+                         const double* shifts_host, int ns, double pivmin, int32_t* counts);
+int lssvr_eig_rayleigh(const double* x, const double* W, int64_t ne, int M, int nq,
+                       const double* a_values, const double* c_values, const double* rho_values, int table_layout,
+                       int kind_left, int kind_right, const double* kappa_host,
+                       double* out3, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
