@@ -12,6 +12,7 @@ from .solver import (  # noqa: F401
     EnhancedSolution,
     FEMLSSVRPrimalSolver,
     GoalEstimate,
+    TransientSolution,
     SinRHS,
     enhance_elements,
     enhance_elements_hetero,

@@ -167,6 +167,12 @@ SIGNATURES = {
     "lssvr_eig_count_host": _sig([_c_hd] * 4, [_c_int, _c_int, _c_hd], [_c_i64, _c_hd, _c_int, _c_dbl, _c_dp]),
     "lssvr_eig_rayleigh": _sig(_SOLN, [_c_int], [_c_dp] * 3, [_c_int], [_c_int, _c_int, _c_hd], [_c_dp, _c_dp],
                                _STREAM),
+    # transient problems (additive to ABI 7): mdiag, moff, U0, U1, loads, phi, ne, nc, R, beta0, beta1, inv_dt, out;
+    # U2, U0, U1, ftab, rho_tab, phi, ne, n_colloc, R, layout, alpha, beta0, beta1, inv_dt, out
+    "lssvr_ts_rhs": _sig([_c_dp] * 6, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_dp], _STREAM),
+    "lssvr_ts_rhs_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_hd]),
+    "lssvr_ts_source_table": _sig([_c_dp] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dbl] * 4, [_c_dp], _STREAM),
+    "lssvr_ts_source_table_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dbl] * 4, [_c_hd]),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

@@ -1530,4 +1530,88 @@ int lssvr_eig_rayleigh(const double* x, const double* W, int64_t ne, int M, int 
                       "eig_rayleigh");
 }
 
+// Transient problems (timestep.hip).  The device and the host entry of each pair share one validated binding.
+static int ts_finite(double v) { return v > -INFINITY && v < INFINITY; }
+
+static int bind_ts_rhs(lssvr::TsRhsArgs& a, const double* mdiag, const double* moff, const double* U0,
+                       const double* U1, const double* loads, const double* phi, int64_t ne, int nc, int R,
+                       double beta0, double beta1, double inv_dt, const double* out) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (nc < 1 || nc > 8) return fail(LSSVR_ERR_SIZE, "nc = %d outside [1, 8]", nc);
+  if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
+  if (!ts_finite(beta0) || !ts_finite(beta1) || !ts_finite(inv_dt))
+    return fail(LSSVR_ERR_SIZE, "beta0 = %g, beta1 = %g, inv_dt = %g must be finite", beta0, beta1, inv_dt);
+  if (!mdiag || !moff || !U0 || !loads || !phi || !out)
+    return fail(LSSVR_ERR_NULL, "mdiag, moff, U0, loads, phi, out must be non-NULL");
+  if (beta1 != 0.0 && !U1) return fail(LSSVR_ERR_NULL, "U1 must be non-NULL when beta1 != 0");
+  if (out == U0 || (beta1 != 0.0 && out == U1)) return fail(LSSVR_ERR_SIZE, "out must not be U0 or U1");
+  a = lssvr::TsRhsArgs{mdiag, moff, U0, U1, loads, phi, ne, nc, R, beta0, beta1, inv_dt};
+  return LSSVR_OK;
+}
+
+int lssvr_ts_rhs(const double* mdiag, const double* moff, const double* U0, const double* U1, const double* loads,
+                 const double* phi, int64_t ne, int nc, int R, double beta0, double beta1, double inv_dt, double* out,
+                 void* stream) {
+  lssvr::TsRhsArgs a{};
+  const int rc = bind_ts_rhs(a, mdiag, moff, U0, U1, loads, phi, ne, nc, R, beta0, beta1, inv_dt, out);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::ts_rhs(a, out, reinterpret_cast<hipStream_t>(stream)), "ts_rhs");
+}
+
+int lssvr_ts_rhs_host(const double* mdiag_host, const double* moff_host, const double* U0_host, const double* U1_host,
+                      const double* loads_host, const double* phi_host, int64_t ne, int nc, int R, double beta0,
+                      double beta1, double inv_dt, double* out_host) {
+  lssvr::TsRhsArgs a{};
+  const int rc = bind_ts_rhs(a, mdiag_host, moff_host, U0_host, U1_host, loads_host, phi_host, ne, nc, R, beta0, beta1,
+                             inv_dt, out_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::ts_rhs_host(a, out_host);
+  return LSSVR_OK;
+}
+
+static int bind_ts_source(lssvr::TsSourceArgs& a, const double* U2, const double* U0, const double* U1,
+                          const double* ftab, const double* rho_tab, const double* phi, int64_t ne, int n_colloc,
+                          int R, int table_layout, double alpha, double beta0, double beta1, double inv_dt,
+                          const double* out) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (n_colloc < 2 || n_colloc > 4096) return fail(LSSVR_ERR_SIZE, "n_colloc = %d outside [2, 4096]", n_colloc);
+  if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
+  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
+    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  if (!ts_finite(alpha) || !ts_finite(beta0) || !ts_finite(beta1) || !ts_finite(inv_dt))
+    return fail(LSSVR_ERR_SIZE, "alpha = %g, beta0 = %g, beta1 = %g, inv_dt = %g must be finite", alpha, beta0, beta1,
+                inv_dt);
+  if (!U2 || !U0 || !ftab || !rho_tab || !phi || !out)
+    return fail(LSSVR_ERR_NULL, "U2, U0, ftab, rho_tab, phi, out must be non-NULL");
+  if (beta1 != 0.0 && !U1) return fail(LSSVR_ERR_NULL, "U1 must be non-NULL when beta1 != 0");
+  a = lssvr::TsSourceArgs{U2, U0, U1, ftab, rho_tab, phi, ne, n_colloc, R, alpha, beta0, beta1, inv_dt};
+  return LSSVR_OK;
+}
+
+int lssvr_ts_source_table(const double* U2, const double* U0, const double* U1, const double* ftab,
+                          const double* rho_tab, const double* phi, int64_t ne, int n_colloc, int R, int table_layout,
+                          double alpha, double beta0, double beta1, double inv_dt, double* out, void* stream) {
+  lssvr::TsSourceArgs a{};
+  const int rc = bind_ts_source(a, U2, U0, U1, ftab, rho_tab, phi, ne, n_colloc, R, table_layout, alpha, beta0, beta1,
+                                inv_dt, out);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::ts_source_table(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out,
+                                             reinterpret_cast<hipStream_t>(stream)),
+                      "ts_source_table");
+}
+
+int lssvr_ts_source_table_host(const double* U2_host, const double* U0_host, const double* U1_host,
+                               const double* ftab_host, const double* rho_tab_host, const double* phi_host, int64_t ne,
+                               int n_colloc, int R, int table_layout, double alpha, double beta0, double beta1,
+                               double inv_dt, double* out_host) {
+  lssvr::TsSourceArgs a{};
+  const int rc = bind_ts_source(a, U2_host, U0_host, U1_host, ftab_host, rho_tab_host, phi_host, ne, n_colloc, R,
+                                table_layout, alpha, beta0, beta1, inv_dt, out_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::ts_source_table_host(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out_host);
+  return LSSVR_OK;
+}
+
 }  // extern "C"

@@ -394,6 +394,37 @@ struct EigRayleighArgs {
 // out3 = {sum_e int (a u_e'^2 + c u_e^2) + sum_ends kappa u(x_end)^2, sum_e int rho u_e^2, sum |terms| of the first}
 hipError_t eig_rayleigh(const EigRayleighArgs& a, bool point_major, double* out3, hipStream_t s);
 
+// timestep.hip: BDF1 / BDF2 steps of rho u_t - (a u')' + c u = f.  Vectors are case-major
+// [nc][ne+1]; the host forms (ts_*_host) run the same inline routines on host arrays, bit for bit.
+struct TsRhsArgs {
+  const double* mdiag;              // the mass bands of rho: [ne+1], [ne]
+  const double* moff;
+  const double* U0;                 // u^n [nc][ne+1]
+  const double* U1;                 // u^{n-1} [nc][ne+1]; not read when beta1 == 0
+  const double* loads;              // [R][ne+1], shared by the cases
+  const double* phi;                // [nc][R]
+  int64_t ne;
+  int nc, R;
+  double beta0, beta1, inv_dt;
+};
+// out[j][i] = inv_dt (M (beta0 U0[j] + beta1 U1[j]))_i + sum_r phi[j][r] loads[r][i]
+hipError_t ts_rhs(const TsRhsArgs& a, double* out, hipStream_t s);
+void ts_rhs_host(const TsRhsArgs& a, double* out);
+struct TsSourceArgs {
+  const double* U2;                 // u^{n+1}, u^n, u^{n-1} [ne+1]; U1 not read when beta1 == 0
+  const double* U0;
+  const double* U1;
+  const double* ftab;               // [R] tables of ne * n_colloc, one layout
+  const double* rho_tab;
+  const double* phi;                // [R]
+  int64_t ne;
+  int n_colloc, R;
+  double alpha, beta0, beta1, inv_dt;
+};
+// out(e, k) = sum_r phi[r] ftab[r](e, k) - rho_tab(e, k) (w_e + (w_{e+1} - w_e) k / (n_colloc - 1))
+hipError_t ts_source_table(const TsSourceArgs& a, bool point_major, double* out, hipStream_t s);
+void ts_source_table_host(const TsSourceArgs& a, bool point_major, double* out);
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

@@ -1843,6 +1843,105 @@ def eig_rayleigh(x, W, nq, a_values, c_values, rho_values, *, point_major=False,
     return out
 
 
+# --------------------------------------------------------------------------
+# transient problems rho u_t - (a u')' + c u = f
+# --------------------------------------------------------------------------
+TS_MAX_TERMS = 8       # most terms phi_r(t) f_r(x) of a separable forcing
+BDF = {"bdf1": (1.0, 1.0, 0.0), "bdf2": (1.5, 2.0, -0.5)}      # scheme -> (alpha, beta0, beta1)
+
+
+def _ts_scalars(**named):
+    out = []
+    for nm, v in named.items():
+        v = float(v)
+        if not math.isfinite(v):
+            raise ValueError(f"{nm} must be finite, got {v!r}")
+        out.append(v)
+    return out
+
+
+def ts_rhs(mdiag, moff, U0, U1, loads, phi, beta0, beta1, inv_dt, *, out=None, stream=None):
+    """``lssvr_ts_rhs``: the right-hand side of one BDF step for ``nc`` cases,
+    out[j] = inv_dt M (beta0 U0[j] + beta1 U1[j]) + sum_r phi[j, r] loads[r], with the mass bands M = (mdiag[ne+1],
+    moff[ne]), U0, U1 float64[nc, ne+1] (nc <= 8), loads float64[R, ne+1] (R <= 8, shared by the cases) and phi
+    float64[nc, R], all on the device.  ``beta1 == 0`` reads no U1 (``None`` allowed).  Rows 0 and ne are the natural
+    end rows.  No synchronisation and no copy; the sums run in a fixed order (bitwise reproducible).  Returns out
+    float64[nc, ne+1]; ``out`` must not be U0 or U1."""
+    lib = _capi.load()
+    for nm, t in (("mdiag", mdiag), ("moff", moff), ("U0", U0), ("loads", loads), ("phi", phi)):
+        _dev(t, nm)
+    beta0, beta1, inv_dt = _ts_scalars(beta0=beta0, beta1=beta1, inv_dt=inv_dt)
+    ne = moff.numel()
+    if ne < 1:
+        raise ValueError("need at least one element")
+    if mdiag.dim() != 1 or moff.dim() != 1 or mdiag.numel() != ne + 1:
+        raise ValueError("band lengths must be ne+1, ne (mdiag, moff)")
+    if U0.dim() != 2 or U0.shape[1] != ne + 1 or not 1 <= U0.shape[0] <= TRIDIAG_MULTI_CASES:
+        raise ValueError(f"U0 must be [nc, ne+1] = [1 .. {TRIDIAG_MULTI_CASES}, {ne + 1}], got {list(U0.shape)}")
+    nc = int(U0.shape[0])
+    if loads.dim() != 2 or loads.shape[1] != ne + 1 or not 1 <= loads.shape[0] <= TS_MAX_TERMS:
+        raise ValueError(f"loads must be [R, ne+1] = [1 .. {TS_MAX_TERMS}, {ne + 1}], got {list(loads.shape)}")
+    R = int(loads.shape[0])
+    if tuple(phi.shape) != (nc, R):
+        raise ValueError(f"phi must be [nc, R] = [{nc}, {R}], got {list(phi.shape)}")
+    if beta1 != 0.0 and U1 is None:
+        raise ValueError("U1 is needed when beta1 != 0")
+    if U1 is not None:
+        _dev(U1, "U1")
+        if U1.shape != U0.shape:
+            raise ValueError(f"U1 must have the shape of U0 {list(U0.shape)}, got {list(U1.shape)}")
+    out = _eig_out(out, "out", (nc, ne + 1), mdiag)
+    if any(s is not None and out.data_ptr() == s.data_ptr() for s in (U0, U1)):
+        raise ValueError("out must not be U0 or U1")
+    _same_device(mdiag, moff=moff, U0=U0, loads=loads, phi=phi, **({} if U1 is None else {"U1": U1}))
+    rc = lib.lssvr_ts_rhs(_ptr(mdiag), _ptr(moff), _ptr(U0), _ptr(U1), _ptr(loads), _ptr(phi), ne, nc, R, beta0, beta1,
+                          inv_dt, _ptr(out), _stream(stream))
+    _capi.check(rc, "lssvr_ts_rhs")
+    return out
+
+
+def ts_source_table(U2, U0, U1, ftab, rho_tab, phi, alpha, beta0, beta1, inv_dt, *, point_major=False, out=None,
+                    stream=None):
+    """``lssvr_ts_source_table``: the right-hand-side table of the elliptic enhancement problem of one snapshot,
+    out(e, k) = sum_r phi[r] ftab[r](e, k) - rho_tab(e, k) (w_e + (w_{e+1} - w_e) k / (n_colloc - 1)) with the nodal
+    BDF difference w = inv_dt (alpha U2 - beta0 U0 - beta1 U1) formed in the kernel.  U2, U0, U1 float64[ne+1];
+    ftab float64[R, ne, n_colloc] and rho_tab float64[ne, n_colloc] at :func:`colloc_points` (``point_major``:
+    [R, n_colloc, ne] and [n_colloc, ne]); phi float64[R]; all on the device.  ``beta1 == 0`` reads no U1 (``None``
+    allowed).  Returns out in rho_tab's shape."""
+    lib = _capi.load()
+    for nm, t in (("U2", U2), ("U0", U0), ("ftab", ftab), ("rho_tab", rho_tab), ("phi", phi)):
+        _dev(t, nm)
+    alpha, beta0, beta1, inv_dt = _ts_scalars(alpha=alpha, beta0=beta0, beta1=beta1, inv_dt=inv_dt)
+    ne = U2.numel() - 1
+    if U2.dim() != 1 or ne < 1:
+        raise ValueError("U2 must be 1-D with at least two nodes")
+    if rho_tab.dim() != 2 or rho_tab.shape[1 if point_major else 0] != ne:
+        raise ValueError(f"rho_tab must be {'[n_colloc, ne]' if point_major else '[ne, n_colloc]'} with ne = {ne}, "
+                         f"got {list(rho_tab.shape)}")
+    n = int(rho_tab.shape[0 if point_major else 1])
+    if n < 2:
+        raise ValueError(f"n_colloc must be >= 2, got {n}")
+    if ftab.dim() != 3 or tuple(ftab.shape[1:]) != tuple(rho_tab.shape) or not 1 <= ftab.shape[0] <= TS_MAX_TERMS:
+        raise ValueError(f"ftab must be [R, ...] = [1 .. {TS_MAX_TERMS}, {', '.join(map(str, rho_tab.shape))}], "
+                         f"got {list(ftab.shape)}")
+    R = int(ftab.shape[0])
+    if tuple(phi.shape) != (R,):
+        raise ValueError(f"phi must be [R] = [{R}], got {list(phi.shape)}")
+    if beta1 != 0.0 and U1 is None:
+        raise ValueError("U1 is needed when beta1 != 0")
+    named = {"U0": U0} if U1 is None else {"U0": U0, "U1": U1}
+    for nm, t in named.items():
+        _dev(t, nm)
+        if t.shape != U2.shape:
+            raise ValueError(f"{nm} must have the shape of U2 {list(U2.shape)}, got {list(t.shape)}")
+    out = _eig_out(out, "out", tuple(rho_tab.shape), U2)
+    _same_device(U2, ftab=ftab, rho_tab=rho_tab, phi=phi, **named)
+    rc = lib.lssvr_ts_source_table(_ptr(U2), _ptr(U0), _ptr(U1), _ptr(ftab), _ptr(rho_tab), _ptr(phi), ne, n, R,
+                                   _layout(point_major), alpha, beta0, beta1, inv_dt, _ptr(out), _stream(stream))
+    _capi.check(rc, "lssvr_ts_source_table")
+    return out
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

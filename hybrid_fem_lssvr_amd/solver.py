@@ -297,6 +297,26 @@ class EigenSolution:
         return self.modes[j].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
 
 
+class TransientSolution:
+    """What :meth:`FEMLSSVRPrimalSolver.solve_transient` returns for its ``ns`` snapshots, in ascending time:
+
+    * ``times`` float64[ns];
+    * ``nodal`` float64[ns, ne+1]: the P1 nodal values;
+    * ``enhanced``: ns :class:`EnhancedSolution` (empty with ``enhance=False``);
+    * ``bands``, a diagnostic: host copies of what the loop ran on, as the device assembled it --
+      dict(mass=(mdiag, moff), step={alpha: (diag, off)}, loads [R, ne+1])."""
+
+    def __init__(self, times, nodal, enhanced, bands):
+        self.times, self.nodal, self.enhanced, self.bands = times, nodal, enhanced, bands
+
+    def evaluate(self, k, x, deriv=0):
+        """The enhanced snapshot ``k`` (its ``deriv``-th x-derivative) at the points ``x``."""
+        if not self.enhanced:
+            raise RuntimeError("solve_transient ran with enhance=False: there are no enhanced snapshots to evaluate")
+        x = np.asarray(x, dtype=np.float64)
+        return self.enhanced[k].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
+
+
 class _ElementFunctions:
     """``solver.lssvr_functions``: a read-only sequence whose item i is
     ``Legendre(W[i], [x_i, x_{i+1}])`` (Dual.py:95, 163) -- built lazily from the device
@@ -1153,6 +1173,191 @@ class FEMLSSVRPrimalSolver:
                                         work=ework).cpu().numpy()
                 values[j] = out3[0] / out3[1]
         return EigenSolution(th[:k].copy(), values, res[:k].copy(), index, it, converged, nodal, modes, sigma)
+
+    # ---- transient problems (no reference counterpart) --------------------
+    def _check_transient(self, u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance):
+        """What :meth:`solve_transient` does not cover and what its data must satisfy, on the host and before any
+        device call -> dict(nodes, kinds, kappa, dt, times, steps, u_init, phi [nsteps, R], g [nsteps + 1, 2], quad,
+        colloc).  Every callable is evaluated here, once per kind of point, and ``quad`` / ``colloc`` are its host
+        tables, the ones the device is handed: a, c, rho [ne, nquad] and f [R, ne, nquad] at the Gauss points of the
+        assembly; with ``enhance`` a, da, c, rho [ne, n_colloc] and f [R, ne, n_colloc] at np.linspace(x_e, x_e+1,
+        n_colloc), the abscissae lssvr_colloc_points writes (else None)."""
+        if self.convection is not None:
+            raise ValueError("solve_transient has no convection term: the step's matrix would need the non-symmetric "
+                             "solve and a cell Peclet check per step size")
+        if self._periodic:
+            raise ValueError("solve_transient has no boundary='periodic': the time loop runs the solve with Dirichlet "
+                             "or Robin ends")
+        if self.fem_solver != "bands":
+            raise ValueError("solve_transient needs fem_solver='bands': the step's matrix K + (alpha / dt) M carries "
+                             "a mass matrix (no flux solve) and is definite (no pivoting)")
+        if self.element_degrees is not None:
+            raise ValueError("solve_transient has no element_degrees: all snapshots are enhanced as cases of one "
+                             "ops.enhance_multi, which has one degree")
+        if self.solver_id != ops.SOLVER_PRIMAL:
+            raise ValueError("solve_transient needs solver=ops.SOLVER_PRIMAL: the snapshots are enhanced through the "
+                             "reaction rows, which have a primal solve only")
+        if not callable(u0):
+            raise ValueError("u0 must be a callable u0(x)")
+        if weight is not None and not callable(weight):
+            raise ValueError("weight must be a callable rho(x) or None")
+        if scheme not in ops.BDF:
+            raise ValueError(f"scheme must be 'bdf1' or 'bdf2', got {scheme!r}")
+        if isinstance(nsteps, bool) or int(nsteps) != nsteps or int(nsteps) < 1:
+            raise ValueError(f"nsteps must be an integer >= 1, got {nsteps!r}")
+        nsteps, t_end = int(nsteps), float(t_end)
+        if not (math.isfinite(t_end) and t_end > 0.0):
+            raise ValueError(f"t_end must be finite and > 0, got {t_end!r}")
+        forcing = [(1.0, self.rhs)] if forcing is None else list(forcing)
+        if not all(isinstance(p, (tuple, list)) and len(p) == 2 and callable(p[1]) for p in forcing):
+            raise ValueError("forcing must be a list of (phi, f_x) pairs: phi a callable of t or a constant, f_x a "
+                             "callable of x")
+        if not 1 <= len(forcing) <= ops.TS_MAX_TERMS:
+            raise ValueError(f"forcing must hold 1 .. {ops.TS_MAX_TERMS} terms (R <= {ops.TS_MAX_TERMS}), got "
+                             f"{len(forcing)}")
+        snapshots = [nsteps] if snapshots is None else list(snapshots)
+        if not snapshots or any(isinstance(s, bool) or int(s) != s or not 1 <= int(s) <= nsteps for s in snapshots):
+            raise ValueError(f"snapshots must be step indices in 1 .. nsteps = {nsteps}, got {snapshots!r}")
+        steps = sorted({int(s) for s in snapshots})
+        bnd = self._bnd
+        kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (tuple(bnd.kinds), tuple(bnd.kappa))
+        if end_data is None:
+            end_data = self._gd_bc()[1]
+        if not isinstance(end_data, (tuple, list)) or len(end_data) != 2:
+            raise ValueError("end_data must be a pair (g_left, g_right) of callables of t or constants")
+        gfn = [v if callable(v) else (lambda t, v=float(v): v) for v in end_data]
+        pfn = [p if callable(p) else (lambda t, p=float(p): p) for p, _ in forcing]
+        m = self._default_mesh() if self.mesh is None else self.mesh
+        nodes = np.asarray(m.nodes, dtype=np.float64)
+        dt = t_end / nsteps
+        times = dt * np.arange(nsteps + 1)
+        phi = np.array([[float(p(t)) for p in pfn] for t in times[1:]], dtype=np.float64)
+        g = np.array([[float(v(t)) for v in gfn] for t in times], dtype=np.float64)
+        # the data at the Gauss points of the assembly, a + h xi on [0, 1] as lssvr_quad_points has them, and at the
+        # collocation points: finite, one value per point, rho > 0, c + rho / dt >= 0
+        xi = 0.5 * (1.0 + np.polynomial.legendre.leggauss(int(self.nquad))[0])
+        xq = nodes[:-1, None] + np.diff(nodes)[:, None] * xi[None, :]
+        eq = self._eq
+        fns = dict(a=_one if eq.a is None else eq.a, da=_zero if eq.da is None else eq.da,
+                   c=_zero if eq.c is None else eq.c, rho=_one if weight is None else weight)
+
+        def tables(pts, names, what):
+            out = {}
+            for nm, fn in (*((k, fns[k]) for k in names), *((r, f) for r, (_, f) in enumerate(forcing))):
+                label = f"forcing[{nm}] f_x" if isinstance(nm, int) else {"a": "coef a", "da": "coef da",
+                                                                          "c": "reaction", "rho": "weight"}[nm]
+                try:
+                    t = np.broadcast_to(np.asarray(fn(pts), dtype=np.float64), pts.shape)
+                except ValueError:
+                    raise ValueError(f"{label} must return one value per point ({list(pts.shape)} at the {what} "
+                                     "points) or a value that broadcasts to them") from None
+                if not np.all(np.isfinite(t)):
+                    raise ValueError(f"{label} is not finite at a {what} point")
+                out[nm] = np.array(t)                       # (an own, writable copy: broadcast_to gives a view)
+            out["f"] = np.stack([out.pop(r) for r in range(len(forcing))])
+            return out
+
+        quad = tables(xq, ("a", "c", "rho"), "quadrature")
+        colloc = None
+        if enhance:
+            n = int(self.n_colloc)
+            if n < 2:
+                raise ValueError(f"n_colloc must be >= 2, got {n}")
+            colloc = tables(np.linspace(nodes[:-1], nodes[1:], n, axis=-1), ("a", "da", "c", "rho"), "collocation")
+        u_init = np.array(np.broadcast_to(np.asarray(u0(nodes), dtype=np.float64), nodes.shape))
+        for i, end in ((0, 0), (1, -1)):
+            if kinds[i] == ops.END_DIRICHLET:
+                u_init[end] = g[0, i]
+        for nm, t in (("u0", u_init), ("end_data", g), ("forcing phi", phi)):
+            if not np.all(np.isfinite(t)):
+                raise ValueError(f"{nm} is not finite where it is tabulated")
+        if not np.all(quad["rho"] > 0.0):
+            raise ValueError("weight must be positive at every quadrature point (rho > 0): M would not be positive "
+                             "definite")
+        if not np.all(quad["c"] + quad["rho"] / dt >= 0.0):
+            raise ValueError(f"c + rho / dt < 0 at a quadrature point (dt = {dt:.6g}): the step's matrix would not be "
+                             "positive definite, and the solve does not pivot; shorten the step")
+        return dict(nodes=nodes, kinds=kinds, kappa=kappa, dt=dt, times=times, steps=steps, u_init=u_init, phi=phi,
+                    g=g, quad=quad, colloc=colloc)
+
+    def solve_transient(self, u0, t_end, *, nsteps, scheme="bdf2", weight=None, forcing=None, end_data=None,
+                        snapshots=None, enhance=True):
+        """rho u_t - (a u')' + c u = f(x, t) for 0 < t <= ``t_end`` with u(x, 0) = ``u0(x)``, on the solver's ``mesh``
+        with its ``coef``, ``reaction`` and ``boundary`` kinds (each end Dirichlet u = g(t) or Robin
+        a du/dn + kappa u = g(t)); ``nsteps`` equal steps of backward Euler (``scheme="bdf1"``) or of BDF2 started by
+        one backward-Euler step (``"bdf2"``).  ``weight`` = rho (a callable; ``None``: 1); ``forcing``: a list of at
+        most 8 pairs (phi, f_x), f(x, t) = sum phi(t) f_x(x), phi a callable of t or a constant (``None``:
+        ``[(1, self.rhs)]``); ``end_data`` = (g_left, g_right), callables of t or constants (``None``: the end values
+        ``solve()`` uses); ``snapshots``: the step indices in 1 .. nsteps to keep (``None``: the last).  ``u0`` is
+        sampled at the nodes, and a Dirichlet end starts at g(0).
+
+        Per step ``ops.ts_rhs`` and one ``ops.tridiag_bc_solve_multi`` on the bands of
+        K + (alpha / dt) M, assembled once per alpha; phi and g of every step are uploaded before the loop, which
+        rotates three nodal buffers on one stream and issues no copy from the host and no synchronisation.  At a
+        snapshot step ``ops.ts_source_table`` writes the right-hand side f(., t) - rho I_h w of the snapshot's elliptic
+        problem (w: the nodal BDF difference); with ``enhance`` all snapshots then go through ONE
+        ``ops.enhance_multi`` (``lssvr_M``, ``n_colloc``, ``lssvr_gamma``; c itself, not shifted by 1 / dt).  Two
+        Neumann ends without a reaction are fine here: M / dt makes the matrix definite.  Returns a
+        :class:`TransientSolution`; the solver's attributes are left as they are."""
+        torch = _torch()
+        p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, bool(enhance))
+        nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
+        nsteps, ne, ns, inv_dt = int(nsteps), nodes.size - 1, len(p["steps"]), 1.0 / p["dt"]
+        dev = _device(self.device)
+        x = _to_dev(nodes, dev)
+        zq = torch.zeros((ne, int(self.nquad)), dtype=torch.float64, device=dev)
+        aq = None if self.coef is None else _to_dev(q["a"], dev)
+        Mb = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["rho"], dev))
+        # the two matrices of the loop: K + (alpha / dt) M as ONE reaction assembly each
+        A = {al: ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq,
+                                 c_quad=_to_dev(q["c"] + al * q["rho"] / dt, dev))
+             for al in {ops.BDF["bdf1"][0], ops.BDF[scheme][0]}}
+        loads = ops.p1_load_multi(x, _to_dev(q["f"], dev), self.nquad)
+        phi, g = _to_dev(p["phi"], dev), _to_dev(p["g"][1:], dev)          # row n - 1: the step that ends at t_n
+        M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
+        pm = M <= 16                         # the lane kernel of lssvr_enhance_multi reads point-major tables
+        if enhance:
+            c = p["colloc"]
+            ta, tda, tc, rtab = (_to_dev(c[k].T if pm else c[k], dev) for k in ("a", "da", "c", "rho"))
+            ftab = _to_dev(np.transpose(c["f"], (0, 2, 1)) if pm else c["f"], dev)
+            src = torch.empty((ns,) + tuple(rtab.shape), dtype=torch.float64, device=dev)
+        U = torch.empty((3, ne + 1), dtype=torch.float64, device=dev)
+        U[0].copy_(_to_dev(p["u_init"], dev))
+        S = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
+        b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
+        work = ops._scratch(None, ops._capi.load().lssvr_tridiag_bc_work_bytes(ne, 1), dev)
+        md, mo = Mb["diag"], Mb["off"]
+        bdf1 = ops.BDF["bdf1"]
+        snap = {s: k for k, s in enumerate(steps)}
+        cur, prev, new = 0, 1, 2
+        # the loop: launches on the current stream only
+        for step in range(1, nsteps + 1):
+            al, b0, b1 = bdf1 if step == 1 else ops.BDF[scheme]
+            u_prev = None if b1 == 0.0 else U[prev:prev + 1]
+            ops.ts_rhs(md, mo, U[cur:cur + 1], u_prev, loads, phi[step - 1:step], b0, b1, inv_dt, out=b)
+            ops.tridiag_bc_solve_multi(A[al]["diag"], A[al]["off"], b, kinds, kappa, g[step - 1:step],
+                                       out=U[new:new + 1], work=work)
+            k = snap.get(step)
+            if k is not None:
+                S[k].copy_(U[new])
+                if enhance:
+                    ops.ts_source_table(U[new], U[cur], None if b1 == 0.0 else U[prev], ftab, rtab, phi[step - 1], al,
+                                        b0, b1, inv_dt, point_major=pm, out=src[k])
+            cur, prev, new = new, cur, prev
+        enhanced = []
+        if enhance:
+            gd = (float(self.global_domain[0]), float(self.global_domain[1]))
+            bc = g[torch.as_tensor([s - 1 for s in steps], device=dev)].contiguous()
+            W, st = ops.enhance_multi(x, S, M, gamma, n, ta, tda, src, c_values=tc, bc=bc, point_major=pm,
+                                      global_domain=gd, **self._shard(ne))
+            enhanced = [EnhancedSolution(x, W[k], st[k]) for k in range(ns)]
+        host = torch.cat([S.reshape(-1), md, mo, *(A[al][k] for al in sorted(A) for k in ("diag", "off")),
+                          loads.reshape(-1)]).cpu().numpy()                  # one copy: the snapshots and the bands
+        cut = np.cumsum([ns * (ne + 1), ne + 1, ne] + [ne + 1, ne] * len(A))
+        parts = np.split(host, cut)
+        bands = dict(mass=(parts[1], parts[2]), loads=parts[-1].reshape(-1, ne + 1),
+                     step={al: (parts[3 + 2 * i], parts[4 + 2 * i]) for i, al in enumerate(sorted(A))})
+        return TransientSolution(p["times"][steps].copy(), parts[0].reshape(ns, ne + 1), enhanced, bands)
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):

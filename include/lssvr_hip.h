@@ -1013,6 +1013,50 @@ int lssvr_eig_rayleigh(const double* x, const double* W, int64_t ne, int M, int 
                        int kind_left, int kind_right, const double* kappa_host,
                        double* out3, void* work, void* stream);
 
+/*
+ * Transient problems: rho u_t - (a u')' + c u = f(x, t), rho > 0, BDF1 / BDF2 with a fixed step dt (no reference
+ * counterpart).  ADDITIVE to ABI 7: four new symbols, no existing entry, struct, constant or
+ * kernel changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * Step n+1 solves  A_alpha u^{n+1} = (1/dt) M (beta0 u^n + beta1 u^{n-1}) + load(t_{n+1})  with alpha, (beta0, beta1)
+ * = 1, (1, 0) for BDF1 and 3/2, (2, -1/2) for BDF2.  M = (mdiag[ne+1], moff[ne]) are the bands of
+ * lssvr_p1_assemble_react with an a_quad of zeros and c_quad = rho, A_alpha those of the same entry with
+ * c_quad = c + alpha rho / dt; the solve is lssvr_tridiag_bc_solve_multi, whose end_values of the step (g(t_{n+1}) per
+ * end) are a device row.  The forcing is separable, f(x, t) = sum_{r<R} phi_r(t) f_r(x), 1 <= R <= 8: the R loads come
+ * from lssvr_p1_load_multi once, and phi of every step lives in a device table.  Nothing here synchronises or copies:
+ * a time loop is launches on one stream.  No reduction, no atomics: bitwise reproducible.
+ *
+ * lssvr_ts_rhs -- out[j*(ne+1) + i] = inv_dt (M (beta0 U0[j] + beta1 U1[j]))_i + sum_r phi[j*R + r] loads[r*(ne+1) + i]
+ * for the nc cases (1 <= nc <= 8) U0, U1, out [nc][ne+1], loads [R][ne+1] shared by the cases, phi [nc][R], all DEVICE
+ * arrays; ne >= 1.  beta1 == 0 does not read U1 (may be NULL).  Rows 0 and ne are the natural end rows (the full mass
+ * row of the end node); the solvers ignore them at a Dirichlet end.  out must not be U0 or U1.  The order of the sums:
+ * v = beta0 U0 + beta1 U1;  m = (moff[i-1] v[i-1] + mdiag[i] v[i]) + moff[i] v[i+1];  then inv_dt m, plus the terms
+ * phi[r] loads[r] one by one, r ascending.
+ *
+ * lssvr_ts_source_table -- for one snapshot, the right-hand-side table of its elliptic enhancement problem
+ * -(a u')' + c u = f(., t) - rho I_h w, in either LSSVR_TABLE_* layout:
+ *   out(e, k) = sum_r phi[r] ftab[r](e, k) - rho_tab(e, k) (w_e + (w_{e+1} - w_e) (k / (n_colloc - 1))),
+ *   w_i = inv_dt ((alpha U2_i - beta0 U0_i) - beta1 U1_i)      (the nodal BDF difference of u^{n+1} = U2),
+ * with ftab [R] tables and rho_tab one table of ne * n_colloc doubles at lssvr_colloc_points(_pm), phi [R], U2, U0, U1
+ * [ne+1], all DEVICE arrays; 2 <= n_colloc <= 4096.  beta1 == 0 does not read U1 (may be NULL).  The sum over r runs
+ * r ascending.
+ *
+ * lssvr_ts_rhs_host, lssvr_ts_source_table_host -- the same routines on HOST arrays, bit for bit: no device is touched.
+ */
+int lssvr_ts_rhs(const double* mdiag, const double* moff, const double* U0, const double* U1, const double* loads,
+                 const double* phi, int64_t ne, int nc, int R, double beta0, double beta1, double inv_dt,
+                 double* out, void* stream);
+int lssvr_ts_rhs_host(const double* mdiag_host, const double* moff_host, const double* U0_host, const double* U1_host,
+                      const double* loads_host, const double* phi_host, int64_t ne, int nc, int R, double beta0,
+                      double beta1, double inv_dt, double* out_host);
+int lssvr_ts_source_table(const double* U2, const double* U0, const double* U1, const double* ftab,
+                          const double* rho_tab, const double* phi, int64_t ne, int n_colloc, int R, int table_layout,
+                          double alpha, double beta0, double beta1, double inv_dt, double* out, void* stream);
+int lssvr_ts_source_table_host(const double* U2_host, const double* U0_host, const double* U1_host,
+                               const double* ftab_host, const double* rho_tab_host, const double* phi_host, int64_t ne,
+                               int n_colloc, int R, int table_layout, double alpha, double beta0, double beta1,
+                               double inv_dt, double* out_host);
+
 #ifdef __cplusplus
 }
 #endif
