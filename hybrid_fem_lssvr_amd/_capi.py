@@ -29,6 +29,8 @@ SOLVER_PRIMAL_WAVE = 2
 SOLVER_PRIMAL_MOMENT = 3
 END_DIRICHLET = 0
 END_ROBIN = 1
+NL_POLY = 0
+NL_EXP = 1
 ST_OK = 0
 ST_FALLBACK = 1
 
@@ -173,6 +175,16 @@ SIGNATURES = {
     "lssvr_ts_rhs_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_hd]),
     "lssvr_ts_source_table": _sig([_c_dp] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dbl] * 4, [_c_dp], _STREAM),
     "lssvr_ts_source_table_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dbl] * 4, [_c_hd]),
+    # semilinear problems (additive to ABI 7): u, t_local, q_tabs, c_tab, f_tab, ne, n, layout, kind, nterm, c_eff,
+    # f_eff, f_res; diag, sub, sup, load, u, u_new, kind_left, kind_right, end_values, kappa_host, ne, out4, work;
+    # u, u_new, lambda, ne, out
+    "lssvr_nl_linearize": _sig([_c_dp] * 5, [_c_i64, _c_int, _c_int, _c_int, _c_int], [_c_dp] * 3, _STREAM),
+    "lssvr_nl_linearize_host": _sig([_c_hd] * 5, [_c_i64, _c_int, _c_int, _c_int, _c_int], [_c_hd] * 3),
+    "lssvr_nl_residual_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_nl_residual": _sig([_c_dp] * 6, _ENDS, [_c_i64, _c_dp], _WS, _STREAM),
+    "lssvr_nl_residual_host": _sig([_c_hd] * 6, [_c_int, _c_int, _c_hd, _c_hd], [_c_i64, _c_hd]),
+    "lssvr_nl_step": _sig([_c_dp, _c_dp, _c_dbl, _c_i64, _c_dp], _STREAM),
+    "lssvr_nl_step_host": _sig([_c_hd, _c_hd, _c_dbl, _c_i64, _c_hd]),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

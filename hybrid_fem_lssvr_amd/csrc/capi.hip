@@ -1614,4 +1614,120 @@ int lssvr_ts_source_table_host(const double* U2_host, const double* U0_host, con
   return LSSVR_OK;
 }
 
+// Semilinear problems (nonlinear.hip).  The device and the host entry of each pair share one validated binding.
+static int bind_nl_linearize(lssvr::NlLinArgs& a, const double* u, const double* t_local, const double* q_tabs,
+                             const double* c_tab, const double* f_tab, int64_t ne, int n, int table_layout, int kind,
+                             int nterm, double* c_eff, double* f_eff, double* f_res) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (n < 1 || n > 64) return fail(LSSVR_ERR_SIZE, "n = %d outside [1, 64]", n);
+  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
+    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  if (kind != LSSVR_NL_POLY && kind != LSSVR_NL_EXP)
+    return fail(LSSVR_ERR_RHS, "unknown kind %d (LSSVR_NL_POLY or LSSVR_NL_EXP)", kind);
+  if (kind == LSSVR_NL_POLY && (nterm < 1 || nterm > 6))
+    return fail(LSSVR_ERR_SIZE, "nterm = %d outside [1, 6]", nterm);
+  if (kind == LSSVR_NL_EXP && nterm != 2) return fail(LSSVR_ERR_SIZE, "nterm = %d: LSSVR_NL_EXP has q_0 and q_1", nterm);
+  if (!u || !t_local || !q_tabs || !f_tab) return fail(LSSVR_ERR_NULL, "u, t_local, q_tabs, f_tab must be non-NULL");
+  if (!c_eff && !f_eff && !f_res) return fail(LSSVR_ERR_NULL, "one of c_eff, f_eff, f_res must be non-NULL");
+  for (const double* o : {(const double*)c_eff, (const double*)f_eff, (const double*)f_res})
+    if (o && (o == u || o == t_local || o == q_tabs || o == c_tab || o == f_tab))
+      return fail(LSSVR_ERR_SIZE, "an output must not be one of the inputs");
+  if ((c_eff && (c_eff == f_eff || c_eff == f_res)) || (f_eff && f_eff == f_res))
+    return fail(LSSVR_ERR_SIZE, "c_eff, f_eff, f_res must be distinct");
+  a = lssvr::NlLinArgs{u, t_local, q_tabs, c_tab, f_tab, ne, n, kind, nterm, c_eff, f_eff, f_res};
+  return LSSVR_OK;
+}
+
+int lssvr_nl_linearize(const double* u, const double* t_local, const double* q_tabs, const double* c_tab,
+                       const double* f_tab, int64_t ne, int n, int table_layout, int kind, int nterm, double* c_eff,
+                       double* f_eff, double* f_res, void* stream) {
+  lssvr::NlLinArgs a{};
+  const int rc = bind_nl_linearize(a, u, t_local, q_tabs, c_tab, f_tab, ne, n, table_layout, kind, nterm, c_eff, f_eff,
+                                   f_res);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::nl_linearize(a, table_layout == LSSVR_TABLE_POINT_MAJOR,
+                                          reinterpret_cast<hipStream_t>(stream)),
+                      "nl_linearize");
+}
+
+int lssvr_nl_linearize_host(const double* u_host, const double* t_local_host, const double* q_tabs_host,
+                            const double* c_tab_host, const double* f_tab_host, int64_t ne, int n, int table_layout,
+                            int kind, int nterm, double* c_eff_host, double* f_eff_host, double* f_res_host) {
+  lssvr::NlLinArgs a{};
+  const int rc = bind_nl_linearize(a, u_host, t_local_host, q_tabs_host, c_tab_host, f_tab_host, ne, n, table_layout,
+                                   kind, nterm, c_eff_host, f_eff_host, f_res_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::nl_linearize_host(a, table_layout == LSSVR_TABLE_POINT_MAJOR);
+  return LSSVR_OK;
+}
+
+int64_t lssvr_nl_residual_work_bytes(int64_t ne) { return lssvr::nl_residual_work_bytes(ne); }
+
+static int bind_nl_residual(lssvr::NlResArgs& a, const double* diag, const double* sub, const double* sup,
+                            const double* load, const double* u, const double* u_new, int kind_left, int kind_right,
+                            const double* end_values, const double* kappa_host, int64_t ne, const double* out4) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
+  if (rc != LSSVR_OK) return rc;
+  if (!diag || !sub || !sup || !load || !u || !u_new || !out4)
+    return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u, u_new, out4 must be non-NULL");
+  const bool robin = kind_left == LSSVR_END_ROBIN || kind_right == LSSVR_END_ROBIN;
+  if (robin && !end_values) return fail(LSSVR_ERR_NULL, "end_values must be non-NULL with a Robin end");
+  a = lssvr::NlResArgs{diag, sub, sup, load, u, u_new, end_values, ne, {kind_left, kind_right}, {0.0, 0.0}};
+  for (int i = 0; i < 2; ++i) a.kappa[i] = a.kind[i] == LSSVR_END_ROBIN ? kappa_host[i] : 0.0;
+  return LSSVR_OK;
+}
+
+int lssvr_nl_residual(const double* diag, const double* sub, const double* sup, const double* load, const double* u,
+                      const double* u_new, int kind_left, int kind_right, const double* end_values,
+                      const double* kappa_host, int64_t ne, double* out4, void* work, int64_t work_bytes,
+                      void* stream) {
+  lssvr::NlResArgs a{};
+  const int rc = bind_nl_residual(a, diag, sub, sup, load, u, u_new, kind_left, kind_right, end_values, kappa_host, ne,
+                                  out4);
+  if (rc != LSSVR_OK) return rc;
+  if (!work) return fail(LSSVR_ERR_NULL, "work must be non-NULL");
+  const int64_t need = lssvr::nl_residual_work_bytes(ne);
+  if (work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work_bytes = %lld < lssvr_nl_residual_work_bytes(%lld) = %lld", (long long)work_bytes,
+                (long long)ne, (long long)need);
+  return check_launch(lssvr::nl_residual(a, out4, work, reinterpret_cast<hipStream_t>(stream)), "nl_residual");
+}
+
+int lssvr_nl_residual_host(const double* diag_host, const double* sub_host, const double* sup_host,
+                           const double* load_host, const double* u_host, const double* u_new_host, int kind_left,
+                           int kind_right, const double* end_values_host, const double* kappa_host, int64_t ne,
+                           double* out4_host) {
+  lssvr::NlResArgs a{};
+  const int rc = bind_nl_residual(a, diag_host, sub_host, sup_host, load_host, u_host, u_new_host, kind_left,
+                                  kind_right, end_values_host, kappa_host, ne, out4_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::nl_residual_host(a, out4_host);
+  return LSSVR_OK;
+}
+
+static int check_nl_step(const double* u, const double* u_new, double lambda, int64_t ne, const double* out) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (!ts_finite(lambda)) return fail(LSSVR_ERR_SIZE, "lambda = %g must be finite", lambda);
+  if (!u || !u_new || !out) return fail(LSSVR_ERR_NULL, "u, u_new, out must be non-NULL");
+  if (out == u || out == u_new) return fail(LSSVR_ERR_SIZE, "out must not be u or u_new");
+  return LSSVR_OK;
+}
+
+int lssvr_nl_step(const double* u, const double* u_new, double lambda, int64_t ne, double* out, void* stream) {
+  const int rc = check_nl_step(u, u_new, lambda, ne, out);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::nl_step(u, u_new, lambda, ne, out, reinterpret_cast<hipStream_t>(stream)), "nl_step");
+}
+
+int lssvr_nl_step_host(const double* u_host, const double* u_new_host, double lambda, int64_t ne, double* out_host) {
+  const int rc = check_nl_step(u_host, u_new_host, lambda, ne, out_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::nl_step_host(u_host, u_new_host, lambda, ne, out_host);
+  return LSSVR_OK;
+}
+
 }  // extern "C"

@@ -425,6 +425,42 @@ struct TsSourceArgs {
 hipError_t ts_source_table(const TsSourceArgs& a, bool point_major, double* out, hipStream_t s);
 void ts_source_table_host(const TsSourceArgs& a, bool point_major, double* out);
 
+// nonlinear.hip: the Newton iteration of -(a u')' + b u' + c u + g(x, u) = f.  The host forms
+// (nl_*_host) run the same inline routines on host arrays, bit for bit except for exp (libm there).
+struct NlLinArgs {
+  const double* u;                  // nodal iterate [ne+1]
+  const double* t_local;            // [n] local coordinates in [0, 1] of the n points of every element
+  const double* q_tabs;             // [nterm] tables of ne * n, one layout; EXP: q_0, q_1
+  const double* c_tab;              // nullptr: c = 0
+  const double* f_tab;
+  int64_t ne;
+  int n, kind, nterm;
+  double* c_eff;                    // c + g_u                    (each output: nullptr = not written)
+  double* f_eff;                    // (f - g) + g_u u_h
+  double* f_res;                    // f - g
+};
+hipError_t nl_linearize(const NlLinArgs& a, bool point_major, hipStream_t s);
+void nl_linearize_host(const NlLinArgs& a, bool point_major);
+struct NlResArgs {
+  const double* diag;               // the bands of the LINEAR operator: [ne+1], [ne], [ne]; symmetric: sub == sup
+  const double* sub;
+  const double* sup;
+  const double* load;               // F - G(u) [ne+1]
+  const double* u;                  // the iterate and the candidate [ne+1]
+  const double* u_new;
+  const double* end_values;         // [2]: g of a Robin end; not read at a Dirichlet end
+  int64_t ne;
+  int kind[2];                      // per end of the domain: 0 Dirichlet, 1 Robin
+  double kappa[2];
+};
+int64_t nl_residual_work_bytes(int64_t ne);
+// out4 = {max |r|, max |u_new - u|, max |u_new|, count of non-finite entries met}
+hipError_t nl_residual(const NlResArgs& a, double* out4, void* work, hipStream_t s);
+void nl_residual_host(const NlResArgs& a, double* out4);
+// out = u + lambda (u_new - u) [ne+1]
+hipError_t nl_step(const double* u, const double* u_new, double lambda, int64_t ne, double* out, hipStream_t s);
+void nl_step_host(const double* u, const double* u_new, double lambda, int64_t ne, double* out);
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

@@ -1942,6 +1942,131 @@ def ts_source_table(U2, U0, U1, ftab, rho_tab, phi, alpha, beta0, beta1, inv_dt,
     return out
 
 
+# ---- semilinear problems -(a u')' + b u' + c u + g(x, u) = f ----------------------------------
+NL_POLY, NL_EXP = _capi.NL_POLY, _capi.NL_EXP      # LSSVR_NL_*: g = sum_k q_k u^k (1 .. 6 terms); g = q_0 exp(q_1 u)
+NL_MAX_TERMS = 6
+NL_MAX_POINTS = 64
+
+
+def nl_kind(kind, nterm):
+    """(LSSVR_NL_* id, nterm) of a kind given as the id or as "poly" / "exp"; ``ValueError`` for an unknown kind or a
+    term count the kind does not have (POLY: 1 .. 6, EXP: 2)."""
+    ids = {"poly": NL_POLY, "exp": NL_EXP, NL_POLY: NL_POLY, NL_EXP: NL_EXP}
+    if isinstance(kind, bool) or kind not in ids:
+        raise ValueError(f"kind must be 'poly' (NL_POLY) or 'exp' (NL_EXP), got {kind!r}")
+    kind, nterm = ids[kind], int(nterm)
+    if kind == NL_POLY and not 1 <= nterm <= NL_MAX_TERMS:
+        raise ValueError(f"nterm = {nterm} outside 1 .. {NL_MAX_TERMS}")
+    if kind == NL_EXP and nterm != 2:
+        raise ValueError(f"kind 'exp' takes the two tables q_0, q_1, got {nterm}")
+    return kind, nterm
+
+
+def nl_linearize(u, t_local, kind, q_tabs, f_tab, *, c_tab=None, point_major=False, c_eff=True, f_eff=True,
+                 f_res=False, stream=None):
+    """``lssvr_nl_linearize``: the tables of one Newton step around the nodal iterate ``u`` float64[ne+1], at the n
+    points per element (n <= 64) whose local coordinates in [0, 1] are ``t_local`` float64[n]: with
+    u_h = u_e + (u_{e+1} - u_e) t_k,
+
+        c_eff = c + g_u(x, u_h),   f_eff = (f - g(x, u_h)) + g_u(x, u_h) u_h,   f_res = f - g(x, u_h).
+
+    ``kind``: ``NL_POLY`` / "poly" (g = sum_k q_k u^k by Horner) or ``NL_EXP`` / "exp" (g = q_0 exp(q_1 u));
+    ``q_tabs`` float64[nterm, ne, n], ``f_tab`` and ``c_tab`` (``None``: c = 0) float64[ne, n] -- ``point_major``:
+    [nterm, n, ne] and [n, ne] --, all on the device.  Each of ``c_eff``, ``f_eff``, ``f_res``: True (allocated), a
+    tensor of f_tab's shape (written), or False / None (not computed).  Returns the dict of those written.  No
+    synchronisation and no copy."""
+    lib = _capi.load()
+    for nm, t in (("u", u), ("t_local", t_local), ("q_tabs", q_tabs), ("f_tab", f_tab)):
+        _dev(t, nm)
+    ne = u.numel() - 1
+    if u.dim() != 1 or ne < 1:
+        raise ValueError("u must be 1-D with at least two nodes")
+    if f_tab.dim() != 2 or f_tab.shape[1 if point_major else 0] != ne:
+        raise ValueError(f"f_tab must be {'[n, ne]' if point_major else '[ne, n]'} with ne = {ne}, "
+                         f"got {list(f_tab.shape)}")
+    n = int(f_tab.shape[0 if point_major else 1])
+    if not 1 <= n <= NL_MAX_POINTS:
+        raise ValueError(f"n = {n} points per element outside 1 .. {NL_MAX_POINTS}")
+    if tuple(t_local.shape) != (n,):
+        raise ValueError(f"t_local must be [n] = [{n}], got {list(t_local.shape)}")
+    if q_tabs.dim() != 3 or tuple(q_tabs.shape[1:]) != tuple(f_tab.shape):
+        raise ValueError(f"q_tabs must be [nterm, {', '.join(map(str, f_tab.shape))}], got {list(q_tabs.shape)}")
+    kind, nterm = nl_kind(kind, q_tabs.shape[0])
+    if c_tab is not None:
+        _dev(c_tab, "c_tab")
+        if c_tab.shape != f_tab.shape:
+            raise ValueError(f"c_tab must have the shape of f_tab {list(f_tab.shape)}, got {list(c_tab.shape)}")
+    outs = {}
+    for nm, o in (("c_eff", c_eff), ("f_eff", f_eff), ("f_res", f_res)):
+        if o is None or o is False:
+            continue
+        outs[nm] = _eig_out(None if o is True else o, nm, tuple(f_tab.shape), u)
+    if not outs:
+        raise ValueError("one of c_eff, f_eff, f_res must be asked for")
+    _same_device(u, t_local=t_local, q_tabs=q_tabs, f_tab=f_tab, c_tab=c_tab)
+    rc = lib.lssvr_nl_linearize(_ptr(u), _ptr(t_local), _ptr(q_tabs), _ptr(c_tab), _ptr(f_tab), ne, n,
+                                _layout(point_major), kind, nterm, _ptr(outs.get("c_eff")), _ptr(outs.get("f_eff")),
+                                _ptr(outs.get("f_res")), _stream(stream))
+    _capi.check(rc, "lssvr_nl_linearize")
+    return outs
+
+
+def nl_residual(diag, sub, sup, load, u, u_new, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0),
+                end_values=None, *, out4=None, work=None, stream=None):
+    """``lssvr_nl_residual``: out4 float64[4] on the device = (max |r|, max |u_new - u|, max |u_new|, the count of
+    non-finite entries met) with r = K u + (Robin end terms) - load on the free rows, 0 on a Dirichlet end row; K the
+    bands diag[ne+1], sub[ne], sup[ne] of the LINEAR operator (symmetric: pass ``off`` twice), load = F - G(u).
+    ``end_values`` float64[2] on the device: g of a Robin end (needed with one).  Bitwise reproducible; no
+    synchronisation -- reading out4 is the caller's."""
+    lib = _capi.load()
+    for nm, t in (("diag", diag), ("sub", sub), ("sup", sup), ("load", load), ("u", u), ("u_new", u_new)):
+        _dev(t, nm)
+    ne = sub.numel()
+    if ne < 1:
+        raise ValueError("need at least one element")
+    if sup.numel() != ne or any(t.dim() != 1 or t.numel() != ne + 1 for t in (diag, load, u, u_new)):
+        raise ValueError("lengths must be ne+1 (diag, load, u, u_new) and ne (sub, sup)")
+    kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
+    if end_values is not None:
+        _dev(end_values, "end_values")
+        if end_values.numel() != 2:
+            raise ValueError(f"end_values must hold 2 doubles, got {end_values.numel()}")
+    elif END_ROBIN in kinds:
+        raise ValueError("end_values (device float64[2]) is needed with a Robin end")
+    out4 = _eig_out(out4, "out4", (4,), diag)
+    need = lib.lssvr_nl_residual_work_bytes(ne)
+    if work is not None:
+        _dev(work, "work")
+        if work.numel() * work.element_size() < need:
+            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                             f"lssvr_nl_residual_work_bytes({ne}) = {need}")
+    work = _scratch(work, need, diag.device)
+    _same_device(diag, sub=sub, sup=sup, load=load, u=u, u_new=u_new, end_values=end_values, work=work)
+    rc = lib.lssvr_nl_residual(_ptr(diag), _ptr(sub), _ptr(sup), _ptr(load), _ptr(u), _ptr(u_new), kinds[0], kinds[1],
+                               _ptr(end_values), kap, ne, _ptr(out4), _ptr(work),
+                               work.numel() * work.element_size(), _stream(stream))
+    _capi.check(rc, "lssvr_nl_residual")
+    return out4
+
+
+def nl_step(u, u_new, lam, *, out=None, stream=None):
+    """``lssvr_nl_step``: out = u + lam (u_new - u), the trial point of the line search; float64[ne+1] device
+    tensors, ``out`` neither u nor u_new."""
+    lib = _capi.load()
+    _dev(u, "u")
+    _dev(u_new, "u_new")
+    (lam,) = _ts_scalars(lam=lam)
+    if u.dim() != 1 or u.numel() < 2 or u_new.shape != u.shape:
+        raise ValueError("u and u_new must be 1-D of one length ne+1 >= 2")
+    out = _eig_out(out, "out", tuple(u.shape), u)
+    if out.data_ptr() in (u.data_ptr(), u_new.data_ptr()):
+        raise ValueError("out must not be u or u_new")
+    _same_device(u, u_new=u_new)
+    _capi.check(lib.lssvr_nl_step(_ptr(u), _ptr(u_new), lam, u.numel() - 1, _ptr(out), _stream(stream)),
+                "lssvr_nl_step")
+    return out
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

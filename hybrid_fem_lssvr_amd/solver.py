@@ -38,7 +38,14 @@ somewhere, coefficients that are periodic on the interval, ``fem_solver="bands"`
 ``solve_goal``; ``None`` keeps the module's Dirichlet functions), ``element_lists`` (``True``: ``element_degrees`` and
 ``solve_adaptive(mode="hp")`` work with ``coef``, ``reaction`` and ``convection`` and every ``boundary``, one element-list
 launch of the table kernels per degree group; ``False``, the default, keeps every path as it was:
-Poisson rows, or ``boundary="periodic"`` through one whole-mesh launch per degree, anything else is refused).
+Poisson rows, or ``boundary="periodic"`` through one whole-mesh launch per degree, anything else is refused),
+``nonlinear`` (``("poly", [q0, q1, ...])``: g(x, u) = sum_k q_k(x) u^k with 1 .. 6 numpy-vectorised callables, or
+``("exp", q0, q1)``: g = q0(x) exp(q1(x) u) -- solve ``-(a u')' + b u' + c u + g(x, u) = f`` by a damped Newton
+iteration inside ``solve_fem()``; ``fem_solver`` "bands" or "pivot", Dirichlet or Robin ends, one
+degree for all elements, and no ``solve_many`` / ``solve_goal`` / ``solve_adaptive`` / ``solve_eigen`` /
+``solve_transient``; the checks of the linear problem hold for a, b, c alone, so two Neumann ends without a ``reaction``
+are refused as singular even where g_u > 0 would make every Newton matrix definite -- give such a problem a small
+``reaction`` and subtract it in q_1; ``None`` keeps every path as it was).
 """
 from __future__ import annotations
 
@@ -212,6 +219,69 @@ class _Boundary:
         the constraint row at a Robin end: their boundary flags fire for global element 0 and ne_global - 1 only."""
         off = 1 if self.kinds[0] == ops.END_ROBIN else 0
         return dict(elem_offset=off, ne_global=off + ne + (1 if self.kinds[1] == ops.END_ROBIN else 0))
+
+
+class _Nonlinear:
+    """``nonlinear=`` of the facade, parsed: ``("poly", [q0, q1, ...])`` -- g(x, u) = sum_k q_k(x) u^k, 1 .. 6 terms --
+    or ``("exp", q0, q1)`` -- g = q0(x) exp(q1(x) u); ``kind`` is the ``ops.NL_*`` id and ``q`` the list of callables.
+    ``ValueError`` for anything else."""
+
+    def __init__(self, spec):
+        if not isinstance(spec, (tuple, list)) or not spec or spec[0] not in ("poly", "exp"):
+            raise ValueError("nonlinear must be ('poly', [q0, q1, ...]) or ('exp', q0, q1), got "
+                             f"{spec!r}" if not callable(spec) else "nonlinear must be ('poly', [q0, q1, ...]) or "
+                             "('exp', q0, q1): g comes from a tabulated family, not from a callable of u")
+        if spec[0] == "poly":
+            if len(spec) != 2 or not isinstance(spec[1], (tuple, list)):
+                raise ValueError("nonlinear=('poly', [q0, q1, ...]) takes one list of callables q_k(x)")
+            q = list(spec[1])
+            if not 1 <= len(q) <= 6:
+                raise ValueError(f"nonlinear 'poly' takes 1 .. 6 terms (nterm), got {len(q)}")
+            self.kind = 0           # ops.NL_POLY (the ids are the header's; ops is not needed to refuse)
+        else:
+            if len(spec) != 3:
+                raise ValueError("nonlinear=('exp', q0, q1) takes the two callables q0(x), q1(x)")
+            q = list(spec[1:])
+            self.kind = 1           # ops.NL_EXP
+        if not all(callable(f) for f in q):
+            raise ValueError("every q_k of nonlinear must be a callable q_k(x)")
+        self.q = q
+
+    def host_tables(self, pts, what):
+        """[nterm, *pts.shape] float64 on the host: every q_k at ``pts``; ``ValueError`` for a q_k that does not return
+        one value per point (or one that broadcasts) or is not finite there."""
+        out = []
+        for k, fn in enumerate(self.q):
+            try:
+                t = np.broadcast_to(np.asarray(fn(pts), dtype=np.float64), pts.shape)
+            except ValueError:
+                raise ValueError(f"nonlinear q_{k} must return one value per point ({list(pts.shape)} at the {what} "
+                                 "points) or a value that broadcasts to them") from None
+            if not np.all(np.isfinite(t)):
+                raise ValueError(f"nonlinear q_{k} is not finite at a {what} point")
+            out.append(t)
+        return np.stack(out)
+
+    def tables(self, pts, what, point_major=False):
+        """Device tables [nterm, ne, k] (``point_major``: [nterm, k, ne]) of the q_k at the device points [ne, k],
+        after the checks of :meth:`host_tables` at those very points (``what`` names them in the message)."""
+        t = self.host_tables(pts.cpu().numpy(), what)
+        return _to_dev(np.transpose(t, (0, 2, 1)) if point_major else t, pts.device)
+
+
+class NewtonReport:
+    """What the Newton iteration of ``solve_fem()`` with ``nonlinear=`` leaves in ``solver.newton``: ``iterations``
+    (linear solves), ``residuals[i]`` = |R(u_i)|_inf and ``steps[i]`` = |u_new - u_i|_inf of iteration i + 1,
+    ``lambdas[i]`` the damping it took, ``converged``.  It is assigned before the first iteration and filled as the
+    loop runs, so it also holds the history of a solve that raised."""
+
+    def __init__(self):
+        self.iterations, self.residuals, self.steps, self.lambdas, self.converged = 0, [], [], [], False
+
+    def __str__(self):
+        return (f"{self.iterations} iteration(s), converged={self.converged}, residuals "
+                f"{[f'{v:.3e}' for v in self.residuals]}, steps {[f'{v:.3e}' for v in self.steps]}, lambdas "
+                f"{self.lambdas}")
 
 
 def _enhance(x, u, M, gamma, n_colloc, *, global_domain, bc, solver, uniform_rtol=1e-9, **kw):
@@ -446,7 +516,7 @@ class FEMLSSVRPrimalSolver:
     def __init__(self, num_fem_nodes=5, lssvr_M=12, lssvr_gamma=1e6, global_domain=(-1, 1), *,
                  n_colloc=12, rhs=poisson_rhs, nquad=2, mesh=None, device="cuda:0",
                  solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None, convection=None,
-                 boundary=None, element_lists=False):
+                 boundary=None, element_lists=False, nonlinear=None):
         # Dual.py:101-108
         self.num_fem_nodes = num_fem_nodes
         self.lssvr_M = lssvr_M
@@ -517,6 +587,24 @@ class FEMLSSVRPrimalSolver:
         # one degree per element (element_degrees, solve_adaptive(mode="hp")) for coef / reaction / convection with any
         # boundary, through the element lists of the table kernels; False: every path as it was
         self.element_lists = bool(element_lists)
+        # -(a u')' + b u' + c u + g(x, u) = f by a damped Newton iteration; None: every path as
+        # it was
+        if nonlinear is not None:
+            _Nonlinear(nonlinear)
+            if fem_solver == "flux":
+                raise ValueError("nonlinear needs fem_solver='bands' or 'pivot': every Newton step carries the mass "
+                                 "matrix of c + g_u, which the flux solve does not hold")
+            if isinstance(boundary, str) and boundary == "periodic":
+                raise ValueError("nonlinear has no boundary='periodic': the Newton loop runs the solves with "
+                                 "Dirichlet or Robin ends")
+            if solver != ops.SOLVER_PRIMAL:
+                raise ValueError("nonlinear needs solver=ops.SOLVER_PRIMAL: the linearised rows are reaction rows, "
+                                 "which have a primal solve only")
+            if self.element_lists:
+                raise ValueError("nonlinear has no element_lists / element_degrees: the linearised tables are "
+                                 "written for one degree")
+        self.nonlinear = nonlinear
+        self.newton = None              # NewtonReport after solve_fem() with nonlinear
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
         self.dual = None                # EnhancedSolution of the dual problem after solve_goal
@@ -652,24 +740,30 @@ class FEMLSSVRPrimalSolver:
         else:
             fq = _to_dev(rhs(xq.cpu().numpy()), x.device)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
+        return m, x, self._p1_solve(bands, "b_quad" in kw, u0, u1), bands
+
+    def _p1_solve(self, bands, conv, u0, u1):
+        """u device [ne+1] of the assembled ``bands`` with the end values ``u0``, ``u1`` for the configured ends and
+        ``fem_solver``; ``conv``: the bands are the non-symmetric ones (sub, sup).  The one dispatch behind
+        :meth:`_fem` and the Newton steps of :meth:`_solve_fem_newton`."""
         bnd = self._bnd
         if self.fem_solver == "pivot":
             u = self._pivot_solve(bands, bands["load"], (u0, u1), False)
         elif self._periodic:
             # node ne is node 0: the cyclic solve reads no end value (_check_periodic has run)
-            if "b_quad" in kw:
+            if conv:
                 u = ops.tridiag_ns_periodic_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"])
             else:
                 u = ops.tridiag_periodic_solve(bands["diag"], bands["off"], bands["load"])
         elif bnd is not None:
             # a Neumann or Robin end stays an unknown; kappa and g join its row inside the solve (_check_boundary has
             # run, and with convection _convection_quad)
-            if "b_quad" in kw:
+            if conv:
                 u = ops.tridiag_ns_bc_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], bnd.kinds,
                                             bnd.kappa, (u0, u1))
             else:
                 u = ops.tridiag_bc_solve(bands["diag"], bands["off"], bands["load"], bnd.kinds, bnd.kappa, (u0, u1))
-        elif "b_quad" in kw:
+        elif conv:
             # no pivoting and no stabilisation: _convection_quad has checked the cell Peclet number
             u = ops.tridiag_ns_dirichlet_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], u0, u1)
         elif self.fem_solver == "flux":
@@ -682,7 +776,7 @@ class FEMLSSVRPrimalSolver:
             # here (the reference negates both forms, Dual.py:117-124: -K u = -b; this code
             # assembles +K u = +b, the same u)
             u = ops.tridiag_dirichlet_solve(bands["diag"], bands["off"], bands["load"], u0, u1)
-        return m, x, u, bands
+        return u
 
     def _fem_many(self, rhs_list, bc):
         """(x device, U device [ncases, ne+1]) of the P1 solves of :meth:`solve_many`: what ``_fem`` per case returns,
@@ -778,11 +872,23 @@ class FEMLSSVRPrimalSolver:
         return _to_dev(bq, x.device)
 
     # ---- Dual.py:110-137 --------------------------------------------------------------
-    def solve_fem(self):
+    def solve_fem(self, *, u_init=None, tol=None, max_iter=None):
         """P1 finite-element solve: mesh, element-local assembly, Dirichlet on all
         boundary dofs, tridiagonal solve, nodal values.  Returns ``(u_fem, basis)``
-        like the reference (``basis`` is scikit-fem shaped, see ``mesh.py``)."""
-        m, x, u, bands = self._fem(self.rhs, *self._gd_bc()[1])
+        like the reference (``basis`` is scikit-fem shaped, see ``mesh.py``).
+
+        With ``nonlinear=`` the solve is a damped Newton iteration from ``u_init`` (a callable
+        sampled at the nodes; ``None``: zeros; Dirichlet ends start at their values) until
+        |u_new - u|_inf <= ``tol`` max(1, |u_new|_inf) (default 1e-12), at most ``max_iter`` (default 30) linear
+        solves; ``RuntimeError`` when it does not converge or meets a non-finite value; the report is ``self.newton``.
+        Without ``nonlinear`` the three keywords must be left alone."""
+        if self.nonlinear is None:
+            if u_init is not None or tol is not None or max_iter is not None:
+                raise ValueError("u_init, tol and max_iter belong to the Newton iteration of nonlinear=")
+            m, x, u, bands = self._fem(self.rhs, *self._gd_bc()[1])
+        else:
+            m, x, u, bands = self._solve_fem_newton(u_init, 1e-12 if tol is None else tol,
+                                                    30 if max_iter is None else max_iter)
         basis = P1Basis(m)
         self.bands = bands
         self._x_dev, self._u_dev = x, u
@@ -790,6 +896,144 @@ class FEMLSSVRPrimalSolver:
         self.fem_nodes = m.p[0]
         self.fem_values = u_fem.copy()
         return u_fem, basis
+
+    # ---- semilinear problems (no reference counterpart) ----------------------------------
+    def _check_nonlinear(self, what=None):
+        """The parsed ``nonlinear`` after the checks that need no device; ``what``: a method that has no semilinear
+        form (``ValueError``)."""
+        if what is not None:
+            if self.nonlinear is not None:
+                raise ValueError(f"{what} has no semilinear form: nonlinear= is solved by solve_fem() / solve() only")
+            return None
+        nl = _Nonlinear(self.nonlinear)
+        if self.fem_solver == "flux" or self._periodic or self.solver_id != ops.SOLVER_PRIMAL:      # (public attributes)
+            raise ValueError("nonlinear needs fem_solver='bands' or 'pivot', Dirichlet or Robin ends and "
+                             "solver=ops.SOLVER_PRIMAL")
+        if self.element_lists or self.element_degrees is not None:
+            raise ValueError("nonlinear has no element_lists / element_degrees: the linearised tables are written for "
+                             "one degree")
+        return nl
+
+    def _nl_host_points(self, nodes):
+        """The host's copy of the points the q_k are checked at before any device call: the Gauss points of the
+        assembly and the collocation points."""
+        xi = 0.5 * (1.0 + np.polynomial.legendre.leggauss(int(self.nquad))[0])
+        xq = nodes[:-1, None] + np.diff(nodes)[:, None] * xi[None, :]
+        return xq, np.linspace(nodes[:-1], nodes[1:], int(self.n_colloc), axis=-1)
+
+    def _solve_fem_newton(self, u_init, tol, max_iter, max_halvings=8):
+        """(mesh, x device, u device, bands of the last Newton step) of the damped Newton iteration.
+
+        Once: the bands K of a, b, c by the existing assembly, and f, c and the q_k at the quadrature points.  One
+        iteration: ``ops.nl_linearize`` -> ONE ``ops.p1_assemble`` with c_quad = c_eff and rhs_quad = f_eff -> the
+        solve of :meth:`_p1_solve` gives u_new.  The merit function |R(v)|_inf, R(v) = K v + G(v) - F, costs
+        ``ops.nl_linearize`` (f_res only) -> ``ops.p1_load_multi`` -> ``ops.nl_residual``, and reading its four
+        numbers is the loop's synchronisation.  The stop test |u_new - u| <= tol max(1, |u_new|) comes first; otherwise
+        lambda = 1, 1/2, ... (at most ``max_halvings`` halvings) until |R(u + lambda d)| <= (1 - 1e-4 lambda) |R(u)|,
+        else the tried lambda with the smallest residual."""
+        torch = _torch()
+        nl = self._check_nonlinear()
+        if not (float(tol) > 0.0) or not math.isfinite(float(tol)):
+            raise ValueError(f"tol must be finite and > 0, got {tol!r}")
+        if isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 1:
+            raise ValueError(f"max_iter must be an integer >= 1, got {max_iter!r}")
+        if u_init is not None and not callable(u_init):
+            raise ValueError("u_init must be a callable u_init(x) or None")
+        tol, max_iter = float(tol), int(max_iter)
+        m = self._default_mesh() if self.mesh is None else self.mesh
+        nodes = np.asarray(m.nodes, dtype=np.float64)
+        ne = nodes.size - 1
+        xq_host, xc_host = self._nl_host_points(nodes)
+        nl.host_tables(xq_host, "quadrature")
+        if int(self.n_colloc) >= 2:
+            nl.host_tables(xc_host, "collocation")
+        u0, u1 = self._gd_bc()[1]
+        bnd = self._bnd
+        kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (tuple(bnd.kinds), tuple(bnd.kappa))
+        start = np.zeros(ne + 1) if u_init is None else \
+            np.array(np.broadcast_to(np.asarray(u_init(nodes), dtype=np.float64), nodes.shape))
+        for i, (end, g) in enumerate(((0, u0), (-1, u1))):
+            if kinds[i] == ops.END_DIRICHLET:
+                start[end] = g
+        if not np.all(np.isfinite(start)):
+            raise ValueError("u_init is not finite at a node")
+        # ---- the device from here on
+        _, x, xq, kw = self._fem_setup()
+        dev = x.device
+        conv = "b_quad" in kw
+        eq = self._eq
+        fq = _tabulate(eq.f, xq)
+        cq = kw.get("c_quad")
+        qq = nl.tables(xq, "quadrature")
+        zq = torch.zeros_like(xq)
+        K = ops.p1_assemble(x, self.nquad, rhs_quad=zq, **kw)
+        ksub, ksup = (K["sub"], K["sup"]) if conv else (K["off"], K["off"])
+        t = ops.quad_points(_to_dev([0.0, 1.0], dev), self.nquad)[0].contiguous()     # the rule's points on [0, 1]
+        ends = _to_dev([u0, u1], dev)
+        u = _to_dev(start, dev)
+        c_eff, f_eff, f_res = (torch.empty_like(xq) for _ in range(3))
+        step_kw = {k: v for k, v in kw.items() if k != "c_quad"}
+        bands = None
+        load = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
+        out4 = torch.empty(4, dtype=torch.float64, device=dev)
+        trial = torch.empty_like(u)
+        work = ops._scratch(None, ops._capi.load().lssvr_nl_residual_work_bytes(ne), dev)
+
+        def merit(v, v_new):
+            """(|R(v)|, |v_new - v|, |v_new|) by one read of out4; ``RuntimeError`` at a non-finite entry."""
+            ops.nl_linearize(v, t, nl.kind, qq, fq, c_tab=cq, c_eff=None, f_eff=None, f_res=f_res)
+            ops.p1_load_multi(x, f_res.unsqueeze(0), self.nquad, out=load)
+            ops.nl_residual(K["diag"], ksub, ksup, load[0], v, v_new, kinds, kappa, ends, out4=out4, work=work)
+            r, du, un, bad = (float(w) for w in out4.cpu().numpy())
+            if bad:
+                raise RuntimeError(f"the Newton iteration met {int(bad)} non-finite value(s) in the residual or the "
+                                   f"iterate; so far: {rep}")
+            return r, du, un
+
+        rep = self.newton = NewtonReport()
+        for it in range(1, max_iter + 1):
+            ops.nl_linearize(u, t, nl.kind, qq, fq, c_tab=cq, c_eff=c_eff, f_eff=f_eff, f_res=None)
+            if self.fem_solver != "pivot" and bool((c_eff < 0).any().item()):
+                raise ValueError(f"c + g_u is negative at a quadrature point in Newton iteration {it}: the tridiagonal "
+                                 "solve does not pivot and assumes an SPD matrix; use fem_solver=\"pivot\"")
+            bands = ops.p1_assemble(x, self.nquad, rhs_quad=f_eff, c_quad=c_eff, out=bands, **step_kw)
+            u_new = self._p1_solve(bands, conv, u0, u1)
+            r0, du, un = merit(u, u_new)
+            rep.iterations = it
+            rep.residuals.append(r0)
+            rep.steps.append(du)
+            if du <= tol * max(1.0, un):
+                u = u_new
+                rep.lambdas.append(1.0)
+                rep.converged = True
+                break
+            lam, tried = 1.0, []
+            for _ in range(int(max_halvings) + 1):
+                v = u_new if lam == 1.0 else ops.nl_step(u, u_new, lam, out=trial)
+                rv = merit(v, v)[0]
+                tried.append((rv, lam))
+                if rv <= (1.0 - 1e-4 * lam) * r0:
+                    break
+                lam *= 0.5
+            else:
+                rv, lam = min(tried, key=lambda p: p[0])
+                v = u_new if lam == 1.0 else ops.nl_step(u, u_new, lam, out=trial)
+            u = v.clone()
+            rep.lambdas.append(lam)
+        if not rep.converged:
+            raise RuntimeError(f"the Newton iteration did not converge in {max_iter} iteration(s) to tol = {tol:g}: "
+                               f"{rep}")
+        return m, x, u, bands
+
+    def _nl_tables(self, pts, what, t_local, point_major, u):
+        """(a, a' - b, f_eff, c_eff) at the device points ``pts`` [ne, k] with the local coordinates ``t_local`` [k]:
+        the tables of the LINEAR problem that the enhancement and the indicator see, ONE ``ops.nl_linearize`` around
+        the P1 interpolant of the nodal values ``u``."""
+        nl = self._check_nonlinear()
+        ta, tda, tf, tc = self._eq.tables(pts, point_major)
+        lin = ops.nl_linearize(u, t_local, nl.kind, nl.tables(pts, what, point_major), tf, c_tab=tc,
+                               point_major=point_major)
+        return ta, tda, lin["f_eff"], lin["c_eff"]
 
     # ---- one degree per element (no reference counterpart: Dual.py:101 has one lssvr_M) ----
     def _check_hp(self, what):
@@ -919,7 +1163,16 @@ class FEMLSSVRPrimalSolver:
             raise ValueError("boundary='periodic' needs a per-element solver, not ops.SOLVER_SHARED")
         shard = self._shard(nodes.size - 1)
         degrees = None
-        if self.element_degrees is not None:
+        if self.nonlinear is not None:
+            # the linear problem around the P1 interpolant of u: c_eff = c + g_u, f_eff = f - g + g_u u_h
+            self._check_nonlinear()
+            if n < 2 or n > ops.NL_MAX_POINTS:
+                raise ValueError(f"nonlinear needs 2 <= n_colloc <= {ops.NL_MAX_POINTS}, got {n}")
+            t = _torch().arange(n, dtype=_torch().float64, device=dev) / float(n - 1)
+            ta, tda, tf, tc = self._nl_tables(ops.colloc_points(x, n), "collocation", t, pm, u)
+            W, st = ops.enhance_varcoef(x, u, M, gamma, n, ta, tda, tf, global_domain=gd, bc=bc, point_major=pm,
+                                        c_values=tc, **shard)
+        elif self.element_degrees is not None:
             degrees = self._check_degrees(nodes.size - 1)
             by_degree = self._enhance_by_degree_tables if self._periodic else self._enhance_by_degree
             if self.element_lists and not eq.poisson:
@@ -949,9 +1202,9 @@ class FEMLSSVRPrimalSolver:
                 print(f"... and {nbad - 10} more elements")
 
     # ---- Dual.py:171-174 --------------------------------------------------------------
-    def solve(self):
-        """Complete solution: FEM + LSSVR."""
-        self.solve_fem()
+    def solve(self, **newton):
+        """Complete solution: FEM + LSSVR.  ``newton``: the keywords of :meth:`solve_fem` (``nonlinear=`` only)."""
+        self.solve_fem(**newton)
         self.solve_lssvr_subproblems()
 
     def solve_many(self, rhs_list, bc=None):
@@ -962,6 +1215,7 @@ class FEMLSSVRPrimalSolver:
         Robin end of ``boundary`` the entry is that case's g; the kinds and kappa belong to the matrix and are shared
         (``boundary="periodic"`` has no end values: ``bc`` must be ``None``).  Returns a list of :class:`EnhancedSolution`, one per case; ``rhs``, ``fem_values``, ``enhanced`` and
         the other attributes of the solver are left as they are.  Without ``coef`` the tables hold a = 1, a' = 0."""
+        self._check_nonlinear("solve_many")
         return self._solve_many(rhs_list, bc)[0]
 
     def _solve_many(self, rhs_list, bc):
@@ -1052,6 +1306,7 @@ class FEMLSSVRPrimalSolver:
         per element by the reaction rows with the table c - theta_j rho (``lssvr_M``, ``n_colloc``, ``lssvr_gamma``,
         ``element_degrees``), and its Rayleigh quotient, by ``nq``-point Gauss, is the enhanced eigenvalue.  Returns
         an :class:`EigenSolution`."""
+        self._check_nonlinear("solve_eigen")
         torch = _torch()
         m, nodes, kinds, kappa, unknowns = self._check_eigen(k, sigma, weight, tol, max_iter, check_every)
         k, sigma, ne = int(k), float(sigma), nodes.size - 1
@@ -1299,6 +1554,7 @@ class FEMLSSVRPrimalSolver:
         ``ops.enhance_multi`` (``lssvr_M``, ``n_colloc``, ``lssvr_gamma``; c itself, not shifted by 1 / dt).  Two
         Neumann ends without a reaction are fine here: M / dt makes the matrix definite.  Returns a
         :class:`TransientSolution`; the solver's attributes are left as they are."""
+        self._check_nonlinear("solve_transient")
         torch = _torch()
         p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, bool(enhance))
         nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
@@ -1381,7 +1637,13 @@ class FEMLSSVRPrimalSolver:
             raise RuntimeError("call solve() first")
         x, W = self.enhanced.nodes, self.enhanced.W
         eq = self._eq
-        if eq.poisson:
+        if self.nonlinear is not None:
+            # the residual of the linear problem around the P1 interpolant of the nodal values
+            u = _to_dev(self.fem_values, x.device)
+            t = ops.estimate_points(_to_dev([0.0, 1.0], x.device), nq)[0].contiguous()
+            ta, tda, tf, tc = self._nl_tables(ops.estimate_points(x, nq), "residual-indicator", t, True, u)
+            eta2, _, out3 = ops.estimate_varcoef(x, W, nq, ta, tda, tf, eq.a_ends(x), point_major=True, c_values=tc)
+        elif eq.poisson:
             eta2, _, out3 = ops.estimate(x, W, nq, **_rhs_mode(eq.f, lambda: ops.estimate_points(x, nq)))
         else:
             # a, a', f (, c) at the Gauss points, point-major (coalesced); a at the nodes from both sides, aL = aR
@@ -1453,6 +1715,7 @@ class FEMLSSVRPrimalSolver:
         sum eta_e, ``corrected`` = their sum -- the enhanced solution is continuous and takes the Dirichlet values, so
         sum eta_e = J(u) - J(u_enh) up to the error of the dual solution and of the ``nq``-point rule on R z: the
         correction is only as good as that rule resolves f."""
+        self._check_nonlinear("solve_goal")
         return self._solve_goal(goal, nq)[0]
 
     def _solve_goal(self, goal, nq):
@@ -1576,6 +1839,7 @@ class FEMLSSVRPrimalSolver:
         correction |sum eta_e|, so cancellation between elements cannot stop the loop early -- and is what ``tol``
         is compared with and what is returned; ``adapt_history`` holds dict(ne, estimate, correction, value, marked)
         per round, value = J(u_enh) and correction = sum eta_e on that round's mesh."""
+        self._check_nonlinear("solve_adaptive")
         if mode not in ("h", "hp"):
             raise ValueError(f"mode must be 'h' or 'hp', got {mode!r}")
         if goal is not None:

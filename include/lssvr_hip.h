@@ -1057,6 +1057,72 @@ int lssvr_ts_source_table_host(const double* U2_host, const double* U0_host, con
                                int n_colloc, int R, int table_layout, double alpha, double beta0, double beta1,
                                double inv_dt, double* out_host);
 
+/*
+ * Semilinear problems: -(a u')' + b u' + c u + g(x, u) = f by a damped Newton iteration (no reference counterpart;
+ * DESIGN.md section 27).  ADDITIVE to ABI 7: seven new symbols and two constants, no existing entry, struct, constant
+ * or kernel changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * One Newton step from the nodal iterate u is the LINEAR problem with the reaction c + g_u(x, u_h) and the right-hand
+ * side f - g(x, u_h) + g_u(x, u_h) u_h, u_h the P1 interpolant of u, solved for the new iterate itself: lssvr_nl_linearize
+ * at the quadrature points writes those two tables, lssvr_p1_assemble_react / _conv assembles them and any of the
+ * lssvr_tridiag_*_solve_multi entries solves, with the boundary conditions of the linear problem.  The merit function
+ * is |R(v)|_inf, R(v) = K v + G(v) - F with K the bands of a, b, c: lssvr_nl_linearize (f_res only), lssvr_p1_load_multi
+ * (one case) and lssvr_nl_residual.  Nothing here synchronises or copies; no atomics: bitwise reproducible.
+ *
+ * g comes from a tabulated family, q_tabs = [nterm] tables stacked, each of ne * n doubles in the layout of the call:
+ *   LSSVR_NL_POLY  g(x, u) = sum_{k < nterm} q_k(x) u^k, 1 <= nterm <= 6.  With K = nterm - 1, by Horner:
+ *                  g = q_K, then g = g u + q_k for k = K-1 .. 0;  g_u: d = (double)K q_K, then d = d u + (double)k q_k
+ *                  for k = K-1 .. 1;  nterm = 1: g_u = 0.
+ *   LSSVR_NL_EXP   g(x, u) = q_0(x) exp(q_1(x) u), nterm = 2:  E = exp(q_1 u), g = q_0 E, g_u = (q_0 q_1) E.
+ *
+ * lssvr_nl_linearize -- for the n points (1 <= n <= 64) of every element, a thread per table entry (e, k) in memory
+ * order, either LSSVR_TABLE_* layout:
+ *   u_h = u_e + (u_{e+1} - u_e) t_local[k],
+ *   c_eff(e, k) = c + g_u,   f_eff(e, k) = (f - g) + g_u u_h,   f_res(e, k) = f - g,
+ * g and g_u at (point, u_h) as above.  u [ne+1], t_local [n] (the local coordinates in [0, 1] of the points: the rule
+ * of lssvr_quad_points, k / (n - 1) for lssvr_colloc_points(_pm), the Gauss points of lssvr_estimate_points), q_tabs,
+ * c_tab (NULL: c = 0) and f_tab are DEVICE arrays; an output that is NULL is not written, at least one must be given.
+ * No output may alias an input.  Return codes: an unknown kind is LSSVR_ERR_RHS (the family of g is data of the
+ * right-hand side, like rhs_id); nterm outside the kind's range, n outside [1, 64], ne < 1, an unknown table_layout and
+ * aliased arguments are LSSVR_ERR_SIZE; a missing pointer, or no output at all, is LSSVR_ERR_NULL.
+ *
+ * lssvr_nl_residual -- out4 (DEVICE, four doubles) = { max_i |r_i|, max_i |u_new_i - u_i|, max_i |u_new_i|, the count of
+ * entries among the 3 (ne + 1) that are not finite } for the bands diag [ne+1], sub [ne], sup [ne] of the linear
+ * operator (a symmetric caller passes off twice), load = F - G(u) [ne+1], u and u_new [ne+1]:
+ *   r_i = ((sub[i-1] u[i-1] + diag[i] u[i]) + sup[i] u[i+1]) - load[i]     (rows 0 and ne: the term of the missing
+ *   neighbour is left out);  at a LSSVR_END_ROBIN end  r_i = r_i + (kappa u_i - g),  g = end_values[end] (DEVICE array
+ * of two doubles; may be NULL with two Dirichlet ends);  at a LSSVR_END_DIRICHLET end  r_i = 0.  kappa_host[2]: host
+ * array, finite, either sign.  An entry that is not finite raises the count and joins no maximum.  Per-workgroup
+ * partials go to work (DEVICE, work_bytes >= lssvr_nl_residual_work_bytes(ne)), a second launch of one workgroup
+ * merges them: a maximum of finite numbers does not depend on the order, and the count is a sum of integers in a fixed
+ * tree, so out4 is bitwise reproducible.
+ *
+ * lssvr_nl_step -- out_i = u_i + lambda (u_new_i - u_i), i = 0 .. ne, lambda finite; u, u_new and out are DEVICE arrays [ne+1], and
+ * out must be neither u nor u_new.
+ *
+ * lssvr_nl_linearize_host, lssvr_nl_residual_host, lssvr_nl_step_host -- the same routines on HOST arrays: no device
+ * is touched.  Bit for bit the device's values, except that exp of LSSVR_NL_EXP is the host's libm there.
+ */
+#define LSSVR_NL_POLY 0
+#define LSSVR_NL_EXP 1
+int lssvr_nl_linearize(const double* u, const double* t_local, const double* q_tabs, const double* c_tab,
+                       const double* f_tab, int64_t ne, int n, int table_layout, int kind, int nterm,
+                       double* c_eff, double* f_eff, double* f_res, void* stream);
+int lssvr_nl_linearize_host(const double* u_host, const double* t_local_host, const double* q_tabs_host,
+                            const double* c_tab_host, const double* f_tab_host, int64_t ne, int n, int table_layout,
+                            int kind, int nterm, double* c_eff_host, double* f_eff_host, double* f_res_host);
+int64_t lssvr_nl_residual_work_bytes(int64_t ne);
+int lssvr_nl_residual(const double* diag, const double* sub, const double* sup, const double* load, const double* u,
+                      const double* u_new, int kind_left, int kind_right, const double* end_values,
+                      const double* kappa_host, int64_t ne, double* out4, void* work, int64_t work_bytes,
+                      void* stream);
+int lssvr_nl_residual_host(const double* diag_host, const double* sub_host, const double* sup_host,
+                           const double* load_host, const double* u_host, const double* u_new_host, int kind_left,
+                           int kind_right, const double* end_values_host, const double* kappa_host, int64_t ne,
+                           double* out4_host);
+int lssvr_nl_step(const double* u, const double* u_new, double lambda, int64_t ne, double* out, void* stream);
+int lssvr_nl_step_host(const double* u_host, const double* u_new_host, double lambda, int64_t ne, double* out_host);
+
 #ifdef __cplusplus
 }
 #endif
