@@ -863,43 +863,6 @@ int lssvr_quad_points(const double* x, int64_t ne, int nquad, double* xq, void* 
                       "quad_points");
 }
 
-// one solver and one workspace formula behind both pairs of entries (tridiag.hip)
-int64_t lssvr_tridiag_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }
-int64_t lssvr_tridiag_ns_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }
-
-// The four entries.  sup == NULL: a symmetric entry, whose one band `off` arrives as sub.  The single-RHS entries are
-// nc = 1 with the end values u0, u1 by value (bc NULL); they have no work_bytes argument, and only the multi entries
-// check it.
-static int tridiag_solve(const double* diag, const double* sub, const double* sup, const double* load, int64_t ne,
-                         int nc, const double* bc, double u0, double u1, double* u, void* work, int64_t work_bytes,
-                         void* stream, bool sym, bool multi) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
-  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
-    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
-  const int64_t need = lssvr::tridiag_multi_work_bytes(ne, nc);
-  if (multi && work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_multi_work_bytes(%lld, %d) = %lld",
-                (long long)work_bytes, (long long)ne, nc, (long long)need);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (sym)
-    return check_launch(lssvr::tridiag_dirichlet_solve(diag, sub, load, ne, nc, bc, u0, u1, u, work, st),
-                        multi ? "tridiag_dirichlet_solve_multi" : "tridiag_dirichlet_solve");
-  return check_launch(lssvr::tridiag_ns_dirichlet_solve(diag, sub, sup, load, ne, nc, bc, u0, u1, u, work, st),
-                      multi ? "tridiag_ns_dirichlet_solve_multi" : "tridiag_ns_dirichlet_solve");
-}
-
-int lssvr_tridiag_dirichlet_solve(const double* diag, const double* off, const double* load,
-                                  int64_t ne, double u0, double u1, double* u, void* work,
-                                  void* stream) {
-  return tridiag_solve(diag, off, nullptr, load, ne, 1, nullptr, u0, u1, u, work, 0, stream, true, false);
-}
-
-int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
-                                     int64_t ne, double u0, double u1, double* u, void* work, void* stream) {
-  return tridiag_solve(diag, sub, sup, load, ne, 1, nullptr, u0, u1, u, work, 0, stream, false, false);
-}
-
 // several load cases on one mesh: the loads in one launch, the solves with the bands read once per pass
 int lssvr_p1_load_multi(const double* x, int64_t ne, int nquad, const double* rhs_quad, int nc, double* load,
                         void* stream) {
@@ -911,22 +874,23 @@ int lssvr_p1_load_multi(const double* x, int64_t ne, int nquad, const double* rh
                       "p1_load_multi");
 }
 
+// The tridiagonal solves (tridiag.hip, tridiag_pivot.hip).  One row per family holds what its entries check before they
+// launch (the table of DESIGN.md section 19 and of ops._TRIDIAG): the fewest elements and what follows "ne = .. <
+// ne_min" in the message, the public sizer the "work holds" message names, whether a Robin kappa may have either sign.
+struct TriFamily { int ne_min; const char* ne_why; const char* sizer; int64_t (*need)(int64_t, int); bool any_sign; };
+#define TRI_SIZER(f) "lssvr_" #f, lssvr::f
+static const TriFamily kTriDirichlet = {1, "", TRI_SIZER(tridiag_multi_work_bytes), false};
+static const TriFamily kTriBc = {1, "", TRI_SIZER(tridiag_bc_work_bytes), false};
+static const TriFamily kTriPivot = {1, "", TRI_SIZER(tridiag_pivot_work_bytes), true};
+static const TriFamily kTriPeriodic = {2, ": a periodic mesh has at least two elements",
+                                       TRI_SIZER(tridiag_periodic_work_bytes), false};
+
+int64_t lssvr_tridiag_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }       // (the multi formula, nc = 1)
+int64_t lssvr_tridiag_ns_work_bytes(int64_t ne) { return lssvr::tridiag_work_bytes(ne); }
 int64_t lssvr_tridiag_multi_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_multi_work_bytes(ne, nc); }
-
-int lssvr_tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne, int nc,
-                                        const double* bc_values, double* u, void* work, int64_t work_bytes,
-                                        void* stream) {
-  return tridiag_solve(diag, off, nullptr, load, ne, nc, bc_values, 0.0, 0.0, u, work, work_bytes, stream, true, true);
-}
-
-int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
-                                           const double* load, int64_t ne, int nc, const double* bc_values, double* u,
-                                           void* work, int64_t work_bytes, void* stream) {
-  return tridiag_solve(diag, sub, sup, load, ne, nc, bc_values, 0.0, 0.0, u, work, work_bytes, stream, false, true);
-}
-
-// Free ends: Dirichlet or Robin at each end (tridiag.hip).  sup == NULL: the symmetric entry, `off` arrives as sub.
 int64_t lssvr_tridiag_bc_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_bc_work_bytes(ne, nc); }
+int64_t lssvr_tridiag_pivot_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_pivot_work_bytes(ne, nc); }
+int64_t lssvr_tridiag_periodic_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_periodic_work_bytes(ne, nc); }
 
 // (any_sign: the pivoting solve takes a kappa of either sign)
 static int check_end_kinds(int kind_left, int kind_right, const double* kappa_host, bool any_sign = false) {
@@ -945,27 +909,85 @@ static int check_end_kinds(int kind_left, int kind_right, const double* kappa_ho
   return LSSVR_OK;
 }
 
+// Two free ends as an entry gets them and, once tridiag_check has checked them, as the launchers take them: f = the end
+// is a Robin end, k = its kappa (0 at a Dirichlet end, whose kappa is not read).
+struct TriEnds { int kind_left, kind_right; const double* kappa_host; bool f0, f1; double k0, k1; };
+enum TriWork { kTriNoWork, kTriWorkUnsized, kTriWorkSized };
+
+// What every tridiagonal entry checks before it launches, in this order: ne, nc, the NULL list (sup == NULL: a symmetric
+// entry, whose one band `off` arrives as sub), the end kinds (`ends` given), work_bytes against the family's sizer.
+// kTriWorkUnsized: the single-RHS Dirichlet entries, which have no work_bytes argument; kTriNoWork: the host entry.
+static int tridiag_check(const TriFamily& fam, bool sym, const double* diag, const double* sub, const double* sup,
+                         const double* load, int64_t ne, int nc, const double* u, TriWork mode, const void* work,
+                         int64_t work_bytes, TriEnds* ends = nullptr) {
+  if (ne < fam.ne_min) return fail(LSSVR_ERR_SIZE, "ne = %lld < %d%s", (long long)ne, fam.ne_min, fam.ne_why);
+  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
+  if (!diag || !sub || (!sym && !sup) || !load || !u || (mode != kTriNoWork && !work))
+    return fail(LSSVR_ERR_NULL, "diag, %s, load, u%s must be non-NULL", sym ? "off" : "sub, sup",
+                mode != kTriNoWork ? ", work" : "");
+  if (ends) {
+    const int rc = check_end_kinds(ends->kind_left, ends->kind_right, ends->kappa_host, fam.any_sign);
+    if (rc != LSSVR_OK) return rc;
+    ends->f0 = ends->kind_left == LSSVR_END_ROBIN, ends->f1 = ends->kind_right == LSSVR_END_ROBIN;
+    ends->k0 = ends->f0 ? ends->kappa_host[0] : 0.0, ends->k1 = ends->f1 ? ends->kappa_host[1] : 0.0;
+  }
+  if (mode == kTriWorkSized && work_bytes < fam.need(ne, nc))
+    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, %s(%lld, %d) = %lld", (long long)work_bytes, fam.sizer,
+                (long long)ne, nc, (long long)fam.need(ne, nc));
+  return LSSVR_OK;
+}
+
+// Two Dirichlet ends.  The single-RHS entries are nc = 1 with the end values u0, u1 by value (bc NULL).
+static int tridiag_solve(const double* diag, const double* sub, const double* sup, const double* load, int64_t ne,
+                         int nc, const double* bc, double u0, double u1, double* u, void* work, int64_t work_bytes,
+                         void* stream, bool sym, bool multi) {
+  const int rc = tridiag_check(kTriDirichlet, sym, diag, sub, sup, load, ne, nc, u,
+                               multi ? kTriWorkSized : kTriWorkUnsized, work, work_bytes);
+  if (rc != LSSVR_OK) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (sym)
+    return check_launch(lssvr::tridiag_dirichlet_solve(diag, sub, load, ne, nc, bc, u0, u1, u, work, st),
+                        multi ? "tridiag_dirichlet_solve_multi" : "tridiag_dirichlet_solve");
+  return check_launch(lssvr::tridiag_ns_dirichlet_solve(diag, sub, sup, load, ne, nc, bc, u0, u1, u, work, st),
+                      multi ? "tridiag_ns_dirichlet_solve_multi" : "tridiag_ns_dirichlet_solve");
+}
+
+int lssvr_tridiag_dirichlet_solve(const double* diag, const double* off, const double* load, int64_t ne, double u0,
+                                  double u1, double* u, void* work, void* stream) {
+  return tridiag_solve(diag, off, nullptr, load, ne, 1, nullptr, u0, u1, u, work, 0, stream, true, false);
+}
+
+int lssvr_tridiag_ns_dirichlet_solve(const double* diag, const double* sub, const double* sup, const double* load,
+                                     int64_t ne, double u0, double u1, double* u, void* work, void* stream) {
+  return tridiag_solve(diag, sub, sup, load, ne, 1, nullptr, u0, u1, u, work, 0, stream, false, false);
+}
+
+int lssvr_tridiag_dirichlet_solve_multi(const double* diag, const double* off, const double* load, int64_t ne, int nc,
+                                        const double* bc_values, double* u, void* work, int64_t work_bytes,
+                                        void* stream) {
+  return tridiag_solve(diag, off, nullptr, load, ne, nc, bc_values, 0.0, 0.0, u, work, work_bytes, stream, true, true);
+}
+
+int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub, const double* sup,
+                                           const double* load, int64_t ne, int nc, const double* bc_values, double* u,
+                                           void* work, int64_t work_bytes, void* stream) {
+  return tridiag_solve(diag, sub, sup, load, ne, nc, bc_values, 0.0, 0.0, u, work, work_bytes, stream, false, true);
+}
+
+// Free ends: Dirichlet or Robin at each end.
 static int tridiag_bc_solve(const double* diag, const double* sub, const double* sup, const double* load,
                             int kind_left, int kind_right, const double* end_values, const double* kappa_host,
                             int64_t ne, int nc, double* u, void* work, int64_t work_bytes, void* stream, bool sym) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
-  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
-    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
-  const int rc = check_end_kinds(kind_left, kind_right, kappa_host);
+  TriEnds e{kind_left, kind_right, kappa_host};
+  const int rc = tridiag_check(kTriBc, sym, diag, sub, sup, load, ne, nc, u, kTriWorkSized, work, work_bytes, &e);
   if (rc != LSSVR_OK) return rc;
-  const int64_t need = lssvr::tridiag_bc_work_bytes(ne, nc);
-  if (work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_bc_work_bytes(%lld, %d) = %lld",
-                (long long)work_bytes, (long long)ne, nc, (long long)need);
-  const bool f0 = kind_left == LSSVR_END_ROBIN, f1 = kind_right == LSSVR_END_ROBIN;
-  const double k0 = f0 ? kappa_host[0] : 0.0, k1 = f1 ? kappa_host[1] : 0.0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (sym)
-    return check_launch(lssvr::tridiag_bc_solve(diag, sub, load, ne, nc, f0, f1, k0, k1, end_values, u, work, st),
+    return check_launch(lssvr::tridiag_bc_solve(diag, sub, load, ne, nc, e.f0, e.f1, e.k0, e.k1, end_values, u, work,
+                                                st),
                         "tridiag_bc_solve_multi");
-  return check_launch(lssvr::tridiag_ns_bc_solve(diag, sub, sup, load, ne, nc, f0, f1, k0, k1, end_values, u, work,
-                                                 st),
+  return check_launch(lssvr::tridiag_ns_bc_solve(diag, sub, sup, load, ne, nc, e.f0, e.f1, e.k0, e.k1, end_values, u,
+                                                 work, st),
                       "tridiag_ns_bc_solve_multi");
 }
 
@@ -984,27 +1006,16 @@ int lssvr_tridiag_ns_bc_solve_multi(const double* diag, const double* sub, const
                           work_bytes, stream, false);
 }
 
-// The pivoting solve (tridiag_pivot.hip): the ends of lssvr_tridiag_ns_bc_solve_multi, any non-singular matrix.
-int64_t lssvr_tridiag_pivot_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_pivot_work_bytes(ne, nc); }
-
+// The pivoting solve: the ends of lssvr_tridiag_ns_bc_solve_multi, any non-singular matrix.
 int lssvr_tridiag_pivot_solve_multi(const double* diag, const double* sub, const double* sup, const double* load,
                                     int kind_left, int kind_right, const double* end_values,
                                     const double* kappa_host, int64_t ne, int nc, double* u, int32_t* info,
                                     void* work, int64_t work_bytes, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
-  if (!diag || !sub || !sup || !load || !u || !work)
-    return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u, work must be non-NULL");
-  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
+  TriEnds e{kind_left, kind_right, kappa_host};
+  const int rc = tridiag_check(kTriPivot, false, diag, sub, sup, load, ne, nc, u, kTriWorkSized, work, work_bytes, &e);
   if (rc != LSSVR_OK) return rc;
-  const int64_t need = lssvr::tridiag_pivot_work_bytes(ne, nc);
-  if (work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_pivot_work_bytes(%lld, %d) = %lld",
-                (long long)work_bytes, (long long)ne, nc, (long long)need);
-  const bool f0 = kind_left == LSSVR_END_ROBIN, f1 = kind_right == LSSVR_END_ROBIN;
-  const double k0 = f0 ? kappa_host[0] : 0.0, k1 = f1 ? kappa_host[1] : 0.0;
-  return check_launch(lssvr::tridiag_pivot_solve(diag, sub, sup, load, ne, nc, f0, f1, k0, k1, end_values, u, info,
-                                                 work, reinterpret_cast<hipStream_t>(stream)),
+  return check_launch(lssvr::tridiag_pivot_solve(diag, sub, sup, load, ne, nc, e.f0, e.f1, e.k0, e.k1, end_values, u,
+                                                 info, work, reinterpret_cast<hipStream_t>(stream)),
                       "tridiag_pivot_solve_multi");
 }
 
@@ -1012,31 +1023,19 @@ int lssvr_tridiag_pivot_solve_multi(const double* diag, const double* sub, const
 int lssvr_tridiag_pivot_solve_host(const double* diag, const double* sub, const double* sup, const double* load,
                                    int kind_left, int kind_right, const double* end_values,
                                    const double* kappa_host, int64_t ne, int nc, double* u, int32_t* info) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
-  if (!diag || !sub || !sup || !load || !u) return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u must be non-NULL");
-  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
+  TriEnds e{kind_left, kind_right, kappa_host};
+  const int rc = tridiag_check(kTriPivot, false, diag, sub, sup, load, ne, nc, u, kTriNoWork, nullptr, 0, &e);
   if (rc != LSSVR_OK) return rc;
-  const bool f0 = kind_left == LSSVR_END_ROBIN, f1 = kind_right == LSSVR_END_ROBIN;
-  lssvr::tridiag_pivot_host(diag, sub, sup, load, ne, nc, f0, f1, f0 ? kappa_host[0] : 0.0, f1 ? kappa_host[1] : 0.0,
-                            end_values, u, info);
+  lssvr::tridiag_pivot_host(diag, sub, sup, load, ne, nc, e.f0, e.f1, e.k0, e.k1, end_values, u, info);
   return LSSVR_OK;
 }
 
-// Periodic ends (tridiag.hip).  sup == NULL: the symmetric entry, `off` arrives as sub.
-int64_t lssvr_tridiag_periodic_work_bytes(int64_t ne, int nc) { return lssvr::tridiag_periodic_work_bytes(ne, nc); }
-
+// Periodic ends.
 static int tridiag_periodic_solve(const double* diag, const double* sub, const double* sup, const double* load,
                                   int64_t ne, int nc, double* u, void* work, int64_t work_bytes, void* stream,
                                   bool sym) {
-  if (ne < 2) return fail(LSSVR_ERR_SIZE, "ne = %lld < 2: a periodic mesh has at least two elements", (long long)ne);
-  if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
-  if (!diag || !sub || (!sym && !sup) || !load || !u || !work)
-    return fail(LSSVR_ERR_NULL, "diag, %s, load, u, work must be non-NULL", sym ? "off" : "sub, sup");
-  const int64_t need = lssvr::tridiag_periodic_work_bytes(ne, nc);
-  if (work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_tridiag_periodic_work_bytes(%lld, %d) = %lld",
-                (long long)work_bytes, (long long)ne, nc, (long long)need);
+  const int rc = tridiag_check(kTriPeriodic, sym, diag, sub, sup, load, ne, nc, u, kTriWorkSized, work, work_bytes);
+  if (rc != LSSVR_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (sym)
     return check_launch(lssvr::tridiag_periodic_solve(diag, sub, load, ne, nc, u, work, st),

@@ -7,6 +7,7 @@ raises otherwise -- there is no CPU path.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
 import math
@@ -773,102 +774,6 @@ def p1_assemble(x, nquad=2, *, rhs=(POISSON_AMP, POISSON_OMEGA), rhs_quad=None, 
     return out
 
 
-def _tridiag_solve(entry, names, bands, lengths, ends, out, work, stream, multi=False):
-    """The C ``entry`` on ``bands`` (``names`` in its order: diag, one or two off-diagonal bands, load) -> u[ne+1];
-    ``lengths`` is the message for bands that are not ne+1, ne(, ne), ne+1 doubles long; ``ends`` = (u0, u1).
-    ``multi``: the ``*_multi`` entry -- load is [nc, ne+1], ``ends`` the device array bc[nc, 2] or None, ``out`` may
-    hold more than nc cases (the first nc are written and returned), a ``work`` that is given must be large enough."""
-    lib = _capi.load()
-    for nm, t in zip(names, bands):
-        _dev(t, nm)
-    diag, load = bands[0], bands[-1]
-    ne = bands[1].numel()
-    per_case = load.shape[-1] if multi and load.dim() == 2 else load.numel()
-    if diag.numel() != ne + 1 or bands[-2].numel() != ne or per_case != ne + 1 or (multi and load.dim() != 2):
-        raise ValueError(lengths)
-    if ne < 1:
-        raise ValueError("need at least one element")
-    nc = int(load.shape[0]) if multi else 1
-    if nc < 1:
-        raise ValueError("need at least one case")
-    shape = (nc, ne + 1) if multi else (ne + 1,)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float64, device=diag.device)
-    else:
-        _dev(out, "out")
-        if multi and (out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc):
-            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
-        if not multi and out.numel() != ne + 1:
-            raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
-    # one solver and one formula behind the four entries: at nc = 1 this is lssvr_tridiag_work_bytes(ne) and
-    # lssvr_tridiag_ns_work_bytes(ne)
-    need = lib.lssvr_tridiag_multi_work_bytes(ne, nc)
-    if multi and work is not None:     # (the single entries replace a work that is too small)
-        _dev(work, "work")
-        if work.numel() * work.element_size() < need:
-            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                             f"lssvr_tridiag_multi_work_bytes({ne}, {nc}) = {need}")
-    work = _scratch(work, need, diag.device)
-    bc = ends if multi else None
-    if bc is not None:
-        if not isinstance(bc, torch.Tensor):
-            bc = torch.as_tensor(np.ascontiguousarray(np.asarray(bc, dtype=np.float64)), device=diag.device)
-        _dev(bc, "bc")
-        if tuple(bc.shape) != (nc, 2):
-            raise ValueError(f"bc must be [nc, 2] = [{nc}, 2], got {list(bc.shape)}")
-    if multi:
-        # (not on the single entries: at 1e5 elements their call is bound by the host, and this loop is 2.6 us of it)
-        for nm, t in (*zip(names, bands), ("bc", bc), ("out", out), ("work", work)):
-            if t is not None and t.device != diag.device:
-                raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
-        tail = (ne, nc, _ptr(bc), _ptr(out), _ptr(work), work.numel() * work.element_size())
-    else:
-        tail = (ne, float(ends[0]), float(ends[1]), _ptr(out), _ptr(work))
-    rc = getattr(lib, entry)(*map(_ptr, bands), *tail, _stream(stream))
-    _capi.check(rc, entry)
-    return out[:nc] if multi else out
-
-
-def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
-    """``enforce`` + ``solve`` (Dual.py:129-130) on the assembled bands -> u[ne+1]."""
-    return _tridiag_solve("lssvr_tridiag_dirichlet_solve", ("diag", "off", "load"), (diag, off, load),
-                          "band lengths must be ne+1, ne, ne+1", (u0, u1), out, work, stream)
-
-
-def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
-    """:func:`tridiag_dirichlet_solve` for bands that are not symmetric (``lssvr_tridiag_ns_dirichlet_solve``):
-    row i is sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i] -> u[ne+1].  No pivoting: the rows must be
-    diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``);
-    :func:`tridiag_pivot_solve` pivots."""
-    return _tridiag_solve("lssvr_tridiag_ns_dirichlet_solve", ("diag", "sub", "sup", "load"), (diag, sub, sup, load),
-                          "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)", (u0, u1), out, work,
-                          stream)
-
-
-# cases per pass of the multi-RHS tridiagonal solve (kTriMultiCases of the library): lssvr_tridiag_multi_work_bytes
-# grows with nc up to here
-TRIDIAG_MULTI_CASES = 8
-
-
-def tridiag_dirichlet_solve_multi(diag, off, load, bc=None, *, out=None, work=None, stream=None):
-    """``load.shape[0]`` calls of :func:`tridiag_dirichlet_solve` on the same bands in one
-    (``lssvr_tridiag_dirichlet_solve_multi``), bit-identical to them: load float64[nc, ne+1] -> u[nc, ne+1] with
-    u[j, 0], u[j, ne] = bc[j] (a float64 device tensor [nc, 2], or an array-like that is copied to the device;
-    ``None``: zeros).  The bands are read and the pivots computed once per pass of ``TRIDIAG_MULTI_CASES`` cases.
-    ``out`` [>= nc, ne+1]: its first nc rows are written and returned; ``work``: at least
-    ``lssvr_tridiag_multi_work_bytes(ne, nc)`` bytes (``ValueError`` otherwise)."""
-    return _tridiag_solve("lssvr_tridiag_dirichlet_solve_multi", ("diag", "off", "load"), (diag, off, load),
-                          "band lengths must be ne+1, ne and load [nc, ne+1]", bc, out, work, stream, multi=True)
-
-
-def tridiag_ns_dirichlet_solve_multi(diag, sub, sup, load, bc=None, *, out=None, work=None, stream=None):
-    """:func:`tridiag_dirichlet_solve_multi` for the non-symmetric bands: ``load.shape[0]`` calls of
-    :func:`tridiag_ns_dirichlet_solve` in one (``lssvr_tridiag_ns_dirichlet_solve_multi``), bit-identical to them."""
-    return _tridiag_solve("lssvr_tridiag_ns_dirichlet_solve_multi", ("diag", "sub", "sup", "load"),
-                          (diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] (diag, sub, "
-                          "sup, load)", bc, out, work, stream, multi=True)
-
-
 END_DIRICHLET, END_ROBIN = _capi.END_DIRICHLET, _capi.END_ROBIN      # LSSVR_END_*: the kind of one end of the domain
 
 
@@ -892,58 +797,144 @@ def _end_kinds(end_kinds, kappa, any_sign=False):
     return (int(kinds[0]), int(kinds[1])), (ctypes.c_double * 2)(*kap)
 
 
-def _tridiag_bc_solve(entry, names, bands, lengths, end_kinds, kappa, end_values, out, work, stream, multi):
-    """The ``*_bc_solve_multi`` entry on ``bands`` (``names`` in its order) -> u[nc, ne+1], or u[ne+1] for the single
-    form (``multi`` False: load [ne+1], ``end_values`` a host pair)."""
+# The tridiagonal solves: one row per family, and `_tridiag` behind all 14 public functions (a new
+# family is a row here, a row of the library's table in capi.hip, and its public functions below).
+#   entries      (symmetric, non-symmetric) ``*_multi`` entry; the single forms are its nc = 1 call ...
+#   by_value     ... except the Dirichlet ones: (symmetric, non-symmetric) single entry that takes u0, u1 by value
+#   sizer        the scratch of (ne, nc), named in the "work holds" message
+#   min_ne       fewest elements, and the message below that
+#   ends         how the end values reach the entry: "bc" a [nc, 2] device tensor (or None) after nc, named ``bc``;
+#                "kinds" the same tensor, named ``end_values``, after the end kinds and before kappa; None: no ends
+#   any_sign     "kinds": kappa of either sign
+#   info         the entry takes the int32 singularity count
+#   strict_work  the single form raises on a short ``work`` as the multi forms do (the others replace it).  Only the
+#                pivoting solve does; nobody chose that difference, and levelling it is a change of behaviour.
+_Tri = collections.namedtuple("_Tri", "entries by_value sizer min_ne too_few ends any_sign info strict_work")
+_ONE_ELEMENT = "need at least one element"
+_TRIDIAG = {
+    "dirichlet": _Tri(("lssvr_tridiag_dirichlet_solve_multi", "lssvr_tridiag_ns_dirichlet_solve_multi"),
+                      ("lssvr_tridiag_dirichlet_solve", "lssvr_tridiag_ns_dirichlet_solve"),
+                      "lssvr_tridiag_multi_work_bytes", 1, _ONE_ELEMENT, "bc", False, False, False),
+    "bc": _Tri(("lssvr_tridiag_bc_solve_multi", "lssvr_tridiag_ns_bc_solve_multi"), None,
+               "lssvr_tridiag_bc_work_bytes", 1, _ONE_ELEMENT, "kinds", False, False, False),
+    "pivot": _Tri((None, "lssvr_tridiag_pivot_solve_multi"), None,
+                  "lssvr_tridiag_pivot_work_bytes", 1, _ONE_ELEMENT, "kinds", True, True, True),
+    "periodic": _Tri(("lssvr_tridiag_periodic_solve_multi", "lssvr_tridiag_ns_periodic_solve_multi"), None,
+                     "lssvr_tridiag_periodic_work_bytes", 2, "a periodic mesh needs at least two elements", None,
+                     False, False, False),
+}
+# (the names of the bands, the message for bands of other lengths by [multi]) by [non-symmetric]
+_TRI_BANDS = ((("diag", "off", "load"), ("band lengths must be ne+1, ne, ne+1",
+                                         "band lengths must be ne+1, ne and load [nc, ne+1]")),
+              (("diag", "sub", "sup", "load"), ("band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)",
+                                                "band lengths must be ne+1, ne, ne and load [nc, ne+1] (diag, sub, "
+                                                "sup, load)")))
+
+
+def _tridiag(family, multi, bands, out, work, stream, end_values=None, ends=None, return_info=False):
+    """The entry of ``family`` (a row of ``_TRIDIAG``) on ``bands`` = (diag, off, load) or (diag, sub, sup, load) ->
+    u[nc, ne+1] with ``multi`` (load [nc, ne+1], ``out`` may hold more than nc cases: the first nc are written and
+    returned, a ``work`` that is given must be large enough), else u[ne+1] (load [ne+1], ``end_values`` a host pair).
+    ``ends`` = (end_kinds, kappa) for the families with free ends; ``return_info``: the pair (u, info)."""
+    row = _TRIDIAG[family]
     lib = _capi.load()
+    ns = len(bands) == 4
+    names, lengths = _TRI_BANDS[ns]
     for nm, t in zip(names, bands):
         _dev(t, nm)
     diag, load = bands[0], bands[-1]
     ne = bands[1].numel()
-    if not multi:
-        if load.dim() != 1:
-            raise ValueError(lengths)
-        load = load.unsqueeze(0)
-    if (diag.numel() != ne + 1 or bands[-2].numel() != ne or load.dim() != 2 or load.shape[1] != ne + 1):
-        raise ValueError(lengths)
-    if ne < 1:
-        raise ValueError("need at least one element")
-    nc = int(load.shape[0])
+    # the single Dirichlet forms, the hot call of the facade: at 1e5 elements they are bound by the host, so they skip
+    # what they can -- no bc tensor, no look at ``work`` beyond its size, no same-device loop (2.6 us) -- and they take
+    # a load of any shape that holds ne+1 doubles
+    by_value = row.by_value is not None and not multi
+    if by_value:
+        fits = load.numel() == ne + 1
+    else:
+        fits = load.dim() == (2 if multi else 1) and load.shape[-1] == ne + 1
+    if diag.numel() != ne + 1 or bands[-2].numel() != ne or not fits:
+        raise ValueError(lengths[multi])
+    if ne < row.min_ne:
+        raise ValueError(row.too_few)
+    nc = int(load.shape[0]) if multi else 1
     if nc < 1:
         raise ValueError("need at least one case")
-    kinds, kap = _end_kinds(end_kinds, kappa)
+    if row.ends == "kinds":
+        kinds, kap = _end_kinds(*ends, any_sign=row.any_sign)
     if out is None:
-        out = torch.empty((nc, ne + 1), dtype=torch.float64, device=diag.device)
+        out = torch.empty((nc, ne + 1) if multi else (ne + 1,), dtype=torch.float64, device=diag.device)
     else:
         _dev(out, "out")
-        if not multi:
-            if out.numel() != ne + 1:
-                raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
-            out = out.view(1, ne + 1)
-        elif out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc:
+        if multi and (out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc):
             raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
-    need = lib.lssvr_tridiag_bc_work_bytes(ne, nc)
-    if work is not None:
+        if not multi and out.numel() != ne + 1:
+            raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
+    need = getattr(lib, row.sizer)(ne, nc)
+    if work is not None and not by_value:
         _dev(work, "work")
-        if multi and work.numel() * work.element_size() < need:
+        if (multi or row.strict_work) and work.numel() * work.element_size() < need:
             raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                             f"lssvr_tridiag_bc_work_bytes({ne}, {nc}) = {need}")
-    work = _scratch(work, need, diag.device)
-    ev = end_values
+                             f"{row.sizer}({ne}, {nc}) = {need}")
+    work = _scratch(work, need, diag.device)         # (the other single forms replace a work that is too small)
+    if by_value:
+        rc = getattr(lib, row.by_value[ns])(*map(_ptr, bands), ne, float(end_values[0]), float(end_values[1]),
+                                            _ptr(out), _ptr(work), _stream(stream))
+        _capi.check(rc, row.by_value[ns])
+        return out
+    ev, ev_name = end_values, "bc" if row.ends == "bc" else "end_values"
     if ev is not None:
         if not isinstance(ev, torch.Tensor):
             ev = np.asarray(ev, dtype=np.float64)
             ev = torch.as_tensor(np.ascontiguousarray(ev if multi else ev.reshape(-1, 2)), device=diag.device)
-        _dev(ev, "end_values")
+        _dev(ev, ev_name)
         if tuple(ev.shape) != (nc, 2):
-            raise ValueError(f"end_values must be [nc, 2] = [{nc}, 2], got {list(ev.shape)}")
-    for nm, t in (*zip(names, bands), ("end_values", ev), ("out", out), ("work", work)):
+            raise ValueError(f"{ev_name} must be [nc, 2] = [{nc}, 2], got {list(ev.shape)}")
+    info = torch.zeros(1, dtype=torch.int32, device=diag.device) if return_info else None
+    for nm, t in (*zip(names, bands), (ev_name, ev), ("out", out), ("work", work)):
         if t is not None and t.device != diag.device:
             raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
-    rc = getattr(lib, entry)(*map(_ptr, bands), kinds[0], kinds[1], _ptr(ev), kap, ne, nc, _ptr(out), _ptr(work),
-                             work.numel() * work.element_size(), _stream(stream))
-    _capi.check(rc, entry)
-    return out[:nc] if multi else out[0]
+    args = (ne, nc, *((_ptr(ev),) if row.ends == "bc" else ()), _ptr(out), *((_ptr(info),) if row.info else ()),
+            _ptr(work), work.numel() * work.element_size(), _stream(stream))
+    if row.ends == "kinds":
+        args = (*kinds, _ptr(ev), kap, *args)
+    rc = getattr(lib, row.entries[ns])(*map(_ptr, bands), *args)
+    _capi.check(rc, row.entries[ns])
+    u = out[:nc] if multi else out.view(ne + 1)
+    return (u, info) if return_info else u
+
+
+def tridiag_dirichlet_solve(diag, off, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
+    """``enforce`` + ``solve`` (Dual.py:129-130) on the assembled bands -> u[ne+1]."""
+    return _tridiag("dirichlet", False, (diag, off, load), out, work, stream, (u0, u1))
+
+
+def tridiag_ns_dirichlet_solve(diag, sub, sup, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
+    """:func:`tridiag_dirichlet_solve` for bands that are not symmetric (``lssvr_tridiag_ns_dirichlet_solve``):
+    row i is sub[i-1] u[i-1] + diag[i] u[i] + sup[i] u[i+1] = load[i] -> u[ne+1].  No pivoting: the rows must be
+    diagonally dominant (cell Peclet number <= 1 and c >= 0 for the bands of ``p1_assemble(..., b_quad=...)``);
+    :func:`tridiag_pivot_solve` pivots."""
+    return _tridiag("dirichlet", False, (diag, sub, sup, load), out, work, stream, (u0, u1))
+
+
+# cases per pass of the multi-RHS tridiagonal solve (kTriMultiCases of the library): lssvr_tridiag_multi_work_bytes
+# grows with nc up to here
+TRIDIAG_MULTI_CASES = 8
+
+
+def tridiag_dirichlet_solve_multi(diag, off, load, bc=None, *, out=None, work=None, stream=None):
+    """``load.shape[0]`` calls of :func:`tridiag_dirichlet_solve` on the same bands in one
+    (``lssvr_tridiag_dirichlet_solve_multi``), bit-identical to them: load float64[nc, ne+1] -> u[nc, ne+1] with
+    u[j, 0], u[j, ne] = bc[j] (a float64 device tensor [nc, 2], or an array-like that is copied to the device;
+    ``None``: zeros).  The bands are read and the pivots computed once per pass of ``TRIDIAG_MULTI_CASES`` cases.
+    ``out`` [>= nc, ne+1]: its first nc rows are written and returned; ``work``: at least
+    ``lssvr_tridiag_multi_work_bytes(ne, nc)`` bytes (``ValueError`` otherwise)."""
+    return _tridiag("dirichlet", True, (diag, off, load), out, work, stream, bc)
+
+
+def tridiag_ns_dirichlet_solve_multi(diag, sub, sup, load, bc=None, *, out=None, work=None, stream=None):
+    """:func:`tridiag_dirichlet_solve_multi` for the non-symmetric bands: ``load.shape[0]`` calls of
+    :func:`tridiag_ns_dirichlet_solve` in one (``lssvr_tridiag_ns_dirichlet_solve_multi``), bit-identical to them."""
+    return _tridiag("dirichlet", True, (diag, sub, sup, load), out, work, stream, bc)
 
 
 def tridiag_bc_solve_multi(diag, off, load, end_kinds, kappa, end_values=None, *, out=None, work=None, stream=None):
@@ -955,17 +946,13 @@ def tridiag_bc_solve_multi(diag, off, load, end_kinds, kappa, end_values=None, *
     inside the kernels; ``diag``, ``off`` and ``load`` are left as they are.  Row j is bit-identical to the call with
     that case alone, and two Dirichlet ends give the bits of :func:`tridiag_dirichlet_solve_multi`.  ``work``: at
     least ``lssvr_tridiag_bc_work_bytes(ne, nc)`` bytes (``ValueError`` otherwise)."""
-    return _tridiag_bc_solve("lssvr_tridiag_bc_solve_multi", ("diag", "off", "load"), (diag, off, load),
-                             "band lengths must be ne+1, ne and load [nc, ne+1]", end_kinds, kappa, end_values, out,
-                             work, stream, True)
+    return _tridiag("bc", True, (diag, off, load), out, work, stream, end_values, (end_kinds, kappa))
 
 
 def tridiag_bc_solve(diag, off, load, end_kinds, kappa, end_values=(0.0, 0.0), *, out=None, work=None, stream=None):
     """One right-hand side of :func:`tridiag_bc_solve_multi` (the nc = 1 call of the same entry): load float64[ne+1],
     ``end_values`` a pair (left, right) -> u[ne+1]."""
-    return _tridiag_bc_solve("lssvr_tridiag_bc_solve_multi", ("diag", "off", "load"), (diag, off, load),
-                             "band lengths must be ne+1, ne, ne+1", end_kinds, kappa, end_values, out, work, stream,
-                             False)
+    return _tridiag("bc", False, (diag, off, load), out, work, stream, end_values, (end_kinds, kappa))
 
 
 def tridiag_ns_bc_solve_multi(diag, sub, sup, load, end_kinds, kappa, end_values=None, *, out=None, work=None,
@@ -973,75 +960,13 @@ def tridiag_ns_bc_solve_multi(diag, sub, sup, load, end_kinds, kappa, end_values
     """:func:`tridiag_bc_solve_multi` for the non-symmetric bands (``lssvr_tridiag_ns_bc_solve_multi``); two Dirichlet
     ends give the bits of :func:`tridiag_ns_dirichlet_solve_multi`.  No pivoting: at a Robin end the row is dominant
     when kappa + b(x_end) n / 2 >= 0 (n = -1 left, +1 right)."""
-    return _tridiag_bc_solve("lssvr_tridiag_ns_bc_solve_multi", ("diag", "sub", "sup", "load"),
-                             (diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] (diag, "
-                             "sub, sup, load)", end_kinds, kappa, end_values, out, work, stream, True)
+    return _tridiag("bc", True, (diag, sub, sup, load), out, work, stream, end_values, (end_kinds, kappa))
 
 
 def tridiag_ns_bc_solve(diag, sub, sup, load, end_kinds, kappa, end_values=(0.0, 0.0), *, out=None, work=None,
                         stream=None):
     """One right-hand side of :func:`tridiag_ns_bc_solve_multi` (the nc = 1 call of the same entry)."""
-    return _tridiag_bc_solve("lssvr_tridiag_ns_bc_solve_multi", ("diag", "sub", "sup", "load"),
-                             (diag, sub, sup, load), "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, load)",
-                             end_kinds, kappa, end_values, out, work, stream, False)
-
-
-def _tridiag_pivot_solve(bands, lengths, end_kinds, kappa, end_values, out, work, stream, multi, return_info):
-    """``lssvr_tridiag_pivot_solve_multi`` on ``bands`` = (diag, sub, sup, load) -> u[nc, ne+1], or u[ne+1] for the
-    single form; with ``return_info`` the pair (u, info), info an int32 device tensor of one element."""
-    lib = _capi.load()
-    names = ("diag", "sub", "sup", "load")
-    for nm, t in zip(names, bands):
-        _dev(t, nm)
-    diag, load = bands[0], bands[-1]
-    ne = bands[1].numel()
-    if not multi:
-        if load.dim() != 1:
-            raise ValueError(lengths)
-        load = load.unsqueeze(0)
-    if (diag.numel() != ne + 1 or bands[2].numel() != ne or load.dim() != 2 or load.shape[1] != ne + 1):
-        raise ValueError(lengths)
-    if ne < 1:
-        raise ValueError("need at least one element")
-    nc = int(load.shape[0])
-    if nc < 1:
-        raise ValueError("need at least one case")
-    kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
-    if out is None:
-        out = torch.empty((nc, ne + 1), dtype=torch.float64, device=diag.device)
-    else:
-        _dev(out, "out")
-        if not multi:
-            if out.numel() != ne + 1:
-                raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
-            out = out.view(1, ne + 1)
-        elif out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc:
-            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
-    need = lib.lssvr_tridiag_pivot_work_bytes(ne, nc)
-    if work is not None:
-        _dev(work, "work")
-        if work.numel() * work.element_size() < need:
-            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                             f"lssvr_tridiag_pivot_work_bytes({ne}, {nc}) = {need}")
-    work = _scratch(work, need, diag.device)
-    ev = end_values
-    if ev is not None:
-        if not isinstance(ev, torch.Tensor):
-            ev = np.asarray(ev, dtype=np.float64)
-            ev = torch.as_tensor(np.ascontiguousarray(ev if multi else ev.reshape(-1, 2)), device=diag.device)
-        _dev(ev, "end_values")
-        if tuple(ev.shape) != (nc, 2):
-            raise ValueError(f"end_values must be [nc, 2] = [{nc}, 2], got {list(ev.shape)}")
-    info = torch.zeros(1, dtype=torch.int32, device=diag.device) if return_info else None
-    for nm, t in (*zip(names, bands), ("end_values", ev), ("out", out), ("work", work)):
-        if t is not None and t.device != diag.device:
-            raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
-    rc = lib.lssvr_tridiag_pivot_solve_multi(*map(_ptr, (diag, bands[1], bands[2], load)), kinds[0], kinds[1],
-                                             _ptr(ev), kap, ne, nc, _ptr(out), _ptr(info), _ptr(work),
-                                             work.numel() * work.element_size(), _stream(stream))
-    _capi.check(rc, "lssvr_tridiag_pivot_solve_multi")
-    u = out[:nc] if multi else out[0]
-    return (u, info) if return_info else u
+    return _tridiag("bc", False, (diag, sub, sup, load), out, work, stream, end_values, (end_kinds, kappa))
 
 
 def tridiag_pivot_solve_multi(diag, sub, sup, load, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0),
@@ -1055,61 +980,16 @@ def tridiag_pivot_solve_multi(diag, sub, sup, load, end_kinds=(END_DIRICHLET, EN
     least ``lssvr_tridiag_pivot_work_bytes(ne, nc)`` bytes.  ``return_info=True``: ``(u, info)`` with ``info`` an
     int32 device tensor [1], the number of pivots that were zero or not finite after the row choice -- nonzero means
     the matrix is singular and ``u`` is not a solution; zero says only that no such pivot was met."""
-    return _tridiag_pivot_solve((diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] (diag, "
-                                "sub, sup, load)", end_kinds, kappa, end_values, out, work, stream, True, return_info)
+    return _tridiag("pivot", True, (diag, sub, sup, load), out, work, stream, end_values, (end_kinds, kappa),
+                    return_info)
 
 
 def tridiag_pivot_solve(diag, sub, sup, load, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0),
                         end_values=(0.0, 0.0), *, out=None, work=None, stream=None, return_info=False):
     """One right-hand side of :func:`tridiag_pivot_solve_multi` (the nc = 1 call of the same entry): load
     float64[ne+1], ``end_values`` a pair (left, right) -> u[ne+1]."""
-    return _tridiag_pivot_solve((diag, sub, sup, load), "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, "
-                                "load)", end_kinds, kappa, end_values, out, work, stream, False, return_info)
-
-
-def _tridiag_periodic_solve(entry, names, bands, lengths, out, work, stream, multi):
-    """The ``*_periodic_solve_multi`` entry on ``bands`` (``names`` in its order) -> u[nc, ne+1], or u[ne+1] for the
-    single form (``multi`` False: load [ne+1])."""
-    lib = _capi.load()
-    for nm, t in zip(names, bands):
-        _dev(t, nm)
-    diag, load = bands[0], bands[-1]
-    ne = bands[1].numel()
-    if not multi:
-        if load.dim() != 1:
-            raise ValueError(lengths)
-        load = load.unsqueeze(0)
-    if (diag.numel() != ne + 1 or bands[-2].numel() != ne or load.dim() != 2 or load.shape[1] != ne + 1):
-        raise ValueError(lengths)
-    if ne < 2:
-        raise ValueError("a periodic mesh needs at least two elements")
-    nc = int(load.shape[0])
-    if nc < 1:
-        raise ValueError("need at least one case")
-    if out is None:
-        out = torch.empty((nc, ne + 1), dtype=torch.float64, device=diag.device)
-    else:
-        _dev(out, "out")
-        if not multi:
-            if out.numel() != ne + 1:
-                raise ValueError(f"out must hold ne+1 = {ne + 1} doubles, got {out.numel()}")
-            out = out.view(1, ne + 1)
-        elif out.dim() != 2 or out.shape[1] != ne + 1 or out.shape[0] < nc:
-            raise ValueError(f"out must be [>= {nc}, ne+1 = {ne + 1}], got {list(out.shape)}")
-    need = lib.lssvr_tridiag_periodic_work_bytes(ne, nc)
-    if work is not None:
-        _dev(work, "work")
-        if multi and work.numel() * work.element_size() < need:
-            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                             f"lssvr_tridiag_periodic_work_bytes({ne}, {nc}) = {need}")
-    work = _scratch(work, need, diag.device)
-    for nm, t in (*zip(names, bands), ("out", out), ("work", work)):
-        if t.device != diag.device:
-            raise RuntimeError(f"{nm} lives on {t.device}, diag on {diag.device}")
-    rc = getattr(lib, entry)(*map(_ptr, bands), ne, nc, _ptr(out), _ptr(work), work.numel() * work.element_size(),
-                             _stream(stream))
-    _capi.check(rc, entry)
-    return out[:nc] if multi else out[0]
+    return _tridiag("pivot", False, (diag, sub, sup, load), out, work, stream, end_values, (end_kinds, kappa),
+                    return_info)
 
 
 def tridiag_periodic_solve_multi(diag, off, load, *, out=None, work=None, stream=None):
@@ -1120,30 +1000,24 @@ def tridiag_periodic_solve_multi(diag, off, load, *, out=None, work=None, stream
     row j is bit-identical to the call with that case alone.  The matrix must not be singular (a reaction term that
     is positive somewhere); no pivoting.  ``work``: at least ``lssvr_tridiag_periodic_work_bytes(ne, nc)`` bytes
     (``ValueError`` otherwise)."""
-    return _tridiag_periodic_solve("lssvr_tridiag_periodic_solve_multi", ("diag", "off", "load"), (diag, off, load),
-                                   "band lengths must be ne+1, ne and load [nc, ne+1]", out, work, stream, True)
+    return _tridiag("periodic", True, (diag, off, load), out, work, stream)
 
 
 def tridiag_periodic_solve(diag, off, load, *, out=None, work=None, stream=None):
     """One right-hand side of :func:`tridiag_periodic_solve_multi` (the nc = 1 call of the same entry): load
     float64[ne+1] -> u[ne+1]."""
-    return _tridiag_periodic_solve("lssvr_tridiag_periodic_solve_multi", ("diag", "off", "load"), (diag, off, load),
-                                   "band lengths must be ne+1, ne, ne+1", out, work, stream, False)
+    return _tridiag("periodic", False, (diag, off, load), out, work, stream)
 
 
 def tridiag_ns_periodic_solve_multi(diag, sub, sup, load, *, out=None, work=None, stream=None):
     """:func:`tridiag_periodic_solve_multi` for the non-symmetric bands (``lssvr_tridiag_ns_periodic_solve_multi``):
     the seam row is (diag[0] + diag[ne]) s + sup[0] u[1] + sub[ne-1] u[ne-1] = load[0] + load[ne]."""
-    return _tridiag_periodic_solve("lssvr_tridiag_ns_periodic_solve_multi", ("diag", "sub", "sup", "load"),
-                                   (diag, sub, sup, load), "band lengths must be ne+1, ne, ne and load [nc, ne+1] "
-                                   "(diag, sub, sup, load)", out, work, stream, True)
+    return _tridiag("periodic", True, (diag, sub, sup, load), out, work, stream)
 
 
 def tridiag_ns_periodic_solve(diag, sub, sup, load, *, out=None, work=None, stream=None):
     """One right-hand side of :func:`tridiag_ns_periodic_solve_multi` (the nc = 1 call of the same entry)."""
-    return _tridiag_periodic_solve("lssvr_tridiag_ns_periodic_solve_multi", ("diag", "sub", "sup", "load"),
-                                   (diag, sub, sup, load), "band lengths must be ne+1, ne, ne, ne+1 (diag, sub, sup, "
-                                   "load)", out, work, stream, False)
+    return _tridiag("periodic", False, (diag, sub, sup, load), out, work, stream)
 
 
 def p1_load_multi(x, rhs_quad, nquad=2, *, out=None, stream=None):
@@ -1332,6 +1206,16 @@ def adapt_work(x, ne):
 def goal_work(x, ne):
     """Device scratch of ``lssvr_goal_work_bytes(ne)`` bytes for :func:`estimate_goal`."""
     return _adapt_scratch(None, x, ne, "lssvr_goal_work_bytes")
+
+
+def tridiag_work(x, ne, nc, *families):
+    """Device scratch on ``x``'s device for the ``tridiag_*`` solves of nc cases on ne elements of every family named
+    ("dirichlet", "bc", "pivot", "periodic"): the largest of their sizers, ``lssvr_tridiag_multi_work_bytes(ne, nc)``,
+    ``lssvr_tridiag_bc_work_bytes``, ``lssvr_tridiag_pivot_work_bytes``, ``lssvr_tridiag_periodic_work_bytes``."""
+    if not families:
+        raise ValueError("name at least one family of " + ", ".join(_TRIDIAG))
+    lib = _capi.load()
+    return _scratch(None, max(getattr(lib, _TRIDIAG[f].sizer)(int(ne), int(nc)) for f in families), x.device)
 
 
 def _pair(name, v):

@@ -746,37 +746,38 @@ class FEMLSSVRPrimalSolver:
         """u device [ne+1] of the assembled ``bands`` with the end values ``u0``, ``u1`` for the configured ends and
         ``fem_solver``; ``conv``: the bands are the non-symmetric ones (sub, sup).  The one dispatch behind
         :meth:`_fem` and the Newton steps of :meth:`_solve_fem_newton`."""
+        if self.fem_solver == "flux" and not (self._periodic or self._bnd is not None or conv):
+            # exact-structure solution of A = D^T K D by the element-flux prefix scan
+            return ops.p1_flux_solve(bands["kloc"], bands["load"], u0, u1)
+        return self._tridiag_solve(bands, bands["load"], conv, (u0, u1), False)
+
+    def _tridiag_solve(self, bands, load, conv, ends, multi):
+        """The tridiagonal solve of ``load`` ([ne+1], or [nc, ne+1] with ``multi``) on the assembled ``bands``: the
+        one ladder that picks the ``ops.tridiag_*`` function by ``fem_solver="pivot"``, the configured ends (periodic,
+        Neumann or Robin, Dirichlet), ``conv`` (the non-symmetric bands sub, sup) and ``multi``.  ``ends``: the pair
+        (u0, u1), with ``multi`` the float64 host array [nc, 2] (uploaded here, where the solve reads it)."""
         bnd = self._bnd
         if self.fem_solver == "pivot":
-            u = self._pivot_solve(bands, bands["load"], (u0, u1), False)
-        elif self._periodic:
-            # node ne is node 0: the cyclic solve reads no end value (_check_periodic has run)
-            if conv:
-                u = ops.tridiag_ns_periodic_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"])
-            else:
-                u = ops.tridiag_periodic_solve(bands["diag"], bands["off"], bands["load"])
-        elif bnd is not None:
-            # a Neumann or Robin end stays an unknown; kappa and g join its row inside the solve (_check_boundary has
-            # run, and with convection _convection_quad)
-            if conv:
-                u = ops.tridiag_ns_bc_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], bnd.kinds,
-                                            bnd.kappa, (u0, u1))
-            else:
-                u = ops.tridiag_bc_solve(bands["diag"], bands["off"], bands["load"], bnd.kinds, bnd.kappa, (u0, u1))
-        elif conv:
-            # no pivoting and no stabilisation: _convection_quad has checked the cell Peclet number
-            u = ops.tridiag_ns_dirichlet_solve(bands["diag"], bands["sub"], bands["sup"], bands["load"], u0, u1)
-        elif self.fem_solver == "flux":
-            # exact-structure solution of A = D^T K D by the element-flux prefix scan
-            u = ops.p1_flux_solve(bands["kloc"], bands["load"], u0, u1)
-        else:
-            # the ASSEMBLED float64 bands (rounded diagonal included) through `enforce` + `solve`
-            # semantics (Dual.py:129-130).  Which matrix scikit-fem itself assembles is an
-            # assumption of SURVEY.md Appendix C -- parity unpinned, the package is not importable
-            # here (the reference negates both forms, Dual.py:117-124: -K u = -b; this code
-            # assembles +K u = +b, the same u)
-            u = ops.tridiag_dirichlet_solve(bands["diag"], bands["off"], bands["load"], u0, u1)
-        return u
+            return self._pivot_solve(bands, load, _to_dev(ends, load.device) if multi else ends, multi)
+        # the families of ops.tridiag_* (none of these pivots or stabilises: with convection, _convection_quad has
+        # checked the cell Peclet number):
+        #   periodic   node ne is node 0: the cyclic solve reads no end value (_check_periodic has run)
+        #   bc         a Neumann or Robin end stays an unknown; kappa and g join its row inside the solve
+        #              (_check_boundary has run)
+        #   dirichlet  the ASSEMBLED float64 bands (rounded diagonal included) through `enforce` + `solve` semantics
+        #              (Dual.py:129-130).  Which matrix scikit-fem itself assembles is an assumption of SURVEY.md
+        #              Appendix C -- parity unpinned, the package is not importable here (the reference negates both
+        #              forms, Dual.py:117-124: -K u = -b; this code assembles +K u = +b, the same u)
+        family = "periodic" if self._periodic else "dirichlet" if bnd is None else "bc"
+        fn = getattr(ops, f"tridiag_{'ns_' if conv else ''}{family}_solve{'_multi' if multi else ''}")
+        system = (bands["diag"], bands["sub"], bands["sup"], load) if conv else (bands["diag"], bands["off"], load)
+        if family == "periodic":
+            return fn(*system)
+        if multi:
+            ends = _to_dev(ends, load.device)
+        if family == "bc":
+            return fn(*system, bnd.kinds, bnd.kappa, ends)
+        return fn(*system, ends) if multi else fn(*system, *ends)
 
     def _fem_many(self, rhs_list, bc):
         """(x device, U device [ncases, ne+1]) of the P1 solves of :meth:`solve_many`: what ``_fem`` per case returns,
@@ -815,25 +816,7 @@ class FEMLSSVRPrimalSolver:
                 load = loads
             else:
                 load[torch.as_tensor(tabulated, device=dev)] = loads
-        if self.fem_solver == "pivot":
-            return x, self._pivot_solve(bands, load, _to_dev(bc, dev), True)
-        if self._periodic:
-            if "b_quad" in kw:
-                return x, ops.tridiag_ns_periodic_solve_multi(bands["diag"], bands["sub"], bands["sup"], load)
-            return x, ops.tridiag_periodic_solve_multi(bands["diag"], bands["off"], load)
-        bc_dev = _to_dev(bc, dev)
-        bnd = self._bnd
-        if bnd is not None:
-            if "b_quad" in kw:
-                U = ops.tridiag_ns_bc_solve_multi(bands["diag"], bands["sub"], bands["sup"], load, bnd.kinds,
-                                                  bnd.kappa, bc_dev)
-            else:
-                U = ops.tridiag_bc_solve_multi(bands["diag"], bands["off"], load, bnd.kinds, bnd.kappa, bc_dev)
-        elif "b_quad" in kw:
-            U = ops.tridiag_ns_dirichlet_solve_multi(bands["diag"], bands["sub"], bands["sup"], load, bc_dev)
-        else:
-            U = ops.tridiag_dirichlet_solve_multi(bands["diag"], bands["off"], load, bc_dev)
-        return x, U
+        return x, self._tridiag_solve(bands, load, "b_quad" in kw, bc, True)
 
     def _pivot_solve(self, bands, load, end_values, multi):
         """The P1 solve of ``fem_solver="pivot"`` on the assembled bands -- symmetric (off) or
@@ -1345,10 +1328,8 @@ class FEMLSSVRPrimalSolver:
         res2 = torch.empty((2, nb), dtype=torch.float64, device=dev)
         rinfo = torch.zeros(1, dtype=torch.int32, device=dev)
         pinfo = rinfo
-        lib = ops._capi.load()
-        swork = ops._scratch(None, max(lib.lssvr_tridiag_pivot_work_bytes(ne, nb),
-                                       lib.lssvr_tridiag_bc_work_bytes(ne, nb)), dev)
-        ework = ops._scratch(None, lib.lssvr_eig_work_bytes(ne, nb), dev)
+        swork = ops.tridiag_work(Y, ne, nb, "pivot", "bc")
+        ework = ops._scratch(None, ops._capi.load().lssvr_eig_work_bytes(ne, nb), dev)
         it, converged, th, res, xn = 0, False, None, None, None
         while it < int(max_iter) and not converged:
             it += 1
@@ -1581,7 +1562,7 @@ class FEMLSSVRPrimalSolver:
         U[0].copy_(_to_dev(p["u_init"], dev))
         S = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
         b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
-        work = ops._scratch(None, ops._capi.load().lssvr_tridiag_bc_work_bytes(ne, 1), dev)
+        work = ops.tridiag_work(b, ne, 1, "bc")
         md, mo = Mb["diag"], Mb["off"]
         bdf1 = ops.BDF["bdf1"]
         snap = {s: k for k, s in enumerate(steps)}

@@ -77,3 +77,25 @@ def test_argument_errors_without_gpu():
         need = lib.lssvr_tridiag_multi_work_bytes(10, 3)
         assert fn(wb=need - 1) == -2 and "work holds" in err() and "lssvr_tridiag_multi_work_bytes" in err()
         assert fn(wb=0) == -2 and fn(wb=-8) == -2
+        # the order of the checks: ne, nc, NULL, work_bytes
+        assert fn(ne=0, nc=0) == -2 and "ne = 0 < 1" in err()
+        assert fn(nc=0, diag=None) == -2 and "nc = 0 < 1" in err()
+        nulls = "diag, %s, load, u, work must be non-NULL" % ", ".join(bands[1:-1])
+        assert fn(diag=None, wb=0) == -1 and nulls in err()
+        assert fn(wb=need - 1) == -2 and "work holds %d bytes, lssvr_tridiag_multi_work_bytes(10, 3) = %d" % (
+            need - 1, need) in err()
+
+    # the single-RHS entries: the same checks, and no work_bytes to check
+    def sym1(diag=F[0], off=F[1], ld=F[2], ne=10, u=F[3], work=F[4]):
+        return lib.lssvr_tridiag_dirichlet_solve(diag, off, ld, ne, 0.0, 0.0, u, work, None)
+
+    def ns1(diag=F[0], sub=F[1], sup=F[5], ld=F[2], ne=10, u=F[3], work=F[4]):
+        return lib.lssvr_tridiag_ns_dirichlet_solve(diag, sub, sup, ld, ne, 0.0, 0.0, u, work, None)
+
+    for fn, bands in ((sym1, ("diag", "off", "ld")), (ns1, ("diag", "sub", "sup", "ld"))):
+        nulls = "diag, %s, load, u, work must be non-NULL" % ", ".join(bands[1:-1])
+        for nm in bands + ("u", "work"):
+            assert fn(**{nm: None}) == -1 and nulls in err(), nm
+        for ne in (0, -1):
+            assert fn(ne=ne) == -2 and "ne = %d < 1" % ne in err()
+        assert fn(ne=0, diag=None) == -2

@@ -82,6 +82,19 @@ def test_argument_errors_without_gpu():
         for arg in ("diag", "load", "u", "work"):
             assert fn(**{arg: None}) == -1, arg
     assert ns(sup=None) == -1
+    # the off-diagonal band too, the words of each message, and the order of the checks: ne, nc, NULL, work_bytes
+    assert lib.lssvr_tridiag_periodic_solve_multi(FAKE, None, FAKE, 10, 1, FAKE, FAKE, big, None) == -1
+    assert b"diag, off, load, u, work must be non-NULL" in lib.lssvr_last_error()
+    assert lib.lssvr_tridiag_ns_periodic_solve_multi(FAKE, None, FAKE, FAKE, 10, 1, FAKE, FAKE, big, None) == -1
+    assert b"diag, sub, sup, load, u, work must be non-NULL" in lib.lssvr_last_error()
+    for fn in (sym, ns):
+        assert fn(ne=1, nc=0) == -2
+        assert b"ne = 1 < 2: a periodic mesh has at least two elements" in lib.lssvr_last_error()
+        assert fn(nc=0, diag=None) == -2 and b"nc = 0 < 1" in lib.lssvr_last_error()
+        assert fn(diag=None, wb=8) == -1
+        need = lib.lssvr_tridiag_periodic_work_bytes(10, 1)
+        assert fn(wb=need - 1) == -2 and b"work holds %d bytes, lssvr_tridiag_periodic_work_bytes(10, 1) = %d" % (
+            need - 1, need) in lib.lssvr_last_error()
     a = (ctypes.c_double * 2)(1.0, 1.0)
 
     def seam(M=9, ne=10, x=FAKE, W=FAKE, ah=a, eta2=FAKE, out3=FAKE):

@@ -208,3 +208,26 @@ def test_argument_errors_without_gpu():
     assert call(kl=2) == -2
     assert call(kappa=(ctypes.c_double * 2)(float("inf"), 0.0)) == -2 and b"finite" in lib.lssvr_last_error()
     assert call(wb=8) == -2 and b"lssvr_tridiag_pivot_work_bytes" in lib.lssvr_last_error()
+    # each NULL, the words of each message, and the order of the checks: ne, nc, NULL, end kinds, work_bytes
+    for nm in ("diag", "sub", "sup", "load", "u", "work"):
+        assert call(**{nm: None}) == -1, nm
+        assert b"diag, sub, sup, load, u, work must be non-NULL" in lib.lssvr_last_error()
+    assert call(ne=0, nc=0) == -2 and b"ne = 0 < 1" in lib.lssvr_last_error()
+    assert call(nc=0, diag=None) == -2 and b"nc = 0 < 1" in lib.lssvr_last_error()
+    assert call(diag=None, kl=2) == -1 and call(kl=2, wb=8) == -2 and b"end kinds" in lib.lssvr_last_error()
+    assert call(kr=1, kappa=(ctypes.c_double * 2)(-0.5, float("nan"))) == -2 and b"kappa[1]" in lib.lssvr_last_error()
+    need = lib.lssvr_tridiag_pivot_work_bytes(10, 1)
+    assert call(wb=need - 1) == -2 and b"work holds %d bytes, lssvr_tridiag_pivot_work_bytes(10, 1) = %d" % (
+        need - 1, need) in lib.lssvr_last_error()
+
+    # the host entry: the same checks but for work, which it does not take
+    def host(diag=f[0], sub=f[1], sup=f[2], load=f[3], kl=1, kr=0, ne=10, nc=1, u=f[4], kappa=kap):
+        return lib.lssvr_tridiag_pivot_solve_host(diag, sub, sup, load, kl, kr, None, kappa, ne, nc, u, None)
+    assert host(ne=0) == -2 and b"ne = 0 < 1" in lib.lssvr_last_error()
+    assert host(nc=0, u=None) == -2 and b"nc = 0 < 1" in lib.lssvr_last_error()
+    for nm in ("diag", "sub", "sup", "load", "u"):
+        assert host(**{nm: None}) == -1, nm
+        assert b"diag, sub, sup, load, u must be non-NULL" in lib.lssvr_last_error()
+    assert host(u=None, kl=2) == -1 and host(kl=2) == -2 and b"end kinds" in lib.lssvr_last_error()
+    assert host(kappa=None) == -1
+    assert host(kappa=(ctypes.c_double * 2)(float("inf"), 0.0)) == -2 and b"finite" in lib.lssvr_last_error()

@@ -73,6 +73,22 @@ def test_argument_errors_without_gpu():
         assert fn(kr=1, kappa=(ctypes.c_double * 2)(0.0, math.nan)) == -2
         assert fn(wb=8) == -2 and b"lssvr_tridiag_bc_work_bytes" in lib.lssvr_last_error()
     assert sym(diag=None) == -1 and sym(work=None) == -1 and ns(sup=None) == -1
+    # each NULL of both entries (end_values may be NULL: zeros), with the list of its bands in the message
+    for entry, nargs, bands, words in ((lib.lssvr_tridiag_bc_solve_multi, 13, (0, 1, 2), b"diag, off, load, u, work"),
+                                       (lib.lssvr_tridiag_ns_bc_solve_multi, 14, (0, 1, 2, 3),
+                                        b"diag, sub, sup, load, u, work")):
+        args = [FAKE] * len(bands) + [1, 0, None, kap, 10, 1, FAKE, FAKE, big, None]
+        assert len(args) == nargs
+        for i in bands + (nargs - 4, nargs - 3):
+            assert entry(*(None if j == i else a for j, a in enumerate(args))) == -1, i
+            assert words in lib.lssvr_last_error(), i
+    # the order of the checks: ne, nc, NULL, end kinds, work_bytes
+    assert sym(ne=0, nc=0) == -2 and b"ne = 0 < 1" in lib.lssvr_last_error()
+    assert sym(nc=0, diag=None) == -2 and b"nc = 0 < 1" in lib.lssvr_last_error()
+    assert sym(diag=None, kl=2) == -1 and sym(kl=2, wb=8) == -2 and b"end kinds" in lib.lssvr_last_error()
+    need = lib.lssvr_tridiag_bc_work_bytes(10, 1)
+    assert sym(wb=need - 1) == -2 and b"work holds %d bytes, lssvr_tridiag_bc_work_bytes(10, 1) = %d" % (
+        need - 1, need) in lib.lssvr_last_error()
     # kappa of a Dirichlet end is not read
     g = (ctypes.c_double * 2)(0.0, 0.0)
 
