@@ -185,6 +185,10 @@ SIGNATURES = {
     "lssvr_nl_residual_host": _sig([_c_hd] * 6, [_c_int, _c_int, _c_hd, _c_hd], [_c_i64, _c_hd]),
     "lssvr_nl_step": _sig([_c_dp, _c_dp, _c_dbl, _c_i64, _c_dp], _STREAM),
     "lssvr_nl_step_host": _sig([_c_hd, _c_hd, _c_dbl, _c_i64, _c_hd]),
+    # semilinear transient problems (additive to ABI 7): x, u, a_quad, cs_quad, q_quad, r, ne, nquad, kind, nterm, diag,
+    # off, rhs
+    "lssvr_ts_nl_assemble": _sig([_c_dp] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dp] * 3, _STREAM),
+    "lssvr_ts_nl_assemble_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_hd] * 3),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

@@ -1729,4 +1729,46 @@ int lssvr_nl_step_host(const double* u_host, const double* u_new_host, double la
   return LSSVR_OK;
 }
 
+// Semilinear transient problems (timestep_nl.hip).  The device and the host entry share one validated binding.
+static int bind_ts_nl_assemble(lssvr::TsNlArgs& a, const double* x, const double* u, const double* a_quad,
+                               const double* cs_quad, const double* q_quad, const double* r, int64_t ne, int nquad,
+                               int kind, int nterm, double* diag, double* off, double* rhs) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  if (kind != LSSVR_NL_POLY && kind != LSSVR_NL_EXP)
+    return fail(LSSVR_ERR_RHS, "unknown kind %d (LSSVR_NL_POLY or LSSVR_NL_EXP)", kind);
+  if (kind == LSSVR_NL_POLY && (nterm < 1 || nterm > 6))
+    return fail(LSSVR_ERR_SIZE, "nterm = %d outside [1, 6]", nterm);
+  if (kind == LSSVR_NL_EXP && nterm != 2) return fail(LSSVR_ERR_SIZE, "nterm = %d: LSSVR_NL_EXP has q_0 and q_1", nterm);
+  if (!x || !u || !cs_quad || !q_quad || !r || !diag || !off || !rhs)
+    return fail(LSSVR_ERR_NULL, "x, u, cs_quad, q_quad, r, diag, off, rhs must be non-NULL");
+  for (const double* o : {(const double*)diag, (const double*)off, (const double*)rhs})
+    if (o == x || o == u || o == a_quad || o == cs_quad || o == q_quad || o == r)
+      return fail(LSSVR_ERR_SIZE, "an output must not be one of the inputs");
+  if (diag == off || diag == rhs || off == rhs) return fail(LSSVR_ERR_SIZE, "diag, off, rhs must be distinct");
+  a = lssvr::TsNlArgs{x, u, a_quad, cs_quad, q_quad, r, ne, nquad, kind, nterm, diag, off, rhs};
+  return LSSVR_OK;
+}
+
+int lssvr_ts_nl_assemble(const double* x, const double* u, const double* a_quad, const double* cs_quad,
+                         const double* q_quad, const double* r, int64_t ne, int nquad, int kind, int nterm,
+                         double* diag, double* off, double* rhs, void* stream) {
+  lssvr::TsNlArgs a{};
+  const int rc = bind_ts_nl_assemble(a, x, u, a_quad, cs_quad, q_quad, r, ne, nquad, kind, nterm, diag, off, rhs);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::ts_nl_assemble(a, reinterpret_cast<hipStream_t>(stream)), "ts_nl_assemble");
+}
+
+int lssvr_ts_nl_assemble_host(const double* x_host, const double* u_host, const double* a_quad_host,
+                              const double* cs_quad_host, const double* q_quad_host, const double* r_host, int64_t ne,
+                              int nquad, int kind, int nterm, double* diag_host, double* off_host, double* rhs_host) {
+  lssvr::TsNlArgs a{};
+  const int rc = bind_ts_nl_assemble(a, x_host, u_host, a_quad_host, cs_quad_host, q_quad_host, r_host, ne, nquad, kind,
+                                     nterm, diag_host, off_host, rhs_host);
+  if (rc != LSSVR_OK) return rc;
+  if (!lssvr::ts_nl_assemble_host(a)) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  return LSSVR_OK;
+}
+
 }  // extern "C"

@@ -461,6 +461,24 @@ void nl_residual_host(const NlResArgs& a, double* out4);
 hipError_t nl_step(const double* u, const double* u_new, double lambda, int64_t ne, double* out, hipStream_t s);
 void nl_step_host(const double* u, const double* u_new, double lambda, int64_t ne, double* out);
 
+// timestep_nl.hip: the Newton matrix and right-hand side of one iteration of a semilinear time step (DESIGN.md
+// section 28).  All tables are [ne][nquad], element-major, at quad_points.
+struct TsNlArgs {
+  const double* x;                  // nodes [ne+1]
+  const double* u;                  // the Newton iterate v_k [ne+1]
+  const double* a_quad;             // nullptr: a = 1
+  const double* cs_quad;            // c + alpha rho / dt
+  const double* q_quad;             // [nterm] tables; EXP: q_0, q_1
+  const double* r;                  // the step's vector of ts_rhs [ne+1]
+  int64_t ne;
+  int nquad, kind, nterm;
+  double* diag;                     // [ne+1], [ne], [ne+1]
+  double* off;
+  double* rhs;
+};
+hipError_t ts_nl_assemble(const TsNlArgs& a, hipStream_t s);
+bool ts_nl_assemble_host(const TsNlArgs& a);      // false: no rule of a.nquad points
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

@@ -14,6 +14,7 @@
 // FP64, -ffp-contract=off.
 #include "lssvr_device.hpp"
 #include "lssvr_kernels.hpp"
+#include "lssvr_nl_family.hpp"
 
 #include <cmath>
 
@@ -34,31 +35,14 @@ int64_t nl_blocks(int64_t n) {
 
 // Entry (e, k) of the tables, idx its position in memory.  The order of every sum:
 //   u_h    = u_e + (u_{e+1} - u_e) t_k
-//   POLY   g = q_K;  g = g u_h + q_k            k = K-1 .. 0      (K = nterm - 1)
-//          d = (double)K q_K;  d = d u_h + (double)k q_k           k = K-1 .. 1;  nterm = 1: d = 0
-//   EXP    E = exp(q_1 u_h);  g = q_0 E;  d = (q_0 q_1) E
+//   g, d   = g and g_u of the family at (point, u_h): nl_family (lssvr_nl_family.hpp)
 //   c_eff  = c + d  (no c_tab: c = 0);   f_eff = (f - g) + d u_h;   f_res = f - g
 LSSVR_NL_HD void nl_entry(const NlLinArgs& a, int64_t e, int k, int64_t idx) {
   const int64_t tab = a.ne * (int64_t)a.n;
   const double u0 = a.u[e];
   const double uh = u0 + (a.u[e + 1] - u0) * a.t_local[k];
   double g, d;
-  if (a.kind == LSSVR_NL_EXP) {
-    const double q0 = a.q_tabs[idx], q1 = a.q_tabs[tab + idx];
-    const double E = exp(q1 * uh);
-    g = q0 * E;
-    d = (q0 * q1) * E;
-  } else {
-    const int K = a.nterm - 1;
-    const double qK = a.q_tabs[(int64_t)K * tab + idx];
-    g = qK;
-    d = K == 0 ? 0.0 : (double)K * qK;
-    for (int j = K - 1; j >= 0; --j) {
-      const double qj = a.q_tabs[(int64_t)j * tab + idx];
-      g = g * uh + qj;
-      if (j >= 1) d = d * uh + (double)j * qj;
-    }
-  }
+  nl_family(a.kind, a.nterm, a.q_tabs, tab, idx, uh, g, d);
   const double fr = a.f_tab[idx] - g;
   if (a.c_eff) a.c_eff[idx] = (a.c_tab ? a.c_tab[idx] : 0.0) + d;
   if (a.f_eff) a.f_eff[idx] = fr + d * uh;

@@ -1951,6 +1951,52 @@ def nl_step(u, u_new, lam, *, out=None, stream=None):
     return out
 
 
+# ---- semilinear transient problems rho u_t - (a u')' + c u + g(x, u) = f ----------------------
+def ts_nl_assemble(x, u, cs_quad, kind, q_quad, r, *, a_quad=None, out=None, stream=None):
+    """``lssvr_ts_nl_assemble``: the bands and the right-hand side of one Newton iteration of a semilinear time step
+    in ONE launch -- bit for bit what :func:`nl_linearize` (``f_tab`` = 0, ``c_tab`` = cs_quad) ->
+    :func:`p1_assemble` (``c_quad`` = c_eff, ``rhs_quad`` = f_eff) -> ``r + load`` gives, without its two tables.
+    ``x``, ``u`` (the iterate) and ``r`` (the step's vector of :func:`ts_rhs`) float64[ne+1]; ``cs_quad``
+    (= c + alpha rho / dt), ``a_quad`` (``None``: a = 1) float64[ne, nquad] and ``q_quad`` float64[nterm, ne, nquad] at
+    :func:`quad_points`, nquad 1 .. 5; ``kind``: ``NL_POLY`` / "poly" or ``NL_EXP`` / "exp"; all on the device.
+    ``out``: a dict with diag[ne+1], off[ne], rhs[ne+1] to write into (``None``: allocated); none of them may be an
+    input.  Returns that dict.  No synchronisation and no copy; bitwise reproducible."""
+    lib = _capi.load()
+    for nm, t in (("x", x), ("u", u), ("cs_quad", cs_quad), ("q_quad", q_quad), ("r", r)):
+        _dev(t, nm)
+    ne = x.numel() - 1
+    if x.dim() != 1 or ne < 1:
+        raise ValueError("x must be 1-D with at least two nodes")
+    for nm, t in (("u", u), ("r", r)):
+        if t.dim() != 1 or t.numel() != ne + 1:
+            raise ValueError(f"{nm} must be [ne+1] = [{ne + 1}], got {list(t.shape)}")
+    if cs_quad.dim() != 2 or cs_quad.shape[0] != ne or not 1 <= cs_quad.shape[1] <= 5:
+        raise ValueError(f"cs_quad must be [ne, nquad] = [{ne}, 1 .. 5], got {list(cs_quad.shape)}")
+    nquad = int(cs_quad.shape[1])
+    if q_quad.dim() != 3 or tuple(q_quad.shape[1:]) != (ne, nquad):
+        raise ValueError(f"q_quad must be [nterm, {ne}, {nquad}], got {list(q_quad.shape)}")
+    kind, nterm = nl_kind(kind, q_quad.shape[0])
+    if a_quad is not None:
+        _dev(a_quad, "a_quad")
+        if a_quad.shape != cs_quad.shape:
+            raise ValueError(f"a_quad must have the shape of cs_quad {list(cs_quad.shape)}, got {list(a_quad.shape)}")
+    want = {"diag": (ne + 1,), "off": (ne,), "rhs": (ne + 1,)}
+    if out is None:
+        out = {}
+    elif not isinstance(out, dict) or any(k not in out for k in want):
+        raise ValueError("out must be a dict with diag, off and rhs")
+    res = {k: _eig_out(out.get(k), k, shape, x) for k, shape in want.items()}
+    ins = [t.data_ptr() for t in (x, u, cs_quad, q_quad, r, a_quad) if t is not None]
+    ptrs = [res[k].data_ptr() for k in want]
+    if any(p in ins for p in ptrs) or len(set(ptrs)) != 3:
+        raise ValueError("diag, off and rhs must be distinct and none of them an input")
+    _same_device(x, u=u, cs_quad=cs_quad, q_quad=q_quad, r=r, a_quad=a_quad)
+    rc = lib.lssvr_ts_nl_assemble(_ptr(x), _ptr(u), _ptr(a_quad), _ptr(cs_quad), _ptr(q_quad), _ptr(r), ne, nquad, kind,
+                                  nterm, _ptr(res["diag"]), _ptr(res["off"]), _ptr(res["rhs"]), _stream(stream))
+    _capi.check(rc, "lssvr_ts_nl_assemble")
+    return res
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

@@ -374,10 +374,14 @@ class TransientSolution:
     * ``nodal`` float64[ns, ne+1]: the P1 nodal values;
     * ``enhanced``: ns :class:`EnhancedSolution` (empty with ``enhance=False``);
     * ``bands``, a diagnostic: host copies of what the loop ran on, as the device assembled it --
-      dict(mass=(mdiag, moff), step={alpha: (diag, off)}, loads [R, ne+1])."""
+      dict(mass=(mdiag, moff), step={alpha: (diag, off)}, loads [R, ne+1]); with ``nonlinear=`` the step matrices are
+      the LINEAR part K + (alpha / dt) M, to which every Newton iteration adds the mass matrix of g_u;
+    * ``newton`` (``None`` without ``nonlinear=``) float64[nsteps, newton_iters, 4]: row [n - 1, k] holds what
+      ``ops.nl_residual`` read in iteration k of step n -- |residual at v_k|_inf, |v_{k+1} - v_k|_inf, |v_{k+1}|_inf
+      and the count of non-finite entries."""
 
-    def __init__(self, times, nodal, enhanced, bands):
-        self.times, self.nodal, self.enhanced, self.bands = times, nodal, enhanced, bands
+    def __init__(self, times, nodal, enhanced, bands, newton=None):
+        self.times, self.nodal, self.enhanced, self.bands, self.newton = times, nodal, enhanced, bands, newton
 
     def evaluate(self, k, x, deriv=0):
         """The enhanced snapshot ``k`` (its ``deriv``-th x-derivative) at the points ``x``."""
@@ -1517,7 +1521,7 @@ class FEMLSSVRPrimalSolver:
                     g=g, quad=quad, colloc=colloc)
 
     def solve_transient(self, u0, t_end, *, nsteps, scheme="bdf2", weight=None, forcing=None, end_data=None,
-                        snapshots=None, enhance=True):
+                        snapshots=None, enhance=True, nonlinear=None, newton_iters=None, newton_tol=None):
         """rho u_t - (a u')' + c u = f(x, t) for 0 < t <= ``t_end`` with u(x, 0) = ``u0(x)``, on the solver's ``mesh``
         with its ``coef``, ``reaction`` and ``boundary`` kinds (each end Dirichlet u = g(t) or Robin
         a du/dn + kappa u = g(t)); ``nsteps`` equal steps of backward Euler (``scheme="bdf1"``) or of BDF2 started by
@@ -1534,8 +1538,32 @@ class FEMLSSVRPrimalSolver:
         problem (w: the nodal BDF difference); with ``enhance`` all snapshots then go through ONE
         ``ops.enhance_multi`` (``lssvr_M``, ``n_colloc``, ``lssvr_gamma``; c itself, not shifted by 1 / dt).  Two
         Neumann ends without a reaction are fine here: M / dt makes the matrix definite.  Returns a
-        :class:`TransientSolution`; the solver's attributes are left as they are."""
-        self._check_nonlinear("solve_transient")
+        :class:`TransientSolution`; the solver's attributes are left as they are.
+
+        ``nonlinear`` = ``("poly", [q0, q1, ...])`` or ``("exp", q0, q1)`` (the specs of the constructor's
+        ``nonlinear=``, given HERE, on a solver built without it) adds g(x, u) to the left-hand side (DESIGN.md section
+        28): every step then runs ``newton_iters`` Newton iterations (a fixed count, 1 .. 8, default 3; no line
+        search) from the extrapolation 2 u^n - u^{n-1} (BDF1 and the first step: u^n), each ONE
+        ``ops.ts_nl_assemble`` -> ``ops.tridiag_bc_solve_multi`` -> ``ops.nl_residual``, whose four numbers go to a
+        device table that is read once, after the loop, with the snapshots (``TransientSolution.newton``).
+        ``RuntimeError`` with the step and its history when a step's last increment exceeds
+        ``newton_tol`` max(1, |v|_inf) (default 1e-10) or a non-finite value was met.  The q_k are tabulated and
+        checked on the host before any device call; that c + alpha rho / dt + g_u >= 0 holds at the iterates cannot
+        be checked without a read-back inside the loop and is not: the solve does not pivot, and the increment test
+        after the loop is the net.  A snapshot is enhanced as the linear problem around its own nodal values, one
+        ``ops.nl_linearize`` at the collocation points and one ``ops.enhance_varcoef`` each (c_eff differs per
+        snapshot).  ``nonlinear=None`` runs exactly the calls above; ``newton_iters`` / ``newton_tol`` then must be
+        left alone."""
+        if self.nonlinear is not None:
+            raise ValueError("solve_transient takes the semilinear term as its own keyword: build the solver without "
+                             "nonlinear= and call solve_transient(..., nonlinear=...)")
+        if nonlinear is None:
+            if newton_iters is not None or newton_tol is not None:
+                raise ValueError("newton_iters and newton_tol belong to solve_transient(..., nonlinear=...)")
+        else:
+            return self._solve_transient_nl(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots,
+                                            bool(enhance), nonlinear, 3 if newton_iters is None else newton_iters,
+                                            1e-10 if newton_tol is None else newton_tol)
         torch = _torch()
         p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, bool(enhance))
         nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
@@ -1595,6 +1623,122 @@ class FEMLSSVRPrimalSolver:
         bands = dict(mass=(parts[1], parts[2]), loads=parts[-1].reshape(-1, ne + 1),
                      step={al: (parts[3 + 2 * i], parts[4 + 2 * i]) for i, al in enumerate(sorted(A))})
         return TransientSolution(p["times"][steps].copy(), parts[0].reshape(ns, ne + 1), enhanced, bands)
+
+    def _solve_transient_nl(self, u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance, nonlinear,
+                            newton_iters, newton_tol):
+        """:meth:`solve_transient` with ``nonlinear=``.  Everything the host can check is
+        checked before the first device call; the loop is launches on the current stream only."""
+        nl = _Nonlinear(nonlinear)
+        if isinstance(newton_iters, bool) or int(newton_iters) != newton_iters or not 1 <= int(newton_iters) <= 8:
+            raise ValueError(f"newton_iters must be an integer in 1 .. 8, got {newton_iters!r}")
+        if not (float(newton_tol) > 0.0) or not math.isfinite(float(newton_tol)):
+            raise ValueError(f"newton_tol must be finite and > 0, got {newton_tol!r}")
+        iters, tol = int(newton_iters), float(newton_tol)
+        p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance)
+        nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
+        n = int(self.n_colloc)
+        if enhance and n > ops.NL_MAX_POINTS:
+            raise ValueError(f"nonlinear needs n_colloc <= {ops.NL_MAX_POINTS} for the enhanced snapshots, got {n}")
+        xq_host, xc_host = self._nl_host_points(nodes)
+        qq_host = nl.host_tables(xq_host, "quadrature")
+        qc_host = nl.host_tables(xc_host, "collocation") if enhance else None
+        # ---- the device from here on
+        torch = _torch()
+        nsteps, ne, ns, inv_dt = int(nsteps), nodes.size - 1, len(steps), 1.0 / dt
+        dev = _device(self.device)
+        x = _to_dev(nodes, dev)
+        zq = torch.zeros((ne, int(self.nquad)), dtype=torch.float64, device=dev)
+        aq = None if self.coef is None else _to_dev(q["a"], dev)
+        Mb = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["rho"], dev))
+        alphas = {ops.BDF["bdf1"][0], ops.BDF[scheme][0]}
+        cs = {al: _to_dev(q["c"] + al * q["rho"] / dt, dev) for al in alphas}
+        A = {al: ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=cs[al]) for al in alphas}   # (diagnostic)
+        qq = _to_dev(qq_host, dev)
+        loads = ops.p1_load_multi(x, _to_dev(q["f"], dev), self.nquad)
+        phi, g = _to_dev(p["phi"], dev), _to_dev(p["g"][1:], dev)          # row n - 1: the step that ends at t_n
+        M, gamma = int(self.lssvr_M), float(self.lssvr_gamma)
+        pm = _point_major(M)
+        if enhance:
+            c = p["colloc"]
+            ta, tda, tc, rtab = (_to_dev(c[k].T if pm else c[k], dev) for k in ("a", "da", "c", "rho"))
+            ftab = _to_dev(np.transpose(c["f"], (0, 2, 1)) if pm else c["f"], dev)
+            qc = _to_dev(np.transpose(qc_host, (0, 2, 1)) if pm else qc_host, dev)
+            tloc = torch.arange(n, dtype=torch.float64, device=dev) / float(n - 1)
+            src = torch.empty(tuple(rtab.shape), dtype=torch.float64, device=dev)
+            c_eff, f_eff = (torch.empty((ns,) + tuple(rtab.shape), dtype=torch.float64, device=dev) for _ in range(2))
+        U = torch.empty((3, ne + 1), dtype=torch.float64, device=dev)
+        U[0].copy_(_to_dev(p["u_init"], dev))
+        V = torch.empty((2, ne + 1), dtype=torch.float64, device=dev)         # the Newton iterates of a step
+        S = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
+        b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)         # r of the step
+        rhs = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
+        nb = dict(diag=torch.empty(ne + 1, dtype=torch.float64, device=dev),
+                  off=torch.empty(ne, dtype=torch.float64, device=dev), rhs=rhs[0])
+        mon = torch.zeros((nsteps, iters, 4), dtype=torch.float64, device=dev)
+        work = ops.tridiag_work(b, ne, 1, "bc")
+        rwork = ops._scratch(None, ops._capi.load().lssvr_nl_residual_work_bytes(ne), dev)
+        md, mo = Mb["diag"], Mb["off"]
+        bdf1 = ops.BDF["bdf1"]
+        snap = {s: k for k, s in enumerate(steps)}
+        cur, prev, new = 0, 1, 2
+        # the loop: launches on the current stream only
+        for step in range(1, nsteps + 1):
+            al, b0, b1 = bdf1 if step == 1 else ops.BDF[scheme]
+            u_prev = None if b1 == 0.0 else U[prev:prev + 1]
+            ops.ts_rhs(md, mo, U[cur:cur + 1], u_prev, loads, phi[step - 1:step], b0, b1, inv_dt, out=b)
+            if b1 == 0.0:
+                V[0].copy_(U[cur])
+            else:
+                ops.nl_step(U[prev], U[cur], 2.0, out=V[0])
+            v, spare = V[0], V[1]
+            for k in range(iters):
+                tgt = U[new] if k == iters - 1 else spare
+                ops.ts_nl_assemble(x, v, cs[al], nl.kind, qq, b[0], a_quad=aq, out=nb)
+                ops.tridiag_bc_solve_multi(nb["diag"], nb["off"], rhs, kinds, kappa, g[step - 1:step],
+                                           out=tgt.unsqueeze(0), work=work)
+                ops.nl_residual(nb["diag"], nb["off"], nb["off"], nb["rhs"], v, tgt, kinds, kappa, g[step - 1],
+                                out4=mon[step - 1, k], work=rwork)
+                v, spare = tgt, v
+            k = snap.get(step)
+            if k is not None:
+                S[k].copy_(U[new])
+                if enhance:
+                    ops.ts_source_table(U[new], U[cur], None if b1 == 0.0 else U[prev], ftab, rtab, phi[step - 1], al,
+                                        b0, b1, inv_dt, point_major=pm, out=src)
+                    ops.nl_linearize(U[new], tloc, nl.kind, qc, src, c_tab=tc, point_major=pm, c_eff=c_eff[k],
+                                     f_eff=f_eff[k])
+            cur, prev, new = new, cur, prev
+        enhanced = []
+        if enhance:
+            gd = (float(self.global_domain[0]), float(self.global_domain[1]))
+            shard = self._shard(ne)
+            for k, s in enumerate(steps):
+                W, st = ops.enhance_varcoef(x, S[k], M, gamma, n, ta, tda, f_eff[k], global_domain=gd,
+                                            bc=(float(p["g"][s, 0]), float(p["g"][s, 1])), point_major=pm,
+                                            c_values=c_eff[k], **shard)
+                enhanced.append(EnhancedSolution(x, W, st))
+        host = torch.cat([S.reshape(-1), md, mo, *(A[al][k] for al in sorted(A) for k in ("diag", "off")),
+                          loads.reshape(-1), mon.reshape(-1)]).cpu().numpy()     # one copy: snapshots, bands, monitor
+        cut = np.cumsum([ns * (ne + 1), ne + 1, ne] + [ne + 1, ne] * len(A) + [loads.numel()])
+        parts = np.split(host, cut)
+        bands = dict(mass=(parts[1], parts[2]), loads=parts[-2].reshape(-1, ne + 1),
+                     step={al: (parts[3 + 2 * i], parts[4 + 2 * i]) for i, al in enumerate(sorted(A))})
+        newton = parts[-1].reshape(nsteps, iters, 4)
+
+        def history(i):
+            return ", ".join(f"|R| {r:.3e} |dv| {d:.3e}" for r, d, _, _ in newton[i])
+        bad = np.nonzero(newton[:, :, 3].sum(axis=1) != 0.0)[0]
+        if bad.size:
+            i = int(bad[0])
+            raise RuntimeError(f"solve_transient: step {i + 1} met {int(newton[i, :, 3].sum())} non-finite value(s) in "
+                               f"its Newton iteration ({history(i)}); shorten the step")
+        last = newton[:, -1, :]
+        slow = np.nonzero(last[:, 1] > tol * np.maximum(1.0, last[:, 2]))[0]
+        if slow.size:
+            i = int(slow[0])
+            raise RuntimeError(f"solve_transient: step {i + 1} did not converge in {iters} Newton iteration(s) to "
+                               f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
+        return TransientSolution(p["times"][steps].copy(), parts[0].reshape(ns, ne + 1), enhanced, bands, newton)
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):

@@ -1123,6 +1123,46 @@ int lssvr_nl_residual_host(const double* diag_host, const double* sub_host, cons
 int lssvr_nl_step(const double* u, const double* u_new, double lambda, int64_t ne, double* out, void* stream);
 int lssvr_nl_step_host(const double* u_host, const double* u_new_host, double lambda, int64_t ne, double* out_host);
 
+/*
+ * Semilinear transient problems: rho u_t - (a u')' + c u + g(x, u) = f(x, t), BDF1 / BDF2 with a fixed step and a fixed
+ * number of Newton iterations per step (no reference counterpart).  ADDITIVE to ABI 7: two new
+ * symbols, no existing entry, struct or constant changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * Step n+1 solves  (alpha / dt) M v + K v + G(v) = r  for v = u^{n+1}, r the vector lssvr_ts_rhs writes (once per
+ * step).  The Newton iterate v_k -> v_{k+1} is the LINEAR problem with the reaction cs + g_u(x, v_k,h),
+ * cs = c + alpha rho / dt, and the right-hand side r + L(-g + g_u v_k,h), v_k,h the P1 interpolant of v_k and L the P1
+ * load assembly, solved for v_{k+1} itself by lssvr_tridiag_bc_solve_multi with the end values g(t_{n+1}) of the step.
+ * lssvr_nl_residual on the iteration's own bands and right-hand side with u = v_k, u_new = v_{k+1} is the monitor: its
+ * first number is the nonlinear residual at v_k (M(g_u) v_k = L(g_u v_k,h) under one quadrature), its second the
+ * increment.  The start is lssvr_nl_step(u^{n-1}, u^n, 2) for BDF2 and u^n otherwise.  Nothing here synchronises or
+ * copies: a time loop is launches on one stream.
+ *
+ * lssvr_ts_nl_assemble -- the bands diag [ne+1], off [ne] and the right-hand side rhs [ne+1] of one Newton iteration
+ * in ONE launch: what lssvr_nl_linearize (f_tab = 0, c_tab = cs_quad) -> lssvr_p1_assemble_react -> r + load gives, bit
+ * for bit, without its two [ne][nquad] tables.  x, u, r [ne+1]; a_quad (NULL: a = 1), cs_quad and the nterm tables
+ * q_quad are [ne][nquad], element-major, at lssvr_quad_points; kind / nterm as for lssvr_nl_linearize; all DEVICE
+ * arrays.  One thread per node gathers its right and its left element; no atomics: bitwise reproducible.  Per
+ * quadrature point (xi, w) of an element of length h, idx = e nquad + k:
+ *   u_h = u_e + (u_{e+1} - u_e) xi;  g, g_u as for lssvr_nl_linearize;  c_eff = cs + g_u;  f_eff = (0 - g) + g_u u_h;
+ *   sl += (w (1 - xi)) f_eff;  sr += (w xi) f_eff;  am += w a;
+ *   ll += (w c_eff) ((1 - xi)(1 - xi));  lr += (w c_eff) ((1 - xi) xi);  rr += (w c_eff) (xi xi);
+ * then k = am / h (a_quad NULL: 1 / h), fl = h sl, fr = h sr, m_ll = h ll, m_lr = h lr, m_rr = h rr, and per node i
+ *   d = 0;  d += k + m_ll (right element);  d += k + m_rr (left element);   l = 0;  l += fl (right);  l += fr (left);
+ *   diag[i] = d;  off[i] = m_lr - k (right element);  rhs[i] = r[i] + l.
+ * Return codes: an unknown kind is LSSVR_ERR_RHS; nterm outside the kind's range, ne < 1 and an output that is one of
+ * the inputs or another output are LSSVR_ERR_SIZE; nquad outside [1, 5] is LSSVR_ERR_QUAD; a missing pointer is
+ * LSSVR_ERR_NULL.
+ *
+ * lssvr_ts_nl_assemble_host -- the same routine on HOST arrays: no device is touched.  Bit for bit the device's values,
+ * except that exp of LSSVR_NL_EXP is the host's libm there.
+ */
+int lssvr_ts_nl_assemble(const double* x, const double* u, const double* a_quad, const double* cs_quad,
+                         const double* q_quad, const double* r, int64_t ne, int nquad, int kind, int nterm,
+                         double* diag, double* off, double* rhs, void* stream);
+int lssvr_ts_nl_assemble_host(const double* x_host, const double* u_host, const double* a_quad_host,
+                              const double* cs_quad_host, const double* q_quad_host, const double* r_host, int64_t ne,
+                              int nquad, int kind, int nterm, double* diag_host, double* off_host, double* rhs_host);
+
 #ifdef __cplusplus
 }
 #endif
