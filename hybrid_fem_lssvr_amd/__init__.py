@@ -13,6 +13,7 @@ from .solver import (  # noqa: F401
     FEMLSSVRPrimalSolver,
     GoalEstimate,
     TransientSolution,
+    WaveSolution,
     SinRHS,
     enhance_elements,
     enhance_elements_hetero,

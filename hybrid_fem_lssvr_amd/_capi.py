@@ -189,6 +189,10 @@ SIGNATURES = {
     # off, rhs
     "lssvr_ts_nl_assemble": _sig([_c_dp] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dp] * 3, _STREAM),
     "lssvr_ts_nl_assemble_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_hd] * 3),
+    # wave problems (additive to ABI 7): U_new, U, V, Acc, mdiag, moff, ddiag, doff, loads, phi, ne, nc, R, dt, beta,
+    # gamma, V_out, Acc_out, rhs_out
+    "lssvr_wave_advance": _sig([_c_dp] * 10, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_dp] * 3, _STREAM),
+    "lssvr_wave_advance_host": _sig([_c_hd] * 10, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_hd] * 3),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

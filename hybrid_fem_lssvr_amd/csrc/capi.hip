@@ -1771,4 +1771,67 @@ int lssvr_ts_nl_assemble_host(const double* x_host, const double* u_host, const 
   return LSSVR_OK;
 }
 
+// Wave problems (wave.hip).  The device and the host entry share one validated binding.
+static int bind_wave_advance(lssvr::WaveArgs& a, const double* U_new, const double* U, const double* V,
+                             const double* Acc, const double* mdiag, const double* moff, const double* ddiag,
+                             const double* doff, const double* loads, const double* phi, int64_t ne, int nc, int R,
+                             double dt, double beta, double gamma, const double* V_out, const double* Acc_out,
+                             const double* rhs_out) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (nc < 1 || nc > 8) return fail(LSSVR_ERR_SIZE, "nc = %d outside [1, 8]", nc);
+  if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
+  if (!(ts_finite(dt) && dt > 0.0) || !(ts_finite(beta) && beta > 0.0) || !(ts_finite(gamma) && gamma > 0.0))
+    return fail(LSSVR_ERR_SIZE, "dt = %g, beta = %g, gamma = %g must be finite and > 0", dt, beta, gamma);
+  if (!U_new && !rhs_out)
+    return fail(LSSVR_ERR_SIZE, "U_new and rhs_out are both NULL: there is nothing to compute");
+  if (!U || !V || !Acc) return fail(LSSVR_ERR_NULL, "U, V, Acc must be non-NULL");
+  if (U_new && (!V_out || !Acc_out)) return fail(LSSVR_ERR_NULL, "V_out, Acc_out must be non-NULL with U_new");
+  if (rhs_out && (!mdiag || !moff || !loads || !phi))
+    return fail(LSSVR_ERR_NULL, "mdiag, moff, loads, phi must be non-NULL with rhs_out");
+  if (rhs_out && ddiag && !doff) return fail(LSSVR_ERR_NULL, "doff must be non-NULL with ddiag");
+  if (U_new) {
+    // a thread recomputes its neighbours' correctors from the old arrays while their owners write the new ones
+    if (V_out == V || V_out == Acc || Acc_out == V || Acc_out == Acc || V_out == U || Acc_out == U ||
+        V_out == U_new || Acc_out == U_new)
+      return fail(LSSVR_ERR_SIZE, "V_out, Acc_out must not be V, Acc, U or U_new (neighbours read the old values)");
+    if (V_out == Acc_out) return fail(LSSVR_ERR_SIZE, "V_out and Acc_out must differ");
+  }
+  if (rhs_out) {
+    if (rhs_out == U || rhs_out == V || rhs_out == Acc || rhs_out == U_new || rhs_out == loads)
+      return fail(LSSVR_ERR_SIZE, "rhs_out must not be U_new, U, V, Acc or loads");
+    if (U_new && (rhs_out == V_out || rhs_out == Acc_out))
+      return fail(LSSVR_ERR_SIZE, "rhs_out must not be V_out or Acc_out");
+  }
+  a = lssvr::WaveArgs{U_new, U, V, Acc, mdiag, moff, ddiag, ddiag ? doff : nullptr, loads, phi, ne, nc, R};
+  lssvr::wave_coefficients(a, dt, beta, gamma);
+  return LSSVR_OK;
+}
+
+int lssvr_wave_advance(const double* U_new, const double* U, const double* V, const double* Acc, const double* mdiag,
+                       const double* moff, const double* ddiag, const double* doff, const double* loads,
+                       const double* phi, int64_t ne, int nc, int R, double dt, double beta, double gamma,
+                       double* V_out, double* Acc_out, double* rhs_out, void* stream) {
+  lssvr::WaveArgs a{};
+  const int rc = bind_wave_advance(a, U_new, U, V, Acc, mdiag, moff, ddiag, doff, loads, phi, ne, nc, R, dt, beta,
+                                   gamma, V_out, Acc_out, rhs_out);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::wave_advance(a, V_out, Acc_out, rhs_out, reinterpret_cast<hipStream_t>(stream)),
+                      "wave_advance");
+}
+
+int lssvr_wave_advance_host(const double* U_new_host, const double* U_host, const double* V_host,
+                            const double* Acc_host, const double* mdiag_host, const double* moff_host,
+                            const double* ddiag_host, const double* doff_host, const double* loads_host,
+                            const double* phi_host, int64_t ne, int nc, int R, double dt, double beta, double gamma,
+                            double* V_out_host, double* Acc_out_host, double* rhs_out_host) {
+  lssvr::WaveArgs a{};
+  const int rc = bind_wave_advance(a, U_new_host, U_host, V_host, Acc_host, mdiag_host, moff_host, ddiag_host,
+                                   doff_host, loads_host, phi_host, ne, nc, R, dt, beta, gamma, V_out_host,
+                                   Acc_out_host, rhs_out_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::wave_advance_host(a, V_out_host, Acc_out_host, rhs_out_host);
+  return LSSVR_OK;
+}
+
 }  // extern "C"

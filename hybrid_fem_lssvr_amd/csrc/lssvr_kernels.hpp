@@ -479,6 +479,29 @@ struct TsNlArgs {
 hipError_t ts_nl_assemble(const TsNlArgs& a, hipStream_t s);
 bool ts_nl_assemble_host(const TsNlArgs& a);      // false: no rule of a.nquad points
 
+// wave.hip: Newmark steps of rho u_tt + d u_t - (a u')' + c u = f.  Vectors are case-major
+// [nc][ne+1]; the host form runs the same inline routines on host arrays, bit for bit.
+struct WaveArgs {
+  const double* U_new;              // the solve's result [nc][ne+1]; nullptr: (U, V, Acc) is the state already
+  const double* U;                  // [nc][ne+1] each
+  const double* V;
+  const double* Acc;
+  const double* mdiag;              // the mass bands of rho: [ne+1], [ne]
+  const double* moff;
+  const double* ddiag;              // the mass bands of d; ddiag == nullptr: d = 0, neither is read
+  const double* doff;
+  const double* loads;              // [R][ne+1], shared by the cases; read with rhs_out only, like phi [nc][R]
+  const double* phi;
+  int64_t ne;
+  int nc, R;
+  double dt, c_u2, c_v1, c_m, c_d, c_va;      // set by wave_coefficients
+};
+// the scalars of the kernel from (dt, beta, gamma), once, on the host, for the device and the host form alike
+void wave_coefficients(WaveArgs& a, double dt, double beta, double gamma);
+// V_out, Acc_out (written when a.U_new is given) and rhs_out (written unless nullptr), each [nc][ne+1]
+hipError_t wave_advance(const WaveArgs& a, double* V_out, double* Acc_out, double* rhs_out, hipStream_t s);
+void wave_advance_host(const WaveArgs& a, double* V_out, double* Acc_out, double* rhs_out);
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

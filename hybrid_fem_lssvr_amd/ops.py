@@ -1997,6 +1997,85 @@ def ts_nl_assemble(x, u, cs_quad, kind, q_quad, r, *, a_quad=None, out=None, str
     return res
 
 
+# ---- wave problems rho u_tt + d u_t - (a u')' + c u = f, Newmark --------------------------------
+def wave_advance(U_new, U, V, Acc, mdiag, moff, ddiag, doff, loads, phi, dt, beta, gamma, *, V_out=None, Acc_out=None,
+                 rhs_out=None, rhs=True, stream=None):
+    """``lssvr_wave_advance``: ONE launch of a Newmark step for ``nc`` cases -- the correctors of the step just solved,
+    Acc_out = (U_new - ut) / (beta dt^2), V_out = vt + gamma dt Acc_out with ut = U + dt V + dt^2 (1/2 - beta) Acc,
+    vt = V + dt (1 - gamma) Acc, and the right-hand side of the next step from the new state (u, v, acc),
+    rhs_out[j] = M_rho (ut / (beta dt^2)) + M_d ((gamma / (beta dt)) ut - vt) + sum_r phi[j, r] loads[r].  U_new, U, V,
+    Acc float64[nc, ne+1] (nc <= 8), the mass bands M_rho = (mdiag[ne+1], moff[ne]) and M_d = (ddiag, doff)
+    (``ddiag=None``: d = 0, neither is read), loads float64[R, ne+1] (R <= 8), phi float64[nc, R], all on the device.
+    ``U_new=None``: (U, V, Acc) is the state already and only rhs_out is written (the first step);  ``rhs=False``: the
+    correctors only (the last step, or a split call; the bands, loads and phi may be ``None``).  V_out and Acc_out
+    must not be V, Acc, U or U_new: every thread recomputes its neighbours' correctors from the old arrays, which is
+    what lets one launch do both without a barrier.  No synchronisation and no copy; the sums run in a fixed order
+    (bitwise reproducible, and the fused call equals the split pair bit for bit).  Returns (V_out, Acc_out, rhs_out),
+    ``None`` for what the mode does not write."""
+    lib = _capi.load()
+    if U_new is None and not rhs:
+        raise ValueError("U_new=None with rhs=False leaves nothing to compute")
+    for nm, t in (("U", U), ("V", V), ("Acc", Acc)):
+        _dev(t, nm)
+    dt, beta, gamma = _ts_scalars(dt=dt, beta=beta, gamma=gamma)
+    if not (dt > 0.0 and beta > 0.0 and gamma > 0.0):
+        raise ValueError(f"dt, beta and gamma must be > 0, got {dt!r}, {beta!r}, {gamma!r}")
+    if U.dim() != 2 or U.shape[1] < 2 or not 1 <= U.shape[0] <= TRIDIAG_MULTI_CASES:
+        raise ValueError(f"U must be [nc, ne+1] with nc in 1 .. {TRIDIAG_MULTI_CASES} and ne >= 1, got {list(U.shape)}")
+    nc, ne = int(U.shape[0]), int(U.shape[1]) - 1
+    named = {"V": V, "Acc": Acc}
+    if U_new is not None:
+        _dev(U_new, "U_new")
+        named["U_new"] = U_new
+    for nm, t in named.items():
+        if t.shape != U.shape:
+            raise ValueError(f"{nm} must have the shape of U {list(U.shape)}, got {list(t.shape)}")
+    R = 1
+    if rhs:
+        for nm, t in (("mdiag", mdiag), ("moff", moff), ("loads", loads), ("phi", phi)):
+            if t is None:
+                raise ValueError(f"{nm} is needed for the right-hand side")
+            _dev(t, nm)
+        if mdiag.dim() != 1 or moff.dim() != 1 or mdiag.numel() != ne + 1 or moff.numel() != ne:
+            raise ValueError(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (mdiag, moff)")
+        if loads.dim() != 2 or loads.shape[1] != ne + 1 or not 1 <= loads.shape[0] <= TS_MAX_TERMS:
+            raise ValueError(f"loads must be [R, ne+1] = [1 .. {TS_MAX_TERMS}, {ne + 1}], got {list(loads.shape)}")
+        R = int(loads.shape[0])
+        if tuple(phi.shape) != (nc, R):
+            raise ValueError(f"phi must be [nc, R] = [{nc}, {R}], got {list(phi.shape)}")
+        named.update(mdiag=mdiag, moff=moff, loads=loads, phi=phi)
+        if ddiag is not None:
+            if doff is None:
+                raise ValueError("doff is needed with ddiag")
+            for nm, t in (("ddiag", ddiag), ("doff", doff)):
+                _dev(t, nm)
+            if ddiag.dim() != 1 or doff.dim() != 1 or ddiag.numel() != ne + 1 or doff.numel() != ne:
+                raise ValueError(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (ddiag, doff)")
+            named.update(ddiag=ddiag, doff=doff)
+    else:
+        mdiag = moff = ddiag = doff = loads = phi = None
+    if ddiag is None:
+        doff = None
+    outs = {}
+    if U_new is not None:
+        outs["V_out"] = _eig_out(V_out, "V_out", tuple(U.shape), U)
+        outs["Acc_out"] = _eig_out(Acc_out, "Acc_out", tuple(U.shape), U)
+    if rhs:
+        outs["rhs_out"] = _eig_out(rhs_out, "rhs_out", tuple(U.shape), U)
+    ins = {t.data_ptr() for t in (U, *named.values())}
+    ptrs = [t.data_ptr() for t in outs.values()]
+    if any(p in ins for p in ptrs) or len(set(ptrs)) != len(ptrs):
+        raise ValueError("V_out, Acc_out and rhs_out must be distinct and none of them an input (neighbours read the "
+                         "old values)")
+    _same_device(U, **named)
+    rc = lib.lssvr_wave_advance(_ptr(U_new), _ptr(U), _ptr(V), _ptr(Acc), _ptr(mdiag), _ptr(moff), _ptr(ddiag),
+                                _ptr(doff), _ptr(loads), _ptr(phi), ne, nc, R, dt, beta, gamma,
+                                _ptr(outs.get("V_out")), _ptr(outs.get("Acc_out")), _ptr(outs.get("rhs_out")),
+                                _stream(stream))
+    _capi.check(rc, "lssvr_wave_advance")
+    return outs.get("V_out"), outs.get("Acc_out"), outs.get("rhs_out")
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

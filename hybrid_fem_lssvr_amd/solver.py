@@ -391,6 +391,29 @@ class TransientSolution:
         return self.enhanced[k].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
 
 
+class WaveSolution:
+    """What :meth:`FEMLSSVRPrimalSolver.solve_wave` returns for its ``ns`` snapshots, in ascending time:
+
+    * ``times`` float64[ns];
+    * ``nodal``, ``velocity``, ``accel`` float64[ns, ne+1]: the nodal u, u_t and u_tt of the Newmark rule;
+    * ``energy`` float64[ns + 1]: 1/2 v^T M_rho v + 1/2 u^T K u + 1/2 sum over the Robin ends of kappa u_end^2 at
+      t = 0 (index 0) and at every snapshot (index k + 1), over all nodes;
+    * ``enhanced``: ns :class:`EnhancedSolution` (empty with ``enhance=False``);
+    * ``bands``, a diagnostic: host copies of what the loop ran on, as the device assembled it --
+      dict(mass=(mdiag, moff), damp=(ddiag, doff) or None, stiff=(kdiag, koff), step=(diag, off), loads [R, ne+1])."""
+
+    def __init__(self, times, nodal, velocity, accel, energy, enhanced, bands):
+        self.times, self.nodal, self.velocity, self.accel = times, nodal, velocity, accel
+        self.energy, self.enhanced, self.bands = energy, enhanced, bands
+
+    def evaluate(self, k, x, deriv=0):
+        """The enhanced snapshot ``k`` (its ``deriv``-th x-derivative) at the points ``x``."""
+        if not self.enhanced:
+            raise RuntimeError("solve_wave ran with enhance=False: there are no enhanced snapshots to evaluate")
+        x = np.asarray(x, dtype=np.float64)
+        return self.enhanced[k].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
+
+
 class _ElementFunctions:
     """``solver.lssvr_functions``: a read-only sequence whose item i is
     ``Legendre(W[i], [x_i, x_{i+1}])`` (Dual.py:95, 163) -- built lazily from the device
@@ -1415,33 +1438,51 @@ class FEMLSSVRPrimalSolver:
         return EigenSolution(th[:k].copy(), values, res[:k].copy(), index, it, converged, nodal, modes, sigma)
 
     # ---- transient problems (no reference counterpart) --------------------
-    def _check_transient(self, u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance):
+    def _check_transient(self, u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance, wave=None):
         """What :meth:`solve_transient` does not cover and what its data must satisfy, on the host and before any
         device call -> dict(nodes, kinds, kappa, dt, times, steps, u_init, phi [nsteps, R], g [nsteps + 1, 2], quad,
         colloc).  Every callable is evaluated here, once per kind of point, and ``quad`` / ``colloc`` are its host
         tables, the ones the device is handed: a, c, rho [ne, nquad] and f [R, ne, nquad] at the Gauss points of the
         assembly; with ``enhance`` a, da, c, rho [ne, n_colloc] and f [R, ne, n_colloc] at np.linspace(x_e, x_e+1,
-        n_colloc), the abscissae lssvr_colloc_points writes (else None)."""
+        n_colloc), the abscissae lssvr_colloc_points writes (else None).
+
+        ``wave`` = dict(v0, damping, beta, gamma, end_accel0) makes it the check of :meth:`solve_wave` (``scheme`` is
+        not read): the tables gain d, phi gains the row of t = 0 ([nsteps + 1, R]), the dict gains v_init, beta, gamma
+        and accel0 [2], and the matrix that must stay definite is the one of the Newmark step."""
+        me = "solve_transient" if wave is None else "solve_wave"
         if self.convection is not None:
-            raise ValueError("solve_transient has no convection term: the step's matrix would need the non-symmetric "
+            raise ValueError(f"{me} has no convection term: the step's matrix would need the non-symmetric "
                              "solve and a cell Peclet check per step size")
         if self._periodic:
-            raise ValueError("solve_transient has no boundary='periodic': the time loop runs the solve with Dirichlet "
+            raise ValueError(f"{me} has no boundary='periodic': the time loop runs the solve with Dirichlet "
                              "or Robin ends")
         if self.fem_solver != "bands":
-            raise ValueError("solve_transient needs fem_solver='bands': the step's matrix K + (alpha / dt) M carries "
+            raise ValueError(f"{me} needs fem_solver='bands': the step's matrix carries "
                              "a mass matrix (no flux solve) and is definite (no pivoting)")
         if self.element_degrees is not None:
-            raise ValueError("solve_transient has no element_degrees: all snapshots are enhanced as cases of one "
+            raise ValueError(f"{me} has no element_degrees: all snapshots are enhanced as cases of one "
                              "ops.enhance_multi, which has one degree")
         if self.solver_id != ops.SOLVER_PRIMAL:
-            raise ValueError("solve_transient needs solver=ops.SOLVER_PRIMAL: the snapshots are enhanced through the "
+            raise ValueError(f"{me} needs solver=ops.SOLVER_PRIMAL: the snapshots are enhanced through the "
                              "reaction rows, which have a primal solve only")
         if not callable(u0):
             raise ValueError("u0 must be a callable u0(x)")
         if weight is not None and not callable(weight):
             raise ValueError("weight must be a callable rho(x) or None")
-        if scheme not in ops.BDF:
+        if wave is not None:
+            beta, gamma = float(wave["beta"]), float(wave["gamma"])
+            if not (math.isfinite(beta) and math.isfinite(gamma)):
+                raise ValueError(f"beta and gamma must be finite, got {wave['beta']!r}, {wave['gamma']!r}")
+            # (the bound itself is allowed: 0.25 * (0.6 + 0.5) ** 2 rounds one ulp above 0.3025)
+            if gamma < 0.5 or beta * (1.0 + 2.0 ** -50) < 0.25 * (gamma + 0.5) ** 2:
+                raise ValueError(f"beta = {beta!r}, gamma = {gamma!r}: the Newmark rule is unconditionally stable for "
+                                 "gamma >= 1/2 and beta >= (gamma + 1/2)^2 / 4 only, and the step is not checked "
+                                 "against the mesh")
+            if not callable(wave["v0"]):
+                raise ValueError("v0 must be a callable v0(x)")
+            if wave["damping"] is not None and not callable(wave["damping"]):
+                raise ValueError("damping must be a callable d(x) or None")
+        elif scheme not in ops.BDF:
             raise ValueError(f"scheme must be 'bdf1' or 'bdf2', got {scheme!r}")
         if isinstance(nsteps, bool) or int(nsteps) != nsteps or int(nsteps) < 1:
             raise ValueError(f"nsteps must be an integer >= 1, got {nsteps!r}")
@@ -1471,7 +1512,7 @@ class FEMLSSVRPrimalSolver:
         nodes = np.asarray(m.nodes, dtype=np.float64)
         dt = t_end / nsteps
         times = dt * np.arange(nsteps + 1)
-        phi = np.array([[float(p(t)) for p in pfn] for t in times[1:]], dtype=np.float64)
+        phi = np.array([[float(p(t)) for p in pfn] for t in (times[1:] if wave is None else times)], dtype=np.float64)
         g = np.array([[float(v(t)) for v in gfn] for t in times], dtype=np.float64)
         # the data at the Gauss points of the assembly, a + h xi on [0, 1] as lssvr_quad_points has them, and at the
         # collocation points: finite, one value per point, rho > 0, c + rho / dt >= 0
@@ -1480,12 +1521,16 @@ class FEMLSSVRPrimalSolver:
         eq = self._eq
         fns = dict(a=_one if eq.a is None else eq.a, da=_zero if eq.da is None else eq.da,
                    c=_zero if eq.c is None else eq.c, rho=_one if weight is None else weight)
+        extra = ()
+        if wave is not None and wave["damping"] is not None:
+            fns["d"], extra = wave["damping"], ("d",)
 
         def tables(pts, names, what):
             out = {}
             for nm, fn in (*((k, fns[k]) for k in names), *((r, f) for r, (_, f) in enumerate(forcing))):
                 label = f"forcing[{nm}] f_x" if isinstance(nm, int) else {"a": "coef a", "da": "coef da",
-                                                                          "c": "reaction", "rho": "weight"}[nm]
+                                                                          "c": "reaction", "rho": "weight",
+                                                                          "d": "damping"}[nm]
                 try:
                     t = np.broadcast_to(np.asarray(fn(pts), dtype=np.float64), pts.shape)
                 except ValueError:
@@ -1497,28 +1542,54 @@ class FEMLSSVRPrimalSolver:
             out["f"] = np.stack([out.pop(r) for r in range(len(forcing))])
             return out
 
-        quad = tables(xq, ("a", "c", "rho"), "quadrature")
+        quad = tables(xq, ("a", "c", "rho") + extra, "quadrature")
         colloc = None
         if enhance:
             n = int(self.n_colloc)
             if n < 2:
                 raise ValueError(f"n_colloc must be >= 2, got {n}")
-            colloc = tables(np.linspace(nodes[:-1], nodes[1:], n, axis=-1), ("a", "da", "c", "rho"), "collocation")
+            colloc = tables(np.linspace(nodes[:-1], nodes[1:], n, axis=-1), ("a", "da", "c", "rho") + extra,
+                            "collocation")
         u_init = np.array(np.broadcast_to(np.asarray(u0(nodes), dtype=np.float64), nodes.shape))
         for i, end in ((0, 0), (1, -1)):
             if kinds[i] == ops.END_DIRICHLET:
                 u_init[end] = g[0, i]
-        for nm, t in (("u0", u_init), ("end_data", g), ("forcing phi", phi)):
+        more = {}
+        if wave is not None:
+            v_init = np.array(np.broadcast_to(np.asarray(wave["v0"](nodes), dtype=np.float64), nodes.shape))
+            acc0 = wave["end_accel0"]
+            for i, end in ((0, 0), (1, -1)):
+                if kinds[i] == ops.END_DIRICHLET:
+                    if callable(end_data[i]) and acc0 is None:
+                        raise ValueError("end_accel0 = (g_left''(0), g_right''(0)) is needed when a Dirichlet end has "
+                                         "callable end_data: the first acceleration takes that value at the end, and "
+                                         "the average-acceleration rule never damps an error in it")
+                    if not callable(end_data[i]):
+                        v_init[end] = 0.0                       # constant Dirichlet data: the end does not move
+            acc0 = (0.0, 0.0) if acc0 is None else acc0
+            if not isinstance(acc0, (tuple, list, np.ndarray)) or len(acc0) != 2:
+                raise ValueError("end_accel0 must be a pair (g_left''(0), g_right''(0))")
+            more = dict(v_init=v_init, beta=beta, gamma=gamma, accel0=np.array([float(acc0[0]), float(acc0[1])]))
+        for nm, t in (("u0", u_init), ("end_data", g), ("forcing phi", phi), *((("v0", more["v_init"]),
+                      ("end_accel0", more["accel0"])) if more else ())):
             if not np.all(np.isfinite(t)):
                 raise ValueError(f"{nm} is not finite where it is tabulated")
         if not np.all(quad["rho"] > 0.0):
             raise ValueError("weight must be positive at every quadrature point (rho > 0): M would not be positive "
                              "definite")
-        if not np.all(quad["c"] + quad["rho"] / dt >= 0.0):
+        if wave is not None:
+            shift = quad["c"] + quad["rho"] / (beta * dt * dt)
+            if "d" in quad:
+                shift = shift + gamma * quad["d"] / (beta * dt)
+            if not np.all(shift >= 0.0):
+                raise ValueError(f"c + rho / (beta dt^2) + gamma d / (beta dt) < 0 at a quadrature point "
+                                 f"(dt = {dt:.6g}): the step's matrix would not be positive definite, and the solve "
+                                 "does not pivot; shorten the step")
+        elif not np.all(quad["c"] + quad["rho"] / dt >= 0.0):
             raise ValueError(f"c + rho / dt < 0 at a quadrature point (dt = {dt:.6g}): the step's matrix would not be "
                              "positive definite, and the solve does not pivot; shorten the step")
         return dict(nodes=nodes, kinds=kinds, kappa=kappa, dt=dt, times=times, steps=steps, u_init=u_init, phi=phi,
-                    g=g, quad=quad, colloc=colloc)
+                    g=g, quad=quad, colloc=colloc, **more)
 
     def solve_transient(self, u0, t_end, *, nsteps, scheme="bdf2", weight=None, forcing=None, end_data=None,
                         snapshots=None, enhance=True, nonlinear=None, newton_iters=None, newton_tol=None):
@@ -1739,6 +1810,141 @@ class FEMLSSVRPrimalSolver:
             raise RuntimeError(f"solve_transient: step {i + 1} did not converge in {iters} Newton iteration(s) to "
                                f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
         return TransientSolution(p["times"][steps].copy(), parts[0].reshape(ns, ne + 1), enhanced, bands, newton)
+
+    # ---- wave problems (no reference counterpart) -----------------------------
+    def solve_wave(self, u0, v0, t_end, *, nsteps, damping=None, weight=None, forcing=None, end_data=None,
+                   end_accel0=None, snapshots=None, enhance=True, beta=0.25, gamma=0.5):
+        """rho u_tt + d u_t - (a u')' + c u = f(x, t) for 0 < t <= ``t_end`` with u(x, 0) = ``u0(x)`` and
+        u_t(x, 0) = ``v0(x)``, on the solver's ``mesh`` with its ``coef``, ``reaction`` and ``boundary`` kinds (each end
+        Dirichlet u = g(t) or Robin a du/dn + kappa u = g(t), kappa >= 0); ``nsteps`` equal steps of the Newmark rule
+        (``beta``, ``gamma``) in displacement form -- the default (1/4, 1/2) is the average-acceleration rule:
+        unconditionally stable, second order, and energy conserving for d = 0, f = 0.  ``damping`` = d and ``weight`` =
+        rho are callables of x (``None``: 0 and 1); ``forcing``, ``end_data`` and ``snapshots`` as in
+        :meth:`solve_transient`.  ``u0`` and ``v0`` are sampled at the nodes; a Dirichlet end starts at g(0), and with
+        constant data its velocity is 0 (with callable data ``v0`` must equal g'(0) there).  ``end_accel0`` =
+        (g_left''(0), g_right''(0)) is the first acceleration's value at a Dirichlet end: required when such an end
+        has callable ``end_data``, zeros otherwise.
+
+        Before the loop the bands of K, M_rho, M_d and of the step's matrix
+        K + M_rho / (beta dt^2) + gamma M_d / (beta dt) are assembled once each, phi and g of every step are uploaded,
+        and the first acceleration solves M_rho acc0 = load(0) - M_d v0 - K u0 with the products of ``ops.eig_apply``.
+        Per step ONE ``ops.tridiag_bc_solve_multi`` and ONE ``ops.wave_advance``, which writes the correctors of the
+        step and the right-hand side of the next; two (v, acc) pairs and two nodal buffers alternate on one stream,
+        with no copy from the host and no synchronisation.  At a snapshot step one ``ops.eig_apply`` on [u, v] gives
+        the energy E = 1/2 v^T M_rho v + 1/2 u^T K u + 1/2 sum over the Robin ends of kappa u_end^2, and
+        ``ops.ts_source_table`` the right-hand side f(., t) - rho I_h acc - d I_h v of the snapshot's elliptic
+        problem; with ``enhance`` all snapshots then go through ONE ``ops.enhance_multi``.  Returns a
+        :class:`WaveSolution`; the solver's attributes are left as they are."""
+        self._check_nonlinear("solve_wave")
+        torch = _torch()
+        p = self._check_transient(u0, t_end, nsteps, None, weight, forcing, end_data, snapshots, bool(enhance),
+                                  wave=dict(v0=v0, damping=damping, beta=beta, gamma=gamma, end_accel0=end_accel0))
+        nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
+        beta, gamma = p["beta"], p["gamma"]
+        nsteps, ne, ns, damped = int(nsteps), nodes.size - 1, len(steps), "d" in q
+        dev = _device(self.device)
+        x = _to_dev(nodes, dev)
+        zq = torch.zeros((ne, int(self.nquad)), dtype=torch.float64, device=dev)
+        aq = None if self.coef is None else _to_dev(q["a"], dev)
+        K = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=_to_dev(q["c"], dev))
+        Mb = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["rho"], dev))
+        Db = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["d"], dev)) if damped else None
+        shift = q["c"] + q["rho"] / (beta * dt ** 2)
+        if damped:
+            shift = shift + gamma * q["d"] / (beta * dt)
+        A = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=_to_dev(shift, dev))       # ONE assembly
+        loads = ops.p1_load_multi(x, _to_dev(q["f"], dev), self.nquad)
+        phi, g = _to_dev(p["phi"], dev), _to_dev(p["g"], dev)              # row n: the time t_n
+        md, mo = Mb["diag"], Mb["off"]
+        dd, do = (Db["diag"], Db["off"]) if damped else (None, None)
+        M, reg, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
+        pm = M <= 16                         # the lane kernel of lssvr_enhance_multi reads point-major tables
+        if enhance:
+            c = p["colloc"]
+            ta, tda, tc, rtab = (_to_dev(c[k].T if pm else c[k], dev) for k in ("a", "da", "c", "rho"))
+            ftab = _to_dev(np.transpose(c["f"], (0, 2, 1)) if pm else c["f"], dev)
+            src = torch.empty((ns,) + tuple(rtab.shape), dtype=torch.float64, device=dev)
+            if damped:
+                dtab = _to_dev(c["d"].T if pm else c["d"], dev)
+                tmp = torch.empty((1,) + tuple(rtab.shape), dtype=torch.float64, device=dev)
+                one = torch.ones(1, dtype=torch.float64, device=dev)
+        # the energy reads every node: all ends as Robin rows, kappa of the problem's Robin ends (eig_apply adds it
+        # to K's end diagonal itself, so u^T K u already holds kappa u_end^2)
+        ekinds = (ops.END_ROBIN, ops.END_ROBIN)
+        ekap = tuple(kp if kd == ops.END_ROBIN else 0.0 for kd, kp in zip(kinds, kappa))
+        U = torch.empty((2, ne + 1), dtype=torch.float64, device=dev)
+        VA = torch.empty((2, 2, ne + 1), dtype=torch.float64, device=dev)     # [pair][v, acc]
+        SZ = torch.empty((ns + 1, 2, ne + 1), dtype=torch.float64, device=dev)     # [t = 0 and the snapshots][u, v]
+        SA = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
+        gram = torch.empty((ns + 1, 2, 2, 2), dtype=torch.float64, device=dev)
+        MZ, KZ = (torch.empty((2, ne + 1), dtype=torch.float64, device=dev) for _ in range(2))
+        b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
+        work = ops.tridiag_work(b, ne, 1, "bc")
+        ework = ops._scratch(None, ops._capi.load().lssvr_eig_work_bytes(ne, 2), dev)
+        # ---- the first acceleration: M_rho acc0 = load(0) - M_d v0 - K u0, Robin rows with g(0) - kappa u0
+        SZ[0, 0].copy_(_to_dev(p["u_init"], dev))
+        SZ[0, 1].copy_(_to_dev(p["v_init"], dev))
+        ops.eig_apply(K["diag"], K["off"], md, mo, SZ[0], ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram[0], work=ework)
+        r0 = (phi[0][:, None] * loads).sum(dim=0)
+        if damped:
+            dv = ops.eig_apply(K["diag"], K["off"], dd, do, SZ[0, 1:2], ekinds, ekap, work=ework)[0]
+            r0 = r0 - dv[0]
+        r0 = r0 - KZ[0]
+        a_ends = [0.0, 0.0]
+        for i, end in ((0, 0), (1, ne)):
+            if kinds[i] == ops.END_ROBIN:
+                r0[end] += g[0, i]
+            else:
+                a_ends[i] = float(p["accel0"][i])
+        U[0].copy_(SZ[0, 0])
+        VA[0, 0].copy_(SZ[0, 1])
+        ops.tridiag_bc_solve_multi(md, mo, r0.unsqueeze(0).contiguous(), kinds, (0.0, 0.0), [a_ends], out=VA[0, 1:2],
+                                   work=work)
+        snap = {s: k for k, s in enumerate(steps)}
+        cur, new, pr = 0, 1, 0
+        ops.wave_advance(None, U[cur:cur + 1], VA[pr, 0:1], VA[pr, 1:2], md, mo, dd, do, loads, phi[1:2], dt, beta,
+                         gamma, rhs_out=b)
+        # the loop: launches on the current stream only
+        for step in range(1, nsteps + 1):
+            ops.tridiag_bc_solve_multi(A["diag"], A["off"], b, kinds, kappa, g[step:step + 1], out=U[new:new + 1],
+                                       work=work)
+            last = step == nsteps
+            ops.wave_advance(U[new:new + 1], U[cur:cur + 1], VA[pr, 0:1], VA[pr, 1:2], md, mo, dd, do, loads,
+                             None if last else phi[step + 1:step + 2], dt, beta, gamma, V_out=VA[1 - pr, 0:1],
+                             Acc_out=VA[1 - pr, 1:2], rhs_out=None if last else b, rhs=not last)
+            cur, new, pr = new, cur, 1 - pr
+            k = snap.get(step)
+            if k is not None:
+                SZ[k + 1, 0].copy_(U[cur])
+                SZ[k + 1, 1].copy_(VA[pr, 0])
+                SA[k].copy_(VA[pr, 1])
+                ops.eig_apply(K["diag"], K["off"], md, mo, SZ[k + 1], ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram[k + 1],
+                              work=ework)
+                if enhance:
+                    # f - rho I_h acc: alpha = 1, beta0 = beta1 = 0, inv_dt = 1 leave U2 as it is (U0 is read, times 0)
+                    ops.ts_source_table(SA[k], SA[k], None, ftab, rtab, phi[step], 1.0, 0.0, 0.0, 1.0, point_major=pm,
+                                        out=tmp[0] if damped else src[k])
+                    if damped:           # ... - d I_h v: the table so far is the single term, phi = 1
+                        ops.ts_source_table(SZ[k + 1, 1], SZ[k + 1, 1], None, tmp, dtab, one, 1.0, 0.0, 0.0, 1.0,
+                                            point_major=pm, out=src[k])
+        enhanced = []
+        if enhance:
+            gd = (float(self.global_domain[0]), float(self.global_domain[1]))
+            bc = g[torch.as_tensor(steps, device=dev)].contiguous()
+            W, st = ops.enhance_multi(x, SZ[1:, 0].contiguous(), M, reg, n, ta, tda, src, c_values=tc, bc=bc,
+                                      point_major=pm, global_domain=gd, **self._shard(ne))
+            enhanced = [EnhancedSolution(x, W[k], st[k]) for k in range(ns)]
+        band_list = [md, mo, K["diag"], K["off"], A["diag"], A["off"]] + ([dd, do] if damped else [])
+        host = torch.cat([SZ.reshape(-1), SA.reshape(-1), gram.reshape(-1), *band_list,
+                          loads.reshape(-1)]).cpu().numpy()         # one copy: the snapshots, the energies and the bands
+        cut = np.cumsum([SZ.numel(), SA.numel(), gram.numel()] + [t.numel() for t in band_list])
+        parts = np.split(host, cut)
+        sz, gr = parts[0].reshape(ns + 1, 2, ne + 1), parts[2].reshape(ns + 1, 2, 2, 2)
+        bands = dict(mass=(parts[3], parts[4]), stiff=(parts[5], parts[6]), step=(parts[7], parts[8]),
+                     damp=(parts[9], parts[10]) if damped else None, loads=parts[-1].reshape(-1, ne + 1))
+        energy = 0.5 * (gr[:, 1, 1, 1] + gr[:, 0, 0, 0])
+        return WaveSolution(p["times"][steps].copy(), sz[1:, 0].copy(), sz[1:, 1].copy(), parts[1].reshape(ns, ne + 1),
+                            energy, enhanced, bands)
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):

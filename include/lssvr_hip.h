@@ -1163,6 +1163,52 @@ int lssvr_ts_nl_assemble_host(const double* x_host, const double* u_host, const 
                               const double* cs_quad_host, const double* q_quad_host, const double* r_host, int64_t ne,
                               int nquad, int kind, int nterm, double* diag_host, double* off_host, double* rhs_host);
 
+/*
+ * Wave problems: rho u_tt + d u_t - (a u')' + c u = f(x, t), Newmark (beta, gamma) in displacement form with a fixed
+ * step dt (no reference counterpart).  ADDITIVE to ABI 7: two new symbols, no existing entry,
+ * struct, constant or kernel instantiation changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * With the predictors  ut = u + dt v + dt^2 (1/2 - beta) acc,  vt = v + dt (1 - gamma) acc  step n+1 solves
+ *   A u' = load(t_{n+1}) + M_rho (ut / (beta dt^2)) + M_d ((gamma / (beta dt)) ut - vt)
+ * with A the bands of lssvr_p1_assemble_react for c_quad = c + rho / (beta dt^2) + gamma d / (beta dt) (assembled once),
+ * M_rho = (mdiag, moff) and M_d = (ddiag, doff) those of the same entry with a_quad = 0 and c_quad = rho, d; the solve
+ * is lssvr_tridiag_bc_solve_multi with a device row of end data.  The correctors are  acc' = (u' - ut) / (beta dt^2),
+ * v' = vt + gamma dt acc'.
+ *
+ * lssvr_wave_advance -- ONE launch per step: the correctors of the step just solved and the right-hand side of the
+ * next.  U_new, U, V, Acc, V_out, Acc_out, rhs_out are [nc][ne+1], case-major, 1 <= nc <= 8; loads [R][ne+1]
+ * (1 <= R <= 8, shared by the cases) and phi [nc][R] as for lssvr_ts_rhs; ddiag == NULL means d = 0, and then
+ * neither ddiag nor doff is read; all DEVICE arrays.  With  c_u2 = (dt dt)(1/2 - beta), c_v1 = dt (1 - gamma),
+ * c_m = 1 / (beta (dt dt)), c_d = gamma / (beta dt), c_va = gamma dt  (computed once on the host), per entry:
+ *   ut = (U + dt V) + c_u2 Acc;  vt = V + c_v1 Acc;  Acc_out = (U_new - ut) c_m;  V_out = vt + c_va Acc_out;
+ * and from the NEW state (u, v, acc) = (U_new, V_out, Acc_out) at i-1, i, i+1:
+ *   ut = (u + dt v) + c_u2 acc;  p = c_m ut;  q = c_d ut - (v + c_v1 acc);
+ *   m  = (moff[i-1] p[i-1] + mdiag[i] p[i]) + moff[i] p[i+1];   dd likewise from (ddiag, doff) and q;
+ *   rhs_out[i] = (((m + dd) + phi[0] loads[0][i]) + phi[1] loads[1][i]) + ...     (d = 0: m in place of m + dd)
+ * Rows 0 and ne leave the missing neighbour's term out.  A thread recomputes its neighbours' correctors from the old
+ * arrays by the routine that computes its own, so the launch needs no barrier and the fused call equals the split pair
+ * bit for bit.  Modes:
+ *   U_new == NULL    (U, V, Acc) is the state already, nothing but rhs_out is written (the first step's right-hand
+ *                    side; V_out, Acc_out are not read and may be NULL);
+ *   rhs_out == NULL  the correctors only (the last step, or the first half of a split pair; the bands, loads and phi
+ *                    are not read and may be NULL).
+ * No reduction, no atomics, no synchronisation, no copy.  Return codes: LSSVR_ERR_SIZE when both U_new and rhs_out
+ * are NULL, when V_out or Acc_out is V, Acc, U, U_new or the other output, when rhs_out is an input or another output,
+ * when ne < 1, nc or R is outside [1, 8], or dt, beta or gamma is not finite and > 0; LSSVR_ERR_NULL for a missing
+ * pointer that the mode reads or writes.  Every check comes before any launch.
+ *
+ * lssvr_wave_advance_host -- the same routine on HOST arrays: no device is touched.  Bit for bit the device's values.
+ */
+int lssvr_wave_advance(const double* U_new, const double* U, const double* V, const double* Acc, const double* mdiag,
+                       const double* moff, const double* ddiag, const double* doff, const double* loads,
+                       const double* phi, int64_t ne, int nc, int R, double dt, double beta, double gamma,
+                       double* V_out, double* Acc_out, double* rhs_out, void* stream);
+int lssvr_wave_advance_host(const double* U_new_host, const double* U_host, const double* V_host,
+                            const double* Acc_host, const double* mdiag_host, const double* moff_host,
+                            const double* ddiag_host, const double* doff_host, const double* loads_host,
+                            const double* phi_host, int64_t ne, int nc, int R, double dt, double beta, double gamma,
+                            double* V_out_host, double* Acc_out_host, double* rhs_out_host);
+
 #ifdef __cplusplus
 }
 #endif
