@@ -50,6 +50,7 @@ are refused as singular even where g_u > 0 would make every Newton matrix defini
 from __future__ import annotations
 
 import math
+import types
 
 import numpy as np
 from numpy.polynomial.legendre import Legendre
@@ -114,6 +115,21 @@ def _device(device):
 def _to_dev(a, device):
     torch = _torch()
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64)), device=device)
+
+
+def _read_back(**tensors):
+    """ONE device-to-host copy of all ``tensors`` -> {name: float64 array in the tensor's shape}.  A value may also be a
+    tuple of tensors (a pair of bands: a tuple of arrays comes back) or None (None comes back); int32 info words come
+    back as float64.  The arrays are views of one host buffer."""
+    torch = _torch()
+    flat = [t for v in tensors.values() if v is not None for t in (v if isinstance(v, tuple) else (v,))]
+    host = torch.cat([t.reshape(-1).double() for t in flat]).cpu().numpy()
+    parts = iter(np.split(host, np.cumsum([t.numel() for t in flat])[:-1]))
+
+    def take(t):
+        return next(parts).reshape(tuple(t.shape))
+    return {k: None if v is None else tuple(take(t) for t in v) if isinstance(v, tuple) else take(v)
+            for k, v in tensors.items()}
 
 
 def _tabulate(fn, pts, point_major=False):
@@ -344,6 +360,14 @@ class GoalEstimate:
         self.corrected = self.value + self.correction
 
 
+def _evaluate_item(items, method, what, i, x, deriv):
+    """``evaluate`` of the solution classes below: item ``i`` of their :class:`EnhancedSolution` list at ``x``."""
+    if not items:
+        raise RuntimeError(f"{method} ran with enhance=False: there are no enhanced {what} to evaluate")
+    x = np.asarray(x, dtype=np.float64)
+    return items[i].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
+
+
 class EigenSolution:
     """What :meth:`FEMLSSVRPrimalSolver.solve_eigen` returns for the k eigenvalues of -(a u')' + c u = lambda rho u
     nearest the shift, in the order of their distance from it:
@@ -361,10 +385,7 @@ class EigenSolution:
 
     def evaluate(self, j, x, deriv=0):
         """The enhanced mode ``j`` (its ``deriv``-th derivative) at the points ``x``."""
-        if not self.modes:
-            raise RuntimeError("solve_eigen ran with enhance=False: there are no enhanced modes to evaluate")
-        x = np.asarray(x, dtype=np.float64)
-        return self.modes[j].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
+        return _evaluate_item(self.modes, "solve_eigen", "modes", j, x, deriv)
 
 
 class TransientSolution:
@@ -385,10 +406,7 @@ class TransientSolution:
 
     def evaluate(self, k, x, deriv=0):
         """The enhanced snapshot ``k`` (its ``deriv``-th x-derivative) at the points ``x``."""
-        if not self.enhanced:
-            raise RuntimeError("solve_transient ran with enhance=False: there are no enhanced snapshots to evaluate")
-        x = np.asarray(x, dtype=np.float64)
-        return self.enhanced[k].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
+        return _evaluate_item(self.enhanced, "solve_transient", "snapshots", k, x, deriv)
 
 
 class WaveSolution:
@@ -408,10 +426,7 @@ class WaveSolution:
 
     def evaluate(self, k, x, deriv=0):
         """The enhanced snapshot ``k`` (its ``deriv``-th x-derivative) at the points ``x``."""
-        if not self.enhanced:
-            raise RuntimeError("solve_wave ran with enhance=False: there are no enhanced snapshots to evaluate")
-        x = np.asarray(x, dtype=np.float64)
-        return self.enhanced[k].evaluate(x.reshape(-1), deriv=deriv).reshape(x.shape)
+        return _evaluate_item(self.enhanced, "solve_wave", "snapshots", k, x, deriv)
 
 
 class _ElementFunctions:
@@ -1370,17 +1385,17 @@ class FEMLSSVRPrimalSolver:
             ops.eig_rotate(Z, MZ, KZ, Q, theta, kinds, X=X, Y=Y, res2=res2, work=ework)
             if it % int(check_every) and it != int(max_iter):
                 continue
-            host = torch.cat([theta, res2.reshape(-1), pinfo.double(), rinfo.double()]).cpu().numpy()     # one small copy
-            th, res, xn = host[:nb], np.sqrt(host[nb:2 * nb]), np.sqrt(host[2 * nb:3 * nb])
-            if pivot and host[3 * nb]:
+            host = _read_back(theta=theta, res2=res2, pinfo=pinfo, rinfo=rinfo)                 # one small copy
+            th, (res, xn) = host["theta"], np.sqrt(host["res2"])
+            if pivot and host["pinfo"][0]:
                 raise RuntimeError(f"K - sigma M is singular to working precision at sigma = {sigma!r}: the pivoting "
-                                   f"solve met {int(host[3 * nb])} pivot(s) that were zero or not finite; sigma is an "
-                                   "eigenvalue of the discrete problem, move it")
-            if host[3 * nb + 1]:
-                raise RuntimeError(f"the block of iteration vectors lost {int(host[3 * nb + 1])} column(s): their "
+                                   f"solve met {int(host['pinfo'][0])} pivot(s) that were zero or not finite; sigma is "
+                                   "an eigenvalue of the discrete problem, move it")
+            if host["rinfo"][0]:
+                raise RuntimeError(f"the block of iteration vectors lost {int(host['rinfo'][0])} column(s): their "
                                    "images under the shifted inverse are linearly dependent to working precision "
                                    "(sigma is too close to an eigenvalue for a block of this width)")
-            if not np.all(np.isfinite(host)):
+            if not all(np.all(np.isfinite(v)) for v in host.values()):
                 raise RuntimeError("block inverse iteration produced non-finite values")
             converged = bool(np.all(res[:k] <= float(tol) * kmax * xn[:k]))
         index = None
@@ -1437,19 +1452,19 @@ class FEMLSSVRPrimalSolver:
                 values[j] = out3[0] / out3[1]
         return EigenSolution(th[:k].copy(), values, res[:k].copy(), index, it, converged, nodal, modes, sigma)
 
-    # ---- transient problems (no reference counterpart) --------------------
-    def _check_transient(self, u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance, wave=None):
-        """What :meth:`solve_transient` does not cover and what its data must satisfy, on the host and before any
-        device call -> dict(nodes, kinds, kappa, dt, times, steps, u_init, phi [nsteps, R], g [nsteps + 1, 2], quad,
-        colloc).  Every callable is evaluated here, once per kind of point, and ``quad`` / ``colloc`` are its host
-        tables, the ones the device is handed: a, c, rho [ne, nquad] and f [R, ne, nquad] at the Gauss points of the
-        assembly; with ``enhance`` a, da, c, rho [ne, n_colloc] and f [R, ne, n_colloc] at np.linspace(x_e, x_e+1,
-        n_colloc), the abscissae lssvr_colloc_points writes (else None).
-
-        ``wave`` = dict(v0, damping, beta, gamma, end_accel0) makes it the check of :meth:`solve_wave` (``scheme`` is
-        not read): the tables gain d, phi gains the row of t = 0 ([nsteps + 1, R]), the dict gains v_init, beta, gamma
-        and accel0 [2], and the matrix that must stay definite is the one of the Newmark step."""
-        me = "solve_transient" if wave is None else "solve_wave"
+    # ---- time stepping: what solve_transient and solve_wave share (DESIGN.md sections 26, 28, 29) -------------
+    def _check_time(self, me, u0, t_end, nsteps, weight, forcing, end_data, snapshots, enhance, damping=None,
+                    phi0=False):
+        """What the time loops (``me``: the method's name in the messages) do not cover and what their data must
+        satisfy, whatever the rule in time; on the host and before any device call -> a namespace of nodes, kinds,
+        kappa, dt, times, steps, u_init, end_data (the pair as given or defaulted), phi [nsteps, R] -- with ``phi0``
+        [nsteps + 1, R]: a row for t = 0 first --, g [nsteps + 1, 2], quad, colloc.  Every callable is evaluated here,
+        once per kind of point, and ``quad`` / ``colloc`` are its host tables, the ones the device is handed: a, c, rho
+        [ne, nquad] and f [R, ne, nquad] at the Gauss points of the assembly; with ``enhance`` a, da, c, rho
+        [ne, n_colloc] and f [R, ne, n_colloc] at np.linspace(x_e, x_e+1, n_colloc), the abscissae lssvr_colloc_points
+        writes (else None).  ``damping``: one more coefficient d(x), tabulated as "d" in both.  The parameters of the
+        rule and the definiteness of its step matrix are the caller's: :meth:`_check_transient`,
+        :meth:`_check_wave`."""
         if self.convection is not None:
             raise ValueError(f"{me} has no convection term: the step's matrix would need the non-symmetric "
                              "solve and a cell Peclet check per step size")
@@ -1469,21 +1484,8 @@ class FEMLSSVRPrimalSolver:
             raise ValueError("u0 must be a callable u0(x)")
         if weight is not None and not callable(weight):
             raise ValueError("weight must be a callable rho(x) or None")
-        if wave is not None:
-            beta, gamma = float(wave["beta"]), float(wave["gamma"])
-            if not (math.isfinite(beta) and math.isfinite(gamma)):
-                raise ValueError(f"beta and gamma must be finite, got {wave['beta']!r}, {wave['gamma']!r}")
-            # (the bound itself is allowed: 0.25 * (0.6 + 0.5) ** 2 rounds one ulp above 0.3025)
-            if gamma < 0.5 or beta * (1.0 + 2.0 ** -50) < 0.25 * (gamma + 0.5) ** 2:
-                raise ValueError(f"beta = {beta!r}, gamma = {gamma!r}: the Newmark rule is unconditionally stable for "
-                                 "gamma >= 1/2 and beta >= (gamma + 1/2)^2 / 4 only, and the step is not checked "
-                                 "against the mesh")
-            if not callable(wave["v0"]):
-                raise ValueError("v0 must be a callable v0(x)")
-            if wave["damping"] is not None and not callable(wave["damping"]):
-                raise ValueError("damping must be a callable d(x) or None")
-        elif scheme not in ops.BDF:
-            raise ValueError(f"scheme must be 'bdf1' or 'bdf2', got {scheme!r}")
+        if damping is not None and not callable(damping):
+            raise ValueError("damping must be a callable d(x) or None")
         if isinstance(nsteps, bool) or int(nsteps) != nsteps or int(nsteps) < 1:
             raise ValueError(f"nsteps must be an integer >= 1, got {nsteps!r}")
         nsteps, t_end = int(nsteps), float(t_end)
@@ -1512,18 +1514,16 @@ class FEMLSSVRPrimalSolver:
         nodes = np.asarray(m.nodes, dtype=np.float64)
         dt = t_end / nsteps
         times = dt * np.arange(nsteps + 1)
-        phi = np.array([[float(p(t)) for p in pfn] for t in (times[1:] if wave is None else times)], dtype=np.float64)
+        phi = np.array([[float(p(t)) for p in pfn] for t in (times if phi0 else times[1:])], dtype=np.float64)
         g = np.array([[float(v(t)) for v in gfn] for t in times], dtype=np.float64)
         # the data at the Gauss points of the assembly, a + h xi on [0, 1] as lssvr_quad_points has them, and at the
-        # collocation points: finite, one value per point, rho > 0, c + rho / dt >= 0
+        # collocation points: finite, one value per point, rho > 0
         xi = 0.5 * (1.0 + np.polynomial.legendre.leggauss(int(self.nquad))[0])
         xq = nodes[:-1, None] + np.diff(nodes)[:, None] * xi[None, :]
         eq = self._eq
         fns = dict(a=_one if eq.a is None else eq.a, da=_zero if eq.da is None else eq.da,
-                   c=_zero if eq.c is None else eq.c, rho=_one if weight is None else weight)
-        extra = ()
-        if wave is not None and wave["damping"] is not None:
-            fns["d"], extra = wave["damping"], ("d",)
+                   c=_zero if eq.c is None else eq.c, rho=_one if weight is None else weight, d=damping)
+        extra = () if damping is None else ("d",)
 
         def tables(pts, names, what):
             out = {}
@@ -1554,42 +1554,81 @@ class FEMLSSVRPrimalSolver:
         for i, end in ((0, 0), (1, -1)):
             if kinds[i] == ops.END_DIRICHLET:
                 u_init[end] = g[0, i]
-        more = {}
-        if wave is not None:
-            v_init = np.array(np.broadcast_to(np.asarray(wave["v0"](nodes), dtype=np.float64), nodes.shape))
-            acc0 = wave["end_accel0"]
-            for i, end in ((0, 0), (1, -1)):
-                if kinds[i] == ops.END_DIRICHLET:
-                    if callable(end_data[i]) and acc0 is None:
-                        raise ValueError("end_accel0 = (g_left''(0), g_right''(0)) is needed when a Dirichlet end has "
-                                         "callable end_data: the first acceleration takes that value at the end, and "
-                                         "the average-acceleration rule never damps an error in it")
-                    if not callable(end_data[i]):
-                        v_init[end] = 0.0                       # constant Dirichlet data: the end does not move
-            acc0 = (0.0, 0.0) if acc0 is None else acc0
-            if not isinstance(acc0, (tuple, list, np.ndarray)) or len(acc0) != 2:
-                raise ValueError("end_accel0 must be a pair (g_left''(0), g_right''(0))")
-            more = dict(v_init=v_init, beta=beta, gamma=gamma, accel0=np.array([float(acc0[0]), float(acc0[1])]))
-        for nm, t in (("u0", u_init), ("end_data", g), ("forcing phi", phi), *((("v0", more["v_init"]),
-                      ("end_accel0", more["accel0"])) if more else ())):
-            if not np.all(np.isfinite(t)):
-                raise ValueError(f"{nm} is not finite where it is tabulated")
+        self._check_finite(("u0", u_init), ("end_data", g), ("forcing phi", phi))
         if not np.all(quad["rho"] > 0.0):
             raise ValueError("weight must be positive at every quadrature point (rho > 0): M would not be positive "
                              "definite")
-        if wave is not None:
-            shift = quad["c"] + quad["rho"] / (beta * dt * dt)
-            if "d" in quad:
-                shift = shift + gamma * quad["d"] / (beta * dt)
-            if not np.all(shift >= 0.0):
-                raise ValueError(f"c + rho / (beta dt^2) + gamma d / (beta dt) < 0 at a quadrature point "
-                                 f"(dt = {dt:.6g}): the step's matrix would not be positive definite, and the solve "
-                                 "does not pivot; shorten the step")
-        elif not np.all(quad["c"] + quad["rho"] / dt >= 0.0):
-            raise ValueError(f"c + rho / dt < 0 at a quadrature point (dt = {dt:.6g}): the step's matrix would not be "
-                             "positive definite, and the solve does not pivot; shorten the step")
-        return dict(nodes=nodes, kinds=kinds, kappa=kappa, dt=dt, times=times, steps=steps, u_init=u_init, phi=phi,
-                    g=g, quad=quad, colloc=colloc, **more)
+        return types.SimpleNamespace(nodes=nodes, kinds=kinds, kappa=kappa, dt=dt, times=times, steps=steps,
+                                     u_init=u_init, end_data=end_data, phi=phi, g=g, quad=quad, colloc=colloc)
+
+    @staticmethod
+    def _check_finite(*named):
+        for nm, t in named:
+            if not np.all(np.isfinite(t)):
+                raise ValueError(f"{nm} is not finite where it is tabulated")
+
+    def _time_setup(self, p, enhance, matrices, per_snapshot=False, nbuf=3):
+        """The device side that the time loops share, from the plan ``p`` of :meth:`_check_time` -> a namespace of
+        dev, x, aq (None without ``coef``), bands {key: (diag, off)} and cq {key: the c table} of every
+        (key, with a, host c table) of ``matrices`` -- each ONE ``ops.p1_assemble``, in the order given --, loads
+        [R, ne+1], phi and g (every row of the plan's), pm, tab (with ``enhance``: the collocation tables a, da, c,
+        rho, f and d, transposed when ``pm``), src [ns, table] (the right-hand sides of the snapshots' elliptic
+        problems), U [nbuf, ne+1] with the start in row 0, S [ns, ne+1], b [1, ne+1], work (of the one-case "bc"
+        solve) and snap {step: snapshot index}.
+
+        ``pm``, the layout of the collocation tables, follows the kernel that reads them: ``ops.enhance_multi`` (all
+        snapshots in one call: solve_transient, solve_wave) takes point-major tables for its lane kernel, M <= 16;
+        ``ops.enhance_varcoef`` (``per_snapshot``: one call each, solve_transient with nonlinear=) when
+        ``_point_major(M)``."""
+        torch = _torch()
+        ne, ns, q = p.nodes.size - 1, len(p.steps), p.quad
+        dev = _device(self.device)
+        x = _to_dev(p.nodes, dev)
+        zq = torch.zeros((ne, int(self.nquad)), dtype=torch.float64, device=dev)
+        aq = None if self.coef is None else _to_dev(q["a"], dev)
+        bands, cq = {}, {}
+        for key, with_a, c_host in matrices:
+            cq[key] = _to_dev(c_host, dev)
+            A = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq if with_a else zq, c_quad=cq[key])
+            bands[key] = (A["diag"], A["off"])
+        loads = ops.p1_load_multi(x, _to_dev(q["f"], dev), self.nquad)
+        pm = _point_major(self.lssvr_M) if per_snapshot else int(self.lssvr_M) <= 16
+        tab = src = None
+        if enhance:
+            c = p.colloc
+            tab = {k: _to_dev(np.transpose(c[k], (0, 2, 1)) if k == "f" else c[k].T, dev) if pm else _to_dev(c[k], dev)
+                   for k in c}
+            src = torch.empty((ns,) + tuple(tab["rho"].shape), dtype=torch.float64, device=dev)
+        U = torch.empty((nbuf, ne + 1), dtype=torch.float64, device=dev)
+        U[0].copy_(_to_dev(p.u_init, dev))
+        S = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
+        b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
+        return types.SimpleNamespace(dev=dev, x=x, aq=aq, bands=bands, cq=cq, loads=loads, phi=_to_dev(p.phi, dev),
+                                     g=_to_dev(p.g, dev), pm=pm, tab=tab, src=src, U=U, S=S, b=b,
+                                     work=ops.tridiag_work(b, ne, 1, "bc"), snap={s: k for k, s in enumerate(p.steps)})
+
+    def _enhance_snapshots(self, p, D, nodal):
+        """The snapshots ``nodal`` [ns, ne+1] through ONE ``ops.enhance_multi``, on the tables and the right-hand sides
+        ``D.src`` of :meth:`_time_setup`, with g at the snapshots' times as the end values -> ns EnhancedSolution."""
+        torch = _torch()
+        bc = D.g[torch.as_tensor(p.steps, device=D.dev)].contiguous()
+        W, st = ops.enhance_multi(D.x, nodal, int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc),
+                                  D.tab["a"], D.tab["da"], D.src, c_values=D.tab["c"], bc=bc, point_major=D.pm,
+                                  global_domain=(float(self.global_domain[0]), float(self.global_domain[1])),
+                                  **self._shard(p.nodes.size - 1))
+        return [EnhancedSolution(D.x, W[k], st[k]) for k in range(len(p.steps))]
+
+    # ---- transient problems (no reference counterpart; DESIGN.md sections 26 and 28) ------------------------------
+    def _check_transient(self, u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance):
+        """:meth:`_check_time` for :meth:`solve_transient`, and what belongs to BDF: the scheme's name, and
+        c + rho / dt >= 0 at the quadrature points."""
+        p = self._check_time("solve_transient", u0, t_end, nsteps, weight, forcing, end_data, snapshots, enhance)
+        if scheme not in ops.BDF:
+            raise ValueError(f"scheme must be 'bdf1' or 'bdf2', got {scheme!r}")
+        if not np.all(p.quad["c"] + p.quad["rho"] / p.dt >= 0.0):
+            raise ValueError(f"c + rho / dt < 0 at a quadrature point (dt = {p.dt:.6g}): the step's matrix would not "
+                             "be positive definite, and the solve does not pivot; shorten the step")
+        return p
 
     def solve_transient(self, u0, t_end, *, nsteps, scheme="bdf2", weight=None, forcing=None, end_data=None,
                         snapshots=None, enhance=True, nonlinear=None, newton_iters=None, newton_tol=None):
@@ -1628,190 +1667,162 @@ class FEMLSSVRPrimalSolver:
         if self.nonlinear is not None:
             raise ValueError("solve_transient takes the semilinear term as its own keyword: build the solver without "
                              "nonlinear= and call solve_transient(..., nonlinear=...)")
+        nl, enhance = None, bool(enhance)
         if nonlinear is None:
             if newton_iters is not None or newton_tol is not None:
                 raise ValueError("newton_iters and newton_tol belong to solve_transient(..., nonlinear=...)")
         else:
-            return self._solve_transient_nl(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots,
-                                            bool(enhance), nonlinear, 3 if newton_iters is None else newton_iters,
-                                            1e-10 if newton_tol is None else newton_tol)
+            nl = _Nonlinear(nonlinear)
+            newton_iters, newton_tol = 3 if newton_iters is None else newton_iters, 1e-10 if newton_tol is None \
+                else newton_tol
+            if isinstance(newton_iters, bool) or int(newton_iters) != newton_iters or not 1 <= int(newton_iters) <= 8:
+                raise ValueError(f"newton_iters must be an integer in 1 .. 8, got {newton_iters!r}")
+            if not (float(newton_tol) > 0.0) or not math.isfinite(float(newton_tol)):
+                raise ValueError(f"newton_tol must be finite and > 0, got {newton_tol!r}")
+            iters, tol = int(newton_iters), float(newton_tol)
+        p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance)
+        kinds, kappa, steps, q, n = p.kinds, p.kappa, p.steps, p.quad, int(self.n_colloc)
+        if nl is not None:
+            if enhance and n > ops.NL_MAX_POINTS:
+                raise ValueError(f"nonlinear needs n_colloc <= {ops.NL_MAX_POINTS} for the enhanced snapshots, got {n}")
+            xq_host, xc_host = self._nl_host_points(p.nodes)
+            qq_host = nl.host_tables(xq_host, "quadrature")
+            qc_host = nl.host_tables(xc_host, "collocation") if enhance else None
+        # ---- the device from here on
         torch = _torch()
-        p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, bool(enhance))
-        nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
-        nsteps, ne, ns, inv_dt = int(nsteps), nodes.size - 1, len(p["steps"]), 1.0 / p["dt"]
-        dev = _device(self.device)
-        x = _to_dev(nodes, dev)
-        zq = torch.zeros((ne, int(self.nquad)), dtype=torch.float64, device=dev)
-        aq = None if self.coef is None else _to_dev(q["a"], dev)
-        Mb = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["rho"], dev))
-        # the two matrices of the loop: K + (alpha / dt) M as ONE reaction assembly each
-        A = {al: ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq,
-                                 c_quad=_to_dev(q["c"] + al * q["rho"] / dt, dev))
-             for al in {ops.BDF["bdf1"][0], ops.BDF[scheme][0]}}
-        loads = ops.p1_load_multi(x, _to_dev(q["f"], dev), self.nquad)
-        phi, g = _to_dev(p["phi"], dev), _to_dev(p["g"][1:], dev)          # row n - 1: the step that ends at t_n
-        M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
-        pm = M <= 16                         # the lane kernel of lssvr_enhance_multi reads point-major tables
+        nsteps, ne, ns, inv_dt = int(nsteps), p.nodes.size - 1, len(steps), 1.0 / p.dt
+        # the matrices of the loop: K + (alpha / dt) M as ONE reaction assembly each (with nonlinear= a diagnostic:
+        # every Newton iteration assembles its own from the same c table)
+        alphas = {ops.BDF["bdf1"][0], ops.BDF[scheme][0]}
+        D = self._time_setup(p, enhance, [("mass", False, q["rho"]),
+                                          *((al, True, q["c"] + al * q["rho"] / p.dt) for al in alphas)],
+                             per_snapshot=nl is not None)
+        dev, x, U, S, b, loads, work, snap, pm = D.dev, D.x, D.U, D.S, D.b, D.loads, D.work, D.snap, D.pm
+        phi, g = D.phi, D.g[1:]                                        # row n - 1: the step that ends at t_n
+        (md, mo), mon = D.bands["mass"], None
         if enhance:
-            c = p["colloc"]
-            ta, tda, tc, rtab = (_to_dev(c[k].T if pm else c[k], dev) for k in ("a", "da", "c", "rho"))
-            ftab = _to_dev(np.transpose(c["f"], (0, 2, 1)) if pm else c["f"], dev)
-            src = torch.empty((ns,) + tuple(rtab.shape), dtype=torch.float64, device=dev)
-        U = torch.empty((3, ne + 1), dtype=torch.float64, device=dev)
-        U[0].copy_(_to_dev(p["u_init"], dev))
-        S = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
-        b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
-        work = ops.tridiag_work(b, ne, 1, "bc")
-        md, mo = Mb["diag"], Mb["off"]
+            ftab, rtab, src = D.tab["f"], D.tab["rho"], D.src
+        if nl is not None:
+            qq = _to_dev(qq_host, dev)
+            V = torch.empty((2, ne + 1), dtype=torch.float64, device=dev)         # the Newton iterates of a step
+            rhs = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
+            nb = dict(diag=torch.empty(ne + 1, dtype=torch.float64, device=dev),
+                      off=torch.empty(ne, dtype=torch.float64, device=dev), rhs=rhs[0])
+            mon = torch.zeros((nsteps, iters, 4), dtype=torch.float64, device=dev)
+            rwork = ops._scratch(None, ops._capi.load().lssvr_nl_residual_work_bytes(ne), dev)
+            if enhance:
+                qc = _to_dev(np.transpose(qc_host, (0, 2, 1)) if pm else qc_host, dev)
+                tloc = torch.arange(n, dtype=torch.float64, device=dev) / float(n - 1)
+                c_eff, f_eff = (torch.empty_like(src) for _ in range(2))
         bdf1 = ops.BDF["bdf1"]
-        snap = {s: k for k, s in enumerate(steps)}
         cur, prev, new = 0, 1, 2
         # the loop: launches on the current stream only
         for step in range(1, nsteps + 1):
             al, b0, b1 = bdf1 if step == 1 else ops.BDF[scheme]
             u_prev = None if b1 == 0.0 else U[prev:prev + 1]
             ops.ts_rhs(md, mo, U[cur:cur + 1], u_prev, loads, phi[step - 1:step], b0, b1, inv_dt, out=b)
-            ops.tridiag_bc_solve_multi(A[al]["diag"], A[al]["off"], b, kinds, kappa, g[step - 1:step],
-                                       out=U[new:new + 1], work=work)
+            if nl is None:
+                ops.tridiag_bc_solve_multi(*D.bands[al], b, kinds, kappa, g[step - 1:step], out=U[new:new + 1],
+                                           work=work)
+            else:
+                if b1 == 0.0:
+                    V[0].copy_(U[cur])
+                else:
+                    ops.nl_step(U[prev], U[cur], 2.0, out=V[0])
+                v, spare = V[0], V[1]
+                for it in range(iters):
+                    tgt = U[new] if it == iters - 1 else spare
+                    ops.ts_nl_assemble(x, v, D.cq[al], nl.kind, qq, b[0], a_quad=D.aq, out=nb)
+                    ops.tridiag_bc_solve_multi(nb["diag"], nb["off"], rhs, kinds, kappa, g[step - 1:step],
+                                               out=tgt.unsqueeze(0), work=work)
+                    ops.nl_residual(nb["diag"], nb["off"], nb["off"], nb["rhs"], v, tgt, kinds, kappa, g[step - 1],
+                                    out4=mon[step - 1, it], work=rwork)
+                    v, spare = tgt, v
             k = snap.get(step)
             if k is not None:
                 S[k].copy_(U[new])
                 if enhance:
                     ops.ts_source_table(U[new], U[cur], None if b1 == 0.0 else U[prev], ftab, rtab, phi[step - 1], al,
                                         b0, b1, inv_dt, point_major=pm, out=src[k])
+                    if nl is not None:
+                        ops.nl_linearize(U[new], tloc, nl.kind, qc, src[k], c_tab=D.tab["c"], point_major=pm,
+                                         c_eff=c_eff[k], f_eff=f_eff[k])
             cur, prev, new = new, cur, prev
         enhanced = []
-        if enhance:
-            gd = (float(self.global_domain[0]), float(self.global_domain[1]))
-            bc = g[torch.as_tensor([s - 1 for s in steps], device=dev)].contiguous()
-            W, st = ops.enhance_multi(x, S, M, gamma, n, ta, tda, src, c_values=tc, bc=bc, point_major=pm,
-                                      global_domain=gd, **self._shard(ne))
-            enhanced = [EnhancedSolution(x, W[k], st[k]) for k in range(ns)]
-        host = torch.cat([S.reshape(-1), md, mo, *(A[al][k] for al in sorted(A) for k in ("diag", "off")),
-                          loads.reshape(-1)]).cpu().numpy()                  # one copy: the snapshots and the bands
-        cut = np.cumsum([ns * (ne + 1), ne + 1, ne] + [ne + 1, ne] * len(A))
-        parts = np.split(host, cut)
-        bands = dict(mass=(parts[1], parts[2]), loads=parts[-1].reshape(-1, ne + 1),
-                     step={al: (parts[3 + 2 * i], parts[4 + 2 * i]) for i, al in enumerate(sorted(A))})
-        return TransientSolution(p["times"][steps].copy(), parts[0].reshape(ns, ne + 1), enhanced, bands)
-
-    def _solve_transient_nl(self, u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance, nonlinear,
-                            newton_iters, newton_tol):
-        """:meth:`solve_transient` with ``nonlinear=``.  Everything the host can check is
-        checked before the first device call; the loop is launches on the current stream only."""
-        nl = _Nonlinear(nonlinear)
-        if isinstance(newton_iters, bool) or int(newton_iters) != newton_iters or not 1 <= int(newton_iters) <= 8:
-            raise ValueError(f"newton_iters must be an integer in 1 .. 8, got {newton_iters!r}")
-        if not (float(newton_tol) > 0.0) or not math.isfinite(float(newton_tol)):
-            raise ValueError(f"newton_tol must be finite and > 0, got {newton_tol!r}")
-        iters, tol = int(newton_iters), float(newton_tol)
-        p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance)
-        nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
-        n = int(self.n_colloc)
-        if enhance and n > ops.NL_MAX_POINTS:
-            raise ValueError(f"nonlinear needs n_colloc <= {ops.NL_MAX_POINTS} for the enhanced snapshots, got {n}")
-        xq_host, xc_host = self._nl_host_points(nodes)
-        qq_host = nl.host_tables(xq_host, "quadrature")
-        qc_host = nl.host_tables(xc_host, "collocation") if enhance else None
-        # ---- the device from here on
-        torch = _torch()
-        nsteps, ne, ns, inv_dt = int(nsteps), nodes.size - 1, len(steps), 1.0 / dt
-        dev = _device(self.device)
-        x = _to_dev(nodes, dev)
-        zq = torch.zeros((ne, int(self.nquad)), dtype=torch.float64, device=dev)
-        aq = None if self.coef is None else _to_dev(q["a"], dev)
-        Mb = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["rho"], dev))
-        alphas = {ops.BDF["bdf1"][0], ops.BDF[scheme][0]}
-        cs = {al: _to_dev(q["c"] + al * q["rho"] / dt, dev) for al in alphas}
-        A = {al: ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=cs[al]) for al in alphas}   # (diagnostic)
-        qq = _to_dev(qq_host, dev)
-        loads = ops.p1_load_multi(x, _to_dev(q["f"], dev), self.nquad)
-        phi, g = _to_dev(p["phi"], dev), _to_dev(p["g"][1:], dev)          # row n - 1: the step that ends at t_n
-        M, gamma = int(self.lssvr_M), float(self.lssvr_gamma)
-        pm = _point_major(M)
-        if enhance:
-            c = p["colloc"]
-            ta, tda, tc, rtab = (_to_dev(c[k].T if pm else c[k], dev) for k in ("a", "da", "c", "rho"))
-            ftab = _to_dev(np.transpose(c["f"], (0, 2, 1)) if pm else c["f"], dev)
-            qc = _to_dev(np.transpose(qc_host, (0, 2, 1)) if pm else qc_host, dev)
-            tloc = torch.arange(n, dtype=torch.float64, device=dev) / float(n - 1)
-            src = torch.empty(tuple(rtab.shape), dtype=torch.float64, device=dev)
-            c_eff, f_eff = (torch.empty((ns,) + tuple(rtab.shape), dtype=torch.float64, device=dev) for _ in range(2))
-        U = torch.empty((3, ne + 1), dtype=torch.float64, device=dev)
-        U[0].copy_(_to_dev(p["u_init"], dev))
-        V = torch.empty((2, ne + 1), dtype=torch.float64, device=dev)         # the Newton iterates of a step
-        S = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
-        b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)         # r of the step
-        rhs = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
-        nb = dict(diag=torch.empty(ne + 1, dtype=torch.float64, device=dev),
-                  off=torch.empty(ne, dtype=torch.float64, device=dev), rhs=rhs[0])
-        mon = torch.zeros((nsteps, iters, 4), dtype=torch.float64, device=dev)
-        work = ops.tridiag_work(b, ne, 1, "bc")
-        rwork = ops._scratch(None, ops._capi.load().lssvr_nl_residual_work_bytes(ne), dev)
-        md, mo = Mb["diag"], Mb["off"]
-        bdf1 = ops.BDF["bdf1"]
-        snap = {s: k for k, s in enumerate(steps)}
-        cur, prev, new = 0, 1, 2
-        # the loop: launches on the current stream only
-        for step in range(1, nsteps + 1):
-            al, b0, b1 = bdf1 if step == 1 else ops.BDF[scheme]
-            u_prev = None if b1 == 0.0 else U[prev:prev + 1]
-            ops.ts_rhs(md, mo, U[cur:cur + 1], u_prev, loads, phi[step - 1:step], b0, b1, inv_dt, out=b)
-            if b1 == 0.0:
-                V[0].copy_(U[cur])
-            else:
-                ops.nl_step(U[prev], U[cur], 2.0, out=V[0])
-            v, spare = V[0], V[1]
-            for k in range(iters):
-                tgt = U[new] if k == iters - 1 else spare
-                ops.ts_nl_assemble(x, v, cs[al], nl.kind, qq, b[0], a_quad=aq, out=nb)
-                ops.tridiag_bc_solve_multi(nb["diag"], nb["off"], rhs, kinds, kappa, g[step - 1:step],
-                                           out=tgt.unsqueeze(0), work=work)
-                ops.nl_residual(nb["diag"], nb["off"], nb["off"], nb["rhs"], v, tgt, kinds, kappa, g[step - 1],
-                                out4=mon[step - 1, k], work=rwork)
-                v, spare = tgt, v
-            k = snap.get(step)
-            if k is not None:
-                S[k].copy_(U[new])
-                if enhance:
-                    ops.ts_source_table(U[new], U[cur], None if b1 == 0.0 else U[prev], ftab, rtab, phi[step - 1], al,
-                                        b0, b1, inv_dt, point_major=pm, out=src)
-                    ops.nl_linearize(U[new], tloc, nl.kind, qc, src, c_tab=tc, point_major=pm, c_eff=c_eff[k],
-                                     f_eff=f_eff[k])
-            cur, prev, new = new, cur, prev
-        enhanced = []
-        if enhance:
+        if enhance and nl is None:
+            enhanced = self._enhance_snapshots(p, D, S)
+        elif enhance:
+            # a snapshot is the linear problem around its own nodal values: c_eff differs per snapshot
             gd = (float(self.global_domain[0]), float(self.global_domain[1]))
             shard = self._shard(ne)
             for k, s in enumerate(steps):
-                W, st = ops.enhance_varcoef(x, S[k], M, gamma, n, ta, tda, f_eff[k], global_domain=gd,
-                                            bc=(float(p["g"][s, 0]), float(p["g"][s, 1])), point_major=pm,
+                W, st = ops.enhance_varcoef(x, S[k], int(self.lssvr_M), float(self.lssvr_gamma), n, D.tab["a"],
+                                            D.tab["da"], f_eff[k], global_domain=gd,
+                                            bc=(float(p.g[s, 0]), float(p.g[s, 1])), point_major=pm,
                                             c_values=c_eff[k], **shard)
                 enhanced.append(EnhancedSolution(x, W, st))
-        host = torch.cat([S.reshape(-1), md, mo, *(A[al][k] for al in sorted(A) for k in ("diag", "off")),
-                          loads.reshape(-1), mon.reshape(-1)]).cpu().numpy()     # one copy: snapshots, bands, monitor
-        cut = np.cumsum([ns * (ne + 1), ne + 1, ne] + [ne + 1, ne] * len(A) + [loads.numel()])
-        parts = np.split(host, cut)
-        bands = dict(mass=(parts[1], parts[2]), loads=parts[-2].reshape(-1, ne + 1),
-                     step={al: (parts[3 + 2 * i], parts[4 + 2 * i]) for i, al in enumerate(sorted(A))})
-        newton = parts[-1].reshape(nsteps, iters, 4)
-
-        def history(i):
-            return ", ".join(f"|R| {r:.3e} |dv| {d:.3e}" for r, d, _, _ in newton[i])
-        bad = np.nonzero(newton[:, :, 3].sum(axis=1) != 0.0)[0]
-        if bad.size:
-            i = int(bad[0])
-            raise RuntimeError(f"solve_transient: step {i + 1} met {int(newton[i, :, 3].sum())} non-finite value(s) in "
-                               f"its Newton iteration ({history(i)}); shorten the step")
-        last = newton[:, -1, :]
-        slow = np.nonzero(last[:, 1] > tol * np.maximum(1.0, last[:, 2]))[0]
-        if slow.size:
-            i = int(slow[0])
-            raise RuntimeError(f"solve_transient: step {i + 1} did not converge in {iters} Newton iteration(s) to "
-                               f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
-        return TransientSolution(p["times"][steps].copy(), parts[0].reshape(ns, ne + 1), enhanced, bands, newton)
+        order = sorted(alphas)
+        host = _read_back(nodal=S, mass=D.bands["mass"], loads=loads, newton=mon,      # one copy: snapshots, bands, monitor
+                          **{f"step{i}": D.bands[al] for i, al in enumerate(order)})
+        bands = dict(mass=host["mass"], loads=host["loads"], step={al: host[f"step{i}"] for i, al in enumerate(order)})
+        newton = host["newton"]
+        if nl is not None:
+            def history(i):
+                return ", ".join(f"|R| {r:.3e} |dv| {d:.3e}" for r, d, _, _ in newton[i])
+            bad = np.nonzero(newton[:, :, 3].sum(axis=1) != 0.0)[0]
+            if bad.size:
+                i = int(bad[0])
+                raise RuntimeError(f"solve_transient: step {i + 1} met {int(newton[i, :, 3].sum())} non-finite value(s) in "
+                                   f"its Newton iteration ({history(i)}); shorten the step")
+            last = newton[:, -1, :]
+            slow = np.nonzero(last[:, 1] > tol * np.maximum(1.0, last[:, 2]))[0]
+            if slow.size:
+                i = int(slow[0])
+                raise RuntimeError(f"solve_transient: step {i + 1} did not converge in {iters} Newton iteration(s) to "
+                                   f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
+        return TransientSolution(p.times[steps].copy(), host["nodal"], enhanced, bands, newton)
 
     # ---- wave problems (no reference counterpart; DESIGN.md section 29) -----------------------------
+    def _check_wave(self, u0, v0, t_end, nsteps, damping, weight, forcing, end_data, end_accel0, snapshots, enhance,
+                    beta, gamma):
+        """:meth:`_check_time` for :meth:`solve_wave` (the tables gain d, phi the row of t = 0), and what belongs to the
+        Newmark rule: the plan gains beta, gamma, v_init, accel0 [2] and shift [ne, nquad], the reaction table of the
+        step's matrix, which must stay definite."""
+        p = self._check_time("solve_wave", u0, t_end, nsteps, weight, forcing, end_data, snapshots, enhance,
+                             damping=damping, phi0=True)
+        p.beta, p.gamma = float(beta), float(gamma)
+        if not (math.isfinite(p.beta) and math.isfinite(p.gamma)):
+            raise ValueError(f"beta and gamma must be finite, got {beta!r}, {gamma!r}")
+        # (the bound itself is allowed: 0.25 * (0.6 + 0.5) ** 2 rounds one ulp above 0.3025)
+        if p.gamma < 0.5 or p.beta * (1.0 + 2.0 ** -50) < 0.25 * (p.gamma + 0.5) ** 2:
+            raise ValueError(f"beta = {p.beta!r}, gamma = {p.gamma!r}: the Newmark rule is unconditionally stable for "
+                             "gamma >= 1/2 and beta >= (gamma + 1/2)^2 / 4 only, and the step is not checked "
+                             "against the mesh")
+        if not callable(v0):
+            raise ValueError("v0 must be a callable v0(x)")
+        p.v_init = np.array(np.broadcast_to(np.asarray(v0(p.nodes), dtype=np.float64), p.nodes.shape))
+        for i, end in ((0, 0), (1, -1)):
+            if p.kinds[i] == ops.END_DIRICHLET:
+                if callable(p.end_data[i]) and end_accel0 is None:
+                    raise ValueError("end_accel0 = (g_left''(0), g_right''(0)) is needed when a Dirichlet end has "
+                                     "callable end_data: the first acceleration takes that value at the end, and "
+                                     "the average-acceleration rule never damps an error in it")
+                if not callable(p.end_data[i]):
+                    p.v_init[end] = 0.0                       # constant Dirichlet data: the end does not move
+        acc0 = (0.0, 0.0) if end_accel0 is None else end_accel0
+        if not isinstance(acc0, (tuple, list, np.ndarray)) or len(acc0) != 2:
+            raise ValueError("end_accel0 must be a pair (g_left''(0), g_right''(0))")
+        p.accel0 = np.array([float(acc0[0]), float(acc0[1])])
+        self._check_finite(("v0", p.v_init), ("end_accel0", p.accel0))
+        p.shift = p.quad["c"] + p.quad["rho"] / (p.beta * p.dt ** 2)
+        if damping is not None:
+            p.shift = p.shift + p.gamma * p.quad["d"] / (p.beta * p.dt)
+        if not np.all(p.shift >= 0.0):
+            raise ValueError(f"c + rho / (beta dt^2) + gamma d / (beta dt) < 0 at a quadrature point "
+                             f"(dt = {p.dt:.6g}): the step's matrix would not be positive definite, and the solve "
+                             "does not pivot; shorten the step")
+        return p
+
     def solve_wave(self, u0, v0, t_end, *, nsteps, damping=None, weight=None, forcing=None, end_data=None,
                    end_accel0=None, snapshots=None, enhance=True, beta=0.25, gamma=0.5):
         """rho u_tt + d u_t - (a u')' + c u = f(x, t) for 0 < t <= ``t_end`` with u(x, 0) = ``u0(x)`` and
@@ -1837,57 +1848,40 @@ class FEMLSSVRPrimalSolver:
         :class:`WaveSolution`; the solver's attributes are left as they are."""
         self._check_nonlinear("solve_wave")
         torch = _torch()
-        p = self._check_transient(u0, t_end, nsteps, None, weight, forcing, end_data, snapshots, bool(enhance),
-                                  wave=dict(v0=v0, damping=damping, beta=beta, gamma=gamma, end_accel0=end_accel0))
-        nodes, kinds, kappa, dt, steps, q = p["nodes"], p["kinds"], p["kappa"], p["dt"], p["steps"], p["quad"]
-        beta, gamma = p["beta"], p["gamma"]
-        nsteps, ne, ns, damped = int(nsteps), nodes.size - 1, len(steps), "d" in q
-        dev = _device(self.device)
-        x = _to_dev(nodes, dev)
-        zq = torch.zeros((ne, int(self.nquad)), dtype=torch.float64, device=dev)
-        aq = None if self.coef is None else _to_dev(q["a"], dev)
-        K = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=_to_dev(q["c"], dev))
-        Mb = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["rho"], dev))
-        Db = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=zq, c_quad=_to_dev(q["d"], dev)) if damped else None
-        shift = q["c"] + q["rho"] / (beta * dt ** 2)
-        if damped:
-            shift = shift + gamma * q["d"] / (beta * dt)
-        A = ops.p1_assemble(x, self.nquad, rhs_quad=zq, a_quad=aq, c_quad=_to_dev(shift, dev))       # ONE assembly
-        loads = ops.p1_load_multi(x, _to_dev(q["f"], dev), self.nquad)
-        phi, g = _to_dev(p["phi"], dev), _to_dev(p["g"], dev)              # row n: the time t_n
-        md, mo = Mb["diag"], Mb["off"]
-        dd, do = (Db["diag"], Db["off"]) if damped else (None, None)
-        M, reg, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
-        pm = M <= 16                         # the lane kernel of lssvr_enhance_multi reads point-major tables
+        enhance = bool(enhance)
+        p = self._check_wave(u0, v0, t_end, nsteps, damping, weight, forcing, end_data, end_accel0, snapshots, enhance,
+                             beta, gamma)
+        kinds, kappa, dt, steps, q, beta, gamma = p.kinds, p.kappa, p.dt, p.steps, p.quad, p.beta, p.gamma
+        nsteps, ne, ns, damped = int(nsteps), p.nodes.size - 1, len(steps), damping is not None
+        # K, M_rho, M_d and the step's matrix K + M_rho / (beta dt^2) + gamma M_d / (beta dt): ONE assembly each
+        D = self._time_setup(p, enhance, [("stiff", True, q["c"]), ("mass", False, q["rho"]),
+                                          *([("damp", False, q["d"])] if damped else []), ("step", True, p.shift)],
+                             nbuf=2)
+        dev, U, b, loads, work, snap, pm = D.dev, D.U, D.b, D.loads, D.work, D.snap, D.pm
+        phi, g, SA = D.phi, D.g, D.S                      # row n: the time t_n; SA: the accelerations of the snapshots
+        (kd, ko), (md, mo), (ad, ao) = D.bands["stiff"], D.bands["mass"], D.bands["step"]
+        dd, do = D.bands["damp"] if damped else (None, None)
         if enhance:
-            c = p["colloc"]
-            ta, tda, tc, rtab = (_to_dev(c[k].T if pm else c[k], dev) for k in ("a", "da", "c", "rho"))
-            ftab = _to_dev(np.transpose(c["f"], (0, 2, 1)) if pm else c["f"], dev)
-            src = torch.empty((ns,) + tuple(rtab.shape), dtype=torch.float64, device=dev)
+            ftab, rtab, src = D.tab["f"], D.tab["rho"], D.src
             if damped:
-                dtab = _to_dev(c["d"].T if pm else c["d"], dev)
                 tmp = torch.empty((1,) + tuple(rtab.shape), dtype=torch.float64, device=dev)
                 one = torch.ones(1, dtype=torch.float64, device=dev)
         # the energy reads every node: all ends as Robin rows, kappa of the problem's Robin ends (eig_apply adds it
         # to K's end diagonal itself, so u^T K u already holds kappa u_end^2)
         ekinds = (ops.END_ROBIN, ops.END_ROBIN)
-        ekap = tuple(kp if kd == ops.END_ROBIN else 0.0 for kd, kp in zip(kinds, kappa))
-        U = torch.empty((2, ne + 1), dtype=torch.float64, device=dev)
+        ekap = tuple(kp if kd_ == ops.END_ROBIN else 0.0 for kd_, kp in zip(kinds, kappa))
         VA = torch.empty((2, 2, ne + 1), dtype=torch.float64, device=dev)     # [pair][v, acc]
         SZ = torch.empty((ns + 1, 2, ne + 1), dtype=torch.float64, device=dev)     # [t = 0 and the snapshots][u, v]
-        SA = torch.empty((ns, ne + 1), dtype=torch.float64, device=dev)
         gram = torch.empty((ns + 1, 2, 2, 2), dtype=torch.float64, device=dev)
         MZ, KZ = (torch.empty((2, ne + 1), dtype=torch.float64, device=dev) for _ in range(2))
-        b = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
-        work = ops.tridiag_work(b, ne, 1, "bc")
         ework = ops._scratch(None, ops._capi.load().lssvr_eig_work_bytes(ne, 2), dev)
         # ---- the first acceleration: M_rho acc0 = load(0) - M_d v0 - K u0, Robin rows with g(0) - kappa u0
-        SZ[0, 0].copy_(_to_dev(p["u_init"], dev))
-        SZ[0, 1].copy_(_to_dev(p["v_init"], dev))
-        ops.eig_apply(K["diag"], K["off"], md, mo, SZ[0], ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram[0], work=ework)
+        SZ[0, 0].copy_(U[0])
+        SZ[0, 1].copy_(_to_dev(p.v_init, dev))
+        ops.eig_apply(kd, ko, md, mo, SZ[0], ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram[0], work=ework)
         r0 = (phi[0][:, None] * loads).sum(dim=0)
         if damped:
-            dv = ops.eig_apply(K["diag"], K["off"], dd, do, SZ[0, 1:2], ekinds, ekap, work=ework)[0]
+            dv = ops.eig_apply(kd, ko, dd, do, SZ[0, 1:2], ekinds, ekap, work=ework)[0]
             r0 = r0 - dv[0]
         r0 = r0 - KZ[0]
         a_ends = [0.0, 0.0]
@@ -1895,19 +1889,16 @@ class FEMLSSVRPrimalSolver:
             if kinds[i] == ops.END_ROBIN:
                 r0[end] += g[0, i]
             else:
-                a_ends[i] = float(p["accel0"][i])
-        U[0].copy_(SZ[0, 0])
+                a_ends[i] = float(p.accel0[i])
         VA[0, 0].copy_(SZ[0, 1])
         ops.tridiag_bc_solve_multi(md, mo, r0.unsqueeze(0).contiguous(), kinds, (0.0, 0.0), [a_ends], out=VA[0, 1:2],
                                    work=work)
-        snap = {s: k for k, s in enumerate(steps)}
         cur, new, pr = 0, 1, 0
         ops.wave_advance(None, U[cur:cur + 1], VA[pr, 0:1], VA[pr, 1:2], md, mo, dd, do, loads, phi[1:2], dt, beta,
                          gamma, rhs_out=b)
         # the loop: launches on the current stream only
         for step in range(1, nsteps + 1):
-            ops.tridiag_bc_solve_multi(A["diag"], A["off"], b, kinds, kappa, g[step:step + 1], out=U[new:new + 1],
-                                       work=work)
+            ops.tridiag_bc_solve_multi(ad, ao, b, kinds, kappa, g[step:step + 1], out=U[new:new + 1], work=work)
             last = step == nsteps
             ops.wave_advance(U[new:new + 1], U[cur:cur + 1], VA[pr, 0:1], VA[pr, 1:2], md, mo, dd, do, loads,
                              None if last else phi[step + 1:step + 2], dt, beta, gamma, V_out=VA[1 - pr, 0:1],
@@ -1918,33 +1909,22 @@ class FEMLSSVRPrimalSolver:
                 SZ[k + 1, 0].copy_(U[cur])
                 SZ[k + 1, 1].copy_(VA[pr, 0])
                 SA[k].copy_(VA[pr, 1])
-                ops.eig_apply(K["diag"], K["off"], md, mo, SZ[k + 1], ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram[k + 1],
-                              work=ework)
+                ops.eig_apply(kd, ko, md, mo, SZ[k + 1], ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram[k + 1], work=ework)
                 if enhance:
                     # f - rho I_h acc: alpha = 1, beta0 = beta1 = 0, inv_dt = 1 leave U2 as it is (U0 is read, times 0)
                     ops.ts_source_table(SA[k], SA[k], None, ftab, rtab, phi[step], 1.0, 0.0, 0.0, 1.0, point_major=pm,
                                         out=tmp[0] if damped else src[k])
                     if damped:           # ... - d I_h v: the table so far is the single term, phi = 1
-                        ops.ts_source_table(SZ[k + 1, 1], SZ[k + 1, 1], None, tmp, dtab, one, 1.0, 0.0, 0.0, 1.0,
+                        ops.ts_source_table(SZ[k + 1, 1], SZ[k + 1, 1], None, tmp, D.tab["d"], one, 1.0, 0.0, 0.0, 1.0,
                                             point_major=pm, out=src[k])
-        enhanced = []
-        if enhance:
-            gd = (float(self.global_domain[0]), float(self.global_domain[1]))
-            bc = g[torch.as_tensor(steps, device=dev)].contiguous()
-            W, st = ops.enhance_multi(x, SZ[1:, 0].contiguous(), M, reg, n, ta, tda, src, c_values=tc, bc=bc,
-                                      point_major=pm, global_domain=gd, **self._shard(ne))
-            enhanced = [EnhancedSolution(x, W[k], st[k]) for k in range(ns)]
-        band_list = [md, mo, K["diag"], K["off"], A["diag"], A["off"]] + ([dd, do] if damped else [])
-        host = torch.cat([SZ.reshape(-1), SA.reshape(-1), gram.reshape(-1), *band_list,
-                          loads.reshape(-1)]).cpu().numpy()         # one copy: the snapshots, the energies and the bands
-        cut = np.cumsum([SZ.numel(), SA.numel(), gram.numel()] + [t.numel() for t in band_list])
-        parts = np.split(host, cut)
-        sz, gr = parts[0].reshape(ns + 1, 2, ne + 1), parts[2].reshape(ns + 1, 2, 2, 2)
-        bands = dict(mass=(parts[3], parts[4]), stiff=(parts[5], parts[6]), step=(parts[7], parts[8]),
-                     damp=(parts[9], parts[10]) if damped else None, loads=parts[-1].reshape(-1, ne + 1))
+        enhanced = self._enhance_snapshots(p, D, SZ[1:, 0].contiguous()) if enhance else []
+        # one copy: the snapshots, the energies and the bands
+        host = _read_back(sz=SZ, accel=SA, gram=gram, loads=loads, damp=D.bands.get("damp"),
+                          **{k: D.bands[k] for k in ("mass", "stiff", "step")})
+        sz, gr = host["sz"], host["gram"]
         energy = 0.5 * (gr[:, 1, 1, 1] + gr[:, 0, 0, 0])
-        return WaveSolution(p["times"][steps].copy(), sz[1:, 0].copy(), sz[1:, 1].copy(), parts[1].reshape(ns, ne + 1),
-                            energy, enhanced, bands)
+        return WaveSolution(p.times[steps].copy(), sz[1:, 0].copy(), sz[1:, 1].copy(), host["accel"], energy, enhanced,
+                            {k: host[k] for k in ("mass", "stiff", "step", "damp", "loads")})
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):

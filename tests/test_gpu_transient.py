@@ -152,4 +152,4 @@ def test_accuracy_record(dev, note):
 
 
 def test_refusals_launch_nothing(dev, monkeypatch):
-    tr.check_refusals(monkeypatch)
+    tr.check_refusals(monkeypatch, tr.call_transient, tr.refusals(), tr.passing())

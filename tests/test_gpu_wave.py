@@ -173,4 +173,4 @@ def test_enhanced_snapshots_against_the_oracle_rows(dev, note, M, n, name):
 
 
 def test_refusals_launch_nothing(dev, monkeypatch):
-    wr.check_refusals(monkeypatch)
+    wr.tr.check_refusals(monkeypatch, wr.call_wave, wr.refusals(), wr.passing())

@@ -141,7 +141,7 @@ def test_ops_wrappers_reject_host_tensors():
 
 
 def test_facade_refusals(monkeypatch):
-    tr.check_refusals(monkeypatch)
+    tr.check_refusals(monkeypatch, tr.call_transient, tr.refusals(), tr.passing())
 
 
 def test_accuracy_record_of_the_prototype():

@@ -87,7 +87,7 @@ def test_ops_refuses_host_tensors_and_shapes():
 
 
 def test_refusals_launch_nothing(monkeypatch):
-    nr.check_refusals(monkeypatch)
+    nr.tr.check_refusals(monkeypatch, nr.tr.call_transient, nr.refusals(), nr.passing())
 
 
 def test_linear_keywords_are_untouched():

@@ -162,7 +162,7 @@ def test_first_acceleration_and_moving_end():
 
 
 def test_facade_refusals(monkeypatch):
-    wr.check_refusals(monkeypatch)
+    wr.tr.check_refusals(monkeypatch, wr.call_wave, wr.refusals(), wr.passing())
 
 
 def test_accuracy_record_of_the_prototype():

@@ -7,7 +7,6 @@ under the bars of tests/semilinear_rules.py.  Every "within rounding" bar of the
 (scripts/proto/transient_semilinear_proto.py, LAPACK's banded LU) itself reads on the SAME case against the same loop in
 np.longdouble, with a floor of 4 eps -- the rule of tests/transient_rules.py.  The reading is taken when the test runs
 (cached), never from the code under test."""
-import ctypes
 import math
 import os
 import re
@@ -33,8 +32,7 @@ BANDS_BAR = tr.BANDS_BAR
 ENH_FAMILY_BAR = 1e-11                  # the reaction-row tests' bar against the float64 restatement, M <= 22
 
 
-def _zero(x):
-    return 0.0 * np.asarray(x, dtype=np.float64)
+_zero, _hp, _h = tr._zero, tr._hp, tr._h
 
 
 def _const(v):
@@ -54,14 +52,6 @@ def kernel_rule(nquad):
 
 
 # ---- the host mirror and the numpy restatement of lssvr_ts_nl_assemble ----------------------------------------------------
-def _hp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-def _h(a):
-    return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-
-
 def assemble_host(x, u, a_q, cs_q, q_q, r, kind, check=True, ne=None, nquad=None, nterm=None, outs=None, drop=()):
     """lssvr_ts_nl_assemble_host -> (rc, diag, off, rhs).  ``drop``: names of pointers handed over as NULL; ``outs``:
     the three output arrays to pass instead of fresh ones (the aliasing refusals)."""
@@ -176,17 +166,9 @@ CASES = {"general-poly-33": general_poly, "general-exp-33": general_exp,
 LOOP_READ = {"cubic-bdf1-2": 4.6e-16, "cubic-bdf1-5": 9.0e-16, "cubic-bdf1-32": 1.6e-15, "cubic-bdf1-33": 2.8e-15,
              "cubic-bdf2-2": 1.4e-15, "cubic-bdf2-5": 9.6e-16, "cubic-bdf2-32": 1.6e-15, "cubic-bdf2-33": 2.8e-15}
 
-_REFERENCES = {}
-
-
 def references(name, bands=None):
     """(case, np.longdouble loop, float64 loop), computed once per (name, bands)."""
-    key = (name, None if bands is None else hash(b"".join(np.ascontiguousarray(t).tobytes()
-                                                          for t in (*bands["mass"], bands["loads"]))))
-    if key not in _REFERENCES:
-        case = CASES[name]()
-        _REFERENCES[key] = (case, case.run(np.longdouble, bands), case.run(bands=bands))
-    return _REFERENCES[key]
+    return tr.references(CASES, name, bands)
 
 
 def loop_reading(name, nodal, bands=None):
@@ -271,70 +253,56 @@ def enhanced_reference(name, M, n_colloc, bands=None):
     return Wl, max(ENH_FAMILY_BAR, MARGIN * noise), noise
 
 
-# ---- what solve_transient(..., nonlinear=...) refuses: (name, constructor kwargs, call kwargs) -----------------------------
+# ---- what solve_transient(..., nonlinear=...) refuses: (name, constructor kwargs, call kwargs, a fragment of the message) ---
 def refusals():
     ok = ("poly", [_zero, _zero, _zero, _const(1.0)])
     nl = dict(nsteps=4, nonlinear=ok)
     nan_q = ("poly", [lambda x: np.full_like(np.asarray(x, dtype=np.float64), np.nan)])
     node_q = ("poly", [lambda x: np.where(np.asarray(x) == -1.0, np.inf, 1.0)])      # a collocation point only
+    me = "solve_transient "
+    # the message of a solver built with nonlinear= points at the keyword of the call
+    own = "build the solver without nonlinear= and call solve_transient(..., nonlinear=...)"
+    family = "nonlinear must be ('poly', [q0, q1, ...]) or ('exp', q0, q1)"
     return [
-        ("nonlinear on the solver", dict(nonlinear=ok), dict(nsteps=4)),
-        ("nonlinear on the solver and the call", dict(nonlinear=ok), nl),
-        ("newton_iters without nonlinear", {}, dict(nsteps=4, newton_iters=3)),
-        ("newton_tol without nonlinear", {}, dict(nsteps=4, newton_tol=1e-8)),
-        ("a callable of u", {}, dict(nsteps=4, nonlinear=lambda x, u: u ** 3)),
-        ("unknown family", {}, dict(nsteps=4, nonlinear=("cubic", [_zero]))),
-        ("7 terms", {}, dict(nsteps=4, nonlinear=("poly", [_zero] * 7))),
-        ("exp with one table", {}, dict(nsteps=4, nonlinear=("exp", _zero))),
-        ("newton_iters 0", {}, dict(newton_iters=0, **nl)),
-        ("newton_iters 9", {}, dict(newton_iters=9, **nl)),
-        ("newton_iters 2.5", {}, dict(newton_iters=2.5, **nl)),
-        ("newton_tol 0", {}, dict(newton_tol=0.0, **nl)),
-        ("newton_tol nan", {}, dict(newton_tol=math.nan, **nl)),
-        ("q not finite", {}, dict(nsteps=4, nonlinear=nan_q)),
-        ("q not finite at a node", {}, dict(nsteps=4, nonlinear=node_q)),
-        ("q of the wrong shape", {}, dict(nsteps=4, nonlinear=("poly", [lambda x: np.ones(3)]))),
-        ("n_colloc > 64 with enhance", dict(n_colloc=65, lssvr_M=9), nl),
-        ("convection", dict(convection=lambda x: 0.0 * x), nl),
-        ("periodic", dict(boundary="periodic", reaction=lambda x: 1.0 + 0.0 * x), nl),
-        ("fem_solver flux", dict(fem_solver="flux"), nl),
-        ("fem_solver pivot", dict(fem_solver="pivot"), nl),
-        ("element_degrees", dict(_degrees=True), nl),
-        ("solver", dict(solver=1), nl),
-        ("rho <= 0", {}, dict(weight=lambda x: x, **nl)),
-        ("c + rho/dt < 0", dict(reaction=lambda x: -100.0 + 0.0 * x), nl),
-        ("snapshot past the end", {}, dict(snapshots=[2, 5], **nl)),
-        ("scheme", {}, dict(scheme="bdf3", **nl)),
+        ("nonlinear on the solver", dict(nonlinear=ok), dict(nsteps=4), own),
+        ("nonlinear on the solver and the call", dict(nonlinear=ok), nl, own),
+        ("newton_iters without nonlinear", {}, dict(nsteps=4, newton_iters=3),
+         "newton_iters and newton_tol belong to solve_transient(..., nonlinear=...)"),
+        ("newton_tol without nonlinear", {}, dict(nsteps=4, newton_tol=1e-8),
+         "newton_iters and newton_tol belong to solve_transient(..., nonlinear=...)"),
+        ("a callable of u", {}, dict(nsteps=4, nonlinear=lambda x, u: u ** 3),
+         family + ": g comes from a tabulated family, not from a callable of u"),
+        ("unknown family", {}, dict(nsteps=4, nonlinear=("cubic", [_zero])), family + ", got ('cubic', ["),
+        ("7 terms", {}, dict(nsteps=4, nonlinear=("poly", [_zero] * 7)), "nonlinear 'poly' takes 1 .. 6 terms (nterm), got 7"),
+        ("exp with one table", {}, dict(nsteps=4, nonlinear=("exp", _zero)),
+         "nonlinear=('exp', q0, q1) takes the two callables q0(x), q1(x)"),
+        ("newton_iters 0", {}, dict(newton_iters=0, **nl), "newton_iters must be an integer in 1 .. 8, got 0"),
+        ("newton_iters 9", {}, dict(newton_iters=9, **nl), "newton_iters must be an integer in 1 .. 8, got 9"),
+        ("newton_iters 2.5", {}, dict(newton_iters=2.5, **nl), "newton_iters must be an integer in 1 .. 8, got 2.5"),
+        ("newton_tol 0", {}, dict(newton_tol=0.0, **nl), "newton_tol must be finite and > 0, got 0.0"),
+        ("newton_tol nan", {}, dict(newton_tol=math.nan, **nl), "newton_tol must be finite and > 0, got nan"),
+        ("q not finite", {}, dict(nsteps=4, nonlinear=nan_q), "nonlinear q_0 is not finite at a quadrature point"),
+        ("q not finite at a node", {}, dict(nsteps=4, nonlinear=node_q),
+         "nonlinear q_0 is not finite at a collocation point"),
+        ("q of the wrong shape", {}, dict(nsteps=4, nonlinear=("poly", [lambda x: np.ones(3)])),
+         "nonlinear q_0 must return one value per point ([8, 2] at the quadrature points)"),
+        ("n_colloc > 64 with enhance", dict(n_colloc=65, lssvr_M=9), nl,
+         "nonlinear needs n_colloc <= 64 for the enhanced snapshots, got 65"),
+        ("convection", dict(convection=lambda x: 0.0 * x), nl, me + tr.STRUCTURAL[0]),
+        ("periodic", dict(boundary="periodic", reaction=lambda x: 1.0 + 0.0 * x), nl, me + tr.STRUCTURAL[1]),
+        ("fem_solver flux", dict(fem_solver="flux"), nl, me + tr.STRUCTURAL[2]),
+        ("fem_solver pivot", dict(fem_solver="pivot"), nl, me + tr.STRUCTURAL[2]),
+        ("element_degrees", dict(_degrees=True), nl, me + tr.STRUCTURAL[3]),
+        ("solver", dict(solver=1), nl, me + tr.STRUCTURAL[4]),
+        ("rho <= 0", {}, dict(weight=lambda x: x, **nl), tr.RHO_MSG),
+        ("c + rho/dt < 0", dict(reaction=lambda x: -100.0 + 0.0 * x), nl,
+         "c + rho / dt < 0 at a quadrature point (dt = 0.1)"),
+        ("snapshot past the end", {}, dict(snapshots=[2, 5], **nl),
+         "snapshots must be step indices in 1 .. nsteps = 4, got [2, 5]"),
+        ("scheme", {}, dict(scheme="bdf3", **nl), "scheme must be 'bdf1' or 'bdf2', got 'bdf3'"),
     ]
 
 
-def check_refusals(monkeypatch):
-    """Every refusal is a ValueError raised on the host: the library loader and the device lookup are replaced by
-    functions that fail the test, so no entry is bound and no kernel can be launched."""
-    import pytest
-    import hybrid_fem_lssvr_amd as pkg
-    from hybrid_fem_lssvr_amd import _capi, solver
-
-    def forbidden(*a, **k):
-        raise AssertionError("a device call was reached before the refusal")
-    monkeypatch.setattr(_capi, "load", forbidden)
-    monkeypatch.setattr(solver, "_device", forbidden)
-    for name, ctor, call in refusals():
-        ctor, call = dict(ctor), dict(call)
-        degrees = ctor.pop("_degrees", False)
-        ctor.setdefault("lssvr_M", 9)
-        ctor.setdefault("n_colloc", 16)
-        s = pkg.FEMLSSVRPrimalSolver(9, **ctor)
-        if degrees:
-            s.element_degrees = np.full(8, 9)
-        with pytest.raises(ValueError):
-            s.solve_transient(lambda x: 0.0 * x, 0.4, **call)
-            raise AssertionError(f"{name}: not refused")
-    # the message of a solver built with nonlinear= points at the keyword of the call
-    s = pkg.FEMLSSVRPrimalSolver(9, nonlinear=refusals()[0][1]["nonlinear"])
-    with pytest.raises(ValueError, match=r"solve_transient\(\.\.\., nonlinear="):
-        s.solve_transient(lambda x: 0.0 * x, 0.4, nsteps=4)
-    # a well-formed call gets as far as the device
-    s = pkg.FEMLSSVRPrimalSolver(9, lssvr_M=9, n_colloc=16)
-    with pytest.raises(AssertionError, match="device call"):
-        s.solve_transient(lambda x: 0.0 * x, 0.4, nsteps=4, nonlinear=refusals()[1][2]["nonlinear"])
+def passing():
+    """A well-formed call gets as far as the device."""
+    return [(dict(lssvr_M=9, n_colloc=16), dict(nsteps=4, nonlinear=refusals()[1][2]["nonlinear"]))]

@@ -197,16 +197,27 @@ def bands_error(case, bands):
 _REFERENCES = {}
 
 
-def _references(name, bands=None):
-    """(case, np.longdouble loop, float64 loop), computed once per (name, bands)."""
-    key = (name, None if bands is None else hashlib.sha1(b"".join(
-        np.ascontiguousarray(t).tobytes() for t in (*bands["mass"], bands["loads"],
-                                                    *(v for al in sorted(bands["step"]) for v in bands["step"][al]))
-    )).hexdigest())
+def _band_bytes(v):
+    """The bytes of every array in ``v`` (arrays, tuples and dicts of them, None), dict entries in key order."""
+    if isinstance(v, dict):
+        v = [v[k] for k in sorted(v)]
+    if isinstance(v, (tuple, list)):
+        return b"".join(_band_bytes(t) for t in v)
+    return b"" if v is None else np.ascontiguousarray(v).tobytes()
+
+
+def references(cases, name, bands=None):
+    """(case, np.longdouble loop, float64 loop) of ``cases[name]``, computed once per (cases, name, bands): the one
+    cache of the transient, semilinear transient and wave rules."""
+    key = (id(cases), name, None if bands is None else hashlib.sha1(_band_bytes(bands)).hexdigest())
     if key not in _REFERENCES:
-        case = CASES[name]()
+        case = cases[name]()
         _REFERENCES[key] = (case, case.run(np.longdouble, bands=bands), case.run(bands=bands))
     return _REFERENCES[key]
+
+
+def _references(name, bands=None):
+    return references(CASES, name, bands)
 
 
 def loop_reading(name, nodal, bands=None):
@@ -228,11 +239,11 @@ CASES = {"general-33": general, "neumann-25": neumann, "decay-bdf2-33": lambda: 
 
 # ---- the host mirrors ---------------------------------------------------------------------------------------------------------
 def _hp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 def _h(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
 def rhs_host(md, mo, U0, U1, loads, phi, beta0, beta1, inv_dt, check=True):
@@ -343,37 +354,67 @@ ACCURACY = {8: (9.298e-3, 2.457e-3), 16: (2.375e-3, 6.184e-4), 32: (5.970e-4, 1.
 ACCURACY_STEPS, ACCURACY_T, ACCURACY_POINTS = 64, 1.0, 2001
 
 
-# ---- what solve_transient refuses: (name, constructor kwargs, call kwargs) -----------------------------------------------
+# ---- what solve_transient refuses: (name, constructor kwargs, call kwargs, a fragment of the message) ----------------------
+STRUCTURAL = ("has no convection term", "has no boundary='periodic'", "needs fem_solver='bands'",
+              "has no element_degrees", "needs solver=ops.SOLVER_PRIMAL")
+RHO_MSG = "weight must be positive at every quadrature point (rho > 0)"
+
+
 def refusals():
     u0 = lambda x: 0.0 * x      # noqa: E731
     base = dict(nsteps=4)
+    me = "solve_transient "
     return [
-        ("convection", dict(convection=lambda x: 0.0 * x), base),
-        ("periodic", dict(boundary="periodic", reaction=lambda x: 1.0 + 0.0 * x), base),
-        ("fem_solver flux", dict(fem_solver="flux"), base),
-        ("fem_solver pivot", dict(fem_solver="pivot"), base),
-        ("element_degrees", dict(_degrees=True), base),
-        ("solver", dict(solver=1), base),
-        ("rho <= 0", {}, dict(nsteps=4, weight=lambda x: x)),
-        ("c + rho/dt < 0", dict(reaction=lambda x: -100.0 + 0.0 * x), dict(nsteps=4)),
-        ("R > 8", {}, dict(nsteps=4, forcing=[(1.0, u0)] * 9)),
-        ("snapshot 0", {}, dict(nsteps=4, snapshots=[0])),
-        ("snapshot past the end", {}, dict(nsteps=4, snapshots=[2, 5])),
-        ("non-finite forcing", {}, dict(nsteps=4, forcing=[(1.0, lambda x: np.full_like(x, np.nan))])),
+        ("convection", dict(convection=lambda x: 0.0 * x), base, me + STRUCTURAL[0]),
+        ("periodic", dict(boundary="periodic", reaction=lambda x: 1.0 + 0.0 * x), base, me + STRUCTURAL[1]),
+        ("fem_solver flux", dict(fem_solver="flux"), base, me + STRUCTURAL[2]),
+        ("fem_solver pivot", dict(fem_solver="pivot"), base, me + STRUCTURAL[2]),
+        ("element_degrees", dict(_degrees=True), base, me + STRUCTURAL[3]),
+        ("solver", dict(solver=1), base, me + STRUCTURAL[4]),
+        ("rho <= 0", {}, dict(nsteps=4, weight=lambda x: x), RHO_MSG),
+        ("c + rho/dt < 0", dict(reaction=lambda x: -100.0 + 0.0 * x), dict(nsteps=4),
+         "c + rho / dt < 0 at a quadrature point (dt = 0.1)"),
+        ("R > 8", {}, dict(nsteps=4, forcing=[(1.0, u0)] * 9), "forcing must hold 1 .. 8 terms (R <= 8), got 9"),
+        ("snapshot 0", {}, dict(nsteps=4, snapshots=[0]), "snapshots must be step indices in 1 .. nsteps = 4, got [0]"),
+        ("snapshot past the end", {}, dict(nsteps=4, snapshots=[2, 5]),
+         "snapshots must be step indices in 1 .. nsteps = 4, got [2, 5]"),
+        ("non-finite forcing", {}, dict(nsteps=4, forcing=[(1.0, lambda x: np.full_like(x, np.nan))]),
+         "forcing[0] f_x is not finite at a quadrature point"),
         ("non-finite forcing at a node (a collocation point, no quadrature point)", {},
-         dict(nsteps=4, forcing=[(1.0, lambda x: np.where(x == -1.0, np.inf, 1.0))])),
-        ("non-finite weight at a node", {}, dict(nsteps=4, weight=lambda x: np.where(x == 1.0, np.nan, 1.0))),
-        ("forcing of the wrong shape", {}, dict(nsteps=4, forcing=[(1.0, lambda x: np.ones(3))])),
-        ("non-finite phi", {}, dict(nsteps=4, forcing=[(lambda t: math.inf, u0)])),
-        ("non-finite end data", {}, dict(nsteps=4, end_data=(lambda t: math.nan, 0.0))),
-        ("non-finite u0", {}, dict(nsteps=4, _u0=lambda x: np.full_like(x, np.inf))),
-        ("scheme", {}, dict(nsteps=4, scheme="bdf3")),
+         dict(nsteps=4, forcing=[(1.0, lambda x: np.where(x == -1.0, np.inf, 1.0))]),
+         "forcing[0] f_x is not finite at a collocation point"),
+        ("non-finite weight at a node", {}, dict(nsteps=4, weight=lambda x: np.where(x == 1.0, np.nan, 1.0)),
+         "weight is not finite at a collocation point"),
+        ("forcing of the wrong shape", {}, dict(nsteps=4, forcing=[(1.0, lambda x: np.ones(3))]),
+         "forcing[0] f_x must return one value per point ([8, 2] at the quadrature points)"),
+        ("non-finite phi", {}, dict(nsteps=4, forcing=[(lambda t: math.inf, u0)]),
+         "forcing phi is not finite where it is tabulated"),
+        # (a Dirichlet end starts at g(0), so the value is met in u0's table first)
+        ("non-finite end data", {}, dict(nsteps=4, end_data=(lambda t: math.nan, 0.0)),
+         "u0 is not finite where it is tabulated"),
+        ("non-finite u0", {}, dict(nsteps=4, _u0=lambda x: np.full_like(x, np.inf)),
+         "u0 is not finite where it is tabulated"),
+        ("scheme", {}, dict(nsteps=4, scheme="bdf3"), "scheme must be 'bdf1' or 'bdf2', got 'bdf3'"),
     ]
 
 
-def check_refusals(monkeypatch):
-    """Every refusal is a ValueError raised on the host: the library loader and the device lookup are replaced by
-    functions that fail the test, so no entry is bound and no kernel can be launched."""
+def passing():
+    """(constructor kwargs, call kwargs) that the check lets through.  c mildly negative is allowed: c + rho / dt >= 0
+    (the refusal comes later, from the missing device)."""
+    return [(dict(reaction=lambda x: -5.0 + 0.0 * x), dict(nsteps=4))]
+
+
+def call_transient(s, u0, v0, **kw):
+    return s.solve_transient(u0, 0.4, **kw)
+
+
+def check_refusals(monkeypatch, call, refusals, passing):
+    """Every row of ``refusals`` is a ValueError with the row's fragment in its message, raised on the host: the library
+    loader and the device lookup are replaced by functions that fail the test, so no entry is bound and no kernel can
+    be launched.  Every row of ``passing`` gets as far as the device.  ``call(solver, u0, v0, **call kwargs)`` runs the
+    method under test; ``_degrees`` / ``_u0`` / ``_v0`` in a row's kwargs set element_degrees and replace the zero
+    start, and lssvr_M = 9, n_colloc = 16, nsteps = 4 where a refusal row does not say."""
+    import re
     import pytest
     import hybrid_fem_lssvr_amd as pkg
     from hybrid_fem_lssvr_amd import _capi, solver
@@ -382,17 +423,20 @@ def check_refusals(monkeypatch):
         raise AssertionError("a device call was reached before the refusal")
     monkeypatch.setattr(_capi, "load", forbidden)
     monkeypatch.setattr(solver, "_device", forbidden)
-    for name, ctor, call in refusals():
-        ctor, call = dict(ctor), dict(call)
+    z = lambda x: 0.0 * x      # noqa: E731
+    for name, ctor, kw, match in refusals:
+        ctor, kw = dict(ctor), dict(kw)
         degrees = ctor.pop("_degrees", False)
-        u0 = call.pop("_u0", lambda x: 0.0 * x)
-        s = pkg.FEMLSSVRPrimalSolver(9, lssvr_M=9, n_colloc=16, **ctor)
+        u0, v0 = kw.pop("_u0", z), kw.pop("_v0", z)
+        ctor.setdefault("lssvr_M", 9)
+        ctor.setdefault("n_colloc", 16)
+        kw.setdefault("nsteps", 4)
+        s = pkg.FEMLSSVRPrimalSolver(9, **ctor)
         if degrees:
             s.element_degrees = np.full(8, 9)
-        with pytest.raises(ValueError):
-            s.solve_transient(u0, 0.4, **call)
+        with pytest.raises(ValueError, match=re.escape(match)):
+            call(s, u0, v0, **kw)
             raise AssertionError(f"{name}: not refused")
-    # c mildly negative is allowed by the check: c + rho / dt >= 0 (the refusal comes later, from the missing device)
-    s = pkg.FEMLSSVRPrimalSolver(9, reaction=lambda x: -5.0 + 0.0 * x)
-    with pytest.raises(AssertionError, match="device call"):
-        s.solve_transient(lambda x: 0.0 * x, 0.4, nsteps=4)
+    for ctor, kw in passing:
+        with pytest.raises(AssertionError, match="device call"):
+            call(pkg.FEMLSSVRPrimalSolver(9, **ctor), z, z, **kw)

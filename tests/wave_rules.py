@@ -6,9 +6,7 @@ The bars follow section 26's rule.  Every "within rounding" bar is 10x what the 
 closed form of the discrete mode, or the same loop in np.longdouble --, with a floor of 4 eps.  The reading is taken
 when the test runs (cached), never from the code under test; the figures read when the cases were written are recorded
 beside them."""
-import ctypes
 import functools
-import hashlib
 import math
 import os
 import sys
@@ -16,11 +14,12 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "scripts", "proto")):
+for _p in (ROOT, os.path.join(ROOT, "scripts", "proto"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
 import wave_proto as proto              # noqa: E402
+import transient_rules as tr            # noqa: E402
 from oracle import lssvr_oracle as orc  # noqa: E402,F401
 
 EPS = 2.0 ** -52
@@ -30,8 +29,7 @@ DIRICHLET, ROBIN = proto.DIRICHLET, proto.ROBIN
 NEWMARK = ((0.25, 0.5), (0.3025, 0.6))          # average acceleration, and a damped pair with beta = (gamma + 1/2)^2 / 4
 
 
-def _zero(x):
-    return np.zeros_like(np.asarray(x, dtype=np.float64))
+_zero, _hp, _h = tr._zero, tr._hp, tr._h
 
 
 class Case:
@@ -197,23 +195,9 @@ def bands_error(case, bands):
     return worst
 
 
-_REFERENCES = {}
-
-
-def _bands_key(bands):
-    if bands is None:
-        return None
-    arrs = [*bands["mass"], *bands["stiff"], *bands["step"], bands["loads"], *(bands["damp"] or ())]
-    return hashlib.sha1(b"".join(np.ascontiguousarray(t).tobytes() for t in arrs)).hexdigest()
-
-
 def references(name, bands=None):
     """(case, np.longdouble loop, float64 loop), computed once per (name, bands)."""
-    key = (name, _bands_key(bands))
-    if key not in _REFERENCES:
-        case = CASES[name]()
-        _REFERENCES[key] = (case, case.run(np.longdouble, bands=bands), case.run(bands=bands))
-    return _REFERENCES[key]
+    return tr.references(CASES, name, bands)
 
 
 def loop_reading(name, got, bands=None):
@@ -295,14 +279,6 @@ ACCURACY = {8: (1.3202e-2, 7.6642e-3), 16: (3.3456e-3, 1.8828e-3), 32: (8.1231e-
 
 
 # ---- the host mirror --------------------------------------------------------------------------------------------------------
-def _hp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-def _h(a):
-    return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-
-
 def advance_host(U_new, U, V, Acc, md, mo, dd, do, loads, phi, dt, beta, gamma, rhs=True, check=True, outs=None,
                  nc=None, R=None):
     """lssvr_wave_advance_host -> (rc, V_out, Acc_out, rhs_out), arrays [nc, ne+1]; what the mode does not write stays
@@ -372,70 +348,63 @@ def modes_of(d, damped):
             ("state", dict(base, U_new=d["U_new"], rhs=False))]
 
 
-# ---- what solve_wave refuses: (name, constructor kwargs, call kwargs) ----------------------------------------------------
+# ---- what solve_wave refuses: (name, constructor kwargs, call kwargs, a fragment of the message) -------------------------
 def refusals():
     z = lambda x: 0.0 * x      # noqa: E731
+    me = "solve_wave "
+    stable = "the Newmark rule is unconditionally stable for gamma >= 1/2 and beta >= (gamma + 1/2)^2 / 4 only"
     return [
-        ("convection", dict(convection=z), {}),
-        ("periodic", dict(boundary="periodic", reaction=lambda x: 1.0 + 0.0 * x), {}),
-        ("fem_solver flux", dict(fem_solver="flux"), {}),
-        ("fem_solver pivot", dict(fem_solver="pivot"), {}),
-        ("element_degrees", dict(_degrees=True), {}),
-        ("solver", dict(solver=1), {}),
-        ("nonlinear", dict(nonlinear=("poly", [z, z])), {}),
-        ("rho <= 0", {}, dict(weight=lambda x: x)),
-        ("shifted reaction < 0", dict(reaction=lambda x: -1e4 + 0.0 * x), {}),
-        ("gamma < 1/2", {}, dict(gamma=0.4)),
-        ("beta < (gamma + 1/2)^2 / 4", {}, dict(beta=0.25, gamma=0.6)),
-        ("beta not finite", {}, dict(beta=math.nan)),
-        ("callable Dirichlet data without end_accel0", {}, dict(end_data=(lambda t: math.sin(t), 0.0))),
-        ("end_accel0 of the wrong shape", {}, dict(end_accel0=(0.0, 0.0, 0.0))),
-        ("end_accel0 not finite", {}, dict(end_accel0=(math.inf, 0.0))),
-        ("damping not callable", {}, dict(damping=1.0)),
-        ("non-finite damping", {}, dict(damping=lambda x: np.full_like(x, np.nan))),
-        ("v0 not callable", {}, dict(_v0=0.0)),
-        ("non-finite v0", {}, dict(_v0=lambda x: np.full_like(x, np.inf))),
-        ("non-finite u0", {}, dict(_u0=lambda x: np.full_like(x, np.inf))),
-        ("R > 8", {}, dict(forcing=[(1.0, z)] * 9)),
-        ("snapshot 0", {}, dict(snapshots=[0])),
-        ("snapshot past the end", {}, dict(snapshots=[2, 5])),
-        ("nsteps 0", {}, dict(nsteps=0)),
-        ("non-finite forcing", {}, dict(forcing=[(1.0, lambda x: np.full_like(x, np.nan))])),
-        ("forcing of the wrong shape", {}, dict(forcing=[(1.0, lambda x: np.ones(3))])),
-        ("non-finite phi", {}, dict(forcing=[(lambda t: math.inf, z)])),
-        ("non-finite end data", {}, dict(end_data=(lambda t: math.nan, 0.0), end_accel0=(0.0, 0.0))),
-        ("non-finite weight at a node", {}, dict(weight=lambda x: np.where(x == 1.0, np.nan, 1.0))),
+        ("convection", dict(convection=z), {}, me + tr.STRUCTURAL[0]),
+        ("periodic", dict(boundary="periodic", reaction=lambda x: 1.0 + 0.0 * x), {}, me + tr.STRUCTURAL[1]),
+        ("fem_solver flux", dict(fem_solver="flux"), {}, me + tr.STRUCTURAL[2]),
+        ("fem_solver pivot", dict(fem_solver="pivot"), {}, me + tr.STRUCTURAL[2]),
+        ("element_degrees", dict(_degrees=True), {}, me + tr.STRUCTURAL[3]),
+        ("solver", dict(solver=1), {}, me + tr.STRUCTURAL[4]),
+        ("nonlinear", dict(nonlinear=("poly", [z, z])), {}, "solve_wave has no semilinear form"),
+        ("rho <= 0", {}, dict(weight=lambda x: x), tr.RHO_MSG),
+        ("shifted reaction < 0", dict(reaction=lambda x: -1e4 + 0.0 * x), {},
+         "c + rho / (beta dt^2) + gamma d / (beta dt) < 0 at a quadrature point (dt = 0.1)"),
+        ("gamma < 1/2", {}, dict(gamma=0.4), "beta = 0.25, gamma = 0.4: " + stable),
+        ("beta < (gamma + 1/2)^2 / 4", {}, dict(beta=0.25, gamma=0.6), "beta = 0.25, gamma = 0.6: " + stable),
+        ("beta not finite", {}, dict(beta=math.nan), "beta and gamma must be finite, got nan, 0.5"),
+        ("callable Dirichlet data without end_accel0", {}, dict(end_data=(lambda t: math.sin(t), 0.0)),
+         "end_accel0 = (g_left''(0), g_right''(0)) is needed when a Dirichlet end has callable end_data"),
+        ("end_accel0 of the wrong shape", {}, dict(end_accel0=(0.0, 0.0, 0.0)),
+         "end_accel0 must be a pair (g_left''(0), g_right''(0))"),
+        ("end_accel0 not finite", {}, dict(end_accel0=(math.inf, 0.0)),
+         "end_accel0 is not finite where it is tabulated"),
+        ("damping not callable", {}, dict(damping=1.0), "damping must be a callable d(x) or None"),
+        ("non-finite damping", {}, dict(damping=lambda x: np.full_like(x, np.nan)),
+         "damping is not finite at a quadrature point"),
+        ("v0 not callable", {}, dict(_v0=0.0), "v0 must be a callable v0(x)"),
+        ("non-finite v0", {}, dict(_v0=lambda x: np.full_like(x, np.inf)), "v0 is not finite where it is tabulated"),
+        ("non-finite u0", {}, dict(_u0=lambda x: np.full_like(x, np.inf)), "u0 is not finite where it is tabulated"),
+        ("R > 8", {}, dict(forcing=[(1.0, z)] * 9), "forcing must hold 1 .. 8 terms (R <= 8), got 9"),
+        ("snapshot 0", {}, dict(snapshots=[0]), "snapshots must be step indices in 1 .. nsteps = 4, got [0]"),
+        ("snapshot past the end", {}, dict(snapshots=[2, 5]),
+         "snapshots must be step indices in 1 .. nsteps = 4, got [2, 5]"),
+        ("nsteps 0", {}, dict(nsteps=0), "nsteps must be an integer >= 1, got 0"),
+        ("non-finite forcing", {}, dict(forcing=[(1.0, lambda x: np.full_like(x, np.nan))]),
+         "forcing[0] f_x is not finite at a quadrature point"),
+        ("forcing of the wrong shape", {}, dict(forcing=[(1.0, lambda x: np.ones(3))]),
+         "forcing[0] f_x must return one value per point ([8, 2] at the quadrature points)"),
+        ("non-finite phi", {}, dict(forcing=[(lambda t: math.inf, z)]),
+         "forcing phi is not finite where it is tabulated"),
+        # (a Dirichlet end starts at g(0), so the value is met in u0's table first)
+        ("non-finite end data", {}, dict(end_data=(lambda t: math.nan, 0.0), end_accel0=(0.0, 0.0)),
+         "u0 is not finite where it is tabulated"),
+        ("non-finite weight at a node", {}, dict(weight=lambda x: np.where(x == 1.0, np.nan, 1.0)),
+         "weight is not finite at a collocation point"),
     ]
 
 
-def check_refusals(monkeypatch):
-    """Every refusal is a ValueError raised on the host: the library loader and the device lookup are replaced by
-    functions that fail the test, so no entry is bound and no kernel can be launched."""
-    import pytest
-    import hybrid_fem_lssvr_amd as pkg
-    from hybrid_fem_lssvr_amd import _capi, solver
+def passing():
+    """(constructor kwargs, call kwargs) that the check lets through: c mildly negative, c + rho / (beta dt^2) >= 0 (the
+    refusal comes from the missing device), and callable data at a ROBIN end, which needs no end_accel0."""
+    return [(dict(reaction=lambda x: -5.0 + 0.0 * x), dict(nsteps=4)),
+            (dict(boundary=(("robin", 1.0, 0.0), ("robin", 1.0, 0.0))),
+             dict(nsteps=4, end_data=(lambda t: math.sin(t), 0.0)))]
 
-    def forbidden(*a, **k):
-        raise AssertionError("a device call was reached before the refusal")
-    monkeypatch.setattr(_capi, "load", forbidden)
-    monkeypatch.setattr(solver, "_device", forbidden)
-    z = lambda x: 0.0 * x      # noqa: E731
-    for name, ctor, call in refusals():
-        ctor, call = dict(ctor), dict(call)
-        degrees = ctor.pop("_degrees", False)
-        u0, v0 = call.pop("_u0", z), call.pop("_v0", z)
-        call.setdefault("nsteps", 4)
-        s = pkg.FEMLSSVRPrimalSolver(9, lssvr_M=9, n_colloc=16, **ctor)
-        if degrees:
-            s.element_degrees = np.full(8, 9)
-        with pytest.raises(ValueError):
-            s.solve_wave(u0, v0, 0.4, **call)
-            raise AssertionError(f"{name}: not refused")
-    # c mildly negative passes the check: c + rho / (beta dt^2) >= 0 (the refusal comes from the missing device)
-    s = pkg.FEMLSSVRPrimalSolver(9, reaction=lambda x: -5.0 + 0.0 * x)
-    with pytest.raises(AssertionError, match="device call"):
-        s.solve_wave(z, z, 0.4, nsteps=4)
-    # callable data at a ROBIN end needs no end_accel0
-    s = pkg.FEMLSSVRPrimalSolver(9, boundary=(("robin", 1.0, 0.0), ("robin", 1.0, 0.0)))
-    with pytest.raises(AssertionError, match="device call"):
-        s.solve_wave(z, z, 0.4, nsteps=4, end_data=(lambda t: math.sin(t), 0.0))
+
+def call_wave(s, u0, v0, **kw):
+    return s.solve_wave(u0, v0, 0.4, **kw)
