@@ -175,6 +175,13 @@ SIGNATURES = {
     "lssvr_ts_rhs_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_hd]),
     "lssvr_ts_source_table": _sig([_c_dp] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dbl] * 4, [_c_dp], _STREAM),
     "lssvr_ts_source_table_host": _sig([_c_hd] * 6, [_c_i64, _c_int, _c_int, _c_int], [_c_dbl] * 4, [_c_hd]),
+    # adaptive time stepping (additive to ABI 7): kdiag, koff, mdiag, moff, U0, U1, loads, phi, ne, R, s, beta0, beta1,
+    # inv_dt, write_bands, adiag, aoff, b; U3, U2, U1, U0, kind_left, kind_right, ne, w3 .. w0, atol, rtol, out4, work
+    "lssvr_ts_step": _sig([_c_dp] * 8, [_c_i64, _c_int], [_c_dbl] * 4, [_c_int], [_c_dp] * 3, _STREAM),
+    "lssvr_ts_step_host": _sig([_c_hd] * 8, [_c_i64, _c_int], [_c_dbl] * 4, [_c_int], [_c_hd] * 3),
+    "lssvr_ts_error_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_ts_error": _sig([_c_dp] * 4, [_c_int, _c_int, _c_i64], [_c_dbl] * 6, [_c_dp], _WS, _STREAM),
+    "lssvr_ts_error_host": _sig([_c_hd] * 4, [_c_int, _c_int, _c_i64], [_c_dbl] * 6, [_c_hd]),
     # semilinear problems (additive to ABI 7): u, t_local, q_tabs, c_tab, f_tab, ne, n, layout, kind, nterm, c_eff,
     # f_eff, f_res; diag, sub, sup, load, u, u_new, kind_left, kind_right, end_values, kappa_host, ne, out4, work;
     # u, u_new, lambda, ne, out

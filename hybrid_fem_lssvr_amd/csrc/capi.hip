@@ -1613,6 +1613,114 @@ int lssvr_ts_source_table_host(const double* U2_host, const double* U0_host, con
   return LSSVR_OK;
 }
 
+// Adaptive time stepping (timestep_adapt.hip).  The device and the host entry of each pair share one validated binding.
+static int ts_misaligned(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (reinterpret_cast<uintptr_t>(p) % alignof(double) != 0) return 1;
+  return 0;
+}
+
+static int bind_ts_step(lssvr::TsStepArgs& a, const double* kdiag, const double* koff, const double* mdiag,
+                        const double* moff, const double* U0, const double* U1, const double* loads,
+                        const double* phi, int64_t ne, int R, double s, double beta0, double beta1, double inv_dt,
+                        int write_bands, double* adiag, double* aoff, const double* b) {
+  const int rc = bind_ts_rhs(a.rhs, mdiag, moff, U0, U1, loads, phi, ne, 1, R, beta0, beta1, inv_dt, b);
+  if (rc != LSSVR_OK) return rc;
+  if (!ts_finite(s)) return fail(LSSVR_ERR_SIZE, "s = %g must be finite", s);
+  if (write_bands != 0 && write_bands != 1) return fail(LSSVR_ERR_SIZE, "write_bands = %d must be 0 or 1", write_bands);
+  if (write_bands && (!kdiag || !koff || !adiag || !aoff))
+    return fail(LSSVR_ERR_NULL, "kdiag, koff, adiag, aoff must be non-NULL with write_bands");
+  if (ts_misaligned({kdiag, koff, mdiag, moff, U0, U1, loads, phi, adiag, aoff, b}))
+    return fail(LSSVR_ERR_SIZE, "every array must be aligned to 8 bytes");
+  if (write_bands) {
+    for (const double* o : {(const double*)adiag, (const double*)aoff, b})
+      if (o == kdiag || o == koff || o == mdiag || o == moff || o == loads || o == phi || o == U0 ||
+          (beta1 != 0.0 && o == U1))
+        return fail(LSSVR_ERR_SIZE, "an output must not be one of the inputs");
+    if (adiag == aoff || adiag == b || aoff == b) return fail(LSSVR_ERR_SIZE, "adiag, aoff, b must be distinct");
+  } else if (b == mdiag || b == moff || b == loads || b == phi) {
+    return fail(LSSVR_ERR_SIZE, "an output must not be one of the inputs");
+  }
+  a.kdiag = kdiag;
+  a.koff = koff;
+  a.s = s;
+  a.write_bands = write_bands;
+  a.adiag = adiag;
+  a.aoff = aoff;
+  return LSSVR_OK;
+}
+
+int lssvr_ts_step(const double* kdiag, const double* koff, const double* mdiag, const double* moff, const double* U0,
+                  const double* U1, const double* loads, const double* phi, int64_t ne, int R, double s, double beta0,
+                  double beta1, double inv_dt, int write_bands, double* adiag, double* aoff, double* b, void* stream) {
+  lssvr::TsStepArgs a{};
+  const int rc = bind_ts_step(a, kdiag, koff, mdiag, moff, U0, U1, loads, phi, ne, R, s, beta0, beta1, inv_dt,
+                              write_bands, adiag, aoff, b);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::ts_step(a, b, reinterpret_cast<hipStream_t>(stream)), "ts_step");
+}
+
+int lssvr_ts_step_host(const double* kdiag_host, const double* koff_host, const double* mdiag_host,
+                       const double* moff_host, const double* U0_host, const double* U1_host, const double* loads_host,
+                       const double* phi_host, int64_t ne, int R, double s, double beta0, double beta1, double inv_dt,
+                       int write_bands, double* adiag_host, double* aoff_host, double* b_host) {
+  lssvr::TsStepArgs a{};
+  const int rc = bind_ts_step(a, kdiag_host, koff_host, mdiag_host, moff_host, U0_host, U1_host, loads_host, phi_host,
+                              ne, R, s, beta0, beta1, inv_dt, write_bands, adiag_host, aoff_host, b_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::ts_step_host(a, b_host);
+  return LSSVR_OK;
+}
+
+int64_t lssvr_ts_error_work_bytes(int64_t ne) { return lssvr::ts_error_work_bytes(ne); }
+
+static int bind_ts_error(lssvr::TsErrArgs& a, const double* U3, const double* U2, const double* U1, const double* U0,
+                         int kind_left, int kind_right, int64_t ne, double w3, double w2, double w1, double w0,
+                         double atol, double rtol, const double* out4) {
+  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
+      (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
+    return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
+                kind_right);
+  if (!ts_finite(w3) || !ts_finite(w2) || !ts_finite(w1) || !ts_finite(w0))
+    return fail(LSSVR_ERR_SIZE, "w3 = %g, w2 = %g, w1 = %g, w0 = %g must be finite", w3, w2, w1, w0);
+  if (!ts_finite(atol) || !ts_finite(rtol) || atol < 0.0 || rtol < 0.0 || !(atol + rtol > 0.0))
+    return fail(LSSVR_ERR_SIZE, "atol = %g, rtol = %g must be finite and >= 0, their sum > 0", atol, rtol);
+  if (!U3 || !U2 || !out4) return fail(LSSVR_ERR_NULL, "U3, U2, out4 must be non-NULL");
+  if (w1 != 0.0 && !U1) return fail(LSSVR_ERR_NULL, "U1 must be non-NULL when w1 != 0");
+  if (w0 != 0.0 && !U0) return fail(LSSVR_ERR_NULL, "U0 must be non-NULL when w0 != 0");
+  if (ts_misaligned({U3, U2, U1, U0, out4})) return fail(LSSVR_ERR_SIZE, "every array must be aligned to 8 bytes");
+  a = lssvr::TsErrArgs{U3, U2, U1, U0, ne, {kind_left, kind_right}, w3, w2, w1, w0, atol, rtol};
+  return LSSVR_OK;
+}
+
+int lssvr_ts_error(const double* U3, const double* U2, const double* U1, const double* U0, int kind_left,
+                   int kind_right, int64_t ne, double w3, double w2, double w1, double w0, double atol, double rtol,
+                   double* out4, void* work, int64_t work_bytes, void* stream) {
+  lssvr::TsErrArgs a{};
+  const int rc = bind_ts_error(a, U3, U2, U1, U0, kind_left, kind_right, ne, w3, w2, w1, w0, atol, rtol, out4);
+  if (rc != LSSVR_OK) return rc;
+  if (!work) return fail(LSSVR_ERR_NULL, "work must be non-NULL");
+  if (ts_misaligned({work})) return fail(LSSVR_ERR_SIZE, "work must be aligned to 8 bytes");
+  const int64_t need = lssvr::ts_error_work_bytes(ne);
+  if (work_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "work_bytes = %lld < lssvr_ts_error_work_bytes(%lld) = %lld", (long long)work_bytes,
+                (long long)ne, (long long)need);
+  return check_launch(lssvr::ts_error(a, out4, work, reinterpret_cast<hipStream_t>(stream)), "ts_error");
+}
+
+int lssvr_ts_error_host(const double* U3_host, const double* U2_host, const double* U1_host, const double* U0_host,
+                        int kind_left, int kind_right, int64_t ne, double w3, double w2, double w1, double w0,
+                        double atol, double rtol, double* out4_host) {
+  lssvr::TsErrArgs a{};
+  const int rc = bind_ts_error(a, U3_host, U2_host, U1_host, U0_host, kind_left, kind_right, ne, w3, w2, w1, w0, atol,
+                               rtol, out4_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::ts_error_host(a, out4_host);
+  return LSSVR_OK;
+}
+
 // Semilinear problems (nonlinear.hip).  The device and the host entry of each pair share one validated binding.
 static int bind_nl_linearize(lssvr::NlLinArgs& a, const double* u, const double* t_local, const double* q_tabs,
                              const double* c_tab, const double* f_tab, int64_t ne, int n, int table_layout, int kind,

@@ -425,6 +425,35 @@ struct TsSourceArgs {
 hipError_t ts_source_table(const TsSourceArgs& a, bool point_major, double* out, hipStream_t s);
 void ts_source_table_host(const TsSourceArgs& a, bool point_major, double* out);
 
+// timestep_adapt.hip: what an attempt of variable-step BDF2 with error control adds to the above (DESIGN.md section
+// 30).  One case; the host forms run the same inline routines on host arrays, bit for bit.
+struct TsStepArgs {
+  TsRhsArgs rhs;                    // nc = 1; inv_dt = 1 / h of the attempt
+  const double* kdiag;              // the bands of -(a u')' + c u: [ne+1], [ne]
+  const double* koff;
+  double s;                         // alpha / h
+  int write_bands;                  // 0: s is the previous attempt's, adiag and aoff are left as they are
+  double* adiag;                    // K + s M: [ne+1], [ne]
+  double* aoff;
+};
+// adiag = kdiag + s mdiag, aoff = koff + s moff (with write_bands), b = the row of ts_rhs
+hipError_t ts_step(const TsStepArgs& a, double* b, hipStream_t s);
+void ts_step_host(const TsStepArgs& a, double* b);
+struct TsErrArgs {
+  const double* U3;                 // the trial u^{n+1}, then u^n, u^{n-1}, u^{n-2} [ne+1]; U1 / U0 not read when
+  const double* U2;                 // w1 / w0 == 0
+  const double* U1;
+  const double* U0;
+  int64_t ne;
+  int kind[2];                      // per end of the domain: 0 Dirichlet (row skipped), 1 Robin
+  double w3, w2, w1, w0;            // the weights of the divided difference, its scalar factor folded in
+  double atol, rtol;
+};
+int64_t ts_error_work_bytes(int64_t ne);
+// out4 = {max |e| / sc, max |e|, max |U3|, count of rows whose e or sc is not finite}
+hipError_t ts_error(const TsErrArgs& a, double* out4, void* work, hipStream_t s);
+void ts_error_host(const TsErrArgs& a, double* out4);
+
 // nonlinear.hip: the Newton iteration of -(a u')' + b u' + c u + g(x, u) = f.  The host forms
 // (nl_*_host) run the same inline routines on host arrays, bit for bit except for exp (libm there).
 struct NlLinArgs {

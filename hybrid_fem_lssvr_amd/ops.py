@@ -1826,6 +1826,103 @@ def ts_source_table(U2, U0, U1, ftab, rho_tab, phi, alpha, beta0, beta1, inv_dt,
     return out
 
 
+# ---- adaptive time stepping: variable-step BDF2 with a local error estimate -------------------
+def ts_step(kdiag, koff, mdiag, moff, U0, U1, loads, phi, s, beta0, beta1, inv_dt, *, adiag, aoff, write_bands=True,
+            out=None, stream=None):
+    """``lssvr_ts_step``: the matrix AND the right-hand side of one attempt of variable-step BDF2, in one pass:
+    adiag = kdiag + s mdiag, aoff = koff + s moff (s = alpha / h; skipped with ``write_bands=False``, when s is the
+    previous attempt's) and out = what :func:`ts_rhs` writes for the one case U0, U1 float64[1, ne+1], loads
+    float64[R, ne+1], phi float64[1, R], bit for bit.  K = (kdiag[ne+1], koff[ne]) are the bands of -(a u')' + c u,
+    M = (mdiag, moff) the mass bands; ``adiag`` [ne+1] and ``aoff`` [ne] are the caller's buffers.  All on the
+    device; ``beta1 == 0`` reads no U1 (``None`` allowed).  No synchronisation and no copy.  Returns out
+    float64[1, ne+1]; no output may be an input."""
+    lib = _capi.load()
+    for nm, t in (("kdiag", kdiag), ("koff", koff), ("mdiag", mdiag), ("moff", moff), ("U0", U0), ("loads", loads),
+                  ("phi", phi), ("adiag", adiag), ("aoff", aoff)):
+        _dev(t, nm)
+    s, beta0, beta1, inv_dt = _ts_scalars(s=s, beta0=beta0, beta1=beta1, inv_dt=inv_dt)
+    ne = moff.numel()
+    if ne < 1:
+        raise ValueError("need at least one element")
+    if any(t.dim() != 1 for t in (kdiag, koff, mdiag, moff, adiag, aoff)) or koff.numel() != ne \
+            or aoff.numel() != ne or any(t.numel() != ne + 1 for t in (kdiag, mdiag, adiag)):
+        raise ValueError("band lengths must be ne+1 (kdiag, mdiag, adiag) and ne (koff, moff, aoff)")
+    if U0.dim() != 2 or tuple(U0.shape) != (1, ne + 1):
+        raise ValueError(f"U0 must be [1, ne+1] = [1, {ne + 1}], got {list(U0.shape)}")
+    if loads.dim() != 2 or loads.shape[1] != ne + 1 or not 1 <= loads.shape[0] <= TS_MAX_TERMS:
+        raise ValueError(f"loads must be [R, ne+1] = [1 .. {TS_MAX_TERMS}, {ne + 1}], got {list(loads.shape)}")
+    R = int(loads.shape[0])
+    if tuple(phi.shape) != (1, R):
+        raise ValueError(f"phi must be [nc, R] = [1, {R}], got {list(phi.shape)}")
+    if beta1 != 0.0 and U1 is None:
+        raise ValueError("U1 is needed when beta1 != 0")
+    if U1 is not None:
+        _dev(U1, "U1")
+        if U1.shape != U0.shape:
+            raise ValueError(f"U1 must have the shape of U0 {list(U0.shape)}, got {list(U1.shape)}")
+    out = _eig_out(out, "out", (1, ne + 1), mdiag)
+    if any(t is not None and out.data_ptr() == t.data_ptr() for t in (U0, U1)):
+        raise ValueError("out must not be U0 or U1")
+    ins = dict(kdiag=kdiag, koff=koff, moff=moff, U0=U0, loads=loads, phi=phi, **({} if U1 is None else {"U1": U1}))
+    outs = (adiag, aoff, out)
+    if any(o.data_ptr() == t.data_ptr() for o in outs for t in (mdiag, *ins.values())) \
+            or len({o.data_ptr() for o in outs}) != 3:
+        raise ValueError("adiag, aoff and out must be three buffers of their own, none of them an input")
+    _same_device(mdiag, adiag=adiag, aoff=aoff, **ins)
+    rc = lib.lssvr_ts_step(_ptr(kdiag), _ptr(koff), _ptr(mdiag), _ptr(moff), _ptr(U0), _ptr(U1), _ptr(loads),
+                           _ptr(phi), ne, R, s, beta0, beta1, inv_dt, int(bool(write_bands)), _ptr(adiag), _ptr(aoff),
+                           _ptr(out), _stream(stream))
+    _capi.check(rc, "lssvr_ts_step")
+    return out
+
+
+def ts_error(U3, U2, U1, U0, weights, atol, rtol, end_kinds=(END_DIRICHLET, END_DIRICHLET), *, out4=None, work=None,
+             stream=None):
+    """``lssvr_ts_error``: out4 float64[4] on the device = (max |e| / sc, max |e|, max |U3|, the count of rows whose e
+    or sc is not finite) with e = ((w3 U3 + w2 U2) + w1 U1) + w0 U0, ``weights`` = (w3, w2, w1, w0) those of a divided
+    difference with the estimate's factor folded in, and sc = atol + rtol max(|U3|, |U2|); a Dirichlet end row of
+    ``end_kinds`` is skipped.  U3 (the trial), U2, U1, U0 float64[ne+1] on the device; a zero w1 / w0 reads no U1 / U0
+    (``None`` allowed).  Bitwise reproducible; no synchronisation -- reading out4 is the caller's."""
+    lib = _capi.load()
+    _dev(U3, "U3")
+    _dev(U2, "U2")
+    if len(weights) != 4:
+        raise ValueError(f"weights must be (w3, w2, w1, w0), got {len(weights)} values")
+    w3, w2, w1, w0 = _ts_scalars(w3=weights[0], w2=weights[1], w1=weights[2], w0=weights[3])
+    atol, rtol = _ts_scalars(atol=atol, rtol=rtol)
+    if atol < 0.0 or rtol < 0.0 or not atol + rtol > 0.0:
+        raise ValueError(f"atol and rtol must be >= 0 and their sum > 0, got atol = {atol!r}, rtol = {rtol!r}")
+    ne = U3.numel() - 1
+    if U3.dim() != 1 or ne < 1:
+        raise ValueError("U3 must be 1-D with at least two nodes")
+    named = {"U2": U2}
+    for nm, t, w in (("U1", U1, w1), ("U0", U0, w0)):
+        if t is None:
+            if w != 0.0:
+                raise ValueError(f"{nm} is needed when w{nm[1]} != 0")
+        else:
+            named[nm] = t
+    for nm, t in named.items():
+        _dev(t, nm)
+        if t.shape != U3.shape:
+            raise ValueError(f"{nm} must have the shape of U3 {list(U3.shape)}, got {list(t.shape)}")
+    kinds, _ = _end_kinds(end_kinds, (0.0, 0.0), any_sign=True)
+    out4 = _eig_out(out4, "out4", (4,), U3)
+    need = lib.lssvr_ts_error_work_bytes(ne)
+    if work is not None:
+        _dev(work, "work")
+        if work.numel() * work.element_size() < need:
+            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
+                             f"lssvr_ts_error_work_bytes({ne}) = {need}")
+    work = _scratch(work, need, U3.device)
+    _same_device(U3, work=work, **named)
+    rc = lib.lssvr_ts_error(_ptr(U3), _ptr(U2), _ptr(named.get("U1")), _ptr(named.get("U0")), kinds[0], kinds[1], ne,
+                            w3, w2, w1, w0, atol, rtol, _ptr(out4), _ptr(work), work.numel() * work.element_size(),
+                            _stream(stream))
+    _capi.check(rc, "lssvr_ts_error")
+    return out4
+
+
 # ---- semilinear problems -(a u')' + b u' + c u + g(x, u) = f (DESIGN.md section 27) ----------------------------------
 NL_POLY, NL_EXP = _capi.NL_POLY, _capi.NL_EXP      # LSSVR_NL_*: g = sum_k q_k u^k (1 .. 6 terms); g = q_0 exp(q_1 u)
 NL_MAX_TERMS = 6

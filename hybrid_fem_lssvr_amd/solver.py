@@ -132,6 +132,65 @@ def _read_back(**tensors):
             for k, v in tensors.items()}
 
 
+# ---- the scalar rules of solve_transient_adaptive: float64, pure --------------------------------
+TS_SAFETY, TS_FAC_MIN, TS_FAC_MAX = 0.9, 0.2, 2.0
+TS_OMEGA_MAX = 2.0              # below the zero-stability limit 1 + sqrt(2) of variable-step BDF2
+TS_OUT_SLACK = 1e-9             # a step that ends within this fraction of itself before an output time is stretched to it
+TS_MAX_RESTARTS = 8
+TS_MONITOR_ROWS = 1024          # rows of one block of the per-attempt monitor on the device
+
+
+def ts_coefficients(omega):
+    """(alpha, beta0, beta1) of variable-step BDF2 at omega = h / h_p; omega = 1 gives (3/2, 2, -1/2) exactly."""
+    return (1.0 + 2.0 * omega) / (1.0 + omega), 1.0 + omega, -(omega * omega) / (1.0 + omega)
+
+
+def ts_error_weights(h, hp, hpp=None, alpha=None):
+    """(w3, w2, w1, w0) of the local error estimate e = w3 u^{n+1} + w2 u^n + w1 u^{n-1} + w0 u^{n-2} for the steps
+    h, hp, hpp between those times (newest first).  With ``hpp``: h^2 (h + hp) / alpha times the third divided
+    difference, the local error of variable-step BDF2 for a cubic.  Without: h^2 times the second divided difference
+    (w0 = 0), the backward-Euler error of step 1 as step 2 reads it.  The differences of the times are sums of steps:
+    nothing cancels."""
+    if hpp is None:
+        f = h * h
+        return f / (h * (h + hp)), -f / (h * hp), f / ((h + hp) * hp), 0.0
+    f = h * h * (h + hp) / alpha
+    return (f / (h * (h + hp) * (h + hp + hpp)), -f / (h * hp * (hp + hpp)), f / ((h + hp) * hp * hpp),
+            -f / ((h + hp + hpp) * (hp + hpp) * hpp))
+
+
+def ts_controller(err, bad, p, after_reject):
+    """(accepted, fac): accepted iff err <= 1 and no row was non-finite (``bad`` == 0); fac =
+    clip(0.9 err^(-1/p), 0.2, grow) with grow = 2, or 1 for the attempt after a rejection; a non-finite attempt is a
+    rejection with fac = 0.2.  ``p``: 3 for the BDF2 estimate, 2 for the step-2 estimate."""
+    grow = 1.0 if after_reject else TS_FAC_MAX
+    if bad != 0 or not math.isfinite(err):
+        return False, TS_FAC_MIN
+    raw = math.inf if err == 0.0 else TS_SAFETY * err ** (-1.0 / p)
+    return err <= 1.0, min(max(raw, TS_FAC_MIN), grow)
+
+
+def ts_trial_step(t, dt, dt_max, h_prev, t_target):
+    """(h, t_new, short): the step of an attempt that starts at ``t`` with the controller's ``dt`` -- capped by dt_max
+    and by omega <= 2 against the last accepted step ``h_prev`` (None at step 1), then, if
+    t + h (1 + 1e-9) >= t_target, set to t_target - t so that the output time is hit exactly (t_new IS t_target).
+    ``short``: the step is below dt."""
+    h = min(dt, dt_max)
+    if h_prev is not None:
+        h = min(h, TS_OMEGA_MAX * h_prev)
+    if t + h * (1.0 + TS_OUT_SLACK) >= t_target:
+        return t_target - t, t_target, (t_target - t) < dt
+    return h, t + h, h < dt
+
+
+def ts_next_dt(dt, h, short, accepted, fac):
+    """The controller's dt after an attempt of step h: fac h, except that an accepted step that was shortened (to hit
+    an output, or by a cap) does not shrink dt when its estimate asks for growth."""
+    if accepted and short and fac >= 1.0:
+        return max(dt, fac * h)
+    return fac * h
+
+
 def _tabulate(fn, pts, point_major=False):
     """Device table of the callable ``fn`` at the device points ``pts`` [ne, k].  The callable ALWAYS sees the
     element-major host array ``x[e, k]`` -- points along the last axis, as in the reference, where it receives the
@@ -399,10 +458,21 @@ class TransientSolution:
       the LINEAR part K + (alpha / dt) M, to which every Newton iteration adds the mass matrix of g_u;
     * ``newton`` (``None`` without ``nonlinear=``) float64[nsteps, newton_iters, 4]: row [n - 1, k] holds what
       ``ops.nl_residual`` read in iteration k of step n -- |residual at v_k|_inf, |v_{k+1} - v_k|_inf, |v_{k+1}|_inf
-      and the count of non-finite entries."""
+      and the count of non-finite entries.
 
-    def __init__(self, times, nodal, enhanced, bands, newton=None):
+    :meth:`FEMLSSVRPrimalSolver.solve_transient_adaptive` returns the same, one snapshot per output time, with
+    ``bands`` = dict(mass, stiff=(kdiag, koff) of -(a u')' + c u, loads), and adds
+
+    * ``steps`` float64[attempts, 4]: every attempt's (t it starts from, its step, the scaled estimate err -- nan at a
+      first step, which has none --, 1.0 accepted / 0.0 rejected), in the order they were made, restarts included;
+    * ``n_accepted``, ``n_rejected``, ``n_restarts``;
+    * ``monitor`` float64[attempts with an estimate, 4]: what ``ops.ts_error`` wrote, as read back after the loop."""
+
+    def __init__(self, times, nodal, enhanced, bands, newton=None, steps=None, n_restarts=0, monitor=None):
         self.times, self.nodal, self.enhanced, self.bands, self.newton = times, nodal, enhanced, bands, newton
+        self.steps, self.n_restarts, self.monitor = steps, n_restarts, monitor
+        self.n_accepted = None if steps is None else int(np.count_nonzero(steps[:, 3]))
+        self.n_rejected = None if steps is None else int(len(steps)) - self.n_accepted
 
     def evaluate(self, k, x, deriv=0):
         """The enhanced snapshot ``k`` (its ``deriv``-th x-derivative) at the points ``x``."""
@@ -1462,7 +1532,10 @@ class FEMLSSVRPrimalSolver:
         once per kind of point, and ``quad`` / ``colloc`` are its host tables, the ones the device is handed: a, c, rho
         [ne, nquad] and f [R, ne, nquad] at the Gauss points of the assembly; with ``enhance`` a, da, c, rho
         [ne, n_colloc] and f [R, ne, n_colloc] at np.linspace(x_e, x_e+1, n_colloc), the abscissae lssvr_colloc_points
-        writes (else None).  ``damping``: one more coefficient d(x), tabulated as "d" in both.  The parameters of the
+        writes (else None).  ``damping``: one more coefficient d(x), tabulated as "d" in both.  ``nsteps=None`` (with
+        ``phi0``) is the caller whose steps are not known beforehand, :meth:`solve_transient_adaptive`: t = 0 is the one
+        time tabulated, dt is None, steps is empty and ``snapshots`` is not looked at; phi_fns / g_fns are the callables
+        of t that it evaluates as it goes.  The parameters of the
         rule and the definiteness of its step matrix are the caller's: :meth:`_check_transient`,
         :meth:`_check_wave`."""
         if self.convection is not None:
@@ -1486,9 +1559,9 @@ class FEMLSSVRPrimalSolver:
             raise ValueError("weight must be a callable rho(x) or None")
         if damping is not None and not callable(damping):
             raise ValueError("damping must be a callable d(x) or None")
-        if isinstance(nsteps, bool) or int(nsteps) != nsteps or int(nsteps) < 1:
+        if nsteps is not None and (isinstance(nsteps, bool) or int(nsteps) != nsteps or int(nsteps) < 1):
             raise ValueError(f"nsteps must be an integer >= 1, got {nsteps!r}")
-        nsteps, t_end = int(nsteps), float(t_end)
+        nsteps, t_end = None if nsteps is None else int(nsteps), float(t_end)
         if not (math.isfinite(t_end) and t_end > 0.0):
             raise ValueError(f"t_end must be finite and > 0, got {t_end!r}")
         forcing = [(1.0, self.rhs)] if forcing is None else list(forcing)
@@ -1498,10 +1571,14 @@ class FEMLSSVRPrimalSolver:
         if not 1 <= len(forcing) <= ops.TS_MAX_TERMS:
             raise ValueError(f"forcing must hold 1 .. {ops.TS_MAX_TERMS} terms (R <= {ops.TS_MAX_TERMS}), got "
                              f"{len(forcing)}")
-        snapshots = [nsteps] if snapshots is None else list(snapshots)
-        if not snapshots or any(isinstance(s, bool) or int(s) != s or not 1 <= int(s) <= nsteps for s in snapshots):
-            raise ValueError(f"snapshots must be step indices in 1 .. nsteps = {nsteps}, got {snapshots!r}")
-        steps = sorted({int(s) for s in snapshots})
+        if nsteps is None:
+            steps = []
+        else:
+            snapshots = [nsteps] if snapshots is None else list(snapshots)
+            if not snapshots or any(isinstance(s, bool) or int(s) != s or not 1 <= int(s) <= nsteps
+                                    for s in snapshots):
+                raise ValueError(f"snapshots must be step indices in 1 .. nsteps = {nsteps}, got {snapshots!r}")
+            steps = sorted({int(s) for s in snapshots})
         bnd = self._bnd
         kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (tuple(bnd.kinds), tuple(bnd.kappa))
         if end_data is None:
@@ -1512,8 +1589,11 @@ class FEMLSSVRPrimalSolver:
         pfn = [p if callable(p) else (lambda t, p=float(p): p) for p, _ in forcing]
         m = self._default_mesh() if self.mesh is None else self.mesh
         nodes = np.asarray(m.nodes, dtype=np.float64)
-        dt = t_end / nsteps
-        times = dt * np.arange(nsteps + 1)
+        if nsteps is None:
+            dt, times = None, np.zeros(1)
+        else:
+            dt = t_end / nsteps
+            times = dt * np.arange(nsteps + 1)
         phi = np.array([[float(p(t)) for p in pfn] for t in (times if phi0 else times[1:])], dtype=np.float64)
         g = np.array([[float(v(t)) for v in gfn] for t in times], dtype=np.float64)
         # the data at the Gauss points of the assembly, a + h xi on [0, 1] as lssvr_quad_points has them, and at the
@@ -1559,7 +1639,8 @@ class FEMLSSVRPrimalSolver:
             raise ValueError("weight must be positive at every quadrature point (rho > 0): M would not be positive "
                              "definite")
         return types.SimpleNamespace(nodes=nodes, kinds=kinds, kappa=kappa, dt=dt, times=times, steps=steps,
-                                     u_init=u_init, end_data=end_data, phi=phi, g=g, quad=quad, colloc=colloc)
+                                     u_init=u_init, end_data=end_data, phi=phi, g=g, quad=quad, colloc=colloc,
+                                     phi_fns=pfn, g_fns=gfn)
 
     @staticmethod
     def _check_finite(*named):
@@ -1781,6 +1862,160 @@ class FEMLSSVRPrimalSolver:
                 raise RuntimeError(f"solve_transient: step {i + 1} did not converge in {iters} Newton iteration(s) to "
                                    f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
         return TransientSolution(p.times[steps].copy(), host["nodal"], enhanced, bands, newton)
+
+    # ---- adaptive time stepping (no reference counterpart) ----------------------------------
+    def _check_adaptive(self, u0, t_end, rtol, atol, dt0, t_out, dt_min, dt_max, max_steps, weight, forcing, end_data,
+                        enhance):
+        """:meth:`_check_time` for :meth:`solve_transient_adaptive`, and what belongs to the controller: the
+        tolerances, dt0, dt_min, dt_max, the output times, max_steps, and c + rho / dt_max >= 0 at the quadrature
+        points (alpha >= 1 for every omega, so this covers every step).  Returns the plan with rtol, atol, dt0, dt_min,
+        dt_max, t_out (a float64 array), max_steps added."""
+        if self.nonlinear is not None:
+            raise ValueError("solve_transient_adaptive has no nonlinear term: the Newton iteration inside a step has "
+                             "no error control yet; use solve_transient(..., nonlinear=...)")
+        p = self._check_time("solve_transient_adaptive", u0, t_end, None, weight, forcing, end_data, None, enhance,
+                             phi0=True)
+        t_end = float(t_end)
+        try:
+            rtol, atol, dt0 = float(rtol), float(atol), float(dt0)
+        except (TypeError, ValueError):
+            raise ValueError("rtol, atol and dt0 must be numbers") from None
+        if not (math.isfinite(rtol) and math.isfinite(atol)) or rtol < 0.0 or atol < 0.0 or not rtol + atol > 0.0:
+            raise ValueError(f"rtol and atol must be finite and >= 0 and rtol + atol > 0, got rtol = {rtol!r}, "
+                             f"atol = {atol!r}")
+        if not 0.0 < dt0 <= t_end:
+            raise ValueError(f"dt0 must lie in (0, t_end = {t_end!r}], got {dt0!r}")
+        dt_min = 16.0 * 2.0 ** -52 * t_end if dt_min is None else float(dt_min)
+        dt_max = t_end if dt_max is None else float(dt_max)
+        if not (math.isfinite(dt_min) and 0.0 <= dt_min <= dt0):
+            raise ValueError(f"dt_min must lie in [0, dt0 = {dt0!r}], got {dt_min!r}")
+        if not (math.isfinite(dt_max) and dt_max >= dt0):
+            raise ValueError(f"dt_max must be finite and >= dt0 = {dt0!r}, got {dt_max!r}")
+        if isinstance(max_steps, bool) or int(max_steps) != max_steps or int(max_steps) < 1:
+            raise ValueError(f"max_steps must be an integer >= 1, got {max_steps!r}")
+        t_out = np.array([t_end] if t_out is None else t_out, dtype=np.float64).reshape(-1)
+        if t_out.size < 1 or not np.all(np.isfinite(t_out)) or not np.all(np.diff(t_out) > 0.0) \
+                or not (t_out[0] > 0.0 and t_out[-1] <= t_end):
+            raise ValueError(f"t_out must be ascending times in (0, t_end = {t_end!r}], got {t_out.tolist()!r}")
+        if not np.all(p.quad["c"] + p.quad["rho"] / dt_max >= 0.0):
+            raise ValueError(f"c + rho / dt_max < 0 at a quadrature point (dt_max = {dt_max:.6g}): a step's matrix "
+                             "would not be positive definite, and the solve does not pivot; give a smaller dt_max")
+        p.rtol, p.atol, p.dt0, p.dt_min, p.dt_max, p.t_out, p.max_steps = rtol, atol, dt0, dt_min, dt_max, t_out, \
+            int(max_steps)
+        return p
+
+    def solve_transient_adaptive(self, u0, t_end, *, rtol, atol, dt0, t_out=None, dt_min=None, dt_max=None,
+                                 max_steps=100000, weight=None, forcing=None, end_data=None, enhance=True):
+        """The problem of :meth:`solve_transient` with steps chosen by a local error estimate: variable-step BDF2
+        (step 1: backward Euler with ``dt0``) and per-step control of
+        err = max_i |e_i| / (``atol`` + ``rtol`` max(|u^{n+1}_i|, |u^n_i|)) over all nodes but Dirichlet end nodes, e a
+        divided difference of the last nodal vectors.  An attempt is accepted iff err <= 1; the
+        next step is the attempt's times clip(0.9 err^(-1/3), 0.2, 2) (no growth right after a rejection).  ``t_out``:
+        ascending output times in (0, t_end] (``None``: ``[t_end]``), each hit exactly: ``times`` of the result equals
+        it bit for bit.  ``dt_max`` (``None``: t_end) caps the step; c + rho / dt_max >= 0 is required, so a negative
+        reaction needs one.  ``RuntimeError`` when the controller's dt falls below ``dt_min`` (``None``:
+        16 eps t_end), after ``max_steps`` attempts, or when step 2 -- whose estimate judges step 1 -- is rejected more
+        than 8 times (each restarts from u0 with a smaller dt0).
+
+        Per attempt: phi(t) and g(t) of the trial time go up as one row of R + 2 doubles, ``ops.ts_step`` writes
+        K + (alpha / h) M and the right-hand side from the bands K and M assembled ONCE before the loop,
+        ``ops.tridiag_bc_solve_multi`` solves, ``ops.ts_error`` reduces the estimate and its four doubles come back --
+        the one synchronisation of an attempt.  Four nodal buffers rotate on acceptance only (a fifth keeps the start).  At an output step
+        ``ops.ts_source_table`` runs with that step's alpha, beta0, beta1 and 1 / h, and with ``enhance`` all snapshots
+        go through ONE ``ops.enhance_multi`` after the loop.  Snapshots, bands and the monitor come back in one copy.
+        Returns a :class:`TransientSolution` with ``steps``, ``n_accepted``, ``n_rejected``, ``n_restarts``,
+        ``monitor``; the solver's attributes are left as they are."""
+        enhance = bool(enhance)
+        p = self._check_adaptive(u0, t_end, rtol, atol, dt0, t_out, dt_min, dt_max, max_steps, weight, forcing,
+                                 end_data, enhance)
+        kinds, kappa, q, t_out = p.kinds, p.kappa, p.quad, p.t_out
+        ns, R = t_out.size, p.phi.shape[1]
+        p.steps = list(range(ns))                                  # the snapshots index the table of g below
+        p.g = np.zeros((ns, 2))
+        # ---- the device from here on
+        torch = _torch()
+        ne = p.nodes.size - 1
+        D = self._time_setup(p, enhance, [("mass", False, q["rho"]), ("stiff", True, q["c"])], nbuf=5)
+        dev, U, S, b, loads, work, pm, G = D.dev, D.U, D.S, D.b, D.loads, D.work, D.pm, D.g
+        (md, mo), (kd, ko) = D.bands["mass"], D.bands["stiff"]
+        U[4].copy_(U[0])                                                   # the start, kept for a restart
+        adiag, aoff = torch.empty_like(kd), torch.empty_like(ko)
+        row = torch.empty(R + 2, dtype=torch.float64, device=dev)          # phi_r(t), then g(t), of the trial time
+        phi, g = row[:R].unsqueeze(0), row[R:].unsqueeze(0)
+        ework = ops._scratch(None, ops._capi.load().lssvr_ts_error_work_bytes(ne), dev)
+        mon = []                                                           # blocks [TS_MONITOR_ROWS, 4] of out4 rows
+        if enhance:
+            ftab, rtab, src = D.tab["f"], D.tab["rho"], D.src
+        steps, hs = [], []                       # every attempt; the accepted steps, newest first
+        new, cur, prev, old = 1, 0, 2, 3
+        t, dt, k, restarts, after_reject, dt_start, s_last, n_est, err = 0.0, p.dt0, 0, 0, False, p.dt0, None, 0, \
+            math.nan
+        # the loop: launches on the current stream; per attempt one small upload and one read-back of four doubles
+        while k < ns:
+            if len(steps) >= p.max_steps:
+                raise RuntimeError(f"solve_transient_adaptive: more than max_steps = {p.max_steps} attempts at "
+                                   f"t = {t:.6g}, dt = {dt:.6g}, last err = {err:.6g}")
+            if dt < p.dt_min:
+                raise RuntimeError(f"solve_transient_adaptive: dt = {dt:.6g} < dt_min = {p.dt_min:.6g} at "
+                                   f"t = {t:.6g}, last err = {err:.6g}")
+            n = len(hs) + 1
+            h, t_new, short = ts_trial_step(t, dt, p.dt_max, hs[0] if hs else None, float(t_out[k]))
+            al, b0, b1 = ops.BDF["bdf1"] if n == 1 else ts_coefficients(h / hs[0])
+            inv_h, s = 1.0 / h, al / h
+            host_row = np.array([float(f(t_new)) for f in (*p.phi_fns, *p.g_fns)], dtype=np.float64)
+            if not np.all(np.isfinite(host_row)):
+                raise ValueError(f"forcing phi or end_data is not finite at t = {t_new!r}")
+            row.copy_(torch.from_numpy(host_row))
+            ops.ts_step(kd, ko, md, mo, U[cur:cur + 1], None if b1 == 0.0 else U[prev:prev + 1], loads, phi, s, b0, b1,
+                        inv_h, adiag=adiag, aoff=aoff, write_bands=s != s_last, out=b)
+            s_last = s
+            ops.tridiag_bc_solve_multi(adiag, aoff, b, kinds, kappa, g, out=U[new:new + 1], work=work)
+            if n == 1:                                       # no estimate: nothing to read, nothing to wait for
+                err, accepted, fac = math.nan, True, 1.0
+            else:
+                w = ts_error_weights(h, hs[0]) if n == 2 else ts_error_weights(h, hs[0], hs[1], al)
+                if n_est % TS_MONITOR_ROWS == 0:
+                    mon.append(torch.zeros((TS_MONITOR_ROWS, 4), dtype=torch.float64, device=dev))
+                out4 = mon[-1][n_est % TS_MONITOR_ROWS]
+                n_est += 1
+                ops.ts_error(U[new], U[cur], U[prev], U[old] if n > 2 else None, w, p.atol, p.rtol, kinds, out4=out4,
+                             work=ework)
+                r4 = out4.cpu().numpy()
+                err = float(r4[0])
+                accepted, fac = ts_controller(err, float(r4[3]), 2 if n == 2 else 3, after_reject)
+            steps.append((t, h, err, float(accepted)))
+            if not accepted and n == 2:
+                # the estimate of step 2 judges step 1, which cannot be retried alone: start again with a smaller dt0
+                restarts += 1
+                if restarts > TS_MAX_RESTARTS:
+                    raise RuntimeError(f"solve_transient_adaptive: step 2 rejected after {TS_MAX_RESTARTS} restarts "
+                                       f"(dt = {h:.6g}, err = {err:.6g}); give a smaller dt0")
+                dt_start = fac * dt_start
+                U[0].copy_(U[4])
+                new, cur, prev, old = 1, 0, 2, 3
+                hs, t, dt, k, after_reject = [], 0.0, dt_start, 0, True
+                continue
+            if n > 1:
+                dt = ts_next_dt(dt, h, short, accepted, fac)
+                after_reject = not accepted
+            if not accepted:
+                continue
+            if t_new == t_out[k]:
+                S[k].copy_(U[new])
+                G[k].copy_(row[R:])
+                if enhance:
+                    ops.ts_source_table(U[new], U[cur], None if b1 == 0.0 else U[prev], ftab, rtab, row[:R], al, b0,
+                                        b1, inv_h, point_major=pm, out=src[k])
+                k += 1
+            new, cur, prev, old = old, new, cur, prev
+            hs, t = [h] + hs[:1], t_new
+        enhanced = self._enhance_snapshots(p, D, S) if enhance else []
+        host = _read_back(nodal=S, mass=D.bands["mass"], stiff=D.bands["stiff"], loads=loads,   # one copy
+                          monitor=torch.cat(mon)[:n_est] if mon else None)
+        bands = dict(mass=host["mass"], stiff=host["stiff"], loads=host["loads"])
+        return TransientSolution(t_out.copy(), host["nodal"], enhanced, bands,
+                                 steps=np.array(steps, dtype=np.float64).reshape(-1, 4), n_restarts=restarts,
+                                 monitor=host["monitor"])
 
     # ---- wave problems (no reference counterpart; DESIGN.md section 29) -----------------------------
     def _check_wave(self, u0, v0, t_end, nsteps, damping, weight, forcing, end_data, end_accel0, snapshots, enhance,

@@ -1058,6 +1058,55 @@ int lssvr_ts_source_table_host(const double* U2_host, const double* U0_host, con
                                double inv_dt, double* out_host);
 
 /*
+ * Adaptive time stepping for the transient problem above: variable-step BDF2 with a local error estimate (no reference
+ * counterpart).  ADDITIVE to ABI 7: five new symbols, no existing entry, struct, constant or
+ * kernel changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * With h the trial step, h_p the last accepted one and omega = h / h_p, an attempt solves
+ *   (K + s M) u^{n+1} = (1/h) M (beta0 u^n + beta1 u^{n-1}) + load(t_{n+1}),     s = alpha / h,
+ *   alpha = (1 + 2 omega) / (1 + omega),  beta0 = 1 + omega,  beta1 = -omega^2 / (1 + omega)
+ * (1, 1, 0 for the first step), K = (kdiag[ne+1], koff[ne]) the bands of lssvr_p1_assemble_react with c_quad = c and
+ * M = (mdiag, moff) those of the same entry with an a_quad of zeros and c_quad = rho: both are assembled once, and the
+ * solve is lssvr_tridiag_bc_solve_multi on (adiag, aoff).  The host owns the controller: it reads out4 after every
+ * attempt.  No atomics: bitwise reproducible.
+ *
+ * lssvr_ts_step -- one pass over the nodes, one case:
+ *   adiag[i] = kdiag[i] + s mdiag[i] (i <= ne),  aoff[i] = koff[i] + s moff[i] (i < ne)      the product first;
+ *   b[i]     = the value lssvr_ts_rhs writes for nc = 1 from (mdiag, moff, U0, U1, loads, phi, R, beta0, beta1, inv_dt),
+ *              by the same routine, bit for bit.
+ * write_bands = 0 skips the two band writes (s is the previous attempt's; kdiag, koff, adiag, aoff are not touched and
+ * may be NULL), write_bands = 1 makes them.  All arrays are DEVICE arrays; no output may be an input.  Return codes:
+ * ne < 1, R outside [1, 8], a scalar that is not finite, write_bands other than 0 / 1, an array not aligned to 8 bytes
+ * and aliased arguments are LSSVR_ERR_SIZE; a missing pointer is LSSVR_ERR_NULL.
+ *
+ * lssvr_ts_error -- out4 (DEVICE, four doubles) = { max_i |e_i| / sc_i, max_i |e_i|, max_i |U3_i|, the count of rows
+ * whose e_i or sc_i is not finite } over the rows i = 0 .. ne except a LSSVR_END_DIRICHLET end row (its value is data):
+ *   e_i  = ((w3 U3_i + w2 U2_i) + w1 U1_i) + w0 U0_i          w1 == 0 reads no U1, w0 == 0 reads no U0 (may be NULL)
+ *   sc_i = atol + rtol max(|U3_i|, |U2_i|)                    max(x, y) = x > y ? x : y
+ * U3 is the trial u^{n+1}, U2, U1, U0 the accepted u^n, u^{n-1}, u^{n-2}, all DEVICE arrays [ne+1]; the weights are those
+ * of a divided difference with the estimate's scalar factor folded in, computed by the caller.  A counted row joins
+ * neither of the first two maxima; |U3_i| joins the third when it is finite.  atol, rtol >= 0, atol + rtol > 0.
+ * Per-workgroup partials go to work (DEVICE, work_bytes >= lssvr_ts_error_work_bytes(ne)), a second launch of one
+ * workgroup merges them.  Return codes as above; bad end kinds are LSSVR_ERR_SIZE.
+ *
+ * lssvr_ts_step_host, lssvr_ts_error_host -- the same routines on HOST arrays, bit for bit: no device is touched.
+ */
+int lssvr_ts_step(const double* kdiag, const double* koff, const double* mdiag, const double* moff, const double* U0,
+                  const double* U1, const double* loads, const double* phi, int64_t ne, int R, double s, double beta0,
+                  double beta1, double inv_dt, int write_bands, double* adiag, double* aoff, double* b, void* stream);
+int lssvr_ts_step_host(const double* kdiag_host, const double* koff_host, const double* mdiag_host,
+                       const double* moff_host, const double* U0_host, const double* U1_host, const double* loads_host,
+                       const double* phi_host, int64_t ne, int R, double s, double beta0, double beta1, double inv_dt,
+                       int write_bands, double* adiag_host, double* aoff_host, double* b_host);
+int64_t lssvr_ts_error_work_bytes(int64_t ne);
+int lssvr_ts_error(const double* U3, const double* U2, const double* U1, const double* U0, int kind_left,
+                   int kind_right, int64_t ne, double w3, double w2, double w1, double w0, double atol, double rtol,
+                   double* out4, void* work, int64_t work_bytes, void* stream);
+int lssvr_ts_error_host(const double* U3_host, const double* U2_host, const double* U1_host, const double* U0_host,
+                        int kind_left, int kind_right, int64_t ne, double w3, double w2, double w1, double w0,
+                        double atol, double rtol, double* out4_host);
+
+/*
  * Semilinear problems: -(a u')' + b u' + c u + g(x, u) = f by a damped Newton iteration (no reference counterpart;
  * DESIGN.md section 27).  ADDITIVE to ABI 7: seven new symbols and two constants, no existing entry, struct, constant
  * or kernel changes, LSSVR_ABI_VERSION stays 7.
