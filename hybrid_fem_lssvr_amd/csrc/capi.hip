@@ -25,6 +25,40 @@ int check_launch(hipError_t e, const char* what) {
   return fail(LSSVR_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
 }
 
+// The checks the entries compose, one per idea and one wording each (the ends and the sized
+// workspace follow with the tridiagonal solves).  A new entry calls these; it does not spell them out again.
+int check_ne(int64_t ne, int ne_min = 1, const char* why = "") {
+  if (ne < ne_min) return fail(LSSVR_ERR_SIZE, "ne = %lld < %d%s", (long long)ne, ne_min, why);
+  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  return LSSVR_OK;
+}
+
+bool is_finite(double v) { return v > -INFINITY && v < INFINITY; }
+
+int check_layout(int table_layout) {
+  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
+    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  return LSSVR_OK;
+}
+
+int check_kinds(int kind_left, int kind_right) {
+  if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
+      (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
+    return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
+                kind_right);
+  return LSSVR_OK;
+}
+
+// g(x, u) of the semilinear entries: sum_k q_k u^k with 1 .. 6 tables, or q_0 exp(q_1 u)
+int check_nl_kind(int kind, int nterm) {
+  if (kind != LSSVR_NL_POLY && kind != LSSVR_NL_EXP)
+    return fail(LSSVR_ERR_RHS, "unknown kind %d (LSSVR_NL_POLY or LSSVR_NL_EXP)", kind);
+  if (kind == LSSVR_NL_POLY && (nterm < 1 || nterm > 6))
+    return fail(LSSVR_ERR_SIZE, "nterm = %d outside [1, 6]", nterm);
+  if (kind == LSSVR_NL_EXP && nterm != 2) return fail(LSSVR_ERR_SIZE, "nterm = %d: LSSVR_NL_EXP has q_0 and q_1", nterm);
+  return LSSVR_OK;
+}
+
 // the arguments every enhancement entry shares, validated and bound
 int bind_enhance(lssvr::EnhanceArgs& a, const double* x, const double* u, int64_t ne, int64_t elem_offset,
                  int64_t ne_global, double gxmin, double gxmax, double bc_left, double bc_right, int M,
@@ -95,8 +129,7 @@ int check_varcoef_tables(const double* a_values, const double* da_values, const 
                          int table_layout, bool need_values) {
   if (need_values && (!a_values || !da_values || !rhs_values))
     return fail(LSSVR_ERR_NULL, "a_values, da_values and rhs_values must be non-NULL");
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  if (const int rc = check_layout(table_layout)) return rc;
   return LSSVR_OK;
 }
 
@@ -119,6 +152,16 @@ int check_work(const void* work, int64_t work_bytes, int64_t need, const char* s
     return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, %s() = %lld (pass work = NULL for the workspace-free "
                 "kernels)", (long long)work_bytes, sizer, (long long)need);
   return LSSVR_OK;
+}
+
+// a workspace the entry requires, against the `need` bytes its public `sizer` reports for (ne) or, nc >= 0, (ne, nc)
+int check_work_sized(const void* work, int64_t work_bytes, int64_t need, const char* sizer, int64_t ne, int nc = -1) {
+  if (!work) return fail(LSSVR_ERR_NULL, "work must be non-NULL");
+  if (work_bytes >= need) return LSSVR_OK;
+  char tail[16] = "";
+  if (nc >= 0) snprintf(tail, sizeof(tail), ", %d", nc);
+  return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, %s(%lld%s) = %lld", (long long)work_bytes, sizer, (long long)ne,
+              tail, (long long)need);
 }
 
 // P1 assembly arguments shared by lssvr_step, lssvr_step_varcoef and lssvr_p1_assemble (rhs left to the caller)
@@ -153,8 +196,7 @@ int bind_p1_rhs(lssvr::P1Args& p, int rhs_id, const double* rhs_params_host, con
 // the arguments lssvr_estimate and lssvr_estimate_varcoef share, validated and bound
 int bind_estimate(lssvr::EstimateArgs& a, const double* x, const double* W, int64_t ne, int M, int nq, double* eta2,
                   double* jump, double* out3, void* work) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
   if (nq < 1 || nq > lssvr::kAdaptMaxNq)
     return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
@@ -756,8 +798,7 @@ int lssvr_colloc_points_subset(const double* x, int64_t ne_mesh, const int64_t* 
                                int n_colloc, int table_layout, double* xc, void* stream) {
   if (ne_mesh < 0 || nsub < 0) return fail(LSSVR_ERR_SIZE, "ne_mesh / nsub < 0");
   if (n_colloc < 2) return fail(LSSVR_ERR_SIZE, "n_colloc < 2");
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
+  if (const int rc = check_layout(table_layout)) return rc;
   if (!elem_ids && nsub != ne_mesh)
     return fail(LSSVR_ERR_SIZE, "elem_ids == NULL means every element: nsub must equal ne_mesh");
   if (elem_ids && nsub > ne_mesh) return fail(LSSVR_ERR_SIZE, "nsub = %lld > ne_mesh = %lld",
@@ -894,24 +935,28 @@ int64_t lssvr_tridiag_periodic_work_bytes(int64_t ne, int nc) { return lssvr::tr
 
 // (any_sign: the pivoting solve takes a kappa of either sign)
 static int check_end_kinds(int kind_left, int kind_right, const double* kappa_host, bool any_sign = false) {
-  if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
-      (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
-    return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
-                kind_right);
+  if (const int rc = check_kinds(kind_left, kind_right)) return rc;
   if (!kappa_host) return fail(LSSVR_ERR_NULL, "kappa_host must be non-NULL");
   for (int i = 0; i < 2; ++i)
     if ((i ? kind_right : kind_left) == LSSVR_END_ROBIN) {
-      if (any_sign && !(kappa_host[i] > -INFINITY && kappa_host[i] < INFINITY))
+      if (any_sign && !is_finite(kappa_host[i]))
         return fail(LSSVR_ERR_SIZE, "kappa[%d] = %g must be finite", i, kappa_host[i]);
-      if (!any_sign && !(kappa_host[i] >= 0.0 && kappa_host[i] < INFINITY))
+      if (!any_sign && !(kappa_host[i] >= 0.0 && is_finite(kappa_host[i])))
         return fail(LSSVR_ERR_SIZE, "kappa[%d] = %g must be finite and >= 0", i, kappa_host[i]);
     }
   return LSSVR_OK;
 }
 
-// Two free ends as an entry gets them and, once tridiag_check has checked them, as the launchers take them: f = the end
-// is a Robin end, k = its kappa (0 at a Dirichlet end, whose kappa is not read).
-struct TriEnds { int kind_left, kind_right; const double* kappa_host; bool f0, f1; double k0, k1; };
+// Two free ends as an entry gets them and, once check_ends has checked them, as the launchers take them: f = the end is
+// a Robin end, k = its kappa (0 at a Dirichlet end, whose kappa is not read).
+struct Ends { int kind_left, kind_right; const double* kappa_host; bool f0, f1; double k0, k1; };
+
+static int check_ends(Ends& e, bool any_sign) {
+  if (const int rc = check_end_kinds(e.kind_left, e.kind_right, e.kappa_host, any_sign)) return rc;
+  e.f0 = e.kind_left == LSSVR_END_ROBIN, e.f1 = e.kind_right == LSSVR_END_ROBIN;
+  e.k0 = e.f0 ? e.kappa_host[0] : 0.0, e.k1 = e.f1 ? e.kappa_host[1] : 0.0;
+  return LSSVR_OK;
+}
 enum TriWork { kTriNoWork, kTriWorkUnsized, kTriWorkSized };
 
 // What every tridiagonal entry checks before it launches, in this order: ne, nc, the NULL list (sup == NULL: a symmetric
@@ -919,21 +964,15 @@ enum TriWork { kTriNoWork, kTriWorkUnsized, kTriWorkSized };
 // kTriWorkUnsized: the single-RHS Dirichlet entries, which have no work_bytes argument; kTriNoWork: the host entry.
 static int tridiag_check(const TriFamily& fam, bool sym, const double* diag, const double* sub, const double* sup,
                          const double* load, int64_t ne, int nc, const double* u, TriWork mode, const void* work,
-                         int64_t work_bytes, TriEnds* ends = nullptr) {
+                         int64_t work_bytes, Ends* ends = nullptr) {
   if (ne < fam.ne_min) return fail(LSSVR_ERR_SIZE, "ne = %lld < %d%s", (long long)ne, fam.ne_min, fam.ne_why);
   if (nc < 1) return fail(LSSVR_ERR_SIZE, "nc = %d < 1", nc);
   if (!diag || !sub || (!sym && !sup) || !load || !u || (mode != kTriNoWork && !work))
     return fail(LSSVR_ERR_NULL, "diag, %s, load, u%s must be non-NULL", sym ? "off" : "sub, sup",
                 mode != kTriNoWork ? ", work" : "");
-  if (ends) {
-    const int rc = check_end_kinds(ends->kind_left, ends->kind_right, ends->kappa_host, fam.any_sign);
-    if (rc != LSSVR_OK) return rc;
-    ends->f0 = ends->kind_left == LSSVR_END_ROBIN, ends->f1 = ends->kind_right == LSSVR_END_ROBIN;
-    ends->k0 = ends->f0 ? ends->kappa_host[0] : 0.0, ends->k1 = ends->f1 ? ends->kappa_host[1] : 0.0;
-  }
-  if (mode == kTriWorkSized && work_bytes < fam.need(ne, nc))
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, %s(%lld, %d) = %lld", (long long)work_bytes, fam.sizer,
-                (long long)ne, nc, (long long)fam.need(ne, nc));
+  if (ends)
+    if (const int rc = check_ends(*ends, fam.any_sign)) return rc;
+  if (mode == kTriWorkSized) return check_work_sized(work, work_bytes, fam.need(ne, nc), fam.sizer, ne, nc);
   return LSSVR_OK;
 }
 
@@ -978,7 +1017,7 @@ int lssvr_tridiag_ns_dirichlet_solve_multi(const double* diag, const double* sub
 static int tridiag_bc_solve(const double* diag, const double* sub, const double* sup, const double* load,
                             int kind_left, int kind_right, const double* end_values, const double* kappa_host,
                             int64_t ne, int nc, double* u, void* work, int64_t work_bytes, void* stream, bool sym) {
-  TriEnds e{kind_left, kind_right, kappa_host};
+  Ends e{kind_left, kind_right, kappa_host};
   const int rc = tridiag_check(kTriBc, sym, diag, sub, sup, load, ne, nc, u, kTriWorkSized, work, work_bytes, &e);
   if (rc != LSSVR_OK) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1011,7 +1050,7 @@ int lssvr_tridiag_pivot_solve_multi(const double* diag, const double* sub, const
                                     int kind_left, int kind_right, const double* end_values,
                                     const double* kappa_host, int64_t ne, int nc, double* u, int32_t* info,
                                     void* work, int64_t work_bytes, void* stream) {
-  TriEnds e{kind_left, kind_right, kappa_host};
+  Ends e{kind_left, kind_right, kappa_host};
   const int rc = tridiag_check(kTriPivot, false, diag, sub, sup, load, ne, nc, u, kTriWorkSized, work, work_bytes, &e);
   if (rc != LSSVR_OK) return rc;
   return check_launch(lssvr::tridiag_pivot_solve(diag, sub, sup, load, ne, nc, e.f0, e.f1, e.k0, e.k1, end_values, u,
@@ -1023,7 +1062,7 @@ int lssvr_tridiag_pivot_solve_multi(const double* diag, const double* sub, const
 int lssvr_tridiag_pivot_solve_host(const double* diag, const double* sub, const double* sup, const double* load,
                                    int kind_left, int kind_right, const double* end_values,
                                    const double* kappa_host, int64_t ne, int nc, double* u, int32_t* info) {
-  TriEnds e{kind_left, kind_right, kappa_host};
+  Ends e{kind_left, kind_right, kappa_host};
   const int rc = tridiag_check(kTriPivot, false, diag, sub, sup, load, ne, nc, u, kTriNoWork, nullptr, 0, &e);
   if (rc != LSSVR_OK) return rc;
   lssvr::tridiag_pivot_host(diag, sub, sup, load, ne, nc, e.f0, e.f1, e.k0, e.k1, end_values, u, info);
@@ -1193,8 +1232,7 @@ int lssvr_estimate_react(const double* x, const double* W, int64_t ne, int M, in
 int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int kind_left, int kind_right,
                         const double* kappa_host, const double* g_host, const double* a_ends_host, double* eta2,
                         double* out3, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
   if (!x || !W || !eta2 || !out3) return fail(LSSVR_ERR_NULL, "x, W, eta2, out3 must be non-NULL");
   const int rc = check_end_kinds(kind_left, kind_right, kappa_host);
@@ -1219,8 +1257,7 @@ int lssvr_estimate_ends(const double* x, const double* W, int M, int64_t ne, int
 
 int lssvr_estimate_seam(const double* x, const double* W, int M, int64_t ne, const double* a_seam_host, double* eta2,
                         double* out3, void* stream) {
-  if (ne < 2) return fail(LSSVR_ERR_SIZE, "ne = %lld < 2: a periodic mesh has at least two elements", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne, 2, ": a periodic mesh has at least two elements")) return rc;
   if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
   if (!x || !W || !eta2 || !out3) return fail(LSSVR_ERR_NULL, "x, W, eta2, out3 must be non-NULL");
   if (!a_seam_host) return fail(LSSVR_ERR_NULL, "a_seam_host must be non-NULL");
@@ -1245,8 +1282,7 @@ int lssvr_estimate_goal(const double* x, const double* Wu, const double* Wz, int
                         const double* a_bnd_host, int jump_free, double* eta, double* eta2, double* q, double* out4,
                         void* work, void* stream) {
   // the checks of bind_estimate_vc, on this entry's own argument names
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
   if (nq < 1 || nq > lssvr::kAdaptMaxNq)
     return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
@@ -1292,8 +1328,7 @@ int lssvr_estimate_goal(const double* x, const double* Wu, const double* Wz, int
 
 int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* eta2_max_dev, double theta,
                  double h_min, void* work, double* x_new, int64_t* parent, int64_t* ne_new_dev, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (!(theta >= 0.0 && theta <= 1.0)) return fail(LSSVR_ERR_SIZE, "theta = %g outside [0, 1]", theta);
   if (!(h_min >= 0.0) || !(h_min < INFINITY)) return fail(LSSVR_ERR_SIZE, "h_min = %g must be finite and >= 0", h_min);
   if (!x || !eta2 || !eta2_max_dev || !work || !x_new || !ne_new_dev)
@@ -1304,8 +1339,7 @@ int lssvr_refine(const double* x, int64_t ne, const double* eta2, const double* 
 }
 
 int lssvr_smoothness(const double* W, int64_t ldw, const int32_t* deg, int64_t ne, double* sigma, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (ldw < 2 || ldw > lssvr::kAdaptMaxM)
     return fail(LSSVR_ERR_DEGREE, "ldw = %lld outside [2, %d]", (long long)ldw, lssvr::kAdaptMaxM);
   if (!W || !deg || !sigma) return fail(LSSVR_ERR_NULL, "W, deg and sigma must be non-NULL");
@@ -1317,8 +1351,7 @@ int lssvr_refine_hp(const double* x, int64_t ne, const double* eta2, const doubl
                     double h_min, const double* sigma, const int32_t* deg, double sigma_min, int dM, int M_max,
                     void* work, double* x_new, int32_t* deg_new, int64_t* parent, int64_t* ne_new_dev,
                     int64_t* counts2_dev, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (!(theta >= 0.0 && theta <= 1.0)) return fail(LSSVR_ERR_SIZE, "theta = %g outside [0, 1]", theta);
   if (!(h_min >= 0.0) || !(h_min < INFINITY)) return fail(LSSVR_ERR_SIZE, "h_min = %g must be finite and >= 0", h_min);
   if (dM < 1) return fail(LSSVR_ERR_DEGREE, "dM = %d < 1", dM);
@@ -1336,8 +1369,7 @@ int lssvr_refine_hp(const double* x, int64_t ne, const double* eta2, const doubl
 int64_t lssvr_group_work_bytes(int64_t ne) { return lssvr::group_work_bytes(ne); }
 
 int lssvr_group_by_degree(const int32_t* deg, int64_t ne, int64_t* ids, int64_t* offsets, void* work, void* stream) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (!deg || !ids || !offsets || !work) return fail(LSSVR_ERR_NULL, "deg, ids, offsets and work must be non-NULL");
   return check_launch(lssvr::group_by_degree(deg, ne, ids, offsets, work, reinterpret_cast<hipStream_t>(stream)),
                       "group_by_degree");
@@ -1366,34 +1398,29 @@ int lssvr_fp64_probe(double* out, int blocks, int iters, int use_mfma, void* str
                       "fp64_probe");
 }
 
-// Eigenproblems (eigen.hip).  What the entries share: the sizes, the four bands and the ends.
+// Eigenproblems (eigen.hip).  What the entries share beyond the common checks: nb, the four bands, the sizer.
 static int bind_eig(lssvr::EigArgs& a, const double* kdiag, const double* koff, const double* mdiag,
                     const double* moff, int kind_left, int kind_right, const double* kappa_host, int64_t ne, int nb) {
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (nb < 1 || nb > 8) return fail(LSSVR_ERR_SIZE, "nb = %d outside [1, 8]", nb);
   if (!kdiag || !koff || !mdiag || !moff) return fail(LSSVR_ERR_NULL, "kdiag, koff, mdiag, moff must be non-NULL");
-  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
-  if (rc != LSSVR_OK) return rc;
+  Ends e{kind_left, kind_right, kappa_host};
+  if (const int rc = check_ends(e, true)) return rc;
   a.kdiag = kdiag;
   a.koff = koff;
   a.mdiag = mdiag;
   a.moff = moff;
   a.ne = ne;
   a.nb = nb;
-  a.f0 = kind_left == LSSVR_END_ROBIN;
-  a.f1 = kind_right == LSSVR_END_ROBIN;
-  a.k0 = a.f0 ? kappa_host[0] : 0.0;
-  a.k1 = a.f1 ? kappa_host[1] : 0.0;
+  a.f0 = e.f0;
+  a.f1 = e.f1;
+  a.k0 = e.k0;
+  a.k1 = e.k1;
   return LSSVR_OK;
 }
 
 static int check_eig_work(const void* work, int64_t work_bytes, int64_t ne, int nb) {
-  if (!work) return fail(LSSVR_ERR_NULL, "work must be non-NULL");
-  const int64_t need = lssvr::eig_work_bytes(ne, nb);
-  if (work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work holds %lld bytes, lssvr_eig_work_bytes(%lld, %d) = %lld", (long long)work_bytes,
-                (long long)ne, nb, (long long)need);
-  return LSSVR_OK;
+  return check_work_sized(work, work_bytes, lssvr::eig_work_bytes(ne, nb), "lssvr_eig_work_bytes", ne, nb);
 }
 
 int64_t lssvr_eig_work_bytes(int64_t ne, int nb) { return lssvr::eig_work_bytes(ne, nb); }
@@ -1415,7 +1442,7 @@ int lssvr_eig_apply(const double* kdiag, const double* koff, const double* mdiag
 static int check_ritz(const double* A, const double* B, int nb, double sigma, const double* theta, const double* Q) {
   if (nb < 1 || nb > 8) return fail(LSSVR_ERR_SIZE, "nb = %d outside [1, 8]", nb);
   if (!A || !B || !theta || !Q) return fail(LSSVR_ERR_NULL, "A, B, theta, Q must be non-NULL");
-  if (!(sigma > -INFINITY && sigma < INFINITY)) return fail(LSSVR_ERR_SIZE, "sigma = %g must be finite", sigma);
+  if (!is_finite(sigma)) return fail(LSSVR_ERR_SIZE, "sigma = %g must be finite", sigma);
   return LSSVR_OK;
 }
 
@@ -1441,14 +1468,11 @@ int lssvr_eig_rotate(const double* Z, const double* MZ, const double* KZ, const 
                      int64_t work_bytes, void* stream) {
   if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
   if (ne == 0) return LSSVR_OK;
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (nb < 1 || nb > 8) return fail(LSSVR_ERR_SIZE, "nb = %d outside [1, 8]", nb);
   if (!Z || !MZ || !KZ || !Q || !theta || !X || !Y || !res2)
     return fail(LSSVR_ERR_NULL, "Z, MZ, KZ, Q, theta, X, Y, res2 must be non-NULL");
-  if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
-      (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
-    return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
-                kind_right);
+  if (const int rc = check_kinds(kind_left, kind_right)) return rc;
   const int rc = check_eig_work(work, work_bytes, ne, nb);
   if (rc != LSSVR_OK) return rc;
   return check_launch(lssvr::eig_rotate(Z, MZ, KZ, Q, theta, ne, nb, kind_left == LSSVR_END_ROBIN,
@@ -1464,7 +1488,7 @@ static int bind_eig_count(lssvr::EigArgs& a, const double* kdiag, const double* 
   const int rc = bind_eig(a, kdiag, koff, mdiag, moff, kind_left, kind_right, kappa_host, ne, 1);
   if (rc != LSSVR_OK) return rc;
   if (ns > 0 && (!shifts || !counts)) return fail(LSSVR_ERR_NULL, "shifts and counts must be non-NULL");
-  if (!(pivmin > 0.0 && pivmin < INFINITY)) return fail(LSSVR_ERR_SIZE, "pivmin = %g must be finite and > 0", pivmin);
+  if (!(pivmin > 0.0 && is_finite(pivmin))) return fail(LSSVR_ERR_SIZE, "pivmin = %g must be finite and > 0", pivmin);
   return LSSVR_OK;
 }
 
@@ -1500,17 +1524,16 @@ int lssvr_eig_rayleigh(const double* x, const double* W, int64_t ne, int M, int 
                        int kind_right, const double* kappa_host, double* out3, void* work, void* stream) {
   if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne = %lld < 0", (long long)ne);
   if (ne == 0) return LSSVR_OK;
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (M < 1 || M > lssvr::kAdaptMaxM) return fail(LSSVR_ERR_DEGREE, "M = %d outside [1, %d]", M, lssvr::kAdaptMaxM);
   if (nq < 1 || nq > lssvr::kAdaptMaxNq)
     return fail(LSSVR_ERR_QUAD, "nq = %d outside [1, %d]", nq, lssvr::kAdaptMaxNq);
   if (!x || !W || !out3 || !work) return fail(LSSVR_ERR_NULL, "x, W, out3, work must be non-NULL");
   if (!a_values || !c_values || !rho_values)
     return fail(LSSVR_ERR_NULL, "a_values, c_values and rho_values must be non-NULL");
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
-  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
-  if (rc != LSSVR_OK) return rc;
+  if (const int rc = check_layout(table_layout)) return rc;
+  Ends e{kind_left, kind_right, kappa_host};
+  if (const int rc = check_ends(e, true)) return rc;
   lssvr::EigRayleighArgs a{};
   a.x = x;
   a.W = W;
@@ -1522,24 +1545,23 @@ int lssvr_eig_rayleigh(const double* x, const double* W, int64_t ne, int M, int 
   a.rho_values = rho_values;
   a.kind[0] = kind_left;
   a.kind[1] = kind_right;
-  for (int i = 0; i < 2; ++i) a.kappa[i] = a.kind[i] == LSSVR_END_ROBIN ? kappa_host[i] : 0.0;
+  a.kappa[0] = e.k0;
+  a.kappa[1] = e.k1;
   a.work = work;
   return check_launch(lssvr::eig_rayleigh(a, table_layout == LSSVR_TABLE_POINT_MAJOR, out3,
                                           reinterpret_cast<hipStream_t>(stream)),
                       "eig_rayleigh");
 }
 
-// Transient problems (timestep.hip).  The device and the host entry of each pair share one validated binding.
-static int ts_finite(double v) { return v > -INFINITY && v < INFINITY; }
-
+// Transient problems (timestep.hip).  The device and the host entry of each pair share one validated binding, made of
+// the common checks above and the entry's own NULL list and aliasing rules.
 static int bind_ts_rhs(lssvr::TsRhsArgs& a, const double* mdiag, const double* moff, const double* U0,
                        const double* U1, const double* loads, const double* phi, int64_t ne, int nc, int R,
                        double beta0, double beta1, double inv_dt, const double* out) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (nc < 1 || nc > 8) return fail(LSSVR_ERR_SIZE, "nc = %d outside [1, 8]", nc);
   if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
-  if (!ts_finite(beta0) || !ts_finite(beta1) || !ts_finite(inv_dt))
+  if (!is_finite(beta0) || !is_finite(beta1) || !is_finite(inv_dt))
     return fail(LSSVR_ERR_SIZE, "beta0 = %g, beta1 = %g, inv_dt = %g must be finite", beta0, beta1, inv_dt);
   if (!mdiag || !moff || !U0 || !loads || !phi || !out)
     return fail(LSSVR_ERR_NULL, "mdiag, moff, U0, loads, phi, out must be non-NULL");
@@ -1573,13 +1595,11 @@ static int bind_ts_source(lssvr::TsSourceArgs& a, const double* U2, const double
                           const double* ftab, const double* rho_tab, const double* phi, int64_t ne, int n_colloc,
                           int R, int table_layout, double alpha, double beta0, double beta1, double inv_dt,
                           const double* out) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (n_colloc < 2 || n_colloc > 4096) return fail(LSSVR_ERR_SIZE, "n_colloc = %d outside [2, 4096]", n_colloc);
   if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
-  if (!ts_finite(alpha) || !ts_finite(beta0) || !ts_finite(beta1) || !ts_finite(inv_dt))
+  if (const int rc = check_layout(table_layout)) return rc;
+  if (!is_finite(alpha) || !is_finite(beta0) || !is_finite(beta1) || !is_finite(inv_dt))
     return fail(LSSVR_ERR_SIZE, "alpha = %g, beta0 = %g, beta1 = %g, inv_dt = %g must be finite", alpha, beta0, beta1,
                 inv_dt);
   if (!U2 || !U0 || !ftab || !rho_tab || !phi || !out)
@@ -1626,7 +1646,7 @@ static int bind_ts_step(lssvr::TsStepArgs& a, const double* kdiag, const double*
                         int write_bands, double* adiag, double* aoff, const double* b) {
   const int rc = bind_ts_rhs(a.rhs, mdiag, moff, U0, U1, loads, phi, ne, 1, R, beta0, beta1, inv_dt, b);
   if (rc != LSSVR_OK) return rc;
-  if (!ts_finite(s)) return fail(LSSVR_ERR_SIZE, "s = %g must be finite", s);
+  if (!is_finite(s)) return fail(LSSVR_ERR_SIZE, "s = %g must be finite", s);
   if (write_bands != 0 && write_bands != 1) return fail(LSSVR_ERR_SIZE, "write_bands = %d must be 0 or 1", write_bands);
   if (write_bands && (!kdiag || !koff || !adiag || !aoff))
     return fail(LSSVR_ERR_NULL, "kdiag, koff, adiag, aoff must be non-NULL with write_bands");
@@ -1677,15 +1697,11 @@ int64_t lssvr_ts_error_work_bytes(int64_t ne) { return lssvr::ts_error_work_byte
 static int bind_ts_error(lssvr::TsErrArgs& a, const double* U3, const double* U2, const double* U1, const double* U0,
                          int kind_left, int kind_right, int64_t ne, double w3, double w2, double w1, double w0,
                          double atol, double rtol, const double* out4) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
-  if ((kind_left != LSSVR_END_DIRICHLET && kind_left != LSSVR_END_ROBIN) ||
-      (kind_right != LSSVR_END_DIRICHLET && kind_right != LSSVR_END_ROBIN))
-    return fail(LSSVR_ERR_SIZE, "end kinds (%d, %d) must be LSSVR_END_DIRICHLET or LSSVR_END_ROBIN", kind_left,
-                kind_right);
-  if (!ts_finite(w3) || !ts_finite(w2) || !ts_finite(w1) || !ts_finite(w0))
+  if (const int rc = check_ne(ne)) return rc;
+  if (const int rc = check_kinds(kind_left, kind_right)) return rc;
+  if (!is_finite(w3) || !is_finite(w2) || !is_finite(w1) || !is_finite(w0))
     return fail(LSSVR_ERR_SIZE, "w3 = %g, w2 = %g, w1 = %g, w0 = %g must be finite", w3, w2, w1, w0);
-  if (!ts_finite(atol) || !ts_finite(rtol) || atol < 0.0 || rtol < 0.0 || !(atol + rtol > 0.0))
+  if (!is_finite(atol) || !is_finite(rtol) || atol < 0.0 || rtol < 0.0 || !(atol + rtol > 0.0))
     return fail(LSSVR_ERR_SIZE, "atol = %g, rtol = %g must be finite and >= 0, their sum > 0", atol, rtol);
   if (!U3 || !U2 || !out4) return fail(LSSVR_ERR_NULL, "U3, U2, out4 must be non-NULL");
   if (w1 != 0.0 && !U1) return fail(LSSVR_ERR_NULL, "U1 must be non-NULL when w1 != 0");
@@ -1699,14 +1715,11 @@ int lssvr_ts_error(const double* U3, const double* U2, const double* U1, const d
                    int kind_right, int64_t ne, double w3, double w2, double w1, double w0, double atol, double rtol,
                    double* out4, void* work, int64_t work_bytes, void* stream) {
   lssvr::TsErrArgs a{};
-  const int rc = bind_ts_error(a, U3, U2, U1, U0, kind_left, kind_right, ne, w3, w2, w1, w0, atol, rtol, out4);
+  int rc = bind_ts_error(a, U3, U2, U1, U0, kind_left, kind_right, ne, w3, w2, w1, w0, atol, rtol, out4);
   if (rc != LSSVR_OK) return rc;
-  if (!work) return fail(LSSVR_ERR_NULL, "work must be non-NULL");
-  if (ts_misaligned({work})) return fail(LSSVR_ERR_SIZE, "work must be aligned to 8 bytes");
-  const int64_t need = lssvr::ts_error_work_bytes(ne);
-  if (work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work_bytes = %lld < lssvr_ts_error_work_bytes(%lld) = %lld", (long long)work_bytes,
-                (long long)ne, (long long)need);
+  if (ts_misaligned({work})) return fail(LSSVR_ERR_SIZE, "work must be aligned to 8 bytes");      // (NULL is aligned)
+  rc = check_work_sized(work, work_bytes, lssvr::ts_error_work_bytes(ne), "lssvr_ts_error_work_bytes", ne);
+  if (rc != LSSVR_OK) return rc;
   return check_launch(lssvr::ts_error(a, out4, work, reinterpret_cast<hipStream_t>(stream)), "ts_error");
 }
 
@@ -1725,16 +1738,10 @@ int lssvr_ts_error_host(const double* U3_host, const double* U2_host, const doub
 static int bind_nl_linearize(lssvr::NlLinArgs& a, const double* u, const double* t_local, const double* q_tabs,
                              const double* c_tab, const double* f_tab, int64_t ne, int n, int table_layout, int kind,
                              int nterm, double* c_eff, double* f_eff, double* f_res) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (n < 1 || n > 64) return fail(LSSVR_ERR_SIZE, "n = %d outside [1, 64]", n);
-  if (table_layout != LSSVR_TABLE_ELEMENT_MAJOR && table_layout != LSSVR_TABLE_POINT_MAJOR)
-    return fail(LSSVR_ERR_SIZE, "unknown table_layout %d", table_layout);
-  if (kind != LSSVR_NL_POLY && kind != LSSVR_NL_EXP)
-    return fail(LSSVR_ERR_RHS, "unknown kind %d (LSSVR_NL_POLY or LSSVR_NL_EXP)", kind);
-  if (kind == LSSVR_NL_POLY && (nterm < 1 || nterm > 6))
-    return fail(LSSVR_ERR_SIZE, "nterm = %d outside [1, 6]", nterm);
-  if (kind == LSSVR_NL_EXP && nterm != 2) return fail(LSSVR_ERR_SIZE, "nterm = %d: LSSVR_NL_EXP has q_0 and q_1", nterm);
+  if (const int rc = check_layout(table_layout)) return rc;
+  if (const int rc = check_nl_kind(kind, nterm)) return rc;
   if (!u || !t_local || !q_tabs || !f_tab) return fail(LSSVR_ERR_NULL, "u, t_local, q_tabs, f_tab must be non-NULL");
   if (!c_eff && !f_eff && !f_res) return fail(LSSVR_ERR_NULL, "one of c_eff, f_eff, f_res must be non-NULL");
   for (const double* o : {(const double*)c_eff, (const double*)f_eff, (const double*)f_res})
@@ -1774,16 +1781,13 @@ int64_t lssvr_nl_residual_work_bytes(int64_t ne) { return lssvr::nl_residual_wor
 static int bind_nl_residual(lssvr::NlResArgs& a, const double* diag, const double* sub, const double* sup,
                             const double* load, const double* u, const double* u_new, int kind_left, int kind_right,
                             const double* end_values, const double* kappa_host, int64_t ne, const double* out4) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
-  const int rc = check_end_kinds(kind_left, kind_right, kappa_host, true);
-  if (rc != LSSVR_OK) return rc;
+  if (const int rc = check_ne(ne)) return rc;
+  Ends e{kind_left, kind_right, kappa_host};
+  if (const int rc = check_ends(e, true)) return rc;
   if (!diag || !sub || !sup || !load || !u || !u_new || !out4)
     return fail(LSSVR_ERR_NULL, "diag, sub, sup, load, u, u_new, out4 must be non-NULL");
-  const bool robin = kind_left == LSSVR_END_ROBIN || kind_right == LSSVR_END_ROBIN;
-  if (robin && !end_values) return fail(LSSVR_ERR_NULL, "end_values must be non-NULL with a Robin end");
-  a = lssvr::NlResArgs{diag, sub, sup, load, u, u_new, end_values, ne, {kind_left, kind_right}, {0.0, 0.0}};
-  for (int i = 0; i < 2; ++i) a.kappa[i] = a.kind[i] == LSSVR_END_ROBIN ? kappa_host[i] : 0.0;
+  if ((e.f0 || e.f1) && !end_values) return fail(LSSVR_ERR_NULL, "end_values must be non-NULL with a Robin end");
+  a = lssvr::NlResArgs{diag, sub, sup, load, u, u_new, end_values, ne, {kind_left, kind_right}, {e.k0, e.k1}};
   return LSSVR_OK;
 }
 
@@ -1792,14 +1796,10 @@ int lssvr_nl_residual(const double* diag, const double* sub, const double* sup, 
                       const double* kappa_host, int64_t ne, double* out4, void* work, int64_t work_bytes,
                       void* stream) {
   lssvr::NlResArgs a{};
-  const int rc = bind_nl_residual(a, diag, sub, sup, load, u, u_new, kind_left, kind_right, end_values, kappa_host, ne,
-                                  out4);
+  int rc = bind_nl_residual(a, diag, sub, sup, load, u, u_new, kind_left, kind_right, end_values, kappa_host, ne, out4);
   if (rc != LSSVR_OK) return rc;
-  if (!work) return fail(LSSVR_ERR_NULL, "work must be non-NULL");
-  const int64_t need = lssvr::nl_residual_work_bytes(ne);
-  if (work_bytes < need)
-    return fail(LSSVR_ERR_SIZE, "work_bytes = %lld < lssvr_nl_residual_work_bytes(%lld) = %lld", (long long)work_bytes,
-                (long long)ne, (long long)need);
+  rc = check_work_sized(work, work_bytes, lssvr::nl_residual_work_bytes(ne), "lssvr_nl_residual_work_bytes", ne);
+  if (rc != LSSVR_OK) return rc;
   return check_launch(lssvr::nl_residual(a, out4, work, reinterpret_cast<hipStream_t>(stream)), "nl_residual");
 }
 
@@ -1816,9 +1816,8 @@ int lssvr_nl_residual_host(const double* diag_host, const double* sub_host, cons
 }
 
 static int check_nl_step(const double* u, const double* u_new, double lambda, int64_t ne, const double* out) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
-  if (!ts_finite(lambda)) return fail(LSSVR_ERR_SIZE, "lambda = %g must be finite", lambda);
+  if (const int rc = check_ne(ne)) return rc;
+  if (!is_finite(lambda)) return fail(LSSVR_ERR_SIZE, "lambda = %g must be finite", lambda);
   if (!u || !u_new || !out) return fail(LSSVR_ERR_NULL, "u, u_new, out must be non-NULL");
   if (out == u || out == u_new) return fail(LSSVR_ERR_SIZE, "out must not be u or u_new");
   return LSSVR_OK;
@@ -1841,14 +1840,9 @@ int lssvr_nl_step_host(const double* u_host, const double* u_new_host, double la
 static int bind_ts_nl_assemble(lssvr::TsNlArgs& a, const double* x, const double* u, const double* a_quad,
                                const double* cs_quad, const double* q_quad, const double* r, int64_t ne, int nquad,
                                int kind, int nterm, double* diag, double* off, double* rhs) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
-  if (kind != LSSVR_NL_POLY && kind != LSSVR_NL_EXP)
-    return fail(LSSVR_ERR_RHS, "unknown kind %d (LSSVR_NL_POLY or LSSVR_NL_EXP)", kind);
-  if (kind == LSSVR_NL_POLY && (nterm < 1 || nterm > 6))
-    return fail(LSSVR_ERR_SIZE, "nterm = %d outside [1, 6]", nterm);
-  if (kind == LSSVR_NL_EXP && nterm != 2) return fail(LSSVR_ERR_SIZE, "nterm = %d: LSSVR_NL_EXP has q_0 and q_1", nterm);
+  if (const int rc = check_nl_kind(kind, nterm)) return rc;
   if (!x || !u || !cs_quad || !q_quad || !r || !diag || !off || !rhs)
     return fail(LSSVR_ERR_NULL, "x, u, cs_quad, q_quad, r, diag, off, rhs must be non-NULL");
   for (const double* o : {(const double*)diag, (const double*)off, (const double*)rhs})
@@ -1885,11 +1879,10 @@ static int bind_wave_advance(lssvr::WaveArgs& a, const double* U_new, const doub
                              const double* doff, const double* loads, const double* phi, int64_t ne, int nc, int R,
                              double dt, double beta, double gamma, const double* V_out, const double* Acc_out,
                              const double* rhs_out) {
-  if (ne < 1) return fail(LSSVR_ERR_SIZE, "ne = %lld < 1", (long long)ne);
-  if (ne > (int64_t)1 << 40) return fail(LSSVR_ERR_SIZE, "ne = %lld too large", (long long)ne);
+  if (const int rc = check_ne(ne)) return rc;
   if (nc < 1 || nc > 8) return fail(LSSVR_ERR_SIZE, "nc = %d outside [1, 8]", nc);
   if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
-  if (!(ts_finite(dt) && dt > 0.0) || !(ts_finite(beta) && beta > 0.0) || !(ts_finite(gamma) && gamma > 0.0))
+  if (!(is_finite(dt) && dt > 0.0) || !(is_finite(beta) && beta > 0.0) || !(is_finite(gamma) && gamma > 0.0))
     return fail(LSSVR_ERR_SIZE, "dt = %g, beta = %g, gamma = %g must be finite and > 0", dt, beta, gamma);
   if (!U_new && !rhs_out)
     return fail(LSSVR_ERR_SIZE, "U_new and rhs_out are both NULL: there is nothing to compute");

@@ -1549,37 +1549,12 @@ def group_by_degree(deg, *, work=None, stream=None):
 # --------------------------------------------------------------------------
 # eigenproblems -(a u')' + c u = lambda rho u
 # --------------------------------------------------------------------------
-EIG_MAX_BLOCK = 8      # widest block of iteration vectors: one pass of the multi solvers
+EIG_MAX_BLOCK = TRIDIAG_MULTI_CASES      # widest block of iteration vectors: one pass of the multi solvers
 
 
-def _eig_bands(kdiag, koff, mdiag, moff):
-    """ne of the four bands K = (kdiag[ne+1], koff[ne]), M = (mdiag[ne+1], moff[ne]), checked."""
-    for nm, t in (("kdiag", kdiag), ("koff", koff), ("mdiag", mdiag), ("moff", moff)):
-        _dev(t, nm)
-    ne = koff.numel()
-    if ne < 1:
-        raise ValueError("need at least one element")
-    if kdiag.numel() != ne + 1 or mdiag.numel() != ne + 1 or moff.numel() != ne:
-        raise ValueError("band lengths must be ne+1, ne, ne+1, ne (kdiag, koff, mdiag, moff)")
-    _same_device(kdiag, koff=koff, mdiag=mdiag, moff=moff)
-    return ne
-
-
-def _eig_block(ne, like, **vectors):
-    """nb of the block vectors [nb, ne+1] (all of one shape, on ``like``'s device), checked."""
-    nb = None
-    for nm, t in vectors.items():
-        _dev(t, nm)
-        if t.dim() != 2 or t.shape[1] != ne + 1 or not 1 <= t.shape[0] <= EIG_MAX_BLOCK:
-            raise ValueError(f"{nm} must be [nb, ne+1] = [1 .. {EIG_MAX_BLOCK}, {ne + 1}], got {list(t.shape)}")
-        if nb is not None and t.shape[0] != nb:
-            raise ValueError(f"{nm} must hold nb = {nb} vectors, got {t.shape[0]}")
-        nb = int(t.shape[0])
-    _same_device(like, **vectors)
-    return nb
-
-
-def _eig_out(t, name, shape, like, dtype=torch.float64):
+# What the wrappers from here to ``wave_advance`` check, one helper per idea: a new wrapper
+# composes these.  ``_dev`` (a contiguous device tensor of the dtype) comes first in every wrapper; these look at shapes.
+def _out(t, name, shape, like, dtype=torch.float64):
     """The output buffer ``t`` (allocated when None) of ``shape`` on ``like``'s device."""
     if t is None:
         return torch.empty(shape, dtype=dtype, device=like.device)
@@ -1590,15 +1565,109 @@ def _eig_out(t, name, shape, like, dtype=torch.float64):
     return t
 
 
-def _eig_work(work, ne, nb, like):
-    need = _capi.load().lssvr_eig_work_bytes(ne, nb)
+def _finite(**named):
+    """The named scalars as floats, each finite."""
+    out = []
+    for nm, v in named.items():
+        v = float(v)
+        if not math.isfinite(v):
+            raise ValueError(f"{nm} must be finite, got {v!r}")
+        out.append(v)
+    return out
+
+
+def _band_pair(message, diag, off, ne=None):
+    """ne of the bands diag[ne+1], off[ne] of one tridiagonal matrix; with ``ne`` given, the check that they have it."""
+    if ne is None:
+        ne = off.numel()
+        if ne < 1:
+            raise ValueError("need at least one element")
+    if diag.dim() != 1 or off.dim() != 1 or diag.numel() != ne + 1 or off.numel() != ne:
+        raise ValueError(message)
+    return ne
+
+
+def _nodes(t, name):
+    """ne of the nodal vector ``t`` [ne+1]."""
+    if t.dim() != 1 or t.numel() < 2:
+        raise ValueError(f"{name} must be 1-D with at least two nodes")
+    return t.numel() - 1
+
+
+def _nodal(ne, message=None, **vectors):
+    """Each vector is [ne+1]."""
+    for nm, t in vectors.items():
+        if t.dim() != 1 or t.numel() != ne + 1:
+            raise ValueError(message or f"{nm} must be [ne+1] = [{ne + 1}], got {list(t.shape)}")
+
+
+def _block(ne, rows, **vectors):
+    """The row count of the blocks [rows, ne+1], 1 .. 8 rows and one count for all of them."""
+    n = None
+    for nm, t in vectors.items():
+        if t.dim() != 2 or t.shape[1] != ne + 1 or not 1 <= t.shape[0] <= TRIDIAG_MULTI_CASES:
+            raise ValueError(f"{nm} must be [{rows}, ne+1] = [1 .. {TRIDIAG_MULTI_CASES}, {ne + 1}], "
+                             f"got {list(t.shape)}")
+        if n is not None and t.shape[0] != n:
+            raise ValueError(f"{nm} must hold {rows} = {n} vectors, got {t.shape[0]}")
+        n = int(t.shape[0])
+    return n
+
+
+def _loads_phi(ne, nc, loads, phi):
+    """R of the separable forcing: loads [R, ne+1] with R in 1 .. 8 and phi [nc, R]."""
+    if loads.dim() != 2 or loads.shape[1] != ne + 1 or not 1 <= loads.shape[0] <= TS_MAX_TERMS:
+        raise ValueError(f"loads must be [R, ne+1] = [1 .. {TS_MAX_TERMS}, {ne + 1}], got {list(loads.shape)}")
+    R = int(loads.shape[0])
+    if tuple(phi.shape) != (nc, R):
+        raise ValueError(f"phi must be [nc, R] = [{nc}, {R}], got {list(phi.shape)}")
+    return R
+
+
+def _lagged(U1, beta1, like, like_name):
+    """The array of the step before last: needed when its coefficient is not zero, a device tensor of ``like``'s shape
+    when given."""
+    if U1 is None:
+        if beta1 != 0.0:
+            raise ValueError("U1 is needed when beta1 != 0")
+        return
+    _dev(U1, "U1")
+    if U1.shape != like.shape:
+        raise ValueError(f"U1 must have the shape of {like_name} {list(like.shape)}, got {list(U1.shape)}")
+
+
+def _sized_work(work, like, sizer, *args):
+    """The scratch of ``sizer(*args)`` bytes on ``like``'s device: the caller's ``work`` once it holds that many (a
+    smaller one raises), else a fresh buffer."""
+    need = getattr(_capi.load(), sizer)(*args)
     if work is not None:
         _dev(work, "work")
         if work.numel() * work.element_size() < need:
             raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                             f"lssvr_eig_work_bytes({ne}, {nb}) = {need}")
+                             f"{sizer}({', '.join(map(str, args))}) = {need}")
         _same_device(like, work=work)
     return _scratch(work, need, like.device)
+
+
+def _no_alias(message, outs, ins):
+    """No output is one of the inputs (``None``: not given), and the outputs are buffers of their own."""
+    ptrs = [t.data_ptr() for t in outs]
+    taken = {t.data_ptr() for t in ins if t is not None}
+    if len(set(ptrs)) != len(ptrs) or not taken.isdisjoint(ptrs):
+        raise ValueError(message)
+
+
+_EIG_BANDS = "band lengths must be ne+1, ne, ne+1, ne (kdiag, koff, mdiag, moff)"
+
+
+def _eig_bands(kdiag, koff, mdiag, moff):
+    """ne of the four bands K = (kdiag[ne+1], koff[ne]), M = (mdiag[ne+1], moff[ne]), checked."""
+    for nm, t in (("kdiag", kdiag), ("koff", koff), ("mdiag", mdiag), ("moff", moff)):
+        _dev(t, nm)
+    ne = _band_pair(_EIG_BANDS, kdiag, koff)
+    _band_pair(_EIG_BANDS, mdiag, moff, ne)
+    _same_device(kdiag, koff=koff, mdiag=mdiag, moff=moff)
+    return ne
 
 
 def eig_apply(kdiag, koff, mdiag, moff, Z, end_kinds=(END_DIRICHLET, END_DIRICHLET), kappa=(0.0, 0.0), *, MZ=None,
@@ -1610,12 +1679,14 @@ def eig_apply(kdiag, koff, mdiag, moff, Z, end_kinds=(END_DIRICHLET, END_DIRICHL
     (MZ, KZ, gram)."""
     lib = _capi.load()
     ne = _eig_bands(kdiag, koff, mdiag, moff)
-    nb = _eig_block(ne, kdiag, Z=Z)
+    _dev(Z, "Z")
+    nb = _block(ne, "nb", Z=Z)
+    _same_device(kdiag, Z=Z)
     kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
-    MZ = _eig_out(MZ, "MZ", (nb, ne + 1), kdiag)
-    KZ = _eig_out(KZ, "KZ", (nb, ne + 1), kdiag)
-    gram = _eig_out(gram, "gram", (2, nb, nb), kdiag)
-    work = _eig_work(work, ne, nb, kdiag)
+    MZ = _out(MZ, "MZ", (nb, ne + 1), kdiag)
+    KZ = _out(KZ, "KZ", (nb, ne + 1), kdiag)
+    gram = _out(gram, "gram", (2, nb, nb), kdiag)
+    work = _sized_work(work, kdiag, "lssvr_eig_work_bytes", ne, nb)
     rc = lib.lssvr_eig_apply(_ptr(kdiag), _ptr(koff), _ptr(mdiag), _ptr(moff), kinds[0], kinds[1], kap, ne, nb, _ptr(Z),
                              _ptr(MZ), _ptr(KZ), _ptr(gram), _ptr(work), work.numel() * work.element_size(),
                              _stream(stream))
@@ -1633,13 +1704,11 @@ def eig_ritz(gram, sigma=0.0, *, theta=None, Q=None, info=None, stream=None):
     if gram.dim() != 3 or gram.shape[0] != 2 or gram.shape[1] != gram.shape[2] or \
             not 1 <= gram.shape[1] <= EIG_MAX_BLOCK:
         raise ValueError(f"gram must be [2, nb, nb] with nb in 1 .. {EIG_MAX_BLOCK}, got {list(gram.shape)}")
-    sigma = float(sigma)
-    if not math.isfinite(sigma):
-        raise ValueError(f"sigma must be finite, got {sigma!r}")
+    (sigma,) = _finite(sigma=sigma)
     nb = int(gram.shape[1])
-    theta = _eig_out(theta, "theta", (nb,), gram)
-    Q = _eig_out(Q, "Q", (nb, nb), gram)
-    info = _eig_out(info, "info", (1,), gram, torch.int32)
+    theta = _out(theta, "theta", (nb,), gram)
+    Q = _out(Q, "Q", (nb, nb), gram)
+    info = _out(info, "info", (1,), gram, torch.int32)
     rc = lib.lssvr_eig_ritz(_ptr(gram[0]), _ptr(gram[1]), nb, sigma, _ptr(theta), _ptr(Q), _ptr(info),
                             _stream(stream))
     _capi.check(rc, "lssvr_eig_ritz")
@@ -1653,24 +1722,22 @@ def eig_rotate(Z, MZ, KZ, Q, theta, end_kinds=(END_DIRICHLET, END_DIRICHLET), *,
     column is signed so that X's value at the first unknown is >= 0; X and Y must not be Z, MZ or KZ.  Returns
     (X, Y, res2)."""
     lib = _capi.load()
-    _dev(Z, "Z")
+    for nm, t in (("Z", Z), ("MZ", MZ), ("KZ", KZ), ("Q", Q), ("theta", theta)):
+        _dev(t, nm)
     if Z.dim() != 2 or Z.shape[1] < 2:
         raise ValueError(f"Z must be [nb, ne+1] with ne >= 1, got {list(Z.shape)}")
     ne = int(Z.shape[1]) - 1
-    nb = _eig_block(ne, Z, Z=Z, MZ=MZ, KZ=KZ)
-    _dev(Q, "Q")
-    _dev(theta, "theta")
+    nb = _block(ne, "nb", Z=Z, MZ=MZ, KZ=KZ)
     if tuple(Q.shape) != (nb, nb) or tuple(theta.shape) != (nb,):
         raise ValueError(f"Q must be [{nb}, {nb}] and theta [{nb}], got {list(Q.shape)} and {list(theta.shape)}")
-    _same_device(Z, Q=Q, theta=theta)
+    _same_device(Z, MZ=MZ, KZ=KZ, Q=Q, theta=theta)
     kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
-    X = _eig_out(X, "X", (nb, ne + 1), Z)
-    Y = _eig_out(Y, "Y", (nb, ne + 1), Z)
+    X = _out(X, "X", (nb, ne + 1), Z)
+    Y = _out(Y, "Y", (nb, ne + 1), Z)
     for nm, t in (("X", X), ("Y", Y)):
-        if any(t.data_ptr() == s.data_ptr() for s in (Z, MZ, KZ)):
-            raise ValueError(f"{nm} must not be Z, MZ or KZ")
-    res2 = _eig_out(res2, "res2", (2, nb), Z)
-    work = _eig_work(work, ne, nb, Z)
+        _no_alias(f"{nm} must not be Z, MZ or KZ", (t,), (Z, MZ, KZ))
+    res2 = _out(res2, "res2", (2, nb), Z)
+    work = _sized_work(work, Z, "lssvr_eig_work_bytes", ne, nb)
     rc = lib.lssvr_eig_rotate(_ptr(Z), _ptr(MZ), _ptr(KZ), _ptr(Q), _ptr(theta), kinds[0], kinds[1], ne, nb, _ptr(X),
                               _ptr(Y), _ptr(res2), _ptr(work), work.numel() * work.element_size(), _stream(stream))
     _capi.check(rc, "lssvr_eig_rotate")
@@ -1693,7 +1760,7 @@ def eig_count(kdiag, koff, mdiag, moff, shifts, pivmin, end_kinds=(END_DIRICHLET
     if not (pivmin > 0.0 and math.isfinite(pivmin)):
         raise ValueError(f"pivmin must be finite and > 0, got {pivmin!r}")
     kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
-    out = _eig_out(out, "out", (ns,), kdiag, torch.int32)
+    out = _out(out, "out", (ns,), kdiag, torch.int32)
     rc = lib.lssvr_eig_count(_ptr(kdiag), _ptr(koff), _ptr(mdiag), _ptr(moff), kinds[0], kinds[1], kap, ne,
                              _ptr(shifts), ns, pivmin, _ptr(out), _stream(stream))
     _capi.check(rc, "lssvr_eig_count")
@@ -1709,16 +1776,14 @@ def eig_rayleigh(x, W, nq, a_values, c_values, rho_values, *, point_major=False,
     lib = _capi.load()
     _dev(x, "x")
     _dev(W, "W")
-    ne = x.numel() - 1
+    ne = _nodes(x, "x")
     nq = int(nq)
-    if x.dim() != 1 or ne < 1:
-        raise ValueError("x must be 1-D with at least two nodes")
     if W.dim() != 2 or W.shape[0] != ne:
         raise ValueError("W must be [ne, M]")
     _tables(ne, nq, point_major, shape=True, a_values=a_values, c_values=c_values, rho_values=rho_values)
     kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
-    out = _eig_out(out, "out", (3,), x)
-    work = _eig_work(work, ne, 1, x)
+    out = _out(out, "out", (3,), x)
+    work = _sized_work(work, x, "lssvr_eig_work_bytes", ne, 1)
     _same_device(x, W=W, a_values=a_values, c_values=c_values, rho_values=rho_values)
     rc = lib.lssvr_eig_rayleigh(_ptr(x), _ptr(W), ne, int(W.shape[1]), nq, _ptr(a_values), _ptr(c_values),
                                 _ptr(rho_values), _layout(point_major), kinds[0], kinds[1], kap, _ptr(out), _ptr(work),
@@ -1734,14 +1799,15 @@ TS_MAX_TERMS = 8       # most terms phi_r(t) f_r(x) of a separable forcing
 BDF = {"bdf1": (1.0, 1.0, 0.0), "bdf2": (1.5, 2.0, -0.5)}      # scheme -> (alpha, beta0, beta1)
 
 
-def _ts_scalars(**named):
-    out = []
-    for nm, v in named.items():
-        v = float(v)
-        if not math.isfinite(v):
-            raise ValueError(f"{nm} must be finite, got {v!r}")
-        out.append(v)
-    return out
+def _bdf_state(ne, like, U0, U1, loads, phi, beta1, out):
+    """What :func:`ts_rhs` and :func:`ts_step` check alike once ne is known -> (nc, R, out): U0 [nc, ne+1], loads and
+    phi, the lagged U1, and an ``out`` [nc, ne+1] that is neither U0 nor U1."""
+    nc = _block(ne, "nc", U0=U0)
+    R = _loads_phi(ne, nc, loads, phi)
+    _lagged(U1, beta1, U0, "U0")
+    out = _out(out, "out", (nc, ne + 1), like)
+    _no_alias("out must not be U0 or U1", (out,), (U0, U1))
+    return nc, R, out
 
 
 def ts_rhs(mdiag, moff, U0, U1, loads, phi, beta0, beta1, inv_dt, *, out=None, stream=None):
@@ -1754,29 +1820,9 @@ def ts_rhs(mdiag, moff, U0, U1, loads, phi, beta0, beta1, inv_dt, *, out=None, s
     lib = _capi.load()
     for nm, t in (("mdiag", mdiag), ("moff", moff), ("U0", U0), ("loads", loads), ("phi", phi)):
         _dev(t, nm)
-    beta0, beta1, inv_dt = _ts_scalars(beta0=beta0, beta1=beta1, inv_dt=inv_dt)
-    ne = moff.numel()
-    if ne < 1:
-        raise ValueError("need at least one element")
-    if mdiag.dim() != 1 or moff.dim() != 1 or mdiag.numel() != ne + 1:
-        raise ValueError("band lengths must be ne+1, ne (mdiag, moff)")
-    if U0.dim() != 2 or U0.shape[1] != ne + 1 or not 1 <= U0.shape[0] <= TRIDIAG_MULTI_CASES:
-        raise ValueError(f"U0 must be [nc, ne+1] = [1 .. {TRIDIAG_MULTI_CASES}, {ne + 1}], got {list(U0.shape)}")
-    nc = int(U0.shape[0])
-    if loads.dim() != 2 or loads.shape[1] != ne + 1 or not 1 <= loads.shape[0] <= TS_MAX_TERMS:
-        raise ValueError(f"loads must be [R, ne+1] = [1 .. {TS_MAX_TERMS}, {ne + 1}], got {list(loads.shape)}")
-    R = int(loads.shape[0])
-    if tuple(phi.shape) != (nc, R):
-        raise ValueError(f"phi must be [nc, R] = [{nc}, {R}], got {list(phi.shape)}")
-    if beta1 != 0.0 and U1 is None:
-        raise ValueError("U1 is needed when beta1 != 0")
-    if U1 is not None:
-        _dev(U1, "U1")
-        if U1.shape != U0.shape:
-            raise ValueError(f"U1 must have the shape of U0 {list(U0.shape)}, got {list(U1.shape)}")
-    out = _eig_out(out, "out", (nc, ne + 1), mdiag)
-    if any(s is not None and out.data_ptr() == s.data_ptr() for s in (U0, U1)):
-        raise ValueError("out must not be U0 or U1")
+    beta0, beta1, inv_dt = _finite(beta0=beta0, beta1=beta1, inv_dt=inv_dt)
+    ne = _band_pair("band lengths must be ne+1, ne (mdiag, moff)", mdiag, moff)
+    nc, R, out = _bdf_state(ne, mdiag, U0, U1, loads, phi, beta1, out)
     _same_device(mdiag, moff=moff, U0=U0, loads=loads, phi=phi, **({} if U1 is None else {"U1": U1}))
     rc = lib.lssvr_ts_rhs(_ptr(mdiag), _ptr(moff), _ptr(U0), _ptr(U1), _ptr(loads), _ptr(phi), ne, nc, R, beta0, beta1,
                           inv_dt, _ptr(out), _stream(stream))
@@ -1795,10 +1841,8 @@ def ts_source_table(U2, U0, U1, ftab, rho_tab, phi, alpha, beta0, beta1, inv_dt,
     lib = _capi.load()
     for nm, t in (("U2", U2), ("U0", U0), ("ftab", ftab), ("rho_tab", rho_tab), ("phi", phi)):
         _dev(t, nm)
-    alpha, beta0, beta1, inv_dt = _ts_scalars(alpha=alpha, beta0=beta0, beta1=beta1, inv_dt=inv_dt)
-    ne = U2.numel() - 1
-    if U2.dim() != 1 or ne < 1:
-        raise ValueError("U2 must be 1-D with at least two nodes")
+    alpha, beta0, beta1, inv_dt = _finite(alpha=alpha, beta0=beta0, beta1=beta1, inv_dt=inv_dt)
+    ne = _nodes(U2, "U2")
     if rho_tab.dim() != 2 or rho_tab.shape[1 if point_major else 0] != ne:
         raise ValueError(f"rho_tab must be {'[n_colloc, ne]' if point_major else '[ne, n_colloc]'} with ne = {ne}, "
                          f"got {list(rho_tab.shape)}")
@@ -1811,15 +1855,11 @@ def ts_source_table(U2, U0, U1, ftab, rho_tab, phi, alpha, beta0, beta1, inv_dt,
     R = int(ftab.shape[0])
     if tuple(phi.shape) != (R,):
         raise ValueError(f"phi must be [R] = [{R}], got {list(phi.shape)}")
-    if beta1 != 0.0 and U1 is None:
-        raise ValueError("U1 is needed when beta1 != 0")
-    named = {"U0": U0} if U1 is None else {"U0": U0, "U1": U1}
-    for nm, t in named.items():
-        _dev(t, nm)
-        if t.shape != U2.shape:
-            raise ValueError(f"{nm} must have the shape of U2 {list(U2.shape)}, got {list(t.shape)}")
-    out = _eig_out(out, "out", tuple(rho_tab.shape), U2)
-    _same_device(U2, ftab=ftab, rho_tab=rho_tab, phi=phi, **named)
+    if U0.shape != U2.shape:
+        raise ValueError(f"U0 must have the shape of U2 {list(U2.shape)}, got {list(U0.shape)}")
+    _lagged(U1, beta1, U2, "U2")
+    out = _out(out, "out", tuple(rho_tab.shape), U2)
+    _same_device(U2, U0=U0, U1=U1, ftab=ftab, rho_tab=rho_tab, phi=phi)
     rc = lib.lssvr_ts_source_table(_ptr(U2), _ptr(U0), _ptr(U1), _ptr(ftab), _ptr(rho_tab), _ptr(phi), ne, n, R,
                                    _layout(point_major), alpha, beta0, beta1, inv_dt, _ptr(out), _stream(stream))
     _capi.check(rc, "lssvr_ts_source_table")
@@ -1840,34 +1880,17 @@ def ts_step(kdiag, koff, mdiag, moff, U0, U1, loads, phi, s, beta0, beta1, inv_d
     for nm, t in (("kdiag", kdiag), ("koff", koff), ("mdiag", mdiag), ("moff", moff), ("U0", U0), ("loads", loads),
                   ("phi", phi), ("adiag", adiag), ("aoff", aoff)):
         _dev(t, nm)
-    s, beta0, beta1, inv_dt = _ts_scalars(s=s, beta0=beta0, beta1=beta1, inv_dt=inv_dt)
-    ne = moff.numel()
-    if ne < 1:
-        raise ValueError("need at least one element")
-    if any(t.dim() != 1 for t in (kdiag, koff, mdiag, moff, adiag, aoff)) or koff.numel() != ne \
-            or aoff.numel() != ne or any(t.numel() != ne + 1 for t in (kdiag, mdiag, adiag)):
-        raise ValueError("band lengths must be ne+1 (kdiag, mdiag, adiag) and ne (koff, moff, aoff)")
-    if U0.dim() != 2 or tuple(U0.shape) != (1, ne + 1):
+    s, beta0, beta1, inv_dt = _finite(s=s, beta0=beta0, beta1=beta1, inv_dt=inv_dt)
+    bands = "band lengths must be ne+1 (kdiag, mdiag, adiag) and ne (koff, moff, aoff)"
+    ne = _band_pair(bands, mdiag, moff)
+    _band_pair(bands, kdiag, koff, ne)
+    _band_pair(bands, adiag, aoff, ne)
+    if tuple(U0.shape) != (1, ne + 1):
         raise ValueError(f"U0 must be [1, ne+1] = [1, {ne + 1}], got {list(U0.shape)}")
-    if loads.dim() != 2 or loads.shape[1] != ne + 1 or not 1 <= loads.shape[0] <= TS_MAX_TERMS:
-        raise ValueError(f"loads must be [R, ne+1] = [1 .. {TS_MAX_TERMS}, {ne + 1}], got {list(loads.shape)}")
-    R = int(loads.shape[0])
-    if tuple(phi.shape) != (1, R):
-        raise ValueError(f"phi must be [nc, R] = [1, {R}], got {list(phi.shape)}")
-    if beta1 != 0.0 and U1 is None:
-        raise ValueError("U1 is needed when beta1 != 0")
-    if U1 is not None:
-        _dev(U1, "U1")
-        if U1.shape != U0.shape:
-            raise ValueError(f"U1 must have the shape of U0 {list(U0.shape)}, got {list(U1.shape)}")
-    out = _eig_out(out, "out", (1, ne + 1), mdiag)
-    if any(t is not None and out.data_ptr() == t.data_ptr() for t in (U0, U1)):
-        raise ValueError("out must not be U0 or U1")
-    ins = dict(kdiag=kdiag, koff=koff, moff=moff, U0=U0, loads=loads, phi=phi, **({} if U1 is None else {"U1": U1}))
-    outs = (adiag, aoff, out)
-    if any(o.data_ptr() == t.data_ptr() for o in outs for t in (mdiag, *ins.values())) \
-            or len({o.data_ptr() for o in outs}) != 3:
-        raise ValueError("adiag, aoff and out must be three buffers of their own, none of them an input")
+    _, R, out = _bdf_state(ne, mdiag, U0, U1, loads, phi, beta1, out)
+    ins = dict(kdiag=kdiag, koff=koff, moff=moff, U0=U0, loads=loads, phi=phi, U1=U1)
+    _no_alias("adiag, aoff and out must be three buffers of their own, none of them an input", (adiag, aoff, out),
+              (mdiag, *ins.values()))
     _same_device(mdiag, adiag=adiag, aoff=aoff, **ins)
     rc = lib.lssvr_ts_step(_ptr(kdiag), _ptr(koff), _ptr(mdiag), _ptr(moff), _ptr(U0), _ptr(U1), _ptr(loads),
                            _ptr(phi), ne, R, s, beta0, beta1, inv_dt, int(bool(write_bands)), _ptr(adiag), _ptr(aoff),
@@ -1888,13 +1911,11 @@ def ts_error(U3, U2, U1, U0, weights, atol, rtol, end_kinds=(END_DIRICHLET, END_
     _dev(U2, "U2")
     if len(weights) != 4:
         raise ValueError(f"weights must be (w3, w2, w1, w0), got {len(weights)} values")
-    w3, w2, w1, w0 = _ts_scalars(w3=weights[0], w2=weights[1], w1=weights[2], w0=weights[3])
-    atol, rtol = _ts_scalars(atol=atol, rtol=rtol)
+    w3, w2, w1, w0, atol, rtol = _finite(w3=weights[0], w2=weights[1], w1=weights[2], w0=weights[3], atol=atol,
+                                         rtol=rtol)
     if atol < 0.0 or rtol < 0.0 or not atol + rtol > 0.0:
         raise ValueError(f"atol and rtol must be >= 0 and their sum > 0, got atol = {atol!r}, rtol = {rtol!r}")
-    ne = U3.numel() - 1
-    if U3.dim() != 1 or ne < 1:
-        raise ValueError("U3 must be 1-D with at least two nodes")
+    ne = _nodes(U3, "U3")
     named = {"U2": U2}
     for nm, t, w in (("U1", U1, w1), ("U0", U0, w0)):
         if t is None:
@@ -1907,15 +1928,9 @@ def ts_error(U3, U2, U1, U0, weights, atol, rtol, end_kinds=(END_DIRICHLET, END_
         if t.shape != U3.shape:
             raise ValueError(f"{nm} must have the shape of U3 {list(U3.shape)}, got {list(t.shape)}")
     kinds, _ = _end_kinds(end_kinds, (0.0, 0.0), any_sign=True)
-    out4 = _eig_out(out4, "out4", (4,), U3)
-    need = lib.lssvr_ts_error_work_bytes(ne)
-    if work is not None:
-        _dev(work, "work")
-        if work.numel() * work.element_size() < need:
-            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                             f"lssvr_ts_error_work_bytes({ne}) = {need}")
-    work = _scratch(work, need, U3.device)
-    _same_device(U3, work=work, **named)
+    out4 = _out(out4, "out4", (4,), U3)
+    work = _sized_work(work, U3, "lssvr_ts_error_work_bytes", ne)
+    _same_device(U3, **named)
     rc = lib.lssvr_ts_error(_ptr(U3), _ptr(U2), _ptr(named.get("U1")), _ptr(named.get("U0")), kinds[0], kinds[1], ne,
                             w3, w2, w1, w0, atol, rtol, _ptr(out4), _ptr(work), work.numel() * work.element_size(),
                             _stream(stream))
@@ -1959,9 +1974,7 @@ def nl_linearize(u, t_local, kind, q_tabs, f_tab, *, c_tab=None, point_major=Fal
     lib = _capi.load()
     for nm, t in (("u", u), ("t_local", t_local), ("q_tabs", q_tabs), ("f_tab", f_tab)):
         _dev(t, nm)
-    ne = u.numel() - 1
-    if u.dim() != 1 or ne < 1:
-        raise ValueError("u must be 1-D with at least two nodes")
+    ne = _nodes(u, "u")
     if f_tab.dim() != 2 or f_tab.shape[1 if point_major else 0] != ne:
         raise ValueError(f"f_tab must be {'[n, ne]' if point_major else '[ne, n]'} with ne = {ne}, "
                          f"got {list(f_tab.shape)}")
@@ -1981,7 +1994,7 @@ def nl_linearize(u, t_local, kind, q_tabs, f_tab, *, c_tab=None, point_major=Fal
     for nm, o in (("c_eff", c_eff), ("f_eff", f_eff), ("f_res", f_res)):
         if o is None or o is False:
             continue
-        outs[nm] = _eig_out(None if o is True else o, nm, tuple(f_tab.shape), u)
+        outs[nm] = _out(None if o is True else o, nm, tuple(f_tab.shape), u)
     if not outs:
         raise ValueError("one of c_eff, f_eff, f_res must be asked for")
     _same_device(u, t_local=t_local, q_tabs=q_tabs, f_tab=f_tab, c_tab=c_tab)
@@ -2002,11 +2015,10 @@ def nl_residual(diag, sub, sup, load, u, u_new, end_kinds=(END_DIRICHLET, END_DI
     lib = _capi.load()
     for nm, t in (("diag", diag), ("sub", sub), ("sup", sup), ("load", load), ("u", u), ("u_new", u_new)):
         _dev(t, nm)
-    ne = sub.numel()
-    if ne < 1:
-        raise ValueError("need at least one element")
-    if sup.numel() != ne or any(t.dim() != 1 or t.numel() != ne + 1 for t in (diag, load, u, u_new)):
-        raise ValueError("lengths must be ne+1 (diag, load, u, u_new) and ne (sub, sup)")
+    lengths = "lengths must be ne+1 (diag, load, u, u_new) and ne (sub, sup)"
+    ne = _band_pair(lengths, diag, sub)
+    _band_pair(lengths, diag, sup, ne)
+    _nodal(ne, lengths, load=load, u=u, u_new=u_new)
     kinds, kap = _end_kinds(end_kinds, kappa, any_sign=True)
     if end_values is not None:
         _dev(end_values, "end_values")
@@ -2014,15 +2026,9 @@ def nl_residual(diag, sub, sup, load, u, u_new, end_kinds=(END_DIRICHLET, END_DI
             raise ValueError(f"end_values must hold 2 doubles, got {end_values.numel()}")
     elif END_ROBIN in kinds:
         raise ValueError("end_values (device float64[2]) is needed with a Robin end")
-    out4 = _eig_out(out4, "out4", (4,), diag)
-    need = lib.lssvr_nl_residual_work_bytes(ne)
-    if work is not None:
-        _dev(work, "work")
-        if work.numel() * work.element_size() < need:
-            raise ValueError(f"work holds {work.numel() * work.element_size()} bytes, "
-                             f"lssvr_nl_residual_work_bytes({ne}) = {need}")
-    work = _scratch(work, need, diag.device)
-    _same_device(diag, sub=sub, sup=sup, load=load, u=u, u_new=u_new, end_values=end_values, work=work)
+    out4 = _out(out4, "out4", (4,), diag)
+    work = _sized_work(work, diag, "lssvr_nl_residual_work_bytes", ne)
+    _same_device(diag, sub=sub, sup=sup, load=load, u=u, u_new=u_new, end_values=end_values)
     rc = lib.lssvr_nl_residual(_ptr(diag), _ptr(sub), _ptr(sup), _ptr(load), _ptr(u), _ptr(u_new), kinds[0], kinds[1],
                                _ptr(end_values), kap, ne, _ptr(out4), _ptr(work),
                                work.numel() * work.element_size(), _stream(stream))
@@ -2036,12 +2042,11 @@ def nl_step(u, u_new, lam, *, out=None, stream=None):
     lib = _capi.load()
     _dev(u, "u")
     _dev(u_new, "u_new")
-    (lam,) = _ts_scalars(lam=lam)
+    (lam,) = _finite(lam=lam)
     if u.dim() != 1 or u.numel() < 2 or u_new.shape != u.shape:
         raise ValueError("u and u_new must be 1-D of one length ne+1 >= 2")
-    out = _eig_out(out, "out", tuple(u.shape), u)
-    if out.data_ptr() in (u.data_ptr(), u_new.data_ptr()):
-        raise ValueError("out must not be u or u_new")
+    out = _out(out, "out", tuple(u.shape), u)
+    _no_alias("out must not be u or u_new", (out,), (u, u_new))
     _same_device(u, u_new=u_new)
     _capi.check(lib.lssvr_nl_step(_ptr(u), _ptr(u_new), lam, u.numel() - 1, _ptr(out), _stream(stream)),
                 "lssvr_nl_step")
@@ -2061,12 +2066,8 @@ def ts_nl_assemble(x, u, cs_quad, kind, q_quad, r, *, a_quad=None, out=None, str
     lib = _capi.load()
     for nm, t in (("x", x), ("u", u), ("cs_quad", cs_quad), ("q_quad", q_quad), ("r", r)):
         _dev(t, nm)
-    ne = x.numel() - 1
-    if x.dim() != 1 or ne < 1:
-        raise ValueError("x must be 1-D with at least two nodes")
-    for nm, t in (("u", u), ("r", r)):
-        if t.dim() != 1 or t.numel() != ne + 1:
-            raise ValueError(f"{nm} must be [ne+1] = [{ne + 1}], got {list(t.shape)}")
+    ne = _nodes(x, "x")
+    _nodal(ne, u=u, r=r)
     if cs_quad.dim() != 2 or cs_quad.shape[0] != ne or not 1 <= cs_quad.shape[1] <= 5:
         raise ValueError(f"cs_quad must be [ne, nquad] = [{ne}, 1 .. 5], got {list(cs_quad.shape)}")
     nquad = int(cs_quad.shape[1])
@@ -2082,11 +2083,9 @@ def ts_nl_assemble(x, u, cs_quad, kind, q_quad, r, *, a_quad=None, out=None, str
         out = {}
     elif not isinstance(out, dict) or any(k not in out for k in want):
         raise ValueError("out must be a dict with diag, off and rhs")
-    res = {k: _eig_out(out.get(k), k, shape, x) for k, shape in want.items()}
-    ins = [t.data_ptr() for t in (x, u, cs_quad, q_quad, r, a_quad) if t is not None]
-    ptrs = [res[k].data_ptr() for k in want]
-    if any(p in ins for p in ptrs) or len(set(ptrs)) != 3:
-        raise ValueError("diag, off and rhs must be distinct and none of them an input")
+    res = {k: _out(out.get(k), k, shape, x) for k, shape in want.items()}
+    _no_alias("diag, off and rhs must be distinct and none of them an input", res.values(),
+              (x, u, cs_quad, q_quad, r, a_quad))
     _same_device(x, u=u, cs_quad=cs_quad, q_quad=q_quad, r=r, a_quad=a_quad)
     rc = lib.lssvr_ts_nl_assemble(_ptr(x), _ptr(u), _ptr(a_quad), _ptr(cs_quad), _ptr(q_quad), _ptr(r), ne, nquad, kind,
                                   nterm, _ptr(res["diag"]), _ptr(res["off"]), _ptr(res["rhs"]), _stream(stream))
@@ -2114,7 +2113,7 @@ def wave_advance(U_new, U, V, Acc, mdiag, moff, ddiag, doff, loads, phi, dt, bet
         raise ValueError("U_new=None with rhs=False leaves nothing to compute")
     for nm, t in (("U", U), ("V", V), ("Acc", Acc)):
         _dev(t, nm)
-    dt, beta, gamma = _ts_scalars(dt=dt, beta=beta, gamma=gamma)
+    dt, beta, gamma = _finite(dt=dt, beta=beta, gamma=gamma)
     if not (dt > 0.0 and beta > 0.0 and gamma > 0.0):
         raise ValueError(f"dt, beta and gamma must be > 0, got {dt!r}, {beta!r}, {gamma!r}")
     if U.dim() != 2 or U.shape[1] < 2 or not 1 <= U.shape[0] <= TRIDIAG_MULTI_CASES:
@@ -2133,21 +2132,15 @@ def wave_advance(U_new, U, V, Acc, mdiag, moff, ddiag, doff, loads, phi, dt, bet
             if t is None:
                 raise ValueError(f"{nm} is needed for the right-hand side")
             _dev(t, nm)
-        if mdiag.dim() != 1 or moff.dim() != 1 or mdiag.numel() != ne + 1 or moff.numel() != ne:
-            raise ValueError(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (mdiag, moff)")
-        if loads.dim() != 2 or loads.shape[1] != ne + 1 or not 1 <= loads.shape[0] <= TS_MAX_TERMS:
-            raise ValueError(f"loads must be [R, ne+1] = [1 .. {TS_MAX_TERMS}, {ne + 1}], got {list(loads.shape)}")
-        R = int(loads.shape[0])
-        if tuple(phi.shape) != (nc, R):
-            raise ValueError(f"phi must be [nc, R] = [{nc}, {R}], got {list(phi.shape)}")
+        _band_pair(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (mdiag, moff)", mdiag, moff, ne)
+        R = _loads_phi(ne, nc, loads, phi)
         named.update(mdiag=mdiag, moff=moff, loads=loads, phi=phi)
         if ddiag is not None:
             if doff is None:
                 raise ValueError("doff is needed with ddiag")
             for nm, t in (("ddiag", ddiag), ("doff", doff)):
                 _dev(t, nm)
-            if ddiag.dim() != 1 or doff.dim() != 1 or ddiag.numel() != ne + 1 or doff.numel() != ne:
-                raise ValueError(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (ddiag, doff)")
+            _band_pair(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (ddiag, doff)", ddiag, doff, ne)
             named.update(ddiag=ddiag, doff=doff)
     else:
         mdiag = moff = ddiag = doff = loads = phi = None
@@ -2155,15 +2148,12 @@ def wave_advance(U_new, U, V, Acc, mdiag, moff, ddiag, doff, loads, phi, dt, bet
         doff = None
     outs = {}
     if U_new is not None:
-        outs["V_out"] = _eig_out(V_out, "V_out", tuple(U.shape), U)
-        outs["Acc_out"] = _eig_out(Acc_out, "Acc_out", tuple(U.shape), U)
+        outs["V_out"] = _out(V_out, "V_out", tuple(U.shape), U)
+        outs["Acc_out"] = _out(Acc_out, "Acc_out", tuple(U.shape), U)
     if rhs:
-        outs["rhs_out"] = _eig_out(rhs_out, "rhs_out", tuple(U.shape), U)
-    ins = {t.data_ptr() for t in (U, *named.values())}
-    ptrs = [t.data_ptr() for t in outs.values()]
-    if any(p in ins for p in ptrs) or len(set(ptrs)) != len(ptrs):
-        raise ValueError("V_out, Acc_out and rhs_out must be distinct and none of them an input (neighbours read the "
-                         "old values)")
+        outs["rhs_out"] = _out(rhs_out, "rhs_out", tuple(U.shape), U)
+    _no_alias("V_out, Acc_out and rhs_out must be distinct and none of them an input (neighbours read the old values)",
+              outs.values(), (U, *named.values()))
     _same_device(U, **named)
     rc = lib.lssvr_wave_advance(_ptr(U_new), _ptr(U), _ptr(V), _ptr(Acc), _ptr(mdiag), _ptr(moff), _ptr(ddiag),
                                 _ptr(doff), _ptr(loads), _ptr(phi), ne, nc, R, dt, beta, gamma,
