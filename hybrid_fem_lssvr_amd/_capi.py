@@ -84,6 +84,9 @@ SIGNATURES = {
     "lssvr_step_plan_create": _sig([C.POINTER(C.c_void_p)], _STEP),
     "lssvr_step_plan_launch": _sig([C.c_void_p], _STREAM),
     "lssvr_step_plan_destroy": _sig([C.c_void_p]),
+    # the step memo (additive to ABI 7): plan; plan, memo, memo_bytes, stream
+    "lssvr_step_plan_memo_bytes": _sig([C.c_void_p], res=_c_i64),
+    "lssvr_step_plan_memo_bind": _sig([C.c_void_p, _c_dp, _c_i64], _STREAM),
     "lssvr_enhance_varcoef": _sig(_SHARD, _VC_TABLES, _OUT, _STREAM),
     "lssvr_enhance_varcoef_work_bytes": _sig([_c_i64, _c_int, _c_int], res=_c_i64),
     "lssvr_enhance_varcoef_ws": _sig(_SHARD, _VC_TABLES, [_c_int], _OUT, _WS, _STREAM, _TIMED),

@@ -457,7 +457,16 @@ int lssvr_enhance_profiled(const double* x, const double* u, int64_t ne, int64_t
 struct lssvr_step_plan {
   lssvr::EnhanceArgs a;
   lssvr::P1Args p;
+  const double* memo = nullptr;     // lssvr_step_plan_memo_bind: caller-owned, read by the fused step only
 };
+
+// bytes of a plan's memo; 0 where the plan cannot use one: no fused step (M > kSmallMaxM, refinement), or loop
+// results that are not functions of the mesh and the plan's constants alone (gamma_values, a tabulated rhs)
+static int64_t step_memo_bytes(const lssvr_step_plan& b) {
+  const lssvr::EnhanceArgs& a = b.a;
+  if (a.M > lssvr::kSmallMaxM || a.refine > 0 || a.gamma_values || a.rhs_id != LSSVR_RHS_SIN || a.ne < 1) return 0;
+  return 8 * lssvr::step_memo_doubles(a.M, a.ne);
+}
 
 static int bind_step(lssvr_step_plan& b, const double* x, const double* u, int64_t ne, int64_t elem_offset,
                      int64_t ne_global, double gxmin, double gxmax, double bc_left, double bc_right,
@@ -483,7 +492,8 @@ static int run_step(const lssvr_step_plan& b, hipStream_t s) {
   const lssvr::EnhanceArgs& a = b.a;
   const lssvr::P1Args& p = b.p;
   // (near-square regime, a.refine > 0: the refinement lives in a kernel of its own -- two launches)
-  if (a.M <= lssvr::kSmallMaxM && a.refine == 0) return check_launch(lssvr::step_small(a, p, s), "step_small");
+  if (a.M <= lssvr::kSmallMaxM && a.refine == 0)
+    return check_launch(lssvr::step_small(a, p, s, nullptr, b.memo), "step_small");
   int rc = check_launch(lssvr::p1_assemble(p, s), "p1_assemble");
   if (rc != LSSVR_OK) return rc;
   if (a.M <= lssvr::kSmallMaxM) return check_launch(lssvr::enhance_small(a, s), "enhance_small(refine)");
@@ -525,6 +535,30 @@ int lssvr_step_plan_create(lssvr_step_plan** plan, const double* x, const double
 int lssvr_step_plan_launch(const lssvr_step_plan* plan, void* stream) {
   if (!plan) return fail(LSSVR_ERR_NULL, "plan must be non-NULL");
   return run_step(*plan, reinterpret_cast<hipStream_t>(stream));
+}
+
+int64_t lssvr_step_plan_memo_bytes(const lssvr_step_plan* plan) { return plan ? step_memo_bytes(*plan) : 0; }
+
+int lssvr_step_plan_memo_bind(lssvr_step_plan* plan, void* memo, int64_t memo_bytes, void* stream) {
+  if (!plan) return fail(LSSVR_ERR_NULL, "plan must be non-NULL");
+  if (!memo) {                       // unbind: the plan runs the loop again
+    plan->memo = nullptr;
+    return LSSVR_OK;
+  }
+  const int64_t need = step_memo_bytes(*plan);
+  if (need == 0)
+    return fail(LSSVR_ERR_SOLVER, "this plan cannot use a memo (lssvr_step_plan_memo_bytes is 0: M = %d, n_colloc = %d)",
+                plan->a.M, plan->a.n);
+  if (memo_bytes < need)
+    return fail(LSSVR_ERR_SIZE, "memo_bytes = %lld < lssvr_step_plan_memo_bytes = %lld", (long long)memo_bytes,
+                (long long)need);
+  if (reinterpret_cast<uintptr_t>(memo) % 8 != 0) return fail(LSSVR_ERR_SIZE, "memo must be 8-byte aligned");
+  plan->memo = nullptr;              // (a failed fill leaves the plan on the loop)
+  const int rc = check_launch(lssvr::step_small_memo_fill(plan->a, static_cast<double*>(memo),
+                                                          reinterpret_cast<hipStream_t>(stream)),
+                              "step_memo_fill");
+  if (rc == LSSVR_OK) plan->memo = static_cast<const double*>(memo);
+  return rc;
 }
 
 int lssvr_step_plan_destroy(lssvr_step_plan* plan) {

@@ -58,6 +58,26 @@ struct NoProbe {
 };
 enum LanePhase : int { kPhEntry = 0, kPhArgs, kPhLoaded, kPhSeeded, kPhMoments, kPhSystem, kPhSolved, kPhStored, kPhCount };
 
+// MEMO POLICY: what the body does with the plan's memo of the mesh-only loop results
+// mom[1..MR-1], P[1..MR-1], rv[0..MR-1] -- functions of (x[id], x[id+1]), n and the plan-constant (amp, omega),
+// not of u.  Layout: step_memo_planes(M) planes of step_memo_ne_pad(ne) doubles, plane[q * ne_pad + e], then the
+// key plane: the ne + 1 node coordinates the planes were computed from (lssvr_kernels.hpp).
+//   NoMemo   : the enhancement kernels; nothing is emitted.
+//   MemoUse  : the fused step.  planes == NULL runs the loop.  Otherwise the wave loads its planes and keys next
+//              to x and u; when every lane's (a, b) equals its key bit for bit the loop is skipped.  Never writes.
+//   MemoFill : runs the body to the end of the loop, stores the planes and the key, and returns.
+struct NoMemo {
+  static constexpr bool kUse = false, kFill = false;
+};
+struct MemoUse {
+  static constexpr bool kUse = true, kFill = false;
+  const double* planes;
+};
+struct MemoFill {
+  static constexpr bool kUse = false, kFill = true;
+  double* planes;
+};
+
 template <int M, int RHS>
 constexpr int kChebTilePerWave =
     (RHS == LSSVR_RHS_ARRAY && 64 * 9 > 64 * M) ? 64 * 9 : 64 * M;   // output tile / rhs staging
@@ -238,13 +258,16 @@ __device__ __attribute__((noinline)) bool cheb_ridge_solve(double* __restrict__ 
 // REFINE: the build with the near-square refinement loop (its own kernel, enhance_small_refine_kernel:
 // compiled into the main kernel the loop cost the NORMAL regime 15-65 % at M = 16..22 through register
 // allocation alone -- 61 -> 101 us at M = 20, n = 40 -- so launches with p.refine == 0 never see it).
-template <int M, int RHS, bool REFINE = false, class Probe = NoProbe>
+template <int M, int RHS, bool REFINE = false, class Probe = NoProbe, class Memo = NoMemo>
 __device__ __forceinline__ void enhance_small_body_cheb(const EnhanceArgs& p, const unsigned block,
-                                                        double* __restrict__ tile, const Probe probe = Probe{}) {
+                                                        double* __restrict__ tile, const Probe probe = Probe{},
+                                                        const Memo memo = Memo{}) {
   constexpr int MR = M - 2;
   constexpr int TD = MR > 0 ? MR : 1;
   constexpr int NT = MR * (MR + 1) / 2;
   constexpr int kStageK = 8;
+  static_assert(!(Memo::kUse || Memo::kFill) || (RHS == LSSVR_RHS_SIN && !REFINE),
+                "the memo holds the loop results of the in-kernel rhs without refinement");
 
   const int tid = threadIdx.x;
   const int64_t e = (int64_t)block * kBlock + tid;
@@ -274,11 +297,30 @@ __device__ __forceinline__ void enhance_small_body_cheb(const EnhanceArgs& p, co
     }
     const double a = p.x[id];
     const double b = p.x[id + 1];
+    // MEMO, use: the wave requests its two keys and its planes in the same round trip as x and u (the step never
+    // writes the memo, so nothing orders these loads), and skips the loop when EVERY lane's (a, b) equals its key
+    // as 64-bit integers (no NaN or -0.0 is equated with anything it is not; wave-uniform, because the loop's own
+    // branches are votes of the wave).  Otherwise the wave runs the loop on the live x and the loads are dropped.
+    [[maybe_unused]] double mq[3 * TD];
+    [[maybe_unused]] bool reuse = false;
+    const double ul = p.u[id], ur = p.u[id + 1];
+    if constexpr (Memo::kUse && MR > 0) {
+      if (memo.planes) {
+        const int64_t np = step_memo_ne_pad(p.ne);
+        const unsigned long long* const key =
+            reinterpret_cast<const unsigned long long*>(memo.planes + step_memo_planes(M) * np);
+        const unsigned long long ka = key[id], kb = key[id + 1];
+#pragma unroll
+        for (int q = 0; q < step_memo_planes(M); ++q) mq[q] = memo.planes[q * np + id];
+        reuse = __all(ka == (unsigned long long)__double_as_longlong(a) &&
+                      kb == (unsigned long long)__double_as_longlong(b));
+      }
+    }
     const int64_t eg = id + p.elem_offset;
     // Dual.py:65-75: Dirichlet value only on a global-boundary element whose end
     // point equals the global end point exactly
-    const double gl = (eg == 0 && a == p.gxmin) ? p.bc_left : p.u[id];
-    const double gr = (eg == p.ne_global - 1 && b == p.gxmax) ? p.bc_right : p.u[id + 1];
+    const double gl = (eg == 0 && a == p.gxmin) ? p.bc_left : ul;
+    const double gr = (eg == p.ne_global - 1 && b == p.gxmax) ? p.bc_right : ur;
     const double inv_gamma = p.gamma_values ? rcp_newton(p.gamma_values[id]) : p.inv_gamma;
 
     probe.mark(kPhLoaded);
@@ -332,12 +374,26 @@ __device__ __forceinline__ void enhance_small_body_cheb(const EnhanceArgs& p, co
       // points, so the rotation's own rounding never exceeds ~64 eps.
       double rs = 0.0, rc = 1.0, sd = 0.0, cd = 1.0, th0 = 0.0, dth = 0.0, kappa = 0.0;
       if constexpr (RHS == LSSVR_RHS_SIN) {
-        dth = p.rhs_omega * step;
-        sincos_tab(dth, sd, cd, p.trig);
-        kappa = -2.0 * (p.rhs_amp * inv_scl2);
+        if (!reuse) {
+          dth = p.rhs_omega * step;
+          sincos_tab(dth, sd, cd, p.trig);
+          kappa = -2.0 * (p.rhs_amp * inv_scl2);
+        }
       }
       [[maybe_unused]] const double fscale = -2.0 * inv_scl2;
       probe.mark(kPhSeeded);
+      if (reuse) {
+        // MEMO hit: the loop's results as the fill launch stored them (same operations, same order: same bits)
+        if constexpr (Memo::kUse) {
+#pragma unroll
+          for (int d = 1; d < MR; ++d) {
+            mom[d] = mq[d - 1];
+            P[d] = mq[MR - 1 + d - 1];
+          }
+#pragma unroll
+          for (int d = 0; d < MR; ++d) rv[d] = mq[2 * MR - 2 + d];
+        }
+      } else {
       // Tabulated rhs ([element][point]): the wave loads kStageK points of its 64 rows at a time
       // with consecutive lanes on consecutive doubles into LDS at pitch kStageK + 1 (conflict-free
       // when every lane then reads its own row); a lane walking its own row would touch 64 cache
@@ -507,6 +563,25 @@ __device__ __forceinline__ void enhance_small_body_cheb(const EnhanceArgs& p, co
         }
         for (; k < kl; ++k) point((double)k * step + a, k);
         if (k1 == n && k < n) point(b, n - 1);
+      }
+      }   // (!reuse)
+      if constexpr (Memo::kFill) {
+        // MEMO, fill: the loop's results and the nodes they were computed from; nothing else of the body runs
+        if (live) {
+          const int64_t np = step_memo_ne_pad(p.ne);
+          double* const mp = memo.planes + id;
+#pragma unroll
+          for (int d = 1; d < MR; ++d) {
+            mp[(d - 1) * np] = mom[d];
+            mp[(MR - 1 + d - 1) * np] = P[d];
+          }
+#pragma unroll
+          for (int d = 0; d < MR; ++d) mp[(2 * MR - 2 + d) * np] = rv[d];
+          double* const key = memo.planes + step_memo_planes(M) * np;
+          key[id] = a;
+          if (id == p.ne - 1) key[id + 1] = b;
+        }
+        return;
       }
       mom[0] = (double)n;
       probe.mark(kPhMoments);

@@ -440,15 +440,31 @@ __global__ __launch_bounds__(kBlock) void enhance_small_react_kernel(EnhanceReac
 // per-element enhancement, the remaining blocks the element-local P1 assembly (one thread
 // per node).  The two halves share nothing but the node array, so fusing them only removes
 // a launch boundary and lets the short assembly run in the shadow of the enhancement.
+// memo: the plan's memo of the mesh-only loop results (MemoUse, enhance_small_cheb.hpp); NULL runs the loop.
 template <int M>
 __global__ __launch_bounds__(kBlock) void step_small_kernel(EnhanceArgs p, P1Args a, QuadRule q,
-                                                             unsigned eblocks) {
+                                                             unsigned eblocks, const double* memo) {
   __shared__ double tile[kBlock * M];
   if (blockIdx.x < eblocks) {
-    enhance_small_body_cheb<M, LSSVR_RHS_SIN>(p, blockIdx.x, tile);
+    enhance_small_body_cheb<M, LSSVR_RHS_SIN, false, NoProbe, MemoUse>(p, blockIdx.x, tile, NoProbe{}, MemoUse{memo});
   } else {
     const int64_t i = (int64_t)(blockIdx.x - eblocks) * kBlock + threadIdx.x;
     if (i <= a.ne) p1_node<true>(a, q, i);
+  }
+}
+
+// The fill launch of a step memo: the enhancement blocks of step_small_kernel<M> -- the same body, hence the same
+// waves on the same elements -- run to the end of the collocation loop (MemoFill).  No LDS, no output but the memo.
+template <int M>
+__global__ __launch_bounds__(kBlock) void step_memo_fill_kernel(EnhanceArgs p, double* memo) {
+  if constexpr (M == 2) {
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;      // no loop at M = 2: the key plane alone
+    if (e < p.ne) {
+      memo[e] = p.x[e];
+      if (e == p.ne - 1) memo[e + 1] = p.x[e + 1];
+    }
+  } else {
+    enhance_small_body_cheb<M, LSSVR_RHS_SIN, false, NoProbe, MemoFill>(p, blockIdx.x, nullptr, NoProbe{}, MemoFill{memo});
   }
 }
 
@@ -485,10 +501,16 @@ static hipError_t launch_small(const EnhanceArgs& a, hipStream_t s, const Launch
 
 template <int M>
 static hipError_t launch_step(const EnhanceArgs& e, const P1Args& a, const QuadRule& q,
-                              hipStream_t s, const LaunchOpts* o) {
+                              hipStream_t s, const LaunchOpts* o, const double* memo) {
   const unsigned eb = (unsigned)((e.ne + kBlock - 1) / kBlock);
   const unsigned ab = (unsigned)((a.ne + 1 + kBlock - 1) / kBlock);
-  return launch(step_small_kernel<M>, dim3(eb + ab), dim3(kBlock), s, o, e, a, q, eb);
+  return launch(step_small_kernel<M>, dim3(eb + ab), dim3(kBlock), s, o, e, a, q, eb, memo);
+}
+
+template <int M>
+static hipError_t launch_memo_fill(const EnhanceArgs& e, double* memo, hipStream_t s) {
+  const unsigned eb = (unsigned)((e.ne + kBlock - 1) / kBlock);
+  return launch(step_memo_fill_kernel<M>, dim3(eb), dim3(kBlock), s, nullptr, e, memo);
 }
 
 template <int M>
@@ -516,9 +538,16 @@ static hipError_t launch_step_vc(const EnhanceArgs& e, const P1Args& a, const Qu
     }                                                                                            \
   }                                                                                              \
   hipError_t step_small_##NAME(const EnhanceArgs& e, const P1Args& a, const QuadRule& q,         \
-                               hipStream_t s, const LaunchOpts* o) {                             \
+                               hipStream_t s, const LaunchOpts* o, const double* memo) {         \
     switch (e.M) {                                                                               \
       FOR_EACH_M(LSSVR_SMALL_CASE_STEP)                                                          \
+      default:                                                                                   \
+        return hipErrorInvalidValue;                                                             \
+    }                                                                                            \
+  }                                                                                              \
+  hipError_t step_memo_fill_##NAME(const EnhanceArgs& e, double* memo, hipStream_t s) {          \
+    switch (e.M) {                                                                               \
+      FOR_EACH_M(LSSVR_SMALL_CASE_MEMO_FILL)                                                     \
       default:                                                                                   \
         return hipErrorInvalidValue;                                                             \
     }                                                                                            \
@@ -549,7 +578,10 @@ static hipError_t launch_step_vc(const EnhanceArgs& e, const P1Args& a, const Qu
   }
 #define LSSVR_SMALL_CASE_STEP(MM) \
   case MM:                        \
-    return launch_step<MM>(e, a, q, s, o);
+    return launch_step<MM>(e, a, q, s, o, memo);
+#define LSSVR_SMALL_CASE_MEMO_FILL(MM) \
+  case MM:                             \
+    return launch_memo_fill<MM>(e, memo, s);
 #define LSSVR_SMALL_CASE_STEP_VC(MM) \
   case MM:                           \
     return launch_step_vc<MM>(e, a, q, s, o);

@@ -179,9 +179,18 @@ struct P1ConvArgs : P1ReactArgs {
   double* sup;
 };
 hipError_t p1_assemble_conv(const P1ConvArgs& a, hipStream_t s);
-// assembly + enhancement of the same mesh in ONE launch (lane-per-element path, in-kernel rhs)
+// assembly + enhancement of the same mesh in ONE launch (lane-per-element path, in-kernel rhs); memo: the plan's
+// memo of the mesh-only loop results (read and validated, never written; NULL: none)
 hipError_t step_small(const EnhanceArgs& e, const P1Args& a, hipStream_t s,
-                      const LaunchOpts* o = nullptr);
+                      const LaunchOpts* o = nullptr, const double* memo = nullptr);
+// The step memo: step_memo_planes(M) = 3 (M-2) - 2 planes of step_memo_ne_pad(ne) doubles
+// (mom[1..MR-1], P[1..MR-1], rv[0..MR-1] of enhance_small_body_cheb, plane[q * ne_pad + e]), then the key plane,
+// the ne + 1 node coordinates they were computed from.  M = 2 has no loop: its memo is the key plane alone.
+__host__ __device__ constexpr int step_memo_planes(int M) { return M > 2 ? 3 * (M - 2) - 2 : 0; }
+__host__ __device__ constexpr int64_t step_memo_ne_pad(int64_t ne) { return (ne + 63) & ~(int64_t)63; }
+constexpr int64_t step_memo_doubles(int M, int64_t ne) { return step_memo_planes(M) * step_memo_ne_pad(ne) + ne + 1; }
+// one launch that fills `memo` from e.x (the enhancement half of step_small's grid, run to the end of the loop)
+hipError_t step_small_memo_fill(const EnhanceArgs& e, double* memo, hipStream_t s);
 constexpr int kStepVarcoefFusedMaxM = 12;   // lssvr_step_varcoef: one launch up to here, two above
 hipError_t step_small_vc(const EnhanceArgs& e, const P1Args& a, hipStream_t s, const LaunchOpts* o = nullptr);
 hipError_t quad_points(const double* x, int64_t ne, int nquad, double* xq, hipStream_t s);

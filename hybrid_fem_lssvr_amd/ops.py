@@ -11,6 +11,7 @@ import collections
 import contextlib
 import ctypes
 import math
+import os
 import threading
 
 import numpy as np
@@ -416,14 +417,29 @@ def _bind(lib, name, args):
     return getattr(lib, name), conv
 
 
+# The step memo's switches, read ONCE at import: LSSVR_STEP_MEMO=0 makes ``StepPlan(memo=None)`` mean off (an A/B run
+# of an unchanged caller); LSSVR_STEP_MEMO_MAX_BYTES replaces the size cap (measurement runs beyond it).
+STEP_MEMO_DEFAULT = os.environ.get("LSSVR_STEP_MEMO", "1") != "0"
+# Largest memo a plan allocates.  MEASURED at degree 8: the memo wins up to 1 250 001 elements
+# (200.0 MB: -4 %; -7 % at 1e6, -23 % at 1e5) and loses at 1e7 (1.6 GB: +13 %, the step is issue-bound there and the
+# memo triples its traffic); the cap sits just above the largest size measured to win.
+STEP_MEMO_MAX_BYTES = int(os.environ.get("LSSVR_STEP_MEMO_MAX_BYTES", 208 << 20))
+
+
 class StepPlan:
     """One step of the hot path (element-local P1 assembly + per-element enhancement of
     the same resident mesh shard) bound once, launched many times: the argument tuple of
-    ``lssvr_step`` is built at construction so that a launch is a single ctypes call."""
+    ``lssvr_step`` is built at construction so that a launch is a single ctypes call.
+
+    ``memo`` (None: on unless ``LSSVR_STEP_MEMO=0``): keep the mesh-only results of the collocation loop in a
+    buffer of the plan's (``lssvr_step_plan_memo_*``; at most ``STEP_MEMO_MAX_BYTES``, and only where the library
+    has a memo for the plan -- otherwise the plan silently runs without).  Construction then enqueues one fill
+    launch on the current stream and synchronises it.  Every launch checks the memo against the live ``x``, so
+    rewriting ``x`` in place keeps the results right and only costs the gain; :meth:`refresh_memo` restores it."""
 
     def __init__(self, x, u, M, gamma, n_colloc=12, *, rhs=(POISSON_AMP, POISSON_OMEGA), nquad=2,
                  elem_offset=0, ne_global=None, global_domain, bc=(0.0, 0.0), bands=None,
-                 out=None, status=None, fail_count=None):
+                 out=None, status=None, fail_count=None, memo=None):
         self.lib = _capi.load()
         ne, ne_global = _shard(x, u, elem_offset, ne_global)
         self.bands = _bands(x, ne, bands)
@@ -451,6 +467,16 @@ class StepPlan:
             self._handle = None
             _capi.check(rc, "lssvr_step_plan_create")
         self._launch = self.lib.lssvr_step_plan_launch
+        # the memo: a buffer of the plan's own, like the workspace above (the library allocates nothing)
+        self._memo = None
+        self.memo_bytes = 0
+        if (STEP_MEMO_DEFAULT if memo is None else memo) and self._work is None:
+            nb = int(self.lib.lssvr_step_plan_memo_bytes(self._handle))
+            if 0 < nb <= STEP_MEMO_MAX_BYTES:
+                self._memo = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+                self.memo_bytes = nb
+                self.refresh_memo()
+                torch.cuda.current_stream(x.device).synchronize()   # construction is no hot path; afterwards any stream
 
         if self._work is not None:
             self._asm_args = (_ptr(x), ne, int(nquad), RHS_SIN, self._keep[2], None, None) + bands + (None, None)
@@ -468,6 +494,18 @@ class StepPlan:
         if rc < 0:
             _capi.check(rc, "lssvr_step")
         return self.W, self.status
+
+    def refresh_memo(self, stream=None):
+        """Fill the memo again from ``x`` as it is now (one launch on ``stream``; None: the current stream of x's
+        device) -- after the mesh has been moved in place.  Not needed for correctness: launches validate the memo
+        against ``x`` themselves and run the full step where it is stale.  Set-up, like construction: no launch
+        of this plan may be in flight on ANOTHER stream, and later launches must be ordered after ``stream``.
+        A plan without a memo does nothing."""
+        if self._memo is None:
+            return
+        st = _stream(torch.cuda.current_stream(self._memo.device) if stream is None else stream)
+        _capi.check(self.lib.lssvr_step_plan_memo_bind(self._handle, _ptr(self._memo), self.memo_bytes, st),
+                    "lssvr_step_plan_memo_bind")
 
     def __del__(self):
         h = getattr(self, "_handle", None)

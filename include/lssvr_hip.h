@@ -197,6 +197,37 @@ int lssvr_step_plan_launch(const lssvr_step_plan* plan, void* stream);
 int lssvr_step_plan_destroy(lssvr_step_plan* plan);
 
 /*
+ * The step memo -- ADDITIVE to ABI 7 (two new symbols; no existing entry, struct or constant changes,
+ * LSSVR_ABI_VERSION stays 7).  Between the launches of a plan u changes and the mesh x usually does not, and
+ * half of the fused step's work -- the collocation loop -- depends on x, n_colloc and rhs_params only.  A memo
+ * keeps the loop's results per element (3 (M-2) - 2 doubles: the Chebyshev power sums, the upper-moment
+ * products and the right-hand-side sums) in CALLER-OWNED device memory; a launch with a memo bound reads them
+ * instead of running the loop.
+ *   memo_bytes : pure host arithmetic.  The bytes a memo of this plan needs,
+ *                  8 * ((3 (M-2) - 2) * ne_pad + ne + 1),  ne_pad = ne rounded up to a multiple of 64
+ *                (3 (M-2) - 2 planes of ne_pad doubles, plane[q * ne_pad + e], then the key plane: a copy of
+ *                the ne + 1 node coordinates the planes were computed from; M = 2 has no loop and no planes),
+ *                or 0 where the plan cannot use one: M > 22, the near-square regime that runs refinement steps
+ *                (lssvr_step then issues two launches), or a NULL plan.
+ *   memo_bind  : checks the buffer (memo_bytes below lssvr_step_plan_memo_bytes or a pointer that is not 8-byte
+ *                aligned: LSSVR_ERR_SIZE; a plan whose memo_bytes is 0: LSSVR_ERR_SOLVER; NULL plan:
+ *                LSSVR_ERR_NULL -- all before any HIP call), enqueues ONE fill launch on `stream` (it reads x as
+ *                it is when that launch runs) and records the pointer in the plan.  memo == NULL unbinds (no
+ *                launch).  Call it again after moving the mesh to refresh the memo.  Launches of the plan must be
+ *                ordered after the fill (same stream, or an event).
+ * VALIDATION: every launch compares each element's live (x[e], x[e+1]) with the memo's key plane, bit for bit;
+ * a wave with any element that differs runs the loop on the live x, exactly as without a memo.  W, status and
+ * the bands are therefore bit-identical with and without a memo, for any contents of x -- a stale memo costs
+ * time, never correctness -- PROVIDED the memo's contents are what a fill launch of this plan wrote: the caller
+ * must not write the buffer, nor share it between plans with different (ne, M, n_colloc, rhs_params).
+ * A step launch never writes the memo.  Binding is set-up: it modifies the plan and is NOT thread-safe against
+ * concurrent launches or other binds of the same plan; after it returns the plan is read-only again and may be
+ * launched on any stream and from several threads.  destroy does not free the memo.
+ */
+int64_t lssvr_step_plan_memo_bytes(const lssvr_step_plan* plan);
+int lssvr_step_plan_memo_bind(lssvr_step_plan* plan, void* memo, int64_t memo_bytes, void* stream);
+
+/*
  * lssvr_enhance_varcoef -- BASELINE config 5, -(a u')' = f (no reference
  * counterpart: Dual.py:44,119 hard-code -u'').  PDE row k of element e is
  *   -a_k (2/h)^2 L_p''(t_k) - da_k (2/h) L_p'(t_k),
