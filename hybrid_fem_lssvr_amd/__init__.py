@@ -5,13 +5,14 @@ Drop-in for the solve-then-enhance path of maryambabaei/hybrid-FEM-LSSVR
 argument meaning, with the per-element SLSQP loop replaced by hand-written
 gfx950 kernels behind a C ABI (``include/lssvr_hip.h``).
 """
-from . import _capi, ops  # noqa: F401
+from . import _capi, autograd, ops  # noqa: F401
 from .mesh import LineMesh, P1Basis, as_line_mesh  # noqa: F401
 from .solver import (  # noqa: F401
     EigenSolution,
     EnhancedSolution,
     FEMLSSVRPrimalSolver,
     GoalEstimate,
+    Sensitivity,
     TransientSolution,
     WaveSolution,
     SinRHS,

@@ -203,6 +203,11 @@ SIGNATURES = {
     # gamma, V_out, Acc_out, rhs_out
     "lssvr_wave_advance": _sig([_c_dp] * 10, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_dp] * 3, _STREAM),
     "lssvr_wave_advance_host": _sig([_c_hd] * 10, [_c_i64, _c_int, _c_int], [_c_dbl] * 3, [_c_hd] * 3),
+    # adjoint sensitivities (additive to ABI 7): x, ne, nquad, U, nu, Z, nc, ga, gb, gc, gf, P, band_ends, kind_left,
+    # kind_right, out_ends
+    "lssvr_p1_sensitivity": _sig(_MESH, [_c_dp, _c_int, _c_dp, _c_int], [_c_dp] * 6, [_c_int, _c_int, _c_dp], _STREAM),
+    "lssvr_p1_sensitivity_host": _sig([_c_hd, _c_i64, _c_int, _c_hd, _c_int, _c_hd, _c_int], [_c_hd] * 6,
+                                      [_c_int, _c_int, _c_hd]),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

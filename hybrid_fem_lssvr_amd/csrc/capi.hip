@@ -1969,4 +1969,44 @@ int lssvr_wave_advance_host(const double* U_new_host, const double* U_host, cons
   return LSSVR_OK;
 }
 
+// Adjoint sensitivities (sensitivity.hip).  The device and the host entry share one validated binding.
+static int bind_sens(lssvr::SensArgs& a, const double* x, int64_t ne, int nquad, const double* U, int nu,
+                     const double* Z, int nc, double* ga, double* gb, double* gc, double* gf, const double* P,
+                     const double* band_ends, int kind_left, int kind_right, double* out_ends) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (nc < 1 || nc > 8) return fail(LSSVR_ERR_SIZE, "nc = %d outside [1, 8]", nc);
+  if (nu != 1 && nu != nc) return fail(LSSVR_ERR_SIZE, "nu = %d must be 1 or nc = %d", nu, nc);
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  if (!x || !U || !Z) return fail(LSSVR_ERR_NULL, "x, U, Z must be non-NULL");
+  if (!ga && !gb && !gc && !gf) return fail(LSSVR_ERR_NULL, "one of ga, gb, gc, gf must be non-NULL");
+  if (out_ends) {
+    if (!band_ends) return fail(LSSVR_ERR_NULL, "band_ends must be non-NULL with out_ends");
+    if (const int rc = check_kinds(kind_left, kind_right)) return rc;
+  }
+  a = lssvr::SensArgs{x, U, Z, P, band_ends, ne, nquad, nu, nc, {kind_left, kind_right}, ga, gb, gc, gf, out_ends};
+  return LSSVR_OK;
+}
+
+int lssvr_p1_sensitivity(const double* x, int64_t ne, int nquad, const double* U, int nu, const double* Z, int nc,
+                         double* ga, double* gb, double* gc, double* gf, const double* P, const double* band_ends,
+                         int kind_left, int kind_right, double* out_ends, void* stream) {
+  lssvr::SensArgs a{};
+  const int rc = bind_sens(a, x, ne, nquad, U, nu, Z, nc, ga, gb, gc, gf, P, band_ends, kind_left, kind_right,
+                           out_ends);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::p1_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "p1_sensitivity");
+}
+
+int lssvr_p1_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* U_host, int nu,
+                              const double* Z_host, int nc, double* ga_host, double* gb_host, double* gc_host,
+                              double* gf_host, const double* P_host, const double* band_ends_host, int kind_left,
+                              int kind_right, double* out_ends_host) {
+  lssvr::SensArgs a{};
+  const int rc = bind_sens(a, x_host, ne, nquad, U_host, nu, Z_host, nc, ga_host, gb_host, gc_host, gf_host, P_host,
+                           band_ends_host, kind_left, kind_right, out_ends_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::p1_sensitivity_host(a);          // (nquad is checked above: the rule exists)
+  return LSSVR_OK;
+}
+
 }  // extern "C"

@@ -540,6 +540,29 @@ void wave_coefficients(WaveArgs& a, double dt, double beta, double gamma);
 hipError_t wave_advance(const WaveArgs& a, double* V_out, double* Acc_out, double* rhs_out, hipStream_t s);
 void wave_advance_host(const WaveArgs& a, double* V_out, double* Acc_out, double* rhs_out);
 
+// sensitivity.hip: adjoint sensitivities of the P1 solve.  From nc pairs (U[j], Z[j]) of a primal
+// and an adjoint nodal solution, case-major [nc][ne+1] (U [1][ne+1] with nu == 1: one primal for all cases), the
+// gradients of J with respect to the tables a_quad, b_quad, c_quad, rhs_quad, each [nc][ne*nquad] in the tables' own
+// layout, and with respect to the end data.  The tables themselves are not arguments: given u and z the gradient does
+// not depend on them.  A nullptr output is skipped, stores included.
+struct SensArgs {
+  const double* x;                  // nodes [ne+1]
+  const double* U;                  // [nu][ne+1]
+  const double* Z;                  // [nc][ne+1]
+  const double* P;                  // dJ/du [nc][ne+1], read for out_ends at a Dirichlet end; nullptr: zero
+  const double* band_ends;          // the raw sub[0] and sup[ne-1]; read for out_ends only
+  int64_t ne;
+  int nquad, nu, nc;
+  int kind[2];                      // LSSVR_END_*; read for out_ends only
+  double* ga;                       // dJ/da_quad, dJ/db_quad, dJ/dc_quad, dJ/drhs_quad
+  double* gb;
+  double* gc;
+  double* gf;
+  double* out_ends;                 // [nc][4] = dJ/dg_0, dJ/dg_ne, dJ/dkappa_0, dJ/dkappa_ne; nullptr: not wanted
+};
+hipError_t p1_sensitivity(const SensArgs& a, hipStream_t s);
+bool p1_sensitivity_host(const SensArgs& a);     // false: no such quadrature rule
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

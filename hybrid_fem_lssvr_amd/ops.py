@@ -2201,6 +2201,80 @@ def wave_advance(U_new, U, V, Acc, mdiag, moff, ddiag, doff, loads, phi, dt, bet
     return outs.get("V_out"), outs.get("Acc_out"), outs.get("rhs_out")
 
 
+# ---- adjoint sensitivities of the P1 solve -------------------------------------------------------
+SENS_TABLES = ("a", "b", "c", "f")      # d/d a_quad, b_quad, c_quad, rhs_quad: the keys of ``want`` and of the result
+
+
+def adjoint_bands(bands):
+    """The band dict of the TRANSPOSED matrix: ``sub`` and ``sup`` exchanged (in csrc/p1_conv.hip sub[i] multiplies u_i
+    in row i+1 and sup[i] multiplies u_{i+1} in row i), every other entry -- ``diag``, ``load``, a symmetric ``off`` --
+    as it is.  A new dict of the same tensors: nothing is copied.  The adjoint solve of :func:`p1_sensitivity` is the
+    primal's solve on these bands."""
+    out = dict(bands)
+    if ("sub" in bands) != ("sup" in bands):
+        raise ValueError("bands must hold both sub and sup, or neither (symmetric: off)")
+    if "sub" in bands:
+        out["sub"], out["sup"] = bands["sup"], bands["sub"]
+    return out
+
+
+def p1_sensitivity(x, U, Z, nquad=2, *, want=SENS_TABLES, P=None, bands=None,
+                   end_kinds=(END_DIRICHLET, END_DIRICHLET), out=None, stream=None):
+    """``lssvr_p1_sensitivity``: from ``nc`` pairs of a primal solution U[j] and an adjoint solution Z[j] (the solve of
+    :func:`adjoint_bands` with load dJ/du, zero end data, the primal's end kinds and kappa) the gradients of J with
+    respect to the tables of :func:`p1_assemble`, in ONE launch.  x float64[ne+1]; Z float64[nc, ne+1] (nc <= 8; a
+    1-D vector is one case); U float64[nc, ne+1], or [1, ne+1] / 1-D for one primal solution shared by all cases.
+    ``want``: which of "a", "b", "c", "f" (a_quad, b_quad, c_quad, rhs_quad) to compute, at least one; a table left
+    out is neither computed nor stored.  The tables themselves are not arguments: given u and z the gradient does not
+    depend on them.  ``bands`` (the RAW primal bands of :func:`p1_assemble`, with ``sub``/``sup`` or ``off``) asks for
+    the end gradients too, for the ends ``end_kinds``; ``P`` float64 like Z is dJ/du, read at a Dirichlet end
+    (``None``: zero).  Returns a dict: every wanted key -> float64[nc, ne, nquad], and with ``bands`` "ends" ->
+    float64[nc, 4] = (dJ/dg_0, dJ/dg_ne, dJ/dkappa_0, dJ/dkappa_ne).  ``out``: a dict of buffers to write into, by
+    those keys.  No synchronisation and no copy; every value is computed in a fixed order (bitwise reproducible)."""
+    lib = _capi.load()
+    for nm, t in (("x", x), ("U", U), ("Z", Z)):
+        _dev(t, nm)
+    ne = _nodes(x, "x")
+    nquad = int(nquad)
+    if not 1 <= nquad <= 5:
+        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
+    want = tuple(want)
+    if not want or len(set(want)) != len(want) or any(k not in SENS_TABLES for k in want):
+        raise ValueError(f"want must name at least one of {SENS_TABLES}, each once, got {want!r}")
+    U2, Z2 = (t.view(1, -1) if t.dim() == 1 else t for t in (U, Z))
+    nc = _block(ne, "nc", Z=Z2)
+    nu = _block(ne, "nu", U=U2)
+    if nu not in (1, nc):
+        raise ValueError(f"U must hold 1 or nc = {nc} vectors, got {nu}")
+    ins = {"U": U, "Z": Z}
+    if P is not None:
+        _dev(P, "P")
+        if P.numel() != Z.numel():
+            raise ValueError(f"P must have the shape of Z {list(Z.shape)}, got {list(P.shape)}")
+        ins["P"] = P
+    out = {} if out is None else out
+    res = {k: _out(out.get(k), f"out[{k!r}]", (nc, ne, nquad), x) for k in want}
+    band_ends = None
+    if bands is not None:
+        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
+        sub, sup = (bands["sub"], bands["sup"]) if "sub" in bands else (bands["off"], bands["off"])
+        for nm, t in (("sub", sub), ("sup", sup)):
+            _dev(t, nm)
+            if t.numel() != ne:
+                raise ValueError(f"{nm} must hold ne = {ne} doubles, got {t.numel()}")
+        band_ends = torch.stack((sub.reshape(-1)[0], sup.reshape(-1)[ne - 1]))
+        ins.update(sub=sub, sup=sup)
+        res["ends"] = _out(out.get("ends"), "out['ends']", (nc, 4), x)
+    else:
+        kinds = (END_DIRICHLET, END_DIRICHLET)
+    _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
+    _same_device(x, **ins)
+    rc = lib.lssvr_p1_sensitivity(_ptr(x), ne, nquad, _ptr(U), nu, _ptr(Z), nc, *(_ptr(res.get(k)) for k in SENS_TABLES),
+                                  _ptr(P), _ptr(band_ends), *kinds, _ptr(res.get("ends")), _stream(stream))
+    _capi.check(rc, "lssvr_p1_sensitivity")
+    return res
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

@@ -419,6 +419,23 @@ class GoalEstimate:
         self.corrected = self.value + self.correction
 
 
+class Sensitivity:
+    """What :meth:`FEMLSSVRPrimalSolver.solve_sensitivity` returns for a functional J of the P1 solution: ``value`` =
+    J(u_h) and its derivatives with respect to the data of the P1 solve, as numpy -- ``d_coef``, ``d_convection``,
+    ``d_reaction``, ``d_rhs`` [ne, nquad]: dJ/d(a, b, c, f at quadrature point q of element e), the tables of
+    ``ops.p1_assemble`` (``d_convection`` / ``d_reaction`` are None where the solver has no such term; without
+    ``coef`` the coefficient is the table a = 1, and ``d_coef`` is the derivative there); ``d_end_values`` [2]: dJ/dg
+    of the left and right end datum (the Dirichlet value, or g of a Neumann or Robin end); ``d_kappa`` [2]: dJ/dkappa
+    (0 at a Dirichlet end); ``adjoint`` the nodal adjoint solution z (0 at a Dirichlet end) and ``nodes`` the mesh.
+    The mesh is not differentiated."""
+
+    def __init__(self, value, tables, ends, adjoint, nodes):
+        self.value = float(value)
+        self.d_coef, self.d_convection, self.d_reaction, self.d_rhs = (tables.get(k) for k in ops.SENS_TABLES)
+        self.d_end_values, self.d_kappa = ends[:2].copy(), ends[2:].copy()
+        self.adjoint, self.nodes = adjoint, nodes
+
+
 def _evaluate_item(items, method, what, i, x, deriv):
     """``evaluate`` of the solution classes below: item ``i`` of their :class:`EnhancedSolution` list at ``x``."""
     if not items:
@@ -2297,6 +2314,118 @@ class FEMLSSVRPrimalSolver:
         self._report_fallbacks()
         self.lssvr_functions = _ElementFunctions(nodes, primal.W)
         return GoalEstimate(eta, eta2, out4), marking
+
+    # ---- adjoint sensitivities of the P1 solve (no reference counterpart) ------------------
+    def _check_sensitivity(self, goal, observe):
+        """What :meth:`solve_sensitivity` needs, on the host and before any device call -> (nodes, functional):
+        ``functional(u)`` -> (J, p = dJ/du) for the nodal vector u."""
+        if self._periodic:
+            raise ValueError("solve_sensitivity has no boundary='periodic': the adjoint solve and the end gradients "
+                             "are written for Dirichlet, Neumann and Robin ends")
+        if self.fem_solver == "flux":
+            raise ValueError("solve_sensitivity needs fem_solver='bands' or 'pivot': the adjoint is the transposed "
+                             "tridiagonal solve, which the flux solve does not have")
+        self._check_nonlinear("solve_sensitivity")
+        if self.solver_id != ops.SOLVER_PRIMAL:
+            raise ValueError("solve_sensitivity needs solver=ops.SOLVER_PRIMAL: the derivatives are those of the P1 "
+                             "solve, the enhancement is not differentiated")
+        if self.element_degrees is not None:
+            raise ValueError("solve_sensitivity has no element_degrees: the derivatives are those of the P1 solve, "
+                             "which has no degree")
+        if (goal is None) == (observe is None):
+            raise ValueError("solve_sensitivity needs exactly one of goal (a callable j(x): J = int j u dx) and "
+                             "observe = (x_obs, d_obs) (J = 1/2 sum (u_h(x_i) - d_i)^2)")
+        m = self._default_mesh() if self.mesh is None else self.mesh
+        nodes = np.asarray(m.nodes, dtype=np.float64)
+        h = np.diff(nodes)
+        xi, w = np.polynomial.legendre.leggauss(int(self.nquad))
+        xi, w = 0.5 * (1.0 + xi), 0.5 * w
+        xq = nodes[:-1, None] + h[:, None] * xi[None, :]
+        eq = self._eq
+        named = [("rhs", eq.f), ("coef a", eq.a), ("convection", eq.b), ("reaction", eq.c)]
+        if goal is not None:
+            if not callable(goal):
+                raise ValueError("goal must be a callable j(x): the density of J(u) = int j u dx")
+            named.append(("goal", goal))
+        tabs = {}
+        for label, fn in named:
+            if fn is None:
+                continue
+            try:
+                t = np.broadcast_to(np.asarray(fn(xq), dtype=np.float64), xq.shape)
+            except ValueError:
+                raise ValueError(f"{label} must return one value per point ({list(xq.shape)} at the quadrature "
+                                 "points) or a value that broadcasts to them") from None
+            if not np.all(np.isfinite(t)):
+                raise ValueError(f"{label} is not finite at a quadrature point")
+            tabs[label] = t
+        self._check_finite(("the end data", np.asarray(self._gd_bc()[1], dtype=np.float64)))
+        if goal is not None:
+            # p = the P1 load of j by the rule of the assembly: J = int j u_h dx = p . u
+            p = np.zeros(nodes.size)
+            p[:-1] += h * ((tabs["goal"] * w) @ (1.0 - xi))
+            p[1:] += h * ((tabs["goal"] * w) @ xi)
+            return nodes, lambda u: (float(p @ u), p)
+        if not isinstance(observe, (tuple, list)) or len(observe) != 2:
+            raise ValueError("observe must be a pair (x_obs, d_obs)")
+        xo, d = (np.asarray(t, dtype=np.float64).reshape(-1) for t in observe)
+        if xo.size < 1 or xo.size != d.size:
+            raise ValueError(f"observe must hold as many points as data, at least one, got {xo.size} and {d.size}")
+        self._check_finite(("observe x_obs", xo), ("observe d_obs", d))
+        if xo.min() < nodes[0] or xo.max() > nodes[-1]:
+            raise ValueError(f"observe: every x_obs must lie in the mesh [{nodes[0]:.6g}, {nodes[-1]:.6g}]")
+        e = np.clip(np.searchsorted(nodes, xo, side="right") - 1, 0, nodes.size - 2)
+        t = (xo - nodes[e]) / h[e]
+
+        def misfit(u):
+            r = u[e] * (1.0 - t) + u[e + 1] * t - d
+            p = np.zeros(nodes.size)
+            np.add.at(p, e, r * (1.0 - t))
+            np.add.at(p, e + 1, r * t)
+            return 0.5 * float(r @ r), p
+        return nodes, misfit
+
+    def _adjoint_solve(self, bands, P, kinds, kappa):
+        """Z [nc, ne+1] of the TRANSPOSED bands with the loads P, zero end data and the primal's ends, through the
+        solver the primal took."""
+        ab = ops.adjoint_bands(bands)
+        if self.fem_solver == "pivot":
+            sub, sup = (ab["sub"], ab["sup"]) if "sub" in ab else (ab["off"], ab["off"])
+            z, info = ops.tridiag_pivot_solve_multi(ab["diag"], sub, sup, P, kinds, kappa, None, return_info=True)
+            bad = int(info.item())
+            if bad:
+                raise RuntimeError(f"adjoint system singular to working precision: the pivoting tridiagonal solve "
+                                   f"met {bad} pivot(s) that were zero or not finite")
+            return z
+        if "sub" in ab:
+            return ops.tridiag_ns_bc_solve_multi(ab["diag"], ab["sub"], ab["sup"], P, kinds, kappa, None)
+        return ops.tridiag_bc_solve_multi(ab["diag"], ab["off"], P, kinds, kappa, None)
+
+    def solve_sensitivity(self, goal=None, *, observe=None):
+        """Derivatives of a functional J of the P1 solution with respect to the data of the solve, by the adjoint
+        method: ONE :meth:`solve_fem`, ONE adjoint solve -- the same tridiagonal solver on the transposed bands
+        (``ops.adjoint_bands``) with load p = dJ/du, zero end data and the same end kinds and kappa -- and ONE
+        ``ops.p1_sensitivity``.  ``goal``: a callable j(x), J(u) = int j u_h dx by the quadrature rule of the assembly;
+        or ``observe=(x_obs, d_obs)``: the misfit J = 1/2 sum_i (u_h(x_i) - d_i)^2 at points inside the mesh (p is
+        formed on the host: a few hundred points at most).  Convection is handled: the transposed solve is what
+        :meth:`solve_goal` lacks.  Returns a :class:`Sensitivity`; ``fem_nodes`` and ``fem_values`` hold the primal
+        solution as after :meth:`solve_fem`.  Refused (``ValueError``, before any device call): ``boundary="periodic"``,
+        ``fem_solver="flux"``, ``nonlinear=``, a solver other than ``ops.SOLVER_PRIMAL``, ``element_degrees``, both or
+        neither of ``goal`` and ``observe``, data that are not finite where they are tabulated.  The mesh is not
+        differentiated."""
+        nodes, functional = self._check_sensitivity(goal, observe)
+        self.solve_fem()
+        x, u, bands = self._x_dev, self._u_dev, self.bands
+        value, p = functional(self.fem_values)
+        bnd = self._bnd
+        kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (tuple(bnd.kinds), tuple(bnd.kappa))
+        P = _to_dev(p[None, :], x.device)
+        Z = self._adjoint_solve(bands, P, kinds, kappa)
+        eq = self._eq
+        want = tuple(k for k, on in zip(ops.SENS_TABLES, (True, eq.b is not None, eq.c is not None, True)) if on)
+        res = ops.p1_sensitivity(x, u, Z, self.nquad, want=want, P=P, bands=bands, end_kinds=kinds)
+        host = _read_back(z=Z, **res)
+        return Sensitivity(value, {k: host[k][0] for k in want}, host["ends"][0], host["z"][0], nodes)
 
     def _adapt_rounds(self, tol, max_elements, max_iter, round_fn, start=None):
         """The round loop of every ``solve_adaptive`` mode; host logic only, so a scripted ``round_fn`` can drive it.

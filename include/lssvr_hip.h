@@ -1289,6 +1289,46 @@ int lssvr_wave_advance_host(const double* U_new_host, const double* U_host, cons
                             const double* phi_host, int64_t ne, int nc, int R, double dt, double beta, double gamma,
                             double* V_out_host, double* Acc_out_host, double* rhs_out_host);
 
+/*
+ * Adjoint sensitivities of the P1 solve of -(a u')' + b u' + c u = f (no reference counterpart).
+ * ADDITIVE to ABI 7: two new symbols, no existing entry, struct, constant or kernel instantiation changes,
+ * LSSVR_ABI_VERSION stays 7.
+ *
+ * For a functional J(u) with p = dJ/du (a nodal vector) the adjoint z solves the TRANSPOSED bands with load p: hand
+ * (diag, sup, sub) to lssvr_tridiag_ns_bc_solve_multi or lssvr_tridiag_pivot_solve_multi where the primal solve took
+ * (diag, sub, sup) -- symmetric bands are their own transpose --, with the primal's end kinds and kappa and with zero
+ * end data, so z = 0 at a Dirichlet end.  With h_e = x[e+1] - x[e], (xi_q, w_q) the nquad-point Gauss rule on [0, 1],
+ * du_e = u[e+1] - u[e], dz_e likewise, u_eq = u[e] (1 - xi_q) + u[e+1] xi_q and z_eq likewise:
+ *   dJ/da_quad[e][q]   = -(w_q / h_e) dz_e du_e        dJ/db_quad[e][q]   = -w_q z_eq du_e
+ *   dJ/dc_quad[e][q]   = -h_e w_q z_eq u_eq            dJ/drhs_quad[e][q] = +h_e w_q z_eq
+ *   Dirichlet end:  dJ/dg_0 = p_0 - sub[0] z_1,  dJ/dg_ne = p_ne - sup[ne-1] z_{ne-1},  dJ/dkappa = 0
+ *   Robin end:      dJ/dg = z_end,  dJ/dkappa = -z_end u_end
+ * (sub, sup: the bands as lssvr_p1_assemble_conv wrote them; for symmetric bands both are `off`).
+ *
+ * lssvr_p1_sensitivity -- ONE launch for nc pairs (U[j], Z[j]), 1 <= nc <= 8: x [ne+1], Z [nc][ne+1] case-major,
+ * U [nu][ne+1] with nu == nc, or nu == 1 for one primal solution shared by all cases (several functionals: rows of a
+ * Jacobian); all DEVICE arrays.  ga, gb, gc, gf receive the four gradients, each [nc][ne*nquad] in the layout of the
+ * input tables; a NULL one is skipped, stores included, and at least one must be given.  NONE of the tables a_quad,
+ * b_quad, c_quad, rhs_quad is an argument: given u and z the gradient does not depend on them.  out_ends [nc][4]
+ * (may be NULL) receives (dJ/dg_0, dJ/dg_ne, dJ/dkappa_0, dJ/dkappa_ne) per case, written by the same launch; it needs
+ * band_ends = {sub[0], sup[ne-1]} (device, 2 doubles) and the end kinds, and reads P [nc][ne+1] = dJ/du at a Dirichlet
+ * end (NULL: taken as zero).  Without out_ends neither P, band_ends nor the kinds are read.  The order of every
+ * operation is fixed (csrc/lssvr_sens.hpp), one thread per table entry, no reduction, no atomics, no synchronisation,
+ * no copy.  No output may be one of the inputs or another output.
+ * Return codes, each before any HIP call: LSSVR_ERR_SIZE for ne < 1, nc outside [1, 8], nu other than 1 or nc, or an
+ * unknown end kind with out_ends; LSSVR_ERR_QUAD for nquad outside [1, 5]; LSSVR_ERR_NULL for a missing x, U or Z, for
+ * four NULL outputs, and for out_ends without band_ends.
+ *
+ * lssvr_p1_sensitivity_host -- the same routines on HOST arrays: no device is touched.  Bit for bit the device's values.
+ */
+int lssvr_p1_sensitivity(const double* x, int64_t ne, int nquad, const double* U, int nu, const double* Z, int nc,
+                         double* ga, double* gb, double* gc, double* gf, const double* P, const double* band_ends,
+                         int kind_left, int kind_right, double* out_ends, void* stream);
+int lssvr_p1_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* U_host, int nu,
+                              const double* Z_host, int nc, double* ga_host, double* gb_host, double* gc_host,
+                              double* gf_host, const double* P_host, const double* band_ends_host, int kind_left,
+                              int kind_right, double* out_ends_host);
+
 #ifdef __cplusplus
 }
 #endif
