@@ -13,6 +13,7 @@ from .solver import (  # noqa: F401
     FEMLSSVRPrimalSolver,
     GoalEstimate,
     Sensitivity,
+    TransientSensitivity,
     TransientSolution,
     WaveSolution,
     SinRHS,

@@ -208,6 +208,14 @@ SIGNATURES = {
     "lssvr_p1_sensitivity": _sig(_MESH, [_c_dp, _c_int, _c_dp, _c_int], [_c_dp] * 6, [_c_int, _c_int, _c_dp], _STREAM),
     "lssvr_p1_sensitivity_host": _sig([_c_hd, _c_i64, _c_int, _c_hd, _c_int, _c_hd, _c_int], [_c_hd] * 6,
                                       [_c_int, _c_int, _c_hd]),
+    # adjoint sensitivities of the BDF loop (additive to ABI 7): x, ne, nquad, Utraj, Z, n0, m, inv_dt, coef_host, phi,
+    # R, ga, gc, grho, gf, accumulate, Brows, band_ends, band_mask, kind_left, kind_right, out_g, out_kappa
+    "lssvr_transient_sensitivity": _sig(_MESH, [_c_dp, _c_dp, _c_i64, _c_int, _c_dbl, _c_hd, _c_dp, _c_int],
+                                        [_c_dp] * 4, [_c_int, _c_dp, _c_dp, _c_int, _c_int, _c_int, _c_dp, _c_dp],
+                                        _STREAM),
+    "lssvr_transient_sensitivity_host": _sig([_c_hd, _c_i64, _c_int, _c_hd, _c_hd, _c_i64, _c_int, _c_dbl, _c_hd,
+                                              _c_hd, _c_int], [_c_hd] * 4,
+                                             [_c_int, _c_hd, _c_hd, _c_int, _c_int, _c_int, _c_hd, _c_hd]),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

@@ -2009,4 +2009,66 @@ int lssvr_p1_sensitivity_host(const double* x_host, int64_t ne, int nquad, const
   return LSSVR_OK;
 }
 
+// Adjoint sensitivities of the BDF loop (timestep_sens.hip).  The device and the host entry share one validated binding.
+static int bind_ts_sens(lssvr::TsSensArgs& a, const double* x, int64_t ne, int nquad, const double* Utraj,
+                        const double* Z, int64_t n0, int m, double inv_dt, const double* coef_host, const double* phi,
+                        int R, double* ga, double* gc, double* grho, double* gf, int accumulate, const double* Brows,
+                        const double* band_ends, int band_mask, int kind_left, int kind_right,
+                        double* out_g, double* out_kappa) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (m < 1 || m > lssvr::kTsSensMaxSteps) return fail(LSSVR_ERR_SIZE, "m = %d outside [1, 8]", m);
+  if (n0 < 1) return fail(LSSVR_ERR_SIZE, "n0 = %lld: the first adjoint step of a chunk is >= 1", (long long)n0);
+  if (R < 0 || R > lssvr::kTsSensMaxTerms) return fail(LSSVR_ERR_SIZE, "R = %d outside [0, 8]", R);
+  if (R == 0 && gf) return fail(LSSVR_ERR_SIZE, "R = 0 is allowed only with gf NULL");
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  if (!x || !Utraj || !Z || !coef_host) return fail(LSSVR_ERR_NULL, "x, Utraj, Z, coef_host must be non-NULL");
+  if (!ga && !gc && !grho && !gf && !out_g)
+    return fail(LSSVR_ERR_NULL, "one of ga, gc, grho, gf, out_g must be non-NULL");
+  if (gf && !phi) return fail(LSSVR_ERR_NULL, "phi must be non-NULL with gf");
+  if (!out_g != !out_kappa) return fail(LSSVR_ERR_NULL, "out_g and out_kappa go together: both or neither");
+  a = lssvr::TsSensArgs{};
+  if (out_g) {
+    if (!Brows || !band_ends) return fail(LSSVR_ERR_NULL, "Brows and band_ends must be non-NULL with out_g");
+    if (const int rc = check_kinds(kind_left, kind_right)) return rc;
+    if (band_mask < 0 || band_mask >> m)
+      return fail(LSSVR_ERR_SIZE, "band_mask = %d has bits beyond the m = %d steps", band_mask, m);
+    for (int i = 0; i < m; ++i) a.band_row[i] = (band_mask >> i) & 1;
+  }
+  a.x = x, a.Utraj = Utraj, a.Z = Z, a.Brows = Brows, a.phi = phi, a.band_ends = band_ends;
+  a.ne = ne, a.n0 = n0, a.nquad = nquad, a.m = m, a.R = R, a.accumulate = accumulate != 0;
+  a.kind[0] = kind_left, a.kind[1] = kind_right;
+  a.inv_dt = inv_dt;
+  for (int i = 0; i < m; ++i)
+    for (int k = 0; k < 3; ++k) a.coef[i][k] = coef_host[3 * i + k];
+  a.ga = ga, a.gc = gc, a.grho = grho, a.gf = gf, a.out_g = out_g, a.out_kappa = out_kappa;
+  return LSSVR_OK;
+}
+
+int lssvr_transient_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj, const double* Z,
+                                int64_t n0, int m, double inv_dt, const double* coef_host, const double* phi, int R,
+                                double* ga, double* gc, double* grho, double* gf, int accumulate, const double* Brows,
+                                const double* band_ends, int band_mask, int kind_left, int kind_right, double* out_g,
+                                double* out_kappa, void* stream) {
+  lssvr::TsSensArgs a;
+  const int rc = bind_ts_sens(a, x, ne, nquad, Utraj, Z, n0, m, inv_dt, coef_host, phi, R, ga, gc, grho, gf, accumulate,
+                              Brows, band_ends, band_mask, kind_left, kind_right, out_g, out_kappa);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::ts_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "ts_sensitivity");
+}
+
+int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
+                                     const double* Z_host, int64_t n0, int m, double inv_dt, const double* coef_host,
+                                     const double* phi_host, int R, double* ga_host, double* gc_host,
+                                     double* grho_host, double* gf_host, int accumulate, const double* Brows_host,
+                                     const double* band_ends_host, int band_mask, int kind_left, int kind_right,
+                                     double* out_g_host, double* out_kappa_host) {
+  lssvr::TsSensArgs a;
+  const int rc = bind_ts_sens(a, x_host, ne, nquad, Utraj_host, Z_host, n0, m, inv_dt, coef_host, phi_host, R, ga_host,
+                              gc_host, grho_host, gf_host, accumulate, Brows_host, band_ends_host, band_mask,
+                              kind_left, kind_right, out_g_host, out_kappa_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::ts_sensitivity_host(a);          // (nquad is checked above: the rule exists)
+  return LSSVR_OK;
+}
+
 }  // extern "C"

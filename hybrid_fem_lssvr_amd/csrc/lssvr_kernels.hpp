@@ -563,6 +563,35 @@ struct SensArgs {
 hipError_t p1_sensitivity(const SensArgs& a, hipStream_t s);
 bool p1_sensitivity_host(const SensArgs& a);     // false: no such quadrature rule
 
+// timestep_sens.hip: adjoint sensitivities of the BDF loop.  One chunk of m <= 8 consecutive
+// adjoint steps n0 .. n0+m-1, summed over the chunk into the tables.  Every array that runs over time is handed over
+// whole and indexed with the step n: Utraj, phi, out_g.  The rows of Z and Brows, coef and band_row stand in the order
+// of the backward sweep: row i belongs to step n0 + m - 1 - i.
+constexpr int kTsSensMaxSteps = 8;   // steps per chunk
+constexpr int kTsSensMaxTerms = 8;   // terms of the separable forcing (TS_MAX_TERMS of the forward loop)
+struct TsSensArgs {
+  const double* x;                  // nodes [ne+1]
+  const double* Utraj;              // the forward trajectory [N+1][ne+1]: row n = u^n; rows n0-2 .. n0+m-1 are read
+  const double* Z;                  // [m][ne+1]: the adjoint states of the chunk
+  const double* Brows;              // [m][ne+1]: their right-hand sides; read for out_g at a Dirichlet end
+  const double* phi;                // [N][R]: row n-1 = phi(t_n), the table the forward loop feeds ts_rhs from; gf only
+  const double* band_ends;          // [2][2]: {sub[0], sup[ne-1]} of two step matrices; read for out_g only
+  int64_t ne, n0;
+  int nquad, m, R, accumulate;      // accumulate: the sums continue from what the outputs hold (0: from 0)
+  int kind[2];                      // LSSVR_END_*; read for out_g only
+  int band_row[kTsSensMaxSteps];    // which row of band_ends is step row i's matrix
+  double inv_dt;
+  double coef[kTsSensMaxSteps][3];  // (alpha, beta0, beta1) of step row i
+  double* ga;                       // dJ/da_quad, dJ/dc_quad, dJ/drho_quad [ne*nquad]; nullptr: skipped
+  double* gc;
+  double* grho;
+  double* gf;                       // dJ/df_quad [R][ne*nquad]
+  double* out_g;                    // [N+1][2]: rows n0 .. n0+m-1 are written; nullptr: no end gradients
+  double* out_kappa;                // [2]
+};
+hipError_t ts_sensitivity(const TsSensArgs& a, hipStream_t s);
+bool ts_sensitivity_host(const TsSensArgs& a);   // false: no such quadrature rule
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

@@ -2275,6 +2275,97 @@ def p1_sensitivity(x, U, Z, nquad=2, *, want=SENS_TABLES, P=None, bands=None,
     return res
 
 
+# ---- adjoint sensitivities of the BDF loop -------------------------------------------------------
+TS_SENS_TABLES = ("a", "c", "rho", "f")     # d/d a_quad, c_quad, rho_quad, f_quad[r]: the keys of ``want`` and the result
+TS_SENS_CHUNK = 8                           # most adjoint steps of one launch
+
+
+def ts_sensitivity(x, Utraj, Z, n0, coef, inv_dt, nquad=2, *, want=TS_SENS_TABLES, phi=None, Brows=None, band_ends=None,
+                   band_rows=None, end_kinds=(END_DIRICHLET, END_DIRICHLET), accumulate=False, out=None, stream=None):
+    """``lssvr_transient_sensitivity``: the gradients of J with respect to the tables of the BDF loop of :func:`ts_rhs`, summed
+    over a CHUNK of m <= 8 consecutive adjoint steps n0 .. n0+m-1, in ONE launch.  x float64[ne+1]; Utraj
+    float64[N+1, ne+1] the whole stored trajectory (row n = u^n, N >= n0+m-1); Z float64[m, ne+1] the adjoint states of
+    the chunk IN THE ORDER OF THE SWEEP: row i belongs to step n0+m-1-i; ``coef``: m triples (alpha, beta0, beta1), the
+    BDF coefficients of step row i (host numbers: they travel in the launch's arguments); phi float64[N, R] the whole
+    table of the forward loop (row n-1 = phi(t_n)), needed for "f" only.  ``want``: which of "a", "c", "rho", "f" to
+    compute; a table left out is neither computed nor stored, and ``want=()`` is allowed with the end gradients.
+    ``Brows`` (float64[m, ne+1], the adjoint right-hand sides of the chunk, in Z's order) asks for the end gradients
+    too: with ``band_ends`` float64[2, 2] = {sub[0], sup[ne-1]} of two step matrices, ``band_rows`` (m values 0 / 1:
+    which of the two is step row i's; ``None``: 0) and ``end_kinds``, rows n0 .. n0+m-1 of "g" float64[N+1, 2] and
+    "kappa" float64[2] are written by the same launch.  ``accumulate``: every sum (the tables and "kappa") continues
+    from what ``out`` holds instead of from 0 -- a sweep gives the same bits however it is cut into chunks -- and then
+    ``out`` must hold every wanted buffer.  Returns a dict: "a", "c", "rho" -> float64[ne, nquad], "f" ->
+    float64[R, ne, nquad], "g", "kappa".  ``out``: a dict of buffers to write into, by those keys ("g" is never
+    allocated here: its other rows are the caller's).  No synchronisation and no copy; every value is computed in a
+    fixed order (bitwise reproducible)."""
+    lib = _capi.load()
+    for nm, t in (("x", x), ("Utraj", Utraj), ("Z", Z)):
+        _dev(t, nm)
+    ne = _nodes(x, "x")
+    nquad, n0 = int(nquad), int(n0)
+    if not 1 <= nquad <= 5:
+        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
+    want = tuple(want)
+    if len(set(want)) != len(want) or any(k not in TS_SENS_TABLES for k in want):
+        raise ValueError(f"want must name tables of {TS_SENS_TABLES}, each once, got {want!r}")
+    if not want and Brows is None:
+        raise ValueError("nothing to compute: want is empty and Brows is not given")
+    m = _block(ne, "m", Z=Z)
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64))
+    if coef.shape != (m, 3) or not np.all(np.isfinite(coef)):
+        raise ValueError(f"coef must be m = {m} finite triples (alpha, beta0, beta1), got shape {list(coef.shape)}")
+    (inv_dt,) = _finite(inv_dt=inv_dt)
+    if n0 < 1:
+        raise ValueError(f"n0 must be >= 1, got {n0}")
+    if Utraj.dim() != 2 or Utraj.shape[1] != ne + 1 or Utraj.shape[0] < n0 + m:
+        raise ValueError(f"Utraj must be [N+1, ne+1] with N >= n0+m-1 = {n0 + m - 1} and ne+1 = {ne + 1}, got "
+                         f"{list(Utraj.shape)}")
+    N = int(Utraj.shape[0]) - 1
+    ins, R = {"Utraj": Utraj, "Z": Z}, 0
+    if "f" in want:
+        if phi is None:
+            raise ValueError("phi is needed for the table 'f'")
+        _dev(phi, "phi")
+        if phi.dim() != 2 or phi.shape[0] != N or not 1 <= phi.shape[1] <= TS_MAX_TERMS:
+            raise ValueError(f"phi must be [N, R] = [{N}, 1 .. {TS_MAX_TERMS}], got {list(phi.shape)}")
+        R = int(phi.shape[1])
+        ins["phi"] = phi
+    out = {} if out is None else out
+    accumulate = bool(accumulate)
+    shapes = {k: ((R, ne, nquad) if k == "f" else (ne, nquad)) for k in want}
+    mask, kinds = 0, (END_DIRICHLET, END_DIRICHLET)
+    if Brows is not None:
+        if band_ends is None:
+            raise ValueError("band_ends is needed with Brows")
+        for nm, t in (("Brows", Brows), ("band_ends", band_ends)):
+            _dev(t, nm)
+        if Brows.shape != Z.shape:
+            raise ValueError(f"Brows must have the shape of Z {list(Z.shape)}, got {list(Brows.shape)}")
+        if tuple(band_ends.shape) != (2, 2):
+            raise ValueError(f"band_ends must be [2, 2], got {list(band_ends.shape)}")
+        rows = [0] * m if band_rows is None else [int(r) for r in band_rows]
+        if len(rows) != m or any(r not in (0, 1) for r in rows):
+            raise ValueError(f"band_rows must be m = {m} values 0 or 1, got {band_rows!r}")
+        mask = sum(r << i for i, r in enumerate(rows))
+        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
+        ins.update(Brows=Brows, band_ends=band_ends)
+        if out.get("g") is None:
+            raise ValueError("out['g'] (float64[N+1, 2]) is needed with Brows: the chunk writes its rows of it")
+        shapes.update(g=(N + 1, 2), kappa=(2,))
+    if accumulate and any(out.get(k) is None for k in shapes):
+        raise ValueError("accumulate needs every buffer it continues from in out")
+    res = {k: _out(out.get(k), f"out[{k!r}]", shape, x) for k, shape in shapes.items()}
+    _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
+    _same_device(x, **ins)
+    rc = lib.lssvr_transient_sensitivity(_ptr(x), ne, nquad, _ptr(Utraj), _ptr(Z), n0, m, inv_dt,
+                                  coef.ctypes.data_as(_capi._c_hd), _ptr(phi) if "f" in want else None, R,
+                                  *(_ptr(res.get(k)) for k in TS_SENS_TABLES), int(accumulate), _ptr(Brows),
+                                  _ptr(band_ends), mask, *kinds, _ptr(res.get("g")), _ptr(res.get("kappa")),
+                                  _stream(stream))
+    _capi.check(rc, "lssvr_transient_sensitivity")
+    return res
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

@@ -436,6 +436,23 @@ class Sensitivity:
         self.adjoint, self.nodes = adjoint, nodes
 
 
+class TransientSensitivity:
+    """What :meth:`FEMLSSVRPrimalSolver.solve_transient_sensitivity` returns for a functional J of the BDF trajectory:
+    ``value`` = J and its derivatives with respect to the data of the loop, as numpy -- ``d_coef``, ``d_reaction``,
+    ``d_weight`` [ne, nquad]: dJ/d(a, c, rho at quadrature point q of element e) (without ``coef`` / ``reaction`` /
+    ``weight`` the derivative at the table a = 1 / c = 0 / rho = 1); ``d_forcing`` [R, ne, nquad]: dJ/df_r there;
+    ``d_u0`` [ne+1]: dJ/du0 at the nodes (0 at a Dirichlet end: the start is g(0) there); ``d_end_values``
+    [nsteps+1, 2]: dJ/dg(t_n) of the left and right end datum, row n for t_n (row 0: the start of a Dirichlet end);
+    ``d_kappa`` [2] (0 at a Dirichlet end); ``times`` [nsteps+1] and ``nodes``.  Neither the mesh nor dt is
+    differentiated."""
+
+    def __init__(self, value, tables, d_u0, d_end_values, d_kappa, times, nodes):
+        self.value = float(value)
+        self.d_coef, self.d_reaction, self.d_weight, self.d_forcing = (tables[k] for k in ops.TS_SENS_TABLES)
+        self.d_u0, self.d_end_values, self.d_kappa = d_u0, d_end_values, d_kappa
+        self.times, self.nodes = times, nodes
+
+
 def _evaluate_item(items, method, what, i, x, deriv):
     """``evaluate`` of the solution classes below: item ``i`` of their :class:`EnhancedSolution` list at ``x``."""
     if not items:
@@ -1879,6 +1896,177 @@ class FEMLSSVRPrimalSolver:
                 raise RuntimeError(f"solve_transient: step {i + 1} did not converge in {iters} Newton iteration(s) to "
                                    f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
         return TransientSolution(p.times[steps].copy(), host["nodal"], enhanced, bands, newton)
+
+    # ---- adjoint sensitivities of the BDF loop (no reference counterpart) ---------------------
+    def _check_transient_sensitivity(self, p, goal, goal_steps, goal_weights, observe, max_state_bytes):
+        """The functional of :meth:`solve_transient_sensitivity` on the plan ``p`` of :meth:`_check_transient`, on the
+        host and before any device call -> (steps, rows, functional): the ascending steps n with p_n != 0, ``rows``
+        [len(steps), ne+1] for a goal (None for a misfit, whose rows need the trajectory), and
+        ``functional(U_steps)`` -> (J, rows) for the nodal states at those steps."""
+        nsteps, nodes = len(p.times) - 1, p.nodes
+        if (goal is None) == (observe is None):
+            raise ValueError("solve_transient_sensitivity needs exactly one of goal (a callable j(x): J = sum_k w_k int "
+                             "j u^{n_k} dx) and observe = (steps, x_obs, d_obs) (J = 1/2 sum (u^{n_k}(x_i) - d_ki)^2)")
+        need = (nsteps + 1) * nodes.size * 8
+        if need > max_state_bytes:
+            raise ValueError(f"the stored trajectory needs (nsteps+1)(ne+1) 8 = {need} bytes > max_state_bytes = "
+                             f"{max_state_bytes}: checkpointing (recomputing the trajectory in pieces) is not built")
+
+        def checked_steps(steps, what):
+            steps = list(steps)
+            if not steps or any(isinstance(s, bool) or int(s) != s or not 1 <= int(s) <= nsteps for s in steps):
+                raise ValueError(f"{what} must be step indices in 1 .. nsteps = {nsteps}, got {steps!r}")
+            steps = [int(s) for s in steps]
+            if len(set(steps)) != len(steps):
+                raise ValueError(f"{what} must not name a step twice, got {steps!r}")
+            return steps
+        h = np.diff(nodes)
+        if goal is not None:
+            if not callable(goal):
+                raise ValueError("goal must be a callable j(x): the density of J = sum_k w_k int j u^{n_k} dx")
+            steps = checked_steps([nsteps] if goal_steps is None else goal_steps, "goal_steps")
+            wts = np.ones(len(steps)) if goal_weights is None else np.asarray(goal_weights, dtype=np.float64).reshape(-1)
+            if wts.size != len(steps):
+                raise ValueError(f"goal_weights must hold one weight per goal step ({len(steps)}), got {wts.size}")
+            self._check_finite(("goal_weights", wts))
+            xi, w = np.polynomial.legendre.leggauss(int(self.nquad))
+            xi, w = 0.5 * (1.0 + xi), 0.5 * w
+            xq = nodes[:-1, None] + h[:, None] * xi[None, :]
+            try:
+                j = np.broadcast_to(np.asarray(goal(xq), dtype=np.float64), xq.shape)
+            except ValueError:
+                raise ValueError(f"goal must return one value per point ({list(xq.shape)} at the quadrature points) or "
+                                 "a value that broadcasts to them") from None
+            if not np.all(np.isfinite(j)):
+                raise ValueError("goal is not finite at a quadrature point")
+            # the P1 load of j by the rule of the assembly: int j u_h dx = load . u
+            load = np.zeros(nodes.size)
+            load[:-1] += h * ((j * w) @ (1.0 - xi))
+            load[1:] += h * ((j * w) @ xi)
+            order = np.argsort(steps)
+            steps, rows = [steps[i] for i in order], wts[order, None] * load[None, :]
+            return steps, rows, lambda U: (float(np.sum(rows * U)), rows)
+        if goal_steps is not None or goal_weights is not None:
+            raise ValueError("goal_steps and goal_weights belong to goal=")
+        if not isinstance(observe, (tuple, list)) or len(observe) != 3:
+            raise ValueError("observe must be a triple (steps, x_obs, d_obs)")
+        steps = checked_steps(observe[0], "observe steps")
+        xo = np.asarray(observe[1], dtype=np.float64).reshape(-1)
+        d = np.asarray(observe[2], dtype=np.float64)
+        if xo.size < 1 or d.shape != (len(steps), xo.size):
+            raise ValueError(f"observe: d_obs must be [len(steps), nobs] = [{len(steps)}, {xo.size}] with at least one "
+                             f"point, got {list(d.shape)}")
+        self._check_finite(("observe x_obs", xo), ("observe d_obs", d))
+        if xo.min() < nodes[0] or xo.max() > nodes[-1]:
+            raise ValueError(f"observe: every x_obs must lie in the mesh [{nodes[0]:.6g}, {nodes[-1]:.6g}]")
+        order = np.argsort(steps)
+        steps, d = [steps[i] for i in order], d[order]
+        e = np.clip(np.searchsorted(nodes, xo, side="right") - 1, 0, nodes.size - 2)
+        t = (xo - nodes[e]) / h[e]
+
+        def misfit(U):
+            r = U[:, e] * (1.0 - t) + U[:, e + 1] * t - d
+            rows = np.zeros(U.shape)
+            for k in range(len(steps)):
+                np.add.at(rows[k], e, r[k] * (1.0 - t))
+                np.add.at(rows[k], e + 1, r[k] * t)
+            return 0.5 * float(np.sum(r * r)), rows
+        return steps, None, misfit
+
+    def solve_transient_sensitivity(self, u0, t_end, *, nsteps, scheme="bdf2", weight=None, forcing=None, end_data=None,
+                                    goal=None, goal_steps=None, goal_weights=None, observe=None,
+                                    max_state_bytes=2 ** 31):
+        """Derivatives of a functional J of the trajectory of :meth:`solve_transient` (same ``u0``, ``t_end``,
+        ``nsteps``, ``scheme``, ``weight``, ``forcing``, ``end_data``) with respect to the data of the loop, by the
+        discrete adjoint: exact for the discrete scheme, at the cost of one more loop of the same length.  ``goal``: a
+        callable j(x), J = sum_k w_k int j u^{n_k} dx by the quadrature rule of the assembly, over ``goal_steps``
+        (default ``[nsteps]``) with ``goal_weights`` (default ones); or ``observe=(steps, x_obs, d_obs)`` with d_obs
+        [len(steps), nobs]: the misfit J = 1/2 sum_k sum_i (u^{n_k}(x_i) - d_ki)^2 at points inside the mesh.
+
+        The forward loop is :meth:`solve_transient`'s, bit for bit, writing every u^n into a stored trajectory
+        [nsteps+1, ne+1].  The rows p_n = dJ/du^n that are not zero are uploaded once (for a misfit they are formed on
+        the host from the observed steps, one read-back between the loops).  The backward sweep runs n = nsteps .. 1
+        in chunks of up to 8 steps: per step ``ops.ts_rhs`` (U0 = lambda^{n+1}, U1 = lambda^{n+2}, the load p_n,
+        phi = 1, coefficients (beta0_{n+1}, beta1_{n+2})) and ``ops.tridiag_bc_solve_multi`` on the forward loop's
+        bands with zero end data, into the chunk's rows; then ONE ``ops.ts_sensitivity`` per chunk adds the chunk to
+        the tables.  Two chunk buffers alternate, so lambda^{n+1}, lambda^{n+2} of a chunk's first steps are still in
+        the other.  One last ``ops.ts_rhs`` gives B_0 = dJ/du0, and one read-back fetches everything.  Neither loop
+        synchronises or copies from the host.  Returns a :class:`TransientSensitivity`; the solver's attributes are
+        left as they are.
+
+        Refused (``ValueError``, before any device call): what :meth:`solve_transient` refuses (convection,
+        ``boundary="periodic"``, a ``fem_solver`` other than "bands", ``element_degrees``, a solver other than
+        ``ops.SOLVER_PRIMAL``), ``nonlinear=``, both or neither of ``goal`` and ``observe``, a step outside
+        1 .. nsteps or named twice, data of the wrong shape or not finite, and a trajectory of more than
+        ``max_state_bytes``: checkpointing is not built."""
+        self._check_nonlinear("solve_transient_sensitivity")
+        p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, None, False)
+        jsteps, rows, functional = self._check_transient_sensitivity(p, goal, goal_steps, goal_weights, observe,
+                                                                     max_state_bytes)
+        kinds, kappa, q = p.kinds, p.kappa, p.quad
+        # ---- the device from here on
+        torch = _torch()
+        nsteps, ne, inv_dt = int(nsteps), p.nodes.size - 1, 1.0 / p.dt
+        bdf1, bdf = ops.BDF["bdf1"], ops.BDF[scheme]
+        alphas = {bdf1[0], bdf[0]}
+        D = self._time_setup(p, False, [("mass", False, q["rho"]),
+                                        *((al, True, q["c"] + al * q["rho"] / p.dt) for al in alphas)],
+                             nbuf=nsteps + 1)
+        dev, x, U, b, loads, work = D.dev, D.x, D.U, D.b, D.loads, D.work
+        phi, g = D.phi, D.g[1:]                                        # row n - 1: the step that ends at t_n
+        md, mo = D.bands["mass"]
+
+        def coefficients(n):
+            """(alpha_n, beta0_n, beta1_n); zeros beyond the last step."""
+            return (0.0, 0.0, 0.0) if n > nsteps else bdf1 if n == 1 else bdf
+
+        # the forward loop of solve_transient, every state kept: row n of U is u^n
+        for n in range(1, nsteps + 1):
+            al, b0, b1 = coefficients(n)
+            ops.ts_rhs(md, mo, U[n - 1:n], None if b1 == 0.0 else U[n - 2:n - 1], loads, phi[n - 1:n], b0, b1, inv_dt,
+                       out=b)
+            ops.tridiag_bc_solve_multi(*D.bands[al], b, kinds, kappa, g[n - 1:n], out=U[n:n + 1], work=work)
+        jidx = torch.as_tensor(jsteps, device=dev)
+        if rows is None:
+            _, rows = functional(_read_back(u=U[jidx])["u"])
+        # the rows p_n that are not zero, and a zero row for every other step (and for lambda^{N+1}, lambda^{N+2})
+        P = _to_dev(np.concatenate([rows, np.zeros((1, ne + 1))]), dev)
+        prow = {n: k for k, n in enumerate(jsteps)}
+        zero, one = P[len(jsteps):], torch.ones((1, 1), dtype=torch.float64, device=dev)
+        chunk = ops.TS_SENS_CHUNK
+        Zb, Bb = (torch.empty((2, chunk, ne + 1), dtype=torch.float64, device=dev) for _ in range(2))
+        band_ends = torch.stack([torch.stack((D.bands[al][1][0], D.bands[al][1][ne - 1])) for al in (bdf1[0], bdf[0])])
+        out = dict(g=torch.zeros((nsteps + 1, 2), dtype=torch.float64, device=dev))
+        lam1, lam2 = zero, zero                                        # lambda^{n+1}, lambda^{n+2}
+        hi, side = nsteps, 0
+        # the backward sweep: launches on the current stream only
+        while hi >= 1:
+            m = min(chunk, hi)
+            Z, B = Zb[side, :m], Bb[side, :m]
+            for i in range(m):
+                n = hi - i
+                b0, b1 = coefficients(n + 1)[1], coefficients(n + 2)[2]
+                k = prow.get(n, len(jsteps))
+                ops.ts_rhs(md, mo, lam1, None if b1 == 0.0 else lam2, P[k:k + 1], one, b0, b1, inv_dt, out=B[i:i + 1])
+                ops.tridiag_bc_solve_multi(*D.bands[coefficients(n)[0]], B[i:i + 1], kinds, kappa, None,
+                                           out=Z[i:i + 1], work=work)
+                lam1, lam2 = Z[i:i + 1], lam1
+            steps = range(hi, hi - m, -1)
+            out = ops.ts_sensitivity(x, U, Z, hi - m + 1, [coefficients(n) for n in steps], inv_dt, self.nquad, phi=phi,
+                                     Brows=B, band_ends=band_ends, band_rows=[0 if n == 1 else 1 for n in steps],
+                                     end_kinds=kinds, accumulate=hi < nsteps, out=out)
+            hi, side = hi - m, 1 - side
+        b0, b1 = coefficients(1)[1], coefficients(2)[2]
+        ops.ts_rhs(md, mo, lam1, None if b1 == 0.0 else lam2, zero, one, b0, b1, inv_dt, out=b)       # B_0
+        host = _read_back(b0=b, u=U[jidx], **out)
+        value, _ = functional(host["u"])
+        d_u0, d_g = host["b0"][0].copy(), host["g"].copy()
+        for s, end in ((0, 0), (1, -1)):
+            if kinds[s] == ops.END_DIRICHLET:
+                d_g[0, s] = d_u0[end]
+                d_u0[end] = 0.0
+        return TransientSensitivity(value, {k: host[k].copy() for k in ops.TS_SENS_TABLES}, d_u0, d_g,
+                                    host["kappa"].copy(), p.times.copy(), p.nodes)
 
     # ---- adaptive time stepping (no reference counterpart; DESIGN.md section 30) ----------------------------------
     def _check_adaptive(self, u0, t_end, rtol, atol, dt0, t_out, dt_min, dt_max, max_steps, weight, forcing, end_data,

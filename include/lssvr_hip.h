@@ -1329,6 +1329,59 @@ int lssvr_p1_sensitivity_host(const double* x_host, int64_t ne, int nquad, const
                               double* gf_host, const double* P_host, const double* band_ends_host, int kind_left,
                               int kind_right, double* out_ends_host);
 
+/*
+ * Adjoint sensitivities of the BDF loop of rho u_t - (a u')' + c u = f(x, t) (no reference counterpart; DESIGN.md section
+ * 32).  ADDITIVE to ABI 7: two new symbols, no existing entry, struct, constant or kernel instantiation changes,
+ * LSSVR_ABI_VERSION stays 7.
+ *
+ * The forward loop is that of lssvr_ts_rhs: step n = 1 .. N solves A_n u^n = (1/dt) M (beta0_n u^{n-1} + beta1_n u^{n-2})
+ * + sum_r phi_r(t_n) L_r + end terms with A_n = K + (alpha_n/dt) M.  For J = sum_n p_n . u^n the adjoint states run
+ * backwards, lambda^{N+1} = lambda^{N+2} = 0:
+ *   B_n = p_n + (1/dt) M (beta0_{n+1} lambda^{n+1} + beta1_{n+2} lambda^{n+2})      -- lssvr_ts_rhs with U0 = lambda^{n+1},
+ *                                                   U1 = lambda^{n+2}, loads = the row p_n, phi = 1
+ *   A_n lambda^n = B_n, the forward loop's end kinds and kappa, zero end data      -- lssvr_tridiag_bc_solve_multi
+ * (K and M are symmetric: no transposition).  This entry turns a CHUNK of m <= 8 consecutive adjoint steps
+ * n0 .. n0+m-1 into gradients, summed over the chunk.  With the notation of lssvr_p1_sensitivity and w^n = (alpha_n u^n -
+ * beta0_n u^{n-1} - beta1_n u^{n-2}) / dt, the nodal BDF difference of lssvr_ts_source_table:
+ *   dJ/da_quad[e][q]   = -sum_n (w_q / h_e) dlambda^n_e du^n_e      dJ/dc_quad[e][q]      = -sum_n h_e w_q lambda^n_eq u^n_eq
+ *   dJ/drho_quad[e][q] = -sum_n h_e w_q lambda^n_eq w^n_eq          dJ/df_quad[r][e][q]   = +sum_n phi_r(t_n) h_e w_q lambda^n_eq
+ *   Dirichlet end:  dJ/dg(t_n) = B_n[end] - aoff_n[end] lambda^n[inner],  dJ/dkappa = 0
+ *   Robin end:      dJ/dg(t_n) = lambda^n[end],                           dJ/dkappa = -sum_n lambda^n[end] u^n[end]
+ * (dJ/du0 and dJ/dg(t_0) are rows of B_0, one more lssvr_ts_rhs: no kernel.)
+ *
+ * lssvr_transient_sensitivity -- ONE launch per chunk.  DEVICE arrays: x [ne+1]; Utraj [N+1][ne+1], the whole stored trajectory
+ * (row n = u^n; rows max(n0-2, 0) .. n0+m-1 are read, u^{-1} counts as 0); Z [m][ne+1] and Brows [m][ne+1], the adjoint
+ * states of the chunk and their right-hand sides IN THE ORDER OF THE SWEEP: row i belongs to step n0+m-1-i; phi [N][R],
+ * the whole table the forward loop fed lssvr_ts_rhs from (row n-1 = phi(t_n); read for gf only), 0 <= R <= 8, R = 0
+ * only with gf NULL.  coef_host: a HOST array [m][3], (alpha_n, beta0_n, beta1_n) of step row i, copied into the launch's
+ * arguments.  ga, gc, grho [ne*nquad] and gf [R][ne*nquad] receive the gradients in the layout of the input tables; a
+ * NULL one is skipped, stores included.  accumulate = 0: every sum starts from 0 (the first chunk of a sweep needs no
+ * memset); 1: it continues from what the output holds, so a sweep gives the same bits however it is cut into chunks.
+ * out_g [N+1][2] and out_kappa [2] (both or neither) receive the end gradients, written by the same launch: rows
+ * n0 .. n0+m-1 of out_g, and out_kappa under the same accumulate flag; they need Brows, the end kinds, band_ends [2][2]
+ * = {sub[0], sup[ne-1]} of two step matrices (device; one per alpha) and band_mask, whose bit i says which of the two
+ * is the matrix of step row i.  Without out_g none of these is read, and the four tables may then all be NULL only if
+ * out_g is given.  The order of every operation is fixed (csrc/lssvr_ts_sens.hpp), one thread per table entry, no
+ * reduction, no atomics, no synchronisation, no copy.  No output may be one of the inputs or another output.
+ * Return codes, each before any HIP call: LSSVR_ERR_SIZE for ne < 1, m outside [1, 8], n0 < 1, R outside [0, 8], R = 0
+ * with gf, a band_mask with bits beyond m, or an unknown end kind with out_g; LSSVR_ERR_QUAD for nquad outside [1, 5];
+ * LSSVR_ERR_NULL for a missing x, Utraj, Z or coef_host, for no output at all, for gf without phi, for one of out_g and
+ * out_kappa without the other, and for out_g without Brows or band_ends.
+ *
+ * lssvr_transient_sensitivity_host -- the same routines on HOST arrays: no device is touched.  Bit for bit the device's values.
+ */
+int lssvr_transient_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj, const double* Z,
+                                int64_t n0, int m, double inv_dt, const double* coef_host, const double* phi, int R,
+                                double* ga, double* gc, double* grho, double* gf, int accumulate, const double* Brows,
+                                const double* band_ends, int band_mask, int kind_left, int kind_right, double* out_g,
+                                double* out_kappa, void* stream);
+int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
+                                     const double* Z_host, int64_t n0, int m, double inv_dt, const double* coef_host,
+                                     const double* phi_host, int R, double* ga_host, double* gc_host,
+                                     double* grho_host, double* gf_host, int accumulate, const double* Brows_host,
+                                     const double* band_ends_host, int band_mask, int kind_left, int kind_right,
+                                     double* out_g_host, double* out_kappa_host);
+
 #ifdef __cplusplus
 }
 #endif
