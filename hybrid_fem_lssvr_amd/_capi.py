@@ -216,6 +216,13 @@ SIGNATURES = {
     "lssvr_transient_sensitivity_host": _sig([_c_hd, _c_i64, _c_int, _c_hd, _c_hd, _c_i64, _c_int, _c_dbl, _c_hd,
                                               _c_hd, _c_int], [_c_hd] * 4,
                                              [_c_int, _c_hd, _c_hd, _c_int, _c_int, _c_int, _c_hd, _c_hd]),
+    # adjoint of the element solve (additive to ABI 7): x, ne, elem_offset, ne_global, gxmin, gxmax, M, n_colloc, gamma,
+    # a, da, c, f, W, status, Wbar, gu, gbc, ga, gda, gc, gf, work, work_bytes
+    "lssvr_enhance_adjoint_work_bytes": _sig([_c_i64], res=_c_i64),
+    "lssvr_enhance_adjoint": _sig([_c_dp, _c_i64, _c_i64, _c_i64, _c_dbl, _c_dbl, _c_int, _c_int, _c_dbl],
+                                  _REACT_TABLES, [_c_dp] * 3, [_c_dp] * 6, _WS, _STREAM),
+    "lssvr_enhance_adjoint_host": _sig([_c_hd, _c_i64, _c_i64, _c_i64, _c_dbl, _c_dbl, _c_int, _c_int, _c_dbl],
+                                       [_c_hd] * 5, [_c_dp, _c_hd], [_c_hd] * 6, _WS),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

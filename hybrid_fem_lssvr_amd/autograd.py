@@ -5,6 +5,9 @@ solve -- as a ``torch.autograd.Function`` over device tensors.  Its backward is 
 transposed bands (``ops.adjoint_bands``) with the incoming gradient as the load, then one ``ops.p1_sensitivity`` for the
 tables whose inputs require a gradient.  All arithmetic runs in the HIP kernels; there is no eager fall-back.
 
+:func:`enhance` is the enhancement -- ``ops.enhance_varcoef`` -- the same way: its backward is one
+``ops.enhance_adjoint``, so ``p1_solve(...)`` -> ``enhance(...)`` -> ``loss.backward()`` runs end to end on the device.
+
 Limits: first derivatives only (the backward is ``once_differentiable``), and the mesh ``x`` is not differentiated --
 its gradient is ``None``.
 """
@@ -94,3 +97,61 @@ def p1_solve(x, rhs_quad, *, a_quad=None, b_quad=None, c_quad=None, end_kinds=(o
         raise ValueError("fem_solver must be 'bands' or 'pivot'")
     kinds = tuple(int(k) for k in end_kinds)
     return _P1Solve.apply(x, rhs_quad, a_quad, b_quad, c_quad, end_values, kappa, kinds, int(nquad), fem_solver)
+
+
+class _Enhance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, u, rhs_values, a_values, da_values, c_values, M, gamma, n_colloc, global_domain, bc):
+        x, u, f = (t.detach().contiguous() for t in (x, u, rhs_values))
+        a, da, c = (None if t is None else t.detach().contiguous() for t in (a_values, da_values, c_values))
+        if a is None and da is not None:
+            raise ValueError("da_values needs a_values")
+        if global_domain is None:
+            ends = torch.stack([x[0], x[-1]]).cpu()
+            global_domain = (float(ends[0]), float(ends[1]))
+        # (the forward entry reads tables: a = 1, a' = 0 as such; the adjoint takes None for them)
+        fa = torch.ones_like(f) if a is None else a
+        fda = torch.zeros_like(f) if da is None else da
+        W, status = ops.enhance_varcoef(x, u, M, gamma, n_colloc, fa, fda, f, c_values=c, global_domain=global_domain,
+                                        bc=bc)
+        ctx.save_for_backward(x, f, W, status, *(t for t in (a, da, c) if t is not None))
+        ctx.meta = (M, gamma, n_colloc, global_domain, a is not None, da is not None, c is not None)
+        return W.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_W):
+        M, gamma, n_colloc, global_domain, has_a, has_da, has_c = ctx.meta
+        x, f, W, status, *rest = ctx.saved_tensors
+        rest = list(rest)
+        a = rest.pop(0) if has_a else None
+        da = rest.pop(0) if has_da else None
+        c = rest.pop(0) if has_c else None
+        need = dict(zip(("u", "f", "a", "da", "c"), ctx.needs_input_grad[1:6]))
+        want = tuple(k for k in ops.ENH_ADJ_OUTPUTS if need.get(k)) or ("u",)
+        res = ops.enhance_adjoint(x, W, grad_W.to(torch.float64).contiguous(), M, gamma, n_colloc, f, a_values=a,
+                                  da_values=da, c_values=c, status=status, want=want, global_domain=global_domain)
+        return (None, *(res[k] if need[k] else None for k in ("u", "f", "a", "da", "c")), None, None, None, None, None)
+
+
+def enhance(x, u, rhs_values, *, M, gamma, n_colloc, a_values=None, da_values=None, c_values=None, global_domain=None,
+            bc=(0.0, 0.0)):
+    """The enhancement coefficients W float64[ne, M] of the nodal values ``u`` float64[ne+1] on the mesh ``x``,
+    differentiable with respect to their data: ``ops.enhance_varcoef`` (with ``c_values`` the reaction entry) as it is,
+    element-major tables float64[ne, n_colloc] at ``ops.colloc_points(x, n_colloc)``; ``a_values=None`` means a = 1,
+    a' = 0 (then ``da_values`` must be None), ``da_values`` holds a' - b with convection, ``c_values=None`` c = 0.
+    ``global_domain`` (``None``: the ends of ``x``, read back) and ``bc`` as in ``ops.enhance_varcoef``: at a global end the
+    forward call puts ``bc`` in place of the nodal value, and the gradient for ``u`` is 0 there.  3 <= M <= 16,
+    max(2, M - 2) <= n_colloc <= 64.
+
+    ``backward`` is ONE ``ops.enhance_adjoint`` with only the outputs whose inputs require a gradient: ``u``,
+    ``rhs_values``, ``a_values``, ``da_values``, ``c_values``; ``None`` for ``x``.  An element the forward call reports
+    as a fallback (the linear interpolant) differentiates by that rule.  No double backward."""
+    M, n_colloc = int(M), int(n_colloc)
+    if not ops.ENH_ADJ_MIN_M <= M <= ops.ENH_ADJ_MAX_M:
+        raise ValueError(f"M must be in {ops.ENH_ADJ_MIN_M} .. {ops.ENH_ADJ_MAX_M}, got {M}")
+    if not max(2, M - 2) <= n_colloc <= ops.ENH_ADJ_MAX_COLLOC:
+        raise ValueError(f"n_colloc must be in {max(2, M - 2)} .. {ops.ENH_ADJ_MAX_COLLOC}, got {n_colloc}")
+    dom = None if global_domain is None else (float(global_domain[0]), float(global_domain[1]))
+    return _Enhance.apply(x, u, rhs_values, a_values, da_values, c_values, M, float(gamma), n_colloc, dom,
+                          (float(bc[0]), float(bc[1])))

@@ -2071,4 +2071,65 @@ int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad
   return LSSVR_OK;
 }
 
+// Adjoint of the element solve (enhance_adjoint.hip).  The device and the host entry share one validated binding.
+int64_t lssvr_enhance_adjoint_work_bytes(int64_t ne) { return ne < 1 ? 0 : ne * (int64_t)(2 * sizeof(double)); }
+
+static int bind_enh_adj(lssvr::EnhAdjArgs& a, const double* x, int64_t ne, int64_t elem_offset, int64_t ne_global,
+                        double gxmin, double gxmax, int M, int n_colloc, double gamma, const double* a_values,
+                        const double* da_values, const double* c_values, const double* rhs_values, const double* W,
+                        const int32_t* status, const double* Wbar, double* gu, double* gbc, double* ga, double* gda,
+                        double* gc, double* gf, void* work, int64_t work_bytes) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (M < lssvr::kEnhAdjMinM || M > lssvr::kEnhAdjMaxM)
+    return fail(LSSVR_ERR_DEGREE, "M = %d outside [%d, %d]", M, lssvr::kEnhAdjMinM, lssvr::kEnhAdjMaxM);
+  const int n_min = M - 2 > 2 ? M - 2 : 2;
+  if (n_colloc < n_min || n_colloc > lssvr::kEnhAdjMaxColloc)
+    return fail(LSSVR_ERR_SIZE, "n_colloc = %d outside [%d, %d]", n_colloc, n_min, lssvr::kEnhAdjMaxColloc);
+  if (elem_offset < 0 || ne_global < elem_offset + ne)
+    return fail(LSSVR_ERR_SIZE, "shard [%lld, %lld) does not fit ne_global = %lld", (long long)elem_offset,
+                (long long)(elem_offset + ne), (long long)ne_global);
+  if (!(gamma > 0.0)) return fail(LSSVR_ERR_SIZE, "gamma must be > 0");
+  if (!x || !rhs_values || !W || !Wbar) return fail(LSSVR_ERR_NULL, "x, rhs_values, W, Wbar must be non-NULL");
+  if (!gu && !gbc && !ga && !gda && !gc && !gf)
+    return fail(LSSVR_ERR_NULL, "one of gu, gbc, ga, gda, gc, gf must be non-NULL");
+  if (da_values && !a_values) return fail(LSSVR_ERR_NULL, "da_values needs a_values");
+  if ((ga || gda) && !a_values) return fail(LSSVR_ERR_NULL, "ga and gda need a_values");
+  if (gc && !c_values) return fail(LSSVR_ERR_NULL, "gc needs c_values");
+  if (const int rc = check_work_sized(work, work_bytes, lssvr_enhance_adjoint_work_bytes(ne),
+                                      "lssvr_enhance_adjoint_work_bytes", ne))
+    return rc;
+  a = lssvr::EnhAdjArgs{x,         ne,       elem_offset, ne_global,  gxmin, gxmax,  gamma, M,  n_colloc,
+                        a_values,  da_values, c_values,   rhs_values, W,     status, Wbar,  gu, gbc,
+                        ga,        gda,      gc,          gf,         static_cast<double*>(work)};
+  return LSSVR_OK;
+}
+
+int lssvr_enhance_adjoint(const double* x, int64_t ne, int64_t elem_offset, int64_t ne_global, double gxmin,
+                          double gxmax, int M, int n_colloc, double gamma, const double* a_values,
+                          const double* da_values, const double* c_values, const double* rhs_values, const double* W,
+                          const int32_t* status, const double* Wbar, double* gu, double* gbc, double* ga, double* gda,
+                          double* gc, double* gf, void* work, int64_t work_bytes, void* stream) {
+  lssvr::EnhAdjArgs a{};
+  const int rc = bind_enh_adj(a, x, ne, elem_offset, ne_global, gxmin, gxmax, M, n_colloc, gamma, a_values, da_values,
+                              c_values, rhs_values, W, status, Wbar, gu, gbc, ga, gda, gc, gf, work, work_bytes);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::enhance_adjoint(a, reinterpret_cast<hipStream_t>(stream)), "enhance_adjoint");
+}
+
+int lssvr_enhance_adjoint_host(const double* x_host, int64_t ne, int64_t elem_offset, int64_t ne_global, double gxmin,
+                               double gxmax, int M, int n_colloc, double gamma, const double* a_values_host,
+                               const double* da_values_host, const double* c_values_host,
+                               const double* rhs_values_host, const double* W_host, const int32_t* status_h,
+                               const double* Wbar_host, double* gu_host, double* gbc_host, double* ga_host,
+                               double* gda_host, double* gc_host, double* gf_host, void* work_h,
+                               int64_t work_bytes) {
+  lssvr::EnhAdjArgs a{};
+  const int rc = bind_enh_adj(a, x_host, ne, elem_offset, ne_global, gxmin, gxmax, M, n_colloc, gamma, a_values_host,
+                              da_values_host, c_values_host, rhs_values_host, W_host, status_h, Wbar_host, gu_host,
+                              gbc_host, ga_host, gda_host, gc_host, gf_host, work_h, work_bytes);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::enhance_adjoint_host(a);         // (M is checked above: the degree is instantiated)
+  return LSSVR_OK;
+}
+
 }  // extern "C"

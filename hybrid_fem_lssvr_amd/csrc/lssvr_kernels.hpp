@@ -592,6 +592,36 @@ struct TsSensArgs {
 hipError_t ts_sensitivity(const TsSensArgs& a, hipStream_t s);
 bool ts_sensitivity_host(const TsSensArgs& a);   // false: no such quadrature rule
 
+// enhance_adjoint.hip: the adjoint of the element solve.  From W and Wbar = dJ/dW, per element one
+// more solve with the forward matrix and a second sweep over the points: the pair (dJ/dg_l, dJ/dg_r) of every element
+// into `pairs`, the table gradients (element-major, a nullptr one is skipped, stores included), then gu and gbc from the
+// pairs in a fixed order.  Degrees kEnhAdjMinM .. kEnhAdjMaxM, the range of the reaction lane kernel.
+constexpr int kEnhAdjMinM = 3;
+constexpr int kEnhAdjMaxM = kReactSmallMaxM;
+constexpr int kEnhAdjMaxColloc = 64;
+struct EnhAdjArgs {
+  const double* x;                  // nodes [ne+1]
+  int64_t ne, elem_offset, ne_global;
+  double gxmin, gxmax, gamma;
+  int M, n;
+  const double* a_values;           // [ne*n] element-major; nullptr: a = 1 (then da_values is nullptr too)
+  const double* da_values;          // nullptr: 0
+  const double* c_values;           // nullptr: 0
+  const double* rhs_values;
+  const double* W;                  // [ne*M], the forward call's output
+  const int32_t* status;            // the forward call's; nullptr: no fallback element
+  const double* Wbar;               // [ne*M]
+  double* gu;                       // [ne+1]
+  double* gbc;                      // [2]
+  double* ga;                       // [ne*n] each
+  double* gda;
+  double* gc;
+  double* gf;
+  double* pairs;                    // workspace [ne][2]
+};
+hipError_t enhance_adjoint(const EnhAdjArgs& a, hipStream_t s);
+bool enhance_adjoint_host(const EnhAdjArgs& a);  // false: no such degree
+
 hipError_t fp64_probe(double* out, int blocks, int iters, int use_mfma, hipStream_t s);
 hipError_t stream_probe(const double* src, double* dst, int64_t n, hipStream_t s);
 hipError_t row_chunk_probe(const double* src, double* dst, int64_t nrows, int rowlen, int chunk, hipStream_t s);

@@ -2275,6 +2275,77 @@ def p1_sensitivity(x, U, Z, nquad=2, *, want=SENS_TABLES, P=None, bands=None,
     return res
 
 
+# ---- adjoint of the element solve ----------------------------------------------------------------
+ENH_ADJ_OUTPUTS = ("u", "bc", "a", "da", "c", "f")      # the keys of ``want`` and of the result
+ENH_ADJ_MIN_M, ENH_ADJ_MAX_M, ENH_ADJ_MAX_COLLOC = 3, 16, 64
+
+
+def enhance_adjoint(x, W, Wbar, M, gamma, n_colloc, rhs_values, *, a_values=None, da_values=None, c_values=None,
+                    status=None, want=("u", "f"), elem_offset=0, ne_global=None, global_domain=None, out=None,
+                    work=None, stream=None):
+    """``lssvr_enhance_adjoint``: the backward of :func:`enhance_varcoef` (element-major tables, primal solve).  From
+    the forward call's ``W`` float64[ne, M] (and ``status`` int32[ne]; ``None``: no fallback element) and
+    ``Wbar`` = dJ/dW float64[ne, M], the gradients of J named in ``want``: "u" float64[ne+1] (nodal values), "bc"
+    float64[2] (the Dirichlet values, where the forward call put them in place of a nodal value; "u" is 0 there), and
+    "a", "da", "c", "f" float64[ne, n_colloc] (the tables; ``da_values`` is what the forward kernel was handed, a' - b
+    with convection).  ``a_values=None`` (then ``da_values`` must be None) means a = 1, a' = 0 and ``c_values=None``
+    c = 0; "a" and "da" need ``a_values``, "c" needs ``c_values``.  Neither u nor the Dirichlet values are arguments:
+    W carries them.  ``elem_offset``, ``ne_global``, ``global_domain`` as in :func:`enhance_varcoef`.  3 <= M <= 16,
+    max(2, M - 2) <= n_colloc <= 64.  Returns a dict of the wanted keys; ``out``: a dict of buffers to write into, by
+    those keys; ``work``: float64[ne, 2], receives the per-element pairs (dJ/dg_l, dJ/dg_r).  One lane kernel and, with
+    "u" or "bc", one gather kernel; no synchronisation and no copy (but the read-back of the shard's ends when
+    ``global_domain`` is None); every value is computed in a fixed order (bitwise reproducible)."""
+    lib = _capi.load()
+    M, n_colloc = int(M), int(n_colloc)
+    _dev(x, "x")
+    ne = _nodes(x, "x")
+    if not ENH_ADJ_MIN_M <= M <= ENH_ADJ_MAX_M:
+        raise ValueError(f"M must be in {ENH_ADJ_MIN_M} .. {ENH_ADJ_MAX_M}, got {M}")
+    if not max(2, M - 2) <= n_colloc <= ENH_ADJ_MAX_COLLOC:
+        raise ValueError(f"n_colloc must be in {max(2, M - 2)} .. {ENH_ADJ_MAX_COLLOC}, got {n_colloc}")
+    want = tuple(want)
+    if not want or len(set(want)) != len(want) or any(k not in ENH_ADJ_OUTPUTS for k in want):
+        raise ValueError(f"want must name at least one of {ENH_ADJ_OUTPUTS}, each once, got {want!r}")
+    if a_values is None and da_values is not None:
+        raise ValueError("da_values needs a_values")
+    if a_values is None and ("a" in want or "da" in want):
+        raise ValueError('want "a" and "da" need a_values')
+    if c_values is None and "c" in want:
+        raise ValueError('want "c" needs c_values')
+    tabs = {k: t for k, t in (("rhs_values", rhs_values), ("a_values", a_values), ("da_values", da_values),
+                              ("c_values", c_values)) if t is not None or k == "rhs_values"}
+    _tables(ne, n_colloc, **tabs)
+    rows = {"W": W, "Wbar": Wbar}
+    for nm, t in rows.items():
+        _dev(t, nm)
+        if t.numel() != ne * M:
+            raise ValueError(f"{nm} must hold ne*M = {ne * M} doubles, got {t.numel()}")
+    ins = dict(tabs, **rows)
+    if status is not None:
+        _dev(status, "status", torch.int32)
+        if status.numel() != ne:
+            raise ValueError(f"status must be int32[ne = {ne}], got {list(status.shape)}")
+        ins["status"] = status
+    out = {} if out is None else out
+    shapes = {"u": (ne + 1,), "bc": (2,)}
+    res = {k: _out(out.get(k), f"out[{k!r}]", shapes.get(k, (ne, n_colloc)), x) for k in want}
+    work = _out(work, "work", (ne, 2), x)
+    _no_alias("the outputs and work must be distinct and none of them an input", (*res.values(), work),
+              (x, *ins.values()))
+    _same_device(x, **ins)
+    ne_global = elem_offset + ne if ne_global is None else ne_global
+    if global_domain is None:
+        ends = torch.stack([x[0], x[-1]]).cpu()
+        global_domain = (float(ends[0]), float(ends[1]))
+    rc = lib.lssvr_enhance_adjoint(_ptr(x), ne, int(elem_offset), int(ne_global), float(global_domain[0]),
+                                   float(global_domain[1]), M, n_colloc, float(gamma), _ptr(a_values), _ptr(da_values),
+                                   _ptr(c_values), _ptr(rhs_values), _ptr(W), _ptr(status), _ptr(Wbar),
+                                   *(_ptr(res.get(k)) for k in ENH_ADJ_OUTPUTS), _ptr(work), work.numel() * 8,
+                                   _stream(stream))
+    _capi.check(rc, "lssvr_enhance_adjoint")
+    return res
+
+
 # ---- adjoint sensitivities of the BDF loop (DESIGN.md section 32) -------------------------------------------------------
 TS_SENS_TABLES = ("a", "c", "rho", "f")     # d/d a_quad, c_quad, rho_quad, f_quad[r]: the keys of ``want`` and the result
 TS_SENS_CHUNK = 8                           # most adjoint steps of one launch

@@ -2589,8 +2589,98 @@ class FEMLSSVRPrimalSolver:
             return ops.tridiag_ns_bc_solve_multi(ab["diag"], ab["sub"], ab["sup"], P, kinds, kappa, None)
         return ops.tridiag_bc_solve_multi(ab["diag"], ab["off"], P, kinds, kappa, None)
 
-    def solve_sensitivity(self, goal=None, *, observe=None):
-        """Derivatives of a functional J of the P1 solution with respect to the data of the solve, by the adjoint
+    # ---- sensitivities of the ENHANCED solution ----------------------------------------------
+    def _check_sensitivity_enhanced(self, goal, observe):
+        """What ``solve_sensitivity(of="enhanced")`` needs beyond :meth:`_check_sensitivity`, on the host and before
+        any device call -> (nodes, functional): ``functional(W)`` -> (J, Wbar = dJ/dW) for the coefficients W [ne, M]."""
+        nodes, _ = self._check_sensitivity(goal, observe)
+        M, n = int(self.lssvr_M), int(self.n_colloc)
+        if not ops.ENH_ADJ_MIN_M <= M <= ops.ENH_ADJ_MAX_M:
+            raise ValueError(f"solve_sensitivity(of='enhanced') needs {ops.ENH_ADJ_MIN_M} <= lssvr_M <= "
+                             f"{ops.ENH_ADJ_MAX_M} (the lane kernel of the adjoint), got {M}")
+        if not max(2, M - 2) <= n <= ops.ENH_ADJ_MAX_COLLOC:
+            raise ValueError(f"solve_sensitivity(of='enhanced') needs max(2, lssvr_M - 2) <= n_colloc <= "
+                             f"{ops.ENH_ADJ_MAX_COLLOC}, got {n}")
+        if self.element_lists:
+            raise ValueError("solve_sensitivity(of='enhanced') has no element_lists: one degree, one launch")
+        h = np.diff(nodes)
+        vander = np.polynomial.legendre.legvander
+
+        def local(e, xo):
+            """L_p at the local coordinate of the points xo of the elements e [len(xo), M]."""
+            return vander((2.0 * xo - nodes[e] - nodes[e + 1]) / h[e], M - 1)
+
+        if goal is not None:
+            # J = int j u_enh dx by the Gauss rule of the estimators on every element: linear in W
+            xi, w = np.polynomial.legendre.leggauss(self._nq(None))
+            xq = 0.5 * (nodes[:-1] + nodes[1:])[:, None] + 0.5 * h[:, None] * xi[None, :]
+            try:
+                jq = np.broadcast_to(np.asarray(goal(xq), dtype=np.float64), xq.shape)
+            except ValueError:
+                raise ValueError(f"goal must return one value per point ({list(xq.shape)}) or a value that "
+                                 "broadcasts to them") from None
+            if not np.all(np.isfinite(jq)):
+                raise ValueError("goal is not finite at a quadrature point")
+            e = np.repeat(np.arange(h.size), xi.size)
+            Wbar = np.einsum("eq,eqm->em", jq * (0.5 * h[:, None] * w[None, :]),
+                             local(e, xq.ravel()).reshape(h.size, xi.size, M))
+            return nodes, lambda W: (float(np.sum(Wbar * W)), Wbar)
+        xo, d = (np.asarray(t, dtype=np.float64).reshape(-1) for t in observe)
+        e = np.clip(np.searchsorted(nodes, xo, side="right") - 1, 0, nodes.size - 2)
+        P = local(e, xo)
+
+        def misfit(W):
+            r = np.sum(P * W[e], axis=1) - d
+            Wbar = np.zeros(W.shape)
+            np.add.at(Wbar, e, r[:, None] * P)
+            return 0.5 * float(r @ r), Wbar
+        return nodes, misfit
+
+    def _solve_sensitivity_enhanced(self, goal, observe):
+        nodes, functional = self._check_sensitivity_enhanced(goal, observe)
+        self.solve_fem()
+        x, u, bands = self._x_dev, self._u_dev, self.bands
+        M, gamma, n = int(self.lssvr_M), float(self.lssvr_gamma), int(self.n_colloc)
+        gd, bc = self._gd_bc()
+        shard = self._shard(nodes.size - 1)
+        eq = self._eq
+        # the forward call on ELEMENT-MAJOR tables (the layout of the adjoint), whatever solve() would take
+        ta, tda, tf, tc = eq.tables(ops.colloc_points(x, n), False)
+        W, st = ops.enhance_varcoef(x, u, M, gamma, n, ta, tda, tf, global_domain=gd, bc=bc, c_values=tc, **shard)
+        Wh = W.cpu().numpy()                    # (a misfit's Wbar depends on W: the one copy besides the results')
+        value, Wbar = functional(Wh)
+        want = ("u", "bc", "a", "da", "f") + (("c",) if tc is not None else ())
+        adj = ops.enhance_adjoint(x, W, _to_dev(Wbar, x.device), M, gamma, n, tf, a_values=ta, da_values=tda,
+                                  c_values=tc, status=st, want=want, global_domain=gd, **shard)
+        bnd = self._bnd
+        kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (tuple(bnd.kinds), tuple(bnd.kappa))
+        P = adj["u"].view(1, -1)
+        Z = self._adjoint_solve(bands, P, kinds, kappa)
+        p1want = tuple(k for k, on in zip(ops.SENS_TABLES, (True, eq.b is not None, eq.c is not None, True)) if on)
+        res = ops.p1_sensitivity(x, u, Z, self.nquad, want=p1want, P=P, bands=bands, end_kinds=kinds)
+        host = _read_back(z=Z, **res, **{"enh_" + k: v for k, v in adj.items()})
+        ends = host["ends"][0].copy()
+        ends[:2] += host["enh_bc"]
+        s = Sensitivity(value, {k: host[k][0] for k in p1want}, ends, host["z"][0], nodes)
+        s.d_rhs_colloc, s.d_coef_colloc, s.d_dcoef_colloc = host["enh_f"], host["enh_a"], host["enh_da"]
+        s.d_reaction_colloc = host.get("enh_c")
+        s.d_convection_colloc = None if eq.b is None else -host["enh_da"]
+        s.enhanced = Wh
+        return s
+
+    def solve_sensitivity(self, goal=None, *, observe=None, of="p1"):
+        """``of="enhanced"``: the functional is one of the ENHANCED solution u_enh = sum_p W[e, p] L_p -- J = int j u_enh
+        dx by the Gauss rule of :meth:`estimate` on every element, or the misfit 1/2 sum_i (u_enh(x_i) - d_i)^2 -- and
+        the chain runs one stage further: the forward enhancement on element-major tables, Wbar = dJ/dW formed on the
+        host and uploaded once, ONE ``ops.enhance_adjoint``, whose nodal gradient is the load of the adjoint solve, then
+        ONE ``ops.p1_sensitivity`` and one read-back.  The :class:`Sensitivity` then also holds ``d_rhs_colloc``,
+        ``d_coef_colloc``, ``d_dcoef_colloc`` (the first-derivative table a' - b), ``d_reaction_colloc`` and
+        ``d_convection_colloc`` = -``d_dcoef_colloc`` [ne, n_colloc] (None where the solver has no such term), and
+        ``d_end_values`` of a Dirichlet end is the sum of the P1 part and of the enhancement's own.  Refused besides what
+        is refused below: ``lssvr_M`` outside 3 .. 16, ``n_colloc`` outside max(2, lssvr_M - 2) .. 64,
+        ``element_lists``.  ``of="p1"`` (the default) is the path below, untouched.
+
+        Derivatives of a functional J of the P1 solution with respect to the data of the solve, by the adjoint
         method: ONE :meth:`solve_fem`, ONE adjoint solve -- the same tridiagonal solver on the transposed bands
         (``ops.adjoint_bands``) with load p = dJ/du, zero end data and the same end kinds and kappa -- and ONE
         ``ops.p1_sensitivity``.  ``goal``: a callable j(x), J(u) = int j u_h dx by the quadrature rule of the assembly;
@@ -2601,6 +2691,10 @@ class FEMLSSVRPrimalSolver:
         ``fem_solver="flux"``, ``nonlinear=``, a solver other than ``ops.SOLVER_PRIMAL``, ``element_degrees``, both or
         neither of ``goal`` and ``observe``, data that are not finite where they are tabulated.  The mesh is not
         differentiated."""
+        if of not in ("p1", "enhanced"):
+            raise ValueError(f"of must be 'p1' or 'enhanced', got {of!r}")
+        if of == "enhanced":
+            return self._solve_sensitivity_enhanced(goal, observe)
         nodes, functional = self._check_sensitivity(goal, observe)
         self.solve_fem()
         x, u, bands = self._x_dev, self._u_dev, self.bands

@@ -1382,6 +1382,57 @@ int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad
                                      const double* band_ends_host, int band_mask, int kind_left, int kind_right,
                                      double* out_g_host, double* out_kappa_host);
 
+/*
+ * Adjoint of the element solve: sensitivities of the ENHANCEMENT (no reference counterpart).
+ * ADDITIVE to ABI 7: three new symbols, no existing entry, struct, constant or kernel instantiation changes,
+ * LSSVR_ABI_VERSION stays 7.
+ *
+ * The forward calls (lssvr_enhance_varcoef, lssvr_enhance_react and their _ws forms, element-major tables, primal
+ * solve) map the nodal values, the Dirichlet values and the collocation tables a, da (which may hold a' - b), c, f to
+ * the coefficients W [ne][M].  For a functional J with Wbar = dJ/dW this entry returns dJ/d(every one of them).  In the
+ * notation of the per-element solve (scl = 2/h, Ahat = -a D2 - (da/scl) D1 + (c/scl^2) L, eps = 1/(gamma scl^4),
+ * C = B1^-1 B2, S = Abar^T Abar + eps (I + C^T C)), per element:
+ *   y  = S^-1 (Wbar_2 - C^T Wbar_1)        one solve with the forward matrix
+ *   yh = (-C y, y),   q = Ahat yh,   e = f/scl^2 - Ahat w      (w: the stored row of W)
+ *   dJ/df_k  =  q_k / scl^2                       dJ/da_k = -[ e_k (D2 yh)_k - q_k (D2 w)_k ]
+ *   dJ/dda_k = -[ e_k (D1 yh)_k - q_k (D1 w)_k ] / scl        dJ/dc_k =  [ e_k (L yh)_k - q_k (L w)_k ] / scl^2
+ *   (dJ/dg_l, dJ/dg_r) = B1^-T ( Wbar_1 + eps C y - Ahat1^T q )
+ * An element whose forward status is LSSVR_ST_FALLBACK has dJ/dg_l = (Wbar_0 - Wbar_1)/2, dJ/dg_r = (Wbar_0 + Wbar_1)/2
+ * and zero table rows.  gu[i] = dJ/dg_r(element i-1) + dJ/dg_l(element i), the left element's term first, no atomics;
+ * where the forward call replaces a nodal value by the Dirichlet value (the global end element whose end point equals
+ * gxmin / gxmax exactly) the term goes to gbc[side] and gu gets 0 there; gbc of an end that is not replaced is 0.  The
+ * mesh and gamma are not differentiated.
+ *
+ * lssvr_enhance_adjoint -- DEVICE arrays: x [ne+1]; rhs_values, a_values, da_values, c_values [ne*n_colloc]
+ * element-major (lssvr_colloc_points); W, Wbar [ne*M]; status [ne] (the forward call's; NULL: no fallback element).
+ * a_values == NULL (then da_values must be NULL too) means a = 1, a' = 0; c_values == NULL means c = 0.  Neither u nor
+ * the Dirichlet values are arguments: W carries them.  Outputs, each may be NULL (it then costs neither arithmetic nor a
+ * store) but not all: gu [ne+1], gbc [2], ga, gda, gc, gf [ne*n_colloc].  gbc and gu are independent: a replaced end
+ * without gbc is dropped.  work: lssvr_enhance_adjoint_work_bytes(ne) bytes on the device; after the call it holds the
+ * pairs (dJ/dg_l, dJ/dg_r) [ne][2].  Two launches on `stream` (one without gu and gbc), no synchronisation, no copy.
+ * 3 <= M <= 16 (one element per lane, direct Gram in every regime), max(2, M-2) <= n_colloc <= 64.  No output may be
+ * one of the inputs or another output.
+ * Return codes, each before any HIP call: LSSVR_ERR_SIZE for ne < 1, n_colloc outside [max(2, M-2), 64], a shard
+ * outside ne_global, gamma not > 0 or work_bytes too small; LSSVR_ERR_DEGREE for M outside [3, 16]; LSSVR_ERR_NULL for a
+ * missing x, rhs_values, W, Wbar or work, for no output at all, for ga or gda without a_values, gc without c_values and
+ * da_values without a_values.
+ *
+ * lssvr_enhance_adjoint_host -- the same routines on HOST arrays: no device is touched.  Bit for bit the device's values.
+ */
+int64_t lssvr_enhance_adjoint_work_bytes(int64_t ne);
+int lssvr_enhance_adjoint(const double* x, int64_t ne, int64_t elem_offset, int64_t ne_global, double gxmin,
+                          double gxmax, int M, int n_colloc, double gamma, const double* a_values,
+                          const double* da_values, const double* c_values, const double* rhs_values, const double* W,
+                          const int32_t* status, const double* Wbar, double* gu, double* gbc, double* ga, double* gda,
+                          double* gc, double* gf, void* work, int64_t work_bytes, void* stream);
+int lssvr_enhance_adjoint_host(const double* x_host, int64_t ne, int64_t elem_offset, int64_t ne_global, double gxmin,
+                               double gxmax, int M, int n_colloc, double gamma, const double* a_values_host,
+                               const double* da_values_host, const double* c_values_host,
+                               const double* rhs_values_host, const double* W_host, const int32_t* status_h,
+                               const double* Wbar_host, double* gu_host, double* gbc_host, double* ga_host,
+                               double* gda_host, double* gc_host, double* gf_host, void* work_h,
+                               int64_t work_bytes);
+
 #ifdef __cplusplus
 }
 #endif
