@@ -15,6 +15,7 @@ from .solver import (  # noqa: F401
     Sensitivity,
     TransientSensitivity,
     TransientSolution,
+    WaveSensitivity,
     WaveSolution,
     SinRHS,
     enhance_elements,

@@ -223,6 +223,15 @@ SIGNATURES = {
                                   _REACT_TABLES, [_c_dp] * 3, [_c_dp] * 6, _WS, _STREAM),
     "lssvr_enhance_adjoint_host": _sig([_c_hd, _c_i64, _c_i64, _c_i64, _c_dbl, _c_dbl, _c_int, _c_int, _c_dbl],
                                        [_c_hd] * 5, [_c_dp, _c_hd], [_c_hd] * 6, _WS),
+    # adjoint sensitivities of the Newmark loop (additive to ABI 7).  advance: lam, Vbar, Abar, P, mdiag, moff, ddiag,
+    # doff, ne, dt, beta, gamma, V_out, A_out, U_out, B_out; sensitivity: x, ne, nquad, Utraj, Vtraj, Atraj, Z, n0, m,
+    # phi, R, ga, gc, grho, gd, gf, accumulate, Brows, band_ends, kind_left, kind_right, out_g, out_kappa
+    "lssvr_newmark_adjoint_advance": _sig([_c_dp] * 8, [_c_i64, _c_dbl, _c_dbl, _c_dbl], [_c_dp] * 4, _STREAM),
+    "lssvr_newmark_adjoint_advance_host": _sig([_c_hd] * 8, [_c_i64, _c_dbl, _c_dbl, _c_dbl], [_c_hd] * 4),
+    "lssvr_newmark_sensitivity": _sig(_MESH, [_c_dp] * 4, [_c_i64, _c_int, _c_dp, _c_int], [_c_dp] * 5,
+                                      [_c_int, _c_dp, _c_dp, _c_int, _c_int, _c_dp, _c_dp], _STREAM),
+    "lssvr_newmark_sensitivity_host": _sig([_c_hd, _c_i64, _c_int], [_c_hd] * 4, [_c_i64, _c_int, _c_hd, _c_int],
+                                           [_c_hd] * 5, [_c_int, _c_hd, _c_hd, _c_int, _c_int, _c_hd, _c_hd]),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

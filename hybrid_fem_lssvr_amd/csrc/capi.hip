@@ -2071,6 +2071,135 @@ int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad
   return LSSVR_OK;
 }
 
+// Adjoint sensitivities of the Newmark loop (newmark_adjoint.hip).  The device and the host entries share one validated
+// binding each.
+// an output (NULL: not given) that is another output or one of the inputs
+static bool aliased(const void* const* outs, int nout, const void* const* ins, int nin) {
+  for (int i = 0; i < nout; ++i) {
+    if (!outs[i]) continue;
+    for (int j = i + 1; j < nout; ++j)
+      if (outs[j] == outs[i]) return true;
+    for (int j = 0; j < nin; ++j)
+      if (ins[j] == outs[i]) return true;
+  }
+  return false;
+}
+
+static int bind_nm_adj(lssvr::NmAdjArgs& a, const double* lam, const double* Vbar, const double* Abar, const double* P,
+                       const double* mdiag, const double* moff, const double* ddiag, const double* doff, int64_t ne,
+                       double dt, double beta, double gamma, double* V_out, double* A_out, double* U_out,
+                       double* B_out) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (!(is_finite(dt) && dt > 0.0) || !(is_finite(beta) && beta > 0.0) || !(is_finite(gamma) && gamma > 0.0))
+    return fail(LSSVR_ERR_SIZE, "dt = %g, beta = %g, gamma = %g must be finite and > 0", dt, beta, gamma);
+  if (!Vbar || !Abar) return fail(LSSVR_ERR_NULL, "Vbar, Abar must be non-NULL");
+  if (!lam) {
+    if (!B_out) return fail(LSSVR_ERR_NULL, "B_out must be non-NULL without lam: the first call of a sweep writes it");
+    if (V_out || A_out || U_out)
+      return fail(LSSVR_ERR_SIZE, "V_out, A_out, U_out must be NULL without lam: the first call writes B_out alone");
+  } else {
+    if (!mdiag || !moff) return fail(LSSVR_ERR_NULL, "mdiag, moff must be non-NULL with lam");
+    if (!ddiag != !doff) return fail(LSSVR_ERR_NULL, "ddiag and doff go together: both or neither");
+    if (!V_out || !A_out) return fail(LSSVR_ERR_NULL, "V_out, A_out must be non-NULL with lam");
+  }
+  const void* outs[] = {V_out, A_out, U_out, B_out};
+  const void* ins[] = {lam, Vbar, Abar, P, mdiag, moff, ddiag, doff};
+  if (aliased(outs, 4, ins, 8))
+    return fail(LSSVR_ERR_SIZE, "V_out, A_out, U_out, B_out must be distinct and none of them an input");
+  lssvr::WaveArgs w{};
+  lssvr::wave_coefficients(w, dt, beta, gamma);
+  a = lssvr::NmAdjArgs{lam, Vbar, Abar, P, mdiag, moff, lam ? ddiag : nullptr, lam ? doff : nullptr, ne,
+                       w.dt, w.c_u2, w.c_v1, w.c_m, w.c_d, w.c_va, V_out, A_out, U_out, B_out};
+  return LSSVR_OK;
+}
+
+int lssvr_newmark_adjoint_advance(const double* lam, const double* Vbar, const double* Abar, const double* P,
+                                  const double* mdiag, const double* moff, const double* ddiag, const double* doff,
+                                  int64_t ne, double dt, double beta, double gamma, double* V_out, double* A_out,
+                                  double* U_out, double* B_out, void* stream) {
+  lssvr::NmAdjArgs a{};
+  const int rc = bind_nm_adj(a, lam, Vbar, Abar, P, mdiag, moff, ddiag, doff, ne, dt, beta, gamma, V_out, A_out, U_out,
+                             B_out);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::newmark_adjoint_advance(a, reinterpret_cast<hipStream_t>(stream)),
+                      "newmark_adjoint_advance");
+}
+
+int lssvr_newmark_adjoint_advance_host(const double* lam_host, const double* Vbar_host, const double* Abar_host,
+                                       const double* P_host, const double* mdiag_host, const double* moff_host,
+                                       const double* ddiag_host, const double* doff_host, int64_t ne, double dt,
+                                       double beta, double gamma, double* V_out_host, double* A_out_host,
+                                       double* U_out_host, double* B_out_host) {
+  lssvr::NmAdjArgs a{};
+  const int rc = bind_nm_adj(a, lam_host, Vbar_host, Abar_host, P_host, mdiag_host, moff_host, ddiag_host, doff_host,
+                             ne, dt, beta, gamma, V_out_host, A_out_host, U_out_host, B_out_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::newmark_adjoint_advance_host(a);
+  return LSSVR_OK;
+}
+
+static int bind_nm_sens(lssvr::NmSensArgs& a, const double* x, int64_t ne, int nquad, const double* Utraj,
+                        const double* Vtraj, const double* Atraj, const double* Z, int64_t n0, int m, const double* phi,
+                        int R, double* ga, double* gc, double* grho, double* gd, double* gf, int accumulate,
+                        const double* Brows, const double* band_ends, int kind_left, int kind_right, double* out_g,
+                        double* out_kappa) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (m < 1 || m > lssvr::kNmSensMaxSteps) return fail(LSSVR_ERR_SIZE, "m = %d outside [1, 8]", m);
+  if (n0 < 0) return fail(LSSVR_ERR_SIZE, "n0 = %lld: the first level of a chunk is >= 0", (long long)n0);
+  if (R < 0 || R > lssvr::kNmSensMaxTerms) return fail(LSSVR_ERR_SIZE, "R = %d outside [0, 8]", R);
+  if (R == 0 && gf) return fail(LSSVR_ERR_SIZE, "R = 0 is allowed only with gf NULL");
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  if (!x || !Utraj || !Z) return fail(LSSVR_ERR_NULL, "x, Utraj, Z must be non-NULL");
+  if (!ga && !gc && !grho && !gd && !gf && !out_g)
+    return fail(LSSVR_ERR_NULL, "one of ga, gc, grho, gd, gf, out_g must be non-NULL");
+  if (gf && !phi) return fail(LSSVR_ERR_NULL, "phi must be non-NULL with gf");
+  if (gd && !Vtraj) return fail(LSSVR_ERR_NULL, "Vtraj must be non-NULL with gd");
+  if (grho && !Atraj) return fail(LSSVR_ERR_NULL, "Atraj must be non-NULL with grho");
+  if (!out_g != !out_kappa) return fail(LSSVR_ERR_NULL, "out_g and out_kappa go together: both or neither");
+  if (out_g) {
+    if (!Brows || !band_ends) return fail(LSSVR_ERR_NULL, "Brows and band_ends must be non-NULL with out_g");
+    if (const int rc = check_kinds(kind_left, kind_right)) return rc;
+  }
+  const void* outs[] = {ga, gc, grho, gd, gf, out_g, out_kappa};
+  const void* ins[] = {x, Utraj, Vtraj, Atraj, Z, phi, Brows, band_ends};
+  if (aliased(outs, 7, ins, 8))
+    return fail(LSSVR_ERR_SIZE, "ga, gc, grho, gd, gf, out_g, out_kappa must be distinct and none of them an input");
+  a = lssvr::NmSensArgs{};
+  a.x = x, a.Utraj = Utraj, a.Vtraj = Vtraj, a.Atraj = Atraj, a.Z = Z, a.Brows = Brows, a.phi = phi;
+  a.band_ends = band_ends;
+  a.ne = ne, a.n0 = n0, a.nquad = nquad, a.m = m, a.R = R, a.accumulate = accumulate != 0;
+  a.kind[0] = kind_left, a.kind[1] = kind_right;
+  a.ga = ga, a.gc = gc, a.grho = grho, a.gd = gd, a.gf = gf, a.out_g = out_g, a.out_kappa = out_kappa;
+  return LSSVR_OK;
+}
+
+int lssvr_newmark_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj, const double* Vtraj,
+                              const double* Atraj, const double* Z, int64_t n0, int m, const double* phi, int R,
+                              double* ga, double* gc, double* grho, double* gd, double* gf, int accumulate,
+                              const double* Brows, const double* band_ends, int kind_left, int kind_right,
+                              double* out_g, double* out_kappa, void* stream) {
+  lssvr::NmSensArgs a;
+  const int rc = bind_nm_sens(a, x, ne, nquad, Utraj, Vtraj, Atraj, Z, n0, m, phi, R, ga, gc, grho, gd, gf, accumulate,
+                              Brows, band_ends, kind_left, kind_right, out_g, out_kappa);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::newmark_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "newmark_sensitivity");
+}
+
+int lssvr_newmark_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
+                                   const double* Vtraj_host, const double* Atraj_host, const double* Z_host, int64_t n0,
+                                   int m, const double* phi_host, int R, double* ga_host, double* gc_host,
+                                   double* grho_host, double* gd_host, double* gf_host, int accumulate,
+                                   const double* Brows_host, const double* band_ends_host, int kind_left,
+                                   int kind_right, double* out_g_host, double* out_kappa_host) {
+  lssvr::NmSensArgs a;
+  const int rc = bind_nm_sens(a, x_host, ne, nquad, Utraj_host, Vtraj_host, Atraj_host, Z_host, n0, m, phi_host, R,
+                              ga_host, gc_host, grho_host, gd_host, gf_host, accumulate, Brows_host, band_ends_host,
+                              kind_left, kind_right, out_g_host, out_kappa_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::newmark_sensitivity_host(a);     // (nquad is checked above: the rule exists)
+  return LSSVR_OK;
+}
+
 // Adjoint of the element solve (enhance_adjoint.hip).  The device and the host entry share one validated binding.
 int64_t lssvr_enhance_adjoint_work_bytes(int64_t ne) { return ne < 1 ? 0 : ne * (int64_t)(2 * sizeof(double)); }
 

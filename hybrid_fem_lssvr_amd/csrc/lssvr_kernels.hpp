@@ -592,6 +592,55 @@ struct TsSensArgs {
 hipError_t ts_sensitivity(const TsSensArgs& a, hipStream_t s);
 bool ts_sensitivity_host(const TsSensArgs& a);   // false: no such quadrature rule
 
+// newmark_adjoint.hip: adjoint sensitivities of the Newmark loop.  One case; nodal vectors
+// [ne+1].  The scalars are those of wave_coefficients.
+struct NmAdjArgs {
+  const double* lam;                // lambda^{n+1}; nullptr: the first call of a sweep, B_out from (P, Vbar, Abar) alone
+  const double* Vbar;               // the bars (vbar, abar) of level n+1
+  const double* Abar;
+  const double* P;                  // the row p_n; nullptr: zero
+  const double* mdiag;              // the mass bands of rho: [ne+1], [ne]; read with lam
+  const double* moff;
+  const double* ddiag;              // the mass bands of d; ddiag == nullptr: d = 0, neither is read
+  const double* doff;
+  int64_t ne;
+  double dt, c_u2, c_v1, c_m, c_d, c_va;
+  double* V_out;                    // the bars (vbar, abar) of level n; written with lam
+  double* A_out;
+  double* U_out;                    // ubar of level n; nullptr: not written
+  double* B_out;                    // B_n = ubar + c_m (abar + c_va vbar); nullptr: not written
+};
+hipError_t newmark_adjoint_advance(const NmAdjArgs& a, hipStream_t s);
+void newmark_adjoint_advance_host(const NmAdjArgs& a);
+
+// One chunk of m <= 8 consecutive levels n0 .. n0+m-1 (n0 >= 0), summed over the chunk into the tables.  Every array
+// that runs over time is handed over whole and indexed with the level n: Utraj, Vtraj, Atraj, phi, out_g.  The rows of Z
+// and Brows stand in the order of the backward sweep: row i belongs to level n0 + m - 1 - i.
+constexpr int kNmSensMaxSteps = 8;   // levels per chunk
+constexpr int kNmSensMaxTerms = 8;   // terms of the separable forcing
+struct NmSensArgs {
+  const double* x;                  // nodes [ne+1]
+  const double* Utraj;              // [N+1][ne+1]: row n = u^n; read for ga, gc and out_kappa
+  const double* Vtraj;              // row n = v^n; read for gd only
+  const double* Atraj;              // row n = acc^n; read for grho only
+  const double* Z;                  // [m][ne+1]: the adjoint states of the chunk
+  const double* Brows;              // [m][ne+1]: their right-hand sides; read for out_g at a Dirichlet end
+  const double* phi;                // [N+1][R]: row n = phi(t_n); gf only
+  const double* band_ends;          // [2]: {sub[0], sup[ne-1]} of the chunk's matrix; read for out_g only
+  int64_t ne, n0;
+  int nquad, m, R, accumulate;      // accumulate: the sums continue from what the outputs hold (0: from 0)
+  int kind[2];                      // LSSVR_END_*; read for out_g only
+  double* ga;                       // dJ/d(a, c, rho, d)_quad [ne*nquad]; nullptr: skipped
+  double* gc;
+  double* grho;
+  double* gd;
+  double* gf;                       // dJ/df_quad [R][ne*nquad]
+  double* out_g;                    // [N+1][2]: rows n0 .. n0+m-1 are written; nullptr: no end gradients
+  double* out_kappa;                // [2]
+};
+hipError_t newmark_sensitivity(const NmSensArgs& a, hipStream_t s);
+bool newmark_sensitivity_host(const NmSensArgs& a);   // false: no such quadrature rule
+
 // enhance_adjoint.hip: the adjoint of the element solve.  From W and Wbar = dJ/dW, per element one
 // more solve with the forward matrix and a second sweep over the points: the pair (dJ/dg_l, dJ/dg_r) of every element
 // into `pairs`, the table gradients (element-major, a nullptr one is skipped, stores included), then gu and gbc from the

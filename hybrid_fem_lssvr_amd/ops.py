@@ -2437,6 +2437,152 @@ def ts_sensitivity(x, Utraj, Z, n0, coef, inv_dt, nquad=2, *, want=TS_SENS_TABLE
     return res
 
 
+# ---- adjoint sensitivities of the Newmark loop ---------------------------------------------------
+NM_SENS_TABLES = ("a", "c", "rho", "d", "f")    # d/d a_quad, c_quad, rho_quad, d_quad, f_quad[r]: the keys of ``want``
+NM_SENS_CHUNK = 8                               # most levels of one launch
+
+
+def newmark_adjoint_advance(lam, Vbar, Abar, mdiag, moff, ddiag, doff, dt, beta, gamma, *, P=None, want_u=False,
+                            want_b=True, out=None, stream=None):
+    """``lssvr_newmark_adjoint_advance``: ONE launch between two backward solves of the Newmark adjoint.  From lam =
+    lambda^{n+1}, the bars (Vbar, Abar) of level n+1 and the row P = p_n (``None``: zero), all float64[ne+1] on the
+    device, with the mass bands (mdiag[ne+1], moff[ne]) and the damping bands (ddiag, doff; both ``None``: d = 0):
+    as = Abar + gamma dt Vbar, ut = c_m M_rho lam + c_d M_d lam - c_m as, vt = Vbar - M_d lam, then "u" = P + ut,
+    "v" = dt ut + vt, "a" = c_u2 ut + c_v1 vt, the bars of level n, and "b" = u + c_m (a + gamma dt v), the next
+    right-hand side.  ``lam=None`` is the first call of a sweep: "b" = P + c_m (Abar + gamma dt Vbar) alone (the bands
+    may be ``None``).  ``want_u``: write "u" (the last call of a sweep); ``want_b=False``: no "b".  Returns a dict by
+    those keys; ``out``: a dict of buffers to write into.  No output may be an input or another output.  No
+    synchronisation and no copy; every sum in a fixed order (bitwise reproducible)."""
+    lib = _capi.load()
+    for nm, t in (("Vbar", Vbar), ("Abar", Abar)):
+        _dev(t, nm)
+    ne = _nodes(Vbar, "Vbar")
+    dt, beta, gamma = _finite(dt=dt, beta=beta, gamma=gamma)
+    if not (dt > 0.0 and beta > 0.0 and gamma > 0.0):
+        raise ValueError(f"dt, beta and gamma must be > 0, got {dt!r}, {beta!r}, {gamma!r}")
+    ins = {"Abar": Abar}
+    if P is not None:
+        _dev(P, "P")
+        ins["P"] = P
+    if lam is None:
+        if want_u or not want_b:
+            raise ValueError("lam=None (the first call of a sweep) writes 'b' alone: want_u=False, want_b=True")
+        mdiag = moff = ddiag = doff = None
+        keys = ("b",)
+    else:
+        _dev(lam, "lam")
+        ins["lam"] = lam
+        if (ddiag is None) != (doff is None):
+            raise ValueError("ddiag and doff go together: both or neither")
+        for nm, t in (("mdiag", mdiag), ("moff", moff)):
+            if t is None:
+                raise ValueError(f"{nm} is needed with lam")
+            _dev(t, nm)
+        _band_pair(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (mdiag, moff)", mdiag, moff, ne)
+        ins.update(mdiag=mdiag, moff=moff)
+        if ddiag is not None:
+            for nm, t in (("ddiag", ddiag), ("doff", doff)):
+                _dev(t, nm)
+            _band_pair(f"band lengths must be ne+1, ne = {ne + 1}, {ne} (ddiag, doff)", ddiag, doff, ne)
+            ins.update(ddiag=ddiag, doff=doff)
+        keys = ("v", "a") + (("u",) if want_u else ()) + (("b",) if want_b else ())
+    _nodal(ne, **{k: ins[k] for k in ("Abar", "P", "lam") if k in ins})
+    out = {} if out is None else out
+    res = {k: _out(out.get(k), f"out[{k!r}]", (ne + 1,), Vbar) for k in keys}
+    _no_alias("the outputs must be distinct and none of them an input", res.values(), (Vbar, *ins.values()))
+    _same_device(Vbar, **ins)
+    rc = lib.lssvr_newmark_adjoint_advance(_ptr(lam), _ptr(Vbar), _ptr(Abar), _ptr(P), _ptr(mdiag), _ptr(moff),
+                                           _ptr(ddiag), _ptr(doff), ne, dt, beta, gamma,
+                                           *(_ptr(res.get(k)) for k in ("v", "a", "u", "b")), _stream(stream))
+    _capi.check(rc, "lssvr_newmark_adjoint_advance")
+    return res
+
+
+def newmark_sensitivity(x, Utraj, Z, n0, nquad=2, *, want=NM_SENS_TABLES, Vtraj=None, Atraj=None, phi=None, Brows=None,
+                        band_ends=None, end_kinds=(END_DIRICHLET, END_DIRICHLET), accumulate=False, out=None,
+                        stream=None):
+    """``lssvr_newmark_sensitivity``: the gradients of J with respect to the tables of the Newmark loop of
+    :func:`wave_advance`, summed over a CHUNK of m <= 8 consecutive levels n0 .. n0+m-1 (n0 >= 0), in ONE launch.
+    x float64[ne+1]; Utraj (and Vtraj for "d", Atraj for "rho") float64[N+1, ne+1] the whole stored trajectories (row
+    n = u^n, v^n, acc^n; N >= n0+m-1); Z float64[m, ne+1] the adjoint states of the chunk IN THE ORDER OF THE SWEEP: row
+    i belongs to level n0+m-1-i; phi float64[N+1, R] (row n = phi(t_n)), needed for "f" only.  ``want``: which of "a",
+    "c", "rho", "d", "f" to compute; a table left out is neither computed nor stored, and ``want=()`` is allowed with
+    the end gradients.  ``Brows`` (float64[m, ne+1], the right-hand sides of the chunk's solves, in Z's order) asks for
+    the end gradients too: with ``band_ends`` float64[2] = {sub[0], sup[ne-1]} of the solves' matrix and
+    ``end_kinds``, rows n0 .. n0+m-1 of "g" float64[N+1, 2] and "kappa" float64[2] are written by the same launch.
+    ``accumulate``: every sum (the tables and "kappa") continues from what ``out`` holds instead of from 0 -- a sweep
+    gives the same bits however it is cut into chunks -- and then ``out`` must hold every wanted buffer.  Returns a
+    dict: "a", "c", "rho", "d" -> float64[ne, nquad], "f" -> float64[R, ne, nquad], "g", "kappa".  ``out``: a dict of
+    buffers to write into, by those keys ("g" is never allocated here: its other rows are the caller's).  No
+    synchronisation and no copy; every value is computed in a fixed order (bitwise reproducible)."""
+    lib = _capi.load()
+    for nm, t in (("x", x), ("Utraj", Utraj), ("Z", Z)):
+        _dev(t, nm)
+    ne = _nodes(x, "x")
+    nquad, n0 = int(nquad), int(n0)
+    if not 1 <= nquad <= 5:
+        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
+    want = tuple(want)
+    if len(set(want)) != len(want) or any(k not in NM_SENS_TABLES for k in want):
+        raise ValueError(f"want must name tables of {NM_SENS_TABLES}, each once, got {want!r}")
+    if not want and Brows is None:
+        raise ValueError("nothing to compute: want is empty and Brows is not given")
+    m = _block(ne, "m", Z=Z)
+    if n0 < 0:
+        raise ValueError(f"n0 must be >= 0, got {n0}")
+    ins, R = {"Utraj": Utraj, "Z": Z}, 0
+    for key, nm, t in (("d", "Vtraj", Vtraj), ("rho", "Atraj", Atraj)):
+        if key in want:
+            if t is None:
+                raise ValueError(f"{nm} is needed for the table {key!r}")
+            _dev(t, nm)
+            ins[nm] = t
+    for nm in ("Utraj", "Vtraj", "Atraj"):
+        t = ins.get(nm)
+        if t is not None and (t.dim() != 2 or t.shape[1] != ne + 1 or t.shape[0] < n0 + m or t.shape != Utraj.shape):
+            raise ValueError(f"{nm} must be [N+1, ne+1] with N >= n0+m-1 = {n0 + m - 1} and ne+1 = {ne + 1}, one N for "
+                             f"all trajectories, got {list(t.shape)}")
+    N = int(Utraj.shape[0]) - 1
+    if "f" in want:
+        if phi is None:
+            raise ValueError("phi is needed for the table 'f'")
+        _dev(phi, "phi")
+        if phi.dim() != 2 or phi.shape[0] != N + 1 or not 1 <= phi.shape[1] <= TS_MAX_TERMS:
+            raise ValueError(f"phi must be [N+1, R] = [{N + 1}, 1 .. {TS_MAX_TERMS}], got {list(phi.shape)}")
+        R = int(phi.shape[1])
+        ins["phi"] = phi
+    out = {} if out is None else out
+    accumulate = bool(accumulate)
+    shapes = {k: ((R, ne, nquad) if k == "f" else (ne, nquad)) for k in want}
+    kinds = (END_DIRICHLET, END_DIRICHLET)
+    if Brows is not None:
+        if band_ends is None:
+            raise ValueError("band_ends is needed with Brows")
+        for nm, t in (("Brows", Brows), ("band_ends", band_ends)):
+            _dev(t, nm)
+        if Brows.shape != Z.shape:
+            raise ValueError(f"Brows must have the shape of Z {list(Z.shape)}, got {list(Brows.shape)}")
+        if tuple(band_ends.shape) != (2,):
+            raise ValueError(f"band_ends must be [2], got {list(band_ends.shape)}")
+        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
+        ins.update(Brows=Brows, band_ends=band_ends)
+        if out.get("g") is None:
+            raise ValueError("out['g'] (float64[N+1, 2]) is needed with Brows: the chunk writes its rows of it")
+        shapes.update(g=(N + 1, 2), kappa=(2,))
+    if accumulate and any(out.get(k) is None for k in shapes):
+        raise ValueError("accumulate needs every buffer it continues from in out")
+    res = {k: _out(out.get(k), f"out[{k!r}]", shape, x) for k, shape in shapes.items()}
+    _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
+    _same_device(x, **ins)
+    rc = lib.lssvr_newmark_sensitivity(_ptr(x), ne, nquad, _ptr(Utraj), _ptr(ins.get("Vtraj")), _ptr(ins.get("Atraj")),
+                                       _ptr(Z), n0, m, _ptr(ins.get("phi")), R,
+                                       *(_ptr(res.get(k)) for k in NM_SENS_TABLES), int(accumulate), _ptr(Brows),
+                                       _ptr(band_ends), *kinds, _ptr(res.get("g")), _ptr(res.get("kappa")),
+                                       _stream(stream))
+    _capi.check(rc, "lssvr_newmark_sensitivity")
+    return res
+
+
 def fp64_probe(blocks=4096, iters=4096, use_mfma=False, *, device="cuda:0", reps=5):
     """Measured FP64 FMA (use_mfma False), v_mfma_f64_16x16x4 (True / 1) or v_mfma_f64_4x4x4_4b (3)
     rate in TFLOP/s -- what the roofline's 78.6 TFLOP/s peak sustains in a pure loop."""

@@ -453,6 +453,25 @@ class TransientSensitivity:
         self.times, self.nodes = times, nodes
 
 
+class WaveSensitivity:
+    """What :meth:`FEMLSSVRPrimalSolver.solve_wave_sensitivity` returns for a functional J of the Newmark trajectory:
+    ``value`` = J and its derivatives with respect to the data of the loop, as numpy -- ``d_coef``, ``d_reaction``,
+    ``d_weight``, ``d_damping`` [ne, nquad]: dJ/d(a, c, rho, d at quadrature point q of element e) (without ``coef`` /
+    ``reaction`` / ``weight`` the derivative at the table a = 1 / c = 0 / rho = 1; ``d_damping`` is ``None`` without
+    ``damping``: the velocities are then not stored); ``d_forcing`` [R, ne, nquad]: dJ/df_r there; ``d_u0``, ``d_v0``
+    [ne+1]: dJ/du0, dJ/dv0 at the nodes (``d_u0`` 0 at a Dirichlet end: the start is g(0) there; ``d_v0`` 0 at a
+    Dirichlet end with constant data: its velocity is 0); ``d_end_values`` [nsteps+1, 2]: dJ/dg(t_n) of the left and
+    right end datum, row n for t_n; ``d_kappa`` [2] (0 at a Dirichlet end); ``d_end_accel0`` [2]: dJ/d end_accel0 (0
+    at a Robin end); ``times`` [nsteps+1] and ``nodes``.  Neither the mesh nor dt, beta, gamma is differentiated."""
+
+    def __init__(self, value, tables, d_u0, d_v0, d_end_values, d_kappa, d_end_accel0, times, nodes):
+        self.value = float(value)
+        self.d_coef, self.d_reaction, self.d_weight, self.d_damping, self.d_forcing = (tables.get(k) for k in
+                                                                                       ops.NM_SENS_TABLES)
+        self.d_u0, self.d_v0, self.d_end_values, self.d_kappa = d_u0, d_v0, d_end_values, d_kappa
+        self.d_end_accel0, self.times, self.nodes = d_end_accel0, times, nodes
+
+
 def _evaluate_item(items, method, what, i, x, deriv):
     """``evaluate`` of the solution classes below: item ``i`` of their :class:`EnhancedSolution` list at ``x``."""
     if not items:
@@ -1898,24 +1917,27 @@ class FEMLSSVRPrimalSolver:
         return TransientSolution(p.times[steps].copy(), host["nodal"], enhanced, bands, newton)
 
     # ---- adjoint sensitivities of the BDF loop (no reference counterpart) ---------------------
-    def _check_transient_sensitivity(self, p, goal, goal_steps, goal_weights, observe, max_state_bytes):
+    def _check_transient_sensitivity(self, p, goal, goal_steps, goal_weights, observe, max_state_bytes,
+                                     who="solve_transient_sensitivity", first=1, ntraj=1):
         """The functional of :meth:`solve_transient_sensitivity` on the plan ``p`` of :meth:`_check_transient`, on the
         host and before any device call -> (steps, rows, functional): the ascending steps n with p_n != 0, ``rows``
         [len(steps), ne+1] for a goal (None for a misfit, whose rows need the trajectory), and
-        ``functional(U_steps)`` -> (J, rows) for the nodal states at those steps."""
+        ``functional(U_steps)`` -> (J, rows) for the nodal states at those steps.  ``who``, ``first`` and ``ntraj``: the
+        caller's name, its first admissible step (0 where u^0 counts) and how many trajectories it stores."""
         nsteps, nodes = len(p.times) - 1, p.nodes
         if (goal is None) == (observe is None):
-            raise ValueError("solve_transient_sensitivity needs exactly one of goal (a callable j(x): J = sum_k w_k int "
+            raise ValueError(f"{who} needs exactly one of goal (a callable j(x): J = sum_k w_k int "
                              "j u^{n_k} dx) and observe = (steps, x_obs, d_obs) (J = 1/2 sum (u^{n_k}(x_i) - d_ki)^2)")
-        need = (nsteps + 1) * nodes.size * 8
+        need = ntraj * (nsteps + 1) * nodes.size * 8
         if need > max_state_bytes:
-            raise ValueError(f"the stored trajectory needs (nsteps+1)(ne+1) 8 = {need} bytes > max_state_bytes = "
+            raise ValueError(f"the stored trajectory needs {'' if ntraj == 1 else f'{ntraj} '}(nsteps+1)(ne+1) 8 = "
+                             f"{need} bytes > max_state_bytes = "
                              f"{max_state_bytes}: checkpointing (recomputing the trajectory in pieces) is not built")
 
         def checked_steps(steps, what):
             steps = list(steps)
-            if not steps or any(isinstance(s, bool) or int(s) != s or not 1 <= int(s) <= nsteps for s in steps):
-                raise ValueError(f"{what} must be step indices in 1 .. nsteps = {nsteps}, got {steps!r}")
+            if not steps or any(isinstance(s, bool) or int(s) != s or not first <= int(s) <= nsteps for s in steps):
+                raise ValueError(f"{what} must be step indices in {first} .. nsteps = {nsteps}, got {steps!r}")
             steps = [int(s) for s in steps]
             if len(set(steps)) != len(steps):
                 raise ValueError(f"{what} must not name a step twice, got {steps!r}")
@@ -2263,6 +2285,40 @@ class FEMLSSVRPrimalSolver:
                              "does not pivot; shorten the step")
         return p
 
+    @staticmethod
+    def _wave_energy_ends(p):
+        """(kinds, kappa) for ``ops.eig_apply`` on every node of a wave problem: all ends as Robin rows, kappa of the
+        problem's Robin ends (eig_apply adds it to K's end diagonal itself, so u^T K u already holds kappa u_end^2)."""
+        return ((ops.END_ROBIN, ops.END_ROBIN),
+                tuple(kp if kd_ == ops.END_ROBIN else 0.0 for kd_, kp in zip(p.kinds, p.kappa)))
+
+    def _wave_first_accel(self, p, D, damped, sz0, MZ, KZ, gram0, ework, v_out, acc_out):
+        """The start of a Newmark loop on the plan ``p`` of :meth:`_check_wave` and the arrays ``D`` of
+        :meth:`_time_setup`: sz0 [2, ne+1] receives [u0, v0], one ``ops.eig_apply`` on it fills MZ, KZ [2, ne+1] and
+        gram0, and the first acceleration solves M_rho acc0 = load(0) - M_d v0 - K u0, Robin rows with
+        g(0) - kappa u0, into ``acc_out`` [1, ne+1]; ``v_out`` [ne+1] receives v0."""
+        kinds, ne, phi, g = p.kinds, p.nodes.size - 1, D.phi, D.g
+        (kd, ko), (md, mo) = D.bands["stiff"], D.bands["mass"]
+        ekinds, ekap = self._wave_energy_ends(p)
+        sz0[0].copy_(D.U[0])
+        sz0[1].copy_(_to_dev(p.v_init, D.dev))
+        ops.eig_apply(kd, ko, md, mo, sz0, ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram0, work=ework)
+        r0 = (phi[0][:, None] * D.loads).sum(dim=0)
+        if damped:
+            dd, do = D.bands["damp"]
+            dv = ops.eig_apply(kd, ko, dd, do, sz0[1:2], ekinds, ekap, work=ework)[0]
+            r0 = r0 - dv[0]
+        r0 = r0 - KZ[0]
+        a_ends = [0.0, 0.0]
+        for i, end in ((0, 0), (1, ne)):
+            if kinds[i] == ops.END_ROBIN:
+                r0[end] += g[0, i]
+            else:
+                a_ends[i] = float(p.accel0[i])
+        v_out.copy_(sz0[1])
+        ops.tridiag_bc_solve_multi(md, mo, r0.unsqueeze(0).contiguous(), kinds, (0.0, 0.0), [a_ends], out=acc_out,
+                                   work=D.work)
+
     def solve_wave(self, u0, v0, t_end, *, nsteps, damping=None, weight=None, forcing=None, end_data=None,
                    end_accel0=None, snapshots=None, enhance=True, beta=0.25, gamma=0.5):
         """rho u_tt + d u_t - (a u')' + c u = f(x, t) for 0 < t <= ``t_end`` with u(x, 0) = ``u0(x)`` and
@@ -2306,33 +2362,13 @@ class FEMLSSVRPrimalSolver:
             if damped:
                 tmp = torch.empty((1,) + tuple(rtab.shape), dtype=torch.float64, device=dev)
                 one = torch.ones(1, dtype=torch.float64, device=dev)
-        # the energy reads every node: all ends as Robin rows, kappa of the problem's Robin ends (eig_apply adds it
-        # to K's end diagonal itself, so u^T K u already holds kappa u_end^2)
-        ekinds = (ops.END_ROBIN, ops.END_ROBIN)
-        ekap = tuple(kp if kd_ == ops.END_ROBIN else 0.0 for kd_, kp in zip(kinds, kappa))
+        ekinds, ekap = self._wave_energy_ends(p)
         VA = torch.empty((2, 2, ne + 1), dtype=torch.float64, device=dev)     # [pair][v, acc]
         SZ = torch.empty((ns + 1, 2, ne + 1), dtype=torch.float64, device=dev)     # [t = 0 and the snapshots][u, v]
         gram = torch.empty((ns + 1, 2, 2, 2), dtype=torch.float64, device=dev)
         MZ, KZ = (torch.empty((2, ne + 1), dtype=torch.float64, device=dev) for _ in range(2))
         ework = ops._scratch(None, ops._capi.load().lssvr_eig_work_bytes(ne, 2), dev)
-        # ---- the first acceleration: M_rho acc0 = load(0) - M_d v0 - K u0, Robin rows with g(0) - kappa u0
-        SZ[0, 0].copy_(U[0])
-        SZ[0, 1].copy_(_to_dev(p.v_init, dev))
-        ops.eig_apply(kd, ko, md, mo, SZ[0], ekinds, ekap, MZ=MZ, KZ=KZ, gram=gram[0], work=ework)
-        r0 = (phi[0][:, None] * loads).sum(dim=0)
-        if damped:
-            dv = ops.eig_apply(kd, ko, dd, do, SZ[0, 1:2], ekinds, ekap, work=ework)[0]
-            r0 = r0 - dv[0]
-        r0 = r0 - KZ[0]
-        a_ends = [0.0, 0.0]
-        for i, end in ((0, 0), (1, ne)):
-            if kinds[i] == ops.END_ROBIN:
-                r0[end] += g[0, i]
-            else:
-                a_ends[i] = float(p.accel0[i])
-        VA[0, 0].copy_(SZ[0, 1])
-        ops.tridiag_bc_solve_multi(md, mo, r0.unsqueeze(0).contiguous(), kinds, (0.0, 0.0), [a_ends], out=VA[0, 1:2],
-                                   work=work)
+        self._wave_first_accel(p, D, damped, SZ[0], MZ, KZ, gram[0], ework, VA[0, 0], VA[0, 1:2])
         cur, new, pr = 0, 1, 0
         ops.wave_advance(None, U[cur:cur + 1], VA[pr, 0:1], VA[pr, 1:2], md, mo, dd, do, loads, phi[1:2], dt, beta,
                          gamma, rhs_out=b)
@@ -2365,6 +2401,121 @@ class FEMLSSVRPrimalSolver:
         energy = 0.5 * (gr[:, 1, 1, 1] + gr[:, 0, 0, 0])
         return WaveSolution(p.times[steps].copy(), sz[1:, 0].copy(), sz[1:, 1].copy(), host["accel"], energy, enhanced,
                             {k: host[k] for k in ("mass", "stiff", "step", "damp", "loads")})
+
+    # ---- adjoint sensitivities of the Newmark loop (no reference counterpart) -----------------
+    def solve_wave_sensitivity(self, u0, v0, t_end, *, nsteps, goal=None, observe=None, goal_steps=None, damping=None,
+                               weight=None, forcing=None, end_data=None, end_accel0=None, beta=0.25, gamma=0.5,
+                               max_state_bytes=2 ** 31):
+        """Derivatives of a functional J of the trajectory of :meth:`solve_wave` (same ``u0``, ``v0``, ``t_end``,
+        ``nsteps``, ``damping``, ``weight``, ``forcing``, ``end_data``, ``end_accel0``, ``beta``, ``gamma``) with
+        respect to the data of the loop, by the discrete adjoint: exact for the discrete scheme, at the cost of one
+        more loop of the same length.  ``goal``: a callable j(x), J = sum_k int j u^{n_k} dx by the quadrature rule of
+        the assembly, over ``goal_steps`` (default ``[nsteps]``); or ``observe=(steps, x_obs, d_obs)`` with d_obs
+        [len(steps), nobs]: the misfit J = 1/2 sum_k sum_i (u^{n_k}(x_i) - d_ki)^2 at points inside the mesh.  Steps
+        are 0 .. nsteps: u^0 counts.
+
+        The forward loop is :meth:`solve_wave`'s, bit for bit, writing every u^n and acc^n (and v^n with ``damping``)
+        into stored trajectories [nsteps+1, ne+1].  The rows p_n = dJ/du^n that are not zero are uploaded once (for a
+        misfit they are formed on the host from the observed steps, one read-back between the loops).  The backward
+        sweep runs the levels nsteps .. 1 in chunks of up to 8: per level ``ops.tridiag_bc_solve_multi`` on the step's
+        bands with zero end data into the chunk's rows and ONE ``ops.newmark_adjoint_advance``, which writes the bars
+        of the level below and the next right-hand side; then ONE ``ops.newmark_sensitivity`` per chunk adds the chunk
+        to the tables.  Two chunk buffers alternate.  Level 0 solves on the M_rho bands and is a chunk of its own; two
+        ``ops.eig_apply`` products (one without damping) give K lambda^0 and M_d lambda^0 for dJ/du0 and dJ/dv0, and
+        one read-back fetches everything.  Neither loop synchronises or copies from the host.  Returns a
+        :class:`WaveSensitivity`; the solver's attributes are left as they are.
+
+        Refused (``ValueError``, before any device call): what :meth:`solve_wave` refuses, both or neither of ``goal``
+        and ``observe``, a step outside 0 .. nsteps or named twice, data of the wrong shape or not finite, and
+        trajectories of more than ``max_state_bytes``: checkpointing is not built."""
+        self._check_nonlinear("solve_wave_sensitivity")
+        p = self._check_wave(u0, v0, t_end, nsteps, damping, weight, forcing, end_data, end_accel0, None, False, beta,
+                             gamma)
+        damped = damping is not None
+        jsteps, rows, functional = self._check_transient_sensitivity(p, goal, goal_steps, None, observe,
+                                                                     max_state_bytes, "solve_wave_sensitivity", 0,
+                                                                     3 if damped else 2)
+        kinds, kappa, dt, q, beta, gamma = p.kinds, p.kappa, p.dt, p.quad, p.beta, p.gamma
+        # ---- the device from here on
+        torch = _torch()
+        nsteps, ne = int(nsteps), p.nodes.size - 1
+        D = self._time_setup(p, False, [("stiff", True, q["c"]), ("mass", False, q["rho"]),
+                                        *([("damp", False, q["d"])] if damped else []), ("step", True, p.shift)],
+                             nbuf=nsteps + 1)
+        dev, x, U, b, loads, work, phi, g = D.dev, D.x, D.U, D.b, D.loads, D.work, D.phi, D.g
+        (kd, ko), (md, mo), (ad, ao) = D.bands["stiff"], D.bands["mass"], D.bands["step"]
+        dd, do = D.bands["damp"] if damped else (None, None)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)      # noqa: E731
+        At = new(nsteps + 1, ne + 1)
+        Vt = new(nsteps + 1 if damped else 2, ne + 1)           # without damping two rows alternate
+        vrow = (lambda n: n) if damped else (lambda n: n % 2)
+        SZ, MZ, KZ, gram = new(2, ne + 1), new(2, ne + 1), new(2, ne + 1), new(2, 2, 2)
+        ework = ops._scratch(None, ops._capi.load().lssvr_eig_work_bytes(ne, 2), dev)
+        self._wave_first_accel(p, D, damped, SZ, MZ, KZ, gram, ework, Vt[0], At[0:1])
+        # the forward loop of solve_wave, every state kept: row n of U, At (and Vt) is the state at t_n
+        ops.wave_advance(None, U[0:1], Vt[0:1], At[0:1], md, mo, dd, do, loads, phi[1:2], dt, beta, gamma, rhs_out=b)
+        for n in range(1, nsteps + 1):
+            ops.tridiag_bc_solve_multi(ad, ao, b, kinds, kappa, g[n:n + 1], out=U[n:n + 1], work=work)
+            last, vo, vn = n == nsteps, vrow(n - 1), vrow(n)
+            ops.wave_advance(U[n:n + 1], U[n - 1:n], Vt[vo:vo + 1], At[n - 1:n], md, mo, dd, do, loads,
+                             None if last else phi[n + 1:n + 2], dt, beta, gamma, V_out=Vt[vn:vn + 1],
+                             Acc_out=At[n:n + 1], rhs_out=None if last else b, rhs=not last)
+        jidx = torch.as_tensor(jsteps, device=dev)
+        if rows is None:
+            _, rows = functional(_read_back(u=U[jidx])["u"])
+        P = _to_dev(rows, dev)                                  # the rows p_n that are not zero
+        prow = {n: P[k] for k, n in enumerate(jsteps)}
+        chunk = ops.NM_SENS_CHUNK
+        Zb, Bb = new(2, chunk, ne + 1), new(2, chunk, ne + 1)
+        bars = torch.zeros((2, 2, ne + 1), dtype=torch.float64, device=dev)      # [pair][vbar, abar]; level N: zeros
+        ub = new(ne + 1)
+        step_ends, mass_ends = (torch.stack((off[0], off[ne - 1])) for off in (ao, mo))
+        want = tuple(k for k in ops.NM_SENS_TABLES if k != "d" or damped)
+        out = dict(g=torch.zeros((nsteps + 1, 2), dtype=torch.float64, device=dev))
+        sens = dict(want=want, Vtraj=Vt if damped else None, Atraj=At, phi=phi, end_kinds=kinds)
+        # the backward sweep: launches on the current stream only
+        ops.newmark_adjoint_advance(None, bars[0, 0], bars[0, 1], None, None, None, None, dt, beta, gamma,
+                                    P=prow.get(nsteps), out=dict(b=Bb[0, 0]))
+        hi, side, pr = nsteps, 0, 0
+        while hi >= 1:
+            m = min(chunk, hi)
+            Z, B = Zb[side, :m], Bb[side, :m]
+            for i in range(m):
+                n = hi - i - 1                                  # lambda^{n+1} and the bars of level n+1 -> level n
+                ops.tridiag_bc_solve_multi(ad, ao, B[i:i + 1], kinds, kappa, None, out=Z[i:i + 1], work=work)
+                bufs = dict(v=bars[1 - pr, 0], a=bars[1 - pr, 1])
+                if n == 0:
+                    bufs["u"] = ub
+                else:
+                    bufs["b"] = B[i + 1] if i + 1 < m else Bb[1 - side, 0]
+                ops.newmark_adjoint_advance(Z[i], bars[pr, 0], bars[pr, 1], md, mo, dd, do, dt, beta, gamma,
+                                            P=prow.get(n), want_u=n == 0, want_b=n > 0, out=bufs)
+                pr = 1 - pr
+            out = ops.newmark_sensitivity(x, U, Z, hi - m + 1, self.nquad, Brows=B, band_ends=step_ends,
+                                          accumulate=hi < nsteps, out=out, **sens)
+            hi, side = hi - m, 1 - side
+        # level 0: M_rho lambda^0 = abar, a Robin end as a natural row; a chunk of its own
+        Z0, A0 = Zb[side, 0:1], bars[pr, 1:2]
+        ops.tridiag_bc_solve_multi(md, mo, A0, kinds, (0.0, 0.0), None, out=Z0, work=work)
+        out = ops.newmark_sensitivity(x, U, Z0, 0, self.nquad, Brows=A0, band_ends=mass_ends, accumulate=True, out=out,
+                                      **sens)
+        ekinds, ekap = self._wave_energy_ends(p)
+        ework1 = ops._scratch(None, ops._capi.load().lssvr_eig_work_bytes(ne, 1), dev)
+        _, KL, _ = ops.eig_apply(kd, ko, md, mo, Z0, ekinds, ekap, work=ework1)
+        DL = ops.eig_apply(kd, ko, dd, do, Z0, ekinds, ekap, work=ework1)[0] if damped else None
+        host = _read_back(ub=ub, vb=bars[pr, 0], kl=KL, dl=DL, u=U[jidx], **out)
+        value, _ = functional(host["u"])
+        d_u0 = host["ub"] - host["kl"][0]
+        d_v0 = host["vb"] - host["dl"][0] if damped else host["vb"].copy()
+        d_g, d_acc = host["g"].copy(), np.zeros(2)
+        for s, end in ((0, 0), (1, -1)):
+            if kinds[s] == ops.END_DIRICHLET:
+                d_acc[s], d_g[0, s] = d_g[0, s], d_u0[end]      # what the pass wrote there is dJ/d(acc^0_end)
+                d_u0[end] = 0.0
+                if not callable(p.end_data[s]):
+                    d_v0[end] = 0.0
+        return WaveSensitivity(value, {k: host[k].copy() for k in want}, d_u0, d_v0, d_g, host["kappa"].copy(), d_acc,
+                               p.times.copy(), p.nodes)
 
     # ---- Dual.py:176-203 --------------------------------------------------------------
     def evaluate_solution(self, x_points):

@@ -1383,6 +1383,85 @@ int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad
                                      double* out_g_host, double* out_kappa_host);
 
 /*
+ * Adjoint sensitivities of the Newmark loop of rho u_tt + d u_t - (a u')' + c u = f(x, t) (no reference counterpart;
+ * DESIGN.md section 34).  ADDITIVE to ABI 7: four new symbols, no existing entry, struct, constant or kernel
+ * instantiation changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * The forward loop is that of lssvr_wave_advance, n = 0 .. N-1, with the scalars c_u2 = dt^2 (1/2 - beta),
+ * c_v1 = dt (1 - gamma), c_m = 1 / (beta dt^2), c_d = gamma / (beta dt), c_va = gamma dt:
+ *   ut = u^n + dt v^n + c_u2 acc^n;   vt = v^n + c_v1 acc^n
+ *   A u^{n+1} = sum_r phi_r(t_{n+1}) L_r + M_rho (c_m ut) + M_d (c_d ut - vt) + end terms,   A = K + c_m M_rho + c_d M_d
+ *   acc^{n+1} = c_m (u^{n+1} - ut);   v^{n+1} = vt + c_va acc^{n+1}
+ * and M_rho acc^0 = load(0) - M_d v^0 - K u^0.  For J = sum_{n=0..N} p_n . u^n the backward sweep carries the bars (ubar,
+ * vbar, abar) of the state of level n+1 (at level N: ubar = p_N, vbar = abar = 0); for n+1 = N .. 1
+ *   B_{n+1} = ubar + c_m (abar + c_va vbar)
+ *   A lambda^{n+1} = B_{n+1}, the forward loop's end kinds and kappa, zero end data      -- lssvr_tridiag_bc_solve_multi
+ *   y = M_rho lambda^{n+1},  z = M_d lambda^{n+1}                                       (all rows)
+ *   ut_bar = c_m y + c_d z - c_m (abar + c_va vbar);   vt_bar = vbar - z
+ *   ubar <- p_n + ut_bar;   vbar <- dt ut_bar + vt_bar;   abar <- c_u2 ut_bar + c_v1 vt_bar   (the bars of level n)
+ * and at level 0  M_rho lambda^0 = abar (a Robin end: a natural row),  dJ/du0 = ubar - K lambda^0,
+ * dJ/dv0 = vbar - M_d lambda^0 (lssvr_eig_apply with both ends as Robin rows).
+ *
+ * lssvr_newmark_adjoint_advance -- ONE launch between two backward solves, one thread per node, nodal DEVICE arrays
+ * [ne+1]: from lam = lambda^{n+1}, (Vbar, Abar) of level n+1, the row P = p_n (NULL: zero), the mass bands
+ * (mdiag [ne+1], moff [ne]) and the damping bands (ddiag, doff; both NULL: d = 0) it writes (V_out, A_out), the bars of
+ * level n, U_out = ubar of level n (NULL: skipped; the last call of a sweep asks for it) and B_out = B_n, the next
+ * right-hand side (NULL: skipped).  lam NULL is the first call of a sweep: B_out = P + c_m (Abar + c_va Vbar) alone, no
+ * bands are read and V_out, A_out, U_out must be NULL.  lam is an input, so no thread reads what another writes; no
+ * output may be one of the inputs or another output.  The order of every sum is fixed (csrc/lssvr_newmark_adj.hpp); at
+ * rows 0 and ne the missing neighbour's term is left out.  Return codes, each before any HIP call: LSSVR_ERR_SIZE for
+ * ne < 1, for dt, beta or gamma not finite and > 0, for V_out, A_out or U_out without lam, and for an output that is
+ * an input or another output; LSSVR_ERR_NULL for a missing Vbar or Abar, B_out missing without lam, mdiag, moff, V_out
+ * or A_out missing with lam, and one of ddiag, doff without the other.
+ *
+ * lssvr_newmark_sensitivity -- ONE launch per chunk of m <= 8 consecutive levels n0 .. n0+m-1, n0 >= 0, summed over the
+ * chunk.  With the notation of lssvr_p1_sensitivity:
+ *   dJ/da_quad[e][q]   = -sum_n (w_q / h_e) dlambda^n_e du^n_e      dJ/dc_quad[e][q]   = -sum_n h_e w_q lambda^n_eq u^n_eq
+ *   dJ/drho_quad[e][q] = -sum_n h_e w_q lambda^n_eq acc^n_eq        dJ/dd_quad[e][q]   = -sum_n h_e w_q lambda^n_eq v^n_eq
+ *   dJ/df_quad[r][e][q] = +sum_n phi_r(t_n) h_e w_q lambda^n_eq
+ *   Dirichlet end:  dJ/dg(t_n) = B_n[end] - off[end] lambda^n[inner]       Robin end:  dJ/dg(t_n) = lambda^n[end],
+ *                                                                          dJ/dkappa = -sum_n lambda^n[end] u^n[end]
+ * DEVICE arrays: x [ne+1]; Utraj, Vtraj, Atraj [N+1][ne+1], the stored trajectories, whole (row n = u^n, v^n, acc^n);
+ * Vtraj is read for gd only and Atraj for grho only, either may be NULL then; Z [m][ne+1] and Brows [m][ne+1], the
+ * adjoint states of the chunk and the right-hand sides of their solves IN THE ORDER OF THE SWEEP: row i belongs to
+ * level n0+m-1-i; phi [N+1][R] (row n = phi(t_n); read for gf only), 0 <= R <= 8, R = 0 only with gf NULL.  ga, gc,
+ * grho, gd [ne*nquad] and gf [R][ne*nquad] receive the gradients in the layout of the input tables; a NULL one is
+ * skipped, stores included.  accumulate = 0: every sum starts from 0; 1: it continues from what the output holds, so
+ * a sweep gives the same bits however it is cut into chunks.  out_g [N+1][2] and out_kappa [2] (both or neither)
+ * receive the end gradients, written by the first thread of the same launch: rows n0 .. n0+m-1 of out_g, and out_kappa
+ * under the same accumulate flag; they need Brows, the end kinds and band_ends [2] = {sub[0], sup[ne-1]} of the matrix
+ * of the chunk's solves (device).  Level 0 is a chunk of its own: its matrix is M_rho, and what a Dirichlet end's entry
+ * of out_g row 0 then holds is dJ/d(acc^0_end).  One thread per table entry, no reduction, no atomics, no
+ * synchronisation, no copy.  Return codes, each before any HIP call: LSSVR_ERR_SIZE for ne < 1, m outside [1, 8],
+ * n0 < 0, R outside [0, 8], R = 0 with gf, an unknown end kind with out_g, or an output that is an input or another
+ * output; LSSVR_ERR_QUAD for nquad outside [1, 5]; LSSVR_ERR_NULL for a missing x, Utraj or Z, for no output at all,
+ * for gf without phi, gd without Vtraj, grho without Atraj, one of out_g and out_kappa without the other, and out_g
+ * without Brows or band_ends.
+ *
+ * The _host entries run the same routines on HOST arrays: no device is touched.  Bit for bit the device's values.
+ */
+int lssvr_newmark_adjoint_advance(const double* lam, const double* Vbar, const double* Abar, const double* P,
+                                  const double* mdiag, const double* moff, const double* ddiag, const double* doff,
+                                  int64_t ne, double dt, double beta, double gamma, double* V_out, double* A_out,
+                                  double* U_out, double* B_out, void* stream);
+int lssvr_newmark_adjoint_advance_host(const double* lam_host, const double* Vbar_host, const double* Abar_host,
+                                       const double* P_host, const double* mdiag_host, const double* moff_host,
+                                       const double* ddiag_host, const double* doff_host, int64_t ne, double dt,
+                                       double beta, double gamma, double* V_out_host, double* A_out_host,
+                                       double* U_out_host, double* B_out_host);
+int lssvr_newmark_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj, const double* Vtraj,
+                              const double* Atraj, const double* Z, int64_t n0, int m, const double* phi, int R,
+                              double* ga, double* gc, double* grho, double* gd, double* gf, int accumulate,
+                              const double* Brows, const double* band_ends, int kind_left, int kind_right,
+                              double* out_g, double* out_kappa, void* stream);
+int lssvr_newmark_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
+                                   const double* Vtraj_host, const double* Atraj_host, const double* Z_host, int64_t n0,
+                                   int m, const double* phi_host, int R, double* ga_host, double* gc_host,
+                                   double* grho_host, double* gd_host, double* gf_host, int accumulate,
+                                   const double* Brows_host, const double* band_ends_host, int kind_left,
+                                   int kind_right, double* out_g_host, double* out_kappa_host);
+
+/*
  * Adjoint of the element solve: sensitivities of the ENHANCEMENT (no reference counterpart).
  * ADDITIVE to ABI 7: three new symbols, no existing entry, struct, constant or kernel instantiation changes,
  * LSSVR_ABI_VERSION stays 7.
