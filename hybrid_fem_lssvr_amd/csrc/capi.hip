@@ -2009,38 +2009,84 @@ int lssvr_p1_sensitivity_host(const double* x_host, int64_t ne, int nquad, const
   return LSSVR_OK;
 }
 
-// Adjoint sensitivities of the BDF loop (timestep_sens.hip).  The device and the host entry share one validated binding.
+// an output (NULL: not given) that is another output or one of the inputs
+static bool aliased(const void* const* outs, int nout, const void* const* ins, int nin) {
+  for (int i = 0; i < nout; ++i) {
+    if (!outs[i]) continue;
+    for (int j = i + 1; j < nout; ++j)
+      if (outs[j] == outs[i]) return true;
+    for (int j = 0; j < nin; ++j)
+      if (ins[j] == outs[i]) return true;
+  }
+  return false;
+}
+
+
+// The chunk pass of the time-loop adjoint sensitivities (chunk_sens.hip).  The two schemes share one validated binding,
+// and the device and the host entry of a scheme share its front.
+// what a scheme says to the shared checks: the words of its messages, and what it has of its own
+struct ChunkSensScheme {
+  int64_t n0_min;              // the lowest first level of a chunk
+  const char* level;           // what n0 counts
+  const char* inputs;          // the inputs that must be given, by name, and whether the scheme's own among them are
+  bool inputs_given;
+  const char* tables;          // the table outputs and out_g, by name
+  double* gd;                  // the scheme's own table output; NULL: none, or not wanted
+  const char* own_null;        // the scheme's own "X must be non-NULL with Y" that applies; NULL: none does
+  const void* own_in[2];       // the scheme's own device inputs (NULL: not given)
+};
+
+static int bind_chunk_sens(lssvr::ChunkSensArgs& a, const ChunkSensScheme& sch, const double* x, int64_t ne, int nquad,
+                           const double* Utraj, const double* Z, int64_t n0, int m, const double* phi, int R,
+                           double* ga, double* gc, double* grho, double* gf, int accumulate, const double* Brows,
+                           const double* band_ends, int kind_left, int kind_right, double* out_g, double* out_kappa) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (m < 1 || m > lssvr::kChunkSensMaxSteps) return fail(LSSVR_ERR_SIZE, "m = %d outside [1, 8]", m);
+  if (n0 < sch.n0_min)
+    return fail(LSSVR_ERR_SIZE, "n0 = %lld: the first %s of a chunk is >= %lld", (long long)n0, sch.level,
+                (long long)sch.n0_min);
+  if (R < 0 || R > lssvr::kChunkSensMaxTerms) return fail(LSSVR_ERR_SIZE, "R = %d outside [0, 8]", R);
+  if (R == 0 && gf) return fail(LSSVR_ERR_SIZE, "R = 0 is allowed only with gf NULL");
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  if (!x || !Utraj || !Z || !sch.inputs_given) return fail(LSSVR_ERR_NULL, "%s must be non-NULL", sch.inputs);
+  if (!ga && !gc && !grho && !sch.gd && !gf && !out_g)
+    return fail(LSSVR_ERR_NULL, "one of %s must be non-NULL", sch.tables);
+  if (gf && !phi) return fail(LSSVR_ERR_NULL, "phi must be non-NULL with gf");
+  if (sch.own_null) return fail(LSSVR_ERR_NULL, "%s", sch.own_null);
+  if (!out_g != !out_kappa) return fail(LSSVR_ERR_NULL, "out_g and out_kappa go together: both or neither");
+  if (out_g) {
+    if (!Brows || !band_ends) return fail(LSSVR_ERR_NULL, "Brows and band_ends must be non-NULL with out_g");
+    if (const int rc = check_kinds(kind_left, kind_right)) return rc;
+  }
+  const void* outs[] = {ga, gc, grho, sch.gd, gf, out_g, out_kappa};
+  const void* ins[] = {x, Utraj, sch.own_in[0], sch.own_in[1], Z, phi, Brows, band_ends};
+  if (aliased(outs, 7, ins, 8))
+    return fail(LSSVR_ERR_SIZE, "%s, out_kappa must be distinct and none of them an input", sch.tables);
+  a = lssvr::ChunkSensArgs{x, Utraj, Z, Brows, phi, band_ends, ne, n0, nquad, m, R, accumulate != 0,
+                           {kind_left, kind_right}, ga, gc, grho, gf, out_g, out_kappa};
+  return LSSVR_OK;
+}
+
+// BDF: n0 >= 1, coef_host and band_mask
 static int bind_ts_sens(lssvr::TsSensArgs& a, const double* x, int64_t ne, int nquad, const double* Utraj,
                         const double* Z, int64_t n0, int m, double inv_dt, const double* coef_host, const double* phi,
                         int R, double* ga, double* gc, double* grho, double* gf, int accumulate, const double* Brows,
                         const double* band_ends, int band_mask, int kind_left, int kind_right,
                         double* out_g, double* out_kappa) {
-  if (const int rc = check_ne(ne)) return rc;
-  if (m < 1 || m > lssvr::kTsSensMaxSteps) return fail(LSSVR_ERR_SIZE, "m = %d outside [1, 8]", m);
-  if (n0 < 1) return fail(LSSVR_ERR_SIZE, "n0 = %lld: the first adjoint step of a chunk is >= 1", (long long)n0);
-  if (R < 0 || R > lssvr::kTsSensMaxTerms) return fail(LSSVR_ERR_SIZE, "R = %d outside [0, 8]", R);
-  if (R == 0 && gf) return fail(LSSVR_ERR_SIZE, "R = 0 is allowed only with gf NULL");
-  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
-  if (!x || !Utraj || !Z || !coef_host) return fail(LSSVR_ERR_NULL, "x, Utraj, Z, coef_host must be non-NULL");
-  if (!ga && !gc && !grho && !gf && !out_g)
-    return fail(LSSVR_ERR_NULL, "one of ga, gc, grho, gf, out_g must be non-NULL");
-  if (gf && !phi) return fail(LSSVR_ERR_NULL, "phi must be non-NULL with gf");
-  if (!out_g != !out_kappa) return fail(LSSVR_ERR_NULL, "out_g and out_kappa go together: both or neither");
+  const ChunkSensScheme sch{1, "adjoint step", "x, Utraj, Z, coef_host", coef_host != nullptr,
+                            "ga, gc, grho, gf, out_g", nullptr, nullptr, {nullptr, nullptr}};
   a = lssvr::TsSensArgs{};
+  if (const int rc = bind_chunk_sens(a, sch, x, ne, nquad, Utraj, Z, n0, m, phi, R, ga, gc, grho, gf, accumulate, Brows,
+                                     band_ends, kind_left, kind_right, out_g, out_kappa))
+    return rc;
   if (out_g) {
-    if (!Brows || !band_ends) return fail(LSSVR_ERR_NULL, "Brows and band_ends must be non-NULL with out_g");
-    if (const int rc = check_kinds(kind_left, kind_right)) return rc;
     if (band_mask < 0 || band_mask >> m)
       return fail(LSSVR_ERR_SIZE, "band_mask = %d has bits beyond the m = %d steps", band_mask, m);
     for (int i = 0; i < m; ++i) a.band_row[i] = (band_mask >> i) & 1;
   }
-  a.x = x, a.Utraj = Utraj, a.Z = Z, a.Brows = Brows, a.phi = phi, a.band_ends = band_ends;
-  a.ne = ne, a.n0 = n0, a.nquad = nquad, a.m = m, a.R = R, a.accumulate = accumulate != 0;
-  a.kind[0] = kind_left, a.kind[1] = kind_right;
   a.inv_dt = inv_dt;
   for (int i = 0; i < m; ++i)
     for (int k = 0; k < 3; ++k) a.coef[i][k] = coef_host[3 * i + k];
-  a.ga = ga, a.gc = gc, a.grho = grho, a.gf = gf, a.out_g = out_g, a.out_kappa = out_kappa;
   return LSSVR_OK;
 }
 
@@ -2053,7 +2099,7 @@ int lssvr_transient_sensitivity(const double* x, int64_t ne, int nquad, const do
   const int rc = bind_ts_sens(a, x, ne, nquad, Utraj, Z, n0, m, inv_dt, coef_host, phi, R, ga, gc, grho, gf, accumulate,
                               Brows, band_ends, band_mask, kind_left, kind_right, out_g, out_kappa);
   if (rc != LSSVR_OK) return rc;
-  return check_launch(lssvr::ts_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "ts_sensitivity");
+  return check_launch(lssvr::chunk_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "ts_sensitivity");
 }
 
 int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
@@ -2067,24 +2113,58 @@ int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad
                               gc_host, grho_host, gf_host, accumulate, Brows_host, band_ends_host, band_mask,
                               kind_left, kind_right, out_g_host, out_kappa_host);
   if (rc != LSSVR_OK) return rc;
-  lssvr::ts_sensitivity_host(a);          // (nquad is checked above: the rule exists)
+  lssvr::chunk_sensitivity_host(a);       // (nquad is checked above: the rule exists)
   return LSSVR_OK;
 }
 
-// Adjoint sensitivities of the Newmark loop (newmark_adjoint.hip).  The device and the host entries share one validated
-// binding each.
-// an output (NULL: not given) that is another output or one of the inputs
-static bool aliased(const void* const* outs, int nout, const void* const* ins, int nin) {
-  for (int i = 0; i < nout; ++i) {
-    if (!outs[i]) continue;
-    for (int j = i + 1; j < nout; ++j)
-      if (outs[j] == outs[i]) return true;
-    for (int j = 0; j < nin; ++j)
-      if (ins[j] == outs[i]) return true;
-  }
-  return false;
+// Newmark: n0 >= 0, Vtraj with gd, Atraj with grho
+static int bind_nm_sens(lssvr::NmSensArgs& a, const double* x, int64_t ne, int nquad, const double* Utraj,
+                        const double* Vtraj, const double* Atraj, const double* Z, int64_t n0, int m, const double* phi,
+                        int R, double* ga, double* gc, double* grho, double* gd, double* gf, int accumulate,
+                        const double* Brows, const double* band_ends, int kind_left, int kind_right, double* out_g,
+                        double* out_kappa) {
+  const ChunkSensScheme sch{0, "level", "x, Utraj, Z", true, "ga, gc, grho, gd, gf, out_g", gd,
+                            gd && !Vtraj      ? "Vtraj must be non-NULL with gd"
+                            : grho && !Atraj ? "Atraj must be non-NULL with grho"
+                                              : nullptr,
+                            {Vtraj, Atraj}};
+  a = lssvr::NmSensArgs{};
+  if (const int rc = bind_chunk_sens(a, sch, x, ne, nquad, Utraj, Z, n0, m, phi, R, ga, gc, grho, gf, accumulate, Brows,
+                                     band_ends, kind_left, kind_right, out_g, out_kappa))
+    return rc;
+  a.Vtraj = Vtraj, a.Atraj = Atraj, a.gd = gd;
+  return LSSVR_OK;
 }
 
+int lssvr_newmark_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj, const double* Vtraj,
+                              const double* Atraj, const double* Z, int64_t n0, int m, const double* phi, int R,
+                              double* ga, double* gc, double* grho, double* gd, double* gf, int accumulate,
+                              const double* Brows, const double* band_ends, int kind_left, int kind_right,
+                              double* out_g, double* out_kappa, void* stream) {
+  lssvr::NmSensArgs a;
+  const int rc = bind_nm_sens(a, x, ne, nquad, Utraj, Vtraj, Atraj, Z, n0, m, phi, R, ga, gc, grho, gd, gf, accumulate,
+                              Brows, band_ends, kind_left, kind_right, out_g, out_kappa);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::chunk_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "newmark_sensitivity");
+}
+
+int lssvr_newmark_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
+                                   const double* Vtraj_host, const double* Atraj_host, const double* Z_host, int64_t n0,
+                                   int m, const double* phi_host, int R, double* ga_host, double* gc_host,
+                                   double* grho_host, double* gd_host, double* gf_host, int accumulate,
+                                   const double* Brows_host, const double* band_ends_host, int kind_left,
+                                   int kind_right, double* out_g_host, double* out_kappa_host) {
+  lssvr::NmSensArgs a;
+  const int rc = bind_nm_sens(a, x_host, ne, nquad, Utraj_host, Vtraj_host, Atraj_host, Z_host, n0, m, phi_host, R,
+                              ga_host, gc_host, grho_host, gd_host, gf_host, accumulate, Brows_host, band_ends_host,
+                              kind_left, kind_right, out_g_host, out_kappa_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::chunk_sensitivity_host(a);       // (nquad is checked above: the rule exists)
+  return LSSVR_OK;
+}
+
+// The adjoint advance of the Newmark loop (newmark_adjoint.hip).  The device and the host entry share one validated
+// binding.
 static int bind_nm_adj(lssvr::NmAdjArgs& a, const double* lam, const double* Vbar, const double* Abar, const double* P,
                        const double* mdiag, const double* moff, const double* ddiag, const double* doff, int64_t ne,
                        double dt, double beta, double gamma, double* V_out, double* A_out, double* U_out,
@@ -2135,68 +2215,6 @@ int lssvr_newmark_adjoint_advance_host(const double* lam_host, const double* Vba
                              ne, dt, beta, gamma, V_out_host, A_out_host, U_out_host, B_out_host);
   if (rc != LSSVR_OK) return rc;
   lssvr::newmark_adjoint_advance_host(a);
-  return LSSVR_OK;
-}
-
-static int bind_nm_sens(lssvr::NmSensArgs& a, const double* x, int64_t ne, int nquad, const double* Utraj,
-                        const double* Vtraj, const double* Atraj, const double* Z, int64_t n0, int m, const double* phi,
-                        int R, double* ga, double* gc, double* grho, double* gd, double* gf, int accumulate,
-                        const double* Brows, const double* band_ends, int kind_left, int kind_right, double* out_g,
-                        double* out_kappa) {
-  if (const int rc = check_ne(ne)) return rc;
-  if (m < 1 || m > lssvr::kNmSensMaxSteps) return fail(LSSVR_ERR_SIZE, "m = %d outside [1, 8]", m);
-  if (n0 < 0) return fail(LSSVR_ERR_SIZE, "n0 = %lld: the first level of a chunk is >= 0", (long long)n0);
-  if (R < 0 || R > lssvr::kNmSensMaxTerms) return fail(LSSVR_ERR_SIZE, "R = %d outside [0, 8]", R);
-  if (R == 0 && gf) return fail(LSSVR_ERR_SIZE, "R = 0 is allowed only with gf NULL");
-  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
-  if (!x || !Utraj || !Z) return fail(LSSVR_ERR_NULL, "x, Utraj, Z must be non-NULL");
-  if (!ga && !gc && !grho && !gd && !gf && !out_g)
-    return fail(LSSVR_ERR_NULL, "one of ga, gc, grho, gd, gf, out_g must be non-NULL");
-  if (gf && !phi) return fail(LSSVR_ERR_NULL, "phi must be non-NULL with gf");
-  if (gd && !Vtraj) return fail(LSSVR_ERR_NULL, "Vtraj must be non-NULL with gd");
-  if (grho && !Atraj) return fail(LSSVR_ERR_NULL, "Atraj must be non-NULL with grho");
-  if (!out_g != !out_kappa) return fail(LSSVR_ERR_NULL, "out_g and out_kappa go together: both or neither");
-  if (out_g) {
-    if (!Brows || !band_ends) return fail(LSSVR_ERR_NULL, "Brows and band_ends must be non-NULL with out_g");
-    if (const int rc = check_kinds(kind_left, kind_right)) return rc;
-  }
-  const void* outs[] = {ga, gc, grho, gd, gf, out_g, out_kappa};
-  const void* ins[] = {x, Utraj, Vtraj, Atraj, Z, phi, Brows, band_ends};
-  if (aliased(outs, 7, ins, 8))
-    return fail(LSSVR_ERR_SIZE, "ga, gc, grho, gd, gf, out_g, out_kappa must be distinct and none of them an input");
-  a = lssvr::NmSensArgs{};
-  a.x = x, a.Utraj = Utraj, a.Vtraj = Vtraj, a.Atraj = Atraj, a.Z = Z, a.Brows = Brows, a.phi = phi;
-  a.band_ends = band_ends;
-  a.ne = ne, a.n0 = n0, a.nquad = nquad, a.m = m, a.R = R, a.accumulate = accumulate != 0;
-  a.kind[0] = kind_left, a.kind[1] = kind_right;
-  a.ga = ga, a.gc = gc, a.grho = grho, a.gd = gd, a.gf = gf, a.out_g = out_g, a.out_kappa = out_kappa;
-  return LSSVR_OK;
-}
-
-int lssvr_newmark_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj, const double* Vtraj,
-                              const double* Atraj, const double* Z, int64_t n0, int m, const double* phi, int R,
-                              double* ga, double* gc, double* grho, double* gd, double* gf, int accumulate,
-                              const double* Brows, const double* band_ends, int kind_left, int kind_right,
-                              double* out_g, double* out_kappa, void* stream) {
-  lssvr::NmSensArgs a;
-  const int rc = bind_nm_sens(a, x, ne, nquad, Utraj, Vtraj, Atraj, Z, n0, m, phi, R, ga, gc, grho, gd, gf, accumulate,
-                              Brows, band_ends, kind_left, kind_right, out_g, out_kappa);
-  if (rc != LSSVR_OK) return rc;
-  return check_launch(lssvr::newmark_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "newmark_sensitivity");
-}
-
-int lssvr_newmark_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
-                                   const double* Vtraj_host, const double* Atraj_host, const double* Z_host, int64_t n0,
-                                   int m, const double* phi_host, int R, double* ga_host, double* gc_host,
-                                   double* grho_host, double* gd_host, double* gf_host, int accumulate,
-                                   const double* Brows_host, const double* band_ends_host, int kind_left,
-                                   int kind_right, double* out_g_host, double* out_kappa_host) {
-  lssvr::NmSensArgs a;
-  const int rc = bind_nm_sens(a, x_host, ne, nquad, Utraj_host, Vtraj_host, Atraj_host, Z_host, n0, m, phi_host, R,
-                              ga_host, gc_host, grho_host, gd_host, gf_host, accumulate, Brows_host, band_ends_host,
-                              kind_left, kind_right, out_g_host, out_kappa_host);
-  if (rc != LSSVR_OK) return rc;
-  lssvr::newmark_sensitivity_host(a);     // (nquad is checked above: the rule exists)
   return LSSVR_OK;
 }
 

@@ -563,36 +563,7 @@ struct SensArgs {
 hipError_t p1_sensitivity(const SensArgs& a, hipStream_t s);
 bool p1_sensitivity_host(const SensArgs& a);     // false: no such quadrature rule
 
-// timestep_sens.hip: adjoint sensitivities of the BDF loop.  One chunk of m <= 8 consecutive
-// adjoint steps n0 .. n0+m-1, summed over the chunk into the tables.  Every array that runs over time is handed over
-// whole and indexed with the step n: Utraj, phi, out_g.  The rows of Z and Brows, coef and band_row stand in the order
-// of the backward sweep: row i belongs to step n0 + m - 1 - i.
-constexpr int kTsSensMaxSteps = 8;   // steps per chunk
-constexpr int kTsSensMaxTerms = 8;   // terms of the separable forcing (TS_MAX_TERMS of the forward loop)
-struct TsSensArgs {
-  const double* x;                  // nodes [ne+1]
-  const double* Utraj;              // the forward trajectory [N+1][ne+1]: row n = u^n; rows n0-2 .. n0+m-1 are read
-  const double* Z;                  // [m][ne+1]: the adjoint states of the chunk
-  const double* Brows;              // [m][ne+1]: their right-hand sides; read for out_g at a Dirichlet end
-  const double* phi;                // [N][R]: row n-1 = phi(t_n), the table the forward loop feeds ts_rhs from; gf only
-  const double* band_ends;          // [2][2]: {sub[0], sup[ne-1]} of two step matrices; read for out_g only
-  int64_t ne, n0;
-  int nquad, m, R, accumulate;      // accumulate: the sums continue from what the outputs hold (0: from 0)
-  int kind[2];                      // LSSVR_END_*; read for out_g only
-  int band_row[kTsSensMaxSteps];    // which row of band_ends is step row i's matrix
-  double inv_dt;
-  double coef[kTsSensMaxSteps][3];  // (alpha, beta0, beta1) of step row i
-  double* ga;                       // dJ/da_quad, dJ/dc_quad, dJ/drho_quad [ne*nquad]; nullptr: skipped
-  double* gc;
-  double* grho;
-  double* gf;                       // dJ/df_quad [R][ne*nquad]
-  double* out_g;                    // [N+1][2]: rows n0 .. n0+m-1 are written; nullptr: no end gradients
-  double* out_kappa;                // [2]
-};
-hipError_t ts_sensitivity(const TsSensArgs& a, hipStream_t s);
-bool ts_sensitivity_host(const TsSensArgs& a);   // false: no such quadrature rule
-
-// newmark_adjoint.hip: adjoint sensitivities of the Newmark loop.  One case; nodal vectors
+// newmark_adjoint.hip: the adjoint advance of the Newmark loop.  One case; nodal vectors
 // [ne+1].  The scalars are those of wave_coefficients.
 struct NmAdjArgs {
   const double* lam;                // lambda^{n+1}; nullptr: the first call of a sweep, B_out from (P, Vbar, Abar) alone
@@ -613,33 +584,46 @@ struct NmAdjArgs {
 hipError_t newmark_adjoint_advance(const NmAdjArgs& a, hipStream_t s);
 void newmark_adjoint_advance_host(const NmAdjArgs& a);
 
-// One chunk of m <= 8 consecutive levels n0 .. n0+m-1 (n0 >= 0), summed over the chunk into the tables.  Every array
-// that runs over time is handed over whole and indexed with the level n: Utraj, Vtraj, Atraj, phi, out_g.  The rows of Z
-// and Brows stand in the order of the backward sweep: row i belongs to level n0 + m - 1 - i.
-constexpr int kNmSensMaxSteps = 8;   // levels per chunk
-constexpr int kNmSensMaxTerms = 8;   // terms of the separable forcing
-struct NmSensArgs {
+// chunk_sens.hip: the chunk pass of the adjoint sensitivities of the BDF loop and of the Newmark
+// loop (section 34).  One chunk of m <= 8 consecutive levels n0 .. n0+m-1 of the backward sweep, summed over the chunk
+// into the tables.  Every array that runs over time is handed over whole and indexed with the level n: the
+// trajectories, phi, out_g.  The rows of Z and Brows (and what a scheme adds per step row) stand in the order of the
+// sweep: row i belongs to level n0 + m - 1 - i.
+constexpr int kChunkSensMaxSteps = 8;   // levels per chunk
+constexpr int kChunkSensMaxTerms = 8;   // terms of the separable forcing (TS_MAX_TERMS of the forward loops)
+struct ChunkSensArgs {
   const double* x;                  // nodes [ne+1]
-  const double* Utraj;              // [N+1][ne+1]: row n = u^n; read for ga, gc and out_kappa
-  const double* Vtraj;              // row n = v^n; read for gd only
-  const double* Atraj;              // row n = acc^n; read for grho only
+  const double* Utraj;              // the forward trajectory [N+1][ne+1]: row n = u^n
   const double* Z;                  // [m][ne+1]: the adjoint states of the chunk
   const double* Brows;              // [m][ne+1]: their right-hand sides; read for out_g at a Dirichlet end
-  const double* phi;                // [N+1][R]: row n = phi(t_n); gf only
-  const double* band_ends;          // [2]: {sub[0], sup[ne-1]} of the chunk's matrix; read for out_g only
+  const double* phi;                // [.][R]: the scheme says which row is phi(t_n); gf only
+  const double* band_ends;          // rows {sub[0], sup[ne-1]} of the chunk's matrices; read for out_g only
   int64_t ne, n0;
   int nquad, m, R, accumulate;      // accumulate: the sums continue from what the outputs hold (0: from 0)
   int kind[2];                      // LSSVR_END_*; read for out_g only
-  double* ga;                       // dJ/d(a, c, rho, d)_quad [ne*nquad]; nullptr: skipped
+  double* ga;                       // dJ/da_quad, dJ/dc_quad, dJ/drho_quad [ne*nquad]; nullptr: skipped
   double* gc;
   double* grho;
-  double* gd;
   double* gf;                       // dJ/df_quad [R][ne*nquad]
   double* out_g;                    // [N+1][2]: rows n0 .. n0+m-1 are written; nullptr: no end gradients
   double* out_kappa;                // [2]
 };
-hipError_t newmark_sensitivity(const NmSensArgs& a, hipStream_t s);
-bool newmark_sensitivity_host(const NmSensArgs& a);   // false: no such quadrature rule
+// BDF (n0 >= 1): rows n0-2 .. n0+m-1 of Utraj are read; phi [N][R], row n-1 = phi(t_n), the table the forward loop feeds
+// ts_rhs from; band_ends [2][2], two step matrices
+struct TsSensArgs : ChunkSensArgs {
+  int band_row[kChunkSensMaxSteps];    // which row of band_ends is step row i's matrix
+  double inv_dt;
+  double coef[kChunkSensMaxSteps][3];  // (alpha, beta0, beta1) of step row i
+};
+// Newmark (n0 >= 0): Utraj is read for ga, gc and out_kappa; phi [N+1][R], row n = phi(t_n); band_ends [2], one matrix
+struct NmSensArgs : ChunkSensArgs {
+  const double* Vtraj;              // [N+1][ne+1]: row n = v^n; read for gd only
+  const double* Atraj;              // row n = acc^n; read for grho only
+  double* gd;                       // dJ/dd_quad [ne*nquad]; nullptr: skipped
+};
+// Args: TsSensArgs or NmSensArgs
+template <class Args> hipError_t chunk_sensitivity(const Args& a, hipStream_t s);
+template <class Args> bool chunk_sensitivity_host(const Args& a);   // false: no such quadrature rule
 
 // enhance_adjoint.hip: the adjoint of the element solve.  From W and Wbar = dJ/dW, per element one
 // more solve with the forward matrix and a second sweep over the points: the pair (dJ/dg_l, dJ/dg_r) of every element

@@ -1,5 +1,5 @@
-// The routines behind every value of newmark_adjoint.hip: the device kernels and the host
-// mirrors call them, and with -ffp-contract=off they are bit-equal.
+// The routines behind every value of newmark_adjoint.hip: the device kernel and the host mirror
+// call them, and with -ffp-contract=off they are bit-equal.
 #pragma once
 #include "lssvr_sens.hpp"
 
@@ -52,92 +52,6 @@ LSSVR_SENS_HD void nm_adj_row(const NmAdjArgs& a, int64_t i) {
   a.A_out[i] = an;
   if (a.U_out) a.U_out[i] = ub;
   if (a.B_out) a.B_out[i] = ub + a.c_m * (an + a.c_va * vn);
-}
-
-// Entry idx = e * nquad + k of the tables ga, gc, grho, gd and gf[r], for the m levels of the chunk.  Row i of Z belongs
-// to level n = n0 + m - 1 - i: the rows stand in the order in which the backward sweep produced them, n descending.
-// With xi, w the point and weight k of the rule on [0, 1], h = x[e+1] - x[e], om = 1 - xi, wh = w / h, hw = h w (each
-// formed once), (u0, u1) = u^n[e], u^n[e+1], (a0, a1) of acc^n, (v0, v1) of v^n and (z0, z1) = Z[i][e], Z[i][e+1], every
-// sum starts from
-//   s = accumulate ? what the output holds : 0
-// and takes the levels one after the other, i = 0 .. m-1, one rounding per operation:
-//   t   = hw (z0 om + z1 xi)
-//   sa  = sa - ((wh (z1 - z0)) (u1 - u0))
-//   sc  = sc - (t (u0 om + u1 xi))
-//   sr  = sr - (t (a0 om + a1 xi))
-//   sd  = sd - (t (v0 om + v1 xi))
-//   sf_r = sf_r + phi[n][r] t                                       r = 0 .. R-1
-// and the sums are stored once.  Because a sum CONTINUES from the stored value, a sweep gives the same bits however it
-// is cut into chunks.  A table that is not asked for costs neither arithmetic nor a load of the trajectory that only
-// it reads, nor a store.
-LSSVR_SENS_HD void nm_sens_entry(const NmSensArgs& a, const QuadRule& q, int64_t idx) {
-  const int64_t tab = a.ne * (int64_t)a.nquad, n1 = a.ne + 1;
-  const int64_t e = tab <= (int64_t)0xffffffffu ? (int64_t)((uint32_t)idx / (uint32_t)a.nquad) : idx / a.nquad;
-  const int k = (int)(idx - e * a.nquad);
-  const double xi = sens_pick(q.xi, k), w = sens_pick(q.wt, k);
-  const double h = a.x[e + 1] - a.x[e];
-  const double om = 1.0 - xi, wh = w / h, hw = h * w;
-  const int64_t nhi = a.n0 + a.m - 1;
-  const bool acc = a.accumulate != 0;
-  double sa = acc && a.ga ? a.ga[idx] : 0.0;
-  double sc = acc && a.gc ? a.gc[idx] : 0.0;
-  double sr = acc && a.grho ? a.grho[idx] : 0.0;
-  double sd = acc && a.gd ? a.gd[idx] : 0.0;
-  double sf[kNmSensMaxTerms];
-#pragma unroll
-  for (int r = 0; r < kNmSensMaxTerms; ++r) sf[r] = acc && a.gf && r < a.R ? a.gf[(int64_t)r * tab + idx] : 0.0;
-  for (int i = 0; i < a.m; ++i) {
-    const int64_t n = nhi - i, o = n * n1 + e;
-    const double* z = a.Z + (int64_t)i * n1 + e;
-    const double z0 = z[0], z1 = z[1];
-    const double t = hw * (z0 * om + z1 * xi);
-    if (a.ga || a.gc) {
-      const double u0 = a.Utraj[o], u1 = a.Utraj[o + 1];
-      if (a.ga) sa = sa - ((wh * (z1 - z0)) * (u1 - u0));
-      if (a.gc) sc = sc - (t * (u0 * om + u1 * xi));
-    }
-    if (a.grho) sr = sr - (t * (a.Atraj[o] * om + a.Atraj[o + 1] * xi));
-    if (a.gd) sd = sd - (t * (a.Vtraj[o] * om + a.Vtraj[o + 1] * xi));
-    if (a.gf) {
-      const double* phi = a.phi + n * a.R;
-#pragma unroll
-      for (int r = 0; r < kNmSensMaxTerms; ++r)
-        if (r < a.R) sf[r] = sf[r] + phi[r] * t;
-    }
-  }
-  if (a.ga) a.ga[idx] = sa;
-  if (a.gc) a.gc[idx] = sc;
-  if (a.grho) a.grho[idx] = sr;
-  if (a.gd) a.gd[idx] = sd;
-  if (a.gf) {
-#pragma unroll
-    for (int r = 0; r < kNmSensMaxTerms; ++r)
-      if (r < a.R) a.gf[(int64_t)r * tab + idx] = sf[r];
-  }
-}
-
-// The end gradients of the chunk: out_g[n][s] of every level n of the chunk, and out_kappa[s] continued from what it
-// holds (accumulate) or from 0.  With z = Z[i], B = Brows[i] (the right-hand side of the solve that gave z), u = u^n
-// and (s0, sn) = band_ends, the end entries {sub[0], sup[ne-1]} of that solve's matrix:
-//   Dirichlet end:  out_g[n][0] = B_0 - s0 z_1,   out_g[n][1] = B_ne - sn z_{ne-1};   kappa is left alone
-//   Robin end:      out_g[n][s] = z_end;          kappa_s = kappa_s - (z_end u_end),   i = 0 .. m-1 in turn
-LSSVR_SENS_HD void nm_sens_ends(const NmSensArgs& a) {
-  const int64_t n1 = a.ne + 1, nhi = a.n0 + a.m - 1;
-  for (int s = 0; s < 2; ++s) {
-    const int64_t end = s ? a.ne : 0, inner = s ? a.ne - 1 : 1;
-    double kap = a.accumulate ? a.out_kappa[s] : 0.0;
-    for (int i = 0; i < a.m; ++i) {
-      const int64_t n = nhi - i;
-      const double* z = a.Z + (int64_t)i * n1;
-      if (a.kind[s] == LSSVR_END_ROBIN) {
-        a.out_g[2 * n + s] = z[end];
-        kap = kap - (z[end] * a.Utraj[n * n1 + end]);
-      } else {
-        a.out_g[2 * n + s] = a.Brows[(int64_t)i * n1 + end] - a.band_ends[s] * z[inner];
-      }
-    }
-    a.out_kappa[s] = kap;
-  }
 }
 
 }  // namespace lssvr

@@ -25,15 +25,32 @@ LSSVR_SENS_HD double sens_pick(const double (&t)[5], int k) {
   return v;
 }
 
+// Entry idx = e * nquad + k of a table [ne][nquad], the start of every sensitivity pass: the element e and, with xi, w
+// the point and weight k of the rule on [0, 1] and h = x[e+1] - x[e], om = 1 - xi, wh = w / h, hw = h w, each formed
+// once
+struct SensPoint {
+  int64_t e;
+  double xi, w, om, wh, hw;
+};
+LSSVR_SENS_HD SensPoint sens_point(const double* x, int64_t ne, int nquad, const QuadRule& q, int64_t idx) {
+  // (a table below 2^32 entries: the 32-bit quotient is the same number and a fraction of the instructions)
+  const int64_t e = ne * (int64_t)nquad <= (int64_t)0xffffffffu ? (int64_t)((uint32_t)idx / (uint32_t)nquad)
+                                                               : idx / nquad;
+  const int k = (int)(idx - e * nquad);
+  const double xi = sens_pick(q.xi, k), w = sens_pick(q.wt, k);
+  const double h = x[e + 1] - x[e];
+  return SensPoint{e, xi, w, 1.0 - xi, w / h, h * w};
+}
+
 // U and Z of case j
 LSSVR_SENS_HD const double* sens_u(const SensArgs& a, int j) {
   return a.U + (a.nu == 1 ? 0 : (int64_t)j * (a.ne + 1));
 }
 LSSVR_SENS_HD const double* sens_z(const SensArgs& a, int j) { return a.Z + (int64_t)j * (a.ne + 1); }
 
-// Entry idx = e * nquad + k of the four tables, for every case.  With xi, w the point and weight k of the rule on
-// [0, 1], h = x[e+1] - x[e], (u0, u1) = U[j][e], U[j][e+1] and (z0, z1) likewise, the order of every operation:
-//   du = u1 - u0;   dz = z1 - z0;   om = 1 - xi
+// Entry idx = e * nquad + k of the four tables, for every case.  With xi, w, h, om of sens_point,
+// (u0, u1) = U[j][e], U[j][e+1] and (z0, z1) likewise, the order of every operation:
+//   du = u1 - u0;   dz = z1 - z0
 //   uq = u0 om + u1 xi;             zq = z0 om + z1 xi
 //   ga = -(((w / h) dz) du)
 //   gb = -((w zq) du)
@@ -43,23 +60,18 @@ LSSVR_SENS_HD const double* sens_z(const SensArgs& a, int j) { return a.Z + (int
 // it needs nor a store.
 LSSVR_SENS_HD void sens_entry(const SensArgs& a, const QuadRule& q, int64_t idx) {
   const int64_t tab = a.ne * (int64_t)a.nquad;
-  // (a table below 2^32 entries: the 32-bit quotient is the same number and a fraction of the instructions)
-  const int64_t e = tab <= (int64_t)0xffffffffu ? (int64_t)((uint32_t)idx / (uint32_t)a.nquad) : idx / a.nquad;
-  const int k = (int)(idx - e * a.nquad);
-  const double xi = sens_pick(q.xi, k), w = sens_pick(q.wt, k);
-  const double h = a.x[e + 1] - a.x[e];
-  const double om = 1.0 - xi, wh = w / h, hw = h * w;
+  const SensPoint p = sens_point(a.x, a.ne, a.nquad, q, idx);
   for (int j = 0; j < a.nc; ++j) {
-    const double* u = sens_u(a, j);
-    const double* z = sens_z(a, j);
-    const double u0 = u[e], u1 = u[e + 1], z0 = z[e], z1 = z[e + 1];
+    const double* u = sens_u(a, j) + p.e;
+    const double* z = sens_z(a, j) + p.e;
+    const double u0 = u[0], u1 = u[1], z0 = z[0], z1 = z[1];
     const double du = u1 - u0;
-    const double zq = z0 * om + z1 * xi;
+    const double zq = z0 * p.om + z1 * p.xi;
     const int64_t o = (int64_t)j * tab + idx;
-    if (a.ga) a.ga[o] = -((wh * (z1 - z0)) * du);
-    if (a.gb) a.gb[o] = -((w * zq) * du);
-    if (a.gc) a.gc[o] = -((hw * zq) * (u0 * om + u1 * xi));
-    if (a.gf) a.gf[o] = hw * zq;
+    if (a.ga) a.ga[o] = -((p.wh * (z1 - z0)) * du);
+    if (a.gb) a.gb[o] = -((p.w * zq) * du);
+    if (a.gc) a.gc[o] = -((p.hw * zq) * (u0 * p.om + u1 * p.xi));
+    if (a.gf) a.gf[o] = p.hw * zq;
   }
 }
 

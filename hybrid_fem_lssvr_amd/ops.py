@@ -2346,6 +2346,76 @@ def enhance_adjoint(x, W, Wbar, M, gamma, n_colloc, rhs_values, *, a_values=None
     return res
 
 
+# ---- the chunk pass of the time-loop adjoint sensitivities (DESIGN.md sections 32 and 34) ------------------------------
+def _chunk_sens(tables, n0_min, phi_rows, band_shape, x, Utraj, Z, n0, nquad, want, trajs, phi, Brows, band_ends,
+                end_kinds, accumulate, out):
+    """What :func:`ts_sensitivity` and :func:`newmark_sensitivity` share: every check of the chunk's arguments, the
+    ``accumulate`` rule, the allocation of the outputs and the alias and device checks.  ``tables``: the scheme's keys of
+    ``want``; ``n0_min``: its lowest first level; ``phi_rows``: how many rows more than N its phi has; ``band_shape``:
+    the shape of its ``band_ends``; ``trajs``: {name: (table, tensor)}, its own trajectories, each needed for one
+    table.  Returns (ne, nquad, n0, m, R, kinds, ins, res): ``ins`` the inputs given, by name, and ``res`` the
+    outputs."""
+    for nm, t in (("x", x), ("Utraj", Utraj), ("Z", Z)):
+        _dev(t, nm)
+    ne = _nodes(x, "x")
+    nquad, n0 = int(nquad), int(n0)
+    if not 1 <= nquad <= 5:
+        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
+    want = tuple(want)
+    if len(set(want)) != len(want) or any(k not in tables for k in want):
+        raise ValueError(f"want must name tables of {tables}, each once, got {want!r}")
+    if not want and Brows is None:
+        raise ValueError("nothing to compute: want is empty and Brows is not given")
+    m = _block(ne, "m", Z=Z)
+    if n0 < n0_min:
+        raise ValueError(f"n0 must be >= {n0_min}, got {n0}")
+    ins, R = {"Utraj": Utraj, "Z": Z}, 0
+    for nm, (key, t) in trajs.items():
+        if key in want:
+            if t is None:
+                raise ValueError(f"{nm} is needed for the table {key!r}")
+            _dev(t, nm)
+            ins[nm] = t
+    for nm in ("Utraj", *trajs):
+        t = ins.get(nm)
+        if t is not None and (t.dim() != 2 or t.shape[1] != ne + 1 or t.shape[0] < n0 + m or t.shape != Utraj.shape):
+            raise ValueError(f"{nm} must be [N+1, ne+1] with N >= n0+m-1 = {n0 + m - 1} and ne+1 = {ne + 1}, one N for "
+                             f"all trajectories, got {list(t.shape)}")
+    N = int(Utraj.shape[0]) - 1
+    if "f" in want:
+        if phi is None:
+            raise ValueError("phi is needed for the table 'f'")
+        _dev(phi, "phi")
+        if phi.dim() != 2 or phi.shape[0] != N + phi_rows or not 1 <= phi.shape[1] <= TS_MAX_TERMS:
+            raise ValueError(f"phi must be [N{'+1' * phi_rows}, R] = [{N + phi_rows}, 1 .. {TS_MAX_TERMS}], got "
+                             f"{list(phi.shape)}")
+        R = int(phi.shape[1])
+        ins["phi"] = phi
+    out = {} if out is None else out
+    shapes = {k: ((R, ne, nquad) if k == "f" else (ne, nquad)) for k in want}
+    kinds = (END_DIRICHLET, END_DIRICHLET)
+    if Brows is not None:
+        if band_ends is None:
+            raise ValueError("band_ends is needed with Brows")
+        for nm, t in (("Brows", Brows), ("band_ends", band_ends)):
+            _dev(t, nm)
+        if Brows.shape != Z.shape:
+            raise ValueError(f"Brows must have the shape of Z {list(Z.shape)}, got {list(Brows.shape)}")
+        if tuple(band_ends.shape) != band_shape:
+            raise ValueError(f"band_ends must be {list(band_shape)}, got {list(band_ends.shape)}")
+        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
+        ins.update(Brows=Brows, band_ends=band_ends)
+        if out.get("g") is None:
+            raise ValueError("out['g'] (float64[N+1, 2]) is needed with Brows: the chunk writes its rows of it")
+        shapes.update(g=(N + 1, 2), kappa=(2,))
+    if accumulate and any(out.get(k) is None for k in shapes):
+        raise ValueError("accumulate needs every buffer it continues from in out")
+    res = {k: _out(out.get(k), f"out[{k!r}]", shape, x) for k, shape in shapes.items()}
+    _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
+    _same_device(x, **ins)
+    return ne, nquad, n0, m, R, kinds, ins, res
+
+
 # ---- adjoint sensitivities of the BDF loop (DESIGN.md section 32) -------------------------------------------------------
 TS_SENS_TABLES = ("a", "c", "rho", "f")     # d/d a_quad, c_quad, rho_quad, f_quad[r]: the keys of ``want`` and the result
 TS_SENS_CHUNK = 8                           # most adjoint steps of one launch
@@ -2370,69 +2440,20 @@ def ts_sensitivity(x, Utraj, Z, n0, coef, inv_dt, nquad=2, *, want=TS_SENS_TABLE
     allocated here: its other rows are the caller's).  No synchronisation and no copy; every value is computed in a
     fixed order (bitwise reproducible)."""
     lib = _capi.load()
-    for nm, t in (("x", x), ("Utraj", Utraj), ("Z", Z)):
-        _dev(t, nm)
-    ne = _nodes(x, "x")
-    nquad, n0 = int(nquad), int(n0)
-    if not 1 <= nquad <= 5:
-        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
-    want = tuple(want)
-    if len(set(want)) != len(want) or any(k not in TS_SENS_TABLES for k in want):
-        raise ValueError(f"want must name tables of {TS_SENS_TABLES}, each once, got {want!r}")
-    if not want and Brows is None:
-        raise ValueError("nothing to compute: want is empty and Brows is not given")
-    m = _block(ne, "m", Z=Z)
+    ne, nquad, n0, m, R, kinds, ins, res = _chunk_sens(TS_SENS_TABLES, 1, 0, (2, 2), x, Utraj, Z, n0, nquad, want, {},
+                                                       phi, Brows, band_ends, end_kinds, accumulate, out)
     coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64))
     if coef.shape != (m, 3) or not np.all(np.isfinite(coef)):
         raise ValueError(f"coef must be m = {m} finite triples (alpha, beta0, beta1), got shape {list(coef.shape)}")
     (inv_dt,) = _finite(inv_dt=inv_dt)
-    if n0 < 1:
-        raise ValueError(f"n0 must be >= 1, got {n0}")
-    if Utraj.dim() != 2 or Utraj.shape[1] != ne + 1 or Utraj.shape[0] < n0 + m:
-        raise ValueError(f"Utraj must be [N+1, ne+1] with N >= n0+m-1 = {n0 + m - 1} and ne+1 = {ne + 1}, got "
-                         f"{list(Utraj.shape)}")
-    N = int(Utraj.shape[0]) - 1
-    ins, R = {"Utraj": Utraj, "Z": Z}, 0
-    if "f" in want:
-        if phi is None:
-            raise ValueError("phi is needed for the table 'f'")
-        _dev(phi, "phi")
-        if phi.dim() != 2 or phi.shape[0] != N or not 1 <= phi.shape[1] <= TS_MAX_TERMS:
-            raise ValueError(f"phi must be [N, R] = [{N}, 1 .. {TS_MAX_TERMS}], got {list(phi.shape)}")
-        R = int(phi.shape[1])
-        ins["phi"] = phi
-    out = {} if out is None else out
-    accumulate = bool(accumulate)
-    shapes = {k: ((R, ne, nquad) if k == "f" else (ne, nquad)) for k in want}
-    mask, kinds = 0, (END_DIRICHLET, END_DIRICHLET)
-    if Brows is not None:
-        if band_ends is None:
-            raise ValueError("band_ends is needed with Brows")
-        for nm, t in (("Brows", Brows), ("band_ends", band_ends)):
-            _dev(t, nm)
-        if Brows.shape != Z.shape:
-            raise ValueError(f"Brows must have the shape of Z {list(Z.shape)}, got {list(Brows.shape)}")
-        if tuple(band_ends.shape) != (2, 2):
-            raise ValueError(f"band_ends must be [2, 2], got {list(band_ends.shape)}")
-        rows = [0] * m if band_rows is None else [int(r) for r in band_rows]
-        if len(rows) != m or any(r not in (0, 1) for r in rows):
-            raise ValueError(f"band_rows must be m = {m} values 0 or 1, got {band_rows!r}")
-        mask = sum(r << i for i, r in enumerate(rows))
-        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
-        ins.update(Brows=Brows, band_ends=band_ends)
-        if out.get("g") is None:
-            raise ValueError("out['g'] (float64[N+1, 2]) is needed with Brows: the chunk writes its rows of it")
-        shapes.update(g=(N + 1, 2), kappa=(2,))
-    if accumulate and any(out.get(k) is None for k in shapes):
-        raise ValueError("accumulate needs every buffer it continues from in out")
-    res = {k: _out(out.get(k), f"out[{k!r}]", shape, x) for k, shape in shapes.items()}
-    _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
-    _same_device(x, **ins)
+    rows = [0] * m if band_rows is None or Brows is None else [int(r) for r in band_rows]
+    if len(rows) != m or any(r not in (0, 1) for r in rows):
+        raise ValueError(f"band_rows must be m = {m} values 0 or 1, got {band_rows!r}")
     rc = lib.lssvr_transient_sensitivity(_ptr(x), ne, nquad, _ptr(Utraj), _ptr(Z), n0, m, inv_dt,
-                                  coef.ctypes.data_as(_capi._c_hd), _ptr(phi) if "f" in want else None, R,
-                                  *(_ptr(res.get(k)) for k in TS_SENS_TABLES), int(accumulate), _ptr(Brows),
-                                  _ptr(band_ends), mask, *kinds, _ptr(res.get("g")), _ptr(res.get("kappa")),
-                                  _stream(stream))
+                                         coef.ctypes.data_as(_capi._c_hd), _ptr(ins.get("phi")), R,
+                                         *(_ptr(res.get(k)) for k in TS_SENS_TABLES), int(bool(accumulate)),
+                                         _ptr(Brows), _ptr(band_ends), sum(r << i for i, r in enumerate(rows)), *kinds,
+                                         _ptr(res.get("g")), _ptr(res.get("kappa")), _stream(stream))
     _capi.check(rc, "lssvr_transient_sensitivity")
     return res
 
@@ -2516,67 +2537,12 @@ def newmark_sensitivity(x, Utraj, Z, n0, nquad=2, *, want=NM_SENS_TABLES, Vtraj=
     buffers to write into, by those keys ("g" is never allocated here: its other rows are the caller's).  No
     synchronisation and no copy; every value is computed in a fixed order (bitwise reproducible)."""
     lib = _capi.load()
-    for nm, t in (("x", x), ("Utraj", Utraj), ("Z", Z)):
-        _dev(t, nm)
-    ne = _nodes(x, "x")
-    nquad, n0 = int(nquad), int(n0)
-    if not 1 <= nquad <= 5:
-        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
-    want = tuple(want)
-    if len(set(want)) != len(want) or any(k not in NM_SENS_TABLES for k in want):
-        raise ValueError(f"want must name tables of {NM_SENS_TABLES}, each once, got {want!r}")
-    if not want and Brows is None:
-        raise ValueError("nothing to compute: want is empty and Brows is not given")
-    m = _block(ne, "m", Z=Z)
-    if n0 < 0:
-        raise ValueError(f"n0 must be >= 0, got {n0}")
-    ins, R = {"Utraj": Utraj, "Z": Z}, 0
-    for key, nm, t in (("d", "Vtraj", Vtraj), ("rho", "Atraj", Atraj)):
-        if key in want:
-            if t is None:
-                raise ValueError(f"{nm} is needed for the table {key!r}")
-            _dev(t, nm)
-            ins[nm] = t
-    for nm in ("Utraj", "Vtraj", "Atraj"):
-        t = ins.get(nm)
-        if t is not None and (t.dim() != 2 or t.shape[1] != ne + 1 or t.shape[0] < n0 + m or t.shape != Utraj.shape):
-            raise ValueError(f"{nm} must be [N+1, ne+1] with N >= n0+m-1 = {n0 + m - 1} and ne+1 = {ne + 1}, one N for "
-                             f"all trajectories, got {list(t.shape)}")
-    N = int(Utraj.shape[0]) - 1
-    if "f" in want:
-        if phi is None:
-            raise ValueError("phi is needed for the table 'f'")
-        _dev(phi, "phi")
-        if phi.dim() != 2 or phi.shape[0] != N + 1 or not 1 <= phi.shape[1] <= TS_MAX_TERMS:
-            raise ValueError(f"phi must be [N+1, R] = [{N + 1}, 1 .. {TS_MAX_TERMS}], got {list(phi.shape)}")
-        R = int(phi.shape[1])
-        ins["phi"] = phi
-    out = {} if out is None else out
-    accumulate = bool(accumulate)
-    shapes = {k: ((R, ne, nquad) if k == "f" else (ne, nquad)) for k in want}
-    kinds = (END_DIRICHLET, END_DIRICHLET)
-    if Brows is not None:
-        if band_ends is None:
-            raise ValueError("band_ends is needed with Brows")
-        for nm, t in (("Brows", Brows), ("band_ends", band_ends)):
-            _dev(t, nm)
-        if Brows.shape != Z.shape:
-            raise ValueError(f"Brows must have the shape of Z {list(Z.shape)}, got {list(Brows.shape)}")
-        if tuple(band_ends.shape) != (2,):
-            raise ValueError(f"band_ends must be [2], got {list(band_ends.shape)}")
-        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
-        ins.update(Brows=Brows, band_ends=band_ends)
-        if out.get("g") is None:
-            raise ValueError("out['g'] (float64[N+1, 2]) is needed with Brows: the chunk writes its rows of it")
-        shapes.update(g=(N + 1, 2), kappa=(2,))
-    if accumulate and any(out.get(k) is None for k in shapes):
-        raise ValueError("accumulate needs every buffer it continues from in out")
-    res = {k: _out(out.get(k), f"out[{k!r}]", shape, x) for k, shape in shapes.items()}
-    _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
-    _same_device(x, **ins)
+    ne, nquad, n0, m, R, kinds, ins, res = _chunk_sens(NM_SENS_TABLES, 0, 1, (2,), x, Utraj, Z, n0, nquad, want,
+                                                       {"Vtraj": ("d", Vtraj), "Atraj": ("rho", Atraj)}, phi, Brows,
+                                                       band_ends, end_kinds, accumulate, out)
     rc = lib.lssvr_newmark_sensitivity(_ptr(x), ne, nquad, _ptr(Utraj), _ptr(ins.get("Vtraj")), _ptr(ins.get("Atraj")),
                                        _ptr(Z), n0, m, _ptr(ins.get("phi")), R,
-                                       *(_ptr(res.get(k)) for k in NM_SENS_TABLES), int(accumulate), _ptr(Brows),
+                                       *(_ptr(res.get(k)) for k in NM_SENS_TABLES), int(bool(accumulate)), _ptr(Brows),
                                        _ptr(band_ends), *kinds, _ptr(res.get("g")), _ptr(res.get("kappa")),
                                        _stream(stream))
     _capi.check(rc, "lssvr_newmark_sensitivity")

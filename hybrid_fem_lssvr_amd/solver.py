@@ -132,6 +132,41 @@ def _read_back(**tensors):
             for k, v in tensors.items()}
 
 
+# ---- what the backward sweeps of solve_transient_sensitivity and solve_wave_sensitivity share -------------------------
+def _functional_rows(U, jsteps, rows, functional, zero_rows=0):
+    """Upload of the functional's rows after the forward loop: (jidx, P, prow).  ``jidx``: the steps of the functional,
+    on the device of the trajectory U; P: the rows p_n = dJ/du^n that are not zero, in the order of ``jsteps``, and
+    ``zero_rows`` zero rows after them, in one upload; prow: {step: its row of P}.  ``rows=None`` (a misfit): they are
+    formed on the host from the observed steps, the one read-back between the loops."""
+    jidx = _torch().as_tensor(jsteps, device=U.device)
+    if rows is None:
+        _, rows = functional(_read_back(u=U[jidx])["u"])
+    P = _to_dev(np.concatenate([rows, np.zeros((zero_rows, U.shape[1]))]), U.device)
+    return jidx, P, {n: k for k, n in enumerate(jsteps)}
+
+
+def _sweep_chunks(nsteps, chunk):
+    """The cut of the backward sweep over the levels nsteps .. 1 into chunks of up to ``chunk``: (hi, m, side) with hi the
+    highest level of a chunk, m its length and side the one of the two alternating chunk buffers it fills."""
+    hi, side = nsteps, 0
+    while hi >= 1:
+        m = min(chunk, hi)
+        yield hi, m, side
+        hi, side = hi - m, 1 - side
+
+
+def _dirichlet_u0(kinds, d_u0, d_g):
+    """The fix-up after the read-back: at a Dirichlet end u^0_end is the end value g(t_0), so its derivative moves from
+    d_u0[end] into d_g[0, s] and d_u0[end] becomes 0, in place.  Returns [(s, end, what d_g[0, s] held)] of those ends."""
+    moved = []
+    for s, end in ((0, 0), (1, -1)):
+        if kinds[s] == ops.END_DIRICHLET:
+            moved.append((s, end, d_g[0, s]))
+            d_g[0, s] = d_u0[end]
+            d_u0[end] = 0.0
+    return moved
+
+
 # ---- the scalar rules of solve_transient_adaptive (DESIGN.md section 30): float64, pure --------------------------------
 TS_SAFETY, TS_FAC_MIN, TS_FAC_MAX = 0.9, 0.2, 2.0
 TS_OMEGA_MAX = 2.0              # below the zero-stability limit 1 + sqrt(2) of variable-step BDF2
@@ -2048,22 +2083,16 @@ class FEMLSSVRPrimalSolver:
             ops.ts_rhs(md, mo, U[n - 1:n], None if b1 == 0.0 else U[n - 2:n - 1], loads, phi[n - 1:n], b0, b1, inv_dt,
                        out=b)
             ops.tridiag_bc_solve_multi(*D.bands[al], b, kinds, kappa, g[n - 1:n], out=U[n:n + 1], work=work)
-        jidx = torch.as_tensor(jsteps, device=dev)
-        if rows is None:
-            _, rows = functional(_read_back(u=U[jidx])["u"])
         # the rows p_n that are not zero, and a zero row for every other step (and for lambda^{N+1}, lambda^{N+2})
-        P = _to_dev(np.concatenate([rows, np.zeros((1, ne + 1))]), dev)
-        prow = {n: k for k, n in enumerate(jsteps)}
+        jidx, P, prow = _functional_rows(U, jsteps, rows, functional, zero_rows=1)
         zero, one = P[len(jsteps):], torch.ones((1, 1), dtype=torch.float64, device=dev)
         chunk = ops.TS_SENS_CHUNK
         Zb, Bb = (torch.empty((2, chunk, ne + 1), dtype=torch.float64, device=dev) for _ in range(2))
         band_ends = torch.stack([torch.stack((D.bands[al][1][0], D.bands[al][1][ne - 1])) for al in (bdf1[0], bdf[0])])
         out = dict(g=torch.zeros((nsteps + 1, 2), dtype=torch.float64, device=dev))
         lam1, lam2 = zero, zero                                        # lambda^{n+1}, lambda^{n+2}
-        hi, side = nsteps, 0
         # the backward sweep: launches on the current stream only
-        while hi >= 1:
-            m = min(chunk, hi)
+        for hi, m, side in _sweep_chunks(nsteps, chunk):
             Z, B = Zb[side, :m], Bb[side, :m]
             for i in range(m):
                 n = hi - i
@@ -2077,16 +2106,12 @@ class FEMLSSVRPrimalSolver:
             out = ops.ts_sensitivity(x, U, Z, hi - m + 1, [coefficients(n) for n in steps], inv_dt, self.nquad, phi=phi,
                                      Brows=B, band_ends=band_ends, band_rows=[0 if n == 1 else 1 for n in steps],
                                      end_kinds=kinds, accumulate=hi < nsteps, out=out)
-            hi, side = hi - m, 1 - side
         b0, b1 = coefficients(1)[1], coefficients(2)[2]
         ops.ts_rhs(md, mo, lam1, None if b1 == 0.0 else lam2, zero, one, b0, b1, inv_dt, out=b)       # B_0
         host = _read_back(b0=b, u=U[jidx], **out)
         value, _ = functional(host["u"])
         d_u0, d_g = host["b0"][0].copy(), host["g"].copy()
-        for s, end in ((0, 0), (1, -1)):
-            if kinds[s] == ops.END_DIRICHLET:
-                d_g[0, s] = d_u0[end]
-                d_u0[end] = 0.0
+        _dirichlet_u0(kinds, d_u0, d_g)
         return TransientSensitivity(value, {k: host[k].copy() for k in ops.TS_SENS_TABLES}, d_u0, d_g,
                                     host["kappa"].copy(), p.times.copy(), p.nodes)
 
@@ -2460,11 +2485,8 @@ class FEMLSSVRPrimalSolver:
             ops.wave_advance(U[n:n + 1], U[n - 1:n], Vt[vo:vo + 1], At[n - 1:n], md, mo, dd, do, loads,
                              None if last else phi[n + 1:n + 2], dt, beta, gamma, V_out=Vt[vn:vn + 1],
                              Acc_out=At[n:n + 1], rhs_out=None if last else b, rhs=not last)
-        jidx = torch.as_tensor(jsteps, device=dev)
-        if rows is None:
-            _, rows = functional(_read_back(u=U[jidx])["u"])
-        P = _to_dev(rows, dev)                                  # the rows p_n that are not zero
-        prow = {n: P[k] for k, n in enumerate(jsteps)}
+        jidx, P, prow = _functional_rows(U, jsteps, rows, functional)     # the rows p_n that are not zero
+        prow = {n: P[k] for n, k in prow.items()}
         chunk = ops.NM_SENS_CHUNK
         Zb, Bb = new(2, chunk, ne + 1), new(2, chunk, ne + 1)
         bars = torch.zeros((2, 2, ne + 1), dtype=torch.float64, device=dev)      # [pair][vbar, abar]; level N: zeros
@@ -2476,12 +2498,11 @@ class FEMLSSVRPrimalSolver:
         # the backward sweep: launches on the current stream only
         ops.newmark_adjoint_advance(None, bars[0, 0], bars[0, 1], None, None, None, None, dt, beta, gamma,
                                     P=prow.get(nsteps), out=dict(b=Bb[0, 0]))
-        hi, side, pr = nsteps, 0, 0
-        while hi >= 1:
-            m = min(chunk, hi)
+        pr = 0
+        for hi, m, side in _sweep_chunks(nsteps, chunk):
             Z, B = Zb[side, :m], Bb[side, :m]
             for i in range(m):
-                n = hi - i - 1                                  # lambda^{n+1} and the bars of level n+1 -> level n
+                n = hi - i - 1                                 # lambda^{n+1} and the bars of level n+1 -> level n
                 ops.tridiag_bc_solve_multi(ad, ao, B[i:i + 1], kinds, kappa, None, out=Z[i:i + 1], work=work)
                 bufs = dict(v=bars[1 - pr, 0], a=bars[1 - pr, 1])
                 if n == 0:
@@ -2493,9 +2514,8 @@ class FEMLSSVRPrimalSolver:
                 pr = 1 - pr
             out = ops.newmark_sensitivity(x, U, Z, hi - m + 1, self.nquad, Brows=B, band_ends=step_ends,
                                           accumulate=hi < nsteps, out=out, **sens)
-            hi, side = hi - m, 1 - side
-        # level 0: M_rho lambda^0 = abar, a Robin end as a natural row; a chunk of its own
-        Z0, A0 = Zb[side, 0:1], bars[pr, 1:2]
+        # level 0: M_rho lambda^0 = abar, a Robin end as a natural row; a chunk of its own, in the other buffer
+        Z0, A0 = Zb[1 - side, 0:1], bars[pr, 1:2]
         ops.tridiag_bc_solve_multi(md, mo, A0, kinds, (0.0, 0.0), None, out=Z0, work=work)
         out = ops.newmark_sensitivity(x, U, Z0, 0, self.nquad, Brows=A0, band_ends=mass_ends, accumulate=True, out=out,
                                       **sens)
@@ -2508,12 +2528,10 @@ class FEMLSSVRPrimalSolver:
         d_u0 = host["ub"] - host["kl"][0]
         d_v0 = host["vb"] - host["dl"][0] if damped else host["vb"].copy()
         d_g, d_acc = host["g"].copy(), np.zeros(2)
-        for s, end in ((0, 0), (1, -1)):
-            if kinds[s] == ops.END_DIRICHLET:
-                d_acc[s], d_g[0, s] = d_g[0, s], d_u0[end]      # what the pass wrote there is dJ/d(acc^0_end)
-                d_u0[end] = 0.0
-                if not callable(p.end_data[s]):
-                    d_v0[end] = 0.0
+        for s, end, was in _dirichlet_u0(kinds, d_u0, d_g):
+            d_acc[s] = was                                      # what the pass wrote there is dJ/d(acc^0_end)
+            if not callable(p.end_data[s]):
+                d_v0[end] = 0.0
         return WaveSensitivity(value, {k: host[k].copy() for k in want}, d_u0, d_v0, d_g, host["kappa"].copy(), d_acc,
                                p.times.copy(), p.nodes)
 

@@ -1361,11 +1361,12 @@ int lssvr_p1_sensitivity_host(const double* x_host, int64_t ne, int nquad, const
  * n0 .. n0+m-1 of out_g, and out_kappa under the same accumulate flag; they need Brows, the end kinds, band_ends [2][2]
  * = {sub[0], sup[ne-1]} of two step matrices (device; one per alpha) and band_mask, whose bit i says which of the two
  * is the matrix of step row i.  Without out_g none of these is read, and the four tables may then all be NULL only if
- * out_g is given.  The order of every operation is fixed (csrc/lssvr_ts_sens.hpp), one thread per table entry, no
+ * out_g is given.  The order of every operation is fixed (csrc/lssvr_chunk_sens.hpp: one routine for this entry and
+ * lssvr_newmark_sensitivity, which differ in the scheme it is instantiated with), one thread per table entry, no
  * reduction, no atomics, no synchronisation, no copy.  No output may be one of the inputs or another output.
  * Return codes, each before any HIP call: LSSVR_ERR_SIZE for ne < 1, m outside [1, 8], n0 < 1, R outside [0, 8], R = 0
- * with gf, a band_mask with bits beyond m, or an unknown end kind with out_g; LSSVR_ERR_QUAD for nquad outside [1, 5];
- * LSSVR_ERR_NULL for a missing x, Utraj, Z or coef_host, for no output at all, for gf without phi, for one of out_g and
+ * with gf, a band_mask with bits beyond m, an unknown end kind with out_g, or an output that is an input or another
+ * output; LSSVR_ERR_QUAD for nquad outside [1, 5]; LSSVR_ERR_NULL for a missing x, Utraj, Z or coef_host, for no output at all, for gf without phi, for one of out_g and
  * out_kappa without the other, and for out_g without Brows or band_ends.
  *
  * lssvr_transient_sensitivity_host -- the same routines on HOST arrays: no device is touched.  Bit for bit the device's values.
@@ -1431,8 +1432,8 @@ int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad
  * receive the end gradients, written by the first thread of the same launch: rows n0 .. n0+m-1 of out_g, and out_kappa
  * under the same accumulate flag; they need Brows, the end kinds and band_ends [2] = {sub[0], sup[ne-1]} of the matrix
  * of the chunk's solves (device).  Level 0 is a chunk of its own: its matrix is M_rho, and what a Dirichlet end's entry
- * of out_g row 0 then holds is dJ/d(acc^0_end).  One thread per table entry, no reduction, no atomics, no
- * synchronisation, no copy.  Return codes, each before any HIP call: LSSVR_ERR_SIZE for ne < 1, m outside [1, 8],
+ * of out_g row 0 then holds is dJ/d(acc^0_end).  The order of every operation is fixed (csrc/lssvr_chunk_sens.hpp),
+ * one thread per table entry, no reduction, no atomics, no synchronisation, no copy.  Return codes, each before any HIP call: LSSVR_ERR_SIZE for ne < 1, m outside [1, 8],
  * n0 < 0, R outside [0, 8], R = 0 with gf, an unknown end kind with out_g, or an output that is an input or another
  * output; LSSVR_ERR_QUAD for nquad outside [1, 5]; LSSVR_ERR_NULL for a missing x, Utraj or Z, for no output at all,
  * for gf without phi, gd without Vtraj, grho without Atraj, one of out_g and out_kappa without the other, and out_g

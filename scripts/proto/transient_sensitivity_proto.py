@@ -2,7 +2,7 @@
 32): the dense forward loop of section 26 (real or complex), the complex-step derivative of a functional
 J = J(u^1 .. u^N) with respect to every datum -- the tables a, c, rho, f_r at the Gauss points, the initial state and the
 end data g(t_n), kappa -- by Im J(theta + i 1e-30 delta) / 1e-30 (no subtraction, so no cancellation), the backward loop
-and the sums over time that csrc/lssvr_ts_sens.hpp evaluates, in its order of operations.  No GPU, nothing but numpy.
+and the sums over time that csrc/lssvr_chunk_sens.hpp evaluates, in its order of operations.  No GPU, nothing but numpy.
 
 Run as a script it prints what DESIGN.md section 32 records: the deviation of the adjoint gradients from the complex
 step per group on the cases of tests/transient_sensitivity_rules.py, what a wrong pair of adjoint coefficients reads, and
@@ -137,7 +137,7 @@ def band_ends(p):
     return np.array([[A[al][1, 0], A[al][-2, -1]] for al in (BDF["bdf1"][0], BDF[p.scheme][0])])
 
 
-# ---- the sums over time, in the order of csrc/lssvr_ts_sens.hpp -----------------------------------------------------------
+# ---- the sums over time, in the order of csrc/lssvr_chunk_sens.hpp -----------------------------------------------------------
 def ts_diff(al, b0, b1, inv_dt, u2, u0, u1):
     d = al * u2 - b0 * u0
     return inv_dt * (d if b1 == 0.0 else d - b1 * u1)
@@ -146,7 +146,7 @@ def ts_diff(al, b0, b1, inv_dt, u2, u0, u1):
 def chunk_tables(x, nq, Utraj, Z, n0, inv_dt, coef, phi, R, init=None):
     """dict(a=, c=, rho= [ne, nq], f= [R, ne, nq]) of the chunk of m = len(Z) steps n0 .. n0+m-1; row i of Z and of coef
     belongs to step n0+m-1-i.  ``init``: the dict the sums continue from (accumulate), else they start from 0.  Every
-    operation in the order of ts_sens_entry, one rounding each: bit for bit the library's values."""
+    operation in the order of chunk_sens_entry, one rounding each: bit for bit the library's values."""
     xi, w = sp.gauss01(nq)
     ne, m = len(x) - 1, len(Z)
     h = (x[1:] - x[:-1])[:, None]
@@ -174,7 +174,7 @@ def chunk_tables(x, nq, Utraj, Z, n0, inv_dt, coef, phi, R, init=None):
 
 
 def chunk_ends(Utraj, Z, Brows, n0, bends, band_row, kinds, out_g, kappa_init=None):
-    """The end gradients of the chunk in the order of ts_sens_ends: rows n0 .. n0+m-1 of ``out_g`` [N+1, 2] are
+    """The end gradients of the chunk in the order of chunk_sens_ends: rows n0 .. n0+m-1 of ``out_g`` [N+1, 2] are
     written in place; returns kappa [2], continued from ``kappa_init`` (accumulate) or from 0."""
     ne, m = Z.shape[1] - 1, len(Z)
     nhi = n0 + m - 1

@@ -4,7 +4,8 @@ assembly, the end treatment and the functionals those of sensitivity_proto / tra
 complex-step derivative of a functional J = sum_n p_n . u^n, n = 0 .. N, with respect to every datum -- the tables a, c,
 rho, d, f_r at the Gauss points, the initial state and velocity, the end data g(t_n), kappa and the first acceleration of
 a Dirichlet end -- by Im J(theta + i 1e-30 delta) / 1e-30, the backward sweep through the transposed Newmark recurrences
-in the order of csrc/lssvr_newmark_adj.hpp, and the sums over time in that file's order.  No GPU, nothing but numpy.
+in the order of csrc/lssvr_newmark_adj.hpp, and the sums over time in that of csrc/lssvr_chunk_sens.hpp.  No GPU, nothing
+but numpy.
 
 Run as a script it prints what DESIGN.md section 34 records: the deviation of the adjoint gradients from the complex
 step per group, with and without damping and for (beta, gamma) = (1/4, 1/2) and (0.3025, 0.6), what the sweep reads
@@ -164,13 +165,13 @@ def backward(p, P, mats=None, wrong=False):
     return lam, B, ub, vb
 
 
-# ---- the sums over time, in the order of csrc/lssvr_newmark_adj.hpp --------------------------------------------------------
+# ---- the sums over time, in the order of csrc/lssvr_chunk_sens.hpp ---------------------------------------------------------
 TABLES = ("a", "c", "rho", "d", "f")
 
 
 def chunk_tables(x, nq, Utraj, Vtraj, Atraj, Z, n0, phi, R, want=TABLES, init=None):
     """{table: sums} of the chunk of m = len(Z) levels n0 .. n0+m-1; row i of Z belongs to level n0+m-1-i.  ``init``:
-    the dict the sums continue from (accumulate), else from 0.  Every operation in the order of nm_sens_entry."""
+    the dict the sums continue from (accumulate), else from 0.  Every operation in the order of chunk_sens_entry."""
     xi, w = sp.gauss01(nq)
     ne, m = len(x) - 1, len(Z)
     h = (x[1:] - x[:-1])[:, None]
@@ -198,7 +199,7 @@ def chunk_tables(x, nq, Utraj, Vtraj, Atraj, Z, n0, phi, R, want=TABLES, init=No
 
 
 def chunk_ends(Utraj, Z, Brows, n0, bends, kinds, out_g, kappa_init=None):
-    """The end gradients of the chunk in the order of nm_sens_ends: rows n0 .. n0+m-1 of ``out_g`` [N+1, 2] are written
+    """The end gradients of the chunk in the order of chunk_sens_ends: rows n0 .. n0+m-1 of ``out_g`` [N+1, 2] are written
     in place; returns kappa [2], continued from ``kappa_init`` (accumulate) or from 0."""
     ne, m = Z.shape[1] - 1, len(Z)
     nhi = n0 + m - 1

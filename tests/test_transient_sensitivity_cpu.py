@@ -117,7 +117,8 @@ def test_argument_errors():
               (dict(coef=None), -1, b"coef_host"), (dict(none4, g=None, kap=None), -1, b"one of ga, gc, grho, gf, out_g"),
               (dict(B=None), -1, b"Brows and band_ends"), (dict(be=None), -1, b"Brows and band_ends"),
               (dict(phi=None), -1, b"phi must be non-NULL with gf"), (dict(kap=None), -1, b"out_g and out_kappa"),
-              (dict(g=None), -1, b"out_g and out_kappa"))
+              (dict(g=None), -1, b"out_g and out_kappa"), (dict(ga=hp(keep[2])), -2, b"none of them an input"),
+              (dict(gc=hp(o["a"])), -2, b"must be distinct"), (dict(g=hp(keep[3])), -2, b"none of them an input"))
     for change, code, word in broken:
         rc = host(**change)
         assert rc == code and word in lib.lssvr_last_error(), (change, rc, lib.lssvr_last_error())

@@ -4,7 +4,7 @@ tests/test_gpu_transient_sensitivity.py through the device.
 
 The restatement is scripts/proto/transient_sensitivity_proto.py: the dense BDF loop, the complex-step derivative of every
 datum (the yardstick: no subtraction, so it carries the rounding of one loop and nothing else), the backward loop and
-the sums over time in the order of csrc/lssvr_ts_sens.hpp.  The bar of a case is 10x what the float64 prototype itself
+the sums over time in the order of csrc/lssvr_chunk_sens.hpp.  The bar of a case is 10x what the float64 prototype itself
 reads on the SAME case -- the deviation of its adjoint gradients from the complex step, the largest over the groups
 (a, c, rho, f tables, u0, g, kappa), each relative to the largest entry of its group.  The reading is taken when the test
 runs (cached), never from the code under test; READ records what it was when the cases were written."""
@@ -195,7 +195,7 @@ def ts_sens_host(d, nq, want=TABLES, kinds=(D, D), ends=False, init=None, check=
 
 
 def ts_sens_numpy(d, nq, kinds=(D, D), init=None):
-    """The same dict from the numpy restatement, in the order of csrc/lssvr_ts_sens.hpp."""
+    """The same dict from the numpy restatement, in the order of csrc/lssvr_chunk_sens.hpp."""
     out = proto.chunk_tables(d["x"], nq, d["Utraj"], d["Z"], d["n0"], d["inv_dt"], d["coef"], d["phi"], d["R"], init)
     out["g"] = np.full((d["Utraj"].shape[0], 2), CANARY)
     out["kappa"] = proto.chunk_ends(d["Utraj"], d["Z"], d["Brows"], d["n0"], d["band_ends"], d["band_rows"], kinds,

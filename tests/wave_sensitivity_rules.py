@@ -3,12 +3,12 @@ tests/test_wave_sensitivity_cpu.py runs them through the numpy prototype and the
 tests/test_gpu_wave_sensitivity.py through the device.
 
 The restatement is scripts/proto/wave_sensitivity_proto.py: the dense Newmark loop, the complex-step derivative of every
-datum (the yardstick: no subtraction, so it carries the rounding of one loop and nothing else), the backward sweep and
-the sums over time in the order of csrc/lssvr_newmark_adj.hpp.  The bar of a case is 10x what the float64 prototype
-itself reads on the SAME case -- the deviation of its adjoint gradients from the complex step, the largest over the
-groups (a, c, rho, d, f tables, u0, v0, g, kappa, accel0), each relative to the largest entry of its group.  The reading
-is taken when the test runs (cached), never from the code under test; READ records what it was when the cases were
-written."""
+datum (the yardstick: no subtraction, so it carries the rounding of one loop and nothing else), the backward sweep in
+the order of csrc/lssvr_newmark_adj.hpp and the sums over time in that of csrc/lssvr_chunk_sens.hpp.  The bar of a
+case is 10x what the float64 prototype itself reads on the SAME case -- the deviation of its adjoint gradients from the
+complex step, the largest over the groups (a, c, rho, d, f tables, u0, v0, g, kappa, accel0), each relative to the
+largest entry of its group.  The reading is taken when the test runs (cached), never from the code under test; READ
+records what it was when the cases were written."""
 import ctypes
 import functools
 import os
@@ -260,7 +260,7 @@ def sens_host(d, nq, want=TABLES, kinds=(D, D), ends=False, init=None, check=Tru
 
 
 def sens_numpy(d, nq, kinds=(D, D), init=None):
-    """The same dict from the numpy restatement, in the order of csrc/lssvr_newmark_adj.hpp."""
+    """The same dict from the numpy restatement, in the order of csrc/lssvr_chunk_sens.hpp."""
     names = TABLES if d["R"] else TABLES[:4]
     out = proto.chunk_tables(d["x"], nq, d["Utraj"], d["Vtraj"], d["Atraj"], d["Z"], d["n0"], d["phi"], d["R"], names,
                              init)
