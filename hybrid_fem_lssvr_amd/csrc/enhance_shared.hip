@@ -12,8 +12,10 @@
 // ~65 + a factorisation, 88 B of HBM traffic per element -- the one genuinely HBM-bound form
 // of the path.  Everything that depends on the element itself stays exact per element: the
 // abscissae x_k (numpy's linspace arithmetic), f(x_k) with numpy's argument rounding, scl_e,
-// the boundary values and the Dual.py:65-75 rule.  What is shared is the operator, i.e. the
-// (in-kernel f needs |omega x| < 3e9: beyond, the coefficients are NaN -> status FALLBACK)
+// the boundary values and the Dual.py:65-75 rule.  The in-kernel f needs |omega x| < 3e9: an
+// element whose every |omega x_k| is beyond has status FALLBACK and the linear interpolant; one
+// that straddles 3e9 has either, and its status says which (the sine of th0 = omega a and of the
+// points the wave evaluates afresh are tested one by one).  What is shared is the operator, i.e. the
 // rounding of t_k = off + scl x_k of the canonical element instead of each element's own:
 // ~(|x|/h) eps relative L2 (1e-11 on BASELINE config 2; tests/test_gpu_shared.py), inside
 // north_star's 1e-10 on the BASELINE single-GPU meshes but outside this repository's 1e-13 bar
@@ -59,9 +61,10 @@ __global__ __launch_bounds__(kBlock) void enhance_shared_kernel(EnhanceArgs p,
     const double inv_scl2 = 0.25 * (oldlen * oldlen);
 
     // in-kernel rhs: (sin, cos)(th0 + k dth) carried by a rotation, pre-scaled by amp / scl^2
-    // (enhance_small_impl.hpp).  While |omega x| stays below 64 over the element, numpy's
-    // rounding of the argument fl(omega fl(x_k)) moves f by < 1e-14 relative and the rotated
-    // value is used as it is; beyond, the argument is restored to first order per point.
+    // (enhance_small_impl.hpp).  numpy's argument fl(omega fl(x_k)) is restored to first order
+    // per point on both paths; while |omega x| stays below 64 over the wave the restore cannot
+    // reach 1e-7 and the loop runs without the test for it (and without the tabulated path's
+    // staging).
     double rs = 0.0, rc = 1.0, sd = 0.0, cd = 1.0, th0 = 0.0, dth = 0.0, kappa = 0.0;
     bool small_args = false;
     if constexpr (RHS == LSSVR_RHS_SIN) {
@@ -96,7 +99,11 @@ __global__ __launch_bounds__(kBlock) void enhance_shared_kernel(EnhanceArgs p,
     }
     if (RHS == LSSVR_RHS_SIN && small_args) {
       for (int k = 0; k < n; ++k) {
-        const double ft = rs;                                 // f(x_k) / scl^2
+        // f(x_k) / scl^2 at numpy's argument fl(omega x_k), restored to first order: delta is only
+        // ~|omega x| eps, but next to a zero of f that is not small against f itself (2e-13 of the
+        // bubble on the end elements of 4096 elements of [-1, 1]; tests/test_gpu_shared.py)
+        const double arg = p.rhs_omega * linspace_at(a, b, oldlen, step, k, n);
+        const double ft = fma(rc, fma(-(double)k, dth, arg - th0), rs);
         const double rs_next = fma(rs, cd, rc * sd);
         rc = fma(rc, cd, -(rs * sd));
         rs = rs_next;
