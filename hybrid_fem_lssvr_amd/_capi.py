@@ -232,6 +232,12 @@ SIGNATURES = {
                                       [_c_int, _c_dp, _c_dp, _c_int, _c_int, _c_dp, _c_dp], _STREAM),
     "lssvr_newmark_sensitivity_host": _sig([_c_hd, _c_i64, _c_int], [_c_hd] * 4, [_c_i64, _c_int, _c_hd, _c_int],
                                            [_c_hd] * 5, [_c_int, _c_hd, _c_hd, _c_int, _c_int, _c_hd, _c_hd]),
+    # adjoint sensitivities of the semilinear solve (additive to ABI 7): x, ne, nquad, U, nu, Z, nc, q_tabs, kind, nterm,
+    # ga, gb, gc, gf, gq, P, band_ends, kind_left, kind_right, out_ends
+    "lssvr_semilinear_sensitivity": _sig(_MESH, [_c_dp, _c_int, _c_dp, _c_int, _c_dp, _c_int, _c_int], [_c_dp] * 7,
+                                         [_c_int, _c_int, _c_dp], _STREAM),
+    "lssvr_semilinear_sensitivity_host": _sig([_c_hd, _c_i64, _c_int, _c_hd, _c_int, _c_hd, _c_int, _c_hd, _c_int,
+                                               _c_int], [_c_hd] * 7, [_c_int, _c_int, _c_hd]),
     "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

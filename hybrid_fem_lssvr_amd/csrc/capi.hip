@@ -1970,15 +1970,18 @@ int lssvr_wave_advance_host(const double* U_new_host, const double* U_host, cons
 }
 
 // Adjoint sensitivities (sensitivity.hip).  The device and the host entry share one validated binding.
+// (tables_optional: an entry with outputs of its own, which checks that one of them is given)
 static int bind_sens(lssvr::SensArgs& a, const double* x, int64_t ne, int nquad, const double* U, int nu,
                      const double* Z, int nc, double* ga, double* gb, double* gc, double* gf, const double* P,
-                     const double* band_ends, int kind_left, int kind_right, double* out_ends) {
+                     const double* band_ends, int kind_left, int kind_right, double* out_ends,
+                     bool tables_optional = false) {
   if (const int rc = check_ne(ne)) return rc;
   if (nc < 1 || nc > 8) return fail(LSSVR_ERR_SIZE, "nc = %d outside [1, 8]", nc);
   if (nu != 1 && nu != nc) return fail(LSSVR_ERR_SIZE, "nu = %d must be 1 or nc = %d", nu, nc);
   if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
   if (!x || !U || !Z) return fail(LSSVR_ERR_NULL, "x, U, Z must be non-NULL");
-  if (!ga && !gb && !gc && !gf) return fail(LSSVR_ERR_NULL, "one of ga, gb, gc, gf must be non-NULL");
+  if (!tables_optional && !ga && !gb && !gc && !gf)
+    return fail(LSSVR_ERR_NULL, "one of ga, gb, gc, gf must be non-NULL");
   if (out_ends) {
     if (!band_ends) return fail(LSSVR_ERR_NULL, "band_ends must be non-NULL with out_ends");
     if (const int rc = check_kinds(kind_left, kind_right)) return rc;
@@ -2006,6 +2009,49 @@ int lssvr_p1_sensitivity_host(const double* x_host, int64_t ne, int nquad, const
                            band_ends_host, kind_left, kind_right, out_ends_host);
   if (rc != LSSVR_OK) return rc;
   lssvr::p1_sensitivity_host(a);          // (nquad is checked above: the rule exists)
+  return LSSVR_OK;
+}
+
+// Adjoint sensitivities of the semilinear solve (nl_sensitivity.hip): the binding above, then the law and its tables.
+static int bind_nl_sens(lssvr::NlSensArgs& a, const double* x, int64_t ne, int nquad, const double* U, int nu,
+                        const double* Z, int nc, const double* q_tabs, int kind, int nterm, double* ga, double* gb,
+                        double* gc, double* gf, double* gq, const double* P, const double* band_ends, int kind_left,
+                        int kind_right, double* out_ends) {
+  if (const int rc = bind_sens(a.s, x, ne, nquad, U, nu, Z, nc, ga, gb, gc, gf, P, band_ends, kind_left, kind_right,
+                               out_ends, true))
+    return rc;
+  if (!ga && !gb && !gc && !gf && !gq && !out_ends)
+    return fail(LSSVR_ERR_NULL, "one of ga, gb, gc, gf, gq, out_ends must be non-NULL");
+  if (const int rc = check_nl_kind(kind, nterm)) return rc;
+  if (kind == LSSVR_NL_EXP && !q_tabs) return fail(LSSVR_ERR_NULL, "q_tabs must be non-NULL with LSSVR_NL_EXP");
+  a.q_tabs = q_tabs;
+  a.kind = kind;
+  a.nterm = nterm;
+  a.gq = gq;
+  return LSSVR_OK;
+}
+
+int lssvr_semilinear_sensitivity(const double* x, int64_t ne, int nquad, const double* U, int nu, const double* Z,
+                                 int nc, const double* q_tabs, int kind, int nterm, double* ga, double* gb, double* gc,
+                                 double* gf, double* gq, const double* P, const double* band_ends, int kind_left,
+                                 int kind_right, double* out_ends, void* stream) {
+  lssvr::NlSensArgs a{};
+  const int rc = bind_nl_sens(a, x, ne, nquad, U, nu, Z, nc, q_tabs, kind, nterm, ga, gb, gc, gf, gq, P, band_ends,
+                              kind_left, kind_right, out_ends);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::nl_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "nl_sensitivity");
+}
+
+int lssvr_semilinear_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* U_host, int nu,
+                                      const double* Z_host, int nc, const double* q_tabs_host, int kind, int nterm,
+                                      double* ga_host, double* gb_host, double* gc_host, double* gf_host,
+                                      double* gq_host, const double* P_host, const double* band_ends_host,
+                                      int kind_left, int kind_right, double* out_ends_host) {
+  lssvr::NlSensArgs a{};
+  const int rc = bind_nl_sens(a, x_host, ne, nquad, U_host, nu, Z_host, nc, q_tabs_host, kind, nterm, ga_host, gb_host,
+                              gc_host, gf_host, gq_host, P_host, band_ends_host, kind_left, kind_right, out_ends_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::nl_sensitivity_host(a);          // (nquad is checked above: the rule exists)
   return LSSVR_OK;
 }
 

@@ -563,6 +563,19 @@ struct SensArgs {
 hipError_t p1_sensitivity(const SensArgs& a, hipStream_t s);
 bool p1_sensitivity_host(const SensArgs& a);     // false: no such quadrature rule
 
+// nl_sensitivity.hip: adjoint sensitivities of the semilinear P1 solve.  `s` holds everything of
+// p1_sensitivity, with U the converged u* and Z the adjoint of the Newton Jacobian (all four of its tables may be nullptr
+// here); gq [nc][nterm][ne*nquad] receives dJ/dq_k for the tables of g(x, u), nullptr: skipped, stores included; q_tabs
+// [nterm][ne*nquad] is read for LSSVR_NL_EXP only.
+struct NlSensArgs {
+  SensArgs s;
+  const double* q_tabs;
+  int kind, nterm;                  // LSSVR_NL_*; POLY 1 <= nterm <= 6, EXP nterm == 2
+  double* gq;
+};
+hipError_t nl_sensitivity(const NlSensArgs& a, hipStream_t s);
+bool nl_sensitivity_host(const NlSensArgs& a);   // false: no such quadrature rule
+
 // newmark_adjoint.hip: the adjoint advance of the Newmark loop.  One case; nodal vectors
 // [ne+1].  The scalars are those of wave_coefficients.
 struct NmAdjArgs {

@@ -2218,6 +2218,52 @@ def adjoint_bands(bands):
     return out
 
 
+def _sens_bind(x, U, Z, nquad, want, tables, P, bands, end_kinds, out, nterm=None):
+    """The host checks and the output buffers :func:`p1_sensitivity` and :func:`nl_sensitivity` share -> (ne, nquad, nu,
+    nc, res, band_ends, kinds, ins): ``tables`` the keys ``want`` may name (an empty ``want`` passes only with
+    ``bands`` and ``nterm``: the end gradients alone), ``res`` the dict of the outputs -- [nc, ne, nquad] per table,
+    [nc, nterm, ne, nquad] for "q", "ends" [nc, 4] with ``bands`` --, ``band_ends`` the pair (sub[0], sup[ne-1]) on the
+    device or None, ``ins`` the inputs by name for the alias and device checks."""
+    for nm, t in (("x", x), ("U", U), ("Z", Z)):
+        _dev(t, nm)
+    ne = _nodes(x, "x")
+    nquad = int(nquad)
+    if not 1 <= nquad <= 5:
+        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
+    want = tuple(want)
+    ends_only = not want and nterm is not None and bands is not None
+    if (not want and not ends_only) or len(set(want)) != len(want) or any(k not in tables for k in want):
+        raise ValueError(f"want must name at least one of {tables}, each once, got {want!r}")
+    U2, Z2 = (t.view(1, -1) if t.dim() == 1 else t for t in (U, Z))
+    nc = _block(ne, "nc", Z=Z2)
+    nu = _block(ne, "nu", U=U2)
+    if nu not in (1, nc):
+        raise ValueError(f"U must hold 1 or nc = {nc} vectors, got {nu}")
+    ins = {"U": U, "Z": Z}
+    if P is not None:
+        _dev(P, "P")
+        if P.numel() != Z.numel():
+            raise ValueError(f"P must have the shape of Z {list(Z.shape)}, got {list(P.shape)}")
+        ins["P"] = P
+    out = {} if out is None else out
+    res = {k: _out(out.get(k), f"out[{k!r}]", (nc, nterm, ne, nquad) if k == "q" else (nc, ne, nquad), x)
+           for k in want}
+    band_ends = None
+    if bands is not None:
+        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
+        sub, sup = (bands["sub"], bands["sup"]) if "sub" in bands else (bands["off"], bands["off"])
+        for nm, t in (("sub", sub), ("sup", sup)):
+            _dev(t, nm)
+            if t.numel() != ne:
+                raise ValueError(f"{nm} must hold ne = {ne} doubles, got {t.numel()}")
+        band_ends = torch.stack((sub.reshape(-1)[0], sup.reshape(-1)[ne - 1]))
+        ins.update(sub=sub, sup=sup)
+        res["ends"] = _out(out.get("ends"), "out['ends']", (nc, 4), x)
+    else:
+        kinds = (END_DIRICHLET, END_DIRICHLET)
+    return ne, nquad, nu, nc, res, band_ends, kinds, ins
+
+
 def p1_sensitivity(x, U, Z, nquad=2, *, want=SENS_TABLES, P=None, bands=None,
                    end_kinds=(END_DIRICHLET, END_DIRICHLET), out=None, stream=None):
     """``lssvr_p1_sensitivity``: from ``nc`` pairs of a primal solution U[j] and an adjoint solution Z[j] (the solve of
@@ -2232,46 +2278,48 @@ def p1_sensitivity(x, U, Z, nquad=2, *, want=SENS_TABLES, P=None, bands=None,
     float64[nc, 4] = (dJ/dg_0, dJ/dg_ne, dJ/dkappa_0, dJ/dkappa_ne).  ``out``: a dict of buffers to write into, by
     those keys.  No synchronisation and no copy; every value is computed in a fixed order (bitwise reproducible)."""
     lib = _capi.load()
-    for nm, t in (("x", x), ("U", U), ("Z", Z)):
-        _dev(t, nm)
-    ne = _nodes(x, "x")
-    nquad = int(nquad)
-    if not 1 <= nquad <= 5:
-        raise ValueError(f"nquad must be in 1 .. 5, got {nquad}")
-    want = tuple(want)
-    if not want or len(set(want)) != len(want) or any(k not in SENS_TABLES for k in want):
-        raise ValueError(f"want must name at least one of {SENS_TABLES}, each once, got {want!r}")
-    U2, Z2 = (t.view(1, -1) if t.dim() == 1 else t for t in (U, Z))
-    nc = _block(ne, "nc", Z=Z2)
-    nu = _block(ne, "nu", U=U2)
-    if nu not in (1, nc):
-        raise ValueError(f"U must hold 1 or nc = {nc} vectors, got {nu}")
-    ins = {"U": U, "Z": Z}
-    if P is not None:
-        _dev(P, "P")
-        if P.numel() != Z.numel():
-            raise ValueError(f"P must have the shape of Z {list(Z.shape)}, got {list(P.shape)}")
-        ins["P"] = P
-    out = {} if out is None else out
-    res = {k: _out(out.get(k), f"out[{k!r}]", (nc, ne, nquad), x) for k in want}
-    band_ends = None
-    if bands is not None:
-        kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
-        sub, sup = (bands["sub"], bands["sup"]) if "sub" in bands else (bands["off"], bands["off"])
-        for nm, t in (("sub", sub), ("sup", sup)):
-            _dev(t, nm)
-            if t.numel() != ne:
-                raise ValueError(f"{nm} must hold ne = {ne} doubles, got {t.numel()}")
-        band_ends = torch.stack((sub.reshape(-1)[0], sup.reshape(-1)[ne - 1]))
-        ins.update(sub=sub, sup=sup)
-        res["ends"] = _out(out.get("ends"), "out['ends']", (nc, 4), x)
-    else:
-        kinds = (END_DIRICHLET, END_DIRICHLET)
+    ne, nquad, nu, nc, res, band_ends, kinds, ins = _sens_bind(x, U, Z, nquad, want, SENS_TABLES, P, bands, end_kinds,
+                                                               out)
     _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
     _same_device(x, **ins)
     rc = lib.lssvr_p1_sensitivity(_ptr(x), ne, nquad, _ptr(U), nu, _ptr(Z), nc, *(_ptr(res.get(k)) for k in SENS_TABLES),
                                   _ptr(P), _ptr(band_ends), *kinds, _ptr(res.get("ends")), _stream(stream))
     _capi.check(rc, "lssvr_p1_sensitivity")
+    return res
+
+
+# ---- adjoint sensitivities of the semilinear P1 solve (DESIGN.md section 35) -----------------------------------------
+NL_SENS_TABLES = SENS_TABLES + ("q",)      # "q": d/d q_tabs, the tables of g(x, u)
+
+
+def nl_sensitivity(x, U, Z, nquad, kind, nterm, *, q_tabs=None, want=NL_SENS_TABLES, P=None, bands=None,
+                   end_kinds=(END_DIRICHLET, END_DIRICHLET), out=None, stream=None):
+    """``lssvr_semilinear_sensitivity``: :func:`p1_sensitivity` for the semilinear problem with g(x, u) of ``kind``
+    ("poly" / ``NL_POLY``, "exp" / ``NL_EXP``) and ``nterm`` tables, in ONE launch.  U is the CONVERGED solution u* and Z
+    the adjoint of the Jacobian AT u*: the solve of :func:`adjoint_bands` of ONE :func:`p1_assemble` with c_quad = c_eff
+    of ONE :func:`nl_linearize` at u*.  ``want`` names any of "a", "b", "c", "f" -- float64[nc, ne, nquad], bit for bit
+    the values of :func:`p1_sensitivity` -- and "q" -- float64[nc, nterm, ne, nquad] = dJ/dq_k at every quadrature
+    point; "q" of "poly" has q[:, 0] == -f and q[:, 1] == c bit for bit.  It may be empty with ``bands`` (the end
+    gradients alone).  ``q_tabs`` float64[nterm, ne, nquad], the tables :func:`nl_linearize` took, is read for "exp"
+    only and must be given then.  ``bands`` are the raw JACOBIAN bands; ``P``, ``end_kinds``, ``out`` and the result as
+    for :func:`p1_sensitivity`.  No synchronisation and no copy."""
+    lib = _capi.load()
+    kind, nterm = nl_kind(kind, nterm)
+    ne, nquad, nu, nc, res, band_ends, kinds, ins = _sens_bind(x, U, Z, nquad, want, NL_SENS_TABLES, P, bands,
+                                                               end_kinds, out, nterm)
+    if q_tabs is not None:
+        _dev(q_tabs, "q_tabs")
+        if tuple(q_tabs.shape) != (nterm, ne, nquad):
+            raise ValueError(f"q_tabs must be [nterm, ne, nquad] = [{nterm}, {ne}, {nquad}], got {list(q_tabs.shape)}")
+        ins["q_tabs"] = q_tabs
+    elif kind == NL_EXP:
+        raise ValueError("kind 'exp' needs q_tabs: dJ/dq_k depends on q_0 and q_1")
+    _no_alias("the outputs must be distinct and none of them an input", res.values(), (x, *ins.values()))
+    _same_device(x, **ins)
+    rc = lib.lssvr_semilinear_sensitivity(_ptr(x), ne, nquad, _ptr(U), nu, _ptr(Z), nc, _ptr(q_tabs), kind, nterm,
+                                  *(_ptr(res.get(k)) for k in NL_SENS_TABLES), _ptr(P), _ptr(band_ends), *kinds,
+                                  _ptr(res.get("ends")), _stream(stream))
+    _capi.check(rc, "lssvr_semilinear_sensitivity")
     return res
 
 

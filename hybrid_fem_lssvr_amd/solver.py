@@ -462,7 +462,8 @@ class Sensitivity:
     ``coef`` the coefficient is the table a = 1, and ``d_coef`` is the derivative there); ``d_end_values`` [2]: dJ/dg
     of the left and right end datum (the Dirichlet value, or g of a Neumann or Robin end); ``d_kappa`` [2]: dJ/dkappa
     (0 at a Dirichlet end); ``adjoint`` the nodal adjoint solution z (0 at a Dirichlet end) and ``nodes`` the mesh.
-    The mesh is not differentiated."""
+    :meth:`FEMLSSVRPrimalSolver.solve_semilinear_sensitivity` adds ``d_nonlinear`` [nterm, ne, nquad]: dJ/dq_k of the
+    tables of g(x, u), and ``newton``, the :class:`NewtonReport` of its solve.  The mesh is not differentiated."""
 
     def __init__(self, value, tables, ends, adjoint, nodes):
         self.value = float(value)
@@ -2673,24 +2674,26 @@ class FEMLSSVRPrimalSolver:
         return GoalEstimate(eta, eta2, out4), marking
 
     # ---- adjoint sensitivities of the P1 solve (no reference counterpart) ------------------
-    def _check_sensitivity(self, goal, observe):
+    def _check_sensitivity(self, goal, observe, what="solve_sensitivity", semilinear=False):
         """What :meth:`solve_sensitivity` needs, on the host and before any device call -> (nodes, functional):
-        ``functional(u)`` -> (J, p = dJ/du) for the nodal vector u."""
+        ``functional(u)`` -> (J, p = dJ/du) for the nodal vector u.  ``what``: the caller's name in the messages;
+        ``semilinear``: the caller differentiates the Newton solve, so ``nonlinear=`` is not refused."""
         if self._periodic:
-            raise ValueError("solve_sensitivity has no boundary='periodic': the adjoint solve and the end gradients "
+            raise ValueError(f"{what} has no boundary='periodic': the adjoint solve and the end gradients "
                              "are written for Dirichlet, Neumann and Robin ends")
         if self.fem_solver == "flux":
-            raise ValueError("solve_sensitivity needs fem_solver='bands' or 'pivot': the adjoint is the transposed "
+            raise ValueError(f"{what} needs fem_solver='bands' or 'pivot': the adjoint is the transposed "
                              "tridiagonal solve, which the flux solve does not have")
-        self._check_nonlinear("solve_sensitivity")
+        if not semilinear:
+            self._check_nonlinear(what)
         if self.solver_id != ops.SOLVER_PRIMAL:
-            raise ValueError("solve_sensitivity needs solver=ops.SOLVER_PRIMAL: the derivatives are those of the P1 "
+            raise ValueError(f"{what} needs solver=ops.SOLVER_PRIMAL: the derivatives are those of the P1 "
                              "solve, the enhancement is not differentiated")
         if self.element_degrees is not None:
-            raise ValueError("solve_sensitivity has no element_degrees: the derivatives are those of the P1 solve, "
+            raise ValueError(f"{what} has no element_degrees: the derivatives are those of the P1 solve, "
                              "which has no degree")
         if (goal is None) == (observe is None):
-            raise ValueError("solve_sensitivity needs exactly one of goal (a callable j(x): J = int j u dx) and "
+            raise ValueError(f"{what} needs exactly one of goal (a callable j(x): J = int j u dx) and "
                              "observe = (x_obs, d_obs) (J = 1/2 sum (u_h(x_i) - d_i)^2)")
         m = self._default_mesh() if self.mesh is None else self.mesh
         nodes = np.asarray(m.nodes, dtype=np.float64)
@@ -2877,6 +2880,52 @@ class FEMLSSVRPrimalSolver:
         res = ops.p1_sensitivity(x, u, Z, self.nquad, want=want, P=P, bands=bands, end_kinds=kinds)
         host = _read_back(z=Z, **res)
         return Sensitivity(value, {k: host[k][0] for k in want}, host["ends"][0], host["z"][0], nodes)
+
+    # ---- adjoint sensitivities of the semilinear P1 solve (no reference counterpart) ----------
+    def solve_semilinear_sensitivity(self, goal=None, *, observe=None, u_init=None, tol=None, max_iter=None):
+        """:meth:`solve_sensitivity` for a solver with ``nonlinear=``: derivatives of a functional J of the converged
+        Newton solution u* of -(a u')' + b u' + c u + g(x, u) = f with respect to the data of the solve, the tables
+        q_k(x) of g among them.  ONE :meth:`solve_fem` (``u_init``, ``tol``, ``max_iter`` are its Newton keywords), ONE
+        ``ops.nl_linearize`` AT u* for c_eff = c + g_u(x, u*_h), ONE ``ops.p1_assemble`` with it -- the Newton Jacobian;
+        ``self.bands`` is not reused, it is linearised at the previous iterate --, ONE adjoint solve on its transposed
+        bands, ONE ``ops.nl_sensitivity`` and one read-back.  ``goal`` / ``observe`` as for :meth:`solve_sensitivity`.
+        Returns a :class:`Sensitivity` that also holds ``d_nonlinear`` [nterm, ne, nquad] = dJ/dq_k at quadrature point
+        q of element e and ``newton``, the :class:`NewtonReport` of the solve; ``d_end_values`` of a Dirichlet end takes
+        the Jacobian's band entry.  ``fem_solver="pivot"`` where c + g_u < 0.  Refused (``ValueError``, before any
+        device call): a solver without ``nonlinear=``, what :meth:`solve_sensitivity` refuses other than ``nonlinear=``,
+        what ``nonlinear=`` refuses, Newton keywords :meth:`solve_fem` refuses.  ``of="enhanced"``, the semilinear
+        time loop, periodic ends and the mesh are not differentiated."""
+        what = "solve_semilinear_sensitivity"
+        if self.nonlinear is None:
+            raise ValueError(f"{what} needs nonlinear=: the linear solve is differentiated by solve_sensitivity")
+        nodes, functional = self._check_sensitivity(goal, observe, what, semilinear=True)
+        nl = self._check_nonlinear()
+        self.solve_fem(u_init=u_init, tol=tol, max_iter=max_iter)
+        x, u = self._x_dev, self._u_dev
+        value, p = functional(self.fem_values)
+        bnd = self._bnd
+        kinds, kappa = ((ops.END_DIRICHLET,) * 2, (0.0, 0.0)) if bnd is None else (tuple(bnd.kinds), tuple(bnd.kappa))
+        # the Jacobian at u*: the tables of the Newton loop, linearised once more
+        _, _, xq, kw = self._fem_setup()
+        fq = _tabulate(self._eq.f, xq)
+        qq = nl.tables(xq, "quadrature")
+        t = ops.quad_points(_to_dev([0.0, 1.0], x.device), self.nquad)[0].contiguous()
+        c_eff = ops.nl_linearize(u, t, nl.kind, qq, fq, c_tab=kw.get("c_quad"), f_eff=False)["c_eff"]
+        if self.fem_solver != "pivot" and bool((c_eff < 0).any().item()):
+            raise ValueError("c + g_u is negative at a quadrature point of the converged solution: the tridiagonal "
+                             "solve of the adjoint does not pivot and assumes an SPD matrix; use fem_solver=\"pivot\"")
+        jac = ops.p1_assemble(x, self.nquad, rhs_quad=fq, **{**kw, "c_quad": c_eff})
+        P = _to_dev(p[None, :], x.device)
+        Z = self._adjoint_solve(jac, P, kinds, kappa)
+        eq = self._eq
+        want = tuple(k for k, on in zip(ops.NL_SENS_TABLES, (True, eq.b is not None, eq.c is not None, True, True))
+                     if on)
+        res = ops.nl_sensitivity(x, u, Z, self.nquad, nl.kind, len(nl.q), q_tabs=qq, want=want, P=P, bands=jac,
+                                 end_kinds=kinds)
+        host = _read_back(z=Z, **res)
+        s = Sensitivity(value, {k: host[k][0] for k in want}, host["ends"][0], host["z"][0], nodes)
+        s.d_nonlinear, s.newton = host["q"][0], self.newton
+        return s
 
     def _adapt_rounds(self, tol, max_elements, max_iter, round_fn, start=None):
         """The round loop of every ``solve_adaptive`` mode; host logic only, so a scripted ``round_fn`` can drive it.

@@ -1513,6 +1513,51 @@ int lssvr_enhance_adjoint_host(const double* x_host, int64_t ne, int64_t elem_of
                                double* gda_host, double* gc_host, double* gf_host, void* work_h,
                                int64_t work_bytes);
 
+/*
+ * Adjoint sensitivities of the semilinear P1 solve of -(a u')' + b u' + c u + g(x, u) = f (no reference counterpart;
+ * DESIGN.md section 35).  ADDITIVE to ABI 7: two new symbols, no existing entry, struct, constant or kernel
+ * instantiation changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * The discrete problem is R(u) = K u + G(u) - F = 0 on the free rows, G_i(u) = sum_e h_e sum_q w_q phi_i(xi_q)
+ * g(x_eq, u_h(x_eq)).  Its Jacobian at the converged u* is K + M(g_u(., u*_h)): the bands of ONE lssvr_p1_assemble (or
+ * _react / _conv) with c_quad = c_eff from ONE lssvr_nl_linearize AT u* (not the bands of the last Newton step, which
+ * are linearised at the previous iterate).  For a functional J(u) with p = dJ/du the adjoint z solves the TRANSPOSED
+ * Jacobian bands with load p, zero end data and the primal's end kinds and kappa, as for lssvr_p1_sensitivity.  The
+ * gradients with respect to a_quad, b_quad, c_quad, rhs_quad and the end data are the formulas of lssvr_p1_sensitivity
+ * with u = u* and band_ends = {sub[0], sup[ne-1]} of the JACOBIAN bands.  With s = (h_e w_q) z_eq and
+ * u_eq = u[e] (1 - xi_q) + u[e+1] xi_q, formed exactly as lssvr_p1_sensitivity forms them, the order of every operation
+ * of the gradients with respect to the tables q_k of the law:
+ *   LSSVR_NL_POLY  p_0 = 1;  p_k = p_{k-1} u_eq;  dJ/dq_0 = -s;  dJ/dq_k = -(s p_k),  k = 1 .. nterm-1
+ *                  (so dJ/dq_0 is -dJ/drhs_quad and dJ/dq_1 is dJ/dc_quad, bit for bit)
+ *   LSSVR_NL_EXP   E = exp(q_1 u_eq);  dJ/dq_0 = -(s E);  dJ/dq_1 = -(s ((q_0 u_eq) E))
+ *
+ * lssvr_semilinear_sensitivity -- ONE launch; x, ne, nquad, U, nu, Z, nc, ga, gb, gc, gf, P, band_ends, the end kinds
+ * and out_ends are the arguments of lssvr_p1_sensitivity, and ga, gb, gc, gf and out_ends receive its values bit for
+ * bit.
+ * kind / nterm as for lssvr_nl_linearize.  gq [nc][nterm][ne*nquad] (element-major tables, case-major) receives
+ * dJ/dq_k.  q_tabs [nterm][ne*nquad], the tables lssvr_nl_linearize took at lssvr_quad_points, is read for LSSVR_NL_EXP
+ * only: it may be NULL for LSSVR_NL_POLY.  All DEVICE arrays.  Each of ga, gb, gc, gf, gq, out_ends may be NULL (it then
+ * costs neither arithmetic nor a store), but not all six.  One thread per table entry, no reduction, no atomics, no
+ * synchronisation, no copy.  No output may be one of the inputs or another output.
+ * Return codes, each before any HIP call: those of lssvr_p1_sensitivity for its arguments (LSSVR_ERR_SIZE for ne < 1, nc
+ * outside [1, 8], nu other than 1 or nc, an unknown end kind with out_ends; LSSVR_ERR_QUAD for nquad outside [1, 5];
+ * LSSVR_ERR_NULL for a missing x, U or Z and for out_ends without band_ends); LSSVR_ERR_NULL for six NULL outputs and for
+ * LSSVR_NL_EXP without q_tabs; LSSVR_ERR_RHS for an unknown kind; LSSVR_ERR_SIZE for nterm outside [1, 6]
+ * (LSSVR_NL_POLY) or other than 2 (LSSVR_NL_EXP).
+ *
+ * lssvr_semilinear_sensitivity_host -- the same routines on HOST arrays: no device is touched.  Bit for bit the device's
+ * values for LSSVR_NL_POLY; for LSSVR_NL_EXP up to the two exp implementations (libm here, the device library's there).
+ */
+int lssvr_semilinear_sensitivity(const double* x, int64_t ne, int nquad, const double* U, int nu, const double* Z,
+                                 int nc, const double* q_tabs, int kind, int nterm, double* ga, double* gb, double* gc,
+                                 double* gf, double* gq, const double* P, const double* band_ends, int kind_left,
+                                 int kind_right, double* out_ends, void* stream);
+int lssvr_semilinear_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* U_host, int nu,
+                                      const double* Z_host, int nc, const double* q_tabs_host, int kind, int nterm,
+                                      double* ga_host, double* gb_host, double* gc_host, double* gf_host,
+                                      double* gq_host, const double* P_host, const double* band_ends_host,
+                                      int kind_left, int kind_right, double* out_ends_host);
+
 #ifdef __cplusplus
 }
 #endif
