@@ -238,7 +238,21 @@ SIGNATURES = {
                                          [_c_int, _c_int, _c_dp], _STREAM),
     "lssvr_semilinear_sensitivity_host": _sig([_c_hd, _c_i64, _c_int, _c_hd, _c_int, _c_hd, _c_int, _c_hd, _c_int,
                                                _c_int], [_c_hd] * 7, [_c_int, _c_int, _c_hd]),
-    "lssvr_fp64_probe": _sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
+    # adjoint sensitivities of the semilinear BDF loop (additive to ABI 7).  sensitivity: x, ne, nquad, Utraj, Z, n0, m,
+    # inv_dt, coef_host, phi, R, q_tabs, kind, nterm, ga, gc, grho, gf, gq, accumulate, Brows, band_ends, kind_left,
+    # kind_right, out_g, out_kappa; step: x, u, a_quad, cs_quad, q_quad, ne, nquad, kind, nterm, mdiag, moff, U0, U1,
+    # loads, phi, R, beta0, beta1, inv_dt, diag, off, B, band_ends
+    "lssvr_semilinear_transient_sensitivity": _sig(_MESH, [_c_dp, _c_dp, _c_i64, _c_int, _c_dbl, _c_hd, _c_dp, _c_int,
+                                                           _c_dp, _c_int, _c_int], [_c_dp] * 5,
+                                                   [_c_int, _c_dp, _c_dp, _c_int, _c_int, _c_dp, _c_dp], _STREAM),
+    "lssvr_semilinear_transient_sensitivity_host": _sig([_c_hd, _c_i64, _c_int, _c_hd, _c_hd, _c_i64, _c_int, _c_dbl,
+                                                         _c_hd, _c_hd, _c_int, _c_hd, _c_int, _c_int], [_c_hd] * 5,
+                                                        [_c_int, _c_hd, _c_hd, _c_int, _c_int, _c_hd, _c_hd]),
+    "lssvr_semilinear_adjoint_step": _sig([_c_dp] * 5, [_c_i64, _c_int, _c_int, _c_int], [_c_dp] * 6, [_c_int],
+                                          [_c_dbl] * 3, [_c_dp] * 4, _STREAM),
+    "lssvr_semilinear_adjoint_step_host": _sig([_c_hd] * 5, [_c_i64, _c_int, _c_int, _c_int], [_c_hd] * 6, [_c_int],
+                                               [_c_dbl] * 3, [_c_hd] * 4),
+    "lssvr_fp64_probe":_sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),
 }

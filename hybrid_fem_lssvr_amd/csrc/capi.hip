@@ -2163,6 +2163,123 @@ int lssvr_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad
   return LSSVR_OK;
 }
 
+// semilinear BDF: the BDF binding with one matrix per level (band_ends [m][2], no band_mask) and
+// the law with its tables
+static int bind_ts_nl_sens(lssvr::TsNlSensArgs& a, const double* x, int64_t ne, int nquad, const double* Utraj,
+                           const double* Z, int64_t n0, int m, double inv_dt, const double* coef_host,
+                           const double* phi, int R, const double* q_tabs, int kind, int nterm, double* ga, double* gc,
+                           double* grho, double* gf, double* gq, int accumulate, const double* Brows,
+                           const double* band_ends, int kind_left, int kind_right, double* out_g,
+                           double* out_kappa) {
+  const ChunkSensScheme sch{1, "adjoint step", "x, Utraj, Z, coef_host", coef_host != nullptr,
+                            "ga, gc, grho, gf, gq, out_g", gq,
+                            gq && kind == LSSVR_NL_EXP && !q_tabs ? "q_tabs must be non-NULL with LSSVR_NL_EXP and gq"
+                                                                  : nullptr,
+                            {q_tabs, nullptr}};
+  a = lssvr::TsNlSensArgs{};
+  if (const int rc = bind_chunk_sens(a, sch, x, ne, nquad, Utraj, Z, n0, m, phi, R, ga, gc, grho, gf, accumulate, Brows,
+                                     band_ends, kind_left, kind_right, out_g, out_kappa))
+    return rc;
+  if (const int rc = check_nl_kind(kind, nterm)) return rc;
+  for (int i = 0; i < m; ++i) a.band_row[i] = i;
+  a.inv_dt = inv_dt;
+  for (int i = 0; i < m; ++i)
+    for (int k = 0; k < 3; ++k) a.coef[i][k] = coef_host[3 * i + k];
+  a.q_tabs = q_tabs, a.law = kind, a.nterm = nterm, a.gq = gq;
+  return LSSVR_OK;
+}
+
+int lssvr_semilinear_transient_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj,
+                                           const double* Z, int64_t n0, int m, double inv_dt, const double* coef_host,
+                                           const double* phi, int R, const double* q_tabs, int kind, int nterm,
+                                           double* ga, double* gc, double* grho, double* gf, double* gq,
+                                           int accumulate, const double* Brows, const double* band_ends,
+                                           int kind_left, int kind_right, double* out_g, double* out_kappa,
+                                           void* stream) {
+  lssvr::TsNlSensArgs a;
+  const int rc = bind_ts_nl_sens(a, x, ne, nquad, Utraj, Z, n0, m, inv_dt, coef_host, phi, R, q_tabs, kind, nterm, ga,
+                                 gc, grho, gf, gq, accumulate, Brows, band_ends, kind_left, kind_right, out_g,
+                                 out_kappa);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::chunk_sensitivity(a, reinterpret_cast<hipStream_t>(stream)), "ts_nl_sensitivity");
+}
+
+int lssvr_semilinear_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
+                                                const double* Z_host, int64_t n0, int m, double inv_dt,
+                                                const double* coef_host, const double* phi_host, int R,
+                                                const double* q_tabs_host, int kind, int nterm, double* ga_host,
+                                                double* gc_host, double* grho_host, double* gf_host, double* gq_host,
+                                                int accumulate, const double* Brows_host,
+                                                const double* band_ends_host, int kind_left, int kind_right,
+                                                double* out_g_host, double* out_kappa_host) {
+  lssvr::TsNlSensArgs a;
+  const int rc = bind_ts_nl_sens(a, x_host, ne, nquad, Utraj_host, Z_host, n0, m, inv_dt, coef_host, phi_host, R,
+                                 q_tabs_host, kind, nterm, ga_host, gc_host, grho_host, gf_host, gq_host, accumulate,
+                                 Brows_host, band_ends_host, kind_left, kind_right, out_g_host, out_kappa_host);
+  if (rc != LSSVR_OK) return rc;
+  lssvr::chunk_sensitivity_host(a);       // (nquad is checked above: the rule exists)
+  return LSSVR_OK;
+}
+
+// The backward step of the semilinear BDF loop (timestep_nl_adjoint.hip): the checks of lssvr_ts_nl_assemble on the
+// Jacobian's side and of lssvr_ts_rhs (one case) on the right-hand side's.  The device and the host entry share one
+// validated binding.
+static int bind_ts_nl_adjoint(lssvr::TsNlAdjArgs& a, const double* x, const double* u, const double* a_quad,
+                              const double* cs_quad, const double* q_quad, int64_t ne, int nquad, int kind, int nterm,
+                              const double* mdiag, const double* moff, const double* U0, const double* U1,
+                              const double* loads, const double* phi, int R, double beta0, double beta1, double inv_dt,
+                              double* diag, double* off, double* B, double* band_ends) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  if (const int rc = check_nl_kind(kind, nterm)) return rc;
+  if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
+  if (!is_finite(beta0) || !is_finite(beta1) || !is_finite(inv_dt))
+    return fail(LSSVR_ERR_SIZE, "beta0 = %g, beta1 = %g, inv_dt = %g must be finite", beta0, beta1, inv_dt);
+  if (!x || !u || !cs_quad || !q_quad || !diag || !off || !B || !band_ends)
+    return fail(LSSVR_ERR_NULL, "x, u, cs_quad, q_quad, diag, off, B, band_ends must be non-NULL");
+  if (!mdiag || !moff || !U0 || !loads || !phi)
+    return fail(LSSVR_ERR_NULL, "mdiag, moff, U0, loads, phi must be non-NULL");
+  if (beta1 != 0.0 && !U1) return fail(LSSVR_ERR_NULL, "U1 must be non-NULL when beta1 != 0");
+  const void* outs[] = {diag, off, B, band_ends};
+  const void* ins[] = {x, u, a_quad, cs_quad, q_quad, mdiag, moff, U0, beta1 != 0.0 ? U1 : nullptr, loads, phi};
+  if (aliased(outs, 4, ins, 11))
+    return fail(LSSVR_ERR_SIZE, "diag, off, B, band_ends must be distinct and none of them an input");
+  a.nl = lssvr::TsNlArgs{x, u, a_quad, cs_quad, q_quad, nullptr, ne, nquad, kind, nterm, diag, off, nullptr};
+  a.rhs = lssvr::TsRhsArgs{mdiag, moff, U0, U1, loads, phi, ne, 1, R, beta0, beta1, inv_dt};
+  a.B = B;
+  a.band_ends = band_ends;
+  return LSSVR_OK;
+}
+
+int lssvr_semilinear_adjoint_step(const double* x, const double* u, const double* a_quad, const double* cs_quad,
+                                  const double* q_quad, int64_t ne, int nquad, int kind, int nterm,
+                                  const double* mdiag, const double* moff, const double* U0, const double* U1,
+                                  const double* loads, const double* phi, int R, double beta0, double beta1,
+                                  double inv_dt, double* diag, double* off, double* B, double* band_ends,
+                                  void* stream) {
+  lssvr::TsNlAdjArgs a{};
+  const int rc = bind_ts_nl_adjoint(a, x, u, a_quad, cs_quad, q_quad, ne, nquad, kind, nterm, mdiag, moff, U0, U1,
+                                    loads, phi, R, beta0, beta1, inv_dt, diag, off, B, band_ends);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::ts_nl_adjoint_step(a, reinterpret_cast<hipStream_t>(stream)), "ts_nl_adjoint_step");
+}
+
+int lssvr_semilinear_adjoint_step_host(const double* x_host, const double* u_host, const double* a_quad_host,
+                                       const double* cs_quad_host, const double* q_quad_host, int64_t ne, int nquad,
+                                       int kind, int nterm, const double* mdiag_host, const double* moff_host,
+                                       const double* U0_host, const double* U1_host, const double* loads_host,
+                                       const double* phi_host, int R, double beta0, double beta1, double inv_dt,
+                                       double* diag_host, double* off_host, double* B_host,
+                                       double* band_ends_host) {
+  lssvr::TsNlAdjArgs a{};
+  const int rc = bind_ts_nl_adjoint(a, x_host, u_host, a_quad_host, cs_quad_host, q_quad_host, ne, nquad, kind, nterm,
+                                    mdiag_host, moff_host, U0_host, U1_host, loads_host, phi_host, R, beta0, beta1,
+                                    inv_dt, diag_host, off_host, B_host, band_ends_host);
+  if (rc != LSSVR_OK) return rc;
+  if (!lssvr::ts_nl_adjoint_step_host(a)) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);
+  return LSSVR_OK;
+}
+
 // Newmark: n0 >= 0, Vtraj with gd, Atraj with grho
 static int bind_nm_sens(lssvr::NmSensArgs& a, const double* x, int64_t ne, int nquad, const double* Utraj,
                         const double* Vtraj, const double* Atraj, const double* Z, int64_t n0, int m, const double* phi,

@@ -1,5 +1,5 @@
 // The chunk pass of the time-loop adjoint sensitivities: it turns the adjoint states of m <= 8 consecutive levels of a
-// backward sweep into gradients, summed over time.  Written once and instantiated for the two loops
+// backward sweep into gradients, summed over time.  Written once and instantiated for the three loops
 // (lssvr_chunk_sens.hpp says what each supplies):
 //   BDF loop of  rho u_t - (a u')' + c u = f(x, t)  (DESIGN.md section 32).  The backward sweep is made of the forward
 //     loop's own calls -- lssvr_ts_rhs with U0 = lambda^{n+1}, U1 = lambda^{n+2}, the row p_n as the load and phi = 1,
@@ -8,7 +8,10 @@
 //   Newmark loop of  rho u_tt + d u_t - (a u')' + c u = f(x, t)  (section 34).  The backward sweep alternates
 //     lssvr_tridiag_bc_solve_multi on the forward loop's bands with the adjoint advance of newmark_adjoint.hip.
 //       dJ/drho_eq = -sum_n h_e w_q lambda^n_eq acc^n_eq       dJ/dd_eq = -sum_n h_e w_q lambda^n_eq v^n_eq
-//   both:
+//   semilinear BDF loop of  rho u_t - (a u')' + c u + g(x, u) = f(x, t)  (section 36).  The BDF pass, with one matrix
+//     J_n per level (timestep_nl_adjoint.hip writes its end entries) and, per table q_k of the law,
+//       dJ/dq_{k,eq} = -sum_n h_e w_q lambda^n_eq dg/dq_k(u^n_eq)      (lssvr_chunk_sens.hpp: ChunkNlGq)
+//   all:
 //       dJ/da_eq   = -sum_n (w_q / h_e) dlambda^n_e du^n_e     dJ/dc_eq = -sum_n h_e w_q lambda^n_eq u^n_eq
 //       dJ/df_{r,eq} = +sum_n phi_r(t_n) h_e w_q lambda^n_eq
 //     and the end gradients dJ/dg(t_n), dJ/dkappa.
@@ -27,7 +30,7 @@ namespace lssvr {
 namespace {
 
 template <class Args> LSSVR_SENS_HD bool any_table(const Args& a) {
-  return a.ga || a.gc || a.grho || ChunkScheme<Args>::gd(a) || a.gf;
+  return a.ga || a.gc || a.grho || ChunkScheme<Args>::gd(a) || a.gf || ChunkScheme<Args>::gq(a);
 }
 
 template <class Args> __global__ __launch_bounds__(kBlock) void chunk_sensitivity_kernel(Args a, QuadRule q) {
@@ -62,7 +65,9 @@ template <class Args> bool chunk_sensitivity_host(const Args& a) {
 
 template hipError_t chunk_sensitivity(const TsSensArgs&, hipStream_t);
 template hipError_t chunk_sensitivity(const NmSensArgs&, hipStream_t);
+template hipError_t chunk_sensitivity(const TsNlSensArgs&, hipStream_t);
 template bool chunk_sensitivity_host(const TsSensArgs&);
 template bool chunk_sensitivity_host(const NmSensArgs&);
+template bool chunk_sensitivity_host(const TsNlSensArgs&);
 
 }  // namespace lssvr

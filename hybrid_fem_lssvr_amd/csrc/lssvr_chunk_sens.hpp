@@ -1,8 +1,9 @@
 // The routines behind every value of chunk_sens.hip, the chunk pass of the BDF loop and of the
-// Newmark loop (section 34): the device kernel and the host mirror call them, and with -ffp-contract=off they are
-// bit-equal.  One routine per job; ChunkScheme<Args> supplies, at compile time, the few points at which the loops differ.
+// Newmark loop (section 34) and of the semilinear BDF loop (section 36): the device kernel and the host mirror call
+// them, and with -ffp-contract=off they are bit-equal (but for exp of the semilinear EXP law, libm on the host).  One
+// routine per job; ChunkScheme<Args> supplies, at compile time, the few points at which the loops differ.
 #pragma once
-#include "lssvr_sens.hpp"
+#include "lssvr_nl_sens.hpp"
 
 namespace lssvr {
 
@@ -17,8 +18,16 @@ LSSVR_SENS_HD double ts_sens_diff(double alpha, double beta0, double beta1, doub
 // What a loop's chunk pass has of its own: where a level takes (u0, u1) = u^n[e], u^n[e+1] and the nodal pair (r0, r1)
 // of the rho term, whether there is a table d with its pair, which row of phi is phi(t_n), and which row of band_ends
 // belongs to step row i.  begin() is called once per entry, load() once per level before the pairs are used, in the
-// order i = 0 .. m-1 (n descending), next() after the level.
+// order i = 0 .. m-1 (n descending), next() after the level.  Gq holds the running sums of the tables gq of a law
+// g(x, u) (gq(a): where they go; nullptr: none): begin() once per entry, add() once per level, store() at the end.
 template <class Args> struct ChunkScheme;
+
+// a scheme without a law: no sums, no code
+struct ChunkNoGq {
+  template <class Args> LSSVR_SENS_HD void begin(const Args&, int64_t, int64_t, bool) {}
+  template <class Args> LSSVR_SENS_HD void add(const Args&, double, double) {}
+  template <class Args> LSSVR_SENS_HD void store(const Args&, int64_t, int64_t) const {}
+};
 
 // BDF: (r0, r1) = (w0, w1), wj = inv_dt ((alpha uj - beta0 pj) - beta1 qj) (ts_sens_diff; (alpha, beta0, beta1) =
 // coef[i]) with (p0, p1) of u^{n-1} and (q0, q1) of u^{n-2} (0 for n < 2: there is no such row).  The three rows of the
@@ -48,6 +57,8 @@ template <> struct ChunkScheme<TsSensArgs> {
   static LSSVR_SENS_HD double* gd(const TsSensArgs&) { return nullptr; }
   static LSSVR_SENS_HD int64_t phi_row(int64_t n) { return n - 1; }
   static LSSVR_SENS_HD int band_row(const TsSensArgs& a, int i) { return a.band_row[i]; }
+  using Gq = ChunkNoGq;
+  static LSSVR_SENS_HD double* gq(const TsSensArgs&) { return nullptr; }
 };
 
 // Newmark: (r0, r1) of acc^n = Atraj[n] and the pair of the table d of v^n = Vtraj[n]; phi(t_n) is row n; one matrix
@@ -71,6 +82,56 @@ template <> struct ChunkScheme<NmSensArgs> {
   static LSSVR_SENS_HD double* gd(const NmSensArgs& a) { return a.gd; }
   static LSSVR_SENS_HD int64_t phi_row(int64_t n) { return n; }
   static LSSVR_SENS_HD int band_row(const NmSensArgs&, int) { return 0; }
+  using Gq = ChunkNoGq;
+  static LSSVR_SENS_HD double* gq(const NmSensArgs&) { return nullptr; }
+};
+
+// The sums of gq [nterm][tab] at one entry.  With s = hw (z0 om + z1 xi) and uq = u0 om + u1 xi of the level, as
+// chunk_sens_entry forms them for sc, level by level, one rounding per operation (the per-level terms are those of
+// nl_sens_entry, lssvr_nl_sens.hpp):
+//   POLY   p_0 = 1;  p_k = p_{k-1} uq;  gq_0 = gq_0 - s;  gq_k = gq_k - (s p_k)       k = 1 .. nterm-1
+//          (p_1 = 1 uq is uq itself: gq_1 is gc, and with phi = 1 gq_0 is -gf, bit for bit)
+//   EXP    E = exp(q_1 uq);  gq_0 = gq_0 - (s E);  gq_1 = gq_1 - (s ((q_0 uq) E))
+// The k-loops are unrolled over kNlSensMaxTerms with the uniform bound nterm: no lane indexes a private array.
+struct ChunkNlGq {
+  double g[kNlSensMaxTerms];
+  double q0, q1;
+  LSSVR_SENS_HD void begin(const TsNlSensArgs& a, int64_t tab, int64_t idx, bool acc) {
+    const bool is_exp = a.law == LSSVR_NL_EXP;
+    q0 = is_exp ? a.q_tabs[idx] : 0.0;
+    q1 = is_exp ? a.q_tabs[tab + idx] : 0.0;
+#pragma unroll
+    for (int k = 0; k < kNlSensMaxTerms; ++k) g[k] = acc && k < a.nterm ? a.gq[(int64_t)k * tab + idx] : 0.0;
+  }
+  LSSVR_SENS_HD void add(const TsNlSensArgs& a, double s, double uq) {
+    if (a.law == LSSVR_NL_EXP) {
+      const double E = exp(q1 * uq);
+      g[0] = g[0] - (s * E);
+      g[1] = g[1] - (s * ((q0 * uq) * E));
+    } else {
+      g[0] = g[0] - s;
+      double pk = 1.0;
+#pragma unroll
+      for (int k = 1; k < kNlSensMaxTerms; ++k) {
+        if (k < a.nterm) {
+          pk = pk * uq;
+          g[k] = g[k] - (s * pk);
+        }
+      }
+    }
+  }
+  LSSVR_SENS_HD void store(const TsNlSensArgs& a, int64_t tab, int64_t idx) const {
+#pragma unroll
+    for (int k = 0; k < kNlSensMaxTerms; ++k)
+      if (k < a.nterm) a.gq[(int64_t)k * tab + idx] = g[k];
+  }
+};
+
+// semilinear BDF: the BDF scheme with one matrix per level (band_ends [m][2]: step row i has row i) and the law's sums
+template <> struct ChunkScheme<TsNlSensArgs> : ChunkScheme<TsSensArgs> {
+  static LSSVR_SENS_HD int band_row(const TsNlSensArgs&, int i) { return i; }
+  using Gq = ChunkNlGq;
+  static LSSVR_SENS_HD double* gq(const TsNlSensArgs& a) { return a.gq; }
 };
 
 // Entry idx = e * nquad + k of the tables ga, gc, grho, gd (a scheme with a table d) and gf[r], for the m levels of the
@@ -85,6 +146,7 @@ template <> struct ChunkScheme<NmSensArgs> {
 //   sr  = sr - (t (r0 om + r1 xi))
 //   sd  = sd - (t (d0 om + d1 xi))
 //   sf_r = sf_r + phi(t_n)[r] t                                     r = 0 .. R-1
+//   the scheme's Gq sums with (t, u0 om + u1 xi)                    (a scheme with a law)
 // and the sums are stored once.  Because a sum CONTINUES from the stored value, a sweep gives the same bits however it
 // is cut into chunks.  A table that is not asked for costs neither arithmetic that only it needs nor a store.
 template <class Args> LSSVR_SENS_HD void chunk_sens_entry(const Args& a, const QuadRule& q, int64_t idx) {
@@ -94,6 +156,7 @@ template <class Args> LSSVR_SENS_HD void chunk_sens_entry(const Args& a, const Q
   const int64_t nhi = a.n0 + a.m - 1;
   const bool acc = a.accumulate != 0;
   double* const gd = S::gd(a);
+  double* const gq = S::gq(a);
   double sa = acc && a.ga ? a.ga[idx] : 0.0;
   double sc = acc && a.gc ? a.gc[idx] : 0.0;
   double sr = acc && a.grho ? a.grho[idx] : 0.0;
@@ -101,6 +164,8 @@ template <class Args> LSSVR_SENS_HD void chunk_sens_entry(const Args& a, const Q
   double sf[kChunkSensMaxTerms];
 #pragma unroll
   for (int r = 0; r < kChunkSensMaxTerms; ++r) sf[r] = acc && a.gf && r < a.R ? a.gf[(int64_t)r * tab + idx] : 0.0;
+  typename S::Gq sq;
+  if (gq) sq.begin(a, tab, idx, acc);
   S s;
   s.begin(a, p.e, nhi);
   for (int i = 0; i < a.m; ++i) {
@@ -127,6 +192,7 @@ template <class Args> LSSVR_SENS_HD void chunk_sens_entry(const Args& a, const Q
       for (int r = 0; r < kChunkSensMaxTerms; ++r)
         if (r < a.R) sf[r] = sf[r] + phi[r] * t;
     }
+    if (gq) sq.add(a, t, s.u0 * p.om + s.u1 * p.xi);
     s.next();
   }
   if (a.ga) a.ga[idx] = sa;
@@ -138,6 +204,7 @@ template <class Args> LSSVR_SENS_HD void chunk_sens_entry(const Args& a, const Q
     for (int r = 0; r < kChunkSensMaxTerms; ++r)
       if (r < a.R) a.gf[(int64_t)r * tab + idx] = sf[r];
   }
+  if (gq) sq.store(a, tab, idx);
 }
 
 // The end gradients of the chunk: out_g[n][s] of every level n of the chunk, and out_kappa[s] continued from what it

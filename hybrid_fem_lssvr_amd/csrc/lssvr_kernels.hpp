@@ -517,6 +517,19 @@ struct TsNlArgs {
 hipError_t ts_nl_assemble(const TsNlArgs& a, hipStream_t s);
 bool ts_nl_assemble_host(const TsNlArgs& a);      // false: no rule of a.nquad points
 
+// timestep_nl_adjoint.hip: the backward step of the semilinear BDF loop.  ONE launch per level
+// n writes the bands of the Jacobian J_n = K + M(cs + g_u(., u^n_h)), the adjoint right-hand side B_n and the end
+// entries of J_n.  `nl` is read as by ts_nl_assemble with u = u^n (nl.r and nl.rhs are not used); `rhs` as by ts_rhs
+// with nc = 1: U0 = lambda^{n+1}, U1 = lambda^{n+2}, loads [R][ne+1] and phi [R] the rows p_n with their weights.
+struct TsNlAdjArgs {
+  TsNlArgs nl;
+  TsRhsArgs rhs;
+  double* B;                        // [ne+1]: the row of ts_rhs
+  double* band_ends;                // [2] = {off[0], off[ne-1]}: the chunk's row of this level
+};
+hipError_t ts_nl_adjoint_step(const TsNlAdjArgs& a, hipStream_t s);
+bool ts_nl_adjoint_step_host(const TsNlAdjArgs& a);      // false: no rule of a.nl.nquad points
+
 // wave.hip: Newmark steps of rho u_tt + d u_t - (a u')' + c u = f.  Vectors are case-major
 // [nc][ne+1]; the host form runs the same inline routines on host arrays, bit for bit.
 struct WaveArgs {
@@ -634,7 +647,15 @@ struct NmSensArgs : ChunkSensArgs {
   const double* Atraj;              // row n = acc^n; read for grho only
   double* gd;                       // dJ/dd_quad [ne*nquad]; nullptr: skipped
 };
-// Args: TsSensArgs or NmSensArgs
+// semilinear BDF (section 36): the BDF scheme, with one matrix per level -- band_ends [m][2], band_row[i] = i -- and the
+// tables of g(x, u): gq [nterm][ne*nquad] receives dJ/dq_k summed over the chunk (nullptr: skipped); q_tabs
+// [nterm][ne*nquad] is read for LSSVR_NL_EXP only
+struct TsNlSensArgs : TsSensArgs {
+  const double* q_tabs;
+  int law, nterm;                   // LSSVR_NL_*; POLY 1 <= nterm <= 6, EXP nterm == 2
+  double* gq;
+};
+// Args: TsSensArgs, NmSensArgs or TsNlSensArgs
 template <class Args> hipError_t chunk_sensitivity(const Args& a, hipStream_t s);
 template <class Args> bool chunk_sensitivity_host(const Args& a);   // false: no such quadrature rule
 

@@ -2396,12 +2396,12 @@ def enhance_adjoint(x, W, Wbar, M, gamma, n_colloc, rhs_values, *, a_values=None
 
 # ---- the chunk pass of the time-loop adjoint sensitivities (DESIGN.md sections 32 and 34) ------------------------------
 def _chunk_sens(tables, n0_min, phi_rows, band_shape, x, Utraj, Z, n0, nquad, want, trajs, phi, Brows, band_ends,
-                end_kinds, accumulate, out):
-    """What :func:`ts_sensitivity` and :func:`newmark_sensitivity` share: every check of the chunk's arguments, the
-    ``accumulate`` rule, the allocation of the outputs and the alias and device checks.  ``tables``: the scheme's keys of
+                end_kinds, accumulate, out, leading=None):
+    """What :func:`ts_sensitivity`, :func:`newmark_sensitivity` and :func:`ts_nl_sensitivity` share: every check of the
+    chunk's arguments, the ``accumulate`` rule, the allocation of the outputs and the alias and device checks.  ``tables``: the scheme's keys of
     ``want``; ``n0_min``: its lowest first level; ``phi_rows``: how many rows more than N its phi has; ``band_shape``:
-    the shape of its ``band_ends``; ``trajs``: {name: (table, tensor)}, its own trajectories, each needed for one
-    table.  Returns (ne, nquad, n0, m, R, kinds, ins, res): ``ins`` the inputs given, by name, and ``res`` the
+    the shape of its ``band_ends`` (-1: the chunk's m); ``trajs``: {name: (table, tensor)}, its own trajectories, each
+    needed for one table; ``leading``: {table: n}, its tables that are [n, ne, nquad].  Returns (ne, nquad, n0, m, R, kinds, ins, res): ``ins`` the inputs given, by name, and ``res`` the
     outputs."""
     for nm, t in (("x", x), ("Utraj", Utraj), ("Z", Z)):
         _dev(t, nm)
@@ -2441,6 +2441,7 @@ def _chunk_sens(tables, n0_min, phi_rows, band_shape, x, Utraj, Z, n0, nquad, wa
         ins["phi"] = phi
     out = {} if out is None else out
     shapes = {k: ((R, ne, nquad) if k == "f" else (ne, nquad)) for k in want}
+    shapes.update({k: (n, ne, nquad) for k, n in (leading or {}).items() if k in want})
     kinds = (END_DIRICHLET, END_DIRICHLET)
     if Brows is not None:
         if band_ends is None:
@@ -2449,6 +2450,7 @@ def _chunk_sens(tables, n0_min, phi_rows, band_shape, x, Utraj, Z, n0, nquad, wa
             _dev(t, nm)
         if Brows.shape != Z.shape:
             raise ValueError(f"Brows must have the shape of Z {list(Z.shape)}, got {list(Brows.shape)}")
+        band_shape = tuple(m if n == -1 else n for n in band_shape)
         if tuple(band_ends.shape) != band_shape:
             raise ValueError(f"band_ends must be {list(band_shape)}, got {list(band_ends.shape)}")
         kinds, _ = _end_kinds(end_kinds, (0.0, 0.0))
@@ -2503,6 +2505,100 @@ def ts_sensitivity(x, Utraj, Z, n0, coef, inv_dt, nquad=2, *, want=TS_SENS_TABLE
                                          _ptr(Brows), _ptr(band_ends), sum(r << i for i, r in enumerate(rows)), *kinds,
                                          _ptr(res.get("g")), _ptr(res.get("kappa")), _stream(stream))
     _capi.check(rc, "lssvr_transient_sensitivity")
+    return res
+
+
+# ---- adjoint sensitivities of the semilinear BDF loop --------------------------------------------
+TS_NL_SENS_TABLES = TS_SENS_TABLES + ("q",)     # "q": d/d q_quad, the tables of g(x, u)
+
+
+def ts_nl_sensitivity(x, Utraj, Z, n0, coef, inv_dt, nquad, kind, nterm, *, q_tabs=None, want=TS_NL_SENS_TABLES,
+                      phi=None, Brows=None, band_ends=None, end_kinds=(END_DIRICHLET, END_DIRICHLET), accumulate=False,
+                      out=None, stream=None):
+    """``lssvr_semilinear_transient_sensitivity``: :func:`ts_sensitivity` for the semilinear loop of
+    :func:`ts_nl_assemble` with g(x, u) of ``kind`` ("poly" / ``NL_POLY``, "exp" / ``NL_EXP``) and ``nterm`` tables, in
+    ONE launch per chunk.  Utraj holds the CONVERGED states u^n and Z the adjoint states of the Jacobians J_n AT u^n
+    (:func:`ts_nl_adjoint_step` and one :func:`tridiag_bc_solve_multi` per level).  ``want`` names any of "a", "c",
+    "rho", "f" -- bit for bit the values of :func:`ts_sensitivity` -- and "q" -- float64[nterm, ne, nquad] = dJ/dq_k at
+    every quadrature point, summed over the chunk's levels; "q" of "poly" has q[1] == c bit for bit, and q[0] == -f[0]
+    where phi is 1.  ``q_tabs`` float64[nterm, ne, nquad], the tables :func:`ts_nl_assemble` took, is read for "exp"
+    with "q" only and must be given then.  ``band_ends`` float64[m, 2]: every level has its own matrix, row i =
+    {off[0], off[ne-1]} of step row i's J_n (there are no ``band_rows``).  Everything else -- the order of the rows,
+    ``coef``, ``phi``, ``Brows``, ``end_kinds``, ``accumulate``, ``out`` and the result -- as for
+    :func:`ts_sensitivity`.  No synchronisation and no copy; bitwise reproducible."""
+    lib = _capi.load()
+    kind, nterm = nl_kind(kind, nterm)
+    ne, nquad, n0, m, R, kinds, ins, res = _chunk_sens(TS_NL_SENS_TABLES, 1, 0, (-1, 2), x, Utraj, Z, n0, nquad, want,
+                                                       {}, phi, Brows, band_ends, end_kinds, accumulate, out,
+                                                       leading={"q": nterm})
+    if q_tabs is not None:
+        _dev(q_tabs, "q_tabs")
+        if tuple(q_tabs.shape) != (nterm, ne, nquad):
+            raise ValueError(f"q_tabs must be [nterm, ne, nquad] = [{nterm}, {ne}, {nquad}], got {list(q_tabs.shape)}")
+        _no_alias("the outputs must be distinct and none of them an input", res.values(), (q_tabs,))
+        _same_device(x, q_tabs=q_tabs)
+    elif kind == NL_EXP and "q" in res:
+        raise ValueError("kind 'exp' needs q_tabs: dJ/dq_k depends on q_0 and q_1")
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.float64))
+    if coef.shape != (m, 3) or not np.all(np.isfinite(coef)):
+        raise ValueError(f"coef must be m = {m} finite triples (alpha, beta0, beta1), got shape {list(coef.shape)}")
+    (inv_dt,) = _finite(inv_dt=inv_dt)
+    rc = lib.lssvr_semilinear_transient_sensitivity(_ptr(x), ne, nquad, _ptr(Utraj), _ptr(Z), n0, m, inv_dt,
+                                                    coef.ctypes.data_as(_capi._c_hd), _ptr(ins.get("phi")), R,
+                                                    _ptr(q_tabs), kind, nterm,
+                                                    *(_ptr(res.get(k)) for k in TS_NL_SENS_TABLES),
+                                                    int(bool(accumulate)), _ptr(Brows), _ptr(band_ends), *kinds,
+                                                    _ptr(res.get("g")), _ptr(res.get("kappa")), _stream(stream))
+    _capi.check(rc, "lssvr_semilinear_transient_sensitivity")
+    return res
+
+
+def ts_nl_adjoint_step(x, u, cs_quad, kind, q_quad, mdiag, moff, U0, U1, loads, phi, beta0, beta1, inv_dt, *,
+                       a_quad=None, out=None, stream=None):
+    """``lssvr_semilinear_adjoint_step``: everything one level of the backward sweep of the semilinear BDF loop needs
+    before its solve, in ONE launch -- the bands of the Jacobian J_n = K + M(cs + g_u(., u_h)) AT ``u`` = u^n, bit for
+    bit "diag" and "off" of :func:`ts_nl_assemble` there (whose right-hand side is not formed); the adjoint right-hand
+    side "B" float64[1, ne+1], bit for bit :func:`ts_rhs` of (mdiag, moff, U0 = lambda^{n+1}, U1 = lambda^{n+2}, loads,
+    phi, beta0, beta1, inv_dt) with one case; and "band_ends" float64[2] = {off[0], off[ne-1]}, the level's row of
+    :func:`ts_nl_sensitivity`'s ``band_ends``.  ``x``, ``u``, ``cs_quad``, ``kind``, ``q_quad``, ``a_quad`` as for
+    :func:`ts_nl_assemble`; U0, U1 float64[1, ne+1] (``beta1 == 0`` reads no U1, ``None`` allowed), loads
+    float64[R, ne+1], phi float64[1, R].  ``out``: a dict of buffers to write into, by those four keys (a missing one is
+    allocated); none of them may be an input.  Returns that dict.  No synchronisation and no copy; bitwise
+    reproducible."""
+    lib = _capi.load()
+    for nm, t in (("x", x), ("u", u), ("cs_quad", cs_quad), ("q_quad", q_quad), ("mdiag", mdiag), ("moff", moff),
+                  ("U0", U0), ("loads", loads), ("phi", phi)):
+        _dev(t, nm)
+    ne = _nodes(x, "x")
+    _nodal(ne, u=u)
+    if cs_quad.dim() != 2 or cs_quad.shape[0] != ne or not 1 <= cs_quad.shape[1] <= 5:
+        raise ValueError(f"cs_quad must be [ne, nquad] = [{ne}, 1 .. 5], got {list(cs_quad.shape)}")
+    nquad = int(cs_quad.shape[1])
+    if q_quad.dim() != 3 or tuple(q_quad.shape[1:]) != (ne, nquad):
+        raise ValueError(f"q_quad must be [nterm, {ne}, {nquad}], got {list(q_quad.shape)}")
+    kind, nterm = nl_kind(kind, q_quad.shape[0])
+    if a_quad is not None:
+        _dev(a_quad, "a_quad")
+        if a_quad.shape != cs_quad.shape:
+            raise ValueError(f"a_quad must have the shape of cs_quad {list(cs_quad.shape)}, got {list(a_quad.shape)}")
+    beta0, beta1, inv_dt = _finite(beta0=beta0, beta1=beta1, inv_dt=inv_dt)
+    _band_pair("band lengths must be ne+1, ne (mdiag, moff)", mdiag, moff, ne)
+    out = {} if out is None else out
+    nc, R, B = _bdf_state(ne, x, U0, U1, loads, phi, beta1, out.get("B"))
+    if nc != 1:
+        raise ValueError(f"U0 must be [1, ne+1]: the backward step has one case, got {list(U0.shape)}")
+    res = {k: _out(out.get(k), f"out[{k!r}]", shape, x) for k, shape in (("diag", (ne + 1,)), ("off", (ne,)),
+                                                                          ("band_ends", (2,)))}
+    res["B"] = B
+    ins = (x, u, cs_quad, q_quad, a_quad, mdiag, moff, U0, U1, loads, phi)
+    _no_alias("diag, off, B and band_ends must be distinct and none of them an input", res.values(), ins)
+    _same_device(x, u=u, cs_quad=cs_quad, q_quad=q_quad, a_quad=a_quad, mdiag=mdiag, moff=moff, U0=U0, loads=loads,
+                 phi=phi, **({} if U1 is None else {"U1": U1}))
+    rc = lib.lssvr_semilinear_adjoint_step(_ptr(x), _ptr(u), _ptr(a_quad), _ptr(cs_quad), _ptr(q_quad), ne, nquad, kind,
+                                           nterm, _ptr(mdiag), _ptr(moff), _ptr(U0), _ptr(U1), _ptr(loads), _ptr(phi),
+                                           R, beta0, beta1, inv_dt, _ptr(res["diag"]), _ptr(res["off"]), _ptr(B),
+                                           _ptr(res["band_ends"]), _stream(stream))
+    _capi.check(rc, "lssvr_semilinear_adjoint_step")
     return res
 
 

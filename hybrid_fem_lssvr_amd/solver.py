@@ -480,13 +480,16 @@ class TransientSensitivity:
     ``d_u0`` [ne+1]: dJ/du0 at the nodes (0 at a Dirichlet end: the start is g(0) there); ``d_end_values``
     [nsteps+1, 2]: dJ/dg(t_n) of the left and right end datum, row n for t_n (row 0: the start of a Dirichlet end);
     ``d_kappa`` [2] (0 at a Dirichlet end); ``times`` [nsteps+1] and ``nodes``.  Neither the mesh nor dt is
-    differentiated."""
+    differentiated.  With ``nonlinear=``: ``d_nonlinear`` [nterm, ne, nquad]: dJ/dq_k of the tables of g(x, u), and
+    ``newton`` [nsteps, newton_iters, 4]: the monitor of the forward loop (|R|, |dv|, |v|, non-finite count per
+    iteration), as ``TransientSolution.newton``; both ``None`` for a linear call."""
 
-    def __init__(self, value, tables, d_u0, d_end_values, d_kappa, times, nodes):
+    def __init__(self, value, tables, d_u0, d_end_values, d_kappa, times, nodes, d_nonlinear=None, newton=None):
         self.value = float(value)
         self.d_coef, self.d_reaction, self.d_weight, self.d_forcing = (tables[k] for k in ops.TS_SENS_TABLES)
         self.d_u0, self.d_end_values, self.d_kappa = d_u0, d_end_values, d_kappa
         self.times, self.nodes = times, nodes
+        self.d_nonlinear, self.newton = d_nonlinear, newton
 
 
 class WaveSensitivity:
@@ -1800,6 +1803,41 @@ class FEMLSSVRPrimalSolver:
                              "be positive definite, and the solve does not pivot; shorten the step")
         return p
 
+    @staticmethod
+    def _newton_args(who, nonlinear, newton_iters, newton_tol):
+        """The semilinear keywords of :meth:`solve_transient` and :meth:`solve_transient_sensitivity` -> (the parsed
+        law or None, newton_iters, newton_tol): ``newton_*`` only come with ``nonlinear``; defaults 3 and 1e-10."""
+        if nonlinear is None:
+            if newton_iters is not None or newton_tol is not None:
+                raise ValueError(f"newton_iters and newton_tol belong to {who}(..., nonlinear=...)")
+            return None, None, None
+        nl = _Nonlinear(nonlinear)
+        newton_iters, newton_tol = 3 if newton_iters is None else newton_iters, 1e-10 if newton_tol is None \
+            else newton_tol
+        if isinstance(newton_iters, bool) or int(newton_iters) != newton_iters or not 1 <= int(newton_iters) <= 8:
+            raise ValueError(f"newton_iters must be an integer in 1 .. 8, got {newton_iters!r}")
+        if not (float(newton_tol) > 0.0) or not math.isfinite(float(newton_tol)):
+            raise ValueError(f"newton_tol must be finite and > 0, got {newton_tol!r}")
+        return nl, int(newton_iters), float(newton_tol)
+
+    @staticmethod
+    def _newton_failures(who, newton, iters, tol):
+        """The two ``RuntimeError``s of a semilinear loop from its monitor ``newton`` [nsteps, iters, 4] on the host: a
+        non-finite value met, or a last increment above ``tol`` max(1, |v|_inf)."""
+        def history(i):
+            return ", ".join(f"|R| {r:.3e} |dv| {d:.3e}" for r, d, _, _ in newton[i])
+        bad = np.nonzero(newton[:, :, 3].sum(axis=1) != 0.0)[0]
+        if bad.size:
+            i = int(bad[0])
+            raise RuntimeError(f"{who}: step {i + 1} met {int(newton[i, :, 3].sum())} non-finite value(s) in "
+                               f"its Newton iteration ({history(i)}); shorten the step")
+        last = newton[:, -1, :]
+        slow = np.nonzero(last[:, 1] > tol * np.maximum(1.0, last[:, 2]))[0]
+        if slow.size:
+            i = int(slow[0])
+            raise RuntimeError(f"{who}: step {i + 1} did not converge in {iters} Newton iteration(s) to "
+                               f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
+
     def solve_transient(self, u0, t_end, *, nsteps, scheme="bdf2", weight=None, forcing=None, end_data=None,
                         snapshots=None, enhance=True, nonlinear=None, newton_iters=None, newton_tol=None):
         """rho u_t - (a u')' + c u = f(x, t) for 0 < t <= ``t_end`` with u(x, 0) = ``u0(x)``, on the solver's ``mesh``
@@ -1837,19 +1875,8 @@ class FEMLSSVRPrimalSolver:
         if self.nonlinear is not None:
             raise ValueError("solve_transient takes the semilinear term as its own keyword: build the solver without "
                              "nonlinear= and call solve_transient(..., nonlinear=...)")
-        nl, enhance = None, bool(enhance)
-        if nonlinear is None:
-            if newton_iters is not None or newton_tol is not None:
-                raise ValueError("newton_iters and newton_tol belong to solve_transient(..., nonlinear=...)")
-        else:
-            nl = _Nonlinear(nonlinear)
-            newton_iters, newton_tol = 3 if newton_iters is None else newton_iters, 1e-10 if newton_tol is None \
-                else newton_tol
-            if isinstance(newton_iters, bool) or int(newton_iters) != newton_iters or not 1 <= int(newton_iters) <= 8:
-                raise ValueError(f"newton_iters must be an integer in 1 .. 8, got {newton_iters!r}")
-            if not (float(newton_tol) > 0.0) or not math.isfinite(float(newton_tol)):
-                raise ValueError(f"newton_tol must be finite and > 0, got {newton_tol!r}")
-            iters, tol = int(newton_iters), float(newton_tol)
+        enhance = bool(enhance)
+        nl, iters, tol = self._newton_args("solve_transient", nonlinear, newton_iters, newton_tol)
         p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, snapshots, enhance)
         kinds, kappa, steps, q, n = p.kinds, p.kappa, p.steps, p.quad, int(self.n_colloc)
         if nl is not None:
@@ -1937,19 +1964,7 @@ class FEMLSSVRPrimalSolver:
         bands = dict(mass=host["mass"], loads=host["loads"], step={al: host[f"step{i}"] for i, al in enumerate(order)})
         newton = host["newton"]
         if nl is not None:
-            def history(i):
-                return ", ".join(f"|R| {r:.3e} |dv| {d:.3e}" for r, d, _, _ in newton[i])
-            bad = np.nonzero(newton[:, :, 3].sum(axis=1) != 0.0)[0]
-            if bad.size:
-                i = int(bad[0])
-                raise RuntimeError(f"solve_transient: step {i + 1} met {int(newton[i, :, 3].sum())} non-finite value(s) in "
-                                   f"its Newton iteration ({history(i)}); shorten the step")
-            last = newton[:, -1, :]
-            slow = np.nonzero(last[:, 1] > tol * np.maximum(1.0, last[:, 2]))[0]
-            if slow.size:
-                i = int(slow[0])
-                raise RuntimeError(f"solve_transient: step {i + 1} did not converge in {iters} Newton iteration(s) to "
-                                   f"newton_tol = {tol:g} ({history(i)}); raise newton_iters or shorten the step")
+            self._newton_failures("solve_transient", newton, iters, tol)
         return TransientSolution(p.times[steps].copy(), host["nodal"], enhanced, bands, newton)
 
     # ---- adjoint sensitivities of the BDF loop (no reference counterpart) ---------------------
@@ -2033,7 +2048,7 @@ class FEMLSSVRPrimalSolver:
 
     def solve_transient_sensitivity(self, u0, t_end, *, nsteps, scheme="bdf2", weight=None, forcing=None, end_data=None,
                                     goal=None, goal_steps=None, goal_weights=None, observe=None,
-                                    max_state_bytes=2 ** 31):
+                                    max_state_bytes=2 ** 31, nonlinear=None, newton_iters=None, newton_tol=None):
         """Derivatives of a functional J of the trajectory of :meth:`solve_transient` (same ``u0``, ``t_end``,
         ``nsteps``, ``scheme``, ``weight``, ``forcing``, ``end_data``) with respect to the data of the loop, by the
         discrete adjoint: exact for the discrete scheme, at the cost of one more loop of the same length.  ``goal``: a
@@ -2052,16 +2067,34 @@ class FEMLSSVRPrimalSolver:
         synchronises or copies from the host.  Returns a :class:`TransientSensitivity`; the solver's attributes are
         left as they are.
 
+        ``nonlinear`` (with ``newton_iters``, ``newton_tol``; the rules of :meth:`solve_transient`: the term is given
+        HERE, on a solver built without it) differentiates the semilinear loop rho u_t - (a u')' + c u + g(x, u) = f
+        (DESIGN.md section 36).  The gradient is that of the CONVERGED implicit step: level n counts as the solution of
+        F_n(u^n) = 0, which the Newton iteration converges to quadratically, so a state whose last increment is |dv|
+        differs from it by O(|dv|^2), and so does the gradient; ``newton`` of the result holds |dv| of every iteration
+        (differentiating through a fixed iteration count would need g_uu and is not built).  The forward loop is
+        :meth:`solve_transient`'s semilinear loop, call for call, into the stored trajectory; its monitor is read once
+        after the loop (with the observed states of a misfit) and the two ``RuntimeError``s of :meth:`solve_transient`
+        are raised BEFORE the backward sweep.  Per level the sweep then issues ONE ``ops.ts_nl_adjoint_step`` -- the
+        bands of the Jacobian J_n = K + M(c + alpha_n rho / dt + g_u(., u^n_h)) AT u^n (not the forward loop's last
+        Newton matrix, linearised one iterate earlier), B_n and the end entries of J_n -- and one
+        ``ops.tridiag_bc_solve_multi``, and per chunk ONE ``ops.ts_nl_sensitivity``, which adds ``d_nonlinear``
+        [nterm, ne, nquad] = dJ/dq_k at every quadrature point.  ``nonlinear=None`` issues exactly the calls above;
+        ``d_nonlinear`` and ``newton`` are then ``None``.
+
         Refused (``ValueError``, before any device call): what :meth:`solve_transient` refuses (convection,
         ``boundary="periodic"``, a ``fem_solver`` other than "bands", ``element_degrees``, a solver other than
-        ``ops.SOLVER_PRIMAL``), ``nonlinear=``, both or neither of ``goal`` and ``observe``, a step outside
-        1 .. nsteps or named twice, data of the wrong shape or not finite, and a trajectory of more than
+        ``ops.SOLVER_PRIMAL``), a solver built with ``nonlinear=``, both or neither of ``goal`` and ``observe``, a step
+        outside 1 .. nsteps or named twice, data of the wrong shape or not finite, and a trajectory of more than
         ``max_state_bytes``: checkpointing is not built."""
         self._check_nonlinear("solve_transient_sensitivity")
+        nl, iters, tol = self._newton_args("solve_transient_sensitivity", nonlinear, newton_iters, newton_tol)
         p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, None, False)
         jsteps, rows, functional = self._check_transient_sensitivity(p, goal, goal_steps, goal_weights, observe,
                                                                      max_state_bytes)
         kinds, kappa, q = p.kinds, p.kappa, p.quad
+        if nl is not None:
+            qq_host = nl.host_tables(self._nl_host_points(p.nodes)[0], "quadrature")
         # ---- the device from here on
         torch = _torch()
         nsteps, ne, inv_dt = int(nsteps), p.nodes.size - 1, 1.0 / p.dt
@@ -2078,17 +2111,51 @@ class FEMLSSVRPrimalSolver:
             """(alpha_n, beta0_n, beta1_n); zeros beyond the last step."""
             return (0.0, 0.0, 0.0) if n > nsteps else bdf1 if n == 1 else bdf
 
+        if nl is not None:
+            qq = _to_dev(qq_host, dev)
+            V = torch.empty((2, ne + 1), dtype=torch.float64, device=dev)         # the Newton iterates of a step
+            rhs = torch.empty((1, ne + 1), dtype=torch.float64, device=dev)
+            nb = dict(diag=torch.empty(ne + 1, dtype=torch.float64, device=dev),
+                      off=torch.empty(ne, dtype=torch.float64, device=dev), rhs=rhs[0])
+            mon = torch.zeros((nsteps, iters, 4), dtype=torch.float64, device=dev)
+            rwork = ops._scratch(None, ops._capi.load().lssvr_nl_residual_work_bytes(ne), dev)
         # the forward loop of solve_transient, every state kept: row n of U is u^n
         for n in range(1, nsteps + 1):
             al, b0, b1 = coefficients(n)
             ops.ts_rhs(md, mo, U[n - 1:n], None if b1 == 0.0 else U[n - 2:n - 1], loads, phi[n - 1:n], b0, b1, inv_dt,
                        out=b)
-            ops.tridiag_bc_solve_multi(*D.bands[al], b, kinds, kappa, g[n - 1:n], out=U[n:n + 1], work=work)
+            if nl is None:
+                ops.tridiag_bc_solve_multi(*D.bands[al], b, kinds, kappa, g[n - 1:n], out=U[n:n + 1], work=work)
+                continue
+            if b1 == 0.0:
+                V[0].copy_(U[n - 1])
+            else:
+                ops.nl_step(U[n - 2], U[n - 1], 2.0, out=V[0])
+            v, spare = V[0], V[1]
+            for it in range(iters):
+                tgt = U[n] if it == iters - 1 else spare
+                ops.ts_nl_assemble(x, v, D.cq[al], nl.kind, qq, b[0], a_quad=D.aq, out=nb)
+                ops.tridiag_bc_solve_multi(nb["diag"], nb["off"], rhs, kinds, kappa, g[n - 1:n], out=tgt.unsqueeze(0),
+                                           work=work)
+                ops.nl_residual(nb["diag"], nb["off"], nb["off"], nb["rhs"], v, tgt, kinds, kappa, g[n - 1],
+                                out4=mon[n - 1, it], work=rwork)
+                v, spare = tgt, v
+        newton = None
+        if nl is not None:
+            # the one read-back between the loops: the monitor, and the observed states a misfit forms its rows from
+            between = _read_back(newton=mon, u=U[torch.as_tensor(jsteps, device=dev)])
+            newton = between["newton"]
+            self._newton_failures("solve_transient_sensitivity", newton, iters, tol)
+            if rows is None:
+                rows = functional(between["u"])[1]
         # the rows p_n that are not zero, and a zero row for every other step (and for lambda^{N+1}, lambda^{N+2})
         jidx, P, prow = _functional_rows(U, jsteps, rows, functional, zero_rows=1)
         zero, one = P[len(jsteps):], torch.ones((1, 1), dtype=torch.float64, device=dev)
         chunk = ops.TS_SENS_CHUNK
         Zb, Bb = (torch.empty((2, chunk, ne + 1), dtype=torch.float64, device=dev) for _ in range(2))
+        if nl is not None:
+            return self._transient_nl_backward(p, D, nl, qq, U, jidx, P, prow, zero, one, Zb, Bb, coefficients,
+                                               functional, newton)
         band_ends = torch.stack([torch.stack((D.bands[al][1][0], D.bands[al][1][ne - 1])) for al in (bdf1[0], bdf[0])])
         out = dict(g=torch.zeros((nsteps + 1, 2), dtype=torch.float64, device=dev))
         lam1, lam2 = zero, zero                                        # lambda^{n+1}, lambda^{n+2}
@@ -2115,6 +2182,46 @@ class FEMLSSVRPrimalSolver:
         _dirichlet_u0(kinds, d_u0, d_g)
         return TransientSensitivity(value, {k: host[k].copy() for k in ops.TS_SENS_TABLES}, d_u0, d_g,
                                     host["kappa"].copy(), p.times.copy(), p.nodes)
+
+    def _transient_nl_backward(self, p, D, nl, qq, U, jidx, P, prow, zero, one, Zb, Bb, coefficients, functional,
+                               newton):
+        """The backward sweep of :meth:`solve_transient_sensitivity` with ``nonlinear=``, on what
+        its forward loop left: per level ONE ``ops.ts_nl_adjoint_step`` (the Jacobian AT u^n, B_n, the end entries) and
+        one solve, per chunk ONE ``ops.ts_nl_sensitivity``; launches on the current stream only."""
+        torch = _torch()
+        dev, x, b, work, kinds, kappa = D.dev, D.x, D.b, D.work, p.kinds, p.kappa
+        nsteps, ne, inv_dt, chunk = len(p.times) - 1, p.nodes.size - 1, 1.0 / p.dt, ops.TS_SENS_CHUNK
+        md, mo = D.bands["mass"]
+        nterm, nzero = int(qq.shape[0]), len(prow)
+        jac = dict(diag=torch.empty(ne + 1, dtype=torch.float64, device=dev),
+                   off=torch.empty(ne, dtype=torch.float64, device=dev))
+        band_ends = torch.empty((chunk, 2), dtype=torch.float64, device=dev)
+        out = dict(g=torch.zeros((nsteps + 1, 2), dtype=torch.float64, device=dev))
+        lam1, lam2 = zero, zero                                        # lambda^{n+1}, lambda^{n+2}
+        for hi, m, side in _sweep_chunks(nsteps, chunk):
+            Z, B = Zb[side, :m], Bb[side, :m]
+            for i in range(m):
+                n = hi - i
+                b0, b1 = coefficients(n + 1)[1], coefficients(n + 2)[2]
+                k = prow.get(n, nzero)
+                ops.ts_nl_adjoint_step(x, U[n], D.cq[coefficients(n)[0]], nl.kind, qq, md, mo, lam1,
+                                       None if b1 == 0.0 else lam2, P[k:k + 1], one, b0, b1, inv_dt, a_quad=D.aq,
+                                       out=dict(jac, B=B[i:i + 1], band_ends=band_ends[i]))
+                ops.tridiag_bc_solve_multi(jac["diag"], jac["off"], B[i:i + 1], kinds, kappa, None, out=Z[i:i + 1],
+                                           work=work)
+                lam1, lam2 = Z[i:i + 1], lam1
+            steps = range(hi, hi - m, -1)
+            out = ops.ts_nl_sensitivity(x, U, Z, hi - m + 1, [coefficients(n) for n in steps], inv_dt, self.nquad,
+                                        nl.kind, nterm, q_tabs=qq, phi=D.phi, Brows=B, band_ends=band_ends[:m],
+                                        end_kinds=kinds, accumulate=hi < nsteps, out=out)
+        b0, b1 = coefficients(1)[1], coefficients(2)[2]
+        ops.ts_rhs(md, mo, lam1, None if b1 == 0.0 else lam2, zero, one, b0, b1, inv_dt, out=b)       # B_0
+        host = _read_back(b0=b, u=U[jidx], **out)
+        value, _ = functional(host["u"])
+        d_u0, d_g = host["b0"][0].copy(), host["g"].copy()
+        _dirichlet_u0(kinds, d_u0, d_g)
+        return TransientSensitivity(value, {k: host[k].copy() for k in ops.TS_SENS_TABLES}, d_u0, d_g,
+                                    host["kappa"].copy(), p.times.copy(), p.nodes, host["q"].copy(), newton)
 
     # ---- adaptive time stepping (no reference counterpart; DESIGN.md section 30) ----------------------------------
     def _check_adaptive(self, u0, t_end, rtol, atol, dt0, t_out, dt_min, dt_max, max_steps, weight, forcing, end_data,

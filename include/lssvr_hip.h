@@ -1558,6 +1558,79 @@ int lssvr_semilinear_sensitivity_host(const double* x_host, int64_t ne, int nqua
                                       double* gq_host, const double* P_host, const double* band_ends_host,
                                       int kind_left, int kind_right, double* out_ends_host);
 
+/*
+ * Adjoint sensitivities of the semilinear BDF loop of rho u_t - (a u')' + c u + g(x, u) = f(x, t) (no reference
+ * counterpart).  ADDITIVE to ABI 7: four new symbols, no existing entry, struct or constant
+ * changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * The function differentiated is the CONVERGED implicit step: level n is the solution of
+ *   F_n(u^n) = K u^n + M(c + alpha_n rho/dt) u^n + G(u^n) - (1/dt) M_rho (beta0_n u^{n-1} + beta1_n u^{n-2}) - L(f(t_n)) = 0
+ * on the free rows (G as for lssvr_semilinear_sensitivity), which the Newton iteration of lssvr_ts_nl_assemble converges
+ * to; a state whose last increment is |dv| differs from it by O(|dv|^2), and so does the gradient.  The Jacobian of
+ * level n is J_n = K + M(c + alpha_n rho/dt + g_u(., u^n_h)), linearised AT u^n (not the last Newton matrix, which is
+ * linearised one iterate earlier), symmetric.  With lambda^{N+1} = lambda^{N+2} = 0, for n = N .. 1:
+ *   B_n = p_n + (1/dt) M_rho (beta0_{n+1} lambda^{n+1} + beta1_{n+2} lambda^{n+2})
+ *   J_n lambda^n = B_n, the forward loop's end kinds and kappa, zero end data        -- lssvr_tridiag_bc_solve_multi
+ *
+ * lssvr_semilinear_adjoint_step -- ONE launch per level, one thread per node.  x, u = u^n, a_quad (NULL: a = 1),
+ * cs_quad = c + alpha_n rho/dt, q_quad, ne, nquad, kind, nterm as for lssvr_ts_nl_assemble; mdiag, moff, U0 =
+ * lambda^{n+1}, U1 = lambda^{n+2} (not read when beta1 == 0), loads [R][ne+1], phi [R], R, beta0, beta1, inv_dt as
+ * for lssvr_ts_rhs with nc = 1 (for B_n: loads = the row p_n, phi = {1}, R = 1).  Writes diag [ne+1] and off [ne], the
+ * bands of J_n -- bit for bit those of lssvr_ts_nl_assemble at u (its right-hand side is not formed) --, B [ne+1] -- bit
+ * for bit lssvr_ts_rhs -- and band_ends [2] = {off[0], off[ne-1]}, the row of this level in the band_ends of the entry
+ * below.  All DEVICE arrays.  No atomics, no synchronisation, no copy.  Return codes, each before any HIP call: those of
+ * the two entries it fuses -- LSSVR_ERR_SIZE for ne < 1, R outside [1, 8], a non-finite beta0, beta1 or inv_dt, nterm
+ * outside [1, 6] (LSSVR_NL_POLY) or other than 2 (LSSVR_NL_EXP), an output that is an input or another output;
+ * LSSVR_ERR_QUAD for nquad outside [1, 5]; LSSVR_ERR_RHS for an unknown kind; LSSVR_ERR_NULL for a missing array (a_quad
+ * may be NULL, U1 with beta1 == 0).
+ *
+ * lssvr_semilinear_transient_sensitivity -- lssvr_transient_sensitivity for this loop, ONE launch per chunk: x .. R, ga,
+ * gc, grho, gf, accumulate, Brows, the end kinds, out_g and out_kappa are its arguments and receive its values bit for
+ * bit, with one difference: every level has its own matrix, so band_ends is [m][2], row i = {off[0], off[ne-1]} of the
+ * J_n of step row i, and there is no band_mask.  kind / nterm as for lssvr_nl_linearize.  gq [nterm][ne*nquad] receives
+ * dJ/dq_k summed over the chunk under the same accumulate flag; NULL: skipped, arithmetic and stores.  With s = (h_e w_q)
+ * lambda^n_eq and u_eq = u^n[e] (1 - xi_q) + u^n[e+1] xi_q, formed as for dJ/dc_quad, level by level, n descending, one
+ * rounding per operation:
+ *   LSSVR_NL_POLY  p_0 = 1;  p_k = p_{k-1} u_eq;  gq_0 = gq_0 - s;  gq_k = gq_k - (s p_k),  k = 1 .. nterm-1
+ *                  (so gq_1 is gc and, with phi = 1, gq_0 is -gf, bit for bit)
+ *   LSSVR_NL_EXP   E = exp(q_1 u_eq);  gq_0 = gq_0 - (s E);  gq_1 = gq_1 - (s ((q_0 u_eq) E))
+ * q_tabs [nterm][ne*nquad] is read for LSSVR_NL_EXP with gq only: it may be NULL otherwise.  Return codes, each before
+ * any HIP call: those of lssvr_transient_sensitivity for its arguments (gq counts as an output); LSSVR_ERR_NULL for
+ * LSSVR_NL_EXP with gq and without q_tabs; LSSVR_ERR_RHS for an unknown kind; LSSVR_ERR_SIZE for nterm outside [1, 6]
+ * (LSSVR_NL_POLY) or other than 2 (LSSVR_NL_EXP).
+ *
+ * The _host entries run the same routines on HOST arrays: no device is touched.  Bit for bit the device's values for
+ * LSSVR_NL_POLY; for LSSVR_NL_EXP up to the two exp implementations (libm here, the device library's there).
+ */
+int lssvr_semilinear_adjoint_step(const double* x, const double* u, const double* a_quad, const double* cs_quad,
+                                  const double* q_quad, int64_t ne, int nquad, int kind, int nterm,
+                                  const double* mdiag, const double* moff, const double* U0, const double* U1,
+                                  const double* loads, const double* phi, int R, double beta0, double beta1,
+                                  double inv_dt, double* diag, double* off, double* B, double* band_ends,
+                                  void* stream);
+int lssvr_semilinear_adjoint_step_host(const double* x_host, const double* u_host, const double* a_quad_host,
+                                       const double* cs_quad_host, const double* q_quad_host, int64_t ne, int nquad,
+                                       int kind, int nterm, const double* mdiag_host, const double* moff_host,
+                                       const double* U0_host, const double* U1_host, const double* loads_host,
+                                       const double* phi_host, int R, double beta0, double beta1, double inv_dt,
+                                       double* diag_host, double* off_host, double* B_host,
+                                       double* band_ends_host);
+int lssvr_semilinear_transient_sensitivity(const double* x, int64_t ne, int nquad, const double* Utraj,
+                                           const double* Z, int64_t n0, int m, double inv_dt, const double* coef_host,
+                                           const double* phi, int R, const double* q_tabs, int kind, int nterm,
+                                           double* ga, double* gc, double* grho, double* gf, double* gq,
+                                           int accumulate, const double* Brows, const double* band_ends,
+                                           int kind_left, int kind_right, double* out_g, double* out_kappa,
+                                           void* stream);
+int lssvr_semilinear_transient_sensitivity_host(const double* x_host, int64_t ne, int nquad, const double* Utraj_host,
+                                                const double* Z_host, int64_t n0, int m, double inv_dt,
+                                                const double* coef_host, const double* phi_host, int R,
+                                                const double* q_tabs_host, int kind, int nterm, double* ga_host,
+                                                double* gc_host, double* grho_host, double* gf_host, double* gq_host,
+                                                int accumulate, const double* Brows_host,
+                                                const double* band_ends_host, int kind_left, int kind_right,
+                                                double* out_g_host, double* out_kappa_host);
+
 #ifdef __cplusplus
 }
 #endif
