@@ -252,6 +252,11 @@ SIGNATURES = {
                                           [_c_dbl] * 3, [_c_dp] * 4, _STREAM),
     "lssvr_semilinear_adjoint_step_host": _sig([_c_hd] * 5, [_c_i64, _c_int, _c_int, _c_int], [_c_hd] * 6, [_c_int],
                                                [_c_dbl] * 3, [_c_hd] * 4),
+    # bubble-condensed assembly (additive to ABI 7): x, ne, order, nquad, R, rhs_quad, a_quad, c_quad, b_quad, diag,
+    # sub, sup, load, kloc4, floc, work, work_bytes
+    "lssvr_p1_bubble_work_bytes": _sig([_c_i64, _c_int], res=_c_i64),
+    "lssvr_p1_assemble_bubble": _sig([_c_dp, _c_i64, _c_int, _c_int, _c_int], [_c_dp] * 10, _WS, _STREAM),
+    "lssvr_p1_assemble_bubble_host": _sig([_c_hd, _c_i64, _c_int, _c_int, _c_int], [_c_hd] * 10, _WS),
     "lssvr_fp64_probe":_sig([_c_dp, _c_int, _c_int, _c_int], _STREAM),
     "lssvr_stream_probe": _sig([_c_dp, _c_dp, _c_i64], _STREAM),
     "lssvr_row_chunk_probe": _sig([_c_dp, _c_dp, _c_i64, _c_int, _c_int], _STREAM),

@@ -930,6 +930,57 @@ int lssvr_p1_assemble_conv(const double* x, int64_t ne, int nquad, int rhs_id,
   return check_launch(lssvr::p1_assemble_conv(a, reinterpret_cast<hipStream_t>(stream)), "p1_assemble_conv");
 }
 
+// Bubble-condensed assembly (p1_bubble.hip).  The device and the host entry share one validated binding.
+static int bind_p1_bubble(lssvr::P1BubbleArgs& a, const double* x, int64_t ne, int order, int nquad, int R,
+                          const double* rhs_quad, const double* a_quad, const double* c_quad, const double* b_quad,
+                          double* diag, double* sub, double* sup, double* load, double* kloc4, double* floc,
+                          void* work, int64_t work_bytes) {
+  if (const int rc = check_ne(ne)) return rc;
+  if (order < 2 || order > 4)
+    return fail(LSSVR_ERR_DEGREE, "order = %d outside [2, 4] (order 1 is lssvr_p1_assemble_conv)", order);
+  if (nquad < order + 1 || nquad > 5)
+    return fail(LSSVR_ERR_QUAD, "nquad = %d outside [order+1, 5] = [%d, 5]", nquad, order + 1);
+  if (R < 1 || R > 8) return fail(LSSVR_ERR_SIZE, "R = %d outside [1, 8]", R);
+  if (!x || !rhs_quad || !diag || !sub || !sup || !load)
+    return fail(LSSVR_ERR_NULL, "x, rhs_quad, diag, sub, sup, load must be non-NULL");
+  if (const int rc = check_work_sized(work, work_bytes, lssvr::p1_bubble_work_bytes(ne, R),
+                                      "lssvr_p1_bubble_work_bytes", ne, R))
+    return rc;
+  if (reinterpret_cast<uintptr_t>(work) % alignof(double) != 0)
+    return fail(LSSVR_ERR_SIZE, "work must be aligned to 8 bytes");
+  a = lssvr::P1BubbleArgs{x,    ne,  order, nquad, R,     rhs_quad, a_quad, c_quad,
+                          b_quad, diag, sub,   sup,   load,  kloc4,    floc,   static_cast<double*>(work)};
+  return LSSVR_OK;
+}
+
+int64_t lssvr_p1_bubble_work_bytes(int64_t ne, int R) {
+  return ne < 1 || R < 1 || R > 8 ? 0 : lssvr::p1_bubble_work_bytes(ne, R);
+}
+
+int lssvr_p1_assemble_bubble(const double* x, int64_t ne, int order, int nquad, int R, const double* rhs_quad,
+                             const double* a_quad, const double* c_quad, const double* b_quad, double* diag,
+                             double* sub, double* sup, double* load, double* kloc4, double* floc, void* work,
+                             int64_t work_bytes, void* stream) {
+  lssvr::P1BubbleArgs a{};
+  const int rc = bind_p1_bubble(a, x, ne, order, nquad, R, rhs_quad, a_quad, c_quad, b_quad, diag, sub, sup, load,
+                                kloc4, floc, work, work_bytes);
+  if (rc != LSSVR_OK) return rc;
+  return check_launch(lssvr::p1_assemble_bubble(a, reinterpret_cast<hipStream_t>(stream)), "p1_assemble_bubble");
+}
+
+int lssvr_p1_assemble_bubble_host(const double* x_host, int64_t ne, int order, int nquad, int R,
+                                  const double* rhs_quad_host, const double* a_quad_host, const double* c_quad_host,
+                                  const double* b_quad_host, double* diag_host, double* sub_host, double* sup_host,
+                                  double* load_host, double* kloc4_host, double* floc_host, void* work,
+                                  int64_t work_bytes) {
+  lssvr::P1BubbleArgs a{};
+  const int rc = bind_p1_bubble(a, x_host, ne, order, nquad, R, rhs_quad_host, a_quad_host, c_quad_host, b_quad_host,
+                                diag_host, sub_host, sup_host, load_host, kloc4_host, floc_host, work, work_bytes);
+  if (rc != LSSVR_OK) return rc;
+  if (!lssvr::p1_assemble_bubble_host(a)) return fail(LSSVR_ERR_QUAD, "no rule for order = %d, nquad = %d", order, nquad);
+  return LSSVR_OK;
+}
+
 int lssvr_quad_points(const double* x, int64_t ne, int nquad, double* xq, void* stream) {
   if (ne < 0) return fail(LSSVR_ERR_SIZE, "ne < 0");
   if (nquad < 1 || nquad > 5) return fail(LSSVR_ERR_QUAD, "nquad = %d outside [1,5]", nquad);

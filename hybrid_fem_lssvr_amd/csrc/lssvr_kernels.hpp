@@ -179,6 +179,30 @@ struct P1ConvArgs : P1ReactArgs {
   double* sup;
 };
 hipError_t p1_assemble_conv(const P1ConvArgs& a, hipStream_t s);
+// The same equation with the hierarchic bubbles of degree 2 .. order condensed out of every element (p1_bubble.hip,
+// DESIGN.md section 37): R tabulated right-hand sides rhs_quad[R][ne][nquad] -> the bands of P1ConvArgs and
+// load[R][ne+1]; kloc4[ne][4] (the condensed element matrices S00, S01, S10, S11) and floc[R][ne][2] may be NULL.
+// work: p1_bubble_work_bytes(ne, R) bytes.  order in 2 .. 4, nquad in order+1 .. 5 (anything else: hipErrorInvalidValue
+// / false).  The host form runs the same routines on host arrays, bit for bit.
+struct P1BubbleArgs {
+  const double* x;
+  int64_t ne;
+  int order, nquad, R;
+  const double* rhs_quad;
+  const double* a_quad;
+  const double* c_quad;
+  const double* b_quad;
+  double* diag;
+  double* sub;
+  double* sup;
+  double* load;
+  double* kloc4;
+  double* floc;
+  double* work;
+};
+int64_t p1_bubble_work_bytes(int64_t ne, int R);
+hipError_t p1_assemble_bubble(const P1BubbleArgs& a, hipStream_t s);
+bool p1_assemble_bubble_host(const P1BubbleArgs& a);
 // assembly + enhancement of the same mesh in ONE launch (lane-per-element path, in-kernel rhs); memo: the plan's
 // memo of the mesh-only loop results (read and validated, never written; NULL: none)
 hipError_t step_small(const EnhanceArgs& e, const P1Args& a, hipStream_t s,

@@ -1087,6 +1087,84 @@ def p1_load_multi(x, rhs_quad, nquad=2, *, out=None, stream=None):
     return out[:nc]
 
 
+BUBBLE_ORDERS = (2, 3, 4)      # lssvr_p1_assemble_bubble: the degree of the condensed element space
+BUBBLE_MAX_CASES = 8
+
+
+def p1_assemble_bubble(x, order, nquad, rhs_quad, *, a_quad=None, c_quad=None, b_quad=None, want_local=False,
+                       out=None, work=None, stream=None):
+    """The bands of -(a u')' + b u' + c u = f with the hierarchic bubbles of degree 2 .. ``order`` (2, 3 or 4)
+    condensed out of every element (``lssvr_p1_assemble_bubble``): tridiagonal on the nodes
+    like those of :func:`p1_assemble`, with nodal values of order h^(2 order).  ``nquad`` in order+1 .. 5;
+    ``rhs_quad`` float64[ne, nquad] or [R, ne, nquad] (R in 1 .. 8; f at :func:`quad_points`), ``a_quad``, ``c_quad``,
+    ``b_quad`` float64[ne, nquad] or None (a = 1, c = 0, b = 0).  Returns dict(diag[ne+1], sub[ne], sup[ne], load) --
+    always ``sub`` and ``sup``, never ``off`` -- with ``load`` [ne+1] or [R, ne+1] to match ``rhs_quad``, plus, with
+    ``want_local``, kloc4[ne, 4] (the condensed element matrices S00, S01, S10, S11) and floc [ne, 2] or [R, ne, 2].
+    ``out``: a dict of those buffers to write into; ``work``: scratch of ``lssvr_p1_bubble_work_bytes(ne, R)``."""
+    lib = _capi.load()
+    _dev(x, "x")
+    _dev(rhs_quad, "rhs_quad")
+    ne, order, nquad = x.numel() - 1, int(order), int(nquad)
+    if x.dim() != 1 or ne < 1:
+        raise ValueError("x must be 1-D with at least two nodes")
+    if order not in BUBBLE_ORDERS:
+        raise ValueError(f"order must be one of {BUBBLE_ORDERS}, got {order} (order 1 is p1_assemble)")
+    if not order + 1 <= nquad <= 5:
+        raise ValueError(f"nquad must be in order+1 .. 5 = {order + 1} .. 5, got {nquad}")
+    single = rhs_quad.dim() == 2
+    if rhs_quad.dim() not in (2, 3) or tuple(rhs_quad.shape[-2:]) != (ne, nquad) or \
+            not (single or 1 <= rhs_quad.shape[0] <= BUBBLE_MAX_CASES):
+        raise ValueError(f"rhs_quad must be [ne, nquad] or [R, ne, nquad] = [1 .. {BUBBLE_MAX_CASES}, {ne}, {nquad}], "
+                         f"got {list(rhs_quad.shape)}")
+    R = 1 if single else int(rhs_quad.shape[0])
+    _tables(ne, nquad, **{k: t for k, t in (("a_quad", a_quad), ("c_quad", c_quad), ("b_quad", b_quad))
+                          if t is not None})
+    lead = () if single else (R,)
+    shapes = {"diag": (ne + 1,), "sub": (ne,), "sup": (ne,), "load": lead + (ne + 1,)}
+    if want_local:
+        shapes.update(kloc4=(ne, 4), floc=lead + (ne, 2))
+    out = {k: _out(None if out is None else out.get(k), k, s, x) for k, s in shapes.items()}
+    work = _sized_work(work, x, "lssvr_p1_bubble_work_bytes", ne, R)
+    _same_device(x, rhs_quad=rhs_quad, a_quad=a_quad, c_quad=c_quad, b_quad=b_quad)
+    rc = lib.lssvr_p1_assemble_bubble(_ptr(x), ne, order, nquad, R, _ptr(rhs_quad), _ptr(a_quad), _ptr(c_quad),
+                                      _ptr(b_quad), _ptr(out["diag"]), _ptr(out["sub"]), _ptr(out["sup"]),
+                                      _ptr(out["load"]), _ptr(out.get("kloc4")), _ptr(out.get("floc")), _ptr(work),
+                                      work.numel() * work.element_size(), _stream(stream))
+    _capi.check(rc, "lssvr_p1_assemble_bubble")
+    return out
+
+
+def band_dominance(diag, sub, sup, free=(False, False), kappa=(0.0, 0.0), periodic=False):
+    """The hypothesis of the unpivoted tridiagonal solves, checked on the device with ONE read-back: every band
+    entry finite and every row of the system dominant, |sub[i-1]| + |sup[i]| <= diag[i].  Rows 0 and ne belong to
+    the system only at a ``free`` (Neumann or Robin) end, where the missing neighbour is left out and ``kappa`` joins
+    the diagonal, or with ``periodic``, where the two are one row, the seam's.  Returns (finite, worst row, its margin
+    diag - |sub| - |sup|): the row with the smallest margin, dominant when the margin is >= 0 (a margin that is not
+    finite counts as -inf).  Plain tensor arithmetic on 3 ne doubles before a solve, not a hot path."""
+    for nm, t in (("diag", diag), ("sub", sub), ("sup", sup)):
+        _dev(t, nm)
+    ne = sub.numel()
+    if diag.numel() != ne + 1 or sup.numel() != ne or ne < 1:
+        raise ValueError("band lengths must be ne+1, ne, ne (diag, sub, sup)")
+    d = diag.clone()
+    d[1:] -= sub.abs()
+    d[:-1] -= sup.abs()
+    d = torch.where(torch.isfinite(d), d, torch.full_like(d, -math.inf))
+    if periodic:
+        seam = d[0] + d[ne]
+        d[0], d[ne] = seam, seam
+    else:
+        for i, f, k in ((0, free[0], kappa[0]), (ne, free[1], kappa[1])):
+            if f:
+                d[i] += float(k)
+            else:
+                d[i] = math.inf
+    finite = torch.isfinite(diag).all() & torch.isfinite(sub).all() & torch.isfinite(sup).all()
+    margin, row = torch.min(d, dim=0)
+    got = torch.stack([finite.to(torch.float64), row.to(torch.float64), margin]).cpu()
+    return bool(got[0]), int(got[1]), float(got[2])
+
+
 def p1_flux_solve(kloc, load, u0=0.0, u1=0.0, *, out=None, work=None, stream=None):
     """``enforce`` + ``solve`` (Dual.py:129-130) for the assembled P1 system through the
     element-flux prefix scan (A = D^T K D); kloc[ne], load[ne+1] from :func:`p1_assemble`."""

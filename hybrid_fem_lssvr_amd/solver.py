@@ -720,7 +720,7 @@ class FEMLSSVRPrimalSolver:
     def __init__(self, num_fem_nodes=5, lssvr_M=12, lssvr_gamma=1e6, global_domain=(-1, 1), *,
                  n_colloc=12, rhs=poisson_rhs, nquad=2, mesh=None, device="cuda:0",
                  solver=ops.SOLVER_PRIMAL, fem_solver="bands", coef=None, reaction=None, convection=None,
-                 boundary=None, element_lists=False, nonlinear=None):
+                 boundary=None, element_lists=False, nonlinear=None, fem_order=1):
         # Dual.py:101-108
         self.num_fem_nodes = num_fem_nodes
         self.lssvr_M = lssvr_M
@@ -808,6 +808,11 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("nonlinear has no element_lists / element_degrees: the linearised tables are "
                                  "written for one degree")
         self.nonlinear = nonlinear
+        # the degree of the element space of the P1 half: 2 .. 4 add the hierarchic bubbles up
+        # to that degree and condense them out, so the nodal values converge like h^(2 fem_order); 1: every path as it
+        # was
+        self.fem_order = fem_order
+        self._check_fem_order()
         self.newton = None              # NewtonReport after solve_fem() with nonlinear
         self.enhanced = None            # EnhancedSolution after solve_lssvr_subproblems
         self.adapt_history = []         # solve_adaptive: one dict(ne, estimate, marked) per round
@@ -815,6 +820,63 @@ class FEMLSSVRPrimalSolver:
         self.element_degrees = None     # one M per element (2 .. 33) instead of lssvr_M; solve_adaptive(mode="hp")
         self._x_dev = None
         self._u_dev = None
+
+    def _check_fem_order(self, what=None):
+        """``fem_order`` and what it needs of the other (public) attributes, on the host; ``what``: a method that
+        assembles for itself and has no ``fem_order > 1`` (``ValueError``)."""
+        p = self.fem_order
+        if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 1 <= p <= 4:
+            raise ValueError(f"fem_order must be an integer in 1 .. 4, got {p!r}")
+        if p == 1:
+            return
+        if what is not None:
+            raise ValueError(f"{what} has no fem_order > 1: it assembles the P1 matrices for itself; the "
+                             "bubble-condensed bands serve solve(), solve_many(), estimate() and "
+                             "solve_adaptive(mode='h')")
+        if int(self.nquad) < p + 1 or int(self.nquad) > 5:
+            raise ValueError(f"fem_order = {p} needs nquad in fem_order+1 .. 5 = {p + 1} .. 5 (the element matrices "
+                             f"hold polynomials of degree 2 fem_order), got nquad = {self.nquad}")
+        if self.fem_solver == "flux":
+            raise ValueError("fem_order > 1 needs fem_solver='bands' or 'pivot': the flux solve factors "
+                             "A = D^T K D, which the condensed element matrices do not have")
+        if self.nonlinear is not None:
+            raise ValueError("nonlinear has no fem_order > 1: the Newton loop assembles the P1 matrices for itself")
+
+    def _check_bubble_rhs(self, rhs_list):
+        """The bubble-condensed entry takes tabulated loads only."""
+        self._check_fem_order()
+        for f in rhs_list:
+            if isinstance(f, SinRHS):
+                raise ValueError("fem_order > 1 takes tabulated loads only: a SinRHS right-hand side is evaluated "
+                                 "inside the P1 assembly kernel, which the bubble-condensed assembly does not do; "
+                                 "pass a callable f(x)")
+        if len(rhs_list) > ops.BUBBLE_MAX_CASES:
+            raise ValueError(f"fem_order > 1 assembles at most {ops.BUBBLE_MAX_CASES} load cases in one call, "
+                             f"got {len(rhs_list)}")
+
+    def _check_bands(self, bands, x):
+        """The hypothesis of the unpivoted solve on the condensed ``bands`` (the header of tridiag.hip), in one
+        device reduction and one read-back before the solve: every entry finite, every row dominant (kappa joins a
+        Robin end row).  ``fem_solver="pivot"`` needs only the first."""
+        bnd, pivot = self._bnd, self.fem_solver == "pivot"
+        free = (False, False) if bnd is None else tuple(k == ops.END_ROBIN for k in bnd.kinds)
+        kappa = (0.0, 0.0) if bnd is None else bnd.kappa
+        finite, row, margin = ops.band_dominance(bands["diag"], bands["sub"], bands["sup"], free, kappa,
+                                                 self._periodic)
+        if finite and (pivot or margin >= 0.0):
+            return
+        nodes = x.cpu().numpy()
+        ne = nodes.size - 1
+        lo, hi = nodes[max(row - 1, 0)], nodes[min(row + 1, ne)]
+        if not finite:
+            msg = (f"the bubble-condensed bands of fem_order = {self.fem_order} are not finite (worst row {row}, "
+                   f"elements on [{lo:.6g}, {hi:.6g}]): a bubble pivot was zero or not finite; refine the mesh there")
+            if pivot:
+                raise RuntimeError(msg)
+            raise ValueError(msg + " or check the coefficients")
+        raise ValueError(f"row {row} of the bubble-condensed bands (elements on [{lo:.6g}, {hi:.6g}]) is not "
+                         f"diagonally dominant: diag - |sub| - |sup| = {margin:.3g} < 0, and the tridiagonal solve "
+                         "does not pivot; refine the mesh there or use fem_solver='pivot'")
 
     @property
     def _eq(self):
@@ -931,13 +993,17 @@ class FEMLSSVRPrimalSolver:
                 raise ValueError("reaction is negative at a quadrature point: the tridiagonal solve does not "
                                  "pivot and assumes an SPD matrix (c >= 0)")
             kw["c_quad"] = cq
-        if eq.b is not None:             # b u' in the bands: sub and sup instead of off
+        if eq.b is not None and self.fem_order > 1:      # (no Peclet bound: _check_bands looks at the bands themselves)
+            kw["b_quad"] = _tabulate(eq.b, xq)
+        elif eq.b is not None:           # b u' in the bands: sub and sup instead of off
             kw["b_quad"] = self._convection_quad(eq, x, xq)
         return m, x, xq, kw
 
     def _fem(self, rhs, u0, u1):
         """(mesh, x device, u device, bands) of the P1 solve for the right-hand side ``rhs`` and the end values
         ``u0``, ``u1`` (:meth:`_gd_bc`); no attribute of the solver is written."""
+        if self.fem_order != 1:
+            return self._fem_bubble(rhs, u0, u1)
         m, x, xq, kw = self._fem_setup()
         if isinstance(rhs, SinRHS):
             bands = ops.p1_assemble(x, self.nquad, rhs=(rhs.amp, rhs.omega), want_local=True, **kw)
@@ -945,6 +1011,29 @@ class FEMLSSVRPrimalSolver:
             fq = _to_dev(rhs(xq.cpu().numpy()), x.device)
             bands = ops.p1_assemble(x, self.nquad, rhs_quad=fq, want_local=True, **kw)
         return m, x, self._p1_solve(bands, "b_quad" in kw, u0, u1), bands
+
+    def _bubble_assemble(self, rhs_list):
+        """(mesh, x device, bands) of ``fem_order > 1``: ONE ``ops.p1_assemble_bubble`` for all right-hand sides
+        (``load`` [ncases, ne+1]), then the check of the bands.  The bands are the non-symmetric ones (sub, sup),
+        with or without convection."""
+        self._check_bubble_rhs(rhs_list)
+        m, x, xq, kw = self._fem_setup()
+        xq_host = xq.cpu().numpy()
+        fq = [_to_dev(f(xq_host), x.device) for f in rhs_list]
+        for j, t in enumerate(fq):
+            if t.numel() != xq.numel():
+                raise ValueError(f"right-hand side {j} must return one value per quadrature point "
+                                 f"({list(xq.shape)}), got {list(t.shape)}")
+        fq = _torch().stack([t.reshape(xq.shape) for t in fq])
+        bands = ops.p1_assemble_bubble(x, int(self.fem_order), int(self.nquad), fq, want_local=True, **kw)
+        self._check_bands(bands, x)
+        return m, x, bands
+
+    def _fem_bubble(self, rhs, u0, u1):
+        """:meth:`_fem` with ``fem_order > 1``."""
+        m, x, bands = self._bubble_assemble([rhs])
+        bands = {k: (v[0] if k in ("load", "floc") else v) for k, v in bands.items()}
+        return m, x, self._tridiag_solve(bands, bands["load"], True, (u0, u1), False), bands
 
     def _p1_solve(self, bands, conv, u0, u1):
         """u device [ne+1] of the assembled ``bands`` with the end values ``u0``, ``u1`` for the configured ends and
@@ -990,6 +1079,9 @@ class FEMLSSVRPrimalSolver:
         one multi-RHS solve.  A ``SinRHS`` keeps its load from the in-kernel-sin assembly; ``fem_solver="flux"``
         keeps the per-case path.  ``bc``: float64 host array [ncases, 2]."""
         torch = _torch()
+        if self.fem_order != 1:
+            _, x, bands = self._bubble_assemble(rhs_list)
+            return x, self._tridiag_solve(bands, bands["load"], True, bc, True)
         if self.fem_solver == "flux" and self.convection is None:
             x, us = None, []
             for f, (u0, u1) in zip(rhs_list, bc):
@@ -1118,6 +1210,7 @@ class FEMLSSVRPrimalSolver:
         numbers is the loop's synchronisation.  The stop test |u_new - u| <= tol max(1, |u_new|) comes first; otherwise
         lambda = 1, 1/2, ... (at most ``max_halvings`` halvings) until |R(u + lambda d)| <= (1 - 1e-4 lambda) |R(u)|,
         else the tried lambda with the smallest residual."""
+        self._check_fem_order("nonlinear=")
         torch = _torch()
         nl = self._check_nonlinear()
         if not (float(tol) > 0.0) or not math.isfinite(float(tol)):
@@ -1493,6 +1586,7 @@ class FEMLSSVRPrimalSolver:
         per element by the reaction rows with the table c - theta_j rho (``lssvr_M``, ``n_colloc``, ``lssvr_gamma``,
         ``element_degrees``), and its Rayleigh quotient, by ``nq``-point Gauss, is the enhanced eigenvalue.  Returns
         an :class:`EigenSolution`."""
+        self._check_fem_order("solve_eigen")
         self._check_nonlinear("solve_eigen")
         torch = _torch()
         m, nodes, kinds, kappa, unknowns = self._check_eigen(k, sigma, weight, tol, max_iter, check_every)
@@ -1872,6 +1966,7 @@ class FEMLSSVRPrimalSolver:
         ``ops.nl_linearize`` at the collocation points and one ``ops.enhance_varcoef`` each (c_eff differs per
         snapshot).  ``nonlinear=None`` runs exactly the calls above; ``newton_iters`` / ``newton_tol`` then must be
         left alone."""
+        self._check_fem_order("solve_transient")
         if self.nonlinear is not None:
             raise ValueError("solve_transient takes the semilinear term as its own keyword: build the solver without "
                              "nonlinear= and call solve_transient(..., nonlinear=...)")
@@ -2087,6 +2182,7 @@ class FEMLSSVRPrimalSolver:
         ``ops.SOLVER_PRIMAL``), a solver built with ``nonlinear=``, both or neither of ``goal`` and ``observe``, a step
         outside 1 .. nsteps or named twice, data of the wrong shape or not finite, and a trajectory of more than
         ``max_state_bytes``: checkpointing is not built."""
+        self._check_fem_order("solve_transient_sensitivity")
         self._check_nonlinear("solve_transient_sensitivity")
         nl, iters, tol = self._newton_args("solve_transient_sensitivity", nonlinear, newton_iters, newton_tol)
         p = self._check_transient(u0, t_end, nsteps, scheme, weight, forcing, end_data, None, False)
@@ -2285,6 +2381,7 @@ class FEMLSSVRPrimalSolver:
         go through ONE ``ops.enhance_multi`` after the loop.  Snapshots, bands and the monitor come back in one copy.
         Returns a :class:`TransientSolution` with ``steps``, ``n_accepted``, ``n_rejected``, ``n_restarts``,
         ``monitor``; the solver's attributes are left as they are."""
+        self._check_fem_order("solve_transient_adaptive")
         enhance = bool(enhance)
         p = self._check_adaptive(u0, t_end, rtol, atol, dt0, t_out, dt_min, dt_max, max_steps, weight, forcing,
                                  end_data, enhance)
@@ -2475,6 +2572,7 @@ class FEMLSSVRPrimalSolver:
         ``ops.ts_source_table`` the right-hand side f(., t) - rho I_h acc - d I_h v of the snapshot's elliptic
         problem; with ``enhance`` all snapshots then go through ONE ``ops.enhance_multi``.  Returns a
         :class:`WaveSolution`; the solver's attributes are left as they are."""
+        self._check_fem_order("solve_wave")
         self._check_nonlinear("solve_wave")
         torch = _torch()
         enhance = bool(enhance)
@@ -2561,6 +2659,7 @@ class FEMLSSVRPrimalSolver:
         Refused (``ValueError``, before any device call): what :meth:`solve_wave` refuses, both or neither of ``goal``
         and ``observe``, a step outside 0 .. nsteps or named twice, data of the wrong shape or not finite, and
         trajectories of more than ``max_state_bytes``: checkpointing is not built."""
+        self._check_fem_order("solve_wave_sensitivity")
         self._check_nonlinear("solve_wave_sensitivity")
         p = self._check_wave(u0, v0, t_end, nsteps, damping, weight, forcing, end_data, end_accel0, None, False, beta,
                              gamma)
@@ -2743,6 +2842,7 @@ class FEMLSSVRPrimalSolver:
         sum eta_e, ``corrected`` = their sum -- the enhanced solution is continuous and takes the Dirichlet values, so
         sum eta_e = J(u) - J(u_enh) up to the error of the dual solution and of the ``nq``-point rule on R z: the
         correction is only as good as that rule resolves f."""
+        self._check_fem_order("solve_goal")
         self._check_nonlinear("solve_goal")
         return self._solve_goal(goal, nq)[0]
 
@@ -2970,6 +3070,7 @@ class FEMLSSVRPrimalSolver:
         ``fem_solver="flux"``, ``nonlinear=``, a solver other than ``ops.SOLVER_PRIMAL``, ``element_degrees``, both or
         neither of ``goal`` and ``observe``, data that are not finite where they are tabulated.  The mesh is not
         differentiated."""
+        self._check_fem_order("solve_sensitivity")
         if of not in ("p1", "enhanced"):
             raise ValueError(f"of must be 'p1' or 'enhanced', got {of!r}")
         if of == "enhanced":
@@ -3002,6 +3103,7 @@ class FEMLSSVRPrimalSolver:
         device call): a solver without ``nonlinear=``, what :meth:`solve_sensitivity` refuses other than ``nonlinear=``,
         what ``nonlinear=`` refuses, Newton keywords :meth:`solve_fem` refuses.  ``of="enhanced"``, the semilinear
         time loop, periodic ends and the mesh are not differentiated."""
+        self._check_fem_order("solve_semilinear_sensitivity")
         what = "solve_semilinear_sensitivity"
         if self.nonlinear is None:
             raise ValueError(f"{what} needs nonlinear=: the linear solve is differentiated by solve_sensitivity")
@@ -3124,6 +3226,8 @@ class FEMLSSVRPrimalSolver:
         self._check_nonlinear("solve_adaptive")
         if mode not in ("h", "hp"):
             raise ValueError(f"mode must be 'h' or 'hp', got {mode!r}")
+        if mode != "h" or goal is not None:
+            self._check_fem_order("solve_adaptive(mode='hp') / solve_adaptive(goal=)")
         if goal is not None:
             if mode != "h":
                 raise ValueError("goal needs mode='h': the dual-weighted residual marks elements for bisection only")

@@ -1631,6 +1631,52 @@ int lssvr_semilinear_transient_sensitivity_host(const double* x_host, int64_t ne
                                                 const double* band_ends_host, int kind_left, int kind_right,
                                                 double* out_g_host, double* out_kappa_host);
 
+/*
+ * Bubble-condensed P1 assembly: nodal values of order h^(2 order) for -(a u')' + b u' + c u = f (no reference
+ * counterpart).  ADDITIVE to ABI 7: three new symbols, no existing entry, struct, constant or
+ * kernel changes, LSSVR_ABI_VERSION stays 7.
+ *
+ * Every element carries, beside the P1 functions N_0 = 1 - t and N_1 = t on t in [0,1], the hierarchic bubbles
+ *   N_k = (P_k(s) - P_{k-2}(s)) / sqrt(2 (2k - 1)),   s = 2t - 1,   k = 2 .. order      (P_k: Legendre)
+ * which vanish at both ends.  With the rule of lssvr_quad_points (points t_q, weights w_q) and N' = dN/dt,
+ *   K_ij  = sum_q w_q [ a_q N_i' N_j' / h + b_q N_i N_j' + c_q h N_i N_j ],      g_i^r = sum_q w_q h f^r_q N_i,
+ * the bubble block is eliminated element by element (Gaussian elimination without pivoting, once per element for all
+ * R cases) and what is assembled is tridiagonal on the nodes again:
+ *   S = K_vv - K_vb K_bb^-1 K_bv  (2 x 2),       g^r_v - K_vb K_bb^-1 g^r_b  (2 per case),
+ *   diag[ne+1]     diag[i] = S11[i-1] + S00[i]           (nodes 0 and ne: the term of the missing element left out)
+ *   sub[ne]        sub[i] = S10[i]: the coefficient of u_i in row i+1
+ *   sup[ne]        sup[i] = S01[i]: the coefficient of u_{i+1} in row i
+ *   load[R][ne+1]  load[r][i] = g1^r[i-1] + g0^r[i]
+ *   kloc4[ne][4]   (may be NULL) S00, S01, S10, S11 of every element
+ *   floc[R][ne][2] (may be NULL) the condensed load pair of every element and case
+ * -- the bands of lssvr_p1_assemble_conv, for lssvr_tridiag_ns_*_solve_multi and lssvr_tridiag_pivot_solve_multi.
+ * The bands are not symmetric in general, even with b = 0 (then sub and sup agree to rounding, not to the bit).
+ *
+ *   order      2 .. 4 (else LSSVR_ERR_DEGREE; order 1 is lssvr_p1_assemble_conv, not served here)
+ *   nquad      order+1 .. 5 (else LSSVR_ERR_QUAD)
+ *   R          1 .. 8 right-hand sides rhs_quad[R][ne][nquad], tabulated at lssvr_quad_points (else LSSVR_ERR_SIZE)
+ *   a_quad, c_quad, b_quad   [ne][nquad], each may be NULL: a = 1, c = 0, b = 0
+ *   work       lssvr_p1_bubble_work_bytes(ne, R) = (4 + 2R) ne 8 bytes, 8-byte aligned: the condensed element
+ *              quantities between the two passes (NULL: LSSVR_ERR_NULL; too small or misaligned: LSSVR_ERR_SIZE)
+ * ne < 1 is LSSVR_ERR_SIZE, a missing x, rhs_quad, diag, sub, sup or load LSSVR_ERR_NULL -- each before any HIP call.
+ * Two launches (a thread per element, a thread per node), no atomics, bitwise reproducible.  There is no info word:
+ * a bubble pivot that is zero or not finite leaves non-finite entries in the bands of its element, which the caller
+ * finds there.  No pivoting: for c >= 0 and a > 0 the bubble block is positive definite when b = 0; the caller
+ * checks the bands (finite, rows dominant) before an unpivoted solve.
+ *
+ * lssvr_p1_assemble_bubble_host -- the same routines on HOST arrays (work included), bit for bit: no device is touched.
+ */
+int64_t lssvr_p1_bubble_work_bytes(int64_t ne, int R);
+int lssvr_p1_assemble_bubble(const double* x, int64_t ne, int order, int nquad, int R, const double* rhs_quad,
+                             const double* a_quad, const double* c_quad, const double* b_quad, double* diag,
+                             double* sub, double* sup, double* load, double* kloc4, double* floc, void* work,
+                             int64_t work_bytes, void* stream);
+int lssvr_p1_assemble_bubble_host(const double* x_host, int64_t ne, int order, int nquad, int R,
+                                  const double* rhs_quad_host, const double* a_quad_host, const double* c_quad_host,
+                                  const double* b_quad_host, double* diag_host, double* sub_host, double* sup_host,
+                                  double* load_host, double* kloc4_host, double* floc_host, void* work,
+                                  int64_t work_bytes);
+
 #ifdef __cplusplus
 }
 #endif
